@@ -322,8 +322,11 @@ class ExternalChain:
         for _ in range(int(n)):
             self.pc.step()
 
-    def state(self):
-        return {"accept_ratio": float(self.pc.adaptivemc.accept_ratio)}
+    def state(self):      # the fields of fit.Chain.state()
+        pc, am = self.pc, self.pc.adaptivemc
+        return dict(theta=pc.param.copy(), Bcoeff=np.array(self.mt.Bcoeff), tausq_inv=np.array(self.mt.tausq_inv),
+                    loglik=float(pc.current_loglik), accept_ratio=float(am.accept_ratio), iteration=pc.m,
+                    paramsd=np.array(am.paramsd))
 
     def profile_levels_all(self):
         C = self._C
@@ -338,6 +341,36 @@ class ExternalChain:
 
     def __getattr__(self, name):      # algorithmic_bytes, profile, profile_get, profile_levels, synchronize, shard_info, close
         return getattr(self.mt, name)
+
+
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: all files together stay below this
+NPY_HEADER = 1024               # allowance per .npy file for its header (np.save writes 128 bytes for these arrays)
+
+
+def timed_outputs(chain):
+    """What a caller of the timed path holds after its last step: the chain's state (theta, Bcoeff, tausq_inv, loglik,
+    accept_ratio, iteration, paramsd) and the latent field w (model row order), all float64."""
+    out = {k: np.atleast_1d(np.asarray(v, dtype=np.float64)) for k, v in chain.state().items()}
+    out["w"] = np.asarray(chain.get_w(), dtype=np.float64)
+    return out
+
+
+def dump_outputs(out, dirname, budget=DUMP_BYTES):
+    """Writes every array of `out` as DIR/<name>.npy.  Smallest first; an array that no longer fits in `budget` is replaced by
+    a fixed sample of its entries (flattened; the same entries on every run: seeded) and the sample's flat indices go to
+    DIR/<name>_index.npy (float64), so that two runs can still be compared entry for entry."""
+    os.makedirs(dirname, exist_ok=True)
+    room = budget
+    for name in sorted(out, key=lambda k: out[k].nbytes):
+        a = np.asarray(out[name], dtype=np.float64)
+        if a.nbytes + NPY_HEADER > room:
+            m = min(a.size, max(0, (room - 2 * NPY_HEADER) // 16))      # 8 bytes for the value, 8 for its index
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=m, replace=False))
+            np.save(os.path.join(dirname, f"{name}_index.npy"), idx.astype(np.float64))
+            room -= idx.size * 8 + NPY_HEADER
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+        room -= a.nbytes + NPY_HEADER
 
 
 def main():
@@ -356,7 +389,12 @@ def main():
     ap.add_argument("--cpu-side", type=int, default=316, help="grid side of the bounded CPU-baseline sample")
     ap.add_argument("--external", action="store_true", help="force the torch.distributed + Python-driver fallback path")
     ap.add_argument("--launch-check", action="store_true", help="CPU rehearsal of the rank launcher (gloo, no GPU work)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (chain state and w) as DIR/<name>.npy, float64, "
+                         f"at most {DUMP_BYTES // 10 ** 6} MB in all (larger arrays: a fixed sample + <name>_index.npy)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "RANK" not in os.environ:
         if args.gpus > 1:
@@ -455,6 +493,9 @@ def main():
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    # the passes below step the chain further (untimed): the outputs of the last TIMED step are taken here
+    if args.dump_outputs and rank == 0:
+        dump_outputs(timed_outputs(chain), args.dump_outputs)
 
     prof = model.profile_get()
     lvl_ms, lvl_bytes = model.profile_levels()

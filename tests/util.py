@@ -105,3 +105,14 @@ def strip_coords(nx, ny, q, width=0.02):
     ys = np.linspace(0.0, width, ny)
     g = np.stack(np.meshgrid(xs, ys, indexing="ij"), axis=-1).reshape(-1, 2)
     return np.tile(g, (q, 1)), np.repeat(np.arange(1, q + 1), nx * ny)
+
+
+def visible_gpus():
+    """GPUs torch sees, asked in a child process.  torch bundles its own HIP / HSA runtimes: once the library has loaded the
+    system ones, importing torch loads a second set next to them, and after torch's set has initialised the library's finds
+    no device.  So a test process that uses the library never initialises torch's runtime itself."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count())"], capture_output=True,
+                       text=True, timeout=300, check=True)
+    return int(r.stdout.split()[-1])
