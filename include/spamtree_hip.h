@@ -184,6 +184,16 @@ int st_profile_levels(st_handle h, int32_t *n_levels, double *ms_by_level, doubl
 #define ST_KERNEL_LCHAIN 6
 #define ST_KERNEL_LCHAIN_REF 7   /* reference level: k_factor_lchain for the chain pass + k_factor_ref_finish per block */
 int st_level_info(st_handle h, int32_t *n_levels, int32_t *kernel, int32_t *max_m, int32_t *max_P, int32_t *n_blocks, int32_t cap);
+/* what the launch sites actually ran the last time each phase ran, as route codes written at the launch (not a recomputed
+ * dispatch): per level g < *n_levels (at most cap levels written) phase_a[ST_ROUTE_A_SLOTS g + i] = phase A's kernels in
+ * launch order (the limited tree's chain pre-pass is on level 0), phase_b[2 g] = the Gram kernel of the level's last sweep,
+ * phase_b[2 g + 1] = its sweep kernel; *phase_p = the kernel of the last st_predict.  ST_ROUTE_NONE: nothing launched.
+ * Any output pointer but n_levels may be NULL.  st_route_name spells a code as the template instantiation in the source
+ * ("k_factor_quad<4, 44, 11, true, true>"); NULL for a code out of range.  Needs no device. */
+#define ST_ROUTE_NONE 0
+#define ST_ROUTE_A_SLOTS 3
+int st_route_info(st_handle h, int32_t *n_levels, int32_t *phase_a, int32_t *phase_b, int32_t *phase_p, int32_t cap);
+const char *st_route_name(int32_t code);
 int st_synchronize(st_handle h);
 void *st_stream(st_handle h);                              /* the hipStream_t every kernel is launched on */
 

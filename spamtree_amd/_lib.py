@@ -59,6 +59,9 @@ SIGNATURES = {
     "st_profile_levels": (C.c_int, [H, C.POINTER(C.c_int32), c_dp, c_dp, C.c_int32]),
     "st_level_info": (C.c_int, [H, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                 C.POINTER(C.c_int32), C.c_int32]),
+    "st_route_info": (C.c_int, [H, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                C.c_int32]),
+    "st_route_name": (C.c_char_p, [C.c_int32]),
     "st_synchronize": (C.c_int, [H]),
     "st_stream": (C.c_void_p, [H]),
     "st_set_stream": (C.c_int, [H, C.c_void_p]),

@@ -84,6 +84,34 @@ struct LevelInfo {
   int own_lo = 0, own_n = 0, gown_lo = 0, gown_n = 0;   // this rank's run of the level's block list / group list
 };
 
+// route codes (st_route_info): written by the launch sites themselves; st_route_name spells them as the source does
+enum RouteCode : int {
+  R_NONE = ST_ROUTE_NONE,
+  R_MARGINAL_INVCHOL_WAVE, R_MARGINAL_INVCHOL,
+  R_FACTOR_LDS, R_FACTOR_SCRATCH, R_PREDICT_LDS, R_PREDICT_SCRATCH,
+  R_QUAD32_REF_WCH, R_QUAD32_REF, R_QUAD32_LEAF, R_QUAD38_REF_WCH, R_QUAD38_REF, R_QUAD38_LEAF,
+  R_QUAD44_REF_WCH, R_QUAD44_REF, R_QUAD44_LEAF, R_QUAD50_REF_WCH, R_QUAD50_REF, R_QUAD50_LEAF,
+  R_FACTOR_MFMA, R_LCHAIN96, R_LCHAIN136, R_REF_FINISH, R_LCHAIN_SCALARS, R_FACTOR_WIDE, R_BIGMFMA3, R_BIGMFMA4, R_BIGMFMA5,
+  R_GRAM, R_GRAM_DIRECT, R_GRAM_BIG,
+  R_SAMPLE_MFMA, R_LEAF_SEG4, R_LEAF_SEG6, R_SAMPLE_LEAF, R_SAMPLE_WAVE, R_SAMPLE_LEAN_LAT, R_SAMPLE_LEAN,
+  R_SAMPLE_BIG_REF, R_SAMPLE_LEAF_WIDE, R_SAMPLE_BIG_LEAF, R_SAMPLE_SMALL,
+  R_COUNT
+};
+static const char *const k_route_names[R_COUNT] = {
+  "",
+  "k_marginal_invchol_wave", "k_marginal_invchol",
+  "k_factor<false, MODE_FACTOR>", "k_factor<true, MODE_FACTOR>", "k_factor<false, MODE_PREDICT>", "k_factor<true, MODE_PREDICT>",
+  "k_factor_quad<4, 32, 8, true, true>", "k_factor_quad<4, 32, 8, true, false>", "k_factor_quad<4, 32, 8, false, true>",
+  "k_factor_quad<4, 38, 10, true, true>", "k_factor_quad<4, 38, 10, true, false>", "k_factor_quad<4, 38, 10, false, true>",
+  "k_factor_quad<4, 44, 11, true, true>", "k_factor_quad<4, 44, 11, true, false>", "k_factor_quad<4, 44, 11, false, true>",
+  "k_factor_quad<4, 50, 13, true, true>", "k_factor_quad<4, 50, 13, true, false>", "k_factor_quad<4, 50, 13, false, true>",
+  "k_factor_mfma", "k_factor_lchain<96>", "k_factor_lchain<136>", "k_factor_ref_finish", "k_lchain_scalars", "k_factor_wide<WG_JT>",
+  "k_factor_bigmfma<3, 5, 34>", "k_factor_bigmfma<4, 5, 34>", "k_factor_bigmfma<5, 3, 24>",
+  "k_gram", "k_gram_direct", "k_gram_big",
+  "k_sample_mfma", "k_sample_leaf_seg<4>", "k_sample_leaf_seg<6>", "k_sample_leaf", "k_sample_wave", "k_sample_lean<true>",
+  "k_sample_lean<false>", "k_sample<true, false>", "k_sample_leaf_wide", "k_sample<true, true>", "k_sample<false>",
+};
+
 struct st_handle_s {
   std::string err;
   int device = 0;
@@ -183,6 +211,8 @@ struct st_handle_s {
   int twin_maxM = 1;
   ncclComm_t comm = nullptr;                  // native RCCL communicator (st_comm_init); null = exchanges are the caller's
   std::vector<LevelInfo> levels;
+  std::vector<int> route_a, route_b;          // per level: ST_ROUTE_A_SLOTS phase-A / 2 phase-B route codes of the last launch
+  int route_p = R_NONE;                       // ... and of the last st_predict
   LevelInfo pred_info;
   int pred_grp_first = 0, pred_grp_count = 0, pred_quad_first = 0, pred_quad_count = 0, pred_nkx = 0;   // phase P on k_factor_quad's leaf path (pred_nkx = 0: generic kernel)
   size_t pred_lds = 0;
@@ -570,6 +600,8 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
     { const char *e = getenv("SPAMTREE_GRAM_BIG"); h->gram_big = (e && e[0] == '0') ? 0 : 1; }
   }
   h->levels.resize(n_actual);
+  h->route_a.assign((size_t)n_actual * ST_ROUTE_A_SLOTS, R_NONE);
+  h->route_b.assign((size_t)n_actual * 2, R_NONE);
   auto geometry = [&](LevelInfo &L, const std::vector<int> &list, bool is_pred) {
     for (int b : list) {
       const Blk &B = h->blks[b];
@@ -1101,7 +1133,15 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
             if (cg < Ll.grp_first || cg >= Ll.grp_first + Ll.grp_count || h->grps[cg].M > 32) ok = false;
           }
         }
-        // ... and every leaf group's record is read by a block of that level only (its direct parent)
+        // ... and every leaf group's record is read by a block of that level only (its direct parent): a leaf block hanging
+        // from a shallower reference level would leave that parent's Gram part unwritten on rebuild sweeps
+        for (int k = 0; k < Ll.grp_count && ok; ++k) {
+          const Grp &G = h->grps[Ll.grp_first + k];
+          for (int b = 0; b < G.nblk && ok; ++b) {
+            const Blk &Bl = h->blks[G.blk0 + b];
+            if (Bl.nanc == 0 || h->blks[h->anc_idx[Bl.anc_ptr + Bl.nanc - 1]].level != gp) ok = false;
+          }
+        }
         if (ok) h->gram_direct_level = gp;
       }
     }
@@ -1482,15 +1522,24 @@ static int factor_launch(st_handle h, int phys, const CovPar &cp, int g_lo = 0, 
   int n_launch = 0;
   for (int g = g_lo; g < g_hi; ++g) n_launch += ((h->levels[g].fast ? h->levels[g].gown_n : h->levels[g].own_n) != 0);
   ProfScope phase(h, 0, -2, n_launch, st);   // profile mode 2: the phase's launches between ONE pair of events (mean launch = total / launches)
+  for (int g = g_lo; g < g_hi; ++g) std::fill_n(h->route_a.begin() + (size_t)g * ST_ROUTE_A_SLOTS, ST_ROUTE_A_SLOTS, (int)R_NONE);
+  auto route = [&](int g, int code) {   // the next free phase-A slot of level g
+    int *r = h->route_a.data() + (size_t)g * ST_ROUTE_A_SLOTS;
+    for (int i = 0; i < ST_ROUTE_A_SLOTS; ++i) if (r[i] == R_NONE) { r[i] = code; return; }
+  };
   if (g_lo == 0 && h->limited && !h->twin_list.empty()) {
     MarginalArgs M;
     M.blks = h->d_blks.p; M.list = h->d_twin.p; M.nlist = (int)h->twin_list.size(); M.cx = h->d_cx.p; M.cy = h->d_cy.p; M.mv = h->d_mv.p;
     M.panels = h->d_panels[phys].p; M.errflag = errflag; M.maxM = h->twin_maxM;
     const size_t lds = (size_t)2 * h->twin_maxM * h->twin_maxM * sizeof(double);
-    if (h->twin_maxM <= 27 && !h->force_generic)   // one block per wave, blocked DPP / MFMA elimination
+    if (h->twin_maxM <= 27 && !h->force_generic) {   // one block per wave, blocked DPP / MFMA elimination
+      route(0, R_MARGINAL_INVCHOL_WAVE);
       hipLaunchKernelGGL(k_marginal_invchol_wave, dim3(std::min((M.nlist + NT / 64 - 1) / (NT / 64), 8 * h->sm_count)), dim3(NT),
                          (size_t)(NT / 64) * 64 * CH_LD * sizeof(double), st, M, cp);
-    else hipLaunchKernelGGL(k_marginal_invchol, dim3(std::min(M.nlist, 8 * h->sm_count)), dim3(NT), lds, st, M, cp);
+    } else {
+      route(0, R_MARGINAL_INVCHOL);
+      hipLaunchKernelGGL(k_marginal_invchol, dim3(std::min(M.nlist, 8 * h->sm_count)), dim3(NT), lds, st, M, cp);
+    }
   }
   for (int g = g_lo; g < g_hi; ++g) {
     const LevelInfo &L = h->levels[g];
@@ -1512,13 +1561,14 @@ static int factor_launch(st_handle h, int phys, const CovPar &cp, int g_lo = 0, 
         F.logdet_c = h->d_logdet[phys].p; F.loglik_c = h->d_loglik[phys].p; F.errflag = errflag; F.ldS = L.q_ldS;
         F.gdesc = h->d_gdesc.p + (size_t)L.grp_first * h->gd_stride; F.gd_stride = h->gd_stride;
         F.wave_chol = L.maxM <= 27 ? 1 : 0;
-#define QLAUNCH(NU_, NKX_, NKT_)                                                                                               \
+#define QLAUNCH(NU_, NKX_, NKT_, R_)   /* R_: route code of <.., true, true>; + 1: <.., true, false>; + 2: <.., false, true> */  \
   do {                                                                                                                         \
-    if (L.isref && F.wave_chol) hipLaunchKernelGGL((k_factor_quad<NU_, NKX_, NKT_, true, true>), dim3(L.qown_n), dim3(128 * NU_), L.lds_quad, st, F, cp); \
-    else if (L.isref) hipLaunchKernelGGL((k_factor_quad<NU_, NKX_, NKT_, true, false>), dim3(L.qown_n), dim3(128 * NU_), L.lds_quad, st, F, cp); \
-    else hipLaunchKernelGGL((k_factor_quad<NU_, NKX_, NKT_, false, true>), dim3(L.qown_n), dim3(128 * NU_), L.lds_quad, st, F, cp);         \
+    if (L.isref && F.wave_chol) { route(g, R_); hipLaunchKernelGGL((k_factor_quad<NU_, NKX_, NKT_, true, true>), dim3(L.qown_n), dim3(128 * NU_), L.lds_quad, st, F, cp); } \
+    else if (L.isref) { route(g, R_ + 1); hipLaunchKernelGGL((k_factor_quad<NU_, NKX_, NKT_, true, false>), dim3(L.qown_n), dim3(128 * NU_), L.lds_quad, st, F, cp); } \
+    else { route(g, R_ + 2); hipLaunchKernelGGL((k_factor_quad<NU_, NKX_, NKT_, false, true>), dim3(L.qown_n), dim3(128 * NU_), L.lds_quad, st, F, cp); } \
   } while (0)
-        if (L.q_nkx == 32) QLAUNCH(4, 32, 8); else if (L.q_nkx == 38) QLAUNCH(4, 38, 10); else if (L.q_nkx == 44) QLAUNCH(4, 44, 11); else QLAUNCH(4, 50, 13);
+        if (L.q_nkx == 32) QLAUNCH(4, 32, 8, R_QUAD32_REF_WCH); else if (L.q_nkx == 38) QLAUNCH(4, 38, 10, R_QUAD38_REF_WCH);
+        else if (L.q_nkx == 44) QLAUNCH(4, 44, 11, R_QUAD44_REF_WCH); else QLAUNCH(4, 50, 13, R_QUAD50_REF_WCH);
 #undef QLAUNCH
       } else if (L.fast) {
         FastArgs F;
@@ -1528,6 +1578,7 @@ static int factor_launch(st_handle h, int phys, const CovPar &cp, int g_lo = 0, 
         F.logdet_c = h->d_logdet[phys].p; F.loglik_c = h->d_loglik[phys].p; F.errflag = errflag;
         F.Pm4 = L.Pm4; F.ldKV = L.ldKV; F.ldS = L.ldS; F.SRm = L.SRm; F.stage_dbl = L.stage_dbl;
         F.gdesc = h->d_gdesc.p + (size_t)(L.grp_first + L.gown_lo) * h->gd_stride; F.gd_stride = h->gd_stride;
+        route(g, R_FACTOR_MFMA);
         hipLaunchKernelGGL(k_factor_mfma, dim3(L.gown_n), dim3(NT), L.lds_fast, st, F, cp);
       } else if (L.bigmfma && h->factor_gen == 3 && L.lchain) {
         LcArgs C;
@@ -1537,14 +1588,17 @@ static int factor_launch(st_handle h, int phys, const CovPar &cp, int g_lo = 0, 
         C.rowtmp = h->d_lcrow.p; C.n_rows = h->n_all; C.errflag = errflag;
         C.errcode = L.lchain_ref ? 2 : 3;
         C.vscr = L.lchain_ref ? h->d_vscr.p : nullptr;
-        if (L.lchain == 96) hipLaunchKernelGGL((k_factor_lchain<96>), dim3(L.lc_count), dim3(LC_NT), lc_dyn_doubles(96) * 8, st, C, cp);
-        else hipLaunchKernelGGL((k_factor_lchain<136>), dim3(L.lc_count), dim3(LC_NT), lc_dyn_doubles(136) * 8, st, C, cp);
+        if (L.lchain == 96) { route(g, R_LCHAIN96); hipLaunchKernelGGL((k_factor_lchain<96>), dim3(L.lc_count), dim3(LC_NT), lc_dyn_doubles(96) * 8, st, C, cp); }
+        else { route(g, R_LCHAIN136); hipLaunchKernelGGL((k_factor_lchain<136>), dim3(L.lc_count), dim3(LC_NT), lc_dyn_doubles(136) * 8, st, C, cp); }
         if (L.lchain_ref) {   // the panels hold [ -r_j T_j | r_j ] per column: finish the blocks (Schur complement, factorisation, -Ri T in place)
           A.vscr = h->d_vscr.p; A.voff = h->d_rfvoff.p + L.rf_first; A.hvrow = h->d_lcrow.p;
+          route(g, R_REF_FINISH);
           hipLaunchKernelGGL(k_factor_ref_finish, dim3(std::min(A.nlist, 2 * h->sm_count)), dim3(BM_NT), L.lds_ref_finish, st, A, cp);
-        } else
-        hipLaunchKernelGGL(k_lchain_scalars, dim3((A.nlist + 255) / 256), dim3(256), 0, st, h->d_blks.p, A.list, A.nlist, h->d_lcrow.p, h->n_all,
-                           h->d_logdet[phys].p, h->d_loglik[phys].p);
+        } else {
+          route(g, R_LCHAIN_SCALARS);
+          hipLaunchKernelGGL(k_lchain_scalars, dim3((A.nlist + 255) / 256), dim3(256), 0, st, h->d_blks.p, A.list, A.nlist, h->d_lcrow.p, h->n_all,
+                             h->d_logdet[phys].p, h->d_loglik[phys].p);
+        }
       } else if (L.bigmfma && h->factor_gen == 3 && L.wide_count > 0) {
         WideArgs W;
         std::memset(&W, 0, sizeof(W));
@@ -1552,14 +1606,15 @@ static int factor_launch(st_handle h, int phys, const CovPar &cp, int g_lo = 0, 
         W.ngroups = L.wide_count; W.cx = h->d_cx.p; W.cy = h->d_cy.p; W.mv = h->d_mv.p; W.w_in = h->d_w.p; W.panels = h->d_panels[phys].p;
         W.logdet_c = h->d_logdet[phys].p; W.loglik_c = h->d_loglik[phys].p; W.errflag = errflag; W.scratch = h->d_scratch.p;
         W.scratch_stride = h->scratch_stride; W.maxP = L.maxP; W.maxN = L.wide_maxN; W.maxM = L.maxM; W.maxMa = L.maxMa; W.ldS = L.bm_ldS;
+        route(g, R_FACTOR_WIDE);
         hipLaunchKernelGGL((k_factor_wide<WG_JT>), dim3(std::min(L.wide_count, h->sm_count)), dim3(WG_NT), L.lds_wide, st, W, cp);
       } else if (L.bigmfma && h->factor_gen == 3) {
         A.scratch = h->d_scratch.p; A.scratch_stride = h->scratch_stride; A.SR = L.bm_ldS;
-        if (L.maxM <= 48) hipLaunchKernelGGL((k_factor_bigmfma<3, 5, 34>), dim3(std::min(A.nlist, h->sm_count)), dim3(BM_NT), L.lds_bigmfma, st, A, cp);
-        else if (L.maxM <= 64) hipLaunchKernelGGL((k_factor_bigmfma<4, 5, 34>), dim3(std::min(A.nlist, h->sm_count)), dim3(BM_NT), L.lds_bigmfma, st, A, cp);
-        else hipLaunchKernelGGL((k_factor_bigmfma<5, 3, 24>), dim3(std::min(A.nlist, h->sm_count)), dim3(BM_NT), L.lds_bigmfma, st, A, cp);
-      } else if (L.big_factor) launch_factor<true, MODE_FACTOR>(h, L, A, cp, st);
-      else launch_factor<false, MODE_FACTOR>(h, L, A, cp, st);
+        if (L.maxM <= 48) { route(g, R_BIGMFMA3); hipLaunchKernelGGL((k_factor_bigmfma<3, 5, 34>), dim3(std::min(A.nlist, h->sm_count)), dim3(BM_NT), L.lds_bigmfma, st, A, cp); }
+        else if (L.maxM <= 64) { route(g, R_BIGMFMA4); hipLaunchKernelGGL((k_factor_bigmfma<4, 5, 34>), dim3(std::min(A.nlist, h->sm_count)), dim3(BM_NT), L.lds_bigmfma, st, A, cp); }
+        else { route(g, R_BIGMFMA5); hipLaunchKernelGGL((k_factor_bigmfma<5, 3, 24>), dim3(std::min(A.nlist, h->sm_count)), dim3(BM_NT), L.lds_bigmfma, st, A, cp); }
+      } else if (L.big_factor) { route(g, R_FACTOR_SCRATCH); launch_factor<true, MODE_FACTOR>(h, L, A, cp, st); }
+      else { route(g, R_FACTOR_LDS); launch_factor<false, MODE_FACTOR>(h, L, A, cp, st); }
     }
     HCHK(h, hipGetLastError());
   }
@@ -1918,6 +1973,8 @@ static int sample_launch(st_handle h, int g_hi, int g_lo) {   // levels g_hi-1 .
   const int phys = h->slot_map[0];
   for (int g = g_hi - 1; g >= g_lo; --g) {
     const LevelInfo &L = h->levels[g];
+    int *route = h->route_b.data() + 2 * (size_t)g;   // [0]: the Gram kernel, [1]: the sweep kernel
+    route[0] = route[1] = R_NONE;
     if ((L.fast ? L.gown_n : L.own_n) == 0) continue;
     SampleArgs A;
     std::memset(&A, 0, sizeof(A));
@@ -1955,8 +2012,8 @@ static int sample_launch(st_handle h, int g_hi, int g_lo) {   // levels g_hi-1 .
         // level 7: 0.84 -> 0.72 ms averaged over a run's sweeps), loses on leaf levels and on smaller reference levels, where
         // the staged Gram of k_sample_mfma is cheaper (SPAMTREE_SPLIT_GRAM=2: every level; records identical either way)
         if (F.do_gram && lean_ok && h->split_gram && (h->split_gram == 2 || (L.isref && L.gown_n >= 32 * h->sm_count))) {
-          if (direct_parent) hipLaunchKernelGGL(k_gram_direct, dim3(L.gown_n), dim3(NT), 0, h->stream, F);
-          else hipLaunchKernelGGL(k_gram, dim3(L.gown_n), dim3(NT), 0, h->stream, F);
+          if (direct_parent) { route[0] = R_GRAM_DIRECT; hipLaunchKernelGGL(k_gram_direct, dim3(L.gown_n), dim3(NT), 0, h->stream, F); }
+          else { route[0] = R_GRAM; hipLaunchKernelGGL(k_gram, dim3(L.gown_n), dim3(NT), 0, h->stream, F); }
           F.do_gram = 0;
         }
         // reference levels on the lean kernels: the theta-only part of the posterior precision (Ri' Ri + the children's Gram parts)
@@ -1966,28 +2023,29 @@ static int sample_launch(st_handle h, int g_hi, int g_lo) {   // levels g_hi-1 .
           F.s0_mode = !h->cache_gram ? 0 : (h->s0_valid[g] ? 2 : 1);
           if (h->cache_gram) h->s0_valid[g] = 1;
         }
-        if (F.do_gram || !lean_ok) hipLaunchKernelGGL(k_sample_mfma, dim3(L.gown_n), dim3(NT), L.lds_sfast, h->stream, F);
+        if (F.do_gram || !lean_ok) { route[1] = R_SAMPLE_MFMA; hipLaunchKernelGGL(k_sample_mfma, dim3(L.gown_n), dim3(NT), L.lds_sfast, h->stream, F); }
         else if (!L.isref) {
           // segment-aligned lanes where the level's chains have at most 12 ancestors of at most 32 rows (SPAMTREE_LEAF_SEG=0: the
           // column-aligned kernel)
           const int need = (L.maxJ + 1) / 2;
-          if (h->leaf_seg && need <= 4 && L.maxMa <= 32) hipLaunchKernelGGL((k_sample_leaf_seg<4>), dim3(L.gown_n), dim3(NT), ((size_t)4 * 64 * 4 + 3 * 32) * 8, h->stream, F);
-          else if (h->leaf_seg && need <= 6 && L.maxMa <= 32) hipLaunchKernelGGL((k_sample_leaf_seg<6>), dim3(L.gown_n), dim3(NT), ((size_t)4 * 64 * 6 + 3 * 32) * 8, h->stream, F);
-          else hipLaunchKernelGGL(k_sample_leaf, dim3(L.gown_n), dim3(NT), ((size_t)L.maxP + 32 + 4 * 256 + 3 * 32) * 8, h->stream, F);
+          if (h->leaf_seg && need <= 4 && L.maxMa <= 32) { route[1] = R_LEAF_SEG4; hipLaunchKernelGGL((k_sample_leaf_seg<4>), dim3(L.gown_n), dim3(NT), ((size_t)4 * 64 * 4 + 3 * 32) * 8, h->stream, F); }
+          else if (h->leaf_seg && need <= 6 && L.maxMa <= 32) { route[1] = R_LEAF_SEG6; hipLaunchKernelGGL((k_sample_leaf_seg<6>), dim3(L.gown_n), dim3(NT), ((size_t)4 * 64 * 6 + 3 * 32) * 8, h->stream, F); }
+          else { route[1] = R_SAMPLE_LEAF; hipLaunchKernelGGL(k_sample_leaf, dim3(L.gown_n), dim3(NT), ((size_t)L.maxP + 32 + 4 * 256 + 3 * 32) * 8, h->stream, F); }
         }
         else if (h->sample_wave && L.maxM <= 27 && (h->sample_wave == 2 || L.gown_n >= 8 * h->sm_count)) {   // one block per wave: faster on a level
           // that keeps every CU busy for several rounds (n = 1e6 after the row-wise panel pass: level 7 0.44 -> 0.35 ms, level 6 -- 4096 blocks --
           // 0.151 -> 0.117), a wash at 1024 blocks (0.050 -> 0.046 there, 0.034 -> 0.039 at config #5), slower on latency-bound small levels (256 blocks: 0.029 -> 0.040): gd | wv | seg | tv, ev | Ri, per wave
           const size_t per = (((size_t)h->gd_stride + L.maxP + 32 + L.av_dbl + 64 + (size_t)std::max(L.maxM, 1) * CH_LD + 1) & ~(size_t)1);
           F.ldN = (int)per; F.Mrows = L.maxM;
+          route[1] = R_SAMPLE_WAVE;
           hipLaunchKernelGGL(k_sample_wave, dim3((L.gown_n + NT / 64 - 1) / (NT / 64)), dim3(NT), per * 8 * (NT / 64), h->stream, F);
         } else {
           // levels that do not fill the chip (fewer groups than 2 x CUs x the five workgroups the occupancy variant fits): the
           // latency variant -- every descriptor-only load of a block in one round trip (SPAMTREE_SAMPLE_LAT=0: never; identical draws)
           static const bool lat_on = !(getenv("SPAMTREE_SAMPLE_LAT") && getenv("SPAMTREE_SAMPLE_LAT")[0] == '0');
           F.av_dbl = L.av_dbl + 224;
-          if (lat_on && L.gown_n <= 2 * h->sm_count) hipLaunchKernelGGL((k_sample_lean<true>), dim3(L.gown_n), dim3(NT), L.lds_slean, h->stream, F);
-          else hipLaunchKernelGGL((k_sample_lean<false>), dim3(L.gown_n), dim3(NT), L.lds_slean, h->stream, F);
+          if (lat_on && L.gown_n <= 2 * h->sm_count) { route[1] = R_SAMPLE_LEAN_LAT; hipLaunchKernelGGL((k_sample_lean<true>), dim3(L.gown_n), dim3(NT), L.lds_slean, h->stream, F); }
+          else { route[1] = R_SAMPLE_LEAN; hipLaunchKernelGGL((k_sample_lean<false>), dim3(L.gown_n), dim3(NT), L.lds_slean, h->stream, F); }
         }
       } else {
         if (A.do_gram && L.big_sample && h->gram_big) {
@@ -2001,16 +2059,19 @@ static int sample_launch(st_handle h, int g_hi, int g_lo) {   // levels g_hi-1 .
           bool all_big = true;
           for (const auto &L2 : h->levels) all_big = all_big && (L2.count == 0 || L2.big_sample);
           Gb.mirror = all_big ? 0 : 1;
+          route[0] = R_GRAM_BIG;
           hipLaunchKernelGGL(k_gram_big, dim3(A.nlist), dim3(NT), 0, h->stream, Gb);
           A.do_gram = 0;
         }
         if (L.big_sample) {
           A.scratch = h->d_scratch.p; A.scratch_stride = h->scratch_stride;
-          if (L.isref) hipLaunchKernelGGL((k_sample<true, false>), dim3(std::min(L.own_n, h->scratch_wgs)), dim3(NT), L.lds_sample, h->stream, A);
-          else if (h->leaf_wide && !A.do_gram && L.maxM <= 64 && L.maxMa <= 96 && L.maxJ <= 8)   // one coalesced pass, segment-aligned lanes
+          if (L.isref) { route[1] = R_SAMPLE_BIG_REF; hipLaunchKernelGGL((k_sample<true, false>), dim3(std::min(L.own_n, h->scratch_wgs)), dim3(NT), L.lds_sample, h->stream, A); }
+          else if (h->leaf_wide && !A.do_gram && L.maxM <= 64 && L.maxMa <= 96 && L.maxJ <= 8) {   // one coalesced pass, segment-aligned lanes
+            route[1] = R_SAMPLE_LEAF_WIDE;
             hipLaunchKernelGGL(k_sample_leaf_wide, dim3(std::min(L.own_n, 16 * h->sm_count)), dim3(NT), ((size_t)4 * 64 * 12 + 3 * 64) * 8, h->stream, A);
-          else hipLaunchKernelGGL((k_sample<true, true>), dim3(std::min(L.own_n, h->scratch_wgs)), dim3(NT), L.lds_sample, h->stream, A);
+          } else { route[1] = R_SAMPLE_BIG_LEAF; hipLaunchKernelGGL((k_sample<true, true>), dim3(std::min(L.own_n, h->scratch_wgs)), dim3(NT), L.lds_sample, h->stream, A); }
         } else {
+          route[1] = R_SAMPLE_SMALL;
           hipLaunchKernelGGL((k_sample<false>), dim3(L.own_n), dim3(NT), L.lds_sample, h->stream, A);
         }
       }
@@ -2223,10 +2284,10 @@ extern "C" int st_predict(st_handle h, int theta_changed) {
     {
       ProfScope ps(h, 6);
       const dim3 grid(h->pred_quad_count), blk(128 * 4);
-      if (h->pred_nkx == 32) hipLaunchKernelGGL((k_factor_quad<4, 32, 8, false, true>), grid, blk, h->pred_lds, h->stream, F, cp);
-      else if (h->pred_nkx == 38) hipLaunchKernelGGL((k_factor_quad<4, 38, 10, false, true>), grid, blk, h->pred_lds, h->stream, F, cp);
-      else if (h->pred_nkx == 44) hipLaunchKernelGGL((k_factor_quad<4, 44, 11, false, true>), grid, blk, h->pred_lds, h->stream, F, cp);
-      else hipLaunchKernelGGL((k_factor_quad<4, 50, 13, false, true>), grid, blk, h->pred_lds, h->stream, F, cp);
+      if (h->pred_nkx == 32) { h->route_p = R_QUAD32_LEAF; hipLaunchKernelGGL((k_factor_quad<4, 32, 8, false, true>), grid, blk, h->pred_lds, h->stream, F, cp); }
+      else if (h->pred_nkx == 38) { h->route_p = R_QUAD38_LEAF; hipLaunchKernelGGL((k_factor_quad<4, 38, 10, false, true>), grid, blk, h->pred_lds, h->stream, F, cp); }
+      else if (h->pred_nkx == 44) { h->route_p = R_QUAD44_LEAF; hipLaunchKernelGGL((k_factor_quad<4, 44, 11, false, true>), grid, blk, h->pred_lds, h->stream, F, cp); }
+      else { h->route_p = R_QUAD50_LEAF; hipLaunchKernelGGL((k_factor_quad<4, 50, 13, false, true>), grid, blk, h->pred_lds, h->stream, F, cp); }
     }
     HCHK(h, hipGetLastError());
     HCHK(h, hipStreamSynchronize(h->stream));
@@ -2240,8 +2301,8 @@ extern "C" int st_predict(st_handle h, int theta_changed) {
   A.maxP = L.maxP; A.maxM = L.maxM; A.maxMa = L.maxMa; A.SR = L.big_factor ? 4 : 8;
   {
     ProfScope ps(h, 6);
-    if (L.big_factor) launch_factor<true, MODE_PREDICT>(h, L, A, cp);
-    else launch_factor<false, MODE_PREDICT>(h, L, A, cp);
+    if (L.big_factor) { h->route_p = R_PREDICT_SCRATCH; launch_factor<true, MODE_PREDICT>(h, L, A, cp); }
+    else { h->route_p = R_PREDICT_LDS; launch_factor<false, MODE_PREDICT>(h, L, A, cp); }
   }
   HCHK(h, hipGetLastError());
   HCHK(h, hipStreamSynchronize(h->stream));
@@ -2429,6 +2490,18 @@ extern "C" int st_level_info(st_handle h, int32_t *n_levels, int32_t *kernel, in
   }
   return ST_OK;
 }
+
+extern "C" int st_route_info(st_handle h, int32_t *n_levels, int32_t *phase_a, int32_t *phase_b, int32_t *phase_p, int32_t cap) {
+  if (!h || !n_levels) return ST_ERR_USAGE;
+  *n_levels = h->n_actual_groups;
+  for (int g = 0; g < h->n_actual_groups && g < cap; ++g) {
+    for (int i = 0; i < ST_ROUTE_A_SLOTS && phase_a; ++i) phase_a[ST_ROUTE_A_SLOTS * g + i] = h->route_a[(size_t)ST_ROUTE_A_SLOTS * g + i];
+    for (int i = 0; i < 2 && phase_b; ++i) phase_b[2 * g + i] = h->route_b[2 * (size_t)g + i];
+  }
+  if (phase_p) *phase_p = h->route_p;
+  return ST_OK;
+}
+extern "C" const char *st_route_name(int32_t code) { return (code >= 0 && code < R_COUNT) ? k_route_names[code] : nullptr; }
 
 // ---- CrossCovarianceAG10 (covariance_functions.cpp:301-355): dense n1 x n2 cross-covariance, column-major output.
 // mv1 / mv2 are 1-based (as in R).  Like the reference it refuses a 1 x 1 Dmat ("Invalid Dmat for multivariate data").

@@ -287,5 +287,23 @@ class SpamTreeMV:
         return [dict(kernel=self.KERNEL_NAMES[arr[0][g]], max_m=int(arr[1][g]), max_P=int(arr[2][g]), n_blocks=int(arr[3][g]))
                 for g in range(nl.value)]
 
+    def route_info(self):
+        """What the launch sites actually ran the last time: dict(levels=[dict(A=[kernels of phase A in launch order],
+        gram=Gram kernel of the level's last sweep or None, sweep=its sweep kernel or None) per observed level],
+        predict=kernel of the last predict or None).  Names are the template instantiations as the source spells them."""
+        nl = C.c_int32()
+        cap = 64
+        a = np.zeros(3 * cap, dtype=np.int32)
+        b = np.zeros(2 * cap, dtype=np.int32)
+        p = C.c_int32()
+        ip = C.POINTER(C.c_int32)
+        self._check(self.lib.st_route_info(self.h, C.byref(nl), a.ctypes.data_as(ip), b.ctypes.data_as(ip), C.byref(p), cap))
+
+        def name(code):
+            return self.lib.st_route_name(int(code)).decode() if code else None
+        levels = [dict(A=[name(c) for c in a[3 * g:3 * g + 3] if c], gram=name(b[2 * g]), sweep=name(b[2 * g + 1]))
+                  for g in range(min(nl.value, cap))]
+        return dict(levels=levels, predict=name(p.value))
+
     def synchronize(self):
         self._check(self.lib.st_synchronize(self.h))

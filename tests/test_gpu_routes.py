@@ -1,0 +1,376 @@
+"""GPU: every phase-A, phase-B and phase-P instantiation of the dispatch table against the NumPy oracle, at the chain
+lengths that select it.
+
+Each row of ROUTES is an oracle-size problem (mostly deep strip trees, tests/util.strip_coords with K = (2, 1)) plus the
+environment switches that make its small levels take the big-level routes.  The row names the instantiations it must
+reach; the test runs the whole device protocol first, proves through st_route_info (what the launch sites actually ran)
+that the row reached them, and only then compares with the oracle (tolerances of test_gpu_parity: REL = 1e-9, H 1e-8):
+
+  phase A on both slots (loglik_w, the components, H / Ri of every observed block), three sweeps of w, each followed by
+  loglik_w and its per-block components, st_predict where the row has NA blocks, then a rebuild sweep after an accepted
+  theta (slot 1 factorised at theta', swapped in, swept twice: the Gram parts rebuilt, then read from the cache) and
+  st_predict again.  The log-density of a sweep is held to REL relative to the magnitudes of the terms it sums.
+
+Route keys: "A" phase A, "gram" the Gram kernel of a rebuild sweep, "sweep" any sweep kernel, "cached" the sweep kernel
+of a sweep that read cached Gram parts ("leaf_cached": that of the last level), "P" st_predict.  NKX (k_factor_quad's
+chain tiles) follows the level's longest chain P: 32 up to 128 rows, 38 up to 152, 44 up to 176, 50 up to 200;
+WCH=true: blocks of <= 27 rows.
+"""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from tests.util import make_problem, oracle_model, strip_coords
+
+pytestmark = pytest.mark.gpu
+REL = 1e-9
+REL_H = 1e-8
+
+
+def quad(nkx, isref, wch):
+    nkt = {32: 8, 38: 10, 44: 11, 50: 13}[nkx]
+    return f"k_factor_quad<4, {nkx}, {nkt}, {'true' if isref else 'false'}, {'true' if wch else 'false'}>"
+
+
+QUAD_MIN = {"SPAMTREE_QUAD_MIN": "1"}    # oracle-size levels have far fewer than 2 x CUs column groups
+
+# id, strip (nx, ny, q), make_problem keywords, environment, routes the row must reach.  The chain lengths in the comments
+# are the levels' longest chains (rows), from the tree the keywords build.
+ROUTES = [
+    # 30-row reference blocks (no wave elimination): P = 120 / 150; leaf P = 180; NA blocks behind the full chain, P = 180
+    dict(id="ref30_leaf50_pred50", strip=(640, 5, 1), kw=dict(cell_size=31, tree_depth=6, missing=0.15), env=QUAD_MIN,
+         routes={"A": [quad(32, True, False), quad(38, True, False), quad(50, False, True)],
+                 "P": [quad(50, False, True)], "sweep": ["k_sample_leaf_seg<4>", "k_sample_lean<true>"]}),
+    # 32-row reference blocks of two outcomes: P = 128 / 160 (the NKX 44 team elimination)
+    dict(id="ref32_nkx44", strip=(640, 4, 2), kw=dict(cell_size=16, tree_depth=6), env=QUAD_MIN,
+         routes={"A": [quad(32, True, False), quad(44, True, False)], "sweep": ["k_sample_lean<true>"]}),
+    # 25-row reference blocks, P = 125 / 150 / 175 (128 blocks): NKX 32 / 38 / 44 with the wave elimination; k_gram on
+    # every level of a rebuild sweep
+    dict(id="ref25_wch_nkx44", strip=(1280, 5, 1), kw=dict(cell_size=25, tree_depth=8), env=dict(QUAD_MIN, SPAMTREE_SPLIT_GRAM="2"),
+         routes={"A": [quad(32, True, True), quad(38, True, True), quad(44, True, True)], "gram": ["k_gram"]}),
+    # 24-row reference blocks, leaf and NA blocks with P = 144: leaf and prediction NKX 38; reference levels one block per
+    # wave (forced)
+    dict(id="leaf38_pred38_wave", strip=(640, 4, 1), kw=dict(cell_size=31, tree_depth=6, missing=0.15),
+         env=dict(QUAD_MIN, SPAMTREE_SAMPLE_WAVE="2"),
+         routes={"A": [quad(38, False, True)], "P": [quad(38, False, True)], "sweep": ["k_sample_wave", "k_sample_leaf_seg<4>"]}),
+    # leaf and NA blocks with P = 168: leaf and prediction NKX 44; SPAMTREE_LEAF_SEG=0: the column-aligned leaf sweep
+    dict(id="leaf44_pred44_leafsweep", strip=(1280, 4, 1), kw=dict(cell_size=31, tree_depth=7, missing=0.15),
+         env=dict(QUAD_MIN, SPAMTREE_LEAF_SEG="0"),
+         routes={"A": [quad(38, True, True), quad(44, False, True)], "P": [quad(44, False, True)], "sweep": ["k_sample_leaf"]}),
+    # two outcomes of 9 knots, nine levels: leaf chains of 9 ancestors (k_sample_leaf_seg<6>); the last reference level
+    # forms its children's Gram parts itself (k_gram_direct)
+    dict(id="seg6_gram_direct", strip=(640, 6, 2), kw=dict(cell_size=9, tree_depth=9), env=dict(QUAD_MIN, SPAMTREE_SPLIT_GRAM="2"),
+         routes={"A": [quad(38, True, True)], "sweep": ["k_sample_leaf_seg<6>"], "gram": ["k_gram", "k_gram_direct"]}),
+    # the 25 x 25 grid with NA rows (test_gpu_parity's CASES[1]): leaf and prediction chains of <= 78 rows, NKX 32
+    dict(id="grid_leaf32_pred32", side=25, kw=dict(missing=0.12), env=QUAD_MIN,
+         routes={"A": [quad(32, False, True)], "P": [quad(32, False, True)]}),
+    # eight 32-row ancestors: the leaf level's chains are 256 rows, the longest the column-group path takes; no lean kernel
+    # there (chains > 255 rows), so its sweeps that read cached Gram parts stay on k_sample_mfma
+    dict(id="leaf256_cached_mfma", strip=(1400, 4, 2), kw=dict(cell_size=16, tree_depth=8), env={}, leaf_P_min=256,
+         routes={"leaf_cached": ["k_sample_mfma"]}),
+]
+# instantiations no row reaches, on purpose
+EXCLUDED = {
+    quad(50, True, True): "never dispatched: a reference level with chains of 177-200 rows takes k_factor_mfma "
+                          "(the NKX 50 team elimination spills registers; spamtree_hip.hip, the q_nkx choice)",
+    quad(50, True, False): "never dispatched, as above",
+}
+
+
+def build_problem(row):
+    if "side" in row:
+        return make_problem(side=row["side"], q=1, seed=11, **row["kw"])
+    nx, ny, q = row["strip"]
+    coords, mv = strip_coords(nx, ny, q)
+    return make_problem(coords=coords, mv_id=mv, q=q, seed=11, K=(2, 1), **row["kw"])
+
+
+def hip_model(pb, **kw):
+    from spamtree_amd.model import SpamTreeMV
+    return SpamTreeMV(pb["y"], pb["X"], pb["Z"], pb["coords"], pb["mv_id"], pb["blocking"], pb["gix_block"],
+                      pb["res_is_ref"], pb["parents"], pb["children"], False, pb["block_names"], pb["block_groups"],
+                      pb["indexing"], kw["w"], kw["beta"], kw["theta"], 1.0 / kw["tausq"])
+
+
+def inputs(pb):
+    rng = np.random.default_rng(7)
+    return dict(w=rng.standard_normal(pb["n"]), beta=np.array([0.3, -0.2, 0.1]), tausq=0.2, theta=pb["theta"],
+                theta2=pb["theta"] * (1.0 + 0.05 * rng.standard_normal(pb["theta"].size)),
+                zs=[rng.standard_normal(pb["n"]) for _ in range(5)])
+
+
+def run_device(pb, inp):
+    """The whole protocol on the device; returns its outputs and the routes every step took."""
+    hm = hip_model(pb, **inp)
+    routes = {k: set() for k in ("A", "gram", "sweep", "cached", "leaf_cached", "P")}
+
+    def note(sweep=None):
+        r = hm.route_info()
+        if sweep == "cached" and r["levels"][-1]["sweep"]:
+            routes["leaf_cached"].add(r["levels"][-1]["sweep"])
+        for L in r["levels"]:
+            if sweep is None:
+                routes["A"].update(L["A"])
+            else:
+                if L["gram"]:
+                    routes["gram"].add(L["gram"])
+                if L["sweep"]:
+                    routes["sweep"].add(L["sweep"])
+                    if sweep == "cached":
+                        routes["cached"].add(L["sweep"])
+        if r["predict"]:
+            routes["P"].add(r["predict"])
+
+    out = dict(blocks=[{}, {}], leaf_P=hm.level_info()[-1]["max_P"])
+    has_pred = bool(np.any(~np.isfinite(pb["y"])))
+    assert hm.get_loglik_comps_w(0)
+    note()
+    hm.theta_update(1, inp["theta2"])
+    assert hm.get_loglik_comps_w(1)
+    note()
+    out["loglik_A"] = list(hm.loglik_w)
+    out["comps"] = [hm.comps(0), hm.comps(1)]
+    observed = [u for u, ix in enumerate(pb["indexing"]) if np.isfinite(pb["y"][ix]).any()]
+    for slot in (0, 1):
+        for u in observed:
+            out["blocks"][slot][u] = hm.block(slot, u)
+    ws, lls, ll_comps = [], [], []
+    for it in range(3):
+        hm.deal_with_w(inp["zs"][it])
+        note("rebuild" if it == 0 else "cached")
+        ws.append(hm.get_w().copy())
+        lls.append(hm.get_loglik_w(0))
+        ll_comps.append(hm.comps(0)[1].copy())
+    if has_pred:
+        hm.predict(True)
+        note("predict")
+        ws.append(hm.get_w().copy())
+    hm.accept_make_change()
+    for it in (3, 4):
+        hm.deal_with_w(inp["zs"][it])
+        note("rebuild" if it == 3 else "cached")
+        ws.append(hm.get_w().copy())
+        lls.append(hm.get_loglik_w(0))
+        ll_comps.append(hm.comps(0)[1].copy())
+    if has_pred:
+        hm.predict(True)
+        ws.append(hm.get_w().copy())
+    hm.close()
+    out.update(ws=ws, lls=lls, ll_comps=ll_comps, routes=routes)
+    return out
+
+
+def relerr(a, b):
+    a = np.asarray(a, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    if a.size == 0:
+        return 0.0
+    return float(np.abs(a - b).max() / max(1e-300, np.abs(b).max()))
+
+
+def compare_with_oracle(pb, inp, out):
+    om = oracle_model(pb, w=inp["w"], beta=inp["beta"], tausq=inp["tausq"])
+    assert om.get_loglik_comps_w(om.param_data)
+    om.theta_update(om.alter_data, inp["theta2"])
+    assert om.get_loglik_comps_w(om.alter_data)
+    for slot, pd in enumerate((om.param_data, om.alter_data)):
+        assert abs(out["loglik_A"][slot] - pd.loglik_w) <= REL * abs(pd.loglik_w), slot
+        ld, ll = out["comps"][slot]
+        assert relerr(ld, pd.logdetCi_comps) <= REL and relerr(ll, pd.loglik_w_comps) <= REL, slot
+        for u in range(om.n_blocks):
+            if om.block_ct_obs[u] == 0:
+                continue
+            H, Ri = out["blocks"][slot][u]
+            if om.parents[u].size:
+                assert relerr(H, pd.w_cond_mean_K[u]) <= REL_H, (slot, u)
+            assert relerr(Ri, pd.Rcc_invchol[u] if om.block_is_reference[u] else pd.ccholprecdiag[u]) <= REL, (slot, u)
+    has_pred = bool(np.any(~np.isfinite(pb["y"])))
+    ws, lls, ll_comps = list(out["ws"]), list(out["lls"]), list(out["ll_comps"])
+
+    def sweep(z):
+        om.gibbs_sample_w(z)
+        assert relerr(ws.pop(0)[om.na_ix_all], om.w[om.na_ix_all]) <= REL
+        om.get_loglik_w(om.param_data)
+        pd = om.param_data
+        # per block, then the sum: loglik_w = sum(logdetCi_comps) + sum(loglik_w_comps).  After a sweep the quadratic forms of
+        # the posterior draw can nearly cancel the log-determinants (the 256-row leaf chains after an accepted theta:
+        # loglik_w = 104 from terms whose magnitudes sum to more than 2.5e4), so the sum is held to REL relative to the
+        # terms it adds up, not to its own small value
+        assert relerr(ll_comps.pop(0), pd.loglik_w_comps) <= REL
+        terms = np.abs(pd.logdetCi_comps).sum() + np.abs(pd.loglik_w_comps).sum()
+        assert abs(lls.pop(0) - pd.loglik_w) <= REL * max(abs(pd.loglik_w), terms)
+
+    def predict():
+        om.predict(True)
+        assert relerr(ws.pop(0), om.w) <= REL
+
+    for it in range(3):
+        sweep(inp["zs"][it])
+    if has_pred:
+        predict()
+    om.accept_make_change()
+    for it in (3, 4):
+        sweep(inp["zs"][it])
+    if has_pred:
+        predict()
+    assert not ws and not lls and not ll_comps
+
+
+def check_routes(row, routes):
+    for key, names in row["routes"].items():
+        for name in names:
+            assert name in routes[key], (row["id"], key, name, sorted(routes[key]))
+
+
+@pytest.mark.parametrize("row", ROUTES, ids=[r["id"] for r in ROUTES])
+def test_route_matches_oracle(row, monkeypatch):
+    for k, v in row["env"].items():
+        monkeypatch.setenv(k, v)
+    pb = build_problem(row)
+    inp = inputs(pb)
+    out = run_device(pb, inp)
+    check_routes(row, out["routes"])
+    assert out["leaf_P"] >= row.get("leaf_P_min", 0), (row["id"], out["leaf_P"])
+    compare_with_oracle(pb, inp, out)
+
+
+# ---- k_sample_lean<false>: SPAMTREE_SAMPLE_LAT is read once per process, so that route runs in a child process
+LEAN_ROW = ROUTES[0]
+
+
+def _lean_child(path):
+    """Runs LEAN_ROW's device protocol in this (child) process and saves its draws and routes."""
+    for k, v in LEAN_ROW["env"].items():
+        os.environ[k] = v
+    pb = build_problem(LEAN_ROW)
+    out = run_device(pb, inputs(pb))
+    np.savez(path, ws=np.array(out["ws"]), lls=np.array(out["lls"]), ll_comps=np.array(out["ll_comps"]),
+             sweep=np.array(sorted(out["routes"]["sweep"])))
+
+
+def test_lean_sample_without_latency_variant_matches_oracle_and_is_bitwise_lean_true(monkeypatch, tmp_path):
+    for k, v in LEAN_ROW["env"].items():
+        monkeypatch.setenv(k, v)
+    path = str(tmp_path / "lean_false.npz")
+    code = f"from tests.test_gpu_routes import _lean_child; _lean_child({path!r})"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, SPAMTREE_SAMPLE_LAT="0"), cwd=root,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    child = np.load(path)
+    assert "k_sample_lean<false>" in child["sweep"].tolist() and "k_sample_lean<true>" not in child["sweep"].tolist()
+    pb = build_problem(LEAN_ROW)
+    inp = inputs(pb)
+    out = run_device(pb, inp)      # this process: the latency variant on the same levels
+    assert "k_sample_lean<true>" in out["routes"]["sweep"]
+    for k in ("ws", "lls", "ll_comps"):
+        assert np.array_equal(child[k], np.array(out[k])), k
+        out[k] = list(child[k])
+    compare_with_oracle(pb, inp, out)
+
+
+# ---- config #2 at full size (n = 99 856, bench.py --side 316) on its default routes, against oracle/refcpu
+CONFIG2_ROUTES = {
+    "A": [quad(32, True, True), quad(38, False, True)],    # the 1 024-block reference level (P = 125) / the leaf level (P = 150)
+    "sweep": ["k_sample_lean<false>"],                       # that reference level: more groups than 2 x CUs
+}
+
+
+def test_config2_full_size_default_routes_match_refcpu():
+    from oracle.refcpu import RefCpu
+    from spamtree_amd.model import SpamTreeMV
+    from spamtree_amd.synthetic import make_workload
+    wl = make_workload(316)
+    beta = np.array([-0.5, 0.2, 0.4])
+    rng = np.random.default_rng(9)
+    w0 = rng.standard_normal(wl["n"])
+    th2 = wl["theta"] * (1.0 + 0.05 * rng.standard_normal(wl["theta"].size))
+    zs = [rng.standard_normal(wl["n"]) for _ in range(3)]
+    hm = SpamTreeMV(wl["y"], wl["X"], wl["Z"], wl["coords"], wl["mv_id"], wl["blocking"], wl["gix_block"], wl["res_is_ref"],
+                    wl["parents"], wl["children"], False, wl["block_names"], wl["block_groups"], wl["indexing"], w0, beta,
+                    wl["theta"], 1.0 / 0.15)
+    info = hm.level_info()
+    assert hm.get_loglik_comps_w(0)
+    ra = hm.route_info()["levels"]
+    comps = hm.comps(0)
+    draws = []
+    for z in zs[:2]:
+        hm.deal_with_w(z)
+        draws.append((hm.get_w().copy(), hm.get_loglik_w(0)))
+    rb = hm.route_info()["levels"]          # the second sweep: cached Gram parts
+    stats = hm.stats()
+    hm.theta_update(1, th2)
+    assert hm.get_loglik_comps_w(1)
+    ll2 = hm.loglik_w[1]
+    hm.accept_make_change()
+    hm.deal_with_w(zs[2])
+    draws.append((hm.get_w().copy(), hm.get_loglik_w(0)))
+    hm.close()
+    # the routes first: the reference level of 1 024 blocks and the leaf level
+    ref = [g for g, L in enumerate(info) if L["n_blocks"] == 1024]
+    assert len(ref) == 1 and info[ref[0]]["max_P"] == 125
+    leaf = len(info) - 1
+    assert info[leaf]["max_P"] == 150
+    assert ra[ref[0]]["A"] == [CONFIG2_ROUTES["A"][0]] and ra[leaf]["A"] == [CONFIG2_ROUTES["A"][1]]
+    assert rb[ref[0]]["sweep"] == CONFIG2_ROUTES["sweep"][0]
+    rc = RefCpu(wl["y"], wl["X"], wl["coords"], wl["mv_id"], wl["res_is_ref"], wl["parents"], wl["children"],
+                wl["block_names"], wl["block_groups"], wl["indexing"], threads=16)
+    rc.set_w(w0); rc.set_beta(beta[:, None]); rc.set_tausq_inv(1.0 / 0.15)
+    code, ll = rc.factor(0, wl["theta"])
+    assert code == 0
+    ld, lc = rc.comps(0)
+    assert relerr(comps[0], ld) <= REL and relerr(comps[1], lc) <= REL
+    obs = np.isfinite(wl["y"])
+    for it in range(2):
+        assert rc.sample_w(zs[it]) == 0
+        assert relerr(draws[it][0][obs], rc.get_w()[obs]) <= REL, it
+        assert abs(draws[it][1] - rc.loglik_w(0)) <= REL * abs(rc.loglik_w(0)), it
+    rxty, rssq = rc.stats()
+    assert relerr(stats[0], rxty) <= REL and relerr(stats[1], rssq) <= REL
+    code, rll2 = rc.factor(1, th2)
+    assert code == 0 and abs(ll2 - rll2) <= REL * abs(rll2)
+    rc.swap()
+    assert rc.sample_w(zs[2]) == 0
+    assert relerr(draws[2][0][obs], rc.get_w()[obs]) <= REL
+    assert abs(draws[2][1] - rc.loglik_w(0)) <= REL * abs(rc.loglik_w(0))
+    rc.close()
+
+
+# ---- k_gram_direct eligibility: a leaf block whose last parent is one level above the last reference level
+def shallow_leaf_problem():
+    """CASES[0] of test_gpu_parity (four levels, the last one the leaf level) with one leaf block re-hung: its parent on the
+    last reference level is dropped (parents and children stay consistent), so its direct parent lies one level higher."""
+    pb = make_problem(side=25, q=1, seed=53)
+    par = [p.copy() for p in pb["parents"]]
+    ch = [c.copy() for c in pb["children"]]
+    grp = pb["block_groups"]
+    leaf = [u for u in range(len(par)) if grp[u] == grp.max() and len(pb["indexing"][u])]
+    u = leaf[len(leaf) // 2]
+    gp = par[u][-1]
+    assert grp[gp] == grp.max() - 1
+    par[u] = par[u][:-1]
+    ch[gp] = ch[gp][ch[gp] != u]
+    assert grp[par[u][-1]] == grp.max() - 2
+    pb.update(parents=par, children=ch)
+    return pb
+
+
+@pytest.mark.parametrize("direct", [None, "0"])
+def test_gram_direct_with_a_leaf_below_a_shallower_parent(direct, monkeypatch):
+    """k_gram_direct lets the last reference level form its children's Gram parts, and the leaf level then writes none.  A
+    leaf whose direct parent is shallower would leave that parent's Gram part unwritten: such a tree must keep k_gram (the
+    draws differed from the oracle while the eligibility check looked at the last reference level's children only)."""
+    monkeypatch.setenv("SPAMTREE_SPLIT_GRAM", "2")
+    if direct is None:
+        monkeypatch.delenv("SPAMTREE_GRAM_DIRECT", raising=False)
+    else:
+        monkeypatch.setenv("SPAMTREE_GRAM_DIRECT", direct)
+    pb = shallow_leaf_problem()
+    inp = inputs(pb)
+    out = run_device(pb, inp)
+    assert "k_gram" in out["routes"]["gram"]
+    assert "k_gram_direct" not in out["routes"]["gram"]    # the last reference level does not hold every leaf's parent
+    compare_with_oracle(pb, inp, out)

@@ -1,0 +1,130 @@
+"""CPU-only: every kernel instantiation the host code launches is covered -- by a row of the route table of
+tests/test_gpu_routes.py (which proves through st_route_info that it reached it and compares it with the oracle), by
+the table's explicit exclusions, or by an existing test named here.  A kernel added later without a test fails here."""
+import os
+import re
+
+from tests import test_gpu_routes as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "spamtree_amd", "csrc", "spamtree_hip.hip")
+
+# launched kernels that other tests compare with the oracle (or, for plumbing, check bit for bit)
+COVERED_ELSEWHERE = {
+    "k_xb": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
+    "k_marginal_invchol_wave": "tests/test_limited_tree.py::test_limited_tree_parity",
+    "k_marginal_invchol": "tests/test_limited_tree.py::test_limited_tree_parity",
+    "k_factor<false, MODE_FACTOR>": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
+    "k_factor<true, MODE_FACTOR>": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
+    "k_factor<false, MODE_PREDICT>": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
+    "k_factor<true, MODE_PREDICT>": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
+    "k_factor_mfma": "tests/test_gpu_deep.py::test_config5_chains_201_to_256_on_k_factor_mfma",
+    "k_factor_lchain<96>": "tests/test_gpu_deep.py::test_config4_chains_bigmfma_second_pass",
+    "k_factor_lchain<136>": "tests/test_gpu_deep.py::test_config4_chains_bigmfma_second_pass",
+    "k_factor_ref_finish": "tests/test_gpu_deep.py::test_config4_reference_levels_on_lchain_and_ref_finish",
+    "k_lchain_scalars": "tests/test_gpu_deep.py::test_config4_chains_bigmfma_second_pass",
+    "k_factor_wide<WG_JT>": "tests/test_gpu_deep.py::test_config4_chains_bigmfma_second_pass",
+    "k_factor_bigmfma<3, 5, 34>": "tests/test_gpu_deep.py::test_config4_chains_bigmfma_second_pass",
+    "k_factor_bigmfma<4, 5, 34>": "tests/test_gpu_deep.py::test_config4_chains_bigmfma_second_pass",
+    "k_factor_bigmfma<5, 3, 24>": "tests/test_gpu_deep.py::test_config4_chains_bigmfma_second_pass",
+    "k_merge_err": "tests/test_gpu_chain.py::test_cpp_driver_with_top_levels_ahead_of_time",
+    "k_pack_comps": "tests/test_gpu_sharded.py::test_sharded_equals_single_process_bitwise",
+    "k_normals": "tests/test_gpu_parity.py::test_generated_sweep_normals_are_the_documented_stream",
+    "k_gram_big": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
+    "k_sample<true, false>": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
+    "k_sample_leaf_wide": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
+    "k_sample<true, true>": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
+    "k_sample<false>": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
+    "k_pack_w": "tests/test_gpu_sharded.py::test_sharded_equals_single_process_bitwise",
+    "k_gather_pack": "tests/test_gpu_sharded.py::test_sharded_equals_single_process_bitwise",
+    "k_gather_unpack": "tests/test_gpu_sharded.py::test_sharded_equals_single_process_bitwise",
+    "k_loglik": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
+    "k_loglik_grp": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
+    "k_stats": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
+    "k_stats_final": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
+    "k_yhat": "tests/test_gpu_parity.py::test_device_normals_match_oracle_stream",
+    "k_cross_cov": "tests/test_gpu_parity.py::test_cross_covariance_ag10_export",
+    "k_axpy_sum": "tests/test_gpu_parity.py::test_posterior_means_and_quantiles_match_oracle_chain",
+    "k_qtile": "tests/test_gpu_parity.py::test_posterior_means_and_quantiles_match_oracle_chain",
+}
+
+
+def _norm(name):
+    return re.sub(r"\s*,\s*", ", ", re.sub(r"\s+", " ", name.strip()))
+
+
+def launched_kernels():
+    """Every instantiation named by a hipLaunchKernelGGL of the host code, the macro and template wrappers expanded."""
+    src = open(SRC).read()
+    names = set()
+    for m in re.finditer(r"hipLaunchKernelGGL\(\s*(\(\s*[A-Za-z_]\w*\s*<[^>]*>\s*\)|[A-Za-z_]\w*)", src):
+        names.add(_norm(m.group(1).strip("() ")))
+    # QLAUNCH(NU_, NKX_, NKT_, ...): k_factor_quad<NU_, NKX_, NKT_, ...> once per invocation
+    calls = re.findall(r"QLAUNCH\(\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)\s*,", src)
+    assert calls, "the QLAUNCH macro is no longer invoked: update this parser"
+    for name in [n for n in names if "NU_" in n]:
+        names.discard(name)
+        for nu, nkx, nkt in calls:
+            names.add(name.replace("NU_", nu).replace("NKX_", nkx).replace("NKT_", nkt))
+    # launch_factor<BIG, MODE>: k_factor<BIG, MODE> for every instantiation of the wrapper
+    wraps = set(re.findall(r"launch_factor<\s*(true|false)\s*,\s*(MODE_\w+)\s*>", src))
+    assert wraps, "launch_factor is no longer instantiated: update this parser"
+    names.discard("k_factor<BIG, MODE>")
+    names |= {f"k_factor<{b}, {m}>" for b, m in wraps}
+    assert not [n for n in names if re.search(r"\b[A-Z][A-Z_]*_\b", n)], names   # no macro parameter left
+    return names
+
+
+def table_routes():
+    names = set()
+    for row in R.ROUTES:
+        for v in row["routes"].values():
+            names.update(v)
+    for v in R.CONFIG2_ROUTES.values():
+        names.update(v)
+    return names | {"k_sample_lean<false>"}      # test_lean_sample_without_latency_variant_matches_oracle_and_is_bitwise_lean_true
+
+
+def test_every_launched_kernel_has_a_test():
+    launched = launched_kernels()
+    assert "k_factor_quad<4, 44, 11, true, false>" in launched and "k_sample_lean<true>" in launched   # the parser sees both forms
+    table = table_routes()
+    missing = sorted(n for n in launched if n not in table and n not in R.EXCLUDED and n not in COVERED_ELSEWHERE)
+    assert not missing, f"launched without a test: {missing}"
+    stale = sorted(n for n in set(COVERED_ELSEWHERE) | set(R.EXCLUDED) | table if n not in launched)
+    assert not stale, f"named but no longer launched: {stale}"
+
+
+def test_covering_tests_exist():
+    for name, ref in COVERED_ELSEWHERE.items():
+        path, test = ref.split("::")
+        assert re.search(rf"^def {re.escape(test)}\(", open(os.path.join(ROOT, path)).read(), re.M), (name, ref)
+
+
+def test_route_table_reaches_the_quad_instantiations():
+    table = table_routes()
+    for nkx in (32, 38, 44):
+        for wch in (True, False):
+            assert R.quad(nkx, True, wch) in table, (nkx, wch)
+    for nkx in (32, 38, 44, 50):
+        assert R.quad(nkx, False, True) in table
+        assert any(R.quad(nkx, False, True) in row["routes"].get("P", []) for row in R.ROUTES), nkx
+    assert {R.quad(50, True, True), R.quad(50, True, False)} <= set(R.EXCLUDED)
+
+
+def test_route_names_spell_launched_instantiations():
+    """st_route_name (host code only, no device needed) spells every route code as a launched instantiation."""
+    from spamtree_amd import build, _lib
+    build.build()          # (a fresh checkout: the library may not be built yet)
+    lib = _lib.load()
+    launched = launched_kernels()
+    assert lib.st_route_name(0) == b""
+    names, code = [], 1
+    while lib.st_route_name(code) is not None:
+        names.append(lib.st_route_name(code).decode())
+        code += 1
+    assert len(names) == len(set(names))
+    assert set(names) <= launched, sorted(set(names) - launched)
+    # every instantiation of the per-level phases has a route code
+    per_level = {n for n in launched if n.startswith(("k_factor", "k_marginal", "k_lchain", "k_gram", "k_sample"))}
+    assert per_level <= set(names), sorted(per_level - set(names))
