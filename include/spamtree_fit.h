@@ -10,6 +10,8 @@
  *   stream 3  gamma draws (Marsaglia-Tsang; index = 2*attempt [+1])  spamtree_model.cpp:1405
  *   stream 4  beta normals (index = component, hi = outcome)         spamtree_model.cpp:1378
  *   stream 5  yhat noise (device)                                    spamtree_fit.cpp:384
+ *   stream 6  new-point normals z of st_points_predict (device, index = point in the caller's order)
+ *   stream 7  new-point yhat noise of st_points_predict (device, same index)
  * normal = sqrt(-2 ln u1) cos(2 pi u2), u from 53 bits of two 32-bit words.  Draws are identical for any GPU count.
  */
 #ifndef SPAMTREE_FIT_H

@@ -216,6 +216,27 @@ int st_summary_get(st_handle h, double *w_mean, double *yhat_mean, int64_t *n_ac
 int st_summary_reserve(st_handle h, int64_t keep);
 int st_summary_quantile(st_handle h, double q, double *w_q, double *yhat_q);
 
+/* ---- new-point prediction from a fitted state: the predictive at locations that are not rows of the problem, the way the model
+ * treats an NA row (make_tree's missing level, predict_std spamtree_model.cpp:1234-1358) without rebuilding the tree.
+ * A point of margin j anchored at block b (the block of its nearest deepest-knot-level row, same margin if cherrypick_same_margin,
+ * ties to the lowest row: spamtree_amd.predict.locate) conditions on S = parents(b), plus b itself when b is a reference block:
+ * with k = K(S, x*), v = Linv_S k, mean = v' Linv_S w_S, var = max(K(x*, x*) - v'v, 0), draw = mean + sqrt(var) z,
+ * yhat = x' beta_j + draw + sqrt(tausq_j) e.  Not for limited_tree or world > 1 handles (ST_ERR_UNSUPPORTED).
+ * st_points_set: coords n_new x 2 column-major, mv 1-based, anchor 0-based block ids with observed rows, X n_new x p column-major
+ *   or NULL (then no yhat).  Replaces the previous point set.
+ * st_points_predict: on slot 0 (refused before st_factor(0, ...)) and the current w / beta / tausq_inv.  mode 0 = draw, 1 =
+ *   conditional mean only (w_new = cond_mean, no noise in yhat).  z: n_new normals in the caller's order, or NULL = Philox stream 6,
+ *   counter (i, i >> 32, iter, 6), i = index in the caller's order; yhat noise: stream 7, same counter.  Any output may be NULL.
+ *   Outputs are in the caller's order; mean, var and draws from a given z do not depend on the order or grouping of the points.
+ * st_points_info: of the last st_points_predict -- route = bit set, bit (code - 1) set when the kernel of that code ran
+ *   (st_points_route_name spells it; NULL out of range); n_groups = conditioning chains of the point set; the algorithmic bytes and
+ *   flops of the call (from shapes).  Any output may be NULL.  Needs no device. */
+int st_points_set(st_handle h, int64_t n_new, const double *coords, const int64_t *mv, const int64_t *anchor, const double *X);
+int st_points_predict(st_handle h, int mode, const double *z, uint64_t seed, uint32_t iter, double *w_new, double *cond_mean,
+                      double *cond_var, double *yhat_new);
+int st_points_info(st_handle h, int32_t *route, int64_t *n_groups, double *alg_bytes, double *flops);
+const char *st_points_route_name(int32_t code);
+
 int st_set_stream(st_handle h, void *stream);              /* launch on the caller's stream (the one its collectives use) */
 
 /* ---- multi-GPU (st_options.world > 1): one process per GPU shares ONE problem.

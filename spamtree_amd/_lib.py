@@ -91,6 +91,10 @@ SIGNATURES = {
     "st_summary_quantile": (C.c_int, [H, C.c_double, c_dp, c_dp]),
     "st_comm_unique_id": (C.c_int, [C.c_void_p, C.c_int32]),
     "st_comm_init": (C.c_int, [H, C.c_void_p]),
+    "st_points_set": (C.c_int, [H, C.c_int64, c_dp, c_ip, c_ip, c_dp]),
+    "st_points_predict": (C.c_int, [H, C.c_int, c_dp, C.c_uint64, C.c_uint32, c_dp, c_dp, c_dp, c_dp]),
+    "st_points_info": (C.c_int, [H, C.POINTER(C.c_int32), c_ip, c_dp, c_dp]),
+    "st_points_route_name": (C.c_char_p, [C.c_int32]),
 }
 
 

@@ -32,11 +32,14 @@
 #include "factor_lchain.hpp"
 #include "sample_kernels.hpp"
 #include "misc_kernels.hpp"
+#include "predict_points.hpp"
 
 // ===============================================================================================================
 // host side
 // ===============================================================================================================
 static thread_local std::string g_create_error;
+struct st_handle_s;
+static void points_free(st_handle_s *h);
 
 template <typename T>
 struct DevBuf {
@@ -218,6 +221,7 @@ struct st_handle_s {
   size_t pred_lds = 0;
   std::vector<double> xtx;
   std::vector<long long> n_obs_q;
+  struct PointSet *pts = nullptr;             // st_points_set: new locations to predict at (owned)
 
   DevBuf<double> d_cx, d_cy, d_y, d_X, d_w, d_xb, d_z, d_B, d_panels[2], d_acc, d_logdet[2], d_loglik[2], d_scalars, d_partial,
       d_stats, d_scratch, d_tmp_n, d_tsq;
@@ -351,6 +355,7 @@ extern "C" int st_destroy(st_handle h) {
   if (h->pin_up) (void)hipHostFree(h->pin_up);
   for (int i = 0; i < 2; ++i) if (h->ev_up[i]) (void)hipEventDestroy(h->ev_up[i]);
   if (h->ev_factor) (void)hipEventDestroy(h->ev_factor);
+  points_free(h);
   if (h->stream && !h->ext_stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return ST_OK;
@@ -2613,3 +2618,196 @@ extern "C" int st_summary_get(st_handle h, double *w_mean, double *yhat_mean, in
   return ST_OK;
 }
 
+
+// ---- new-point prediction (predict_points.hpp has the model; the kernels and their launcher live in k_predict.hip) ----------
+struct PointSet {
+  long long n = 0;
+  int ntile128 = 0, ntile256 = 0, grid_generic = 0, n_chains = 0;
+  bool has_X = false;
+  long long scratch_stride = 1;
+  double alg_bytes = 0.0, flops = 0.0;
+  int route_mask = 0;
+  DevBuf<double> d_px, d_py, d_X, d_z, d_out, d_scratch;
+  DevBuf<int> d_pmv, d_chain_blk, d_pt_chain, d_gen;
+  DevBuf<long long> d_order;
+  DevBuf<PtChain> d_chains;
+  DevBuf<PtTile> d_tiles;
+  void free() {
+    d_px.free(); d_py.free(); d_X.free(); d_z.free(); d_out.free(); d_scratch.free(); d_pmv.free(); d_chain_blk.free(); d_pt_chain.free();
+    d_gen.free(); d_order.free(); d_chains.free(); d_tiles.free();
+  }
+};
+
+static void points_free(st_handle_s *h) {
+  if (h->pts) { h->pts->free(); delete h->pts; h->pts = nullptr; }
+}
+
+extern "C" int st_points_set(st_handle h, int64_t n_new, const double *coords, const int64_t *mv, const int64_t *anchor, const double *X) {
+  if (!h) return ST_ERR_USAGE;
+  if (h->limited) { h->err = "st_points_set: limited_tree handles are not supported (new-point prediction is out of scope for them)"; return ST_ERR_UNSUPPORTED; }
+  if (h->world > 1) { h->err = "st_points_set: multi-GPU handles (world > 1) are not supported (new-point prediction is out of scope for them)"; return ST_ERR_UNSUPPORTED; }
+  if (n_new < 0 || n_new > (int64_t)INT32_MAX || (n_new > 0 && (!coords || !mv || !anchor))) { h->err = "st_points_set: bad sizes or NULL inputs"; return ST_ERR_USAGE; }
+  for (int64_t i = 0; i < n_new; ++i) {
+    if (anchor[i] < 0 || anchor[i] >= h->n_blocks) { h->err = "st_points_set: anchor " + std::to_string(i) + " is not a block id"; return ST_ERR_USAGE; }
+    if (h->blks[h->blk_model2dev[anchor[i]]].nobs == 0) {
+      h->err = "st_points_set: anchor " + std::to_string(i) + " is a prediction block (no observed rows)"; return ST_ERR_USAGE;
+    }
+    if (mv[i] < 1 || mv[i] > h->q) { h->err = "st_points_set: margin of point " + std::to_string(i) + " is not in 1..q"; return ST_ERR_USAGE; }
+    if (!std::isfinite(coords[i]) || !std::isfinite(coords[n_new + i])) { h->err = "st_points_set: coordinates must be finite"; return ST_ERR_USAGE; }
+  }
+  HCHK(h, hipSetDevice(h->device));
+  points_free(h);
+  PointSet *ps = new PointSet();
+  h->pts = ps;
+  ps->n = n_new;
+  if (n_new == 0) return ST_OK;
+  // conditioning chain of every point: ends at r = the anchor (reference) or its last parent (non-reference)
+  std::vector<int> rdev(n_new);
+  for (int64_t i = 0; i < n_new; ++i) {
+    const int b = h->blk_model2dev[anchor[i]];
+    const Blk &B = h->blks[b];
+    rdev[i] = B.isref ? b : (B.nanc > 0 ? h->anc_idx[B.anc_ptr + B.nanc - 1] : -1);
+  }
+  std::vector<int> keys(rdev);
+  std::sort(keys.begin(), keys.end());
+  keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+  std::vector<PtChain> chains(keys.size());
+  std::vector<int> chain_blk;
+  std::vector<char> gen_chain(keys.size(), 0);
+  const bool lds256 = PP_LDS_BYTES(256) <= h->lds_limit;
+  for (size_t c = 0; c < keys.size(); ++c) {
+    PtChain &C = chains[c];
+    C.first = (int)chain_blk.size(); C.nblk = 0; C.rows = 0; C.pad = 0;
+    if (keys[c] >= 0) {
+      const Blk &R = h->blks[keys[c]];
+      for (int t = 0; t < R.nanc; ++t) chain_blk.push_back(h->anc_idx[R.anc_ptr + t]);
+      chain_blk.push_back(keys[c]);
+      C.nblk = R.nanc + 1;
+      C.rows = R.P + R.m;
+    }
+    gen_chain[c] = h->force_generic || C.rows > 256 || (C.rows > 128 && !lds256) || C.nblk > PP_MAXB;
+  }
+  // sorted order: 128-row chains, then 256-row chains, then the generic route; by chain, then by the caller's index
+  std::vector<int> chain_of(n_new), cls(keys.size());
+  for (size_t c = 0; c < keys.size(); ++c) cls[c] = gen_chain[c] ? 2 : (chains[c].rows <= 128 ? 0 : 1);
+  for (int64_t i = 0; i < n_new; ++i) chain_of[i] = (int)(std::lower_bound(keys.begin(), keys.end(), rdev[i]) - keys.begin());
+  std::vector<long long> order(n_new);
+  for (int64_t i = 0; i < n_new; ++i) order[i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](long long a, long long b) {
+    const int ca = chain_of[a], cb = chain_of[b];
+    return cls[ca] != cls[cb] ? cls[ca] < cls[cb] : ca < cb;
+  });
+  std::vector<int> pt_chain(n_new), gen;
+  std::vector<PtTile> tiles;
+  double bytes = 0.0, flops = 0.0;
+  auto chain_cost = [&](const PtChain &C, double *panel_bytes, double *tri_flops) {
+    double pb = 0.0;
+    long long o = 0;
+    for (int t = 0; t < C.nblk; ++t) { const Blk &A = h->blks[chain_blk[C.first + t]]; o += A.m; pb += (double)A.m * (double)o * 8.0; }
+    *panel_bytes = pb + (double)C.rows * 28.0;                          // stored panels + coordinates, margin, w of the chain rows
+    *tri_flops = (double)C.rows * (double)(C.rows + 1);                  // one lower-triangular product: 2 x rows (rows + 1) / 2
+  };
+  const double per_point_bytes = 2 * 8.0 + 4.0 + 8.0 + 8.0 + 4 * 8.0;   // coordinates, margin, order, z in; mean, var, w, yhat out
+  for (int64_t s = 0; s < n_new;) {
+    const int c = chain_of[order[s]];
+    int64_t e = s;
+    while (e < n_new && chain_of[order[e]] == c) { pt_chain[e] = c; ++e; }
+    double pb, tf;
+    chain_cost(chains[c], &pb, &tf);
+    if (cls[c] == 2) {
+      for (int64_t i = s; i < e; ++i) gen.push_back((int)i);
+      bytes += (double)(e - s) * (pb + per_point_bytes);
+      flops += (double)(e - s) * (2.0 * tf + 4.0 * chains[c].rows);    // v and u per point, then v'v and v'u
+    } else {
+      for (int64_t p0 = s; p0 < e; p0 += PP_NCOL) {
+        PtTile T; T.chain = c; T.p0 = (int)p0; T.np = (int)std::min<int64_t>(PP_NCOL, e - p0); T.pad = 0;
+        tiles.push_back(T);
+        if (cls[c] == 0) ++ps->ntile128; else ++ps->ntile256;
+        bytes += pb;
+        flops += tf + (double)T.np * (tf + 4.0 * chains[c].rows);       // u once per tile, v per point
+      }
+      bytes += (double)(e - s) * per_point_bytes;
+    }
+    s = e;
+  }
+  ps->n_chains = (int)keys.size();
+  ps->alg_bytes = bytes; ps->flops = flops;
+  long long maxrows = 1;
+  for (size_t c = 0; c < keys.size(); ++c) if (gen_chain[c]) maxrows = std::max<long long>(maxrows, chains[c].rows);
+  ps->scratch_stride = (maxrows + 31) & ~31LL;
+  ps->grid_generic = (int)std::min<size_t>(gen.size(), (size_t)4 * h->sm_count);
+  std::vector<double> px(coords, coords + n_new), py(coords + n_new, coords + 2 * n_new);
+  std::vector<int> pmv(n_new);
+  for (int64_t i = 0; i < n_new; ++i) pmv[i] = (int)(mv[i] - 1);
+  if (chain_blk.empty()) chain_blk.push_back(0);
+  if (tiles.empty()) tiles.push_back(PtTile{0, 0, 0, 0});
+  if (gen.empty()) gen.push_back(0);
+  HCHK(h, ps->d_px.upload(px)); HCHK(h, ps->d_py.upload(py)); HCHK(h, ps->d_pmv.upload(pmv));
+  HCHK(h, ps->d_order.upload(order)); HCHK(h, ps->d_pt_chain.upload(pt_chain)); HCHK(h, ps->d_chains.upload(chains));
+  HCHK(h, ps->d_chain_blk.upload(chain_blk)); HCHK(h, ps->d_tiles.upload(tiles)); HCHK(h, ps->d_gen.upload(gen));
+  HCHK(h, ps->d_z.alloc(n_new));
+  HCHK(h, ps->d_out.alloc((size_t)4 * n_new));
+  if (ps->grid_generic > 0) HCHK(h, ps->d_scratch.alloc((size_t)ps->grid_generic * 2 * ps->scratch_stride));
+  if (X) {
+    std::vector<double> xv(X, X + (size_t)n_new * h->p);
+    HCHK(h, ps->d_X.upload(xv));
+    ps->has_X = true;
+  }
+  return ST_OK;
+}
+
+extern "C" int st_points_predict(st_handle h, int mode, const double *z, uint64_t seed, uint32_t iter, double *w_new, double *cond_mean,
+                                 double *cond_var, double *yhat_new) {
+  if (!h) return ST_ERR_USAGE;
+  if (h->limited || h->world > 1) { h->err = "st_points_predict: limited_tree and multi-GPU handles are not supported (out of scope)"; return ST_ERR_UNSUPPORTED; }
+  if (!h->pts) { h->err = "st_points_predict before st_points_set"; return ST_ERR_USAGE; }
+  if (h->theta[0].empty()) { h->err = "st_points_predict before st_factor(slot 0)"; return ST_ERR_USAGE; }
+  if (h->factor_open) { h->err = "st_points_predict between st_factor_enqueue and st_factor_finish"; return ST_ERR_USAGE; }
+  if (mode != 0 && mode != 1) { h->err = "st_points_predict: mode must be 0 (draw) or 1 (conditional mean)"; return ST_ERR_USAGE; }
+  PointSet *ps = h->pts;
+  if (yhat_new && !ps->has_X) { h->err = "st_points_predict: yhat_new needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  ps->route_mask = 0;
+  if (ps->n == 0) return ST_OK;
+  HCHK(h, hipSetDevice(h->device));
+  CovPar cp;
+  int rc = make_covpar(h, h->theta[0].data(), (int)h->theta[0].size(), &cp);
+  if (rc) return rc;
+  const long long n = ps->n;
+  if (z && mode == 0) HCHK(h, hipMemcpyAsync(ps->d_z.p, z, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  double *o = ps->d_out.p;
+  PointsArgs A;
+  std::memset(&A, 0, sizeof(A));
+  A.blks = h->d_blks.p; A.chain_blk = ps->d_chain_blk.p; A.chains = ps->d_chains.p; A.tiles = ps->d_tiles.p; A.ntiles = 0;
+  A.gen_list = ps->d_gen.p; A.ngen = ps->grid_generic > 0 ? (int)(ps->d_gen.n) : 0;
+  A.pt_chain = ps->d_pt_chain.p; A.order = ps->d_order.p; A.px = ps->d_px.p; A.py = ps->d_py.p; A.pmv = ps->d_pmv.p;
+  A.cx = h->d_cx.p; A.cy = h->d_cy.p; A.mv = h->d_mv.p; A.w = h->d_w.p; A.panels = h->d_panels[h->slot_map[0]].p;
+  A.z = (z && mode == 0) ? ps->d_z.p : nullptr; A.seed = seed; A.iter = iter; A.mode = mode;
+  A.X = ps->has_X ? ps->d_X.p : nullptr; A.B = h->d_B.p; A.tsq_inv = h->d_tsq.p; A.p = h->p; A.n_new = n;
+  A.w_new = w_new ? o : nullptr; A.mean = cond_mean ? o + n : nullptr; A.var = cond_var ? o + 2 * n : nullptr;
+  A.yhat = yhat_new ? o + 3 * n : nullptr;
+  A.scratch = ps->d_scratch.p; A.scratch_stride = ps->scratch_stride;
+  PointsLaunch L;
+  L.ntile128 = ps->ntile128; L.ntile256 = ps->ntile256; L.grid_generic = ps->grid_generic;
+  {
+    ProfScope pscope(h, 6);
+    const int e = points_launch(L, A, cp, h->stream, &ps->route_mask);
+    if (e) { h->err = std::string("st_points_predict launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+  }
+  double *dst[4] = {w_new, cond_mean, cond_var, yhat_new};
+  for (int k = 0; k < 4; ++k)
+    if (dst[k]) HCHK(h, hipMemcpyAsync(dst[k], o + (size_t)k * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  return ST_OK;
+}
+
+extern "C" int st_points_info(st_handle h, int32_t *route, int64_t *n_groups, double *alg_bytes, double *flops) {
+  if (!h) return ST_ERR_USAGE;
+  const PointSet *ps = h->pts;
+  if (route) *route = ps ? ps->route_mask : 0;
+  if (n_groups) *n_groups = ps ? ps->n_chains : 0;
+  if (alg_bytes) *alg_bytes = ps ? ps->alg_bytes : 0.0;
+  if (flops) *flops = ps ? ps->flops : 0.0;
+  return ST_OK;
+}
+
+extern "C" const char *st_points_route_name(int32_t code) { return points_route_name(code); }

@@ -307,3 +307,48 @@ class SpamTreeMV:
 
     def synchronize(self):
         self._check(self.lib.st_synchronize(self.h))
+
+    # ---- new-point prediction (include/spamtree_hip.h, st_points_*): not a method of the reference object
+    def set_points(self, coords, mv, anchor, X=None):
+        """New locations to predict at: coords n_new x 2, mv 1-based margins, anchor 0-based block ids
+        (spamtree_amd.predict.locate), X n_new x p regressors or None (then no yhat)."""
+        coords = np.asfortranarray(np.asarray(coords, dtype=np.float64).reshape(-1, 2))
+        n = coords.shape[0]
+        mv = _i64(np.asarray(mv).reshape(-1))
+        anchor = _i64(np.asarray(anchor).reshape(-1))
+        if mv.size != n or anchor.size != n:
+            raise ValueError("coords, mv and anchor must describe the same points")
+        Xf = None
+        if X is not None:
+            Xf = np.asfortranarray(np.asarray(X, dtype=np.float64).reshape(n, self.p))
+        self._check(self.lib.st_points_set(self.h, n, _dp(coords), _ip(mv), _ip(anchor), _dp(Xf) if Xf is not None else None))
+        self.n_points = n
+        self.points_have_X = Xf is not None
+
+    def predict_points(self, mode=0, z=None, seed=0, it=0):
+        """Predictive at the point set on slot 0 and the current w / beta / tausq: dict(w, mean, var, yhat) in the caller's
+        order (yhat None without X).  mode 0 draws (z given, or Philox stream 6), mode 1 gives the conditional mean."""
+        n = self.n_points
+        out = {k: np.zeros(n) for k in ("w", "mean", "var")}
+        out["yhat"] = np.zeros(n) if self.points_have_X else None
+        zz = _f64(np.asarray(z).reshape(-1)) if z is not None else None
+        if zz is not None and zz.size != n:
+            raise ValueError("z must hold one normal per point")
+        self._check(self.lib.st_points_predict(self.h, int(mode), _dp(zz) if zz is not None else None, int(seed), int(it),
+                                               _dp(out["w"]), _dp(out["mean"]), _dp(out["var"]),
+                                               _dp(out["yhat"]) if out["yhat"] is not None else None))
+        return out
+
+    def points_info(self):
+        """Of the last predict_points: dict(routes=[kernel names that ran], n_groups, alg_bytes, flops)."""
+        r = C.c_int32()
+        ng = C.c_int64()
+        by, fl = C.c_double(), C.c_double()
+        self._check(self.lib.st_points_info(self.h, C.byref(r), C.byref(ng), C.byref(by), C.byref(fl)))
+        routes = []
+        code = 1
+        while self.lib.st_points_route_name(code) is not None:
+            if r.value & (1 << (code - 1)):
+                routes.append(self.lib.st_points_route_name(code).decode())
+            code += 1
+        return dict(routes=routes, n_groups=int(ng.value), alg_bytes=float(by.value), flops=float(fl.value))

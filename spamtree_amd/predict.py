@@ -1,0 +1,108 @@
+"""Prediction at new locations from a saved chain, without refitting.
+
+The model defines the predictive of a location that is not a row of the problem through the way it treats NA rows:
+``make_tree`` sends an NA row to the block of its nearest row on the deepest knot level (same margin when
+``cherrypick_same_margin`` is set, ties to the lowest row), and ``predict_std`` draws it from its conditional given the
+reference ancestors on that path.  :func:`locate` is that first step for arbitrary points; :func:`predict_new` replays a
+saved chain draw by draw through ``st_points_predict`` (include/spamtree_hip.h).
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+
+from .model import SpamTreeMV, _dp, _f64
+from .topology import Topology, _nearest_rows
+
+__all__ = ["locate", "conditioning_set", "predict_new"]
+
+
+def locate(topo: Topology, coords_new, mv_new, device: Optional[int] = None) -> np.ndarray:
+    """0-based anchor block of every new point, in the caller's order: the block of the nearest row on the deepest knot
+    level -- the rule ``make_tree`` applies to missing rows, through the same nearest-row search (``device``: on the GPU)."""
+    if topo.knot_level is None:
+        raise ValueError("this topology does not record its deepest knot level (build it with topology.prepare)")
+    coords_new = np.asarray(coords_new, dtype=np.float64).reshape(-1, 2)
+    mv_new = np.asarray(mv_new, dtype=np.int64).reshape(-1)
+    if mv_new.size != coords_new.shape[0]:
+        raise ValueError("coords_new and mv_new must describe the same points")
+    if coords_new.shape[0] == 0:
+        return np.zeros(0, dtype=np.int64)
+    res_row = topo.block_groups[topo.blocking - 1]
+    targets = np.nonzero(res_row == topo.knot_level)[0]           # ascending row ids, as make_tree orders its knots
+    n_marg = int(topo.mv_id.max())
+    nn = _nearest_rows(topo.coords[targets], topo.mv_id[targets] - 1, coords_new, mv_new - 1, n_marg,
+                       topo.cherrypick_same_margin, device)
+    return (topo.blocking[targets[nn]] - 1).astype(np.int64)
+
+
+def conditioning_set(topo: Topology, anchor: int) -> np.ndarray:
+    """Blocks a point anchored at ``anchor`` conditions on: parents(anchor), plus the anchor itself when it is a reference
+    block -- the ancestors of the missing block ``make_tree`` would hang under it."""
+    levels = np.unique(topo.block_groups)
+    rank = int(np.searchsorted(levels, topo.block_groups[anchor]))
+    par = topo.parents(int(anchor))
+    return np.concatenate([par, [int(anchor)]]).astype(np.int64) if topo.res_is_ref[rank] else par.astype(np.int64)
+
+
+def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, return_draws=True, device=0, z=None,
+                mode=0, force_generic=False):
+    """Predictive at new locations for every saved draw of a chain.
+
+    ``model_inputs``: the problem as ``spamtree_mv_mcmc`` took it (the dict of ``synthetic.make_workload``; its ``topo``
+    locates the points).  ``draws``: the dict ``fit.spamtree_mv_mcmc`` returns (``w_mcmc``, ``beta_mcmc``, ``tausq_mcmc``,
+    ``theta_mcmc``).  For saved draw s: st_set_w, st_set_beta, st_set_tausq_inv, st_factor(0, theta_s), st_points_predict
+    with iteration counter s (``z``: n_new x keep caller normals instead of Philox stream 6).
+
+    Returns dict(mean, var) -- the Rao-Blackwellised predictive mean (mean of the conditional means) and variance (mean of
+    the conditional variances + variance of the conditional means) of w -- and, with ``return_draws``, ``w`` and ``yhat``
+    (n_new x keep; yhat only with ``X_new``).  Everything in the caller's order of the points.
+    """
+    mi = model_inputs
+    topo = mi["topo"]
+    coords_new = np.asarray(coords_new, dtype=np.float64).reshape(-1, 2)
+    mv_new = np.asarray(mv_new, dtype=np.int64).reshape(-1)
+    n_new = coords_new.shape[0]
+    anchor = locate(topo, coords_new, mv_new, device=device)
+    w_list = draws["w_mcmc"]
+    keep = len(w_list)
+    p, q = int(mi["p"]), int(mi["q"])
+    beta = np.asarray(draws["beta_mcmc"]).reshape(p, keep, q)
+    tausq = np.asarray(draws["tausq_mcmc"]).reshape(q, keep)
+    theta = np.asarray(draws["theta_mcmc"])
+    theta = theta.reshape(theta.shape[0], keep)
+    if z is not None:
+        z = np.asarray(z, dtype=np.float64).reshape(n_new, keep)
+    m = SpamTreeMV(mi["y"], mi["X"], mi["Z"], mi["coords"], mi["mv_id"], mi["blocking"], mi["gix_block"], mi["res_is_ref"],
+                   mi["parents"], mi["children"], False, mi["block_names"], mi["block_groups"], mi["indexing"],
+                   np.asarray(w_list[0]).reshape(-1), np.zeros(p), theta[:, 0], 1.0 / tausq[0, 0], device=device,
+                   force_generic=force_generic)
+    try:
+        m.set_points(coords_new, mv_new, anchor, X_new)
+        w_out = np.zeros((n_new, keep)) if return_draws else None
+        y_out = np.zeros((n_new, keep)) if (return_draws and X_new is not None) else None
+        cm = np.zeros((n_new, keep))
+        cv = np.zeros((n_new, keep))
+        for s in range(keep):
+            m.set_w(np.asarray(w_list[s]).reshape(-1))
+            m.beta_update(beta[:, s, :])
+            m.tausq_inv = _f64(1.0 / tausq[:, s])
+            m._check(m.lib.st_set_tausq_inv(m.h, _dp(m.tausq_inv)))
+            m.theta_update(0, theta[:, s])
+            if not m.get_loglik_comps_w(0):
+                raise FloatingPointError(f"st_factor failed on saved draw {s} (errtype {m.last_errtype})")
+            out = m.predict_points(mode=mode, z=None if z is None else z[:, s], seed=seed, it=s)
+            cm[:, s] = out["mean"]
+            cv[:, s] = out["var"]
+            if w_out is not None:
+                w_out[:, s] = out["w"]
+            if y_out is not None:
+                y_out[:, s] = out["yhat"]
+        res = dict(mean=cm.mean(axis=1), var=cv.mean(axis=1) + cm.var(axis=1), anchor=anchor, route=m.points_info()["routes"])
+        if return_draws:
+            res["w"] = w_out
+            res["yhat"] = y_out
+        return res
+    finally:
+        m.close()

@@ -3,7 +3,8 @@ Rcpp -- arma::randn, R::runif, R::rgamma; /root/reference/src/spamtree_fit.cpp:2
 spamtree_model.cpp:1378, 1405 -- is not available outside R, so the stream contract is this build's own).
 
 counter = (index_lo, index_hi | outcome, iteration, stream), key = seed.  Streams: 0 sweep normals (generated on
-the device, same contract), 1 theta proposal, 2 MH uniform, 3 gamma, 4 beta normals, 5 yhat noise (device).
+the device, same contract), 1 theta proposal, 2 MH uniform, 3 gamma, 4 beta normals, 5 yhat noise (device), 6 new-point
+normals and 7 new-point yhat noise of st_points_predict (device, index = point in the caller's order).
 """
 import math
 
@@ -67,3 +68,13 @@ class HostRng:
 
     def beta_normals(self, it, j, p):
         return self._normal(np.arange(p), j, it, 4)
+
+    def point_normals(self, it, n):
+        """Stream 6: the normals z of st_points_predict with z = NULL (index = point in the caller's order)."""
+        i = np.arange(n, dtype=np.uint64)
+        return self._normal(i, i >> np.uint64(32), it, 6)
+
+    def point_noise(self, it, n):
+        """Stream 7: the yhat noise of st_points_predict (same index)."""
+        i = np.arange(n, dtype=np.uint64)
+        return self._normal(i, i >> np.uint64(32), it, 7)

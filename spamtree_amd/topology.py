@@ -198,6 +198,8 @@ class TreeResult:
     parchi_map: np.ndarray    # unique root->leaf paths, one column per level, 1-based block ids, 0 = NA
     res_is_ref: np.ndarray    # one flag per level column
     thresholds: list = field(default_factory=list)
+    knot_level: Optional[int] = None        # level ("res") of the deepest knots: missing rows go to the block of the nearest one
+    cherrypick_same_margin: bool = True     # ... of the same margin (when that margin has knots there)
 
 
 def make_tree(coords: np.ndarray, observed: np.ndarray, mv_id: np.ndarray,
@@ -354,7 +356,8 @@ def make_tree(coords: np.ndarray, observed: np.ndarray, mv_id: np.ndarray,
     res_is_ref = np.asarray(res_is_ref_l, dtype=np.int64)
     parchi = _unique_rows(parchi)
     return TreeResult(ix=np.concatenate(all_ix), block=np.concatenate(all_block), res=np.concatenate(all_res),
-                      parchi_map=parchi, res_is_ref=res_is_ref, thresholds=thresholds_list)
+                      parchi_map=parchi, res_is_ref=res_is_ref, thresholds=thresholds_list,
+                      knot_level=int(r_res.max()) if r_res.size else None, cherrypick_same_margin=bool(cherrypick_same_margin))
 
 
 def make_edges(parchimat: np.ndarray, non_empty_blocks: np.ndarray, res_is_ref: np.ndarray):
@@ -467,6 +470,8 @@ class Topology:
     indexing_ptr: np.ndarray
     indexing_idx: np.ndarray
     parchi_map: np.ndarray
+    knot_level: Optional[int] = None        # TreeResult.knot_level: what spamtree_amd.predict.locate anchors new points on
+    cherrypick_same_margin: bool = True
 
     @property
     def n_blocks(self) -> int:
@@ -542,7 +547,8 @@ def prepare(y: np.ndarray, coords: np.ndarray, mv_id: Optional[np.ndarray] = Non
     return Topology(n=n, q=int(np.unique(ms).size), sort_ix=sort_ix, coords=cs, mv_id=ms, blocking=blocking,
                     gix_block=gix_block, res_is_ref=tree.res_is_ref, parents_ptr=pp, parents_idx=pi,
                     children_ptr=cp, children_idx=ci, block_names=block_names, block_groups=block_groups,
-                    indexing_ptr=idx_ptr, indexing_idx=idx, parchi_map=tree.parchi_map)
+                    indexing_ptr=idx_ptr, indexing_idx=idx, parchi_map=tree.parchi_map, knot_level=tree.knot_level,
+                    cherrypick_same_margin=tree.cherrypick_same_margin)
 
 
 def grid_coords(side: int, q: int = 1):
