@@ -12,6 +12,7 @@
  *   stream 5  yhat noise (device)                                    spamtree_fit.cpp:384
  *   stream 6  new-point normals z of st_points_predict (device, index = point in the caller's order)
  *   stream 7  new-point yhat noise of st_points_predict (device, same index)
+ * (st_points_accumulate in stm_mcmc_points draws streams 6 and 7 with iteration counter = saved index, as predict_new.)
  * normal = sqrt(-2 ln u1) cos(2 pi u2), u from 53 bits of two 32-bit words.  Draws are identical for any GPU count.
  */
 #ifndef SPAMTREE_FIT_H
@@ -51,6 +52,27 @@ int spamtree_mv_mcmc_c(const st_problem *pb, const st_options *opt, const double
                        const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn, int mcmc_thin, uint64_t seed,
                        const stm_flags *flags, double *w_mcmc, double *yhat_mcmc, double *beta_mcmc, double *tausq_mcmc,
                        double *theta_mcmc, double *paramsd, double *mcmc_time);
+
+/* New locations predicted during the fit (include/spamtree_hip.h, st_points_*).  stm_points_set: the point set of st_points_set
+ * and room on the device for the first keep_draws saved draws (quantiles; at most 16384, else ST_ERR_UNSUPPORTED).  Call it
+ * before the first iteration.  limited_tree and world > 1 chains are refused (ST_ERR_UNSUPPORTED). */
+int stm_points_set(stm_chain c, int64_t n_new, const double *coords, const int64_t *mv, const int64_t *anchor, const double *X,
+                   int64_t keep_draws);
+/* spamtree_mv_mcmc_c plus prediction at n_new new locations on every saved iteration: after tausq and beta are drawn and before the
+ * next sweep, whatever sample_predicts is, st_points_accumulate(seed, saved index) on the saved theta's factor (slot 0) and the
+ * saved w, beta and tausq.  It consumes no draw of streams 0-5 and changes no chain state: every output of spamtree_mv_mcmc_c is
+ * the same bit for bit.  Inputs as stm_points_set (X_new n_new x p or NULL); quantiles: n_quantiles levels in [0, 1], which need
+ * keep_draws >= 1.  Outputs (column-major, any may be NULL): new_w, new_cond_mean, new_cond_var, new_yhat n_new x keep;
+ * new_mean, new_var, new_w_mean, new_yhat_mean n_new (st_points_summary_get); new_w_q, new_yhat_q n_new x n_quantiles;
+ * new_route st_points_info's route bit set.  Inconsistent requests and every refusal return before the first factorisation. */
+int stm_mcmc_points(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
+                              int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
+                              int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc, double *beta_mcmc,
+                              double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time, int64_t n_new,
+                              const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new, const double *X_new,
+                              int64_t keep_draws, const double *quantiles, int32_t n_quantiles, double *new_w, double *new_cond_mean,
+                              double *new_cond_var, double *new_yhat, double *new_mean, double *new_var, double *new_w_mean,
+                              double *new_yhat_mean, double *new_w_q, double *new_yhat_q, int32_t *new_route);
 
 #ifdef __cplusplus
 }

@@ -237,6 +237,26 @@ int st_points_predict(st_handle h, int mode, const double *z, uint64_t seed, uin
 int st_points_info(st_handle h, int32_t *route, int64_t *n_groups, double *alg_bytes, double *flops);
 const char *st_points_route_name(int32_t code);
 
+/* ---- predictive summaries of the point set over saved iterations, kept on the device (the st_summary_* of the new points).
+ * st_points_accumulate: st_points_predict's draw (mode 0, Philox streams 6 / 7 with counter `iter`) into device buffers, then one
+ *   element-wise update per point, in call order: Welford mean and M2 of the conditional mean, running sums of the conditional
+ *   variance, of w* and of yhat* (with X).  With a reservation it also stores w* and yhat* as row n_accumulated of [keep][n_new].
+ *   Outputs (caller order, n_new each) may be NULL: then nothing is copied to the host and nothing is synchronised.  Changes no
+ *   state of the handle but the point set's.
+ * st_points_summary_reset: zero the summaries and the stored draws (st_points_set starts a new set with none of either).
+ * st_points_summary_reserve: room for the first `keep` draws (at most 16384, else ST_ERR_UNSUPPORTED); 0 releases it.  Resets
+ *   the stored draws.
+ * st_points_summary_get: mean = mean of the conditional means; var = mean of the conditional variances + population variance of the
+ *   conditional means (st_points_predict's Rao-Blackwellised moments); w_mean, yhat_mean = means of the draws.  Any may be NULL.
+ * st_points_summary_quantile: k_qtile over the stored draws (the rule and limit of st_summary_quantile); ST_ERR_USAGE without a
+ *   stored draw or q outside [0, 1].
+ * All refuse limited_tree and world > 1 handles (ST_ERR_UNSUPPORTED) and need st_points_set (ST_ERR_USAGE). */
+int st_points_accumulate(st_handle h, uint64_t seed, uint32_t iter, double *w_new, double *cond_mean, double *cond_var, double *yhat_new);
+int st_points_summary_reset(st_handle h);
+int st_points_summary_reserve(st_handle h, int64_t keep);
+int st_points_summary_get(st_handle h, double *mean, double *var, double *w_mean, double *yhat_mean, int64_t *n_accumulated);
+int st_points_summary_quantile(st_handle h, double q, double *w_q, double *yhat_q);
+
 int st_set_stream(st_handle h, void *stream);              /* launch on the caller's stream (the one its collectives use) */
 
 /* ---- multi-GPU (st_options.world > 1): one process per GPU shares ONE problem.

@@ -95,6 +95,11 @@ SIGNATURES = {
     "st_points_predict": (C.c_int, [H, C.c_int, c_dp, C.c_uint64, C.c_uint32, c_dp, c_dp, c_dp, c_dp]),
     "st_points_info": (C.c_int, [H, C.POINTER(C.c_int32), c_ip, c_dp, c_dp]),
     "st_points_route_name": (C.c_char_p, [C.c_int32]),
+    "st_points_accumulate": (C.c_int, [H, C.c_uint64, C.c_uint32, c_dp, c_dp, c_dp, c_dp]),
+    "st_points_summary_reset": (C.c_int, [H]),
+    "st_points_summary_reserve": (C.c_int, [H, C.c_int64]),
+    "st_points_summary_get": (C.c_int, [H, c_dp, c_dp, c_dp, c_dp, c_ip]),
+    "st_points_summary_quantile": (C.c_int, [H, C.c_double, c_dp, c_dp]),
 }
 
 
@@ -116,6 +121,11 @@ SIGNATURES.update({
     "spamtree_mv_mcmc_c": (C.c_int, [C.POINTER(StProblem), C.POINTER(StOptions), c_dp, c_dp, C.c_int, c_dp, C.c_double,
                                      c_dp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(StmFlags), c_dp, c_dp,
                                      c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "stm_points_set": (C.c_int, [H, C.c_int64, c_dp, c_ip, c_ip, c_dp, C.c_int64]),
+    "stm_mcmc_points": (C.c_int, [C.POINTER(StProblem), C.POINTER(StOptions), c_dp, c_dp, C.c_int, c_dp, C.c_double, c_dp,
+                                  C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(StmFlags), c_dp, c_dp, c_dp, c_dp, c_dp,
+                                  c_dp, c_dp, C.c_int64, c_dp, c_ip, c_ip, c_dp, C.c_int64, c_dp, C.c_int32, c_dp, c_dp,
+                                  c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, C.POINTER(C.c_int32)]),
 })
 
 # include/spamtree_tree.h (device parts of the tree builder)

@@ -290,3 +290,21 @@ struct PointsLaunch {
 };
 int points_launch(const PointsLaunch &L, const PointsArgs &A, const CovPar &cp, hipStream_t st, int *route_mask);
 const char *points_route_name(int code);
+
+// ---- per-point predictive summaries over saved iterations (st_points_accumulate; kernel and launcher in k_points_acc.hip) -----
+// acc holds PA_NACC arrays of n_new doubles, caller order: the Welford mean and M2 of the conditional mean, and the running sums
+// of the conditional variance, the draw w* and yhat*.  One element-wise update per saved iteration, in saved order.
+#define PA_MEAN 0
+#define PA_M2 1
+#define PA_VAR 2
+#define PA_W 3
+#define PA_YHAT 4
+#define PA_NACC 5
+struct PointsAccArgs {
+  const double *w, *mean, *var, *yhat;   // this iteration's outputs of k_points_*, caller order (yhat NULL: no regressors)
+  double *acc;                           // PA_NACC x n
+  double *keep_w, *keep_yhat;            // row of this draw in the [keep][n] stores, or NULL
+  double count;                          // iterations accumulated including this one
+  long long n;
+};
+int points_acc_launch(const PointsAccArgs &A, hipStream_t st);

@@ -392,16 +392,31 @@ extern "C" int stm_state(stm_chain c, double *theta, double *Bcoeff, double *tau
   return ST_OK;
 }
 
-// The whole of spamtree_mv_mcmc (spamtree_fit.cpp:5-430): outputs into caller buffers (column-major):
-// beta_mcmc p x keep x q, tausq_mcmc q x keep, theta_mcmc k x keep, w_mcmc / yhat_mcmc n_all x keep (may be NULL).
-extern "C" int spamtree_mv_mcmc_c(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
-                                  int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
-                                  int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
-                                  double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time) {
-  stm_chain c = nullptr;
-  int rc = stm_create(pb, opt, set_unif_bounds, mcmcsd, theta, ntheta, beta, tausq, seed, flags, &c);
-  if (rc == 0) rc = stm_init(c);
-  if (rc != 0) { stm_destroy(c); return rc; }
+// New locations predicted during the fit (st_points_*): the point set and the summaries' reservation, before any iteration
+extern "C" int stm_points_set(stm_chain c, int64_t n_new, const double *coords, const int64_t *mv, const int64_t *anchor, const double *X,
+                              int64_t keep_draws) {
+  if (!c || !c->h) return ST_ERR_USAGE;
+  int rc = st_points_set(c->h, n_new, coords, mv, anchor, X);
+  if (rc == 0) rc = st_points_summary_reset(c->h);
+  if (rc == 0) rc = st_points_summary_reserve(c->h, keep_draws);
+  if (rc != 0) { c->err = st_last_error(c->h); return rc; }
+  return ST_OK;
+}
+
+namespace {
+struct FitPoints {   // the point set of stm_mcmc_points and where its per-draw outputs go (n_new x keep, any may be NULL)
+  int64_t n;
+  double *w, *cond_mean, *cond_var, *yhat;
+};
+}  // namespace
+
+// The whole of spamtree_mv_mcmc (spamtree_fit.cpp:5-430), on a created chain.  With pts, every saved iteration also predicts at the
+// point set once tausq and beta are drawn: the saved theta's factor in slot 0, the saved w, beta and tausq; draw counter = saved
+// index, Philox streams 6 / 7 only, so the chain itself is the same draw for draw.
+static int run_fit(stm_chain c, int mcmc_keep, int mcmc_burn, int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc,
+                   double *yhat_mcmc, double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
+                   const FitPoints *pts) {
+  int rc = 0;
   const int sample_predicts = flags ? flags->sample_predicts : 1;
   const auto t0 = std::chrono::steady_clock::now();
   const long long mcmc = (long long)mcmc_thin * mcmc_keep + mcmc_burn;
@@ -430,6 +445,12 @@ extern "C" int spamtree_mv_mcmc_c(const st_problem *pb, const st_options *opt, c
       if (theta_mcmc) std::memcpy(theta_mcmc + (size_t)msaved * k, c->param.data(), k * sizeof(double));
       if (w_mcmc) rc = st_get_w(c->h, w_mcmc + (size_t)msaved * n);
       if (!rc && yhat_mcmc) rc = st_yhat(c->h, nullptr, seed, (uint32_t)m, yhat_mcmc + (size_t)msaved * n);
+      if (!rc && pts) {
+        const size_t o = (size_t)msaved * pts->n;
+        auto col = [&](double *a) { return a ? a + o : nullptr; };
+        rc = st_points_accumulate(c->h, seed, (uint32_t)msaved, col(pts->w), col(pts->cond_mean), col(pts->cond_var), col(pts->yhat));
+        if (rc) c->err = st_last_error(c->h);
+      }
       ++msaved;
     }
   }
@@ -437,6 +458,50 @@ extern "C" int spamtree_mv_mcmc_c(const st_problem *pb, const st_options *opt, c
     if (paramsd) std::memcpy(paramsd, c->am.paramsd.data(), (size_t)k * k * sizeof(double));
     if (mcmc_time) *mcmc_time = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   }
+  return rc;
+}
+
+// beta_mcmc p x keep x q, tausq_mcmc q x keep, theta_mcmc k x keep, w_mcmc / yhat_mcmc n_all x keep (may be NULL).
+extern "C" int spamtree_mv_mcmc_c(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
+                                  int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
+                                  int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
+                                  double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time) {
+  stm_chain c = nullptr;
+  int rc = stm_create(pb, opt, set_unif_bounds, mcmcsd, theta, ntheta, beta, tausq, seed, flags, &c);
+  if (rc == 0) rc = stm_init(c);
+  if (rc != 0) { stm_destroy(c); return rc; }
+  rc = run_fit(c, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc, yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time,
+               nullptr);
+  stm_destroy(c);
+  return rc;
+}
+
+extern "C" int stm_mcmc_points(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
+                                         int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
+                                         int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
+                                         double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
+                                         int64_t n_new, const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new,
+                                         const double *X_new, int64_t keep_draws, const double *quantiles, int32_t n_quantiles,
+                                         double *new_w, double *new_cond_mean, double *new_cond_var, double *new_yhat, double *new_mean,
+                                         double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q, double *new_yhat_q,
+                                         int32_t *new_route) {
+  if (n_quantiles < 0 || (n_quantiles > 0 && (!quantiles || keep_draws < 1))) return ST_ERR_USAGE;   // a quantile needs stored draws
+  for (int32_t i = 0; i < n_quantiles; ++i) if (!(quantiles[i] >= 0.0 && quantiles[i] <= 1.0)) return ST_ERR_USAGE;
+  if ((new_yhat || new_yhat_mean || new_yhat_q) && !X_new) return ST_ERR_USAGE;
+  stm_chain c = nullptr;
+  int rc = stm_create(pb, opt, set_unif_bounds, mcmcsd, theta, ntheta, beta, tausq, seed, flags, &c);
+  if (rc == 0) rc = stm_points_set(c, n_new, coords_new, mv_new, anchor_new, X_new, keep_draws);   // refusals: before any factorisation
+  if (rc == 0) rc = stm_init(c);
+  if (rc != 0) { stm_destroy(c); return rc; }
+  const FitPoints pts{n_new, new_w, new_cond_mean, new_cond_var, new_yhat};
+  rc = run_fit(c, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc, yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time,
+               &pts);
+  if (rc == 0 && mcmc_keep > 0 && (new_mean || new_var || new_w_mean || new_yhat_mean))
+    rc = st_points_summary_get(c->h, new_mean, new_var, new_w_mean, new_yhat_mean, nullptr);
+  for (int32_t i = 0; rc == 0 && i < n_quantiles && (new_w_q || new_yhat_q); ++i)
+    rc = st_points_summary_quantile(c->h, quantiles[i], new_w_q ? new_w_q + (size_t)i * n_new : nullptr,
+                                    new_yhat_q ? new_yhat_q + (size_t)i * n_new : nullptr);
+  if (rc == 0 && new_route) rc = st_points_info(c->h, new_route, nullptr, nullptr, nullptr);
   stm_destroy(c);
   return rc;
 }

@@ -2632,9 +2632,12 @@ struct PointSet {
   DevBuf<long long> d_order;
   DevBuf<PtChain> d_chains;
   DevBuf<PtTile> d_tiles;
+  // st_points_accumulate: PA_NACC x n accumulators, and with st_points_summary_reserve the draws themselves, [keep][n] each
+  DevBuf<double> d_acc, d_keep_w, d_keep_yhat;
+  long long n_acc = 0, keep_cap = 0, n_kept = 0;
   void free() {
     d_px.free(); d_py.free(); d_X.free(); d_z.free(); d_out.free(); d_scratch.free(); d_pmv.free(); d_chain_blk.free(); d_pt_chain.free();
-    d_gen.free(); d_order.free(); d_chains.free(); d_tiles.free();
+    d_gen.free(); d_order.free(); d_chains.free(); d_tiles.free(); d_acc.free(); d_keep_w.free(); d_keep_yhat.free();
   }
 };
 
@@ -2756,6 +2759,33 @@ extern "C" int st_points_set(st_handle h, int64_t n_new, const double *coords, c
   return ST_OK;
 }
 
+// launches the k_points_* routes of the point set on slot 0 and the current w / beta / tausq_inv into ps->d_out (w, mean, var,
+// yhat: n doubles each, caller order; out[k] false: that output is not written).  No synchronisation.
+static int points_run(st_handle h, PointSet *ps, int mode, bool use_z, uint64_t seed, uint32_t iter, const bool out[4], const char *who) {
+  CovPar cp;
+  int rc = make_covpar(h, h->theta[0].data(), (int)h->theta[0].size(), &cp);
+  if (rc) return rc;
+  const long long n = ps->n;
+  double *o = ps->d_out.p;
+  PointsArgs A;
+  std::memset(&A, 0, sizeof(A));
+  A.blks = h->d_blks.p; A.chain_blk = ps->d_chain_blk.p; A.chains = ps->d_chains.p; A.tiles = ps->d_tiles.p; A.ntiles = 0;
+  A.gen_list = ps->d_gen.p; A.ngen = ps->grid_generic > 0 ? (int)(ps->d_gen.n) : 0;
+  A.pt_chain = ps->d_pt_chain.p; A.order = ps->d_order.p; A.px = ps->d_px.p; A.py = ps->d_py.p; A.pmv = ps->d_pmv.p;
+  A.cx = h->d_cx.p; A.cy = h->d_cy.p; A.mv = h->d_mv.p; A.w = h->d_w.p; A.panels = h->d_panels[h->slot_map[0]].p;
+  A.z = use_z ? ps->d_z.p : nullptr; A.seed = seed; A.iter = iter; A.mode = mode;
+  A.X = ps->has_X ? ps->d_X.p : nullptr; A.B = h->d_B.p; A.tsq_inv = h->d_tsq.p; A.p = h->p; A.n_new = n;
+  A.w_new = out[0] ? o : nullptr; A.mean = out[1] ? o + n : nullptr; A.var = out[2] ? o + 2 * n : nullptr;
+  A.yhat = out[3] ? o + 3 * n : nullptr;
+  A.scratch = ps->d_scratch.p; A.scratch_stride = ps->scratch_stride;
+  PointsLaunch L;
+  L.ntile128 = ps->ntile128; L.ntile256 = ps->ntile256; L.grid_generic = ps->grid_generic;
+  ProfScope pscope(h, 6);
+  const int e = points_launch(L, A, cp, h->stream, &ps->route_mask);
+  if (e) { h->err = std::string(who) + " launch: " + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+  return ST_OK;
+}
+
 extern "C" int st_points_predict(st_handle h, int mode, const double *z, uint64_t seed, uint32_t iter, double *w_new, double *cond_mean,
                                  double *cond_var, double *yhat_new) {
   if (!h) return ST_ERR_USAGE;
@@ -2769,33 +2799,14 @@ extern "C" int st_points_predict(st_handle h, int mode, const double *z, uint64_
   ps->route_mask = 0;
   if (ps->n == 0) return ST_OK;
   HCHK(h, hipSetDevice(h->device));
-  CovPar cp;
-  int rc = make_covpar(h, h->theta[0].data(), (int)h->theta[0].size(), &cp);
-  if (rc) return rc;
   const long long n = ps->n;
   if (z && mode == 0) HCHK(h, hipMemcpyAsync(ps->d_z.p, z, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  double *o = ps->d_out.p;
-  PointsArgs A;
-  std::memset(&A, 0, sizeof(A));
-  A.blks = h->d_blks.p; A.chain_blk = ps->d_chain_blk.p; A.chains = ps->d_chains.p; A.tiles = ps->d_tiles.p; A.ntiles = 0;
-  A.gen_list = ps->d_gen.p; A.ngen = ps->grid_generic > 0 ? (int)(ps->d_gen.n) : 0;
-  A.pt_chain = ps->d_pt_chain.p; A.order = ps->d_order.p; A.px = ps->d_px.p; A.py = ps->d_py.p; A.pmv = ps->d_pmv.p;
-  A.cx = h->d_cx.p; A.cy = h->d_cy.p; A.mv = h->d_mv.p; A.w = h->d_w.p; A.panels = h->d_panels[h->slot_map[0]].p;
-  A.z = (z && mode == 0) ? ps->d_z.p : nullptr; A.seed = seed; A.iter = iter; A.mode = mode;
-  A.X = ps->has_X ? ps->d_X.p : nullptr; A.B = h->d_B.p; A.tsq_inv = h->d_tsq.p; A.p = h->p; A.n_new = n;
-  A.w_new = w_new ? o : nullptr; A.mean = cond_mean ? o + n : nullptr; A.var = cond_var ? o + 2 * n : nullptr;
-  A.yhat = yhat_new ? o + 3 * n : nullptr;
-  A.scratch = ps->d_scratch.p; A.scratch_stride = ps->scratch_stride;
-  PointsLaunch L;
-  L.ntile128 = ps->ntile128; L.ntile256 = ps->ntile256; L.grid_generic = ps->grid_generic;
-  {
-    ProfScope pscope(h, 6);
-    const int e = points_launch(L, A, cp, h->stream, &ps->route_mask);
-    if (e) { h->err = std::string("st_points_predict launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
-  }
   double *dst[4] = {w_new, cond_mean, cond_var, yhat_new};
+  const bool out[4] = {w_new != nullptr, cond_mean != nullptr, cond_var != nullptr, yhat_new != nullptr};
+  const int rc = points_run(h, ps, mode, z && mode == 0, seed, iter, out, "st_points_predict");
+  if (rc) return rc;
   for (int k = 0; k < 4; ++k)
-    if (dst[k]) HCHK(h, hipMemcpyAsync(dst[k], o + (size_t)k * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (dst[k]) HCHK(h, hipMemcpyAsync(dst[k], ps->d_out.p + (size_t)k * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HCHK(h, hipStreamSynchronize(h->stream));
   return ST_OK;
 }
@@ -2811,3 +2822,133 @@ extern "C" int st_points_info(st_handle h, int32_t *route, int64_t *n_groups, do
 }
 
 extern "C" const char *st_points_route_name(int32_t code) { return points_route_name(code); }
+
+// ---- predictive summaries of the point set over saved iterations (st_points_accumulate; the kernel lives in k_points_acc.hip) ----
+static int points_refuse(st_handle h, const char *who) {
+  if (h->limited || h->world > 1) {
+    h->err = std::string(who) + ": limited_tree and multi-GPU handles are not supported (out of scope)";
+    return ST_ERR_UNSUPPORTED;
+  }
+  if (!h->pts) { h->err = std::string(who) + " before st_points_set"; return ST_ERR_USAGE; }
+  return ST_OK;
+}
+
+extern "C" int st_points_summary_reset(st_handle h) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_summary_reset")) return rc;
+  PointSet *ps = h->pts;
+  HCHK(h, hipSetDevice(h->device));
+  const size_t cnt = (size_t)PA_NACC * ps->n;
+  if (cnt > 0 && !ps->d_acc.p) HCHK(h, ps->d_acc.alloc(cnt));
+  if (cnt > 0) HCHK(h, hipMemsetAsync(ps->d_acc.p, 0, cnt * sizeof(double), h->stream));
+  ps->n_acc = 0; ps->n_kept = 0;
+  return ST_OK;
+}
+
+extern "C" int st_points_summary_reserve(st_handle h, int64_t keep) {
+  if (!h || keep < 0) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_summary_reserve")) return rc;
+  if (keep > 16384) { h->err = "st_points_summary_reserve: at most 16384 saved draws (one point's draws are sorted in one workgroup's LDS)"; return ST_ERR_UNSUPPORTED; }
+  PointSet *ps = h->pts;
+  HCHK(h, hipSetDevice(h->device));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  ps->d_keep_w.free(); ps->d_keep_yhat.free();
+  ps->keep_cap = 0; ps->n_kept = 0;
+  if (keep == 0 || ps->n == 0) return ST_OK;
+  HCHK(h, ps->d_keep_w.alloc((size_t)keep * ps->n));
+  if (ps->has_X) HCHK(h, ps->d_keep_yhat.alloc((size_t)keep * ps->n));
+  ps->keep_cap = keep;
+  return ST_OK;
+}
+
+extern "C" int st_points_accumulate(st_handle h, uint64_t seed, uint32_t iter, double *w_new, double *cond_mean, double *cond_var,
+                                    double *yhat_new) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_accumulate")) return rc;
+  if (h->theta[0].empty()) { h->err = "st_points_accumulate before st_factor(slot 0)"; return ST_ERR_USAGE; }
+  if (h->factor_open) { h->err = "st_points_accumulate between st_factor_enqueue and st_factor_finish"; return ST_ERR_USAGE; }
+  PointSet *ps = h->pts;
+  if (yhat_new && !ps->has_X) { h->err = "st_points_accumulate: yhat_new needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  if (!ps->d_acc.p && ps->n > 0) { const int rc0 = st_points_summary_reset(h); if (rc0) return rc0; }
+  ps->route_mask = 0;
+  if (ps->n == 0) { ps->n_acc += 1; return ST_OK; }
+  HCHK(h, hipSetDevice(h->device));
+  const long long n = ps->n;
+  const bool out[4] = {true, true, true, ps->has_X};
+  int rc = points_run(h, ps, 0, false, seed, iter, out, "st_points_accumulate");
+  if (rc) return rc;
+  const double *o = ps->d_out.p;
+  PointsAccArgs A;
+  A.w = o; A.mean = o + n; A.var = o + 2 * n; A.yhat = ps->has_X ? o + 3 * n : nullptr;
+  A.acc = ps->d_acc.p;
+  const bool keep = ps->n_kept < ps->keep_cap;
+  A.keep_w = keep ? ps->d_keep_w.p + (size_t)ps->n_kept * n : nullptr;
+  A.keep_yhat = (keep && ps->has_X) ? ps->d_keep_yhat.p + (size_t)ps->n_kept * n : nullptr;
+  A.count = (double)(ps->n_acc + 1);
+  A.n = n;
+  {
+    ProfScope pscope(h, 6);
+    const int e = points_acc_launch(A, h->stream);
+    if (e) { h->err = std::string("st_points_accumulate launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+  }
+  ps->n_acc += 1;
+  if (keep) ps->n_kept += 1;
+  double *dst[4] = {w_new, cond_mean, cond_var, yhat_new};
+  bool copied = false;
+  for (int k = 0; k < 4; ++k)
+    if (dst[k]) { HCHK(h, hipMemcpyAsync(dst[k], o + (size_t)k * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream)); copied = true; }
+  if (copied) HCHK(h, hipStreamSynchronize(h->stream));
+  return ST_OK;
+}
+
+extern "C" int st_points_summary_get(st_handle h, double *mean, double *var, double *w_mean, double *yhat_mean, int64_t *n_accumulated) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_summary_get")) return rc;
+  PointSet *ps = h->pts;
+  if (n_accumulated) *n_accumulated = ps->n_acc;
+  if (ps->n_acc == 0) { h->err = "st_points_summary_get: no iteration accumulated"; return ST_ERR_USAGE; }
+  if (yhat_mean && !ps->has_X) { h->err = "st_points_summary_get: yhat_mean needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  const long long n = ps->n;
+  if (n == 0) return ST_OK;
+  HCHK(h, hipSetDevice(h->device));
+  std::vector<double> acc((size_t)PA_NACC * n);
+  HCHK(h, hipMemcpyAsync(acc.data(), ps->d_acc.p, acc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  const double cnt = (double)ps->n_acc;
+  const double *a = acc.data();
+  for (long long i = 0; i < n; ++i) {
+    if (mean) mean[i] = a[PA_MEAN * n + i];
+    if (var) var[i] = a[PA_VAR * n + i] / cnt + a[PA_M2 * n + i] / cnt;   // mean conditional variance + variance of the conditional means
+    if (w_mean) w_mean[i] = a[PA_W * n + i] / cnt;
+    if (yhat_mean) yhat_mean[i] = a[PA_YHAT * n + i] / cnt;
+  }
+  return ST_OK;
+}
+
+extern "C" int st_points_summary_quantile(st_handle h, double q, double *w_q, double *yhat_q) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_summary_quantile")) return rc;
+  if (!(q >= 0.0 && q <= 1.0)) { h->err = "st_points_summary_quantile: q must lie in [0, 1]"; return ST_ERR_USAGE; }
+  PointSet *ps = h->pts;
+  if (ps->n_kept == 0) { h->err = "st_points_summary_quantile: no draw stored (call st_points_summary_reserve before the saved iterations)"; return ST_ERR_USAGE; }
+  if (yhat_q && !ps->has_X) { h->err = "st_points_summary_quantile: yhat_q needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  HCHK(h, hipSetDevice(h->device));
+  const long long n = ps->n;
+  int Kpad = 2;
+  while (Kpad < ps->n_kept) Kpad <<= 1;
+  const int R = std::max(1, std::min(8, (int)(128 * 1024 / ((size_t)Kpad * 8))));
+  const size_t lds = (size_t)R * Kpad * sizeof(double);
+  (void)hipFuncSetAttribute((const void *)k_qtile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_limit);
+  for (int which = 0; which < 2; ++which) {
+    double *dst = which == 0 ? w_q : yhat_q;
+    if (!dst) continue;
+    QtArgs A;
+    A.draws = which == 0 ? ps->d_keep_w.p : ps->d_keep_yhat.p; A.n = n; A.keep = (int)ps->n_kept; A.Kpad = Kpad; A.R = R; A.q = q;
+    A.out = ps->d_out.p;   // scratch: the next st_points_accumulate rewrites it anyway
+    hipLaunchKernelGGL(k_qtile, dim3((unsigned)((n + R - 1) / R)), dim3(NT), lds, h->stream, A);
+    HCHK(h, hipGetLastError());
+    HCHK(h, hipMemcpyAsync(dst, ps->d_out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HCHK(h, hipStreamSynchronize(h->stream));
+  }
+  return ST_OK;
+}

@@ -159,34 +159,118 @@ class Chain:
             pass
 
 
+def _points_inputs(new_points, p, q, new_quantiles):
+    """Checks the point set of spamtree_mv_mcmc(new_points=...) against itself and the problem, before any device call."""
+    pts = dict(new_points)
+    unknown = set(pts) - {"coords", "mv", "anchor", "X"}
+    if unknown:
+        raise ValueError(f"new_points: unknown keys {sorted(unknown)} (coords, mv, anchor, X)")
+    coords = np.asarray(pts["coords"], dtype=np.float64)
+    if coords.ndim != 2 or coords.shape[1] != 2:
+        raise ValueError("new_points: coords must be n_new x 2")
+    n_new = coords.shape[0]
+    mv = np.asarray(pts["mv"])
+    anchor = np.asarray(pts["anchor"])
+    if mv.shape != (n_new,) or anchor.shape != (n_new,):
+        raise ValueError("new_points: mv and anchor must hold one entry per row of coords")
+    if not (np.issubdtype(mv.dtype, np.integer) and np.issubdtype(anchor.dtype, np.integer)):
+        raise ValueError("new_points: mv and anchor must be integers")
+    if n_new and (mv.min() < 1 or mv.max() > q):
+        raise ValueError(f"new_points: mv must lie in 1..{q}")
+    if not np.all(np.isfinite(coords)):
+        raise ValueError("new_points: coords must be finite")
+    X = pts.get("X")
+    if X is not None:
+        X = np.asfortranarray(np.asarray(X, dtype=np.float64))
+        if X.shape != (n_new, p):
+            raise ValueError(f"new_points: X must be n_new x p = {n_new} x {p}")
+    qs = np.asarray(new_quantiles, dtype=np.float64).reshape(-1)
+    if not np.all((qs >= 0.0) & (qs <= 1.0)):
+        raise ValueError("new_quantiles must lie in [0, 1]")
+    return np.asfortranarray(coords), _i64(mv), _i64(anchor), X, qs
+
+
 def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, parents, children, limited_tree,
                      layer_names, layer_gibbs_group, indexing, set_unif_bounds_in, start_w, theta, beta, tausq, mcmcsd,
                      mcmc_keep=100, mcmc_burn=100, mcmc_thin=1, num_threads=1, use_alg="S", adapting=False,
                      main_verbose=True, verbose=False, debug=False, printall=False, sample_beta=True, sample_tausq=True,
-                     sample_theta=True, sample_w=True, sample_predicts=True, seed=2021, device=0, reference_quirks=True):
+                     sample_theta=True, sample_w=True, sample_predicts=True, seed=2021, device=0, reference_quirks=True,
+                     new_points=None, new_draws=True, new_quantiles=(), save_w=True, save_yhat=True, force_generic=False):
     """spamtree_fit.cpp:5-430 through the C++ driver.  `num_threads`, `use_alg`, the verbosity flags and `start_w` are
-    accepted and ignored exactly where the reference ignores them (start_w, :95) or where they do not apply to a GPU."""
+    accepted and ignored exactly where the reference ignores them (start_w, :95) or where they do not apply to a GPU.
+
+    Not in the reference: ``save_w`` / ``save_yhat`` False leave ``w_mcmc`` / ``yhat_mcmc`` out (nothing is copied or
+    allocated for them); ``force_generic`` runs the generic kernels.  ``new_points=dict(coords, mv, anchor, X=None)``
+    (n_new x 2, 1-based margins, 0-based anchor blocks of ``predict.locate``, n_new x p regressors) predicts at those
+    locations on every saved iteration, on the device (stm_mcmc_points); the chain is the same bit for bit.  Then the
+    result also holds ``new``: dict(mean, var, w_mean, yhat_mean, quantiles={q: (w_q, yhat_q)}, route) and, with
+    ``new_draws``, the per-draw n_new x keep arrays ``w``, ``cond_mean``, ``cond_var``, ``yhat`` (yhat entries None
+    without X).  ``new_quantiles`` keeps the draws on the device.  With points, a failure raises SpamTreeError."""
+    if new_points is not None:
+        pts = _points_inputs(new_points, np.asarray(X).shape[1], int(np.unique(_i64(mv_id)).size), new_quantiles)
+    elif len(tuple(new_quantiles)):
+        raise ValueError("new_quantiles needs new_points")
     lib = _lib.load()
     pb, keep, n, p, q = _problem(y, X, coords, mv_id, res_is_ref, parents, children, layer_names, layer_gibbs_group, indexing)
     theta = _f64(theta)
     k = theta.size
     bounds = np.asfortranarray(np.asarray(set_unif_bounds_in, dtype=np.float64))
     sd = np.asfortranarray(np.asarray(mcmcsd, dtype=np.float64))
-    opt = _lib.StOptions(int(device), int(bool(reference_quirks)), 0, 1, 0, 2 if limited_tree else 0)
+    opt = _lib.StOptions(int(device), int(bool(reference_quirks)), 0, 1, int(bool(force_generic)), 2 if limited_tree else 0)
     fl = _lib.StmFlags(int(adapting), int(sample_beta), int(sample_tausq), int(sample_theta), int(sample_w), int(sample_predicts))
-    w_all = np.zeros((n, mcmc_keep), order="F"); yh_all = np.zeros((n, mcmc_keep), order="F")
+    w_all = np.zeros((n, mcmc_keep), order="F") if save_w else None
+    yh_all = np.zeros((n, mcmc_keep), order="F") if save_yhat else None
     beta_mcmc = np.zeros((p, mcmc_keep, q), order="F"); tausq_mcmc = np.zeros((q, mcmc_keep), order="F")
     theta_mcmc = np.zeros((k, mcmc_keep), order="F"); paramsd = np.zeros((k, k), order="F")
     t = C.c_double()
-    rc = lib.spamtree_mv_mcmc_c(C.byref(pb), C.byref(opt), _dp(bounds), _dp(theta), k, _dp(_f64(beta)), float(tausq), _dp(sd),
-                                int(mcmc_keep), int(mcmc_burn), int(mcmc_thin), int(seed), C.byref(fl), _dp(w_all), _dp(yh_all),
-                                _dp(beta_mcmc), _dp(tausq_mcmc), _dp(theta_mcmc), _dp(paramsd), C.byref(t))
+    dp = lambda a: _dp(a) if a is not None else None   # noqa: E731
+    common = (C.byref(pb), C.byref(opt), _dp(bounds), _dp(theta), k, _dp(_f64(beta)), float(tausq), _dp(sd), int(mcmc_keep),
+              int(mcmc_burn), int(mcmc_thin), int(seed), C.byref(fl), dp(w_all), dp(yh_all), _dp(beta_mcmc), _dp(tausq_mcmc),
+              _dp(theta_mcmc), _dp(paramsd), C.byref(t))
+    new = None
+    if new_points is None:
+        rc = lib.spamtree_mv_mcmc_c(*common)
+    else:
+        pc, pmv, pan, pX, qs = pts
+        n_new = pc.shape[0]
+        draws = {key: np.zeros((n_new, mcmc_keep), order="F") if new_draws else None for key in ("w", "cond_mean", "cond_var")}
+        draws["yhat"] = np.zeros((n_new, mcmc_keep), order="F") if (new_draws and pX is not None) else None
+        summ = {key: np.zeros(n_new) for key in ("mean", "var", "w_mean")}
+        summ["yhat_mean"] = np.zeros(n_new) if pX is not None else None
+        wq = np.zeros((n_new, qs.size), order="F")
+        yq = np.zeros((n_new, qs.size), order="F") if pX is not None else None
+        route = C.c_int32()
+        rc = lib.stm_mcmc_points(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), int(mcmc_keep) if qs.size else 0,
+                                 _dp(qs), int(qs.size), dp(draws["w"]), dp(draws["cond_mean"]), dp(draws["cond_var"]),
+                                 dp(draws["yhat"]), dp(summ["mean"]), dp(summ["var"]), dp(summ["w_mean"]),
+                                 dp(summ["yhat_mean"]), dp(wq if qs.size else None), dp(yq if qs.size else None),
+                                 C.byref(route))
+        if rc == 0:
+            names, code = [], 1
+            while lib.st_points_route_name(code) is not None:
+                if route.value & (1 << (code - 1)):
+                    names.append(lib.st_points_route_name(code).decode())
+                code += 1
+            new = dict(summ, route=names,
+                       quantiles={float(x): (wq[:, i].copy(), None if yq is None else yq[:, i].copy()) for i, x in enumerate(qs)})
+            if new_draws:
+                new.update(draws)
     if rc == -10:
         raise FloatingPointError("At nan loglik: error.")
+    if rc != 0 and new_points is not None:
+        err = SpamTreeError(f"stm_mcmc_points failed ({rc})")
+        err.code = rc
+        raise err
     if rc != 0:
         if main_verbose:
             print("MCMC has been interrupted.")
         return {"None": np.zeros(0)}
-    return dict(w_mcmc=[w_all[:, i].reshape(-1, 1).copy() for i in range(mcmc_keep)],
-                yhat_mcmc=[yh_all[:, i].reshape(-1, 1).copy() for i in range(mcmc_keep)], beta_mcmc=beta_mcmc,
-                tausq_mcmc=tausq_mcmc, theta_mcmc=theta_mcmc, paramsd=paramsd, mcmc_time=t.value)
+    out = {}
+    if save_w:
+        out["w_mcmc"] = [w_all[:, i].reshape(-1, 1).copy() for i in range(mcmc_keep)]
+    if save_yhat:
+        out["yhat_mcmc"] = [yh_all[:, i].reshape(-1, 1).copy() for i in range(mcmc_keep)]
+    out.update(beta_mcmc=beta_mcmc, tausq_mcmc=tausq_mcmc, theta_mcmc=theta_mcmc, paramsd=paramsd, mcmc_time=t.value)
+    if new is not None:
+        out["new"] = new
+    return out

@@ -4,7 +4,8 @@ The model defines the predictive of a location that is not a row of the problem 
 ``make_tree`` sends an NA row to the block of its nearest row on the deepest knot level (same margin when
 ``cherrypick_same_margin`` is set, ties to the lowest row), and ``predict_std`` draws it from its conditional given the
 reference ancestors on that path.  :func:`locate` is that first step for arbitrary points; :func:`predict_new` replays a
-saved chain draw by draw through ``st_points_predict`` (include/spamtree_hip.h).
+saved chain draw by draw through ``st_points_predict`` (include/spamtree_hip.h); :func:`fit_predict` predicts during the
+fit instead, on every saved iteration, with the summaries kept on the device (``st_points_accumulate``).
 """
 from __future__ import annotations
 
@@ -12,10 +13,11 @@ from typing import Optional
 
 import numpy as np
 
+from . import fit
 from .model import SpamTreeMV, _dp, _f64
 from .topology import Topology, _nearest_rows
 
-__all__ = ["locate", "conditioning_set", "predict_new"]
+__all__ = ["locate", "conditioning_set", "predict_new", "fit_predict"]
 
 
 def locate(topo: Topology, coords_new, mv_new, device: Optional[int] = None) -> np.ndarray:
@@ -47,7 +49,7 @@ def conditioning_set(topo: Topology, anchor: int) -> np.ndarray:
 
 
 def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, return_draws=True, device=0, z=None,
-                mode=0, force_generic=False):
+                mode=0, force_generic=False, return_moments=False):
     """Predictive at new locations for every saved draw of a chain.
 
     ``model_inputs``: the problem as ``spamtree_mv_mcmc`` took it (the dict of ``synthetic.make_workload``; its ``topo``
@@ -57,7 +59,8 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
 
     Returns dict(mean, var) -- the Rao-Blackwellised predictive mean (mean of the conditional means) and variance (mean of
     the conditional variances + variance of the conditional means) of w -- and, with ``return_draws``, ``w`` and ``yhat``
-    (n_new x keep; yhat only with ``X_new``).  Everything in the caller's order of the points.
+    (n_new x keep; yhat only with ``X_new``); with ``return_moments`` also the per-draw ``cond_mean`` and ``cond_var``
+    (n_new x keep).  Everything in the caller's order of the points.
     """
     mi = model_inputs
     topo = mi["topo"]
@@ -103,6 +106,45 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
         if return_draws:
             res["w"] = w_out
             res["yhat"] = y_out
+        if return_moments:
+            res["cond_mean"] = cm
+            res["cond_var"] = cv
         return res
     finally:
         m.close()
+
+
+def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), return_draws=True, **mcmc):
+    """Fit the chain and predict at new locations on every saved iteration, without replaying it.
+
+    ``model_inputs``: the problem as for :func:`predict_new`.  The points are located with :func:`locate` and handed to
+    ``fit.spamtree_mv_mcmc(new_points=...)``; ``mcmc`` takes its keyword arguments (start values default to the workload's
+    ``theta``, beta 0, tausq 0.1 and mcmcsd 0.01 I).  Each saved draw s is the one :func:`predict_new` gives for that draw
+    with ``seed`` = the chain's seed, and the chain is the same as without points.
+
+    Returns the fit's dict plus ``new``: ``mean``, ``var`` (Rao-Blackwellised, as :func:`predict_new`), ``anchor``, ``route``,
+    ``w_mean``, ``yhat_mean`` and ``quantiles[q] = (w_q, yhat_q)`` from the device summaries, and with ``return_draws`` the
+    n_new x keep draws ``w``, ``yhat`` and the per-draw ``cond_mean``, ``cond_var``.  yhat entries are None without ``X_new``.
+    """
+    mi = model_inputs
+    coords_new = np.asarray(coords_new, dtype=np.float64).reshape(-1, 2)
+    mv_new = np.asarray(mv_new, dtype=np.int64).reshape(-1)
+    if mv_new.size != coords_new.shape[0]:
+        raise ValueError("coords_new and mv_new must describe the same points")
+    if X_new is not None and np.asarray(X_new).shape != (coords_new.shape[0], int(mi["p"])):
+        raise ValueError("X_new must be n_new x p")
+    qs = tuple(float(x) for x in quantiles)
+    if not all(0.0 <= x <= 1.0 for x in qs):
+        raise ValueError("quantiles must lie in [0, 1]")
+    anchor = locate(mi["topo"], coords_new, mv_new, device=mcmc.get("device", 0))
+    theta = np.asarray(mcmc.pop("theta", mi["theta"]), dtype=np.float64)
+    kw = dict(set_unif_bounds_in=mi["bounds"], start_w=np.zeros((int(mi["n"]), 1)), theta=theta, beta=np.zeros(int(mi["p"])),
+              tausq=0.1, mcmcsd=0.01 * np.eye(theta.size))
+    kw.update(mcmc)
+    out = fit.spamtree_mv_mcmc(mi["y"], mi["X"], mi["Z"], mi["coords"], mi["mv_id"], mi["blocking"], mi["gix_block"],
+                               mi["res_is_ref"], mi["parents"], mi["children"], bool(mi.get("limited_tree", False)),
+                               mi["block_names"], mi["block_groups"], mi["indexing"],
+                               new_points=dict(coords=coords_new, mv=mv_new, anchor=anchor, X=X_new), new_draws=return_draws,
+                               new_quantiles=qs, **kw)
+    out["new"]["anchor"] = anchor
+    return out
