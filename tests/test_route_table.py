@@ -9,32 +9,13 @@ from tests import test_gpu_routes as R
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "spamtree_amd", "csrc", "spamtree_hip.hip")
 
-# launched kernels that other tests compare with the oracle (or, for plumbing, check bit for bit)
+# launched kernels without a route code that other tests compare with the oracle (or, for plumbing, check bit for bit);
+# every route-coded kernel is reached by a row of the route table instead (test_every_route_coded_kernel_is_in_the_table)
 COVERED_ELSEWHERE = {
     "k_xb": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
-    "k_marginal_invchol_wave": "tests/test_limited_tree.py::test_limited_tree_parity",
-    "k_marginal_invchol": "tests/test_limited_tree.py::test_limited_tree_parity",
-    "k_factor<false, MODE_FACTOR>": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
-    "k_factor<true, MODE_FACTOR>": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
-    "k_factor<false, MODE_PREDICT>": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
-    "k_factor<true, MODE_PREDICT>": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
-    "k_factor_mfma": "tests/test_gpu_deep.py::test_config5_chains_201_to_256_on_k_factor_mfma",
-    "k_factor_lchain<96>": "tests/test_gpu_deep.py::test_config4_chains_bigmfma_second_pass",
-    "k_factor_lchain<136>": "tests/test_gpu_deep.py::test_config4_chains_bigmfma_second_pass",
-    "k_factor_ref_finish": "tests/test_gpu_deep.py::test_config4_reference_levels_on_lchain_and_ref_finish",
-    "k_lchain_scalars": "tests/test_gpu_deep.py::test_config4_chains_bigmfma_second_pass",
-    "k_factor_wide<WG_JT>": "tests/test_gpu_deep.py::test_config4_chains_bigmfma_second_pass",
-    "k_factor_bigmfma<3, 5, 34>": "tests/test_gpu_deep.py::test_config4_chains_bigmfma_second_pass",
-    "k_factor_bigmfma<4, 5, 34>": "tests/test_gpu_deep.py::test_config4_chains_bigmfma_second_pass",
-    "k_factor_bigmfma<5, 3, 24>": "tests/test_gpu_deep.py::test_config4_chains_bigmfma_second_pass",
     "k_merge_err": "tests/test_gpu_chain.py::test_cpp_driver_with_top_levels_ahead_of_time",
     "k_pack_comps": "tests/test_gpu_sharded.py::test_sharded_equals_single_process_bitwise",
     "k_normals": "tests/test_gpu_parity.py::test_generated_sweep_normals_are_the_documented_stream",
-    "k_gram_big": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
-    "k_sample<true, false>": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
-    "k_sample_leaf_wide": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
-    "k_sample<true, true>": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
-    "k_sample<false>": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
     "k_pack_w": "tests/test_gpu_sharded.py::test_sharded_equals_single_process_bitwise",
     "k_gather_pack": "tests/test_gpu_sharded.py::test_sharded_equals_single_process_bitwise",
     "k_gather_unpack": "tests/test_gpu_sharded.py::test_sharded_equals_single_process_bitwise",
@@ -77,7 +58,7 @@ def launched_kernels():
 
 def table_routes():
     names = set()
-    for row in R.ROUTES:
+    for row in R.ROUTES + R.WIDE_ROUTES:
         for v in row["routes"].values():
             names.update(v)
     for v in R.CONFIG2_ROUTES.values():
@@ -112,19 +93,36 @@ def test_route_table_reaches_the_quad_instantiations():
     assert {R.quad(50, True, True), R.quad(50, True, False)} <= set(R.EXCLUDED)
 
 
-def test_route_names_spell_launched_instantiations():
-    """st_route_name (host code only, no device needed) spells every route code as a launched instantiation."""
+def route_names():
+    """Every name st_route_name spells (host code only, no device needed), in route-code order."""
     from spamtree_amd import build, _lib
     build.build()          # (a fresh checkout: the library may not be built yet)
     lib = _lib.load()
-    launched = launched_kernels()
     assert lib.st_route_name(0) == b""
     names, code = [], 1
     while lib.st_route_name(code) is not None:
         names.append(lib.st_route_name(code).decode())
         code += 1
+    return names
+
+
+def test_route_names_spell_launched_instantiations():
+    """st_route_name spells every route code as a launched instantiation."""
+    launched = launched_kernels()
+    names = route_names()
     assert len(names) == len(set(names))
     assert set(names) <= launched, sorted(set(names) - launched)
     # every instantiation of the per-level phases has a route code
     per_level = {n for n in launched if n.startswith(("k_factor", "k_marginal", "k_lchain", "k_gram", "k_sample"))}
     assert per_level <= set(names), sorted(per_level - set(names))
+
+
+def test_every_route_coded_kernel_is_in_the_table():
+    """A kernel with a route code is reached by a row of the route table (which proves it ran, through st_route_info, before
+    comparing with the oracle) or excluded there with its reason -- never only mapped to a test that does not look at routes."""
+    names = set(route_names())
+    table = table_routes()
+    assert not names & set(COVERED_ELSEWHERE), sorted(names & set(COVERED_ELSEWHERE))
+    missing = sorted(n for n in names if n not in table and n not in R.EXCLUDED)
+    assert not missing, f"route-coded but in no row of the route table: {missing}"
+    assert not set(R.EXCLUDED) & table, sorted(set(R.EXCLUDED) & table)
