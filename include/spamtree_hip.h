@@ -162,6 +162,9 @@ int st_algorithmic_bytes(st_handle h, double *out5, double *flops3);
  * bytes, `bytes` per buffer, best of `reps`), out3[1] = FP64 MFMA TFLOP/s (v_mfma_f64_16x16x4_f64), out3[2] = FP64 FMA TFLOP/s
  * (v_fma_f64).  About 0.15 s. */
 int st_probe_peaks(int device, int64_t bytes, int reps, double *out3);
+/* the covariance kernels' elementary functions (csrc/st_device.hpp), evaluated on the device through the same inlined helpers
+ * (csrc/probe.hip; no handle needed): out[i] = f(x[i]), f = cov_sqrt (fn 0), cov_exp (1), cov_exp_tab (2). */
+int st_probe_math(int32_t fn, const double *x, int64_t n, int32_t device, double *out);
 /* per-kernel-family device time from HIP events recorded on the launch stream around every launch (enable=1), or around
  * the phase-A launches only (enable=2: the roofline measurement at a third of the event traffic; ~60 event records per
  * iteration cost 4-6 % of the iteration at n = 1e6).  Events are harvested lazily: no host synchronisation is added.

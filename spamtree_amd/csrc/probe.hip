@@ -1,11 +1,13 @@
 // Box-measured peaks for the roofline report (bench.py `roofline.peak_measured`; BASELINE.md section 3 asks for a stream-copy
 // and an FP64 FMA / MFMA peak measured on the box next to the vendor figures).  Not on the product path: three self-contained
-// kernels timed with HIP events on a private stream, about 50 ms each.
+// kernels timed with HIP events on a private stream, about 50 ms each.  Also st_probe_math: the covariance kernels' elementary
+// functions evaluated through the very helpers they inline (tests/test_gpu_device_math.py).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "spamtree_hip.h"
+#include "st_device.hpp"
 
 namespace {
 
@@ -65,6 +67,18 @@ __global__ __launch_bounds__(512) void k_probe_fma(double *out, int iters) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) s += x[i];
   out[(size_t)blockIdx.x * blockDim.x + threadIdx.x] = s;
+}
+
+// out[i] = f(x[i]) for f = cov_sqrt (fn 0), cov_exp (1), cov_exp_tab over EXP2_64 copied to LDS as k_factor_quad does (2)
+__global__ __launch_bounds__(256) void k_probe_math(int fn, const double *__restrict__ x, long long n, double *__restrict__ out) {
+  __shared__ double tab[64];
+  if (threadIdx.x < 64) tab[threadIdx.x] = EXP2_64[threadIdx.x];
+  __syncthreads();
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const double v = x[i];
+    out[i] = fn == 0 ? cov_sqrt(v) : fn == 1 ? cov_exp(v) : cov_exp_tab(v, tab);
+  }
 }
 
 #define PCHK(call)                          \
@@ -131,5 +145,24 @@ done:
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
   if (st) (void)hipStreamDestroy(st);
+  return rc;
+}
+
+extern "C" int st_probe_math(int32_t fn, const double *x, int64_t n, int32_t device, double *out) {
+  if (fn < 0 || fn > 2 || n < 0 || (n > 0 && (!x || !out))) return ST_ERR_USAGE;
+  if (n == 0) return ST_OK;
+  int rc = ST_OK;
+  double *dx = nullptr, *dy = nullptr;
+  const size_t bytes = (size_t)n * sizeof(double);
+  if (hipSetDevice(device) != hipSuccess || hipMalloc(&dx, bytes) != hipSuccess || hipMalloc(&dy, bytes) != hipSuccess ||
+      hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    rc = ST_ERR_HIP;
+  } else {
+    const long long nb = std::min<long long>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_probe_math, dim3((unsigned)nb), dim3(256), 0, 0, (int)fn, (const double *)dx, (long long)n, dy);
+    if (hipGetLastError() != hipSuccess || hipMemcpy(out, dy, bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = ST_ERR_HIP;
+  }
+  if (dx) (void)hipFree(dx);
+  if (dy) (void)hipFree(dy);
   return rc;
 }

@@ -389,6 +389,14 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
   if (pb->q < 1 || pb->q > QMAX) { g_create_error = "q out of range"; return ST_ERR_UNSUPPORTED; }
   if (pb->p < 1 || pb->p > 8) { g_create_error = "p must be in 1..8"; return ST_ERR_UNSUPPORTED; }
   if (opt && (opt->world < 1 || opt->rank < 0 || opt->rank >= opt->world || opt->world > 64)) { g_create_error = "bad rank/world"; return ST_ERR_USAGE; }
+  // the covariance helpers map a NaN distance to a covariance of 0 (cov_exp clamps with fmax), so a non-finite coordinate
+  // would factorise silently instead of failing
+  if (pb->n_all > 0 && !pb->coords) { g_create_error = "st_create: coords is NULL"; return ST_ERR_USAGE; }
+  for (int64_t i = 0; i < 2 * pb->n_all; ++i)
+    if (!std::isfinite(pb->coords[i])) {
+      g_create_error = "st_create: coordinates must be finite (row " + std::to_string(i % pb->n_all) + ")";
+      return ST_ERR_USAGE;
+    }
   st_handle_s *h = new st_handle_s();
   h->rank = opt ? opt->rank : 0;
   h->world = opt ? opt->world : 1;

@@ -50,31 +50,34 @@ struct Blk {
 // exp(x) for the covariance kernels: two-step Cody-Waite reduction to |r| <= ln2/2, degree-13 Taylor polynomial in
 // Estrin form (truncation error < 5e-18; short dependency chains, no register copies), v_ldexp_f64 for the scaling
 // (overflow -> inf, underflow -> denormals / 0 as in libm).  Under half the instructions of the library routine;
-// relative error < 3e-16.
+// relative error < 3e-16 (2.3e-16 measured, tests/test_gpu_device_math.py): the polynomial sums e^r - 1 = r + r^2 (...)
+// and adds the leading 1 last, so only that final add rounds at the result's scale.  A scheme that forms 1 + r first and
+// then adds the higher terms with three fmas rounds four times at that scale and reaches 4e-16.
 __device__ __forceinline__ double cov_exp(double x) {
   x = fmax(x, -1500.0);
   const double t = __builtin_rint(x * 1.44269504088896338700e+00);
   double r = fma(t, -6.93147180369123816490e-01, x);
   r = fma(t, -1.90821492927058770002e-10, r);
   const double r2 = r * r, r4 = r2 * r2, r8 = r4 * r4;
-  const double a0 = 1.0 + r;
   const double a1 = fma(1.6666666666666666e-01, r, 0.5);                         // 1/3!, 1/2!
   const double a2 = fma(8.3333333333333332e-03, r, 4.1666666666666664e-02);      // 1/5!, 1/4!
   const double a3 = fma(1.9841269841269841e-04, r, 1.3888888888888889e-03);      // 1/7!, 1/6!
   const double a4 = fma(2.7557319223985893e-06, r, 2.4801587301587302e-05);      // 1/9!, 1/8!
   const double a5 = fma(2.5052108385441720e-08, r, 2.7557319223985888e-07);      // 1/11!, 1/10!
   const double a6 = fma(1.6059043836821613e-10, r, 2.0876756987868100e-09);      // 1/13!, 1/12!
-  const double b0 = fma(a1, r2, a0), b1 = fma(a3, r2, a2), b2 = fma(a5, r2, a4);
+  const double b0 = fma(a1, r2, r), b1 = fma(a3, r2, a2), b2 = fma(a5, r2, a4);
   const double d0 = fma(b1, r4, b0), d1 = fma(a6, r4, b2);
-  const double p = fma(d1, r8, d0);
+  const double p = 1.0 + fma(d1, r8, d0);                                         // e^r - 1 (|.| < 0.42), then the 1
   return __builtin_ldexp(p, (int)t);   // |t| < 2^31 after the clamp above, or +huge -> saturating conversion -> inf
 }
 
 // exp(x) with a 64-entry table of 2^(j/64) (in LDS: EXP2_64 copied by the kernel), for the covariance pass of k_factor_quad,
 // which runs at the FP64 pipe's issue rate (44 FP64 instructions per entry, 4 cycles each, stamps of round 3): the reduced
-// argument is |r| <= ln2/128, so a degree-5 polynomial is exact to 3.5e-17 and the whole exponential costs 16 FP64
+// argument is |r| <= ln2/128, so a degree-5 polynomial is exact to 3.5e-17 and the whole exponential costs 15 FP64
 // instructions + one LDS read instead of 24.  x = t ln2/64 + r, t = 64 k + j: exp(x) = 2^k 2^(j/64) e^r.  Relative error
-// < 3e-16 (the table entries are correctly rounded); over- / underflow as cov_exp.
+// < 3e-16 (2.3e-16 measured): the table entries are correctly rounded, and the result is T + T (e^r - 1) in one fma.
+// Forming p = 1 + r + ... first and then the product p T would round twice more and reach 4e-16.  Over- / underflow as
+// cov_exp.
 __device__ const double EXP2_64[64] = {
   0x1.0000000000000p+0, 0x1.02c9a3e778061p+0, 0x1.059b0d3158574p+0, 0x1.0874518759bc8p+0,
   0x1.0b5586cf9890fp+0, 0x1.0e3ec32d3d1a2p+0, 0x1.11301d0125b51p+0, 0x1.1429aaea92de0p+0,
@@ -101,20 +104,22 @@ __device__ __forceinline__ double cov_exp_tab(double x, const double *tab) {
   const int ti = (int)t;
   const double T = tab[ti & 63];
   const double r2 = r * r;
-  const double a0 = 1.0 + r;
   const double a1 = fma(1.6666666666666666e-01, r, 0.5);
   const double a2 = fma(8.3333333333333332e-03, r, 4.1666666666666664e-02);
-  const double p = fma(fma(a2, r2, a1), r2, a0);
-  return __builtin_ldexp(p * T, ti >> 6);
+  const double p = fma(fma(a2, r2, a1), r2, r);                                  // e^r - 1
+  return __builtin_ldexp(fma(T, p, T), ti >> 6);
 }
 
 // sqrt(a) for squared distances (a >= 0): v_rsq_f64 seed (relative error 5e-8 on gfx950, measured), one coupled Goldschmidt
-// step (4e-15) and ONE residual correction, after which the result is the correctly rounded square root for every one of 2^20
-// random arguments in [1e-8, 2] (round 3 probe; the library's scheme adds a second correction, which changed nothing).  a is
-// clamped to 1e-300 from below, so coincident points give 1e-150 instead of 0 (exp(-phi * 1e-150) == 1 exactly); squared
-// distances above ~1e300 are outside the contract.
+// step (4e-15) and ONE residual correction, after which the result is the correctly rounded square root of max(a, 1e-270):
+// bitwise equal to sqrt over every binade from 2^-996 to 2^996, the grid distances of config #3 and the clamp
+// (tests/test_gpu_device_math.py).  The residual a - g^2 (~2^-47 a) must not be subnormal, or it loses the low bits the
+// correction needs: with the clamp at 1e-300 (~2^-997), 13 arguments of that sweep from 2^-994 up came out an ulp off, with
+// one correction or two.  Scaling such arguments (as the library does) cost 1 % of config #3; the clamp at 1e-270 (~2^-897)
+// costs nothing, and below it only coincident points are affected: they give 1e-135 instead of 0, and exp(-phi * 1e-135) == 1
+// exactly for every phi of the bounds, as exp(-phi * 1e-150) was.  Squared distances above ~1e300 are outside the contract.
 __device__ __forceinline__ double cov_sqrt(double a) {
-  a = fmax(a, 1e-300);
+  a = fmax(a, 1e-270);
   const double y = __builtin_amdgcn_rsq(a);
   double g = a * y, h = 0.5 * y;
   const double r = fma(-h, g, 0.5);

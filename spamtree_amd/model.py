@@ -220,9 +220,10 @@ class SpamTreeMV:
         return out
 
     # ---- inspection for parity tests
-    def block(self, slot, u):
+    def block(self, slot, u, raw=False):
         """(H, Ri) of block u: H = K_{u,pa} K_{pa,pa}^{-1} (m x P) recovered from the stored panel, Ri = chol(R)^{-1}
-        (m x m) for a reference block or the m per-row values 1/sqrt(r_ii) for a non-reference block."""
+        (m x m) for a reference block or the m per-row values 1/sqrt(r_ii) for a non-reference block.  raw=True: (N, Ri)
+        with N = -Ri H (m x P) the stored panel itself, without the solve that recovers H."""
         m, P = C.c_int64(), C.c_int64()
         isref, nobs = C.c_int32(), C.c_int32()
         self._check(self.lib.st_block_dims(self.h, u, C.byref(m), C.byref(P), C.byref(isref), C.byref(nobs)))
@@ -233,6 +234,9 @@ class SpamTreeMV:
         N = N[: m * P].reshape(P, m).T if P else np.zeros((m, 0))
         if isref.value:
             Ri = Ri.reshape(m, m).T
+        if raw:
+            return N, Ri
+        if isref.value:
             H = -np.linalg.solve(Ri, N) if P else N
         else:
             H = -N / Ri[:, None] if P else N

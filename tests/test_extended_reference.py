@@ -1,0 +1,172 @@
+"""CPU: the extended-precision per-block reference (oracle/extended.py) that judges the kernels at ill-conditioned theta.
+
+It is checked against mpmath at 50 digits on small blocks, against the float64 oracle where that oracle is accurate
+(nice_theta), and it shows that the oracle itself loses digits as phi falls, which is why the GPU conditioning tests
+(tests/test_gpu_conditioning.py) need it.
+"""
+import types
+
+import numpy as np
+import pytest
+
+from oracle.extended import LD, ExtendedBlocks, covariance
+from tests.util import make_problem, nice_theta, oracle_model
+
+
+def relerr(a, b):
+    a = np.asarray(a, dtype=LD)
+    b = np.asarray(b, dtype=LD)
+    return float(np.abs(a - b).max() / np.abs(b).max())
+
+
+def tiny_tree(q, nloc=(8, 4, 2), seed=3):
+    """Three blocks in a chain: a root of nloc[0] locations, a reference child of nloc[1] and a non-reference grandchild of
+    nloc[2] (every location carries all q outcomes).  Only the fields ExtendedBlocks reads."""
+    rng = np.random.default_rng(seed)
+    ix, rows, mv, coords = [], 0, [], []
+    for k in nloc:
+        pts = rng.uniform(size=(k, 2))
+        ix.append(np.arange(rows, rows + k * q))
+        rows += k * q
+        coords.append(np.tile(pts, (q, 1)))
+        mv.append(np.repeat(np.arange(1, q + 1), k))
+    parents = [np.zeros(0, dtype=np.int64), np.array([0]), np.array([0, 1])]
+    om = types.SimpleNamespace(
+        q=q, coords=np.vstack(coords), mv_id=np.concatenate(mv), indexing=ix,
+        parents=parents, children=[np.array([1]), np.array([2]), np.zeros(0, dtype=np.int64)],
+        parents_indexing=[np.zeros(0, dtype=np.int64), ix[0], np.concatenate([ix[0], ix[1]])],
+        block_groups=np.array([1.0, 2.0, 3.0]), res_is_ref=np.array([1, 1, 0]), limited_tree=False)
+    return om
+
+
+def mp_covariance(om, theta, i1, i2):
+    import mpmath as mp
+    q = om.q
+    K = mp.matrix(len(i1), len(i2))
+    if q > 1:
+        from oracle.extended import unpack_theta
+        ai1, ai2, phi, tmv, D = unpack_theta(theta, q)
+    for a, r in enumerate(i1):
+        for b, s in enumerate(i2):
+            h = mp.sqrt((mp.mpf(om.coords[r, 0]) - mp.mpf(om.coords[s, 0])) ** 2 +
+                        (mp.mpf(om.coords[r, 1]) - mp.mpf(om.coords[s, 1])) ** 2)
+            if q == 1:
+                K[a, b] = mp.mpf(theta[0]) * mp.exp(-mp.mpf(theta[3]) * h)
+                continue
+            vi, vj = om.mv_id[r] - 1, om.mv_id[s] - 1
+            v = mp.mpf(D[vi, vj])
+            if q > 2:
+                psi = (mp.mpf(tmv[0]) * v + 1) ** mp.mpf(tmv[1])          # (a v + 1)^beta
+                cb = mp.exp(-mp.mpf(tmv[2]) * h / mp.sqrt(psi)) / psi
+            else:
+                cb = mp.exp(-mp.mpf(tmv[0]) * h / mp.sqrt(v + 1)) / (v + 1)
+            if v == 0:
+                K[a, b] = mp.mpf(ai1[vi]) ** 2 * cb + mp.mpf(ai2[vi]) ** 2 * mp.exp(-mp.mpf(phi[vi]) * h)
+            else:
+                K[a, b] = mp.mpf(ai1[vi]) * mp.mpf(ai1[vj]) * cb
+    return K
+
+
+def mp_block(om, theta, u):
+    import mpmath as mp
+    iu, pa = om.indexing[u], om.parents_indexing[u]
+    Kuu = mp_covariance(om, theta, iu, iu)
+    H = mp_covariance(om, theta, iu, pa) * mp.inverse(mp_covariance(om, theta, pa, pa)) if pa.size else None
+    R = Kuu - H * mp_covariance(om, theta, pa, iu) if pa.size else Kuu
+    if om.res_is_ref[u] or not pa.size:
+        Ri = mp.inverse(mp.cholesky(R))
+        diag = [Ri[i, i] for i in range(iu.size)]
+        N = -Ri * H if pa.size else None
+    else:
+        diag = [1 / mp.sqrt(R[i, i]) for i in range(iu.size)]
+        Ri = None
+        N = mp.matrix([[-diag[i] * H[i, j] for j in range(pa.size)] for i in range(iu.size)])
+    return dict(Ri=Ri, N=N, diag=diag, logdet=mp.fsum(mp.log(d) for d in diag))
+
+
+def as_ld(M):
+    return np.array([[LD(str(M[i, j])) for j in range(M.cols)] for i in range(M.rows)], dtype=LD)
+
+
+@pytest.mark.parametrize("q,theta", [(1, np.array([2.3, 1.0, 1.0, 6.0])), (1, np.array([2.3, 1.0, 1.0, 0.3])),
+                                     (3, nice_theta(3))], ids=["q1_phi6", "q1_phi0.3", "q3_nice"])
+def test_blocks_match_mpmath(q, theta):
+    import mpmath as mp
+    om = tiny_tree(q, nloc=(8, 4, 2) if q == 1 else (6, 2, 2))
+    ex = ExtendedBlocks(om, theta)
+    with mp.workdps(50):
+        for u in range(3):
+            assert om.indexing[u].size <= 18 and om.parents_indexing[u].size <= 24
+            ref = mp_block(om, theta, u)
+            b = ex.block(u)
+            diag = np.diag(b["Ri"]) if b["isref"] else b["d"]
+            assert relerr(diag, np.array([LD(str(d)) for d in ref["diag"]])) <= 1e-17, u
+            if ref["Ri"] is not None:
+                assert relerr(b["Ri"], as_ld(ref["Ri"])) <= 1e-17, u
+            if ref["N"] is not None:
+                assert relerr(b["N"], as_ld(ref["N"])) <= 1e-17, u
+            lref = LD(str(ref["logdet"]))
+            assert abs(b["logdet"] - lref) <= 1e-17 * max(1, abs(lref)), u
+
+
+def test_ag10_entries_match_mpmath():
+    """The long-double Apanasovich-Genton entries against 50-digit values: the inputs of man/CrossCovarianceAG10.Rd (q = 2,
+    the set test_oracle_identities.test_cross_covariance_ag10_mpmath uses) and nice_theta(3)."""
+    import mpmath as mp
+    xl = np.linspace(0.0, 1.0, 10)
+    g = np.array([(a, b) for b in xl for a in xl])
+    th2 = np.array([1.0, 1.5, 0.1, 0.51, 1.0, 2.0, 5.0, 1.0])      # ai1, ai2, phi_i, thetamv, Dvec
+    rng = np.random.default_rng(1)
+    for q, theta, pts in ((2, th2, g), (3, nice_theta(3), rng.uniform(size=(30, 2)))):
+        om = types.SimpleNamespace(q=q, coords=np.tile(pts, (q, 1)), mv_id=np.repeat(np.arange(1, q + 1), pts.shape[0]))
+        n = om.coords.shape[0]
+        i1, i2 = rng.integers(0, n, 40), rng.integers(0, n, 40)
+        K = covariance(om.coords, om.mv_id - 1, theta, q, i1, i2)
+        with mp.workdps(50):
+            Km = as_ld(mp_covariance(om, theta, i1, i2))
+        assert relerr(K, Km) <= 1e-17, q
+
+
+def oracle_vs_extended(pb, theta, w):
+    """Max relative errors of the float64 oracle's Ri and panel N over the reference blocks, and its logdet error (nats)."""
+    om = oracle_model(pb, theta=theta, w=w)
+    assert om.get_loglik_comps_w(om.param_data)
+    pd = om.param_data
+    ex = ExtendedBlocks(om, theta)
+    eRi = eN = 0.0
+    ld = LD(0)
+    for u in range(om.n_blocks):
+        if om.block_ct_obs[u] == 0:
+            continue
+        b = ex.block(u)
+        ld += b["logdet"]
+        if not b["isref"]:
+            continue
+        eRi = max(eRi, relerr(pd.Rcc_invchol[u], b["Ri"]))
+        if b["P"]:
+            eN = max(eN, relerr(-pd.Rcc_invchol[u] @ pd.w_cond_mean_K[u], b["N"]))
+    return eRi, eN, float(abs(ld - LD(pd.logdetCi)))
+
+
+def test_oracle_agrees_at_nice_theta():
+    w = np.random.default_rng(0).standard_normal(625)
+    pb = make_problem(side=25, q=1, seed=11, missing=0.1)
+    eRi, eN, eld = oracle_vs_extended(pb, pb["theta"], w)
+    assert eRi <= 1e-13 and eN <= 1e-13 and eld <= 1e-13 * 625, (eRi, eN, eld)
+    pb = make_problem(side=9, q=3, seed=11)
+    eRi, eN, eld = oracle_vs_extended(pb, pb["theta"], np.zeros(pb["n"]))
+    assert eRi <= 1e-13 and eN <= 1e-13 and eld <= 1e-13 * pb["n"], (eRi, eN, eld)
+
+
+def test_oracle_loses_digits_as_phi_falls():
+    """make_problem(side=25, q=1, seed=11), sigma^2 = 2.3: the float64 oracle's error against the extended reference grows as
+    phi falls (measured: Ri 7e-15 / 6e-12 / 4e-10 / 1.3e-6 at phi = 6 / 0.5 / 0.05 / 1e-3), so at the bottom of the bounds
+    the suite's REL = 1e-9 against the oracle says nothing about a kernel."""
+    pb = make_problem(side=25, q=1, seed=11)
+    w = np.random.default_rng(0).standard_normal(pb["n"])
+    errs = [oracle_vs_extended(pb, np.array([2.3, 1.0, 1.0, phi]), w) for phi in (6.0, 0.5, 0.05, 1e-3)]
+    for k in range(2):                       # Ri, N: monotone in phi
+        col = [e[k] for e in errs]
+        assert all(a < b for a, b in zip(col, col[1:])), (k, col)
+    assert errs[0][0] < 1e-13 and errs[-1][0] > 1e-8 and errs[-1][1] > 1e-8, errs
+    assert errs[-1][2] > 1e2 * errs[0][2], errs
