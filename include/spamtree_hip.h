@@ -72,7 +72,9 @@ typedef struct st_options {
                                   per accepted theta -- identical values
                                   bit 1: limited_tree = TRUE (spamtree_fit.cpp:20, spamtree_model.cpp:901-903, 1275-1278):
                                   parents(u) is the single parent of make_edges_limited (tree_dep.cpp:133-186), children(u)
-                                  the direct children, and Kxx_inv(u) = inv_sympd(K_uu); sharded like full trees since round 3                  */
+                                  the direct children, and Kxx_inv(u) = inv_sympd(K_uu); sharded like full trees since round 3
+                                  bit 2: st_factor_enqueue(1, ...) factorises the quad leaf levels in full; default 0 defers
+                                  their panels' T to the first reader of the slot (see st_factor_enqueue) -- identical results */
 } st_options;
 
 /* ---- lifetime: SpamTreeMV::SpamTreeMV (spamtree_model.cpp:8-192) incl. init_indexing/init_finalize/init_model_data */
@@ -96,6 +98,10 @@ int st_factor(st_handle h, int slot, const double *theta, int ntheta, double *lo
  * touch the slot -- the C++ driver draws tausq / beta from the sweep's statistics and uploads them (st_tausq_stats, st_beta_stats,
  * st_set_tausq_inv, st_set_beta: none of them waits for the main stream), so that the Metropolis step's host round trip
  * (src/spamtree_fit.cpp:232-262, then :308-330) is the only one of the iteration.  No st_swap / st_sample_w* in between. */
+/* On slot 1 (one GPU, st_options.reserved bit 2 clear) the quad leaf levels compute V = Linv_pa K_pa,j and the log-density
+ * only; their panel rows [-r_j T_j | r_j] are finished from the stored V by the first call that reads the slot's panels --
+ * st_swap (before it swaps), st_get_block, st_loglik_w / st_loglik_local, st_sample_w_loglik(_begin) -- on the launch
+ * stream, bit-identical to st_factor's.  Re-factorising the slot (st_factor*, st_factor_begin) drops the deferred half. */
 int st_factor_enqueue(st_handle h, int slot, const double *theta, int ntheta);
 int st_factor_is_async(st_handle h);   /* 1: _enqueue really starts the work (one GPU, no communicator) */
 int st_factor_finish(st_handle h, double *loglik);

@@ -46,7 +46,22 @@ struct QuadArgs {
   int predict;     // leaf instantiations: phase P (spamtree_model.cpp:1296-1326) -- draw w_j = H_j w_pa + sqrt(max(K_jj - H_j K_pa,j, 0)) z_j
   const double *z; // ... from these normals (device order), into w_out; nothing else is written
   double *w_out;
+  int mode;        // leaf levels: QM_FULL / QM_VONLY / QM_TFROMV (reference levels: QM_FULL)
+  double *vscr;    // QM_VONLY / QM_TFROMV: the V tiles, [quad][vtiles][wave][4][64] (C layout, one 16 x 16 tile per wave)
+  int vtiles;      // tiles per quad: 2 private sub-panels + 2 per step of the shared chain
 };
+
+// Leaf levels only (QuadArgs::mode).  QM_FULL: everything.  QM_VONLY (a proposal's leaf level): V = Linv K, the
+// log-density terms and the V tiles into A.vscr -- no T, no panel rows.  QM_TFROMV (after the proposal is accepted): the
+// chain staged as in QM_FULL, V taken from A.vscr, T += V' Linv and the panel rows -- no covariance pass, no log-density
+// terms.  Both halves walk the tiles in QM_FULL's order with QM_FULL's arithmetic: the same bits as one QM_FULL launch.
+// A workgroup-uniform argument of the leaf instantiation, not a template parameter: every launched instantiation is one
+// of the route table's (tests/test_route_table.py).  The three modes share ONE register allocation, so the split modes
+// keep nothing live in QM_FULL's main loop beyond what QM_FULL holds: QM_TFROMV's V tiles sit in kx, QM_VONLY's go out
+// as soon as they are formed.  No instantiation spills (NKX 50: 256 VGPRs); occupancy is bound by LDS (one workgroup per
+// CU) at every NKX, so the larger allocation of the smaller instantiations costs no waves.
+enum { QM_FULL = 0, QM_VONLY = 1, QM_TFROMV = 2 };
+__host__ __device__ constexpr int quad_vtiles(int nkx) { return 2 + 2 * ((4 * nkx + 31) / 32); }
 
 #define RFL(x) __builtin_amdgcn_readfirstlane(x)
 
@@ -79,6 +94,8 @@ __device__ __forceinline__ void dma_row(const double *src, double *dst, int Kb, 
 template <int NU, int NKX, int NKT, bool ISREF, bool WCH = true>
 __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar cp) {
   constexpr int NTQ = 128 * NU, NW = 2 * NU;
+  static_assert(NU >= 2, "s_g overlays two rows of s_e2");
+  const int QM = ISREF ? QM_FULL : RFL(A.mode);
   // covariance scratch ([KH][64] doubles per wave, lane-private slots): reference levels keep it in the SECOND staging buffer
   // (4 passes), leaf levels behind the arena (KH = 5: 20 KB), so that the first panel rows can travel by LDS-DMA UNDER the
   // covariance pass instead of after it
@@ -106,6 +123,10 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
   __shared__ double s_cvr[QMAX * QMAX], s_cva[QMAX * QMAX], s_cva2[QMAX * QMAX], s_cvp[QMAX];
   __shared__ int s_rlen[PMAX];          // chain row c: its length (entries up to and including its own ancestor's rows) ...
   __shared__ long long s_rsrc[PMAX];    // ... and where it starts in the panel arena
+  // leaf units: g = Linv_pa w_pa, one entry per staged chain row, for the residual r_j (w_j - V_j' g).  Overlays: s_e2 is
+  // written after the main loop only, s_hv is a reference-level array (and phase P's, also after the main loop)
+  double (*s_g)[32] = s_e2;    // [step buffer][row of the step]
+  double (*s_gp)[32] = s_hv;   // [unit][row of the private ancestor]
 
   const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, l4 = lane >> 4, ttid = tid & 127;
   const int wid = RFL(tid >> 6), u = wid >> 1, jt = (wid & 1) ^ ((wid >> 2) & 1);   // waves w, w + 4 share a SIMD: one jt = 0 (it also has the off-diagonal Schur tile) and one jt = 1 each
@@ -267,7 +288,7 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
   // unit u], in a rolled loop (one covariance body per pass) through lane-private LDS slots, then picks them up with
   // static register indices.  No barrier: nobody else touches the slots.
   double kx[NKX];
-  {
+  if (QM != QM_TFROMV) {
     const int jc = jt * 16 + l15;
     const bool cok = jc < Mu;
     const double mx = s_colx[u][jc], my = s_coly[u][jc];
@@ -329,6 +350,29 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
   for (int n = 0; n < NKT; ++n) tacc[n] = (d4){0.0, 0.0, 0.0, 0.0};
   d4 rown = (d4){0.0, 0.0, 0.0, 0.0}, rcross = rown;   // Schur tiles (jt, jt), (1, 0)
   double dacc = 0.0;                                   // leaf units: sum_k V[k][column l15]^2 (this lane's rows)
+  double hacc = 0.0;                                   // leaf units: sum_k V[k][column l15] g[k] (this lane's rows)
+  // split modes: tile t of this wave in the V scratch (coalesced: 512 bytes per register and wave; streamed past the caches)
+  const size_t vq0 = ((size_t)qidx * A.vtiles * NW + wid) * 256;   // (uniform: the lane is added at the access)
+  auto vstore = [&](int t, const d4 &p) __attribute__((always_inline)) {
+    double *d = A.vscr + (vq0 + (size_t)t * (NW * 256)) + lane;
+    __builtin_nontemporal_store(p[0], d); __builtin_nontemporal_store(p[1], d + 64);
+    __builtin_nontemporal_store(p[2], d + 128); __builtin_nontemporal_store(p[3], d + 192);
+  };
+  auto vload = [&](int t) __attribute__((always_inline)) {
+    const double *d = A.vscr + (vq0 + (size_t)t * (NW * 256)) + lane;
+    return (d4){__builtin_nontemporal_load(d), __builtin_nontemporal_load(d + 64), __builtin_nontemporal_load(d + 128),
+                __builtin_nontemporal_load(d + 192)};
+  };
+  // g of one staged row per group of NS consecutive lanes (sub = lane % NS; one accumulator per lane, the group's sum complete
+  // in each of its lanes)
+  auto grow = [&](const double *row, int len, int wlim, const double *pw, int sub, auto ns) __attribute__((always_inline)) {
+    constexpr int NS = decltype(ns)::value;
+    double s = 0.0;
+    for (int k = sub; k < len; k += NS) s = fma(row[k], k < wlim ? s_wpa[k] : pw[k - wlim], s);
+#pragma unroll
+    for (int o = NS >> 1; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+    return s;
+  };
 
 #define QMFMA(a_, b_, c_) c_ = __builtin_amdgcn_mfma_f64_16x16x4f64(a_, b_, c_, 0, 0, 0)
   // One 16-row tile of the step (rows at tg, nk = ceil(rows / 4) K-steps of the T update, row length KbT): V = Linv K for
@@ -339,9 +383,11 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
   // jt = 0 wave forms the Schur tile (1, 0) = V_1' V_0 from it and its own tile, still in registers.
   // rmask >= 0 (private sub-panels packed without padding rows): V rows >= rmask are forced to zero (what the tile holds there
   // belongs to the next unit: finite, but not ours).
-  auto tile = [&](const double *tg, int nk, int KbT, int slot, int rmask) __attribute__((always_inline)) {
+  // gt: g of the tile's 16 rows (leaf units); pv: the V tile itself (QM_TFROMV); tix: the tile's index in the V scratch.
+  auto tile = [&](const double *tg, int nk, int KbT, int slot, int rmask, const double *gt, d4 pv, int tix) __attribute__((always_inline)) {
     d4 p = (d4){0.0, 0.0, 0.0, 0.0};
-    if (wact) {
+    if (QM == QM_TFROMV) p = pv;
+    else if (wact) {
       const int ns = (KbT + 3) >> 2;
       const double *ap = tg + l15 * ldS + l4;   // rows beyond the step's last are zero (staging)
 #pragma unroll
@@ -369,30 +415,38 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
       }
     }
     if (wact) {
-      // T[column][chain k] += V' Linv: A = the V tile (C layout read as A: contraction over the tile's rows), B from LDS
-      const double *b0 = tg + l4 * ldS + l15;
+      if (QM != QM_VONLY) {
+        // T[column][chain k] += V' Linv: A = the V tile (C layout read as A: contraction over the tile's rows), B from LDS
+        const double *b0 = tg + l4 * ldS + l15;
 #pragma unroll
-      for (int n = 0; n < NKT; ++n) {
-        if (n * 16 >= KbT) break;
-        const double x0 = b0[16 * n], x1 = b0[4 * ldS + 16 * n], x2 = b0[8 * ldS + 16 * n], x3 = b0[12 * ldS + 16 * n];
-        QMFMA(p[0], x0, tacc[n]);
-        if (nk > 1) QMFMA(p[1], x1, tacc[n]);
-        if (nk > 2) QMFMA(p[2], x2, tacc[n]);
-        if (nk > 3) QMFMA(p[3], x3, tacc[n]);
+        for (int n = 0; n < NKT; ++n) {
+          if (n * 16 >= KbT) break;
+          const double x0 = b0[16 * n], x1 = b0[4 * ldS + 16 * n], x2 = b0[8 * ldS + 16 * n], x3 = b0[12 * ldS + 16 * n];
+          QMFMA(p[0], x0, tacc[n]);
+          if (nk > 1) QMFMA(p[1], x1, tacc[n]);
+          if (nk > 2) QMFMA(p[2], x2, tacc[n]);
+          if (nk > 3) QMFMA(p[3], x3, tacc[n]);
+        }
       }
-      if (isref) {
+      if constexpr (ISREF) {
         QMFMA(p[0], p[0], rown); QMFMA(p[1], p[1], rown); QMFMA(p[2], p[2], rown); QMFMA(p[3], p[3], rown);
       } else {
-        dacc += p[0] * p[0] + p[1] * p[1] + p[2] * p[2] + p[3] * p[3];
+        // explicit fma chains: the same bits in every mode, whatever the compiler would contract
+        dacc = fma(p[3], p[3], fma(p[2], p[2], fma(p[1], p[1], fma(p[0], p[0], dacc))));
+        if (QM != QM_TFROMV) hacc = fma(p[3], gt[l4 + 12], fma(p[2], gt[l4 + 8], fma(p[1], gt[l4 + 4], fma(p[0], gt[l4], hacc))));
       }
     }
+    // QM_VONLY: the tile goes out at once (held any longer, across the next tile's MFMAs, it would push K operands of
+    // QM_FULL's main loop into scratch: the three modes share one register allocation)
+    if (!ISREF && QM == QM_VONLY && wact) vstore(tix, p);
   };
   // one step (sr <= 32 rows of Linv staged at stg with stride ldS; Kb / KbA: length of the longest row of the step / of its
   // first tile -- shorter when the step straddles ancestors; columns up to Kb + 24 are zero beyond a row's own length).
   // Called by every wave of the workgroup (barriers inside for reference units); sr is the same for all of them.
-  auto compute = [&](const double *stg, int sr, int Kb, int KbA) __attribute__((always_inline)) {
-    tile(stg, (min(sr, 16) + 3) >> 2, KbA, 0, -1);
-    if (sr > 16) tile(stg + 16 * ldS, (sr - 16 + 3) >> 2, Kb, 1, -1);
+  // gs: g of the step's 32 rows; pA / pB: the step's V tiles (QM_TFROMV); tix: the index of its first tile
+  auto compute = [&](const double *stg, int sr, int Kb, int KbA, const double *gs, const d4 &pA, const d4 &pB, int tix) __attribute__((always_inline)) {
+    tile(stg, (min(sr, 16) + 3) >> 2, KbA, 0, -1, gs, pA, tix);
+    if (sr > 16) tile(stg + 16 * ldS, (sr - 16 + 3) >> 2, Kb, 1, -1, gs + 16, pB, tix + 1);
   };
 
   // ---- private (last) ancestors (leaf quads): every unit's sub-panel staged side by side (LDS-DMA), all waves busy.
@@ -400,6 +454,14 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
   // rows per unit, is packed WITHOUT padding rows into rows [0, 48): rows [48, 64) then take the first step of the shared
   // chain (<= 16 rows: 175 chain rows = 5 x 32 + 15), requested when the matrix cores start on sub-panel 1.
   bool pf = false;   // the shared chain's first step sits at row 48 (workgroup-uniform)
+  // QM_TFROMV keeps the V tiles it has requested in kx (no covariance pass: free), QM_VONLY the ones it has yet to store in
+  // tacc[0..1] (no T: free) -- the three modes share one register budget, QM_FULL's
+  auto kget = [&](int o) __attribute__((always_inline)) { return (d4){kx[o], kx[o + 1], kx[o + 2], kx[o + 3]}; };
+  auto kset = [&](int o, const d4 &v) __attribute__((always_inline)) { kx[o] = v[0]; kx[o + 1] = v[1]; kx[o + 2] = v[2]; kx[o + 3] = v[3]; };
+  if (QM == QM_TFROMV && wact && pmmax > 0) {   // both private tiles requested at once, long before they are needed
+    if (priv_rows(0) > 0) kset(16, vload(0));
+    if (pmmax > 16 && priv_rows(1) > 0) kset(20, vload(1));
+  }
   if constexpr (!ISREF) if (pmmax > 0) {
     const int ts1 = pmmax > 16 ? pmmax >> 1 : 0;                      // rows of sub-panel 1, longest unit
     const bool tight = ts1 > 0 && ts1 <= 12;
@@ -418,10 +480,19 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
           if (row < sr && lane < 24) buf[(size_t)row * ldS + p_Kb + lane] = 0.0;
           if (row >= sr && stride == 16) for (int k = lane; k < p_Kb + 24; k += 64) buf[(size_t)row * ldS + k] = 0.0;   // absent rows of the tile
         }
+        const int r0 = sp == 0 ? 0 : p_sr0;
+        if (QM != QM_TFROMV) {   // g of the rows this wave staged, 8 lanes per row (zero for absent rows: they meet V rows of zeros)
+          const int row = jt + 2 * (lane >> 3);
+          double gv = 0.0;
+          if (row < sr) gv = grow(buf + (size_t)row * ldS, p_Kb, Pc, s_pw[u], lane & 7, std::integral_constant<int, 8>());
+          if ((lane & 7) == 0) s_gp[u][r0 + row] = gv;
+        }
         lds_barrier();
         if (sp == 1 && pf) issue(0, arena + (size_t)48 * ldS);
         // (row i of the sub-panel is chain row Pc + r0 + i of a LOWER-TRIANGULAR factor: nothing beyond column Pc + r0 + sr)
-        if (sr > 0) tile(buf, (sr + 3) >> 2, min(p_Kb, Pc + (sp == 0 ? 0 : p_sr0) + sr), 0, sr);
+        if (sr > 0) {
+          tile(buf, (sr + 3) >> 2, min(p_Kb, Pc + r0 + sr), 0, sr, &s_gp[u][r0], kget(16 + 4 * sp), sp);
+        }
         lds_barrier();
       }
     }
@@ -436,6 +507,9 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
   {
     if constexpr (!ISREF) { if (nit > 0 && !pf) issue(0, arena); }   // (reference quads: requested before the covariance pass)
     int cur = pf ? 1 : 0;
+    // QM_TFROMV: the V tiles of step i + 1 are requested when step i starts -- this step's in kx[0..7], the next step's in
+    // kx[8..15] (no covariance pass: free registers); QM_VONLY stores each tile as soon as it is formed (tile)
+    if (QM == QM_TFROMV && wact && nit > 0) { kset(0, vload(2)); if (Pc - 32 * (nit - 1) > 16) kset(4, vload(3)); }
     for (int i = 0; i < nit; ++i) {
       const int c0 = 32 * (nit - 1 - i), sr = min(32, Pc - c0);
       const int kb_v = s_rlen[c0 + sr - 1], kba_v = s_rlen[c0 + min(sr, 16) - 1];   // (both reads in flight together)
@@ -455,23 +529,36 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
           for (int k = lane; k < Kb + 24; k += 64) buf[(size_t)row * ldS + k] = 0.0;   // absent rows of a tile in use (first step only)
         }
       }
+      if (!ISREF && QM != QM_TFROMV) {   // g of the rows this wave staged, 64 / RP lanes per row (zero for absent rows)
+        constexpr int NS = 64 / RP;
+        const int rq = lane / NS, row = wid + NW * rq;
+        int len = rlen_cur[0];
+#pragma unroll
+        for (int rr = 1; rr < RP; ++rr) len = rq == rr ? rlen_cur[rr] : len;
+        double gv = 0.0;
+        if (row < sr) gv = grow(buf + (size_t)row * ldS, len, PMAX, s_wpa, lane % NS, std::integral_constant<int, NS>());
+        if (lane % NS == 0) s_g[cur][row] = gv;
+      }
       STAMP(5);
       lds_barrier();
       STAMP(3);
       if (i + 1 < nit) issue(i + 1, arena + (size_t)(cur ^ 1) * 32 * ldS);
+      if (QM == QM_TFROMV && wact && i + 1 < nit) { kset(8, vload(2 * i + 4)); if (Pc - 32 * (nit - 2 - i) > 16) kset(12, vload(2 * i + 5)); }
       STAMP(6);
       // the chain's factor is lower triangular in chain order: a row's stored length runs to the end of its ancestor's block,
       // but beyond the tile's last row index there are only (explicit) zeros -- 11 % of the V and 16 % of the T MFMAs at 25-row blocks
-      compute(buf, sr, min(Kb, c0 + 32), min(KbA0, c0 + 16));
+      compute(buf, sr, min(Kb, c0 + 32), min(KbA0, c0 + 16), ISREF ? nullptr : s_g[cur], kget(0), kget(4), 2 + 2 * i);
+      if (QM == QM_TFROMV) { kset(0, kget(8)); kset(4, kget(12)); }
       STAMP(4);
       cur ^= 1;
     }
   }
   lds_barrier();
 
-  // ---- hv = T w_pa for this wave's columns (tile rows l4 + 4 r), summed over the 16 chain columns of a tile row
+  // ---- hv = T w_pa for this wave's columns (tile rows l4 + 4 r), summed over the 16 chain columns of a tile row: reference
+  // units and phase P (the leaf units' log-density takes V' g instead: hacc)
   double h0 = 0.0, h1 = 0.0, h2 = 0.0, h3 = 0.0;
-  {
+  if (QM == QM_FULL && (ISREF || A.predict)) {
 #pragma unroll
     for (int n = 0; n < NKT; ++n) {
       const int k = n * 16 + l15;
@@ -495,33 +582,38 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
   double *pub = R + 32 * CH_LD;
   if constexpr (!ISREF) {
     // ---- leaf units: r_j = 1 / sqrt(K_jj - sum_k V[k][j]^2); panel row of column j = [ -r_j T[j][:] | r_j ]
-    double dsum = dacc;
+    double dsum = dacc, hsum = hacc;
     dsum += __shfl_xor(dsum, 16, 64);
     dsum += __shfl_xor(dsum, 32, 64);
+    hsum += __shfl_xor(hsum, 16, 64);
+    hsum += __shfl_xor(hsum, 32, 64);
     const int jc = jt * 16 + l15;
     double rj = 0.0;
     double dj = 1.0;
     if (jc < Mu) {
       dj = cov_entry(cp, s_colx[u][jc], s_coly[u][jc], s_colmv[u][jc], s_colx[u][jc], s_coly[u][jc], s_colmv[u][jc]) - dsum;
-      if (!(dj > 0.0) && !A.predict) s_fail[u] = 1;
+      if (!(dj > 0.0) && !A.predict && QM != QM_TFROMV) s_fail[u] = 1;
       rj = 1.0 / sqrt(dj);
     }
-    // hv of column l15 sits in h_{l15 >> 2} of the lanes with l4 == (l15 & 3)
-    const int srcl = ((l15 & 3) << 4) | l15;
-    const double t0 = __shfl(h0, srcl, 64), t1 = __shfl(h1, srcl, 64), t2 = __shfl(h2, srcl, 64), t3 = __shfl(h3, srcl, 64);
-    const double hvc = (l15 >> 2) == 0 ? t0 : ((l15 >> 2) == 1 ? t1 : ((l15 >> 2) == 2 ? t2 : t3));
-    if (A.predict) {   // (workgroup-uniform) phase P, spamtree_model.cpp:1306-1326: w_j = H_j w_pa + sqrt(max(K_jj - H_j K_pa,j, 0)) z_j;
+    if (QM == QM_FULL && A.predict) {
+      // hv of column l15 sits in h_{l15 >> 2} of the lanes with l4 == (l15 & 3)
+      const int srcl = ((l15 & 3) << 4) | l15;
+      const double t0 = __shfl(h0, srcl, 64), t1 = __shfl(h1, srcl, 64), t2 = __shfl(h2, srcl, 64), t3 = __shfl(h3, srcl, 64);
+      const double hvc = (l15 >> 2) == 0 ? t0 : ((l15 >> 2) == 1 ? t1 : ((l15 >> 2) == 2 ? t2 : t3));
+      // (workgroup-uniform) phase P, spamtree_model.cpp:1306-1326: w_j = H_j w_pa + sqrt(max(K_jj - H_j K_pa,j, 0)) z_j;
       // no panel, no scalars, no failure: prediction blocks own neither
       if (jc < Mu && l4 == 0) {
         const long long r = s_urow0[u] + jc;
         A.w_out[r] = hvc + (dj > 0.0 ? sqrt(dj) : 0.0) * A.z[r];
       }
     } else {
-      if (jc < Mu && l4 == 0) {
-        const double e = rj * (s_colw[u][jc] - hvc);
+      // hv_j = V_j' (Linv_pa w_pa) = T_j w_pa
+      if (QM != QM_TFROMV && jc < Mu && l4 == 0) {
+        const double e = rj * (s_colw[u][jc] - hsum);
         s_e2[u][jc] = e * e;
         s_lg[u][jc] = log(rj);
       }
+      if (QM != QM_VONLY) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int j = jt * 16 + l4 + 4 * r;
@@ -537,6 +629,7 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
           if (l15 == 0) prow[Pu] = rr;
         }
       }
+      }   // QM != QM_VONLY
     }
   } else {
     // ---- reference units: R = K_uu - V'V (lower triangle) from the Schur tiles
@@ -757,7 +850,7 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
       A.loglik_c[s_ublk0[u]] = (double)Mu * HL2PI - 0.5 * wc;
       if (s_fail[u]) atomicMin(A.errflag, s_level * 16 + (s_uJ[u] == 0 ? 1 : 2));
     }
-  } else if (!A.predict) {
+  } else if (!A.predict && QM != QM_TFROMV) {
     if (ttid < s_unblk[u]) {
       const int bi = ttid;
       double wc = 0.0, ldt = 0.0;

@@ -312,9 +312,11 @@ static int step_w_theta(stm_chain c, bool early_ok = true) {
     const double u = c->rng.uniform(0, 0, m, 2);
     const bool accepted = (u < acceptj) && acceptable;
     if (accepted) {
+      // accept_make_change first: it finishes the proposal's leaf panels (a launch, which can fail) -- an error leaves the
+      // chain's own state as it was before the step's Metropolis outcome
+      if ((rc = st_swap(c->h)) != 0) { c->err = st_last_error(c->h); return rc; }
       am.count_accepted();
       c->current_loglik = c->loglik[1];
-      st_swap(c->h);                                     // accept_make_change
       std::swap(c->loglik[0], c->loglik[1]);
       std::swap(c->param, c->theta_alt);
     }

@@ -83,6 +83,7 @@ struct LevelInfo {
   int rf_first = 0;                // its blocks' entries (this rank's run) in d_rfvoff / d_rfvld
   int lc_first = 0, lc_count = 0;  // its slabs (this rank's run) in d_lcslabs
   int quad_first = 0, quad_count = 0, qown_lo = 0, qown_n = 0, q_ldS = 0, q_nkx = 0;   // k_factor_quad (q_nkx = 0: not eligible)
+  long long vl_off = -1;           // leaf quad level whose T a proposal defers: its V tiles in d_vleaf (-1: always QM_FULL)
   size_t lds_quad = 0;
   int own_lo = 0, own_n = 0, gown_lo = 0, gown_n = 0;   // this rank's run of the level's block list / group list
 };
@@ -208,6 +209,12 @@ struct st_handle_s {
   std::vector<char> s0_valid;                 // per level: d_s0 holds the theta-only precision parts of the accepted theta (column-group levels)
   bool gram_valid = false;                    // message Gram parts in `acc` match the accepted theta (slot 0)
   bool cache_gram = true;
+  // a proposal's quad leaf levels (st_factor_enqueue on slot 1): QM_VONLY, their panels finished by QM_TFROMV from d_vleaf when
+  // the slot is read (st_swap, st_get_block, st_loglik_*); re-factorising the slot drops the pending half
+  bool defer_leaf = false;
+  bool leaf_pending[2] = {false, false};   // per physical arena
+  CovPar leaf_cp[2];
+  DevBuf<double> d_vleaf;
   bool limited = false;               // limited_tree: single parents, marginal chain factors (k_marginal_invchol)
   std::vector<int> twin_list;         // limited_tree: device ids of the blocks that own a chain panel
   DevBuf<int> d_twin;
@@ -278,7 +285,8 @@ static void prof_harvest(st_handle_s *h) {
     if (hipEventSynchronize(r.b) == hipSuccess && hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess) {
       h->prof_ms[r.fam] += ms;
       h->prof_n[r.fam] += r.count;
-      if (r.level >= 0 && r.level < (int)h->prof_level_ms.size()) { h->prof_level_ms[r.level] += ms; h->prof_level_n[r.level] += 1; }
+      // (count 0: the deferred half of a level's launch -- its time, not another launch)
+      if (r.level >= 0 && r.level < (int)h->prof_level_ms.size()) { h->prof_level_ms[r.level] += ms; h->prof_level_n[r.level] += r.count > 0; }
     }
     h->ev_free.push_back(r.a);
     h->ev_free.push_back(r.b);
@@ -342,7 +350,7 @@ extern "C" int st_destroy(st_handle h) {
   for (int s = 0; s < 2; ++s) { h->d_logdet[s].free(); h->d_loglik[s].free(); }
   h->d_scalars.free(); h->d_partial.free(); h->d_stats.free(); h->d_scratch.free(); h->d_tmp_n.free(); h->d_tsq.free();
   h->d_mv.free(); h->d_anc.free(); h->d_dch.free(); h->d_lvl.free(); h->d_pred.free(); h->d_allobs.free(); h->d_err.free();
-  h->d_twin.free(); h->d_wgrps.free(); h->d_lcslabs.free(); h->d_lcrow.free(); h->d_rfvoff.free(); h->d_vscr.free(); h->d_s0.free(); h->d_s0off.free(); h->d_obs.free(); h->d_dev2model.free(); h->d_partner.free(); h->d_blks.free(); h->d_grps.free(); h->d_quads.free(); h->d_gdesc.free();
+  h->d_twin.free(); h->d_wgrps.free(); h->d_lcslabs.free(); h->d_lcrow.free(); h->d_rfvoff.free(); h->d_vscr.free(); h->d_vleaf.free(); h->d_s0.free(); h->d_s0off.free(); h->d_obs.free(); h->d_dev2model.free(); h->d_partner.free(); h->d_blks.free(); h->d_grps.free(); h->d_quads.free(); h->d_gdesc.free();
   h->d_ownobs.free(); h->d_owngrp.free(); h->d_ownslow.free(); h->d_rowmask.free(); h->d_blkmask.free(); h->d_comm.free(); h->d_gather.free(); h->d_gidx.free(); h->d_gerr.free(); h->d_err2.free(); h->d_toplist.free();
   if (h->ev_top) (void)hipEventDestroy(h->ev_top);
   if (h->ev_main) (void)hipEventDestroy(h->ev_main);
@@ -405,6 +413,7 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
   h->force_generic = opt ? opt->force_generic : 0;
   h->cache_gram = !(opt && (opt->reserved & 1));
   h->limited = opt && (opt->reserved & 2);
+  h->defer_leaf = !(opt && (opt->reserved & 4));
   const long long n = pb->n_all, nb = pb->n_blocks;
   h->n_all = n; h->n_blocks = nb; h->q = pb->q; h->p = pb->p; h->d = pb->d; h->n_groups = pb->n_groups;
   for (int j = 0; j < QMAX; ++j) h->tausq_inv[j] = 1.0;
@@ -1321,6 +1330,15 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
   (void)hipFuncSetAttribute((const void *)k_factor_quad<NU_, NKX_, NKT_, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)stat)
     QATTR(4, 50, 13); QATTR(4, 44, 11); QATTR(4, 38, 10); QATTR(4, 32, 8);
 #undef QATTR
+    // the V tiles of the deferred leaf levels (one GPU only: the sharded protocol has no st_factor_enqueue of its own)
+    size_t vl = 0;
+    for (auto &L : h->levels) {
+      L.vl_off = -1;
+      if (!h->defer_leaf || h->world > 1 || h->limited || h->factor_gen != 3 || !L.fast || L.isref || L.q_nkx == 0 || L.qown_n == 0) continue;
+      L.vl_off = (long long)vl;
+      vl += (size_t)L.qown_n * quad_vtiles(L.q_nkx) * (2 * h->quad_nu) * 256;
+    }
+    if (vl) CCHK(h->d_vleaf.alloc(vl));
   }
   {
     // top levels that st_factor_begin may run ahead: the leading levels on k_factor_mfma (no global scratch), when every
@@ -1429,12 +1447,42 @@ static int settle_top(st_handle h) {
   if (h->top_pending) { HCHK(h, hipSetDevice(h->device)); HCHK(h, hipStreamWaitEvent(h->stream, h->ev_top, 0)); }
   return ST_OK;
 }
+// A slot whose leaf levels ran QM_VONLY gets its leaf panels here (QM_TFROMV, on the launch stream), before anything reads
+// them.  The time counts as phase A: the levels' launch slots (mean per phase-A launch) and the phase bracket, no launch added.
+static int complete_leaf(st_handle h, int slot) {
+  const int phys = h->slot_map[slot];
+  if (!h->leaf_pending[phys]) return ST_OK;
+  HCHK(h, hipSetDevice(h->device));
+  const CovPar &cp = h->leaf_cp[phys];
+  ProfScope phase(h, 0, -2, 0);
+  for (int g = 0; g < h->n_actual_groups; ++g) {
+    const LevelInfo &L = h->levels[g];
+    if (L.vl_off < 0) continue;
+    QuadArgs F;
+    std::memset(&F, 0, sizeof(F));
+    F.blks = h->d_blks.p; F.anc_idx = h->d_anc.p; F.grps = h->d_grps.p + L.grp_first;
+    F.quads = h->d_quads.p + L.quad_first + L.qown_lo; F.nquad = L.qown_n;
+    F.cx = h->d_cx.p; F.cy = h->d_cy.p; F.mv = h->d_mv.p; F.w = h->d_w.p; F.panels = h->d_panels[phys].p;
+    F.errflag = h->d_err.p; F.ldS = L.q_ldS;
+    F.gdesc = h->d_gdesc.p + (size_t)L.grp_first * h->gd_stride; F.gd_stride = h->gd_stride;
+    F.wave_chol = L.maxM <= 27 ? 1 : 0;
+    F.mode = QM_TFROMV; F.vscr = h->d_vleaf.p + L.vl_off; F.vtiles = quad_vtiles(L.q_nkx);
+    ProfScope ps(h, 0, g, 0);
+#define QT(NU_, NKX_, NKT_) hipLaunchKernelGGL((k_factor_quad<NU_, NKX_, NKT_, false, true>), dim3(L.qown_n), dim3(128 * NU_), L.lds_quad, h->stream, F, cp)
+    if (L.q_nkx == 32) QT(4, 32, 8); else if (L.q_nkx == 38) QT(4, 38, 10); else if (L.q_nkx == 44) QT(4, 44, 11); else QT(4, 50, 13);
+#undef QT
+    HCHK(h, hipGetLastError());
+  }
+  h->leaf_pending[phys] = false;   // (only once every launch is in: after an error the slot still counts as unfinished)
+  return ST_OK;
+}
 extern "C" int st_swap(st_handle h) {
   if (!h) return ST_ERR_USAGE;
   if (h->top_pending) {   // the proposal's top levels are being written into the arena that would become the accepted slot
     h->err = "st_swap between st_factor_begin and the st_factor / st_factor_local that picks its result up";
     return ST_ERR_USAGE;
   }
+  { const int rc = complete_leaf(h, 1); if (rc) return rc; }   // the only way a slot becomes the sweep's
   std::swap(h->slot_map[0], h->slot_map[1]);
   std::swap(h->theta[0], h->theta[1]);
   h->gram_valid = false;
@@ -1528,7 +1576,9 @@ static int reset_err(st_handle h) {
 // all-gather form of the exchange of w: a rank's slice of the gather buffer = its owned rows + its failure word
 
 // levels [g_lo, g_hi); `st` / `errflag`: the launch stream and failure word (st_factor_begin: the second stream, d_err2)
-static int factor_launch(st_handle h, int phys, const CovPar &cp, int g_lo = 0, int g_hi = INT_MAX, hipStream_t st = nullptr, int *errflag = nullptr) {
+// vonly: the deferrable leaf levels take QM_VONLY (*deferred = true when one did)
+static int factor_launch(st_handle h, int phys, const CovPar &cp, int g_lo = 0, int g_hi = INT_MAX, hipStream_t st = nullptr, int *errflag = nullptr,
+                         bool vonly = false, bool *deferred = nullptr) {
   g_hi = std::min(g_hi, h->n_actual_groups);
   if (!st) st = h->stream;
   if (!errflag) errflag = h->d_err.p;
@@ -1578,7 +1628,9 @@ static int factor_launch(st_handle h, int phys, const CovPar &cp, int g_lo = 0, 
   do {                                                                                                                         \
     if (L.isref && F.wave_chol) { route(g, R_); hipLaunchKernelGGL((k_factor_quad<NU_, NKX_, NKT_, true, true>), dim3(L.qown_n), dim3(128 * NU_), L.lds_quad, st, F, cp); } \
     else if (L.isref) { route(g, R_ + 1); hipLaunchKernelGGL((k_factor_quad<NU_, NKX_, NKT_, true, false>), dim3(L.qown_n), dim3(128 * NU_), L.lds_quad, st, F, cp); } \
-    else { route(g, R_ + 2); hipLaunchKernelGGL((k_factor_quad<NU_, NKX_, NKT_, false, true>), dim3(L.qown_n), dim3(128 * NU_), L.lds_quad, st, F, cp); } \
+    else {                                                                                                                     \
+      if (vonly && L.vl_off >= 0) { F.mode = QM_VONLY; F.vscr = h->d_vleaf.p + L.vl_off; F.vtiles = quad_vtiles(NKX_); *deferred = true; } \
+      route(g, R_ + 2); hipLaunchKernelGGL((k_factor_quad<NU_, NKX_, NKT_, false, true>), dim3(L.qown_n), dim3(128 * NU_), L.lds_quad, st, F, cp); } \
   } while (0)
         if (L.q_nkx == 32) QLAUNCH(4, 32, 8, R_QUAD32_REF_WCH); else if (L.q_nkx == 38) QLAUNCH(4, 38, 10, R_QUAD38_REF_WCH);
         else if (L.q_nkx == 44) QLAUNCH(4, 44, 11, R_QUAD44_REF_WCH); else QLAUNCH(4, 50, 13, R_QUAD50_REF_WCH);
@@ -1658,6 +1710,7 @@ extern "C" int st_factor_begin(st_handle h, int slot, const double *theta, int n
   const int init[2] = {INT_MAX, 0};
   HCHK(h, hipMemcpyAsync(h->d_err2.p, init, 2 * sizeof(int), hipMemcpyHostToDevice, h->stream2));
   const int phys = h->slot_map[slot];
+  h->leaf_pending[phys] = false;   // the slot is being re-factorised: its deferred half is void
   h->prof_suspend = true;   // not timed: the launches overlap the sweep on another stream
   rc = factor_launch(h, phys, cp, 0, h->g_top, h->stream2, h->d_err2.p);
   h->prof_suspend = false;
@@ -1686,7 +1739,9 @@ static int stats_begin(st_handle h) {
   return ST_OK;
 }
 
-extern "C" int st_factor_local(st_handle h, int slot, const double *theta, int ntheta) {
+static int factor_local(st_handle h, int slot, const double *theta, int ntheta, bool vonly);
+extern "C" int st_factor_local(st_handle h, int slot, const double *theta, int ntheta) { return factor_local(h, slot, theta, ntheta, false); }
+static int factor_local(st_handle h, int slot, const double *theta, int ntheta, bool vonly) {
   if (!h || !theta || slot < 0 || slot > 1) return ST_ERR_USAGE;
   HCHK(h, hipSetDevice(h->device));
   CovPar cp;
@@ -1697,6 +1752,7 @@ extern "C" int st_factor_local(st_handle h, int slot, const double *theta, int n
   rc = reset_err(h);
   if (rc) return rc;
   const int phys = h->slot_map[slot];
+  h->leaf_pending[phys] = false;
   if (slot == 1) { rc = stats_begin(h); if (rc) return rc; }
   bool reuse = false;
   if (h->top_pending) {
@@ -1704,9 +1760,10 @@ extern "C" int st_factor_local(st_handle h, int slot, const double *theta, int n
     reuse = h->top_phys == phys && (int)h->top_theta.size() == ntheta && std::equal(theta, theta + ntheta, h->top_theta.begin());
     h->top_pending = false;
   }
-  if (!reuse) return factor_launch(h, phys, cp);
-  rc = factor_launch(h, phys, cp, h->g_top);
-  if (rc) return rc;
+  bool deferred = false;
+  rc = factor_launch(h, phys, cp, reuse ? h->g_top : 0, INT_MAX, nullptr, nullptr, vonly, &deferred);
+  if (deferred) { h->leaf_pending[phys] = true; h->leaf_cp[phys] = cp; }
+  if (rc || !reuse) return rc;
   rc = fix_top_comps(h, phys);
   if (rc) return rc;
   hipLaunchKernelGGL(k_merge_err, dim3(1), dim3(64), 0, h->stream, h->d_err.p, h->d_err2.p);
@@ -1786,6 +1843,7 @@ extern "C" int st_comm_init(st_handle h, const void *unique_id) {
   return ST_OK;
 }
 
+static int factor_enqueue(st_handle h, int slot, const double *theta, int ntheta, bool vonly);
 extern "C" int st_factor(st_handle h, int slot, const double *theta, int ntheta, double *loglik) {
   if (!h) return ST_ERR_USAGE;
   if (h->world > 1 || h->comm) {   // an attached communicator selects the exchange protocol even with one rank (tests)
@@ -1794,7 +1852,7 @@ extern "C" int st_factor(st_handle h, int slot, const double *theta, int ntheta,
     if (rc) return rc;
     return exchange_comps_and_finish(h, slot, loglik);
   }
-  int rc = st_factor_enqueue(h, slot, theta, ntheta);
+  int rc = factor_enqueue(h, slot, theta, ntheta, false);
   if (rc) return rc;
   return st_factor_finish(h, loglik);
 }
@@ -1804,14 +1862,18 @@ extern "C" int st_factor(st_handle h, int slot, const double *theta, int ntheta,
 // (ready early in phase A: they run on the second stream) and uploads them, so that XB is current when phase A ends instead of
 // two host round trips later.  With a communicator attached the first half enqueues nothing and the second does all of st_factor.
 extern "C" int st_factor_is_async(st_handle h) { return (h && !(h->world > 1 || h->comm)) ? 1 : 0; }
+// the proposal's slot (1) defers its leaf levels' T (unless st_options.reserved bit 2); synchronous st_factor never does
 extern "C" int st_factor_enqueue(st_handle h, int slot, const double *theta, int ntheta) {
+  return factor_enqueue(h, slot, theta, ntheta, h && h->defer_leaf && slot == 1);
+}
+static int factor_enqueue(st_handle h, int slot, const double *theta, int ntheta, bool vonly) {
   if (!h || !theta || slot < 0 || slot > 1) return ST_ERR_USAGE;
   if (h->factor_open) { h->err = "st_factor_enqueue: the previous one has not been finished"; return ST_ERR_USAGE; }
   if (h->world > 1 || h->comm) {
     h->factor_open = true; h->factor_open_slot = slot; h->top_theta_open.assign(theta, theta + ntheta);
     return ST_OK;
   }
-  int rc = st_factor_local(h, slot, theta, ntheta);
+  int rc = factor_local(h, slot, theta, ntheta, vonly);
   if (rc) return rc;
   // the failure word and the two sums come back in ONE synchronisation (the sums are meaningless after a failure)
   {
@@ -1848,6 +1910,7 @@ extern "C" int st_factor_finish(st_handle h, double *loglik) {
 static int gather_w_scatter(st_handle h);
 extern "C" int st_sample_w_loglik(st_handle h, const double *z, uint64_t seed, uint32_t iter, int slot, double *loglik) {
   if (!h || slot < 0 || slot > 1) return ST_ERR_USAGE;
+  { const int rc0 = complete_leaf(h, slot); if (rc0) return rc0; }
   if (h->world > 1 || h->comm) {   // an attached communicator selects the exchange protocol even with one rank (tests)
     if (!h->comm) {
       int rc = st_sample_w(h, z, seed, iter);   // reports the missing communicator
@@ -1931,6 +1994,7 @@ extern "C" int st_sample_w_loglik(st_handle h, const double *z, uint64_t seed, u
 extern "C" int st_sample_w_loglik_begin(st_handle h, const double *z, uint64_t seed, uint32_t iter, int slot) {
   if (!h || slot < 0 || slot > 1) return ST_ERR_USAGE;
   if (h->c_pending) return ST_ERR_USAGE;
+  { const int rc0 = complete_leaf(h, slot); if (rc0) return rc0; }
   if (h->world > 1 || h->comm) {
     h->c_ll = 0.0;
     h->c_rc = st_sample_w_loglik(h, z, seed, iter, slot, &h->c_ll);
@@ -2219,6 +2283,7 @@ extern "C" int st_loglik_local(st_handle h, int slot) {
   if (!h || slot < 0 || slot > 1) return ST_ERR_USAGE;
   HCHK(h, hipSetDevice(h->device));
   if (slot == 1) { const int rc0 = settle_top(h); if (rc0) return rc0; }
+  { const int rc0 = complete_leaf(h, slot); if (rc0) return rc0; }
   const int phys = h->slot_map[slot];
   int maxP = 0, maxM = 0;
   for (auto &L : h->levels) { maxP = std::max(maxP, L.maxP); maxM = std::max(maxM, L.maxM); }
@@ -2258,6 +2323,7 @@ static int fix_top_comps(st_handle h, int phys) {
 }
 extern "C" int st_loglik_w(st_handle h, int slot, double *loglik) {
   if (!h) return ST_ERR_USAGE;
+  if (slot >= 0 && slot <= 1) { const int rc0 = complete_leaf(h, slot); if (rc0) return rc0; }
   if (h->world > 1 || h->comm) {   // an attached communicator selects the exchange protocol even with one rank (tests)
     if (!h->comm) { h->err = "world > 1: call st_comm_init first, or use st_loglik_local / st_mg_pack_comps / (all-reduce) / st_mg_finish"; return ST_ERR_USAGE; }
     int rc = st_loglik_local(h, slot);
@@ -2412,6 +2478,7 @@ extern "C" int st_get_block(st_handle h, int slot, int64_t u, double *negRiH, do
   if (B.panel_off < 0) { h->err = "block has no observations, hence no cache"; return ST_ERR_USAGE; }
   HCHK(h, hipSetDevice(h->device));
   { const int rc0 = settle_top(h); if (rc0) return rc0; }
+  { const int rc0 = complete_leaf(h, slot); if (rc0) return rc0; }
   std::vector<double> pan((size_t)B.m * B.ld);
   HCHK(h, hipMemcpyAsync(pan.data(), h->d_panels[h->slot_map[slot]].p + B.panel_off, pan.size() * sizeof(double), hipMemcpyDeviceToHost,
                          h->stream));

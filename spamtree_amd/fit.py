@@ -44,7 +44,7 @@ class Chain:
     def __init__(self, y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, parents, children, limited_tree,
                  block_names, block_groups, indexing, set_unif_bounds, theta, beta, tausq, mcmcsd, seed=2021,
                  adapting=True, sample_beta=True, sample_tausq=True, sample_theta=True, sample_w=True, device=0,
-                 reference_quirks=True, rank=0, world=1, unique_id=None, defer_comm=False):
+                 reference_quirks=True, rank=0, world=1, unique_id=None, defer_comm=False, defer_leaf=True):
         self.lib = _lib.load()
         pb, self._keep, self.n, self.p, self.q = _problem(y, X, coords, mv_id, res_is_ref, parents, children,
                                                           block_names, block_groups, indexing)
@@ -52,7 +52,8 @@ class Chain:
         self.k = theta.size
         bounds = np.asfortranarray(np.asarray(set_unif_bounds, dtype=np.float64))
         sd = np.asfortranarray(np.asarray(mcmcsd, dtype=np.float64))
-        opt = _lib.StOptions(int(device), int(bool(reference_quirks)), int(rank), int(world), 0, 2 if limited_tree else 0)
+        opt = _lib.StOptions(int(device), int(bool(reference_quirks)), int(rank), int(world), 0,
+                             (2 if limited_tree else 0) | (0 if defer_leaf else 4))
         fl = _lib.StmFlags(int(adapting), int(sample_beta), int(sample_tausq), int(sample_theta), int(sample_w), 1)
         c = C.c_void_p()
         self.c = None
