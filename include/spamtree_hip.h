@@ -266,6 +266,21 @@ int st_points_summary_reserve(st_handle h, int64_t keep);
 int st_points_summary_get(st_handle h, double *mean, double *var, double *w_mean, double *yhat_mean, int64_t *n_accumulated);
 int st_points_summary_quantile(st_handle h, double q, double *w_q, double *yhat_q);
 
+/* ---- prior simulation from slot 0: exact draws w ~ N(0, C_DAG) of the tree's own model and y = XB + w + sqrt(tau^2_j) eps.
+ * st_simulate: a root-to-leaf sweep over slot 0 as the last st_factor(h, 0, theta) left it (a deferred leaf half is finished
+ *   first), Ri_u w_u = z_u - N_u w_pa(u) per block, with the handle's current beta (XB) and tau^-2.  nd draws (1..16) in one
+ *   sweep; draw d uses Philox counter (row in model order, iter0 + d, stream 8) for z and stream 9 for eps, or the caller's z /
+ *   eps (n_all x nd column-major, model row order; NULL: Philox).  w_out, y_out: n_all x nd column-major, model row order; either
+ *   may be NULL (y_out NULL: no outcomes; w_out NULL: the draws stay on the device).  A draw does not depend on nd (bitwise).
+ *   Changes no state of the handle: w, XB, both slots, the records and the chain's streams stay as they are.  Refused before any
+ *   launch: NA rows or world > 1 (ST_ERR_UNSUPPORTED), nd outside 1..16 or slot 0 never factorised (ST_ERR_USAGE).
+ * st_simulate_info: the bit set of routes the sweep takes (bit code - 1; a function of the tree only), the algorithmic bytes
+ *   (every panel once + 8 nd B per row for z, eps, w, y and the ancestor gathers + 8 B per row for XB) and flops of an nd-draw call.
+ * st_simulate_route_name: the kernel behind a route code (NULL outside the table). */
+int st_simulate(st_handle h, int nd, const double *z, const double *eps, uint64_t seed, uint32_t iter0, double *w_out, double *y_out);
+int st_simulate_info(st_handle h, int nd, int32_t *route_mask, double *alg_bytes, double *flops);
+const char *st_simulate_route_name(int32_t code);
+
 int st_set_stream(st_handle h, void *stream);              /* launch on the caller's stream (the one its collectives use) */
 
 /* ---- multi-GPU (st_options.world > 1): one process per GPU shares ONE problem.

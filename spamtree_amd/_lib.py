@@ -101,6 +101,9 @@ SIGNATURES = {
     "st_points_summary_reserve": (C.c_int, [H, C.c_int64]),
     "st_points_summary_get": (C.c_int, [H, c_dp, c_dp, c_dp, c_dp, c_ip]),
     "st_points_summary_quantile": (C.c_int, [H, C.c_double, c_dp, c_dp]),
+    "st_simulate": (C.c_int, [H, C.c_int, c_dp, c_dp, C.c_uint64, C.c_uint32, c_dp, c_dp]),
+    "st_simulate_info": (C.c_int, [H, C.c_int, C.POINTER(C.c_int32), c_dp, c_dp]),
+    "st_simulate_route_name": (C.c_char_p, [C.c_int32]),
 }
 
 

@@ -33,6 +33,7 @@
 #include "sample_kernels.hpp"
 #include "misc_kernels.hpp"
 #include "predict_points.hpp"
+#include "simulate_kernels.hpp"
 
 // ===============================================================================================================
 // host side
@@ -229,6 +230,11 @@ struct st_handle_s {
   std::vector<double> xtx;
   std::vector<long long> n_obs_q;
   struct PointSet *pts = nullptr;             // st_points_set: new locations to predict at (owned)
+  // st_simulate: draws [row][sim_cap] on the device (allocated on first use, grown with nd), the device block of every row
+  DevBuf<double> d_simz, d_sime, d_simw, d_simy;
+  DevBuf<int> d_rowblk;
+  int sim_cap = 0;
+  std::vector<SimLevel> sim_levels;
 
   DevBuf<double> d_cx, d_cy, d_y, d_X, d_w, d_xb, d_z, d_B, d_panels[2], d_acc, d_logdet[2], d_loglik[2], d_scalars, d_partial,
       d_stats, d_scratch, d_tmp_n, d_tsq;
@@ -364,6 +370,7 @@ extern "C" int st_destroy(st_handle h) {
   for (int i = 0; i < 2; ++i) if (h->ev_up[i]) (void)hipEventDestroy(h->ev_up[i]);
   if (h->ev_factor) (void)hipEventDestroy(h->ev_factor);
   points_free(h);
+  h->d_simz.free(); h->d_sime.free(); h->d_simw.free(); h->d_simy.free(); h->d_rowblk.free();
   if (h->stream && !h->ext_stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return ST_OK;
@@ -3027,3 +3034,130 @@ extern "C" int st_points_summary_quantile(st_handle h, double q, double *w_q, do
   }
   return ST_OK;
 }
+
+// ---- prior simulation from slot 0 (st_simulate; the kernels and their launcher live in k_simulate.hip) ----
+static int sim_pad(int nd) { int p = 1; while (p < nd) p <<= 1; return p; }
+
+// the sweep's levels, their routes and row ranges: a function of the tree only
+static void sim_plan(st_handle h) {
+  if (!h->sim_levels.empty()) return;
+  for (int g = 0; g < h->n_actual_groups; ++g) {
+    const LevelInfo &L = h->levels[g];
+    SimLevel S;
+    S.first = L.first; S.count = L.count; S.maxM = 0;
+    S.row_lo = LLONG_MAX; S.row_hi = 0;
+    for (int k = 0; k < L.count; ++k) {
+      const Blk &B = h->blks[h->lvl_list[L.first + k]];
+      S.maxM = std::max(S.maxM, B.m);
+      S.row_lo = std::min(S.row_lo, B.row0); S.row_hi = std::max(S.row_hi, B.row0 + B.m);
+    }
+    if (L.count == 0) S.row_lo = 0;
+    S.route = simulate_route(L.isref != 0, S.maxM, h->force_generic != 0);
+    h->sim_levels.push_back(S);
+  }
+}
+
+static int sim_refuse(st_handle h, int nd) {
+  if (h->world > 1) { h->err = "st_simulate: multi-GPU handles are not supported"; return ST_ERR_UNSUPPORTED; }
+  if (h->n_obs != h->n_all) { h->err = "st_simulate: the tree has NA rows; build it with every row observed"; return ST_ERR_UNSUPPORTED; }
+  if (nd < 1 || nd > SIM_MAX_ND) { h->err = "st_simulate: nd must be in 1..16"; return ST_ERR_USAGE; }
+  if (h->theta[0].empty()) { h->err = "st_simulate before st_factor(slot 0)"; return ST_ERR_USAGE; }
+  return ST_OK;
+}
+
+// caller's n_all x nd column-major (model order) -> [device row][ndp], unused columns zero
+static int sim_upload(st_handle h, const double *src, int nd, int ndp, double *dst) {
+  const long long n = h->n_all;
+  std::vector<double> tmp((size_t)n * ndp, 0.0);
+  for (long long i = 0; i < n; ++i) {
+    const long long r = h->dev2model[i];
+    for (int d = 0; d < nd; ++d) tmp[(size_t)i * ndp + d] = src[(size_t)d * n + r];
+  }
+  HCHK(h, hipMemcpyAsync(dst, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  return ST_OK;
+}
+static int sim_download(st_handle h, const double *src, int nd, int ndp, double *dst) {
+  const long long n = h->n_all;
+  std::vector<double> tmp((size_t)n * ndp);
+  HCHK(h, hipMemcpyAsync(tmp.data(), src, tmp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  for (long long i = 0; i < n; ++i) {
+    const long long r = h->dev2model[i];
+    for (int d = 0; d < nd; ++d) dst[(size_t)d * n + r] = tmp[(size_t)i * ndp + d];
+  }
+  return ST_OK;
+}
+
+extern "C" int st_simulate(st_handle h, int nd, const double *z, const double *eps, uint64_t seed, uint32_t iter0, double *w_out,
+                           double *y_out) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = sim_refuse(h, nd)) return rc;
+  HCHK(h, hipSetDevice(h->device));
+  if (const int rc = settle_top(h)) return rc;
+  if (const int rc = complete_leaf(h, 0)) return rc;
+  sim_plan(h);
+  const long long n = h->n_all;
+  const int ndp = sim_pad(nd);
+  for (const SimLevel &S : h->sim_levels)
+    if (S.route == SIM_ROUTE_GENERIC && SIM_GEN_LDS(S.maxM, ndp) > h->lds_limit) {
+      h->err = "st_simulate: a block too wide for the generic kernel's LDS";
+      return ST_ERR_UNSUPPORTED;
+    }
+  if (ndp > h->sim_cap) {
+    h->d_simz.free(); h->d_sime.free(); h->d_simw.free(); h->d_simy.free();
+    HCHK(h, h->d_simz.alloc((size_t)n * ndp)); HCHK(h, h->d_sime.alloc((size_t)n * ndp));
+    HCHK(h, h->d_simw.alloc((size_t)n * ndp)); HCHK(h, h->d_simy.alloc((size_t)n * ndp));
+    h->sim_cap = ndp;
+  }
+  if (!h->d_rowblk.p) {
+    std::vector<int> rb(n);
+    for (size_t b = 0; b < h->blks.size(); ++b)
+      for (int i = 0; i < h->blks[b].m; ++i) rb[h->blks[b].row0 + i] = (int)b;
+    HCHK(h, h->d_rowblk.upload(rb));
+  }
+  if (z) { if (const int rc = sim_upload(h, z, nd, ndp, h->d_simz.p)) return rc; }
+  else HCHK(h, (hipError_t)simulate_normals(h->d_simz.p, h->d_dev2model.p, n, nd, ndp, iter0, SIM_NOISE_Z, seed, h->stream));
+  if (y_out) {
+    if (eps) { if (const int rc = sim_upload(h, eps, nd, ndp, h->d_sime.p)) return rc; }
+    else HCHK(h, (hipError_t)simulate_normals(h->d_sime.p, h->d_dev2model.p, n, nd, ndp, iter0, SIM_NOISE_EPS, seed, h->stream));
+  }
+  SimArgs A;
+  std::memset(&A, 0, sizeof(A));
+  A.blks = h->d_blks.p; A.anc_idx = h->d_anc.p; A.list = h->d_lvl.p;
+  A.panels = h->d_panels[h->slot_map[0]].p;
+  A.z = h->d_simz.p; A.eps = h->d_sime.p; A.xb = h->d_xb.p; A.mv = h->d_mv.p; A.tsq_inv = h->d_tsq.p;
+  A.w = h->d_simw.p; A.y = y_out ? h->d_simy.p : nullptr; A.rowblk = h->d_rowblk.p;
+  int mask = 0;
+  HCHK(h, (hipError_t)simulate_launch(h->sim_levels.data(), (int)h->sim_levels.size(), A, ndp, h->stream, &mask));
+  if (w_out) { if (const int rc = sim_download(h, h->d_simw.p, nd, ndp, w_out)) return rc; }
+  if (y_out) { if (const int rc = sim_download(h, h->d_simy.p, nd, ndp, y_out)) return rc; }
+  return ST_OK;
+}
+
+extern "C" int st_simulate_info(st_handle h, int nd, int32_t *route_mask, double *alg_bytes, double *flops) {
+  if (!h) return ST_ERR_USAGE;
+  if (nd < 1 || nd > SIM_MAX_ND) { h->err = "st_simulate_info: nd must be in 1..16"; return ST_ERR_USAGE; }
+  sim_plan(h);
+  int mask = 0;
+  double bytes = 0.0, fl = 0.0;
+  for (size_t g = 0; g < h->sim_levels.size(); ++g) {
+    const SimLevel &S = h->sim_levels[g];
+    if (S.count == 0) continue;
+    mask |= 1 << (S.route - 1);
+    for (int k = 0; k < S.count; ++k) {
+      const Blk &B = h->blks[h->lvl_list[S.first + k]];
+      const double m = B.m, P = B.P, ri = B.isref ? m * (m + 1) / 2 : m;
+      bytes += 8.0 * (m * P + ri);                   // the block's panel, once
+      fl += 2.0 * nd * (m * P + ri);
+    }
+  }
+  // per row: z, eps, w, y and the ancestor gathers (8 nd B each), XB (8 B)
+  bytes += (double)h->n_all * (5.0 * 8.0 * nd + 8.0);
+  if (route_mask) *route_mask = mask;
+  if (alg_bytes) *alg_bytes = bytes;
+  if (flops) *flops = fl;
+  return ST_OK;
+}
+
+extern "C" const char *st_simulate_route_name(int32_t code) { return simulate_route_name(code); }

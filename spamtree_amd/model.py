@@ -243,6 +243,25 @@ class SpamTreeMV:
             H = -N / Ri[:, None] if P else N
         return H, Ri
 
+    def simulate(self, nd=1, z=None, eps=None, seed=2021, it=0, outcomes=True):
+        """Draws from the model slot 0 was last factorised for (st_simulate): w ~ N(0, C_DAG) and y = XB + w + tau eps with
+        the handle's beta and tausq.  Returns (w, y), n x nd in model order (y None without ``outcomes``).  Draw d uses Philox
+        iteration it + d (streams 8 / 9), or column d of the caller's ``z`` / ``eps`` (n x nd).  Changes no state."""
+        nd = int(nd)
+        zz = None if z is None else np.asfortranarray(np.asarray(z, dtype=np.float64).reshape(self.n_all, nd))
+        ee = None if eps is None else np.asfortranarray(np.asarray(eps, dtype=np.float64).reshape(self.n_all, nd))
+        w = np.zeros((self.n_all, max(nd, 0)), order="F")
+        y = np.zeros((self.n_all, max(nd, 0)), order="F") if outcomes else None
+        self._check(self.lib.st_simulate(self.h, nd, _dp(zz) if zz is not None else None, _dp(ee) if ee is not None else None,
+                                         int(seed), int(it), _dp(w), _dp(y) if y is not None else None))
+        return w, y
+
+    def simulate_info(self, nd=1):
+        mask, b, f = C.c_int32(0), C.c_double(0.0), C.c_double(0.0)
+        self._check(self.lib.st_simulate_info(self.h, int(nd), C.byref(mask), C.byref(b), C.byref(f)))
+        names = [self.lib.st_simulate_route_name(c).decode() for c in range(1, 32) if mask.value >> (c - 1) & 1]
+        return dict(route_mask=mask.value, routes=names, alg_bytes=b.value, flops=f.value)
+
     def comps(self, slot):
         a = np.zeros(self.n_blocks)
         b = np.zeros(self.n_blocks)

@@ -4,7 +4,8 @@ spamtree_model.cpp:1378, 1405 -- is not available outside R, so the stream contr
 
 counter = (index_lo, index_hi | outcome, iteration, stream), key = seed.  Streams: 0 sweep normals (generated on
 the device, same contract), 1 theta proposal, 2 MH uniform, 3 gamma, 4 beta normals, 5 yhat noise (device), 6 new-point
-normals and 7 new-point yhat noise of st_points_predict (device, index = point in the caller's order).
+normals and 7 new-point yhat noise of st_points_predict (device, index = point in the caller's order), 8 the normals z
+and 9 the outcome noise eps of st_simulate (device, index = row in model order, iteration = iter0 + draw).
 """
 import math
 
