@@ -5,6 +5,11 @@ One "step" = one body of the reference's MCMC loop (/root/reference/src/spamtree
 samplers on, no prediction, no saving: w sweep (B) + w log-density (C) + Metropolis proposal for theta, i.e. a
 full re-factorisation of the proposal slot (A) + tausq and beta conjugate draws (S1, S2).
 Prints ONE JSON line on rank 0 (contract in the task statement).
+
+A plain run sets up, warms up, times the steps, dumps (--dump-outputs) and prints the line: the headline figures and what the
+timed steps' own HIP events give (roofline.achieved / frac, fp64_pipe).  --full adds everything that takes runs of its own, after
+the timed steps: the per-launch phase pass (by-level and per-family times), st_predict, the box's measured peaks, the stationary
+windows and the CPU baseline.
 """
 import argparse
 import json
@@ -373,6 +378,88 @@ def dump_outputs(out, dirname, budget=DUMP_BYTES):
         room -= a.nbytes + NPY_HEADER
 
 
+def phase_pass(chain, model, wl, native, fence, steps):
+    """--full: a short untimed pass with every launch bracketed by events (phase breakdown of the other kernel families and
+    per-level phase-A / phase-B times), then st_predict on its own when the workload has rows without an observation."""
+    n_extra = max(1, min(10, steps))
+    model.profile(1)
+    if native:      # every level of phase A on the launch stream for this pass (under the sweep, on the second stream, the top
+        from spamtree_amd import _lib as _l      # levels' launch times would not be their own)
+        import ctypes as _C
+        _l.load().st_factor_ahead_enable(_C.c_void_p(_l.load().stm_handle(chain.c)), 0)
+    chain.step(n_extra)
+    fence()
+    prof_all = model.profile_get()
+    lvl_ms, lvl_bytes, smp_ms, smp_bytes = model.profile_levels_all()
+    if native:
+        _l.load().st_factor_ahead_enable(_C.c_void_p(_l.load().stm_handle(chain.c)), 1)
+    # phase P (draws at the rows without an observation, spamtree_model.cpp:1234-1358; the reference runs it on every SAVED
+    # iteration, spamtree_fit.cpp:300-306): not part of the timed iteration, timed on its own when the workload has such rows
+    predict = None
+    n_na = int(np.sum(~np.isfinite(wl["y"])))
+    if n_na > 0 and native:
+        import ctypes as C
+        from spamtree_amd import _lib
+        lib = _lib.load()
+        for _ in range(4):
+            lib.st_predict(C.c_void_p(lib.stm_handle(chain.c)), 1)
+        pp = model.profile_get()["predict"]
+        predict = {"rows": n_na, "ms_per_call": round(pp[0] / max(1, pp[1]), 4), "calls": pp[1],
+                   "note": "st_predict on its own (HIP events), after the timed region; the leaf path of k_factor_quad where the prediction "
+                           "blocks are eligible, else the generic kernel"}
+    return dict(n_extra=n_extra, prof_all=prof_all, lvl_ms=lvl_ms, lvl_bytes=lvl_bytes, smp_ms=smp_ms, smp_bytes=smp_bytes,
+                predict=predict)
+
+
+def probe_peaks(device, achieved, fp64_achieved):
+    """--full: box-measured peaks: a stream copy and the FP64 matrix / vector pipes, ~0.15 s, outside the
+    timed region."""
+    try:
+        import ctypes as C
+        from spamtree_amd import _lib
+        pk = np.zeros(3)
+        if _lib.load().st_probe_peaks(device, 1 << 30, 5, pk.ctypes.data_as(C.POINTER(C.c_double))) == 0:
+            return {"stream_copy_GBps": round(float(pk[0]), 1), "fp64_mfma_TFLOPs": round(float(pk[1]), 2),
+                    "fp64_fma_TFLOPs": round(float(pk[2]), 2),
+                    "frac_of_stream_copy": round(achieved / pk[0], 4) if pk[0] > 0 else None,
+                    "fp64_frac_of_mfma": round(fp64_achieved / pk[1], 4) if pk[1] > 0 else None,
+                    "note": "this box, this run: float4-wide copy of 1 GiB (read + written bytes), v_mfma_f64_16x16x4_f64 "
+                            "and v_fma_f64 loops at 2 waves per SIMD (csrc/probe.hip); `peak` stays the vendor figure"}
+    except Exception as exc:      # noqa: BLE001
+        return {"error": repr(exc)}
+    return None
+
+
+def stationary_windows(chain, fence, steps, max_windows):
+    """--full: stationary throughput.  The timed window starts at the data-generating theta with a 0.01 I proposal, where the
+    adaptation has not reached its 0.234 target yet, so it under-samples the sweeps that follow an ACCEPTED theta (the records'
+    Gram parts are rebuilt: dearer).  Untimed extra windows until one has accepted >= 20 % of its proposals (bounded), then
+    THAT window's rate."""
+    try:
+        win = max(20, min(50, steps))
+        st0 = chain.state()
+        acc0, it0 = st0["accept_ratio"] * st0["iteration"], st0["iteration"]
+        hist = []
+        for wdx in range(max_windows):
+            fence()
+            tw = time.perf_counter()
+            chain.step(win)
+            fence()
+            tw = time.perf_counter() - tw
+            st1 = chain.state()
+            acc1, it1 = st1["accept_ratio"] * st1["iteration"], st1["iteration"]
+            ar = (acc1 - acc0) / max(1, it1 - it0)
+            hist.append({"iterations": int(it1 - it0), "accept": round(float(ar), 3), "it_per_s": round(win / tw, 2)})
+            acc0, it0 = acc1, it1
+            if ar >= 0.2:
+                break
+        return {"value": hist[-1]["it_per_s"], "unit": "Gibbs iterations/s", "window_accept_ratio": hist[-1]["accept"],
+                "reached_0.2": bool(hist[-1]["accept"] >= 0.2), "windows": hist,
+                "note": f"windows of {win} iterations after the timed region, not part of `value`; the last one is reported"}
+    except Exception as exc:      # noqa: BLE001
+        return {"error": repr(exc)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -383,10 +470,14 @@ def main():
     ap.add_argument("--cell-size", type=int, default=25, help="knots per cell (config #5: 9)")
     ap.add_argument("--missing", type=str, default="", help="per-outcome drop probabilities, e.g. 0.1,0.3,0.5 (config #5)")
     ap.add_argument("--limited-tree", action="store_true", help="limited_tree = TRUE: single-parent edges (tree_dep.cpp:133-186); a timing of that variant, not a BASELINE config")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the untimed measurements: per-launch phase pass (by-level and per-family "
+                         "times), st_predict, measured peaks, stationary windows and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--stationary-windows", type=int, default=12,
-                    help="at most this many untimed 50-iteration windows after the timed region until one accepts >= 20 %% (0 = skip)")
-    ap.add_argument("--cpu-side", type=int, default=316, help="grid side of the bounded CPU-baseline sample")
+                    help="with --full: at most this many untimed 50-iteration windows after the timed region until one accepts "
+                         ">= 20 %% (0 = skip)")
+    ap.add_argument("--cpu-side", type=int, default=316, help="with --full: grid side of the bounded CPU-baseline sample")
     ap.add_argument("--external", action="store_true", help="force the torch.distributed + Python-driver fallback path")
     ap.add_argument("--launch-check", action="store_true", help="CPU rehearsal of the rank launcher (gloo, no GPU work)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -493,40 +584,16 @@ def main():
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    # the passes below step the chain further (untimed): the outputs of the last TIMED step are taken here
+    # the passes of --full step the chain further (untimed): the outputs of the last TIMED step are taken here
     if args.dump_outputs and rank == 0:
         dump_outputs(timed_outputs(chain), args.dump_outputs)
 
     prof = model.profile_get()
-    lvl_ms, lvl_bytes = model.profile_levels()
+    lvl_ms, lvl_bytes = model.profile_levels()      # level count and algorithmic bytes (static); times: the phase pass
     fac_ms, fac_n = prof["factor"]
-    # phase breakdown of the other kernel families: a short untimed pass with every launch bracketed by events
-    n_extra = max(1, min(10, args.steps))
-    model.profile(1)
-    if native:      # every level of phase A on the launch stream for this pass (under the sweep, on the second stream, the top
-        from spamtree_amd import _lib as _l      # levels' launch times would not be their own)
-        import ctypes as _C
-        _l.load().st_factor_ahead_enable(_C.c_void_p(_l.load().stm_handle(chain.c)), 0)
-    chain.step(n_extra)
-    fence()
-    prof_all = model.profile_get()
-    lvl_ms, lvl_bytes, smp_ms, smp_bytes = model.profile_levels_all()   # per-level phase-A / phase-B times come from this pass too
-    if native:
-        _l.load().st_factor_ahead_enable(_C.c_void_p(_l.load().stm_handle(chain.c)), 1)
-    # phase P (draws at the rows without an observation, spamtree_model.cpp:1234-1358; the reference runs it on every SAVED
-    # iteration, spamtree_fit.cpp:300-306): not part of the timed iteration, timed on its own when the workload has such rows
-    predict = None
-    n_na = int(np.sum(~np.isfinite(wl["y"])))
-    if n_na > 0 and native:
-        import ctypes as C
-        from spamtree_amd import _lib
-        lib = _lib.load()
-        for _ in range(4):
-            lib.st_predict(C.c_void_p(lib.stm_handle(chain.c)), 1)
-        pp = model.profile_get()["predict"]
-        predict = {"rows": n_na, "ms_per_call": round(pp[0] / max(1, pp[1]), 4), "calls": pp[1],
-                   "note": "st_predict on its own (HIP events), after the timed region; the leaf path of k_factor_quad where the prediction "
-                           "blocks are eligible, else the generic kernel"}
+    passes = phase_pass(chain, model, wl, native, fence, args.steps) if args.full else None
+    if passes is not None:
+        lvl_ms, lvl_bytes = passes["lvl_ms"], passes["lvl_bytes"]
     model.profile(0)
     n_levels = max(1, len(lvl_ms))
     avg_launch_ms = fac_ms / max(1, fac_n)
@@ -565,56 +632,9 @@ def main():
                         "source_commit": pmc_commit,
                         "note": "rocprofv3 --pmc FETCH_SIZE (x2, gfx950) + WRITE_SIZE, separate passes, same command"}
     fp64_achieved = alg["flops_A"] * share / (avg_launch_ms * n_bracket * 1e-3) / 1e12 if avg_launch_ms > 0 else 0.0
-    all_ms = float(np.sum(lvl_ms))
-    all_levels = {"ms": round(all_ms, 4), "launches": int(np.count_nonzero(np.asarray(lvl_ms) > 0)),
-                  "GBps": round(float(np.sum(lvl_bytes)) * share / (all_ms * 1e-3) / 1e9, 1) if all_ms > 0 else 0.0,
-                  "frac": round(float(np.sum(lvl_bytes)) * share / (all_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if all_ms > 0 else 0.0,
-                  "note": "every level of phase A run back to back on one stream (the per-launch pass), algorithmic bytes"}
-    # box-measured peaks: a stream copy and the FP64 matrix / vector pipes, ~0.15 s, outside the timed region
-    peak_measured = None
-    try:
-        import ctypes as C
-        from spamtree_amd import _lib
-        pk = np.zeros(3)
-        if _lib.load().st_probe_peaks(local_rank, 1 << 30, 5, pk.ctypes.data_as(C.POINTER(C.c_double))) == 0:
-            peak_measured = {"stream_copy_GBps": round(float(pk[0]), 1), "fp64_mfma_TFLOPs": round(float(pk[1]), 2),
-                             "fp64_fma_TFLOPs": round(float(pk[2]), 2),
-                             "frac_of_stream_copy": round(achieved / pk[0], 4) if pk[0] > 0 else None,
-                             "fp64_frac_of_mfma": round(fp64_achieved / pk[1], 4) if pk[1] > 0 else None,
-                             "note": "this box, this run: float4-wide copy of 1 GiB (read + written bytes), v_mfma_f64_16x16x4_f64 "
-                                     "and v_fma_f64 loops at 2 waves per SIMD (csrc/probe.hip); `peak` stays the vendor figure"}
-    except Exception as exc:      # noqa: BLE001
-        peak_measured = {"error": repr(exc)}
-
-    # stationary throughput: the timed window above starts at the data-generating theta with a 0.01 I proposal, where the
-    # adaptation has not reached its 0.234 target yet, so it under-samples the sweeps that follow an ACCEPTED theta (the
-    # records' Gram parts are rebuilt: dearer).  Untimed extra windows until one has accepted >= 20 % of its proposals
-    # (bounded), then THAT window's rate; plus the cached / rebuild sweep times for an acceptance-weighted estimate.
-    stationary = None
-    if world == 1 and args.stationary_windows > 0:
-        try:
-            win = max(20, min(50, args.steps))
-            st0 = chain.state()
-            acc0, it0 = st0["accept_ratio"] * st0["iteration"], st0["iteration"]
-            hist = []
-            for wdx in range(args.stationary_windows):
-                fence()
-                tw = time.perf_counter()
-                chain.step(win)
-                fence()
-                tw = time.perf_counter() - tw
-                st1 = chain.state()
-                acc1, it1 = st1["accept_ratio"] * st1["iteration"], st1["iteration"]
-                ar = (acc1 - acc0) / max(1, it1 - it0)
-                hist.append({"iterations": int(it1 - it0), "accept": round(float(ar), 3), "it_per_s": round(win / tw, 2)})
-                acc0, it0 = acc1, it1
-                if ar >= 0.2:
-                    break
-            stationary = {"value": hist[-1]["it_per_s"], "unit": "Gibbs iterations/s", "window_accept_ratio": hist[-1]["accept"],
-                          "reached_0.2": bool(hist[-1]["accept"] >= 0.2), "windows": hist,
-                          "note": f"windows of {win} iterations after the timed region, not part of `value`; the last one is reported"}
-        except Exception as exc:      # noqa: BLE001
-            stationary = {"error": repr(exc)}
+    peak_measured = probe_peaks(local_rank, achieved, fp64_achieved) if passes is not None else None
+    stationary = (stationary_windows(chain, fence, args.steps, args.stationary_windows)
+                  if passes is not None and world == 1 and args.stationary_windows > 0 else None)
 
     info1 = model.shard_info() if world > 1 else None
     out = {
@@ -627,21 +647,15 @@ def main():
                    "mh_accept_ratio": float(chain.state()["accept_ratio"]),
                    "algorithmic_bytes_per_iter": alg["total"], "algorithmic_flops_per_iter":
                        alg["flops_A"] + alg["flops_B"] + alg["flops_C"], "setup_s": round(t_setup, 2)},
-        "stationary": stationary,
         "multi_gpu": None if world == 1 else {
             "n_gpus": world, "rccl_ranks": int(info1["world"]), "cut_level": int(info1["cut_level"]),
-            "owned_rows_rank0": int(info1["owned_rows"]), "native_rccl": bool(native),
-            "collective_ms_per_iter": round(prof_all.get("comm", (0.0, 0))[0] / n_extra, 4),
-            "collective_launches_per_iter": prof_all.get("comm", (0.0, 0))[1] / n_extra,
-            "note": "rank 0's view; collective time = HIP events around the library's RCCL calls on its stream in the untimed "
-                    "bracketed pass (includes waiting for the slowest rank)"},
+            "owned_rows_rank0": int(info1["owned_rows"]), "native_rccl": bool(native)},
         "roofline": {"bound": "mfma",
                      "bound_note": "what limits the kernel by the counters is the FP64 matrix / vector pipe (ONE pipe per SIMD: "
                                    "fp64_pipe below) and latency, not HBM (hbm_measured ~0.1 of peak).  achieved / peak / frac / unit "
                                    "stay the CONTRACT figure of north_star and SURVEY.md 8(d): algorithmic bytes per launch over the "
                                    "launch time against the 8 TB/s HBM roofline",
                      "contract_bound": "hbm",
-                     "peak_measured": peak_measured,
                      "kernel": "k_factor (phase A: covariance build + chain solve + Cholesky)"
                      + (f"; levels {g_top}-{n_levels - 1} (levels 0-{g_top - 1}, 0.4 % of the bytes, run ahead of time on a second "
                         "stream under the sweep and are not in the timed bracket)" if g_top > 0 else ""),
@@ -656,28 +670,41 @@ def main():
                      "fp64_pipe": {"achieved": fp64_achieved, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
                                    "frac": fp64_achieved / FP64_PEAK_TFLOPS,
                                    "note": "algorithmic flops of phase A (no tile padding, covariance / Cholesky arithmetic not counted) "
-                                           "over the bracket's time"},
-                     "all_levels": all_levels,
-                     "by_level_ms": [round(float(x), 4) for x in lvl_ms],
-                     "by_level_GBps": [round(float(b / (m * 1e-3) / 1e9), 1) if m > 0 else 0.0
-                                       for b, m in zip(lvl_bytes, lvl_ms)],
-                     "by_level_frac": [round(float(b / (m * 1e-3) / 1e9 / HBM_PEAK_GBS), 3) if m > 0 else 0.0
-                                       for b, m in zip(lvl_bytes, lvl_ms)],   # the same ratio per launch (one kernel per level)
-                     "sample_by_level_ms": [round(float(x), 4) for x in smp_ms],
-                     "sample_by_level_GBps": [round(float(b / (m * 1e-3) / 1e9), 1) if m > 0 else 0.0
-                                              for b, m in zip(smp_bytes, smp_ms)],
-                     "phase_ms_per_iter": {kk: round((prof[kk][0] / args.steps) if kk == "factor" else (v[0] / n_extra), 4)
-                                           for kk, v in prof_all.items()},
-                     "predict": predict,
-                     "phase_ms_note": "factor (and avg_launch_ms, achieved): one HIP-event pair around each phase A of the timed "
-                                      "steps; by_level_ms and the other families: an untimed pass of "
-                                      f"{n_extra} steps with every launch bracketed (event traffic costs 4-6 % of an iteration)"},
+                                           "over the bracket's time"}},
     }
+    if passes is not None:
+        n_extra, prof_all, smp_ms, smp_bytes = passes["n_extra"], passes["prof_all"], passes["smp_ms"], passes["smp_bytes"]
+        all_ms = float(np.sum(lvl_ms))
+        out["stationary"] = stationary
+        out["roofline"].update({
+            "peak_measured": peak_measured,
+            "all_levels": {"ms": round(all_ms, 4), "launches": int(np.count_nonzero(np.asarray(lvl_ms) > 0)),
+                           "GBps": round(float(np.sum(lvl_bytes)) * share / (all_ms * 1e-3) / 1e9, 1) if all_ms > 0 else 0.0,
+                           "frac": round(float(np.sum(lvl_bytes)) * share / (all_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if all_ms > 0 else 0.0,
+                           "note": "every level of phase A run back to back on one stream (the per-launch pass), algorithmic bytes"},
+            "by_level_ms": [round(float(x), 4) for x in lvl_ms],
+            "by_level_GBps": [round(float(b / (m * 1e-3) / 1e9), 1) if m > 0 else 0.0 for b, m in zip(lvl_bytes, lvl_ms)],
+            "by_level_frac": [round(float(b / (m * 1e-3) / 1e9 / HBM_PEAK_GBS), 3) if m > 0 else 0.0
+                              for b, m in zip(lvl_bytes, lvl_ms)],   # the same ratio per launch (one kernel per level)
+            "sample_by_level_ms": [round(float(x), 4) for x in smp_ms],
+            "sample_by_level_GBps": [round(float(b / (m * 1e-3) / 1e9), 1) if m > 0 else 0.0 for b, m in zip(smp_bytes, smp_ms)],
+            "phase_ms_per_iter": {kk: round((prof[kk][0] / args.steps) if kk == "factor" else (v[0] / n_extra), 4)
+                                  for kk, v in prof_all.items()},
+            "predict": passes["predict"],
+            "phase_ms_note": "factor (and avg_launch_ms, achieved): one HIP-event pair around each phase A of the timed "
+                             "steps; by_level_ms and the other families: an untimed pass of "
+                             f"{n_extra} steps with every launch bracketed (event traffic costs 4-6 % of an iteration)"})
+        if world > 1:
+            out["multi_gpu"].update({
+                "collective_ms_per_iter": round(prof_all.get("comm", (0.0, 0))[0] / n_extra, 4),
+                "collective_launches_per_iter": prof_all.get("comm", (0.0, 0))[1] / n_extra,
+                "note": "rank 0's view; collective time = HIP events around the library's RCCL calls on its stream in the untimed "
+                        "bracketed pass (includes waiting for the slowest rank)"})
     if dog is not None:
         dog.cancel()
     if rank == 0:
         mark_done()
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(wl, args.cpu_side)
             except Exception as exc:          # noqa: BLE001  (a missing checker must not lose the GPU line)

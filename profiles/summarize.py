@@ -1,4 +1,4 @@
-"""Condenses the raw rocprofv3 output of profiles/collect.sh (gpurun_out/<tag>_*) into the committed summaries
+"""Condenses the raw rocprofv3 output of profiles/collect.sh ($PROFILE_RAW/<tag>_*, default profiles/raw/) into the committed summaries
 profiles/<round>/<tag>_bench.json (ROUND env, default r03), <tag>_kernel_stats.csv and <tag>_pmc_hbm.json.
 
 HBM bytes per kernel family = FETCH_SIZE x 2 (the gfx950 correction of MI355X_MICROARCH.md: 128-byte requests are
@@ -13,7 +13,7 @@ import sys
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "c_quad"
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = os.path.join(root, "gpurun_out")
+src = os.environ.get("PROFILE_RAW") or os.path.join(root, "profiles", "raw")
 dst = os.path.join(root, "profiles", os.environ.get("ROUND", "r03"))
 os.makedirs(dst, exist_ok=True)
 

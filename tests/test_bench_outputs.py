@@ -75,3 +75,33 @@ def test_dump_outputs_are_the_last_timed_step_and_repeat_exactly(tmp_path):
         x, y = np.load(a / f), np.load(b / f)
         assert x.dtype in (np.float32, np.float64) and np.all(np.isfinite(x))
         assert np.array_equal(x, y), f
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_full_adds_the_untimed_figures_after_the_same_step(tmp_path):
+    """A plain run prints the headline figures of its timed steps and nothing that takes runs of its own; --full adds the
+    per-launch phase pass, the measured peaks and the stationary windows, after the dump: the dumped step is the same."""
+    common = ["--side", "60", "--steps", "3", "--warmup", "2"]
+    r = run(common + ["--dump-outputs", str(tmp_path / "plain")])
+    assert r.returncode == 0, r.stderr[-2000:]
+    plain = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    r = run(common + ["--full", "--no-cpu-baseline", "--stationary-windows", "1", "--dump-outputs", str(tmp_path / "full")])
+    assert r.returncode == 0, r.stderr[-2000:]
+    full = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    for res in (plain, full):
+        assert res["unit"] == "Gibbs iterations/s" and res["higher_is_better"] is True and res["dtype"] == "f64"
+        assert res["metric"].startswith("Gibbs iterations/sec") and res["steps"] == 3 and res["warmup"] == 2
+        assert abs(res["ms_per_step"] * res["value"] - 1e3) < 1e-6 * 1e3
+        assert res["roofline"]["achieved"] > 0 and res["roofline"]["fp64_pipe"]["achieved"] > 0
+    assert not {"stationary", "cpu_baseline"} & set(plain)
+    assert not {"by_level_ms", "sample_by_level_ms", "phase_ms_per_iter", "peak_measured", "all_levels"} & set(plain["roofline"])
+    assert "cpu_baseline" not in full and full["stationary"]["windows"]
+    rf = full["roofline"]
+    assert len(rf["by_level_ms"]) == full["config"]["levels"] == plain["config"]["levels"]
+    assert {"factor", "sample", "loglik"} <= set(rf["phase_ms_per_iter"]) and "stream_copy_GBps" in rf["peak_measured"]
+    assert rf["algorithmic_bytes_per_launch"] == plain["roofline"]["algorithmic_bytes_per_launch"]
+    a, b = tmp_path / "plain", tmp_path / "full"
+    names = sorted(os.listdir(a))
+    assert names == sorted(os.listdir(b)) and np.load(a / "iteration.npy")[0] == 2 + 3
+    for f in names:
+        assert np.array_equal(np.load(a / f), np.load(b / f)), f
