@@ -158,6 +158,7 @@ struct stm_chain_s {
   long long m = 0;
   int last_accepted = 0, last_acceptable = 1;
   bool tb_drawn = false;   // this iteration's tausq / beta were drawn under the proposal's factorisation already
+  bool defer_sync = true, early_beta = true;   // SPAMTREE_DEFER_SYNC / SPAMTREE_EARLY_BETA, read by stm_create
   double last_logaccept = 0;
   bool initialised = false;
 };
@@ -181,6 +182,9 @@ extern "C" int stm_create(const st_problem *pb, const st_options *opt, const dou
   stm_chain c = new stm_chain_s();
   int rc = st_create(pb, opt, &c->h);
   if (rc != 0) { delete c; return rc; }
+  const char *e;
+  c->defer_sync = !((e = getenv("SPAMTREE_DEFER_SYNC")) && e[0] == '0');
+  c->early_beta = !((e = getenv("SPAMTREE_EARLY_BETA")) && e[0] == '0');
   c->q = pb->q; c->p = pb->p; c->k = ntheta; c->n_all = pb->n_all; c->seed = seed; c->rng = HostRng(seed);
   if (flags) { c->adapting = flags->adapting; c->sample_beta = flags->sample_beta; c->sample_tausq = flags->sample_tausq;
                c->sample_theta = flags->sample_theta; c->sample_w = flags->sample_w; }
@@ -266,9 +270,8 @@ static int step_w_theta(stm_chain c, bool early_ok = true) {
   if (c->sample_w) {
     rc = st_sample_w_loglik_begin(c->h, nullptr, c->seed, m, 0);
     if (rc) { c->err = st_last_error(c->h); return rc; }
-    static const bool defer = !(getenv("SPAMTREE_DEFER_SYNC") && getenv("SPAMTREE_DEFER_SYNC")[0] == '0');   // 0: read the sweep's results at once
-    if ((!c->sample_theta || !defer) && (rc = finish_sweep()) != 0) return rc;
-    sweep_open = c->sample_theta && defer;
+    if ((!c->sample_theta || !c->defer_sync) && (rc = finish_sweep()) != 0) return rc;   // SPAMTREE_DEFER_SYNC=0: read the sweep's results at once
+    sweep_open = c->sample_theta && c->defer_sync;
   }
   if (c->sample_theta) {
     c->theta_alt = np;
@@ -280,8 +283,7 @@ static int step_w_theta(stm_chain c, bool early_ok = true) {
     // the end of phase A and the next kernel: ~50 us of idle GPU per iteration (SPAMTREE_EARLY_BETA=0: the old order; same chain).
     // Not on iterations whose prediction step runs in between: with quirk Q3 the beta statistics pair y with w of ALL rows
     // (spamtree_model.cpp:1375), i.e. they see the predicted values.
-    static const bool early = !(getenv("SPAMTREE_EARLY_BETA") && getenv("SPAMTREE_EARLY_BETA")[0] == '0');
-    if (early && early_ok && c->sample_w && st_factor_is_async(c->h)) {
+    if (c->early_beta && early_ok && c->sample_w && st_factor_is_async(c->h)) {
       rc = st_factor_enqueue(c->h, 1, np.data(), k);
       if (rc == 0) {
         const int r3 = draw_tausq_beta(c);

@@ -117,11 +117,42 @@ static const char *const k_route_names[R_COUNT] = {
   "k_sample_lean<false>", "k_sample<true, false>", "k_sample_leaf_wide", "k_sample<true, true>", "k_sample<false>",
 };
 
+// The library's environment switches ("Runtime switches", says what each one does), read once per handle
+// by create_impl.  The defaults are the measured best.  wide, split_gram, sample_wave: 0 never, 2 on every eligible level.
+struct Switches {
+  int wide = 1, split_gram = 1, sample_wave = 1;
+  bool lchain = true, lchain_ref = true, gram_big = true, gram_direct = true, sample_lean = true, sample_lat = true,
+       leaf_seg = true, leaf_wide = true, async_top = true;
+  int lchain_ref_min = 1;
+  int factor_gen = 3;     // 3: k_factor_quad where a column-group level is eligible, k_factor_mfma elsewhere; 1: k_factor_mfma everywhere
+  int quad_units = 0;     // k_factor_quad's units per workgroup, honoured in 1 .. quad_nu
+  int quad_min = -1;      // smallest level that takes k_factor_quad (-1: 2 x CUs)
+};
+
+static Switches read_switches() {
+  auto level = [](const char *name) {   // 0 / 2 when the value starts with '0' / '2', else (unset too) 1
+    const char *e = getenv(name);
+    return (e && e[0] == '0') ? 0 : ((e && e[0] == '2') ? 2 : 1);
+  };
+  Switches s;
+  s.wide = level("SPAMTREE_WIDE"); s.split_gram = level("SPAMTREE_SPLIT_GRAM"); s.sample_wave = level("SPAMTREE_SAMPLE_WAVE");
+  s.lchain = level("SPAMTREE_LCHAIN"); s.lchain_ref = level("SPAMTREE_LCHAIN_REF"); s.gram_big = level("SPAMTREE_GRAM_BIG");
+  s.gram_direct = level("SPAMTREE_GRAM_DIRECT"); s.sample_lean = level("SPAMTREE_SAMPLE_LEAN"); s.sample_lat = level("SPAMTREE_SAMPLE_LAT");
+  s.leaf_seg = level("SPAMTREE_LEAF_SEG"); s.leaf_wide = level("SPAMTREE_LEAF_WIDE"); s.async_top = level("SPAMTREE_ASYNC_TOP");
+  const char *e;
+  if ((e = getenv("SPAMTREE_LCHAIN_REF_MIN"))) s.lchain_ref_min = atoi(e);
+  if ((e = getenv("SPAMTREE_FACTOR_KERNEL")) && e[0] == '1') s.factor_gen = 1;
+  if ((e = getenv("SPAMTREE_QUAD_UNITS"))) s.quad_units = atoi(e);
+  if ((e = getenv("SPAMTREE_QUAD_MIN"))) s.quad_min = std::max(atoi(e), 0);   // (any value <= 0 lets every level through)
+  return s;
+}
+
 struct st_handle_s {
   std::string err;
   int device = 0;
   hipStream_t stream = nullptr;
   int quirks = 1, force_generic = 0;
+  Switches sw;
   long long n_all = 0, n_blocks = 0;
   int q = 1, p = 1, d = 2, n_groups = 0, n_actual_groups = 0;
   long long n_obs = 0;
@@ -138,7 +169,6 @@ struct st_handle_s {
   DevBuf<Quad> d_quads;
   std::vector<WideGrp> wgrps;                 // sibling groups of the wide levels (k_factor_wide)
   DevBuf<WideGrp> d_wgrps;
-  int wide_on = 1;                            // SPAMTREE_WIDE=0: k_factor_bigmfma (one block per workgroup) instead
   std::vector<LcSlab> lcslabs;                // k_factor_lchain: slabs of sibling groups
   DevBuf<LcSlab> d_lcslabs;
   std::vector<long long> rfvoff;   // k_factor_ref_finish: per block of a reference level on the lchain route, its columns in the V scratch
@@ -150,8 +180,6 @@ struct st_handle_s {
   DevBuf<long long> d_s0off;                  // per block: offset into d_s0, -1 = none
   bool c_pending = false;                     // st_sample_w_loglik_begin: the sweep's failure word and log-density are on their way to pin[8..10]
   int c_rc = 0; double c_ll = 0.0;            // ... or (multi-GPU / communicator attached) already here
-  int gram_big = 1;                           // SPAMTREE_GRAM_BIG=0: the generic sweep kernel rebuilds the records' Gram parts itself (one thread per entry)
-  int lchain_on = 1;                          // SPAMTREE_LCHAIN=0: non-reference long-chain levels stay on k_factor_wide / k_factor_bigmfma
   std::vector<long long> gdesc;               // group descriptors (GdHead layout), gd_stride words per group
   DevBuf<long long> d_gdesc;
   int gd_stride = 8;
@@ -188,14 +216,7 @@ struct st_handle_s {
   long long n_summary = 0;
   DevBuf<double> d_draws_w, d_draws_yhat;     // st_summary_reserve: the saved draws themselves, [keep][n_all] (quantiles)
   long long draws_cap = 0, n_draws = 0;
-  int factor_gen = 1;
-  int sample_lean = 1;                        // sweeps with cached Gram parts take k_sample_lean (SPAMTREE_SAMPLE_LEAN=0: never)
-  int sample_wave = 1;                        // reference blocks of <= 27 rows: one block per wave (SPAMTREE_SAMPLE_WAVE=0: k_sample_lean)
-  int lchain_ref_on = 1, lchain_ref_min = 1;   // reference levels of wide-block trees (with at least that many blocks): k_factor_lchain + k_factor_ref_finish
-  int leaf_wide = 1;                          // k_sample_leaf_wide for the non-reference levels of wide-block trees (SPAMTREE_LEAF_WIDE=0: the generic kernel)
-  int leaf_seg = 1;                           // k_sample_leaf_seg (segment-aligned lanes) where eligible
   int gram_direct_level = -1;                 // >= 0: that (last reference) level forms its children's Gram parts itself: k_gram_direct
-  int split_gram = 1;                         // sweeps that rebuild the Gram parts: k_gram + lean kernels (SPAMTREE_SPLIT_GRAM=0: k_sample_mfma)
   bool stats_valid = false;                   // d_stats matches the current w and XB
   bool host_stats_valid = false;              // ... and host_stats holds a copy of it
   std::vector<double> host_stats;
@@ -421,6 +442,7 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
   h->cache_gram = !(opt && (opt->reserved & 1));
   h->limited = opt && (opt->reserved & 2);
   h->defer_leaf = !(opt && (opt->reserved & 4));
+  h->sw = read_switches();
   const long long n = pb->n_all, nb = pb->n_blocks;
   h->n_all = n; h->n_blocks = nb; h->q = pb->q; h->p = pb->p; h->d = pb->d; h->n_groups = pb->n_groups;
   for (int j = 0; j < QMAX; ++j) h->tausq_inv[j] = 1.0;
@@ -622,11 +644,6 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
     if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device) == hipSuccess && v > 0) h->lds_limit = (size_t)v;
     if (h->lds_limit > 160 * 1024) h->lds_limit = 160 * 1024;
     h->quad_nu = 4;   // units per workgroup of k_factor_quad (2 per workgroup with two workgroups per CU measured slower)
-    { const char *e = getenv("SPAMTREE_WIDE"); h->wide_on = (e && e[0] == '0') ? 0 : ((e && e[0] == '2') ? 2 : 1); }
-    { const char *e = getenv("SPAMTREE_LCHAIN"); h->lchain_on = (e && e[0] == '0') ? 0 : 1; }
-    { const char *e = getenv("SPAMTREE_LCHAIN_REF"); h->lchain_ref_on = (e && e[0] == '0') ? 0 : 1; }
-    { const char *e = getenv("SPAMTREE_LCHAIN_REF_MIN"); h->lchain_ref_min = e ? atoi(e) : 1; }
-    { const char *e = getenv("SPAMTREE_GRAM_BIG"); h->gram_big = (e && e[0] == '0') ? 0 : 1; }
   }
   h->levels.resize(n_actual);
   h->route_a.assign((size_t)n_actual * ST_ROUTE_A_SLOTS, R_NONE);
@@ -753,7 +770,7 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
         L.bigmfma = L.lds_bigmfma <= h->lds_limit;
         // non-reference blocks, <= 64 columns, every block behind at least one ancestor: k_factor_lchain (K in registers, the
         // chain factor streamed through LDS twice); a property of the level, the same on every rank
-        if (L.bigmfma && h->lchain_on && !h->limited && !L.isref && L.maxM <= 64 && L.maxP <= 544) {
+        if (L.bigmfma && h->sw.lchain && !h->limited && !L.isref && L.maxM <= 64 && L.maxP <= 544) {
           bool all_anc = true;
           for (int b : list) all_anc = all_anc && h->blks[b].nanc >= 1 && !h->blks[b].isref;
           if (all_anc) L.lchain = L.maxP <= 384 ? 96 : 136;
@@ -761,7 +778,7 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
         // REFERENCE levels behind a chain (round 3): k_factor_lchain for the chain pass (it runs it at more than twice
         // k_factor_bigmfma's rate, and a block's columns are two slabs on two CUs: the single-block top levels gain too), then
         // k_factor_ref_finish per block.  L.count, not the rank's share: a property of the level
-        if (L.bigmfma && h->lchain_on && h->lchain_ref_on && !h->limited && L.isref && L.maxM <= 80 && L.maxP <= 544 && L.count >= h->lchain_ref_min) {
+        if (L.bigmfma && h->sw.lchain && h->sw.lchain_ref && !h->limited && L.isref && L.maxM <= 80 && L.maxP <= 544 && L.count >= h->sw.lchain_ref_min) {
           bool all_anc = true;
           for (int b : list) all_anc = all_anc && h->blks[b].nanc >= 1 && h->blks[b].isref;
           if (all_anc) { L.lchain = L.maxP <= 384 ? 96 : 136; L.lchain_ref = true; }
@@ -821,7 +838,7 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
     // measured at config #4 (577^2 x 3 outcomes): the leaf level 32.7 -> 28.2 ms, the 75-column reference level 13.9 -> 15.1 ms
     // (two blocks per group: more passes than staging saved), levels with fewer groups than CUs lose parallelism -- so only
     // big non-reference levels take it (SPAMTREE_WIDE=2 forces it on every eligible level: tests)
-    if (L.bigmfma && !L.lchain && h->wide_on && !h->limited && (h->wide_on == 2 || (!L.isref && L.count >= 2 * h->sm_count))) {   // L.count, not the rank's share: the two kernels round
+    if (L.bigmfma && !L.lchain && h->sw.wide && !h->limited && (h->sw.wide == 2 || (!L.isref && L.count >= 2 * h->sm_count))) {   // L.count, not the rank's share: the two kernels round
       // differently, and a level must take the same one on every rank of every world size (bit-identical sharded runs)
       int k = L.own_lo;
       const int kend = L.own_lo + L.own_n;
@@ -913,8 +930,7 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
           const double rounds = std::ceil((double)std::max(owned, 1) / (double)(cand[c] * h->sm_count));
           if (rounds * tl[c] < best - 1e-9) { best = rounds * tl[c]; nu_max = cand[c]; }
         }
-        const char *e = getenv("SPAMTREE_QUAD_UNITS");   // tests: force the units per workgroup (1, 2 or 4)
-        if (e && atoi(e) >= 1 && atoi(e) <= h->quad_nu) nu_max = atoi(e);
+        if (h->sw.quad_units >= 1 && h->sw.quad_units <= h->quad_nu) nu_max = h->sw.quad_units;   // tests: force the units per workgroup
       }
       for (int pass = 0; pass < 2; ++pass) {
         int k = 0;
@@ -952,8 +968,7 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
       const int ldS = quad_lds_stride(L.q_nkx);   // the kernel's compile-time row stride (>= maxP + 24)
       L.q_ldS = ldS;
       L.lds_quad = ((size_t)h->quad_nu * 16 * ldS + ldS + (L.isref ? (size_t)h->quad_nu * 512 : (size_t)2 * h->quad_nu * QUAD_LEAF_KH * 64)) * 8;   // arena, zero row, V exchange / covariance scratch
-      int min_groups = 2 * h->sm_count;   // smaller levels do not fill the chip with quads: k_factor_mfma's 4x more workgroups win
-      { const char *e = getenv("SPAMTREE_QUAD_MIN"); if (e) min_groups = atoi(e); }
+      const int min_groups = h->sw.quad_min >= 0 ? h->sw.quad_min : 2 * h->sm_count;   // smaller levels do not fill the chip with quads: k_factor_mfma's 4x more workgroups win
       if (L.grp_count < 2 * nq_any || mixed || L.grp_count < min_groups) L.q_nkx = 0;   // mostly singletons: nothing to share
       if (L.isref && L.q_nkx == 50) L.q_nkx = 0;                   // that instantiation spills registers: k_factor_mfma is faster
     }
@@ -991,8 +1006,7 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
   h->pred_grp_first = (int)h->grps.size(); h->pred_grp_count = 0; h->pred_quad_first = (int)h->quads.size(); h->pred_quad_count = 0; h->pred_nkx = 0;
   {
     const LevelInfo &Lp = h->pred_info;
-    const char *e = getenv("SPAMTREE_PREDICT_FAST");
-    bool ok = !(e && e[0] == '0') && !h->force_generic && !h->pred_list.empty() && Lp.maxP > 0 && Lp.maxP <= 200 && Lp.maxMa <= 32 && Lp.maxM <= 32;
+    bool ok = !h->force_generic && !h->pred_list.empty() && Lp.maxP > 0 && Lp.maxP <= 200 && Lp.maxMa <= 32 && Lp.maxM <= 32;
     const std::vector<int> &list = h->pred_list;
     size_t i = 0;
     while (ok && i < list.size()) {
@@ -1148,8 +1162,7 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
     h->gram_direct_level = -1;
     {
       const int gl = n_actual - 1, gp = n_actual - 2;
-      const char *e = getenv("SPAMTREE_GRAM_DIRECT");
-      if (!(e && e[0] == '0') && gp >= 0 && !h->limited && h->levels[gl].fast && !h->levels[gl].isref && h->levels[gp].fast && h->levels[gp].isref &&
+      if (h->sw.gram_direct && gp >= 0 && !h->limited && h->levels[gl].fast && !h->levels[gl].isref && h->levels[gp].fast && h->levels[gp].isref &&
           h->levels[gl].maxM <= 32 && h->levels[gl].maxP <= 255) {
         bool ok = true;
         const LevelInfo &Lp = h->levels[gp], &Ll = h->levels[gl];
@@ -1304,17 +1317,6 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
   (void)hipFuncSetAttribute((const void *)k_marginal_invchol, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
   (void)hipFuncSetAttribute((const void *)k_marginal_invchol_wave, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
   {
-    // phase A kernel for the column-group levels: 3 (default) = k_factor_quad where a level is eligible (big enough,
-    // chains <= 200 rows, LDS fits) and k_factor_mfma elsewhere; 1 = k_factor_mfma everywhere
-    const char *e = getenv("SPAMTREE_FACTOR_KERNEL");
-    h->factor_gen = (e && e[0] == '1') ? 1 : 3;
-    { const char *e2 = getenv("SPAMTREE_SAMPLE_LEAN"); h->sample_lean = (e2 && e2[0] == '0') ? 0 : 1; }
-    { const char *e2 = getenv("SPAMTREE_LEAF_SEG"); h->leaf_seg = (e2 && e2[0] == '0') ? 0 : 1; }
-    { const char *e2 = getenv("SPAMTREE_LEAF_WIDE"); h->leaf_wide = (e2 && e2[0] == '0') ? 0 : 1; }
-    { const char *e2 = getenv("SPAMTREE_SPLIT_GRAM"); h->split_gram = (e2 && e2[0] == '0') ? 0 : ((e2 && e2[0] == '2') ? 2 : 1); }
-    { const char *e2 = getenv("SPAMTREE_SAMPLE_WAVE"); h->sample_wave = (e2 && e2[0] == '0') ? 0 : ((e2 && e2[0] == '2') ? 2 : 1); }   // 2: every eligible level (tests)
-  }
-  {
     // k_factor_quad: static + dynamic LDS must fit; levels that do not fit (or are too small to fill the chip) keep k_factor_mfma
     const void *fq = (const void *)k_factor_quad<4, 50, 13, false, true>;
     hipFuncAttributes fa;
@@ -1341,7 +1343,7 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
     size_t vl = 0;
     for (auto &L : h->levels) {
       L.vl_off = -1;
-      if (!h->defer_leaf || h->world > 1 || h->limited || h->factor_gen != 3 || !L.fast || L.isref || L.q_nkx == 0 || L.qown_n == 0) continue;
+      if (!h->defer_leaf || h->world > 1 || h->limited || h->sw.factor_gen != 3 || !L.fast || L.isref || L.q_nkx == 0 || L.qown_n == 0) continue;
       L.vl_off = (long long)vl;
       vl += (size_t)L.qown_n * quad_vtiles(L.q_nkx) * (2 * h->quad_nu) * 256;
     }
@@ -1354,13 +1356,12 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
     bool all_fast = !h->limited && !h->force_generic;
     for (int g = 0; g < n_actual; ++g) all_fast = all_fast && h->levels[g].fast;
     if (all_fast) {
-      while (h->g_top < n_actual && !(h->factor_gen == 3 && h->levels[h->g_top].q_nkx > 0)) ++h->g_top;
+      while (h->g_top < n_actual && !(h->sw.factor_gen == 3 && h->levels[h->g_top].q_nkx > 0)) ++h->g_top;
       if (h->g_top >= n_actual) h->g_top = 0;   // nothing would be left for the main stream to hide it under
     }
     // the top levels are a fixed cost (0.19 ms at n = 1e6: a quarter of a rank's phase A on 8 GPUs, 40 % of phase A at
     // n = 1e5); at n = 1e6 on one GPU the sweep fills the chip and the gain is 1.5 % (SPAMTREE_ASYNC_TOP=0 turns it off)
-    const char *e = getenv("SPAMTREE_ASYNC_TOP");
-    h->async_top = h->g_top > 0 && !(e && e[0] == '0');
+    h->async_top = h->g_top > 0 && h->sw.async_top;
     std::vector<int> tl;
     for (int b : h->own_obs_list) if (h->blks[b].level < h->g_top) tl.push_back(b);
     h->n_toplist = (int)tl.size();
@@ -1622,7 +1623,7 @@ static int factor_launch(st_handle h, int phys, const CovPar &cp, int g_lo = 0, 
     A.errflag = errflag; A.maxP = L.maxP; A.maxM = L.maxM; A.maxMa = L.maxMa; A.SR = L.big_factor ? 4 : 8;
     {
       ProfScope ps(h, 0, g, 1, st);
-      if (L.fast && h->factor_gen == 3 && L.q_nkx > 0) {
+      if (L.fast && h->sw.factor_gen == 3 && L.q_nkx > 0) {
         QuadArgs F;
         std::memset(&F, 0, sizeof(F));
         F.blks = h->d_blks.p; F.anc_idx = h->d_anc.p; F.grps = h->d_grps.p + L.grp_first;
@@ -1652,7 +1653,7 @@ static int factor_launch(st_handle h, int phys, const CovPar &cp, int g_lo = 0, 
         F.gdesc = h->d_gdesc.p + (size_t)(L.grp_first + L.gown_lo) * h->gd_stride; F.gd_stride = h->gd_stride;
         route(g, R_FACTOR_MFMA);
         hipLaunchKernelGGL(k_factor_mfma, dim3(L.gown_n), dim3(NT), L.lds_fast, st, F, cp);
-      } else if (L.bigmfma && h->factor_gen == 3 && L.lchain) {
+      } else if (L.bigmfma && h->sw.factor_gen == 3 && L.lchain) {
         LcArgs C;
         std::memset(&C, 0, sizeof(C));
         C.blks = h->d_blks.p; C.anc_idx = h->d_anc.p; C.slabs = h->d_lcslabs.p + L.lc_first; C.nslab = L.lc_count;
@@ -1671,7 +1672,7 @@ static int factor_launch(st_handle h, int phys, const CovPar &cp, int g_lo = 0, 
           hipLaunchKernelGGL(k_lchain_scalars, dim3((A.nlist + 255) / 256), dim3(256), 0, st, h->d_blks.p, A.list, A.nlist, h->d_lcrow.p, h->n_all,
                              h->d_logdet[phys].p, h->d_loglik[phys].p);
         }
-      } else if (L.bigmfma && h->factor_gen == 3 && L.wide_count > 0) {
+      } else if (L.bigmfma && h->sw.factor_gen == 3 && L.wide_count > 0) {
         WideArgs W;
         std::memset(&W, 0, sizeof(W));
         W.blks = h->d_blks.p; W.anc_idx = h->d_anc.p; W.list = h->d_lvl.p + L.first + L.own_lo; W.groups = h->d_wgrps.p + L.wide_first;
@@ -1680,7 +1681,7 @@ static int factor_launch(st_handle h, int phys, const CovPar &cp, int g_lo = 0, 
         W.scratch_stride = h->scratch_stride; W.maxP = L.maxP; W.maxN = L.wide_maxN; W.maxM = L.maxM; W.maxMa = L.maxMa; W.ldS = L.bm_ldS;
         route(g, R_FACTOR_WIDE);
         hipLaunchKernelGGL((k_factor_wide<WG_JT>), dim3(std::min(L.wide_count, h->sm_count)), dim3(WG_NT), L.lds_wide, st, W, cp);
-      } else if (L.bigmfma && h->factor_gen == 3) {
+      } else if (L.bigmfma && h->sw.factor_gen == 3) {
         A.scratch = h->d_scratch.p; A.scratch_stride = h->scratch_stride; A.SR = L.bm_ldS;
         if (L.maxM <= 48) { route(g, R_BIGMFMA3); hipLaunchKernelGGL((k_factor_bigmfma<3, 5, 34>), dim3(std::min(A.nlist, h->sm_count)), dim3(BM_NT), L.lds_bigmfma, st, A, cp); }
         else if (L.maxM <= 64) { route(g, R_BIGMFMA4); hipLaunchKernelGGL((k_factor_bigmfma<4, 5, 34>), dim3(std::min(A.nlist, h->sm_count)), dim3(BM_NT), L.lds_bigmfma, st, A, cp); }
@@ -2081,13 +2082,13 @@ static int sample_launch(st_handle h, int g_hi, int g_lo) {   // levels g_hi-1 .
         F.acc = h->d_acc.p; F.errflag = h->d_err.p; F.ldN = L.ldN; F.Mr4 = L.Mr4; F.Mrows = L.Mrows; F.maxP = L.maxP; F.av_dbl = L.av_dbl;
         F.gdesc = h->d_gdesc.p + (size_t)(L.grp_first + L.gown_lo) * h->gd_stride; F.gd_stride = h->gd_stride;
         for (int j = 0; j < QMAX; ++j) F.tausq_inv[j] = h->tausq_inv[j];
-        const bool lean_ok = h->sample_lean != 0 && !(!L.isref && L.maxP > 255);
+        const bool lean_ok = h->sw.sample_lean && !(!L.isref && L.maxP > 255);
         F.gdesc_all = h->d_gdesc.p;
         // does level `gq` take k_gram + the lean kernels on a rebuild sweep?  (the same test for the level itself, below)
         auto splits = [&](int gq) {
           const LevelInfo &Lq = h->levels[gq];
-          const bool lean_q = h->sample_lean != 0 && !(!Lq.isref && Lq.maxP > 255);
-          return Lq.fast && lean_q && h->split_gram && (h->split_gram == 2 || (Lq.isref && Lq.gown_n >= 32 * h->sm_count));
+          const bool lean_q = h->sw.sample_lean && !(!Lq.isref && Lq.maxP > 255);
+          return Lq.fast && lean_q && h->sw.split_gram && (h->sw.split_gram == 2 || (Lq.isref && Lq.gown_n >= 32 * h->sm_count));
         };
         // the leaf level of a rebuild sweep writes NO Gram parts when its parents form them from the leaf panels (k_gram_direct)
         const bool direct_parent = F.do_gram && h->gram_direct_level == g && splits(g) && h->levels[g + 1].gown_n > 0;
@@ -2095,7 +2096,7 @@ static int sample_launch(st_handle h, int g_hi, int g_lo) {   // levels g_hi-1 .
         // the theta-only Gram parts on their own (k_gram), then the lean sweep kernels: pays on big reference levels (n = 1e6,
         // level 7: 0.84 -> 0.72 ms averaged over a run's sweeps), loses on leaf levels and on smaller reference levels, where
         // the staged Gram of k_sample_mfma is cheaper (SPAMTREE_SPLIT_GRAM=2: every level; records identical either way)
-        if (F.do_gram && lean_ok && h->split_gram && (h->split_gram == 2 || (L.isref && L.gown_n >= 32 * h->sm_count))) {
+        if (F.do_gram && lean_ok && h->sw.split_gram && (h->sw.split_gram == 2 || (L.isref && L.gown_n >= 32 * h->sm_count))) {
           if (direct_parent) { route[0] = R_GRAM_DIRECT; hipLaunchKernelGGL(k_gram_direct, dim3(L.gown_n), dim3(NT), 0, h->stream, F); }
           else { route[0] = R_GRAM; hipLaunchKernelGGL(k_gram, dim3(L.gown_n), dim3(NT), 0, h->stream, F); }
           F.do_gram = 0;
@@ -2112,11 +2113,11 @@ static int sample_launch(st_handle h, int g_hi, int g_lo) {   // levels g_hi-1 .
           // segment-aligned lanes where the level's chains have at most 12 ancestors of at most 32 rows (SPAMTREE_LEAF_SEG=0: the
           // column-aligned kernel)
           const int need = (L.maxJ + 1) / 2;
-          if (h->leaf_seg && need <= 4 && L.maxMa <= 32) { route[1] = R_LEAF_SEG4; hipLaunchKernelGGL((k_sample_leaf_seg<4>), dim3(L.gown_n), dim3(NT), ((size_t)4 * 64 * 4 + 3 * 32) * 8, h->stream, F); }
-          else if (h->leaf_seg && need <= 6 && L.maxMa <= 32) { route[1] = R_LEAF_SEG6; hipLaunchKernelGGL((k_sample_leaf_seg<6>), dim3(L.gown_n), dim3(NT), ((size_t)4 * 64 * 6 + 3 * 32) * 8, h->stream, F); }
+          if (h->sw.leaf_seg && need <= 4 && L.maxMa <= 32) { route[1] = R_LEAF_SEG4; hipLaunchKernelGGL((k_sample_leaf_seg<4>), dim3(L.gown_n), dim3(NT), ((size_t)4 * 64 * 4 + 3 * 32) * 8, h->stream, F); }
+          else if (h->sw.leaf_seg && need <= 6 && L.maxMa <= 32) { route[1] = R_LEAF_SEG6; hipLaunchKernelGGL((k_sample_leaf_seg<6>), dim3(L.gown_n), dim3(NT), ((size_t)4 * 64 * 6 + 3 * 32) * 8, h->stream, F); }
           else { route[1] = R_SAMPLE_LEAF; hipLaunchKernelGGL(k_sample_leaf, dim3(L.gown_n), dim3(NT), ((size_t)L.maxP + 32 + 4 * 256 + 3 * 32) * 8, h->stream, F); }
         }
-        else if (h->sample_wave && L.maxM <= 27 && (h->sample_wave == 2 || L.gown_n >= 8 * h->sm_count)) {   // one block per wave: faster on a level
+        else if (h->sw.sample_wave && L.maxM <= 27 && (h->sw.sample_wave == 2 || L.gown_n >= 8 * h->sm_count)) {   // one block per wave: faster on a level
           // that keeps every CU busy for several rounds (n = 1e6 after the row-wise panel pass: level 7 0.44 -> 0.35 ms, level 6 -- 4096 blocks --
           // 0.151 -> 0.117), a wash at 1024 blocks (0.050 -> 0.046 there, 0.034 -> 0.039 at config #5), slower on latency-bound small levels (256 blocks: 0.029 -> 0.040): gd | wv | seg | tv, ev | Ri, per wave
           const size_t per = (((size_t)h->gd_stride + L.maxP + 32 + L.av_dbl + 64 + (size_t)std::max(L.maxM, 1) * CH_LD + 1) & ~(size_t)1);
@@ -2126,13 +2127,12 @@ static int sample_launch(st_handle h, int g_hi, int g_lo) {   // levels g_hi-1 .
         } else {
           // levels that do not fill the chip (fewer groups than 2 x CUs x the five workgroups the occupancy variant fits): the
           // latency variant -- every descriptor-only load of a block in one round trip (SPAMTREE_SAMPLE_LAT=0: never; identical draws)
-          static const bool lat_on = !(getenv("SPAMTREE_SAMPLE_LAT") && getenv("SPAMTREE_SAMPLE_LAT")[0] == '0');
           F.av_dbl = L.av_dbl + 224;
-          if (lat_on && L.gown_n <= 2 * h->sm_count) { route[1] = R_SAMPLE_LEAN_LAT; hipLaunchKernelGGL((k_sample_lean<true>), dim3(L.gown_n), dim3(NT), L.lds_slean, h->stream, F); }
+          if (h->sw.sample_lat && L.gown_n <= 2 * h->sm_count) { route[1] = R_SAMPLE_LEAN_LAT; hipLaunchKernelGGL((k_sample_lean<true>), dim3(L.gown_n), dim3(NT), L.lds_slean, h->stream, F); }
           else { route[1] = R_SAMPLE_LEAN; hipLaunchKernelGGL((k_sample_lean<false>), dim3(L.gown_n), dim3(NT), L.lds_slean, h->stream, F); }
         }
       } else {
-        if (A.do_gram && L.big_sample && h->gram_big) {
+        if (A.do_gram && L.big_sample && h->sw.gram_big) {
           // the theta-only parts first, on the matrix cores (k_gram_big); the sweep kernel then takes its cached branch
           GramBigArgs Gb;
           std::memset(&Gb, 0, sizeof(Gb));
@@ -2150,7 +2150,7 @@ static int sample_launch(st_handle h, int g_hi, int g_lo) {   // levels g_hi-1 .
         if (L.big_sample) {
           A.scratch = h->d_scratch.p; A.scratch_stride = h->scratch_stride;
           if (L.isref) { route[1] = R_SAMPLE_BIG_REF; hipLaunchKernelGGL((k_sample<true, false>), dim3(std::min(L.own_n, h->scratch_wgs)), dim3(NT), L.lds_sample, h->stream, A); }
-          else if (h->leaf_wide && !A.do_gram && L.maxM <= 64 && L.maxMa <= 96 && L.maxJ <= 8) {   // one coalesced pass, segment-aligned lanes
+          else if (h->sw.leaf_wide && !A.do_gram && L.maxM <= 64 && L.maxMa <= 96 && L.maxJ <= 8) {   // one coalesced pass, segment-aligned lanes
             route[1] = R_SAMPLE_LEAF_WIDE;
             hipLaunchKernelGGL(k_sample_leaf_wide, dim3(std::min(L.own_n, 16 * h->sm_count)), dim3(NT), ((size_t)4 * 64 * 12 + 3 * 64) * 8, h->stream, A);
           } else { route[1] = R_SAMPLE_BIG_LEAF; hipLaunchKernelGGL((k_sample<true, true>), dim3(std::min(L.own_n, h->scratch_wgs)), dim3(NT), L.lds_sample, h->stream, A); }
@@ -2567,9 +2567,9 @@ extern "C" int st_level_info(st_handle h, int32_t *n_levels, int32_t *kernel, in
   for (int g = 0; g < h->n_actual_groups && g < cap; ++g) {
     const LevelInfo &L = h->levels[g];
     int k = L.big_factor ? ST_KERNEL_GENERIC_SCRATCH : ST_KERNEL_GENERIC_LDS;
-    if (L.fast && h->factor_gen == 3 && L.q_nkx > 0) k = ST_KERNEL_QUAD;
+    if (L.fast && h->sw.factor_gen == 3 && L.q_nkx > 0) k = ST_KERNEL_QUAD;
     else if (L.fast) k = ST_KERNEL_MFMA;
-    else if (L.bigmfma && h->factor_gen == 3) k = L.lchain ? (L.lchain_ref ? ST_KERNEL_LCHAIN_REF : ST_KERNEL_LCHAIN) : (L.wide_count > 0 ? ST_KERNEL_WIDE : ST_KERNEL_BIGMFMA);
+    else if (L.bigmfma && h->sw.factor_gen == 3) k = L.lchain ? (L.lchain_ref ? ST_KERNEL_LCHAIN_REF : ST_KERNEL_LCHAIN) : (L.wide_count > 0 ? ST_KERNEL_WIDE : ST_KERNEL_BIGMFMA);
     if (kernel) kernel[g] = k;
     if (max_m) max_m[g] = L.maxM;
     if (max_P) max_P[g] = L.maxP;

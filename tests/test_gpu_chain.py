@@ -143,27 +143,24 @@ def test_deferred_sweep_protocol_failure_and_misuse():
     hm.close()
 
 
-def test_chain_with_and_without_deferred_sync_are_identical():
+def test_chain_with_and_without_deferred_sync_are_identical(monkeypatch):
     """SPAMTREE_DEFER_SYNC and SPAMTREE_EARLY_BETA (the tausq / beta draws made under the proposal's factorisation:
-    st_factor_enqueue / st_factor_finish) are read once per process, so the settings run in subprocesses: same chain bit for bit."""
-    import os
-    import subprocess
-    import sys
-    code = ("import numpy as np, sys; sys.path.insert(0, %r)\n"
-            "from tests.util import make_problem\nfrom spamtree_amd import fit\n"
-            "pb = make_problem(side=25, q=1, seed=3, missing=0.1)\n"
-            "ch = fit.Chain(pb['y'], pb['X'], pb['Z'], pb['coords'], pb['mv_id'], pb['blocking'], pb['gix_block'], pb['res_is_ref'],"
-            " pb['parents'], pb['children'], False, pb['block_names'], pb['block_groups'], pb['indexing'], pb['bounds'], pb['theta'],"
-            " np.zeros(pb['p']), 0.1, 0.01 * np.eye(4), seed=5)\n"
-            "ch.step(40); st = ch.state()\n"
-            "print(repr((st['theta'].tolist(), st['tausq_inv'].tolist(), st['loglik'], float(np.sum(ch.get_w())))))\n") % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    st_factor_enqueue / st_factor_finish) are read when the chain is created: same chain bit for bit."""
+    from spamtree_amd import fit
+    pb = make_problem(side=25, q=1, seed=3, missing=0.1)
     outs = []
     for defer, early in (("1", "1"), ("0", "1"), ("1", "0")):
-        r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, SPAMTREE_DEFER_SYNC=defer, SPAMTREE_EARLY_BETA=early),
-                           capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
-        outs.append(r.stdout.strip().splitlines()[-1])
-    assert outs[0] == outs[1] == outs[2]
+        monkeypatch.setenv("SPAMTREE_DEFER_SYNC", defer)
+        monkeypatch.setenv("SPAMTREE_EARLY_BETA", early)
+        ch = fit.Chain(pb["y"], pb["X"], pb["Z"], pb["coords"], pb["mv_id"], pb["blocking"], pb["gix_block"], pb["res_is_ref"],
+                       pb["parents"], pb["children"], False, pb["block_names"], pb["block_groups"], pb["indexing"], pb["bounds"],
+                       pb["theta"], np.zeros(pb["p"]), 0.1, 0.01 * np.eye(4), seed=5)
+        ch.step(40)
+        outs.append(dict(ch.state(), w=ch.get_w()))
+        ch.close()
+    for o in outs[1:]:
+        for k in ("theta", "tausq_inv", "loglik", "w"):
+            assert np.array_equal(o[k], outs[0][k]), k
 
 
 def test_factor_in_two_halves_equals_st_factor():

@@ -18,10 +18,6 @@ sweep kernel of a sweep that formed / read cached Gram parts ("leaf_rebuild" / "
 chain tiles) follows the level's longest chain P: 32 up to 128 rows, 38 up to 152, 44 up to 176, 50 up to 200;
 WCH=true: blocks of <= 27 rows.
 """
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
@@ -404,39 +400,24 @@ def test_route_matches_oracle(row, monkeypatch):
     compare_with_oracle(pb, inp, out, key=problem_key(row))
 
 
-# ---- k_sample_lean<false>: SPAMTREE_SAMPLE_LAT is read once per process, so that route runs in a child process
+# ---- k_sample_lean<false>: the same row with SPAMTREE_SAMPLE_LAT=0, then without it (each handle reads its own switches)
 LEAN_ROW = ROUTES[0]
 
 
-def _lean_child(path):
-    """Runs LEAN_ROW's device protocol in this (child) process and saves its draws and routes."""
-    for k, v in LEAN_ROW["env"].items():
-        os.environ[k] = v
-    pb = build_problem(LEAN_ROW)
-    out = run_device(pb, inputs(pb))
-    np.savez(path, ws=np.array(out["ws"]), lls=np.array(out["lls"]), ll_comps=np.array(out["ll_comps"]),
-             xty=np.array(out["xty"]), ssq=np.array(out["ssq"]), sweep=np.array(sorted(out["routes"]["sweep"])))
-
-
-def test_lean_sample_without_latency_variant_matches_oracle_and_is_bitwise_lean_true(monkeypatch, tmp_path):
+def test_lean_sample_without_latency_variant_matches_oracle_and_is_bitwise_lean_true(monkeypatch):
     for k, v in LEAN_ROW["env"].items():
         monkeypatch.setenv(k, v)
-    path = str(tmp_path / "lean_false.npz")
-    code = f"from tests.test_gpu_routes import _lean_child; _lean_child({path!r})"
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, SPAMTREE_SAMPLE_LAT="0"), cwd=root,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    child = np.load(path)
-    assert "k_sample_lean<false>" in child["sweep"].tolist() and "k_sample_lean<true>" not in child["sweep"].tolist()
     pb = build_problem(LEAN_ROW)
     inp = inputs(pb)
-    out = run_device(pb, inp)      # this process: the latency variant on the same levels
+    monkeypatch.setenv("SPAMTREE_SAMPLE_LAT", "0")
+    lean = run_device(pb, inp)
+    assert "k_sample_lean<false>" in lean["routes"]["sweep"] and "k_sample_lean<true>" not in lean["routes"]["sweep"]
+    monkeypatch.delenv("SPAMTREE_SAMPLE_LAT")
+    out = run_device(pb, inp)      # the latency variant on the same levels
     assert "k_sample_lean<true>" in out["routes"]["sweep"]
     for k in ("ws", "lls", "ll_comps", "xty", "ssq"):
-        assert np.array_equal(child[k], np.array(out[k])), k
-        out[k] = list(child[k])
-    compare_with_oracle(pb, inp, out, key=problem_key(LEAN_ROW))
+        assert np.array_equal(np.array(lean[k]), np.array(out[k])), k
+    compare_with_oracle(pb, inp, lean, key=problem_key(LEAN_ROW))
 
 
 # ---- config #2 at full size (n = 99 856, bench.py --side 316) on its default routes, against oracle/refcpu
