@@ -170,3 +170,118 @@ def test_oracle_loses_digits_as_phi_falls():
         assert all(a < b for a, b in zip(col, col[1:])), (k, col)
     assert errs[0][0] < 1e-13 and errs[-1][0] > 1e-8 and errs[-1][1] > 1e-8, errs
     assert errs[-1][2] > 1e2 * errs[0][2], errs
+
+
+# ---- the index-only view and the restated draws (what tests/test_gpu_full_size.py checks full-size runs with)
+def view_and_oracle(pb, w, beta, tausq=0.2):
+    from oracle.extended import WorkloadView
+    om = oracle_model(pb, w=w, beta=beta, tausq=tausq)
+    assert om.get_loglik_comps_w(om.param_data)
+    view = WorkloadView(csr_problem(pb), beta, 1.0 / tausq, limited_tree=pb.get("limited_tree", False))
+    return om, view
+
+
+def csr_problem(pb):
+    """pb with indexing / parents / children as the (ptr, idx) CSR pairs of make_workload."""
+    t = pb["topo"]
+    return dict(pb, indexing=(t.indexing_ptr, t.indexing_idx), parents=(t.parents_ptr, t.parents_idx),
+                children=(t.children_ptr, t.children_idx))
+
+
+@pytest.mark.parametrize("q,missing,limited", [(1, 0.1, False), (3, 0.2, False), (2, 0.0, True)],
+                         ids=["q1_na", "q3_na", "q2_limited"])
+def test_view_gives_the_oracle_model_blocks_bitwise(q, missing, limited):
+    pb = make_problem(side=16 if q == 1 else 8, q=q, seed=4, missing=missing, limited_tree=limited)
+    rng = np.random.default_rng(2)
+    w, beta = rng.standard_normal(pb["n"]), rng.standard_normal(pb["p"])
+    om, view = view_and_oracle(pb, w, beta)
+    from oracle.extended import WorkloadView
+    assert isinstance(view, WorkloadView)
+    a, b = ExtendedBlocks(om, pb["theta"]), ExtendedBlocks(view, pb["theta"])
+    assert np.array_equal(view.block_ct_obs, om.block_ct_obs)
+    assert np.array_equal(view.y, om.y) and np.array_equal(view.XB, om.XB)
+    assert np.array_equal(view.tausq_inv_long, om.tausq_inv_long)
+    for u in range(om.n_blocks):
+        assert np.array_equal(view.parents_indexing[u], om.parents_indexing[u]), u
+        assert np.array_equal(view.children[u], om.children[u]), u
+        x, y = a.block(u), b.block(u)
+        for k in ("H", "N", "Ri", "d", "rdiag", "logdet"):
+            if k in x:
+                assert np.array_equal(x[k], y[k]), (u, k)
+        assert a.loglik_comp(u, w) == b.loglik_comp(u, w), u
+        if om.block_ct_obs[u] and b.block(u)["isref"]:
+            assert np.array_equal(a.cond_mean(u, w), b.cond_mean(u, w)), u
+
+
+@pytest.mark.parametrize("q,missing,limited", [(1, 0.1, False), (3, 0.2, False), (2, 0.1, True)],
+                         ids=["q1_na", "q3_na", "q2_limited"])
+def test_draws_match_the_oracle(q, missing, limited):
+    """cond_draw against gibbs_sample_w (each block given the values before the sweep, its descendants' own rows after it),
+    predict_draw against predict, at nice theta."""
+    pb = make_problem(side=16 if q == 1 else 8, q=q, seed=6, missing=missing, limited_tree=limited)
+    rng = np.random.default_rng(3)
+    w0, beta, z = rng.standard_normal(pb["n"]), rng.standard_normal(pb["p"]), rng.standard_normal(pb["n"])
+    om, view = view_and_oracle(pb, w0, beta)
+    ex = ExtendedBlocks(view, pb["theta"])
+    om.gibbs_sample_w(z)
+    w1 = om.w.copy()
+    checked = 0
+    for u in range(om.n_blocks):
+        if om.block_ct_obs[u] == 0:
+            continue
+        iu = om.indexing[u]
+        assert relerr(ex.cond_draw(u, w0, z[iu], w_desc=w1), w1[iu]) <= 1e-12, u
+        checked += 1
+    assert checked > 3
+    om.predict(True)
+    w2 = om.w
+    pred = [u for u in range(om.n_blocks) if om.block_ct_obs[u] == 0 and om.indexing[u].size]
+    assert pred
+    for u in pred:
+        iu = om.indexing[u]
+        assert relerr(ex.predict_draw(u, w2, z[iu]), w2[iu]) <= 1e-12, u
+
+
+@pytest.mark.parametrize("q,limited", [(1, False), (3, False), (2, True)], ids=["q1", "q3", "q2_limited"])
+def test_prior_draw_matches_the_restated_prior_sweep(q, limited):
+    from tests.prior_sweep import prior_sweep
+    pb = make_problem(side=16 if q == 1 else 8, q=q, seed=8, limited_tree=limited)
+    z = np.random.default_rng(4).standard_normal(pb["n"])
+    om, view = view_and_oracle(pb, np.zeros(pb["n"]), np.zeros(pb["p"]))
+    W = prior_sweep(om, z)[:, 0]
+    ex = ExtendedBlocks(view, pb["theta"])
+    for u in range(om.n_blocks):
+        iu = om.indexing[u]
+        if iu.size:
+            assert relerr(ex.prior_draw(u, W, z[iu]), W[iu]) <= 1e-12, u
+
+
+@pytest.mark.parametrize("q", [1, 3])
+def test_point_moments_equal_the_dense_identity(q):
+    """The new-point mean and variance on the anchor's chain against the dense kriging identity on its conditioning set (the
+    one test_gpu_predict_points checks the kernels with)."""
+    from oracle.spamtree_oracle import CovarianceParams, Covariancef
+    from spamtree_amd.predict import conditioning_set, locate
+    pb = make_problem(side=16 if q == 1 else 9, q=q, seed=5, missing=0.1)
+    topo = pb["topo"]
+    rng = np.random.default_rng(6)
+    w = rng.standard_normal(pb["n"])
+    _, view = view_and_oracle(pb, w, np.zeros(pb["p"]))
+    ex = ExtendedBlocks(view, pb["theta"])
+    pts = rng.uniform(size=(60, 2))
+    mv = rng.integers(1, q + 1, size=60)
+    anchor = locate(topo, pts, mv)
+    cp = CovarianceParams(2, q)
+    cp.transform(pb["theta"])
+    allc = np.vstack([topo.coords, pts])
+    allv = np.concatenate([topo.mv_id - 1, mv - 1])
+    n = pb["n"]
+    for i in range(pts.shape[0]):
+        S = np.concatenate([topo.indexing(int(b)) for b in conditioning_set(topo, int(anchor[i]))])
+        Kss = Covariancef(allc, allv, S, S, cp, same=True)
+        ks = Covariancef(allc, allv, S, [n + i], cp)[:, 0]
+        kxx = Covariancef(allc, allv, [n + i], [n + i], cp)[0, 0]
+        sol = np.linalg.solve(Kss, np.column_stack([w[S], ks]))
+        mean, var = ex.point_moments(int(anchor[i]), pts[i:i + 1], mv[i:i + 1], w)
+        assert abs(float(mean[0]) - ks @ sol[:, 0]) <= 1e-10 * max(1.0, abs(ks @ sol[:, 0])), i
+        assert abs(float(var[0]) - max(kxx - ks @ sol[:, 1], 0)) <= 1e-10 * max(1.0, kxx), i
