@@ -269,8 +269,11 @@ __global__ void k_yhat(const double *xb, const double *w, const double *noise, c
 __global__ void k_cross_cov(const double *c1, const int *mv1, long long n1, const double *c2, const int *mv2, long long n2, CovPar cp,
                             double *out) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long j = blockIdx.y;
-  if (i < n1 && j < n2) out[j * n1 + i] = cov_entry(cp, c1[i], c1[n1 + i], mv1[i], c2[j], c2[n2 + j], mv2[j]);
+  if (i >= n1) return;
+  const double x1 = c1[i], y1 = c1[n1 + i];
+  const int v1 = mv1[i];
+  // columns blockIdx.y, blockIdx.y + gridDim.y, ...: the launch keeps gridDim.y within the y extent of a grid for any n2
+  for (long long j = blockIdx.y; j < n2; j += gridDim.y) out[j * n1 + i] = cov_entry(cp, x1, y1, v1, c2[j], c2[n2 + j], mv2[j]);
 }
 // Posterior quantiles per row over the saved draws (list_qtile / prctile_stl, /root/reference/src/list_mean.cpp:62-137):
 // draws[d * n + row], d < keep.  A workgroup sorts the draws of R rows in LDS (bitonic, rows padded to Kpad = 2^k with +inf)

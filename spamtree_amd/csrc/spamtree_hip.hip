@@ -2599,6 +2599,8 @@ extern "C" int st_cross_covariance_ag10(const double *coords1, const int64_t *mv
     g_create_error = q < 2 ? "Invalid Dmat for multivariate data" : "st_cross_covariance_ag10: bad argument";
     return ST_ERR_USAGE;
   }
+  if (n1 < 0 || n2 < 0) { g_create_error = "st_cross_covariance_ag10: negative extent"; return ST_ERR_USAGE; }
+  if (n1 == 0 || n2 == 0) return ST_OK;   // the reference's empty matrix: nothing to compute, nothing written
   if (hipSetDevice(device) != hipSuccess) { g_create_error = "no usable HIP device"; return ST_ERR_HIP; }
   CovPar cp;
   std::memset(&cp, 0, sizeof(cp));
@@ -2617,7 +2619,9 @@ extern "C" int st_cross_covariance_ag10(const double *coords1, const int64_t *mv
   if (!bad(d1.alloc(2 * n1)) && !bad(d2.alloc(2 * n2)) && !bad(dout.alloc((size_t)n1 * n2)) && !bad(dm1.upload(m1)) && !bad(dm2.upload(m2)) &&
       !bad(hipMemcpy(d1.p, coords1, 2 * n1 * sizeof(double), hipMemcpyHostToDevice)) &&
       !bad(hipMemcpy(d2.p, coords2, 2 * n2 * sizeof(double), hipMemcpyHostToDevice))) {
-    hipLaunchKernelGGL(k_cross_cov, dim3((unsigned)((n1 + NT - 1) / NT), (unsigned)n2), dim3(NT), 0, 0, d1.p, dm1.p, (long long)n1, d2.p, dm2.p,
+    // gridDim.y is bounded (a grid's y extent is limited to 65535 workgroups): k_cross_cov strides over the columns beyond it
+    const unsigned gy = (unsigned)std::min<int64_t>(n2, 4096);
+    hipLaunchKernelGGL(k_cross_cov, dim3((unsigned)((n1 + NT - 1) / NT), gy), dim3(NT), 0, 0, d1.p, dm1.p, (long long)n1, d2.p, dm2.p,
                        (long long)n2, cp, dout.p);
     if (!bad(hipGetLastError())) bad(hipMemcpy(out, dout.p, (size_t)n1 * n2 * sizeof(double), hipMemcpyDeviceToHost));
   }

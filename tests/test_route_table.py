@@ -8,11 +8,12 @@ from tests import test_gpu_routes as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "spamtree_amd", "csrc", "spamtree_hip.hip")
+SRC_POINTS_ACC = os.path.join(ROOT, "spamtree_amd", "csrc", "k_points_acc.hip")
 
 # launched kernels without a route code that other tests compare with the oracle (or, for plumbing, check bit for bit);
 # every route-coded kernel is reached by a row of the route table instead (test_every_route_coded_kernel_is_in_the_table)
 COVERED_ELSEWHERE = {
-    "k_xb": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
+    "k_xb": "tests/test_gpu_outputs.py::test_statistics_xb_yhat_xtx_match_extended_precision",
     "k_merge_err": "tests/test_gpu_chain.py::test_cpp_driver_with_top_levels_ahead_of_time",
     "k_pack_comps": "tests/test_gpu_sharded.py::test_sharded_equals_single_process_bitwise",
     "k_normals": "tests/test_gpu_parity.py::test_generated_sweep_normals_are_the_documented_stream",
@@ -21,12 +22,13 @@ COVERED_ELSEWHERE = {
     "k_gather_unpack": "tests/test_gpu_sharded.py::test_sharded_equals_single_process_bitwise",
     "k_loglik": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
     "k_loglik_grp": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
-    "k_stats": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
-    "k_stats_final": "tests/test_gpu_parity.py::test_factor_sample_loglik_predict_match_oracle",
-    "k_yhat": "tests/test_gpu_parity.py::test_device_normals_match_oracle_stream",
-    "k_cross_cov": "tests/test_gpu_parity.py::test_cross_covariance_ag10_export",
-    "k_axpy_sum": "tests/test_gpu_parity.py::test_posterior_means_and_quantiles_match_oracle_chain",
-    "k_qtile": "tests/test_gpu_parity.py::test_posterior_means_and_quantiles_match_oracle_chain",
+    "k_stats": "tests/test_gpu_outputs.py::test_statistics_xb_yhat_xtx_match_extended_precision",
+    "k_stats_final": "tests/test_gpu_outputs.py::test_statistics_xb_yhat_xtx_match_extended_precision",
+    "k_yhat": "tests/test_gpu_outputs.py::test_statistics_xb_yhat_xtx_match_extended_precision",
+    "k_cross_cov": "tests/test_gpu_outputs.py::test_cross_covariance_outcomes_and_row_counts",
+    "k_axpy_sum": "tests/test_gpu_outputs.py::test_running_means_match_exact_sums",
+    "k_qtile": "tests/test_gpu_outputs.py::test_summary_quantiles_at_every_pad_and_row_count",
+    "k_points_acc": "tests/test_gpu_outputs.py::test_point_summaries_match_exact_moments",
 }
 
 
@@ -36,7 +38,7 @@ def _norm(name):
 
 def launched_kernels():
     """Every instantiation named by a hipLaunchKernelGGL of the host code, the macro and template wrappers expanded."""
-    src = open(SRC).read()
+    src = open(SRC).read() + open(SRC_POINTS_ACC).read()     # k_points_acc is launched from its own translation unit
     names = set()
     for m in re.finditer(r"hipLaunchKernelGGL\(\s*(\(\s*[A-Za-z_]\w*\s*<[^>]*>\s*\)|[A-Za-z_]\w*)", src):
         names.add(_norm(m.group(1).strip("() ")))
@@ -69,6 +71,7 @@ def table_routes():
 def test_every_launched_kernel_has_a_test():
     launched = launched_kernels()
     assert "k_factor_quad<4, 44, 11, true, false>" in launched and "k_sample_lean<true>" in launched   # the parser sees both forms
+    assert "k_points_acc" in launched
     table = table_routes()
     missing = sorted(n for n in launched if n not in table and n not in R.EXCLUDED and n not in COVERED_ELSEWHERE)
     assert not missing, f"launched without a test: {missing}"

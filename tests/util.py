@@ -48,7 +48,8 @@ def nice_theta(q):
     return np.concatenate([ai1, ai2, phi, thetamv, dvec])
 
 
-def make_problem(side=25, q=1, seed=0, missing=0.0, coords=None, mv_id=None, p=3, random_coords=False, **tree_kw):
+def make_problem(side=25, q=1, seed=0, missing=0.0, coords=None, mv_id=None, p=3, random_coords=False, single_obs=None,
+                 **tree_kw):
     """Synthetic inputs in the layout spamtree_mv_mcmc receives (R/spamtree_fit.R:327-362)."""
     rng = np.random.default_rng(seed)
     if coords is None:
@@ -61,7 +62,7 @@ def make_problem(side=25, q=1, seed=0, missing=0.0, coords=None, mv_id=None, p=3
             coords, mv_id = grid_coords(side, q)
     n = coords.shape[0]
     X = rng.standard_normal((n, p))
-    beta = np.array([-1.0, 0.5, 1.0, 0.25, -0.3][:p])
+    beta = np.array([-1.0, 0.5, 1.0, 0.25, -0.3, 0.7, -0.6, 0.4][:p])      # p = 1..8 (the library's limit)
     f = np.zeros(n)
     for _ in range(6):
         kx, ky, ph = rng.uniform(1, 6), rng.uniform(1, 6), rng.uniform(0, 6.28)
@@ -73,6 +74,10 @@ def make_problem(side=25, q=1, seed=0, missing=0.0, coords=None, mv_id=None, p=3
     elif missing > 0:
         y = y.copy()
         y[rng.uniform(size=n) < missing] = np.nan
+    if single_obs is not None:    # outcome `single_obs` (1-based) keeps exactly one observed row, its first finite one
+        y = y.copy()
+        rows = np.nonzero((np.asarray(mv_id) == single_obs) & np.isfinite(y))[0]
+        y[rows[1:]] = np.nan
     limited_tree = bool(tree_kw.get("limited_tree", False))
     topo = prepare(y, coords, mv_id, **tree_kw)
     s = topo.sort_ix
