@@ -34,6 +34,7 @@ extern "C" {
 #define ST_ERR_UNSUPPORTED (-4)
 
 #define ST_MAX_Q 6          /* outcomes (theta has 3q + (q>2?3:1) + q(q-1)/2 <= 39 entries) */
+#define ST_MAX_P 64         /* regressors: st_create refuses a problem with more (one pass of eight columns each through the statistics kernel) */
 #define ST_MAX_ANCESTORS 24 /* tree depth - 1 */
 
 typedef struct st_handle_s *st_handle;
@@ -43,7 +44,7 @@ typedef struct st_problem {
   int64_t n_all;               /* rows (observed + NA)                                   coords.n_rows            */
   int32_t d;                   /* coordinate columns, must be 2                           coords.n_cols            */
   int32_t q;                   /* outcomes                                                unique(mv_id)            */
-  int32_t p;                   /* regressors                                              X.n_cols                 */
+  int32_t p;                   /* regressors, 1 .. ST_MAX_P                               X.n_cols                 */
   int32_t n_groups;            /* length of res_is_ref                                                             */
   int64_t n_blocks;            /*                                                         block_names.n_elem       */
   const double *y;             /* n_all, NaN = NA                                         y_in                     */
@@ -144,10 +145,15 @@ int st_predict(st_handle h, int theta_changed);
 
 /* ---- reductions for gibbs_sample_beta / gibbs_sample_tausq (spamtree_model.cpp:1374-1375, 1397-1400).
  * xty: p x q column-major, column j = X_avail_j' (y_avail_j - w[...]);  ssq: q, sum (y - XB - w)^2 over observed rows.
- * n_obs_by_q: q (may be NULL).  The draws themselves (R::rgamma, arma::randn) stay with the host driver. */
+ * n_obs_by_q: q (may be NULL).  The draws themselves (R::rgamma, arma::randn) stay with the host driver.
+ * One reduction serves both (and is kept until w or XB changes); its order of additions depends on n_all only, not on p or q,
+ * so every statistic is reproducible bit for bit and identical on every rank of a sharded run. */
 int st_beta_stats(st_handle h, double *xty);
 int st_tausq_stats(st_handle h, double *ssq, int64_t *n_obs_by_q);
-int st_xtx(st_handle h, double *xtx);                      /* p x p x q, XtX(j) of spamtree_model.cpp:151-155 */
+/* XtX(j) = X_avail_j' X_avail_j over the observed rows of outcome j (spamtree_model.cpp:151-155), p x p x q, formed once by
+ * st_create: for p <= 8 by a serial host sum in row order, for p > 8 on the device by the statistics reduction with a column of X
+ * as the row weight (fixed shape, deterministic, XtX(j) symmetric to the bit). */
+int st_xtx(st_handle h, double *xtx);
 
 /* ---- yhat = XB + w + tausq^{1/2} * normal (spamtree_fit.cpp:384); noise==NULL: device stream 5 */
 int st_yhat(st_handle h, const double *noise, uint64_t seed, uint32_t iter, double *yhat);

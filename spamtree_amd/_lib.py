@@ -6,6 +6,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # SPAMTREE_LIB: an alternative build of the SAME library (A/B timing of kernel variants under profiles/micro); never a fallback
 LIB_PATH = os.environ.get("SPAMTREE_LIB") or os.path.join(HERE, "libspamtree_hip.so")
 
+ST_MAX_P = 64   # include/spamtree_hip.h: the most regressors st_create accepts
+
 c_dp = C.POINTER(C.c_double)
 c_ip = C.POINTER(C.c_int64)
 

@@ -217,29 +217,76 @@ __global__ void k_xb(const double *X, const int *mv, const double *B, long long 
   xb[i] = acc;
 }
 
-// partial sums for beta / tausq: per workgroup nq = p*q + q values; stage 2 reduces in workgroup order.
+// partial sums for beta / tausq: per workgroup nq = p*q + q values; stage 2 reduces in workgroup order.  Grid (STATS_WG,
+// ceil(p / 8)): slice blockIdx.y owns the columns 8 s .. min(p, 8 s + 8) - 1 of X and never reads a column >= p; slice 0
+// also owns the q sums of squares.  A row of margin v adds to acc[v][.] and e2[v] only: the update sits under the predicate
+// v == vv in a loop over vv that is fully unrolled, so every accumulator has a compile-time index and lives in a register
+// (no private array indexed at run time, no scratch), and a skipped accumulator keeps its bits whatever X holds.
+// Q = q: the accumulators are Q * 8 + Q doubles per thread.  XTX: the row weight is wt[i] (a column of X) instead of
+// y_i - w[partner_i], and no sums of squares are formed -- with weight column b, statistic v p + a is XtX(v)[a, b].
+// The order of additions into one statistic (a workgroup's chunk of ceil(n / STATS_WG) rows, a thread's serial walk over
+// every NT-th row of it, block_sum, k_stats_final) depends on neither p nor the slice.
+template <int Q, bool XTX>
 __global__ __launch_bounds__(NT) void k_stats(const double *X, const double *y, const double *w, const double *xb, const int *mv,
-                                               const unsigned char *obs, const long long *partner, long long n, int p, int q,
-                                               double *partial) {
+                                               const unsigned char *obs, const long long *partner, const double *wt, long long n,
+                                               int p, double *partial) {
   __shared__ double s_red[NT / 64];
-  const int nq = p * q + q;
-  double acc[QMAX * 8 + QMAX];  // p <= 8 enforced on the host for this kernel
-  for (int k = 0; k < nq; ++k) acc[k] = 0.0;
+  const int nq = p * Q + Q;
+  const int j0 = 8 * (int)blockIdx.y, pj = min(8, p - j0);
+  const bool ssq = !XTX && blockIdx.y == 0;
+  double acc[Q][8], e2[Q];
+#pragma unroll
+  for (int vv = 0; vv < Q; ++vv) {
+    e2[vv] = 0.0;
+#pragma unroll
+    for (int jj = 0; jj < 8; ++jj) acc[vv][jj] = 0.0;
+  }
   const long long chunk = (n + gridDim.x - 1) / gridDim.x;
   const long long lo = (long long)blockIdx.x * chunk, hi = min(n, lo + chunk);
+  const double *Xs = X + (size_t)j0 * n;
   for (long long i = lo + threadIdx.x; i < hi; i += NT) {
     if (!obs[i]) continue;
     const int v = mv[i];
-    const double rw = y[i] - w[partner[i]];
-    for (int j = 0; j < p; ++j) acc[v * p + j] += X[(size_t)j * n + i] * rw;
-    const double e = y[i] - xb[i] - w[i];
-    acc[p * q + v] += e * e;
+    const double rw = XTX ? wt[i] : y[i] - w[partner[i]];
+    double x[8];
+#pragma unroll
+    for (int jj = 0; jj < 8; ++jj) x[jj] = jj < pj ? Xs[(size_t)jj * n + i] : 0.0;
+    double e = 0.0;
+    if (ssq) e = y[i] - xb[i] - w[i];
+#pragma unroll
+    for (int vv = 0; vv < Q; ++vv) {
+      if (v == vv) {
+#pragma unroll
+        for (int jj = 0; jj < 8; ++jj) acc[vv][jj] = fma(x[jj], rw, acc[vv][jj]);   // (columns >= pj: never stored)
+        e2[vv] = fma(e, e, e2[vv]);   // fma spelled out: shared between the vv, e * e would be rounded on its own
+      }
+    }
   }
-  for (int k = 0; k < nq; ++k) {
-    const double s = block_sum(acc[k], s_red);
-    if (threadIdx.x == 0) partial[(size_t)blockIdx.x * nq + k] = s;
+#pragma unroll
+  for (int vv = 0; vv < Q; ++vv) {
+#pragma unroll
+    for (int jj = 0; jj < 8; ++jj) {
+      if (jj < pj) {   // uniform over the workgroup
+        const double s = block_sum(acc[vv][jj], s_red);
+        if (threadIdx.x == 0) partial[(size_t)blockIdx.x * nq + vv * p + j0 + jj] = s;
+      }
+    }
+  }
+  if (ssq) {
+#pragma unroll
+    for (int vv = 0; vv < Q; ++vv) {
+      const double s = block_sum(e2[vv], s_red);
+      if (threadIdx.x == 0) partial[(size_t)blockIdx.x * nq + p * Q + vv] = s;
+    }
   }
 }
+#define ST_INST_STATS(Q)                                                                                                       \
+  template __global__ void k_stats<Q, false>(const double *, const double *, const double *, const double *, const int *,    \
+                                             const unsigned char *, const long long *, const double *, long long, int, double *); \
+  template __global__ void k_stats<Q, true>(const double *, const double *, const double *, const double *, const int *,     \
+                                            const unsigned char *, const long long *, const double *, long long, int, double *);
+ST_INST_STATS(1) ST_INST_STATS(2) ST_INST_STATS(3) ST_INST_STATS(4) ST_INST_STATS(5) ST_INST_STATS(6)
+#undef ST_INST_STATS
 // one workgroup per statistic: fixed-shape tree over the STATS_WG partial sums (deterministic)
 __global__ __launch_bounds__(NT) void k_stats_final(const double *partial, int nwg, int nq, double *out) {
   __shared__ double sm[NT];
@@ -376,7 +423,7 @@ __global__ void k_loglik_grp(LoglikGrpArgs A);
 __global__ void k_sum2_partial(const double *a, const double *b, int n, double *partial);
 __global__ void k_sum2_final(const double *partial, double *out);
 __global__ void k_xb(const double *X, const int *mv, const double *B, long long n, int p, double *xb);
-__global__ void k_stats(const double *X, const double *y, const double *w, const double *xb, const int *mv, const unsigned char *obs, const long long *partner, long long n, int p, int q, double *partial);
+template <int Q, bool XTX> __global__ void k_stats(const double *X, const double *y, const double *w, const double *xb, const int *mv, const unsigned char *obs, const long long *partner, const double *wt, long long n, int p, double *partial);
 __global__ void k_stats_final(const double *partial, int nwg, int nq, double *out);
 __global__ void k_yhat(const double *xb, const double *w, const double *noise, const int *mv, long long n, const double *tsq_inv_q, double *yhat);
 __global__ void k_cross_cov(const double *c1, const int *mv1, long long n1, const double *c2, const int *mv2, long long n2, CovPar cp, double *out);

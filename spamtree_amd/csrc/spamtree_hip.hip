@@ -258,7 +258,7 @@ struct st_handle_s {
   std::vector<SimLevel> sim_levels;
 
   DevBuf<double> d_cx, d_cy, d_y, d_X, d_w, d_xb, d_z, d_B, d_panels[2], d_acc, d_logdet[2], d_loglik[2], d_scalars, d_partial,
-      d_stats, d_scratch, d_tmp_n, d_tsq;
+      d_stats, d_xtx, d_scratch, d_tmp_n, d_tsq;
   DevBuf<int> d_mv, d_anc, d_dch, d_lvl, d_pred, d_allobs, d_err;
   DevBuf<unsigned char> d_obs;
   DevBuf<long long> d_dev2model, d_partner;
@@ -297,6 +297,22 @@ static int fail_create(st_handle_s *h, int code, const std::string &msg) {
     st_destroy(h);
   }
   return code;
+}
+
+// The statistics kernel for q outcomes: k_stats<q, false> (xty and ssq), or k_stats<q, true> (the row weight is a column of X).
+typedef void (*StatsKernel)(const double *, const double *, const double *, const double *, const int *, const unsigned char *,
+                            const long long *, const double *, long long, int, double *);
+static StatsKernel stats_kernel(int q, bool xtx) {
+  static const StatsKernel tab[2][QMAX] = {
+      {k_stats<1, false>, k_stats<2, false>, k_stats<3, false>, k_stats<4, false>, k_stats<5, false>, k_stats<6, false>},
+      {k_stats<1, true>, k_stats<2, true>, k_stats<3, true>, k_stats<4, true>, k_stats<5, true>, k_stats<6, true>}};
+  return tab[xtx ? 1 : 0][q - 1];
+}
+// ... over all rows into d_partial: one slice of eight columns of X per grid row.  wt: the weight column (XtX), or null.
+static void launch_stats(st_handle_s *h, hipStream_t st, const double *wt) {
+  const StatsKernel k_stats = stats_kernel(h->q, wt != nullptr);
+  hipLaunchKernelGGL(k_stats, dim3(STATS_WG, (h->p + 7) / 8), dim3(NT), 0, st, h->d_X.p, h->d_y.p, h->d_w.p, h->d_xb.p, h->d_mv.p,
+                     h->d_obs.p, h->d_partner.p, wt, h->n_all, h->p, h->d_partial.p);
 }
 
 // Launch timing with HIP events on the launch stream, harvested lazily (no host sync inside the measured region).
@@ -375,7 +391,7 @@ extern "C" int st_destroy(st_handle h) {
   h->d_cx.free(); h->d_cy.free(); h->d_y.free(); h->d_X.free(); h->d_w.free(); h->d_xb.free(); h->d_z.free(); h->d_B.free();
   h->d_panels[0].free(); h->d_panels[1].free(); h->d_acc.free();
   for (int s = 0; s < 2; ++s) { h->d_logdet[s].free(); h->d_loglik[s].free(); }
-  h->d_scalars.free(); h->d_partial.free(); h->d_stats.free(); h->d_scratch.free(); h->d_tmp_n.free(); h->d_tsq.free();
+  h->d_scalars.free(); h->d_partial.free(); h->d_stats.free(); h->d_xtx.free(); h->d_scratch.free(); h->d_tmp_n.free(); h->d_tsq.free();
   h->d_mv.free(); h->d_anc.free(); h->d_dch.free(); h->d_lvl.free(); h->d_pred.free(); h->d_allobs.free(); h->d_err.free();
   h->d_twin.free(); h->d_wgrps.free(); h->d_lcslabs.free(); h->d_lcrow.free(); h->d_rfvoff.free(); h->d_vscr.free(); h->d_vleaf.free(); h->d_s0.free(); h->d_s0off.free(); h->d_obs.free(); h->d_dev2model.free(); h->d_partner.free(); h->d_blks.free(); h->d_grps.free(); h->d_quads.free(); h->d_gdesc.free();
   h->d_ownobs.free(); h->d_owngrp.free(); h->d_ownslow.free(); h->d_rowmask.free(); h->d_blkmask.free(); h->d_comm.free(); h->d_gather.free(); h->d_gidx.free(); h->d_gerr.free(); h->d_err2.free(); h->d_toplist.free();
@@ -423,7 +439,7 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
   *out = nullptr;
   if (pb->d != 2) { g_create_error = "only d=2 is reachable from spamtree() (R/spamtree_fit.R:58-60)"; return ST_ERR_UNSUPPORTED; }
   if (pb->q < 1 || pb->q > QMAX) { g_create_error = "q out of range"; return ST_ERR_UNSUPPORTED; }
-  if (pb->p < 1 || pb->p > 8) { g_create_error = "p must be in 1..8"; return ST_ERR_UNSUPPORTED; }
+  if (pb->p < 1 || pb->p > ST_MAX_P) { g_create_error = "p must be in 1.." + std::to_string(ST_MAX_P) + " (ST_MAX_P)"; return ST_ERR_UNSUPPORTED; }
   if (opt && (opt->world < 1 || opt->rank < 0 || opt->rank >= opt->world || opt->world > 64)) { g_create_error = "bad rank/world"; return ST_ERR_USAGE; }
   // the covariance helpers map a NaN distance to a covariance of 0 (cov_exp clamps with fmax), so a non-finite coordinate
   // would factorise silently instead of failing
@@ -1083,9 +1099,10 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
       partner[i] = (h->quirks && rank_av[r] >= 0) ? h->model2dev[rank_av[r]] : i;
     }
   }
-  // XtX(j) over observed rows of outcome j (:151-155)
+  // XtX(j) over observed rows of outcome j (:151-155).  p <= 8: this serial host loop stays, because its order of additions
+  // fixes the last bits of every existing chain; p > 8: k_stats<q, true> on the device copy of X, further down
   h->xtx.assign((size_t)pb->p * pb->p * pb->q, 0.0);
-  for (long long r = 0; r < n; ++r) {
+  for (long long r = 0; pb->p <= 8 && r < n; ++r) {
     if (!std::isfinite(pb->y[r])) continue;
     const int v = (int)(pb->mv_id[r] - 1);
     for (int a = 0; a < pb->p; ++a)
@@ -1261,6 +1278,25 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
   CCHK(h->d_err.alloc(2));
   CCHK(h->d_partial.alloc((size_t)STATS_WG * (pb->p * pb->q + pb->q)));
   CCHK(h->d_stats.alloc((size_t)pb->p * pb->q + pb->q));
+  if (pb->p > 8) {
+    // XtX(v)[a, b] is the statistic xty[a, v] with the row weight X[i, b]: one pass of k_stats per weight column b over the
+    // observed rows, reduced like every statistic (fixed shape, deterministic).  Entries [a, b] and [b, a] add the same
+    // products x_a x_b in the same order: the result is symmetric to the bit.
+    const int p = pb->p, pq = p * pb->q;
+    CCHK(h->d_xtx.alloc((size_t)p * pq));
+    for (int b2 = 0; b2 < p; ++b2) {
+      launch_stats(h, h->stream, h->d_X.p + (size_t)b2 * n);
+      hipLaunchKernelGGL(k_stats_final, dim3(pq), dim3(NT), 0, h->stream, h->d_partial.p, STATS_WG, pq + pb->q, h->d_xtx.p + (size_t)b2 * pq);
+    }
+    CCHK(hipGetLastError());
+    std::vector<double> t((size_t)p * pq);
+    CCHK(hipMemcpyAsync(t.data(), h->d_xtx.p, t.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    CCHK(hipStreamSynchronize(h->stream));
+    h->d_xtx.free();
+    for (int v = 0; v < pb->q; ++v)
+      for (int b2 = 0; b2 < p; ++b2)
+        for (int a = 0; a < p; ++a) h->xtx[(size_t)v * p * p + (size_t)b2 * p + a] = t[(size_t)b2 * pq + v * p + a];
+  }
   // scratch for the generic kernels: a bounded number of resident workgroups, each with its own slice
   {
     size_t need = 0;
@@ -2401,8 +2437,7 @@ static int run_stats(st_handle h, hipStream_t st = nullptr) {
   if (!st) st = h->stream;
   {
     ProfScope ps(h, 4, -1, 1, st);
-    hipLaunchKernelGGL(k_stats, dim3(STATS_WG), dim3(NT), 0, st, h->d_X.p, h->d_y.p, h->d_w.p, h->d_xb.p, h->d_mv.p, h->d_obs.p,
-                       h->d_partner.p, h->n_all, h->p, h->q, h->d_partial.p);
+    launch_stats(h, st, nullptr);
     hipLaunchKernelGGL(k_stats_final, dim3(nq), dim3(NT), 0, st, h->d_partial.p, STATS_WG, nq, h->d_stats.p);
   }
   HCHK(h, hipGetLastError());

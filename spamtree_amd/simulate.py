@@ -9,6 +9,7 @@ import math
 
 import numpy as np
 
+from ._lib import ST_MAX_P
 from .synthetic import theta_layout
 from .topology import prepare
 
@@ -46,8 +47,8 @@ def _check_inputs(coords, theta, mv_id, X, beta, tausq, n_draws):
     X = np.asarray(X, dtype=np.float64)
     if X.ndim == 1:
         X = X[:, None]
-    if X.ndim != 2 or X.shape[0] != n or not 1 <= X.shape[1] <= 8:
-        raise ValueError("X must be n x p with 1 <= p <= 8")
+    if X.ndim != 2 or X.shape[0] != n or not 1 <= X.shape[1] <= ST_MAX_P:
+        raise ValueError(f"X must be n x p with 1 <= p <= {ST_MAX_P}")
     if not np.isfinite(X).all():
         raise ValueError("X must be finite")
     p = X.shape[1]
