@@ -74,6 +74,22 @@ int stm_mcmc_points(const st_problem *pb, const st_options *opt, const double *s
                               double *new_cond_var, double *new_yhat, double *new_mean, double *new_var, double *new_w_mean,
                               double *new_yhat_mean, double *new_w_q, double *new_yhat_q, int32_t *new_route);
 
+/* The joint forms (st_points_set_joint): joint_id one label per point or NULL.  stm_mcmc_points_joint is stm_mcmc_points on a
+ * joint set, with two more outputs packed by st_points_joint_layout: new_cond_cov (packed length x keep, the conditional covariance
+ * of every saved draw) and new_cov (st_points_summary_get_cov).  new_cond_var is then max(diag, 0) of new_cond_cov.  The packed
+ * length is the sum of g_k^2 over the groups, known to the caller from the labels.  The chain is again the same bit for bit. */
+int stm_points_set_joint(stm_chain c, int64_t n_new, const double *coords, const int64_t *mv, const int64_t *anchor, const double *X,
+                         const int64_t *joint_id, int64_t keep_draws);
+int stm_mcmc_points_joint(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
+                          int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
+                          int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc, double *beta_mcmc,
+                          double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time, int64_t n_new,
+                          const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new, const double *X_new,
+                          const int64_t *joint_id_new, int64_t keep_draws, const double *quantiles, int32_t n_quantiles, double *new_w,
+                          double *new_cond_mean, double *new_cond_var, double *new_yhat, double *new_mean, double *new_var,
+                          double *new_w_mean, double *new_yhat_mean, double *new_w_q, double *new_yhat_q, int32_t *new_route,
+                          double *new_cond_cov, double *new_cov);
+
 #ifdef __cplusplus
 }
 #endif

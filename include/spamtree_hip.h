@@ -272,6 +272,39 @@ int st_points_summary_reserve(st_handle h, int64_t keep);
 int st_points_summary_get(st_handle h, double *mean, double *var, double *w_mean, double *yhat_mean, int64_t *n_accumulated);
 int st_points_summary_quantile(st_handle h, double q, double *w_q, double *yhat_q);
 
+/* ---- joint prediction of groups of new points.  A joint group is 1..ST_POINTS_MAX_JOINT points of the set that share one
+ * conditioning chain S (the "groups" of st_points_info are those chains) and are predicted together, e.g. the q outcomes at a site
+ * or a few neighbouring cells.  For a group G with members in the caller's order, V = Linv_S K(S, G) and u = Linv_S w_S:
+ *   cond_mean = V'u (per point, as st_points_predict),  cond_cov Sigma = K(G, G) - V'V,  cond_chol L = lower Cholesky factor of Sigma,
+ *   w_G = cond_mean + L z_G,  yhat as st_points_predict;  z and the yhat noise: the same streams 6 / 7 and per-point counters.
+ * A pivot d_j of the factorisation that is not above (P + g) 2^-52 K(x_j, x_j) (P rows of S, g members) counts as zero: L_jj and the
+ * column below it are zero, z_j is not used, and row j keeps what the earlier members explain -- a duplicate of an earlier member
+ * repeats its draw, a point on a conditioning row gets its w to rounding.  Sigma is not clamped; nothing is NaN.
+ * st_points_set_joint: st_points_set plus one label per point (any int64, members need not be adjacent); joint_id NULL is exactly
+ *   st_points_set.  ST_ERR_USAGE (naming the group) when a group's members do not end in the same chain -- give them one anchor --
+ *   and ST_ERR_UNSUPPORTED beyond ST_POINTS_MAX_JOINT members; both leave the previous point set in place.
+ * st_points_joint_layout: n_joint groups ordered by first appearance in the caller's order; group k's g_k x g_k column-major block of
+ *   cond_cov / cond_chol / st_points_summary_get_cov starts at offsets[k] (offsets: n_joint + 1, the last = the packed length); its
+ *   members, in the caller's order, are members[member_ptr[k] .. member_ptr[k + 1]) (member_ptr: n_joint + 1, members: n_new point
+ *   indices).  Any output may be NULL; call once for n_joint, then with buffers.
+ * st_points_predict_joint: st_points_predict on a joint set; cond_cov and cond_chol packed as above.  Any output may be NULL.  A
+ *   group's cond_mean, cond_cov, cond_chol and draws from a given z depend on its chain and its own members only, not on the other
+ *   groups, their order or the labels.  st_points_predict on a joint set still gives the per-point predictive.
+ * st_points_accumulate on a joint set draws jointly and also updates, per group and pair a >= b in call order, the running sum of
+ *   Sigma_ab and the Welford co-moment of the conditional means; st_points_accumulate_joint is the same call returning cond_cov /
+ *   cond_chol in place of cond_var (= max(Sigma_aa, 0) in the per-point summaries).  st_points_summary_get_cov: the packed
+ *   mean_s(Sigma_s) + cov_s(cond_mean_s), the joint form of st_points_summary_get's var; st_points_summary_reset clears it too.
+ * st_points_info reports the joint kernels under route codes of their own.  Refusals as st_points_predict. */
+#define ST_POINTS_MAX_JOINT 16
+int st_points_set_joint(st_handle h, int64_t n_new, const double *coords, const int64_t *mv, const int64_t *anchor, const double *X,
+                        const int64_t *joint_id);
+int st_points_joint_layout(st_handle h, int64_t *n_joint, int64_t *offsets, int64_t *member_ptr, int64_t *members);
+int st_points_predict_joint(st_handle h, int mode, const double *z, uint64_t seed, uint32_t iter, double *w_new, double *cond_mean,
+                            double *cond_cov, double *cond_chol, double *yhat_new);
+int st_points_accumulate_joint(st_handle h, uint64_t seed, uint32_t iter, double *w_new, double *cond_mean, double *cond_cov,
+                               double *cond_chol, double *yhat_new);
+int st_points_summary_get_cov(st_handle h, double *cov);
+
 /* ---- prior simulation from slot 0: exact draws w ~ N(0, C_DAG) of the tree's own model and y = XB + w + sqrt(tau^2_j) eps.
  * st_simulate: a root-to-leaf sweep over slot 0 as the last st_factor(h, 0, theta) left it (a deferred leaf half is finished
  *   first), Ri_u w_u = z_u - N_u w_pa(u) per block, with the handle's current beta (XB) and tau^-2.  nd draws (1..16) in one

@@ -103,6 +103,11 @@ SIGNATURES = {
     "st_points_summary_reserve": (C.c_int, [H, C.c_int64]),
     "st_points_summary_get": (C.c_int, [H, c_dp, c_dp, c_dp, c_dp, c_ip]),
     "st_points_summary_quantile": (C.c_int, [H, C.c_double, c_dp, c_dp]),
+    "st_points_set_joint": (C.c_int, [H, C.c_int64, c_dp, c_ip, c_ip, c_dp, c_ip]),
+    "st_points_joint_layout": (C.c_int, [H, c_ip, c_ip, c_ip, c_ip]),
+    "st_points_predict_joint": (C.c_int, [H, C.c_int, c_dp, C.c_uint64, C.c_uint32, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "st_points_accumulate_joint": (C.c_int, [H, C.c_uint64, C.c_uint32, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "st_points_summary_get_cov": (C.c_int, [H, c_dp]),
     "st_simulate": (C.c_int, [H, C.c_int, c_dp, c_dp, C.c_uint64, C.c_uint32, c_dp, c_dp]),
     "st_simulate_info": (C.c_int, [H, C.c_int, C.POINTER(C.c_int32), c_dp, c_dp]),
     "st_simulate_route_name": (C.c_char_p, [C.c_int32]),
@@ -132,6 +137,11 @@ SIGNATURES.update({
                                   C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(StmFlags), c_dp, c_dp, c_dp, c_dp, c_dp,
                                   c_dp, c_dp, C.c_int64, c_dp, c_ip, c_ip, c_dp, C.c_int64, c_dp, C.c_int32, c_dp, c_dp,
                                   c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, C.POINTER(C.c_int32)]),
+    "stm_points_set_joint": (C.c_int, [H, C.c_int64, c_dp, c_ip, c_ip, c_dp, c_ip, C.c_int64]),
+    "stm_mcmc_points_joint": (C.c_int, [C.POINTER(StProblem), C.POINTER(StOptions), c_dp, c_dp, C.c_int, c_dp, C.c_double, c_dp,
+                                        C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(StmFlags), c_dp, c_dp, c_dp, c_dp, c_dp,
+                                        c_dp, c_dp, C.c_int64, c_dp, c_ip, c_ip, c_dp, c_ip, C.c_int64, c_dp, C.c_int32, c_dp,
+                                        c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, C.POINTER(C.c_int32), c_dp, c_dp]),
 })
 
 # include/spamtree_tree.h (device parts of the tree builder)

@@ -400,7 +400,13 @@ extern "C" int stm_state(stm_chain c, double *theta, double *Bcoeff, double *tau
 extern "C" int stm_points_set(stm_chain c, int64_t n_new, const double *coords, const int64_t *mv, const int64_t *anchor, const double *X,
                               int64_t keep_draws) {
   if (!c || !c->h) return ST_ERR_USAGE;
-  int rc = st_points_set(c->h, n_new, coords, mv, anchor, X);
+  return stm_points_set_joint(c, n_new, coords, mv, anchor, X, nullptr, keep_draws);
+}
+
+extern "C" int stm_points_set_joint(stm_chain c, int64_t n_new, const double *coords, const int64_t *mv, const int64_t *anchor, const double *X,
+                                    const int64_t *joint_id, int64_t keep_draws) {
+  if (!c || !c->h) return ST_ERR_USAGE;
+  int rc = st_points_set_joint(c->h, n_new, coords, mv, anchor, X, joint_id);
   if (rc == 0) rc = st_points_summary_reset(c->h);
   if (rc == 0) rc = st_points_summary_reserve(c->h, keep_draws);
   if (rc != 0) { c->err = st_last_error(c->h); return rc; }
@@ -411,6 +417,8 @@ namespace {
 struct FitPoints {   // the point set of stm_mcmc_points and where its per-draw outputs go (n_new x keep, any may be NULL)
   int64_t n;
   double *w, *cond_mean, *cond_var, *yhat;
+  double *cond_cov;     // joint sets: packed length x keep, or NULL
+  int64_t cov_len;      // the packed length of st_points_joint_layout
 };
 }  // namespace
 
@@ -452,7 +460,12 @@ static int run_fit(stm_chain c, int mcmc_keep, int mcmc_burn, int mcmc_thin, uin
       if (!rc && pts) {
         const size_t o = (size_t)msaved * pts->n;
         auto col = [&](double *a) { return a ? a + o : nullptr; };
-        rc = st_points_accumulate(c->h, seed, (uint32_t)msaved, col(pts->w), col(pts->cond_mean), col(pts->cond_var), col(pts->yhat));
+        if (pts->cond_cov) {   // cond_var = max(diag, 0), from the packed blocks below
+          rc = st_points_accumulate_joint(c->h, seed, (uint32_t)msaved, col(pts->w), col(pts->cond_mean),
+                                          pts->cond_cov + (size_t)msaved * pts->cov_len, nullptr, col(pts->yhat));
+        } else {
+          rc = st_points_accumulate(c->h, seed, (uint32_t)msaved, col(pts->w), col(pts->cond_mean), col(pts->cond_var), col(pts->yhat));
+        }
         if (rc) c->err = st_last_error(c->h);
       }
       ++msaved;
@@ -489,19 +502,53 @@ extern "C" int stm_mcmc_points(const st_problem *pb, const st_options *opt, cons
                                          double *new_w, double *new_cond_mean, double *new_cond_var, double *new_yhat, double *new_mean,
                                          double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q, double *new_yhat_q,
                                          int32_t *new_route) {
+  return stm_mcmc_points_joint(pb, opt, set_unif_bounds, theta, ntheta, beta, tausq, mcmcsd, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc,
+                               yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time, n_new, coords_new, mv_new, anchor_new, X_new,
+                               nullptr, keep_draws, quantiles, n_quantiles, new_w, new_cond_mean, new_cond_var, new_yhat, new_mean, new_var,
+                               new_w_mean, new_yhat_mean, new_w_q, new_yhat_q, new_route, nullptr, nullptr);
+}
+
+extern "C" int stm_mcmc_points_joint(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
+                                     int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
+                                     int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
+                                     double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
+                                     int64_t n_new, const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new,
+                                     const double *X_new, const int64_t *joint_id_new, int64_t keep_draws, const double *quantiles,
+                                     int32_t n_quantiles, double *new_w, double *new_cond_mean, double *new_cond_var, double *new_yhat,
+                                     double *new_mean, double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q,
+                                     double *new_yhat_q, int32_t *new_route, double *new_cond_cov, double *new_cov) {
+  if ((new_cond_cov || new_cov) && !joint_id_new) return ST_ERR_USAGE;
   if (n_quantiles < 0 || (n_quantiles > 0 && (!quantiles || keep_draws < 1))) return ST_ERR_USAGE;   // a quantile needs stored draws
   for (int32_t i = 0; i < n_quantiles; ++i) if (!(quantiles[i] >= 0.0 && quantiles[i] <= 1.0)) return ST_ERR_USAGE;
   if ((new_yhat || new_yhat_mean || new_yhat_q) && !X_new) return ST_ERR_USAGE;
   stm_chain c = nullptr;
   int rc = stm_create(pb, opt, set_unif_bounds, mcmcsd, theta, ntheta, beta, tausq, seed, flags, &c);
-  if (rc == 0) rc = stm_points_set(c, n_new, coords_new, mv_new, anchor_new, X_new, keep_draws);   // refusals: before any factorisation
+  if (rc == 0) rc = stm_points_set_joint(c, n_new, coords_new, mv_new, anchor_new, X_new, joint_id_new, keep_draws);   // refusals: before any factorisation
+  int64_t nj = 0;
+  std::vector<int64_t> joff, jptr, jmem;
+  std::vector<double> cov_scratch;
+  if (rc == 0 && joint_id_new) {
+    rc = st_points_joint_layout(c->h, &nj, nullptr, nullptr, nullptr);
+    joff.resize(nj + 1); jptr.resize(nj + 1); jmem.resize(n_new);
+    if (rc == 0) rc = st_points_joint_layout(c->h, &nj, joff.data(), jptr.data(), jmem.data());
+    if (rc == 0 && !new_cond_cov && new_cond_var) cov_scratch.resize((size_t)joff[nj] * std::max(mcmc_keep, 0));
+  }
   if (rc == 0) rc = stm_init(c);
   if (rc != 0) { stm_destroy(c); return rc; }
-  const FitPoints pts{n_new, new_w, new_cond_mean, new_cond_var, new_yhat};
+  double *const ccov = !joint_id_new ? nullptr : (new_cond_cov ? new_cond_cov : (cov_scratch.empty() ? nullptr : cov_scratch.data()));
+  const FitPoints pts{n_new, new_w, new_cond_mean, new_cond_var, new_yhat, ccov, joint_id_new ? joff[nj] : 0};
   rc = run_fit(c, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc, yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time,
                &pts);
+  if (rc == 0 && ccov && new_cond_var)
+    for (int s = 0; s < mcmc_keep; ++s)
+      for (int64_t k = 0; k < nj; ++k) {
+        const int64_t g = jptr[k + 1] - jptr[k];
+        for (int64_t a = 0; a < g; ++a)
+          new_cond_var[(size_t)s * n_new + jmem[jptr[k] + a]] = std::max(ccov[(size_t)s * joff[nj] + joff[k] + a * (g + 1)], 0.0);
+      }
   if (rc == 0 && mcmc_keep > 0 && (new_mean || new_var || new_w_mean || new_yhat_mean))
     rc = st_points_summary_get(c->h, new_mean, new_var, new_w_mean, new_yhat_mean, nullptr);
+  if (rc == 0 && mcmc_keep > 0 && new_cov) rc = st_points_summary_get_cov(c->h, new_cov);
   for (int32_t i = 0; rc == 0 && i < n_quantiles && (new_w_q || new_yhat_q); ++i)
     rc = st_points_summary_quantile(c->h, quantiles[i], new_w_q ? new_w_q + (size_t)i * n_new : nullptr,
                                     new_yhat_q ? new_yhat_q + (size_t)i * n_new : nullptr);

@@ -22,6 +22,8 @@
 // (k_factor_generic.hip, k_factor_mfma.hip, k_factor_quad.hip, k_factor_wide.hip, k_sample.hip, k_misc.hip); the headers
 // included here give their argument structures, launch constants and prototypes.
 
+#include <unordered_map>
+
 #include "st_device.hpp"
 #include "factor_generic.hpp"
 #include "factor_mfma.hpp"
@@ -33,6 +35,7 @@
 #include "sample_kernels.hpp"
 #include "misc_kernels.hpp"
 #include "predict_points.hpp"
+#include "predict_joint.hpp"
 #include "simulate_kernels.hpp"
 
 // ===============================================================================================================
@@ -2756,7 +2759,21 @@ struct PointSet {
   // st_points_accumulate: PA_NACC x n accumulators, and with st_points_summary_reserve the draws themselves, [keep][n] each
   DevBuf<double> d_acc, d_keep_w, d_keep_yhat;
   long long n_acc = 0, keep_cap = 0, n_kept = 0;
+  // st_points_set_joint: the joint groups in layout order (first appearance), their packing into slots and the pair accumulators
+  bool joint = false;
+  long long n_joint = 0, cov_total = 0;
+  int jtile128 = 0, jtile256 = 0, jgrid_generic = 0;
+  double j_alg_bytes = 0.0, j_flops = 0.0;
+  std::vector<int64_t> j_off, j_mptr, j_mem;   // packed block offsets (n_joint + 1), member list pointers (n_joint + 1), members
+  DevBuf<PtJoint> d_jgroups;
+  DevBuf<long long> d_jmem;
+  DevBuf<PtCol> d_jcols;
+  DevBuf<PtTile> d_jtiles;
+  DevBuf<int> d_jgen, d_pt_grp, d_pt_a;
+  DevBuf<double> d_jout, d_jscratch, d_pacc;   // cov and chol of the last call (2 x cov_total); scratch; pair accumulators
   void free() {
+    d_jgroups.free(); d_jmem.free(); d_jcols.free(); d_jtiles.free(); d_jgen.free(); d_pt_grp.free(); d_pt_a.free();
+    d_jout.free(); d_jscratch.free(); d_pacc.free();
     d_px.free(); d_py.free(); d_X.free(); d_z.free(); d_out.free(); d_scratch.free(); d_pmv.free(); d_chain_blk.free(); d_pt_chain.free();
     d_gen.free(); d_order.free(); d_chains.free(); d_tiles.free(); d_acc.free(); d_keep_w.free(); d_keep_yhat.free();
   }
@@ -2766,7 +2783,9 @@ static void points_free(st_handle_s *h) {
   if (h->pts) { h->pts->free(); delete h->pts; h->pts = nullptr; }
 }
 
-extern "C" int st_points_set(st_handle h, int64_t n_new, const double *coords, const int64_t *mv, const int64_t *anchor, const double *X) {
+// st_points_set (joint_id NULL) and st_points_set_joint
+static int points_set_impl(st_handle h, int64_t n_new, const double *coords, const int64_t *mv, const int64_t *anchor, const double *X,
+                           const int64_t *joint_id) {
   if (!h) return ST_ERR_USAGE;
   if (h->limited) { h->err = "st_points_set: limited_tree handles are not supported (new-point prediction is out of scope for them)"; return ST_ERR_UNSUPPORTED; }
   if (h->world > 1) { h->err = "st_points_set: multi-GPU handles (world > 1) are not supported (new-point prediction is out of scope for them)"; return ST_ERR_UNSUPPORTED; }
@@ -2779,12 +2798,6 @@ extern "C" int st_points_set(st_handle h, int64_t n_new, const double *coords, c
     if (mv[i] < 1 || mv[i] > h->q) { h->err = "st_points_set: margin of point " + std::to_string(i) + " is not in 1..q"; return ST_ERR_USAGE; }
     if (!std::isfinite(coords[i]) || !std::isfinite(coords[n_new + i])) { h->err = "st_points_set: coordinates must be finite"; return ST_ERR_USAGE; }
   }
-  HCHK(h, hipSetDevice(h->device));
-  points_free(h);
-  PointSet *ps = new PointSet();
-  h->pts = ps;
-  ps->n = n_new;
-  if (n_new == 0) return ST_OK;
   // conditioning chain of every point: ends at r = the anchor (reference) or its last parent (non-reference)
   std::vector<int> rdev(n_new);
   for (int64_t i = 0; i < n_new; ++i) {
@@ -2792,6 +2805,41 @@ extern "C" int st_points_set(st_handle h, int64_t n_new, const double *coords, c
     const Blk &B = h->blks[b];
     rdev[i] = B.isref ? b : (B.nanc > 0 ? h->anc_idx[B.anc_ptr + B.nanc - 1] : -1);
   }
+  // joint groups: by first appearance, members in the caller's order; one chain and at most ST_POINTS_MAX_JOINT members each
+  std::vector<int64_t> j_mptr, j_mem;
+  std::vector<int> pt_grp, pt_a;
+  if (joint_id) {
+    std::unordered_map<int64_t, int> index;
+    std::vector<int> gsz;
+    pt_grp.resize(n_new); pt_a.resize(n_new);
+    for (int64_t i = 0; i < n_new; ++i) {
+      auto it = index.find(joint_id[i]);
+      if (it == index.end()) { it = index.emplace(joint_id[i], (int)gsz.size()).first; gsz.push_back(0); j_mem.push_back(i); }
+      const int k = it->second;
+      if (rdev[i] != rdev[j_mem[k]]) {
+        h->err = "st_points_set_joint: the members of joint group " + std::to_string(joint_id[i]) + " do not end in the same conditioning chain (point " +
+                 std::to_string(i) + " and point " + std::to_string(j_mem[k]) + ")";
+        return ST_ERR_USAGE;
+      }
+      pt_grp[i] = k; pt_a[i] = gsz[k]++;
+      if (gsz[k] > ST_POINTS_MAX_JOINT) {
+        h->err = "st_points_set_joint: joint group " + std::to_string(joint_id[i]) + " has more than " + std::to_string(ST_POINTS_MAX_JOINT) +
+                 " members (ST_POINTS_MAX_JOINT)";
+        return ST_ERR_UNSUPPORTED;
+      }
+    }
+    j_mptr.assign(gsz.size() + 1, 0);
+    for (size_t k = 0; k < gsz.size(); ++k) j_mptr[k + 1] = j_mptr[k] + gsz[k];
+    j_mem.assign(n_new, 0);
+    for (int64_t i = 0; i < n_new; ++i) j_mem[j_mptr[pt_grp[i]] + pt_a[i]] = i;
+  }
+  HCHK(h, hipSetDevice(h->device));
+  points_free(h);
+  PointSet *ps = new PointSet();
+  h->pts = ps;
+  ps->n = n_new;
+  if (joint_id) { ps->joint = true; ps->j_off.assign(1, 0); ps->j_mptr.assign(1, 0); }
+  if (n_new == 0) return ST_OK;
   std::vector<int> keys(rdev);
   std::sort(keys.begin(), keys.end());
   keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
@@ -2877,18 +2925,104 @@ extern "C" int st_points_set(st_handle h, int64_t n_new, const double *coords, c
     HCHK(h, ps->d_X.upload(xv));
     ps->has_X = true;
   }
+  if (!joint_id) return ST_OK;
+  // ---- the joint packing: MFMA chains into 16-column slots of whole groups, four slots to a workgroup, one chain per workgroup;
+  // the groups of the other chains one workgroup each
+  const int64_t nj = (int64_t)j_mptr.size() - 1;
+  std::vector<PtJoint> groups(nj);
+  std::vector<int64_t> j_off(nj + 1, 0);
+  std::vector<std::vector<int>> by_chain(keys.size());
+  for (int64_t k = 0; k < nj; ++k) {
+    const int g = (int)(j_mptr[k + 1] - j_mptr[k]);
+    PtJoint &G = groups[k];
+    G.cov_off = j_off[k]; G.first = (int)j_mptr[k]; G.g = g; G.chain = chain_of[j_mem[j_mptr[k]]]; G.pad = 0;
+    j_off[k + 1] = j_off[k] + (int64_t)g * g;
+    by_chain[G.chain].push_back((int)k);
+  }
+  std::vector<PtTile> jtiles;
+  std::vector<PtCol> jcols;
+  std::vector<int> jgen;
+  double jb = 0.0, jf = 0.0;
+  for (int pass = 0; pass < 3; ++pass)
+    for (size_t c = 0; c < keys.size(); ++c) {
+      if (cls[c] != pass || by_chain[c].empty()) continue;
+      double pb, tf;
+      chain_cost(chains[c], &pb, &tf);
+      const double rows = chains[c].rows;
+      for (int k : by_chain[c]) {
+        const double g = groups[k].g;
+        jb += g * (per_point_bytes + 8.0) + 2.0 * g * g * 8.0;                    // + the member index; cov and chol out
+        jf += g * (g + 1.0) * rows + g * g * g / 3.0 + g * (g + 1.0);             // the Gram, the factorisation, L z
+      }
+      if (pass == 2) {
+        for (int k : by_chain[c]) {
+          jgen.push_back(k);
+          jb += pb + groups[k].g * 2.0 * rows * 8.0;                              // the chain once per group; V written and read
+          jf += (groups[k].g + 1.0) * (tf + 2.0 * rows);
+        }
+        continue;
+      }
+      int slot = 4, used = 16;                                                     // no open tile
+      for (int k : by_chain[c]) {
+        const int g = groups[k].g;
+        if (used + g > 16) {
+          if (++slot >= 4) {
+            PtTile T; T.chain = (int)c; T.p0 = 0; T.np = 0; T.pad = 0;
+            jtiles.push_back(T);
+            jcols.resize(jcols.size() + PP_NCOL, PtCol{k, -1});
+            if (pass == 0) ++ps->jtile128; else ++ps->jtile256;
+            jb += pb; jf += tf;
+            slot = 0;
+          }
+          used = 0;
+          jtiles.back().np = slot + 1;
+        }
+        PtCol *col = jcols.data() + (jtiles.size() - 1) * PP_NCOL + slot * 16 + used;
+        for (int a = 0; a < g; ++a) { col[a].grp = k; col[a].a = a; }
+        used += g;
+        jf += g * (tf + 4.0 * rows);
+      }
+    }
+  ps->n_joint = nj; ps->cov_total = j_off[nj];
+  ps->j_alg_bytes = jb; ps->j_flops = jf;
+  ps->jgrid_generic = (int)std::min<size_t>(jgen.size(), (size_t)4 * h->sm_count);
+  std::vector<long long> jmem_ll(j_mem.begin(), j_mem.end());
+  if (jtiles.empty()) jtiles.push_back(PtTile{0, 0, 0, 0});
+  if (jcols.empty()) jcols.push_back(PtCol{0, -1});
+  if (jgen.empty()) jgen.push_back(0);
+  HCHK(h, ps->d_jgroups.upload(groups)); HCHK(h, ps->d_jmem.upload(jmem_ll)); HCHK(h, ps->d_jtiles.upload(jtiles));
+  HCHK(h, ps->d_jcols.upload(jcols)); HCHK(h, ps->d_jgen.upload(jgen)); HCHK(h, ps->d_pt_grp.upload(pt_grp)); HCHK(h, ps->d_pt_a.upload(pt_a));
+  HCHK(h, ps->d_jout.alloc((size_t)2 * ps->cov_total));
+  if (ps->jgrid_generic > 0) HCHK(h, ps->d_jscratch.alloc((size_t)ps->jgrid_generic * PJ_SCRATCH_COLS * ps->scratch_stride));
+  ps->j_off = j_off; ps->j_mptr = j_mptr; ps->j_mem = j_mem;
+  return ST_OK;
+}
+
+extern "C" int st_points_set(st_handle h, int64_t n_new, const double *coords, const int64_t *mv, const int64_t *anchor, const double *X) {
+  return points_set_impl(h, n_new, coords, mv, anchor, X, nullptr);
+}
+
+extern "C" int st_points_set_joint(st_handle h, int64_t n_new, const double *coords, const int64_t *mv, const int64_t *anchor, const double *X,
+                                   const int64_t *joint_id) {
+  return points_set_impl(h, n_new, coords, mv, anchor, X, joint_id);
+}
+
+extern "C" int st_points_joint_layout(st_handle h, int64_t *n_joint, int64_t *offsets, int64_t *member_ptr, int64_t *members) {
+  if (!h) return ST_ERR_USAGE;
+  const PointSet *ps = h->pts;
+  if (!ps || !ps->joint) { h->err = "st_points_joint_layout before st_points_set_joint"; return ST_ERR_USAGE; }
+  if (n_joint) *n_joint = ps->n_joint;
+  if (offsets) std::copy(ps->j_off.begin(), ps->j_off.end(), offsets);
+  if (member_ptr) std::copy(ps->j_mptr.begin(), ps->j_mptr.end(), member_ptr);
+  if (members) std::copy(ps->j_mem.begin(), ps->j_mem.end(), members);
   return ST_OK;
 }
 
 // launches the k_points_* routes of the point set on slot 0 and the current w / beta / tausq_inv into ps->d_out (w, mean, var,
 // yhat: n doubles each, caller order; out[k] false: that output is not written).  No synchronisation.
-static int points_run(st_handle h, PointSet *ps, int mode, bool use_z, uint64_t seed, uint32_t iter, const bool out[4], const char *who) {
-  CovPar cp;
-  int rc = make_covpar(h, h->theta[0].data(), (int)h->theta[0].size(), &cp);
-  if (rc) return rc;
+static void points_args(st_handle h, PointSet *ps, int mode, bool use_z, uint64_t seed, uint32_t iter, const bool out[4], PointsArgs &A) {
   const long long n = ps->n;
   double *o = ps->d_out.p;
-  PointsArgs A;
   std::memset(&A, 0, sizeof(A));
   A.blks = h->d_blks.p; A.chain_blk = ps->d_chain_blk.p; A.chains = ps->d_chains.p; A.tiles = ps->d_tiles.p; A.ntiles = 0;
   A.gen_list = ps->d_gen.p; A.ngen = ps->grid_generic > 0 ? (int)(ps->d_gen.n) : 0;
@@ -2899,6 +3033,14 @@ static int points_run(st_handle h, PointSet *ps, int mode, bool use_z, uint64_t 
   A.w_new = out[0] ? o : nullptr; A.mean = out[1] ? o + n : nullptr; A.var = out[2] ? o + 2 * n : nullptr;
   A.yhat = out[3] ? o + 3 * n : nullptr;
   A.scratch = ps->d_scratch.p; A.scratch_stride = ps->scratch_stride;
+}
+
+static int points_run(st_handle h, PointSet *ps, int mode, bool use_z, uint64_t seed, uint32_t iter, const bool out[4], const char *who) {
+  CovPar cp;
+  int rc = make_covpar(h, h->theta[0].data(), (int)h->theta[0].size(), &cp);
+  if (rc) return rc;
+  PointsArgs A;
+  points_args(h, ps, mode, use_z, seed, iter, out, A);
   PointsLaunch L;
   L.ntile128 = ps->ntile128; L.ntile256 = ps->ntile256; L.grid_generic = ps->grid_generic;
   ProfScope pscope(h, 6);
@@ -2932,17 +3074,70 @@ extern "C" int st_points_predict(st_handle h, int mode, const double *z, uint64_
   return ST_OK;
 }
 
-extern "C" int st_points_info(st_handle h, int32_t *route, int64_t *n_groups, double *alg_bytes, double *flops) {
-  if (!h) return ST_ERR_USAGE;
-  const PointSet *ps = h->pts;
-  if (route) *route = ps ? ps->route_mask : 0;
-  if (n_groups) *n_groups = ps ? ps->n_chains : 0;
-  if (alg_bytes) *alg_bytes = ps ? ps->alg_bytes : 0.0;
-  if (flops) *flops = ps ? ps->flops : 0.0;
+// the joint routes of the point set (st_points_set_joint) into ps->d_out as points_run, plus cov and chol into ps->d_jout
+static int points_run_joint(st_handle h, PointSet *ps, int mode, bool use_z, uint64_t seed, uint32_t iter, const bool out[4], bool want_cov,
+                            bool want_chol, const char *who) {
+  CovPar cp;
+  int rc = make_covpar(h, h->theta[0].data(), (int)h->theta[0].size(), &cp);
+  if (rc) return rc;
+  JointArgs J;
+  std::memset(&J, 0, sizeof(J));
+  points_args(h, ps, mode, use_z, seed, iter, out, J.P);
+  J.P.tiles = ps->d_jtiles.p;
+  J.P.scratch = ps->d_jscratch.p;
+  J.groups = ps->d_jgroups.p; J.members = ps->d_jmem.p; J.cols = ps->d_jcols.p;
+  J.gen_groups = ps->d_jgen.p; J.ngen_groups = ps->jgrid_generic > 0 ? (int)ps->d_jgen.n : 0;
+  J.cov = want_cov ? ps->d_jout.p : nullptr; J.chol = want_chol ? ps->d_jout.p + ps->cov_total : nullptr;
+  JointLaunch L;
+  L.ntile128 = ps->jtile128; L.ntile256 = ps->jtile256; L.grid_generic = ps->jgrid_generic;
+  ProfScope pscope(h, 6);
+  const int e = points_joint_launch(L, J, cp, h->stream, &ps->route_mask);
+  if (e) { h->err = std::string(who) + " launch: " + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
   return ST_OK;
 }
 
-extern "C" const char *st_points_route_name(int32_t code) { return points_route_name(code); }
+extern "C" int st_points_predict_joint(st_handle h, int mode, const double *z, uint64_t seed, uint32_t iter, double *w_new, double *cond_mean,
+                                       double *cond_cov, double *cond_chol, double *yhat_new) {
+  if (!h) return ST_ERR_USAGE;
+  if (h->limited || h->world > 1) { h->err = "st_points_predict_joint: limited_tree and multi-GPU handles are not supported (out of scope)"; return ST_ERR_UNSUPPORTED; }
+  if (!h->pts || !h->pts->joint) { h->err = "st_points_predict_joint before st_points_set_joint"; return ST_ERR_USAGE; }
+  if (h->theta[0].empty()) { h->err = "st_points_predict_joint before st_factor(slot 0)"; return ST_ERR_USAGE; }
+  if (h->factor_open) { h->err = "st_points_predict_joint between st_factor_enqueue and st_factor_finish"; return ST_ERR_USAGE; }
+  if (mode != 0 && mode != 1) { h->err = "st_points_predict_joint: mode must be 0 (draw) or 1 (conditional mean)"; return ST_ERR_USAGE; }
+  PointSet *ps = h->pts;
+  if (yhat_new && !ps->has_X) { h->err = "st_points_predict_joint: yhat_new needs the regressors X of st_points_set_joint"; return ST_ERR_USAGE; }
+  ps->route_mask = 0;
+  if (ps->n == 0) return ST_OK;
+  HCHK(h, hipSetDevice(h->device));
+  const long long n = ps->n;
+  if (z && mode == 0) HCHK(h, hipMemcpyAsync(ps->d_z.p, z, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  const bool out[4] = {w_new != nullptr, cond_mean != nullptr, false, yhat_new != nullptr};
+  const int rc = points_run_joint(h, ps, mode, z && mode == 0, seed, iter, out, cond_cov != nullptr, cond_chol != nullptr, "st_points_predict_joint");
+  if (rc) return rc;
+  double *dst[4] = {w_new, cond_mean, nullptr, yhat_new};
+  for (int k = 0; k < 4; ++k)
+    if (dst[k]) HCHK(h, hipMemcpyAsync(dst[k], ps->d_out.p + (size_t)k * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  const size_t cb = (size_t)ps->cov_total * sizeof(double);
+  if (cond_cov) HCHK(h, hipMemcpyAsync(cond_cov, ps->d_jout.p, cb, hipMemcpyDeviceToHost, h->stream));
+  if (cond_chol) HCHK(h, hipMemcpyAsync(cond_chol, ps->d_jout.p + ps->cov_total, cb, hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  return ST_OK;
+}
+
+extern "C" int st_points_info(st_handle h, int32_t *route, int64_t *n_groups, double *alg_bytes, double *flops) {
+  if (!h) return ST_ERR_USAGE;
+  const PointSet *ps = h->pts;
+  const bool jr = ps && (ps->route_mask >> (PP_ROUTE_JOINT_MFMA128 - 1)) != 0;   // the last call took the joint routes
+  if (route) *route = ps ? ps->route_mask : 0;
+  if (n_groups) *n_groups = ps ? ps->n_chains : 0;
+  if (alg_bytes) *alg_bytes = ps ? (jr ? ps->j_alg_bytes : ps->alg_bytes) : 0.0;
+  if (flops) *flops = ps ? (jr ? ps->j_flops : ps->flops) : 0.0;
+  return ST_OK;
+}
+
+extern "C" const char *st_points_route_name(int32_t code) {
+  return code < PP_ROUTE_COUNT ? points_route_name(code) : points_joint_route_name(code);
+}
 
 // ---- predictive summaries of the point set over saved iterations (st_points_accumulate; the kernel lives in k_points_acc.hip) ----
 static int points_refuse(st_handle h, const char *who) {
@@ -2962,6 +3157,9 @@ extern "C" int st_points_summary_reset(st_handle h) {
   const size_t cnt = (size_t)PA_NACC * ps->n;
   if (cnt > 0 && !ps->d_acc.p) HCHK(h, ps->d_acc.alloc(cnt));
   if (cnt > 0) HCHK(h, hipMemsetAsync(ps->d_acc.p, 0, cnt * sizeof(double), h->stream));
+  const size_t pcnt = (size_t)2 * ps->cov_total;
+  if (pcnt > 0 && !ps->d_pacc.p) HCHK(h, ps->d_pacc.alloc(pcnt));
+  if (pcnt > 0) HCHK(h, hipMemsetAsync(ps->d_pacc.p, 0, pcnt * sizeof(double), h->stream));
   ps->n_acc = 0; ps->n_kept = 0;
   return ST_OK;
 }
@@ -2982,8 +3180,9 @@ extern "C" int st_points_summary_reserve(st_handle h, int64_t keep) {
   return ST_OK;
 }
 
-extern "C" int st_points_accumulate(st_handle h, uint64_t seed, uint32_t iter, double *w_new, double *cond_mean, double *cond_var,
-                                    double *yhat_new) {
+// st_points_accumulate and st_points_accumulate_joint (cond_cov, cond_chol: a joint set's packed outputs, NULL otherwise)
+static int points_accumulate(st_handle h, uint64_t seed, uint32_t iter, double *w_new, double *cond_mean, double *cond_var, double *yhat_new,
+                             double *cond_cov, double *cond_chol) {
   if (!h) return ST_ERR_USAGE;
   if (const int rc = points_refuse(h, "st_points_accumulate")) return rc;
   if (h->theta[0].empty()) { h->err = "st_points_accumulate before st_factor(slot 0)"; return ST_ERR_USAGE; }
@@ -2996,9 +3195,18 @@ extern "C" int st_points_accumulate(st_handle h, uint64_t seed, uint32_t iter, d
   HCHK(h, hipSetDevice(h->device));
   const long long n = ps->n;
   const bool out[4] = {true, true, true, ps->has_X};
-  int rc = points_run(h, ps, 0, false, seed, iter, out, "st_points_accumulate");
+  int rc = ps->joint ? points_run_joint(h, ps, 0, false, seed, iter, out, true, cond_chol != nullptr, "st_points_accumulate")
+                     : points_run(h, ps, 0, false, seed, iter, out, "st_points_accumulate");
   if (rc) return rc;
   const double *o = ps->d_out.p;
+  if (ps->joint) {   // the pair accumulators, before k_points_acc moves the Welford means
+    PointsPairArgs B;
+    B.mean = o + n; B.cov = ps->d_jout.p; B.acc = ps->d_acc.p; B.pacc = ps->d_pacc.p; B.groups = ps->d_jgroups.p; B.members = ps->d_jmem.p;
+    B.pt_grp = ps->d_pt_grp.p; B.pt_a = ps->d_pt_a.p; B.count = (double)(ps->n_acc + 1); B.n = n; B.cov_total = ps->cov_total;
+    ProfScope pscope(h, 6);
+    const int e = points_pair_acc_launch(B, h->stream);
+    if (e) { h->err = std::string("st_points_accumulate launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+  }
   PointsAccArgs A;
   A.w = o; A.mean = o + n; A.var = o + 2 * n; A.yhat = ps->has_X ? o + 3 * n : nullptr;
   A.acc = ps->d_acc.p;
@@ -3018,7 +3226,47 @@ extern "C" int st_points_accumulate(st_handle h, uint64_t seed, uint32_t iter, d
   bool copied = false;
   for (int k = 0; k < 4; ++k)
     if (dst[k]) { HCHK(h, hipMemcpyAsync(dst[k], o + (size_t)k * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream)); copied = true; }
+  const size_t cb = (size_t)ps->cov_total * sizeof(double);
+  if (cond_cov) { HCHK(h, hipMemcpyAsync(cond_cov, ps->d_jout.p, cb, hipMemcpyDeviceToHost, h->stream)); copied = true; }
+  if (cond_chol) { HCHK(h, hipMemcpyAsync(cond_chol, ps->d_jout.p + ps->cov_total, cb, hipMemcpyDeviceToHost, h->stream)); copied = true; }
   if (copied) HCHK(h, hipStreamSynchronize(h->stream));
+  return ST_OK;
+}
+
+extern "C" int st_points_accumulate(st_handle h, uint64_t seed, uint32_t iter, double *w_new, double *cond_mean, double *cond_var,
+                                    double *yhat_new) {
+  return points_accumulate(h, seed, iter, w_new, cond_mean, cond_var, yhat_new, nullptr, nullptr);
+}
+
+extern "C" int st_points_accumulate_joint(st_handle h, uint64_t seed, uint32_t iter, double *w_new, double *cond_mean, double *cond_cov,
+                                          double *cond_chol, double *yhat_new) {
+  if (!h) return ST_ERR_USAGE;
+  if (h->pts && !h->pts->joint) { h->err = "st_points_accumulate_joint before st_points_set_joint"; return ST_ERR_USAGE; }
+  return points_accumulate(h, seed, iter, w_new, cond_mean, nullptr, yhat_new, cond_cov, cond_chol);
+}
+
+extern "C" int st_points_summary_get_cov(st_handle h, double *cov) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_summary_get_cov")) return rc;
+  PointSet *ps = h->pts;
+  if (!ps->joint) { h->err = "st_points_summary_get_cov before st_points_set_joint"; return ST_ERR_USAGE; }
+  if (ps->n_acc == 0) { h->err = "st_points_summary_get_cov: no iteration accumulated"; return ST_ERR_USAGE; }
+  if (ps->cov_total == 0 || !cov) return ST_OK;
+  HCHK(h, hipSetDevice(h->device));
+  const long long tot = ps->cov_total;
+  std::vector<double> acc((size_t)2 * tot);
+  HCHK(h, hipMemcpyAsync(acc.data(), ps->d_pacc.p, acc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  const double cnt = (double)ps->n_acc;
+  for (long long k = 0; k < ps->n_joint; ++k) {
+    const long long o = ps->j_off[k], g = ps->j_mptr[k + 1] - ps->j_mptr[k];
+    for (long long a = 0; a < g; ++a)
+      for (long long b = 0; b <= a; ++b) {
+        const long long e = o + a + b * g;
+        const double v = acc[e] / cnt + acc[tot + e] / cnt;   // mean conditional covariance + covariance of the conditional means
+        cov[e] = v; cov[o + b + a * g] = v;
+      }
+  }
   return ST_OK;
 }
 

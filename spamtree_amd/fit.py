@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .model import SpamTreeError, _dp, _f64, _i64, _ip, _lists_to_csr
+from .model import SpamTreeError, _dp, _f64, _i64, _ip, _lists_to_csr, joint_labels
 
 
 def _problem(y, X, coords, mv_id, res_is_ref, parents, children, block_names, block_groups, indexing):
@@ -163,9 +163,9 @@ class Chain:
 def _points_inputs(new_points, p, q, new_quantiles):
     """Checks the point set of spamtree_mv_mcmc(new_points=...) against itself and the problem, before any device call."""
     pts = dict(new_points)
-    unknown = set(pts) - {"coords", "mv", "anchor", "X"}
+    unknown = set(pts) - {"coords", "mv", "anchor", "X", "joint"}
     if unknown:
-        raise ValueError(f"new_points: unknown keys {sorted(unknown)} (coords, mv, anchor, X)")
+        raise ValueError(f"new_points: unknown keys {sorted(unknown)} (coords, mv, anchor, X, joint)")
     coords = np.asarray(pts["coords"], dtype=np.float64)
     if coords.ndim != 2 or coords.shape[1] != 2:
         raise ValueError("new_points: coords must be n_new x 2")
@@ -188,7 +188,29 @@ def _points_inputs(new_points, p, q, new_quantiles):
     qs = np.asarray(new_quantiles, dtype=np.float64).reshape(-1)
     if not np.all((qs >= 0.0) & (qs <= 1.0)):
         raise ValueError("new_quantiles must lie in [0, 1]")
-    return np.asfortranarray(coords), _i64(mv), _i64(anchor), X, qs
+    labels = pts.get("joint")
+    if labels is not None:
+        try:
+            labels = joint_labels(labels, n_new)
+        except ValueError as e:
+            raise ValueError(f"new_points: {e}") from None
+    return np.asfortranarray(coords), _i64(mv), _i64(anchor), X, qs, labels
+
+
+def _joint_layout(labels):
+    """Host mirror of st_points_joint_layout: groups by first appearance, members in the caller's order, g x g blocks."""
+    _, first, inv = np.unique(labels, return_index=True, return_inverse=True)
+    rank = np.empty(first.size, dtype=np.int64)
+    rank[np.argsort(first, kind="stable")] = np.arange(first.size)
+    grp = rank[np.asarray(inv).reshape(-1)]
+    groups = [np.nonzero(grp == k)[0] for k in range(first.size)]
+    off = np.concatenate([[0], np.cumsum([g.size ** 2 for g in groups])]).astype(np.int64)
+    return groups, off
+
+
+def _unpack_joint(packed, groups, off):
+    blocks = [np.asarray(packed[off[k]:off[k + 1]]).reshape(g.size, g.size, order="F").copy() for k, g in enumerate(groups)]
+    return np.stack(blocks) if blocks and len({b.shape for b in blocks}) == 1 else blocks
 
 
 def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, parents, children, limited_tree,
@@ -206,7 +228,11 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     locations on every saved iteration, on the device (stm_mcmc_points); the chain is the same bit for bit.  Then the
     result also holds ``new``: dict(mean, var, w_mean, yhat_mean, quantiles={q: (w_q, yhat_q)}, route) and, with
     ``new_draws``, the per-draw n_new x keep arrays ``w``, ``cond_mean``, ``cond_var``, ``yhat`` (yhat entries None
-    without X).  ``new_quantiles`` keeps the draws on the device.  With points, a failure raises SpamTreeError."""
+    without X).  ``new_quantiles`` keeps the draws on the device.  With points, a failure raises SpamTreeError.
+    ``new_points["joint"]``: one integer label per point; each label's points (at most 16, one anchor) are drawn jointly
+    (stm_mcmc_points_joint) and ``new`` also holds ``groups`` (member indices per group), ``cov`` (per group the predictive
+    covariance, mean conditional covariance + covariance of the conditional means) and, with ``new_draws``, ``cond_cov``
+    (per saved draw, per group)."""
     if new_points is not None:
         pts = _points_inputs(new_points, np.asarray(X).shape[1], int(np.unique(_i64(mv_id)).size), new_quantiles)
     elif len(tuple(new_quantiles)):
@@ -232,7 +258,7 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     if new_points is None:
         rc = lib.spamtree_mv_mcmc_c(*common)
     else:
-        pc, pmv, pan, pX, qs = pts
+        pc, pmv, pan, pX, qs, labels = pts
         n_new = pc.shape[0]
         draws = {key: np.zeros((n_new, mcmc_keep), order="F") if new_draws else None for key in ("w", "cond_mean", "cond_var")}
         draws["yhat"] = np.zeros((n_new, mcmc_keep), order="F") if (new_draws and pX is not None) else None
@@ -241,11 +267,17 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
         wq = np.zeros((n_new, qs.size), order="F")
         yq = np.zeros((n_new, qs.size), order="F") if pX is not None else None
         route = C.c_int32()
-        rc = lib.stm_mcmc_points(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), int(mcmc_keep) if qs.size else 0,
-                                 _dp(qs), int(qs.size), dp(draws["w"]), dp(draws["cond_mean"]), dp(draws["cond_var"]),
-                                 dp(draws["yhat"]), dp(summ["mean"]), dp(summ["var"]), dp(summ["w_mean"]),
-                                 dp(summ["yhat_mean"]), dp(wq if qs.size else None), dp(yq if qs.size else None),
-                                 C.byref(route))
+        tail = (int(mcmc_keep) if qs.size else 0, _dp(qs), int(qs.size), dp(draws["w"]), dp(draws["cond_mean"]),
+                dp(draws["cond_var"]), dp(draws["yhat"]), dp(summ["mean"]), dp(summ["var"]), dp(summ["w_mean"]),
+                dp(summ["yhat_mean"]), dp(wq if qs.size else None), dp(yq if qs.size else None), C.byref(route))
+        if labels is None:
+            rc = lib.stm_mcmc_points(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), *tail)
+        else:
+            groups, off = _joint_layout(labels)
+            ccov = np.zeros((int(off[-1]), mcmc_keep), order="F") if new_draws else None
+            cov = np.zeros(int(off[-1]))
+            rc = lib.stm_mcmc_points_joint(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), _ip(labels), *tail, dp(ccov),
+                                           _dp(cov))
         if rc == 0:
             names, code = [], 1
             while lib.st_points_route_name(code) is not None:
@@ -256,6 +288,10 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                        quantiles={float(x): (wq[:, i].copy(), None if yq is None else yq[:, i].copy()) for i, x in enumerate(qs)})
             if new_draws:
                 new.update(draws)
+            if labels is not None:
+                new.update(groups=groups, cov=_unpack_joint(cov, groups, off))
+                if new_draws:
+                    new["cond_cov"] = [_unpack_joint(ccov[:, s], groups, off) for s in range(mcmc_keep)]
     if rc == -10:
         raise FloatingPointError("At nan loglik: error.")
     if rc != 0 and new_points is not None:

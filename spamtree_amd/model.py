@@ -41,6 +41,21 @@ class SpamTreeError(RuntimeError):
     pass
 
 
+POINTS_MAX_JOINT = 16   # include/spamtree_hip.h: ST_POINTS_MAX_JOINT
+
+
+def joint_labels(joint, n):
+    """The joint-group labels of a point set as int64, checked: one integer per point, at most POINTS_MAX_JOINT per label."""
+    labels = np.asarray(joint)
+    if labels.ndim != 1 or labels.shape[0] != n:
+        raise ValueError("joint must hold one label per point")
+    if not np.issubdtype(labels.dtype, np.integer):
+        raise ValueError("joint labels must be integers")
+    if n and np.unique(labels, return_counts=True)[1].max() > POINTS_MAX_JOINT:
+        raise ValueError(f"a joint group holds at most {POINTS_MAX_JOINT} points")
+    return _i64(labels)
+
+
 class SpamTreeMV:
     """spamtree_model.cpp:8-192.  `param_data` / `alter_data` are slots 0 / 1 of the device handle."""
 
@@ -333,9 +348,11 @@ class SpamTreeMV:
         self._check(self.lib.st_synchronize(self.h))
 
     # ---- new-point prediction (include/spamtree_hip.h, st_points_*): not a method of the reference object
-    def set_points(self, coords, mv, anchor, X=None):
+    def set_points(self, coords, mv, anchor, X=None, joint=None):
         """New locations to predict at: coords n_new x 2, mv 1-based margins, anchor 0-based block ids
-        (spamtree_amd.predict.locate), X n_new x p regressors or None (then no yhat)."""
+        (spamtree_amd.predict.locate), X n_new x p regressors or None (then no yhat).  ``joint``: one integer label per
+        point; points with the same label (at most 16, one conditioning chain: give them one anchor, predict.locate(joint=))
+        form a joint group and predict_points draws them together (st_points_set_joint)."""
         coords = np.asfortranarray(np.asarray(coords, dtype=np.float64).reshape(-1, 2))
         n = coords.shape[0]
         mv = _i64(np.asarray(mv).reshape(-1))
@@ -345,14 +362,42 @@ class SpamTreeMV:
         Xf = None
         if X is not None:
             Xf = np.asfortranarray(np.asarray(X, dtype=np.float64).reshape(n, self.p))
-        self._check(self.lib.st_points_set(self.h, n, _dp(coords), _ip(mv), _ip(anchor), _dp(Xf) if Xf is not None else None))
+        Xp = _dp(Xf) if Xf is not None else None
+        self.joint_groups = None
+        if joint is None:
+            self._check(self.lib.st_points_set(self.h, n, _dp(coords), _ip(mv), _ip(anchor), Xp))
+        else:
+            labels = joint_labels(joint, n)
+            self._check(self.lib.st_points_set_joint(self.h, n, _dp(coords), _ip(mv), _ip(anchor), Xp, _ip(labels)))
+            nj = C.c_int64()
+            self._check(self.lib.st_points_joint_layout(self.h, C.byref(nj), None, None, None))
+            off, ptr, mem = (np.zeros(nj.value + 1, dtype=np.int64), np.zeros(nj.value + 1, dtype=np.int64),
+                             np.zeros(n, dtype=np.int64))
+            self._check(self.lib.st_points_joint_layout(self.h, C.byref(nj), _ip(off), _ip(ptr), _ip(mem)))
+            self.joint_offsets = off
+            self.joint_groups = [mem[ptr[k]:ptr[k + 1]].copy() for k in range(nj.value)]
         self.n_points = n
         self.points_have_X = Xf is not None
 
+    def unpack_joint(self, packed):
+        """The g x g blocks of a packed cond_cov / cond_chol / summary covariance, in group order: one [n_groups, g, g] array
+        when every group has the same size, else a list."""
+        off = self.joint_offsets
+        blocks = [np.asarray(packed[off[k]:off[k + 1]]).reshape(m.size, m.size, order="F").copy()
+                  for k, m in enumerate(self.joint_groups)]
+        if blocks and len({b.shape for b in blocks}) == 1:
+            return np.stack(blocks)
+        return blocks
+
     def predict_points(self, mode=0, z=None, seed=0, it=0):
         """Predictive at the point set on slot 0 and the current w / beta / tausq: dict(w, mean, var, yhat) in the caller's
-        order (yhat None without X).  mode 0 draws (z given, or Philox stream 6), mode 1 gives the conditional mean."""
+        order (yhat None without X).  mode 0 draws (z given, or Philox stream 6), mode 1 gives the conditional mean.
+        On a joint set (set_points(joint=)) the groups are drawn jointly and the dict also holds ``cov`` and ``chol``, the
+        conditional covariance of every group and its lower Cholesky factor (unpack_joint; groups and members as
+        ``joint_groups``), and ``var`` is the diagonal of ``cov`` clamped at 0."""
         n = self.n_points
+        if getattr(self, "joint_groups", None) is not None:
+            return self._predict_points_joint(mode, z, seed, it)
         out = {k: np.zeros(n) for k in ("w", "mean", "var")}
         out["yhat"] = np.zeros(n) if self.points_have_X else None
         zz = _f64(np.asarray(z).reshape(-1)) if z is not None else None
@@ -361,6 +406,23 @@ class SpamTreeMV:
         self._check(self.lib.st_points_predict(self.h, int(mode), _dp(zz) if zz is not None else None, int(seed), int(it),
                                                _dp(out["w"]), _dp(out["mean"]), _dp(out["var"]),
                                                _dp(out["yhat"]) if out["yhat"] is not None else None))
+        return out
+
+    def _predict_points_joint(self, mode, z, seed, it):
+        n = self.n_points
+        out = {k: np.zeros(n) for k in ("w", "mean", "var")}
+        out["yhat"] = np.zeros(n) if self.points_have_X else None
+        zz = _f64(np.asarray(z).reshape(-1)) if z is not None else None
+        if zz is not None and zz.size != n:
+            raise ValueError("z must hold one normal per point")
+        cov, chol = np.zeros(int(self.joint_offsets[-1])), np.zeros(int(self.joint_offsets[-1]))
+        self._check(self.lib.st_points_predict_joint(self.h, int(mode), _dp(zz) if zz is not None else None, int(seed), int(it),
+                                                     _dp(out["w"]), _dp(out["mean"]), _dp(cov), _dp(chol),
+                                                     _dp(out["yhat"]) if out["yhat"] is not None else None))
+        out["cov"], out["chol"] = self.unpack_joint(cov), self.unpack_joint(chol)
+        out["cov_packed"], out["chol_packed"] = cov, chol
+        for k, m in enumerate(self.joint_groups):
+            out["var"][m] = np.maximum(cov[self.joint_offsets[k]:self.joint_offsets[k + 1]][::m.size + 1], 0.0)
         return out
 
     def points_info(self):

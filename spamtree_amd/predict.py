@@ -6,6 +6,10 @@ The model defines the predictive of a location that is not a row of the problem 
 reference ancestors on that path.  :func:`locate` is that first step for arbitrary points; :func:`predict_new` replays a
 saved chain draw by draw through ``st_points_predict`` (include/spamtree_hip.h); :func:`fit_predict` predicts during the
 fit instead, on every saved iteration, with the summaries kept on the device (``st_points_accumulate``).
+
+Points can be predicted jointly: ``joint`` labels put up to 16 points that share a conditioning chain into one joint group
+(:func:`group_sites` labels the outcomes of a site), which is drawn from its g-variate conditional and reported with its
+g x g predictive covariance (``st_points_set_joint``).
 """
 from __future__ import annotations
 
@@ -14,21 +18,36 @@ from typing import Optional
 import numpy as np
 
 from . import fit
-from .model import SpamTreeMV, _dp, _f64
+from .model import SpamTreeMV, _dp, _f64, joint_labels
 from .topology import Topology, _nearest_rows
 
-__all__ = ["locate", "conditioning_set", "predict_new", "fit_predict"]
+__all__ = ["locate", "conditioning_set", "group_sites", "predict_new", "fit_predict"]
 
 
-def locate(topo: Topology, coords_new, mv_new, device: Optional[int] = None) -> np.ndarray:
+def group_sites(coords) -> np.ndarray:
+    """Joint-group labels that put the points with identical coordinates (the outcomes at one site) into one group:
+    0, 1, ... by first appearance in the caller's order."""
+    coords = np.asarray(coords, dtype=np.float64).reshape(-1, 2)
+    if coords.shape[0] == 0:
+        return np.zeros(0, dtype=np.int64)
+    _, first, inv = np.unique(coords, axis=0, return_index=True, return_inverse=True)
+    rank = np.empty(first.size, dtype=np.int64)
+    rank[np.argsort(first, kind="stable")] = np.arange(first.size)
+    return rank[np.asarray(inv).reshape(-1)]
+
+
+def locate(topo: Topology, coords_new, mv_new, device: Optional[int] = None, joint=None) -> np.ndarray:
     """0-based anchor block of every new point, in the caller's order: the block of the nearest row on the deepest knot
-    level -- the rule ``make_tree`` applies to missing rows, through the same nearest-row search (``device``: on the GPU)."""
+    level -- the rule ``make_tree`` applies to missing rows, through the same nearest-row search (``device``: on the GPU).
+    ``joint``: one label per point; every member of a joint group gets the anchor of the group's first member, so that
+    the group shares one conditioning chain (as ``cherrypick_group_locations`` keeps same-location rows in one block)."""
     if topo.knot_level is None:
         raise ValueError("this topology does not record its deepest knot level (build it with topology.prepare)")
     coords_new = np.asarray(coords_new, dtype=np.float64).reshape(-1, 2)
     mv_new = np.asarray(mv_new, dtype=np.int64).reshape(-1)
     if mv_new.size != coords_new.shape[0]:
         raise ValueError("coords_new and mv_new must describe the same points")
+    labels = None if joint is None else joint_labels(joint, coords_new.shape[0])
     if coords_new.shape[0] == 0:
         return np.zeros(0, dtype=np.int64)
     res_row = topo.block_groups[topo.blocking - 1]
@@ -36,7 +55,11 @@ def locate(topo: Topology, coords_new, mv_new, device: Optional[int] = None) -> 
     n_marg = int(topo.mv_id.max())
     nn = _nearest_rows(topo.coords[targets], topo.mv_id[targets] - 1, coords_new, mv_new - 1, n_marg,
                        topo.cherrypick_same_margin, device)
-    return (topo.blocking[targets[nn]] - 1).astype(np.int64)
+    anchor = (topo.blocking[targets[nn]] - 1).astype(np.int64)
+    if labels is not None:
+        _, first, inv = np.unique(labels, return_index=True, return_inverse=True)
+        anchor = anchor[first[np.asarray(inv).reshape(-1)]]
+    return anchor
 
 
 def conditioning_set(topo: Topology, anchor: int) -> np.ndarray:
@@ -49,7 +72,7 @@ def conditioning_set(topo: Topology, anchor: int) -> np.ndarray:
 
 
 def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, return_draws=True, device=0, z=None,
-                mode=0, force_generic=False, return_moments=False):
+                mode=0, force_generic=False, return_moments=False, joint=None):
     """Predictive at new locations for every saved draw of a chain.
 
     ``model_inputs``: the problem as ``spamtree_mv_mcmc`` took it (the dict of ``synthetic.make_workload``; its ``topo``
@@ -61,13 +84,18 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
     the conditional variances + variance of the conditional means) of w -- and, with ``return_draws``, ``w`` and ``yhat``
     (n_new x keep; yhat only with ``X_new``); with ``return_moments`` also the per-draw ``cond_mean`` and ``cond_var``
     (n_new x keep).  Everything in the caller's order of the points.
+
+    ``joint``: one label per point (see :func:`group_sites`); the groups are located together and drawn jointly.  Then the
+    result also holds ``groups`` (the member indices of every group), ``cov`` -- per group the Rao-Blackwellised predictive
+    covariance, mean of the conditional covariances + covariance of the conditional means -- and, with ``return_draws``,
+    ``cond_cov``: per saved draw the conditional covariances (``SpamTreeMV.unpack_joint``'s list or array).
     """
     mi = model_inputs
     topo = mi["topo"]
     coords_new = np.asarray(coords_new, dtype=np.float64).reshape(-1, 2)
     mv_new = np.asarray(mv_new, dtype=np.int64).reshape(-1)
     n_new = coords_new.shape[0]
-    anchor = locate(topo, coords_new, mv_new, device=device)
+    anchor = locate(topo, coords_new, mv_new, device=device, joint=joint)
     w_list = draws["w_mcmc"]
     keep = len(w_list)
     p, q = int(mi["p"]), int(mi["q"])
@@ -82,7 +110,8 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
                    np.asarray(w_list[0]).reshape(-1), np.zeros(p), theta[:, 0], 1.0 / tausq[0, 0], device=device,
                    force_generic=force_generic)
     try:
-        m.set_points(coords_new, mv_new, anchor, X_new)
+        m.set_points(coords_new, mv_new, anchor, X_new, joint=joint)
+        cc = []
         w_out = np.zeros((n_new, keep)) if return_draws else None
         y_out = np.zeros((n_new, keep)) if (return_draws and X_new is not None) else None
         cm = np.zeros((n_new, keep))
@@ -98,6 +127,8 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
             out = m.predict_points(mode=mode, z=None if z is None else z[:, s], seed=seed, it=s)
             cm[:, s] = out["mean"]
             cv[:, s] = out["var"]
+            if joint is not None:
+                cc.append(out["cov_packed"])
             if w_out is not None:
                 w_out[:, s] = out["w"]
             if y_out is not None:
@@ -109,12 +140,21 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
         if return_moments:
             res["cond_mean"] = cm
             res["cond_var"] = cv
+        if joint is not None:
+            packed = np.mean(cc, axis=0) if keep else np.zeros(0)
+            for k, g in enumerate(m.joint_groups):
+                d = cm[g] - cm[g].mean(axis=1, keepdims=True)
+                packed[m.joint_offsets[k]:m.joint_offsets[k + 1]] += (d @ d.T / keep).reshape(-1, order="F")
+            res["groups"] = m.joint_groups
+            res["cov"] = m.unpack_joint(packed)
+            if return_draws:
+                res["cond_cov"] = [m.unpack_joint(c) for c in cc]
         return res
     finally:
         m.close()
 
 
-def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), return_draws=True, **mcmc):
+def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), return_draws=True, joint=None, **mcmc):
     """Fit the chain and predict at new locations on every saved iteration, without replaying it.
 
     ``model_inputs``: the problem as for :func:`predict_new`.  The points are located with :func:`locate` and handed to
@@ -125,6 +165,7 @@ def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), retu
     Returns the fit's dict plus ``new``: ``mean``, ``var`` (Rao-Blackwellised, as :func:`predict_new`), ``anchor``, ``route``,
     ``w_mean``, ``yhat_mean`` and ``quantiles[q] = (w_q, yhat_q)`` from the device summaries, and with ``return_draws`` the
     n_new x keep draws ``w``, ``yhat`` and the per-draw ``cond_mean``, ``cond_var``.  yhat entries are None without ``X_new``.
+    With ``joint`` labels also ``groups``, ``cov`` and (``return_draws``) ``cond_cov``, as :func:`predict_new`.
     """
     mi = model_inputs
     coords_new = np.asarray(coords_new, dtype=np.float64).reshape(-1, 2)
@@ -136,7 +177,10 @@ def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), retu
     qs = tuple(float(x) for x in quantiles)
     if not all(0.0 <= x <= 1.0 for x in qs):
         raise ValueError("quantiles must lie in [0, 1]")
-    anchor = locate(mi["topo"], coords_new, mv_new, device=mcmc.get("device", 0))
+    anchor = locate(mi["topo"], coords_new, mv_new, device=mcmc.get("device", 0), joint=joint)
+    points = dict(coords=coords_new, mv=mv_new, anchor=anchor, X=X_new)
+    if joint is not None:
+        points["joint"] = joint
     theta = np.asarray(mcmc.pop("theta", mi["theta"]), dtype=np.float64)
     kw = dict(set_unif_bounds_in=mi["bounds"], start_w=np.zeros((int(mi["n"]), 1)), theta=theta, beta=np.zeros(int(mi["p"])),
               tausq=0.1, mcmcsd=0.01 * np.eye(theta.size))
@@ -144,7 +188,7 @@ def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), retu
     out = fit.spamtree_mv_mcmc(mi["y"], mi["X"], mi["Z"], mi["coords"], mi["mv_id"], mi["blocking"], mi["gix_block"],
                                mi["res_is_ref"], mi["parents"], mi["children"], bool(mi.get("limited_tree", False)),
                                mi["block_names"], mi["block_groups"], mi["indexing"],
-                               new_points=dict(coords=coords_new, mv=mv_new, anchor=anchor, X=X_new), new_draws=return_draws,
+                               new_points=points, new_draws=return_draws,
                                new_quantiles=qs, **kw)
     out["new"]["anchor"] = anchor
     return out
