@@ -664,6 +664,13 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
     if (h->lds_limit > 160 * 1024) h->lds_limit = 160 * 1024;
     h->quad_nu = 4;   // units per workgroup of k_factor_quad (2 per workgroup with two workgroups per CU measured slower)
   }
+  // limited_tree: k_marginal_invchol keeps K_uu and its inverse factor of a reference block in LDS (2 m^2 doubles: 101 rows
+  // at 160 KB).  Refused here: at launch the runtime would only answer "invalid argument" from inside st_factor
+  if (h->limited && (size_t)2 * h->twin_maxM * h->twin_maxM * sizeof(double) > h->lds_limit) {
+    const int lim = (int)std::floor(std::sqrt((double)h->lds_limit / (2.0 * sizeof(double))));
+    return fail_create(h, ST_ERR_UNSUPPORTED, "limited_tree: a reference block of " + std::to_string(h->twin_maxM) + " rows is wider than the " +
+                       std::to_string(lim) + " rows whose marginal factor fits the LDS (k_marginal_invchol keeps 2 m^2 doubles)");
+  }
   h->levels.resize(n_actual);
   h->route_a.assign((size_t)n_actual * ST_ROUTE_A_SLOTS, R_NONE);
   h->route_b.assign((size_t)n_actual * 2, R_NONE);

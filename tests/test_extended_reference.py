@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from oracle.extended import LD, ExtendedBlocks, covariance
-from tests.util import make_problem, nice_theta, oracle_model
+from tests.util import distinct_theta, make_problem, nice_theta, oracle_model
 
 
 def relerr(a, b):
@@ -89,10 +89,11 @@ def as_ld(M):
 
 
 @pytest.mark.parametrize("q,theta", [(1, np.array([2.3, 1.0, 1.0, 6.0])), (1, np.array([2.3, 1.0, 1.0, 0.3])),
-                                     (3, nice_theta(3))], ids=["q1_phi6", "q1_phi0.3", "q3_nice"])
+                                     (3, nice_theta(3)), (4, distinct_theta(4))],
+                         ids=["q1_phi6", "q1_phi0.3", "q3_nice", "q4_distinct"])
 def test_blocks_match_mpmath(q, theta):
     import mpmath as mp
-    om = tiny_tree(q, nloc=(8, 4, 2) if q == 1 else (6, 2, 2))
+    om = tiny_tree(q, nloc={1: (8, 4, 2), 3: (6, 2, 2), 4: (4, 2, 2)}[q])     # q = 4: 16-, 8- and 8-row blocks, chains of 16 / 24
     ex = ExtendedBlocks(om, theta)
     with mp.workdps(50):
         for u in range(3):
@@ -111,16 +112,21 @@ def test_blocks_match_mpmath(q, theta):
 
 def test_ag10_entries_match_mpmath():
     """The long-double Apanasovich-Genton entries against 50-digit values: the inputs of man/CrossCovarianceAG10.Rd (q = 2,
-    the set test_oracle_identities.test_cross_covariance_ag10_mpmath uses) and nice_theta(3)."""
+    the set test_oracle_identities.test_cross_covariance_ag10_mpmath uses), nice_theta(3), and distinct_theta(q) for
+    q = 4, 5, 6 (every per-outcome and per-pair parameter different)."""
     import mpmath as mp
     xl = np.linspace(0.0, 1.0, 10)
     g = np.array([(a, b) for b in xl for a in xl])
     th2 = np.array([1.0, 1.5, 0.1, 0.51, 1.0, 2.0, 5.0, 1.0])      # ai1, ai2, phi_i, thetamv, Dvec
     rng = np.random.default_rng(1)
-    for q, theta, pts in ((2, th2, g), (3, nice_theta(3), rng.uniform(size=(30, 2)))):
+    for q, theta, pts in ((2, th2, g), (3, nice_theta(3), rng.uniform(size=(30, 2)))) + \
+            tuple((q, distinct_theta(q), rng.uniform(size=(30, 2))) for q in (4, 5, 6)):
         om = types.SimpleNamespace(q=q, coords=np.tile(pts, (q, 1)), mv_id=np.repeat(np.arange(1, q + 1), pts.shape[0]))
         n = om.coords.shape[0]
         i1, i2 = rng.integers(0, n, 40), rng.integers(0, n, 40)
+        if q > 3:       # every ordered pair of outcomes at least once
+            i1 = np.concatenate([i1, np.repeat(np.arange(q), q) * pts.shape[0] + rng.integers(0, pts.shape[0], q * q)])
+            i2 = np.concatenate([i2, np.tile(np.arange(q), q) * pts.shape[0] + rng.integers(0, pts.shape[0], q * q)])
         K = covariance(om.coords, om.mv_id - 1, theta, q, i1, i2)
         with mp.workdps(50):
             Km = as_ld(mp_covariance(om, theta, i1, i2))
@@ -156,6 +162,10 @@ def test_oracle_agrees_at_nice_theta():
     pb = make_problem(side=9, q=3, seed=11)
     eRi, eN, eld = oracle_vs_extended(pb, pb["theta"], np.zeros(pb["n"]))
     assert eRi <= 1e-13 and eN <= 1e-13 and eld <= 1e-13 * pb["n"], (eRi, eN, eld)
+    for q, side in ((4, 10), (5, 10), (6, 8)):         # n = 400, 500, 384
+        pb = make_problem(side=side, q=q, seed=11)
+        eRi, eN, eld = oracle_vs_extended(pb, pb["theta"], np.zeros(pb["n"]))
+        assert eRi <= 1e-13 and eN <= 1e-13 and eld <= 1e-13 * pb["n"], (q, eRi, eN, eld)
 
 
 def test_oracle_loses_digits_as_phi_falls():
@@ -213,8 +223,8 @@ def test_view_gives_the_oracle_model_blocks_bitwise(q, missing, limited):
             assert np.array_equal(a.cond_mean(u, w), b.cond_mean(u, w)), u
 
 
-@pytest.mark.parametrize("q,missing,limited", [(1, 0.1, False), (3, 0.2, False), (2, 0.1, True)],
-                         ids=["q1_na", "q3_na", "q2_limited"])
+@pytest.mark.parametrize("q,missing,limited", [(1, 0.1, False), (3, 0.2, False), (2, 0.1, True), (5, 0.2, False)],
+                         ids=["q1_na", "q3_na", "q2_limited", "q5_na"])
 def test_draws_match_the_oracle(q, missing, limited):
     """cond_draw against gibbs_sample_w (each block given the values before the sweep, its descendants' own rows after it),
     predict_draw against predict, at nice theta."""
@@ -242,7 +252,7 @@ def test_draws_match_the_oracle(q, missing, limited):
         assert relerr(ex.predict_draw(u, w2, z[iu]), w2[iu]) <= 1e-12, u
 
 
-@pytest.mark.parametrize("q,limited", [(1, False), (3, False), (2, True)], ids=["q1", "q3", "q2_limited"])
+@pytest.mark.parametrize("q,limited", [(1, False), (3, False), (2, True), (6, False)], ids=["q1", "q3", "q2_limited", "q6"])
 def test_prior_draw_matches_the_restated_prior_sweep(q, limited):
     from tests.prior_sweep import prior_sweep
     pb = make_problem(side=16 if q == 1 else 8, q=q, seed=8, limited_tree=limited)
@@ -256,7 +266,7 @@ def test_prior_draw_matches_the_restated_prior_sweep(q, limited):
             assert relerr(ex.prior_draw(u, W, z[iu]), W[iu]) <= 1e-12, u
 
 
-@pytest.mark.parametrize("q", [1, 3])
+@pytest.mark.parametrize("q", [1, 3, 5])
 def test_point_moments_equal_the_dense_identity(q):
     """The new-point mean and variance on the anchor's chain against the dense kriging identity on its conditioning set (the
     one test_gpu_predict_points checks the kernels with)."""

@@ -20,16 +20,39 @@ def relerr(a, b):
 
 
 @pytest.mark.parametrize("case", [dict(side=25, q=1, seed=11, missing=0.1), dict(side=12, q=2, seed=12),
-                                  dict(side=25, q=1, seed=13, missing=0.1, limited_tree=True)])
+                                  dict(side=25, q=1, seed=13, missing=0.1, limited_tree=True),
+                                  dict(side=10, q=4, seed=14, missing=0.1, signed_sd=2e-4),
+                                  dict(side=10, q=6, seed=15, missing=0.1, signed_sd=2e-4)])
 def test_cpp_and_python_drivers_match_oracle_chain(case):
+    """q = 4 and 6 (a 21- and a 36-entry theta, 100- and 136-row root blocks, NA rows): `signed_sd` is the initial proposal
+    scale of ai1[1:], whose bounds are (-1e3, 1e3): at the 0.01 of the other entries a step moves them by about 5, no
+    multivariate proposal is ever accepted (logaccept about -500), and the chain would put no theta through the swap.  With
+    it both chains accept several proposals during the burn-in (asserted).  That matters for the NA rows as well: the oracle
+    restates the reference's predict(need_update), which reads prediction caches that nothing has filled until the first
+    accepted theta (H = 0: the rows are drawn from their marginals), while st_predict rebuilds H on every call; a chain with
+    NA rows that accepts nothing before its first saved iteration differs there from its first saved beta on (measured at
+    q = 3 and 4, side 10, missing 0.1, the 0.01 scale: beta 2e-2 to 1e-1, w of the NA rows O(1))."""
     from oracle import spamtree_oracle as so
     from spamtree_amd import fit, mcmc
+    case = dict(case)
+    signed_sd = case.pop("signed_sd", None)
     pb = make_problem(**case)
     k = pb["theta"].size
+
+    def args():
+        a = list(args_of(pb, k))
+        if signed_sd is not None:
+            sd = np.full(k, 0.01)
+            sd[1:pb["q"]] = signed_sd
+            a[19] = np.diag(sd)
+        return tuple(a)
+
     kw = dict(mcmc_keep=4, mcmc_burn=58, mcmc_thin=2, adapting=True, seed=99, main_verbose=False)   # crosses g0 = 50
-    ref = so.spamtree_mv_mcmc(*args_of(pb, k), **kw)
+    ref = so.spamtree_mv_mcmc(*args(), **kw)
+    if signed_sd is not None:
+        assert not np.array_equal(ref["theta_mcmc"][:, 0], pb["theta"])      # accepted proposals before the first saved draw
     for drv in (fit.spamtree_mv_mcmc, mcmc.spamtree_mv_mcmc):
-        got = drv(*args_of(pb, k), **kw)
+        got = drv(*args(), **kw)
         assert "None" not in got
         assert relerr(got["theta_mcmc"], ref["theta_mcmc"]) < 1e-8
         assert relerr(got["tausq_mcmc"], ref["tausq_mcmc"]) < 1e-8

@@ -207,6 +207,9 @@ def reference(key, pb, inp, theta):
         try:
             om.gibbs_sample_w(np.zeros(pb["n"]))
             ref["w64"] = om.w.copy()
+            if np.any(om.block_ct_obs[[u for u in range(om.n_blocks) if om.indexing[u].size]] == 0):
+                om.predict(True)          # the rows without observations, from the same z = 0 (predict_errors)
+                ref["w64p"] = om.w.copy()
         except RuntimeError:
             ref["w64"] = None
     _SHARED[key] = ref
@@ -264,17 +267,29 @@ def sweep_errors(ref, w_dev):
     return out
 
 
-@pytest.mark.parametrize("rid,regime", PARAMS, ids=[f"{r}-{g}" for r, g in PARAMS])
-def test_kernels_lose_no_more_than_lapack(rid, regime, monkeypatch):
-    row = ROW[rid]
-    for k, v in row["env"].items():
-        monkeypatch.setenv(k, v)
-    pb = build_problem(row)
-    if regime == "near":
-        pb = near_coincident(pb)
-    theta = regime_theta(pb["q"], regime)
-    inp = dict(inputs(pb), theta=theta, theta2=theta)
-    key = (repr((row.get("side"), row.get("q", 1), row.get("strip"), sorted(row["kw"].items()))), regime)
+def predict_errors(ref, w_dev):
+    """{("P", "predict"): (e_dev, e_64)}: the rows of up to NMAX blocks without observations after st_predict with z = 0, each
+    against ExtendedBlocks.predict_draw given the same run's own values of the block's parents."""
+    om, ex = ref["om"], ref["ex"]
+    na = [u for u in range(om.n_blocks) if om.block_ct_obs[u] == 0 and om.indexing[u].size]
+    if not na or ref.get("w64p") is None:
+        return {}
+    pick = np.unique(np.linspace(0, len(na) - 1, min(NMAX, len(na))).round().astype(int))
+    e_d = e_o = 0.0
+    for u in (na[k] for k in pick):
+        iu = om.indexing[u]
+        zero = np.zeros(iu.size)
+        e_d = max(e_d, err(w_dev[iu], ex.predict_draw(u, w_dev, zero)))
+        e_o = max(e_o, err(ref["w64p"][iu], ex.predict_draw(u, ref["w64p"], zero)))
+    return {("P", "predict"): (e_d, e_o)}
+
+
+def kernels_vs_extended(row, pb, inp, theta, regime, key, raised=C_FAMILY, predict=False):
+    """The criterion of this file on one (row, regime): `row`'s environment is set by the caller, inp holds theta = theta2 =
+    `theta`, `key` names the problem and regime in the shared cache of references.  `raised`: the raised bounds, keyed
+    (row or row prefix, regime, level, quantity).  predict: also the rows without observations after st_predict (predict_errors).  Returns
+    (smallest relative pivot, worst e_64, worst e_dev, worst ratio), or None where a refusal inside the band ended it."""
+    rid = row["id"]
     ref = reference(key, pb, inp, theta)
     ref["w0"] = inp["w"]
     fg = row.get("force_generic", False)
@@ -289,7 +304,7 @@ def test_kernels_lose_no_more_than_lapack(rid, regime, monkeypatch):
         if not ok[0]:
             assert ref["min_pivot"] <= PIVOT_BAND, (rid, regime, ref["min_pivot"], hm.last_errtype)
             print(f"{rid} {regime}: device refused (errtype {hm.last_errtype}), min pivot {ref['min_pivot']:.2e}")
-            return
+            return None
         devs = []
         for slot in (0, 1):
             ld, ll = hm.comps(slot)
@@ -302,6 +317,10 @@ def test_kernels_lose_no_more_than_lapack(rid, regime, monkeypatch):
             devs.append(dev)
         hm.deal_with_w(np.zeros(pb["n"]))
         w_dev = hm.get_w().copy()
+        w_pred = None
+        if predict and np.any(~np.isfinite(pb["y"])):
+            hm.predict(True)
+            w_pred = hm.get_w().copy()
     finally:
         hm.close()
 
@@ -311,18 +330,38 @@ def test_kernels_lose_no_more_than_lapack(rid, regime, monkeypatch):
 
     if not ref["ok64"]:
         print(f"{rid} {regime}: the float64 oracle refused; device succeeded (min pivot {ref['min_pivot']:.2e})")
-        return
+        return None
     errs = {}
     for slot, dev in enumerate(devs):
         for k, v in level_errors(ref, dev).items():
             errs[(slot,) + k] = v
     for k, v in sweep_errors(ref, w_dev).items():
         errs[(0,) + k] = v
+    if w_pred is not None:
+        assert np.all(np.isfinite(w_pred)), (rid, regime)
+        for k, v in predict_errors(ref, w_pred).items():
+            errs[(0,) + k] = v
     floor = 64 * EPS
     print(f"{rid} {regime}: min pivot {ref['min_pivot']:.2e}")
-    for (slot, lv, X), (e_d, e_o) in sorted(errs.items()):
+    for (slot, lv, X), (e_d, e_o) in sorted(errs.items(), key=str):
         print(f"  slot {slot} level {lv} {X:6s} e_dev {e_d:.2e} e_64 {e_o:.2e} ratio {e_d / max(e_o, floor):.2f}")
     fam = rid.split("_")[0]
     bad = {k: v for k, v in errs.items()
-           if not v[0] <= C_FAMILY.get((fam, regime, k[1], k[2]), C_BOUND) * max(v[1], floor)}
+           if not v[0] <= raised.get((rid, regime, k[1], k[2]), raised.get((fam, regime, k[1], k[2]), C_BOUND)) * max(v[1], floor)}
     assert not bad, (rid, regime, bad)
+    return (ref["min_pivot"], max(v[1] for v in errs.values()), max(v[0] for v in errs.values()),
+            max(v[0] / max(v[1], floor) for v in errs.values()))
+
+
+@pytest.mark.parametrize("rid,regime", PARAMS, ids=[f"{r}-{g}" for r, g in PARAMS])
+def test_kernels_lose_no_more_than_lapack(rid, regime, monkeypatch):
+    row = ROW[rid]
+    for k, v in row["env"].items():
+        monkeypatch.setenv(k, v)
+    pb = build_problem(row)
+    if regime == "near":
+        pb = near_coincident(pb)
+    theta = regime_theta(pb["q"], regime)
+    inp = dict(inputs(pb), theta=theta, theta2=theta)
+    key = (repr((row.get("side"), row.get("q", 1), row.get("strip"), sorted(row["kw"].items()))), regime)
+    kernels_vs_extended(row, pb, inp, theta, regime, key)

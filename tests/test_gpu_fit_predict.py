@@ -46,6 +46,11 @@ CASES = {
     # q = 2 with missing outcomes: chains on both sides of 128 rows
     "q2": dict(pb=lambda: make_problem(side=24, q=2, seed=2, missing=0.2), n=500, seed=23, beyond=0.0, fg=False,
                routes={"k_points_mfma<128>", "k_points_mfma<256>"}),
+    # q = 4 (a 21-entry theta), 24-row blocks with missing outcomes
+    # (sd: the initial proposal scales.  ai1[1:] range over (-1e3, 1e3), where the default 0.01 moves them by about 5 and no
+    # proposal is accepted; with these the chain accepts at iterations 0, 5, 7 and 16, two of them inside the saved window)
+    "q4": dict(pb=lambda: make_problem(side=12, q=4, seed=4, missing=0.2, cell_size=6), n=300, seed=25, beyond=0.0, fg=False,
+               routes=None, sd=np.diag(np.where(np.isin(np.arange(21), (1, 2, 3)), 2e-5, 1e-3))),
     "generic": dict(pb=lambda: make_problem(side=30, q=1, seed=1, missing=0.1), n=200, seed=24, beyond=0.1, fg=True,
                     routes={"k_points_generic"}),
 }
@@ -58,6 +63,8 @@ def run_case(name, **extra):
     pts, mv, Xn = points_for(pb, c["n"], c["seed"], c["beyond"])
     seed = 1000 + c["seed"]
     kw = dict(MCMC, seed=seed, force_generic=c["fg"], device=0)
+    if "sd" in c:
+        kw["mcmcsd"] = c["sd"]
     kw.update(extra)
     out = fit_predict(pb, pts, mv, Xn, quantiles=QS, **kw)
     return pb, pts, mv, Xn, seed, out
@@ -94,7 +101,7 @@ def test_fit_time_prediction_equals_the_replay(case):
     plain = fit.spamtree_mv_mcmc(pb["y"], pb["X"], pb["Z"], pb["coords"], pb["mv_id"], pb["blocking"], pb["gix_block"],
                                  pb["res_is_ref"], pb["parents"], pb["children"], False, pb["block_names"], pb["block_groups"],
                                  pb["indexing"], pb["bounds"], np.zeros((pb["n"], 1)), pb["theta"], np.zeros(pb["p"]), 0.1,
-                                 0.01 * np.eye(pb["theta"].size), seed=seed, force_generic=CASES[case]["fg"], device=0, **MCMC)
+                                 CASES[case].get("sd", 0.01 * np.eye(pb["theta"].size)), seed=seed, force_generic=CASES[case]["fg"], device=0, **MCMC)
     for key in ("beta_mcmc", "tausq_mcmc", "theta_mcmc", "paramsd"):
         assert np.array_equal(plain[key], out[key]), key
     for key in ("w_mcmc", "yhat_mcmc"):

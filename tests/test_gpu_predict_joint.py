@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from tests.test_gpu_predict_points import _deep4, _deep5, args_of, fitted, hip_model, new_points, relerr
-from tests.util import make_problem
+from tests.util import distinct_theta, make_problem
 
 pytestmark = pytest.mark.gpu
 
@@ -122,16 +122,24 @@ def check_dense(pb, hm, pts, mv, labels, anchor, routes):
 
 @functools.lru_cache(maxsize=None)
 def small(q):
+    if q == 6:      # 54-row blocks of six outcomes, chains of <= 128 rows, every per-outcome and per-pair parameter different
+        pb = make_problem(side=12, q=q, seed=5, missing=0.1, cell_size=9)
+        pb["theta"] = distinct_theta(q)
+        return pb
     return make_problem(side=20, q=q, seed=5, missing=0.1)
 
 
-@pytest.mark.parametrize("q", [1, 3])
+@pytest.mark.parametrize("q", [1, 3, 6])
 def test_conditional_moments_equal_the_dense_identity(q):
     """25-row blocks (sub-panels of 16 + 9 rows: the stale rows of a short sub-panel must not reach the Gram); q = 3: 100 sites
-    of 3 outcomes, q = 1: groups of 1, 2, 5, 6 and 16 same-anchor points.  This is also the check of the MFMA operand layout."""
+    of 3 outcomes, q = 6: 60 sites of all six outcomes (g = 6, a 6 x 6 predictive covariance per site), q = 1: groups of 1, 2,
+    5, 6 and 16 same-anchor points.  This is also the check of the MFMA operand layout."""
     pb = small(q)
     hm = fitted(pb, 6)
-    check_dense(pb, hm, *(site_set(pb, 100, 7) if q == 3 else run_set(pb, 300, 7)), MFMA)
+    points = site_set(pb, 60 if q == 6 else 100, 7) if q >= 3 else run_set(pb, 300, 7)
+    if q == 6:
+        assert np.all(np.bincount(points[2]) == 6)
+    check_dense(pb, hm, *points, MFMA)
     hm.close()
 
 

@@ -9,7 +9,7 @@
 import numpy as np
 import pytest
 
-from tests.util import make_problem, strip_coords
+from tests.util import distinct_theta, make_problem, strip_coords
 
 pytestmark = pytest.mark.gpu
 
@@ -89,11 +89,15 @@ def test_replay_at_the_na_rows_reproduces_the_chain(case):
     assert np.all(np.isfinite(out["mean"])) and np.all(out["var"] >= 0) and cm.shape == out["mean"].shape
 
 
-@pytest.mark.parametrize("q", [1, 3])
+@pytest.mark.parametrize("q", [1, 3, 5])
 def test_conditional_moments_equal_the_dense_identity(q):
     from oracle.spamtree_oracle import CovarianceParams, Covariancef
     from spamtree_amd.predict import conditioning_set, locate
-    pb = make_problem(side=20, q=q, seed=5, missing=0.1)
+    if q == 5:      # 45-row blocks, chains of <= 135 rows (the default 125-row blocks would leave the column-group kernels);
+        pb = make_problem(side=14, q=q, seed=5, missing=0.1, cell_size=9)      # every per-outcome parameter different
+        pb["theta"] = distinct_theta(q)
+    else:
+        pb = make_problem(side=20, q=q, seed=5, missing=0.1)
     topo = pb["topo"]
     hm = fitted(pb, 6)
     w = hm.get_w()

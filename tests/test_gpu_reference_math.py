@@ -108,7 +108,7 @@ def test_hip_one_level_tree_is_exact_gp():
 
 
 @pytest.mark.parametrize("q,side,kw", [(1, 25, {}), (2, 16, {}), (3, 12, {}), (1, 30, dict(cell_size=9, K=(3, 2))),
-                                       (3, 18, dict(cell_size=9))])
+                                       (3, 18, dict(cell_size=9)), (4, 10, {}), (5, 10, {}), (6, 10, {})])
 @pytest.mark.parametrize("generic", [False, True])
 def test_hip_loglik_equals_dense_dag_density(q, side, kw, generic):
     """log p(w | theta) of phases A and C = log N(w; 0, Q^-1) with Q assembled from the full covariance matrix by generic

@@ -157,11 +157,19 @@ def build_problem(row):
 
 
 def hip_model(pb, force_generic=False, **kw):
+    """beta: p values for every outcome, or p x q (one column per outcome); tausq: one value, or q."""
     from spamtree_amd.model import SpamTreeMV
-    return SpamTreeMV(pb["y"], pb["X"], pb["Z"], pb["coords"], pb["mv_id"], pb["blocking"], pb["gix_block"],
-                      pb["res_is_ref"], pb["parents"], pb["children"], pb.get("limited_tree", False), pb["block_names"],
-                      pb["block_groups"], pb["indexing"], kw["w"], kw["beta"], kw["theta"], 1.0 / kw["tausq"],
-                      force_generic=force_generic)
+    beta, tausq = np.asarray(kw["beta"], dtype=np.float64), np.asarray(kw["tausq"], dtype=np.float64)
+    hm = SpamTreeMV(pb["y"], pb["X"], pb["Z"], pb["coords"], pb["mv_id"], pb["blocking"], pb["gix_block"],
+                    pb["res_is_ref"], pb["parents"], pb["children"], pb.get("limited_tree", False), pb["block_names"],
+                    pb["block_groups"], pb["indexing"], kw["w"], beta[:, 0] if beta.ndim == 2 else beta, kw["theta"],
+                    1.0 / float(tausq.ravel()[0]), force_generic=force_generic)
+    if beta.ndim == 2:
+        hm.beta_update(beta)
+    if tausq.ndim > 0:
+        hm.tausq_inv = 1.0 / tausq
+        hm._check(hm.lib.st_set_tausq_inv(hm.h, hm.tausq_inv.ctypes.data_as(hm.lib.st_set_tausq_inv.argtypes[1])))
+    return hm
 
 
 def inputs(pb):

@@ -8,7 +8,7 @@ import pytest
 
 from tests.prior_sweep import prior_sweep
 from tests.test_oracle_identities import dense_precision
-from tests.util import make_problem, oracle_model, strip_coords
+from tests.util import distinct_theta, make_problem, oracle_model, strip_coords
 
 pytestmark = pytest.mark.gpu
 
@@ -20,8 +20,18 @@ def hip_model(pb, force_generic=False, tausq=0.2):
     hm = SpamTreeMV(pb["y"], pb["X"], pb["Z"], pb["coords"], pb["mv_id"], pb["blocking"], pb["gix_block"], pb["res_is_ref"],
                     pb["parents"], pb["children"], pb.get("limited_tree", False), pb["block_names"], pb["block_groups"],
                     pb["indexing"], np.zeros(pb["n"]), pb["beta_true"], pb["theta"], 1.0 / tausq, force_generic=force_generic)
+    if "tausq" in pb:       # one noise variance per outcome
+        hm.tausq_inv = 1.0 / np.asarray(pb["tausq"], dtype=np.float64)
+        assert hm.lib.st_set_tausq_inv(hm.h, hm.tausq_inv.ctypes.data_as(C.POINTER(C.c_double))) == 0
     assert hm.get_loglik_comps_w(0)
     return hm
+
+
+def q5_problem():
+    """Five outcomes (20-row blocks), every per-outcome and per-pair covariance parameter and every tausq different."""
+    pb = make_problem(side=12, q=5, seed=5, cell_size=6)
+    pb.update(theta=distinct_theta(5), tausq=np.array([0.2, 0.05, 0.4, 0.1, 0.3]))
+    return pb
 
 
 CASES = {
@@ -30,6 +40,7 @@ CASES = {
     "q2": lambda: make_problem(side=14, q=2, seed=5),
     "q3_wide": lambda: make_problem(side=12, q=3, seed=5),
     "limited": lambda: make_problem(side=20, q=2, seed=5, limited_tree=True),
+    "q5": q5_problem,
     "strip_deep": lambda: make_problem(coords=strip_coords(640, 4, 1)[0], mv_id=strip_coords(640, 4, 1)[1], q=1, seed=5,
                                        K=(2, 1), cell_size=16, tree_depth=7),
 }
@@ -53,7 +64,7 @@ def test_caller_normals_match_the_restated_sweep_and_reach_every_route():
         w, y = hm.simulate(3, z=z, eps=eps)
         wr = prior_sweep(om, z)
         assert rel(w, wr) <= 1e-10, (name, generic, rel(w, wr))
-        tau = np.sqrt(0.2)
+        tau = np.sqrt(np.broadcast_to(pb.get("tausq", 0.2), (pb["q"],)))[pb["mv_id"] - 1][:, None]
         yr = (pb["X"] @ pb["beta_true"])[:, None] + wr + tau * eps
         assert rel(y, yr) <= 1e-10, (name, generic)
         reached |= hm.simulate_info(3)["route_mask"]

@@ -136,7 +136,8 @@ def test_one_level_tree_is_exact_gp():
     assert abs(m.param_data.loglik_w - exact) < 1e-9 * abs(exact)
 
 
-@pytest.mark.parametrize("q,side,missing", [(1, 25, 0.0), (2, 16, 0.0), (3, 12, 0.0), (1, 24, 0.15)])
+@pytest.mark.parametrize("q,side,missing", [(1, 25, 0.0), (2, 16, 0.0), (3, 12, 0.0), (1, 24, 0.15), (4, 10, 0.0), (5, 10, 0.0),
+                                             (6, 10, 0.0)])
 def test_loglik_equals_dense_dag_density(q, side, missing):
     pb = make_problem(side=side, q=q, seed=5, missing=missing)
     rng = np.random.default_rng(1)

@@ -30,6 +30,24 @@ def test_locate_gives_a_joint_group_the_anchor_of_its_first_member():
     assert np.array_equal(locate(pb["topo"], pts, mv, joint=np.arange(200)), plain)
 
 
+def test_locate_gives_a_site_of_all_six_outcomes_one_anchor():
+    """q = 6: 30 sites, each asked for with all six outcomes (interleaved in the caller's order): group_sites labels every
+    site's six points alike, and locate(joint=) gives the six the anchor of the first, whichever outcome that is."""
+    from spamtree_amd.predict import group_sites, locate
+    pb = make_problem(side=10, q=6, seed=3, missing=[0.05, 0.1, 0.15, 0.2, 0.3, 0.4])
+    rng = np.random.default_rng(4)
+    perm = rng.permutation(180)
+    pts = np.tile(rng.uniform(size=(30, 2)), (6, 1))[perm]
+    mv = np.repeat(np.arange(1, 7), 30)[perm]
+    labels = group_sites(pts)
+    assert np.unique(labels).size == 30 and np.all(np.bincount(labels) == 6)
+    plain = locate(pb["topo"], pts, mv)
+    joint = locate(pb["topo"], pts, mv, joint=labels)
+    for lab in range(30):
+        m = np.nonzero(labels == lab)[0]
+        assert sorted(mv[m]) == [1, 2, 3, 4, 5, 6] and np.all(joint[m] == plain[m[0]]), lab
+
+
 def test_bad_joint_labels_raise_before_any_device_call():
     from spamtree_amd import fit
     from spamtree_amd.model import joint_labels

@@ -20,7 +20,8 @@ NEW_SYMBOLS = ["st_points_set", "st_points_predict", "st_points_info", "st_point
     dict(side=30, q=1, seed=1, missing=0.1),
     dict(side=20, q=3, seed=3, missing=[0.1, 0.3, 0.5], cherrypick_same_margin=True),
     dict(side=30, q=1, seed=5, missing=0.1, last_not_reference=False),
-], ids=["q1", "q3_same_margin", "reference_anchors"])
+    dict(side=12, q=6, seed=3, missing=[0.05, 0.1, 0.15, 0.2, 0.3, 0.4], cherrypick_same_margin=True),
+], ids=["q1", "q3_same_margin", "reference_anchors", "q6_same_margin"])
 def test_locate_reproduces_the_missing_rows_parents(kw):
     from spamtree_amd.predict import conditioning_set, locate
     pb = make_problem(**kw)

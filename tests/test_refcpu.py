@@ -7,7 +7,7 @@ from tests.util import make_problem, oracle_model
 
 
 @pytest.mark.parametrize("case", [dict(side=25, q=1), dict(side=24, q=1, missing=0.15), dict(side=14, q=3, missing=0.1),
-                                  dict(side=16, q=2)])
+                                  dict(side=16, q=2), dict(side=10, q=5, missing=(0.05, 0.1, 0.2, 0.3, 0.4))])
 def test_refcpu_matches_numpy_oracle(case):
     pb = make_problem(seed=23, **case)
     rng = np.random.default_rng(2)

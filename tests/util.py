@@ -48,6 +48,19 @@ def nice_theta(q):
     return np.concatenate([ai1, ai2, phi, thetamv, dvec])
 
 
+def distinct_theta(q):
+    """nice_theta with every per-outcome and per-pair entry different (q >= 3): ai1 of mixed sign and distinct for outcomes
+    4 to 6 (nice_theta gives them all 1.0), so an index mix-up among the later outcomes changes the covariance.  The dense K
+    of the many-outcome shapes (n = 864 to 1280) has eigenvalues between 0.044 and 226."""
+    assert 3 <= q <= 6
+    ai1 = np.array([1.0, -0.8, 1.3, 0.9, -1.1, 0.7][:q])
+    ai2 = np.linspace(0.3, 0.6, q)
+    phi = np.linspace(3.0, 5.0, q)
+    thetamv = np.array([1.2, 0.7, 4.0])
+    dvec = np.linspace(0.5, 1.5, q * (q - 1) // 2)
+    return np.concatenate([ai1, ai2, phi, thetamv, dvec])
+
+
 def make_problem(side=25, q=1, seed=0, missing=0.0, coords=None, mv_id=None, p=3, random_coords=False, single_obs=None,
                  **tree_kw):
     """Synthetic inputs in the layout spamtree_mv_mcmc receives (R/spamtree_fit.R:327-362)."""
@@ -98,9 +111,27 @@ def oracle_model(pb, theta=None, beta=None, tausq=0.1, w=None, **kw):
     theta = pb["theta"] if theta is None else theta
     beta = np.zeros(pb["p"]) if beta is None else beta
     w = np.zeros(pb["n"]) if w is None else w
-    return SpamTreeMV(pb["y"], pb["X"], pb["Z"], pb["coords"], pb["mv_id"], pb["blocking"], pb["gix_block"],
-                      pb["res_is_ref"], pb["parents"], pb["children"], pb.get("limited_tree", False), pb["block_names"],
-                      pb["block_groups"], pb["indexing"], w, beta, theta, 1.0 / tausq, **kw)
+    beta, tausq = np.asarray(beta, dtype=np.float64), np.asarray(tausq, dtype=np.float64)
+    om = SpamTreeMV(pb["y"], pb["X"], pb["Z"], pb["coords"], pb["mv_id"], pb["blocking"], pb["gix_block"],
+                    pb["res_is_ref"], pb["parents"], pb["children"], pb.get("limited_tree", False), pb["block_names"],
+                    pb["block_groups"], pb["indexing"], w, beta[:, 0] if beta.ndim == 2 else beta, theta,
+                    1.0 / float(tausq.ravel()[0]), **kw)
+    if beta.ndim == 2 or tausq.ndim > 0:
+        per_outcome(om, beta if beta.ndim == 2 else None, tausq if tausq.ndim > 0 else None)
+    return om
+
+
+def per_outcome(om, Bcoeff=None, tausq=None):
+    """Gives an oracle model one coefficient column (Bcoeff p x q) and one noise variance (tausq, q values) per outcome, as
+    its beta and tausq updates leave them (the constructor takes one of each for all outcomes)."""
+    if Bcoeff is not None:
+        om.Bcoeff = np.array(Bcoeff, dtype=np.float64)
+        for j in range(om.q):
+            om.XB[om.ix_by_q[j]] = om.X[om.ix_by_q[j]] @ om.Bcoeff[:, j]
+    if tausq is not None:
+        om.tausq_inv = 1.0 / np.asarray(tausq, dtype=np.float64)
+        for j in range(om.q):
+            om.tausq_inv_long[om.ix_by_q[j]] = om.tausq_inv[j]
 
 
 def strip_coords(nx, ny, q, width=0.02):
