@@ -56,10 +56,15 @@ struct QuadArgs {
 // chain staged as in QM_FULL, V taken from A.vscr, T += V' Linv and the panel rows -- no covariance pass, no log-density
 // terms.  Both halves walk the tiles in QM_FULL's order with QM_FULL's arithmetic: the same bits as one QM_FULL launch.
 // A workgroup-uniform argument of the leaf instantiation, not a template parameter: every launched instantiation is one
-// of the route table's (tests/test_route_table.py).  The three modes share ONE register allocation, so the split modes
-// keep nothing live in QM_FULL's main loop beyond what QM_FULL holds: QM_TFROMV's V tiles sit in kx, QM_VONLY's go out
-// as soon as they are formed.  No instantiation spills (NKX 50: 256 VGPRs); occupancy is bound by LDS (one workgroup per
-// CU) at every NKX, so the larger allocation of the smaller instantiations costs no waves.
+// of the route table's (tests/test_route_table.py).  Inside the kernel the mode IS a compile-time constant: everything
+// behind the LDS declarations is a generic lambda instantiated once per mode, and the kernel branches to one of the three
+// copies on the argument.  Each mode therefore has its own control flow and its own live ranges.  (As one body with a
+// run-time mode, the registers in which QM_TFROMV parks its loaded V tiles -- kx -- were B operands of the V MFMAs on the
+// other modes' paths, and the compiler's wait insertion guarded every such use with a full vmcnt(0) in EVERY mode: five
+// drains per step of the shared chain besides the hand-written one, the first of them between the next step's LDS-DMA
+// requests and the first MFMA.)  The kernel's register count is the largest of the three (QM_FULL's; NKX 50: 256 VGPRs,
+// no instantiation spills); occupancy is bound by LDS (one workgroup per CU) at every NKX.  Code size: three bodies, of
+// which a launch executes one.
 enum { QM_FULL = 0, QM_VONLY = 1, QM_TFROMV = 2 };
 __host__ __device__ constexpr int quad_vtiles(int nkx) { return 2 + 2 * ((4 * nkx + 31) / 32); }
 
@@ -95,7 +100,6 @@ template <int NU, int NKX, int NKT, bool ISREF, bool WCH = true>
 __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar cp) {
   constexpr int NTQ = 128 * NU, NW = 2 * NU;
   static_assert(NU >= 2, "s_g overlays two rows of s_e2");
-  const int QM = ISREF ? QM_FULL : RFL(A.mode);
   // covariance scratch ([KH][64] doubles per wave, lane-private slots): reference levels keep it in the SECOND staging buffer
   // (4 passes), leaf levels behind the arena (KH = 5: 20 KB), so that the first panel rows can travel by LDS-DMA UNDER the
   // covariance pass instead of after it
@@ -128,6 +132,10 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
   double (*s_g)[32] = s_e2;    // [step buffer][row of the step]
   double (*s_gp)[32] = s_hv;   // [unit][row of the private ancestor]
 
+  // Everything from here on is compiled once per mode (the dispatch follows the body, at the end of the kernel); the LDS
+  // declarations above exist once.  The body keeps the kernel's indentation.
+  auto body = [&](auto qmc) __attribute__((always_inline)) {
+  constexpr int QM = decltype(qmc)::value;
   const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, l4 = lane >> 4, ttid = tid & 127;
   const int wid = RFL(tid >> 6), u = wid >> 1, jt = (wid & 1) ^ ((wid >> 2) & 1);   // waves w, w + 4 share a SIMD: one jt = 0 (it also has the off-diagonal Schur tile) and one jt = 1 each
   constexpr int ldS = quad_lds_stride(NKX);   // == A.ldS (host)
@@ -436,8 +444,7 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
         if (QM != QM_TFROMV) hacc = fma(p[3], gt[l4 + 12], fma(p[2], gt[l4 + 8], fma(p[1], gt[l4 + 4], fma(p[0], gt[l4], hacc))));
       }
     }
-    // QM_VONLY: the tile goes out at once (held any longer, across the next tile's MFMAs, it would push K operands of
-    // QM_FULL's main loop into scratch: the three modes share one register allocation)
+    // QM_VONLY: the tile goes out at once
     if (!ISREF && QM == QM_VONLY && wact) vstore(tix, p);
   };
   // one step (sr <= 32 rows of Linv staged at stg with stride ldS; Kb / KbA: length of the longest row of the step / of its
@@ -454,8 +461,7 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
   // rows per unit, is packed WITHOUT padding rows into rows [0, 48): rows [48, 64) then take the first step of the shared
   // chain (<= 16 rows: 175 chain rows = 5 x 32 + 15), requested when the matrix cores start on sub-panel 1.
   bool pf = false;   // the shared chain's first step sits at row 48 (workgroup-uniform)
-  // QM_TFROMV keeps the V tiles it has requested in kx (no covariance pass: free), QM_VONLY the ones it has yet to store in
-  // tacc[0..1] (no T: free) -- the three modes share one register budget, QM_FULL's
+  // QM_TFROMV keeps the V tiles it has requested in kx (no covariance pass: kx holds nothing else in that body)
   auto kget = [&](int o) __attribute__((always_inline)) { return (d4){kx[o], kx[o + 1], kx[o + 2], kx[o + 3]}; };
   auto kset = [&](int o, const d4 &v) __attribute__((always_inline)) { kx[o] = v[0]; kx[o + 1] = v[1]; kx[o + 2] = v[2]; kx[o + 3] = v[3]; };
   if (QM == QM_TFROMV && wact && pmmax > 0) {   // both private tiles requested at once, long before they are needed
@@ -867,6 +873,14 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
   }
   STAMP(13);
   STAMP_FLUSH_LEVEL(s_level);
+  };   // body
+  if constexpr (ISREF) body(std::integral_constant<int, QM_FULL>());
+  else {
+    const int qm = RFL(A.mode);   // workgroup-uniform: one scalar branch, each mode runs its own code only
+    if (qm == QM_VONLY) body(std::integral_constant<int, QM_VONLY>());
+    else if (qm == QM_TFROMV) body(std::integral_constant<int, QM_TFROMV>());
+    else body(std::integral_constant<int, QM_FULL>());
+  }
 }
 template __global__ void k_factor_quad<4, 32, 8, true, true>(QuadArgs, CovPar);
 template __global__ void k_factor_quad<4, 32, 8, true, false>(QuadArgs, CovPar);
