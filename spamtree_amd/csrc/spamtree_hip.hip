@@ -18,21 +18,14 @@
 // Messages to ancestors are pushed as per-ancestor (m_a x m_a, m_a) pairs and summed hierarchically through
 // direct children in a fixed order (no FP64 atomics -> bit-reproducible for any launch geometry).
 //
-// This translation unit is the HOST side: handle, C-ABI, launches.  The kernels live in one translation unit per family
-// (k_factor_generic.hip, k_factor_mfma.hip, k_factor_quad.hip, k_factor_wide.hip, k_sample.hip, k_misc.hip); the headers
-// included here give their argument structures, launch constants and prototypes.
+// This translation unit is the HOST side: handle, C-ABI, the device step of st_create and EVERY launch.  The launch structures
+// the launches index are built without a device call in tree_layout.cpp (the handle derives from its TreeLayout).  The kernels
+// live in one translation unit per family (k_factor_generic.hip, k_factor_mfma.hip, k_factor_quad.hip, k_factor_wide.hip,
+// k_sample.hip, k_misc.hip); the headers included here give their argument structures, launch constants and prototypes.
 
 #include <unordered_map>
 
-#include "st_device.hpp"
-#include "factor_generic.hpp"
-#include "factor_mfma.hpp"
-#include "chol_blocked.hpp"
-#include "factor_quad.hpp"
-#include "factor_big.hpp"
-#include "factor_wide.hpp"
-#include "factor_lchain.hpp"
-#include "sample_kernels.hpp"
+#include "tree_layout.hpp"
 #include "misc_kernels.hpp"
 #include "predict_points.hpp"
 #include "predict_joint.hpp"
@@ -45,10 +38,17 @@ static thread_local std::string g_create_error;
 struct st_handle_s;
 static void points_free(st_handle_s *h);
 
+// A device allocation that frees itself; a null buffer makes no HIP call.  (The owner has the device current when it goes.)
 template <typename T>
 struct DevBuf {
   T *p = nullptr;
   size_t n = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+  DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { free(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; } return *this; }
+  ~DevBuf() { free(); }
   hipError_t alloc(size_t count) {
     n = count;
     if (count == 0) { p = nullptr; return hipSuccess; }
@@ -60,36 +60,6 @@ struct DevBuf {
     return hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
   }
   void free() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
-
-struct LevelInfo {
-  int first = 0, count = 0;   // into lvl_list
-  int isref = 1;
-  int maxP = 0, maxM = 0, maxMa = 0, maxLd = 0;
-  bool big_factor = false, big_sample = false, sample_sq = false;   // sample_sq: k_sample<true> keeps S and chol(S)^-1 in LDS
-  size_t lds_factor = 0, lds_sample = 0, lds_loglik = 0;
-  double alg_bytes_A = 0, alg_bytes_B = 0, alg_bytes_C = 0, alg_bytes_msg = 0;
-  double flops_A = 0, flops_B = 0, flops_C = 0;
-  // MFMA fast path of phase A (column groups)
-  bool fast = false;
-  int grp_first = 0, grp_count = 0, Pm4 = 0, ldKV = 2, ldS = 2, SRm = 1, stage_dbl = 0;
-  size_t lds_fast = 0;
-  int ldN = 2, Mr4 = 4, Mrows = 1, av_dbl = 224, maxJ = 0;
-  size_t lds_sfast = 0, lds_slean = 0;
-  bool bigmfma = false;            // generic level whose phase A takes k_factor_bigmfma
-  int wide_first = 0, wide_count = 0, wide_maxN = 0;   // sibling groups of this rank's run (k_factor_wide); count 0: not used
-  size_t lds_wide = 0;
-  int bm_ldS = 0;
-  size_t lds_bigmfma = 0;
-  int lchain = 0;                  // non-reference level on k_factor_lchain<lchain> (0: not used)
-  bool lchain_ref = false;         // ... a REFERENCE level: k_factor_lchain, then k_factor_ref_finish
-  size_t lds_ref_finish = 0;
-  int rf_first = 0;                // its blocks' entries (this rank's run) in d_rfvoff / d_rfvld
-  int lc_first = 0, lc_count = 0;  // its slabs (this rank's run) in d_lcslabs
-  int quad_first = 0, quad_count = 0, qown_lo = 0, qown_n = 0, q_ldS = 0, q_nkx = 0;   // k_factor_quad (q_nkx = 0: not eligible)
-  long long vl_off = -1;           // leaf quad level whose T a proposal defers: its V tiles in d_vleaf (-1: always QM_FULL)
-  size_t lds_quad = 0;
-  int own_lo = 0, own_n = 0, gown_lo = 0, gown_n = 0;   // this rank's run of the level's block list / group list
 };
 
 // route codes (st_route_info): written by the launch sites themselves; st_route_name spells them as the source does
@@ -120,106 +90,46 @@ static const char *const k_route_names[R_COUNT] = {
   "k_sample_lean<false>", "k_sample<true, false>", "k_sample_leaf_wide", "k_sample<true, true>", "k_sample<false>",
 };
 
-// The library's environment switches ("Runtime switches", says what each one does), read once per handle
-// by create_impl.  The defaults are the measured best.  wide, split_gram, sample_wave: 0 never, 2 on every eligible level.
-struct Switches {
-  int wide = 1, split_gram = 1, sample_wave = 1;
-  bool lchain = true, lchain_ref = true, gram_big = true, gram_direct = true, sample_lean = true, sample_lat = true,
-       leaf_seg = true, leaf_wide = true, async_top = true;
-  int lchain_ref_min = 1;
-  int factor_gen = 3;     // 3: k_factor_quad where a column-group level is eligible, k_factor_mfma elsewhere; 1: k_factor_mfma everywhere
-  int quad_units = 0;     // k_factor_quad's units per workgroup, honoured in 1 .. quad_nu
-  int quad_min = -1;      // smallest level that takes k_factor_quad (-1: 2 x CUs)
-};
-
-static Switches read_switches() {
-  auto level = [](const char *name) {   // 0 / 2 when the value starts with '0' / '2', else (unset too) 1
-    const char *e = getenv(name);
-    return (e && e[0] == '0') ? 0 : ((e && e[0] == '2') ? 2 : 1);
-  };
-  Switches s;
-  s.wide = level("SPAMTREE_WIDE"); s.split_gram = level("SPAMTREE_SPLIT_GRAM"); s.sample_wave = level("SPAMTREE_SAMPLE_WAVE");
-  s.lchain = level("SPAMTREE_LCHAIN"); s.lchain_ref = level("SPAMTREE_LCHAIN_REF"); s.gram_big = level("SPAMTREE_GRAM_BIG");
-  s.gram_direct = level("SPAMTREE_GRAM_DIRECT"); s.sample_lean = level("SPAMTREE_SAMPLE_LEAN"); s.sample_lat = level("SPAMTREE_SAMPLE_LAT");
-  s.leaf_seg = level("SPAMTREE_LEAF_SEG"); s.leaf_wide = level("SPAMTREE_LEAF_WIDE"); s.async_top = level("SPAMTREE_ASYNC_TOP");
-  const char *e;
-  if ((e = getenv("SPAMTREE_LCHAIN_REF_MIN"))) s.lchain_ref_min = atoi(e);
-  if ((e = getenv("SPAMTREE_FACTOR_KERNEL")) && e[0] == '1') s.factor_gen = 1;
-  if ((e = getenv("SPAMTREE_QUAD_UNITS"))) s.quad_units = atoi(e);
-  if ((e = getenv("SPAMTREE_QUAD_MIN"))) s.quad_min = std::max(atoi(e), 0);   // (any value <= 0 lets every level through)
-  return s;
-}
-
-struct st_handle_s {
+struct st_handle_s : TreeLayout {
   std::string err;
   int device = 0;
   hipStream_t stream = nullptr;
-  int quirks = 1, force_generic = 0;
-  Switches sw;
-  long long n_all = 0, n_blocks = 0;
-  int q = 1, p = 1, d = 2, n_groups = 0, n_actual_groups = 0;
+  int quirks = 1;
   long long n_obs = 0;
-  size_t lds_limit = 65536;
-  int sm_count = 256;
-
-  std::vector<long long> dev2model, model2dev;       // rows
-  std::vector<int> blk_model2dev;                    // blocks
-  std::vector<Blk> blks;                             // device block order
-  std::vector<int> anc_idx, dch_idx, lvl_list, pred_list, all_obs_list;
-  std::vector<Grp> grps;
-  DevBuf<Grp> d_grps;
-  std::vector<Quad> quads;
+  DevBuf<Grp> d_grps;                         // the device copies of the layout's lists (tree_layout.hpp)
   DevBuf<Quad> d_quads;
-  std::vector<WideGrp> wgrps;                 // sibling groups of the wide levels (k_factor_wide)
   DevBuf<WideGrp> d_wgrps;
-  std::vector<LcSlab> lcslabs;                // k_factor_lchain: slabs of sibling groups
   DevBuf<LcSlab> d_lcslabs;
-  std::vector<long long> rfvoff;   // k_factor_ref_finish: per block of a reference level on the lchain route, its columns in the V scratch
-  DevBuf<long long> d_rfvoff;
+  DevBuf<long long> d_rfvoff, d_gdesc;
   DevBuf<double> d_vscr;                      // V = Linv_pa K_pa,u of ONE such level (the largest): written by k_factor_lchain, read by k_factor_ref_finish
-  size_t vscr_need = 0;
   DevBuf<double> d_lcrow;                     // per-row e^2 | log r of the lchain levels (2 n)
   DevBuf<double> d_s0;                        // Ri' Ri of the reference blocks on the generic phase-B path (theta-only, cached with the Gram parts)
   DevBuf<long long> d_s0off;                  // per block: offset into d_s0, -1 = none
   bool c_pending = false;                     // st_sample_w_loglik_begin: the sweep's failure word and log-density are on their way to pin[8..10]
   int c_rc = 0; double c_ll = 0.0;            // ... or (multi-GPU / communicator attached) already here
-  std::vector<long long> gdesc;               // group descriptors (GdHead layout), gd_stride words per group
-  DevBuf<long long> d_gdesc;
-  int gd_stride = 8;
-  int quad_nu = 4;
   // multi-GPU sharding
-  int rank = 0, world = 1, cut = 0;
-  std::vector<int> blk_owner;                 // device block -> owning rank, -1 = replicated
-  std::vector<int> own_obs_list;              // observed blocks this rank evaluates in phase C
-  DevBuf<int> d_ownobs;
-  std::vector<int> own_grp_list, own_obs_slow; // the same set split: column groups of the fast levels / blocks of the others
-  DevBuf<int> d_owngrp, d_ownslow;
+  DevBuf<int> d_ownobs, d_owngrp, d_ownslow;  // this rank's observed blocks; the same set split: column groups of the fast levels / blocks of the others
   DevBuf<unsigned char> d_rowmask, d_blkmask; // 1 = this rank contributes the entry to a sum-with-zeros exchange
   DevBuf<double> d_comm;                      // 2*n_blocks + 64 doubles
   DevBuf<double> d_gather;                    // all-gather of w: world x gather_cnt (a rank's owned rows in device order + its failure word)
   DevBuf<int> d_gidx;                         // device row of every slot of d_gather (-1: padding / the failure word)
-  int gather_cnt = 1;
   DevBuf<double> d_gerr;                      // the ranks' failure words after the all-gather (64)
   // phase A of the latency-bound top levels ahead of time (st_factor_begin): they depend on theta only -- except for the
   // blocks' quadratic forms, redone with the current w afterwards -- and run on a second stream under the sweep
   hipStream_t stream2 = nullptr;
   hipEvent_t ev_top = nullptr, ev_main = nullptr;
   DevBuf<int> d_err2, d_toplist;
-  int n_toplist = 0, g_top = 0;
   bool async_top = false, top_pending = false, prof_suspend = false, async_top_off = false;
   hipEvent_t ev_stats = nullptr;
   bool stats_on_stream2 = false;   // the statistics kernels of the current (w, XB) are in flight on the second stream
   bool stats_prefetched = false;   // ... and their results follow them to pin[20 ..] on that stream
   int top_phys = -1;
   std::vector<double> top_theta;
-  long long top_off = 0, top_len = 0;         // message records of the cut level inside `acc`
-  std::vector<std::pair<long long, long long>> top_zero;   // sub-ranges of it owned by other ranks
   bool ext_stream = false;
   DevBuf<double> d_sum_w, d_sum_yhat;         // running sums over saved iterations (st_summary_*)
   long long n_summary = 0;
   DevBuf<double> d_draws_w, d_draws_yhat;     // st_summary_reserve: the saved draws themselves, [keep][n_all] (quantiles)
   long long draws_cap = 0, n_draws = 0;
-  int gram_direct_level = -1;                 // >= 0: that (last reference) level forms its children's Gram parts itself: k_gram_direct
   bool stats_valid = false;                   // d_stats matches the current w and XB
   bool host_stats_valid = false;              // ... and host_stats holds a copy of it
   std::vector<double> host_stats;
@@ -236,21 +146,13 @@ struct st_handle_s {
   bool cache_gram = true;
   // a proposal's quad leaf levels (st_factor_enqueue on slot 1): QM_VONLY, their panels finished by QM_TFROMV from d_vleaf when
   // the slot is read (st_swap, st_get_block, st_loglik_*); re-factorising the slot drops the pending half
-  bool defer_leaf = false;
   bool leaf_pending[2] = {false, false};   // per physical arena
   CovPar leaf_cp[2];
   DevBuf<double> d_vleaf;
-  bool limited = false;               // limited_tree: single parents, marginal chain factors (k_marginal_invchol)
-  std::vector<int> twin_list;         // limited_tree: device ids of the blocks that own a chain panel
   DevBuf<int> d_twin;
-  int twin_maxM = 1;
   ncclComm_t comm = nullptr;                  // native RCCL communicator (st_comm_init); null = exchanges are the caller's
-  std::vector<LevelInfo> levels;
   std::vector<int> route_a, route_b;          // per level: ST_ROUTE_A_SLOTS phase-A / 2 phase-B route codes of the last launch
   int route_p = R_NONE;                       // ... and of the last st_predict
-  LevelInfo pred_info;
-  int pred_grp_first = 0, pred_grp_count = 0, pred_quad_first = 0, pred_quad_count = 0, pred_nkx = 0;   // phase P on k_factor_quad's leaf path (pred_nkx = 0: generic kernel)
-  size_t pred_lds = 0;
   std::vector<double> xtx;
   std::vector<long long> n_obs_q;
   struct PointSet *pts = nullptr;             // st_points_set: new locations to predict at (owned)
@@ -266,9 +168,6 @@ struct st_handle_s {
   DevBuf<unsigned char> d_obs;
   DevBuf<long long> d_dev2model, d_partner;
   DevBuf<Blk> d_blks;
-  size_t panel_total = 0, acc_total = 0;
-  long long scratch_stride = 0;
-  int scratch_wgs = 0;
   int slot_map[2] = {0, 1};    // logical slot (0 param, 1 alter) -> physical arena
   double tausq_inv[QMAX];
   std::vector<double> theta[2];
@@ -368,22 +267,6 @@ static void invalidate_stats(st_handle_s *h) {
   h->stats_valid = false; h->host_stats_valid = false;
 }
 
-static size_t lds_factor_bytes(int maxP, int maxM, int maxMa, int SR, bool big) {
-  size_t dbl = (size_t)3 * (maxP + maxM) + 3 * (size_t)maxM + (size_t)SR * maxP;
-  size_t bytes = dbl * 8 + (size_t)((maxP + maxM + 1) & ~1) * 4;
-  if (!big) bytes += ((size_t)2 * maxP * maxM + (size_t)maxMa * maxM + (size_t)2 * maxM * maxM) * 8;
-  return bytes + 64;
-}
-static size_t scratch_factor_doubles(int maxP, int maxM, int maxMa) {
-  return (size_t)2 * maxP * maxM + (size_t)maxMa * maxM + (size_t)2 * maxM * maxM;
-}
-static size_t lds_sample_sq_bytes(int maxM) { return ((size_t)maxM * ((maxM + 7) | 1) + maxM + 16) * 8; }   // S (odd row stride) + the pivot column
-static size_t lds_sample_bytes(int maxP, int maxM, int maxLd, bool big) {
-  size_t dbl = (size_t)(maxP + maxM) + 4 * (size_t)maxM + (size_t)MAXJ * maxM;   // ... + segment sums seg[t][r]
-  if (!big) dbl += (size_t)maxM * maxLd + (size_t)maxM * maxM;
-  return dbl * 8 + 64;
-}
-static size_t lds_loglik_bytes(int maxP, int maxM) { return ((size_t)maxP + 2 * (size_t)maxM) * 8 + 64; }
 
 extern "C" const char *st_last_error(st_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 extern "C" void st_set_create_error(const char *msg) { g_create_error = msg ? msg : ""; }   // other translation units of the library
@@ -391,17 +274,10 @@ extern "C" void st_set_create_error(const char *msg) { g_create_error = msg ? ms
 extern "C" int st_destroy(st_handle h) {
   if (!h) return ST_OK;
   (void)hipSetDevice(h->device);
-  h->d_cx.free(); h->d_cy.free(); h->d_y.free(); h->d_X.free(); h->d_w.free(); h->d_xb.free(); h->d_z.free(); h->d_B.free();
-  h->d_panels[0].free(); h->d_panels[1].free(); h->d_acc.free();
-  for (int s = 0; s < 2; ++s) { h->d_logdet[s].free(); h->d_loglik[s].free(); }
-  h->d_scalars.free(); h->d_partial.free(); h->d_stats.free(); h->d_xtx.free(); h->d_scratch.free(); h->d_tmp_n.free(); h->d_tsq.free();
-  h->d_mv.free(); h->d_anc.free(); h->d_dch.free(); h->d_lvl.free(); h->d_pred.free(); h->d_allobs.free(); h->d_err.free();
-  h->d_twin.free(); h->d_wgrps.free(); h->d_lcslabs.free(); h->d_lcrow.free(); h->d_rfvoff.free(); h->d_vscr.free(); h->d_vleaf.free(); h->d_s0.free(); h->d_s0off.free(); h->d_obs.free(); h->d_dev2model.free(); h->d_partner.free(); h->d_blks.free(); h->d_grps.free(); h->d_quads.free(); h->d_gdesc.free();
-  h->d_ownobs.free(); h->d_owngrp.free(); h->d_ownslow.free(); h->d_rowmask.free(); h->d_blkmask.free(); h->d_comm.free(); h->d_gather.free(); h->d_gidx.free(); h->d_gerr.free(); h->d_err2.free(); h->d_toplist.free();
   if (h->ev_top) (void)hipEventDestroy(h->ev_top);
   if (h->ev_main) (void)hipEventDestroy(h->ev_main);
   if (h->ev_stats) (void)hipEventDestroy(h->ev_stats);
-  if (h->stream2) (void)hipStreamDestroy(h->stream2); h->d_sum_w.free(); h->d_sum_yhat.free(); h->d_draws_w.free(); h->d_draws_yhat.free();
+  if (h->stream2) (void)hipStreamDestroy(h->stream2);
   prof_harvest(h);
   for (auto e : h->ev_free) (void)hipEventDestroy(e);
   if (h->comm) (void)ncclCommDestroy(h->comm);
@@ -410,677 +286,61 @@ extern "C" int st_destroy(st_handle h) {
   for (int i = 0; i < 2; ++i) if (h->ev_up[i]) (void)hipEventDestroy(h->ev_up[i]);
   if (h->ev_factor) (void)hipEventDestroy(h->ev_factor);
   points_free(h);
-  h->d_simz.free(); h->d_sime.free(); h->d_simw.free(); h->d_simy.free(); h->d_rowblk.free();
   if (h->stream && !h->ext_stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;   // the device buffers free themselves (DevBuf)
   return ST_OK;
-}
-
-static int create_impl(const st_problem *pb, const st_options *opt, st_handle *out, bool plan_only, int64_t *owner_out, int32_t *cut_out);
-
-extern "C" int st_create(const st_problem *pb, const st_options *opt, st_handle *out) {
-  return create_impl(pb, opt, out, false, nullptr, nullptr);
 }
 
 // Pure host: which rank owns each block (0-based block id) when `world` processes share one problem; -1 = replicated
 // on every rank (the levels above the cut).  No GPU needed: lets the sharding plan be tested on CPU.
-extern "C" int st_shard_plan(const st_problem *pb, int32_t world, int64_t *owner, int32_t *cut_level) {
-  st_options opt = {0, 1, 0, world, 0, 0};
-  st_handle dummy = nullptr;
-  return create_impl(pb, &opt, &dummy, true, owner, cut_level);
-}
-// the same for a problem that needs options to be read at all (limited_tree: st_options.reserved bit 1); rank / device of `opt` are ignored
 extern "C" int st_shard_plan_opt(const st_problem *pb, const st_options *opt_in, int32_t world, int64_t *owner, int32_t *cut_level) {
-  st_options opt = {0, 1, 0, world, 0, 0};
+  st_options opt = {0, 1, 0, world, 0, 0};   // rank / device of `opt_in` are ignored; it is there for a problem that needs options
+  // to be read at all (limited_tree: st_options.reserved bit 1)
   if (opt_in) { opt.reference_quirks = opt_in->reference_quirks; opt.force_generic = opt_in->force_generic; opt.reserved = opt_in->reserved; }
-  st_handle dummy = nullptr;
-  return create_impl(pb, &opt, &dummy, true, owner, cut_level);
+  TreeLayout t;
+  if (int rc = layout_order(pb, &opt, t, g_create_error)) return rc;
+  if (owner) for (size_t i = 0; i < t.blks.size(); ++i) owner[t.blks[i].model_id] = t.blk_owner[i];
+  if (cut_level) *cut_level = t.cut;
+  return ST_OK;
+}
+extern "C" int st_shard_plan(const st_problem *pb, int32_t world, int64_t *owner, int32_t *cut_level) {
+  return st_shard_plan_opt(pb, nullptr, world, owner, cut_level);
 }
 
-static int create_impl(const st_problem *pb, const st_options *opt, st_handle *out, bool plan_only, int64_t *owner_out, int32_t *cut_out) {
-  if (!pb || !out) { g_create_error = "st_create: null argument"; return ST_ERR_USAGE; }
-  *out = nullptr;
-  if (pb->d != 2) { g_create_error = "only d=2 is reachable from spamtree() (R/spamtree_fit.R:58-60)"; return ST_ERR_UNSUPPORTED; }
-  if (pb->q < 1 || pb->q > QMAX) { g_create_error = "q out of range"; return ST_ERR_UNSUPPORTED; }
-  if (pb->p < 1 || pb->p > ST_MAX_P) { g_create_error = "p must be in 1.." + std::to_string(ST_MAX_P) + " (ST_MAX_P)"; return ST_ERR_UNSUPPORTED; }
-  if (opt && (opt->world < 1 || opt->rank < 0 || opt->rank >= opt->world || opt->world > 64)) { g_create_error = "bad rank/world"; return ST_ERR_USAGE; }
-  // the covariance helpers map a NaN distance to a covariance of 0 (cov_exp clamps with fmax), so a non-finite coordinate
-  // would factorise silently instead of failing
-  if (pb->n_all > 0 && !pb->coords) { g_create_error = "st_create: coords is NULL"; return ST_ERR_USAGE; }
-  for (int64_t i = 0; i < 2 * pb->n_all; ++i)
-    if (!std::isfinite(pb->coords[i])) {
-      g_create_error = "st_create: coordinates must be finite (row " + std::to_string(i % pb->n_all) + ")";
-      return ST_ERR_USAGE;
-    }
-  st_handle_s *h = new st_handle_s();
-  h->rank = opt ? opt->rank : 0;
-  h->world = opt ? opt->world : 1;
-  h->device = opt ? opt->device : 0;
-  h->quirks = opt ? opt->reference_quirks : 1;
-  h->force_generic = opt ? opt->force_generic : 0;
-  h->cache_gram = !(opt && (opt->reserved & 1));
-  h->limited = opt && (opt->reserved & 2);
-  h->defer_leaf = !(opt && (opt->reserved & 4));
-  h->sw = read_switches();
-  const long long n = pb->n_all, nb = pb->n_blocks;
-  h->n_all = n; h->n_blocks = nb; h->q = pb->q; h->p = pb->p; h->d = pb->d; h->n_groups = pb->n_groups;
-  for (int j = 0; j < QMAX; ++j) h->tausq_inv[j] = 1.0;
+// ---- st_create, the device step ("st_create in three steps"): what the layout needs to know of the device,
+// then, with the layout built, the handle's streams, buffers and kernel attributes.  A failing HIP call leaves its text in
+// g_create_error and returns; st_create destroys the half-built handle, whose buffers free themselves.
+#define CCHK(call)                                                                                            \
+  do {                                                                                                        \
+    hipError_t e_ = (call);                                                                                   \
+    if (e_ != hipSuccess) { g_create_error = std::string(#call) + ": " + hipGetErrorString(e_); return ST_ERR_HIP; } \
+  } while (0)
 
-  // ---- block census (na_study :303-313), levels (make_gibbs_groups :194-301)
-  std::vector<int> m_of(nb), obs_of(nb, 0), grp_of(nb);
-  std::vector<long long> labels(pb->block_groups, pb->block_groups + nb);
-  std::sort(labels.begin(), labels.end());
-  labels.erase(std::unique(labels.begin(), labels.end()), labels.end());
-  if ((int)labels.size() > pb->n_groups) return fail_create(h, ST_ERR_TOPOLOGY, "more levels in block_groups than entries in res_is_ref");
-  std::vector<char> row_seen(n, 0);
-  for (long long u = 0; u < nb; ++u) {
-    m_of[u] = (int)(pb->indexing_ptr[u + 1] - pb->indexing_ptr[u]);
-    grp_of[u] = (int)(std::lower_bound(labels.begin(), labels.end(), pb->block_groups[u]) - labels.begin());
-    for (long long k = pb->indexing_ptr[u]; k < pb->indexing_ptr[u + 1]; ++k) {
-      const long long r = pb->indexing_idx[k];
-      if (r < 0 || r >= n || row_seen[r]) return fail_create(h, ST_ERR_TOPOLOGY, "indexing is not a partition of the rows");
-      row_seen[r] = 1;
-      if (std::isfinite(pb->y[r])) obs_of[u]++;
-    }
-  }
-  for (long long r = 0; r < n; ++r)
-    if (!row_seen[r]) return fail_create(h, ST_ERR_TOPOLOGY, "row without a block");
-  const int G = (int)labels.size();
-  std::vector<int> grp_has_obs(G, 0);
-  for (long long u = 0; u < nb; ++u)
-    if (obs_of[u] > 0) grp_has_obs[grp_of[u]] = 1;
-  int n_actual = 0;
-  for (int g = 0; g < G; ++g) n_actual += grp_has_obs[g];
-  for (int g = 0; g < n_actual; ++g)
-    if (!grp_has_obs[g]) return fail_create(h, ST_ERR_TOPOLOGY, "an empty level precedes an observed one");
-  h->n_actual_groups = n_actual;
-
-  // ---- device block order: by (level, id); rows contiguous per block
-  std::vector<int> order(nb);
-  std::iota(order.begin(), order.end(), 0);
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return grp_of[a] < grp_of[b]; });
-  h->blk_model2dev.assign(nb, -1);
-  {
-    // inside a level, blocks with the same last parent (identical ancestor chain) are made contiguous, so a
-    // workgroup can take several sibling leaf blocks as one column group
-    int i0 = 0;
-    while (i0 < nb) {
-      int i1 = i0;
-      while (i1 < nb && grp_of[order[i1]] == grp_of[order[i0]]) ++i1;
-      auto key = [&](int u) -> long long {
-        const long long p0 = pb->parents_ptr[u], p1 = pb->parents_ptr[u + 1];
-        if (p1 == p0) return -1;
-        const long long a = pb->parents_idx[p1 - 1];
-        return (a >= 0 && a < nb) ? (long long)h->blk_model2dev[a] : -1;
-      };
-      std::stable_sort(order.begin() + i0, order.begin() + i1, [&](int a, int b) { return key(a) < key(b); });
-      for (int i = i0; i < i1; ++i) h->blk_model2dev[order[i]] = i;
-      i0 = i1;
-    }
-  }
-  h->dev2model.resize(n); h->model2dev.resize(n);
-  h->blks.resize(nb);
-  long long row = 0, panel_total = 0, acc_total = 0;
-  for (int i = 0; i < nb; ++i) {
-    const int u = order[i];
-    Blk &B = h->blks[i];
-    B.row0 = row; B.m = m_of[u]; B.level = grp_of[u]; B.model_id = u; B.nobs = obs_of[u];
-    for (long long k = pb->indexing_ptr[u]; k < pb->indexing_ptr[u + 1]; ++k) {
-      if (k > pb->indexing_ptr[u] && pb->indexing_idx[k] <= pb->indexing_idx[k - 1])
-        return fail_create(h, ST_ERR_TOPOLOGY, "indexing(u) must be ascending");
-      h->dev2model[row] = pb->indexing_idx[k];
-      h->model2dev[pb->indexing_idx[k]] = row;
-      ++row;
-    }
-  }
-  // ---- ancestors: chain property anc(u) = anc(last parent) + [last parent]
-  for (int i = 0; i < nb; ++i) {
-    const int u = order[i];
-    Blk &B = h->blks[i];
-    const long long p0 = pb->parents_ptr[u], p1 = pb->parents_ptr[u + 1];
-    B.nanc = (int)(p1 - p0);
-    if (B.nanc > MAXJ) return fail_create(h, ST_ERR_UNSUPPORTED, "more than ST_MAX_ANCESTORS ancestors");
-    B.anc_ptr = (int)h->anc_idx.size();
-    int P = 0;
-    for (long long k = p0; k < p1; ++k) {
-      const long long a = pb->parents_idx[k];
-      if (a < 0 || a >= nb) return fail_create(h, ST_ERR_TOPOLOGY, "parent id out of range");
-      if (k > p0 && a <= pb->parents_idx[k - 1]) return fail_create(h, ST_ERR_TOPOLOGY, "parents(u) must be ascending");
-      if (grp_of[a] >= grp_of[u]) return fail_create(h, ST_ERR_TOPOLOGY, "parent on the same or a deeper level");
-      if (pb->res_is_ref[grp_of[a]] != 1) return fail_create(h, ST_ERR_TOPOLOGY, "parent on a non-reference level");
-      if (obs_of[a] == 0) return fail_create(h, ST_ERR_TOPOLOGY, "ancestor block without observations");
-      h->anc_idx.push_back(h->blk_model2dev[a]);
-      P += m_of[a];
-    }
-    B.P = P;
-    if (h->limited) {
-      if (B.nanc > 1) return fail_create(h, ST_ERR_TOPOLOGY, "limited_tree: a block has more than one parent (make_edges_limited gives one)");
-    } else if (B.nanc > 0) {
-      const long long last = pb->parents_idx[p1 - 1];
-      const long long q0 = pb->parents_ptr[last], q1 = pb->parents_ptr[last + 1];
-      bool ok = (q1 - q0) == (p1 - p0 - 1);
-      for (long long k = 0; ok && k < q1 - q0; ++k) ok = pb->parents_idx[q0 + k] == pb->parents_idx[p0 + k];
-      if (!ok) return fail_create(h, ST_ERR_UNSUPPORTED, "parents(u) is not parents(last parent)+[last parent]: for make_edges_limited's single-parent lists set the limited_tree bit of st_options");
-    }
-    const bool observed = B.nobs > 0;
-    B.isref = (observed && B.level < pb->n_groups && pb->res_is_ref[B.level] == 1) ? 1 : 0;
-    B.ld = B.P + (B.isref ? B.m : 1);
-    B.panel_off = -1; B.acc_off = 0; B.acc_len = 0;
-    B.chain_off = -1;
-    if (observed) {
-      B.panel_off = panel_total;
-      panel_total += (long long)B.m * B.ld;
-      B.chain_off = B.panel_off;
-      if (h->limited) {
-        B.chain_off = -1;
-        if (B.isref) {   // every observed reference block may be somebody's parent (observed or prediction children)
-          B.chain_off = panel_total;
-          panel_total += (long long)B.m * B.m;
-          h->twin_list.push_back(i);
-          h->twin_maxM = std::max(h->twin_maxM, B.m);
-        }
-      }
-    }
-  }
-  // acc layout + direct children
-  std::vector<std::vector<int>> dch(nb);
-  for (int i = 0; i < nb; ++i) {
-    Blk &B = h->blks[i];
-    if (B.nobs == 0) continue;
-    long long len = 0;
-    for (int t = 0; t < B.nanc; ++t) {
-      const int ma = h->blks[h->anc_idx[B.anc_ptr + t]].m;
-      len += (long long)ma * ma + ma;
-    }
-    if (len > INT_MAX) return fail_create(h, ST_ERR_UNSUPPORTED, "message record too large");
-    B.acc_len = (int)len;
-    B.acc_off = acc_total;
-    acc_total += len;
-    if (B.nanc > 0) dch[h->anc_idx[B.anc_ptr + B.nanc - 1]].push_back(i);
-  }
-  h->panel_total = (size_t)panel_total;
-  h->acc_total = (size_t)acc_total;
-
-  // ---- multi-GPU ownership: whole subtrees below a cut level go to one rank, the levels
-  // above the cut are replicated.  cut = first reference level (not the last observed one) with >= 2*world
-  // observed blocks; its blocks, contiguous in device order, are split into `world` runs of equal weight
-  // (weight = sum over the subtree of m*P^2, the factorisation cost).
-  h->blk_owner.assign(nb, -1);
-  h->cut = n_actual;            // nothing sharded unless a cut is found
-  if (h->world > 1) {
-    std::vector<int> cnt(G, 0);
-    for (int i = 0; i < nb; ++i) if (h->blks[i].nobs > 0) cnt[h->blks[i].level]++;
-    for (int g = 0; g + 1 < n_actual; ++g)
-      if (pb->res_is_ref[g] == 1 && cnt[g] >= 2 * h->world) { h->cut = g; break; }
-    if (h->cut < n_actual) {
-      const int cut = h->cut;
-      std::vector<int> root_of(nb, -1);   // device index of the cut-level ancestor (or self)
-      std::vector<double> wsub(nb, 0.0);
-      for (int i = 0; i < nb; ++i) {
-        const Blk &B = h->blks[i];
-        if (B.level < cut) continue;
-        int r = -1;
-        if (B.level == cut) r = i;
-        else if (B.nanc > 0) {
-          // through the DIRECT parent (the last ancestor), whose own root is known already: device order sorts blocks by level.
-          // Works for make_edges' full ancestor lists and for make_edges_limited's single parents (tree_dep.cpp:133-186) alike
-          const int par = h->anc_idx[B.anc_ptr + B.nanc - 1];
-          r = h->blks[par].level == cut ? par : root_of[par];
-        }
-        if (r < 0) return fail_create(h, ST_ERR_TOPOLOGY, "block below the cut level without an ancestor on it");
-        root_of[i] = r;
-        wsub[r] += (double)B.m * ((double)B.P * B.P + 1.0);
-      }
-      std::vector<int> roots;
-      double tot = 0;
-      for (int i = 0; i < nb; ++i) if (h->blks[i].level == cut && h->blks[i].nobs > 0) { roots.push_back(i); tot += wsub[i]; }
-      double acc_w = 0;
-      std::vector<int> root_owner(nb, 0);
-      for (size_t k = 0; k < roots.size(); ++k) {
-        int r = (int)std::floor((acc_w + 0.5 * wsub[roots[k]]) / tot * h->world);
-        r = std::min(std::max(r, 0), h->world - 1);
-        if (k > 0) r = std::max(r, root_owner[roots[k - 1]]);   // keep runs contiguous
-        root_owner[roots[k]] = r;
-        acc_w += wsub[roots[k]];
-      }
-      for (int i = 0; i < nb; ++i) if (root_of[i] >= 0) h->blk_owner[i] = root_owner[root_of[i]];
-    }
-  }
-  if (plan_only) {
-    if (owner_out) for (int i = 0; i < nb; ++i) owner_out[h->blks[i].model_id] = h->blk_owner[i];
-    if (cut_out) *cut_out = h->cut;
-    delete h;
-    return ST_OK;
-  }
-
-  // ---- level lists (u_by_block_groups) and per-level launch geometry
+static bool query_device(int device, DeviceLimits &dl) {
   hipDeviceProp_t prop;
-  if (hipSetDevice(h->device) != hipSuccess || hipGetDeviceProperties(&prop, h->device) != hipSuccess)
-    return fail_create(h, ST_ERR_HIP, "no usable HIP device (the product path has no CPU fallback)");
-  h->sm_count = prop.multiProcessorCount;
-  {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device) == hipSuccess && v > 0) h->lds_limit = (size_t)v;
-    if (h->lds_limit > 160 * 1024) h->lds_limit = 160 * 1024;
-    h->quad_nu = 4;   // units per workgroup of k_factor_quad (2 per workgroup with two workgroups per CU measured slower)
-  }
-  // limited_tree: k_marginal_invchol keeps K_uu and its inverse factor of a reference block in LDS (2 m^2 doubles: 101 rows
-  // at 160 KB).  Refused here: at launch the runtime would only answer "invalid argument" from inside st_factor
-  if (h->limited && (size_t)2 * h->twin_maxM * h->twin_maxM * sizeof(double) > h->lds_limit) {
-    const int lim = (int)std::floor(std::sqrt((double)h->lds_limit / (2.0 * sizeof(double))));
-    return fail_create(h, ST_ERR_UNSUPPORTED, "limited_tree: a reference block of " + std::to_string(h->twin_maxM) + " rows is wider than the " +
-                       std::to_string(lim) + " rows whose marginal factor fits the LDS (k_marginal_invchol keeps 2 m^2 doubles)");
-  }
-  h->levels.resize(n_actual);
-  h->route_a.assign((size_t)n_actual * ST_ROUTE_A_SLOTS, R_NONE);
-  h->route_b.assign((size_t)n_actual * 2, R_NONE);
-  auto geometry = [&](LevelInfo &L, const std::vector<int> &list, bool is_pred) {
-    for (int b : list) {
-      const Blk &B = h->blks[b];
-      L.maxP = std::max(L.maxP, B.P); L.maxM = std::max(L.maxM, B.m); L.maxLd = std::max(L.maxLd, B.ld); L.maxJ = std::max(L.maxJ, B.nanc);
-      for (int t = 0; t < B.nanc; ++t) L.maxMa = std::max(L.maxMa, h->blks[h->anc_idx[B.anc_ptr + t]].m);
-      // algorithmic bytes / flops, SURVEY.md section 8d
-      const double m = B.m, P = B.P, tri = P * (P + 1) / 2, rim = B.isref ? m * (m + 1) / 2 : m;
-      double trisum = 0;
-      for (int t = 0; t < B.nanc; ++t) { const double ma = h->blks[h->anc_idx[B.anc_ptr + t]].m; trisum += ma * (ma + 1) / 2; }
-      if (!is_pred) {
-        L.alg_bytes_A += (8.0 * 2 + 8) * (m + P) + (h->q > 1 ? 4 * (m + P) : 0) + 8 * tri + 8 * m * P + 8 * rim + 16;
-        L.alg_bytes_B += 8 * m * P + 8 * rim + 8 * P + 40 * m;
-        L.alg_bytes_C += 8 * m * P + 8 * rim + 8 * (m + P) + 8;
-        L.alg_bytes_msg += 2 * 8 * (P + trisum);
-        L.flops_A += 2 * m * P * P + (B.isref ? 2 * m * m * P + m * m * m : 0);
-        L.flops_B += (B.isref ? 2.0 / 3 * m * m * m : 0) + 4 * m * P;
-        for (int t = 0; t < B.nanc; ++t) { const double ma = h->blks[h->anc_idx[B.anc_ptr + t]].m; L.flops_B += 2 * ma * ma * m; }
-        L.flops_C += 2 * m * P + (B.isref ? m * m : 0);
-      }
-    }
-    L.maxMa = std::max(L.maxMa, 1);
-    const int SR = 8;
-    L.lds_factor = lds_factor_bytes(L.maxP, L.maxM, L.maxMa, SR, false);
-    L.big_factor = h->force_generic || L.lds_factor > h->lds_limit;
-    if (L.big_factor) L.lds_factor = lds_factor_bytes(L.maxP, L.maxM, L.maxMa, 4, true);
-    L.lds_sample = lds_sample_bytes(L.maxP, L.maxM, L.maxLd, false);
-    L.big_sample = h->force_generic || L.lds_sample > h->lds_limit || (L.isref && L.maxM > 32 && L.maxM <= 80);   // wide reference blocks: the
-    // scratch-arena kernel has the blocked matrix-core solve (the LDS-panel kernel factorises with three barriers per pivot)
-    if (L.big_sample) {
-      L.lds_sample = lds_sample_bytes(L.maxP, L.maxM, L.maxLd, true);
-      // the posterior precision in LDS, factorised and solved by ONE wave without workgroup barriers (wave_chol_solve_lds):
-      // every reference level where it fits (config #4: 74 KB, two workgroups per CU).  [The earlier LDS variant -- S and
-      // chol(S)^-1, 100 KB, one barrier per pivot -- only paid on levels of at most 2 x CUs blocks.]
-      if (L.isref && L.maxM <= 80 && L.lds_sample + lds_sample_sq_bytes(L.maxM) <= h->lds_limit) {
-        L.lds_sample += lds_sample_sq_bytes(L.maxM); L.sample_sq = true;
-      }
-    }
-    L.lds_loglik = lds_loglik_bytes(L.maxP, L.maxM);
-  };
-  for (int g = 0; g < n_actual; ++g) {
-    LevelInfo &L = h->levels[g];
-    L.first = (int)h->lvl_list.size();
-    L.isref = (int)pb->res_is_ref[g];
-    // reference order inside a level: block_names order (make_gibbs_groups :238-246); order is irrelevant on device
-    for (long long i = 0; i < nb; ++i) {
-      const long long u = pb->block_names[i] - 1;
-      if (u < 0 || u >= nb) return fail_create(h, ST_ERR_TOPOLOGY, "block_names out of range");
-      if (grp_of[u] == g && obs_of[u] > 0) h->lvl_list.push_back(h->blk_model2dev[u]);
-    }
-    L.count = (int)h->lvl_list.size() - L.first;
-    std::sort(h->lvl_list.begin() + L.first, h->lvl_list.end());
-    std::vector<int> list(h->lvl_list.begin() + L.first, h->lvl_list.end());
-    geometry(L, list, false);
-    // column groups for the MFMA path: a reference block alone, or consecutive sibling non-reference blocks
-    {
-      L.grp_first = (int)h->grps.size();
-      bool ok = !h->force_generic && L.maxP <= 256 && L.maxMa <= 32;
-      int maxM = 0, maxKb = 0, maxSub = 1;
-      size_t i = 0;
-      while (ok && i < list.size()) {
-        const Blk &B = h->blks[list[i]];
-        Grp G;
-        G.row0 = B.row0; G.blk0 = list[i]; G.nblk = 1; G.M = B.m; G.P = B.P;
-        if (B.m > 32) { ok = false; break; }
-        size_t j = i + 1;
-        if (!B.isref) {
-          const int lastp = B.nanc ? h->anc_idx[B.anc_ptr + B.nanc - 1] : -1;
-          while (j < list.size() && G.nblk < 32) {
-            const Blk &C = h->blks[list[j]];
-            const int lp = C.nanc ? h->anc_idx[C.anc_ptr + C.nanc - 1] : -1;
-            if (C.isref || lp != lastp || list[j] != list[j - 1] + 1 || G.M + C.m > 32) break;
-            G.M += C.m; G.nblk += 1; ++j;
-          }
-        }
-        maxM = std::max(maxM, G.M);
-        for (int t = 0; t < B.nanc; ++t) {
-          const int ma = h->blks[h->anc_idx[B.anc_ptr + t]].m;
-          maxSub = std::max(maxSub, ma > 16 ? (ma + 1) / 2 : ma);
-        }
-        maxKb = std::max(maxKb, B.P);
-        h->grps.push_back(G);
-        i = j;
-      }
-      L.grp_count = (int)h->grps.size() - L.grp_first;
-      if (ok) {
-        L.Pm4 = (L.maxP + 3) & ~3;
-        L.ldKV = std::max(2, (maxM + 1) & ~1);
-        int ldS = std::max(2, maxKb + 4);                       // 4 zero-filled pad columns per staged row
-        while ((ldS & 1) || ((ldS >> 1) & 1) == 0) ++ldS;   // 2 * odd: conflict-free A-operand reads
-        L.ldS = ldS; L.SRm = maxSub;
-        size_t st = (size_t)L.SRm * L.ldS + 16;
-        st = std::max(st, (size_t)2 * L.Pm4 + L.Pm4 / 2 + 2);   // prologue alias: ancestor x, y, outcome ids
-        st = std::max(st, (size_t)2 * 32 * CH_LD + 216 + 36);     // epilogue alias: R, Ri (stride CH_LD), elimination scratch
-        st = ((st + 1) & ~(size_t)1) + (size_t)L.ldS + 16;       // + the zero row at the end
-        L.stage_dbl = (int)((st + 1) & ~(size_t)1);
-        L.lds_fast = ((size_t)L.Pm4 * L.ldKV + 16 + L.stage_dbl + FM_VPART + 5 * 32) * 8 + 64 * 4 + 64;
-        ok = L.lds_fast <= h->lds_limit;
-      }
-      if (ok) {
-        L.Mr4 = std::max(4, (maxM + 3) & ~3);
-        L.Mrows = std::max(1, maxM);
-        L.ldN = L.maxLd | 1;              // odd stride >= the longest panel row
-        int maxJ = 0;
-        for (int b : list) maxJ = std::max(maxJ, h->blks[b].nanc);
-        L.av_dbl = std::max(32 * maxJ, 224);
-        L.maxJ = maxJ;
-        const size_t dbl = (size_t)maxM * L.ldN + 32 + (size_t)L.maxP + 32 + 6 * 32 + (size_t)L.av_dbl + 16 + (L.isref ? (size_t)maxM * CH_LD : 0) + 16;
-        L.lds_sfast = dbl * 8 + 64 * 4 + 64;
-        L.lds_slean = ((size_t)L.maxP + 32 + (size_t)L.av_dbl + 224 + 16 + 7 * 32 + (L.isref ? 2 * 32 * CH_LD : 0) + 16) * 8;
-        ok = L.lds_sfast <= h->lds_limit;
-      }
-      L.fast = ok;
-      if (!ok) { h->grps.resize(L.grp_first); L.grp_count = 0; }
-      if (!ok && !h->force_generic && L.maxM <= 80 && L.maxP <= BM_MAXP) {   // (a root level, P = 0, included: its 75 x 75 factorisation is the blocked one of the epilogue)
-        int ldS = L.maxP + 24;
-        while ((ldS & 1) || ((ldS >> 1) & 1) == 0) ++ldS;
-        L.bm_ldS = ldS;
-        const size_t work = std::max((size_t)17 * ldS + 16 * 80 + BM_KS * 5 * 256, (size_t)2 * L.maxM * L.maxM + 64);   // stage + zero row + V tile + partial V tiles | R, Ri of the epilogue
-        L.lds_bigmfma = ((size_t)3 * (L.maxP + L.maxM) + 3 * (size_t)L.maxM + work) * 8 + (size_t)((L.maxP + L.maxM + 1) & ~1) * 4 + 64;
-        L.bigmfma = L.lds_bigmfma <= h->lds_limit;
-        // non-reference blocks, <= 64 columns, every block behind at least one ancestor: k_factor_lchain (K in registers, the
-        // chain factor streamed through LDS twice); a property of the level, the same on every rank
-        if (L.bigmfma && h->sw.lchain && !h->limited && !L.isref && L.maxM <= 64 && L.maxP <= 544) {
-          bool all_anc = true;
-          for (int b : list) all_anc = all_anc && h->blks[b].nanc >= 1 && !h->blks[b].isref;
-          if (all_anc) L.lchain = L.maxP <= 384 ? 96 : 136;
-        }
-        // REFERENCE levels behind a chain (round 3): k_factor_lchain for the chain pass (it runs it at more than twice
-        // k_factor_bigmfma's rate, and a block's columns are two slabs on two CUs: the single-block top levels gain too), then
-        // k_factor_ref_finish per block.  L.count, not the rank's share: a property of the level
-        if (L.bigmfma && h->sw.lchain && h->sw.lchain_ref && !h->limited && L.isref && L.maxM <= 80 && L.maxP <= 544 && L.count >= h->sw.lchain_ref_min) {
-          bool all_anc = true;
-          for (int b : list) all_anc = all_anc && h->blks[b].nanc >= 1 && h->blks[b].isref;
-          if (all_anc) { L.lchain = L.maxP <= 384 ? 96 : 136; L.lchain_ref = true; }
-        }
-      }
-    }
-    if (L.lds_factor > h->lds_limit || L.lds_sample > h->lds_limit || L.lds_loglik > h->lds_limit)
-      return fail_create(h, ST_ERR_UNSUPPORTED, "block too large for the LDS-resident vectors");
-  }
-  // direct children that hold a message record: every observed block of a generic level, the first block of each
-  // column group of a fast level (the group's record is the sum over its sibling blocks)
-  {
-    std::vector<char> holder(nb, 0);
-    for (int g = 0; g < n_actual; ++g) {
-      const LevelInfo &L = h->levels[g];
-      if (L.fast) for (int k = 0; k < L.grp_count; ++k) holder[h->grps[L.grp_first + k].blk0] = 1;
-      else for (int k = 0; k < L.count; ++k) holder[h->lvl_list[L.first + k]] = 1;
-    }
-    for (int i = 0; i < nb; ++i) {
-      Blk &B = h->blks[i];
-      B.dch_ptr = (int)h->dch_idx.size();
-      B.ndch = 0;
-      if (!dch[i].empty() && !B.isref) return fail_create(h, ST_ERR_TOPOLOGY, "a non-reference block has observed children");
-      for (int c : dch[i]) if (holder[c]) { h->dch_idx.push_back(c); B.ndch++; }
-      if (B.ndch > 64 && B.nobs > 0 && h->levels[B.level].fast)
-        return fail_create(h, ST_ERR_UNSUPPORTED, "more than 64 direct child groups under one block");
-    }
-  }
-  // this rank's runs per level, exchange masks, cut-level record region
-  std::vector<unsigned char> rowmask(n, 0), blkmask(nb, 0);
-  for (int g = 0; g < n_actual; ++g) {
-    LevelInfo &L = h->levels[g];
-    L.own_lo = 0; L.own_n = L.count; L.gown_lo = 0; L.gown_n = L.grp_count;
-    if (g >= h->cut) {
-      int lo = L.count, hi = 0;
-      for (int k = 0; k < L.count; ++k)
-        if (h->blk_owner[h->lvl_list[L.first + k]] == h->rank) { lo = std::min(lo, k); hi = std::max(hi, k + 1); }
-      L.own_lo = lo < hi ? lo : 0; L.own_n = lo < hi ? hi - lo : 0;
-      for (int k = L.own_lo; k < L.own_lo + L.own_n; ++k)
-        if (h->blk_owner[h->lvl_list[L.first + k]] != h->rank) return fail_create(h, ST_ERR_TOPOLOGY, "a rank's blocks are not contiguous in a level");
-      if (L.fast) {
-        int glo = L.grp_count, ghi = 0;
-        for (int k = 0; k < L.grp_count; ++k) {
-          const Grp &Gr = h->grps[L.grp_first + k];
-          const bool mine = h->blk_owner[Gr.blk0] == h->rank;
-          for (int b2 = 0; b2 < Gr.nblk; ++b2)
-            if ((h->blk_owner[Gr.blk0 + b2] == h->rank) != mine) return fail_create(h, ST_ERR_TOPOLOGY, "a column group straddles two ranks");
-          if (mine) { glo = std::min(glo, k); ghi = std::max(ghi, k + 1); }
-        }
-        L.gown_lo = glo < ghi ? glo : 0; L.gown_n = glo < ghi ? ghi - glo : 0;
-      }
-    }
-    // sibling groups for k_factor_wide (levels on the wide-block path): consecutive blocks of this rank's run with the same
-    // last parent (= the same chain; device order keeps siblings and their rows contiguous), at most WG_MAXB blocks and
-    // WG_MAXN columns per group
-    L.wide_first = (int)h->wgrps.size(); L.wide_count = 0; L.wide_maxN = 0;
-    // measured at config #4 (577^2 x 3 outcomes): the leaf level 32.7 -> 28.2 ms, the 75-column reference level 13.9 -> 15.1 ms
-    // (two blocks per group: more passes than staging saved), levels with fewer groups than CUs lose parallelism -- so only
-    // big non-reference levels take it (SPAMTREE_WIDE=2 forces it on every eligible level: tests)
-    if (L.bigmfma && !L.lchain && h->sw.wide && !h->limited && (h->sw.wide == 2 || (!L.isref && L.count >= 2 * h->sm_count))) {   // L.count, not the rank's share: the two kernels round
-      // differently, and a level must take the same one on every rank of every world size (bit-identical sharded runs)
-      int k = L.own_lo;
-      const int kend = L.own_lo + L.own_n;
-      while (k < kend) {
-        const int b0 = h->lvl_list[L.first + k];
-        const Blk &B0 = h->blks[b0];
-        const int lastp = B0.nanc ? h->anc_idx[B0.anc_ptr + B0.nanc - 1] : -1;
-        WideGrp Gw; Gw.first = k - L.own_lo; Gw.count = 1;
-        int Ncols = B0.m;
-        while (k + Gw.count < kend && Gw.count < WG_MAXB) {
-          const int b1 = h->lvl_list[L.first + k + Gw.count];
-          const Blk &B1 = h->blks[b1];
-          const int lp1 = B1.nanc ? h->anc_idx[B1.anc_ptr + B1.nanc - 1] : -2;
-          if (lp1 != lastp || B1.nanc != B0.nanc || B1.isref != B0.isref || b1 != b0 + Gw.count || Ncols + B1.m > WG_MAXN ||
-              B1.row0 != B0.row0 + Ncols) break;
-          Ncols += B1.m; ++Gw.count;
-        }
-        L.wide_maxN = std::max(L.wide_maxN, Ncols);
-        h->wgrps.push_back(Gw);
-        ++L.wide_count;
-        k += Gw.count;
-      }
-      int ldS = L.maxP + 24;
-      while ((ldS & 1) || ((ldS >> 1) & 1) == 0) ++ldS;
-      L.bm_ldS = ldS;
-      const size_t work = std::max((size_t)17 * ldS + 16 * 16 * WG_JT, (size_t)2 * L.maxM * L.maxM + 64);
-      L.lds_wide = ((size_t)3 * (L.maxP + L.wide_maxN) + 2 * (size_t)L.wide_maxN + work) * 8 + (size_t)((L.maxP + L.wide_maxN + 1) & ~1) * 4 + 64;
-      if (L.lds_wide > h->lds_limit) { h->wgrps.resize(L.wide_first); L.wide_count = 0; }
-    }
-    // slabs for k_factor_lchain: sibling groups (consecutive blocks of this rank's run with the same last parent, contiguous
-    // rows AND panels, one row stride) cut into runs of <= 4 column tiles, as equal as possible (9 tiles -> 3 + 3 + 3)
-    L.lc_first = (int)h->lcslabs.size(); L.lc_count = 0;
-    L.rf_first = (int)h->rfvoff.size();
-    if (L.lchain) {
-      int k = L.own_lo;
-      const int kend = L.own_lo + L.own_n;
-      long long vrun = 0;   // reference levels: the groups' V matrices (P x the group's columns, row-major) follow each other
-      while (k < kend) {
-        const int b0 = h->lvl_list[L.first + k];
-        const Blk &B0 = h->blks[b0];
-        const int lastp = h->anc_idx[B0.anc_ptr + B0.nanc - 1];
-        int cnt = 1, Ncols = B0.m;
-        while (k + cnt < kend && cnt < 16) {
-          const int b1 = h->lvl_list[L.first + k + cnt];
-          const Blk &B1 = h->blks[b1];
-          if (b1 != b0 + cnt || B1.nanc != B0.nanc || h->anc_idx[B1.anc_ptr + B1.nanc - 1] != lastp || B1.P != B0.P || B1.ld != B0.ld ||
-              B1.row0 != B0.row0 + Ncols || B1.panel_off != B0.panel_off + (long long)Ncols * B0.ld) break;
-          Ncols += B1.m; ++cnt;
-        }
-        const int JT = (Ncols + 15) / 16, nsl = (JT + 3) / 4, tps = (JT + nsl - 1) / nsl;
-        for (int s0 = 0; s0 < Ncols; s0 += 16 * tps) {
-          LcSlab S;
-          S.row0 = B0.row0 + s0; S.pan0 = B0.panel_off + (long long)s0 * B0.ld; S.blk0 = b0;
-          S.ncol = std::min(16 * tps, Ncols - s0); S.ld = B0.ld; S.vcol0 = s0; S.vs0 = vrun;
-          h->lcslabs.push_back(S);
-          ++L.lc_count;
-        }
-        if (L.lchain_ref) {   // the group's blocks are equally wide (same P and ld): block i of the group owns columns [i m, (i + 1) m)
-          for (int i = 0; i < cnt; ++i) { h->rfvoff.push_back(vrun); vrun += rf_vsize(B0.P); }
-        }
-        k += cnt;
-      }
-      if (L.lchain_ref) h->vscr_need = std::max(h->vscr_need, (size_t)vrun);
-    }
-    // quads for k_factor_quad: runs of up to quad_nu column groups of one rank that share their ancestor chain
-    // (reference levels) or the chain without its last ancestor (leaf levels: cousins)
-    L.quad_first = (int)h->quads.size(); L.quad_count = 0; L.q_nkx = 0; L.qown_lo = 0; L.qown_n = 0;
-    if (L.fast && L.maxP > 0 && L.maxP <= 200 && L.maxMa <= 32) {
-      bool mixed = false;
-      int qlo = INT_MAX, qhi = 0;
-      // pass 0 ignores ownership: its quad count decides eligibility, so that every rank of every world size takes
-      // the same kernel for a level (results are then bit-identical across world sizes); pass 1 builds this rank's quads
-      int nq_any = 0;
-      // units per workgroup on THIS rank: a sharded level with few owned groups takes smaller quads, so that its
-      // workgroups still cover the CUs (a workgroup of 2 / 1 units lives about 0.72 / 0.5 as long as one of 4; results do
-      // not depend on the grouping: every unit's arithmetic is its own)
-      int nu_max = h->quad_nu;
-      {
-        int owned = 0;
-        for (int k2 = 0; k2 < L.grp_count; ++k2) {
-          const Grp &Gq = h->grps[L.grp_first + k2];
-          if (g < h->cut || h->blk_owner[Gq.blk0] == h->rank) ++owned;
-        }
-        double best = 1e300;
-        const int cand[3] = {4, 2, 1};
-        const double tl[3] = {1.0, 0.72, 0.5};
-        for (int c = 0; c < 3; ++c) {
-          if (cand[c] > h->quad_nu) continue;
-          const double rounds = std::ceil((double)std::max(owned, 1) / (double)(cand[c] * h->sm_count));
-          if (rounds * tl[c] < best - 1e-9) { best = rounds * tl[c]; nu_max = cand[c]; }
-        }
-        if (h->sw.quad_units >= 1 && h->sw.quad_units <= h->quad_nu) nu_max = h->sw.quad_units;   // tests: force the units per workgroup
-      }
-      for (int pass = 0; pass < 2; ++pass) {
-        int k = 0;
-        while (k < L.grp_count) {
-          const Grp &G0 = h->grps[L.grp_first + k];
-          const Blk &B0 = h->blks[G0.blk0];
-          const int J = B0.nanc, Jc = B0.isref ? J : std::max(J - 1, 0);
-          if ((B0.isref != 0) != (L.isref != 0)) mixed = true;
-          Quad Qd;
-          Qd.g0 = k; Qd.nu = 1; Qd.Jc = Jc; Qd.Pc = 0;
-          for (int t = 0; t < Jc; ++t) Qd.Pc += h->blks[h->anc_idx[B0.anc_ptr + t]].m;
-          while (Qd.nu < (pass == 0 ? h->quad_nu : nu_max) && k + Qd.nu < L.grp_count) {
-            const Grp &G1 = h->grps[L.grp_first + k + Qd.nu];
-            const Blk &B1 = h->blks[G1.blk0];
-            if (B1.nanc != J || B1.isref != B0.isref) break;
-            if (pass == 1 && h->blk_owner[G1.blk0] != h->blk_owner[G0.blk0]) break;
-            bool same = true;
-            for (int t = 0; t < Jc && same; ++t) same = h->anc_idx[B1.anc_ptr + t] == h->anc_idx[B0.anc_ptr + t];
-            if (!same) break;
-            ++Qd.nu;
-          }
-          if (pass == 0) ++nq_any;
-          else {
-            const bool mine = g < h->cut || h->blk_owner[G0.blk0] == h->rank;
-            if (mine) { qlo = std::min(qlo, L.quad_count); qhi = std::max(qhi, L.quad_count + 1); }
-            h->quads.push_back(Qd);
-            L.quad_count++;
-          }
-          k += Qd.nu;
-        }
-      }
-      L.qown_lo = qlo < qhi ? qlo : 0; L.qown_n = qlo < qhi ? qhi - qlo : 0;
-      const int need = (L.maxP + 3) / 4;
-      L.q_nkx = need <= 32 ? 32 : (need <= 38 ? 38 : (need <= 44 ? 44 : 50));
-      const int ldS = quad_lds_stride(L.q_nkx);   // the kernel's compile-time row stride (>= maxP + 24)
-      L.q_ldS = ldS;
-      L.lds_quad = ((size_t)h->quad_nu * 16 * ldS + ldS + (L.isref ? (size_t)h->quad_nu * 512 : (size_t)2 * h->quad_nu * QUAD_LEAF_KH * 64)) * 8;   // arena, zero row, V exchange / covariance scratch
-      const int min_groups = h->sw.quad_min >= 0 ? h->sw.quad_min : 2 * h->sm_count;   // smaller levels do not fill the chip with quads: k_factor_mfma's 4x more workgroups win
-      if (L.grp_count < 2 * nq_any || mixed || L.grp_count < min_groups) L.q_nkx = 0;   // mostly singletons: nothing to share
-      if (L.isref && L.q_nkx == 50) L.q_nkx = 0;                   // that instantiation spills registers: k_factor_mfma is faster
-    }
-  }
-  for (int i = 0; i < nb; ++i) {
-    const Blk &B = h->blks[i];
-    const bool mine = (h->blk_owner[i] == h->rank) || (h->blk_owner[i] < 0 && h->rank == 0);
-    blkmask[i] = mine ? 1 : 0;
-    if (mine) for (int r2 = 0; r2 < B.m; ++r2) rowmask[B.row0 + r2] = 1;
-    if (B.nobs > 0 && (h->blk_owner[i] < 0 || h->blk_owner[i] == h->rank)) h->own_obs_list.push_back(i);
-  }
-  if (h->cut < n_actual) {
-    const LevelInfo &L = h->levels[h->cut];
-    long long lo = -1, hi = -1;
-    for (int k = 0; k < L.count; ++k) {
-      const Blk &B = h->blks[h->lvl_list[L.first + k]];
-      if (lo < 0) lo = B.acc_off;
-      hi = B.acc_off + B.acc_len;
-      if (h->blk_owner[h->lvl_list[L.first + k]] != h->rank && B.acc_len > 0) h->top_zero.push_back({B.acc_off, (long long)B.acc_len});
-    }
-    h->top_off = std::max(0LL, lo); h->top_len = hi > lo ? hi - lo : 0;
-  }
-  for (int i = 0; i < nb; ++i) {
-    if (h->blks[i].nobs > 0) h->all_obs_list.push_back(i);
-    else {
-      if (h->blks[i].nanc == 0) return fail_create(h, ST_ERR_TOPOLOGY, "prediction block without parents");
-      h->pred_list.push_back(i);
-    }
-  }
-  geometry(h->pred_info, h->pred_list, true);
-  // ---- phase P on the leaf path of k_factor_quad (prediction blocks are non-reference blocks behind a chain of reference
-  // blocks, exactly what a leaf level is: spamtree_model.cpp:1296-1326 is A7 + a draw): column groups of consecutive sibling
-  // prediction blocks (<= 32 columns) and quads of up to four groups that share all but the last ancestor.  Every rank predicts
-  // every block (as the generic kernel does: w is replicated).  Not eligible (long chains, wide blocks): the generic kernel.
-  h->pred_grp_first = (int)h->grps.size(); h->pred_grp_count = 0; h->pred_quad_first = (int)h->quads.size(); h->pred_quad_count = 0; h->pred_nkx = 0;
-  {
-    const LevelInfo &Lp = h->pred_info;
-    bool ok = !h->force_generic && !h->pred_list.empty() && Lp.maxP > 0 && Lp.maxP <= 200 && Lp.maxMa <= 32 && Lp.maxM <= 32;
-    const std::vector<int> &list = h->pred_list;
-    size_t i = 0;
-    while (ok && i < list.size()) {
-      const Blk &B = h->blks[list[i]];
-      if (B.isref || B.nanc < 1) { ok = false; break; }
-      Grp G;
-      G.row0 = B.row0; G.blk0 = list[i]; G.nblk = 1; G.M = B.m; G.P = B.P;
-      const int lastp = h->anc_idx[B.anc_ptr + B.nanc - 1];
-      size_t j = i + 1;
-      while (j < list.size() && G.nblk < 32) {
-        const Blk &C = h->blks[list[j]];
-        const int lp = C.nanc ? h->anc_idx[C.anc_ptr + C.nanc - 1] : -1;
-        if (C.isref || lp != lastp || list[j] != list[j - 1] + 1 || G.M + C.m > 32 || C.row0 != G.row0 + G.M || C.P != B.P) break;
-        G.M += C.m; G.nblk += 1; ++j;
-      }
-      h->grps.push_back(G);
-      i = j;
-    }
-    if (!ok) h->grps.resize(h->pred_grp_first);
-    h->pred_grp_count = (int)h->grps.size() - h->pred_grp_first;
-    if (ok && h->pred_grp_count > 0) {
-      int k = 0;
-      while (k < h->pred_grp_count) {
-        const Grp &G0 = h->grps[h->pred_grp_first + k];
-        const Blk &B0 = h->blks[G0.blk0];
-        const int J = B0.nanc, Jc = J - 1;
-        Quad Qd;
-        Qd.g0 = k; Qd.nu = 1; Qd.Jc = Jc; Qd.Pc = 0;
-        for (int t = 0; t < Jc; ++t) Qd.Pc += h->blks[h->anc_idx[B0.anc_ptr + t]].m;
-        while (Qd.nu < h->quad_nu && k + Qd.nu < h->pred_grp_count) {
-          const Blk &B1 = h->blks[h->grps[h->pred_grp_first + k + Qd.nu].blk0];
-          if (B1.nanc != J) break;
-          bool same = true;
-          for (int t = 0; t < Jc && same; ++t) same = h->anc_idx[B1.anc_ptr + t] == h->anc_idx[B0.anc_ptr + t];
-          if (!same) break;
-          ++Qd.nu;
-        }
-        h->quads.push_back(Qd);
-        k += Qd.nu;
-      }
-      h->pred_quad_count = (int)h->quads.size() - h->pred_quad_first;
-      const int need = (Lp.maxP + 3) / 4;
-      h->pred_nkx = need <= 32 ? 32 : (need <= 38 ? 38 : (need <= 44 ? 44 : 50));
-      h->pred_lds = ((size_t)h->quad_nu * 16 * quad_lds_stride(h->pred_nkx) + quad_lds_stride(h->pred_nkx) + (size_t)2 * h->quad_nu * QUAD_LEAF_KH * 64) * 8;
-    }
-  }
+  if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) return false;
+  dl.sm_count = prop.multiProcessorCount;
+  int v = 0;
+  if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, device) == hipSuccess && v > 0) dl.lds_limit = (size_t)v;
+  hipFuncAttributes fa;
+  // a build whose unrolling failed keeps K in scratch memory (localSizeBytes > 0): never use that
+  const void *lc[2] = {(const void *)k_factor_lchain<96>, (const void *)k_factor_lchain<136>};
+  for (int i = 0; i < 2; ++i)
+    if (hipFuncGetAttributes(&fa, lc[i]) == hipSuccess) { dl.lchain_static[i] = fa.sharedSizeBytes; dl.lchain_no_scratch[i] = fa.localSizeBytes == 0; }
+  if (hipFuncGetAttributes(&fa, (const void *)k_factor_quad<4, 50, 13, false, true>) == hipSuccess) dl.quad_static = fa.sharedSizeBytes;
+  for (const void *f : {(const void *)k_factor_quad<4, 50, 13, true, true>, (const void *)k_factor_quad<4, 50, 13, true, false>})
+    if (hipFuncGetAttributes(&fa, f) == hipSuccess) dl.quad_static = std::max(dl.quad_static, (size_t)fa.sharedSizeBytes);
+  return true;
+}
 
-  // ---- row data in device order
+template <typename T>
+static hipError_t upload_or_dummy(DevBuf<T> &d, const std::vector<T> &v) {   // an empty list still gets one (zero) element to point at
+  return v.empty() ? d.upload(std::vector<T>(1)) : d.upload(v);
+}
+
+// stream, events, pinned buffers; the row data in device order
+static int create_rows(st_handle_s *h, const st_problem *pb) {
+  const long long n = h->n_all;
   std::vector<double> cx(n), cy(n), y(n), X((size_t)n * pb->p);
   std::vector<int> mv(n);
   std::vector<unsigned char> obs(n);
@@ -1088,8 +348,7 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
   for (long long i = 0; i < n; ++i) {
     const long long r = h->dev2model[i];
     cx[i] = pb->coords[r]; cy[i] = pb->coords[n + r];
-    const long long v = pb->mv_id[r] - 1;
-    if (v < 0 || v >= pb->q) return fail_create(h, ST_ERR_USAGE, "mv_id out of range");
+    const long long v = pb->mv_id[r] - 1;   // (in range: layout_levels has checked)
     mv[i] = (int)v;
     const bool ok = std::isfinite(pb->y[r]);
     obs[i] = ok ? 1 : 0;
@@ -1098,19 +357,16 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
     for (int j = 0; j < pb->p; ++j) X[(size_t)j * n + i] = pb->X[(size_t)j * n + r];
   }
   // Q3 partner rows (spamtree_model.cpp:1375): the t-th available row is paired with w[t]
-  std::vector<long long> partner(n);
-  {
-    std::vector<long long> rank_av(n, -1);
-    long long t = 0;
-    for (long long r = 0; r < n; ++r)
-      if (std::isfinite(pb->y[r])) rank_av[r] = t++;
-    for (long long i = 0; i < n; ++i) {
-      const long long r = h->dev2model[i];
-      partner[i] = (h->quirks && rank_av[r] >= 0) ? h->model2dev[rank_av[r]] : i;
-    }
+  std::vector<long long> partner(n), rank_av(n, -1);
+  long long t = 0;
+  for (long long r = 0; r < n; ++r)
+    if (std::isfinite(pb->y[r])) rank_av[r] = t++;
+  for (long long i = 0; i < n; ++i) {
+    const long long r = h->dev2model[i];
+    partner[i] = (h->quirks && rank_av[r] >= 0) ? h->model2dev[rank_av[r]] : i;
   }
   // XtX(j) over observed rows of outcome j (:151-155).  p <= 8: this serial host loop stays, because its order of additions
-  // fixes the last bits of every existing chain; p > 8: k_stats<q, true> on the device copy of X, further down
+  // fixes the last bits of every existing chain; p > 8: k_stats<q, true> on the device copy of X (create_state)
   h->xtx.assign((size_t)pb->p * pb->p * pb->q, 0.0);
   for (long long r = 0; pb->p <= 8 && r < n; ++r) {
     if (!std::isfinite(pb->y[r])) continue;
@@ -1119,12 +375,6 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
       for (int b2 = 0; b2 < pb->p; ++b2)
         h->xtx[(size_t)v * pb->p * pb->p + (size_t)b2 * pb->p + a] += pb->X[(size_t)a * n + r] * pb->X[(size_t)b2 * n + r];
   }
-
-#define CCHK(call)                                                                                            \
-  do {                                                                                                        \
-    hipError_t e_ = (call);                                                                                   \
-    if (e_ != hipSuccess) return fail_create(h, ST_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-  } while (0)
   CCHK(hipStreamCreate(&h->stream));
   CCHK(hipHostMalloc((void **)&h->pin, 64 * sizeof(double), hipHostMallocDefault));
   h->pin_up_len = QMAX + std::max(1, h->p * h->q);
@@ -1134,144 +384,51 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
   CCHK(h->d_cx.upload(cx)); CCHK(h->d_cy.upload(cy)); CCHK(h->d_y.upload(y)); CCHK(h->d_X.upload(X));
   CCHK(h->d_mv.upload(mv)); CCHK(h->d_obs.upload(obs)); CCHK(h->d_partner.upload(partner));
   CCHK(h->d_dev2model.upload(h->dev2model));
+  return ST_OK;
+}
+
+// the layout's lists on the device
+static int create_layout_buffers(st_handle_s *h) {
   {
     // device copy: acc_len = where, inside a child's record, the part FOR this block starts (after the block's own
     // ancestors in the full tree; at 0 when every block has a single parent)
     std::vector<Blk> db = h->blks;
     if (h->limited) for (Blk &B : db) B.acc_len = 0;
     CCHK(h->d_blks.upload(db));
-    if (h->limited) { std::vector<int> t = h->twin_list; if (t.empty()) t.push_back(0); CCHK(h->d_twin.upload(t)); }
+    if (h->limited) CCHK(upload_or_dummy(h->d_twin, h->twin_list));
   }
-  { std::vector<int> a = h->anc_idx; if (a.empty()) a.push_back(0); CCHK(h->d_anc.upload(a)); }
-  { std::vector<int> a = h->dch_idx; if (a.empty()) a.push_back(0); CCHK(h->d_dch.upload(a)); }
+  CCHK(upload_or_dummy(h->d_anc, h->anc_idx)); CCHK(upload_or_dummy(h->d_dch, h->dch_idx));
   CCHK(h->d_lvl.upload(h->lvl_list));
-  { std::vector<Grp> g = h->grps; if (g.empty()) g.push_back(Grp{0, 0, 0, 0, 0}); CCHK(h->d_grps.upload(g)); }
-  {
-    // group descriptors: the flattened metadata of every column group (layout: GdHead / gd_unpack)
-    int stride = 8;
-    for (const Grp &G : h->grps) {
-      const Blk &B0 = h->blks[G.blk0];
-      stride = std::max(stride, 8 + 4 * B0.nanc + 3 * G.nblk + 2 * std::min(B0.ndch, 64));   // children: record offset + group id
-    }
-    stride = (stride + 1) & ~1;
-    if (stride > GD_MAXW) return fail_create(h, ST_ERR_UNSUPPORTED, "group descriptor too long");
-    h->gd_stride = stride;
-    h->gdesc.assign(std::max<size_t>(1, h->grps.size()) * (size_t)stride, 0);
-    auto pack = [](long long lo, long long hi) { return (lo & 0xffffffffLL) | (hi << 32); };
-    std::vector<long long> blk2grp((size_t)nb, -1);   // the group that holds a block (its first block holds the group's record)
-    for (size_t g = 0; g < h->grps.size(); ++g)
-      for (int b = 0; b < h->grps[g].nblk; ++b) blk2grp[h->grps[g].blk0 + b] = (long long)g;
-    for (size_t g = 0; g < h->grps.size(); ++g) {
-      const Grp &G = h->grps[g];
-      const Blk &B0 = h->blks[G.blk0];
-      long long *w = h->gdesc.data() + g * (size_t)stride;
-      const int nch = std::min(B0.ndch, 64);
-      w[0] = G.row0; w[1] = B0.acc_off; w[2] = pack(G.M, G.P); w[3] = pack(B0.nanc, G.nblk); w[4] = pack(B0.isref, B0.level);
-      w[5] = pack(nch, h->limited ? 0 : B0.acc_len); w[6] = pack(G.blk0, 0);
-      long long ao = 0, aoff = 0;
-      for (int t = 0; t < B0.nanc; ++t) {
-        const Blk &Ba = h->blks[h->anc_idx[B0.anc_ptr + t]];
-        long long *a = w + 8 + 4 * t;
-        a[0] = pack(Ba.m, ao); a[1] = Ba.row0; a[2] = Ba.chain_off; a[3] = aoff;
-        ao += Ba.m; aoff += (long long)Ba.m * Ba.m + Ba.m;
-      }
-      w[7] = aoff;
-      for (int b = 0; b < G.nblk; ++b) {
-        const Blk &Bb = h->blks[G.blk0 + b];
-        long long *q = w + 8 + 4 * B0.nanc + 3 * b;
-        q[0] = Bb.panel_off; q[1] = Bb.row0; q[2] = Bb.ld;
-      }
-      for (int c = 0; c < nch; ++c) w[8 + 4 * B0.nanc + 3 * G.nblk + c] = h->blks[h->dch_idx[B0.dch_ptr + c]].acc_off;
-      for (int c = 0; c < nch; ++c) w[8 + 4 * B0.nanc + 3 * G.nblk + nch + c] = blk2grp[h->dch_idx[B0.dch_ptr + c]];   // k_gram_direct
-    }
-    // Gram parts of the last reference level straight from the leaf groups' panels (k_gram_direct): every block of that level
-    // has at most GRAM_DIRECT_MAXCH children, all of them column groups of the (non-reference) last level
-    h->gram_direct_level = -1;
-    {
-      const int gl = n_actual - 1, gp = n_actual - 2;
-      if (h->sw.gram_direct && gp >= 0 && !h->limited && h->levels[gl].fast && !h->levels[gl].isref && h->levels[gp].fast && h->levels[gp].isref &&
-          h->levels[gl].maxM <= 32 && h->levels[gl].maxP <= 255) {
-        bool ok = true;
-        const LevelInfo &Lp = h->levels[gp], &Ll = h->levels[gl];
-        for (int k = 0; k < Lp.grp_count && ok; ++k) {
-          const Grp &G = h->grps[Lp.grp_first + k];
-          const Blk &B0 = h->blks[G.blk0];
-          if (G.nblk != 1 || B0.ndch > GRAM_DIRECT_MAXCH) ok = false;
-          for (int c = 0; c < B0.ndch && ok; ++c) {
-            const long long cg = blk2grp[h->dch_idx[B0.dch_ptr + c]];
-            if (cg < Ll.grp_first || cg >= Ll.grp_first + Ll.grp_count || h->grps[cg].M > 32) ok = false;
-          }
-        }
-        // ... and every leaf group's record is read by a block of that level only (its direct parent): a leaf block hanging
-        // from a shallower reference level would leave that parent's Gram part unwritten on rebuild sweeps
-        for (int k = 0; k < Ll.grp_count && ok; ++k) {
-          const Grp &G = h->grps[Ll.grp_first + k];
-          for (int b = 0; b < G.nblk && ok; ++b) {
-            const Blk &Bl = h->blks[G.blk0 + b];
-            if (Bl.nanc == 0 || h->blks[h->anc_idx[Bl.anc_ptr + Bl.nanc - 1]].level != gp) ok = false;
-          }
-        }
-        if (ok) h->gram_direct_level = gp;
-      }
-    }
-    CCHK(h->d_gdesc.upload(h->gdesc));
-  }
-  { std::vector<Quad> g = h->quads; if (g.empty()) g.push_back(Quad{0, 0, 0, 0}); CCHK(h->d_quads.upload(g)); }
-  { std::vector<WideGrp> g = h->wgrps; if (g.empty()) g.push_back(WideGrp{0, 0}); CCHK(h->d_wgrps.upload(g)); }
+  CCHK(upload_or_dummy(h->d_grps, h->grps)); CCHK(h->d_gdesc.upload(h->gdesc));
+  CCHK(upload_or_dummy(h->d_quads, h->quads)); CCHK(upload_or_dummy(h->d_wgrps, h->wgrps));
   if (!h->lcslabs.empty()) { CCHK(h->d_lcslabs.upload(h->lcslabs)); CCHK(h->d_lcrow.alloc((size_t)2 * h->n_all)); }
   if (!h->rfvoff.empty()) { CCHK(h->d_rfvoff.upload(h->rfvoff)); CCHK(h->d_vscr.alloc(h->vscr_need + (size_t)2 * RF_BUFD)); }   // (+ what a chunk's DMA reads past the last block)
-  {
-    std::vector<long long> s0off((size_t)(nb > 0 ? nb : 1), -1);
-    size_t tot = 0;
-    for (int g = 0; g < n_actual; ++g) {
-      const LevelInfo &L = h->levels[g];
-      if (!L.isref || !(L.big_sample || L.fast)) continue;   // generic wide-block levels (round 2) and the column-group levels (round 3)
-      for (int k = 0; k < L.count; ++k) {
-        const int b = h->lvl_list[L.first + k];
-        s0off[b] = (long long)tot;
-        tot += (size_t)h->blks[b].m * h->blks[b].m;
-      }
-    }
-    CCHK(h->d_s0off.upload(s0off));
-    CCHK(h->d_s0.alloc(std::max(tot, (size_t)1)));
-  }
-  { std::vector<int> a = h->pred_list; if (a.empty()) a.push_back(0); CCHK(h->d_pred.upload(a)); }
+  CCHK(h->d_s0off.upload(h->s0off));
+  CCHK(h->d_s0.alloc(std::max(h->s0_total, (size_t)1)));
+  CCHK(upload_or_dummy(h->d_pred, h->pred_list));
   CCHK(h->d_allobs.upload(h->all_obs_list));
-  { std::vector<int> a = h->own_obs_list; if (a.empty()) a.push_back(0); CCHK(h->d_ownobs.upload(a)); }
-  for (int g = 0; g < n_actual; ++g) {
-    const LevelInfo &L = h->levels[g];
-    if (L.fast) for (int k = 0; k < L.gown_n; ++k) h->own_grp_list.push_back(L.grp_first + L.gown_lo + k);
-  }
-  for (int b : h->own_obs_list) if (!h->levels[h->blks[b].level].fast) h->own_obs_slow.push_back(b);
-  { std::vector<int> a = h->own_grp_list; if (a.empty()) a.push_back(0); CCHK(h->d_owngrp.upload(a)); }
-  { std::vector<int> a = h->own_obs_slow; if (a.empty()) a.push_back(0); CCHK(h->d_ownslow.upload(a)); }
-  CCHK(h->d_rowmask.upload(rowmask)); CCHK(h->d_blkmask.upload(blkmask));
-  CCHK(h->d_comm.alloc((size_t)2 * nb + 64));
-  {
-    // all-gather of w: every rank's owned rows (blocks below the cut, prediction blocks included), in device order; the
-    // replicated top is sampled identically everywhere and does not travel
-    std::vector<std::vector<int>> rows_of(h->world);
-    for (int i = 0; i < nb; ++i) {
-      const int o = h->blk_owner[i];
-      if (o < 0) continue;
-      const Blk &B = h->blks[i];
-      for (int r2 = 0; r2 < B.m; ++r2) rows_of[o].push_back((int)(B.row0 + r2));
-    }
-    size_t mx = 0;
-    for (auto &v : rows_of) mx = std::max(mx, v.size());
-    h->gather_cnt = (int)mx + 1;   // last slot: the rank's failure word
-    std::vector<int> gi((size_t)h->world * h->gather_cnt, -1);
-    for (int r = 0; r < h->world; ++r)
-      for (size_t i2 = 0; i2 < rows_of[r].size(); ++i2) gi[(size_t)r * h->gather_cnt + i2] = rows_of[r][i2];
-    CCHK(h->d_gidx.upload(gi));
-    CCHK(h->d_gather.alloc(gi.size()));
-    CCHK(h->d_gerr.alloc(64));
-  }
+  CCHK(upload_or_dummy(h->d_ownobs, h->own_obs_list));
+  CCHK(upload_or_dummy(h->d_owngrp, h->own_grp_list)); CCHK(upload_or_dummy(h->d_ownslow, h->own_obs_slow));
+  CCHK(h->d_rowmask.upload(h->rowmask)); CCHK(h->d_blkmask.upload(h->blkmask));
+  CCHK(h->d_comm.alloc((size_t)2 * h->n_blocks + 64));
+  CCHK(h->d_gidx.upload(h->gidx));
+  CCHK(h->d_gather.alloc(h->gidx.size()));
+  CCHK(h->d_gerr.alloc(64));
+  CCHK(upload_or_dummy(h->d_toplist, h->top_list));
+  CCHK(h->d_err2.alloc(2));
+  if (h->scratch_stride) CCHK(h->d_scratch.alloc((size_t)h->scratch_wgs * h->scratch_stride));
+  if (h->vleaf_total) CCHK(h->d_vleaf.alloc(h->vleaf_total));
+  return ST_OK;
+}
+
+// the chain's state: w, XB, z, the two panel arenas, the message arena, the statistics
+static int create_state(st_handle_s *h) {
+  const size_t n = (size_t)h->n_all, nb = (size_t)h->n_blocks;
   CCHK(h->d_w.alloc(n)); CCHK(h->d_xb.alloc(n)); CCHK(h->d_z.alloc(n)); CCHK(h->d_tmp_n.alloc(n + 64));
   CCHK(hipMemset(h->d_w.p, 0, n * sizeof(double)));
   CCHK(hipMemset(h->d_xb.p, 0, n * sizeof(double)));
   CCHK(hipMemset(h->d_z.p, 0, n * sizeof(double)));
-  CCHK(h->d_B.alloc((size_t)pb->p * pb->q));
+  CCHK(h->d_B.alloc((size_t)h->p * h->q));
   CCHK(h->d_tsq.alloc(QMAX));
   for (int s = 0; s < 2; ++s) {
     // + 128: k_factor_lchain stages chain rows in whole 128-double LDS-DMA pieces and may read up to 127 doubles past a row's
@@ -1286,146 +443,86 @@ static int create_impl(const st_problem *pb, const st_options *opt, st_handle *o
   CCHK(hipMemset(h->d_acc.p, 0, std::max<size_t>(h->acc_total, 1) * sizeof(double)));
   CCHK(h->d_scalars.alloc(8 + 2 * SUM2_WG));
   CCHK(h->d_err.alloc(2));
-  CCHK(h->d_partial.alloc((size_t)STATS_WG * (pb->p * pb->q + pb->q)));
-  CCHK(h->d_stats.alloc((size_t)pb->p * pb->q + pb->q));
-  if (pb->p > 8) {
-    // XtX(v)[a, b] is the statistic xty[a, v] with the row weight X[i, b]: one pass of k_stats per weight column b over the
-    // observed rows, reduced like every statistic (fixed shape, deterministic).  Entries [a, b] and [b, a] add the same
-    // products x_a x_b in the same order: the result is symmetric to the bit.
-    const int p = pb->p, pq = p * pb->q;
-    CCHK(h->d_xtx.alloc((size_t)p * pq));
-    for (int b2 = 0; b2 < p; ++b2) {
-      launch_stats(h, h->stream, h->d_X.p + (size_t)b2 * n);
-      hipLaunchKernelGGL(k_stats_final, dim3(pq), dim3(NT), 0, h->stream, h->d_partial.p, STATS_WG, pq + pb->q, h->d_xtx.p + (size_t)b2 * pq);
-    }
-    CCHK(hipGetLastError());
-    std::vector<double> t((size_t)p * pq);
-    CCHK(hipMemcpyAsync(t.data(), h->d_xtx.p, t.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    CCHK(hipStreamSynchronize(h->stream));
-    h->d_xtx.free();
-    for (int v = 0; v < pb->q; ++v)
-      for (int b2 = 0; b2 < p; ++b2)
-        for (int a = 0; a < p; ++a) h->xtx[(size_t)v * p * p + (size_t)b2 * p + a] = t[(size_t)b2 * pq + v * p + a];
+  CCHK(h->d_partial.alloc((size_t)STATS_WG * (h->p * h->q + h->q)));
+  CCHK(h->d_stats.alloc((size_t)h->p * h->q + h->q));
+  if (h->p <= 8) return ST_OK;
+  // XtX(v)[a, b] is the statistic xty[a, v] with the row weight X[i, b]: one pass of k_stats per weight column b over the
+  // observed rows, reduced like every statistic (fixed shape, deterministic).  Entries [a, b] and [b, a] add the same
+  // products x_a x_b in the same order: the result is symmetric to the bit.
+  const int p = h->p, pq = p * h->q;
+  CCHK(h->d_xtx.alloc((size_t)p * pq));
+  for (int b2 = 0; b2 < p; ++b2) {
+    launch_stats(h, h->stream, h->d_X.p + (size_t)b2 * n);
+    hipLaunchKernelGGL(k_stats_final, dim3(pq), dim3(NT), 0, h->stream, h->d_partial.p, STATS_WG, pq + h->q, h->d_xtx.p + (size_t)b2 * pq);
   }
-  // scratch for the generic kernels: a bounded number of resident workgroups, each with its own slice
-  {
-    size_t need = 0;
-    auto upd = [&](const LevelInfo &L) {
-      if (L.big_factor || L.bigmfma) need = std::max(need, scratch_factor_doubles(L.maxP, L.maxM, L.maxMa));
-      if (L.wide_count > 0) need = std::max(need, (size_t)2 * L.maxP * L.wide_maxN + (size_t)L.maxMa * L.wide_maxN);
-      if (L.big_sample) need = std::max(need, (size_t)L.maxM * L.maxM);
-    };
-    for (auto &L : h->levels) upd(L);
-    if (!h->pred_list.empty()) upd(h->pred_info);
-    if (need > 0) {
-      h->scratch_wgs = h->sm_count * 4;
-      h->scratch_stride = (long long)((need + 15) & ~(size_t)15);
-      CCHK(h->d_scratch.alloc((size_t)h->scratch_wgs * h->scratch_stride));
-    }
-  }
-  // opt in to > 64 KiB dynamic LDS
-  const int lim = (int)h->lds_limit;
-  (void)hipFuncSetAttribute((const void *)k_factor<false, MODE_FACTOR>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipFuncSetAttribute((const void *)k_factor<true, MODE_FACTOR>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipFuncSetAttribute((const void *)k_factor<false, MODE_PREDICT>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipFuncSetAttribute((const void *)k_factor<true, MODE_PREDICT>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipFuncSetAttribute((const void *)k_sample<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipFuncSetAttribute((const void *)k_sample<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipFuncSetAttribute((const void *)k_sample<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipFuncSetAttribute((const void *)k_loglik, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipFuncSetAttribute((const void *)k_factor_mfma, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipFuncSetAttribute((const void *)k_factor_wide<WG_JT>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  {
-    // k_factor_lchain: static + dynamic LDS must fit one CU's 160 KB, else the level stays on the older kernels
-    hipFuncAttributes fa;
-    size_t st96 = 16 * 1024, st136 = 16 * 1024;
-    bool ok96 = false, ok136 = false;   // a build whose unrolling failed keeps K in scratch memory (localSizeBytes > 0): never use that
-    if (hipFuncGetAttributes(&fa, (const void *)k_factor_lchain<96>) == hipSuccess) { st96 = fa.sharedSizeBytes; ok96 = fa.localSizeBytes == 0; }
-    if (hipFuncGetAttributes(&fa, (const void *)k_factor_lchain<136>) == hipSuccess) { st136 = fa.sharedSizeBytes; ok136 = fa.localSizeBytes == 0; }
-    for (auto &L : h->levels) {
-      if (!L.lchain) continue;
-      const size_t need = lc_dyn_doubles(L.lchain) * 8 + (L.lchain == 96 ? st96 : st136);
-      if (need > 160 * 1024 || !(L.lchain == 96 ? ok96 : ok136)) { L.lchain = 0; L.lchain_ref = false; }
-      if (L.lchain_ref) {
-        L.lds_ref_finish = rf_lds_bytes(L.maxM);
-        if (L.lds_ref_finish > h->lds_limit) { L.lchain = 0; L.lchain_ref = false; }
-      }
-    }
-    (void)hipFuncSetAttribute((const void *)k_factor_ref_finish, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-    (void)hipFuncSetAttribute((const void *)k_factor_lchain<96>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lc_dyn_doubles(96) * 8));
-    (void)hipFuncSetAttribute((const void *)k_factor_lchain<136>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lc_dyn_doubles(136) * 8));
-  }
-  (void)hipFuncSetAttribute((const void *)k_factor_bigmfma<5, 3, 24>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipFuncSetAttribute((const void *)k_factor_bigmfma<3, 5, 34>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipFuncSetAttribute((const void *)k_factor_bigmfma<4, 5, 34>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipFuncSetAttribute((const void *)k_sample_mfma, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipFuncSetAttribute((const void *)k_sample_wave, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipFuncSetAttribute((const void *)k_marginal_invchol, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipFuncSetAttribute((const void *)k_marginal_invchol_wave, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  {
-    // k_factor_quad: static + dynamic LDS must fit; levels that do not fit (or are too small to fill the chip) keep k_factor_mfma
-    const void *fq = (const void *)k_factor_quad<4, 50, 13, false, true>;
-    hipFuncAttributes fa;
-    size_t stat = 24 * 1024;
-    if (hipFuncGetAttributes(&fa, fq) == hipSuccess) stat = fa.sharedSizeBytes;
-    {
-      const void *fr = (const void *)k_factor_quad<4, 50, 13, true, true>;
-      if (hipFuncGetAttributes(&fa, fr) == hipSuccess) stat = std::max(stat, (size_t)fa.sharedSizeBytes);
-      const void *ft = (const void *)k_factor_quad<4, 50, 13, true, false>;
-      if (hipFuncGetAttributes(&fa, ft) == hipSuccess) stat = std::max(stat, (size_t)fa.sharedSizeBytes);
-    }
-    for (auto &L : h->levels) {
-      if (L.q_nkx == 0) continue;
-      if (L.lds_quad + stat > 160 * 1024) L.q_nkx = 0;
-    }
-    if (h->pred_nkx && h->pred_lds + stat > 160 * 1024) h->pred_nkx = 0;
-#define QATTR(NU_, NKX_, NKT_)                                                                                                       \
-  (void)hipFuncSetAttribute((const void *)k_factor_quad<NU_, NKX_, NKT_, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)stat); \
-  (void)hipFuncSetAttribute((const void *)k_factor_quad<NU_, NKX_, NKT_, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)stat); \
-  (void)hipFuncSetAttribute((const void *)k_factor_quad<NU_, NKX_, NKT_, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)stat)
-    QATTR(4, 50, 13); QATTR(4, 44, 11); QATTR(4, 38, 10); QATTR(4, 32, 8);
+  CCHK(hipGetLastError());
+  std::vector<double> t((size_t)p * pq);
+  CCHK(hipMemcpyAsync(t.data(), h->d_xtx.p, t.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  CCHK(hipStreamSynchronize(h->stream));
+  h->d_xtx.free();
+  for (int v = 0; v < h->q; ++v)
+    for (int b2 = 0; b2 < p; ++b2)
+      for (int a = 0; a < p; ++a) h->xtx[(size_t)v * p * p + (size_t)b2 * p + a] = t[(size_t)b2 * pq + v * p + a];
+  return ST_OK;
+}
+
+// opt in to > 64 KiB dynamic LDS; the second stream of the ahead-of-time top levels
+static int create_attributes(st_handle_s *h, const DeviceLimits &dl) {
+  const int lim = (int)h->lds_limit, cu = (int)DeviceLimits::CU_LDS;
+  auto dyn = [](const void *f, int bytes) { (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); };
+  for (const void *f : {(const void *)k_factor<false, MODE_FACTOR>, (const void *)k_factor<true, MODE_FACTOR>, (const void *)k_factor<false, MODE_PREDICT>,
+                        (const void *)k_factor<true, MODE_PREDICT>, (const void *)k_sample<false>, (const void *)k_sample<true>,
+                        (const void *)k_sample<true, true>, (const void *)k_loglik, (const void *)k_factor_mfma, (const void *)k_factor_wide<WG_JT>,
+                        (const void *)k_factor_ref_finish, (const void *)k_factor_bigmfma<5, 3, 24>, (const void *)k_factor_bigmfma<3, 5, 34>,
+                        (const void *)k_factor_bigmfma<4, 5, 34>, (const void *)k_sample_mfma, (const void *)k_sample_wave,
+                        (const void *)k_marginal_invchol, (const void *)k_marginal_invchol_wave})
+    dyn(f, lim);
+  dyn((const void *)k_factor_lchain<96>, (int)(lc_dyn_doubles(96) * 8));
+  dyn((const void *)k_factor_lchain<136>, (int)(lc_dyn_doubles(136) * 8));
+#define QATTR(NU_, NKX_, NKT_)                                                              \
+  dyn((const void *)k_factor_quad<NU_, NKX_, NKT_, true, true>, cu - (int)dl.quad_static);  \
+  dyn((const void *)k_factor_quad<NU_, NKX_, NKT_, true, false>, cu - (int)dl.quad_static); \
+  dyn((const void *)k_factor_quad<NU_, NKX_, NKT_, false, true>, cu - (int)dl.quad_static)
+  QATTR(4, 50, 13); QATTR(4, 44, 11); QATTR(4, 38, 10); QATTR(4, 32, 8);
 #undef QATTR
-    // the V tiles of the deferred leaf levels (one GPU only: the sharded protocol has no st_factor_enqueue of its own)
-    size_t vl = 0;
-    for (auto &L : h->levels) {
-      L.vl_off = -1;
-      if (!h->defer_leaf || h->world > 1 || h->limited || h->sw.factor_gen != 3 || !L.fast || L.isref || L.q_nkx == 0 || L.qown_n == 0) continue;
-      L.vl_off = (long long)vl;
-      vl += (size_t)L.qown_n * quad_vtiles(L.q_nkx) * (2 * h->quad_nu) * 256;
-    }
-    if (vl) CCHK(h->d_vleaf.alloc(vl));
-  }
-  {
-    // top levels that st_factor_begin may run ahead: the leading levels on k_factor_mfma (no global scratch), when every
-    // level of the tree is on the column-group path (the generic kernels share one scratch arena between phases)
-    h->g_top = 0;
-    bool all_fast = !h->limited && !h->force_generic;
-    for (int g = 0; g < n_actual; ++g) all_fast = all_fast && h->levels[g].fast;
-    if (all_fast) {
-      while (h->g_top < n_actual && !(h->sw.factor_gen == 3 && h->levels[h->g_top].q_nkx > 0)) ++h->g_top;
-      if (h->g_top >= n_actual) h->g_top = 0;   // nothing would be left for the main stream to hide it under
-    }
-    // the top levels are a fixed cost (0.19 ms at n = 1e6: a quarter of a rank's phase A on 8 GPUs, 40 % of phase A at
-    // n = 1e5); at n = 1e6 on one GPU the sweep fills the chip and the gain is 1.5 % (SPAMTREE_ASYNC_TOP=0 turns it off)
-    h->async_top = h->g_top > 0 && h->sw.async_top;
-    std::vector<int> tl;
-    for (int b : h->own_obs_list) if (h->blks[b].level < h->g_top) tl.push_back(b);
-    h->n_toplist = (int)tl.size();
-    if (tl.empty()) tl.push_back(0);
-    CCHK(h->d_toplist.upload(tl));
-    CCHK(h->d_err2.alloc(2));
-    if (h->async_top) {
-      CCHK(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
-      CCHK(hipEventCreateWithFlags(&h->ev_top, hipEventDisableTiming));
-      CCHK(hipEventCreateWithFlags(&h->ev_main, hipEventDisableTiming));
-      CCHK(hipEventCreateWithFlags(&h->ev_stats, hipEventDisableTiming));
-    }
+  // the top levels are a fixed cost (0.19 ms at n = 1e6: a quarter of a rank's phase A on 8 GPUs, 40 % of phase A at
+  // n = 1e5); at n = 1e6 on one GPU the sweep fills the chip and the gain is 1.5 % (SPAMTREE_ASYNC_TOP=0 turns it off)
+  h->async_top = h->g_top > 0 && h->sw.async_top;
+  if (h->async_top) {
+    CCHK(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
+    CCHK(hipEventCreateWithFlags(&h->ev_top, hipEventDisableTiming));
+    CCHK(hipEventCreateWithFlags(&h->ev_main, hipEventDisableTiming));
+    CCHK(hipEventCreateWithFlags(&h->ev_stats, hipEventDisableTiming));
   }
   (void)hipGetLastError();
+  return ST_OK;
+}
 #undef CCHK
+
+// st_create in three steps: the order of the blocks (layout_order), what the device allows (query_device), the launch
+// structures (layout_levels); then the handle's device side
+extern "C" int st_create(const st_problem *pb, const st_options *opt, st_handle *out) {
+  if (!pb || !out) { g_create_error = "st_create: null argument"; return ST_ERR_USAGE; }
+  *out = nullptr;
+  st_handle_s *h = new st_handle_s();
+  h->device = opt ? opt->device : 0;
+  h->quirks = opt ? opt->reference_quirks : 1;
+  h->cache_gram = !(opt && (opt->reserved & 1));
+  for (int j = 0; j < QMAX; ++j) h->tausq_inv[j] = 1.0;
+  std::string msg;
+  DeviceLimits dl;
+  int rc = layout_order(pb, opt, *h, msg);
+  if (rc == ST_OK && !query_device(h->device, dl)) { rc = ST_ERR_HIP; msg = "no usable HIP device (the product path has no CPU fallback)"; }
+  if (rc == ST_OK) rc = layout_levels(pb, read_switches(), dl, *h, msg);
+  if (rc != ST_OK) return fail_create(h, rc, msg);
+  const int n_actual = h->n_actual_groups;
+  h->route_a.assign((size_t)n_actual * ST_ROUTE_A_SLOTS, R_NONE);
+  h->route_b.assign((size_t)n_actual * 2, R_NONE);
   h->s0_valid.assign((size_t)std::max(n_actual, 1), 0);
   h->prof_level_ms.assign(2 * n_actual, 0.0);
   h->prof_level_n.assign(2 * n_actual, 0);
+  if ((rc = create_rows(h, pb)) || (rc = create_layout_buffers(h)) || (rc = create_state(h)) || (rc = create_attributes(h, dl)))
+    return fail_create(h, rc, std::string(g_create_error));
   *out = h;
   return ST_OK;
 }
@@ -2670,7 +1767,6 @@ extern "C" int st_cross_covariance_ag10(const double *coords1, const int64_t *mv
                        (long long)n2, cp, dout.p);
     if (!bad(hipGetLastError())) bad(hipMemcpy(out, dout.p, (size_t)n1 * n2 * sizeof(double), hipMemcpyDeviceToHost));
   }
-  d1.free(); d2.free(); dout.free(); dm1.free(); dm2.free();
   return rc;
 }
 
@@ -2778,16 +1874,11 @@ struct PointSet {
   DevBuf<PtTile> d_jtiles;
   DevBuf<int> d_jgen, d_pt_grp, d_pt_a;
   DevBuf<double> d_jout, d_jscratch, d_pacc;   // cov and chol of the last call (2 x cov_total); scratch; pair accumulators
-  void free() {
-    d_jgroups.free(); d_jmem.free(); d_jcols.free(); d_jtiles.free(); d_jgen.free(); d_pt_grp.free(); d_pt_a.free();
-    d_jout.free(); d_jscratch.free(); d_pacc.free();
-    d_px.free(); d_py.free(); d_X.free(); d_z.free(); d_out.free(); d_scratch.free(); d_pmv.free(); d_chain_blk.free(); d_pt_chain.free();
-    d_gen.free(); d_order.free(); d_chains.free(); d_tiles.free(); d_acc.free(); d_keep_w.free(); d_keep_yhat.free();
-  }
 };
 
 static void points_free(st_handle_s *h) {
-  if (h->pts) { h->pts->free(); delete h->pts; h->pts = nullptr; }
+  delete h->pts;   // its device buffers free themselves
+  h->pts = nullptr;
 }
 
 // st_points_set (joint_id NULL) and st_points_set_joint
@@ -2918,12 +2009,9 @@ static int points_set_impl(st_handle h, int64_t n_new, const double *coords, con
   std::vector<double> px(coords, coords + n_new), py(coords + n_new, coords + 2 * n_new);
   std::vector<int> pmv(n_new);
   for (int64_t i = 0; i < n_new; ++i) pmv[i] = (int)(mv[i] - 1);
-  if (chain_blk.empty()) chain_blk.push_back(0);
-  if (tiles.empty()) tiles.push_back(PtTile{0, 0, 0, 0});
-  if (gen.empty()) gen.push_back(0);
   HCHK(h, ps->d_px.upload(px)); HCHK(h, ps->d_py.upload(py)); HCHK(h, ps->d_pmv.upload(pmv));
   HCHK(h, ps->d_order.upload(order)); HCHK(h, ps->d_pt_chain.upload(pt_chain)); HCHK(h, ps->d_chains.upload(chains));
-  HCHK(h, ps->d_chain_blk.upload(chain_blk)); HCHK(h, ps->d_tiles.upload(tiles)); HCHK(h, ps->d_gen.upload(gen));
+  HCHK(h, upload_or_dummy(ps->d_chain_blk, chain_blk)); HCHK(h, upload_or_dummy(ps->d_tiles, tiles)); HCHK(h, upload_or_dummy(ps->d_gen, gen));
   HCHK(h, ps->d_z.alloc(n_new));
   HCHK(h, ps->d_out.alloc((size_t)4 * n_new));
   if (ps->grid_generic > 0) HCHK(h, ps->d_scratch.alloc((size_t)ps->grid_generic * 2 * ps->scratch_stride));
@@ -2994,11 +2082,9 @@ static int points_set_impl(st_handle h, int64_t n_new, const double *coords, con
   ps->j_alg_bytes = jb; ps->j_flops = jf;
   ps->jgrid_generic = (int)std::min<size_t>(jgen.size(), (size_t)4 * h->sm_count);
   std::vector<long long> jmem_ll(j_mem.begin(), j_mem.end());
-  if (jtiles.empty()) jtiles.push_back(PtTile{0, 0, 0, 0});
   if (jcols.empty()) jcols.push_back(PtCol{0, -1});
-  if (jgen.empty()) jgen.push_back(0);
-  HCHK(h, ps->d_jgroups.upload(groups)); HCHK(h, ps->d_jmem.upload(jmem_ll)); HCHK(h, ps->d_jtiles.upload(jtiles));
-  HCHK(h, ps->d_jcols.upload(jcols)); HCHK(h, ps->d_jgen.upload(jgen)); HCHK(h, ps->d_pt_grp.upload(pt_grp)); HCHK(h, ps->d_pt_a.upload(pt_a));
+  HCHK(h, ps->d_jgroups.upload(groups)); HCHK(h, ps->d_jmem.upload(jmem_ll)); HCHK(h, upload_or_dummy(ps->d_jtiles, jtiles));
+  HCHK(h, ps->d_jcols.upload(jcols)); HCHK(h, upload_or_dummy(ps->d_jgen, jgen)); HCHK(h, ps->d_pt_grp.upload(pt_grp)); HCHK(h, ps->d_pt_a.upload(pt_a));
   HCHK(h, ps->d_jout.alloc((size_t)2 * ps->cov_total));
   if (ps->jgrid_generic > 0) HCHK(h, ps->d_jscratch.alloc((size_t)ps->jgrid_generic * PJ_SCRATCH_COLS * ps->scratch_stride));
   ps->j_off = j_off; ps->j_mptr = j_mptr; ps->j_mem = j_mem;

@@ -152,3 +152,30 @@ def visible_gpus():
     r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count())"], capture_output=True,
                        text=True, timeout=300, check=True)
     return int(r.stdout.split()[-1])
+
+
+def problem_arrays(pb):
+    """The arrays of a make_problem result in the layout st_problem points at (int64 ids, column-major X and coords).  The
+    caller may corrupt an entry before handing them to st_problem_struct."""
+    from spamtree_amd.model import _f64, _i64, _lists_to_csr
+    a = dict(n_all=int(pb["n"]), d=2, q=int(pb["q"]), p=int(pb["p"]), y=_f64(pb["y"]).copy(),
+             X=np.asfortranarray(pb["X"], dtype=np.float64).copy(order="F"),
+             coords=np.asfortranarray(pb["coords"], dtype=np.float64).copy(order="F"), mv_id=_i64(pb["mv_id"]).copy(),
+             res_is_ref=_i64(pb["res_is_ref"]).copy(), block_names=_i64(pb["block_names"]).copy(),
+             block_groups=_i64(pb["block_groups"]).copy())
+    for name in ("indexing", "parents", "children"):
+        a[name + "_ptr"], a[name + "_idx"] = _lists_to_csr(pb[name])
+    return a
+
+
+def st_problem_struct(a):
+    """st_problem over the arrays of problem_arrays (which must outlive it); a None array becomes a null pointer."""
+    from spamtree_amd import _lib
+
+    def ptr(x, ty):
+        return x.ctypes.data_as(ty) if x is not None else ty()
+    return _lib.StProblem(a["n_all"], a["d"], a["q"], a["p"], int(a["res_is_ref"].size), int(a["block_names"].size),
+                          ptr(a["y"], _lib.c_dp), ptr(a["X"], _lib.c_dp), ptr(a["coords"], _lib.c_dp), ptr(a["mv_id"], _lib.c_ip),
+                          *[ptr(a[k], _lib.c_ip) for k in ("res_is_ref", "block_names", "block_groups", "indexing_ptr",
+                                                           "indexing_idx", "parents_ptr", "parents_idx", "children_ptr",
+                                                           "children_idx")])
