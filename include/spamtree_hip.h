@@ -11,7 +11,8 @@
  * Return value of every function: 0 = ok; 1/2/3 = Cholesky failed in phase A at the root / a reference block /
  * a non-reference row (the reference's `errtype`, spamtree_model.cpp:876, 919, 958); 10/11 = Cholesky failed in
  * the w sweep (spamtree_model.cpp:1056, 1135); negative = usage / HIP error (st_last_error() has the text).
- * No exception crosses this boundary.
+ * No exception crosses this boundary.  tests/test_gpu_failure_routes.py pins these codes against the oracle with every
+ * phase-A and sweep kernel as the one that fails, on every path the failure word takes back to the caller.
  */
 #ifndef SPAMTREE_HIP_H
 #define SPAMTREE_HIP_H

@@ -92,6 +92,7 @@ class SpamTreeMV:
         self.n_blocks = int(keep[5].size)
         self.theta = [np.asarray(theta, dtype=np.float64).copy(), np.asarray(theta, dtype=np.float64).copy()]
         self.loglik_w = [float("nan"), float("nan")]
+        self.last_errtype = self.last_sample_errtype = -1      # errtype of the last phase A / sweep (-1: none)
         self.Bcoeff = np.zeros((self.p, self.q), order="F")
         beta = np.asarray(beta, dtype=np.float64).reshape(-1)
         for j in range(self.q):
@@ -150,6 +151,7 @@ class SpamTreeMV:
             rc = self._check(self.lib.st_sample_w(self.h, _dp(z), 0, 0))
         else:
             rc = self._check(self.lib.st_sample_w(self.h, None, int(seed), int(it)))
+        self.last_sample_errtype = rc if rc > 0 else -1
         if rc > 0:
             raise SpamTreeError("Error at gibbs_sample_w")           # Rcpp::stop (:1215-1217)
 

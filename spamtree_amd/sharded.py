@@ -141,6 +141,7 @@ class ShardedSpamTreeMV(SpamTreeMV):
             rc = self._check(self.lib.st_mg_unpack_w(self.h))
         else:
             rc = self._exchange_w()
+        self.last_sample_errtype = rc if rc > 0 else -1
         if rc > 0:
             raise SpamTreeError("Error at gibbs_sample_w")
 
@@ -169,6 +170,7 @@ class ShardedSpamTreeMV(SpamTreeMV):
         self._allgather(rcv.value, cnt.value)
         self._allreduce(pc.value, nc.value)
         rc = self._check(self.lib.st_mg_gather_w_unpack(self.h))
+        self.last_sample_errtype = rc if rc > 0 else -1
         if rc > 0:
             raise SpamTreeError("Error at gibbs_sample_w")
         ll = C.c_double(0.0)

@@ -70,9 +70,121 @@ def plan_worker(rank, world, port, case, out_dir):
     dist.destroy_process_group()
 
 
-def gpu_worker(rank, world, port, side, q, out_dir, steps, limited=False):
-    """Needs a GPU: `world` processes share device 0 and one problem; results go to out_dir for the parent to compare."""
+FAILURE_CASE = dict(side=40, q=1, seed=21, missing=0.05)      # the two-rank failure case of tests/test_gpu_sharded.py
+
+
+def failure_problem(case):
+    """make_problem(**case) with rows of its deepest level relabelled as a further outcome (tests/util.level_failure_problem),
+    all of them inside subtrees that ONE rank -- the second -- of the two-rank plan owns.  Returns (pb, relabelled problem,
+    its failing inputs, the level, the plan's owners)."""
+    from spamtree_amd.sharded import shard_plan
+    from tests.util import level_failure_problem, make_problem, problem_arrays, st_problem_struct
+    pb = make_problem(**case)
+    arrays = problem_arrays(pb)
+    owner, cut = shard_plan(st_problem_struct(arrays), 2)
+    labels = np.unique(pb["block_groups"])
+    observed = [u for u, ix in enumerate(pb["indexing"]) if np.isfinite(pb["y"][ix]).any()]
+    level = int(np.searchsorted(labels, max(pb["block_groups"][u] for u in observed)))
+    assert level >= cut
+    blocks = [u for u in observed if pb["block_groups"][u] == labels[level] and owner[u] == 1]
+    fp, f = level_failure_problem(pb, level, blocks=blocks)
+    rng = np.random.default_rng(7)
+    f.update(w=rng.standard_normal(pb["n"]), zs=[rng.standard_normal(pb["n"]) for _ in range(3)], theta2=fp["theta"] * 1.03)
+    return pb, fp, f, level, owner
+
+
+def failure_problem_on_oracle(case):
+    """failure_problem(case) checked on the oracle, no GPU involved: every relabelled row lies in a subtree of the second
+    rank, phase A at theta_bad fails at that level with errtype 3 (shallower levels succeed), the sweep with the bad
+    tausq^-1 fails there only with 11.  Returns failure_problem's tuple and the oracle's w after the sweep with zs[2] from
+    the restored state."""
+    from tests.util import oracle_model, oracle_phase_a_failure, oracle_sweep_failing_levels
+    pb, fp, f, level, owner = failure_problem(case)
+    block_of = np.empty(pb["n"], dtype=np.int64)
+    for u, ix in enumerate(pb["indexing"]):
+        block_of[ix] = u
+    assert f["rows"].size >= 4 and np.all(owner[block_of[f["rows"]]] == 1) and np.any(owner == 0)
+    om = oracle_model(fp, theta=fp["theta"], w=f["w"], beta=np.array([0.3, -0.2, 0.1]), tausq=1.0 / f["tausq_inv_ok"])
+    assert om.get_loglik_comps_w(om.param_data)
+    om.theta_update(om.alter_data, f["theta_bad"])
+    assert oracle_phase_a_failure(om, om.alter_data) == (3, level)
+    om.gibbs_sample_w(f["zs"][0])
+
+    def set_tausq_inv(t):
+        om.tausq_inv = t.copy()
+        om.tausq_inv_long = om.tausq_inv[om.mv_id - 1].astype(np.float64)
+
+    set_tausq_inv(f["tausq_inv_bad"])
+    with np.errstate(all="ignore"):
+        try:
+            om.gibbs_sample_w(f["zs"][1])
+        except RuntimeError:
+            pass
+    assert om.last_sample_errtype == 11 and oracle_sweep_failing_levels(om) == [level]
+    set_tausq_inv(f["tausq_inv_ok"])
+    om.w = f["w"].copy()
+    om.gibbs_sample_w(f["zs"][2])
+    return (pb, fp, f, level, owner), om.w.copy(), om.na_ix_all
+
+
+def _failure_case(rank, world, dist, case, out_dir):
+    """A phase-A and a sweep failure that only one rank's kernels see: the codes every rank reports (phase A; the sweep with
+    w exchanged by all-gather, by all-reduce and in the fused form), and the state every rank has afterwards."""
+    from spamtree_amd.model import SpamTreeError, _dp, _f64
+    from spamtree_amd.sharded import ShardedSpamTreeMV
+    _, fp, f, level, _ = failure_problem(case)
+    m = ShardedSpamTreeMV(fp["y"], fp["X"], fp["Z"], fp["coords"], fp["mv_id"], fp["blocking"], fp["gix_block"],
+                          fp["res_is_ref"], fp["parents"], fp["children"], False, fp["block_names"], fp["block_groups"],
+                          fp["indexing"], f["w"], np.array([0.3, -0.2, 0.1]), fp["theta"], 1.0, device=0,
+                          dist=dist if world > 1 else None)
+
+    def set_tausq_inv(t):
+        m.tausq_inv = _f64(t).copy()
+        m._check(m.lib.st_set_tausq_inv(m.h, _dp(m.tausq_inv)))
+
+    set_tausq_inv(f["tausq_inv_ok"])
+    res = {}
+    assert m.get_loglik_comps_w(0)
+    res["ll_A"] = m.loglik_w[0]
+    m.theta_update(1, f["theta_bad"])
+    assert m.get_loglik_comps_w(1) is False
+    res["a_code"] = m.last_errtype
+    m.theta_update(1, f["theta2"])
+    assert m.get_loglik_comps_w(1)
+    res["ll_A2"] = m.loglik_w[1]
+    m.deal_with_w(f["zs"][0])
+    res["w_0"] = m.get_w().copy()
+    for form in ("gather", "allreduce", "fused"):
+        m.use_allreduce_w = form == "allreduce"
+        set_tausq_inv(f["tausq_inv_bad"])
+        m.set_w(f["w"])
+        try:
+            if form == "fused":
+                m.deal_with_w_loglik(0, f["zs"][1])
+            else:
+                m.deal_with_w(f["zs"][1])
+            res[f"s_code_{form}"] = -1
+        except SpamTreeError:
+            res[f"s_code_{form}"] = m.last_sample_errtype
+        set_tausq_inv(f["tausq_inv_ok"])
+        m.set_w(f["w"])
+        res[f"ll_{form}"] = m.deal_with_w_loglik(0, f["zs"][2])
+        res[f"w_{form}"] = m.get_w().copy()
+    m.accept_make_change()
+    m.deal_with_w(f["zs"][1])
+    res["w_accepted"] = m.get_w().copy()
+    np.savez(os.path.join(out_dir, f"fail_{world}_{rank}.npz"), level=level, **res)
+    m.close()
+
+
+def gpu_worker(rank, world, port, side, q, out_dir, steps, limited=False, failure=None):
+    """Needs a GPU: `world` processes share device 0 and one problem; results go to out_dir for the parent to compare.
+    failure: the make_problem keywords of a failure case (_failure_case), run in place of the protocol below."""
     dist = _init(rank, world, port)
+    if failure is not None:
+        _failure_case(rank, world, dist, failure, out_dir)
+        dist.destroy_process_group()
+        return
     from spamtree_amd.sharded import ShardedSpamTreeMV
     from spamtree_amd.synthetic import make_workload
     wl = make_workload(side, q=q, limited_tree=limited)

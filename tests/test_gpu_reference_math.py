@@ -16,7 +16,7 @@ import pytest
 
 from tests.test_gpu_parity import hip_model, relerr
 from tests.test_oracle_identities import dense_cov, dense_precision
-from tests.util import default_bounds, make_problem, nice_theta, oracle_model
+from tests.util import level_failure_problem, make_problem, nice_theta, oracle_model
 
 pytestmark = pytest.mark.gpu
 
@@ -186,22 +186,14 @@ def test_hip_block_draw_is_exact_full_conditional(last_not_reference):
 # ---------------------------------------------------------------------------------------------------------------------
 def _relabelled_problem(level_from_bottom, side=16, n_relabel=12):
     """A univariate tree whose rows on ONE level (counted from the deepest observed level) are relabelled as a second
-    outcome.  With a negative Dmat entry (outside the reference's bounds, but finite) the Apanasovich-Genton cross-covariance
-    between the two outcomes exceeds what a valid model allows, so exactly that level's conditional variances go negative."""
+    outcome (tests/util.level_failure_problem), at the theta with a negative Dmat entry (outside the reference's bounds, but
+    finite): the Apanasovich-Genton cross-covariance between the two outcomes exceeds what a valid model allows, so exactly
+    that level's conditional variances go negative.  Returns the problem and the level's index."""
     pb = make_problem(side=side, q=1, seed=3)
-    labels = np.unique(pb["block_groups"])
-    lev = labels[labels.size - 1 - level_from_bottom]
-    rows = np.concatenate([pb["indexing"][u] for u in range(len(pb["indexing"])) if pb["block_groups"][u] == lev])
-    pick = np.random.default_rng(0).choice(rows, n_relabel, replace=False)
-    mv = pb["mv_id"].copy()
-    mv[pick] = 2
-    Z = np.zeros((pb["n"], 2))
-    Z[np.arange(pb["n"]), mv - 1] = 1.0
-    pb.update(mv_id=mv, Z=Z, q=2, bounds=default_bounds(2))
-    th = nice_theta(2).copy()
-    th[-1] = -0.9
-    pb["theta"] = th
-    return pb, int(np.nonzero(labels == lev)[0][0])
+    level = np.unique(pb["block_groups"]).size - 1 - level_from_bottom
+    pb, fail = level_failure_problem(pb, level, n_relabel=n_relabel)
+    pb["theta"] = fail["theta_bad"]
+    return pb, level
 
 
 @pytest.mark.parametrize("level_from_bottom,code", [(1, 2), (0, 3)])

@@ -73,3 +73,31 @@ def test_limited_tree_sharded_equals_single_process_bitwise(side, q, quad_min, t
             for k in ["ll_A", "ll_A2", "err", "ll_C0", "ll_C1"]:
                 assert float(r[k]) == float(ref[k]), (world, rank, k)
             assert np.array_equal(r["w"], ref["w"]) and np.array_equal(r["xty"], ref["xty"]) and np.array_equal(r["ssq"], ref["ssq"])
+
+
+def test_a_failure_in_one_ranks_subtree_reaches_every_rank(tmp_path, monkeypatch):
+    """The rows that make phase A (errtype 3) and the sweep (11) fail all lie in subtrees the second of two ranks owns
+    (tests/_sharded_worker.failure_problem, from st_shard_plan): the other rank's kernels see nothing wrong, and the word
+    reaches it through k_pack_comps / st_mg_finish and through the all-gather, the all-reduce and the fused form of the
+    exchange of w.  Both ranks report the oracle's codes, which are the single process's, and recover to the single
+    process's state bit for bit."""
+    import torch.multiprocessing as mp
+    from tests._sharded_worker import FAILURE_CASE as case, failure_problem_on_oracle, gpu_worker
+    monkeypatch.setenv("SPAMTREE_QUAD_MIN", "1")
+    (_, _, _, level, _), w_oracle, na = failure_problem_on_oracle(case)      # (also in tests/test_failure_constructions_cpu.py)
+    a_code = 3
+    for world in (1, 2):
+        mp.spawn(gpu_worker, args=(world, free_port(), 0, 1, str(tmp_path), 0, False, case), nprocs=world, join=True)
+    ref = np.load(tmp_path / "fail_1_0.npz")
+    assert np.abs(ref["w_gather"][na] - w_oracle[na]).max() <= 1e-9 * np.abs(w_oracle[na]).max()
+    for rank in (0, 1):
+        r = np.load(tmp_path / f"fail_2_{rank}.npz")
+        print(f"two ranks, rank {rank}: level {level}  phase A code {int(r['a_code'])}  sweep codes "
+              f"{[int(r['s_code_' + k]) for k in ('gather', 'allreduce', 'fused')]}")
+        assert int(ref["a_code"]) == a_code and int(r["a_code"]) == a_code
+        for form in ("gather", "allreduce", "fused"):
+            assert int(ref[f"s_code_{form}"]) == 11 and int(r[f"s_code_{form}"]) == 11, (rank, form)
+            assert np.array_equal(r[f"w_{form}"], ref["w_gather"]) and float(r[f"ll_{form}"]) == float(ref["ll_gather"]), (rank, form)
+        for k in ("ll_A", "ll_A2"):
+            assert float(r[k]) == float(ref[k]), (rank, k)
+        assert np.array_equal(r["w_0"], ref["w_0"]) and np.array_equal(r["w_accepted"], ref["w_accepted"])

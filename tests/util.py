@@ -1,4 +1,4 @@
-"""Shared synthetic-problem builder for the tests (inputs only; no oracle or product logic here)."""
+"""Shared synthetic-problem builders for the tests (inputs only; no product logic here), and what reads the oracle's state for them."""
 import numpy as np
 
 from spamtree_amd.topology import grid_coords, prepare
@@ -132,6 +132,88 @@ def per_outcome(om, Bcoeff=None, tausq=None):
         om.tausq_inv = 1.0 / np.asarray(tausq, dtype=np.float64)
         for j in range(om.q):
             om.tausq_inv_long[om.ix_by_q[j]] = om.tausq_inv[j]
+
+
+def level_failure_problem(pb, level, n_relabel=12, seed=0, blocks=None):
+    """A copy of `pb` (q <= 5 outcomes) in which some observed rows of ONE level (index into the sorted level labels, as
+    the oracle's groups and st_level_info count them; a sequence: of each of these levels) are relabelled as outcome q + 1,
+    with Z, the bounds and theta extended.  Nothing else changes: the tree, the block widths and the chain lengths are those
+    of `pb`.  `blocks`: take the rows from these blocks of the level only (a multi-rank test keeps them inside one rank's
+    subtrees).  Returns
+    (problem, fail), the problem with theta = nice_theta(q + 1), and fail =
+      theta_bad     the same theta with the Dmat entries towards the new outcome negative (finite, outside the bounds): the
+                    cross-covariance between the new outcome and the others is inflated about tenfold, so exactly the
+                    conditional variances of that level's relabelled rows go negative, while shallower levels hold no row of
+                    the new outcome and see the same covariances as before;
+      tausq_inv_ok / tausq_inv_bad   per-outcome tausq^-1; the bad one is negative for the new outcome only, so only that
+                    level's posterior precisions are indefinite;
+      levels, rows  the levels and the relabelled rows."""
+    from oracle.spamtree_oracle import vec_to_symmat
+    q = int(pb["q"])
+    assert q <= 5
+    labels = np.unique(pb["block_groups"])
+    levels = [int(level)] if np.ndim(level) == 0 else [int(g) for g in level]
+    rng = np.random.default_rng(seed)
+    pick = []
+    for g in levels:
+        in_level = [u for u in range(len(pb["indexing"])) if pb["block_groups"][u] == labels[g]]
+        if blocks is not None:
+            assert set(blocks) <= set(in_level)
+            in_level = list(blocks)
+        rows = np.concatenate([pb["indexing"][u] for u in in_level])
+        rows = rows[np.isfinite(pb["y"][rows])]
+        pick.append(rng.choice(rows, min(n_relabel, rows.size), replace=False))
+    pick = np.sort(np.concatenate(pick))
+    mv = np.asarray(pb["mv_id"]).copy()
+    mv[pick] = q + 1
+    Z = np.zeros((pb["n"], q + 1))
+    Z[np.arange(pb["n"]), mv - 1] = 1.0
+    good = nice_theta(q + 1)
+    npars, n_cbase, k = theta_layout(q + 1)
+    to_new = vec_to_symmat(np.arange(1.0, k + 1))[q, :q].astype(np.int64) - 1     # positions of Dmat[q, 0..q-1] in the vector
+    bad = good.copy()
+    # q + 1 = 2: psi = v + 1; q + 1 > 2: psi = (1 + a v)^beta with a = thetamv[0].  1 + a v = 0.1 in both
+    bad[npars + to_new] = -0.9 if q + 1 == 2 else -0.9 / good[3 * (q + 1)]
+    ok_t = np.full(q + 1, 5.0)
+    bad_t = ok_t.copy()
+    bad_t[q] = -1e6
+    out = dict(pb, mv_id=mv, Z=Z, q=q + 1, bounds=default_bounds(q + 1), theta=good)
+    return out, dict(theta_bad=bad, tausq_inv_ok=ok_t, tausq_inv_bad=bad_t, levels=levels, rows=pick)
+
+
+def oracle_phase_a_failure(om, data):
+    """Runs the oracle's phase A on `data` and returns (errtype, level): the oracle returns after the first level with an
+    error, so the failing level is the deepest one whose blocks it visited -- read from its per-block log-density
+    components, cleared beforehand.  (-1, None) where it succeeds."""
+    data.loglik_w_comps[:] = 0.0
+    with np.errstate(all="ignore"):
+        if om.get_loglik_comps_w(data):
+            return -1, None
+    seen = [g for g, us in enumerate(om.u_by_block_groups) if any(data.loglik_w_comps[u] != 0.0 for u in us)]
+    return om.last_errtype, max(seen)
+
+
+def oracle_sweep_failing_levels(om):
+    """The levels holding a block whose posterior precision, rebuilt from the oracle's per-block caches and its current
+    tausq^-1, is not positive definite: where a sweep fails."""
+    groups = om.u_by_block_groups
+    pd = om.param_data
+    bad = []
+    for g, us in enumerate(groups):
+        for u in us:
+            iu = om.indexing[u]
+            if om.res_is_ref[g] == 1:
+                S = pd.w_cond_prec[u].copy()
+                if om.children[u].size:
+                    S += np.sum(pd.Sigi_children[u], axis=2)
+                S[np.diag_indices_from(S)] += om.tausq_inv_long[iu]
+                ok = np.all(np.isfinite(S)) and np.linalg.eigvalsh(np.triu(S) + np.triu(S, 1).T).min() > 0
+            else:
+                ok = all(pd.w_cond_prec_noref[u][ix][0, 0] + om.tausq_inv_long[iu[ix]] > 0 for ix in range(iu.size))
+            if not ok:
+                bad.append(g)
+                break
+    return bad
 
 
 def strip_coords(nx, ny, q, width=0.02):
