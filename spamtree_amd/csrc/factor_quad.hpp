@@ -30,7 +30,8 @@ struct QuadArgs {
   const Blk *blks;
   const int *anc_idx;
   const Grp *grps;
-  const Quad *quads;
+  const long long *qrec;   // the launch's quad records (QuadRec), one per workgroup: record i at qrec + i * qrec_stride
+  int qrec_stride;         // ... 8-byte words (sizeof(QuadRec) / 8 of the launched instantiation)
   int nquad;
   const double *cx, *cy;
   const int *mv;
@@ -38,8 +39,6 @@ struct QuadArgs {
   double *panels;
   double *logdet_c, *loglik_c;
   int *errflag;
-  const long long *gdesc;   // group descriptors of the level's first group onwards (Quad::g0 is relative to it)
-  int gd_stride;
   int ldS;   // staged row stride: >= longest row + 24 zero-filled columns
   int wave_chol;   // the level's blocks have <= 27 rows: one-wave register elimination (a property of the LEVEL, so that a
                    // unit's arithmetic does not depend on which units share its workgroup)
@@ -67,6 +66,44 @@ struct QuadArgs {
 // which a launch executes one.
 enum { QM_FULL = 0, QM_VONLY = 1, QM_TFROMV = 2 };
 __host__ __device__ constexpr int quad_vtiles(int nkx) { return 2 + 2 * ((4 * nkx + 31) / 32); }
+
+// The quad record: everything a workgroup's prologue used to derive from Quad, the units' group descriptors and the
+// coordinate arrays -- a function of the tree and the coordinates, fixed for the life of a handle -- laid out on the host
+// (tree_layout.cpp, build_quad_records) exactly as the kernel keeps it in LDS.  The workgroup of launch position i copies
+// record i into this image with one round of LDS-DMA and takes one barrier.  Only w changes from call to call: the
+// slots wpa / colw / pw of a record hold the GLOBAL ROW of their entry (a long long in the double's bits, -1: no entry),
+// the kernel replaces them by w of that row.  Entries a quad does not have (units >= nu, columns >= M, private rows >=
+// pm, blocks >= nblk, chain rows >= Pc) are zero.  Every member's size is a multiple of 16 bytes (the DMA's piece).
+template <int NU, int PMAX, bool ISREF>
+struct alignas(16) QuadRec {
+  // leaf-only arrays: one 16-byte piece each in a reference quad's record (never read there)
+  static constexpr int NB = ISREF ? 1 : 32, NUL = ISREF ? 1 : NU, NLD = ISREF ? 2 : 32, NLI = ISREF ? 4 : 32;
+  int g0, nu, Jc, Pc;       // Quad
+  int level, nit, pad[2];   // tree level of unit 0; steps of 32 chain rows over the shared chain
+  int uM[NU], uP[NU], ublk0[NU], unblk[NU], uref[NU], uJ[NU], pm[NU], fail[NU];   // per unit (pm: rows of its private ancestor; fail: 0)
+  long long urow0[NU], prow[NU], ppan[NU];
+  long long bpan[NU][NB], brow[NU][NB];   // per unit and block: panel offset, first row, row stride
+  int bld[NU][NB];
+  double colx[NU][32], coly[NU][32], colw[NU][32];   // the units' columns
+  int colmv[NU][32], colblk[NUL][NLI];               // colblk: the block of the unit that owns the column
+  double px[NUL][NLD], py[NUL][NLD], pw[NUL][NLD];   // the private ancestors' rows
+  int pmv[NUL][NLI];
+  double sx[PMAX], sy[PMAX], wpa[PMAX];              // the shared chain's rows
+  int smv[PMAX];
+  int rlen[PMAX];          // chain row c: its length (entries up to and including its own ancestor's rows) ...
+  long long rsrc[PMAX];    // ... and where it starts in the panel arena
+};
+static_assert(sizeof(QuadRec<4, 128, true>) % 16 == 0 && sizeof(QuadRec<4, 152, false>) % 16 == 0 && sizeof(QuadRec<4, 176, true>) % 16 == 0 &&
+              sizeof(QuadRec<4, 200, false>) % 16 == 0, "a record is a whole number of 16-byte DMA pieces");
+// 8-byte words of the record of k_factor_quad<4, nkx, ., isref, .>
+inline int quad_rec_words(int nkx, bool isref) {
+  switch (nkx) {
+    case 32: return (int)((isref ? sizeof(QuadRec<4, 128, true>) : sizeof(QuadRec<4, 128, false>)) / 8);
+    case 38: return (int)((isref ? sizeof(QuadRec<4, 152, true>) : sizeof(QuadRec<4, 152, false>)) / 8);
+    case 44: return (int)((isref ? sizeof(QuadRec<4, 176, true>) : sizeof(QuadRec<4, 176, false>)) / 8);
+    default: return (int)((isref ? sizeof(QuadRec<4, 200, true>) : sizeof(QuadRec<4, 200, false>)) / 8);
+  }
+}
 
 #define RFL(x) __builtin_amdgcn_readfirstlane(x)
 
@@ -106,27 +143,25 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
   constexpr int PMAX = 4 * NKX, KH = ISREF ? (NKX + 3) / 4 : QUAD_LEAF_KH, NPASS = (NKX + KH - 1) / KH;
   static_assert(NKT * 16 >= PMAX, "T tiles must cover the chain");
   extern __shared__ double lds[];
-  __shared__ int s_am[MAXJ], s_ao[MAXJ + 1];
-  __shared__ long long s_arow[MAXJ], s_apan[MAXJ];
-  __shared__ int s_uM[NU], s_uP[NU], s_ublk0[NU], s_unblk[NU], s_uref[NU], s_uJ[NU], s_pm[NU], s_fail[NU], s_level;
-  __shared__ long long s_urow0[NU], s_prow[NU], s_ppan[NU];
   constexpr int NB = ISREF ? 1 : 32, NUL = ISREF ? 1 : NU;   // leaf-only arrays
-  __shared__ long long s_bpan[NU][NB], s_brow[NU][NB];
-  __shared__ int s_bld[NU][NB];
-  __shared__ double s_colx[NU][32], s_coly[NU][32], s_colw[NU][32], s_hv[NU][32];
-  __shared__ double s_px[NUL][32], s_py[NUL][32], s_pw[NUL][32];
+  typedef QuadRec<NU, PMAX, ISREF> Rec;
+  static_assert(PMAX <= NTQ / 2 && NU * 32 * 2 <= NTQ / 2, "one parked w per thread: chain | columns | private rows");
+  __shared__ Rec s_q;   // the quad's record, as the host laid it out (w in the slots wpa / colw / pw once it has been gathered)
+  auto &s_uM = s_q.uM; auto &s_uP = s_q.uP; auto &s_ublk0 = s_q.ublk0; auto &s_unblk = s_q.unblk; auto &s_uJ = s_q.uJ;
+  auto &s_pm = s_q.pm; auto &s_fail = s_q.fail; auto &s_level = s_q.level; auto &s_nit = s_q.nit;
+  auto &s_urow0 = s_q.urow0; auto &s_ppan = s_q.ppan;
+  auto &s_bpan = s_q.bpan; auto &s_brow = s_q.brow; auto &s_bld = s_q.bld;
+  auto &s_colx = s_q.colx; auto &s_coly = s_q.coly; auto &s_colw = s_q.colw; auto &s_colmv = s_q.colmv; auto &s_colblk = s_q.colblk;
+  auto &s_px = s_q.px; auto &s_py = s_q.py; auto &s_pw = s_q.pw; auto &s_pmv = s_q.pmv;
+  auto &s_sx = s_q.sx; auto &s_sy = s_q.sy; auto &s_wpa = s_q.wpa; auto &s_smv = s_q.smv;
+  auto &s_rlen = s_q.rlen; auto &s_rsrc = s_q.rsrc;
+  __shared__ double s_hv[NU][32];
   __shared__ double s_e2[NU][32], s_lg[NU][32];
-  __shared__ int s_colmv[NU][32], s_colblk[NUL][32], s_pmv[NUL][32];
-  __shared__ int s_nit;   // steps of 32 chain rows over the shared chain
-  __shared__ double s_sx[PMAX], s_sy[PMAX], s_wpa[PMAX];
-  __shared__ int s_smv[PMAX];
   __shared__ double s_exp2[64];         // 2^(j/64): cov_exp_tab
   // multivariate covariance: the per-outcome-pair constants (rate, amp, amp2 of every pair, phi of every outcome).  Indexed per
   // lane out of the kernel arguments they are GLOBAL loads -- three or four dependent round trips per entry; the covariance
   // pass was 21-24 % of a quad's life at config #5 (stamps) -- so they live in LDS
   __shared__ double s_cvr[QMAX * QMAX], s_cva[QMAX * QMAX], s_cva2[QMAX * QMAX], s_cvp[QMAX];
-  __shared__ int s_rlen[PMAX];          // chain row c: its length (entries up to and including its own ancestor's rows) ...
-  __shared__ long long s_rsrc[PMAX];    // ... and where it starts in the panel arena
   // leaf units: g = Linv_pa w_pa, one entry per staged chain row, for the residual r_j (w_j - V_j' g).  Overlays: s_e2 is
   // written after the main loop only, s_hv is a reference-level array (and phase P's, also after the main loop)
   double (*s_g)[32] = s_e2;    // [step buffer][row of the step]
@@ -149,16 +184,17 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
     const int per = A.nquad >> 3;   // one contiguous run of quads per XCD (private L2): neighbours share chain panels
     if (qidx < per * 8) qidx = (qidx & 7) * per + (qidx >> 3);
   }
-  const Quad Q = A.quads[qidx];
-  const int Jc = Q.Jc, Pc = Q.Pc, nu = Q.nu;
-
-  // ---- topology of the quad: the units' group descriptors (layout: GdHead) land in the arena, which is free until the
-  // covariance pass -- one round trip instead of the grps -> blks -> anc_idx -> blks chain
-  long long *gdl = (long long *)arena;   // [nu][gd_stride]
-  const int gds = A.gd_stride;
-  for (int e = tid; e < nu * gds; e += NTQ) {
-    const int uu = e / gds, i = e - uu * gds;
-    gdl[e] = A.gdesc[(size_t)(Q.g0 + uu) * gds + i];
+  // ---- the quad's record: one round of LDS-DMA (16 bytes per lane, 1 KiB per wave-instruction) straight into s_q, one wait,
+  // one barrier -- the only global round trip before the covariance pass
+  {
+    constexpr int NPIECE = (int)(sizeof(Rec) / 16);
+    const char *rec = (const char *)(A.qrec + (size_t)qidx * A.qrec_stride);
+    char *img = (char *)&s_q;
+#pragma unroll
+    for (int p0 = 0; p0 < NPIECE; p0 += 64 * NW) {
+      const int pw0 = p0 + 64 * wid;   // (wave-uniform: the DMA's LDS base)
+      if (pw0 + lane < NPIECE) __builtin_amdgcn_global_load_lds((q_glb_void *)(rec + (size_t)(pw0 + lane) * 16), (q_lds_void *)(img + (size_t)pw0 * 16), 16, 0, 0);
+    }
   }
   for (int k = tid; k < ldS; k += NTQ) zrow[k] = 0.0;
   if (tid < 64) s_exp2[tid] = EXP2_64[tid];
@@ -167,47 +203,9 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
     s_cvr[e] = cp.rate[e]; s_cva[e] = cp.amp[e]; s_cva2[e] = cp.amp2[e];
     if (e < QMAX) s_cvp[e] = cp.phi[e];
   }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (tid < NU) {
-    int M = 0, P = 0, blk0 = 0, nblk = 0, isref = 0, J = 0, pm = 0;
-    long long row0 = 0, prow = 0, ppan = 0;
-    if (tid < nu) {
-      const long long *g = gdl + (size_t)tid * gds;
-      row0 = g[0];
-      M = (int)(g[2] & 0xffffffffLL); P = (int)(g[2] >> 32);
-      J = (int)(g[3] & 0xffffffffLL); nblk = (int)(g[3] >> 32);
-      isref = (int)(g[4] & 0xffffffffLL);
-      blk0 = (int)(g[6] & 0xffffffffLL);
-      if (tid == 0) s_level = (int)(g[4] >> 32);
-      if (J > Jc) {   // the private (last) ancestor
-        const long long *a = g + 8 + 4 * Jc;
-        pm = (int)(a[0] & 0xffffffffLL); prow = a[1]; ppan = a[2];
-      }
-    }
-    s_uM[tid] = M; s_uP[tid] = P; s_ublk0[tid] = blk0; s_unblk[tid] = nblk; s_uref[tid] = isref; s_uJ[tid] = J;
-    s_pm[tid] = pm; s_urow0[tid] = row0; s_prow[tid] = prow; s_ppan[tid] = ppan; s_fail[tid] = 0;
-  }
-  if (tid >= 64 && tid < 64 + Jc) {   // the shared chain: the first Jc ancestors of unit 0
-    const int t = tid - 64;
-    const long long *a = gdl + 8 + 4 * t;
-    s_am[t] = (int)(a[0] & 0xffffffffLL); s_ao[t] = (int)(a[0] >> 32); s_arow[t] = a[1]; s_apan[t] = a[2];
-  }
-  if (tid == 32) {
-    s_ao[Jc] = Pc;
-    s_nit = (Pc + 31) >> 5;
-  }
-  for (int e = tid; e < NU * NB; e += NTQ) {
-    const int uu = e / NB, b = e - uu * NB;
-    if (uu < nu) {
-      const long long *g = gdl + (size_t)uu * gds;
-      const int J = (int)(g[3] & 0xffffffffLL), nblk = (int)(g[3] >> 32);
-      if (b < nblk) {
-        const long long *q = g + 8 + 4 * J + 3 * b;
-        s_bpan[uu][b] = q[0]; s_brow[uu][b] = q[1]; s_bld[uu][b] = (int)q[2];
-      }
-    }
-  }
-  __syncthreads();
+  const int Pc = RFL(s_q.Pc);
   const int Mu = RFL(s_uM[u]), Pu = RFL(s_uP[u]), pmu = RFL(s_pm[u]);
   constexpr bool isref = ISREF;   // a level is all reference blocks or all leaf groups (host)
   const bool wact = jt * 16 < Mu;   // this wave owns at least one column
@@ -218,35 +216,25 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
   Mmax = RFL(Mmax); pmmax = RFL(pmmax);
   constexpr bool anyref = ISREF;
 
-  // ---- coordinates and w of the shared chain, of the private ancestors, of the units' columns
-  for (int k = tid; k < Pc; k += NTQ) {
-    int t = 0;   // the ancestor of chain row k: independent compares (a search loop is a chain of dependent LDS reads)
-#pragma unroll
-    for (int j = 1; j < 8; ++j) t += (j < Jc && k >= s_ao[j]) ? 1 : 0;
-    for (int j = 8; j < Jc; ++j) t += (k >= s_ao[j]) ? 1 : 0;
-    const long long r = s_arow[t] + (k - s_ao[t]);
-    s_sx[k] = A.cx[r]; s_sy[k] = A.cy[r]; s_smv[k] = A.mv[r]; s_wpa[k] = A.w[r];
-    const int len = s_ao[t + 1];
-    s_rlen[k] = len; s_rsrc[k] = s_apan[t] + (long long)(k - s_ao[t]) * len;
-  }
-  for (int e = tid; e < NU * 32; e += NTQ) {
-    const int uu = e >> 5, i = e & 31;
-    double x = 0.0, y = 0.0, ww = 0.0; int v = 0;
-    if constexpr (!ISREF) {
-      if (i < s_pm[uu]) { const long long r = s_prow[uu] + i; x = A.cx[r]; y = A.cy[r]; ww = A.w[r]; v = A.mv[r]; }
-      s_px[uu][i] = x; s_py[uu][i] = y; s_pw[uu][i] = ww; s_pmv[uu][i] = v;
-      x = 0.0; y = 0.0; ww = 0.0; v = 0;
+  // ---- w of the shared chain (threads [0, Pc)), of the units' columns ([NTQ/2, NTQ/2 + 32 NU)) and of the private
+  // ancestors' rows (the last 32 NU threads): requested here, ahead of the first panel rows, from the rows the record names;
+  // the values stay in a register over the covariance pass and go to their slots behind it (nothing reads them before).
+  // QM_TFROMV reads no w.
+  double wpark = 0.0;
+  constexpr int o_wpa = (int)(offsetof(Rec, wpa) / 8), o_colw = (int)(offsetof(Rec, colw) / 8), o_pw = (int)(offsetof(Rec, pw) / 8);
+  auto wslot = [&]() __attribute__((always_inline)) {   // this thread's slot (a double's index in s_q), -1: none
+    if (tid < Pc) return o_wpa + tid;
+    if (tid >= NTQ / 2 && tid < NTQ / 2 + 32 * NU) return o_colw + (tid - NTQ / 2);
+    if (!ISREF && tid >= NTQ / 2 + 32 * NU) return o_pw + (tid - (NTQ / 2 + 32 * NU));
+    return -1;
+  };
+  if (QM != QM_TFROMV) {
+    const int ws = wslot();
+    if (ws >= 0) {
+      const long long r = __double_as_longlong(((const double *)&s_q)[ws]);
+      if (r >= 0) wpark = A.w[r];
     }
-    int bi = 0;
-    if (i < s_uM[uu]) {
-      const long long r = s_urow0[uu] + i;
-      x = A.cx[r]; y = A.cy[r]; ww = A.w[r]; v = A.mv[r];
-      if constexpr (!ISREF) { while (bi + 1 < s_unblk[uu] && r >= s_brow[uu][bi + 1]) ++bi; }
-    }
-    s_colx[uu][i] = x; s_coly[uu][i] = y; s_colw[uu][i] = ww; s_colmv[uu][i] = v;
-    if constexpr (!ISREF) s_colblk[uu][i] = bi;
   }
-  __syncthreads();
 
   STAMP(0);
   const int p_sr0 = pmu > 16 ? (pmu + 1) >> 1 : pmu;   // rows of the first private sub-panel
@@ -352,6 +340,13 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
   }
   // no barrier here: the scratch slots are lane-private, and the first DMA into their region (reference quads: step 1 into
   // the second buffer) is requested after the first barrier below
+  // the parked w to its slot (no entry: 0).  Leaf quads read the slots in the first staged step already (grow, by other
+  // threads than wrote them): one barrier; reference quads read them behind the main loop's barriers
+  if (QM != QM_TFROMV) {
+    const int ws = wslot();
+    if (ws >= 0) ((double *)&s_q)[ws] = wpark;
+    if constexpr (!ISREF) lds_barrier();
+  }
   STAMP(1);
   d4 tacc[NKT];
 #pragma unroll
@@ -505,10 +500,18 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
   }
 
   STAMP(2);
+  // Team-elimination instantiations (256 registers): the T accumulators pass through an empty asm before and behind the main
+  // loop.  No instruction; it ends their live ranges there, so that what the epilogue's elimination cannot keep in registers
+  // is spilled BEHIND the loop -- as one range the allocator kept two T tiles in scratch through the loop (a reload and a
+  // store per tile and step, each waiting on vmcnt, i.e. on the next step's LDS-DMA too)
+  if constexpr (ISREF && !WCH) {
+#pragma unroll
+    for (int n = 0; n < NKT; ++n) asm volatile("" : "+v"(tacc[n]));
+  }
   // ---- the shared chain, last rows first, 32 rows of the concatenated chain per step (two 16-row MFMA tiles; the step
   // that holds the chain's last rows may be shorter).  Rows travel from global memory straight into one of two LDS
   // buffers (LDS-DMA, no registers): the next step is requested when the matrix cores start on the current one; one
-  // LDS-only barrier per step.  Row c of the chain belongs to ancestor t (s_ao[t] <= c < s_ao[t+1]) and has s_ao[t+1]
+  // LDS-only barrier per step.  Row c of the chain belongs to ancestor t (ao[t] <= c < ao[t+1]) and has ao[t+1] = s_rlen[c]
   // entries; a step's row length Kb is that of its last row, shorter rows are zero-filled up to Kb + 24.
   {
     if constexpr (!ISREF) { if (nit > 0 && !pf) issue(0, arena); }   // (reference quads: requested before the covariance pass)
@@ -560,6 +563,10 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
     }
   }
   lds_barrier();
+  if constexpr (ISREF && !WCH) {   // (see before the loop)
+#pragma unroll
+    for (int n = 0; n < NKT; ++n) asm volatile("" : "+v"(tacc[n]));
+  }
 
   // ---- hv = T w_pa for this wave's columns (tile rows l4 + 4 r), summed over the 16 chain columns of a tile row: reference
   // units and phase P (the leaf units' log-density takes V' g instead: hacc)

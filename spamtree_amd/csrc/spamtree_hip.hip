@@ -97,7 +97,7 @@ struct st_handle_s : TreeLayout {
   int quirks = 1;
   long long n_obs = 0;
   DevBuf<Grp> d_grps;                         // the device copies of the layout's lists (tree_layout.hpp)
-  DevBuf<Quad> d_quads;
+  DevBuf<long long> d_qrec;                   // the quad records (TreeLayout::qrec): k_factor_quad's workgroups start from them
   DevBuf<WideGrp> d_wgrps;
   DevBuf<LcSlab> d_lcslabs;
   DevBuf<long long> d_rfvoff, d_gdesc;
@@ -400,7 +400,8 @@ static int create_layout_buffers(st_handle_s *h) {
   CCHK(upload_or_dummy(h->d_anc, h->anc_idx)); CCHK(upload_or_dummy(h->d_dch, h->dch_idx));
   CCHK(h->d_lvl.upload(h->lvl_list));
   CCHK(upload_or_dummy(h->d_grps, h->grps)); CCHK(h->d_gdesc.upload(h->gdesc));
-  CCHK(upload_or_dummy(h->d_quads, h->quads)); CCHK(upload_or_dummy(h->d_wgrps, h->wgrps));
+  CCHK(upload_or_dummy(h->d_qrec, h->qrec)); std::vector<long long>().swap(h->qrec);   // (qrec_bytes keeps the size)
+  CCHK(upload_or_dummy(h->d_wgrps, h->wgrps));
   if (!h->lcslabs.empty()) { CCHK(h->d_lcslabs.upload(h->lcslabs)); CCHK(h->d_lcrow.alloc((size_t)2 * h->n_all)); }
   if (!h->rfvoff.empty()) { CCHK(h->d_rfvoff.upload(h->rfvoff)); CCHK(h->d_vscr.alloc(h->vscr_need + (size_t)2 * RF_BUFD)); }   // (+ what a chunk's DMA reads past the last block)
   CCHK(h->d_s0off.upload(h->s0off));
@@ -612,10 +613,9 @@ static int complete_leaf(st_handle h, int slot) {
     QuadArgs F;
     std::memset(&F, 0, sizeof(F));
     F.blks = h->d_blks.p; F.anc_idx = h->d_anc.p; F.grps = h->d_grps.p + L.grp_first;
-    F.quads = h->d_quads.p + L.quad_first + L.qown_lo; F.nquad = L.qown_n;
+    F.qrec = L.qr_off >= 0 ? h->d_qrec.p + L.qr_off : nullptr; F.qrec_stride = L.qr_words; F.nquad = L.qown_n;
     F.cx = h->d_cx.p; F.cy = h->d_cy.p; F.mv = h->d_mv.p; F.w = h->d_w.p; F.panels = h->d_panels[phys].p;
     F.errflag = h->d_err.p; F.ldS = L.q_ldS;
-    F.gdesc = h->d_gdesc.p + (size_t)L.grp_first * h->gd_stride; F.gd_stride = h->gd_stride;
     F.wave_chol = L.maxM <= 27 ? 1 : 0;
     F.mode = QM_TFROMV; F.vscr = h->d_vleaf.p + L.vl_off; F.vtiles = quad_vtiles(L.q_nkx);
     ProfScope ps(h, 0, g, 0);
@@ -770,10 +770,9 @@ static int factor_launch(st_handle h, int phys, const CovPar &cp, int g_lo = 0, 
         QuadArgs F;
         std::memset(&F, 0, sizeof(F));
         F.blks = h->d_blks.p; F.anc_idx = h->d_anc.p; F.grps = h->d_grps.p + L.grp_first;
-        F.quads = h->d_quads.p + L.quad_first + L.qown_lo; F.nquad = L.qown_n;
+        F.qrec = L.qr_off >= 0 ? h->d_qrec.p + L.qr_off : nullptr; F.qrec_stride = L.qr_words; F.nquad = L.qown_n;
         F.cx = h->d_cx.p; F.cy = h->d_cy.p; F.mv = h->d_mv.p; F.w = h->d_w.p; F.panels = h->d_panels[phys].p;
         F.logdet_c = h->d_logdet[phys].p; F.loglik_c = h->d_loglik[phys].p; F.errflag = errflag; F.ldS = L.q_ldS;
-        F.gdesc = h->d_gdesc.p + (size_t)L.grp_first * h->gd_stride; F.gd_stride = h->gd_stride;
         F.wave_chol = L.maxM <= 27 ? 1 : 0;
 #define QLAUNCH(NU_, NKX_, NKT_, R_)   /* R_: route code of <.., true, true>; + 1: <.., true, false>; + 2: <.., false, true> */  \
   do {                                                                                                                         \
@@ -1505,10 +1504,9 @@ extern "C" int st_predict(st_handle h, int theta_changed) {
     QuadArgs F;
     std::memset(&F, 0, sizeof(F));
     F.blks = h->d_blks.p; F.anc_idx = h->d_anc.p; F.grps = h->d_grps.p + h->pred_grp_first;
-    F.quads = h->d_quads.p + h->pred_quad_first; F.nquad = h->pred_quad_count;
+    F.qrec = h->d_qrec.p + h->pred_qr_off; F.qrec_stride = h->pred_qr_words; F.nquad = h->pred_quad_count;
     F.cx = h->d_cx.p; F.cy = h->d_cy.p; F.mv = h->d_mv.p; F.w = h->d_w.p; F.panels = h->d_panels[h->slot_map[0]].p;
     F.logdet_c = nullptr; F.loglik_c = nullptr; F.errflag = h->d_err.p; F.ldS = quad_lds_stride(h->pred_nkx);
-    F.gdesc = h->d_gdesc.p + (size_t)h->pred_grp_first * h->gd_stride; F.gd_stride = h->gd_stride;
     F.wave_chol = 1; F.predict = 1; F.z = h->d_z.p; F.w_out = h->d_w.p;
     {
       ProfScope ps(h, 6);

@@ -813,6 +813,89 @@ static void demote_by_static_lds(TreeLayout &t, const DeviceLimits &dl) {
     t.vleaf_total += (size_t)L.qown_n * quad_vtiles(L.q_nkx) * (2 * t.quad_nu) * 256;
   }
 }
+// One quad's record (QuadRec, factor_quad.hpp) from the blocks and groups: the values k_factor_quad's prologue used to
+// gather -- the units' extents, the shared chain's and the private ancestors' rows with their coordinates, the units'
+// columns, the rows' places in the panel arena.  Coordinates and outcome ids are the device arrays' (create_rows): row r is
+// model row dev2model[r].  The slots wpa / colw / pw take the entry's global row (the kernel puts w there).
+template <int PMAX, bool ISREF>
+static void fill_quad_record(const st_problem *pb, const TreeLayout &t, int grp_first, const Quad &Qd, long long *out) {
+  typedef QuadRec<4, PMAX, ISREF> Rec;
+  Rec R;
+  std::memset(&R, 0, sizeof(R));
+  const long long n = t.n_all;
+  auto put = [&](long long r, double &x, double &y, int &mv, double &wslot) {
+    const long long m = t.dev2model[r];
+    x = pb->coords[m]; y = pb->coords[n + m]; mv = (int)(pb->mv_id[m] - 1);
+    std::memcpy(&wslot, &r, sizeof(double));
+  };
+  const long long none = -1;
+  for (int i = 0; i < 4 * 32; ++i) std::memcpy(&R.colw[0][0] + i, &none, sizeof(double));
+  for (int i = 0; i < Rec::NUL * Rec::NLD; ++i) std::memcpy(&R.pw[0][0] + i, &none, sizeof(double));
+  for (int k = 0; k < PMAX; ++k) std::memcpy(&R.wpa[k], &none, sizeof(double));
+  R.g0 = Qd.g0; R.nu = Qd.nu; R.Jc = Qd.Jc; R.Pc = Qd.Pc;
+  R.nit = (Qd.Pc + 31) >> 5;
+  const Blk &U0 = t.blks[t.grps[grp_first + Qd.g0].blk0];
+  R.level = U0.level;
+  int k = 0;   // the shared chain: the first Jc ancestors of unit 0, row after row
+  for (int a = 0; a < Qd.Jc; ++a) {
+    const Blk &Ba = t.blks[t.anc_idx[U0.anc_ptr + a]];
+    const int len = k + Ba.m;   // a row runs to the end of its own ancestor's rows
+    for (int i = 0; i < Ba.m && k < PMAX; ++i, ++k) {
+      put(Ba.row0 + i, R.sx[k], R.sy[k], R.smv[k], R.wpa[k]);
+      R.rlen[k] = len; R.rsrc[k] = Ba.chain_off + (long long)i * len;
+    }
+  }
+  for (int u = 0; u < Qd.nu; ++u) {
+    const Grp &G = t.grps[grp_first + Qd.g0 + u];
+    const Blk &B0 = t.blks[G.blk0];
+    R.uM[u] = G.M; R.uP[u] = G.P; R.ublk0[u] = G.blk0; R.unblk[u] = G.nblk; R.uref[u] = B0.isref; R.uJ[u] = B0.nanc; R.urow0[u] = G.row0;
+    if (B0.nanc > Qd.Jc) {   // the private (last) ancestor
+      const Blk &Bp = t.blks[t.anc_idx[B0.anc_ptr + Qd.Jc]];
+      R.pm[u] = Bp.m; R.prow[u] = Bp.row0; R.ppan[u] = Bp.chain_off;
+      if constexpr (!ISREF) for (int i = 0; i < Bp.m && i < 32; ++i) put(Bp.row0 + i, R.px[u][i], R.py[u][i], R.pmv[u][i], R.pw[u][i]);
+    }
+    for (int b = 0; b < G.nblk && b < Rec::NB; ++b) {
+      const Blk &Bb = t.blks[G.blk0 + b];
+      R.bpan[u][b] = Bb.panel_off; R.brow[u][b] = Bb.row0; R.bld[u][b] = Bb.ld;
+    }
+    int bi = 0;
+    for (int i = 0; i < G.M && i < 32; ++i) {
+      put(G.row0 + i, R.colx[u][i], R.coly[u][i], R.colmv[u][i], R.colw[u][i]);
+      if constexpr (!ISREF) {
+        while (bi + 1 < G.nblk && G.row0 + i >= t.blks[G.blk0 + bi + 1].row0) ++bi;
+        R.colblk[u][i] = bi;
+      }
+    }
+  }
+  std::memcpy(out, &R, sizeof(R));
+}
+// the records of `count` quads from quads[qfirst] on (their groups from grp_first on), appended to qrec; returns their offset
+static long long append_quad_records(const st_problem *pb, TreeLayout &t, int grp_first, int qfirst, int count, int nkx, bool isref, int &words) {
+  words = quad_rec_words(nkx, isref);
+  const long long off = (long long)t.qrec.size();
+  t.qrec.resize(t.qrec.size() + (size_t)count * words);
+  for (int k = 0; k < count; ++k) {
+    long long *out = t.qrec.data() + off + (size_t)k * words;
+    const Quad &Qd = t.quads[qfirst + k];
+#define QR(P_) (isref ? fill_quad_record<P_, true>(pb, t, grp_first, Qd, out) : fill_quad_record<P_, false>(pb, t, grp_first, Qd, out))
+    if (nkx == 32) QR(128); else if (nkx == 38) QR(152); else if (nkx == 44) QR(176); else QR(200);
+#undef QR
+  }
+  return off;
+}
+// Quad records of every level that takes k_factor_quad (this rank's run of its quads: a launch's workgroup i starts from
+// record i) and of the prediction quads.  After demote_by_static_lds: q_nkx / pred_nkx are final.
+static void build_quad_records(const st_problem *pb, TreeLayout &t) {
+  t.qrec.clear(); t.pred_qr_off = -1; t.pred_qr_words = 0;
+  for (auto &L : t.levels) {
+    L.qr_off = -1; L.qr_words = 0;
+    if (t.sw.factor_gen != 3 || !L.fast || L.q_nkx == 0 || L.qown_n == 0) continue;
+    L.qr_off = append_quad_records(pb, t, L.grp_first, L.quad_first + L.qown_lo, L.qown_n, L.q_nkx, L.isref != 0, L.qr_words);
+  }
+  if (t.pred_nkx && t.pred_quad_count > 0)
+    t.pred_qr_off = append_quad_records(pb, t, t.pred_grp_first, t.pred_quad_first, t.pred_quad_count, t.pred_nkx, false, t.pred_qr_words);
+  t.qrec_bytes = t.qrec.size() * sizeof(long long);
+}
 // top levels that st_factor_begin may run ahead: the leading levels on k_factor_mfma (no global scratch), when every
 // level of the tree is on the column-group path (the generic kernels share one scratch arena between phases)
 static void choose_top_levels(TreeLayout &t) {
@@ -859,6 +942,7 @@ int layout_levels(const st_problem *pb, const Switches &sw, const DeviceLimits &
   choose_gram_direct(t, blk2grp);
   size_buffers(t);
   demote_by_static_lds(t, dl);
+  build_quad_records(pb, t);
   choose_top_levels(t);
   return ST_OK;
 }

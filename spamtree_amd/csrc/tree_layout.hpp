@@ -38,6 +38,8 @@ struct LevelInfo {
   int rf_first = 0;                // its blocks' entries (this rank's run) in d_rfvoff / d_rfvld
   int lc_first = 0, lc_count = 0;  // its slabs (this rank's run) in d_lcslabs
   int quad_first = 0, quad_count = 0, qown_lo = 0, qown_n = 0, q_ldS = 0, q_nkx = 0;   // k_factor_quad (q_nkx = 0: not eligible)
+  long long qr_off = -1;           // level on k_factor_quad with quads of this rank: its records in qrec (8-byte words) ...
+  int qr_words = 0;                // ... and a record's length
   long long vl_off = -1;           // leaf quad level whose T a proposal defers: its V tiles in d_vleaf (-1: always QM_FULL)
   size_t lds_quad = 0;
   int own_lo = 0, own_n = 0, gown_lo = 0, gown_n = 0;   // this rank's run of the level's block list / group list
@@ -85,6 +87,13 @@ struct TreeLayout {
   std::vector<int> anc_idx, dch_idx, lvl_list, pred_list, all_obs_list;
   std::vector<Grp> grps;
   std::vector<Quad> quads;
+  // quad records (QuadRec, factor_quad.hpp): what k_factor_quad's workgroups start from, per level on that kernel one record
+  // per quad of this rank's run (LevelInfo::qr_off), then the prediction quads' (pred_qr_off).  The device step uploads
+  // them once and drops the host copy; qrec_bytes stays
+  std::vector<long long> qrec;
+  size_t qrec_bytes = 0;
+  long long pred_qr_off = -1;
+  int pred_qr_words = 0;
   std::vector<WideGrp> wgrps;                 // sibling groups of the wide levels (k_factor_wide)
   std::vector<LcSlab> lcslabs;                // k_factor_lchain: slabs of sibling groups
   std::vector<long long> rfvoff;   // k_factor_ref_finish: per block of a reference level on the lchain route, its columns in the V scratch
