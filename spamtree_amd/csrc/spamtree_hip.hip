@@ -18,49 +18,20 @@
 // Messages to ancestors are pushed as per-ancestor (m_a x m_a, m_a) pairs and summed hierarchically through
 // direct children in a fixed order (no FP64 atomics -> bit-reproducible for any launch geometry).
 //
-// This translation unit is the HOST side: handle, C-ABI, the device step of st_create and EVERY launch.  The launch structures
-// the launches index are built without a device call in tree_layout.cpp (the handle derives from its TreeLayout).  The kernels
+// This translation unit is the HOST side: handle (st_handle.hpp), C-ABI, the device step of st_create and every launch of the
+// fit; new-point prediction (st_points_*) has its C-ABI in st_points.hip.  The launch structures the launches index are built
+// without a device call in tree_layout.cpp (the handle derives from its TreeLayout).  The kernels
 // live in one translation unit per family (k_factor_generic.hip, k_factor_mfma.hip, k_factor_quad.hip, k_factor_wide.hip,
 // k_sample.hip, k_misc.hip); the headers included here give their argument structures, launch constants and prototypes.
 
-#include <unordered_map>
-
-#include "tree_layout.hpp"
+#include "st_handle.hpp"
 #include "misc_kernels.hpp"
-#include "predict_points.hpp"
-#include "predict_joint.hpp"
-#include "simulate_kernels.hpp"
 
 // ===============================================================================================================
 // host side
 // ===============================================================================================================
 static thread_local std::string g_create_error;
-struct st_handle_s;
-static void points_free(st_handle_s *h);
-
-// A device allocation that frees itself; a null buffer makes no HIP call.  (The owner has the device current when it goes.)
-template <typename T>
-struct DevBuf {
-  T *p = nullptr;
-  size_t n = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
-  DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { free(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; } return *this; }
-  ~DevBuf() { free(); }
-  hipError_t alloc(size_t count) {
-    n = count;
-    if (count == 0) { p = nullptr; return hipSuccess; }
-    return hipMalloc((void **)&p, count * sizeof(T));
-  }
-  hipError_t upload(const std::vector<T> &v) {
-    hipError_t e = alloc(v.size());
-    if (e != hipSuccess || v.empty()) return e;
-    return hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-  }
-  void free() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
+void points_free(st_handle_s *h);   // st_points.hip: drops the handle's point set (st_destroy)
 
 // route codes (st_route_info): written by the launch sites themselves; st_route_name spells them as the source does
 enum RouteCode : int {
@@ -90,109 +61,6 @@ static const char *const k_route_names[R_COUNT] = {
   "k_sample_lean<false>", "k_sample<true, false>", "k_sample_leaf_wide", "k_sample<true, true>", "k_sample<false>",
 };
 
-struct st_handle_s : TreeLayout {
-  std::string err;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  int quirks = 1;
-  long long n_obs = 0;
-  DevBuf<Grp> d_grps;                         // the device copies of the layout's lists (tree_layout.hpp)
-  DevBuf<long long> d_qrec;                   // the quad records (TreeLayout::qrec): k_factor_quad's workgroups start from them
-  DevBuf<WideGrp> d_wgrps;
-  DevBuf<LcSlab> d_lcslabs;
-  DevBuf<long long> d_rfvoff, d_gdesc;
-  DevBuf<double> d_vscr;                      // V = Linv_pa K_pa,u of ONE such level (the largest): written by k_factor_lchain, read by k_factor_ref_finish
-  DevBuf<double> d_lcrow;                     // per-row e^2 | log r of the lchain levels (2 n)
-  DevBuf<double> d_s0;                        // Ri' Ri of the reference blocks on the generic phase-B path (theta-only, cached with the Gram parts)
-  DevBuf<long long> d_s0off;                  // per block: offset into d_s0, -1 = none
-  bool c_pending = false;                     // st_sample_w_loglik_begin: the sweep's failure word and log-density are on their way to pin[8..10]
-  int c_rc = 0; double c_ll = 0.0;            // ... or (multi-GPU / communicator attached) already here
-  // multi-GPU sharding
-  DevBuf<int> d_ownobs, d_owngrp, d_ownslow;  // this rank's observed blocks; the same set split: column groups of the fast levels / blocks of the others
-  DevBuf<unsigned char> d_rowmask, d_blkmask; // 1 = this rank contributes the entry to a sum-with-zeros exchange
-  DevBuf<double> d_comm;                      // 2*n_blocks + 64 doubles
-  DevBuf<double> d_gather;                    // all-gather of w: world x gather_cnt (a rank's owned rows in device order + its failure word)
-  DevBuf<int> d_gidx;                         // device row of every slot of d_gather (-1: padding / the failure word)
-  DevBuf<double> d_gerr;                      // the ranks' failure words after the all-gather (64)
-  // phase A of the latency-bound top levels ahead of time (st_factor_begin): they depend on theta only -- except for the
-  // blocks' quadratic forms, redone with the current w afterwards -- and run on a second stream under the sweep
-  hipStream_t stream2 = nullptr;
-  hipEvent_t ev_top = nullptr, ev_main = nullptr;
-  DevBuf<int> d_err2, d_toplist;
-  bool async_top = false, top_pending = false, prof_suspend = false, async_top_off = false;
-  hipEvent_t ev_stats = nullptr;
-  bool stats_on_stream2 = false;   // the statistics kernels of the current (w, XB) are in flight on the second stream
-  bool stats_prefetched = false;   // ... and their results follow them to pin[20 ..] on that stream
-  int top_phys = -1;
-  std::vector<double> top_theta;
-  bool ext_stream = false;
-  DevBuf<double> d_sum_w, d_sum_yhat;         // running sums over saved iterations (st_summary_*)
-  long long n_summary = 0;
-  DevBuf<double> d_draws_w, d_draws_yhat;     // st_summary_reserve: the saved draws themselves, [keep][n_all] (quantiles)
-  long long draws_cap = 0, n_draws = 0;
-  bool stats_valid = false;                   // d_stats matches the current w and XB
-  bool host_stats_valid = false;              // ... and host_stats holds a copy of it
-  std::vector<double> host_stats;
-  double *pin = nullptr;                      // 64 doubles of pinned host memory for the small device-to-host reads: [0..3] st_factor (comm path) /
-                                              // st_loglik_w sums + failure word, [8..11] st_sample_w_loglik_end, [12..15] st_factor_enqueue / _finish, [20..] statistics
-  double *pin_up = nullptr;                   // pinned staging of the small per-iteration uploads (beta, tausq_inv): two slots taken in turn,
-  int pin_up_slot = 0, pin_up_len = 0;        // so that the copy is truly asynchronous and the setters need no host synchronisation
-  hipEvent_t ev_up[2] = {nullptr, nullptr};   // recorded behind a slot's copy: a slot is rewritten only after its last copy has run
-  bool factor_open = false; int factor_open_slot = 0;   // st_factor_enqueue without its st_factor_finish yet
-  std::vector<double> top_theta_open;                   // ... its theta where the work itself waits for st_factor_finish (communicator attached)
-  hipEvent_t ev_factor = nullptr;                       // behind the copies of an enqueued factorisation's sums and failure word
-  std::vector<char> s0_valid;                 // per level: d_s0 holds the theta-only precision parts of the accepted theta (column-group levels)
-  bool gram_valid = false;                    // message Gram parts in `acc` match the accepted theta (slot 0)
-  bool cache_gram = true;
-  // a proposal's quad leaf levels (st_factor_enqueue on slot 1): QM_VONLY, their panels finished by QM_TFROMV from d_vleaf when
-  // the slot is read (st_swap, st_get_block, st_loglik_*); re-factorising the slot drops the pending half
-  bool leaf_pending[2] = {false, false};   // per physical arena
-  CovPar leaf_cp[2];
-  DevBuf<double> d_vleaf;
-  DevBuf<int> d_twin;
-  ncclComm_t comm = nullptr;                  // native RCCL communicator (st_comm_init); null = exchanges are the caller's
-  std::vector<int> route_a, route_b;          // per level: ST_ROUTE_A_SLOTS phase-A / 2 phase-B route codes of the last launch
-  int route_p = R_NONE;                       // ... and of the last st_predict
-  std::vector<double> xtx;
-  std::vector<long long> n_obs_q;
-  struct PointSet *pts = nullptr;             // st_points_set: new locations to predict at (owned)
-  // st_simulate: draws [row][sim_cap] on the device (allocated on first use, grown with nd), the device block of every row
-  DevBuf<double> d_simz, d_sime, d_simw, d_simy;
-  DevBuf<int> d_rowblk;
-  int sim_cap = 0;
-  std::vector<SimLevel> sim_levels;
-
-  DevBuf<double> d_cx, d_cy, d_y, d_X, d_w, d_xb, d_z, d_B, d_panels[2], d_acc, d_logdet[2], d_loglik[2], d_scalars, d_partial,
-      d_stats, d_xtx, d_scratch, d_tmp_n, d_tsq;
-  DevBuf<int> d_mv, d_anc, d_dch, d_lvl, d_pred, d_allobs, d_err;
-  DevBuf<unsigned char> d_obs;
-  DevBuf<long long> d_dev2model, d_partner;
-  DevBuf<Blk> d_blks;
-  int slot_map[2] = {0, 1};    // logical slot (0 param, 1 alter) -> physical arena
-  double tausq_inv[QMAX];
-  std::vector<double> theta[2];
-  bool z_valid = false;
-
-  // profiling
-  int prof = 0;   // 0 off, 1 every kernel family, 2 phase A only (the roofline measurement at the lowest cost)
-  double prof_ms[ST_N_KERNEL_FAMILIES] = {0};
-  long long prof_n[ST_N_KERNEL_FAMILIES] = {0};
-  std::vector<double> prof_level_ms;   // phase-A time per level, accumulated
-  std::vector<long long> prof_level_n;
-  struct ProfRec { hipEvent_t a, b; int fam, level, count; };   // count: kernel launches inside the bracket
-  std::vector<ProfRec> prof_pending;
-  std::vector<hipEvent_t> ev_free;
-};
-
-#define HCHK(h, call)                                                                                         \
-  do {                                                                                                        \
-    hipError_t e_ = (call);                                                                                   \
-    if (e_ != hipSuccess) {                                                                                   \
-      (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                                           \
-      return ST_ERR_HIP;                                                                                      \
-    }                                                                                                         \
-  } while (0)
-
 static int fail_create(st_handle_s *h, int code, const std::string &msg) {
   g_create_error = msg;
   if (h) {
@@ -216,46 +84,6 @@ static void launch_stats(st_handle_s *h, hipStream_t st, const double *wt) {
   hipLaunchKernelGGL(k_stats, dim3(STATS_WG, (h->p + 7) / 8), dim3(NT), 0, st, h->d_X.p, h->d_y.p, h->d_w.p, h->d_xb.p, h->d_mv.p,
                      h->d_obs.p, h->d_partner.p, wt, h->n_all, h->p, h->d_partial.p);
 }
-
-// Launch timing with HIP events on the launch stream, harvested lazily (no host sync inside the measured region).
-static hipEvent_t prof_event(st_handle_s *h) {
-  if (!h->ev_free.empty()) { hipEvent_t e = h->ev_free.back(); h->ev_free.pop_back(); return e; }
-  hipEvent_t e = nullptr;
-  (void)hipEventCreate(&e);
-  return e;
-}
-static void prof_harvest(st_handle_s *h) {
-  for (auto &r : h->prof_pending) {
-    float ms = 0.f;
-    if (hipEventSynchronize(r.b) == hipSuccess && hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess) {
-      h->prof_ms[r.fam] += ms;
-      h->prof_n[r.fam] += r.count;
-      // (count 0: the deferred half of a level's launch -- its time, not another launch)
-      if (r.level >= 0 && r.level < (int)h->prof_level_ms.size()) { h->prof_level_ms[r.level] += ms; h->prof_level_n[r.level] += r.count > 0; }
-    }
-    h->ev_free.push_back(r.a);
-    h->ev_free.push_back(r.b);
-  }
-  h->prof_pending.clear();
-}
-struct ProfScope {
-  st_handle_s *h;
-  st_handle_s::ProfRec r;
-  // mode 1: every launch is bracketed; mode 2: only the whole-phase bracket of phase A (level == -2), one pair of events
-  hipStream_t st;
-  ProfScope(st_handle_s *h_, int fam, int level = -1, int count = 1, hipStream_t st_ = nullptr) : h(h_), st(st_ ? st_ : h_->stream) {
-    r.fam = fam; r.level = level; r.count = count; r.a = r.b = nullptr;
-    const bool on = level == -2 ? (h->prof == 2 && !h->prof_suspend) : h->prof == 1;
-    if (on) { r.a = prof_event(h); r.b = prof_event(h); (void)hipEventRecord(r.a, st); }
-  }
-  ~ProfScope() {
-    if (r.a && r.b) {
-      (void)hipEventRecord(r.b, st);
-      h->prof_pending.push_back(r);
-      if (h->prof_pending.size() > 8192) prof_harvest(h);
-    }
-  }
-};
 
 // w or XB is about to change: the cached statistics die; a reduction still in flight on the second stream finishes first
 static void invalidate_stats(st_handle_s *h) {
@@ -331,11 +159,6 @@ static bool query_device(int device, DeviceLimits &dl) {
   for (const void *f : {(const void *)k_factor_quad<4, 50, 13, true, true>, (const void *)k_factor_quad<4, 50, 13, true, false>})
     if (hipFuncGetAttributes(&fa, f) == hipSuccess) dl.quad_static = std::max(dl.quad_static, (size_t)fa.sharedSizeBytes);
   return true;
-}
-
-template <typename T>
-static hipError_t upload_or_dummy(DevBuf<T> &d, const std::vector<T> &v) {   // an empty list still gets one (zero) element to point at
-  return v.empty() ? d.upload(std::vector<T>(1)) : d.upload(v);
 }
 
 // stream, events, pinned buffers; the row data in device order
@@ -672,7 +495,7 @@ extern "C" int st_shard_info(st_handle h, int32_t *rank, int32_t *world, int32_t
 }
 
 // CovarianceParams::transform (covariance_functions.cpp:34-75) + vec_to_symmat (:77-92)
-static int make_covpar(st_handle h, const double *theta, int ntheta, CovPar *cp) {
+int make_covpar(st_handle h, const double *theta, int ntheta, CovPar *cp) {
   const int q = h->q, ncb = q > 2 ? 3 : 1, npars = 3 * q + ncb, k = q * (q - 1) / 2;
   if (ntheta != npars + k) { h->err = "theta has the wrong length"; return ST_ERR_USAGE; }
   std::memset(cp, 0, sizeof(*cp));
@@ -1843,575 +1666,6 @@ extern "C" int st_summary_get(st_handle h, double *w_mean, double *yhat_mean, in
   return ST_OK;
 }
 
-
-// ---- new-point prediction (predict_points.hpp has the model; the kernels and their launcher live in k_predict.hip) ----------
-struct PointSet {
-  long long n = 0;
-  int ntile128 = 0, ntile256 = 0, grid_generic = 0, n_chains = 0;
-  bool has_X = false;
-  long long scratch_stride = 1;
-  double alg_bytes = 0.0, flops = 0.0;
-  int route_mask = 0;
-  DevBuf<double> d_px, d_py, d_X, d_z, d_out, d_scratch;
-  DevBuf<int> d_pmv, d_chain_blk, d_pt_chain, d_gen;
-  DevBuf<long long> d_order;
-  DevBuf<PtChain> d_chains;
-  DevBuf<PtTile> d_tiles;
-  // st_points_accumulate: PA_NACC x n accumulators, and with st_points_summary_reserve the draws themselves, [keep][n] each
-  DevBuf<double> d_acc, d_keep_w, d_keep_yhat;
-  long long n_acc = 0, keep_cap = 0, n_kept = 0;
-  // st_points_set_joint: the joint groups in layout order (first appearance), their packing into slots and the pair accumulators
-  bool joint = false;
-  long long n_joint = 0, cov_total = 0;
-  int jtile128 = 0, jtile256 = 0, jgrid_generic = 0;
-  double j_alg_bytes = 0.0, j_flops = 0.0;
-  std::vector<int64_t> j_off, j_mptr, j_mem;   // packed block offsets (n_joint + 1), member list pointers (n_joint + 1), members
-  DevBuf<PtJoint> d_jgroups;
-  DevBuf<long long> d_jmem;
-  DevBuf<PtCol> d_jcols;
-  DevBuf<PtTile> d_jtiles;
-  DevBuf<int> d_jgen, d_pt_grp, d_pt_a;
-  DevBuf<double> d_jout, d_jscratch, d_pacc;   // cov and chol of the last call (2 x cov_total); scratch; pair accumulators
-};
-
-static void points_free(st_handle_s *h) {
-  delete h->pts;   // its device buffers free themselves
-  h->pts = nullptr;
-}
-
-// st_points_set (joint_id NULL) and st_points_set_joint
-static int points_set_impl(st_handle h, int64_t n_new, const double *coords, const int64_t *mv, const int64_t *anchor, const double *X,
-                           const int64_t *joint_id) {
-  if (!h) return ST_ERR_USAGE;
-  if (h->limited) { h->err = "st_points_set: limited_tree handles are not supported (new-point prediction is out of scope for them)"; return ST_ERR_UNSUPPORTED; }
-  if (h->world > 1) { h->err = "st_points_set: multi-GPU handles (world > 1) are not supported (new-point prediction is out of scope for them)"; return ST_ERR_UNSUPPORTED; }
-  if (n_new < 0 || n_new > (int64_t)INT32_MAX || (n_new > 0 && (!coords || !mv || !anchor))) { h->err = "st_points_set: bad sizes or NULL inputs"; return ST_ERR_USAGE; }
-  for (int64_t i = 0; i < n_new; ++i) {
-    if (anchor[i] < 0 || anchor[i] >= h->n_blocks) { h->err = "st_points_set: anchor " + std::to_string(i) + " is not a block id"; return ST_ERR_USAGE; }
-    if (h->blks[h->blk_model2dev[anchor[i]]].nobs == 0) {
-      h->err = "st_points_set: anchor " + std::to_string(i) + " is a prediction block (no observed rows)"; return ST_ERR_USAGE;
-    }
-    if (mv[i] < 1 || mv[i] > h->q) { h->err = "st_points_set: margin of point " + std::to_string(i) + " is not in 1..q"; return ST_ERR_USAGE; }
-    if (!std::isfinite(coords[i]) || !std::isfinite(coords[n_new + i])) { h->err = "st_points_set: coordinates must be finite"; return ST_ERR_USAGE; }
-  }
-  // conditioning chain of every point: ends at r = the anchor (reference) or its last parent (non-reference)
-  std::vector<int> rdev(n_new);
-  for (int64_t i = 0; i < n_new; ++i) {
-    const int b = h->blk_model2dev[anchor[i]];
-    const Blk &B = h->blks[b];
-    rdev[i] = B.isref ? b : (B.nanc > 0 ? h->anc_idx[B.anc_ptr + B.nanc - 1] : -1);
-  }
-  // joint groups: by first appearance, members in the caller's order; one chain and at most ST_POINTS_MAX_JOINT members each
-  std::vector<int64_t> j_mptr, j_mem;
-  std::vector<int> pt_grp, pt_a;
-  if (joint_id) {
-    std::unordered_map<int64_t, int> index;
-    std::vector<int> gsz;
-    pt_grp.resize(n_new); pt_a.resize(n_new);
-    for (int64_t i = 0; i < n_new; ++i) {
-      auto it = index.find(joint_id[i]);
-      if (it == index.end()) { it = index.emplace(joint_id[i], (int)gsz.size()).first; gsz.push_back(0); j_mem.push_back(i); }
-      const int k = it->second;
-      if (rdev[i] != rdev[j_mem[k]]) {
-        h->err = "st_points_set_joint: the members of joint group " + std::to_string(joint_id[i]) + " do not end in the same conditioning chain (point " +
-                 std::to_string(i) + " and point " + std::to_string(j_mem[k]) + ")";
-        return ST_ERR_USAGE;
-      }
-      pt_grp[i] = k; pt_a[i] = gsz[k]++;
-      if (gsz[k] > ST_POINTS_MAX_JOINT) {
-        h->err = "st_points_set_joint: joint group " + std::to_string(joint_id[i]) + " has more than " + std::to_string(ST_POINTS_MAX_JOINT) +
-                 " members (ST_POINTS_MAX_JOINT)";
-        return ST_ERR_UNSUPPORTED;
-      }
-    }
-    j_mptr.assign(gsz.size() + 1, 0);
-    for (size_t k = 0; k < gsz.size(); ++k) j_mptr[k + 1] = j_mptr[k] + gsz[k];
-    j_mem.assign(n_new, 0);
-    for (int64_t i = 0; i < n_new; ++i) j_mem[j_mptr[pt_grp[i]] + pt_a[i]] = i;
-  }
-  HCHK(h, hipSetDevice(h->device));
-  points_free(h);
-  PointSet *ps = new PointSet();
-  h->pts = ps;
-  ps->n = n_new;
-  if (joint_id) { ps->joint = true; ps->j_off.assign(1, 0); ps->j_mptr.assign(1, 0); }
-  if (n_new == 0) return ST_OK;
-  std::vector<int> keys(rdev);
-  std::sort(keys.begin(), keys.end());
-  keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
-  std::vector<PtChain> chains(keys.size());
-  std::vector<int> chain_blk;
-  std::vector<char> gen_chain(keys.size(), 0);
-  const bool lds256 = PP_LDS_BYTES(256) <= h->lds_limit;
-  for (size_t c = 0; c < keys.size(); ++c) {
-    PtChain &C = chains[c];
-    C.first = (int)chain_blk.size(); C.nblk = 0; C.rows = 0; C.pad = 0;
-    if (keys[c] >= 0) {
-      const Blk &R = h->blks[keys[c]];
-      for (int t = 0; t < R.nanc; ++t) chain_blk.push_back(h->anc_idx[R.anc_ptr + t]);
-      chain_blk.push_back(keys[c]);
-      C.nblk = R.nanc + 1;
-      C.rows = R.P + R.m;
-    }
-    gen_chain[c] = h->force_generic || C.rows > 256 || (C.rows > 128 && !lds256) || C.nblk > PP_MAXB;
-  }
-  // sorted order: 128-row chains, then 256-row chains, then the generic route; by chain, then by the caller's index
-  std::vector<int> chain_of(n_new), cls(keys.size());
-  for (size_t c = 0; c < keys.size(); ++c) cls[c] = gen_chain[c] ? 2 : (chains[c].rows <= 128 ? 0 : 1);
-  for (int64_t i = 0; i < n_new; ++i) chain_of[i] = (int)(std::lower_bound(keys.begin(), keys.end(), rdev[i]) - keys.begin());
-  std::vector<long long> order(n_new);
-  for (int64_t i = 0; i < n_new; ++i) order[i] = i;
-  std::stable_sort(order.begin(), order.end(), [&](long long a, long long b) {
-    const int ca = chain_of[a], cb = chain_of[b];
-    return cls[ca] != cls[cb] ? cls[ca] < cls[cb] : ca < cb;
-  });
-  std::vector<int> pt_chain(n_new), gen;
-  std::vector<PtTile> tiles;
-  double bytes = 0.0, flops = 0.0;
-  auto chain_cost = [&](const PtChain &C, double *panel_bytes, double *tri_flops) {
-    double pb = 0.0;
-    long long o = 0;
-    for (int t = 0; t < C.nblk; ++t) { const Blk &A = h->blks[chain_blk[C.first + t]]; o += A.m; pb += (double)A.m * (double)o * 8.0; }
-    *panel_bytes = pb + (double)C.rows * 28.0;                          // stored panels + coordinates, margin, w of the chain rows
-    *tri_flops = (double)C.rows * (double)(C.rows + 1);                  // one lower-triangular product: 2 x rows (rows + 1) / 2
-  };
-  const double per_point_bytes = 2 * 8.0 + 4.0 + 8.0 + 8.0 + 4 * 8.0;   // coordinates, margin, order, z in; mean, var, w, yhat out
-  for (int64_t s = 0; s < n_new;) {
-    const int c = chain_of[order[s]];
-    int64_t e = s;
-    while (e < n_new && chain_of[order[e]] == c) { pt_chain[e] = c; ++e; }
-    double pb, tf;
-    chain_cost(chains[c], &pb, &tf);
-    if (cls[c] == 2) {
-      for (int64_t i = s; i < e; ++i) gen.push_back((int)i);
-      bytes += (double)(e - s) * (pb + per_point_bytes);
-      flops += (double)(e - s) * (2.0 * tf + 4.0 * chains[c].rows);    // v and u per point, then v'v and v'u
-    } else {
-      for (int64_t p0 = s; p0 < e; p0 += PP_NCOL) {
-        PtTile T; T.chain = c; T.p0 = (int)p0; T.np = (int)std::min<int64_t>(PP_NCOL, e - p0); T.pad = 0;
-        tiles.push_back(T);
-        if (cls[c] == 0) ++ps->ntile128; else ++ps->ntile256;
-        bytes += pb;
-        flops += tf + (double)T.np * (tf + 4.0 * chains[c].rows);       // u once per tile, v per point
-      }
-      bytes += (double)(e - s) * per_point_bytes;
-    }
-    s = e;
-  }
-  ps->n_chains = (int)keys.size();
-  ps->alg_bytes = bytes; ps->flops = flops;
-  long long maxrows = 1;
-  for (size_t c = 0; c < keys.size(); ++c) if (gen_chain[c]) maxrows = std::max<long long>(maxrows, chains[c].rows);
-  ps->scratch_stride = (maxrows + 31) & ~31LL;
-  ps->grid_generic = (int)std::min<size_t>(gen.size(), (size_t)4 * h->sm_count);
-  std::vector<double> px(coords, coords + n_new), py(coords + n_new, coords + 2 * n_new);
-  std::vector<int> pmv(n_new);
-  for (int64_t i = 0; i < n_new; ++i) pmv[i] = (int)(mv[i] - 1);
-  HCHK(h, ps->d_px.upload(px)); HCHK(h, ps->d_py.upload(py)); HCHK(h, ps->d_pmv.upload(pmv));
-  HCHK(h, ps->d_order.upload(order)); HCHK(h, ps->d_pt_chain.upload(pt_chain)); HCHK(h, ps->d_chains.upload(chains));
-  HCHK(h, upload_or_dummy(ps->d_chain_blk, chain_blk)); HCHK(h, upload_or_dummy(ps->d_tiles, tiles)); HCHK(h, upload_or_dummy(ps->d_gen, gen));
-  HCHK(h, ps->d_z.alloc(n_new));
-  HCHK(h, ps->d_out.alloc((size_t)4 * n_new));
-  if (ps->grid_generic > 0) HCHK(h, ps->d_scratch.alloc((size_t)ps->grid_generic * 2 * ps->scratch_stride));
-  if (X) {
-    std::vector<double> xv(X, X + (size_t)n_new * h->p);
-    HCHK(h, ps->d_X.upload(xv));
-    ps->has_X = true;
-  }
-  if (!joint_id) return ST_OK;
-  // ---- the joint packing: MFMA chains into 16-column slots of whole groups, four slots to a workgroup, one chain per workgroup;
-  // the groups of the other chains one workgroup each
-  const int64_t nj = (int64_t)j_mptr.size() - 1;
-  std::vector<PtJoint> groups(nj);
-  std::vector<int64_t> j_off(nj + 1, 0);
-  std::vector<std::vector<int>> by_chain(keys.size());
-  for (int64_t k = 0; k < nj; ++k) {
-    const int g = (int)(j_mptr[k + 1] - j_mptr[k]);
-    PtJoint &G = groups[k];
-    G.cov_off = j_off[k]; G.first = (int)j_mptr[k]; G.g = g; G.chain = chain_of[j_mem[j_mptr[k]]]; G.pad = 0;
-    j_off[k + 1] = j_off[k] + (int64_t)g * g;
-    by_chain[G.chain].push_back((int)k);
-  }
-  std::vector<PtTile> jtiles;
-  std::vector<PtCol> jcols;
-  std::vector<int> jgen;
-  double jb = 0.0, jf = 0.0;
-  for (int pass = 0; pass < 3; ++pass)
-    for (size_t c = 0; c < keys.size(); ++c) {
-      if (cls[c] != pass || by_chain[c].empty()) continue;
-      double pb, tf;
-      chain_cost(chains[c], &pb, &tf);
-      const double rows = chains[c].rows;
-      for (int k : by_chain[c]) {
-        const double g = groups[k].g;
-        jb += g * (per_point_bytes + 8.0) + 2.0 * g * g * 8.0;                    // + the member index; cov and chol out
-        jf += g * (g + 1.0) * rows + g * g * g / 3.0 + g * (g + 1.0);             // the Gram, the factorisation, L z
-      }
-      if (pass == 2) {
-        for (int k : by_chain[c]) {
-          jgen.push_back(k);
-          jb += pb + groups[k].g * 2.0 * rows * 8.0;                              // the chain once per group; V written and read
-          jf += (groups[k].g + 1.0) * (tf + 2.0 * rows);
-        }
-        continue;
-      }
-      int slot = 4, used = 16;                                                     // no open tile
-      for (int k : by_chain[c]) {
-        const int g = groups[k].g;
-        if (used + g > 16) {
-          if (++slot >= 4) {
-            PtTile T; T.chain = (int)c; T.p0 = 0; T.np = 0; T.pad = 0;
-            jtiles.push_back(T);
-            jcols.resize(jcols.size() + PP_NCOL, PtCol{k, -1});
-            if (pass == 0) ++ps->jtile128; else ++ps->jtile256;
-            jb += pb; jf += tf;
-            slot = 0;
-          }
-          used = 0;
-          jtiles.back().np = slot + 1;
-        }
-        PtCol *col = jcols.data() + (jtiles.size() - 1) * PP_NCOL + slot * 16 + used;
-        for (int a = 0; a < g; ++a) { col[a].grp = k; col[a].a = a; }
-        used += g;
-        jf += g * (tf + 4.0 * rows);
-      }
-    }
-  ps->n_joint = nj; ps->cov_total = j_off[nj];
-  ps->j_alg_bytes = jb; ps->j_flops = jf;
-  ps->jgrid_generic = (int)std::min<size_t>(jgen.size(), (size_t)4 * h->sm_count);
-  std::vector<long long> jmem_ll(j_mem.begin(), j_mem.end());
-  if (jcols.empty()) jcols.push_back(PtCol{0, -1});
-  HCHK(h, ps->d_jgroups.upload(groups)); HCHK(h, ps->d_jmem.upload(jmem_ll)); HCHK(h, upload_or_dummy(ps->d_jtiles, jtiles));
-  HCHK(h, ps->d_jcols.upload(jcols)); HCHK(h, upload_or_dummy(ps->d_jgen, jgen)); HCHK(h, ps->d_pt_grp.upload(pt_grp)); HCHK(h, ps->d_pt_a.upload(pt_a));
-  HCHK(h, ps->d_jout.alloc((size_t)2 * ps->cov_total));
-  if (ps->jgrid_generic > 0) HCHK(h, ps->d_jscratch.alloc((size_t)ps->jgrid_generic * PJ_SCRATCH_COLS * ps->scratch_stride));
-  ps->j_off = j_off; ps->j_mptr = j_mptr; ps->j_mem = j_mem;
-  return ST_OK;
-}
-
-extern "C" int st_points_set(st_handle h, int64_t n_new, const double *coords, const int64_t *mv, const int64_t *anchor, const double *X) {
-  return points_set_impl(h, n_new, coords, mv, anchor, X, nullptr);
-}
-
-extern "C" int st_points_set_joint(st_handle h, int64_t n_new, const double *coords, const int64_t *mv, const int64_t *anchor, const double *X,
-                                   const int64_t *joint_id) {
-  return points_set_impl(h, n_new, coords, mv, anchor, X, joint_id);
-}
-
-extern "C" int st_points_joint_layout(st_handle h, int64_t *n_joint, int64_t *offsets, int64_t *member_ptr, int64_t *members) {
-  if (!h) return ST_ERR_USAGE;
-  const PointSet *ps = h->pts;
-  if (!ps || !ps->joint) { h->err = "st_points_joint_layout before st_points_set_joint"; return ST_ERR_USAGE; }
-  if (n_joint) *n_joint = ps->n_joint;
-  if (offsets) std::copy(ps->j_off.begin(), ps->j_off.end(), offsets);
-  if (member_ptr) std::copy(ps->j_mptr.begin(), ps->j_mptr.end(), member_ptr);
-  if (members) std::copy(ps->j_mem.begin(), ps->j_mem.end(), members);
-  return ST_OK;
-}
-
-// launches the k_points_* routes of the point set on slot 0 and the current w / beta / tausq_inv into ps->d_out (w, mean, var,
-// yhat: n doubles each, caller order; out[k] false: that output is not written).  No synchronisation.
-static void points_args(st_handle h, PointSet *ps, int mode, bool use_z, uint64_t seed, uint32_t iter, const bool out[4], PointsArgs &A) {
-  const long long n = ps->n;
-  double *o = ps->d_out.p;
-  std::memset(&A, 0, sizeof(A));
-  A.blks = h->d_blks.p; A.chain_blk = ps->d_chain_blk.p; A.chains = ps->d_chains.p; A.tiles = ps->d_tiles.p; A.ntiles = 0;
-  A.gen_list = ps->d_gen.p; A.ngen = ps->grid_generic > 0 ? (int)(ps->d_gen.n) : 0;
-  A.pt_chain = ps->d_pt_chain.p; A.order = ps->d_order.p; A.px = ps->d_px.p; A.py = ps->d_py.p; A.pmv = ps->d_pmv.p;
-  A.cx = h->d_cx.p; A.cy = h->d_cy.p; A.mv = h->d_mv.p; A.w = h->d_w.p; A.panels = h->d_panels[h->slot_map[0]].p;
-  A.z = use_z ? ps->d_z.p : nullptr; A.seed = seed; A.iter = iter; A.mode = mode;
-  A.X = ps->has_X ? ps->d_X.p : nullptr; A.B = h->d_B.p; A.tsq_inv = h->d_tsq.p; A.p = h->p; A.n_new = n;
-  A.w_new = out[0] ? o : nullptr; A.mean = out[1] ? o + n : nullptr; A.var = out[2] ? o + 2 * n : nullptr;
-  A.yhat = out[3] ? o + 3 * n : nullptr;
-  A.scratch = ps->d_scratch.p; A.scratch_stride = ps->scratch_stride;
-}
-
-static int points_run(st_handle h, PointSet *ps, int mode, bool use_z, uint64_t seed, uint32_t iter, const bool out[4], const char *who) {
-  CovPar cp;
-  int rc = make_covpar(h, h->theta[0].data(), (int)h->theta[0].size(), &cp);
-  if (rc) return rc;
-  PointsArgs A;
-  points_args(h, ps, mode, use_z, seed, iter, out, A);
-  PointsLaunch L;
-  L.ntile128 = ps->ntile128; L.ntile256 = ps->ntile256; L.grid_generic = ps->grid_generic;
-  ProfScope pscope(h, 6);
-  const int e = points_launch(L, A, cp, h->stream, &ps->route_mask);
-  if (e) { h->err = std::string(who) + " launch: " + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
-  return ST_OK;
-}
-
-extern "C" int st_points_predict(st_handle h, int mode, const double *z, uint64_t seed, uint32_t iter, double *w_new, double *cond_mean,
-                                 double *cond_var, double *yhat_new) {
-  if (!h) return ST_ERR_USAGE;
-  if (h->limited || h->world > 1) { h->err = "st_points_predict: limited_tree and multi-GPU handles are not supported (out of scope)"; return ST_ERR_UNSUPPORTED; }
-  if (!h->pts) { h->err = "st_points_predict before st_points_set"; return ST_ERR_USAGE; }
-  if (h->theta[0].empty()) { h->err = "st_points_predict before st_factor(slot 0)"; return ST_ERR_USAGE; }
-  if (h->factor_open) { h->err = "st_points_predict between st_factor_enqueue and st_factor_finish"; return ST_ERR_USAGE; }
-  if (mode != 0 && mode != 1) { h->err = "st_points_predict: mode must be 0 (draw) or 1 (conditional mean)"; return ST_ERR_USAGE; }
-  PointSet *ps = h->pts;
-  if (yhat_new && !ps->has_X) { h->err = "st_points_predict: yhat_new needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
-  ps->route_mask = 0;
-  if (ps->n == 0) return ST_OK;
-  HCHK(h, hipSetDevice(h->device));
-  const long long n = ps->n;
-  if (z && mode == 0) HCHK(h, hipMemcpyAsync(ps->d_z.p, z, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  double *dst[4] = {w_new, cond_mean, cond_var, yhat_new};
-  const bool out[4] = {w_new != nullptr, cond_mean != nullptr, cond_var != nullptr, yhat_new != nullptr};
-  const int rc = points_run(h, ps, mode, z && mode == 0, seed, iter, out, "st_points_predict");
-  if (rc) return rc;
-  for (int k = 0; k < 4; ++k)
-    if (dst[k]) HCHK(h, hipMemcpyAsync(dst[k], ps->d_out.p + (size_t)k * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  return ST_OK;
-}
-
-// the joint routes of the point set (st_points_set_joint) into ps->d_out as points_run, plus cov and chol into ps->d_jout
-static int points_run_joint(st_handle h, PointSet *ps, int mode, bool use_z, uint64_t seed, uint32_t iter, const bool out[4], bool want_cov,
-                            bool want_chol, const char *who) {
-  CovPar cp;
-  int rc = make_covpar(h, h->theta[0].data(), (int)h->theta[0].size(), &cp);
-  if (rc) return rc;
-  JointArgs J;
-  std::memset(&J, 0, sizeof(J));
-  points_args(h, ps, mode, use_z, seed, iter, out, J.P);
-  J.P.tiles = ps->d_jtiles.p;
-  J.P.scratch = ps->d_jscratch.p;
-  J.groups = ps->d_jgroups.p; J.members = ps->d_jmem.p; J.cols = ps->d_jcols.p;
-  J.gen_groups = ps->d_jgen.p; J.ngen_groups = ps->jgrid_generic > 0 ? (int)ps->d_jgen.n : 0;
-  J.cov = want_cov ? ps->d_jout.p : nullptr; J.chol = want_chol ? ps->d_jout.p + ps->cov_total : nullptr;
-  JointLaunch L;
-  L.ntile128 = ps->jtile128; L.ntile256 = ps->jtile256; L.grid_generic = ps->jgrid_generic;
-  ProfScope pscope(h, 6);
-  const int e = points_joint_launch(L, J, cp, h->stream, &ps->route_mask);
-  if (e) { h->err = std::string(who) + " launch: " + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
-  return ST_OK;
-}
-
-extern "C" int st_points_predict_joint(st_handle h, int mode, const double *z, uint64_t seed, uint32_t iter, double *w_new, double *cond_mean,
-                                       double *cond_cov, double *cond_chol, double *yhat_new) {
-  if (!h) return ST_ERR_USAGE;
-  if (h->limited || h->world > 1) { h->err = "st_points_predict_joint: limited_tree and multi-GPU handles are not supported (out of scope)"; return ST_ERR_UNSUPPORTED; }
-  if (!h->pts || !h->pts->joint) { h->err = "st_points_predict_joint before st_points_set_joint"; return ST_ERR_USAGE; }
-  if (h->theta[0].empty()) { h->err = "st_points_predict_joint before st_factor(slot 0)"; return ST_ERR_USAGE; }
-  if (h->factor_open) { h->err = "st_points_predict_joint between st_factor_enqueue and st_factor_finish"; return ST_ERR_USAGE; }
-  if (mode != 0 && mode != 1) { h->err = "st_points_predict_joint: mode must be 0 (draw) or 1 (conditional mean)"; return ST_ERR_USAGE; }
-  PointSet *ps = h->pts;
-  if (yhat_new && !ps->has_X) { h->err = "st_points_predict_joint: yhat_new needs the regressors X of st_points_set_joint"; return ST_ERR_USAGE; }
-  ps->route_mask = 0;
-  if (ps->n == 0) return ST_OK;
-  HCHK(h, hipSetDevice(h->device));
-  const long long n = ps->n;
-  if (z && mode == 0) HCHK(h, hipMemcpyAsync(ps->d_z.p, z, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  const bool out[4] = {w_new != nullptr, cond_mean != nullptr, false, yhat_new != nullptr};
-  const int rc = points_run_joint(h, ps, mode, z && mode == 0, seed, iter, out, cond_cov != nullptr, cond_chol != nullptr, "st_points_predict_joint");
-  if (rc) return rc;
-  double *dst[4] = {w_new, cond_mean, nullptr, yhat_new};
-  for (int k = 0; k < 4; ++k)
-    if (dst[k]) HCHK(h, hipMemcpyAsync(dst[k], ps->d_out.p + (size_t)k * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  const size_t cb = (size_t)ps->cov_total * sizeof(double);
-  if (cond_cov) HCHK(h, hipMemcpyAsync(cond_cov, ps->d_jout.p, cb, hipMemcpyDeviceToHost, h->stream));
-  if (cond_chol) HCHK(h, hipMemcpyAsync(cond_chol, ps->d_jout.p + ps->cov_total, cb, hipMemcpyDeviceToHost, h->stream));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  return ST_OK;
-}
-
-extern "C" int st_points_info(st_handle h, int32_t *route, int64_t *n_groups, double *alg_bytes, double *flops) {
-  if (!h) return ST_ERR_USAGE;
-  const PointSet *ps = h->pts;
-  const bool jr = ps && (ps->route_mask >> (PP_ROUTE_JOINT_MFMA128 - 1)) != 0;   // the last call took the joint routes
-  if (route) *route = ps ? ps->route_mask : 0;
-  if (n_groups) *n_groups = ps ? ps->n_chains : 0;
-  if (alg_bytes) *alg_bytes = ps ? (jr ? ps->j_alg_bytes : ps->alg_bytes) : 0.0;
-  if (flops) *flops = ps ? (jr ? ps->j_flops : ps->flops) : 0.0;
-  return ST_OK;
-}
-
-extern "C" const char *st_points_route_name(int32_t code) {
-  return code < PP_ROUTE_COUNT ? points_route_name(code) : points_joint_route_name(code);
-}
-
-// ---- predictive summaries of the point set over saved iterations (st_points_accumulate; the kernel lives in k_points_acc.hip) ----
-static int points_refuse(st_handle h, const char *who) {
-  if (h->limited || h->world > 1) {
-    h->err = std::string(who) + ": limited_tree and multi-GPU handles are not supported (out of scope)";
-    return ST_ERR_UNSUPPORTED;
-  }
-  if (!h->pts) { h->err = std::string(who) + " before st_points_set"; return ST_ERR_USAGE; }
-  return ST_OK;
-}
-
-extern "C" int st_points_summary_reset(st_handle h) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = points_refuse(h, "st_points_summary_reset")) return rc;
-  PointSet *ps = h->pts;
-  HCHK(h, hipSetDevice(h->device));
-  const size_t cnt = (size_t)PA_NACC * ps->n;
-  if (cnt > 0 && !ps->d_acc.p) HCHK(h, ps->d_acc.alloc(cnt));
-  if (cnt > 0) HCHK(h, hipMemsetAsync(ps->d_acc.p, 0, cnt * sizeof(double), h->stream));
-  const size_t pcnt = (size_t)2 * ps->cov_total;
-  if (pcnt > 0 && !ps->d_pacc.p) HCHK(h, ps->d_pacc.alloc(pcnt));
-  if (pcnt > 0) HCHK(h, hipMemsetAsync(ps->d_pacc.p, 0, pcnt * sizeof(double), h->stream));
-  ps->n_acc = 0; ps->n_kept = 0;
-  return ST_OK;
-}
-
-extern "C" int st_points_summary_reserve(st_handle h, int64_t keep) {
-  if (!h || keep < 0) return ST_ERR_USAGE;
-  if (const int rc = points_refuse(h, "st_points_summary_reserve")) return rc;
-  if (keep > 16384) { h->err = "st_points_summary_reserve: at most 16384 saved draws (one point's draws are sorted in one workgroup's LDS)"; return ST_ERR_UNSUPPORTED; }
-  PointSet *ps = h->pts;
-  HCHK(h, hipSetDevice(h->device));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  ps->d_keep_w.free(); ps->d_keep_yhat.free();
-  ps->keep_cap = 0; ps->n_kept = 0;
-  if (keep == 0 || ps->n == 0) return ST_OK;
-  HCHK(h, ps->d_keep_w.alloc((size_t)keep * ps->n));
-  if (ps->has_X) HCHK(h, ps->d_keep_yhat.alloc((size_t)keep * ps->n));
-  ps->keep_cap = keep;
-  return ST_OK;
-}
-
-// st_points_accumulate and st_points_accumulate_joint (cond_cov, cond_chol: a joint set's packed outputs, NULL otherwise)
-static int points_accumulate(st_handle h, uint64_t seed, uint32_t iter, double *w_new, double *cond_mean, double *cond_var, double *yhat_new,
-                             double *cond_cov, double *cond_chol) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = points_refuse(h, "st_points_accumulate")) return rc;
-  if (h->theta[0].empty()) { h->err = "st_points_accumulate before st_factor(slot 0)"; return ST_ERR_USAGE; }
-  if (h->factor_open) { h->err = "st_points_accumulate between st_factor_enqueue and st_factor_finish"; return ST_ERR_USAGE; }
-  PointSet *ps = h->pts;
-  if (yhat_new && !ps->has_X) { h->err = "st_points_accumulate: yhat_new needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
-  if (!ps->d_acc.p && ps->n > 0) { const int rc0 = st_points_summary_reset(h); if (rc0) return rc0; }
-  ps->route_mask = 0;
-  if (ps->n == 0) { ps->n_acc += 1; return ST_OK; }
-  HCHK(h, hipSetDevice(h->device));
-  const long long n = ps->n;
-  const bool out[4] = {true, true, true, ps->has_X};
-  int rc = ps->joint ? points_run_joint(h, ps, 0, false, seed, iter, out, true, cond_chol != nullptr, "st_points_accumulate")
-                     : points_run(h, ps, 0, false, seed, iter, out, "st_points_accumulate");
-  if (rc) return rc;
-  const double *o = ps->d_out.p;
-  if (ps->joint) {   // the pair accumulators, before k_points_acc moves the Welford means
-    PointsPairArgs B;
-    B.mean = o + n; B.cov = ps->d_jout.p; B.acc = ps->d_acc.p; B.pacc = ps->d_pacc.p; B.groups = ps->d_jgroups.p; B.members = ps->d_jmem.p;
-    B.pt_grp = ps->d_pt_grp.p; B.pt_a = ps->d_pt_a.p; B.count = (double)(ps->n_acc + 1); B.n = n; B.cov_total = ps->cov_total;
-    ProfScope pscope(h, 6);
-    const int e = points_pair_acc_launch(B, h->stream);
-    if (e) { h->err = std::string("st_points_accumulate launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
-  }
-  PointsAccArgs A;
-  A.w = o; A.mean = o + n; A.var = o + 2 * n; A.yhat = ps->has_X ? o + 3 * n : nullptr;
-  A.acc = ps->d_acc.p;
-  const bool keep = ps->n_kept < ps->keep_cap;
-  A.keep_w = keep ? ps->d_keep_w.p + (size_t)ps->n_kept * n : nullptr;
-  A.keep_yhat = (keep && ps->has_X) ? ps->d_keep_yhat.p + (size_t)ps->n_kept * n : nullptr;
-  A.count = (double)(ps->n_acc + 1);
-  A.n = n;
-  {
-    ProfScope pscope(h, 6);
-    const int e = points_acc_launch(A, h->stream);
-    if (e) { h->err = std::string("st_points_accumulate launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
-  }
-  ps->n_acc += 1;
-  if (keep) ps->n_kept += 1;
-  double *dst[4] = {w_new, cond_mean, cond_var, yhat_new};
-  bool copied = false;
-  for (int k = 0; k < 4; ++k)
-    if (dst[k]) { HCHK(h, hipMemcpyAsync(dst[k], o + (size_t)k * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream)); copied = true; }
-  const size_t cb = (size_t)ps->cov_total * sizeof(double);
-  if (cond_cov) { HCHK(h, hipMemcpyAsync(cond_cov, ps->d_jout.p, cb, hipMemcpyDeviceToHost, h->stream)); copied = true; }
-  if (cond_chol) { HCHK(h, hipMemcpyAsync(cond_chol, ps->d_jout.p + ps->cov_total, cb, hipMemcpyDeviceToHost, h->stream)); copied = true; }
-  if (copied) HCHK(h, hipStreamSynchronize(h->stream));
-  return ST_OK;
-}
-
-extern "C" int st_points_accumulate(st_handle h, uint64_t seed, uint32_t iter, double *w_new, double *cond_mean, double *cond_var,
-                                    double *yhat_new) {
-  return points_accumulate(h, seed, iter, w_new, cond_mean, cond_var, yhat_new, nullptr, nullptr);
-}
-
-extern "C" int st_points_accumulate_joint(st_handle h, uint64_t seed, uint32_t iter, double *w_new, double *cond_mean, double *cond_cov,
-                                          double *cond_chol, double *yhat_new) {
-  if (!h) return ST_ERR_USAGE;
-  if (h->pts && !h->pts->joint) { h->err = "st_points_accumulate_joint before st_points_set_joint"; return ST_ERR_USAGE; }
-  return points_accumulate(h, seed, iter, w_new, cond_mean, nullptr, yhat_new, cond_cov, cond_chol);
-}
-
-extern "C" int st_points_summary_get_cov(st_handle h, double *cov) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = points_refuse(h, "st_points_summary_get_cov")) return rc;
-  PointSet *ps = h->pts;
-  if (!ps->joint) { h->err = "st_points_summary_get_cov before st_points_set_joint"; return ST_ERR_USAGE; }
-  if (ps->n_acc == 0) { h->err = "st_points_summary_get_cov: no iteration accumulated"; return ST_ERR_USAGE; }
-  if (ps->cov_total == 0 || !cov) return ST_OK;
-  HCHK(h, hipSetDevice(h->device));
-  const long long tot = ps->cov_total;
-  std::vector<double> acc((size_t)2 * tot);
-  HCHK(h, hipMemcpyAsync(acc.data(), ps->d_pacc.p, acc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  const double cnt = (double)ps->n_acc;
-  for (long long k = 0; k < ps->n_joint; ++k) {
-    const long long o = ps->j_off[k], g = ps->j_mptr[k + 1] - ps->j_mptr[k];
-    for (long long a = 0; a < g; ++a)
-      for (long long b = 0; b <= a; ++b) {
-        const long long e = o + a + b * g;
-        const double v = acc[e] / cnt + acc[tot + e] / cnt;   // mean conditional covariance + covariance of the conditional means
-        cov[e] = v; cov[o + b + a * g] = v;
-      }
-  }
-  return ST_OK;
-}
-
-extern "C" int st_points_summary_get(st_handle h, double *mean, double *var, double *w_mean, double *yhat_mean, int64_t *n_accumulated) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = points_refuse(h, "st_points_summary_get")) return rc;
-  PointSet *ps = h->pts;
-  if (n_accumulated) *n_accumulated = ps->n_acc;
-  if (ps->n_acc == 0) { h->err = "st_points_summary_get: no iteration accumulated"; return ST_ERR_USAGE; }
-  if (yhat_mean && !ps->has_X) { h->err = "st_points_summary_get: yhat_mean needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
-  const long long n = ps->n;
-  if (n == 0) return ST_OK;
-  HCHK(h, hipSetDevice(h->device));
-  std::vector<double> acc((size_t)PA_NACC * n);
-  HCHK(h, hipMemcpyAsync(acc.data(), ps->d_acc.p, acc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  const double cnt = (double)ps->n_acc;
-  const double *a = acc.data();
-  for (long long i = 0; i < n; ++i) {
-    if (mean) mean[i] = a[PA_MEAN * n + i];
-    if (var) var[i] = a[PA_VAR * n + i] / cnt + a[PA_M2 * n + i] / cnt;   // mean conditional variance + variance of the conditional means
-    if (w_mean) w_mean[i] = a[PA_W * n + i] / cnt;
-    if (yhat_mean) yhat_mean[i] = a[PA_YHAT * n + i] / cnt;
-  }
-  return ST_OK;
-}
-
-extern "C" int st_points_summary_quantile(st_handle h, double q, double *w_q, double *yhat_q) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = points_refuse(h, "st_points_summary_quantile")) return rc;
-  if (!(q >= 0.0 && q <= 1.0)) { h->err = "st_points_summary_quantile: q must lie in [0, 1]"; return ST_ERR_USAGE; }
-  PointSet *ps = h->pts;
-  if (ps->n_kept == 0) { h->err = "st_points_summary_quantile: no draw stored (call st_points_summary_reserve before the saved iterations)"; return ST_ERR_USAGE; }
-  if (yhat_q && !ps->has_X) { h->err = "st_points_summary_quantile: yhat_q needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
-  HCHK(h, hipSetDevice(h->device));
-  const long long n = ps->n;
-  int Kpad = 2;
-  while (Kpad < ps->n_kept) Kpad <<= 1;
-  const int R = std::max(1, std::min(8, (int)(128 * 1024 / ((size_t)Kpad * 8))));
-  const size_t lds = (size_t)R * Kpad * sizeof(double);
-  (void)hipFuncSetAttribute((const void *)k_qtile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_limit);
-  for (int which = 0; which < 2; ++which) {
-    double *dst = which == 0 ? w_q : yhat_q;
-    if (!dst) continue;
-    QtArgs A;
-    A.draws = which == 0 ? ps->d_keep_w.p : ps->d_keep_yhat.p; A.n = n; A.keep = (int)ps->n_kept; A.Kpad = Kpad; A.R = R; A.q = q;
-    A.out = ps->d_out.p;   // scratch: the next st_points_accumulate rewrites it anyway
-    hipLaunchKernelGGL(k_qtile, dim3((unsigned)((n + R - 1) / R)), dim3(NT), lds, h->stream, A);
-    HCHK(h, hipGetLastError());
-    HCHK(h, hipMemcpyAsync(dst, ps->d_out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HCHK(h, hipStreamSynchronize(h->stream));
-  }
-  return ST_OK;
-}
 
 // ---- prior simulation from slot 0 (st_simulate; the kernels and their launcher live in k_simulate.hip) ----
 static int sim_pad(int nd) { int p = 1; while (p < nd) p <<= 1; return p; }

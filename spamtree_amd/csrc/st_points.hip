@@ -1,0 +1,408 @@
+// st_points.hip -- the C-ABI of new-point prediction (st_points_*): the device step of st_points_set / st_points_set_joint, predict,
+// accumulate, the summaries and quantiles.  predict_points.hpp and predict_joint.hpp have the model; the launch structures of a
+// point set are built without a device call in points_layout.cpp; the kernels and their launchers live in k_predict.hip,
+// k_predict_joint.hip and k_points_acc.hip (k_qtile in k_misc.hip).
+#include <memory>
+
+#include "st_handle.hpp"
+#include "misc_kernels.hpp"
+#include "points_layout.hpp"
+
+struct PointSet : PointsCounts {
+  long long n = 0;
+  bool has_X = false;
+  int route_mask = 0;
+  DevBuf<double> d_px, d_py, d_X, d_z, d_out, d_scratch;
+  DevBuf<int> d_pmv, d_chain_blk, d_pt_chain, d_gen;
+  DevBuf<long long> d_order;
+  DevBuf<PtChain> d_chains;
+  DevBuf<PtTile> d_tiles;
+  // st_points_accumulate: PA_NACC x n accumulators, and with st_points_summary_reserve the draws themselves, [keep][n] each
+  DevBuf<double> d_acc, d_keep_w, d_keep_yhat;
+  long long n_acc = 0, keep_cap = 0, n_kept = 0;
+  // st_points_set_joint: the joint groups in layout order (first appearance), their packing into slots and the pair accumulators
+  bool joint = false;
+  std::vector<int64_t> j_off, j_mptr, j_mem;   // packed block offsets (n_joint + 1), member list pointers (n_joint + 1), members
+  DevBuf<PtJoint> d_jgroups;
+  DevBuf<long long> d_jmem;
+  DevBuf<PtCol> d_jcols;
+  DevBuf<PtTile> d_jtiles;
+  DevBuf<int> d_jgen, d_pt_grp, d_pt_a;
+  DevBuf<double> d_jout, d_jscratch, d_pacc;   // cov and chol of the last call (2 x cov_total); scratch; pair accumulators
+};
+
+void points_free(st_handle_s *h) {
+  delete h->pts;   // its device buffers free themselves
+  h->pts = nullptr;
+}
+
+// ---- st_points_set, the device step ("st_points_set in two steps"): the layout's lists go to the device, its counts
+// into the point set; of the lists only j_off, j_mptr and j_mem stay on the host
+static int points_upload(st_handle h, PointSet *ps, const PointsLayout &L, const double *coords, const int64_t *mv, const double *X) {
+  const long long n_new = ps->n;
+  std::vector<double> px(coords, coords + n_new), py(coords + n_new, coords + 2 * n_new);
+  std::vector<int> pmv(n_new);
+  for (long long i = 0; i < n_new; ++i) pmv[i] = (int)(mv[i] - 1);
+  HCHK(h, ps->d_px.upload(px)); HCHK(h, ps->d_py.upload(py)); HCHK(h, ps->d_pmv.upload(pmv));
+  HCHK(h, ps->d_order.upload(L.order)); HCHK(h, ps->d_pt_chain.upload(L.pt_chain)); HCHK(h, ps->d_chains.upload(L.chains));
+  HCHK(h, upload_or_dummy(ps->d_chain_blk, L.chain_blk)); HCHK(h, upload_or_dummy(ps->d_tiles, L.tiles)); HCHK(h, upload_or_dummy(ps->d_gen, L.gen));
+  HCHK(h, ps->d_z.alloc(n_new));
+  HCHK(h, ps->d_out.alloc((size_t)4 * n_new));
+  if (ps->grid_generic > 0) HCHK(h, ps->d_scratch.alloc((size_t)ps->grid_generic * 2 * ps->scratch_stride));
+  if (X) {
+    std::vector<double> xv(X, X + (size_t)n_new * h->p);
+    HCHK(h, ps->d_X.upload(xv));
+    ps->has_X = true;
+  }
+  return ST_OK;
+}
+
+static int points_upload_joint(st_handle h, PointSet *ps, const PointsLayout &L) {
+  std::vector<long long> jmem_ll(ps->j_mem.begin(), ps->j_mem.end());
+  HCHK(h, ps->d_jgroups.upload(L.groups)); HCHK(h, ps->d_jmem.upload(jmem_ll)); HCHK(h, upload_or_dummy(ps->d_jtiles, L.jtiles));
+  HCHK(h, ps->d_jcols.upload(L.jcols)); HCHK(h, upload_or_dummy(ps->d_jgen, L.jgen)); HCHK(h, ps->d_pt_grp.upload(L.pt_grp)); HCHK(h, ps->d_pt_a.upload(L.pt_a));
+  HCHK(h, ps->d_jout.alloc((size_t)2 * ps->cov_total));
+  if (ps->jgrid_generic > 0) HCHK(h, ps->d_jscratch.alloc((size_t)ps->jgrid_generic * PJ_SCRATCH_COLS * ps->scratch_stride));
+  return ST_OK;
+}
+
+// st_points_set (joint_id NULL) and st_points_set_joint: a refusal of the layout leaves the previous point set in place, a
+// failing HIP call none
+static int points_set_impl(st_handle h, int64_t n_new, const double *coords, const int64_t *mv, const int64_t *anchor, const double *X,
+                           const int64_t *joint_id) {
+  if (!h) return ST_ERR_USAGE;
+  PointsLayout L;
+  if (const int rc = points_layout(*h, n_new, coords, mv, anchor, joint_id, L, h->err)) return rc;
+  HCHK(h, hipSetDevice(h->device));
+  points_free(h);
+  std::unique_ptr<PointSet> ps(new PointSet());   // the handle takes it once every upload has succeeded
+  static_cast<PointsCounts &>(*ps) = L;
+  ps->n = n_new;
+  ps->joint = joint_id != nullptr;
+  ps->j_off = std::move(L.j_off); ps->j_mptr = std::move(L.j_mptr); ps->j_mem = std::move(L.j_mem);
+  if (n_new > 0) {
+    if (const int rc = points_upload(h, ps.get(), L, coords, mv, X)) return rc;
+    if (joint_id)
+      if (const int rc = points_upload_joint(h, ps.get(), L)) return rc;
+  }
+  h->pts = ps.release();
+  return ST_OK;
+}
+
+extern "C" int st_points_set(st_handle h, int64_t n_new, const double *coords, const int64_t *mv, const int64_t *anchor, const double *X) {
+  return points_set_impl(h, n_new, coords, mv, anchor, X, nullptr);
+}
+
+extern "C" int st_points_set_joint(st_handle h, int64_t n_new, const double *coords, const int64_t *mv, const int64_t *anchor, const double *X,
+                                   const int64_t *joint_id) {
+  return points_set_impl(h, n_new, coords, mv, anchor, X, joint_id);
+}
+
+extern "C" int st_points_joint_layout(st_handle h, int64_t *n_joint, int64_t *offsets, int64_t *member_ptr, int64_t *members) {
+  if (!h) return ST_ERR_USAGE;
+  const PointSet *ps = h->pts;
+  if (!ps || !ps->joint) { h->err = "st_points_joint_layout before st_points_set_joint"; return ST_ERR_USAGE; }
+  if (n_joint) *n_joint = ps->n_joint;
+  if (offsets) std::copy(ps->j_off.begin(), ps->j_off.end(), offsets);
+  if (member_ptr) std::copy(ps->j_mptr.begin(), ps->j_mptr.end(), member_ptr);
+  if (members) std::copy(ps->j_mem.begin(), ps->j_mem.end(), members);
+  return ST_OK;
+}
+
+// What every entry point that works on the point set refuses first.  need_factor: it reads slot 0; joint: the set must be one of
+// st_points_set_joint
+static int points_refuse(st_handle h, const char *who, bool need_factor = false, bool joint = false) {
+  if (h->limited || h->world > 1) {
+    h->err = std::string(who) + ": limited_tree and multi-GPU handles are not supported (out of scope)";
+    return ST_ERR_UNSUPPORTED;
+  }
+  if (!h->pts || (joint && !h->pts->joint)) { h->err = std::string(who) + (joint ? " before st_points_set_joint" : " before st_points_set"); return ST_ERR_USAGE; }
+  if (need_factor && h->theta[0].empty()) { h->err = std::string(who) + " before st_factor(slot 0)"; return ST_ERR_USAGE; }
+  if (need_factor && h->factor_open) { h->err = std::string(who) + " between st_factor_enqueue and st_factor_finish"; return ST_ERR_USAGE; }
+  return ST_OK;
+}
+
+// The outputs of the last launch to the caller: dst[k] from the k-th n doubles of d_out, the packed cov and chol from d_jout
+// (any may be NULL); waits for the stream if it copied anything, or if `always`
+static int points_copy_out(st_handle h, PointSet *ps, double *const dst[4], double *cond_cov, double *cond_chol, bool always) {
+  const long long n = ps->n;
+  bool copied = always;
+  for (int k = 0; k < 4; ++k)
+    if (dst[k]) { HCHK(h, hipMemcpyAsync(dst[k], ps->d_out.p + (size_t)k * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream)); copied = true; }
+  const size_t cb = (size_t)ps->cov_total * sizeof(double);
+  if (cond_cov) { HCHK(h, hipMemcpyAsync(cond_cov, ps->d_jout.p, cb, hipMemcpyDeviceToHost, h->stream)); copied = true; }
+  if (cond_chol) { HCHK(h, hipMemcpyAsync(cond_chol, ps->d_jout.p + ps->cov_total, cb, hipMemcpyDeviceToHost, h->stream)); copied = true; }
+  if (copied) HCHK(h, hipStreamSynchronize(h->stream));
+  return ST_OK;
+}
+
+// launches the k_points_* routes of the point set on slot 0 and the current w / beta / tausq_inv into ps->d_out (w, mean, var,
+// yhat: n doubles each, caller order; out[k] false: that output is not written).  No synchronisation.
+static void points_args(st_handle h, PointSet *ps, int mode, bool use_z, uint64_t seed, uint32_t iter, const bool out[4], PointsArgs &A) {
+  const long long n = ps->n;
+  double *o = ps->d_out.p;
+  std::memset(&A, 0, sizeof(A));
+  A.blks = h->d_blks.p; A.chain_blk = ps->d_chain_blk.p; A.chains = ps->d_chains.p; A.tiles = ps->d_tiles.p; A.ntiles = 0;
+  A.gen_list = ps->d_gen.p; A.ngen = ps->grid_generic > 0 ? (int)(ps->d_gen.n) : 0;
+  A.pt_chain = ps->d_pt_chain.p; A.order = ps->d_order.p; A.px = ps->d_px.p; A.py = ps->d_py.p; A.pmv = ps->d_pmv.p;
+  A.cx = h->d_cx.p; A.cy = h->d_cy.p; A.mv = h->d_mv.p; A.w = h->d_w.p; A.panels = h->d_panels[h->slot_map[0]].p;
+  A.z = use_z ? ps->d_z.p : nullptr; A.seed = seed; A.iter = iter; A.mode = mode;
+  A.X = ps->has_X ? ps->d_X.p : nullptr; A.B = h->d_B.p; A.tsq_inv = h->d_tsq.p; A.p = h->p; A.n_new = n;
+  A.w_new = out[0] ? o : nullptr; A.mean = out[1] ? o + n : nullptr; A.var = out[2] ? o + 2 * n : nullptr;
+  A.yhat = out[3] ? o + 3 * n : nullptr;
+  A.scratch = ps->d_scratch.p; A.scratch_stride = ps->scratch_stride;
+}
+
+static int points_run(st_handle h, PointSet *ps, int mode, bool use_z, uint64_t seed, uint32_t iter, const bool out[4], const char *who) {
+  CovPar cp;
+  int rc = make_covpar(h, h->theta[0].data(), (int)h->theta[0].size(), &cp);
+  if (rc) return rc;
+  PointsArgs A;
+  points_args(h, ps, mode, use_z, seed, iter, out, A);
+  PointsLaunch L;
+  L.ntile128 = ps->ntile128; L.ntile256 = ps->ntile256; L.grid_generic = ps->grid_generic;
+  ProfScope pscope(h, 6);
+  const int e = points_launch(L, A, cp, h->stream, &ps->route_mask);
+  if (e) { h->err = std::string(who) + " launch: " + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+  return ST_OK;
+}
+
+extern "C" int st_points_predict(st_handle h, int mode, const double *z, uint64_t seed, uint32_t iter, double *w_new, double *cond_mean,
+                                 double *cond_var, double *yhat_new) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_predict", true)) return rc;
+  if (mode != 0 && mode != 1) { h->err = "st_points_predict: mode must be 0 (draw) or 1 (conditional mean)"; return ST_ERR_USAGE; }
+  PointSet *ps = h->pts;
+  if (yhat_new && !ps->has_X) { h->err = "st_points_predict: yhat_new needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  ps->route_mask = 0;
+  if (ps->n == 0) return ST_OK;
+  HCHK(h, hipSetDevice(h->device));
+  const long long n = ps->n;
+  if (z && mode == 0) HCHK(h, hipMemcpyAsync(ps->d_z.p, z, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  double *const dst[4] = {w_new, cond_mean, cond_var, yhat_new};
+  const bool out[4] = {w_new != nullptr, cond_mean != nullptr, cond_var != nullptr, yhat_new != nullptr};
+  const int rc = points_run(h, ps, mode, z && mode == 0, seed, iter, out, "st_points_predict");
+  if (rc) return rc;
+  return points_copy_out(h, ps, dst, nullptr, nullptr, true);
+}
+
+// the joint routes of the point set (st_points_set_joint) into ps->d_out as points_run, plus cov and chol into ps->d_jout
+static int points_run_joint(st_handle h, PointSet *ps, int mode, bool use_z, uint64_t seed, uint32_t iter, const bool out[4], bool want_cov,
+                            bool want_chol, const char *who) {
+  CovPar cp;
+  int rc = make_covpar(h, h->theta[0].data(), (int)h->theta[0].size(), &cp);
+  if (rc) return rc;
+  JointArgs J;
+  std::memset(&J, 0, sizeof(J));
+  points_args(h, ps, mode, use_z, seed, iter, out, J.P);
+  J.P.tiles = ps->d_jtiles.p;
+  J.P.scratch = ps->d_jscratch.p;
+  J.groups = ps->d_jgroups.p; J.members = ps->d_jmem.p; J.cols = ps->d_jcols.p;
+  J.gen_groups = ps->d_jgen.p; J.ngen_groups = ps->jgrid_generic > 0 ? (int)ps->d_jgen.n : 0;
+  J.cov = want_cov ? ps->d_jout.p : nullptr; J.chol = want_chol ? ps->d_jout.p + ps->cov_total : nullptr;
+  JointLaunch L;
+  L.ntile128 = ps->jtile128; L.ntile256 = ps->jtile256; L.grid_generic = ps->jgrid_generic;
+  ProfScope pscope(h, 6);
+  const int e = points_joint_launch(L, J, cp, h->stream, &ps->route_mask);
+  if (e) { h->err = std::string(who) + " launch: " + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+  return ST_OK;
+}
+
+extern "C" int st_points_predict_joint(st_handle h, int mode, const double *z, uint64_t seed, uint32_t iter, double *w_new, double *cond_mean,
+                                       double *cond_cov, double *cond_chol, double *yhat_new) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_predict_joint", true, true)) return rc;
+  if (mode != 0 && mode != 1) { h->err = "st_points_predict_joint: mode must be 0 (draw) or 1 (conditional mean)"; return ST_ERR_USAGE; }
+  PointSet *ps = h->pts;
+  if (yhat_new && !ps->has_X) { h->err = "st_points_predict_joint: yhat_new needs the regressors X of st_points_set_joint"; return ST_ERR_USAGE; }
+  ps->route_mask = 0;
+  if (ps->n == 0) return ST_OK;
+  HCHK(h, hipSetDevice(h->device));
+  const long long n = ps->n;
+  if (z && mode == 0) HCHK(h, hipMemcpyAsync(ps->d_z.p, z, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  const bool out[4] = {w_new != nullptr, cond_mean != nullptr, false, yhat_new != nullptr};
+  const int rc = points_run_joint(h, ps, mode, z && mode == 0, seed, iter, out, cond_cov != nullptr, cond_chol != nullptr, "st_points_predict_joint");
+  if (rc) return rc;
+  double *const dst[4] = {w_new, cond_mean, nullptr, yhat_new};
+  return points_copy_out(h, ps, dst, cond_cov, cond_chol, true);
+}
+
+extern "C" int st_points_info(st_handle h, int32_t *route, int64_t *n_groups, double *alg_bytes, double *flops) {
+  if (!h) return ST_ERR_USAGE;
+  const PointSet *ps = h->pts;
+  const bool jr = ps && (ps->route_mask >> (PP_ROUTE_JOINT_MFMA128 - 1)) != 0;   // the last call took the joint routes
+  if (route) *route = ps ? ps->route_mask : 0;
+  if (n_groups) *n_groups = ps ? ps->n_chains : 0;
+  if (alg_bytes) *alg_bytes = ps ? (jr ? ps->j_alg_bytes : ps->alg_bytes) : 0.0;
+  if (flops) *flops = ps ? (jr ? ps->j_flops : ps->flops) : 0.0;
+  return ST_OK;
+}
+
+extern "C" const char *st_points_route_name(int32_t code) {
+  return code < PP_ROUTE_COUNT ? points_route_name(code) : points_joint_route_name(code);
+}
+
+// ---- predictive summaries of the point set over saved iterations (st_points_accumulate; the kernel lives in k_points_acc.hip) ----
+extern "C" int st_points_summary_reset(st_handle h) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_summary_reset")) return rc;
+  PointSet *ps = h->pts;
+  HCHK(h, hipSetDevice(h->device));
+  const size_t cnt = (size_t)PA_NACC * ps->n;
+  if (cnt > 0 && !ps->d_acc.p) HCHK(h, ps->d_acc.alloc(cnt));
+  if (cnt > 0) HCHK(h, hipMemsetAsync(ps->d_acc.p, 0, cnt * sizeof(double), h->stream));
+  const size_t pcnt = (size_t)2 * ps->cov_total;
+  if (pcnt > 0 && !ps->d_pacc.p) HCHK(h, ps->d_pacc.alloc(pcnt));
+  if (pcnt > 0) HCHK(h, hipMemsetAsync(ps->d_pacc.p, 0, pcnt * sizeof(double), h->stream));
+  ps->n_acc = 0; ps->n_kept = 0;
+  return ST_OK;
+}
+
+extern "C" int st_points_summary_reserve(st_handle h, int64_t keep) {
+  if (!h || keep < 0) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_summary_reserve")) return rc;
+  if (keep > 16384) { h->err = "st_points_summary_reserve: at most 16384 saved draws (one point's draws are sorted in one workgroup's LDS)"; return ST_ERR_UNSUPPORTED; }
+  PointSet *ps = h->pts;
+  HCHK(h, hipSetDevice(h->device));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  ps->d_keep_w.free(); ps->d_keep_yhat.free();
+  ps->keep_cap = 0; ps->n_kept = 0;
+  if (keep == 0 || ps->n == 0) return ST_OK;
+  HCHK(h, ps->d_keep_w.alloc((size_t)keep * ps->n));
+  if (ps->has_X) HCHK(h, ps->d_keep_yhat.alloc((size_t)keep * ps->n));
+  ps->keep_cap = keep;
+  return ST_OK;
+}
+
+// st_points_accumulate and st_points_accumulate_joint (cond_cov, cond_chol: a joint set's packed outputs, NULL otherwise)
+static int points_accumulate(st_handle h, uint64_t seed, uint32_t iter, double *w_new, double *cond_mean, double *cond_var, double *yhat_new,
+                             double *cond_cov, double *cond_chol) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_accumulate", true)) return rc;
+  PointSet *ps = h->pts;
+  if (yhat_new && !ps->has_X) { h->err = "st_points_accumulate: yhat_new needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  if (!ps->d_acc.p && ps->n > 0) { const int rc0 = st_points_summary_reset(h); if (rc0) return rc0; }
+  ps->route_mask = 0;
+  if (ps->n == 0) { ps->n_acc += 1; return ST_OK; }
+  HCHK(h, hipSetDevice(h->device));
+  const long long n = ps->n;
+  const bool out[4] = {true, true, true, ps->has_X};
+  int rc = ps->joint ? points_run_joint(h, ps, 0, false, seed, iter, out, true, cond_chol != nullptr, "st_points_accumulate")
+                     : points_run(h, ps, 0, false, seed, iter, out, "st_points_accumulate");
+  if (rc) return rc;
+  const double *o = ps->d_out.p;
+  if (ps->joint) {   // the pair accumulators, before k_points_acc moves the Welford means
+    PointsPairArgs B;
+    B.mean = o + n; B.cov = ps->d_jout.p; B.acc = ps->d_acc.p; B.pacc = ps->d_pacc.p; B.groups = ps->d_jgroups.p; B.members = ps->d_jmem.p;
+    B.pt_grp = ps->d_pt_grp.p; B.pt_a = ps->d_pt_a.p; B.count = (double)(ps->n_acc + 1); B.n = n; B.cov_total = ps->cov_total;
+    ProfScope pscope(h, 6);
+    const int e = points_pair_acc_launch(B, h->stream);
+    if (e) { h->err = std::string("st_points_accumulate launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+  }
+  PointsAccArgs A;
+  A.w = o; A.mean = o + n; A.var = o + 2 * n; A.yhat = ps->has_X ? o + 3 * n : nullptr;
+  A.acc = ps->d_acc.p;
+  const bool keep = ps->n_kept < ps->keep_cap;
+  A.keep_w = keep ? ps->d_keep_w.p + (size_t)ps->n_kept * n : nullptr;
+  A.keep_yhat = (keep && ps->has_X) ? ps->d_keep_yhat.p + (size_t)ps->n_kept * n : nullptr;
+  A.count = (double)(ps->n_acc + 1);
+  A.n = n;
+  {
+    ProfScope pscope(h, 6);
+    const int e = points_acc_launch(A, h->stream);
+    if (e) { h->err = std::string("st_points_accumulate launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+  }
+  ps->n_acc += 1;
+  if (keep) ps->n_kept += 1;
+  double *const dst[4] = {w_new, cond_mean, cond_var, yhat_new};
+  return points_copy_out(h, ps, dst, cond_cov, cond_chol, false);
+}
+
+extern "C" int st_points_accumulate(st_handle h, uint64_t seed, uint32_t iter, double *w_new, double *cond_mean, double *cond_var,
+                                    double *yhat_new) {
+  return points_accumulate(h, seed, iter, w_new, cond_mean, cond_var, yhat_new, nullptr, nullptr);
+}
+
+extern "C" int st_points_accumulate_joint(st_handle h, uint64_t seed, uint32_t iter, double *w_new, double *cond_mean, double *cond_cov,
+                                          double *cond_chol, double *yhat_new) {
+  if (!h) return ST_ERR_USAGE;
+  if (h->pts && !h->pts->joint) { h->err = "st_points_accumulate_joint before st_points_set_joint"; return ST_ERR_USAGE; }
+  return points_accumulate(h, seed, iter, w_new, cond_mean, nullptr, yhat_new, cond_cov, cond_chol);
+}
+
+extern "C" int st_points_summary_get_cov(st_handle h, double *cov) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_summary_get_cov")) return rc;
+  PointSet *ps = h->pts;
+  if (!ps->joint) { h->err = "st_points_summary_get_cov before st_points_set_joint"; return ST_ERR_USAGE; }
+  if (ps->n_acc == 0) { h->err = "st_points_summary_get_cov: no iteration accumulated"; return ST_ERR_USAGE; }
+  if (ps->cov_total == 0 || !cov) return ST_OK;
+  HCHK(h, hipSetDevice(h->device));
+  const long long tot = ps->cov_total;
+  std::vector<double> acc((size_t)2 * tot);
+  HCHK(h, hipMemcpyAsync(acc.data(), ps->d_pacc.p, acc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  const double cnt = (double)ps->n_acc;
+  for (long long k = 0; k < ps->n_joint; ++k) {
+    const long long o = ps->j_off[k], g = ps->j_mptr[k + 1] - ps->j_mptr[k];
+    for (long long a = 0; a < g; ++a)
+      for (long long b = 0; b <= a; ++b) {
+        const long long e = o + a + b * g;
+        const double v = acc[e] / cnt + acc[tot + e] / cnt;   // mean conditional covariance + covariance of the conditional means
+        cov[e] = v; cov[o + b + a * g] = v;
+      }
+  }
+  return ST_OK;
+}
+
+extern "C" int st_points_summary_get(st_handle h, double *mean, double *var, double *w_mean, double *yhat_mean, int64_t *n_accumulated) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_summary_get")) return rc;
+  PointSet *ps = h->pts;
+  if (n_accumulated) *n_accumulated = ps->n_acc;
+  if (ps->n_acc == 0) { h->err = "st_points_summary_get: no iteration accumulated"; return ST_ERR_USAGE; }
+  if (yhat_mean && !ps->has_X) { h->err = "st_points_summary_get: yhat_mean needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  const long long n = ps->n;
+  if (n == 0) return ST_OK;
+  HCHK(h, hipSetDevice(h->device));
+  std::vector<double> acc((size_t)PA_NACC * n);
+  HCHK(h, hipMemcpyAsync(acc.data(), ps->d_acc.p, acc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  const double cnt = (double)ps->n_acc;
+  const double *a = acc.data();
+  for (long long i = 0; i < n; ++i) {
+    if (mean) mean[i] = a[PA_MEAN * n + i];
+    if (var) var[i] = a[PA_VAR * n + i] / cnt + a[PA_M2 * n + i] / cnt;   // mean conditional variance + variance of the conditional means
+    if (w_mean) w_mean[i] = a[PA_W * n + i] / cnt;
+    if (yhat_mean) yhat_mean[i] = a[PA_YHAT * n + i] / cnt;
+  }
+  return ST_OK;
+}
+
+extern "C" int st_points_summary_quantile(st_handle h, double q, double *w_q, double *yhat_q) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_summary_quantile")) return rc;
+  if (!(q >= 0.0 && q <= 1.0)) { h->err = "st_points_summary_quantile: q must lie in [0, 1]"; return ST_ERR_USAGE; }
+  PointSet *ps = h->pts;
+  if (ps->n_kept == 0) { h->err = "st_points_summary_quantile: no draw stored (call st_points_summary_reserve before the saved iterations)"; return ST_ERR_USAGE; }
+  if (yhat_q && !ps->has_X) { h->err = "st_points_summary_quantile: yhat_q needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  HCHK(h, hipSetDevice(h->device));
+  const long long n = ps->n;
+  int Kpad = 2;
+  while (Kpad < ps->n_kept) Kpad <<= 1;
+  const int R = std::max(1, std::min(8, (int)(128 * 1024 / ((size_t)Kpad * 8))));
+  const size_t lds = (size_t)R * Kpad * sizeof(double);
+  (void)hipFuncSetAttribute((const void *)k_qtile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_limit);
+  for (int which = 0; which < 2; ++which) {
+    double *dst = which == 0 ? w_q : yhat_q;
+    if (!dst) continue;
+    QtArgs A;
+    A.draws = which == 0 ? ps->d_keep_w.p : ps->d_keep_yhat.p; A.n = n; A.keep = (int)ps->n_kept; A.Kpad = Kpad; A.R = R; A.q = q;
+    A.out = ps->d_out.p;   // scratch: the next st_points_accumulate rewrites it anyway
+    hipLaunchKernelGGL(k_qtile, dim3((unsigned)((n + R - 1) / R)), dim3(NT), lds, h->stream, A);
+    HCHK(h, hipGetLastError());
+    HCHK(h, hipMemcpyAsync(dst, ps->d_out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HCHK(h, hipStreamSynchronize(h->stream));
+  }
+  return ST_OK;
+}

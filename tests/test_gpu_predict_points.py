@@ -242,3 +242,37 @@ def test_refusals_leave_the_handle_usable():
     assert rc == ST_ERR_UNSUPPORTED and b"limited_tree" in hl.lib.st_last_error(hl.h)
     assert hl.get_loglik_comps_w(0)
     hl.close()
+
+
+def test_a_refused_set_leaves_the_previous_point_set_in_place():
+    """st_points_set and st_points_set_joint refuse before they release the old set: after a bad margin and after a 17-member
+    joint group the next st_points_predict, without setting the points anew, gives the first one's outputs bit for bit."""
+    from spamtree_amd.predict import locate
+    import ctypes as C
+    pb = make_problem(side=20, q=1, seed=18, missing=0.1)
+    hm = fitted(pb, 19)
+    lib, h = hm.lib, hm.h
+    pts, mv = new_points(pb, 30, 20)
+    anchor = np.ascontiguousarray(locate(pb["topo"], pts, mv, device=0))
+    c, mv = np.asfortranarray(pts), np.ascontiguousarray(mv)
+    dp, ip = (lambda a: a.ctypes.data_as(C.POINTER(C.c_double))), (lambda a: a.ctypes.data_as(C.POINTER(C.c_int64)))
+    z = np.random.default_rng(21).standard_normal(30)
+
+    def predict():
+        out = np.full((4, 30), np.nan)
+        assert lib.st_points_predict(h, 0, dp(z), 1, 0, dp(out[0]), dp(out[1]), dp(out[2]), None) == 0
+        assert np.all(np.isfinite(out[:3]))
+        return out[:3].copy()
+
+    assert lib.st_points_set(h, 30, dp(c), ip(mv), ip(anchor), None) == 0
+    first = predict()
+    bad_mv = mv.copy()
+    bad_mv[3] = 2
+    assert lib.st_points_set(h, 30, dp(c), ip(bad_mv), ip(anchor), None) == ST_ERR_USAGE
+    assert b"margin of point 3" in lib.st_last_error(h)
+    labels = np.ascontiguousarray(np.concatenate([np.zeros(17), np.arange(1, 14)]).astype(np.int64))
+    same = np.ascontiguousarray(np.full(30, anchor[0]))
+    assert lib.st_points_set_joint(h, 30, dp(c), ip(mv), ip(same), None, ip(labels)) == ST_ERR_UNSUPPORTED
+    assert b"more than 16 members" in lib.st_last_error(h)
+    assert np.array_equal(predict(), first)
+    hm.close()

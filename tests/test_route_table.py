@@ -8,6 +8,7 @@ from tests import test_gpu_routes as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "spamtree_amd", "csrc", "spamtree_hip.hip")
+SRC_POINTS = os.path.join(ROOT, "spamtree_amd", "csrc", "st_points.hip")
 SRC_POINTS_ACC = os.path.join(ROOT, "spamtree_amd", "csrc", "k_points_acc.hip")
 
 # launched kernels without a route code that other tests compare with the oracle (or, for plumbing, check bit for bit);
@@ -38,7 +39,8 @@ def _norm(name):
 
 def launched_kernels():
     """Every instantiation named by a hipLaunchKernelGGL of the host code, the macro and template wrappers expanded."""
-    src = open(SRC).read() + open(SRC_POINTS_ACC).read()     # k_points_acc is launched from its own translation unit
+    # (st_points.hip: the C-ABI of new-point prediction; k_points_acc is launched from its own translation unit)
+    src = open(SRC).read() + open(SRC_POINTS).read() + open(SRC_POINTS_ACC).read()
     names = set()
     for m in re.finditer(r"hipLaunchKernelGGL\(\s*(\(\s*[A-Za-z_]\w*\s*<[^>]*>\s*\)|[A-Za-z_]\w*)", src):
         names.add(_norm(m.group(1).strip("() ")))
