@@ -1,6 +1,7 @@
 """ORACLE -- test infrastructure only.  Restatement of the reference's after-the-fact posterior summaries over the `keep`
 stored draws (/root/reference/src/list_mean.cpp): list_mean (:10-30) and list_qtile / cqtile / prctile_stl (:62-137).
-Parity unpinned (the reference ships no fixtures); checked in tests against numpy order statistics."""
+Pinned to the compiled reference source: tests/test_reference_binary.py compares both with list_mean.cpp itself
+(oracle/_ref/libspamtree_ref.so; list_qtile bitwise)."""
 import math
 
 import numpy as np

@@ -1,8 +1,15 @@
 """ORACLE -- test infrastructure only.  NumPy/SciPy FP64 restatement of spamtree's per-sweep hot path.
 
-STATUS: **parity unpinned**.  The reference (/root/reference, R package spamtree 0.2.1) ships no tests, no
-golden vectors and no recorded outputs, and it cannot be built here (needs R, Rcpp,
-RcppArmadillo, LAPACK/BLAS; none present, no network).  This restatement is therefore pinned only by
+STATUS: **pinned to compiled reference source for covariance_functions.{h,cpp} and mh_adapt.{h,cpp}; parity unpinned
+for the rest**.  Those two files (with list_mean.cpp and find_nan.cpp) compile unchanged against the stand-in
+oracle/refshim/RcppArmadillo.h (oracle/Makefile -> oracle/_ref/libspamtree_ref.so), and tests/test_reference_binary.py holds
+CovarianceParams, vec_to_symmat, cexpcov (reference_distance=True), C_base, mvCovAG20107, Covariancef, CrossCovarianceAG10,
+par_huvtransf_*, unif_bounds, calc_jacobian, do_I_accept and RAMAdapt of this module to that library (oracle/list_summaries.py
+likewise for list_mean.cpp).  What remains restatement only: spamtree_model.cpp, spamtree_fit.cpp, tree_dep.cpp and the R
+tree builder -- the reference (/root/reference, R package spamtree 0.2.1) ships no tests, no golden vectors and no recorded
+outputs, and as a package it cannot be built here (needs R, Rcpp, RcppArmadillo, LAPACK/BLAS) --
+and the last bits that depend on the reference's BLAS/LAPACK, which the stand-in's own matrix product and Cholesky replace
+(the "fma" flavour of the distance form is still only emulated).  The restatement of those parts is pinned only by
 (a) the dense brute-force identities in tests/test_oracle_identities.py (exact GP on a one-level tree, the
 treed-DAG precision matrix, the exact Gaussian full conditional of a block, inverse-Cholesky extension),
 (b) 50-digit mpmath values of the Apanasovich-Genton cross-covariance on the man-page inputs, and

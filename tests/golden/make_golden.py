@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Generates the committed golden vectors from the NumPy oracle (oracle/spamtree_oracle.py).
 
-The reference ships no fixtures and cannot be run here, so these vectors pin THIS
-repository's oracle against regressions and give the GPU path a device-independent target; they are not outputs
-of the reference.  Run from the repo root:  python tests/golden/make_golden.py
+These vectors are ORACLE outputs: the reference ships no fixtures and its model code cannot be built here (SURVEY.md
+section 8c), so they pin THIS repository's oracle against regressions and give the GPU path a device-independent target; they
+are not outputs of the reference.  Outputs of compiled reference source (covariance, adaptation helpers, summaries) are
+recorded by tests/golden/make_reference_golden.py into tests/golden/ref_*.npz.
+Run from the repo root:  python tests/golden/make_golden.py
 """
 import os
 import sys

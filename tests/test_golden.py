@@ -1,4 +1,5 @@
-"""Golden vectors (tests/golden/*.npz, made by tests/golden/make_golden.py from the NumPy oracle).
+"""Golden vectors (tests/golden/*.npz, made by tests/golden/make_golden.py from the NumPy oracle; the ref_*.npz next to them
+are recorded from compiled reference source and belong to tests/test_reference_binary.py and tests/test_gpu_reference_binary.py).
 
 CPU: the oracle and the OpenMP restatement reproduce them (pins both against regressions).
 GPU: the HIP path reproduces them through the C-ABI."""
@@ -8,7 +9,8 @@ import os
 import numpy as np
 import pytest
 
-GOLD = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "*.npz")))
+GOLD = sorted(f for f in glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "*.npz"))
+              if not os.path.basename(f).startswith("ref_"))
 REL = 1e-9
 
 

@@ -19,10 +19,12 @@ def dense_cov(pb, theta, rows=None):
     return so.Covariancef(pb["coords"], pb["mv_id"] - 1, rows, rows, cp, True)
 
 
-def dense_precision(pb, theta):
-    """Q = sum_u (I_u - H_u E_pa)' R_u^{-1} (I_u - H_u E_pa), R_u diagonal on non-reference levels."""
+def dense_precision(pb, theta, K=None):
+    """Q = sum_u (I_u - H_u E_pa)' R_u^{-1} (I_u - H_u E_pa), R_u diagonal on non-reference levels.  K: the full covariance
+    matrix to assemble it from (default: the oracle's at theta)."""
     n = pb["n"]
-    K = dense_cov(pb, theta)
+    K = dense_cov(pb, theta) if K is None else np.asarray(K, dtype=np.float64)
+    assert K.shape == (n, n)
     Q = np.zeros((n, n))
     logdet = 0.0
     labels = np.unique(pb["block_groups"])
