@@ -90,6 +90,32 @@ int stm_mcmc_points_joint(const st_problem *pb, const st_options *opt, const dou
                           double *new_w_mean, double *new_yhat_mean, double *new_w_q, double *new_yhat_q, int32_t *new_route,
                           double *new_cond_cov, double *new_cov);
 
+/* Linear functionals of the new-point predictions (include/spamtree_hip.h, st_points_functionals_*).  stm_points_functionals_set:
+ * st_points_functionals_set on the chain's point set; call it after stm_points_set(_joint) and before the first iteration.
+ * stm_mcmc_functionals is stm_mcmc_points_joint (joint_id_new NULL: a plain set; new_cond_cov and new_cov then NULL) plus the
+ * functionals in CSR form and their outputs, column-major, any of which may be NULL: per saved draw fun_w, fun_cond_mean,
+ * fun_cond_var, fun_yhat (n_fun x keep, st_points_functionals_last); fun_mean, fun_var, fun_w_mean, fun_yhat_mean (n_fun,
+ * st_points_functionals_get); fun_w_q, fun_yhat_q (n_fun x n_quantiles).  The yhat outputs need X_new.  It consumes no draw of
+ * any stream and changes no chain state: every output stm_mcmc_points(_joint) also produces is the same bit for bit. */
+typedef struct stm_functionals {
+  int64_t n_fun;
+  const int64_t *ptr, *idx;
+  const double *wt;
+  double *fun_w, *fun_cond_mean, *fun_cond_var, *fun_yhat;
+  double *fun_mean, *fun_var, *fun_w_mean, *fun_yhat_mean;
+  double *fun_w_q, *fun_yhat_q;
+} stm_functionals;
+int stm_points_functionals_set(stm_chain c, int64_t n_fun, const int64_t *ptr, const int64_t *idx, const double *wt);
+int stm_mcmc_functionals(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
+                         int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
+                         int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc, double *beta_mcmc,
+                         double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time, int64_t n_new,
+                         const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new, const double *X_new,
+                         const int64_t *joint_id_new, int64_t keep_draws, const double *quantiles, int32_t n_quantiles, double *new_w,
+                         double *new_cond_mean, double *new_cond_var, double *new_yhat, double *new_mean, double *new_var,
+                         double *new_w_mean, double *new_yhat_mean, double *new_w_q, double *new_yhat_q, int32_t *new_route,
+                         double *new_cond_cov, double *new_cov, const stm_functionals *fun);
+
 #ifdef __cplusplus
 }
 #endif

@@ -306,6 +306,35 @@ int st_points_accumulate_joint(st_handle h, uint64_t seed, uint32_t iter, double
                                double *cond_chol, double *yhat_new);
 int st_points_summary_get_cov(st_handle h, double *cov);
 
+/* ---- linear functionals of the new-point predictions: F_f = sum_{k in [ptr[f], ptr[f+1])} wt[k] value[idx[k]], e.g. the mean of
+ * the field over a region, a total, a contrast of two outcomes at a site.  Every new point (joint group) is a leaf block of its
+ * own, so given w_S and theta distinct points (groups) are independent and for one saved draw
+ *   Var(a'w* | w, theta) = sum_groups a_g' Sigma_g a_g   (= sum_i a_i^2 cond_var_i on a plain set),
+ * which gives F the Rao-Blackwellised moments st_points_summary_get / _get_cov give points and groups.
+ * st_points_functionals_set: n_fun functionals in CSR form on the current point set (needs one, ST_ERR_USAGE); idx 0-based in the
+ *   caller's order of the points; an empty row is the functional 0; n_fun = 0 removes them.  Replaces the previous functionals and
+ *   zeroes their accumulators and stored draws; the per-point and pair summaries are left alone.  ST_ERR_USAGE, naming the
+ *   functional and entry, when ptr[0] != 0, ptr decreases, an index is outside 0..n_new-1, a weight is not finite or a point
+ *   occurs twice in one functional; the previous functionals then stay.  st_points_set / st_points_set_joint drop them.
+ * With functionals set, st_points_accumulate(_joint) also forms per functional F_w = a'w*, F_m = a'cond_mean, F_y = a'yhat (with X)
+ *   and F_v = Var(a'w* | w, theta) (a plain set: from the clamped cond_var; a joint set: from the packed Sigma, the sum clamped at
+ *   0) and updates the Welford mean and M2 of F_m, the running sums of F_v, F_w, F_y and, within st_points_summary_reserve's room,
+ *   the stored draws F_w, F_y.  st_points_summary_reserve / _reset size and clear these along with their own.  (A point set of
+ *   size 0 reserves nothing, as for its points: its functionals, all 0, store no draw and have no quantile.)  The summation order
+ *   is fixed (spamtree_amd/csrc/points_fun.hpp): a functional's values depend on its own terms only, bit for bit.
+ * st_points_functionals_last: the four values of the last accumulated iteration.
+ * st_points_functionals_get: mean = mean of F_m; var = mean of F_v + population variance of F_m; w_mean, yhat_mean = means of
+ *   the draws; refusals as st_points_summary_get.  st_points_functionals_quantile: k_qtile over the stored F_w / F_y, rules as
+ *   st_points_summary_quantile.  Outputs hold n_fun doubles; any may be NULL.
+ * st_points_functionals_info: the counts of the term lists (nnz linear terms, n_var_terms variance terms, n_chunks chunks of both
+ *   lists) and the algorithmic bytes of the functional step of one saved iteration; zeros without functionals.
+ * All but _info refuse limited_tree and world > 1 handles (ST_ERR_UNSUPPORTED). */
+int st_points_functionals_set(st_handle h, int64_t n_fun, const int64_t *ptr, const int64_t *idx, const double *wt);
+int st_points_functionals_last(st_handle h, double *f_w, double *f_cond_mean, double *f_cond_var, double *f_yhat);
+int st_points_functionals_get(st_handle h, double *mean, double *var, double *w_mean, double *yhat_mean, int64_t *n_accumulated);
+int st_points_functionals_quantile(st_handle h, double q, double *w_q, double *yhat_q);
+int st_points_functionals_info(st_handle h, int64_t *n_fun, int64_t *nnz, int64_t *n_chunks, int64_t *n_var_terms, double *alg_bytes);
+
 /* ---- prior simulation from slot 0: exact draws w ~ N(0, C_DAG) of the tree's own model and y = XB + w + sqrt(tau^2_j) eps.
  * st_simulate: a root-to-leaf sweep over slot 0 as the last st_factor(h, 0, theta) left it (a deferred leaf half is finished
  *   first), Ri_u w_u = z_u - N_u w_pa(u) per block, with the handle's current beta (XB) and tau^-2.  nd draws (1..16) in one

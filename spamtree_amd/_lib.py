@@ -108,6 +108,11 @@ SIGNATURES = {
     "st_points_predict_joint": (C.c_int, [H, C.c_int, c_dp, C.c_uint64, C.c_uint32, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "st_points_accumulate_joint": (C.c_int, [H, C.c_uint64, C.c_uint32, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "st_points_summary_get_cov": (C.c_int, [H, c_dp]),
+    "st_points_functionals_set": (C.c_int, [H, C.c_int64, c_ip, c_ip, c_dp]),
+    "st_points_functionals_last": (C.c_int, [H, c_dp, c_dp, c_dp, c_dp]),
+    "st_points_functionals_get": (C.c_int, [H, c_dp, c_dp, c_dp, c_dp, c_ip]),
+    "st_points_functionals_quantile": (C.c_int, [H, C.c_double, c_dp, c_dp]),
+    "st_points_functionals_info": (C.c_int, [H, c_ip, c_ip, c_ip, c_ip, c_dp]),
     "st_simulate": (C.c_int, [H, C.c_int, c_dp, c_dp, C.c_uint64, C.c_uint32, c_dp, c_dp]),
     "st_simulate_info": (C.c_int, [H, C.c_int, C.POINTER(C.c_int32), c_dp, c_dp]),
     "st_simulate_route_name": (C.c_char_p, [C.c_int32]),
@@ -117,6 +122,13 @@ SIGNATURES = {
 class StmFlags(C.Structure):
     _fields_ = [("adapting", C.c_int32), ("sample_beta", C.c_int32), ("sample_tausq", C.c_int32),
                 ("sample_theta", C.c_int32), ("sample_w", C.c_int32), ("sample_predicts", C.c_int32)]
+
+
+class StmFunctionals(C.Structure):   # include/spamtree_fit.h, stm_functionals
+    _fields_ = [("n_fun", C.c_int64), ("ptr", c_ip), ("idx", c_ip), ("wt", c_dp),
+                ("fun_w", c_dp), ("fun_cond_mean", c_dp), ("fun_cond_var", c_dp), ("fun_yhat", c_dp),
+                ("fun_mean", c_dp), ("fun_var", c_dp), ("fun_w_mean", c_dp), ("fun_yhat_mean", c_dp),
+                ("fun_w_q", c_dp), ("fun_yhat_q", c_dp)]
 
 
 # include/spamtree_fit.h (C++ host driver)
@@ -142,6 +154,12 @@ SIGNATURES.update({
                                         C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(StmFlags), c_dp, c_dp, c_dp, c_dp, c_dp,
                                         c_dp, c_dp, C.c_int64, c_dp, c_ip, c_ip, c_dp, c_ip, C.c_int64, c_dp, C.c_int32, c_dp,
                                         c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, C.POINTER(C.c_int32), c_dp, c_dp]),
+    "stm_points_functionals_set": (C.c_int, [H, C.c_int64, c_ip, c_ip, c_dp]),
+    "stm_mcmc_functionals": (C.c_int, [C.POINTER(StProblem), C.POINTER(StOptions), c_dp, c_dp, C.c_int, c_dp, C.c_double, c_dp,
+                                       C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(StmFlags), c_dp, c_dp, c_dp, c_dp, c_dp,
+                                       c_dp, c_dp, C.c_int64, c_dp, c_ip, c_ip, c_dp, c_ip, C.c_int64, c_dp, C.c_int32, c_dp,
+                                       c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, C.POINTER(C.c_int32), c_dp, c_dp,
+                                       C.POINTER(StmFunctionals)]),
 })
 
 # include/spamtree_tree.h (device parts of the tree builder)

@@ -229,3 +229,80 @@ int points_layout(const TreeLayout &t, int64_t n_new, const double *coords, cons
   if (joint_id) pack_joint(t, cm, out);
   return ST_OK;
 }
+
+// ---- linear functionals (points_fun.hpp): argument checks, the linear and the variance term list, their chunks ----
+namespace {
+
+int check_functionals(const FunFacts &p, int64_t n_fun, const int64_t *ptr, const int64_t *idx, const double *wt, std::string &msg) {
+  const char *who = "st_points_functionals_set: ";
+  if (n_fun < 0 || n_fun > (int64_t)INT32_MAX || (n_fun > 0 && !ptr)) return refuse(msg, ST_ERR_USAGE, std::string(who) + "bad sizes or NULL inputs");
+  if (n_fun == 0) return ST_OK;
+  if (ptr[0] != 0) return refuse(msg, ST_ERR_USAGE, std::string(who) + "ptr[0] is not 0");
+  for (int64_t f = 0; f < n_fun; ++f)
+    if (ptr[f + 1] < ptr[f]) return refuse(msg, ST_ERR_USAGE, std::string(who) + "ptr decreases at functional " + std::to_string(f));
+  if (ptr[n_fun] > 0 && (!idx || !wt)) return refuse(msg, ST_ERR_USAGE, std::string(who) + "bad sizes or NULL inputs");
+  std::vector<int64_t> seen((size_t)p.n, -1);   // the last functional that named the point
+  for (int64_t f = 0; f < n_fun; ++f)
+    for (int64_t k = ptr[f]; k < ptr[f + 1]; ++k) {
+      const std::string at = "functional " + std::to_string(f) + ", entry " + std::to_string(k - ptr[f]);
+      if (idx[k] < 0 || idx[k] >= p.n) return refuse(msg, ST_ERR_USAGE, who + at + ": index " + std::to_string(idx[k]) + " is not a point of the set (0.." + std::to_string(p.n - 1) + ")");
+      if (!std::isfinite(wt[k])) return refuse(msg, ST_ERR_USAGE, who + at + ": the weight is not finite");
+      if (seen[idx[k]] == f) return refuse(msg, ST_ERR_USAGE, who + at + ": point " + std::to_string(idx[k]) + " occurs twice in the functional");
+      seen[idx[k]] = f;
+    }
+  return ST_OK;
+}
+
+// the variance terms of functional [k0, k1): (a_i^2, i), or per touched group (layout order) the pairs a >= b of its members in
+// column-major order with (a_a a_b, doubled off the diagonal; j_off[g] + a + b g)
+void variance_terms(const FunFacts &p, const int64_t *idx, const double *wt, int64_t k0, int64_t k1, std::vector<FunTerm> &var) {
+  if (!p.joint) {
+    for (int64_t k = k0; k < k1; ++k) var.push_back(FunTerm{wt[k] * wt[k], (long long)idx[k]});
+    return;
+  }
+  struct Mem { int grp, a; double w; };
+  std::vector<Mem> mem;
+  mem.reserve((size_t)(k1 - k0));
+  for (int64_t k = k0; k < k1; ++k) mem.push_back(Mem{p.pt_grp[idx[k]], p.pt_a[idx[k]], wt[k]});
+  std::sort(mem.begin(), mem.end(), [](const Mem &x, const Mem &y) { return x.grp != y.grp ? x.grp < y.grp : x.a < y.a; });
+  for (size_t s = 0; s < mem.size();) {
+    size_t e = s;
+    while (e < mem.size() && mem[e].grp == mem[s].grp) ++e;
+    const long long o = p.j_off[mem[s].grp], g = p.j_mptr[mem[s].grp + 1] - p.j_mptr[mem[s].grp];
+    for (size_t b = s; b < e; ++b)
+      for (size_t a = b; a < e; ++a) {
+        const double c = mem[a].w * mem[b].w;
+        var.push_back(FunTerm{a == b ? c : 2.0 * c, o + mem[a].a + (long long)mem[b].a * g});
+      }
+    s = e;
+  }
+}
+
+// terms [t0, t1) of a list, all of functional f, into chunks of FUN_CHUNK
+void cut_chunks(long long t0, long long t1, int f, std::vector<FunChunk> &chunks) {
+  for (long long t = t0; t < t1; t += FUN_CHUNK) chunks.push_back(FunChunk{t, (int)std::min<long long>(FUN_CHUNK, t1 - t), f});
+}
+
+}   // namespace
+
+int functionals_layout(const FunFacts &p, int64_t n_fun, const int64_t *ptr, const int64_t *idx, const double *wt, FunLayout &out,
+                       std::string &msg) {
+  out = FunLayout();
+  if (int rc = check_functionals(p, n_fun, ptr, idx, wt, msg)) return rc;
+  out.n_fun = n_fun;
+  out.lin_cptr.assign((size_t)n_fun + 1, 0); out.var_cptr.assign((size_t)n_fun + 1, 0);
+  if (n_fun == 0) return ST_OK;
+  out.nnz = ptr[n_fun];
+  out.lin.reserve((size_t)out.nnz);
+  for (int64_t f = 0; f < n_fun; ++f) {
+    const long long l0 = (long long)out.lin.size(), v0 = (long long)out.var.size();
+    for (int64_t k = ptr[f]; k < ptr[f + 1]; ++k) out.lin.push_back(FunTerm{wt[k], (long long)idx[k]});
+    variance_terms(p, idx, wt, ptr[f], ptr[f + 1], out.var);
+    cut_chunks(l0, (long long)out.lin.size(), (int)f, out.lin_chunks);
+    cut_chunks(v0, (long long)out.var.size(), (int)f, out.var_chunks);
+    out.lin_cptr[f + 1] = (long long)out.lin_chunks.size(); out.var_cptr[f + 1] = (long long)out.var_chunks.size();
+  }
+  out.n_var_terms = (long long)out.var.size();
+  if (out.lin_chunks.size() + out.var_chunks.size() > (size_t)INT32_MAX) return refuse(msg, ST_ERR_UNSUPPORTED, "st_points_functionals_set: more than 2^31 - 1 chunks");
+  return ST_OK;
+}

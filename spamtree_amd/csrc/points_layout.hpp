@@ -5,6 +5,7 @@
 #pragma once
 #include "tree_layout.hpp"
 #include "predict_joint.hpp"
+#include "points_fun.hpp"
 
 // what the launch sites read after st_points_set has returned
 struct PointsCounts {
@@ -36,3 +37,29 @@ struct PointsLayout : PointsCounts {
 // Returns ST_OK, or the ST_ERR_* code of the first failing check with its text in msg.  joint_id NULL: st_points_set.
 int points_layout(const TreeLayout &t, int64_t n_new, const double *coords, const int64_t *mv, const int64_t *anchor,
                   const int64_t *joint_id, PointsLayout &out, std::string &msg);
+
+// ---- linear functionals of the point set (st_points_functionals_set; points_fun.hpp has the term lists and the kernels) ----
+// what functionals_layout reads of the current point set: its size and, of a joint set, the groups
+struct FunFacts {
+  long long n = 0;                             // points
+  bool joint = false;
+  const int64_t *j_off = nullptr, *j_mptr = nullptr;   // n_joint + 1 each (PointsLayout)
+  const int *pt_grp = nullptr, *pt_a = nullptr;        // per point, caller order
+};
+
+struct FunLayout {
+  long long n_fun = 0, nnz = 0, n_var_terms = 0;
+  std::vector<FunTerm> lin, var;               // the linear and the variance list, functional after functional
+  std::vector<FunChunk> lin_chunks, var_chunks;   // each list cut into chunks of <= FUN_CHUNK terms of one functional
+  std::vector<long long> lin_cptr, var_cptr;   // n_fun + 1 each: functional f owns chunks [cptr[f], cptr[f + 1]) of its list
+  double alg_bytes(bool has_yhat) const {      // per saved iteration: terms, gathered values, chunk sums out and in, k_fun_finish
+    const double nc = (double)(lin_chunks.size() + var_chunks.size());
+    return 16.0 * (double)(nnz + n_var_terms) + 8.0 * ((has_yhat ? 3.0 : 2.0) * (double)nnz + (double)n_var_terms) + 64.0 * nc +
+           (double)n_fun * (2.0 * PA_NACC * 8.0 + 4 * 8.0 + 2 * 8.0 + 4 * 8.0);
+  }
+};
+
+// CSR functionals on the point set `p`: the argument checks of st_points_functionals_set and the two chunked term lists.
+// Returns ST_OK, or ST_ERR_USAGE with the functional and entry named in msg.
+int functionals_layout(const FunFacts &p, int64_t n_fun, const int64_t *ptr, const int64_t *idx, const double *wt, FunLayout &out,
+                       std::string &msg);

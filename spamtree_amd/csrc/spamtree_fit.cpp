@@ -413,12 +413,20 @@ extern "C" int stm_points_set_joint(stm_chain c, int64_t n_new, const double *co
   return ST_OK;
 }
 
+extern "C" int stm_points_functionals_set(stm_chain c, int64_t n_fun, const int64_t *ptr, const int64_t *idx, const double *wt) {
+  if (!c || !c->h) return ST_ERR_USAGE;
+  const int rc = st_points_functionals_set(c->h, n_fun, ptr, idx, wt);
+  if (rc != 0) { c->err = st_last_error(c->h); return rc; }
+  return ST_OK;
+}
+
 namespace {
 struct FitPoints {   // the point set of stm_mcmc_points and where its per-draw outputs go (n_new x keep, any may be NULL)
   int64_t n;
   double *w, *cond_mean, *cond_var, *yhat;
   double *cond_cov;     // joint sets: packed length x keep, or NULL
   int64_t cov_len;      // the packed length of st_points_joint_layout
+  const stm_functionals *fun;   // functionals of the set and where their per-draw outputs go (n_fun x keep), or NULL
 };
 }  // namespace
 
@@ -465,6 +473,12 @@ static int run_fit(stm_chain c, int mcmc_keep, int mcmc_burn, int mcmc_thin, uin
                                           pts->cond_cov + (size_t)msaved * pts->cov_len, nullptr, col(pts->yhat));
         } else {
           rc = st_points_accumulate(c->h, seed, (uint32_t)msaved, col(pts->w), col(pts->cond_mean), col(pts->cond_var), col(pts->yhat));
+        }
+        if (!rc && pts->fun && (pts->fun->fun_w || pts->fun->fun_cond_mean || pts->fun->fun_cond_var || pts->fun->fun_yhat)) {
+          const size_t of = (size_t)msaved * pts->fun->n_fun;
+          auto fcol = [&](double *a) { return a ? a + of : nullptr; };
+          rc = st_points_functionals_last(c->h, fcol(pts->fun->fun_w), fcol(pts->fun->fun_cond_mean), fcol(pts->fun->fun_cond_var),
+                                          fcol(pts->fun->fun_yhat));
         }
         if (rc) c->err = st_last_error(c->h);
       }
@@ -517,6 +531,25 @@ extern "C" int stm_mcmc_points_joint(const st_problem *pb, const st_options *opt
                                      int32_t n_quantiles, double *new_w, double *new_cond_mean, double *new_cond_var, double *new_yhat,
                                      double *new_mean, double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q,
                                      double *new_yhat_q, int32_t *new_route, double *new_cond_cov, double *new_cov) {
+  return stm_mcmc_functionals(pb, opt, set_unif_bounds, theta, ntheta, beta, tausq, mcmcsd, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc,
+                              yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time, n_new, coords_new, mv_new, anchor_new, X_new,
+                              joint_id_new, keep_draws, quantiles, n_quantiles, new_w, new_cond_mean, new_cond_var, new_yhat, new_mean, new_var,
+                              new_w_mean, new_yhat_mean, new_w_q, new_yhat_q, new_route, new_cond_cov, new_cov, nullptr);
+}
+
+// fun NULL: stm_mcmc_points_joint itself
+extern "C" int stm_mcmc_functionals(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
+                                    int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
+                                    int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
+                                    double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
+                                    int64_t n_new, const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new,
+                                    const double *X_new, const int64_t *joint_id_new, int64_t keep_draws, const double *quantiles,
+                                    int32_t n_quantiles, double *new_w, double *new_cond_mean, double *new_cond_var, double *new_yhat,
+                                    double *new_mean, double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q,
+                                    double *new_yhat_q, int32_t *new_route, double *new_cond_cov, double *new_cov,
+                                    const stm_functionals *fun) {
+  if (fun && fun->n_fun <= 0) fun = nullptr;
+  if (fun && (fun->fun_yhat || fun->fun_yhat_mean || fun->fun_yhat_q) && !X_new) return ST_ERR_USAGE;
   if ((new_cond_cov || new_cov) && !joint_id_new) return ST_ERR_USAGE;
   if (n_quantiles < 0 || (n_quantiles > 0 && (!quantiles || keep_draws < 1))) return ST_ERR_USAGE;   // a quantile needs stored draws
   for (int32_t i = 0; i < n_quantiles; ++i) if (!(quantiles[i] >= 0.0 && quantiles[i] <= 1.0)) return ST_ERR_USAGE;
@@ -527,6 +560,7 @@ extern "C" int stm_mcmc_points_joint(const st_problem *pb, const st_options *opt
   int64_t nj = 0;
   std::vector<int64_t> joff, jptr, jmem;
   std::vector<double> cov_scratch;
+  if (rc == 0 && fun) rc = stm_points_functionals_set(c, fun->n_fun, fun->ptr, fun->idx, fun->wt);
   if (rc == 0 && joint_id_new) {
     rc = st_points_joint_layout(c->h, &nj, nullptr, nullptr, nullptr);
     joff.resize(nj + 1); jptr.resize(nj + 1); jmem.resize(n_new);
@@ -536,7 +570,7 @@ extern "C" int stm_mcmc_points_joint(const st_problem *pb, const st_options *opt
   if (rc == 0) rc = stm_init(c);
   if (rc != 0) { stm_destroy(c); return rc; }
   double *const ccov = !joint_id_new ? nullptr : (new_cond_cov ? new_cond_cov : (cov_scratch.empty() ? nullptr : cov_scratch.data()));
-  const FitPoints pts{n_new, new_w, new_cond_mean, new_cond_var, new_yhat, ccov, joint_id_new ? joff[nj] : 0};
+  const FitPoints pts{n_new, new_w, new_cond_mean, new_cond_var, new_yhat, ccov, joint_id_new ? joff[nj] : 0, fun};
   rc = run_fit(c, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc, yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time,
                &pts);
   if (rc == 0 && ccov && new_cond_var)
@@ -553,6 +587,11 @@ extern "C" int stm_mcmc_points_joint(const st_problem *pb, const st_options *opt
     rc = st_points_summary_quantile(c->h, quantiles[i], new_w_q ? new_w_q + (size_t)i * n_new : nullptr,
                                     new_yhat_q ? new_yhat_q + (size_t)i * n_new : nullptr);
   if (rc == 0 && new_route) rc = st_points_info(c->h, new_route, nullptr, nullptr, nullptr);
+  if (rc == 0 && fun && mcmc_keep > 0 && (fun->fun_mean || fun->fun_var || fun->fun_w_mean || fun->fun_yhat_mean))
+    rc = st_points_functionals_get(c->h, fun->fun_mean, fun->fun_var, fun->fun_w_mean, fun->fun_yhat_mean, nullptr);
+  for (int32_t i = 0; rc == 0 && fun && i < n_quantiles && (fun->fun_w_q || fun->fun_yhat_q); ++i)
+    rc = st_points_functionals_quantile(c->h, quantiles[i], fun->fun_w_q ? fun->fun_w_q + (size_t)i * fun->n_fun : nullptr,
+                                        fun->fun_yhat_q ? fun->fun_yhat_q + (size_t)i * fun->n_fun : nullptr);
   stm_destroy(c);
   return rc;
 }

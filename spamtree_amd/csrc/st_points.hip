@@ -1,12 +1,25 @@
 // st_points.hip -- the C-ABI of new-point prediction (st_points_*): the device step of st_points_set / st_points_set_joint, predict,
-// accumulate, the summaries and quantiles.  predict_points.hpp and predict_joint.hpp have the model; the launch structures of a
-// point set are built without a device call in points_layout.cpp; the kernels and their launchers live in k_predict.hip,
-// k_predict_joint.hip and k_points_acc.hip (k_qtile in k_misc.hip).
+// accumulate, the summaries and quantiles, and the linear functionals of the predictions (st_points_functionals_*).
+// predict_points.hpp, predict_joint.hpp and points_fun.hpp have the model; the launch structures of a point set and the term lists
+// of its functionals are built without a device call in points_layout.cpp; the kernels and their launchers live in k_predict.hip,
+// k_predict_joint.hip, k_points_acc.hip and k_points_fun.hip (k_qtile in k_misc.hip).
 #include <memory>
 
 #include "st_handle.hpp"
 #include "misc_kernels.hpp"
 #include "points_layout.hpp"
+
+// The functionals of a point set (st_points_functionals_set): the term lists and chunks on the device, their accumulators, the
+// values of the last iteration and, with a reservation, the draws F_w and F_y, [keep][n_fun] each
+struct FunSet {
+  long long n_fun = 0, nnz = 0, n_var_terms = 0, n_lin_chunks = 0, n_var_chunks = 0;
+  double alg_bytes = 0.0;
+  DevBuf<FunTerm> d_lin, d_var;
+  DevBuf<FunChunk> d_lin_chunks, d_var_chunks;
+  DevBuf<long long> d_lin_cptr, d_var_cptr;
+  DevBuf<double> d_part, d_acc, d_last, d_keep_w, d_keep_yhat, d_q;
+  long long n_acc = 0, n_kept = 0;
+};
 
 struct PointSet : PointsCounts {
   long long n = 0;
@@ -23,12 +36,14 @@ struct PointSet : PointsCounts {
   // st_points_set_joint: the joint groups in layout order (first appearance), their packing into slots and the pair accumulators
   bool joint = false;
   std::vector<int64_t> j_off, j_mptr, j_mem;   // packed block offsets (n_joint + 1), member list pointers (n_joint + 1), members
+  std::vector<int> pt_grp, pt_a;               // per point, caller order: its group and member index (functionals_layout reads them)
   DevBuf<PtJoint> d_jgroups;
   DevBuf<long long> d_jmem;
   DevBuf<PtCol> d_jcols;
   DevBuf<PtTile> d_jtiles;
   DevBuf<int> d_jgen, d_pt_grp, d_pt_a;
   DevBuf<double> d_jout, d_jscratch, d_pacc;   // cov and chol of the last call (2 x cov_total); scratch; pair accumulators
+  std::unique_ptr<FunSet> fun;                 // st_points_functionals_set; leaves with the point set
 };
 
 void points_free(st_handle_s *h) {
@@ -85,6 +100,7 @@ static int points_set_impl(st_handle h, int64_t n_new, const double *coords, con
     if (joint_id)
       if (const int rc = points_upload_joint(h, ps.get(), L)) return rc;
   }
+  ps->pt_grp = std::move(L.pt_grp); ps->pt_a = std::move(L.pt_a);
   h->pts = ps.release();
   return ST_OK;
 }
@@ -242,6 +258,49 @@ extern "C" const char *st_points_route_name(int32_t code) {
   return code < PP_ROUTE_COUNT ? points_route_name(code) : points_joint_route_name(code);
 }
 
+// ---- the functionals' share of reset, reserve and accumulate (the entry points follow the summaries) ----
+static int fun_reset(st_handle h, FunSet *fs) {
+  HCHK(h, hipMemsetAsync(fs->d_acc.p, 0, (size_t)PA_NACC * fs->n_fun * sizeof(double), h->stream));
+  fs->n_acc = 0; fs->n_kept = 0;
+  return ST_OK;
+}
+
+// room for the functional draws of the point set's reservation (keep_cap)
+static int fun_reserve(st_handle h, const PointSet *ps, FunSet *fs) {
+  fs->d_keep_w.free(); fs->d_keep_yhat.free();
+  fs->n_kept = 0;
+  if (ps->keep_cap == 0) return ST_OK;
+  HCHK(h, fs->d_keep_w.alloc((size_t)ps->keep_cap * fs->n_fun));
+  if (ps->has_X) HCHK(h, fs->d_keep_yhat.alloc((size_t)ps->keep_cap * fs->n_fun));
+  return ST_OK;
+}
+
+// the functional step of one saved iteration: after k_points_acc, on the same stream, from d_out / d_jout
+static int fun_step(st_handle h, PointSet *ps) {
+  FunSet *fs = ps->fun.get();
+  const long long n = ps->n, nf = fs->n_fun;
+  const double *o = ps->d_out.p;
+  FunArgs A;
+  A.lin = fs->d_lin.p; A.var = fs->d_var.p; A.lin_chunks = fs->d_lin_chunks.p; A.var_chunks = fs->d_var_chunks.p;
+  A.lin_cptr = fs->d_lin_cptr.p; A.var_cptr = fs->d_var_cptr.p;
+  A.n_lin_chunks = fs->n_lin_chunks; A.n_var_chunks = fs->n_var_chunks; A.n_fun = nf;
+  A.w = o; A.mean = o + n; A.yhat = ps->has_X ? o + 3 * n : nullptr;
+  A.vsrc = ps->joint ? ps->d_jout.p : o + 2 * n;
+  A.part = fs->d_part.p; A.acc = fs->d_acc.p; A.last = fs->d_last.p;
+  const bool keep = fs->n_kept < ps->keep_cap && fs->d_keep_w.p;
+  A.keep_w = keep ? fs->d_keep_w.p + (size_t)fs->n_kept * nf : nullptr;
+  A.keep_yhat = (keep && ps->has_X) ? fs->d_keep_yhat.p + (size_t)fs->n_kept * nf : nullptr;
+  A.count = (double)(fs->n_acc + 1);
+  {
+    ProfScope pscope(h, 6);
+    const int e = points_fun_launch(A, h->stream);
+    if (e) { h->err = std::string("st_points_accumulate launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+  }
+  fs->n_acc += 1;
+  if (keep) fs->n_kept += 1;
+  return ST_OK;
+}
+
 // ---- predictive summaries of the point set over saved iterations (st_points_accumulate; the kernel lives in k_points_acc.hip) ----
 extern "C" int st_points_summary_reset(st_handle h) {
   if (!h) return ST_ERR_USAGE;
@@ -255,6 +314,7 @@ extern "C" int st_points_summary_reset(st_handle h) {
   if (pcnt > 0 && !ps->d_pacc.p) HCHK(h, ps->d_pacc.alloc(pcnt));
   if (pcnt > 0) HCHK(h, hipMemsetAsync(ps->d_pacc.p, 0, pcnt * sizeof(double), h->stream));
   ps->n_acc = 0; ps->n_kept = 0;
+  if (ps->fun) return fun_reset(h, ps->fun.get());
   return ST_OK;
 }
 
@@ -267,10 +327,12 @@ extern "C" int st_points_summary_reserve(st_handle h, int64_t keep) {
   HCHK(h, hipStreamSynchronize(h->stream));
   ps->d_keep_w.free(); ps->d_keep_yhat.free();
   ps->keep_cap = 0; ps->n_kept = 0;
+  if (ps->fun) { ps->fun->d_keep_w.free(); ps->fun->d_keep_yhat.free(); ps->fun->n_kept = 0; }
   if (keep == 0 || ps->n == 0) return ST_OK;
   HCHK(h, ps->d_keep_w.alloc((size_t)keep * ps->n));
   if (ps->has_X) HCHK(h, ps->d_keep_yhat.alloc((size_t)keep * ps->n));
   ps->keep_cap = keep;
+  if (ps->fun) return fun_reserve(h, ps, ps->fun.get());
   return ST_OK;
 }
 
@@ -283,7 +345,12 @@ static int points_accumulate(st_handle h, uint64_t seed, uint32_t iter, double *
   if (yhat_new && !ps->has_X) { h->err = "st_points_accumulate: yhat_new needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
   if (!ps->d_acc.p && ps->n > 0) { const int rc0 = st_points_summary_reset(h); if (rc0) return rc0; }
   ps->route_mask = 0;
-  if (ps->n == 0) { ps->n_acc += 1; return ST_OK; }
+  if (ps->n == 0) {   // functionals of an empty set have no term: zeros
+    ps->n_acc += 1;
+    if (!ps->fun) return ST_OK;
+    HCHK(h, hipSetDevice(h->device));
+    return fun_step(h, ps);
+  }
   HCHK(h, hipSetDevice(h->device));
   const long long n = ps->n;
   const bool out[4] = {true, true, true, ps->has_X};
@@ -314,6 +381,8 @@ static int points_accumulate(st_handle h, uint64_t seed, uint32_t iter, double *
   }
   ps->n_acc += 1;
   if (keep) ps->n_kept += 1;
+  if (ps->fun)
+    if (const int rcf = fun_step(h, ps)) return rcf;
   double *const dst[4] = {w_new, cond_mean, cond_var, yhat_new};
   return points_copy_out(h, ps, dst, cond_cov, cond_chol, false);
 }
@@ -379,6 +448,28 @@ extern "C" int st_points_summary_get(st_handle h, double *mean, double *var, dou
   return ST_OK;
 }
 
+// k_qtile over the first n_kept rows of [keep][n] stores (draws[0]: w, draws[1]: yhat) into dst[which] (NULL: skipped), through
+// n doubles of device scratch
+static int points_qtile(st_handle h, const double *const draws[2], long long n, long long n_kept, double q, double *scratch, double *const dst[2]) {
+  HCHK(h, hipSetDevice(h->device));
+  int Kpad = 2;
+  while (Kpad < n_kept) Kpad <<= 1;
+  const int R = std::max(1, std::min(8, (int)(128 * 1024 / ((size_t)Kpad * 8))));
+  const size_t lds = (size_t)R * Kpad * sizeof(double);
+  (void)hipFuncSetAttribute((const void *)k_qtile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_limit);
+  for (int which = 0; which < 2; ++which) {
+    if (!dst[which]) continue;
+    QtArgs A;
+    A.draws = draws[which]; A.n = n; A.keep = (int)n_kept; A.Kpad = Kpad; A.R = R; A.q = q;
+    A.out = scratch;
+    hipLaunchKernelGGL(k_qtile, dim3((unsigned)((n + R - 1) / R)), dim3(NT), lds, h->stream, A);
+    HCHK(h, hipGetLastError());
+    HCHK(h, hipMemcpyAsync(dst[which], scratch, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HCHK(h, hipStreamSynchronize(h->stream));
+  }
+  return ST_OK;
+}
+
 extern "C" int st_points_summary_quantile(st_handle h, double q, double *w_q, double *yhat_q) {
   if (!h) return ST_ERR_USAGE;
   if (const int rc = points_refuse(h, "st_points_summary_quantile")) return rc;
@@ -386,23 +477,105 @@ extern "C" int st_points_summary_quantile(st_handle h, double q, double *w_q, do
   PointSet *ps = h->pts;
   if (ps->n_kept == 0) { h->err = "st_points_summary_quantile: no draw stored (call st_points_summary_reserve before the saved iterations)"; return ST_ERR_USAGE; }
   if (yhat_q && !ps->has_X) { h->err = "st_points_summary_quantile: yhat_q needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  double *const dst[2] = {w_q, yhat_q};
+  const double *const draws[2] = {ps->d_keep_w.p, ps->d_keep_yhat.p};
+  return points_qtile(h, draws, ps->n, ps->n_kept, q, ps->d_out.p, dst);   // d_out as scratch: the next st_points_accumulate rewrites it anyway
+}
+
+// ---- linear functionals of the predictions (points_fun.hpp): the term lists come from functionals_layout, without a device call
+extern "C" int st_points_functionals_set(st_handle h, int64_t n_fun, const int64_t *ptr, const int64_t *idx, const double *wt) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_functionals_set")) return rc;
+  PointSet *ps = h->pts;
+  FunFacts F;
+  F.n = ps->n; F.joint = ps->joint;
+  F.j_off = ps->j_off.data(); F.j_mptr = ps->j_mptr.data(); F.pt_grp = ps->pt_grp.data(); F.pt_a = ps->pt_a.data();
+  FunLayout L;
+  if (const int rc = functionals_layout(F, n_fun, ptr, idx, wt, L, h->err)) return rc;   // the previous functionals stay
   HCHK(h, hipSetDevice(h->device));
-  const long long n = ps->n;
-  int Kpad = 2;
-  while (Kpad < ps->n_kept) Kpad <<= 1;
-  const int R = std::max(1, std::min(8, (int)(128 * 1024 / ((size_t)Kpad * 8))));
-  const size_t lds = (size_t)R * Kpad * sizeof(double);
-  (void)hipFuncSetAttribute((const void *)k_qtile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_limit);
-  for (int which = 0; which < 2; ++which) {
-    double *dst = which == 0 ? w_q : yhat_q;
-    if (!dst) continue;
-    QtArgs A;
-    A.draws = which == 0 ? ps->d_keep_w.p : ps->d_keep_yhat.p; A.n = n; A.keep = (int)ps->n_kept; A.Kpad = Kpad; A.R = R; A.q = q;
-    A.out = ps->d_out.p;   // scratch: the next st_points_accumulate rewrites it anyway
-    hipLaunchKernelGGL(k_qtile, dim3((unsigned)((n + R - 1) / R)), dim3(NT), lds, h->stream, A);
-    HCHK(h, hipGetLastError());
-    HCHK(h, hipMemcpyAsync(dst, ps->d_out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HCHK(h, hipStreamSynchronize(h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  if (n_fun == 0) { ps->fun.reset(); return ST_OK; }
+  std::unique_ptr<FunSet> fs(new FunSet());   // the point set takes it once every upload has succeeded
+  fs->n_fun = L.n_fun; fs->nnz = L.nnz; fs->n_var_terms = L.n_var_terms;
+  fs->n_lin_chunks = (long long)L.lin_chunks.size(); fs->n_var_chunks = (long long)L.var_chunks.size();
+  fs->alg_bytes = L.alg_bytes(ps->has_X);
+  HCHK(h, upload_or_dummy(fs->d_lin, L.lin)); HCHK(h, upload_or_dummy(fs->d_var, L.var));
+  HCHK(h, upload_or_dummy(fs->d_lin_chunks, L.lin_chunks)); HCHK(h, upload_or_dummy(fs->d_var_chunks, L.var_chunks));
+  HCHK(h, fs->d_lin_cptr.upload(L.lin_cptr)); HCHK(h, fs->d_var_cptr.upload(L.var_cptr));
+  HCHK(h, fs->d_part.alloc((size_t)4 * std::max<long long>(1, fs->n_lin_chunks + fs->n_var_chunks)));
+  HCHK(h, fs->d_acc.alloc((size_t)PA_NACC * fs->n_fun)); HCHK(h, fs->d_last.alloc((size_t)4 * fs->n_fun)); HCHK(h, fs->d_q.alloc((size_t)fs->n_fun));
+  if (const int rc = fun_reset(h, fs.get())) return rc;
+  if (const int rc = fun_reserve(h, ps, fs.get())) return rc;
+  ps->fun = std::move(fs);
+  return ST_OK;
+}
+
+// what the functional outputs refuse first
+static int fun_refuse(st_handle h, const char *who, bool need_acc) {
+  if (const int rc = points_refuse(h, who)) return rc;
+  if (!h->pts->fun) { h->err = std::string(who) + " before st_points_functionals_set"; return ST_ERR_USAGE; }
+  if (need_acc && h->pts->fun->n_acc == 0) { h->err = std::string(who) + ": no iteration accumulated"; return ST_ERR_USAGE; }
+  return ST_OK;
+}
+
+extern "C" int st_points_functionals_info(st_handle h, int64_t *n_fun, int64_t *nnz, int64_t *n_chunks, int64_t *n_var_terms, double *alg_bytes) {
+  if (!h) return ST_ERR_USAGE;
+  const FunSet *fs = h->pts ? h->pts->fun.get() : nullptr;
+  if (n_fun) *n_fun = fs ? fs->n_fun : 0;
+  if (nnz) *nnz = fs ? fs->nnz : 0;
+  if (n_chunks) *n_chunks = fs ? fs->n_lin_chunks + fs->n_var_chunks : 0;
+  if (n_var_terms) *n_var_terms = fs ? fs->n_var_terms : 0;
+  if (alg_bytes) *alg_bytes = fs ? fs->alg_bytes : 0.0;
+  return ST_OK;
+}
+
+extern "C" int st_points_functionals_last(st_handle h, double *f_w, double *f_cond_mean, double *f_cond_var, double *f_yhat) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = fun_refuse(h, "st_points_functionals_last", true)) return rc;
+  const PointSet *ps = h->pts;
+  FunSet *fs = ps->fun.get();
+  if (f_yhat && !ps->has_X) { h->err = "st_points_functionals_last: f_yhat needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  HCHK(h, hipSetDevice(h->device));
+  double *const dst[4] = {f_w, f_cond_mean, f_cond_var, f_yhat};
+  for (int k = 0; k < 4; ++k)
+    if (dst[k]) HCHK(h, hipMemcpyAsync(dst[k], fs->d_last.p + (size_t)k * fs->n_fun, (size_t)fs->n_fun * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  return ST_OK;
+}
+
+extern "C" int st_points_functionals_get(st_handle h, double *mean, double *var, double *w_mean, double *yhat_mean, int64_t *n_accumulated) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = fun_refuse(h, "st_points_functionals_get", false)) return rc;
+  const PointSet *ps = h->pts;
+  FunSet *fs = ps->fun.get();
+  if (n_accumulated) *n_accumulated = fs->n_acc;
+  if (fs->n_acc == 0) { h->err = "st_points_functionals_get: no iteration accumulated"; return ST_ERR_USAGE; }
+  if (yhat_mean && !ps->has_X) { h->err = "st_points_functionals_get: yhat_mean needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  HCHK(h, hipSetDevice(h->device));
+  const long long n = fs->n_fun;
+  std::vector<double> acc((size_t)PA_NACC * n);
+  HCHK(h, hipMemcpyAsync(acc.data(), fs->d_acc.p, acc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  const double cnt = (double)fs->n_acc;
+  const double *a = acc.data();
+  for (long long i = 0; i < n; ++i) {   // the expressions of st_points_summary_get
+    if (mean) mean[i] = a[PA_MEAN * n + i];
+    if (var) var[i] = a[PA_VAR * n + i] / cnt + a[PA_M2 * n + i] / cnt;
+    if (w_mean) w_mean[i] = a[PA_W * n + i] / cnt;
+    if (yhat_mean) yhat_mean[i] = a[PA_YHAT * n + i] / cnt;
   }
   return ST_OK;
+}
+
+extern "C" int st_points_functionals_quantile(st_handle h, double q, double *w_q, double *yhat_q) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = fun_refuse(h, "st_points_functionals_quantile", false)) return rc;
+  if (!(q >= 0.0 && q <= 1.0)) { h->err = "st_points_functionals_quantile: q must lie in [0, 1]"; return ST_ERR_USAGE; }
+  const PointSet *ps = h->pts;
+  FunSet *fs = ps->fun.get();
+  if (fs->n_kept == 0) { h->err = "st_points_functionals_quantile: no draw stored (call st_points_summary_reserve before the saved iterations)"; return ST_ERR_USAGE; }
+  if (yhat_q && !ps->has_X) { h->err = "st_points_functionals_quantile: yhat_q needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  double *const dst[2] = {w_q, yhat_q};
+  const double *const draws[2] = {fs->d_keep_w.p, fs->d_keep_yhat.p};
+  return points_qtile(h, draws, fs->n_fun, fs->n_kept, q, fs->d_q.p, dst);
 }

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .model import SpamTreeError, _dp, _f64, _i64, _ip, _lists_to_csr, joint_labels
+from .model import SpamTreeError, _dp, _f64, _i64, _ip, _lists_to_csr, functionals_csr, joint_labels
 
 
 def _problem(y, X, coords, mv_id, res_is_ref, parents, children, block_names, block_groups, indexing):
@@ -163,9 +163,9 @@ class Chain:
 def _points_inputs(new_points, p, q, new_quantiles):
     """Checks the point set of spamtree_mv_mcmc(new_points=...) against itself and the problem, before any device call."""
     pts = dict(new_points)
-    unknown = set(pts) - {"coords", "mv", "anchor", "X", "joint"}
+    unknown = set(pts) - {"coords", "mv", "anchor", "X", "joint", "functionals"}
     if unknown:
-        raise ValueError(f"new_points: unknown keys {sorted(unknown)} (coords, mv, anchor, X, joint)")
+        raise ValueError(f"new_points: unknown keys {sorted(unknown)} (coords, mv, anchor, X, joint, functionals)")
     coords = np.asarray(pts["coords"], dtype=np.float64)
     if coords.ndim != 2 or coords.shape[1] != 2:
         raise ValueError("new_points: coords must be n_new x 2")
@@ -194,7 +194,15 @@ def _points_inputs(new_points, p, q, new_quantiles):
             labels = joint_labels(labels, n_new)
         except ValueError as e:
             raise ValueError(f"new_points: {e}") from None
-    return np.asfortranarray(coords), _i64(mv), _i64(anchor), X, qs, labels
+    fun = pts.get("functionals")
+    if fun is not None:
+        try:
+            fun = functionals_csr(fun, n_new)
+        except ValueError as e:
+            raise ValueError(f"new_points: {e}") from None
+        if fun[0].size == 1:
+            fun = None
+    return np.asfortranarray(coords), _i64(mv), _i64(anchor), X, qs, labels, fun
 
 
 def _joint_layout(labels):
@@ -232,7 +240,11 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     ``new_points["joint"]``: one integer label per point; each label's points (at most 16, one anchor) are drawn jointly
     (stm_mcmc_points_joint) and ``new`` also holds ``groups`` (member indices per group), ``cov`` (per group the predictive
     covariance, mean conditional covariance + covariance of the conditional means) and, with ``new_draws``, ``cond_cov``
-    (per saved draw, per group)."""
+    (per saved draw, per group).
+    ``new_points["functionals"]``: linear functionals of the predictions (``model.functionals_csr`` has the accepted forms;
+    ``predict.areal_means`` / ``predict.contrasts`` build common ones), summarised on the device (stm_mcmc_functionals); ``new``
+    then also holds ``functionals``: dict(mean, var, w_mean, yhat_mean, quantiles={q: (w_q, yhat_q)}) and, with ``new_draws``,
+    the per-draw n_fun x keep arrays ``w``, ``cond_mean``, ``cond_var``, ``yhat``."""
     if new_points is not None:
         pts = _points_inputs(new_points, np.asarray(X).shape[1], int(np.unique(_i64(mv_id)).size), new_quantiles)
     elif len(tuple(new_quantiles)):
@@ -258,7 +270,7 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     if new_points is None:
         rc = lib.spamtree_mv_mcmc_c(*common)
     else:
-        pc, pmv, pan, pX, qs, labels = pts
+        pc, pmv, pan, pX, qs, labels, fun = pts
         n_new = pc.shape[0]
         draws = {key: np.zeros((n_new, mcmc_keep), order="F") if new_draws else None for key in ("w", "cond_mean", "cond_var")}
         draws["yhat"] = np.zeros((n_new, mcmc_keep), order="F") if (new_draws and pX is not None) else None
@@ -270,12 +282,27 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
         tail = (int(mcmc_keep) if qs.size else 0, _dp(qs), int(qs.size), dp(draws["w"]), dp(draws["cond_mean"]),
                 dp(draws["cond_var"]), dp(draws["yhat"]), dp(summ["mean"]), dp(summ["var"]), dp(summ["w_mean"]),
                 dp(summ["yhat_mean"]), dp(wq if qs.size else None), dp(yq if qs.size else None), C.byref(route))
-        if labels is None:
-            rc = lib.stm_mcmc_points(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), *tail)
-        else:
+        groups = off = ccov = cov = None
+        if labels is not None:
             groups, off = _joint_layout(labels)
             ccov = np.zeros((int(off[-1]), mcmc_keep), order="F") if new_draws else None
             cov = np.zeros(int(off[-1]))
+        if fun is not None:       # stm_mcmc_functionals: both kinds of set, plus the functional outputs in one struct
+            nf = fun[0].size - 1
+            fdraws = {key: np.zeros((nf, mcmc_keep), order="F") if new_draws else None for key in ("w", "cond_mean", "cond_var")}
+            fdraws["yhat"] = np.zeros((nf, mcmc_keep), order="F") if (new_draws and pX is not None) else None
+            fsumm = {key: np.zeros(nf) for key in ("mean", "var", "w_mean")}
+            fsumm["yhat_mean"] = np.zeros(nf) if pX is not None else None
+            fwq = np.zeros((nf, qs.size), order="F")
+            fyq = np.zeros((nf, qs.size), order="F") if pX is not None else None
+            fs = _lib.StmFunctionals(nf, _ip(fun[0]), _ip(fun[1]), _dp(fun[2]), dp(fdraws["w"]), dp(fdraws["cond_mean"]),
+                                     dp(fdraws["cond_var"]), dp(fdraws["yhat"]), dp(fsumm["mean"]), dp(fsumm["var"]), dp(fsumm["w_mean"]),
+                                     dp(fsumm["yhat_mean"]), dp(fwq if qs.size else None), dp(fyq if qs.size else None))
+            rc = lib.stm_mcmc_functionals(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), _ip(labels) if labels is not None else None,
+                                          *tail, dp(ccov), dp(cov), C.byref(fs))
+        elif labels is None:
+            rc = lib.stm_mcmc_points(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), *tail)
+        else:
             rc = lib.stm_mcmc_points_joint(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), _ip(labels), *tail, dp(ccov),
                                            _dp(cov))
         if rc == 0:
@@ -292,6 +319,11 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                 new.update(groups=groups, cov=_unpack_joint(cov, groups, off))
                 if new_draws:
                     new["cond_cov"] = [_unpack_joint(ccov[:, s], groups, off) for s in range(mcmc_keep)]
+            if fun is not None:
+                new["functionals"] = dict(fsumm, quantiles={float(x): (fwq[:, i].copy(), None if fyq is None else fyq[:, i].copy())
+                                                            for i, x in enumerate(qs)})
+                if new_draws:
+                    new["functionals"].update(fdraws)
     if rc == -10:
         raise FloatingPointError("At nan loglik: error.")
     if rc != 0 and new_points is not None:

@@ -56,6 +56,54 @@ def joint_labels(joint, n):
     return _i64(labels)
 
 
+def functionals_csr(A, n_points):
+    """Linear functionals of the predictions at ``n_points`` points as CSR ``(ptr, idx, wt)``, checked before any device call.
+    ``A``: a ``(ptr, idx, wt)`` triple (a tuple of three whose entries are not themselves (indices, weights) pairs); a dense n_fun x n_points array, whose zeros are dropped; or a list of
+    ``(indices, weights)`` pairs.  ValueError on bad shapes, indices outside 0..n_points-1, non-finite weights or a point that
+    occurs twice in one functional."""
+    n_points = int(n_points)
+    if isinstance(A, tuple) and len(A) == 3 and not all(isinstance(x, (list, tuple)) and len(x) == 2 and np.ndim(x[0]) == 1 for x in A):
+        ptr, idx, wt = (np.asarray(x) for x in A)
+        if ptr.ndim != 1 or idx.ndim != 1 or wt.ndim != 1 or ptr.size < 1:
+            raise ValueError("functionals: ptr, idx and wt must be one-dimensional and ptr must hold n_fun + 1 entries")
+        if not (np.issubdtype(ptr.dtype, np.integer) and np.issubdtype(idx.dtype, np.integer)):
+            raise ValueError("functionals: ptr and idx must be integers")
+    elif isinstance(A, (list, tuple)):
+        rows = []
+        for f, pair in enumerate(A):
+            if not (isinstance(pair, (list, tuple)) and len(pair) == 2):
+                raise ValueError(f"functionals: entry {f} is not an (indices, weights) pair")
+            i, w = np.asarray(pair[0]).reshape(-1), np.asarray(pair[1], dtype=np.float64).reshape(-1)
+            if i.size and not np.issubdtype(i.dtype, np.integer):
+                raise ValueError(f"functionals: the indices of functional {f} must be integers")
+            if i.size != w.size:
+                raise ValueError(f"functionals: functional {f} has {i.size} indices and {w.size} weights")
+            rows.append((i.astype(np.int64), w))
+        ptr = np.concatenate([[0], np.cumsum([r[0].size for r in rows])]).astype(np.int64)
+        idx = np.concatenate([r[0] for r in rows]) if rows else np.zeros(0, dtype=np.int64)
+        wt = np.concatenate([r[1] for r in rows]) if rows else np.zeros(0)
+    else:
+        D = np.asarray(A, dtype=np.float64)
+        if D.ndim != 2 or D.shape[1] != n_points:
+            raise ValueError(f"functionals: a dense array must be n_fun x n_new = n_fun x {n_points}")
+        if not np.all(np.isfinite(D)):
+            raise ValueError("functionals: weights must be finite")
+        r, c = np.nonzero(D)
+        ptr = np.concatenate([[0], np.cumsum(np.bincount(r, minlength=D.shape[0]))]).astype(np.int64)
+        idx, wt = c.astype(np.int64), D[r, c]
+    ptr, idx, wt = _i64(ptr), _i64(idx), _f64(wt)
+    if ptr[0] != 0 or np.any(np.diff(ptr) < 0) or ptr[-1] != idx.size or idx.size != wt.size:
+        raise ValueError("functionals: ptr must start at 0, not decrease and end at the number of entries of idx and wt")
+    if idx.size and (idx.min() < 0 or idx.max() >= n_points):
+        raise ValueError(f"functionals: indices must lie in 0..{n_points - 1}")
+    if not np.all(np.isfinite(wt)):
+        raise ValueError("functionals: weights must be finite")
+    row = np.repeat(np.arange(ptr.size - 1, dtype=np.int64), np.diff(ptr))
+    if idx.size and np.unique(row * max(n_points, 1) + idx).size != idx.size:
+        raise ValueError("functionals: a point occurs twice in one functional")
+    return ptr, idx, wt
+
+
 class SpamTreeMV:
     """spamtree_model.cpp:8-192.  `param_data` / `alter_data` are slots 0 / 1 of the device handle."""
 
@@ -380,6 +428,7 @@ class SpamTreeMV:
             self.joint_groups = [mem[ptr[k]:ptr[k + 1]].copy() for k in range(nj.value)]
         self.n_points = n
         self.points_have_X = Xf is not None
+        self.n_functionals = 0       # a new point set has none
 
     def unpack_joint(self, packed):
         """The g x g blocks of a packed cond_cov / cond_chol / summary covariance, in group order: one [n_groups, g, g] array
@@ -426,6 +475,68 @@ class SpamTreeMV:
         for k, m in enumerate(self.joint_groups):
             out["var"][m] = np.maximum(cov[self.joint_offsets[k]:self.joint_offsets[k + 1]][::m.size + 1], 0.0)
         return out
+
+    def accumulate_points(self, seed=0, it=0):
+        """One saved iteration (st_points_accumulate): predict_points' draw with Philox streams 6 / 7 and counter ``it``, folded
+        into the device summaries and, when set, the functionals.  Returns predict_points' dict."""
+        n = self.n_points
+        out = {k: np.zeros(n) for k in ("w", "mean", "var")}
+        out["yhat"] = np.zeros(n) if self.points_have_X else None
+        yp = _dp(out["yhat"]) if out["yhat"] is not None else None
+        if getattr(self, "joint_groups", None) is None:
+            self._check(self.lib.st_points_accumulate(self.h, int(seed), int(it), _dp(out["w"]), _dp(out["mean"]), _dp(out["var"]), yp))
+            return out
+        cov, chol = np.zeros(int(self.joint_offsets[-1])), np.zeros(int(self.joint_offsets[-1]))
+        self._check(self.lib.st_points_accumulate_joint(self.h, int(seed), int(it), _dp(out["w"]), _dp(out["mean"]), _dp(cov), _dp(chol), yp))
+        out["cov"], out["chol"] = self.unpack_joint(cov), self.unpack_joint(chol)
+        out["cov_packed"], out["chol_packed"] = cov, chol
+        for k, m in enumerate(self.joint_groups):
+            out["var"][m] = np.maximum(cov[self.joint_offsets[k]:self.joint_offsets[k + 1]][::m.size + 1], 0.0)
+        return out
+
+    # ---- linear functionals of the predictions at the point set (st_points_functionals_*)
+    def set_functionals(self, A):
+        """Functionals F = sum a_i value_i of the point set's predictions (``functionals_csr`` has the accepted forms of ``A``;
+        None or no row removes them).  Every accumulate_points then also forms them on the device."""
+        ptr, idx, wt = functionals_csr(A, self.n_points) if A is not None else (np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros(0))
+        self._check(self.lib.st_points_functionals_set(self.h, ptr.size - 1, _ip(ptr), _ip(idx), _dp(wt)))
+        self.n_functionals = ptr.size - 1
+
+    def functionals_last(self):
+        """F_w, F_m, F_v, F_y of the last accumulated iteration: dict(w, cond_mean, cond_var, yhat), yhat None without X."""
+        nf = self.n_functionals
+        out = {k: np.zeros(nf) for k in ("w", "cond_mean", "cond_var")}
+        out["yhat"] = np.zeros(nf) if self.points_have_X else None
+        self._check(self.lib.st_points_functionals_last(self.h, _dp(out["w"]), _dp(out["cond_mean"]), _dp(out["cond_var"]),
+                                                        _dp(out["yhat"]) if out["yhat"] is not None else None))
+        return out
+
+    def functionals(self):
+        """Summaries over the accumulated iterations: dict(mean, var, w_mean, yhat_mean, n) -- mean of F_m, mean of F_v +
+        population variance of F_m, means of the draws."""
+        nf = self.n_functionals
+        out = {k: np.zeros(nf) for k in ("mean", "var", "w_mean")}
+        out["yhat_mean"] = np.zeros(nf) if self.points_have_X else None
+        cnt = C.c_int64()
+        self._check(self.lib.st_points_functionals_get(self.h, _dp(out["mean"]), _dp(out["var"]), _dp(out["w_mean"]),
+                                                       _dp(out["yhat_mean"]) if out["yhat_mean"] is not None else None, C.byref(cnt)))
+        out["n"] = int(cnt.value)
+        return out
+
+    def functionals_quantile(self, q):
+        """(w_q, yhat_q) of the stored functional draws (st_points_summary_reserve before the iterations); yhat_q None without X."""
+        nf = self.n_functionals
+        wq = np.zeros(nf)
+        yq = np.zeros(nf) if self.points_have_X else None
+        self._check(self.lib.st_points_functionals_quantile(self.h, float(q), _dp(wq), _dp(yq) if yq is not None else None))
+        return wq, yq
+
+    def functionals_info(self):
+        """dict(n_fun, nnz, n_chunks, n_var_terms, alg_bytes) of the functionals' term lists."""
+        v = [C.c_int64() for _ in range(4)]
+        by = C.c_double()
+        self._check(self.lib.st_points_functionals_info(self.h, *[C.byref(x) for x in v], C.byref(by)))
+        return dict(n_fun=v[0].value, nnz=v[1].value, n_chunks=v[2].value, n_var_terms=v[3].value, alg_bytes=by.value)
 
     def points_info(self):
         """Of the last predict_points: dict(routes=[kernel names that ran], n_groups, alg_bytes, flops)."""

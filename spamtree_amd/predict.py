@@ -18,10 +18,43 @@ from typing import Optional
 import numpy as np
 
 from . import fit
-from .model import SpamTreeMV, _dp, _f64, joint_labels
+from .model import SpamTreeMV, _dp, _f64, functionals_csr, joint_labels
 from .topology import Topology, _nearest_rows
 
-__all__ = ["locate", "conditioning_set", "group_sites", "predict_new", "fit_predict"]
+__all__ = ["locate", "conditioning_set", "group_sites", "predict_new", "fit_predict", "areal_means", "contrasts"]
+
+
+def areal_means(labels, weights=None):
+    """One averaging functional per region: ``labels`` holds one integer per point, a negative label means no region; the
+    functionals come in ascending label order.  ``weights`` (one positive number per point, e.g. cell areas) are normalised to
+    sum to 1 inside each region; None: equal weights.  Returns CSR ``(ptr, idx, wt)`` for ``functionals=``."""
+    labels = np.asarray(labels)
+    if labels.ndim != 1 or (labels.size and not np.issubdtype(labels.dtype, np.integer)):
+        raise ValueError("areal_means: labels must hold one integer per point")
+    w = np.ones(labels.size) if weights is None else np.asarray(weights, dtype=np.float64)
+    if w.shape != labels.shape or not np.all(np.isfinite(w)) or np.any(w <= 0):
+        raise ValueError("areal_means: weights must hold one positive finite number per point")
+    idx = np.nonzero(labels >= 0)[0]
+    idx = idx[np.argsort(labels[idx], kind="stable")].astype(np.int64)         # by region, the caller's order inside it
+    regions, counts = np.unique(labels[idx], return_counts=True)
+    ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    wt = w[idx].copy()
+    for k in range(regions.size):
+        wt[ptr[k]:ptr[k + 1]] /= wt[ptr[k]:ptr[k + 1]].sum()
+    return ptr, idx, wt
+
+
+def contrasts(pairs):
+    """The functionals value_i - value_j for every ``(i, j)`` of ``pairs`` (k x 2 point indices, i != j): CSR ``(ptr, idx, wt)``."""
+    pairs = np.asarray(pairs)
+    if pairs.size == 0:
+        return np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros(0)
+    if pairs.ndim != 2 or pairs.shape[1] != 2 or not np.issubdtype(pairs.dtype, np.integer):
+        raise ValueError("contrasts: pairs must be k x 2 integer point indices")
+    if np.any(pairs[:, 0] == pairs[:, 1]) or pairs.min() < 0:
+        raise ValueError("contrasts: a pair needs two different points, indices from 0")
+    k = pairs.shape[0]
+    return 2 * np.arange(k + 1, dtype=np.int64), pairs.astype(np.int64).reshape(-1), np.tile([1.0, -1.0], k)
 
 
 def group_sites(coords) -> np.ndarray:
@@ -72,7 +105,7 @@ def conditioning_set(topo: Topology, anchor: int) -> np.ndarray:
 
 
 def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, return_draws=True, device=0, z=None,
-                mode=0, force_generic=False, return_moments=False, joint=None):
+                mode=0, force_generic=False, return_moments=False, joint=None, functionals=None):
     """Predictive at new locations for every saved draw of a chain.
 
     ``model_inputs``: the problem as ``spamtree_mv_mcmc`` took it (the dict of ``synthetic.make_workload``; its ``topo``
@@ -89,12 +122,23 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
     result also holds ``groups`` (the member indices of every group), ``cov`` -- per group the Rao-Blackwellised predictive
     covariance, mean of the conditional covariances + covariance of the conditional means -- and, with ``return_draws``,
     ``cond_cov``: per saved draw the conditional covariances (``SpamTreeMV.unpack_joint``'s list or array).
+
+    ``functionals``: linear functionals of the predictions (``model.functionals_csr``'s forms, :func:`areal_means`,
+    :func:`contrasts`).  The replay then goes through ``st_points_accumulate`` -- the same draw as ``st_points_predict`` with
+    that seed and counter, so every other output is unchanged bit for bit -- which needs the device's normals (``z`` None) and
+    ``mode`` 0.  The result also holds ``functionals``: dict(mean, var, w_mean, yhat_mean) and, with ``return_draws``, the
+    n_fun x keep arrays ``w``, ``cond_mean``, ``cond_var``, ``yhat``.
     """
     mi = model_inputs
     topo = mi["topo"]
     coords_new = np.asarray(coords_new, dtype=np.float64).reshape(-1, 2)
     mv_new = np.asarray(mv_new, dtype=np.int64).reshape(-1)
     n_new = coords_new.shape[0]
+    fun = None
+    if functionals is not None:
+        fun = functionals_csr(functionals, n_new)
+        if z is not None or mode != 0:
+            raise ValueError("functionals need the device draw: z=None and mode=0")
     anchor = locate(topo, coords_new, mv_new, device=device, joint=joint)
     w_list = draws["w_mcmc"]
     keep = len(w_list)
@@ -111,6 +155,10 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
                    force_generic=force_generic)
     try:
         m.set_points(coords_new, mv_new, anchor, X_new, joint=joint)
+        fdraws = None
+        if fun is not None:
+            m.set_functionals(fun)
+            fdraws = {k: np.zeros((fun[0].size - 1, keep)) for k in ("w", "cond_mean", "cond_var", "yhat")}
         cc = []
         w_out = np.zeros((n_new, keep)) if return_draws else None
         y_out = np.zeros((n_new, keep)) if (return_draws and X_new is not None) else None
@@ -124,7 +172,13 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
             m.theta_update(0, theta[:, s])
             if not m.get_loglik_comps_w(0):
                 raise FloatingPointError(f"st_factor failed on saved draw {s} (errtype {m.last_errtype})")
-            out = m.predict_points(mode=mode, z=None if z is None else z[:, s], seed=seed, it=s)
+            if fun is None:
+                out = m.predict_points(mode=mode, z=None if z is None else z[:, s], seed=seed, it=s)
+            else:
+                out = m.accumulate_points(seed=seed, it=s)
+                for k, v in m.functionals_last().items():
+                    if v is not None:
+                        fdraws[k][:, s] = v
             cm[:, s] = out["mean"]
             cv[:, s] = out["var"]
             if joint is not None:
@@ -140,6 +194,10 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
         if return_moments:
             res["cond_mean"] = cm
             res["cond_var"] = cv
+        if fun is not None:
+            res["functionals"] = {k: v for k, v in m.functionals().items() if k != "n"} if keep else {}
+            if return_draws:
+                res["functionals"].update(fdraws, yhat=fdraws["yhat"] if X_new is not None else None)
         if joint is not None:
             packed = np.mean(cc, axis=0) if keep else np.zeros(0)
             for k, g in enumerate(m.joint_groups):
@@ -154,7 +212,7 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
         m.close()
 
 
-def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), return_draws=True, joint=None, **mcmc):
+def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), return_draws=True, joint=None, functionals=None, **mcmc):
     """Fit the chain and predict at new locations on every saved iteration, without replaying it.
 
     ``model_inputs``: the problem as for :func:`predict_new`.  The points are located with :func:`locate` and handed to
@@ -166,6 +224,8 @@ def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), retu
     ``w_mean``, ``yhat_mean`` and ``quantiles[q] = (w_q, yhat_q)`` from the device summaries, and with ``return_draws`` the
     n_new x keep draws ``w``, ``yhat`` and the per-draw ``cond_mean``, ``cond_var``.  yhat entries are None without ``X_new``.
     With ``joint`` labels also ``groups``, ``cov`` and (``return_draws``) ``cond_cov``, as :func:`predict_new`.
+    With ``functionals`` (as :func:`predict_new`) also ``functionals``: dict(mean, var, w_mean, yhat_mean, quantiles) from the
+    device and, with ``return_draws``, the n_fun x keep arrays ``w``, ``cond_mean``, ``cond_var``, ``yhat``.
     """
     mi = model_inputs
     coords_new = np.asarray(coords_new, dtype=np.float64).reshape(-1, 2)
@@ -177,10 +237,13 @@ def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), retu
     qs = tuple(float(x) for x in quantiles)
     if not all(0.0 <= x <= 1.0 for x in qs):
         raise ValueError("quantiles must lie in [0, 1]")
+    fun = None if functionals is None else functionals_csr(functionals, coords_new.shape[0])
     anchor = locate(mi["topo"], coords_new, mv_new, device=mcmc.get("device", 0), joint=joint)
     points = dict(coords=coords_new, mv=mv_new, anchor=anchor, X=X_new)
     if joint is not None:
         points["joint"] = joint
+    if fun is not None:
+        points["functionals"] = fun
     theta = np.asarray(mcmc.pop("theta", mi["theta"]), dtype=np.float64)
     kw = dict(set_unif_bounds_in=mi["bounds"], start_w=np.zeros((int(mi["n"]), 1)), theta=theta, beta=np.zeros(int(mi["p"])),
               tausq=0.1, mcmcsd=0.01 * np.eye(theta.size))
