@@ -26,6 +26,7 @@
 
 #include "st_handle.hpp"
 #include "misc_kernels.hpp"
+#include <new>
 
 // ===============================================================================================================
 // host side
@@ -83,6 +84,25 @@ static void launch_stats(st_handle_s *h, hipStream_t st, const double *wt) {
   const StatsKernel k_stats = stats_kernel(h->q, wt != nullptr);
   hipLaunchKernelGGL(k_stats, dim3(STATS_WG, (h->p + 7) / 8), dim3(NT), 0, st, h->d_X.p, h->d_y.p, h->d_w.p, h->d_xb.p, h->d_mv.p,
                      h->d_obs.p, h->d_partner.p, wt, h->n_all, h->p, h->d_partial.p);
+}
+
+// The instantiations of k_factor_quad, in the order of their route codes: chain rows nkx = 32 / 38 / 44 / 50 (`size` 0 .. 3), each as
+// <.., true, true> (reference level, wave Cholesky), <.., true, false> (reference level) and <.., false, true> (leaf) (`kind` 0 .. 2).
+typedef void (*QuadKernel)(QuadArgs, CovPar);
+constexpr int QUAD_SIZES = 4, QUAD_KINDS = 3;
+static QuadKernel quad_kernel(int size, int kind) {
+  static const QuadKernel tab[QUAD_SIZES][QUAD_KINDS] = {
+      {k_factor_quad<4, 32, 8, true, true>, k_factor_quad<4, 32, 8, true, false>, k_factor_quad<4, 32, 8, false, true>},
+      {k_factor_quad<4, 38, 10, true, true>, k_factor_quad<4, 38, 10, true, false>, k_factor_quad<4, 38, 10, false, true>},
+      {k_factor_quad<4, 44, 11, true, true>, k_factor_quad<4, 44, 11, true, false>, k_factor_quad<4, 44, 11, false, true>},
+      {k_factor_quad<4, 50, 13, true, true>, k_factor_quad<4, 50, 13, true, false>, k_factor_quad<4, 50, 13, false, true>}};
+  return tab[size][kind];
+}
+// One launch of k_factor_quad: `nquad` workgroups of four units; returns the route code of the instantiation it took.
+static int launch_quad(int nkx, bool isref, bool wave_chol, int nquad, size_t lds, hipStream_t st, const QuadArgs &F, const CovPar &cp) {
+  const int size = nkx == 32 ? 0 : nkx == 38 ? 1 : nkx == 44 ? 2 : 3, kind = isref ? (wave_chol ? 0 : 1) : 2;
+  hipLaunchKernelGGL(quad_kernel(size, kind), dim3(nquad), dim3(128 * 4), lds, st, F, cp);
+  return R_QUAD32_REF_WCH + QUAD_KINDS * size + kind;
 }
 
 // w or XB is about to change: the cached statistics die; a reduction still in flight on the second stream finishes first
@@ -155,9 +175,9 @@ static bool query_device(int device, DeviceLimits &dl) {
   const void *lc[2] = {(const void *)k_factor_lchain<96>, (const void *)k_factor_lchain<136>};
   for (int i = 0; i < 2; ++i)
     if (hipFuncGetAttributes(&fa, lc[i]) == hipSuccess) { dl.lchain_static[i] = fa.sharedSizeBytes; dl.lchain_no_scratch[i] = fa.localSizeBytes == 0; }
-  if (hipFuncGetAttributes(&fa, (const void *)k_factor_quad<4, 50, 13, false, true>) == hipSuccess) dl.quad_static = fa.sharedSizeBytes;
-  for (const void *f : {(const void *)k_factor_quad<4, 50, 13, true, true>, (const void *)k_factor_quad<4, 50, 13, true, false>})
-    if (hipFuncGetAttributes(&fa, f) == hipSuccess) dl.quad_static = std::max(dl.quad_static, (size_t)fa.sharedSizeBytes);
+  if (hipFuncGetAttributes(&fa, (const void *)quad_kernel(QUAD_SIZES - 1, 2)) == hipSuccess) dl.quad_static = fa.sharedSizeBytes;
+  for (int kind = 0; kind < 2; ++kind)
+    if (hipFuncGetAttributes(&fa, (const void *)quad_kernel(QUAD_SIZES - 1, kind)) == hipSuccess) dl.quad_static = std::max(dl.quad_static, (size_t)fa.sharedSizeBytes);
   return true;
 }
 
@@ -199,7 +219,8 @@ static int create_rows(st_handle_s *h, const st_problem *pb) {
         h->xtx[(size_t)v * pb->p * pb->p + (size_t)b2 * pb->p + a] += pb->X[(size_t)a * n + r] * pb->X[(size_t)b2 * n + r];
   }
   CCHK(hipStreamCreate(&h->stream));
-  CCHK(hipHostMalloc((void **)&h->pin, 64 * sizeof(double), hipHostMallocDefault));
+  CCHK(hipHostMalloc((void **)&h->pin, sizeof(PinnedArea), hipHostMallocDefault));
+  new (h->pin) PinnedArea();
   h->pin_up_len = QMAX + std::max(1, h->p * h->q);
   CCHK(hipHostMalloc((void **)&h->pin_up, (size_t)2 * h->pin_up_len * sizeof(double), hipHostMallocDefault));
   for (int i = 0; i < 2; ++i) CCHK(hipEventCreateWithFlags(&h->ev_up[i], hipEventDisableTiming));
@@ -234,10 +255,10 @@ static int create_layout_buffers(st_handle_s *h) {
   CCHK(upload_or_dummy(h->d_ownobs, h->own_obs_list));
   CCHK(upload_or_dummy(h->d_owngrp, h->own_grp_list)); CCHK(upload_or_dummy(h->d_ownslow, h->own_obs_slow));
   CCHK(h->d_rowmask.upload(h->rowmask)); CCHK(h->d_blkmask.upload(h->blkmask));
-  CCHK(h->d_comm.alloc((size_t)2 * h->n_blocks + 64));
+  CCHK(h->d_comm.alloc((size_t)2 * h->n_blocks + ST_MAX_RANKS));
   CCHK(h->d_gidx.upload(h->gidx));
   CCHK(h->d_gather.alloc(h->gidx.size()));
-  CCHK(h->d_gerr.alloc(64));
+  CCHK(h->d_gerr.alloc(ST_MAX_RANKS));
   CCHK(upload_or_dummy(h->d_toplist, h->top_list));
   CCHK(h->d_err2.alloc(2));
   if (h->scratch_stride) CCHK(h->d_scratch.alloc((size_t)h->scratch_wgs * h->scratch_stride));
@@ -303,12 +324,8 @@ static int create_attributes(st_handle_s *h, const DeviceLimits &dl) {
     dyn(f, lim);
   dyn((const void *)k_factor_lchain<96>, (int)(lc_dyn_doubles(96) * 8));
   dyn((const void *)k_factor_lchain<136>, (int)(lc_dyn_doubles(136) * 8));
-#define QATTR(NU_, NKX_, NKT_)                                                              \
-  dyn((const void *)k_factor_quad<NU_, NKX_, NKT_, true, true>, cu - (int)dl.quad_static);  \
-  dyn((const void *)k_factor_quad<NU_, NKX_, NKT_, true, false>, cu - (int)dl.quad_static); \
-  dyn((const void *)k_factor_quad<NU_, NKX_, NKT_, false, true>, cu - (int)dl.quad_static)
-  QATTR(4, 50, 13); QATTR(4, 44, 11); QATTR(4, 38, 10); QATTR(4, 32, 8);
-#undef QATTR
+  for (int size = QUAD_SIZES - 1; size >= 0; --size)
+    for (int kind = 0; kind < QUAD_KINDS; ++kind) dyn((const void *)quad_kernel(size, kind), cu - (int)dl.quad_static);
   // the top levels are a fixed cost (0.19 ms at n = 1e6: a quarter of a rank's phase A on 8 GPUs, 40 % of phase A at
   // n = 1e5); at n = 1e6 on one GPU the sweep fills the chip and the gain is 1.5 % (SPAMTREE_ASYNC_TOP=0 turns it off)
   h->async_top = h->g_top > 0 && h->sw.async_top;
@@ -422,6 +439,17 @@ static int settle_top(st_handle h) {
   if (h->top_pending) { HCHK(h, hipSetDevice(h->device)); HCHK(h, hipStreamWaitEvent(h->stream, h->ev_top, 0)); }
   return ST_OK;
 }
+// What every launch of k_factor_quad is given alike: `nquad` quads of the groups from grp_first, their records (qr_off < 0: none)
+// of qr_words words, the arena `phys`.  The sites add their own: the component arrays, wave_chol, mode / vscr / vtiles, predict / z / w_out.
+static QuadArgs quad_args(st_handle h, int grp_first, long long qr_off, int qr_words, int nquad, int ldS, int phys, int *errflag) {
+  QuadArgs F;
+  std::memset(&F, 0, sizeof(F));
+  F.blks = h->d_blks.p; F.anc_idx = h->d_anc.p; F.grps = h->d_grps.p + grp_first;
+  F.qrec = qr_off >= 0 ? h->d_qrec.p + qr_off : nullptr; F.qrec_stride = qr_words; F.nquad = nquad;
+  F.cx = h->d_cx.p; F.cy = h->d_cy.p; F.mv = h->d_mv.p; F.w = h->d_w.p; F.panels = h->d_panels[phys].p;
+  F.errflag = errflag; F.ldS = ldS;
+  return F;
+}
 // A slot whose leaf levels ran QM_VONLY gets its leaf panels here (QM_TFROMV, on the launch stream), before anything reads
 // them.  The time counts as phase A: the levels' launch slots (mean per phase-A launch) and the phase bracket, no launch added.
 static int complete_leaf(st_handle h, int slot) {
@@ -433,18 +461,11 @@ static int complete_leaf(st_handle h, int slot) {
   for (int g = 0; g < h->n_actual_groups; ++g) {
     const LevelInfo &L = h->levels[g];
     if (L.vl_off < 0) continue;
-    QuadArgs F;
-    std::memset(&F, 0, sizeof(F));
-    F.blks = h->d_blks.p; F.anc_idx = h->d_anc.p; F.grps = h->d_grps.p + L.grp_first;
-    F.qrec = L.qr_off >= 0 ? h->d_qrec.p + L.qr_off : nullptr; F.qrec_stride = L.qr_words; F.nquad = L.qown_n;
-    F.cx = h->d_cx.p; F.cy = h->d_cy.p; F.mv = h->d_mv.p; F.w = h->d_w.p; F.panels = h->d_panels[phys].p;
-    F.errflag = h->d_err.p; F.ldS = L.q_ldS;
+    QuadArgs F = quad_args(h, L.grp_first, L.qr_off, L.qr_words, L.qown_n, L.q_ldS, phys, h->d_err.p);
     F.wave_chol = L.maxM <= 27 ? 1 : 0;
     F.mode = QM_TFROMV; F.vscr = h->d_vleaf.p + L.vl_off; F.vtiles = quad_vtiles(L.q_nkx);
     ProfScope ps(h, 0, g, 0);
-#define QT(NU_, NKX_, NKT_) hipLaunchKernelGGL((k_factor_quad<NU_, NKX_, NKT_, false, true>), dim3(L.qown_n), dim3(128 * NU_), L.lds_quad, h->stream, F, cp)
-    if (L.q_nkx == 32) QT(4, 32, 8); else if (L.q_nkx == 38) QT(4, 38, 10); else if (L.q_nkx == 44) QT(4, 44, 11); else QT(4, 50, 13);
-#undef QT
+    (void)launch_quad(L.q_nkx, false, true, L.qown_n, L.lds_quad, h->stream, F, cp);   // (the route stays that of the level's launch)
     HCHK(h, hipGetLastError());
   }
   h->leaf_pending[phys] = false;   // (only once every launch is in: after an error the slot still counts as unfinished)
@@ -519,24 +540,39 @@ static void launch_factor(st_handle h, const LevelInfo &L, FactorArgs &A, const 
   hipLaunchKernelGGL((k_factor<BIG, MODE>), dim3(grid), dim3(NT), L.lds_factor, st ? st : h->stream, A, cp);
 }
 
-static int reduce_loglik(st_handle h, int phys, double *loglik) {
+// ---- the read-back protocol (st_protocol.hpp): every result of the iteration comes back as a Landing --------------------------
+static bool uses_exchange(st_handle h) { return h->world > 1 || h->comm; }   // an attached communicator selects the exchange protocol even with one rank (tests)
+// ... without a communicator: the refusal; `alternatives`: the entry points that leave the exchanges to the caller
+static int refuse_without_comm(st_handle h, const char *alternatives) {
+  h->err = std::string("world > 1: call st_comm_init first, or use ") + alternatives;
+  return ST_ERR_USAGE;
+}
+// The sums of a and b (n entries each) on the launch stream, and their copy into dst.
+static int enqueue_result(st_handle h, const double *a, const double *b, int n, Landing *dst) {
   {
     ProfScope ps(h, 3);
-    launch_sum2(h->stream, h->d_logdet[phys].p, h->d_loglik[phys].p, (int)h->n_blocks, h->d_scalars.p + 8, h->d_scalars.p);
+    launch_sum2(h->stream, a, b, n, h->d_scalars.p + 8, h->d_scalars.p);
   }
   HCHK(h, hipGetLastError());
-  double s[2];
-  HCHK(h, hipMemcpyAsync(s, h->d_scalars.p, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  *loglik = s[0] + s[1];   // loglik_w = logdetCi + sum(loglik_w_comps)  (:987-988, :815-816)
+  HCHK(h, hipMemcpyAsync(dst->sums, h->d_scalars.p, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   return ST_OK;
 }
-
-static int read_err(st_handle h, int *code) {
-  int e[2];
-  HCHK(h, hipMemcpyAsync(e, h->d_err.p, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  *code = (e[0] == INT_MAX) ? 0 : (e[0] & 15);
+// ... of a slot's component arrays
+static int enqueue_slot_result(st_handle h, int slot, Landing *dst) {
+  const int phys = h->slot_map[slot];
+  return enqueue_result(h, h->d_logdet[phys].p, h->d_loglik[phys].p, (int)h->n_blocks, dst);
+}
+// ... of the exchanged components (st_mg_pack_comps + all-reduce), with the ranks' failure words behind them
+static int enqueue_comm_result(st_handle h, Landing *dst, double *rank_words) {
+  const int nb = (int)h->n_blocks;
+  if (const int rc = enqueue_result(h, h->d_comm.p, h->d_comm.p + nb, nb, dst)) return rc;
+  HCHK(h, hipMemcpyAsync(rank_words, h->d_comm.p + 2 * (size_t)nb, h->world * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  return ST_OK;
+}
+// The failure word's copy into dst.  On its own because a sweep's word has to leave EARLIER in stream order than the sums: phase C
+// (st_loglik_local) resets it.
+static int enqueue_fail_word(st_handle h, Landing *dst) {
+  HCHK(h, hipMemcpyAsync(dst->err, h->d_err.p, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   return ST_OK;
 }
 static int reset_err(st_handle h) {
@@ -590,24 +626,11 @@ static int factor_launch(st_handle h, int phys, const CovPar &cp, int g_lo = 0, 
     {
       ProfScope ps(h, 0, g, 1, st);
       if (L.fast && h->sw.factor_gen == 3 && L.q_nkx > 0) {
-        QuadArgs F;
-        std::memset(&F, 0, sizeof(F));
-        F.blks = h->d_blks.p; F.anc_idx = h->d_anc.p; F.grps = h->d_grps.p + L.grp_first;
-        F.qrec = L.qr_off >= 0 ? h->d_qrec.p + L.qr_off : nullptr; F.qrec_stride = L.qr_words; F.nquad = L.qown_n;
-        F.cx = h->d_cx.p; F.cy = h->d_cy.p; F.mv = h->d_mv.p; F.w = h->d_w.p; F.panels = h->d_panels[phys].p;
-        F.logdet_c = h->d_logdet[phys].p; F.loglik_c = h->d_loglik[phys].p; F.errflag = errflag; F.ldS = L.q_ldS;
+        QuadArgs F = quad_args(h, L.grp_first, L.qr_off, L.qr_words, L.qown_n, L.q_ldS, phys, errflag);
+        F.logdet_c = h->d_logdet[phys].p; F.loglik_c = h->d_loglik[phys].p;
         F.wave_chol = L.maxM <= 27 ? 1 : 0;
-#define QLAUNCH(NU_, NKX_, NKT_, R_)   /* R_: route code of <.., true, true>; + 1: <.., true, false>; + 2: <.., false, true> */  \
-  do {                                                                                                                         \
-    if (L.isref && F.wave_chol) { route(g, R_); hipLaunchKernelGGL((k_factor_quad<NU_, NKX_, NKT_, true, true>), dim3(L.qown_n), dim3(128 * NU_), L.lds_quad, st, F, cp); } \
-    else if (L.isref) { route(g, R_ + 1); hipLaunchKernelGGL((k_factor_quad<NU_, NKX_, NKT_, true, false>), dim3(L.qown_n), dim3(128 * NU_), L.lds_quad, st, F, cp); } \
-    else {                                                                                                                     \
-      if (vonly && L.vl_off >= 0) { F.mode = QM_VONLY; F.vscr = h->d_vleaf.p + L.vl_off; F.vtiles = quad_vtiles(NKX_); *deferred = true; } \
-      route(g, R_ + 2); hipLaunchKernelGGL((k_factor_quad<NU_, NKX_, NKT_, false, true>), dim3(L.qown_n), dim3(128 * NU_), L.lds_quad, st, F, cp); } \
-  } while (0)
-        if (L.q_nkx == 32) QLAUNCH(4, 32, 8, R_QUAD32_REF_WCH); else if (L.q_nkx == 38) QLAUNCH(4, 38, 10, R_QUAD38_REF_WCH);
-        else if (L.q_nkx == 44) QLAUNCH(4, 44, 11, R_QUAD44_REF_WCH); else QLAUNCH(4, 50, 13, R_QUAD50_REF_WCH);
-#undef QLAUNCH
+        if (!L.isref && vonly && L.vl_off >= 0) { F.mode = QM_VONLY; F.vscr = h->d_vleaf.p + L.vl_off; F.vtiles = quad_vtiles(L.q_nkx); *deferred = true; }
+        route(g, launch_quad(L.q_nkx, L.isref != 0, F.wave_chol != 0, L.qown_n, L.lds_quad, st, F, cp));
       } else if (L.fast) {
         FastArgs F;
         std::memset(&F, 0, sizeof(F));
@@ -705,8 +728,8 @@ static int stats_begin(st_handle h) {
   // the results travel to pinned host memory on the same stream: when the driver asks (after the Metropolis step) they are
   // there, and fetching them costs an event query instead of a copy + a synchronisation of the main stream
   const size_t nq = (size_t)h->p * h->q + h->q;
-  h->stats_prefetched = nq <= 40;
-  if (h->stats_prefetched) HCHK(h, hipMemcpyAsync(h->pin + 20, h->d_stats.p, nq * sizeof(double), hipMemcpyDeviceToHost, h->stream2));
+  h->stats_prefetched = nq <= (size_t)ST_PIN_STATS;
+  if (h->stats_prefetched) HCHK(h, hipMemcpyAsync(h->pin->stats, h->d_stats.p, nq * sizeof(double), hipMemcpyDeviceToHost, h->stream2));
   HCHK(h, hipEventRecord(h->ev_stats, h->stream2));
   h->stats_on_stream2 = true;
   return ST_OK;
@@ -764,21 +787,12 @@ extern "C" int st_mg_pack_comps(st_handle h, int slot, void **dev_ptr, int64_t *
 extern "C" int st_mg_finish(st_handle h, double *loglik) {
   if (!h) return ST_ERR_USAGE;
   HCHK(h, hipSetDevice(h->device));
-  const int nb = (int)h->n_blocks;
-  {
-    ProfScope ps(h, 3);
-    launch_sum2(h->stream, h->d_comm.p, h->d_comm.p + nb, nb, h->d_scalars.p + 8, h->d_scalars.p);
-  }
-  HCHK(h, hipGetLastError());
-  double s2[2], errw[64];
-  HCHK(h, hipMemcpyAsync(s2, h->d_scalars.p, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HCHK(h, hipMemcpyAsync(errw, h->d_comm.p + 2 * (size_t)nb, h->world * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  Landing res;
+  double errc[ST_MAX_RANKS];
+  if (const int rc = enqueue_comm_result(h, &res, errc)) return rc;
   HCHK(h, hipStreamSynchronize(h->stream));
-  int best = INT_MAX;
-  for (int r = 0; r < h->world; ++r) if (errw[r] > 0.5) best = std::min(best, (int)errw[r]);
-  if (best != INT_MAX) return best & 15;
-  if (loglik) *loglik = s2[0] + s2[1];   // loglik_w = logdetCi + sum(loglik_w_comps)  (:987-988, :815-816)
-  return ST_OK;
+  if (const int code = rank_failure(errc, h->world)) return code;
+  return landing_code(res, loglik);
 }
 
 #define NCHK(h, call)                                                                                        \
@@ -819,8 +833,8 @@ extern "C" int st_comm_init(st_handle h, const void *unique_id) {
 static int factor_enqueue(st_handle h, int slot, const double *theta, int ntheta, bool vonly);
 extern "C" int st_factor(st_handle h, int slot, const double *theta, int ntheta, double *loglik) {
   if (!h) return ST_ERR_USAGE;
-  if (h->world > 1 || h->comm) {   // an attached communicator selects the exchange protocol even with one rank (tests)
-    if (!h->comm) { h->err = "world > 1: call st_comm_init first, or use st_factor_local / st_mg_pack_comps / (all-reduce) / st_mg_finish"; return ST_ERR_USAGE; }
+  if (uses_exchange(h)) {
+    if (!h->comm) return refuse_without_comm(h, "st_factor_local / st_mg_pack_comps / (all-reduce) / st_mg_finish");
     int rc = st_factor_local(h, slot, theta, ntheta);
     if (rc) return rc;
     return exchange_comps_and_finish(h, slot, loglik);
@@ -834,7 +848,7 @@ extern "C" int st_factor(st_handle h, int slot, const double *theta, int ntheta,
 // host may enqueue work that does not touch the proposal's slot: the C++ driver draws tausq and beta from the sweep's statistics
 // (ready early in phase A: they run on the second stream) and uploads them, so that XB is current when phase A ends instead of
 // two host round trips later.  With a communicator attached the first half enqueues nothing and the second does all of st_factor.
-extern "C" int st_factor_is_async(st_handle h) { return (h && !(h->world > 1 || h->comm)) ? 1 : 0; }
+extern "C" int st_factor_is_async(st_handle h) { return (h && !uses_exchange(h)) ? 1 : 0; }
 // the proposal's slot (1) defers its leaf levels' T (unless st_options.reserved bit 2); synchronous st_factor never does
 extern "C" int st_factor_enqueue(st_handle h, int slot, const double *theta, int ntheta) {
   return factor_enqueue(h, slot, theta, ntheta, h && h->defer_leaf && slot == 1);
@@ -842,21 +856,14 @@ extern "C" int st_factor_enqueue(st_handle h, int slot, const double *theta, int
 static int factor_enqueue(st_handle h, int slot, const double *theta, int ntheta, bool vonly) {
   if (!h || !theta || slot < 0 || slot > 1) return ST_ERR_USAGE;
   if (h->factor_open) { h->err = "st_factor_enqueue: the previous one has not been finished"; return ST_ERR_USAGE; }
-  if (h->world > 1 || h->comm) {
+  if (uses_exchange(h)) {
     h->factor_open = true; h->factor_open_slot = slot; h->top_theta_open.assign(theta, theta + ntheta);
     return ST_OK;
   }
   int rc = factor_local(h, slot, theta, ntheta, vonly);
   if (rc) return rc;
   // the failure word and the two sums come back in ONE synchronisation (the sums are meaningless after a failure)
-  {
-    ProfScope ps(h, 3);
-    const int phys = h->slot_map[slot];
-    launch_sum2(h->stream, h->d_logdet[phys].p, h->d_loglik[phys].p, (int)h->n_blocks, h->d_scalars.p + 8, h->d_scalars.p);
-  }
-  HCHK(h, hipGetLastError());
-  HCHK(h, hipMemcpyAsync(h->pin + 12, h->d_scalars.p, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HCHK(h, hipMemcpyAsync(h->pin + 14, h->d_err.p, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if ((rc = enqueue_slot_result(h, slot, &h->pin->factor)) || (rc = enqueue_fail_word(h, &h->pin->factor))) return rc;
   HCHK(h, hipEventRecord(h->ev_factor, h->stream));
   h->factor_open = true; h->factor_open_slot = slot; h->top_theta_open.clear();
   return ST_OK;
@@ -865,98 +872,91 @@ extern "C" int st_factor_finish(st_handle h, double *loglik) {
   if (!h) return ST_ERR_USAGE;
   if (!h->factor_open) { h->err = "st_factor_finish without st_factor_enqueue"; return ST_ERR_USAGE; }
   h->factor_open = false;
-  if (h->world > 1 || h->comm) {
-    if (!h->comm) { h->err = "world > 1: call st_comm_init first, or use st_factor_local / st_mg_pack_comps / (all-reduce) / st_mg_finish"; return ST_ERR_USAGE; }
+  if (uses_exchange(h)) {
+    if (!h->comm) return refuse_without_comm(h, "st_factor_local / st_mg_pack_comps / (all-reduce) / st_mg_finish");
     int rc = st_factor_local(h, h->factor_open_slot, h->top_theta_open.data(), (int)h->top_theta_open.size());
     if (rc) return rc;
     return exchange_comps_and_finish(h, h->factor_open_slot, loglik);
   }
   HCHK(h, hipSetDevice(h->device));
   HCHK(h, hipEventSynchronize(h->ev_factor));
-  const int e0 = ((const int *)(h->pin + 14))[0];
-  if (e0 != INT_MAX) return e0 & 15;  // the reference's `return false` (:971-982); deeper levels hold unspecified values (Q5)
-  if (loglik) *loglik = h->pin[12] + h->pin[13];   // loglik_w = logdetCi + sum(loglik_w_comps)  (:987-988)
-  return ST_OK;
+  return landing_code(h->pin->factor, loglik);   // a code: the reference's `return false` (:971-982)
 }
 
-// st_sample_w followed by st_loglik_w(slot) with ONE synchronisation (the sweep's failure word travels with the sums).
-static int gather_w_scatter(st_handle h);
-extern "C" int st_sample_w_loglik(st_handle h, const double *z, uint64_t seed, uint32_t iter, int slot, double *loglik) {
-  if (!h || slot < 0 || slot > 1) return ST_ERR_USAGE;
-  { const int rc0 = complete_leaf(h, slot); if (rc0) return rc0; }
-  if (h->world > 1 || h->comm) {   // an attached communicator selects the exchange protocol even with one rank (tests)
-    if (!h->comm) {
-      int rc = st_sample_w(h, z, seed, iter);   // reports the missing communicator
-      if (rc) return rc;
-      return st_loglik_w(h, slot, loglik);
-    }
-    // Fused exchange: the log-density of a rank's own blocks needs w of its own subtrees and of the replicated top only,
-    // both current BEFORE the other ranks' rows arrive -- so phase C runs ahead of the exchange of w, and w and the
-    // log-density components travel in ONE grouped RCCL call, followed by ONE host synchronisation.
-    int rc = st_sample_w_local(h, z, seed, iter);
-    if (rc) return rc;
-    if (h->top_len > 0) {
-      ProfScope ps(h, 7);
-      NCHK(h, ncclAllReduce(h->d_acc.p + h->top_off, h->d_acc.p + h->top_off, (size_t)h->top_len, ncclDouble, ncclSum, h->comm, h->stream));
-    }
-    rc = st_sample_w_top(h);
-    if (rc) return rc;
-    void *pw = nullptr, *pr = nullptr, *pc = nullptr;
-    int64_t lw = 0, lc = 0;
-    rc = st_mg_gather_w_pack(h, &pw, &pr, &lw);   // own rows of w + this rank's failure word of the sweep
-    if (rc) return rc;
-    rc = st_loglik_local(h, slot);          // resets the failure word after the pack above (stream order)
-    if (rc) return rc;
-    rc = st_mg_pack_comps(h, slot, &pc, &lc);
-    if (rc) return rc;
-    {
-      ProfScope ps(h, 7);
-      NCHK(h, ncclGroupStart());
-      NCHK(h, ncclAllGather(pw, pr, (size_t)lw, ncclDouble, h->comm, h->stream));
-      NCHK(h, ncclAllReduce(pc, pc, (size_t)lc, ncclDouble, ncclSum, h->comm, h->stream));
-      NCHK(h, ncclGroupEnd());
-    }
-    rc = gather_w_scatter(h);
-    if (rc) return rc;
-    invalidate_stats(h);
-    const int nb = (int)h->n_blocks;
-    {
-      ProfScope ps(h, 3);
-      launch_sum2(h->stream, h->d_comm.p, h->d_comm.p + nb, nb, h->d_scalars.p + 8, h->d_scalars.p);
-    }
-    HCHK(h, hipGetLastError());
-    double s2[2], errw[64], errc[64];
-    HCHK(h, hipMemcpyAsync(errw, h->d_gerr.p, h->world * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HCHK(h, hipMemcpyAsync(s2, h->d_scalars.p, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HCHK(h, hipMemcpyAsync(errc, h->d_comm.p + 2 * (size_t)nb, h->world * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HCHK(h, hipStreamSynchronize(h->stream));
-    int best = INT_MAX;
-    for (int r = 0; r < h->world; ++r) if (errw[r] > 0.5) best = std::min(best, (int)errw[r]);
-    if (best != INT_MAX) return best & 15;   // 10 / 11: the reference stops with "Error at gibbs_sample_w" (:1215-1217)
-    for (int r = 0; r < h->world; ++r) if (errc[r] > 0.5) best = std::min(best, (int)errc[r]);
-    if (best != INT_MAX) return best & 15;
-    if (loglik) *loglik = s2[0] + s2[1];
-    return ST_OK;
-  }
+// The sweep and the log-density of its w (one GPU), ENQUEUED with their read-back into dst: the sweep's failure word travels with
+// the sums, so that ONE synchronisation brings both.  10 / 11: the reference stops with "Error at gibbs_sample_w" (:1215-1217).
+static int enqueue_sweep_loglik(st_handle h, const double *z, uint64_t seed, uint32_t iter, int slot, Landing *dst) {
   int rc = st_sample_w_local(h, z, seed, iter);
   if (rc) return rc;
   rc = st_sample_w_top(h);
   if (rc) return rc;
-  HCHK(h, hipMemcpyAsync(h->pin + 2, h->d_err.p, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  rc = enqueue_fail_word(h, dst);
+  if (rc) return rc;
   rc = st_loglik_local(h, slot);   // resets the failure word after the copy above (stream order)
   if (rc) return rc;
-  {
-    ProfScope ps(h, 3);
-    const int phys = h->slot_map[slot];
-    launch_sum2(h->stream, h->d_logdet[phys].p, h->d_loglik[phys].p, (int)h->n_blocks, h->d_scalars.p + 8, h->d_scalars.p);
+  return enqueue_slot_result(h, slot, dst);
+}
+
+// The sweep's exchange (communicator attached) up to the gather-pack: this rank's subtrees, all-reduce of the cut level's message
+// records, the replicated top levels, then the rank's own rows of w and its failure word packed for the all-gather.
+static int gather_w_scatter(st_handle h);
+static int sweep_exchange(st_handle h, const double *z, uint64_t seed, uint32_t iter, void **send, void **recv, int64_t *count) {
+  int rc = st_sample_w_local(h, z, seed, iter);
+  if (rc) return rc;
+  if (h->top_len > 0) {
+    ProfScope ps(h, 7);
+    NCHK(h, ncclAllReduce(h->d_acc.p + h->top_off, h->d_acc.p + h->top_off, (size_t)h->top_len, ncclDouble, ncclSum, h->comm, h->stream));
   }
-  HCHK(h, hipGetLastError());
-  HCHK(h, hipMemcpyAsync(h->pin, h->d_scalars.p, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  rc = st_sample_w_top(h);
+  if (rc) return rc;
+  return st_mg_gather_w_pack(h, send, recv, count);
+}
+
+// st_sample_w followed by st_loglik_w(slot) with ONE synchronisation.
+extern "C" int st_sample_w_loglik(st_handle h, const double *z, uint64_t seed, uint32_t iter, int slot, double *loglik) {
+  if (!h || slot < 0 || slot > 1) return ST_ERR_USAGE;
+  { const int rc0 = complete_leaf(h, slot); if (rc0) return rc0; }
+  if (!uses_exchange(h)) {
+    const int rc = enqueue_sweep_loglik(h, z, seed, iter, slot, &h->pin->sweep);
+    if (rc) return rc;
+    HCHK(h, hipStreamSynchronize(h->stream));
+    return landing_code(h->pin->sweep, loglik);
+  }
+  if (!h->comm) {
+    int rc = st_sample_w(h, z, seed, iter);   // reports the missing communicator
+    if (rc) return rc;
+    return st_loglik_w(h, slot, loglik);
+  }
+  // Fused exchange: the log-density of a rank's own blocks needs w of its own subtrees and of the replicated top only,
+  // both current BEFORE the other ranks' rows arrive -- so phase C runs ahead of the exchange of w, and w and the
+  // log-density components travel in ONE grouped RCCL call, followed by ONE host synchronisation.
+  void *pw = nullptr, *pr = nullptr, *pc = nullptr;
+  int64_t lw = 0, lc = 0;
+  int rc = sweep_exchange(h, z, seed, iter, &pw, &pr, &lw);   // own rows of w + this rank's failure word of the sweep
+  if (rc) return rc;
+  rc = st_loglik_local(h, slot);          // resets the failure word after the pack above (stream order)
+  if (rc) return rc;
+  rc = st_mg_pack_comps(h, slot, &pc, &lc);
+  if (rc) return rc;
+  {
+    ProfScope ps(h, 7);
+    NCHK(h, ncclGroupStart());
+    NCHK(h, ncclAllGather(pw, pr, (size_t)lw, ncclDouble, h->comm, h->stream));
+    NCHK(h, ncclAllReduce(pc, pc, (size_t)lc, ncclDouble, ncclSum, h->comm, h->stream));
+    NCHK(h, ncclGroupEnd());
+  }
+  rc = gather_w_scatter(h);
+  if (rc) return rc;
+  invalidate_stats(h);
+  Landing res;
+  double errw[ST_MAX_RANKS], errc[ST_MAX_RANKS];
+  rc = enqueue_comm_result(h, &res, errc);
+  if (rc) return rc;
+  HCHK(h, hipMemcpyAsync(errw, h->d_gerr.p, h->world * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HCHK(h, hipStreamSynchronize(h->stream));
-  const int e0 = ((const int *)(h->pin + 2))[0];
-  if (e0 != INT_MAX) return e0 & 15;  // 10 / 11: the reference stops with "Error at gibbs_sample_w" (:1215-1217)
-  if (loglik) *loglik = h->pin[0] + h->pin[1];
-  return ST_OK;
+  if (const int code = rank_failure(errw, h->world)) return code;   // the sweep's words first, then the components'
+  if (const int code = rank_failure(errc, h->world)) return code;
+  return landing_code(res, loglik);
 }
 
 // The same pair WITHOUT the host synchronisation: the log-density of the sweep's w is not needed on the host before the
@@ -968,27 +968,15 @@ extern "C" int st_sample_w_loglik_begin(st_handle h, const double *z, uint64_t s
   if (!h || slot < 0 || slot > 1) return ST_ERR_USAGE;
   if (h->c_pending) return ST_ERR_USAGE;
   { const int rc0 = complete_leaf(h, slot); if (rc0) return rc0; }
-  if (h->world > 1 || h->comm) {
+  if (uses_exchange(h)) {
     h->c_ll = 0.0;
     h->c_rc = st_sample_w_loglik(h, z, seed, iter, slot, &h->c_ll);
     if (h->c_rc < 0) return h->c_rc;   // a HIP / RCCL / usage error: nothing is pending, the caller must not call _end
     h->c_pending = true;
     return ST_OK;
   }
-  int rc = st_sample_w_local(h, z, seed, iter);
+  const int rc = enqueue_sweep_loglik(h, z, seed, iter, slot, &h->pin->deferred);
   if (rc) return rc;
-  rc = st_sample_w_top(h);
-  if (rc) return rc;
-  HCHK(h, hipMemcpyAsync(h->pin + 10, h->d_err.p, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  rc = st_loglik_local(h, slot);   // resets the failure word after the copy above (stream order)
-  if (rc) return rc;
-  {
-    ProfScope ps(h, 3);
-    const int phys = h->slot_map[slot];
-    launch_sum2(h->stream, h->d_logdet[phys].p, h->d_loglik[phys].p, (int)h->n_blocks, h->d_scalars.p + 8, h->d_scalars.p);
-  }
-  HCHK(h, hipGetLastError());
-  HCHK(h, hipMemcpyAsync(h->pin + 8, h->d_scalars.p, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   h->c_rc = INT_MIN;   // not known yet
   h->c_pending = true;
   return ST_OK;
@@ -1001,10 +989,7 @@ extern "C" int st_sample_w_loglik_end(st_handle h, double *loglik) {
     return h->c_rc;
   }
   HCHK(h, hipStreamSynchronize(h->stream));   // returns at once when a later call (st_factor) has synchronised already
-  const int e0 = ((const int *)(h->pin + 10))[0];
-  if (e0 != INT_MAX) return e0 & 15;   // 10 / 11: "Error at gibbs_sample_w"
-  if (loglik) *loglik = h->pin[8] + h->pin[9];
-  return ST_OK;
+  return landing_code(h->pin->deferred, loglik);
 }
 
 static int gen_or_upload_z(st_handle h, const double *z, uint64_t seed, uint32_t iter, unsigned stream_id, double *dst) {
@@ -1175,13 +1160,11 @@ extern "C" int st_mg_unpack_w(st_handle h) {
   if (!h) return ST_ERR_USAGE;
   invalidate_stats(h);
   HCHK(h, hipSetDevice(h->device));
-  double errw[64];
+  double errw[ST_MAX_RANKS];
   HCHK(h, hipMemcpyAsync(h->d_w.p, h->d_tmp_n.p, (size_t)h->n_all * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
   HCHK(h, hipMemcpyAsync(errw, h->d_tmp_n.p + h->n_all, h->world * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HCHK(h, hipStreamSynchronize(h->stream));
-  int best = INT_MAX;
-  for (int r = 0; r < h->world; ++r) if (errw[r] > 0.5) best = std::min(best, (int)errw[r]);
-  return best == INT_MAX ? ST_OK : (best & 15);
+  return rank_failure(errw, h->world);
 }
 
 // all-gather form (half the traffic of the all-reduce of n doubles): pack -> all-gather(recv, count per rank) -> unpack
@@ -1211,29 +1194,19 @@ extern "C" int st_mg_gather_w_unpack(st_handle h) {
   HCHK(h, hipSetDevice(h->device));
   int rc = gather_w_scatter(h);
   if (rc) return rc;
-  double errw[64];
+  double errw[ST_MAX_RANKS];
   HCHK(h, hipMemcpyAsync(errw, h->d_gerr.p, h->world * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HCHK(h, hipStreamSynchronize(h->stream));
-  int best = INT_MAX;
-  for (int r = 0; r < h->world; ++r) if (errw[r] > 0.5) best = std::min(best, (int)errw[r]);
-  return best == INT_MAX ? ST_OK : (best & 15);
+  return rank_failure(errw, h->world);
 }
 
 extern "C" int st_sample_w(st_handle h, const double *z, uint64_t seed, uint32_t iter) {
   if (!h) return ST_ERR_USAGE;
-  if (h->world > 1 || h->comm) {   // an attached communicator selects the exchange protocol even with one rank (tests)
-    if (!h->comm) { h->err = "world > 1: call st_comm_init first, or use st_sample_w_local / st_mg_top_region / st_sample_w_top / st_mg_pack_w / st_mg_unpack_w"; return ST_ERR_USAGE; }
-    int rc = st_sample_w_local(h, z, seed, iter);
-    if (rc) return rc;
-    if (h->top_len > 0) {
-      ProfScope ps(h, 7);
-      NCHK(h, ncclAllReduce(h->d_acc.p + h->top_off, h->d_acc.p + h->top_off, (size_t)h->top_len, ncclDouble, ncclSum, h->comm, h->stream));
-    }
-    rc = st_sample_w_top(h);
-    if (rc) return rc;
+  if (uses_exchange(h)) {
+    if (!h->comm) return refuse_without_comm(h, "st_sample_w_local / st_mg_top_region / st_sample_w_top / st_mg_pack_w / st_mg_unpack_w");
     void *snd = nullptr, *rcv = nullptr;
     int64_t cnt = 0;
-    rc = st_mg_gather_w_pack(h, &snd, &rcv, &cnt);
+    int rc = sweep_exchange(h, z, seed, iter, &snd, &rcv, &cnt);
     if (rc) return rc;
     {
       ProfScope ps(h, 7);
@@ -1245,10 +1218,11 @@ extern "C" int st_sample_w(st_handle h, const double *z, uint64_t seed, uint32_t
   if (rc) return rc;
   rc = st_sample_w_top(h);
   if (rc) return rc;
-  int code = 0;
-  rc = read_err(h, &code);
+  Landing res;
+  rc = enqueue_fail_word(h, &res);
   if (rc) return rc;
-  return code;  // 10 / 11: the reference stops with "Error at gibbs_sample_w" (:1215-1217)
+  HCHK(h, hipStreamSynchronize(h->stream));
+  return landing_code(res, nullptr);  // 10 / 11: the reference stops with "Error at gibbs_sample_w" (:1215-1217)
 }
 
 extern "C" int st_loglik_local(st_handle h, int slot) {
@@ -1296,19 +1270,19 @@ static int fix_top_comps(st_handle h, int phys) {
 extern "C" int st_loglik_w(st_handle h, int slot, double *loglik) {
   if (!h) return ST_ERR_USAGE;
   if (slot >= 0 && slot <= 1) { const int rc0 = complete_leaf(h, slot); if (rc0) return rc0; }
-  if (h->world > 1 || h->comm) {   // an attached communicator selects the exchange protocol even with one rank (tests)
-    if (!h->comm) { h->err = "world > 1: call st_comm_init first, or use st_loglik_local / st_mg_pack_comps / (all-reduce) / st_mg_finish"; return ST_ERR_USAGE; }
+  if (uses_exchange(h)) {
+    if (!h->comm) return refuse_without_comm(h, "st_loglik_local / st_mg_pack_comps / (all-reduce) / st_mg_finish");
     int rc = st_loglik_local(h, slot);
     if (rc) return rc;
     return exchange_comps_and_finish(h, slot, loglik);
   }
   int rc = st_loglik_local(h, slot);
   if (rc) return rc;
-  double ll = 0.0;
-  rc = reduce_loglik(h, h->slot_map[slot], &ll);
+  Landing res;
+  rc = enqueue_slot_result(h, slot, &res);
   if (rc) return rc;
-  if (loglik) *loglik = ll;
-  return ST_OK;
+  HCHK(h, hipStreamSynchronize(h->stream));
+  return landing_code(res, loglik);
 }
 
 extern "C" int st_predict(st_handle h, int theta_changed) {
@@ -1324,20 +1298,12 @@ extern "C" int st_predict(st_handle h, int theta_changed) {
   if (rc) return rc;
   const LevelInfo &L = h->pred_info;
   if (h->pred_nkx > 0 && h->pred_quad_count > 0) {
-    QuadArgs F;
-    std::memset(&F, 0, sizeof(F));
-    F.blks = h->d_blks.p; F.anc_idx = h->d_anc.p; F.grps = h->d_grps.p + h->pred_grp_first;
-    F.qrec = h->d_qrec.p + h->pred_qr_off; F.qrec_stride = h->pred_qr_words; F.nquad = h->pred_quad_count;
-    F.cx = h->d_cx.p; F.cy = h->d_cy.p; F.mv = h->d_mv.p; F.w = h->d_w.p; F.panels = h->d_panels[h->slot_map[0]].p;
-    F.logdet_c = nullptr; F.loglik_c = nullptr; F.errflag = h->d_err.p; F.ldS = quad_lds_stride(h->pred_nkx);
+    // (the records exist: layout_levels appends them under this very condition)
+    QuadArgs F = quad_args(h, h->pred_grp_first, h->pred_qr_off, h->pred_qr_words, h->pred_quad_count, quad_lds_stride(h->pred_nkx), h->slot_map[0], h->d_err.p);
     F.wave_chol = 1; F.predict = 1; F.z = h->d_z.p; F.w_out = h->d_w.p;
     {
       ProfScope ps(h, 6);
-      const dim3 grid(h->pred_quad_count), blk(128 * 4);
-      if (h->pred_nkx == 32) { h->route_p = R_QUAD32_LEAF; hipLaunchKernelGGL((k_factor_quad<4, 32, 8, false, true>), grid, blk, h->pred_lds, h->stream, F, cp); }
-      else if (h->pred_nkx == 38) { h->route_p = R_QUAD38_LEAF; hipLaunchKernelGGL((k_factor_quad<4, 38, 10, false, true>), grid, blk, h->pred_lds, h->stream, F, cp); }
-      else if (h->pred_nkx == 44) { h->route_p = R_QUAD44_LEAF; hipLaunchKernelGGL((k_factor_quad<4, 44, 11, false, true>), grid, blk, h->pred_lds, h->stream, F, cp); }
-      else { h->route_p = R_QUAD50_LEAF; hipLaunchKernelGGL((k_factor_quad<4, 50, 13, false, true>), grid, blk, h->pred_lds, h->stream, F, cp); }
+      h->route_p = launch_quad(h->pred_nkx, false, true, h->pred_quad_count, h->pred_lds, h->stream, F, cp);
     }
     HCHK(h, hipGetLastError());
     HCHK(h, hipStreamSynchronize(h->stream));
@@ -1384,7 +1350,7 @@ static int fetch_stats(st_handle h) {
       HCHK(h, hipEventSynchronize(h->ev_stats));
       HCHK(h, hipStreamWaitEvent(h->stream, h->ev_stats, 0));   // later work on the main stream stays ordered behind the reduction
       h->stats_on_stream2 = false;
-      for (size_t i = 0; i < nq; ++i) h->host_stats[i] = h->pin[20 + i];
+      for (size_t i = 0; i < nq; ++i) h->host_stats[i] = h->pin->stats[i];
       h->host_stats_valid = true;
       return ST_OK;
     }

@@ -3,6 +3,7 @@
 // st_destroy) and everything the Gibbs sweep launches; st_points.hip has new-point prediction (st_points_*).
 #pragma once
 #include "tree_layout.hpp"
+#include "st_protocol.hpp"
 #include "simulate_kernels.hpp"
 
 // A device allocation that frees itself; a null buffer makes no HIP call.  (The owner has the device current when it goes.)
@@ -44,7 +45,7 @@ struct st_handle_s : TreeLayout {
   DevBuf<double> d_lcrow;                     // per-row e^2 | log r of the lchain levels (2 n)
   DevBuf<double> d_s0;                        // Ri' Ri of the reference blocks on the generic phase-B path (theta-only, cached with the Gram parts)
   DevBuf<long long> d_s0off;                  // per block: offset into d_s0, -1 = none
-  bool c_pending = false;                     // st_sample_w_loglik_begin: the sweep's failure word and log-density are on their way to pin[8..10]
+  bool c_pending = false;                     // st_sample_w_loglik_begin: the sweep's failure word and log-density are on their way to pin->deferred
   int c_rc = 0; double c_ll = 0.0;            // ... or (multi-GPU / communicator attached) already here
   // multi-GPU sharding
   DevBuf<int> d_ownobs, d_owngrp, d_ownslow;  // this rank's observed blocks; the same set split: column groups of the fast levels / blocks of the others
@@ -61,7 +62,7 @@ struct st_handle_s : TreeLayout {
   bool async_top = false, top_pending = false, prof_suspend = false, async_top_off = false;
   hipEvent_t ev_stats = nullptr;
   bool stats_on_stream2 = false;   // the statistics kernels of the current (w, XB) are in flight on the second stream
-  bool stats_prefetched = false;   // ... and their results follow them to pin[20 ..] on that stream
+  bool stats_prefetched = false;   // ... and their results follow them to pin->stats on that stream
   int top_phys = -1;
   std::vector<double> top_theta;
   bool ext_stream = false;
@@ -72,8 +73,7 @@ struct st_handle_s : TreeLayout {
   bool stats_valid = false;                   // d_stats matches the current w and XB
   bool host_stats_valid = false;              // ... and host_stats holds a copy of it
   std::vector<double> host_stats;
-  double *pin = nullptr;                      // 64 doubles of pinned host memory for the small device-to-host reads: [0..3] st_factor (comm path) /
-                                              // st_loglik_w sums + failure word, [8..11] st_sample_w_loglik_end, [12..15] st_factor_enqueue / _finish, [20..] statistics
+  PinnedArea *pin = nullptr;                  // pinned host memory of the small device-to-host reads, one member per request (st_protocol.hpp)
   double *pin_up = nullptr;                   // pinned staging of the small per-iteration uploads (beta, tausq_inv): two slots taken in turn,
   int pin_up_slot = 0, pin_up_len = 0;        // so that the copy is truly asynchronous and the setters need no host synchronisation
   hipEvent_t ev_up[2] = {nullptr, nullptr};   // recorded behind a slot's copy: a slot is rewritten only after its last copy has run

@@ -2,6 +2,7 @@
 // layout_order and layout_levels is part of the behaviour (which check reports first, which flag a later step sees):
 // DESIGN.md, "st_create in three steps", has the rule.
 #include "tree_layout.hpp"
+#include "st_protocol.hpp"
 
 Switches read_switches() {
   auto level = [](const char *name) {   // 0 / 2 when the value starts with '0' / '2', else (unset too) 1
@@ -62,7 +63,7 @@ static int check_arguments(const st_problem *pb, const st_options *opt, std::str
   if (pb->d != 2) return refuse(msg, ST_ERR_UNSUPPORTED, "only d=2 is reachable from spamtree() (R/spamtree_fit.R:58-60)");
   if (pb->q < 1 || pb->q > QMAX) return refuse(msg, ST_ERR_UNSUPPORTED, "q out of range");
   if (pb->p < 1 || pb->p > ST_MAX_P) return refuse(msg, ST_ERR_UNSUPPORTED, "p must be in 1.." + std::to_string(ST_MAX_P) + " (ST_MAX_P)");
-  if (opt && (opt->world < 1 || opt->rank < 0 || opt->rank >= opt->world || opt->world > 64)) return refuse(msg, ST_ERR_USAGE, "bad rank/world");
+  if (opt && (opt->world < 1 || opt->rank < 0 || opt->rank >= opt->world || opt->world > ST_MAX_RANKS)) return refuse(msg, ST_ERR_USAGE, "bad rank/world");
   // the covariance helpers map a NaN distance to a covariance of 0 (cov_exp clamps with fmax), so a non-finite coordinate
   // would factorise silently instead of failing
   if (pb->n_all > 0 && !pb->coords) return refuse(msg, ST_ERR_USAGE, "st_create: coords is NULL");

@@ -219,3 +219,65 @@ def test_factor_in_two_halves_equals_st_factor():
     hr.deal_with_w(z)
     assert np.array_equal(hm.get_w(), hr.get_w())
     hm.close(); hr.close()
+
+
+def test_four_ways_to_run_the_sweep_are_bitwise_identical(monkeypatch):
+    """One iteration's sweep and the log-density of its w, from the same w, the same supplied normals and the same theta:
+    st_sample_w + st_loglik_w, st_sample_w_loglik, st_sample_w_loglik_begin + _end, and the first two again on a second
+    handle with a one-rank communicator (the exchange protocol: gather-pack, all-gather, k_pack_comps, all-reduce,
+    st_mg_finish / the fused exchange).  They share their steps in the library; w and the log-density are equal to the
+    bit.  The tree (side 25, a tenth of the rows missing, SPAMTREE_QUAD_MIN=1) has a reference level and the leaf level
+    on k_factor_quad and blocks without observed rows (asserted)."""
+    import ctypes as C
+    from spamtree_amd import fit
+    from tests.test_gpu_parity import hip_model
+    monkeypatch.setenv("SPAMTREE_QUAD_MIN", "1")
+    pb = make_problem(side=25, q=1, seed=21, missing=0.1)
+    rng = np.random.default_rng(8)
+    w0, z_warm, z = (rng.standard_normal(pb["n"]) for _ in range(3))
+    dp = C.POINTER(C.c_double)
+    zp = z.ctypes.data_as(dp)
+    n_obs = np.bincount(pb["blocking"] - 1, weights=np.isfinite(pb["y"]).astype(float), minlength=pb["block_names"].size)
+    assert np.any(n_obs == 0)                                    # prediction blocks
+    results = {}
+    for comm in (False, True):
+        hm = hip_model(pb, w=w0, tausq=0.2)
+        lib, h = hm.lib, hm.h
+        if comm:
+            buf = C.create_string_buffer(bytes(fit.make_unique_id()), 128)
+            assert lib.st_comm_init(h, C.cast(buf, C.c_void_p)) == 0
+        assert hm.get_loglik_comps_w(0)
+        quad = [any(k.startswith("k_factor_quad<") for k in lv["A"]) for lv in hm.route_info()["levels"]]
+        assert quad[-1] and quad[-2], quad                       # the leaf level and the last reference level
+        hm.deal_with_w(z_warm)       # (the first sweep after a factorisation also rebuilds the records' Gram parts: other kernels)
+
+        def run(name, sweep):
+            hm.set_w(w0)
+            ll = sweep()
+            results[(name, comm)] = (hm.get_w().copy(), ll)
+
+        def two_calls():
+            hm.deal_with_w(z)
+            return hm.get_loglik_w(0)
+
+        def one_call():
+            ll = C.c_double()
+            assert lib.st_sample_w_loglik(h, zp, 0, 0, 0, C.byref(ll)) == 0
+            return ll.value
+
+        def two_halves():
+            ll = C.c_double()
+            assert lib.st_sample_w_loglik_begin(h, zp, 0, 0, 0) == 0
+            assert lib.st_sample_w_loglik_end(h, C.byref(ll)) == 0
+            return ll.value
+
+        run("st_sample_w + st_loglik_w", two_calls)
+        run("st_sample_w_loglik", one_call)
+        if not comm:
+            run("_begin + _end", two_halves)
+        hm.close()
+    assert len(results) == 5
+    w_ref, ll_ref = results[("st_sample_w + st_loglik_w", False)]
+    assert np.isfinite(ll_ref) and not np.array_equal(w_ref, w0)
+    for key, (w, ll) in results.items():
+        assert np.array_equal(w, w_ref) and ll == ll_ref, key

@@ -38,19 +38,19 @@ def _norm(name):
 
 
 def launched_kernels():
-    """Every instantiation named by a hipLaunchKernelGGL of the host code, the macro and template wrappers expanded."""
+    """Every instantiation named by a hipLaunchKernelGGL of the host code, the kernel table and template wrappers expanded."""
     # (st_points.hip: the C-ABI of new-point prediction; k_points_acc is launched from its own translation unit)
     src = open(SRC).read() + open(SRC_POINTS).read() + open(SRC_POINTS_ACC).read()
     names = set()
     for m in re.finditer(r"hipLaunchKernelGGL\(\s*(\(\s*[A-Za-z_]\w*\s*<[^>]*>\s*\)|[A-Za-z_]\w*)", src):
         names.add(_norm(m.group(1).strip("() ")))
-    # QLAUNCH(NU_, NKX_, NKT_, ...): k_factor_quad<NU_, NKX_, NKT_, ...> once per invocation
-    calls = re.findall(r"QLAUNCH\(\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)\s*,", src)
-    assert calls, "the QLAUNCH macro is no longer invoked: update this parser"
-    for name in [n for n in names if "NU_" in n]:
-        names.discard(name)
-        for nu, nkx, nkt in calls:
-            names.add(name.replace("NU_", nu).replace("NKX_", nkx).replace("NKT_", nkt))
+    # launch_quad launches quad_kernel(size, kind): every instantiation of k_factor_quad in that function's table
+    assert "quad_kernel" in names, "k_factor_quad is no longer launched through quad_kernel: update this parser"
+    names.discard("quad_kernel")
+    table = re.search(r"static QuadKernel quad_kernel\(.*?\n}\n", src, re.S)
+    quads = {_norm(q) for q in re.findall(r"k_factor_quad<[^>]*>", table.group(0))}
+    assert len(quads) == 12, quads
+    names |= quads
     # launch_factor<BIG, MODE>: k_factor<BIG, MODE> for every instantiation of the wrapper
     wraps = set(re.findall(r"launch_factor<\s*(true|false)\s*,\s*(MODE_\w+)\s*>", src))
     assert wraps, "launch_factor is no longer instantiated: update this parser"
