@@ -178,6 +178,10 @@ int st_probe_peaks(int device, int64_t bytes, int reps, double *out3);
 /* the covariance kernels' elementary functions (csrc/st_device.hpp), evaluated on the device through the same inlined helpers
  * (csrc/probe.hip; no handle needed): out[i] = f(x[i]), f = cov_sqrt (fn 0), cov_exp (1), cov_exp_tab (2). */
 int st_probe_math(int32_t fn, const double *x, int64_t n, int32_t device, double *out);
+/* the leaf factor kernel's sum over groups of ns (8 or 16) consecutive lanes of a wave (csrc/st_device.hpp: group_xor_sum, DPP
+ * moves; dpp = 0: the __shfl_xor butterfly with the same partners and order), one value per lane: out[i] = the sum of x over
+ * lane i's group.  n: a multiple of 64 (one wave per 64 values). */
+int st_probe_group_sum(int32_t ns, int32_t dpp, const double *x, int64_t n, int32_t device, double *out);
 /* per-kernel-family device time from HIP events recorded on the launch stream around every launch (enable=1), or around
  * the phase-A launches only (enable=2: the roofline measurement at a third of the event traffic; ~60 event records per
  * iteration cost 4-6 % of the iteration at n = 1e6).  Events are harvested lazily: no host synchronisation is added.

@@ -57,6 +57,7 @@ SIGNATURES = {
     "st_factor_ahead_enable": (C.c_int, [H, C.c_int]),
     "st_probe_peaks": (C.c_int, [C.c_int, C.c_int64, C.c_int, c_dp]),
     "st_probe_math": (C.c_int, [C.c_int32, c_dp, C.c_int64, C.c_int32, c_dp]),
+    "st_probe_group_sum": (C.c_int, [C.c_int32, C.c_int32, c_dp, C.c_int64, C.c_int32, c_dp]),
     "st_profile_enable": (C.c_int, [H, C.c_int]),
     "st_profile_get": (C.c_int, [H, c_dp, c_ip]),
     "st_profile_levels": (C.c_int, [H, C.POINTER(C.c_int32), c_dp, c_dp, C.c_int32]),

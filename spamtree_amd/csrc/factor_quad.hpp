@@ -366,15 +366,40 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
     return (d4){__builtin_nontemporal_load(d), __builtin_nontemporal_load(d + 64), __builtin_nontemporal_load(d + 128),
                 __builtin_nontemporal_load(d + 192)};
   };
-  // g of one staged row per group of NS consecutive lanes (sub = lane % NS; one accumulator per lane, the group's sum complete
-  // in each of its lanes)
-  auto grow = [&](const double *row, int len, int wlim, const double *pw, int sub, auto ns) __attribute__((always_inline)) {
-    constexpr int NS = decltype(ns)::value;
+  // g of one staged row per group of NS consecutive lanes (sub = lane % NS): s = fma(row[k], w[k], s) for k = sub, sub + NS, ...
+  // < len, in that order into ONE accumulator per lane, then the group's xor butterfly (the complete sum in each of its lanes).
+  // The operands of NB trips are requested TOGETHER before the batch's first fma: one LDS round trip per batch (as a loop of
+  // single products every trip was a fully exposed round trip, and every wave of the workgroup makes them at the same time,
+  // ahead of a barrier).  A trip with k >= len leaves s untouched -- it adds no product with zero; what it read (inside the
+  // staged rows / the record) is dropped.  w[k] = s_wpa[k] below wlim, beyond it the double at index k + pwo of the record
+  // (the unit's private rows).
+  //   * V-only body (no T accumulators): the loop is unrolled to its compile-time bound, ceil(PMAX / NS) trips, in ONE batch
+  //     -- one round trip per row; wreg != nullptr: the lane's w operands, already in registers.
+  //   * full body (at its register limit): a rolled loop over batches of 3 (shared step: 5 round trips instead of 13) or 5
+  //     trips (private sub-panel: 5 instead of 25) up to lmax (wave-uniform, >= len) -- the deepest batches at which no
+  //     instantiation gains a register; unrolled, the same batches cost 14 registers at every NKX and spills at NKX 50.
+  constexpr bool gdeep = QM == QM_VONLY;
+  const bool needg = !(QM == QM_FULL && A.predict);   // phase P takes hv = T w_pa and never reads hacc: no g (workgroup-uniform)
+  auto grow = [&](const double *row, int len, int lmax, int wlim, int pwo, const double *wreg, int sub, auto ns) __attribute__((always_inline)) {
+    constexpr int NS = decltype(ns)::value, NTR = (PMAX + NS - 1) / NS, NB = gdeep ? NTR : (NS == 8 ? 5 : 3);
+    const double *rec = (const double *)&s_q;
     double s = 0.0;
-    for (int k = sub; k < len; k += NS) s = fma(row[k], k < wlim ? s_wpa[k] : pw[k - wlim], s);
+#pragma unroll 1
+    for (int k0 = sub; k0 < (gdeep ? sub + 1 : lmax); k0 += NB * NS) {   // (V-only body: one pass)
+      double a[NB], wv[NB];
 #pragma unroll
-    for (int o = NS >> 1; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
-    return s;
+      for (int i = 0; i < NB; ++i) {
+        const int k = k0 + NS * i;
+        a[i] = row[k];
+        wv[i] = wreg ? wreg[i] : rec[k + (k < wlim ? o_wpa : pwo)];
+      }
+#pragma unroll
+      for (int i = 0; i < NB; ++i) {
+        const double t = fma(a[i], wv[i], s);
+        s = k0 + NS * i < len ? t : s;
+      }
+    }
+    return group_xor_sum<NS>(s);
   };
 
 #define QMFMA(a_, b_, c_) c_ = __builtin_amdgcn_mfma_f64_16x16x4f64(a_, b_, c_, 0, 0, 0)
@@ -436,7 +461,7 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
       } else {
         // explicit fma chains: the same bits in every mode, whatever the compiler would contract
         dacc = fma(p[3], p[3], fma(p[2], p[2], fma(p[1], p[1], fma(p[0], p[0], dacc))));
-        if (QM != QM_TFROMV) hacc = fma(p[3], gt[l4 + 12], fma(p[2], gt[l4 + 8], fma(p[1], gt[l4 + 4], fma(p[0], gt[l4], hacc))));
+        if (QM != QM_TFROMV && needg) hacc = fma(p[3], gt[l4 + 12], fma(p[2], gt[l4 + 8], fma(p[1], gt[l4 + 4], fma(p[0], gt[l4], hacc))));
       }
     }
     // QM_VONLY: the tile goes out at once
@@ -482,12 +507,14 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
           if (row >= sr && stride == 16) for (int k = lane; k < p_Kb + 24; k += 64) buf[(size_t)row * ldS + k] = 0.0;   // absent rows of the tile
         }
         const int r0 = sp == 0 ? 0 : p_sr0;
-        if (QM != QM_TFROMV) {   // g of the rows this wave staged, 8 lanes per row (zero for absent rows: they meet V rows of zeros)
+        STAMP(2);
+        if (QM != QM_TFROMV && needg) {   // g of the rows this wave staged, 8 lanes per row (zero for absent rows: they meet V rows of zeros)
           const int row = jt + 2 * (lane >> 3);
-          double gv = 0.0;
-          if (row < sr) gv = grow(buf + (size_t)row * ldS, p_Kb, Pc, s_pw[u], lane & 7, std::integral_constant<int, 8>());
+          const double gv = grow(buf + (size_t)row * ldS, row < sr ? p_Kb : 0, p_Kb, Pc, o_pw + u * Rec::NLD - Pc, nullptr, lane & 7,
+                                 std::integral_constant<int, 8>());
           if ((lane & 7) == 0) s_gp[u][r0 + row] = gv;
         }
+        STAMP(15);
         lds_barrier();
         if (sp == 1 && pf) issue(0, arena + (size_t)48 * ldS);
         // (row i of the sub-panel is chain row Pc + r0 + i of a LOWER-TRIANGULAR factor: nothing beyond column Pc + r0 + sr)
@@ -516,6 +543,13 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
   {
     if constexpr (!ISREF) { if (nit > 0 && !pf) issue(0, arena); }   // (reference quads: requested before the covariance pass)
     int cur = pf ? 1 : 0;
+    // V-only body: the lane's w operands of grow (s_wpa[lane % NS + NS i], the same on every step) stay in registers over the loop
+    constexpr int NSG = 64 / RP, NTG = (!ISREF && gdeep) ? (PMAX + NSG - 1) / NSG : 1;
+    double wsh[NTG];
+    if (!ISREF && gdeep) {
+#pragma unroll
+      for (int i = 0; i < NTG; ++i) wsh[i] = ((const double *)&s_q)[o_wpa + lane % NSG + NSG * i];
+    }
     // QM_TFROMV: the V tiles of step i + 1 are requested when step i starts -- this step's in kx[0..7], the next step's in
     // kx[8..15] (no covariance pass: free registers); QM_VONLY stores each tile as soon as it is formed (tile)
     if (QM == QM_TFROMV && wact && nit > 0) { kset(0, vload(2)); if (Pc - 32 * (nit - 1) > 16) kset(4, vload(3)); }
@@ -538,17 +572,18 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
           for (int k = lane; k < Kb + 24; k += 64) buf[(size_t)row * ldS + k] = 0.0;   // absent rows of a tile in use (first step only)
         }
       }
-      if (!ISREF && QM != QM_TFROMV) {   // g of the rows this wave staged, 64 / RP lanes per row (zero for absent rows)
+      STAMP(5);
+      if (!ISREF && QM != QM_TFROMV && needg) {   // g of the rows this wave staged, 64 / RP lanes per row (zero for absent rows)
         constexpr int NS = 64 / RP;
         const int rq = lane / NS, row = wid + NW * rq;
         int len = rlen_cur[0];
 #pragma unroll
         for (int rr = 1; rr < RP; ++rr) len = rq == rr ? rlen_cur[rr] : len;
-        double gv = 0.0;
-        if (row < sr) gv = grow(buf + (size_t)row * ldS, len, PMAX, s_wpa, lane % NS, std::integral_constant<int, NS>());
+        const double gv = grow(buf + (size_t)(row < sr ? row : 0) * ldS, row < sr ? len : 0, Kb, 1 << 30, 0, gdeep ? wsh : nullptr, lane % NS,
+                               std::integral_constant<int, NS>());
         if (lane % NS == 0) s_g[cur][row] = gv;
       }
-      STAMP(5);
+      STAMP(14);
       lds_barrier();
       STAMP(3);
       if (i + 1 < nit) issue(i + 1, arena + (size_t)(cur ^ 1) * 32 * ldS);

@@ -1,7 +1,8 @@
 // Box-measured peaks for the roofline report (bench.py `roofline.peak_measured`; BASELINE.md section 3 asks for a stream-copy
 // and an FP64 FMA / MFMA peak measured on the box next to the vendor figures).  Not on the product path: three self-contained
 // kernels timed with HIP events on a private stream, about 50 ms each.  Also st_probe_math: the covariance kernels' elementary
-// functions evaluated through the very helpers they inline (tests/test_gpu_device_math.py).
+// functions evaluated through the very helpers they inline (tests/test_gpu_device_math.py), and st_probe_group_sum: the leaf factor
+// kernel's lane-group sum beside the shuffle butterfly it replaces (tests/test_gpu_leaf_g.py).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -79,6 +80,17 @@ __global__ __launch_bounds__(256) void k_probe_math(int fn, const double *__rest
     const double v = x[i];
     out[i] = fn == 0 ? cov_sqrt(v) : fn == 1 ? cov_exp(v) : cov_exp_tab(v, tab);
   }
+}
+
+// out[i] = the sum over lane i's group of NS consecutive lanes of a 64-lane wave, by the DPP butterfly the leaf factor kernel uses
+// (dpp = 1) or by the __shfl_xor butterfly it replaces (dpp = 0); one value per lane, n a multiple of 64
+__global__ __launch_bounds__(64) void k_probe_group_sum(int ns, int dpp, const double *__restrict__ x, double *__restrict__ out) {
+  const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
+  const double v = x[i];
+  double r;
+  if (ns == 8) r = dpp ? group_xor_sum<8>(v) : group_xor_sum_shfl<8>(v);
+  else r = dpp ? group_xor_sum<16>(v) : group_xor_sum_shfl<16>(v);
+  out[i] = r;
 }
 
 #define PCHK(call)                          \
@@ -160,6 +172,25 @@ extern "C" int st_probe_math(int32_t fn, const double *x, int64_t n, int32_t dev
   } else {
     const long long nb = std::min<long long>((n + 255) / 256, 4096);
     hipLaunchKernelGGL(k_probe_math, dim3((unsigned)nb), dim3(256), 0, 0, (int)fn, (const double *)dx, (long long)n, dy);
+    if (hipGetLastError() != hipSuccess || hipMemcpy(out, dy, bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = ST_ERR_HIP;
+  }
+  if (dx) (void)hipFree(dx);
+  if (dy) (void)hipFree(dy);
+  return rc;
+}
+
+extern "C" int st_probe_group_sum(int32_t ns, int32_t dpp, const double *x, int64_t n, int32_t device, double *out) {
+  if ((ns != 8 && ns != 16) || (dpp != 0 && dpp != 1) || n < 0 || n % 64 != 0 || n > (int64_t)64 * 65535 || (n > 0 && (!x || !out)))
+    return ST_ERR_USAGE;
+  if (n == 0) return ST_OK;
+  int rc = ST_OK;
+  double *dx = nullptr, *dy = nullptr;
+  const size_t bytes = (size_t)n * sizeof(double);
+  if (hipSetDevice(device) != hipSuccess || hipMalloc(&dx, bytes) != hipSuccess || hipMalloc(&dy, bytes) != hipSuccess ||
+      hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    rc = ST_ERR_HIP;
+  } else {
+    hipLaunchKernelGGL(k_probe_group_sum, dim3((unsigned)(n / 64)), dim3(64), 0, 0, (int)ns, (int)dpp, (const double *)dx, dy);
     if (hipGetLastError() != hipSuccess || hipMemcpy(out, dy, bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = ST_ERR_HIP;
   }
   if (dx) (void)hipFree(dx);

@@ -332,7 +332,36 @@ __device__ __forceinline__ double wave_allsum(double x) {
   return ((r0 + r1) + r2) + r3;
 }
 
-typedef __attribute__((address_space(3))) void q_lds_void;          // LDS-DMA destinations / sources (global_load_lds)
+// The xor butterfly over groups of NS (8 or 16) consecutive lanes -- s += s[lane ^ o] for o = NS / 2, ..., 1, the complete sum
+// in every lane of the group -- with the partners and the order of the __shfl_xor loop, so the same bits in every lane, but
+// without its LDS round trips (a ds_bpermute pair and a wait per exchange): the partners sit in one 16-lane row and are
+// reached by DPP moves of the two 32-bit halves.  xor 8 = row_ror:8; xor 4 = row_shl:4 for the banks whose lanes have bit 2
+// clear (0 and 2: the partner is 4 lanes up) and row_shr:4 for the others; xor 2, xor 1 = quad_perm [2,3,0,1], [1,0,3,2].
+// Every lane of a group must be active or none.
+template <int CTRL, int BANKS>
+__device__ __forceinline__ double dpp_mov_f64(double old, double x) {
+  const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(x), CTRL, 0xf, BANKS, false);
+  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(x), CTRL, 0xf, BANKS, false);
+  return __hiloint2double(hi, lo);
+}
+template <int NS>
+__device__ __forceinline__ double group_xor_sum(double s) {
+  static_assert(NS == 8 || NS == 16, "groups of 8 or 16 lanes");
+  if (NS == 16) s += dpp_mov_f64<0x128, 0xf>(s, s);
+  s += dpp_mov_f64<0x114, 0xa>(dpp_mov_f64<0x104, 0x5>(s, s), s);
+  s += dpp_mov_f64<0x4e, 0xf>(s, s);
+  s += dpp_mov_f64<0xb1, 0xf>(s, s);
+  return s;
+}
+// ... and the loop it replaces (csrc/probe.hip compares the two bit by bit)
+template <int NS>
+__device__ __forceinline__ double group_xor_sum_shfl(double s) {
+#pragma unroll
+  for (int o = NS >> 1; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+  return s;
+}
+
+typedef __attribute__((address_space(3))) void q_lds_void;         // LDS-DMA destinations / sources (global_load_lds)
 typedef __attribute__((address_space(1))) const void q_glb_void;
 #define CH_LD 33
 
