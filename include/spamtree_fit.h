@@ -116,6 +116,28 @@ int stm_mcmc_functionals(const st_problem *pb, const st_options *opt, const doub
                          double *new_w_mean, double *new_yhat_mean, double *new_w_q, double *new_yhat_q, int32_t *new_route,
                          double *new_cond_cov, double *new_cov, const stm_functionals *fun);
 
+/* Scores of held-out observations at the new points (include/spamtree_hip.h, st_points_score_*).  stm_points_score_set:
+ * st_points_score_set on the chain's point set; call it after stm_points_set(_joint) and before the first iteration.
+ * stm_mcmc_scored is stm_mcmc_functionals plus the scores: y_new (n_new, NaN = not scored; NULL: no scores, the call is
+ * stm_mcmc_functionals itself) and their outputs, any of which may be NULL: lpd, pit, crps (n_new), lpd_joint (one per joint group;
+ * needs joint_id_new), n_scored, n_degenerate (one each).  crps needs keep_draws >= 1, the scores X_new.  It consumes no draw of any
+ * stream and changes no chain state: every output stm_mcmc_functionals also produces is the same bit for bit. */
+typedef struct stm_scores {
+  const double *y_new;
+  double *lpd, *pit, *crps, *lpd_joint;
+  int64_t *n_scored, *n_degenerate;
+} stm_scores;
+int stm_points_score_set(stm_chain c, const double *y_new);
+int stm_mcmc_scored(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
+                    int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
+                    int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc, double *beta_mcmc,
+                    double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time, int64_t n_new,
+                    const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new, const double *X_new,
+                    const int64_t *joint_id_new, int64_t keep_draws, const double *quantiles, int32_t n_quantiles, double *new_w,
+                    double *new_cond_mean, double *new_cond_var, double *new_yhat, double *new_mean, double *new_var,
+                    double *new_w_mean, double *new_yhat_mean, double *new_w_q, double *new_yhat_q, int32_t *new_route,
+                    double *new_cond_cov, double *new_cov, const stm_functionals *fun, const stm_scores *scores);
+
 #ifdef __cplusplus
 }
 #endif

@@ -339,6 +339,34 @@ int st_points_functionals_get(st_handle h, double *mean, double *var, double *w_
 int st_points_functionals_quantile(st_handle h, double q, double *w_q, double *yhat_q);
 int st_points_functionals_info(st_handle h, int64_t *n_fun, int64_t *nnz, int64_t *n_chunks, int64_t *n_var_terms, double *alg_bytes);
 
+/* ---- scores of held-out observations at the new points.  A scored point i of margin j has an observed y_i; saved draw s gives it
+ * the Gaussian predictive mu_s = x_i'beta_j + cond_mean_s(i), sigma2_s = cond_var_s(i) + tau2_j (cond_var as st_points_accumulate
+ * forms it, clamped at 0; tau2_j = 1 / tausq_inv_j).  With r_s = (y_i - mu_s) / sigma_s, l_s = -r_s^2 / 2 - log sigma_s - log(2 pi) / 2
+ * and the S draws accumulated since the scores were set:
+ *   lpd_i  = log((1 / S) sum_s exp l_s), a streaming log-sum-exp (two doubles of state per point; finite when every exp l_s underflows)
+ *   pit_i  = (1 / S) sum_s Phi(r_s)
+ *   crps_i = (1 / K) sum_k |d_(k)| - (1 / K^2) sum_k (2 k - K - 1) d_(k), d_k = yhat*_k - y_i sorted ascending: the CRPS of the
+ *            empirical distribution of the K stored yhat* draws of the point (st_points_summary_reserve)
+ * and, on a joint set, per group G with observed members o (in member order, g_o >= 1)
+ *   lpd_joint_G = log((1 / S) sum_s N_{g_o}(y_o; mu_o, Sigma_oo + diag tau2)), Sigma the draw's cond_cov (lower triangle, not clamped),
+ *            factorised by an unpivoted Cholesky.  A pivot that is not > 0 gives that draw density 0 for that group and adds one
+ *            to n_degenerate.
+ * st_points_score_set: y_new holds n_new values in the caller's order; NaN: the point is predicted as before and not scored.  NULL
+ *   removes the scores.  Needs a point set with X (ST_ERR_USAGE); an infinite value is ST_ERR_USAGE naming the index, and the
+ *   previous scores then stay.  Replaces the previous scores and zeroes their state; the point, pair and functional summaries are
+ *   left alone.  st_points_set / st_points_set_joint drop the scores, st_points_summary_reset clears their state.
+ * With scores set, st_points_accumulate(_joint) also runs the score step after its summaries, on the same stream: it reads this
+ *   iteration's outputs, X, beta and tausq_inv, consumes no draw of any stream and writes nothing another step reads, so every
+ *   other output is the same bit for bit; with NULL outputs it still copies nothing and synchronises nothing.  The order of every
+ *   operation is fixed (spamtree_amd/csrc/points_score.hpp): a point's or group's scores depend on its own inputs only, bit for bit.
+ * st_points_score_get: lpd, pit, crps (n_new each; NaN where y_new is), lpd_joint (one per joint group in st_points_joint_layout's
+ *   order; NaN for a group without an observed member; -inf when no draw had a positive density), n_scored, n_degenerate.  Any may
+ *   be NULL.  ST_ERR_USAGE: before st_points_score_set, no scored point (n_scored is still written), no iteration accumulated,
+ *   crps without a stored draw, lpd_joint on a plain set.
+ * Both refuse limited_tree and world > 1 handles (ST_ERR_UNSUPPORTED). */
+int st_points_score_set(st_handle h, const double *y_new);
+int st_points_score_get(st_handle h, double *lpd, double *pit, double *crps, double *lpd_joint, int64_t *n_scored, int64_t *n_degenerate);
+
 /* ---- prior simulation from slot 0: exact draws w ~ N(0, C_DAG) of the tree's own model and y = XB + w + sqrt(tau^2_j) eps.
  * st_simulate: a root-to-leaf sweep over slot 0 as the last st_factor(h, 0, theta) left it (a deferred leaf half is finished
  *   first), Ri_u w_u = z_u - N_u w_pa(u) per block, with the handle's current beta (XB) and tau^-2.  nd draws (1..16) in one

@@ -114,6 +114,8 @@ SIGNATURES = {
     "st_points_functionals_get": (C.c_int, [H, c_dp, c_dp, c_dp, c_dp, c_ip]),
     "st_points_functionals_quantile": (C.c_int, [H, C.c_double, c_dp, c_dp]),
     "st_points_functionals_info": (C.c_int, [H, c_ip, c_ip, c_ip, c_ip, c_dp]),
+    "st_points_score_set": (C.c_int, [H, c_dp]),
+    "st_points_score_get": (C.c_int, [H, c_dp, c_dp, c_dp, c_dp, c_ip, c_ip]),
     "st_simulate": (C.c_int, [H, C.c_int, c_dp, c_dp, C.c_uint64, C.c_uint32, c_dp, c_dp]),
     "st_simulate_info": (C.c_int, [H, C.c_int, C.POINTER(C.c_int32), c_dp, c_dp]),
     "st_simulate_route_name": (C.c_char_p, [C.c_int32]),
@@ -130,6 +132,11 @@ class StmFunctionals(C.Structure):   # include/spamtree_fit.h, stm_functionals
                 ("fun_w", c_dp), ("fun_cond_mean", c_dp), ("fun_cond_var", c_dp), ("fun_yhat", c_dp),
                 ("fun_mean", c_dp), ("fun_var", c_dp), ("fun_w_mean", c_dp), ("fun_yhat_mean", c_dp),
                 ("fun_w_q", c_dp), ("fun_yhat_q", c_dp)]
+
+
+class StmScores(C.Structure):   # include/spamtree_fit.h, stm_scores
+    _fields_ = [("y_new", c_dp), ("lpd", c_dp), ("pit", c_dp), ("crps", c_dp), ("lpd_joint", c_dp),
+                ("n_scored", c_ip), ("n_degenerate", c_ip)]
 
 
 # include/spamtree_fit.h (C++ host driver)
@@ -161,7 +168,9 @@ SIGNATURES.update({
                                        c_dp, c_dp, C.c_int64, c_dp, c_ip, c_ip, c_dp, c_ip, C.c_int64, c_dp, C.c_int32, c_dp,
                                        c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, C.POINTER(C.c_int32), c_dp, c_dp,
                                        C.POINTER(StmFunctionals)]),
+    "stm_points_score_set": (C.c_int, [H, c_dp]),
 })
+SIGNATURES["stm_mcmc_scored"] = (C.c_int, SIGNATURES["stm_mcmc_functionals"][1] + [C.POINTER(StmScores)])
 
 # include/spamtree_tree.h (device parts of the tree builder)
 c_i32p = C.POINTER(C.c_int32)

@@ -40,6 +40,26 @@ struct QtArgs {
   double *out;
 };
 
+// The sort of k_qtile, shared with k_score_crps (k_points_score.hip): R rows of K = 2^k doubles each in LDS (row r at lds + r K),
+// every row sorted ascending by a bitonic network over the NT threads of the workgroup.  The rows are in LDS behind a barrier on
+// entry and sorted behind one on return.
+__device__ __forceinline__ void qt_sort_rows(double *lds, int R, int K, int tid) {
+  const int half = K >> 1;
+  for (int k = 2; k <= K; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int p = tid; p < R * half; p += NT) {
+        const int r = p / half, i = p - r * half;
+        const int i1 = 2 * j * (i / j) + (i % j), i2 = i1 + j;
+        double *a = lds + (size_t)r * K;
+        const double x = a[i1], y = a[i2];
+        const bool up = (i1 & k) == 0;
+        if ((x > y) == up) { a[i1] = y; a[i2] = x; }
+      }
+      __syncthreads();
+    }
+  }
+}
+
 #ifdef ST_DEFS_MISC
 __global__ void k_normals(double *z, const long long *dev2model, long long n, unsigned iter, unsigned stream, unsigned long long seed) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -336,20 +356,7 @@ __global__ __launch_bounds__(NT) void k_qtile(QtArgs A) {
     lds[(size_t)r * K + d] = v;
   }
   __syncthreads();
-  const int half = K >> 1;
-  for (int k = 2; k <= K; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int p = tid; p < R * half; p += NT) {
-        const int r = p / half, i = p - r * half;
-        const int i1 = 2 * j * (i / j) + (i % j), i2 = i1 + j;
-        double *a = lds + (size_t)r * K;
-        const double x = a[i1], y = a[i2];
-        const bool up = (i1 & k) == 0;
-        if ((x > y) == up) { a[i1] = y; a[i2] = x; }
-      }
-      __syncthreads();
-    }
-  }
+  qt_sort_rows(lds, R, K, tid);
   if (tid < R && row0 + tid < A.n) {
     const double *a = lds + (size_t)tid * K;
     const int len = A.keep;

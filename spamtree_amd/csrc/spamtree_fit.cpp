@@ -420,6 +420,13 @@ extern "C" int stm_points_functionals_set(stm_chain c, int64_t n_fun, const int6
   return ST_OK;
 }
 
+extern "C" int stm_points_score_set(stm_chain c, const double *y_new) {
+  if (!c || !c->h) return ST_ERR_USAGE;
+  const int rc = st_points_score_set(c->h, y_new);
+  if (rc != 0) { c->err = st_last_error(c->h); return rc; }
+  return ST_OK;
+}
+
 namespace {
 struct FitPoints {   // the point set of stm_mcmc_points and where its per-draw outputs go (n_new x keep, any may be NULL)
   int64_t n;
@@ -537,7 +544,6 @@ extern "C" int stm_mcmc_points_joint(const st_problem *pb, const st_options *opt
                               new_w_mean, new_yhat_mean, new_w_q, new_yhat_q, new_route, new_cond_cov, new_cov, nullptr);
 }
 
-// fun NULL: stm_mcmc_points_joint itself
 extern "C" int stm_mcmc_functionals(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
                                     int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
                                     int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
@@ -548,7 +554,26 @@ extern "C" int stm_mcmc_functionals(const st_problem *pb, const st_options *opt,
                                     double *new_mean, double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q,
                                     double *new_yhat_q, int32_t *new_route, double *new_cond_cov, double *new_cov,
                                     const stm_functionals *fun) {
+  return stm_mcmc_scored(pb, opt, set_unif_bounds, theta, ntheta, beta, tausq, mcmcsd, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc,
+                         yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time, n_new, coords_new, mv_new, anchor_new, X_new,
+                         joint_id_new, keep_draws, quantiles, n_quantiles, new_w, new_cond_mean, new_cond_var, new_yhat, new_mean, new_var,
+                         new_w_mean, new_yhat_mean, new_w_q, new_yhat_q, new_route, new_cond_cov, new_cov, fun, nullptr);
+}
+
+// fun NULL: stm_mcmc_points_joint itself; scores NULL: stm_mcmc_functionals itself
+extern "C" int stm_mcmc_scored(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
+                                    int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
+                                    int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
+                                    double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
+                                    int64_t n_new, const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new,
+                                    const double *X_new, const int64_t *joint_id_new, int64_t keep_draws, const double *quantiles,
+                                    int32_t n_quantiles, double *new_w, double *new_cond_mean, double *new_cond_var, double *new_yhat,
+                                    double *new_mean, double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q,
+                                    double *new_yhat_q, int32_t *new_route, double *new_cond_cov, double *new_cov,
+                                    const stm_functionals *fun, const stm_scores *scores) {
   if (fun && fun->n_fun <= 0) fun = nullptr;
+  if (scores && !scores->y_new) scores = nullptr;
+  if (scores && (!X_new || (scores->lpd_joint && !joint_id_new) || (scores->crps && keep_draws < 1))) return ST_ERR_USAGE;
   if (fun && (fun->fun_yhat || fun->fun_yhat_mean || fun->fun_yhat_q) && !X_new) return ST_ERR_USAGE;
   if ((new_cond_cov || new_cov) && !joint_id_new) return ST_ERR_USAGE;
   if (n_quantiles < 0 || (n_quantiles > 0 && (!quantiles || keep_draws < 1))) return ST_ERR_USAGE;   // a quantile needs stored draws
@@ -561,6 +586,7 @@ extern "C" int stm_mcmc_functionals(const st_problem *pb, const st_options *opt,
   std::vector<int64_t> joff, jptr, jmem;
   std::vector<double> cov_scratch;
   if (rc == 0 && fun) rc = stm_points_functionals_set(c, fun->n_fun, fun->ptr, fun->idx, fun->wt);
+  if (rc == 0 && scores) rc = stm_points_score_set(c, scores->y_new);
   if (rc == 0 && joint_id_new) {
     rc = st_points_joint_layout(c->h, &nj, nullptr, nullptr, nullptr);
     joff.resize(nj + 1); jptr.resize(nj + 1); jmem.resize(n_new);
@@ -592,6 +618,8 @@ extern "C" int stm_mcmc_functionals(const st_problem *pb, const st_options *opt,
   for (int32_t i = 0; rc == 0 && fun && i < n_quantiles && (fun->fun_w_q || fun->fun_yhat_q); ++i)
     rc = st_points_functionals_quantile(c->h, quantiles[i], fun->fun_w_q ? fun->fun_w_q + (size_t)i * fun->n_fun : nullptr,
                                         fun->fun_yhat_q ? fun->fun_yhat_q + (size_t)i * fun->n_fun : nullptr);
+  if (rc == 0 && scores && mcmc_keep > 0)
+    rc = st_points_score_get(c->h, scores->lpd, scores->pit, scores->crps, scores->lpd_joint, scores->n_scored, scores->n_degenerate);
   stm_destroy(c);
   return rc;
 }

@@ -1,13 +1,15 @@
 // st_points.hip -- the C-ABI of new-point prediction (st_points_*): the device step of st_points_set / st_points_set_joint, predict,
-// accumulate, the summaries and quantiles, and the linear functionals of the predictions (st_points_functionals_*).
-// predict_points.hpp, predict_joint.hpp and points_fun.hpp have the model; the launch structures of a point set and the term lists
+// accumulate, the summaries and quantiles, the linear functionals of the predictions (st_points_functionals_*) and the scores of
+// held-out observations (st_points_score_*).
+// predict_points.hpp, predict_joint.hpp, points_fun.hpp and points_score.hpp have the model; the launch structures of a point set and the term lists
 // of its functionals are built without a device call in points_layout.cpp; the kernels and their launchers live in k_predict.hip,
-// k_predict_joint.hip, k_points_acc.hip and k_points_fun.hip (k_qtile in k_misc.hip).
+// k_predict_joint.hip, k_points_acc.hip, k_points_fun.hip and k_points_score.hip (k_qtile in k_misc.hip).
 #include <memory>
 
 #include "st_handle.hpp"
 #include "misc_kernels.hpp"
 #include "points_layout.hpp"
+#include "points_score.hpp"
 
 // The functionals of a point set (st_points_functionals_set): the term lists and chunks on the device, their accumulators, the
 // values of the last iteration and, with a reservation, the draws F_w and F_y, [keep][n_fun] each
@@ -19,6 +21,16 @@ struct FunSet {
   DevBuf<long long> d_lin_cptr, d_var_cptr;
   DevBuf<double> d_part, d_acc, d_last, d_keep_w, d_keep_yhat, d_q;
   long long n_acc = 0, n_kept = 0;
+};
+
+// The scores of held-out observations at the point set (st_points_score_set): y on the device, the running state of every point
+// (SC_NACC x n) and joint group ([n_joint][2]), the counter of degenerate factorisations and room for the CRPS
+struct ScoreSet {
+  long long n_scored = 0, n_acc = 0;
+  int gmax = 0;                    // the largest joint group
+  std::vector<char> pt_obs, grp_obs;   // per point / joint group: scored (a group: any member observed)
+  DevBuf<double> d_y, d_acc, d_jacc, d_crps;
+  DevBuf<unsigned long long> d_ndeg;
 };
 
 struct PointSet : PointsCounts {
@@ -44,6 +56,7 @@ struct PointSet : PointsCounts {
   DevBuf<int> d_jgen, d_pt_grp, d_pt_a;
   DevBuf<double> d_jout, d_jscratch, d_pacc;   // cov and chol of the last call (2 x cov_total); scratch; pair accumulators
   std::unique_ptr<FunSet> fun;                 // st_points_functionals_set; leaves with the point set
+  std::unique_ptr<ScoreSet> score;             // st_points_score_set; leaves with the point set
 };
 
 void points_free(st_handle_s *h) {
@@ -301,6 +314,37 @@ static int fun_step(st_handle h, PointSet *ps) {
   return ST_OK;
 }
 
+// ---- the scores' share of reset and accumulate (the entry points follow the functionals) ----
+static int score_reset(st_handle h, ScoreSet *sc) {
+  if (sc->d_acc.p) HCHK(h, hipMemsetAsync(sc->d_acc.p, 0, sc->d_acc.n * sizeof(double), h->stream));
+  if (sc->d_jacc.p) HCHK(h, hipMemsetAsync(sc->d_jacc.p, 0, sc->d_jacc.n * sizeof(double), h->stream));
+  HCHK(h, hipMemsetAsync(sc->d_ndeg.p, 0, sizeof(unsigned long long), h->stream));
+  sc->n_acc = 0;
+  return ST_OK;
+}
+
+// the score step of one saved iteration: after k_points_acc, on the same stream, from d_out / d_jout, d_X, d_B and d_tsq
+static int score_step(st_handle h, PointSet *ps) {
+  ScoreSet *sc = ps->score.get();
+  const long long n = ps->n;
+  sc->n_acc += 1;
+  if (n == 0 || sc->n_scored == 0) return ST_OK;
+  const double *o = ps->d_out.p;
+  ProfScope pscope(h, 6, -1, ps->joint ? 2 : 1);
+  ScoreArgs A;
+  A.y = sc->d_y.p; A.mean = o + n; A.var = o + 2 * n; A.X = ps->d_X.p; A.B = h->d_B.p; A.tsq_inv = h->d_tsq.p; A.pmv = ps->d_pmv.p;
+  A.p = h->p; A.n = n; A.acc = sc->d_acc.p;
+  int e = points_score_launch(A, h->stream);
+  if (!e && ps->joint) {
+    ScoreJointArgs J;
+    J.y = A.y; J.mean = A.mean; J.cov = ps->d_jout.p; J.X = A.X; J.B = A.B; J.tsq_inv = A.tsq_inv; J.pmv = A.pmv; J.p = A.p; J.n = n;
+    J.n_joint = ps->n_joint; J.groups = ps->d_jgroups.p; J.members = ps->d_jmem.p; J.jacc = sc->d_jacc.p; J.n_degenerate = sc->d_ndeg.p;
+    e = points_score_joint_launch(J, sc->gmax, h->stream);
+  }
+  if (e) { h->err = std::string("st_points_accumulate launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+  return ST_OK;
+}
+
 // ---- predictive summaries of the point set over saved iterations (st_points_accumulate; the kernel lives in k_points_acc.hip) ----
 extern "C" int st_points_summary_reset(st_handle h) {
   if (!h) return ST_ERR_USAGE;
@@ -314,6 +358,8 @@ extern "C" int st_points_summary_reset(st_handle h) {
   if (pcnt > 0 && !ps->d_pacc.p) HCHK(h, ps->d_pacc.alloc(pcnt));
   if (pcnt > 0) HCHK(h, hipMemsetAsync(ps->d_pacc.p, 0, pcnt * sizeof(double), h->stream));
   ps->n_acc = 0; ps->n_kept = 0;
+  if (ps->score)
+    if (const int rc = score_reset(h, ps->score.get())) return rc;
   if (ps->fun) return fun_reset(h, ps->fun.get());
   return ST_OK;
 }
@@ -347,6 +393,7 @@ static int points_accumulate(st_handle h, uint64_t seed, uint32_t iter, double *
   ps->route_mask = 0;
   if (ps->n == 0) {   // functionals of an empty set have no term: zeros
     ps->n_acc += 1;
+    if (ps->score) (void)score_step(h, ps);   // counts the iteration; an empty set launches nothing
     if (!ps->fun) return ST_OK;
     HCHK(h, hipSetDevice(h->device));
     return fun_step(h, ps);
@@ -381,6 +428,8 @@ static int points_accumulate(st_handle h, uint64_t seed, uint32_t iter, double *
   }
   ps->n_acc += 1;
   if (keep) ps->n_kept += 1;
+  if (ps->score)
+    if (const int rcs = score_step(h, ps)) return rcs;
   if (ps->fun)
     if (const int rcf = fun_step(h, ps)) return rcf;
   double *const dst[4] = {w_new, cond_mean, cond_var, yhat_new};
@@ -578,4 +627,86 @@ extern "C" int st_points_functionals_quantile(st_handle h, double q, double *w_q
   double *const dst[2] = {w_q, yhat_q};
   const double *const draws[2] = {fs->d_keep_w.p, fs->d_keep_yhat.p};
   return points_qtile(h, draws, fs->n_fun, fs->n_kept, q, fs->d_q.p, dst);
+}
+
+// ---- scores of held-out observations at the point set (points_score.hpp)
+extern "C" int st_points_score_set(st_handle h, const double *y_new) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_score_set")) return rc;
+  PointSet *ps = h->pts;
+  const long long n = ps->n;
+  if (y_new) {   // a refusal leaves the previous scores in place
+    if (!ps->has_X) { h->err = "st_points_score_set: the scores need the regressors X of st_points_set"; return ST_ERR_USAGE; }
+    for (long long i = 0; i < n; ++i)
+      if (std::isinf(y_new[i])) { h->err = "st_points_score_set: y_new[" + std::to_string(i) + "] is infinite (NaN marks a point that is not scored)"; return ST_ERR_USAGE; }
+  }
+  HCHK(h, hipSetDevice(h->device));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  if (!y_new) { ps->score.reset(); return ST_OK; }
+  std::unique_ptr<ScoreSet> sc(new ScoreSet());   // the point set takes it once every upload has succeeded
+  sc->pt_obs.resize((size_t)n);
+  for (long long i = 0; i < n; ++i) { sc->pt_obs[i] = !std::isnan(y_new[i]); sc->n_scored += sc->pt_obs[i]; }
+  if (ps->joint) {
+    sc->grp_obs.assign((size_t)ps->n_joint, 0);
+    for (long long k = 0; k < ps->n_joint; ++k) {
+      sc->gmax = std::max(sc->gmax, (int)(ps->j_mptr[k + 1] - ps->j_mptr[k]));
+      for (int64_t a = ps->j_mptr[k]; a < ps->j_mptr[k + 1]; ++a) sc->grp_obs[k] |= sc->pt_obs[ps->j_mem[a]];
+    }
+  }
+  HCHK(h, sc->d_y.upload(std::vector<double>(y_new, y_new + n)));
+  HCHK(h, sc->d_acc.alloc((size_t)SC_NACC * n)); HCHK(h, sc->d_crps.alloc((size_t)n));
+  if (ps->joint) HCHK(h, sc->d_jacc.alloc((size_t)2 * ps->n_joint));
+  HCHK(h, sc->d_ndeg.alloc(1));
+  if (const int rc = score_reset(h, sc.get())) return rc;
+  ps->score = std::move(sc);
+  return ST_OK;
+}
+
+extern "C" int st_points_score_get(st_handle h, double *lpd, double *pit, double *crps, double *lpd_joint, int64_t *n_scored,
+                                   int64_t *n_degenerate) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_score_get")) return rc;
+  PointSet *ps = h->pts;
+  ScoreSet *sc = ps->score.get();
+  if (!sc) { h->err = "st_points_score_get before st_points_score_set"; return ST_ERR_USAGE; }
+  if (n_scored) *n_scored = sc->n_scored;
+  if (sc->n_scored == 0) { h->err = "st_points_score_get: no point is scored (every y_new is NaN)"; return ST_ERR_USAGE; }
+  if (sc->n_acc == 0) { h->err = "st_points_score_get: no iteration accumulated"; return ST_ERR_USAGE; }
+  if (crps && ps->n_kept == 0) { h->err = "st_points_score_get: crps needs a stored draw (call st_points_summary_reserve before the saved iterations)"; return ST_ERR_USAGE; }
+  if (lpd_joint && !ps->joint) { h->err = "st_points_score_get: lpd_joint before st_points_set_joint"; return ST_ERR_USAGE; }
+  HCHK(h, hipSetDevice(h->device));
+  const long long n = ps->n;
+  const double S = (double)sc->n_acc, nan = std::nan("");
+  std::vector<double> acc, jacc;
+  unsigned long long ndeg = 0;
+  if (lpd || pit) {
+    acc.resize((size_t)SC_NACC * n);
+    HCHK(h, hipMemcpyAsync(acc.data(), sc->d_acc.p, acc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  if (lpd_joint) {
+    jacc.resize((size_t)2 * ps->n_joint);
+    HCHK(h, hipMemcpyAsync(jacc.data(), sc->d_jacc.p, jacc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  if (n_degenerate) HCHK(h, hipMemcpyAsync(&ndeg, sc->d_ndeg.p, sizeof(ndeg), hipMemcpyDeviceToHost, h->stream));
+  if (crps) {   // the launch rule of points_qtile
+    ScoreCrpsArgs A;
+    int Kpad = 2;
+    while (Kpad < ps->n_kept) Kpad <<= 1;
+    A.draws = ps->d_keep_yhat.p; A.y = sc->d_y.p; A.n = n; A.keep = (int)ps->n_kept; A.Kpad = Kpad;
+    A.R = std::max(1, std::min(8, (int)(128 * 1024 / ((size_t)Kpad * 8))));
+    A.out = sc->d_crps.p;
+    const int e = points_score_crps_launch(A, h->lds_limit, h->stream);
+    if (e) { h->err = std::string("st_points_score_get launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+    HCHK(h, hipMemcpyAsync(crps, sc->d_crps.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  HCHK(h, hipStreamSynchronize(h->stream));
+  // lpd = M + log(A / S); no draw of positive density: log 0
+  auto lme = [&](double M, double A) { return A > 0.0 ? M + std::log(A / S) : -HUGE_VAL; };
+  for (long long i = 0; i < n && (lpd || pit); ++i) {
+    if (lpd) lpd[i] = sc->pt_obs[i] ? lme(acc[SC_M * n + i], acc[SC_A * n + i]) : nan;
+    if (pit) pit[i] = sc->pt_obs[i] ? acc[SC_PIT * n + i] / S : nan;
+  }
+  for (long long k = 0; lpd_joint && k < ps->n_joint; ++k) lpd_joint[k] = sc->grp_obs[k] ? lme(jacc[2 * k], jacc[2 * k + 1]) : nan;
+  if (n_degenerate) *n_degenerate = (int64_t)ndeg;
+  return ST_OK;
 }

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .model import SpamTreeError, _dp, _f64, _i64, _ip, _lists_to_csr, functionals_csr, joint_labels
+from .model import SpamTreeError, _dp, _f64, _i64, _ip, _lists_to_csr, functionals_csr, joint_labels, score_totals, score_values
 
 
 def _problem(y, X, coords, mv_id, res_is_ref, parents, children, block_names, block_groups, indexing):
@@ -160,12 +160,15 @@ class Chain:
             pass
 
 
+MAX_STORED_DRAWS = 16384   # st_points_summary_reserve: one point's draws are sorted in one workgroup's LDS
+
+
 def _points_inputs(new_points, p, q, new_quantiles):
     """Checks the point set of spamtree_mv_mcmc(new_points=...) against itself and the problem, before any device call."""
     pts = dict(new_points)
-    unknown = set(pts) - {"coords", "mv", "anchor", "X", "joint", "functionals"}
+    unknown = set(pts) - {"coords", "mv", "anchor", "X", "joint", "functionals", "y", "crps"}
     if unknown:
-        raise ValueError(f"new_points: unknown keys {sorted(unknown)} (coords, mv, anchor, X, joint, functionals)")
+        raise ValueError(f"new_points: unknown keys {sorted(unknown)} (coords, mv, anchor, X, joint, functionals, y, crps)")
     coords = np.asarray(pts["coords"], dtype=np.float64)
     if coords.ndim != 2 or coords.shape[1] != 2:
         raise ValueError("new_points: coords must be n_new x 2")
@@ -202,7 +205,16 @@ def _points_inputs(new_points, p, q, new_quantiles):
             raise ValueError(f"new_points: {e}") from None
         if fun[0].size == 1:
             fun = None
-    return np.asfortranarray(coords), _i64(mv), _i64(anchor), X, qs, labels, fun
+    y = pts.get("y")
+    if y is not None:
+        try:
+            y = score_values(y, n_new, X is not None)
+        except ValueError as e:
+            raise ValueError(f"new_points: {e}") from None
+    crps = bool(pts.get("crps", True)) and y is not None
+    if "crps" in pts and y is None:
+        raise ValueError("new_points: crps needs y")
+    return np.asfortranarray(coords), _i64(mv), _i64(anchor), X, qs, labels, fun, y, crps
 
 
 def _joint_layout(labels):
@@ -244,9 +256,19 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     ``new_points["functionals"]``: linear functionals of the predictions (``model.functionals_csr`` has the accepted forms;
     ``predict.areal_means`` / ``predict.contrasts`` build common ones), summarised on the device (stm_mcmc_functionals); ``new``
     then also holds ``functionals``: dict(mean, var, w_mean, yhat_mean, quantiles={q: (w_q, yhat_q)}) and, with ``new_draws``,
-    the per-draw n_fun x keep arrays ``w``, ``cond_mean``, ``cond_var``, ``yhat``."""
+    the per-draw n_fun x keep arrays ``w``, ``cond_mean``, ``cond_var``, ``yhat``.
+    ``new_points["y"]``: held-out observations at the points (one per point, NaN = not scored; needs ``X``), scored on the device
+    on every saved iteration (stm_mcmc_scored); ``new`` then also holds ``scores``: dict(lpd, pit, crps, lpd_joint, n_scored,
+    n_degenerate, totals) -- the per-point log predictive density of the mixture over the saved draws, its PIT, the CRPS of the
+    stored yhat draws (which stay on the device: nothing per draw comes to the host for it), per joint group the joint log
+    predictive density, and ``model.score_totals``' means, with the coverage of [yhat_lo, yhat_hi] for the lowest and highest of
+    two or more ``new_quantiles``.  The CRPS makes the device keep ``mcmc_keep`` draws of w and yhat per point (16 B each per
+    point and draw; at most 16384 draws, more is a ValueError); ``new_points["crps"] = False`` scores without it and stores nothing."""
     if new_points is not None:
         pts = _points_inputs(new_points, np.asarray(X).shape[1], int(np.unique(_i64(mv_id)).size), new_quantiles)
+        if pts[8] and int(mcmc_keep) > MAX_STORED_DRAWS:
+            raise ValueError(f"new_points: the CRPS keeps mcmc_keep = {int(mcmc_keep)} draws per point on the device, at most "
+                             f"{MAX_STORED_DRAWS} (crps=False scores without it)")
     elif len(tuple(new_quantiles)):
         raise ValueError("new_quantiles needs new_points")
     lib = _lib.load()
@@ -270,7 +292,7 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     if new_points is None:
         rc = lib.spamtree_mv_mcmc_c(*common)
     else:
-        pc, pmv, pan, pX, qs, labels, fun = pts
+        pc, pmv, pan, pX, qs, labels, fun, ynew, want_crps = pts
         n_new = pc.shape[0]
         draws = {key: np.zeros((n_new, mcmc_keep), order="F") if new_draws else None for key in ("w", "cond_mean", "cond_var")}
         draws["yhat"] = np.zeros((n_new, mcmc_keep), order="F") if (new_draws and pX is not None) else None
@@ -279,7 +301,7 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
         wq = np.zeros((n_new, qs.size), order="F")
         yq = np.zeros((n_new, qs.size), order="F") if pX is not None else None
         route = C.c_int32()
-        tail = (int(mcmc_keep) if qs.size else 0, _dp(qs), int(qs.size), dp(draws["w"]), dp(draws["cond_mean"]),
+        tail = (int(mcmc_keep) if (qs.size or want_crps) else 0, _dp(qs), int(qs.size), dp(draws["w"]), dp(draws["cond_mean"]),
                 dp(draws["cond_var"]), dp(draws["yhat"]), dp(summ["mean"]), dp(summ["var"]), dp(summ["w_mean"]),
                 dp(summ["yhat_mean"]), dp(wq if qs.size else None), dp(yq if qs.size else None), C.byref(route))
         groups = off = ccov = cov = None
@@ -287,6 +309,7 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
             groups, off = _joint_layout(labels)
             ccov = np.zeros((int(off[-1]), mcmc_keep), order="F") if new_draws else None
             cov = np.zeros(int(off[-1]))
+        fsp = None
         if fun is not None:       # stm_mcmc_functionals: both kinds of set, plus the functional outputs in one struct
             nf = fun[0].size - 1
             fdraws = {key: np.zeros((nf, mcmc_keep), order="F") if new_draws else None for key in ("w", "cond_mean", "cond_var")}
@@ -298,8 +321,18 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
             fs = _lib.StmFunctionals(nf, _ip(fun[0]), _ip(fun[1]), _dp(fun[2]), dp(fdraws["w"]), dp(fdraws["cond_mean"]),
                                      dp(fdraws["cond_var"]), dp(fdraws["yhat"]), dp(fsumm["mean"]), dp(fsumm["var"]), dp(fsumm["w_mean"]),
                                      dp(fsumm["yhat_mean"]), dp(fwq if qs.size else None), dp(fyq if qs.size else None))
+            fsp = C.byref(fs)
+        if ynew is not None:      # stm_mcmc_scored: the same call plus the scores; crps from the draws the device keeps
+            sc = dict(lpd=np.zeros(n_new), pit=np.zeros(n_new), crps=np.zeros(n_new) if (want_crps and mcmc_keep > 0) else None,
+                      lpd_joint=np.zeros(len(groups)) if labels is not None else None)
+            nsc, ndg = C.c_int64(), C.c_int64()
+            ss = _lib.StmScores(_dp(ynew), dp(sc["lpd"]), dp(sc["pit"]), dp(sc["crps"]), dp(sc["lpd_joint"]),
+                                C.pointer(nsc), C.pointer(ndg))
+            rc = lib.stm_mcmc_scored(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), _ip(labels) if labels is not None else None,
+                                     *tail, dp(ccov), dp(cov), fsp, C.byref(ss))
+        elif fun is not None:
             rc = lib.stm_mcmc_functionals(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), _ip(labels) if labels is not None else None,
-                                          *tail, dp(ccov), dp(cov), C.byref(fs))
+                                          *tail, dp(ccov), dp(cov), fsp)
         elif labels is None:
             rc = lib.stm_mcmc_points(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), *tail)
         else:
@@ -324,6 +357,11 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                                                             for i, x in enumerate(qs)})
                 if new_draws:
                     new["functionals"].update(fdraws)
+            if ynew is not None and mcmc_keep > 0:
+                sc.update(n_scored=int(nsc.value), n_degenerate=int(ndg.value))
+                lo_hi = (yq[:, int(np.argmin(qs))], yq[:, int(np.argmax(qs))]) if qs.size >= 2 else (None, None)
+                sc["totals"] = score_totals(sc, ynew, pmv, q, *lo_hi)
+                new["scores"] = sc
     if rc == -10:
         raise FloatingPointError("At nan loglik: error.")
     if rc != 0 and new_points is not None:

@@ -56,6 +56,42 @@ def joint_labels(joint, n):
     return _i64(labels)
 
 
+def score_values(y_new, n_points, have_X=True):
+    """Held-out observations at ``n_points`` points as one float64 vector, checked before any device call: one value per point,
+    NaN for a point that is not scored, nothing infinite; the scores need the regressors of the points."""
+    y = np.asarray(y_new, dtype=np.float64)
+    if y.ndim == 2 and 1 in y.shape:
+        y = y.reshape(-1)
+    if y.ndim != 1 or y.size != n_points:
+        raise ValueError(f"y_new must hold one value per new point ({n_points}), NaN where a point is not scored")
+    if not have_X:
+        raise ValueError("y_new needs X_new: the scored predictive is that of the outcome, x'beta + w + noise")
+    bad = np.nonzero(np.isinf(y))[0]
+    if bad.size:
+        raise ValueError(f"y_new[{int(bad[0])}] is infinite (NaN marks a point that is not scored)")
+    return _f64(y)
+
+
+def score_totals(scores, y, mv, q, yhat_lo=None, yhat_hi=None):
+    """Host-side totals of st_points_score_get's per-point arrays: the mean lpd, pit and crps over the scored points, overall and
+    per outcome (``by_outcome``: q entries, NaN for an outcome without a scored point) and, with the lowest and highest requested
+    quantile of yhat, the coverage of [yhat_lo, yhat_hi]."""
+    obs = ~np.isnan(y)
+    mv = np.asarray(mv).reshape(-1)
+    keys = [k for k in ("lpd", "pit", "crps") if scores.get(k) is not None]
+    cover = None
+    if yhat_lo is not None and yhat_hi is not None:
+        cover = ((y >= yhat_lo) & (y <= yhat_hi)).astype(np.float64)
+        keys.append("coverage")
+
+    def mean(k, sel):
+        v = cover if k == "coverage" else scores[k]
+        return float(np.mean(v[sel])) if np.any(sel) else float("nan")
+    tot = {k: mean(k, obs) for k in keys}
+    tot["by_outcome"] = {k: np.array([mean(k, obs & (mv == j + 1)) for j in range(q)]) for k in keys}
+    return tot
+
+
 def functionals_csr(A, n_points):
     """Linear functionals of the predictions at ``n_points`` points as CSR ``(ptr, idx, wt)``, checked before any device call.
     ``A``: a ``(ptr, idx, wt)`` triple (a tuple of three whose entries are not themselves (indices, weights) pairs); a dense n_fun x n_points array, whose zeros are dropped; or a list of
@@ -429,6 +465,8 @@ class SpamTreeMV:
         self.n_points = n
         self.points_have_X = Xf is not None
         self.n_functionals = 0       # a new point set has none
+        self.score_y = None          # ... and no scores
+        self.points_mv = mv
 
     def unpack_joint(self, packed):
         """The g x g blocks of a packed cond_cov / cond_chol / summary covariance, in group order: one [n_groups, g, g] array
@@ -537,6 +575,36 @@ class SpamTreeMV:
         by = C.c_double()
         self._check(self.lib.st_points_functionals_info(self.h, *[C.byref(x) for x in v], C.byref(by)))
         return dict(n_fun=v[0].value, nnz=v[1].value, n_chunks=v[2].value, n_var_terms=v[3].value, alg_bytes=by.value)
+
+    # ---- scores of held-out observations at the point set (st_points_score_*)
+    def set_scores(self, y_new):
+        """Held-out observations at the point set, one per point in the caller's order, NaN where a point is not scored
+        (``score_values`` checks them); None removes the scores.  Every accumulate_points then also scores them on the device."""
+        if y_new is None:
+            self._check(self.lib.st_points_score_set(self.h, None))
+            self.score_y = None
+            return
+        y = score_values(y_new, self.n_points, self.points_have_X)
+        self._check(self.lib.st_points_score_set(self.h, _dp(y)))
+        self.score_y = y
+
+    def scores(self, crps=True, yhat_lo=None, yhat_hi=None):
+        """The scores over the iterations accumulated since set_scores: dict(lpd, pit, crps, n_scored, n_degenerate), the arrays
+        in the caller's order with NaN where a point is not scored; on a joint set also ``lpd_joint``, one per group of
+        ``joint_groups``; ``crps`` (None with ``crps=False``) needs a stored draw (st_points_summary_reserve).  ``totals`` has
+        ``score_totals``' means, with the coverage of [yhat_lo, yhat_hi] when both are given."""
+        if self.score_y is None:
+            raise ValueError("scores before set_scores")
+        n = self.n_points
+        out = dict(lpd=np.zeros(n), pit=np.zeros(n), crps=np.zeros(n) if crps else None)
+        joint = getattr(self, "joint_groups", None) is not None
+        out["lpd_joint"] = np.zeros(len(self.joint_groups)) if joint else None
+        ns, nd = C.c_int64(), C.c_int64()
+        self._check(self.lib.st_points_score_get(self.h, _dp(out["lpd"]), _dp(out["pit"]), _dp(out["crps"]) if crps else None,
+                                                 _dp(out["lpd_joint"]) if joint else None, C.byref(ns), C.byref(nd)))
+        out.update(n_scored=int(ns.value), n_degenerate=int(nd.value))
+        out["totals"] = score_totals(out, self.score_y, self.points_mv, self.q, yhat_lo, yhat_hi)
+        return out
 
     def points_info(self):
         """Of the last predict_points: dict(routes=[kernel names that ran], n_groups, alg_bytes, flops)."""

@@ -18,7 +18,7 @@ from typing import Optional
 import numpy as np
 
 from . import fit
-from .model import SpamTreeMV, _dp, _f64, functionals_csr, joint_labels
+from .model import SpamTreeMV, _dp, _f64, functionals_csr, joint_labels, score_values
 from .topology import Topology, _nearest_rows
 
 __all__ = ["locate", "conditioning_set", "group_sites", "predict_new", "fit_predict", "areal_means", "contrasts"]
@@ -105,7 +105,8 @@ def conditioning_set(topo: Topology, anchor: int) -> np.ndarray:
 
 
 def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, return_draws=True, device=0, z=None,
-                mode=0, force_generic=False, return_moments=False, joint=None, functionals=None):
+                mode=0, force_generic=False, return_moments=False, joint=None, functionals=None, y_new=None, quantiles=(),
+                crps=True):
     """Predictive at new locations for every saved draw of a chain.
 
     ``model_inputs``: the problem as ``spamtree_mv_mcmc`` took it (the dict of ``synthetic.make_workload``; its ``topo``
@@ -128,6 +129,12 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
     that seed and counter, so every other output is unchanged bit for bit -- which needs the device's normals (``z`` None) and
     ``mode`` 0.  The result also holds ``functionals``: dict(mean, var, w_mean, yhat_mean) and, with ``return_draws``, the
     n_fun x keep arrays ``w``, ``cond_mean``, ``cond_var``, ``yhat``.
+
+    ``y_new``: held-out observations at the points (one per point, NaN = not scored; needs ``X_new``), scored on the device.
+    As with ``functionals`` the replay goes through ``st_points_accumulate`` (``z`` None, ``mode`` 0), with every saved draw's
+    yhat kept on the device for the CRPS.  The result also holds ``scores`` (``SpamTreeMV.scores``); ``quantiles=(lo, ..., hi)``
+    adds the coverage of [yhat_lo, yhat_hi] to its totals.  ``crps=False`` leaves the CRPS out and keeps no draw on the device
+    (neither then has ``quantiles``); with it the chain may hold at most 16384 saved draws.
     """
     mi = model_inputs
     topo = mi["topo"]
@@ -139,6 +146,20 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
         fun = functionals_csr(functionals, n_new)
         if z is not None or mode != 0:
             raise ValueError("functionals need the device draw: z=None and mode=0")
+    ys = None
+    if y_new is not None:
+        ys = score_values(y_new, n_new, X_new is not None)
+        if z is not None or mode != 0:
+            raise ValueError("y_new needs the device draw: z=None and mode=0")
+    qs = tuple(float(x) for x in quantiles)
+    if not all(0.0 <= x <= 1.0 for x in qs):
+        raise ValueError("quantiles must lie in [0, 1]")
+    if qs and ys is None:
+        raise ValueError("quantiles need y_new (they bound the interval whose coverage is scored)")
+    if qs and not crps:
+        raise ValueError("quantiles need the stored draws: crps=True")
+    if ys is not None and crps and len(draws["w_mcmc"]) > fit.MAX_STORED_DRAWS:
+        raise ValueError(f"the CRPS keeps every saved draw of yhat on the device, at most {fit.MAX_STORED_DRAWS} (crps=False scores without)")
     anchor = locate(topo, coords_new, mv_new, device=device, joint=joint)
     w_list = draws["w_mcmc"]
     keep = len(w_list)
@@ -159,6 +180,10 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
         if fun is not None:
             m.set_functionals(fun)
             fdraws = {k: np.zeros((fun[0].size - 1, keep)) for k in ("w", "cond_mean", "cond_var", "yhat")}
+        if ys is not None:
+            m.set_scores(ys)
+            if crps:
+                m._check(m.lib.st_points_summary_reserve(m.h, keep))
         cc = []
         w_out = np.zeros((n_new, keep)) if return_draws else None
         y_out = np.zeros((n_new, keep)) if (return_draws and X_new is not None) else None
@@ -172,11 +197,11 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
             m.theta_update(0, theta[:, s])
             if not m.get_loglik_comps_w(0):
                 raise FloatingPointError(f"st_factor failed on saved draw {s} (errtype {m.last_errtype})")
-            if fun is None:
+            if fun is None and ys is None:
                 out = m.predict_points(mode=mode, z=None if z is None else z[:, s], seed=seed, it=s)
             else:
                 out = m.accumulate_points(seed=seed, it=s)
-                for k, v in m.functionals_last().items():
+                for k, v in (m.functionals_last().items() if fun is not None else ()):
                     if v is not None:
                         fdraws[k][:, s] = v
             cm[:, s] = out["mean"]
@@ -198,6 +223,15 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
             res["functionals"] = {k: v for k, v in m.functionals().items() if k != "n"} if keep else {}
             if return_draws:
                 res["functionals"].update(fdraws, yhat=fdraws["yhat"] if X_new is not None else None)
+        if ys is not None and keep:
+            lo_hi = (None, None)
+            if len(qs) >= 2:
+                yq = np.zeros(n_new)
+                lo_hi = []
+                for x in (min(qs), max(qs)):
+                    m._check(m.lib.st_points_summary_quantile(m.h, x, None, _dp(yq)))
+                    lo_hi.append(yq.copy())
+            res["scores"] = m.scores(crps=crps, yhat_lo=lo_hi[0], yhat_hi=lo_hi[1])
         if joint is not None:
             packed = np.mean(cc, axis=0) if keep else np.zeros(0)
             for k, g in enumerate(m.joint_groups):
@@ -212,7 +246,8 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
         m.close()
 
 
-def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), return_draws=True, joint=None, functionals=None, **mcmc):
+def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), return_draws=True, joint=None, functionals=None,
+                y_new=None, crps=True, **mcmc):
     """Fit the chain and predict at new locations on every saved iteration, without replaying it.
 
     ``model_inputs``: the problem as for :func:`predict_new`.  The points are located with :func:`locate` and handed to
@@ -226,6 +261,11 @@ def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), retu
     With ``joint`` labels also ``groups``, ``cov`` and (``return_draws``) ``cond_cov``, as :func:`predict_new`.
     With ``functionals`` (as :func:`predict_new`) also ``functionals``: dict(mean, var, w_mean, yhat_mean, quantiles) from the
     device and, with ``return_draws``, the n_fun x keep arrays ``w``, ``cond_mean``, ``cond_var``, ``yhat``.
+    With ``y_new`` (held-out observations, one per point, NaN = not scored; needs ``X_new``) also ``scores``: the per-point ``lpd``,
+    ``pit`` and ``crps``, per joint group ``lpd_joint``, ``n_scored``, ``n_degenerate`` and ``totals`` (means over the scored
+    points, overall and per outcome; with two or more ``quantiles`` the coverage of [yhat_lo, yhat_hi]), all formed on the device
+    during the fit, whatever ``return_draws`` is.  For the CRPS the device keeps ``mcmc_keep`` draws of w and yhat per point (16 B
+    each per point and draw, at most 16384 draws); ``crps=False`` scores without it and stores nothing.
     """
     mi = model_inputs
     coords_new = np.asarray(coords_new, dtype=np.float64).reshape(-1, 2)
@@ -238,12 +278,18 @@ def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), retu
     if not all(0.0 <= x <= 1.0 for x in qs):
         raise ValueError("quantiles must lie in [0, 1]")
     fun = None if functionals is None else functionals_csr(functionals, coords_new.shape[0])
+    ys = None if y_new is None else score_values(y_new, coords_new.shape[0], X_new is not None)
+    if ys is not None and crps and int(mcmc.get("mcmc_keep", 100)) > fit.MAX_STORED_DRAWS:
+        raise ValueError(f"the CRPS keeps mcmc_keep draws per point on the device, at most {fit.MAX_STORED_DRAWS} (crps=False scores without it)")
     anchor = locate(mi["topo"], coords_new, mv_new, device=mcmc.get("device", 0), joint=joint)
     points = dict(coords=coords_new, mv=mv_new, anchor=anchor, X=X_new)
     if joint is not None:
         points["joint"] = joint
     if fun is not None:
         points["functionals"] = fun
+    if ys is not None:
+        points["y"] = ys
+        points["crps"] = bool(crps)
     theta = np.asarray(mcmc.pop("theta", mi["theta"]), dtype=np.float64)
     kw = dict(set_unif_bounds_in=mi["bounds"], start_w=np.zeros((int(mi["n"]), 1)), theta=theta, beta=np.zeros(int(mi["p"])),
               tausq=0.1, mcmcsd=0.01 * np.eye(theta.size))
