@@ -138,6 +138,31 @@ int stm_mcmc_scored(const st_problem *pb, const st_options *opt, const double *s
                     double *new_w_mean, double *new_yhat_mean, double *new_w_q, double *new_yhat_q, int32_t *new_route,
                     double *new_cond_cov, double *new_cov, const stm_functionals *fun, const stm_scores *scores);
 
+/* Criteria over the fit's own rows (include/spamtree_hip.h, st_rows_score_*): WAIC and DIC over the observed rows and the scores
+ * of held-out values at NA rows, conditional on w.  stm_rows_score_set: st_rows_score_set on the chain's handle; call it before the
+ * first iteration.  stm_mcmc_criteria is spamtree_mv_mcmc_c plus one stm_criteria: on every saved iteration, once tausq and beta are
+ * drawn and st_predict has run, st_rows_score_accumulate and, with want_crps and a y_holdout, st_summary_accumulate(seed, m) into a
+ * reservation of mcmc_keep draws (Philox stream 5 with the iteration's counter: the yhat that st_yhat(seed, m) returns).  It consumes
+ * no draw of streams 0-4 and changes no chain state: every output of spamtree_mv_mcmc_c is the same bit for bit.
+ * y_holdout: n_all values in model row order, NaN = none, or NULL (criteria over the observed rows only).  Outputs, any of which may
+ * be NULL: lppd, p_waic, mean_ll, mu_mean, pit, crps (n_all each, st_rows_score_get); obs (ST_ROWS_OBS_N x q), held
+ * (ST_ROWS_HELD_N x q), n_obs, n_held (q each, st_rows_score_totals); n_accumulated.
+ * Refused before the first factorisation: want_crps with more than 16384 saved draws (ST_ERR_UNSUPPORTED); a y_holdout with
+ * sample_predicts = 0 or sample_w = 0 (ST_ERR_USAGE: the NA rows' w would be stale); crps without want_crps or without y_holdout
+ * (ST_ERR_USAGE); st_rows_score_set's own refusals. */
+typedef struct stm_criteria {
+  const double *y_holdout;
+  int32_t want_crps;
+  double *lppd, *p_waic, *mean_ll, *mu_mean, *pit, *crps;
+  double *obs, *held;
+  int64_t *n_obs, *n_held, *n_accumulated;
+} stm_criteria;
+int stm_rows_score_set(stm_chain c, const double *y_holdout);
+int stm_mcmc_criteria(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta, int ntheta,
+                      const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn, int mcmc_thin, uint64_t seed,
+                      const stm_flags *flags, double *w_mcmc, double *yhat_mcmc, double *beta_mcmc, double *tausq_mcmc,
+                      double *theta_mcmc, double *paramsd, double *mcmc_time, const stm_criteria *criteria);
+
 #ifdef __cplusplus
 }
 #endif

@@ -367,6 +367,56 @@ int st_points_functionals_info(st_handle h, int64_t *n_fun, int64_t *nnz, int64_
 int st_points_score_set(st_handle h, const double *y_new);
 int st_points_score_get(st_handle h, double *lpd, double *pit, double *crps, double *lpd_joint, int64_t *n_scored, int64_t *n_degenerate);
 
+/* ---- criteria over the fit's own rows, on the device: WAIC and DIC over the observed rows, and the scores of held-out values at
+ * NA rows of the problem (the reference's hold-out workflow: set part of y to NA, fit, compare yhat there with the truth).  All of
+ * it is CONDITIONAL ON w: saved draw s gives row i of margin j the Gaussian N(mu_s, tau2_j), mu_s = XB_i + w_i, tau2_j = 1 / tausq_inv_j,
+ * and nothing integrates the latent field out -- the WAIC penalty therefore counts the effective dimension of w as well.
+ * Row i has a target t_i: y_i when observed; y_holdout_i at an NA row with a finite held-out value; none otherwise (outputs NaN).
+ * With r_s = (t_i - mu_s) / sqrt(tau2_j), l_s = -r_s^2 / 2 - log(tau2_j) / 2 - log(2 pi) / 2 and the S draws accumulated since _set:
+ *   lppd_i = log((1 / S) sum_s exp l_s)   (the streaming log-sum-exp of st_points_score_*),   mean_ll_i = mean_s l_s,
+ *   p_waic_i = the sample variance of l_s (0 when S = 1),   mu_mean_i = mean_s mu_s,   pit_i = mean_s Phi(r_s) (held-out rows),
+ *   crps_i (held-out rows) = st_points_score_get's formula over the K yhat draws of the row that st_summary_reserve stored.
+ * Per outcome j (spamtree_amd/csrc/rows_score.hpp has every operation's order; tau2bar_j = mean_s tau2_j):
+ *   observed rows: lppd, p_waic, waic = -2 (lppd - p_waic), Dbar = -2 sum mean_ll, Dhat = -2 sum log N(y_i; mu_mean_i, tau2bar_j),
+ *                  p_D = Dbar - Dhat, dic = Dbar + p_D;      held-out rows: the sums of lppd, pit, crps and (t_i - mu_mean_i)^2.
+ * st_rows_score_set: y_holdout holds n_all values in model row order, NaN = none; NULL: criteria over the observed rows only.  A
+ *   finite value at an observed row, or an infinite value anywhere, is ST_ERR_USAGE naming the row, and the previous state stays.
+ *   Allocates and zeroes the state (6 doubles per row, 6 more for the outputs and the CRPS).  st_rows_score_clear frees it.
+ * st_rows_score_accumulate: one draw from the current w, XB and tausq_inv, on the handle's stream.  It consumes no draw of any
+ *   Philox stream, copies nothing to the host, synchronises nothing and writes nothing another step reads.
+ * st_rows_score_get: n_all values each, model row order, NaN where a row has no target (pit, crps: off the held-out rows); any
+ *   output may be NULL.  crps without a stored draw (st_summary_reserve before the st_summary_accumulate calls) is ST_ERR_USAGE.
+ * st_rows_score_totals: obs is ST_ROWS_OBS_N x q and held ST_ROWS_HELD_N x q, column-major (column j = outcome j), rows as the
+ *   macros below; n_obs and n_held hold q counts.  An outcome without rows reports count 0 and zeros.  The crps sums are 0 without
+ *   a stored draw.  Any output may be NULL.  Sums, not means: the caller divides by the counts.  The CRPS is sorted once per state
+ *   of the stored draws, and only for a call that returns it (crps of _get, held of _totals); the outputs and sums once per state.
+ * st_rows_score_info: the algorithmic bytes of one st_rows_score_accumulate, from shapes; needs no device (0 before _set).
+ * limited_tree handles are supported (nothing here depends on the tree); world > 1 handles are refused (ST_ERR_UNSUPPORTED).
+ * ST_ERR_USAGE with a text: any call before _set; _get / _totals before the first accumulate.
+ * A draw whose l_s is not finite (tausq_inv_j of 0 or infinity: a density of 0) leaves the row's log-sum-exp alone and enters the
+ * moments of l at their running mean: lppd stays the log of the mean density, but mean_ll and p_waic (hence Dbar, p_D, dic) are then
+ * not the moments of the draws, and tau2bar_j, Dhat, p_D and dic may be infinite.  Nothing is NaN. */
+#define ST_ROWS_OBS_LPPD 0
+#define ST_ROWS_OBS_P_WAIC 1
+#define ST_ROWS_OBS_WAIC 2
+#define ST_ROWS_OBS_DBAR 3
+#define ST_ROWS_OBS_DHAT 4
+#define ST_ROWS_OBS_P_D 5
+#define ST_ROWS_OBS_DIC 6
+#define ST_ROWS_OBS_N 7
+#define ST_ROWS_HELD_LPPD 0
+#define ST_ROWS_HELD_PIT 1
+#define ST_ROWS_HELD_CRPS 2
+#define ST_ROWS_HELD_SQERR 3
+#define ST_ROWS_HELD_N 4
+int st_rows_score_set(st_handle h, const double *y_holdout);
+int st_rows_score_clear(st_handle h);
+int st_rows_score_accumulate(st_handle h);
+int st_rows_score_get(st_handle h, double *lppd, double *p_waic, double *mean_ll, double *mu_mean, double *pit, double *crps,
+                      int64_t *n_accumulated);
+int st_rows_score_totals(st_handle h, double *obs, double *held, int64_t *n_obs, int64_t *n_held);
+int st_rows_score_info(st_handle h, double *alg_bytes);
+
 /* ---- prior simulation from slot 0: exact draws w ~ N(0, C_DAG) of the tree's own model and y = XB + w + sqrt(tau^2_j) eps.
  * st_simulate: a root-to-leaf sweep over slot 0 as the last st_factor(h, 0, theta) left it (a deferred leaf half is finished
  *   first), Ri_u w_u = z_u - N_u w_pa(u) per block, with the handle's current beta (XB) and tau^-2.  nd draws (1..16) in one

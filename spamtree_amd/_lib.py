@@ -116,6 +116,12 @@ SIGNATURES = {
     "st_points_functionals_info": (C.c_int, [H, c_ip, c_ip, c_ip, c_ip, c_dp]),
     "st_points_score_set": (C.c_int, [H, c_dp]),
     "st_points_score_get": (C.c_int, [H, c_dp, c_dp, c_dp, c_dp, c_ip, c_ip]),
+    "st_rows_score_set": (C.c_int, [H, c_dp]),
+    "st_rows_score_clear": (C.c_int, [H]),
+    "st_rows_score_accumulate": (C.c_int, [H]),
+    "st_rows_score_get": (C.c_int, [H, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_ip]),
+    "st_rows_score_totals": (C.c_int, [H, c_dp, c_dp, c_ip, c_ip]),
+    "st_rows_score_info": (C.c_int, [H, c_dp]),
     "st_simulate": (C.c_int, [H, C.c_int, c_dp, c_dp, C.c_uint64, C.c_uint32, c_dp, c_dp]),
     "st_simulate_info": (C.c_int, [H, C.c_int, C.POINTER(C.c_int32), c_dp, c_dp]),
     "st_simulate_route_name": (C.c_char_p, [C.c_int32]),
@@ -138,6 +144,15 @@ class StmScores(C.Structure):   # include/spamtree_fit.h, stm_scores
     _fields_ = [("y_new", c_dp), ("lpd", c_dp), ("pit", c_dp), ("crps", c_dp), ("lpd_joint", c_dp),
                 ("n_scored", c_ip), ("n_degenerate", c_ip)]
 
+
+class StmCriteria(C.Structure):   # include/spamtree_fit.h, stm_criteria
+    _fields_ = [("y_holdout", c_dp), ("want_crps", C.c_int32), ("lppd", c_dp), ("p_waic", c_dp), ("mean_ll", c_dp),
+                ("mu_mean", c_dp), ("pit", c_dp), ("crps", c_dp), ("obs", c_dp), ("held", c_dp), ("n_obs", c_ip),
+                ("n_held", c_ip), ("n_accumulated", c_ip)]
+
+
+ST_ROWS_OBS = ("lppd", "p_waic", "waic", "Dbar", "Dhat", "p_D", "dic")   # include/spamtree_hip.h: ST_ROWS_OBS_*, ST_ROWS_HELD_*
+ST_ROWS_HELD = ("lppd", "pit", "crps", "sqerr")
 
 # include/spamtree_fit.h (C++ host driver)
 SIGNATURES.update({
@@ -171,6 +186,9 @@ SIGNATURES.update({
     "stm_points_score_set": (C.c_int, [H, c_dp]),
 })
 SIGNATURES["stm_mcmc_scored"] = (C.c_int, SIGNATURES["stm_mcmc_functionals"][1] + [C.POINTER(StmScores)])
+
+SIGNATURES["stm_rows_score_set"] = (C.c_int, [H, c_dp])
+SIGNATURES["stm_mcmc_criteria"] = (C.c_int, SIGNATURES["spamtree_mv_mcmc_c"][1] + [C.POINTER(StmCriteria)])
 
 # include/spamtree_tree.h (device parts of the tree builder)
 c_i32p = C.POINTER(C.c_int32)

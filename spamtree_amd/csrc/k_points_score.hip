@@ -12,15 +12,6 @@ __device__ __forceinline__ double sc_xb(const double *X, const double *B, long l
   return xb;
 }
 
-// One draw's log density l into the running (M, A) of log sum exp: A == 0 marks "no draw yet" (afterwards A >= 1: the maximum
-// itself contributes exp(0)); a tie takes the first branch.  A density of 0 (l = -inf) leaves the state alone.
-__device__ __forceinline__ void sc_lse(double l, double &M, double &A) {
-  if (!(l >= -__DBL_MAX__)) return;
-  if (A == 0.0) { M = l; A = 1.0; }
-  else if (l <= M) A += exp(l - M);
-  else { A = fma(A, exp(M - l), 1.0); M = l; }
-}
-
 // One thread per point: reads y, cond_mean, cond_var, the margin and p regressors (28 + 8 p B) and the three state values (24 B),
 // writes the state back (24 B).  In order: xb (p fma), mu = xb + cond_mean, e = y - mu, s2 = cond_var + 1 / tausq_inv, sigma =
 // sqrt(s2), r = e / sigma, l = fma(-r / 2, r, -log sigma) + HL2PI, the (M, A) update, pit += erfc(-r / sqrt 2) / 2.

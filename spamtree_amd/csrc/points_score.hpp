@@ -27,6 +27,16 @@
 #define SC_NACC 3
 #define SC_GROUPS_PER_WG (NT / 16)               // k_score_joint_acc: 16 lanes a group
 
+// One draw's log density l into the running (M, A) of log sum exp: A == 0 marks "no draw yet" (afterwards A >= 1: the maximum
+// itself contributes exp(0)); a tie takes the first branch.  A density of 0 (l = -inf) leaves the state alone.  The one copy:
+// k_score_acc, k_score_joint_acc and k_rows_score_acc (rows_score.hpp) all update through it.
+__device__ __forceinline__ void sc_lse(double l, double &M, double &A) {
+  if (!(l >= -__DBL_MAX__)) return;
+  if (A == 0.0) { M = l; A = 1.0; }
+  else if (l <= M) A += exp(l - M);
+  else { A = fma(A, exp(M - l), 1.0); M = l; }
+}
+
 struct ScoreArgs {                 // k_score_acc
   const double *y;                 // n, caller order; NaN: not scored
   const double *mean, *var;        // this iteration's cond_mean and clamped cond_var (d_out)

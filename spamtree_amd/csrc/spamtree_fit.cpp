@@ -427,6 +427,13 @@ extern "C" int stm_points_score_set(stm_chain c, const double *y_new) {
   return ST_OK;
 }
 
+extern "C" int stm_rows_score_set(stm_chain c, const double *y_holdout) {
+  if (!c || !c->h) return ST_ERR_USAGE;
+  const int rc = st_rows_score_set(c->h, y_holdout);
+  if (rc != 0) { c->err = st_last_error(c->h); return rc; }
+  return ST_OK;
+}
+
 namespace {
 struct FitPoints {   // the point set of stm_mcmc_points and where its per-draw outputs go (n_new x keep, any may be NULL)
   int64_t n;
@@ -439,10 +446,12 @@ struct FitPoints {   // the point set of stm_mcmc_points and where its per-draw 
 
 // The whole of spamtree_mv_mcmc (spamtree_fit.cpp:5-430), on a created chain.  With pts, every saved iteration also predicts at the
 // point set once tausq and beta are drawn: the saved theta's factor in slot 0, the saved w, beta and tausq; draw counter = saved
-// index, Philox streams 6 / 7 only, so the chain itself is the same draw for draw.
+// index, Philox streams 6 / 7 only, so the chain itself is the same draw for draw.  With crit, every saved iteration also updates
+// the criteria over the fit's own rows (st_rows_score_accumulate) and, when their CRPS is wanted, stores the iteration's yhat on
+// the device (st_summary_accumulate: stream 5 with the iteration's counter, what st_yhat draws).
 static int run_fit(stm_chain c, int mcmc_keep, int mcmc_burn, int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc,
                    double *yhat_mcmc, double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
-                   const FitPoints *pts) {
+                   const FitPoints *pts, const stm_criteria *crit = nullptr) {
   int rc = 0;
   const int sample_predicts = flags ? flags->sample_predicts : 1;
   const auto t0 = std::chrono::steady_clock::now();
@@ -487,6 +496,11 @@ static int run_fit(stm_chain c, int mcmc_keep, int mcmc_burn, int mcmc_thin, uin
           rc = st_points_functionals_last(c->h, fcol(pts->fun->fun_w), fcol(pts->fun->fun_cond_mean), fcol(pts->fun->fun_cond_var),
                                           fcol(pts->fun->fun_yhat));
         }
+        if (rc) c->err = st_last_error(c->h);
+      }
+      if (!rc && crit) {
+        rc = st_rows_score_accumulate(c->h);
+        if (!rc && crit->want_crps && crit->y_holdout) rc = st_summary_accumulate(c->h, seed, (uint32_t)m);
         if (rc) c->err = st_last_error(c->h);
       }
       ++msaved;
@@ -620,6 +634,36 @@ extern "C" int stm_mcmc_scored(const st_problem *pb, const st_options *opt, cons
                                         fun->fun_yhat_q ? fun->fun_yhat_q + (size_t)i * fun->n_fun : nullptr);
   if (rc == 0 && scores && mcmc_keep > 0)
     rc = st_points_score_get(c->h, scores->lpd, scores->pit, scores->crps, scores->lpd_joint, scores->n_scored, scores->n_degenerate);
+  stm_destroy(c);
+  return rc;
+}
+
+// spamtree_mv_mcmc_c plus the criteria over the fit's own rows; criteria NULL: spamtree_mv_mcmc_c itself
+extern "C" int stm_mcmc_criteria(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
+                                 int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
+                                 int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
+                                 double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
+                                 const stm_criteria *criteria) {
+  const stm_criteria *cr = criteria;
+  const bool crps = cr && cr->want_crps && cr->y_holdout;
+  if (cr && cr->crps && !crps) return ST_ERR_USAGE;
+  if (crps && mcmc_keep > 16384) return ST_ERR_UNSUPPORTED;   // st_summary_reserve's limit
+  if (cr && cr->y_holdout && flags && (!flags->sample_predicts || !flags->sample_w)) return ST_ERR_USAGE;   // the NA rows' w would be stale
+  stm_chain c = nullptr;
+  int rc = stm_create(pb, opt, set_unif_bounds, mcmcsd, theta, ntheta, beta, tausq, seed, flags, &c);
+  if (rc == 0 && cr) rc = stm_rows_score_set(c, cr->y_holdout);   // refusals: before any factorisation
+  if (rc == 0 && crps && mcmc_keep > 0) {
+    rc = st_summary_reset(c->h);
+    if (rc == 0) rc = st_summary_reserve(c->h, mcmc_keep);
+  }
+  if (rc == 0) rc = stm_init(c);
+  if (rc != 0) { stm_destroy(c); return rc; }
+  rc = run_fit(c, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc, yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time,
+               nullptr, cr);
+  if (rc == 0 && cr && mcmc_keep > 0) {
+    rc = st_rows_score_get(c->h, cr->lppd, cr->p_waic, cr->mean_ll, cr->mu_mean, cr->pit, cr->crps, cr->n_accumulated);
+    if (rc == 0) rc = st_rows_score_totals(c->h, cr->obs, cr->held, cr->n_obs, cr->n_held);
+  }
   stm_destroy(c);
   return rc;
 }

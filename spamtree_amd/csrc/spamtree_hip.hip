@@ -26,6 +26,7 @@
 
 #include "st_handle.hpp"
 #include "misc_kernels.hpp"
+#include "rows_score.hpp"
 #include <new>
 
 // ===============================================================================================================
@@ -1564,7 +1565,7 @@ extern "C" int st_summary_reset(st_handle h) {
   if (!h->d_sum_w.p) { HCHK(h, h->d_sum_w.alloc(h->n_all)); HCHK(h, h->d_sum_yhat.alloc(h->n_all)); }
   HCHK(h, hipMemsetAsync(h->d_sum_w.p, 0, h->n_all * sizeof(double), h->stream));
   HCHK(h, hipMemsetAsync(h->d_sum_yhat.p, 0, h->n_all * sizeof(double), h->stream));
-  h->n_summary = 0; h->n_draws = 0;
+  h->n_summary = 0; h->n_draws = 0; h->draws_epoch += 1;
   return ST_OK;
 }
 extern "C" int st_summary_accumulate(st_handle h, uint64_t seed, uint32_t iter) {   // yhat noise: device stream 5 (spamtree_fit.cpp:384)
@@ -1581,7 +1582,7 @@ extern "C" int st_summary_accumulate(st_handle h, uint64_t seed, uint32_t iter) 
   if (h->n_draws < h->draws_cap) {   // keep the draw itself for the quantiles (device order, one contiguous row per draw)
     HCHK(h, hipMemcpyAsync(h->d_draws_w.p + (size_t)h->n_draws * h->n_all, h->d_w.p, h->n_all * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     HCHK(h, hipMemcpyAsync(h->d_draws_yhat.p + (size_t)h->n_draws * h->n_all, h->d_tmp_n.p, h->n_all * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    h->n_draws += 1;
+    h->n_draws += 1; h->draws_epoch += 1;
   }
   h->n_summary += 1;
   return ST_OK;
@@ -1591,7 +1592,7 @@ extern "C" int st_summary_reserve(st_handle h, int64_t keep) {
   HCHK(h, hipSetDevice(h->device));
   HCHK(h, hipStreamSynchronize(h->stream));
   h->d_draws_w.free(); h->d_draws_yhat.free();
-  h->draws_cap = 0; h->n_draws = 0;
+  h->draws_cap = 0; h->n_draws = 0; h->draws_epoch += 1;
   if (keep == 0) return ST_OK;
   if (keep > 16384) { h->err = "st_summary_reserve: at most 16384 saved draws (one row's draws are sorted in one workgroup's LDS)"; return ST_ERR_UNSUPPORTED; }
   HCHK(h, h->d_draws_w.alloc((size_t)keep * h->n_all));
@@ -1632,6 +1633,173 @@ extern "C" int st_summary_get(st_handle h, double *w_mean, double *yhat_mean, in
   return ST_OK;
 }
 
+
+// ---- criteria over the fit's own rows (rows_score.hpp; the kernels and their launchers live in k_rows_score.hip) ----
+static int rows_refuse(st_handle h, const char *who, bool need_set = true, bool need_draw = false) {
+  if (h->world > 1) { h->err = std::string(who) + ": multi-GPU handles are not supported"; return ST_ERR_UNSUPPORTED; }
+  if (need_set && !h->rs_set) { h->err = std::string(who) + " before st_rows_score_set"; return ST_ERR_USAGE; }
+  if (need_draw && h->rs_n_acc == 0) { h->err = std::string(who) + ": no iteration accumulated"; return ST_ERR_USAGE; }
+  return ST_OK;
+}
+static void rows_free(st_handle h) {
+  h->d_rs_tgt.free(); h->d_rs_hold.free(); h->d_rs_acc.free(); h->d_rs_rows.free(); h->d_rs_crps.free(); h->d_rs_partial.free();
+  h->d_rs_tot.free();
+  h->rs_set = false; h->rs_n_acc = 0; h->rs_n_tgt = 0; h->rs_n_held = 0;
+  h->rs_crps_epoch = -1; h->rs_fin_acc = -1; h->rs_fin_crps = -2;
+}
+extern "C" int st_rows_score_set(st_handle h, const double *y_holdout) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = rows_refuse(h, "st_rows_score_set", false)) return rc;
+  HCHK(h, hipSetDevice(h->device));
+  const long long n = h->n_all;
+  std::vector<double> y(n), tgt(n), hold(n);
+  std::vector<unsigned char> obs(n);
+  std::vector<int> mv(n);
+  HCHK(h, hipMemcpyAsync(y.data(), h->d_y.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipMemcpyAsync(obs.data(), h->d_obs.p, n * sizeof(unsigned char), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipMemcpyAsync(mv.data(), h->d_mv.p, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  // a refusal leaves the previous state in place: every check comes before the first change
+  for (long long r = 0; y_holdout && r < n; ++r) {
+    const double v = y_holdout[r];
+    if (std::isinf(v)) { h->err = "st_rows_score_set: y_holdout[" + std::to_string(r) + "] is infinite (NaN marks a row without a held-out value)"; return ST_ERR_USAGE; }
+    if (!std::isnan(v) && obs[h->model2dev[r]]) { h->err = "st_rows_score_set: y_holdout[" + std::to_string(r) + "] is finite at an observed row (held-out values belong to NA rows)"; return ST_ERR_USAGE; }
+  }
+  std::vector<long long> nobs(h->q, 0), nheld(h->q, 0);
+  long long n_tgt = 0, n_held = 0;
+  const double nan = std::nan("");
+  for (long long i = 0; i < n; ++i) {
+    const double v = y_holdout ? y_holdout[h->dev2model[i]] : nan;
+    hold[i] = obs[i] ? nan : v;
+    tgt[i] = obs[i] ? y[i] : v;
+    if (obs[i]) nobs[mv[i]]++;
+    else if (!std::isnan(v)) { nheld[mv[i]]++; ++n_held; }
+    n_tgt += !std::isnan(tgt[i]);
+  }
+  DevBuf<double> d_tgt, d_hold, d_acc, d_rows, d_crps, d_partial, d_tot;   // the handle takes them once every allocation has succeeded
+  HCHK(h, d_tgt.upload(tgt)); HCHK(h, d_hold.upload(hold));
+  HCHK(h, d_acc.alloc((size_t)RS_NACC * n)); HCHK(h, d_rows.alloc((size_t)RS_NOUT * n)); HCHK(h, d_crps.alloc((size_t)n));
+  HCHK(h, d_partial.alloc((size_t)STATS_WG * h->q * RS_NSUM)); HCHK(h, d_tot.alloc((size_t)h->q * RS_NSUM));
+  HCHK(h, hipMemsetAsync(d_acc.p, 0, (size_t)RS_NACC * n * sizeof(double), h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  h->d_rs_tgt = std::move(d_tgt); h->d_rs_hold = std::move(d_hold); h->d_rs_acc = std::move(d_acc); h->d_rs_rows = std::move(d_rows);
+  h->d_rs_crps = std::move(d_crps); h->d_rs_partial = std::move(d_partial); h->d_rs_tot = std::move(d_tot);
+  h->rs_nobs_q = nobs; h->rs_nheld_q = nheld;
+  h->rs_n_tgt = n_tgt; h->rs_n_held = n_held; h->rs_n_acc = 0; h->rs_set = true;
+  h->rs_crps_epoch = -1; h->rs_fin_acc = -1; h->rs_fin_crps = -2;
+  for (int j = 0; j < QMAX; ++j) h->rs_tau2_sum[j] = 0.0;
+  return ST_OK;
+}
+extern "C" int st_rows_score_clear(st_handle h) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = rows_refuse(h, "st_rows_score_clear", false)) return rc;
+  HCHK(h, hipSetDevice(h->device));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  rows_free(h);
+  return ST_OK;
+}
+extern "C" int st_rows_score_accumulate(st_handle h) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = rows_refuse(h, "st_rows_score_accumulate")) return rc;
+  HCHK(h, hipSetDevice(h->device));
+  RowsScoreArgs A;
+  A.tgt = h->d_rs_tgt.p; A.obs = h->d_obs.p; A.xb = h->d_xb.p; A.w = h->d_w.p; A.tsq_inv = h->d_tsq.p; A.mv = h->d_mv.p;
+  A.n = h->n_all; A.S = (double)(h->rs_n_acc + 1); A.acc = h->d_rs_acc.p;
+  const int e = rows_score_launch(A, h->stream);
+  if (e) { h->err = std::string("st_rows_score_accumulate launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+  for (int j = 0; j < h->q; ++j) h->rs_tau2_sum[j] += 1.0 / h->tausq_inv[j];
+  h->rs_n_acc += 1;
+  return ST_OK;
+}
+// The per-row outputs and the sums, enqueued on the handle's stream; with need_crps (and draws stored, and a held-out row) first
+// the CRPS of the held-out rows.  Each is computed once per state: the CRPS per epoch of the stored draws, the outputs and sums per
+// (draws accumulated, CRPS summed), so st_rows_score_get followed by st_rows_score_totals sorts the draws once.
+static int rows_finish(st_handle h, bool need_crps, bool *have_crps) {
+  const bool can = h->n_draws > 0 && h->rs_n_held > 0;
+  if (need_crps && can && h->rs_crps_epoch != h->draws_epoch) {   // the launch rule of st_summary_quantile
+    ScoreCrpsArgs C;
+    int Kpad = 2;
+    while (Kpad < h->n_draws) Kpad <<= 1;
+    C.draws = h->d_draws_yhat.p; C.y = h->d_rs_hold.p; C.n = h->n_all; C.keep = (int)h->n_draws; C.Kpad = Kpad;
+    C.R = std::max(1, std::min(8, (int)(128 * 1024 / ((size_t)Kpad * 8))));
+    C.out = h->d_rs_crps.p;
+    const int e = points_score_crps_launch(C, h->lds_limit, h->stream);
+    if (e) { h->err = std::string("st_rows_score crps launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+    h->rs_crps_epoch = h->draws_epoch;
+  }
+  *have_crps = can && h->rs_crps_epoch == h->draws_epoch;
+  const long long with = *have_crps ? h->draws_epoch : -1;
+  if (h->rs_fin_acc == h->rs_n_acc && h->rs_fin_crps == with) return ST_OK;
+  RowsTotalsArgs T;
+  T.tgt = h->d_rs_tgt.p; T.obs = h->d_obs.p; T.mv = h->d_mv.p; T.acc = h->d_rs_acc.p; T.crps = *have_crps ? h->d_rs_crps.p : nullptr;
+  T.n = h->n_all; T.S = (double)h->rs_n_acc; T.rows = h->d_rs_rows.p; T.partial = h->d_rs_partial.p;
+  for (int j = 0; j < QMAX; ++j) T.tau2bar[j] = j < h->q ? h->rs_tau2_sum[j] / (double)h->rs_n_acc : 1.0;
+  const int e = rows_score_totals_launch(T, h->q, h->d_rs_tot.p, h->stream);
+  if (e) { h->err = std::string("st_rows_score totals launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+  h->rs_fin_acc = h->rs_n_acc; h->rs_fin_crps = with;
+  return ST_OK;
+}
+extern "C" int st_rows_score_get(st_handle h, double *lppd, double *p_waic, double *mean_ll, double *mu_mean, double *pit, double *crps,
+                                 int64_t *n_accumulated) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = rows_refuse(h, "st_rows_score_get")) return rc;
+  if (n_accumulated) *n_accumulated = h->rs_n_acc;
+  if (const int rc = rows_refuse(h, "st_rows_score_get", true, true)) return rc;
+  if (crps && h->n_draws == 0) { h->err = "st_rows_score_get: crps needs a stored draw (st_summary_reserve before the st_summary_accumulate calls)"; return ST_ERR_USAGE; }
+  HCHK(h, hipSetDevice(h->device));
+  bool have_crps = false;
+  if (const int rc = rows_finish(h, crps != nullptr, &have_crps)) return rc;
+  double *const dst[RS_NOUT] = {lppd, mean_ll, p_waic, mu_mean, pit};   // RS_OUT_* order
+  for (int k = 0; k < RS_NOUT; ++k)
+    if (dst[k])
+      if (const int rc = download_rows(h, h->d_rs_rows.p + (size_t)k * h->n_all, dst[k])) return rc;
+  if (crps) {
+    if (have_crps) { if (const int rc = download_rows(h, h->d_rs_crps.p, crps)) return rc; }
+    else for (long long i = 0; i < h->n_all; ++i) crps[i] = std::nan("");   // (no held-out row)
+  }
+  return ST_OK;
+}
+extern "C" int st_rows_score_totals(st_handle h, double *obs, double *held, int64_t *n_obs, int64_t *n_held) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = rows_refuse(h, "st_rows_score_totals", true, true)) return rc;
+  HCHK(h, hipSetDevice(h->device));
+  bool have_crps = false;
+  if (const int rc = rows_finish(h, held != nullptr, &have_crps)) return rc;
+  std::vector<double> t((size_t)h->q * RS_NSUM);
+  HCHK(h, hipMemcpyAsync(t.data(), h->d_rs_tot.p, t.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  for (int j = 0; j < h->q; ++j) {
+    const double *s = t.data() + (size_t)j * RS_NSUM;
+    if (n_obs) n_obs[j] = h->rs_nobs_q[j];
+    if (n_held) n_held[j] = h->rs_nheld_q[j];
+    if (obs) {
+      double *o = obs + (size_t)j * ST_ROWS_OBS_N;
+      o[ST_ROWS_OBS_LPPD] = s[RS_SUM_O_LPPD];
+      o[ST_ROWS_OBS_P_WAIC] = s[RS_SUM_O_PWAIC];
+      o[ST_ROWS_OBS_WAIC] = -2.0 * (o[ST_ROWS_OBS_LPPD] - o[ST_ROWS_OBS_P_WAIC]);
+      o[ST_ROWS_OBS_DBAR] = -2.0 * s[RS_SUM_O_MEANLL];
+      o[ST_ROWS_OBS_DHAT] = -2.0 * s[RS_SUM_O_LOGN];
+      o[ST_ROWS_OBS_P_D] = o[ST_ROWS_OBS_DBAR] - o[ST_ROWS_OBS_DHAT];
+      o[ST_ROWS_OBS_DIC] = o[ST_ROWS_OBS_DBAR] + o[ST_ROWS_OBS_P_D];
+      if (h->rs_nobs_q[j] == 0) for (int k = 0; k < ST_ROWS_OBS_N; ++k) o[k] = 0.0;   // (not -0)
+    }
+    if (held) {
+      double *o = held + (size_t)j * ST_ROWS_HELD_N;
+      o[ST_ROWS_HELD_LPPD] = s[RS_SUM_H_LPPD];
+      o[ST_ROWS_HELD_PIT] = s[RS_SUM_H_PIT];
+      o[ST_ROWS_HELD_CRPS] = s[RS_SUM_H_CRPS];
+      o[ST_ROWS_HELD_SQERR] = s[RS_SUM_H_SQERR];
+    }
+  }
+  return ST_OK;
+}
+// from shapes: every row reads its target; a targeted row also obs, mv, xb, w (21 B) and reads and writes five doubles of
+// state, a held-out row six
+extern "C" int st_rows_score_info(st_handle h, double *alg_bytes) {
+  if (!h || !alg_bytes) return ST_ERR_USAGE;
+  *alg_bytes = h->rs_set ? 8.0 * (double)h->n_all + (21.0 + 80.0) * (double)h->rs_n_tgt + 16.0 * (double)h->rs_n_held : 0.0;
+  return ST_OK;
+}
 
 // ---- prior simulation from slot 0 (st_simulate; the kernels and their launcher live in k_simulate.hip) ----
 static int sim_pad(int nd) { int p = 1; while (p < nd) p <<= 1; return p; }

@@ -70,6 +70,16 @@ struct st_handle_s : TreeLayout {
   long long n_summary = 0;
   DevBuf<double> d_draws_w, d_draws_yhat;     // st_summary_reserve: the saved draws themselves, [keep][n_all] (quantiles)
   long long draws_cap = 0, n_draws = 0;
+  // st_rows_score_*: criteria over the fit's own rows (rows_score.hpp); device row order throughout
+  DevBuf<double> d_rs_tgt, d_rs_hold;         // the targets; the same with NaN off the held-out rows (k_score_crps's y)
+  DevBuf<double> d_rs_acc, d_rs_rows, d_rs_crps, d_rs_partial, d_rs_tot;
+  bool rs_set = false;
+  long long rs_n_acc = 0, rs_n_tgt = 0, rs_n_held = 0;
+  std::vector<long long> rs_nobs_q, rs_nheld_q;
+  long long draws_epoch = 0;                  // advances whenever the stored draws of st_summary_reserve change
+  long long rs_crps_epoch = -1;               // d_rs_crps holds the CRPS of the stored draws of that epoch (-1: none)
+  long long rs_fin_acc = -1, rs_fin_crps = -2;   // d_rs_rows / d_rs_tot are those of rs_fin_acc draws, with the CRPS of that epoch summed (-1: without)
+  double rs_tau2_sum[ST_MAX_Q] = {0};         // sum over the accumulated draws of 1 / tausq_inv_j, added in call order
   bool stats_valid = false;                   // d_stats matches the current w and XB
   bool host_stats_valid = false;              // ... and host_stats holds a copy of it
   std::vector<double> host_stats;

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .model import SpamTreeError, _dp, _f64, _i64, _ip, _lists_to_csr, functionals_csr, joint_labels, score_totals, score_values
+from .model import SpamTreeError, _dp, _f64, _i64, _ip, _lists_to_csr, functionals_csr, joint_labels, rows_criteria, rows_holdout, score_totals, score_values
 
 
 def _problem(y, X, coords, mv_id, res_is_ref, parents, children, block_names, block_groups, indexing):
@@ -238,7 +238,8 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                      mcmc_keep=100, mcmc_burn=100, mcmc_thin=1, num_threads=1, use_alg="S", adapting=False,
                      main_verbose=True, verbose=False, debug=False, printall=False, sample_beta=True, sample_tausq=True,
                      sample_theta=True, sample_w=True, sample_predicts=True, seed=2021, device=0, reference_quirks=True,
-                     new_points=None, new_draws=True, new_quantiles=(), save_w=True, save_yhat=True, force_generic=False):
+                     new_points=None, new_draws=True, new_quantiles=(), save_w=True, save_yhat=True, force_generic=False,
+                     criteria=False, y_holdout=None, holdout_crps=True):
     """spamtree_fit.cpp:5-430 through the C++ driver.  `num_threads`, `use_alg`, the verbosity flags and `start_w` are
     accepted and ignored exactly where the reference ignores them (start_w, :95) or where they do not apply to a GPU.
 
@@ -263,7 +264,29 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     stored yhat draws (which stay on the device: nothing per draw comes to the host for it), per joint group the joint log
     predictive density, and ``model.score_totals``' means, with the coverage of [yhat_lo, yhat_hi] for the lowest and highest of
     two or more ``new_quantiles``.  The CRPS makes the device keep ``mcmc_keep`` draws of w and yhat per point (16 B each per
-    point and draw; at most 16384 draws, more is a ValueError); ``new_points["crps"] = False`` scores without it and stores nothing."""
+    point and draw; at most 16384 draws, more is a ValueError); ``new_points["crps"] = False`` scores without it and stores nothing.
+    ``criteria=True``: WAIC and DIC over the observed rows, on the device (stm_mcmc_criteria; the chain is the same bit for bit, and
+    nothing per draw comes to the host, so it works with ``save_w=False, save_yhat=False``).  ``y_holdout``: the truth at NA rows
+    of ``y`` (one value per row, NaN = none; ``model.rows_holdout`` checks it), scored there on every saved iteration; it implies
+    ``criteria`` and needs ``sample_predicts``.  The result then holds ``criteria``: the per-row arrays ``lppd``, ``p_waic``,
+    ``mean_ll``, ``mu_mean``, ``pit``, ``crps`` (NaN where a row has no target; pit and crps at held-out rows only) and ``totals`` =
+    ``model.rows_criteria``'s dict(observed, held_out), each overall and by outcome.  Every criterion is CONDITIONAL ON w: the
+    likelihood is N(y; XB + w, tausq), so the WAIC and DIC penalties count the effective dimension of the latent field too.  The
+    CRPS makes the device keep ``mcmc_keep`` draws of w and yhat per row (at most 16384, more is a ValueError);
+    ``holdout_crps=False`` scores without it.  Not together with ``new_points``.  As with ``new_points``, a failure of the
+    chain (a refusal of the library, a Cholesky failure code) raises SpamTreeError with ``code`` set, where the plain call prints
+    "MCMC has been interrupted." and returns ``{"None": ...}``; a NaN log-density is a FloatingPointError in both."""
+    crit = bool(criteria) or y_holdout is not None
+    if crit:
+        if new_points is not None:
+            raise ValueError("criteria and new_points are separate drivers (stm_mcmc_criteria, stm_mcmc_scored): one per call")
+        y_hold = rows_holdout(y_holdout, y)
+        if y_hold is not None and not (sample_predicts and sample_w):
+            raise ValueError("y_holdout needs sample_predicts and sample_w: the NA rows' w would be stale")
+        want_crps = bool(holdout_crps) and y_hold is not None
+        if want_crps and int(mcmc_keep) > MAX_STORED_DRAWS:
+            raise ValueError(f"y_holdout: the CRPS keeps mcmc_keep = {int(mcmc_keep)} draws per row on the device, at most "
+                             f"{MAX_STORED_DRAWS} (holdout_crps=False scores without it)")
     if new_points is not None:
         pts = _points_inputs(new_points, np.asarray(X).shape[1], int(np.unique(_i64(mv_id)).size), new_quantiles)
         if pts[8] and int(mcmc_keep) > MAX_STORED_DRAWS:
@@ -289,7 +312,24 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
               int(mcmc_burn), int(mcmc_thin), int(seed), C.byref(fl), dp(w_all), dp(yh_all), _dp(beta_mcmc), _dp(tausq_mcmc),
               _dp(theta_mcmc), _dp(paramsd), C.byref(t))
     new = None
-    if new_points is None:
+    crit_out = None
+    if crit:
+        rows = {key: np.zeros(n) for key in ("lppd", "p_waic", "mean_ll", "mu_mean", "pit")}
+        rows["crps"] = np.zeros(n) if (want_crps and mcmc_keep > 0) else None
+        tobs = np.zeros((len(_lib.ST_ROWS_OBS), q), order="F"); theld = np.zeros((len(_lib.ST_ROWS_HELD), q), order="F")
+        n_obs, n_held = np.zeros(q, dtype=np.int64), np.zeros(q, dtype=np.int64)
+        nacc = C.c_int64()
+        cs = _lib.StmCriteria(dp(y_hold), int(want_crps), *[dp(rows[key]) for key in ("lppd", "p_waic", "mean_ll", "mu_mean", "pit", "crps")],
+                              _dp(tobs), _dp(theld), _ip(n_obs), _ip(n_held), C.pointer(nacc))
+        rc = lib.stm_mcmc_criteria(*common, C.byref(cs))
+        if rc == 0 and mcmc_keep > 0:
+            crit_out = dict(rows, n_accumulated=int(nacc.value),
+                            totals=rows_criteria(tobs, theld, n_obs, n_held, have_crps=rows["crps"] is not None))
+        elif rc not in (0, -10):
+            err = SpamTreeError(f"stm_mcmc_criteria failed ({rc})")
+            err.code = rc
+            raise err
+    elif new_points is None:
         rc = lib.spamtree_mv_mcmc_c(*common)
     else:
         pc, pmv, pan, pX, qs, labels, fun, ynew, want_crps = pts
@@ -380,4 +420,6 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     out.update(beta_mcmc=beta_mcmc, tausq_mcmc=tausq_mcmc, theta_mcmc=theta_mcmc, paramsd=paramsd, mcmc_time=t.value)
     if new is not None:
         out["new"] = new
+    if crit_out is not None:
+        out["criteria"] = crit_out
     return out

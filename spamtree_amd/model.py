@@ -92,6 +92,65 @@ def score_totals(scores, y, mv, q, yhat_lo=None, yhat_hi=None):
     return tot
 
 
+def rows_holdout(y_holdout, y):
+    """Held-out values at NA rows of the problem as one float64 vector in model row order, checked before any device call: one
+    value per row of ``y``, NaN where there is none, finite only where ``y`` is NaN, nothing infinite.  None stays None."""
+    if y_holdout is None:
+        return None
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    t = np.asarray(y_holdout, dtype=np.float64)
+    if t.ndim == 2 and 1 in t.shape:
+        t = t.reshape(-1)
+    if t.ndim != 1 or t.size != y.size:
+        raise ValueError(f"y_holdout must hold one value per row of y ({y.size}), NaN where there is no held-out value")
+    bad = np.nonzero(np.isinf(t))[0]
+    if bad.size:
+        raise ValueError(f"y_holdout[{int(bad[0])}] is infinite (NaN marks a row without a held-out value)")
+    bad = np.nonzero(np.isfinite(t) & np.isfinite(y))[0]
+    if bad.size:
+        raise ValueError(f"y_holdout[{int(bad[0])}] is finite at an observed row (held-out values belong to the NA rows of y)")
+    return _f64(t)
+
+
+def rows_criteria(obs, held, n_obs, n_held, have_crps=True):
+    """st_rows_score_totals' two tables (ST_ROWS_OBS_N x q and ST_ROWS_HELD_N x q, one column per outcome) as
+    dict(observed, held_out), each overall and ``by_outcome``.  observed: n, lppd, p_waic, waic, Dbar, Dhat, p_D, dic -- the overall
+    lppd, p_waic, Dbar and Dhat are the outcomes' sums in outcome order and waic = -2 (lppd - p_waic), p_D = Dbar - Dhat,
+    dic = Dbar + p_D are formed from those doubles, as the library forms each outcome's.  held_out: n and the means lppd (the log
+    score), pit, crps (None without stored draws), mse, and rmse; NaN where there is no held-out row.  All conditional on w."""
+    obs = np.asarray(obs, dtype=np.float64).reshape(len(_lib.ST_ROWS_OBS), -1, order="F")
+    held = np.asarray(held, dtype=np.float64).reshape(len(_lib.ST_ROWS_HELD), -1, order="F")
+    n_obs, n_held = np.asarray(n_obs, dtype=np.int64), np.asarray(n_held, dtype=np.int64)
+    o = {k: obs[i].copy() for i, k in enumerate(_lib.ST_ROWS_OBS)}
+    observed = dict(n=int(n_obs.sum()))
+    for k in ("lppd", "p_waic", "Dbar", "Dhat"):
+        t = 0.0
+        for v in o[k]:          # in outcome order
+            t = t + float(v)
+        observed[k] = t
+    observed["waic"] = -2.0 * (observed["lppd"] - observed["p_waic"])
+    observed["p_D"] = observed["Dbar"] - observed["Dhat"]
+    observed["dic"] = observed["Dbar"] + observed["p_D"]
+    observed["by_outcome"] = dict(o, n=n_obs.copy())
+    with np.errstate(invalid="ignore", divide="ignore"):
+        hm = {k: np.where(n_held > 0, held[i] / n_held, np.nan) for i, k in enumerate(_lib.ST_ROWS_HELD)}
+    nh = int(n_held.sum())
+    held_out = dict(n=nh)
+    for i, k in enumerate(_lib.ST_ROWS_HELD):
+        t = 0.0
+        for v in held[i]:
+            t = t + float(v)
+        held_out[k] = t / nh if nh else float("nan")
+    for d in (held_out, hm):
+        d["mse"] = d.pop("sqerr")
+        d["rmse"] = np.sqrt(d["mse"])
+        if not have_crps:
+            d["crps"] = None
+    held_out["rmse"] = float(held_out["rmse"])
+    held_out["by_outcome"] = dict(hm, n=n_held.copy())
+    return dict(observed=observed, held_out=held_out)
+
+
 def functionals_csr(A, n_points):
     """Linear functionals of the predictions at ``n_points`` points as CSR ``(ptr, idx, wt)``, checked before any device call.
     ``A``: a ``(ptr, idx, wt)`` triple (a tuple of three whose entries are not themselves (indices, weights) pairs); a dense n_fun x n_points array, whose zeros are dropped; or a list of
@@ -605,6 +664,53 @@ class SpamTreeMV:
         out.update(n_scored=int(ns.value), n_degenerate=int(nd.value))
         out["totals"] = score_totals(out, self.score_y, self.points_mv, self.q, yhat_lo, yhat_hi)
         return out
+
+    # ---- criteria over the fit's own rows (st_rows_score_*): conditional on w
+    def rows_score_set(self, y_holdout=None, y=None):
+        """Starts the criteria over the model's rows: WAIC / DIC over the observed rows and, with ``y_holdout`` (one value per
+        row in model row order, NaN = none, finite only at NA rows), the scores of those held-out values.  ``y``: the model's y,
+        to check ``y_holdout`` against before the device call (``rows_holdout``); without it the library checks."""
+        t = rows_holdout(y_holdout, y) if (y is not None and y_holdout is not None) else (None if y_holdout is None else _f64(y_holdout))
+        if t is not None and t.shape != (self.n_all,):
+            raise ValueError(f"y_holdout must hold one value per row ({self.n_all})")
+        self._check(self.lib.st_rows_score_set(self.h, _dp(t) if t is not None else None))
+
+    def rows_score_clear(self):
+        self._check(self.lib.st_rows_score_clear(self.h))
+
+    def rows_score_accumulate(self):
+        """One draw from the current w, XB and tausq_inv into the criteria's state; nothing comes to the host."""
+        self._check(self.lib.st_rows_score_accumulate(self.h))
+
+    def rows_score_get(self, crps=False):
+        """dict(lppd, p_waic, mean_ll, mu_mean, pit, crps, n_accumulated): n_all values each in model row order, NaN where a row
+        has no target (pit, crps: off the held-out rows); ``crps`` needs draws stored by st_summary_reserve / st_summary_accumulate."""
+        out = {k: np.zeros(self.n_all) for k in ("lppd", "p_waic", "mean_ll", "mu_mean", "pit")}
+        out["crps"] = np.zeros(self.n_all) if crps else None
+        cnt = C.c_int64()
+        self._check(self.lib.st_rows_score_get(self.h, _dp(out["lppd"]), _dp(out["p_waic"]), _dp(out["mean_ll"]), _dp(out["mu_mean"]),
+                                               _dp(out["pit"]), _dp(out["crps"]) if crps else None, C.byref(cnt)))
+        out["n_accumulated"] = int(cnt.value)
+        return out
+
+    def rows_score_totals(self, raw=False, have_crps=None):
+        """``rows_criteria`` of st_rows_score_totals' tables; ``raw``: (obs, held, n_obs, n_held) as the library returned them.
+        ``have_crps``: whether yhat draws are stored (st_summary_reserve / st_summary_accumulate), so that the held-out ``crps``
+        is a figure and not None; by default asked of the library (st_rows_score_get refuses ``crps`` without a stored draw)."""
+        obs = np.zeros((len(_lib.ST_ROWS_OBS), self.q), order="F")
+        held = np.zeros((len(_lib.ST_ROWS_HELD), self.q), order="F")
+        n_obs, n_held = np.zeros(self.q, dtype=np.int64), np.zeros(self.q, dtype=np.int64)
+        self._check(self.lib.st_rows_score_totals(self.h, _dp(obs), _dp(held), _ip(n_obs), _ip(n_held)))
+        if raw:
+            return obs, held, n_obs, n_held
+        if have_crps is None:
+            have_crps = self.lib.st_rows_score_get(self.h, None, None, None, None, None, _dp(np.zeros(self.n_all)), None) == 0
+        return rows_criteria(obs, held, n_obs, n_held, have_crps=bool(have_crps))
+
+    def rows_score_info(self):
+        by = C.c_double()
+        self._check(self.lib.st_rows_score_info(self.h, C.byref(by)))
+        return dict(alg_bytes=float(by.value))
 
     def points_info(self):
         """Of the last predict_points: dict(routes=[kernel names that ran], n_groups, alg_bytes, flops)."""
