@@ -138,6 +138,34 @@ int stm_mcmc_scored(const st_problem *pb, const st_options *opt, const double *s
                     double *new_w_mean, double *new_yhat_mean, double *new_w_q, double *new_yhat_q, int32_t *new_route,
                     double *new_cond_cov, double *new_cov, const stm_functionals *fun, const stm_scores *scores);
 
+/* Convergence diagnostics of the stored draws (include/spamtree_hip.h, st_*_diagnostics): ESS, MCSE, sd and split-R-hat per row,
+ * new point and functional.  stm_mcmc_diagnosed is stm_mcmc_scored plus one stm_diagnostics, every array of which is optional; n_new = 0
+ * with NULL coords_new, mv_new and anchor_new (and no other point argument) is the plain chain, spamtree_mv_mcmc_c.
+ * With want_rows the driver reserves mcmc_keep draws (st_summary_reserve) before the first iteration and calls
+ * st_summary_accumulate(seed, m) on every saved iteration -- stream 5 with the iteration's counter, the yhat st_yhat(seed, m)
+ * returns; with point or functional outputs it reserves mcmc_keep draws on the point set.  After the last iteration it calls
+ * st_summary_diagnostics / st_points_summary_diagnostics / st_points_functionals_diagnostics with max_lag.  It consumes no draw of
+ * streams 0-4, 6, 7 and changes no chain state: every output stm_mcmc_scored also produces is the same bit for bit.
+ * Refused before the first factorisation: any diagnostics output with mcmc_keep > 16384 (ST_ERR_UNSUPPORTED) or mcmc_keep <
+ * ST_DIAG_MIN_DRAWS, max_lag < 0, row outputs without want_rows, point or functional outputs without their set, yhat outputs
+ * without X_new (ST_ERR_USAGE). */
+typedef struct stm_diagnostics {
+  int32_t max_lag, want_rows;
+  st_series_diag rows_w, rows_yhat;   /* n_all each, model row order */
+  st_series_diag new_w, new_yhat;     /* n_new each, caller order */
+  st_series_diag fun_w, fun_yhat;     /* n_fun each */
+} stm_diagnostics;
+int stm_mcmc_diagnosed(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
+                       int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
+                       int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc, double *beta_mcmc,
+                       double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time, int64_t n_new,
+                       const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new, const double *X_new,
+                       const int64_t *joint_id_new, int64_t keep_draws, const double *quantiles, int32_t n_quantiles, double *new_w,
+                       double *new_cond_mean, double *new_cond_var, double *new_yhat, double *new_mean, double *new_var,
+                       double *new_w_mean, double *new_yhat_mean, double *new_w_q, double *new_yhat_q, int32_t *new_route,
+                       double *new_cond_cov, double *new_cov, const stm_functionals *fun, const stm_scores *scores,
+                       const stm_diagnostics *diag);
+
 /* Criteria over the fit's own rows (include/spamtree_hip.h, st_rows_score_*): WAIC and DIC over the observed rows and the scores
  * of held-out values at NA rows, conditional on w.  stm_rows_score_set: st_rows_score_set on the chain's handle; call it before the
  * first iteration.  stm_mcmc_criteria is spamtree_mv_mcmc_c plus one stm_criteria: on every saved iteration, once tausq and beta are

@@ -236,6 +236,40 @@ int st_summary_get(st_handle h, double *w_mean, double *yhat_mean, int64_t *n_ac
 int st_summary_reserve(st_handle h, int64_t keep);
 int st_summary_quantile(st_handle h, double q, double *w_q, double *yhat_q);
 
+/* ---- convergence diagnostics of the stored draws, on the device: per series x_0 .. x_{K-1} of K >= ST_DIAG_MIN_DRAWS stored draws
+ * (a row's w or yhat, a new point's w* or yhat*, a functional's F_w or F_y) the effective sample size, the Monte-Carlo standard
+ * error of the posterior mean, the posterior sd of the draws and the split-R-hat of the one chain.  The definition (the kernel,
+ * spamtree_amd.diagnostics.series_diagnostics and the tests' reference restate it):
+ *   moments     m = (1/K) sum x_s;  d_s = x_s - m;  gamma_t = (1/K) sum_{s=0}^{K-1-t} d_s d_{s+t};
+ *               sd = sqrt(K/(K-1) gamma_0);  rho_t = gamma_t / gamma_0
+ *   lag cap     L = min(max_lag, K - 2), max_lag = 0 meaning ST_DIAG_DEFAULT_MAX_LAG (a design constant that bounds the worst-case
+ *               cost per series, not a measurement);  k_max = (L - 1) / 2 (integer division)
+ *   tau         Geyer's initial positive sequence, made monotone: for k = 0 .. k_max, Gamma_k = rho_2k + rho_2k+1; stop at the
+ *               first k with !(Gamma_k > 0) (that Gamma_k is not added; a NaN stops too); otherwise Gamma_k <- min(Gamma_k,
+ *               Gamma_k-1);  tau = -1 + 2 sum Gamma_k, floored at 1 / log10(K) (which caps ess at K log10 K)
+ *   outputs     ess = K / tau;  mcse = sd / sqrt(ess);  lags = 2 x (number of pairs added).  A series is TRUNCATED when the loop
+ *               ends at k_max without meeting a non-positive pair, lags == 2 (k_max + 1): its ess is then an overestimate.
+ *               The monotone rule makes ess continuous in the data: a pair that changes sign in its last bit moves tau by no
+ *               more than the pairs behind it can add, each of them at most that bit.
+ *   split-R-hat h = K / 2 (integer division); halves x_0 .. x_{h-1} and x_{K-h} .. x_{K-1} (K odd: the middle draw is dropped);
+ *               half means m_1, m_2; half sample variances s_1^2, s_2^2 with divisor h - 1;  W = (s_1^2 + s_2^2) / 2;
+ *               B = h ((m_1 - mb)^2 + (m_2 - mb)^2), mb = (m_1 + m_2) / 2;  rhat = sqrt(((h-1)/h W + B/h) / W)
+ *   degenerate  gamma_0 == 0: ess = NaN, mcse = 0, sd = 0, rhat = NaN, lags = 0.  W == 0 with gamma_0 > 0: rhat = NaN only.
+ * One pass over a store gives all five outputs of its series; every sum is taken in an order that depends on K, max_lag and the
+ * lane geometry only (spamtree_amd/csrc/diag_kernels.hpp), so the outputs of a series are bitwise a function of its K values and
+ * max_lag, wherever it is stored.  Each call works on the draws stored so far, changes no state and consumes no Philox draw.
+ * st_summary_diagnostics: the stores of st_summary_reserve; n_all values per array, model row order; limited_tree handles included.
+ * st_points_summary_diagnostics: the point set's stores; n_new values, caller order; st_points_summary_quantile's refusals.
+ * st_points_functionals_diagnostics: the functionals' stores; n_fun values; st_points_functionals_quantile's refusals.
+ * Either struct, and any pointer in it, may be NULL.  ST_ERR_USAGE with a text: fewer than ST_DIAG_MIN_DRAWS stored draws (no
+ * reservation included), max_lag < 0, a yhat request on a point set without X.  A point or functional set of size 0: ST_OK. */
+#define ST_DIAG_MIN_DRAWS 4
+#define ST_DIAG_DEFAULT_MAX_LAG 1024
+typedef struct st_series_diag { double *ess, *mcse, *sd, *rhat; int32_t *lags; } st_series_diag;   /* any pointer may be NULL */
+int st_summary_diagnostics(st_handle h, int32_t max_lag, const st_series_diag *w, const st_series_diag *yhat);
+int st_points_summary_diagnostics(st_handle h, int32_t max_lag, const st_series_diag *w, const st_series_diag *yhat);
+int st_points_functionals_diagnostics(st_handle h, int32_t max_lag, const st_series_diag *w, const st_series_diag *yhat);
+
 /* ---- new-point prediction from a fitted state: the predictive at locations that are not rows of the problem, the way the model
  * treats an NA row (make_tree's missing level, predict_std spamtree_model.cpp:1234-1358) without rebuilding the tree.
  * A point of margin j anchored at block b (the block of its nearest deepest-knot-level row, same margin if cherrypick_same_margin,

@@ -25,8 +25,16 @@ class StOptions(C.Structure):
                 ("force_generic", C.c_int32), ("reserved", C.c_int32)]
 
 
+class StSeriesDiag(C.Structure):   # include/spamtree_hip.h, st_series_diag: n values each, any may be NULL
+    _fields_ = [("ess", c_dp), ("mcse", c_dp), ("sd", c_dp), ("rhat", c_dp), ("lags", C.POINTER(C.c_int32))]
+
+
+ST_DIAG_MIN_DRAWS = 4
+ST_DIAG_DEFAULT_MAX_LAG = 1024
+
 # every symbol include/spamtree_hip.h declares: name -> (restype, argtypes)
 H = C.c_void_p
+c_sdp = C.POINTER(StSeriesDiag)
 SIGNATURES = {
     "st_create": (C.c_int, [C.POINTER(StProblem), C.POINTER(StOptions), C.POINTER(H)]),
     "st_destroy": (C.c_int, [H]),
@@ -93,6 +101,9 @@ SIGNATURES = {
     "st_summary_get": (C.c_int, [H, c_dp, c_dp, c_ip]),
     "st_summary_reserve": (C.c_int, [H, C.c_int64]),
     "st_summary_quantile": (C.c_int, [H, C.c_double, c_dp, c_dp]),
+    "st_summary_diagnostics": (C.c_int, [H, C.c_int32, c_sdp, c_sdp]),
+    "st_points_summary_diagnostics": (C.c_int, [H, C.c_int32, c_sdp, c_sdp]),
+    "st_points_functionals_diagnostics": (C.c_int, [H, C.c_int32, c_sdp, c_sdp]),
     "st_comm_unique_id": (C.c_int, [C.c_void_p, C.c_int32]),
     "st_comm_init": (C.c_int, [H, C.c_void_p]),
     "st_points_set": (C.c_int, [H, C.c_int64, c_dp, c_ip, c_ip, c_dp]),
@@ -186,6 +197,15 @@ SIGNATURES.update({
     "stm_points_score_set": (C.c_int, [H, c_dp]),
 })
 SIGNATURES["stm_mcmc_scored"] = (C.c_int, SIGNATURES["stm_mcmc_functionals"][1] + [C.POINTER(StmScores)])
+
+
+
+class StmDiagnostics(C.Structure):   # include/spamtree_fit.h, stm_diagnostics
+    _fields_ = [("max_lag", C.c_int32), ("want_rows", C.c_int32), ("rows_w", StSeriesDiag), ("rows_yhat", StSeriesDiag),
+                ("new_w", StSeriesDiag), ("new_yhat", StSeriesDiag), ("fun_w", StSeriesDiag), ("fun_yhat", StSeriesDiag)]
+
+
+SIGNATURES["stm_mcmc_diagnosed"] = (C.c_int, SIGNATURES["stm_mcmc_scored"][1] + [C.POINTER(StmDiagnostics)])
 
 SIGNATURES["stm_rows_score_set"] = (C.c_int, [H, c_dp])
 SIGNATURES["stm_mcmc_criteria"] = (C.c_int, SIGNATURES["spamtree_mv_mcmc_c"][1] + [C.POINTER(StmCriteria)])

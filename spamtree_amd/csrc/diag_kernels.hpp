@@ -1,0 +1,51 @@
+// Convergence diagnostics of the stored draws (st_summary_diagnostics, st_points_summary_diagnostics,
+// st_points_functionals_diagnostics; the kernel and its launcher live in k_diag.hip): per series of K stored draws the effective
+// sample size, the Monte-Carlo standard error of the mean, the posterior sd of the draws and the split-R-hat of the one chain.
+// include/spamtree_hip.h has the definition; this header restates it in the order the kernel evaluates it.
+//
+// A store is draws[d * n + i], d < K <= 16384, i < n.  A workgroup stages the K draws of R consecutive series into LDS, transposed
+// (series r at lds + r Kp; Kp = K | 1 when R > 1, so that the R values of one draw land on different banks), and wave w takes the
+// series w, w + nw, ... of the tile, one at a time.  Every sum below is taken the same way: lane l adds the terms s = l, l + 64,
+// l + 128, ... in ascending order into one accumulator (products by fma), then the 64 accumulators are added by the xor butterfly
+// with partners 8, 4, 2, 1 (DPP moves inside a row of 16 lanes), then 16 and 32 -- the order depends on K and the term's index only, not on n, R, the series' place in the
+// store or the workgroup, so the outputs of a series are bitwise a function of its K values and max_lag.  In order:
+//   P1  a = sum x_s;  m0 = a / K
+//   P2  c = sum (x_s - m0);  m = m0 + c / K               (the mean to the rounding of the data's spread, not of its offset:
+//                                                           a constant series gets m = x_0 and d = 0 exactly)
+//   P3  d_s = x_s - m, in place;  g0 = sum d_s^2;  b1 = sum_{s < h} d_s;  b2 = sum_{s >= K - h} d_s;  h = K / 2
+//       mu1 = b1 / h, mu2 = b2 / h                         (the half means less m)
+//   P4  v1 = sum_{s < h} (d_s - mu1)^2;  v2 = sum_{s >= K - h} (d_s - mu2)^2
+//       sd = sqrt(g0 / (K - 1));  W = (v1 / (h - 1) + v2 / (h - 1)) / 2;  mb = (mu1 + mu2) / 2;
+//       B = h ((mu1 - mb)^2 + (mu2 - mb)^2);  rhat = sqrt(((h - 1) / h W + B / h) / W)
+//   lags, DIAG_NL = 4 at a time (two pairs per pass over d):  a_t = sum_{s < K - t} d_s d_{s + t},  rho_t = a_t / g0
+//       (a_0 is g0's own chain: rho_0 = 1 exactly);  pair k: G = rho_2k + rho_2k+1;  stop at !(G > 0);  G = min(G, G_prev);
+//       tsum += G, in pair order.  A pass is made only while no pair has stopped.
+//   tau = max(-1 + 2 tsum, 1 / log10 K);  ess = K / tau;  mcse = sd / sqrt(ess);  lags = 2 pairs.
+// g0 == 0: ess = NaN, mcse = 0, sd = 0, rhat = NaN, lags = 0.  W == 0: rhat = NaN.
+// LDS: unit stride across lanes in every pass (d[s] and d[s + t] alike): no bank conflict.  No atomics, no scratch.
+#pragma once
+#include "st_device.hpp"
+
+#define DIAG_NL 4              // lags per pass over the centred series
+#define DIAG_MAX_R 8           // series per workgroup at most
+#define DIAG_NT 512            // one wave per series of the tile: 64 min(R, 8) threads
+#define DIAG_TILE (64 * 1024)  // the tile a workgroup aims for (two workgroups per CU); a longer series takes what the device allows
+
+struct DiagArgs {
+  const double *draws;   // [K][n]
+  long long n;
+  int K, Kp, R;
+  int L;                 // min(max_lag, K - 2), max_lag = 0 resolved
+  double *ess, *mcse, *sd, *rhat;   // n each (device), store order
+  int *lags;
+};
+
+// R and Kp of a store of K draws under a per-workgroup LDS limit; false: one series does not fit
+bool series_diag_plan(long long K, size_t lds_limit, int *R, int *Kp);
+int series_diag_launch(const DiagArgs &A, size_t lds_limit, hipStream_t st);
+
+// The one launcher of the three C-ABI calls: diagnostics of the first K rows of the store draws[K][n] into out's host arrays (any
+// may be NULL), element i of the store at out[perm ? perm[i] : i].  The caller has checked K and max_lag.
+struct st_handle_s;
+int series_diag_store(st_handle_s *h, const char *who, const double *draws, long long n, long long K, int32_t max_lag,
+                      const long long *perm, const st_series_diag *out);

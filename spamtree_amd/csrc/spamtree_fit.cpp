@@ -448,10 +448,11 @@ struct FitPoints {   // the point set of stm_mcmc_points and where its per-draw 
 // point set once tausq and beta are drawn: the saved theta's factor in slot 0, the saved w, beta and tausq; draw counter = saved
 // index, Philox streams 6 / 7 only, so the chain itself is the same draw for draw.  With crit, every saved iteration also updates
 // the criteria over the fit's own rows (st_rows_score_accumulate) and, when their CRPS is wanted, stores the iteration's yhat on
-// the device (st_summary_accumulate: stream 5 with the iteration's counter, what st_yhat draws).
+// the device (st_summary_accumulate: stream 5 with the iteration's counter, what st_yhat draws).  With store_rows every saved
+// iteration makes that st_summary_accumulate call (the caller has reserved the room): the stores the diagnostics read.
 static int run_fit(stm_chain c, int mcmc_keep, int mcmc_burn, int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc,
                    double *yhat_mcmc, double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
-                   const FitPoints *pts, const stm_criteria *crit = nullptr) {
+                   const FitPoints *pts, const stm_criteria *crit = nullptr, bool store_rows = false) {
   int rc = 0;
   const int sample_predicts = flags ? flags->sample_predicts : 1;
   const auto t0 = std::chrono::steady_clock::now();
@@ -501,6 +502,10 @@ static int run_fit(stm_chain c, int mcmc_keep, int mcmc_burn, int mcmc_thin, uin
       if (!rc && crit) {
         rc = st_rows_score_accumulate(c->h);
         if (!rc && crit->want_crps && crit->y_holdout) rc = st_summary_accumulate(c->h, seed, (uint32_t)m);
+        if (rc) c->err = st_last_error(c->h);
+      }
+      if (!rc && store_rows) {   // the diagnostics' draws of w and yhat (stream 5, the iteration's counter: st_yhat's yhat)
+        rc = st_summary_accumulate(c->h, seed, (uint32_t)m);
         if (rc) c->err = st_last_error(c->h);
       }
       ++msaved;
@@ -574,8 +579,10 @@ extern "C" int stm_mcmc_functionals(const st_problem *pb, const st_options *opt,
                          new_w_mean, new_yhat_mean, new_w_q, new_yhat_q, new_route, new_cond_cov, new_cov, fun, nullptr);
 }
 
-// fun NULL: stm_mcmc_points_joint itself; scores NULL: stm_mcmc_functionals itself
-extern "C" int stm_mcmc_scored(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
+static bool diag_any(const st_series_diag &d) { return d.ess || d.mcse || d.sd || d.rhat || d.lags; }
+
+// fun NULL: stm_mcmc_points_joint itself; scores NULL: stm_mcmc_functionals itself; diag NULL: stm_mcmc_scored itself
+extern "C" int stm_mcmc_diagnosed(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
                                     int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
                                     int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
                                     double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
@@ -584,8 +591,23 @@ extern "C" int stm_mcmc_scored(const st_problem *pb, const st_options *opt, cons
                                     int32_t n_quantiles, double *new_w, double *new_cond_mean, double *new_cond_var, double *new_yhat,
                                     double *new_mean, double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q,
                                     double *new_yhat_q, int32_t *new_route, double *new_cond_cov, double *new_cov,
-                                    const stm_functionals *fun, const stm_scores *scores) {
+                                    const stm_functionals *fun, const stm_scores *scores, const stm_diagnostics *diag) {
   if (fun && fun->n_fun <= 0) fun = nullptr;
+  const bool plain = diag && n_new == 0 && !coords_new && !mv_new && !anchor_new;   // the plain chain (with diag only: stm_mcmc_scored handles an empty set as before)
+  const bool d_rows = diag && diag->want_rows && (diag_any(diag->rows_w) || diag_any(diag->rows_yhat));
+  const bool d_new = diag && !plain && (diag_any(diag->new_w) || diag_any(diag->new_yhat));
+  const bool d_fun = diag && fun && (diag_any(diag->fun_w) || diag_any(diag->fun_yhat));
+  if (diag && diag->max_lag < 0) return ST_ERR_USAGE;
+  if (diag && ((diag_any(diag->rows_w) || diag_any(diag->rows_yhat)) && !diag->want_rows)) return ST_ERR_USAGE;
+  if (diag && plain && (diag_any(diag->new_w) || diag_any(diag->new_yhat))) return ST_ERR_USAGE;
+  if (diag && !fun && (diag_any(diag->fun_w) || diag_any(diag->fun_yhat))) return ST_ERR_USAGE;
+  if ((d_new && diag_any(diag->new_yhat) && !X_new) || (d_fun && diag_any(diag->fun_yhat) && !X_new)) return ST_ERR_USAGE;
+  if (d_rows || d_new || d_fun) {
+    if (mcmc_keep > 16384) return ST_ERR_UNSUPPORTED;   // the stores' limit
+    if (mcmc_keep < ST_DIAG_MIN_DRAWS) return ST_ERR_USAGE;
+    if (d_new || d_fun) keep_draws = std::max<int64_t>(keep_draws, mcmc_keep);
+  }
+  if (plain && (fun || (scores && scores->y_new) || joint_id_new || X_new || n_quantiles != 0)) return ST_ERR_USAGE;
   if (scores && !scores->y_new) scores = nullptr;
   if (scores && (!X_new || (scores->lpd_joint && !joint_id_new) || (scores->crps && keep_draws < 1))) return ST_ERR_USAGE;
   if (fun && (fun->fun_yhat || fun->fun_yhat_mean || fun->fun_yhat_q) && !X_new) return ST_ERR_USAGE;
@@ -595,7 +617,11 @@ extern "C" int stm_mcmc_scored(const st_problem *pb, const st_options *opt, cons
   if ((new_yhat || new_yhat_mean || new_yhat_q) && !X_new) return ST_ERR_USAGE;
   stm_chain c = nullptr;
   int rc = stm_create(pb, opt, set_unif_bounds, mcmcsd, theta, ntheta, beta, tausq, seed, flags, &c);
-  if (rc == 0) rc = stm_points_set_joint(c, n_new, coords_new, mv_new, anchor_new, X_new, joint_id_new, keep_draws);   // refusals: before any factorisation
+  if (rc == 0 && !plain) rc = stm_points_set_joint(c, n_new, coords_new, mv_new, anchor_new, X_new, joint_id_new, keep_draws);   // refusals: before any factorisation
+  if (rc == 0 && d_rows) {
+    rc = st_summary_reset(c->h);
+    if (rc == 0) rc = st_summary_reserve(c->h, mcmc_keep);
+  }
   int64_t nj = 0;
   std::vector<int64_t> joff, jptr, jmem;
   std::vector<double> cov_scratch;
@@ -612,7 +638,12 @@ extern "C" int stm_mcmc_scored(const st_problem *pb, const st_options *opt, cons
   double *const ccov = !joint_id_new ? nullptr : (new_cond_cov ? new_cond_cov : (cov_scratch.empty() ? nullptr : cov_scratch.data()));
   const FitPoints pts{n_new, new_w, new_cond_mean, new_cond_var, new_yhat, ccov, joint_id_new ? joff[nj] : 0, fun};
   rc = run_fit(c, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc, yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time,
-               &pts);
+               plain ? nullptr : &pts, nullptr, d_rows);
+  if (plain) {   // the diagnostics of the rows are all a plain chain can ask for
+    if (rc == 0 && d_rows) rc = st_summary_diagnostics(c->h, diag->max_lag, &diag->rows_w, &diag->rows_yhat);
+    stm_destroy(c);
+    return rc;
+  }
   if (rc == 0 && ccov && new_cond_var)
     for (int s = 0; s < mcmc_keep; ++s)
       for (int64_t k = 0; k < nj; ++k) {
@@ -634,8 +665,29 @@ extern "C" int stm_mcmc_scored(const st_problem *pb, const st_options *opt, cons
                                         fun->fun_yhat_q ? fun->fun_yhat_q + (size_t)i * fun->n_fun : nullptr);
   if (rc == 0 && scores && mcmc_keep > 0)
     rc = st_points_score_get(c->h, scores->lpd, scores->pit, scores->crps, scores->lpd_joint, scores->n_scored, scores->n_degenerate);
+  if (rc == 0 && d_rows) rc = st_summary_diagnostics(c->h, diag->max_lag, &diag->rows_w, &diag->rows_yhat);
+  if (rc == 0 && d_new)
+    rc = st_points_summary_diagnostics(c->h, diag->max_lag, &diag->new_w, diag_any(diag->new_yhat) ? &diag->new_yhat : nullptr);
+  if (rc == 0 && d_fun)
+    rc = st_points_functionals_diagnostics(c->h, diag->max_lag, &diag->fun_w, diag_any(diag->fun_yhat) ? &diag->fun_yhat : nullptr);
   stm_destroy(c);
   return rc;
+}
+
+extern "C" int stm_mcmc_scored(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
+                                    int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
+                                    int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
+                                    double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
+                                    int64_t n_new, const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new,
+                                    const double *X_new, const int64_t *joint_id_new, int64_t keep_draws, const double *quantiles,
+                                    int32_t n_quantiles, double *new_w, double *new_cond_mean, double *new_cond_var, double *new_yhat,
+                                    double *new_mean, double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q,
+                                    double *new_yhat_q, int32_t *new_route, double *new_cond_cov, double *new_cov,
+                                    const stm_functionals *fun, const stm_scores *scores) {
+  return stm_mcmc_diagnosed(pb, opt, set_unif_bounds, theta, ntheta, beta, tausq, mcmcsd, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc,
+                            yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time, n_new, coords_new, mv_new, anchor_new, X_new,
+                            joint_id_new, keep_draws, quantiles, n_quantiles, new_w, new_cond_mean, new_cond_var, new_yhat, new_mean, new_var,
+                            new_w_mean, new_yhat_mean, new_w_q, new_yhat_q, new_route, new_cond_cov, new_cov, fun, scores, nullptr);
 }
 
 // spamtree_mv_mcmc_c plus the criteria over the fit's own rows; criteria NULL: spamtree_mv_mcmc_c itself

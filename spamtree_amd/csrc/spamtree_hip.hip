@@ -26,6 +26,7 @@
 
 #include "st_handle.hpp"
 #include "misc_kernels.hpp"
+#include "diag_kernels.hpp"
 #include "rows_score.hpp"
 #include <new>
 
@@ -1621,6 +1622,18 @@ extern "C" int st_summary_quantile(st_handle h, double q, double *w_q, double *y
     if (rc) return rc;
   }
   return ST_OK;
+}
+// ESS, MCSE, sd and split-R-hat of every row's stored draws (diag_kernels.hpp): k_series_diag over each requested store
+extern "C" int st_summary_diagnostics(st_handle h, int32_t max_lag, const st_series_diag *w, const st_series_diag *yhat) {
+  if (!h) return ST_ERR_USAGE;
+  if (max_lag < 0) { h->err = "st_summary_diagnostics: max_lag must not be negative (0: the default cap)"; return ST_ERR_USAGE; }
+  if (h->n_draws < ST_DIAG_MIN_DRAWS) {
+    h->err = "st_summary_diagnostics: " + std::to_string(h->n_draws) + " draws stored, the diagnostics need at least " +
+             std::to_string(ST_DIAG_MIN_DRAWS) + " (call st_summary_reserve before the saved iterations)";
+    return ST_ERR_USAGE;
+  }
+  if (const int rc = series_diag_store(h, "st_summary_diagnostics", h->d_draws_w.p, h->n_all, h->n_draws, max_lag, h->dev2model.data(), w)) return rc;
+  return series_diag_store(h, "st_summary_diagnostics", h->d_draws_yhat.p, h->n_all, h->n_draws, max_lag, h->dev2model.data(), yhat);
 }
 extern "C" int st_summary_get(st_handle h, double *w_mean, double *yhat_mean, int64_t *n_accumulated) {
   if (!h) return ST_ERR_USAGE;

@@ -8,6 +8,7 @@
 
 #include "st_handle.hpp"
 #include "misc_kernels.hpp"
+#include "diag_kernels.hpp"
 #include "points_layout.hpp"
 #include "points_score.hpp"
 
@@ -531,6 +532,22 @@ extern "C" int st_points_summary_quantile(st_handle h, double q, double *w_q, do
   return points_qtile(h, draws, ps->n, ps->n_kept, q, ps->d_out.p, dst);   // d_out as scratch: the next st_points_accumulate rewrites it anyway
 }
 
+extern "C" int st_points_summary_diagnostics(st_handle h, int32_t max_lag, const st_series_diag *w, const st_series_diag *yhat) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_summary_diagnostics")) return rc;
+  if (max_lag < 0) { h->err = "st_points_summary_diagnostics: max_lag must not be negative (0: the default cap)"; return ST_ERR_USAGE; }
+  PointSet *ps = h->pts;
+  if (ps->n == 0) return ST_OK;
+  if (ps->n_kept < ST_DIAG_MIN_DRAWS) {
+    h->err = "st_points_summary_diagnostics: " + std::to_string(ps->n_kept) + " draws stored, the diagnostics need at least " +
+             std::to_string(ST_DIAG_MIN_DRAWS) + " (call st_points_summary_reserve before the saved iterations)";
+    return ST_ERR_USAGE;
+  }
+  if (yhat && !ps->has_X) { h->err = "st_points_summary_diagnostics: yhat needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  if (const int rc = series_diag_store(h, "st_points_summary_diagnostics", ps->d_keep_w.p, ps->n, ps->n_kept, max_lag, nullptr, w)) return rc;
+  return series_diag_store(h, "st_points_summary_diagnostics", ps->d_keep_yhat.p, ps->n, ps->n_kept, max_lag, nullptr, yhat);
+}
+
 // ---- linear functionals of the predictions (points_fun.hpp): the term lists come from functionals_layout, without a device call
 extern "C" int st_points_functionals_set(st_handle h, int64_t n_fun, const int64_t *ptr, const int64_t *idx, const double *wt) {
   if (!h) return ST_ERR_USAGE;
@@ -627,6 +644,23 @@ extern "C" int st_points_functionals_quantile(st_handle h, double q, double *w_q
   double *const dst[2] = {w_q, yhat_q};
   const double *const draws[2] = {fs->d_keep_w.p, fs->d_keep_yhat.p};
   return points_qtile(h, draws, fs->n_fun, fs->n_kept, q, fs->d_q.p, dst);
+}
+
+extern "C" int st_points_functionals_diagnostics(st_handle h, int32_t max_lag, const st_series_diag *w, const st_series_diag *yhat) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = fun_refuse(h, "st_points_functionals_diagnostics", false)) return rc;
+  if (max_lag < 0) { h->err = "st_points_functionals_diagnostics: max_lag must not be negative (0: the default cap)"; return ST_ERR_USAGE; }
+  const PointSet *ps = h->pts;
+  FunSet *fs = ps->fun.get();
+  if (fs->n_fun == 0 || ps->n == 0) return ST_OK;   // (the functionals of an empty point set store no draw)
+  if (fs->n_kept < ST_DIAG_MIN_DRAWS) {
+    h->err = "st_points_functionals_diagnostics: " + std::to_string(fs->n_kept) + " draws stored, the diagnostics need at least " +
+             std::to_string(ST_DIAG_MIN_DRAWS) + " (call st_points_summary_reserve before the saved iterations)";
+    return ST_ERR_USAGE;
+  }
+  if (yhat && !ps->has_X) { h->err = "st_points_functionals_diagnostics: yhat needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  if (const int rc = series_diag_store(h, "st_points_functionals_diagnostics", fs->d_keep_w.p, fs->n_fun, fs->n_kept, max_lag, nullptr, w)) return rc;
+  return series_diag_store(h, "st_points_functionals_diagnostics", fs->d_keep_yhat.p, fs->n_fun, fs->n_kept, max_lag, nullptr, yhat);
 }
 
 // ---- scores of held-out observations at the point set (points_score.hpp)

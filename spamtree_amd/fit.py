@@ -8,7 +8,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .model import SpamTreeError, _dp, _f64, _i64, _ip, _lists_to_csr, functionals_csr, joint_labels, rows_criteria, rows_holdout, score_totals, score_values
+from . import diagnostics as _diag
+from .model import (SpamTreeError, _dp, _f64, _i64, _ip, _lists_to_csr, functionals_csr, joint_labels, rows_criteria, rows_holdout, score_totals,
+                    score_values, series_diag_buffers, series_diag_finish)
 
 
 def _problem(y, X, coords, mv_id, res_is_ref, parents, children, block_names, block_groups, indexing):
@@ -239,7 +241,7 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                      main_verbose=True, verbose=False, debug=False, printall=False, sample_beta=True, sample_tausq=True,
                      sample_theta=True, sample_w=True, sample_predicts=True, seed=2021, device=0, reference_quirks=True,
                      new_points=None, new_draws=True, new_quantiles=(), save_w=True, save_yhat=True, force_generic=False,
-                     criteria=False, y_holdout=None, holdout_crps=True):
+                     criteria=False, y_holdout=None, holdout_crps=True, diagnostics=False, diagnostics_max_lag=0):
     """spamtree_fit.cpp:5-430 through the C++ driver.  `num_threads`, `use_alg`, the verbosity flags and `start_w` are
     accepted and ignored exactly where the reference ignores them (start_w, :95) or where they do not apply to a GPU.
 
@@ -275,8 +277,28 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     CRPS makes the device keep ``mcmc_keep`` draws of w and yhat per row (at most 16384, more is a ValueError);
     ``holdout_crps=False`` scores without it.  Not together with ``new_points``.  As with ``new_points``, a failure of the
     chain (a refusal of the library, a Cholesky failure code) raises SpamTreeError with ``code`` set, where the plain call prints
-    "MCMC has been interrupted." and returns ``{"None": ...}``; a NaN log-density is a FloatingPointError in both."""
+    "MCMC has been interrupted." and returns ``{"None": ...}``; a NaN log-density is a FloatingPointError in both.
+    ``diagnostics=True``: the effective sample size ``ess``, the Monte-Carlo standard error of the posterior mean ``mcse``, the
+    posterior sd of the draws ``sd``, the split-R-hat of the one chain ``rhat``, the lags used ``lags`` and whether the lag cap was
+    hit ``truncated`` (``spamtree_amd.diagnostics`` has the definition; ``diagnostics_max_lag`` = 0 is its default cap of 1024
+    lags).  The result then holds ``diagnostics``: ``theta`` (k), ``beta`` (p x q) and ``tausq`` (q) from the saved scalar chains
+    on the host; ``w`` and ``yhat`` per row of the problem from the device, which keeps ``mcmc_keep`` draws of both per row for it
+    (stm_mcmc_diagnosed: the chain is the same bit for bit; nothing per draw comes to the host, so it works with ``save_w=False,
+    save_yhat=False, new_draws=False``); and ``summary``: ``diagnostics.summarise`` of each part, w and yhat also by outcome.  With
+    ``new_points`` also ``new["diagnostics"]`` (w, yhat per point) and ``new["functionals"]["diagnostics"]``.  ``mcmc_keep`` must lie
+    in 4 .. 16384 (ValueError); not together with ``criteria`` / ``y_holdout`` (one driver per call).  A failure of the chain raises
+    SpamTreeError, as with ``new_points``."""
     crit = bool(criteria) or y_holdout is not None
+    diagnostics = bool(diagnostics)
+    if diagnostics:
+        if crit:
+            raise ValueError("diagnostics and criteria / y_holdout are separate drivers (stm_mcmc_diagnosed, stm_mcmc_criteria): one per call")
+        if not _diag.MIN_DRAWS <= int(mcmc_keep) <= _diag.MAX_DRAWS:
+            raise ValueError(f"diagnostics: mcmc_keep = {int(mcmc_keep)} must lie in {_diag.MIN_DRAWS} .. {_diag.MAX_DRAWS} "
+                             "(the series' length, and the draws the device keeps per row)")
+        if int(diagnostics_max_lag) < 0:
+            raise ValueError("diagnostics_max_lag must not be negative (0: the default cap)")
+    max_lag = int(diagnostics_max_lag)
     if crit:
         if new_points is not None:
             raise ValueError("criteria and new_points are separate drivers (stm_mcmc_criteria, stm_mcmc_scored): one per call")
@@ -313,6 +335,12 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
               _dp(theta_mcmc), _dp(paramsd), C.byref(t))
     new = None
     crit_out = None
+    diag_rows = ds = None
+    if diagnostics:       # stm_mcmc_diagnosed: the rows' outputs here, the points' and functionals' below
+        dw, sw = series_diag_buffers(n)
+        dy, sy = series_diag_buffers(n)
+        diag_rows = dict(w=dw, yhat=dy)
+        ds = _lib.StmDiagnostics(max_lag, 1, sw, sy)
     if crit:
         rows = {key: np.zeros(n) for key in ("lppd", "p_waic", "mean_ll", "mu_mean", "pit")}
         rows["crps"] = np.zeros(n) if (want_crps and mcmc_keep > 0) else None
@@ -327,6 +355,12 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                             totals=rows_criteria(tobs, theld, n_obs, n_held, have_crps=rows["crps"] is not None))
         elif rc not in (0, -10):
             err = SpamTreeError(f"stm_mcmc_criteria failed ({rc})")
+            err.code = rc
+            raise err
+    elif new_points is None and diagnostics:   # the plain chain through the diagnosed driver: no point argument
+        rc = lib.stm_mcmc_diagnosed(*common, 0, None, None, None, None, None, 0, None, 0, *([None] * 15), C.byref(ds))
+        if rc not in (0, -10):
+            err = SpamTreeError(f"stm_mcmc_diagnosed failed ({rc})")
             err.code = rc
             raise err
     elif new_points is None:
@@ -362,12 +396,29 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                                      dp(fdraws["cond_var"]), dp(fdraws["yhat"]), dp(fsumm["mean"]), dp(fsumm["var"]), dp(fsumm["w_mean"]),
                                      dp(fsumm["yhat_mean"]), dp(fwq if qs.size else None), dp(fyq if qs.size else None))
             fsp = C.byref(fs)
+        ss = None
         if ynew is not None:      # stm_mcmc_scored: the same call plus the scores; crps from the draws the device keeps
             sc = dict(lpd=np.zeros(n_new), pit=np.zeros(n_new), crps=np.zeros(n_new) if (want_crps and mcmc_keep > 0) else None,
                       lpd_joint=np.zeros(len(groups)) if labels is not None else None)
             nsc, ndg = C.c_int64(), C.c_int64()
             ss = _lib.StmScores(_dp(ynew), dp(sc["lpd"]), dp(sc["pit"]), dp(sc["crps"]), dp(sc["lpd_joint"]),
                                 C.pointer(nsc), C.pointer(ndg))
+        diag_new = diag_fun = None
+        if diagnostics:           # stm_mcmc_diagnosed: the same call plus the diagnostics of the rows, points and functionals
+            dnw, ds.new_w = series_diag_buffers(n_new)
+            dny, s_ny = series_diag_buffers(n_new, pX is not None)
+            if s_ny is not None:
+                ds.new_yhat = s_ny
+            diag_new = dict(w=dnw, yhat=dny)
+            if fun is not None:
+                dfw, ds.fun_w = series_diag_buffers(nf)
+                dfy, s_fy = series_diag_buffers(nf, pX is not None)
+                if s_fy is not None:
+                    ds.fun_yhat = s_fy
+                diag_fun = dict(w=dfw, yhat=dfy)
+            rc = lib.stm_mcmc_diagnosed(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), _ip(labels) if labels is not None else None,
+                                        *tail, dp(ccov), dp(cov), fsp, C.byref(ss) if ss is not None else None, C.byref(ds))
+        elif ynew is not None:
             rc = lib.stm_mcmc_scored(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), _ip(labels) if labels is not None else None,
                                      *tail, dp(ccov), dp(cov), fsp, C.byref(ss))
         elif fun is not None:
@@ -402,6 +453,10 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                 lo_hi = (yq[:, int(np.argmin(qs))], yq[:, int(np.argmax(qs))]) if qs.size >= 2 else (None, None)
                 sc["totals"] = score_totals(sc, ynew, pmv, q, *lo_hi)
                 new["scores"] = sc
+            if diag_new is not None and n_new > 0:
+                new["diagnostics"] = {key: series_diag_finish(v, mcmc_keep, max_lag) for key, v in diag_new.items()}
+            if diag_fun is not None and n_new > 0:
+                new["functionals"]["diagnostics"] = {key: series_diag_finish(v, mcmc_keep, max_lag) for key, v in diag_fun.items()}
     if rc == -10:
         raise FloatingPointError("At nan loglik: error.")
     if rc != 0 and new_points is not None:
@@ -422,4 +477,12 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
         out["new"] = new
     if crit_out is not None:
         out["criteria"] = crit_out
+    if diagnostics:
+        d = dict(theta=_diag.chains_diagnostics(theta_mcmc, max_lag),
+                 beta=_diag.chains_diagnostics(np.transpose(beta_mcmc, (0, 2, 1)), max_lag),
+                 tausq=_diag.chains_diagnostics(tausq_mcmc, max_lag),
+                 w=series_diag_finish(diag_rows["w"], mcmc_keep, max_lag), yhat=series_diag_finish(diag_rows["yhat"], mcmc_keep, max_lag))
+        mv_rows = _i64(mv_id).reshape(-1)
+        d["summary"] = {key: _diag.summarise(d[key], mv_rows if key in ("w", "yhat") else None) for key in ("theta", "beta", "tausq", "w", "yhat")}
+        out["diagnostics"] = d
     return out

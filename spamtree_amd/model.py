@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import diagnostics as _diag
 
 
 def _f64(a):
@@ -39,6 +40,23 @@ def _lists_to_csr(lists):
 
 class SpamTreeError(RuntimeError):
     pass
+
+
+def series_diag_buffers(n, want=True):
+    """(dict of n-vectors ess, mcse, sd, rhat, lags; the st_series_diag pointing at them), or (None, None) without ``want``."""
+    if not want:
+        return None, None
+    d = {k: np.zeros(n) for k in ("ess", "mcse", "sd", "rhat")}
+    d["lags"] = np.zeros(n, dtype=np.int32)
+    s = _lib.StSeriesDiag(_dp(d["ess"]), _dp(d["mcse"]), _dp(d["sd"]), _dp(d["rhat"]), d["lags"].ctypes.data_as(C.POINTER(C.c_int32)))
+    return d, s
+
+
+def series_diag_finish(d, K, max_lag=0):
+    """Adds ``truncated`` (the series that ran into the lag cap) to a dict of device diagnostics of K stored draws."""
+    if d is not None:
+        d["truncated"] = _diag.truncated(d["lags"], K, max_lag)
+    return d
 
 
 POINTS_MAX_JOINT = 16   # include/spamtree_hip.h: ST_POINTS_MAX_JOINT
@@ -664,6 +682,31 @@ class SpamTreeMV:
         out.update(n_scored=int(ns.value), n_degenerate=int(nd.value))
         out["totals"] = score_totals(out, self.score_y, self.points_mv, self.q, yhat_lo, yhat_hi)
         return out
+
+    # ---- convergence diagnostics of the stored draws (st_*_diagnostics; spamtree_amd.diagnostics has the definition)
+    def _diagnostics(self, call, n, max_lag, yhat, n_kept):
+        dw, sw = series_diag_buffers(n)
+        dy, sy = series_diag_buffers(n, yhat)
+        self._check(call(self.h, int(max_lag), C.byref(sw), C.byref(sy) if sy is not None else None))
+        if n_kept is not None:   # the number of stored draws tells which series ran into the lag cap
+            series_diag_finish(dw, n_kept, max_lag)
+            series_diag_finish(dy, n_kept, max_lag)
+        return dict(w=dw, yhat=dy)
+
+    def summary_diagnostics(self, max_lag=0, n_kept=None):
+        """ESS, MCSE, sd, split-R-hat and lags of every row's stored w and yhat draws (st_summary_reserve before the saved
+        iterations): dict(w=dict(ess, mcse, sd, rhat, lags), yhat=the same), n_all values each in model row order.  With
+        ``n_kept``, the number of stored draws, each also holds ``truncated``: the series that ran into the lag cap."""
+        return self._diagnostics(self.lib.st_summary_diagnostics, self.n_all, max_lag, True, n_kept)
+
+    def points_diagnostics(self, max_lag=0, n_kept=None):
+        """The same of the point set's stored w* and yhat* draws (st_points_summary_reserve), in the caller's order; ``yhat``
+        None without X."""
+        return self._diagnostics(self.lib.st_points_summary_diagnostics, self.n_points, max_lag, self.points_have_X, n_kept)
+
+    def functionals_diagnostics(self, max_lag=0, n_kept=None):
+        """The same of the functionals' stored F_w and F_y draws; ``yhat`` None without X."""
+        return self._diagnostics(self.lib.st_points_functionals_diagnostics, self.n_functionals, max_lag, self.points_have_X, n_kept)
 
     # ---- criteria over the fit's own rows (st_rows_score_*): conditional on w
     def rows_score_set(self, y_holdout=None, y=None):

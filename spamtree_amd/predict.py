@@ -106,7 +106,7 @@ def conditioning_set(topo: Topology, anchor: int) -> np.ndarray:
 
 def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, return_draws=True, device=0, z=None,
                 mode=0, force_generic=False, return_moments=False, joint=None, functionals=None, y_new=None, quantiles=(),
-                crps=True):
+                crps=True, diagnostics=False, diagnostics_max_lag=0):
     """Predictive at new locations for every saved draw of a chain.
 
     ``model_inputs``: the problem as ``spamtree_mv_mcmc`` took it (the dict of ``synthetic.make_workload``; its ``topo``
@@ -135,6 +135,10 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
     yhat kept on the device for the CRPS.  The result also holds ``scores`` (``SpamTreeMV.scores``); ``quantiles=(lo, ..., hi)``
     adds the coverage of [yhat_lo, yhat_hi] to its totals.  ``crps=False`` leaves the CRPS out and keeps no draw on the device
     (neither then has ``quantiles``); with it the chain may hold at most 16384 saved draws.
+
+    ``diagnostics``: ESS, MCSE, sd and split-R-hat of every point's w* and yhat* draws (``spamtree_amd.diagnostics``), formed on
+    the device after the last draw from the draws it keeps (``z`` None, ``mode`` 0; 4 .. 16384 saved draws).  The result then
+    holds ``diagnostics``: dict(w, yhat) and, with ``functionals``, ``functionals["diagnostics"]``.
     """
     mi = model_inputs
     topo = mi["topo"]
@@ -151,6 +155,13 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
         ys = score_values(y_new, n_new, X_new is not None)
         if z is not None or mode != 0:
             raise ValueError("y_new needs the device draw: z=None and mode=0")
+    if diagnostics:
+        if z is not None or mode != 0:
+            raise ValueError("diagnostics need the device draw: z=None and mode=0")
+        if not 4 <= len(draws["w_mcmc"]) <= fit.MAX_STORED_DRAWS:
+            raise ValueError(f"diagnostics need 4 .. {fit.MAX_STORED_DRAWS} saved draws (the device keeps them)")
+        if int(diagnostics_max_lag) < 0:
+            raise ValueError("diagnostics_max_lag must not be negative (0: the default cap)")
     qs = tuple(float(x) for x in quantiles)
     if not all(0.0 <= x <= 1.0 for x in qs):
         raise ValueError("quantiles must lie in [0, 1]")
@@ -184,6 +195,8 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
             m.set_scores(ys)
             if crps:
                 m._check(m.lib.st_points_summary_reserve(m.h, keep))
+        if diagnostics:
+            m._check(m.lib.st_points_summary_reserve(m.h, keep))
         cc = []
         w_out = np.zeros((n_new, keep)) if return_draws else None
         y_out = np.zeros((n_new, keep)) if (return_draws and X_new is not None) else None
@@ -197,7 +210,7 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
             m.theta_update(0, theta[:, s])
             if not m.get_loglik_comps_w(0):
                 raise FloatingPointError(f"st_factor failed on saved draw {s} (errtype {m.last_errtype})")
-            if fun is None and ys is None:
+            if fun is None and ys is None and not diagnostics:
                 out = m.predict_points(mode=mode, z=None if z is None else z[:, s], seed=seed, it=s)
             else:
                 out = m.accumulate_points(seed=seed, it=s)
@@ -232,6 +245,10 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
                     m._check(m.lib.st_points_summary_quantile(m.h, x, None, _dp(yq)))
                     lo_hi.append(yq.copy())
             res["scores"] = m.scores(crps=crps, yhat_lo=lo_hi[0], yhat_hi=lo_hi[1])
+        if diagnostics and n_new:
+            res["diagnostics"] = m.points_diagnostics(int(diagnostics_max_lag), n_kept=keep)
+            if fun is not None:
+                res["functionals"]["diagnostics"] = m.functionals_diagnostics(int(diagnostics_max_lag), n_kept=keep)
         if joint is not None:
             packed = np.mean(cc, axis=0) if keep else np.zeros(0)
             for k, g in enumerate(m.joint_groups):
@@ -247,7 +264,7 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
 
 
 def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), return_draws=True, joint=None, functionals=None,
-                y_new=None, crps=True, **mcmc):
+                y_new=None, crps=True, diagnostics=False, diagnostics_max_lag=0, **mcmc):
     """Fit the chain and predict at new locations on every saved iteration, without replaying it.
 
     ``model_inputs``: the problem as for :func:`predict_new`.  The points are located with :func:`locate` and handed to
@@ -266,6 +283,7 @@ def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), retu
     points, overall and per outcome; with two or more ``quantiles`` the coverage of [yhat_lo, yhat_hi]), all formed on the device
     during the fit, whatever ``return_draws`` is.  For the CRPS the device keeps ``mcmc_keep`` draws of w and yhat per point (16 B
     each per point and draw, at most 16384 draws); ``crps=False`` scores without it and stores nothing.
+    With ``diagnostics`` the fit's ``diagnostics`` (``fit.spamtree_mv_mcmc``) and ``new["diagnostics"]``, ``new["functionals"]["diagnostics"]``.
     """
     mi = model_inputs
     coords_new = np.asarray(coords_new, dtype=np.float64).reshape(-1, 2)
@@ -298,6 +316,6 @@ def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), retu
                                mi["res_is_ref"], mi["parents"], mi["children"], bool(mi.get("limited_tree", False)),
                                mi["block_names"], mi["block_groups"], mi["indexing"],
                                new_points=points, new_draws=return_draws,
-                               new_quantiles=qs, **kw)
+                               new_quantiles=qs, diagnostics=diagnostics, diagnostics_max_lag=diagnostics_max_lag, **kw)
     out["new"]["anchor"] = anchor
     return out
