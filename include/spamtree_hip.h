@@ -270,6 +270,56 @@ int st_summary_diagnostics(st_handle h, int32_t max_lag, const st_series_diag *w
 int st_points_summary_diagnostics(st_handle h, int32_t max_lag, const st_series_diag *w, const st_series_diag *yhat);
 int st_points_functionals_diagnostics(st_handle h, int32_t max_lag, const st_series_diag *w, const st_series_diag *yhat);
 
+/* ---- exceedance probabilities, excursion functions and simultaneous bands of the stored draws, on the device.  One store
+ * X[d][i] has draws d < K (1 <= K <= 16384) and series i < n (a row's w or yhat, a new point's w* or yhat*, a functional's F_w or
+ * F_y).  The definition (the kernel file, spamtree_amd.excursions and the tests' reference restate it):
+ *   domain      every series has g(i) in {-1, 0 .. G-1}: rows and new points g(i) = outcome (mv - 1), G = q; functionals G = 1.
+ *               mask (n bytes in the order of the outputs, 0 = out, NULL = all in) sets g(i) = -1: such a series still gets its
+ *               marginal outputs (count, prob, mean, sd) and takes part in no joint one.
+ *   thresholds  T = n_thr of them, 1 <= T <= ST_EXC_MAX_THRESHOLDS, each with a side s_t in {+1, -1} (side NULL: all +1) and the
+ *               values c_t(i) = thr[t q + outcome(i)] for rows and points, thr[t n_fun + i] for functionals.
+ *   event       E_t(d,i): X[d][i] > c_t(i) for side +1, X[d][i] < c_t(i) for side -1, both strict; a NaN draw makes it false.
+ *   exceedance  count_t(i) = #{d : E_t(d,i)} (int32);  prob_t(i) = count_t(i) / K, one double division.
+ *   excursion   the nested family is the level sets of the marginal count, D_{t,g}(c) = {i : g(i) = g, count_t(i) >= c}; whole
+ *               tie classes enter together, no order among ties is invented.  Per draw
+ *                 m_{t,g}(d) = max{count_t(i) : g(i) = g, not E_t(d,i)}, -1 if no series of the domain fails;
+ *               draw d satisfies D(c) exactly when m(d) < c, so
+ *                 excur_t(i) = #{d : m_{t,g(i)}(d) < count_t(i)} / K for g(i) >= 0, NaN for g(i) = -1;
+ *                 joint_all[t][g] = #{d : m_{t,g}(d) < 0} / K, the share of draws with the event on the whole domain (an empty
+ *               domain gives 1).  The level-alpha excursion set of a domain is {i : excur_t(i) >= 1 - alpha}.  excur <= prob, and
+ *               excur does not decrease as count grows within a domain.  Integer comparisons, integer max and one division:
+ *               bitwise defined, whatever the order of the reductions.
+ *   band        (want_band, or any of mean / sd / maxdev / n_flat asked for; K >= 2)  per series Welford over ascending d in one
+ *               chain: delta = x - m; m <- fma(delta, r_d, m) with r_d = 1 / (d + 1) rounded once; M2 <- fma(delta, x - m, M2);
+ *               mean = m, sd = sqrt(M2 / (K - 1)).  Per draw and domain
+ *                 maxdev[g][d] = max{|X[d][i] - mean_i| / sd_i : g(i) = g, sd_i > 0 and finite}, 0 if there is no such series;
+ *               the series of a domain with sd_i = 0 or NaN are left out and counted in n_flat[g].  The band factor is not a
+ *               device output: it is the ceil((1 - alpha) K)-th smallest maxdev[g][.] (an order statistic, not interpolated;
+ *               spamtree_amd.excursions.band_factor), and the band is mean +- factor sd.
+ * No reduction over series depends on the launch geometry in its value (integer max, max of non-negative doubles, integer sums);
+ * the outputs of a store are a function of its contents, the thresholds and the mask only.
+ * Any pointer of st_excursion_out may be NULL: only what is asked for is computed and copied.  count, prob, excur: n_thr x n,
+ * threshold-major; joint_all: n_thr x G; mean, sd: n; maxdev: G x K; n_flat: G; n_draws: the K the call worked on.
+ * st_summary_excursions: the stores of st_summary_reserve; n = n_all, model row order; limited_tree handles included.
+ * st_points_summary_excursions: the point set's stores, caller order; st_points_summary_quantile's refusals.
+ * st_points_functionals_excursions: the functionals' stores; st_points_functionals_quantile's refusals.
+ * Each call works on the draws stored so far, changes no state and consumes no Philox draw; either out may be NULL.
+ * ST_ERR_USAGE with a text: no stored draw; n_thr outside 1 .. 8 when thr is given; a NaN or infinite threshold; a side other
+ * than +-1; a band request with K < 2; count / prob / excur / joint_all without thr; yhat on a point set without X; a spec with
+ * neither thresholds nor band.  A point or functional set of size 0: ST_OK, nothing written.  A refusal leaves the handle usable. */
+#define ST_EXC_MAX_THRESHOLDS 8
+typedef struct st_excursion_spec { int32_t n_thr; const double *thr; const int32_t *side; const uint8_t *mask; int32_t want_band; } st_excursion_spec;
+typedef struct st_excursion_out {      /* any pointer may be NULL; only what is asked for is computed and copied */
+  int32_t *count; double *prob, *excur;        /* n_thr x n, threshold-major */
+  double *joint_all;                           /* n_thr x G */
+  double *mean, *sd;                           /* n */
+  double *maxdev; int64_t *n_flat;             /* G x K; G */
+  int64_t *n_draws;
+} st_excursion_out;
+int st_summary_excursions(st_handle h, const st_excursion_spec *spec, const st_excursion_out *w, const st_excursion_out *yhat);
+int st_points_summary_excursions(st_handle h, const st_excursion_spec *spec, const st_excursion_out *w, const st_excursion_out *yhat);
+int st_points_functionals_excursions(st_handle h, const st_excursion_spec *spec, const st_excursion_out *w, const st_excursion_out *yhat);
+
 /* ---- new-point prediction from a fitted state: the predictive at locations that are not rows of the problem, the way the model
  * treats an NA row (make_tree's missing level, predict_std spamtree_model.cpp:1234-1358) without rebuilding the tree.
  * A point of margin j anchored at block b (the block of its nearest deepest-knot-level row, same margin if cherrypick_same_margin,

@@ -29,12 +29,25 @@ class StSeriesDiag(C.Structure):   # include/spamtree_hip.h, st_series_diag: n v
     _fields_ = [("ess", c_dp), ("mcse", c_dp), ("sd", c_dp), ("rhat", c_dp), ("lags", C.POINTER(C.c_int32))]
 
 
+class StExcursionSpec(C.Structure):   # include/spamtree_hip.h, st_excursion_spec
+    _fields_ = [("n_thr", C.c_int32), ("thr", C.POINTER(C.c_double)), ("side", C.POINTER(C.c_int32)), ("mask", C.POINTER(C.c_uint8)),
+                ("want_band", C.c_int32)]
+
+
+class StExcursionOut(C.Structure):    # st_excursion_out: any pointer may be NULL
+    _fields_ = [("count", C.POINTER(C.c_int32)), ("prob", C.POINTER(C.c_double)), ("excur", C.POINTER(C.c_double)),
+                ("joint_all", C.POINTER(C.c_double)), ("mean", C.POINTER(C.c_double)), ("sd", C.POINTER(C.c_double)),
+                ("maxdev", C.POINTER(C.c_double)), ("n_flat", C.POINTER(C.c_int64)), ("n_draws", C.POINTER(C.c_int64))]
+
+
+ST_EXC_MAX_THRESHOLDS = 8
 ST_DIAG_MIN_DRAWS = 4
 ST_DIAG_DEFAULT_MAX_LAG = 1024
 
 # every symbol include/spamtree_hip.h declares: name -> (restype, argtypes)
 H = C.c_void_p
 c_sdp = C.POINTER(StSeriesDiag)
+c_xsp, c_xop = C.POINTER(StExcursionSpec), C.POINTER(StExcursionOut)
 SIGNATURES = {
     "st_create": (C.c_int, [C.POINTER(StProblem), C.POINTER(StOptions), C.POINTER(H)]),
     "st_destroy": (C.c_int, [H]),
@@ -104,6 +117,9 @@ SIGNATURES = {
     "st_summary_diagnostics": (C.c_int, [H, C.c_int32, c_sdp, c_sdp]),
     "st_points_summary_diagnostics": (C.c_int, [H, C.c_int32, c_sdp, c_sdp]),
     "st_points_functionals_diagnostics": (C.c_int, [H, C.c_int32, c_sdp, c_sdp]),
+    "st_summary_excursions": (C.c_int, [H, c_xsp, c_xop, c_xop]),
+    "st_points_summary_excursions": (C.c_int, [H, c_xsp, c_xop, c_xop]),
+    "st_points_functionals_excursions": (C.c_int, [H, c_xsp, c_xop, c_xop]),
     "st_comm_unique_id": (C.c_int, [C.c_void_p, C.c_int32]),
     "st_comm_init": (C.c_int, [H, C.c_void_p]),
     "st_points_set": (C.c_int, [H, C.c_int64, c_dp, c_ip, c_ip, c_dp]),
@@ -206,6 +222,16 @@ class StmDiagnostics(C.Structure):   # include/spamtree_fit.h, stm_diagnostics
 
 
 SIGNATURES["stm_mcmc_diagnosed"] = (C.c_int, SIGNATURES["stm_mcmc_scored"][1] + [C.POINTER(StmDiagnostics)])
+
+
+
+class StmExcursions(C.Structure):    # include/spamtree_fit.h, stm_excursions
+    _fields_ = [("want_rows", C.c_int32), ("rows_spec", StExcursionSpec), ("new_spec", StExcursionSpec), ("fun_spec", StExcursionSpec),
+                ("rows_w", StExcursionOut), ("rows_yhat", StExcursionOut), ("new_w", StExcursionOut), ("new_yhat", StExcursionOut),
+                ("fun_w", StExcursionOut), ("fun_yhat", StExcursionOut)]
+
+
+SIGNATURES["stm_mcmc_excursions"] = (C.c_int, SIGNATURES["stm_mcmc_diagnosed"][1] + [C.POINTER(StmExcursions)])
 
 SIGNATURES["stm_rows_score_set"] = (C.c_int, [H, c_dp])
 SIGNATURES["stm_mcmc_criteria"] = (C.c_int, SIGNATURES["spamtree_mv_mcmc_c"][1] + [C.POINTER(StmCriteria)])

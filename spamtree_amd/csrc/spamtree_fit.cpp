@@ -581,8 +581,25 @@ extern "C" int stm_mcmc_functionals(const st_problem *pb, const st_options *opt,
 
 static bool diag_any(const st_series_diag &d) { return d.ess || d.mcse || d.sd || d.rhat || d.lags; }
 
-// fun NULL: stm_mcmc_points_joint itself; scores NULL: stm_mcmc_functionals itself; diag NULL: stm_mcmc_scored itself
-extern "C" int stm_mcmc_diagnosed(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
+static bool exc_thr_any(const st_excursion_out &o) { return o.count || o.prob || o.excur || o.joint_all; }
+static bool exc_band_any(const st_excursion_out &o) { return o.mean || o.sd || o.maxdev || o.n_flat; }
+static bool exc_any(const st_excursion_out &o) { return exc_thr_any(o) || exc_band_any(o) || o.n_draws; }
+// what st_*_excursions would refuse of a spec after the chain, found before it: nvals thresholds per t, keep draws to be stored
+static int exc_spec_refused(const st_excursion_spec &sp, int64_t nvals, const st_excursion_out &w, const st_excursion_out &y, int keep) {
+  const bool band = sp.want_band || exc_band_any(w) || exc_band_any(y);
+  if (!sp.thr && !band) return ST_ERR_USAGE;
+  if (sp.thr) {
+    if (sp.n_thr < 1 || sp.n_thr > ST_EXC_MAX_THRESHOLDS) return ST_ERR_USAGE;
+    for (int64_t k = 0; k < (int64_t)sp.n_thr * nvals; ++k) if (!std::isfinite(sp.thr[k])) return ST_ERR_USAGE;
+    for (int t = 0; sp.side && t < sp.n_thr; ++t) if (sp.side[t] != 1 && sp.side[t] != -1) return ST_ERR_USAGE;
+  } else if (exc_thr_any(w) || exc_thr_any(y)) return ST_ERR_USAGE;
+  if (keep < 1 || (band && keep < 2)) return ST_ERR_USAGE;
+  return 0;
+}
+
+// fun NULL: stm_mcmc_points_joint itself; scores NULL: stm_mcmc_functionals itself; diag NULL: stm_mcmc_scored itself; exc NULL:
+// stm_mcmc_diagnosed itself
+extern "C" int stm_mcmc_excursions(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
                                     int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
                                     int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
                                     double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
@@ -591,9 +608,10 @@ extern "C" int stm_mcmc_diagnosed(const st_problem *pb, const st_options *opt, c
                                     int32_t n_quantiles, double *new_w, double *new_cond_mean, double *new_cond_var, double *new_yhat,
                                     double *new_mean, double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q,
                                     double *new_yhat_q, int32_t *new_route, double *new_cond_cov, double *new_cov,
-                                    const stm_functionals *fun, const stm_scores *scores, const stm_diagnostics *diag) {
+                                    const stm_functionals *fun, const stm_scores *scores, const stm_diagnostics *diag,
+                                    const stm_excursions *exc) {
   if (fun && fun->n_fun <= 0) fun = nullptr;
-  const bool plain = diag && n_new == 0 && !coords_new && !mv_new && !anchor_new;   // the plain chain (with diag only: stm_mcmc_scored handles an empty set as before)
+  const bool plain = (diag || exc) && n_new == 0 && !coords_new && !mv_new && !anchor_new;   // the plain chain (with diag only: stm_mcmc_scored handles an empty set as before)
   const bool d_rows = diag && diag->want_rows && (diag_any(diag->rows_w) || diag_any(diag->rows_yhat));
   const bool d_new = diag && !plain && (diag_any(diag->new_w) || diag_any(diag->new_yhat));
   const bool d_fun = diag && fun && (diag_any(diag->fun_w) || diag_any(diag->fun_yhat));
@@ -607,6 +625,21 @@ extern "C" int stm_mcmc_diagnosed(const st_problem *pb, const st_options *opt, c
     if (mcmc_keep < ST_DIAG_MIN_DRAWS) return ST_ERR_USAGE;
     if (d_new || d_fun) keep_draws = std::max<int64_t>(keep_draws, mcmc_keep);
   }
+  const bool e_rows = exc && exc->want_rows && (exc_any(exc->rows_w) || exc_any(exc->rows_yhat));
+  const bool e_new = exc && !plain && (exc_any(exc->new_w) || exc_any(exc->new_yhat));
+  const bool e_fun = exc && fun && (exc_any(exc->fun_w) || exc_any(exc->fun_yhat));
+  if (exc && !exc->want_rows && (exc_any(exc->rows_w) || exc_any(exc->rows_yhat))) return ST_ERR_USAGE;
+  if (exc && plain && (exc_any(exc->new_w) || exc_any(exc->new_yhat))) return ST_ERR_USAGE;
+  if (exc && !fun && (exc_any(exc->fun_w) || exc_any(exc->fun_yhat))) return ST_ERR_USAGE;
+  if ((e_new && exc_any(exc->new_yhat) && !X_new) || (e_fun && exc_any(exc->fun_yhat) && !X_new)) return ST_ERR_USAGE;
+  if (e_rows || e_new || e_fun) {
+    if (mcmc_keep > 16384) return ST_ERR_UNSUPPORTED;   // the stores' limit
+    if (e_rows) if (const int r = exc_spec_refused(exc->rows_spec, pb->q, exc->rows_w, exc->rows_yhat, mcmc_keep)) return r;
+    if (e_new) if (const int r = exc_spec_refused(exc->new_spec, pb->q, exc->new_w, exc->new_yhat, mcmc_keep)) return r;
+    if (e_fun) if (const int r = exc_spec_refused(exc->fun_spec, fun->n_fun, exc->fun_w, exc->fun_yhat, mcmc_keep)) return r;
+    if (e_new || e_fun) keep_draws = std::max<int64_t>(keep_draws, mcmc_keep);
+  }
+  const bool store_rows = d_rows || e_rows;   // one reservation serves both
   if (plain && (fun || (scores && scores->y_new) || joint_id_new || X_new || n_quantiles != 0)) return ST_ERR_USAGE;
   if (scores && !scores->y_new) scores = nullptr;
   if (scores && (!X_new || (scores->lpd_joint && !joint_id_new) || (scores->crps && keep_draws < 1))) return ST_ERR_USAGE;
@@ -618,7 +651,7 @@ extern "C" int stm_mcmc_diagnosed(const st_problem *pb, const st_options *opt, c
   stm_chain c = nullptr;
   int rc = stm_create(pb, opt, set_unif_bounds, mcmcsd, theta, ntheta, beta, tausq, seed, flags, &c);
   if (rc == 0 && !plain) rc = stm_points_set_joint(c, n_new, coords_new, mv_new, anchor_new, X_new, joint_id_new, keep_draws);   // refusals: before any factorisation
-  if (rc == 0 && d_rows) {
+  if (rc == 0 && store_rows) {
     rc = st_summary_reset(c->h);
     if (rc == 0) rc = st_summary_reserve(c->h, mcmc_keep);
   }
@@ -638,9 +671,11 @@ extern "C" int stm_mcmc_diagnosed(const st_problem *pb, const st_options *opt, c
   double *const ccov = !joint_id_new ? nullptr : (new_cond_cov ? new_cond_cov : (cov_scratch.empty() ? nullptr : cov_scratch.data()));
   const FitPoints pts{n_new, new_w, new_cond_mean, new_cond_var, new_yhat, ccov, joint_id_new ? joff[nj] : 0, fun};
   rc = run_fit(c, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc, yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time,
-               plain ? nullptr : &pts, nullptr, d_rows);
-  if (plain) {   // the diagnostics of the rows are all a plain chain can ask for
+               plain ? nullptr : &pts, nullptr, store_rows);
+  if (plain) {   // the diagnostics and excursions of the rows are all a plain chain can ask for
     if (rc == 0 && d_rows) rc = st_summary_diagnostics(c->h, diag->max_lag, &diag->rows_w, &diag->rows_yhat);
+    if (rc == 0 && e_rows) rc = st_summary_excursions(c->h, &exc->rows_spec, &exc->rows_w, &exc->rows_yhat);
+    if (rc) c->err = st_last_error(c->h);
     stm_destroy(c);
     return rc;
   }
@@ -670,8 +705,29 @@ extern "C" int stm_mcmc_diagnosed(const st_problem *pb, const st_options *opt, c
     rc = st_points_summary_diagnostics(c->h, diag->max_lag, &diag->new_w, diag_any(diag->new_yhat) ? &diag->new_yhat : nullptr);
   if (rc == 0 && d_fun)
     rc = st_points_functionals_diagnostics(c->h, diag->max_lag, &diag->fun_w, diag_any(diag->fun_yhat) ? &diag->fun_yhat : nullptr);
+  if (rc == 0 && e_rows) rc = st_summary_excursions(c->h, &exc->rows_spec, &exc->rows_w, &exc->rows_yhat);
+  if (rc == 0 && e_new)
+    rc = st_points_summary_excursions(c->h, &exc->new_spec, &exc->new_w, exc_any(exc->new_yhat) ? &exc->new_yhat : nullptr);
+  if (rc == 0 && e_fun)
+    rc = st_points_functionals_excursions(c->h, &exc->fun_spec, &exc->fun_w, exc_any(exc->fun_yhat) ? &exc->fun_yhat : nullptr);
   stm_destroy(c);
   return rc;
+}
+
+extern "C" int stm_mcmc_diagnosed(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
+                                    int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
+                                    int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
+                                    double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
+                                    int64_t n_new, const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new,
+                                    const double *X_new, const int64_t *joint_id_new, int64_t keep_draws, const double *quantiles,
+                                    int32_t n_quantiles, double *new_w, double *new_cond_mean, double *new_cond_var, double *new_yhat,
+                                    double *new_mean, double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q,
+                                    double *new_yhat_q, int32_t *new_route, double *new_cond_cov, double *new_cov,
+                                    const stm_functionals *fun, const stm_scores *scores, const stm_diagnostics *diag) {
+  return stm_mcmc_excursions(pb, opt, set_unif_bounds, theta, ntheta, beta, tausq, mcmcsd, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc,
+                             yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time, n_new, coords_new, mv_new, anchor_new, X_new,
+                             joint_id_new, keep_draws, quantiles, n_quantiles, new_w, new_cond_mean, new_cond_var, new_yhat, new_mean, new_var,
+                             new_w_mean, new_yhat_mean, new_w_q, new_yhat_q, new_route, new_cond_cov, new_cov, fun, scores, diag, nullptr);
 }
 
 extern "C" int stm_mcmc_scored(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,

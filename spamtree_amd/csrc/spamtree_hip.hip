@@ -27,6 +27,7 @@
 #include "st_handle.hpp"
 #include "misc_kernels.hpp"
 #include "diag_kernels.hpp"
+#include "excursion_kernels.hpp"
 #include "rows_score.hpp"
 #include <new>
 
@@ -1634,6 +1635,14 @@ extern "C" int st_summary_diagnostics(st_handle h, int32_t max_lag, const st_ser
   }
   if (const int rc = series_diag_store(h, "st_summary_diagnostics", h->d_draws_w.p, h->n_all, h->n_draws, max_lag, h->dev2model.data(), w)) return rc;
   return series_diag_store(h, "st_summary_diagnostics", h->d_draws_yhat.p, h->n_all, h->n_draws, max_lag, h->dev2model.data(), yhat);
+}
+// exceedance counts, excursion functions and the simultaneous band of every row's stored draws (excursion_kernels.hpp): the
+// domains are the outcomes (d_mv, device order), the outputs come back in model row order
+extern "C" int st_summary_excursions(st_handle h, const st_excursion_spec *spec, const st_excursion_out *w, const st_excursion_out *yhat) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = exc_check_spec(h, "st_summary_excursions", spec, h->n_draws, h->q, w, yhat)) return rc;
+  if (const int rc = store_excursions(h, "st_summary_excursions", h->d_draws_w.p, h->n_all, h->n_draws, h->d_mv.p, h->q, false, h->dev2model.data(), spec, w)) return rc;
+  return store_excursions(h, "st_summary_excursions", h->d_draws_yhat.p, h->n_all, h->n_draws, h->d_mv.p, h->q, false, h->dev2model.data(), spec, yhat);
 }
 extern "C" int st_summary_get(st_handle h, double *w_mean, double *yhat_mean, int64_t *n_accumulated) {
   if (!h) return ST_ERR_USAGE;

@@ -9,8 +9,9 @@ import numpy as np
 
 from . import _lib
 from . import diagnostics as _diag
+from . import excursions as _exc
 from .model import (SpamTreeError, _dp, _f64, _i64, _ip, _lists_to_csr, functionals_csr, joint_labels, rows_criteria, rows_holdout, score_totals,
-                    score_values, series_diag_buffers, series_diag_finish)
+                    score_values, series_diag_buffers, series_diag_finish, excursion_spec, excursion_buffers, excursion_finish)
 
 
 def _problem(y, X, coords, mv_id, res_is_ref, parents, children, block_names, block_groups, indexing):
@@ -241,7 +242,7 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                      main_verbose=True, verbose=False, debug=False, printall=False, sample_beta=True, sample_tausq=True,
                      sample_theta=True, sample_w=True, sample_predicts=True, seed=2021, device=0, reference_quirks=True,
                      new_points=None, new_draws=True, new_quantiles=(), save_w=True, save_yhat=True, force_generic=False,
-                     criteria=False, y_holdout=None, holdout_crps=True, diagnostics=False, diagnostics_max_lag=0):
+                     criteria=False, y_holdout=None, holdout_crps=True, diagnostics=False, diagnostics_max_lag=0, excursions=None):
     """spamtree_fit.cpp:5-430 through the C++ driver.  `num_threads`, `use_alg`, the verbosity flags and `start_w` are
     accepted and ignored exactly where the reference ignores them (start_w, :95) or where they do not apply to a GPU.
 
@@ -287,8 +288,36 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     save_yhat=False, new_draws=False``); and ``summary``: ``diagnostics.summarise`` of each part, w and yhat also by outcome.  With
     ``new_points`` also ``new["diagnostics"]`` (w, yhat per point) and ``new["functionals"]["diagnostics"]``.  ``mcmc_keep`` must lie
     in 4 .. 16384 (ValueError); not together with ``criteria`` / ``y_holdout`` (one driver per call).  A failure of the chain raises
-    SpamTreeError, as with ``new_points``."""
+    SpamTreeError, as with ``new_points``.
+    ``excursions=dict(thresholds=, side=, mask=, band=)``: exceedance probabilities, the excursion function and, with ``band``,
+    the simultaneous band's ingredients (``spamtree_amd.excursions`` has the definition and what to do with them), formed on the
+    device after the last iteration from ``mcmc_keep`` draws of w and yhat it keeps per row (stm_mcmc_excursions: the chain is the
+    same bit for bit; it works with ``save_w=False, save_yhat=False, new_draws=False``).  ``thresholds``: a scalar or up to 8
+    entries, each a scalar or one value per outcome; ``side``: +1 (above) / -1 (below), a scalar or one per threshold; ``mask``:
+    one entry per row, 0 = in no domain.  The result holds ``excursions``: dict(w, yhat) of dict(count, prob, excur (T x n),
+    joint_all (T x q), mean, sd (n), maxdev (q x K), n_flat (q), n_draws).  With ``new_points`` also ``new["excursions"]``
+    (``mask_new`` masks the points) and ``new["functionals"]["excursions"]`` (``thresholds_fun``: entries scalar or one value per
+    functional, default ``thresholds`` when all its entries are scalars; ``mask_fun``).  May be combined with ``diagnostics``, not
+    with ``criteria`` / ``y_holdout``.  ValueError before any device call: bad shapes, more than 8 thresholds, non-finite
+    thresholds, ``mcmc_keep`` outside 1 .. 16384 (2 with ``band``)."""
     crit = bool(criteria) or y_holdout is not None
+    exc = None
+    if excursions is not None:
+        exc = dict(excursions)
+        unknown = set(exc) - {"thresholds", "side", "mask", "band", "mask_new", "thresholds_fun", "mask_fun"}
+        if unknown:
+            raise ValueError(f"excursions: unknown keys {sorted(unknown)}")
+        if crit:
+            raise ValueError("excursions and criteria / y_holdout are separate drivers (stm_mcmc_excursions, stm_mcmc_criteria): one per call")
+        exc["band"] = bool(exc.get("band", False))
+        if exc.get("thresholds") is None and not exc["band"]:
+            raise ValueError("excursions: neither thresholds nor band")
+        _exc.check_keep(mcmc_keep, exc["band"])
+        if exc.get("thresholds") is not None:   # the count, the values and the sides; the shapes once q is known
+            entries = _exc.threshold_entries(exc["thresholds"])
+            _exc.expand_thresholds([0.0] * len(entries), 1, exc.get("side", 1))
+            for e in entries:
+                _exc.expand_thresholds([e], np.size(e), 1)
     diagnostics = bool(diagnostics)
     if diagnostics:
         if crit:
@@ -316,6 +345,25 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                              f"{MAX_STORED_DRAWS} (crps=False scores without it)")
     elif len(tuple(new_quantiles)):
         raise ValueError("new_quantiles needs new_points")
+    xs = None
+    if exc is not None:   # the shapes, still before any device call
+        n_rows, q_out = int(np.asarray(y).size), int(np.unique(_i64(mv_id)).size)
+        thr = sides = None
+        if exc.get("thresholds") is not None:
+            thr, sides = _exc.expand_thresholds(exc["thresholds"], q_out, exc.get("side", 1))
+        exc["spec_rows"] = excursion_spec(thr, sides, _exc.check_mask(exc.get("mask"), n_rows), exc["band"])
+        exc["T"] = 0 if thr is None else thr.shape[0]
+        if new_points is not None:
+            exc["spec_new"] = excursion_spec(thr, sides, _exc.check_mask(exc.get("mask_new"), pts[0].shape[0]), exc["band"])
+            if pts[6] is not None:
+                nf_ = pts[6][0].size - 1
+                tf = exc.get("thresholds_fun", exc.get("thresholds"))
+                thr_f = sides_f = None
+                if tf is not None:
+                    thr_f, sides_f = _exc.expand_thresholds(tf, nf_, exc.get("side", 1))
+                exc["spec_fun"] = excursion_spec(thr_f, sides_f, _exc.check_mask(exc.get("mask_fun"), nf_), exc["band"])
+        elif any(exc.get(key) is not None for key in ("mask_new", "thresholds_fun", "mask_fun")):
+            raise ValueError("excursions: mask_new, thresholds_fun and mask_fun need new_points")
     lib = _lib.load()
     pb, keep, n, p, q = _problem(y, X, coords, mv_id, res_is_ref, parents, children, layer_names, layer_gibbs_group, indexing)
     theta = _f64(theta)
@@ -341,6 +389,15 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
         dy, sy = series_diag_buffers(n)
         diag_rows = dict(w=dw, yhat=dy)
         ds = _lib.StmDiagnostics(max_lag, 1, sw, sy)
+    exc_rows = exc_new = exc_fun = None
+    if exc is not None:   # stm_mcmc_excursions: stm_mcmc_diagnosed plus the excursions of the rows, points and functionals
+        xs = _lib.StmExcursions()
+        xs.want_rows = 1
+        xs.rows_spec = exc["spec_rows"][0]
+        xw, xs.rows_w = excursion_buffers(n, exc["T"], q, int(mcmc_keep), exc["band"])
+        xy, xs.rows_yhat = excursion_buffers(n, exc["T"], q, int(mcmc_keep), exc["band"])
+        exc_rows = dict(w=xw, yhat=xy)
+    dsp = C.byref(ds) if ds is not None else None
     if crit:
         rows = {key: np.zeros(n) for key in ("lppd", "p_waic", "mean_ll", "mu_mean", "pit")}
         rows["crps"] = np.zeros(n) if (want_crps and mcmc_keep > 0) else None
@@ -355,6 +412,12 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                             totals=rows_criteria(tobs, theld, n_obs, n_held, have_crps=rows["crps"] is not None))
         elif rc not in (0, -10):
             err = SpamTreeError(f"stm_mcmc_criteria failed ({rc})")
+            err.code = rc
+            raise err
+    elif new_points is None and exc is not None:   # the plain chain through the excursions driver: no point argument
+        rc = lib.stm_mcmc_excursions(*common, 0, None, None, None, None, None, 0, None, 0, *([None] * 15), dsp, C.byref(xs))
+        if rc not in (0, -10):
+            err = SpamTreeError(f"stm_mcmc_excursions failed ({rc})")
             err.code = rc
             raise err
     elif new_points is None and diagnostics:   # the plain chain through the diagnosed driver: no point argument
@@ -416,6 +479,26 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                 if s_fy is not None:
                     ds.fun_yhat = s_fy
                 diag_fun = dict(w=dfw, yhat=dfy)
+        if exc is not None:
+            xs.new_spec = exc["spec_new"][0]
+            T_f = 0
+            xnw, xs.new_w = excursion_buffers(n_new, exc["T"], q, int(mcmc_keep), exc["band"])
+            xny, o_ny = excursion_buffers(n_new, exc["T"], q, int(mcmc_keep), exc["band"], pX is not None)
+            if o_ny is not None:
+                xs.new_yhat = o_ny
+            exc_new = dict(w=xnw, yhat=xny)
+            if fun is not None:
+                xs.fun_spec = exc["spec_fun"][0]
+                T_f = int(xs.fun_spec.n_thr)
+                xfw, xs.fun_w = excursion_buffers(nf, T_f, 1, int(mcmc_keep), exc["band"])
+                xfy, o_fy = excursion_buffers(nf, T_f, 1, int(mcmc_keep), exc["band"], pX is not None)
+                if o_fy is not None:
+                    xs.fun_yhat = o_fy
+                exc_fun = dict(w=xfw, yhat=xfy)
+            rc = lib.stm_mcmc_excursions(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), _ip(labels) if labels is not None else None,
+                                         *tail, dp(ccov), dp(cov), fsp, C.byref(ss) if ss is not None else None,
+                                         C.byref(ds) if ds is not None else None, C.byref(xs))
+        elif diagnostics:
             rc = lib.stm_mcmc_diagnosed(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), _ip(labels) if labels is not None else None,
                                         *tail, dp(ccov), dp(cov), fsp, C.byref(ss) if ss is not None else None, C.byref(ds))
         elif ynew is not None:
@@ -457,6 +540,10 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                 new["diagnostics"] = {key: series_diag_finish(v, mcmc_keep, max_lag) for key, v in diag_new.items()}
             if diag_fun is not None and n_new > 0:
                 new["functionals"]["diagnostics"] = {key: series_diag_finish(v, mcmc_keep, max_lag) for key, v in diag_fun.items()}
+            if exc_new is not None and n_new > 0:
+                new["excursions"] = {key: excursion_finish(v) for key, v in exc_new.items()}
+            if exc_fun is not None and n_new > 0:
+                new["functionals"]["excursions"] = {key: excursion_finish(v) for key, v in exc_fun.items()}
     if rc == -10:
         raise FloatingPointError("At nan loglik: error.")
     if rc != 0 and new_points is not None:
@@ -485,4 +572,6 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
         mv_rows = _i64(mv_id).reshape(-1)
         d["summary"] = {key: _diag.summarise(d[key], mv_rows if key in ("w", "yhat") else None) for key in ("theta", "beta", "tausq", "w", "yhat")}
         out["diagnostics"] = d
+    if exc_rows is not None:
+        out["excursions"] = {key: excursion_finish(v) for key, v in exc_rows.items()}
     return out

@@ -12,6 +12,7 @@ import numpy as np
 
 from . import _lib
 from . import diagnostics as _diag
+from . import excursions as _exc
 
 
 def _f64(a):
@@ -56,6 +57,41 @@ def series_diag_finish(d, K, max_lag=0):
     """Adds ``truncated`` (the series that ran into the lag cap) to a dict of device diagnostics of K stored draws."""
     if d is not None:
         d["truncated"] = _diag.truncated(d["lags"], K, max_lag)
+    return d
+
+
+def excursion_spec(thr, side, mask, band):
+    """The st_excursion_spec of checked inputs (``thr`` (T, m) float64 or None, ``side`` (T,) int32, ``mask`` uint8 or None) and
+    the arrays it points at, which must outlive the call."""
+    keep = (thr, side, mask)
+    s = _lib.StExcursionSpec(0 if thr is None else int(thr.shape[0]), None if thr is None else _dp(thr),
+                             None if thr is None else side.ctypes.data_as(C.POINTER(C.c_int32)),
+                             None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint8)), 1 if band else 0)
+    return s, keep
+
+
+def excursion_buffers(n, T, G, K, band, want=True):
+    """(dict of the outputs of one store; the st_excursion_out pointing at them), or (None, None) without ``want``: count, prob,
+    excur (T, n) and joint_all (T, G) with T > 0; mean, sd (n), maxdev (G, K), n_flat (G) with ``band``; n_draws."""
+    if not want:
+        return None, None
+    d, o = {}, _lib.StExcursionOut()
+    if T:
+        d.update(count=np.zeros((T, n), dtype=np.int32), prob=np.zeros((T, n)), excur=np.zeros((T, n)), joint_all=np.zeros((T, G)))
+        o.count = d["count"].ctypes.data_as(C.POINTER(C.c_int32))
+        o.prob, o.excur, o.joint_all = _dp(d["prob"]), _dp(d["excur"]), _dp(d["joint_all"])
+    if band:
+        d.update(mean=np.zeros(n), sd=np.zeros(n), maxdev=np.zeros((G, K)), n_flat=np.zeros(G, dtype=np.int64))
+        o.mean, o.sd, o.maxdev = _dp(d["mean"]), _dp(d["sd"]), _dp(d["maxdev"])
+        o.n_flat = d["n_flat"].ctypes.data_as(C.POINTER(C.c_int64))
+    d["n_draws"] = np.zeros(1, dtype=np.int64)
+    o.n_draws = d["n_draws"].ctypes.data_as(C.POINTER(C.c_int64))
+    return d, o
+
+
+def excursion_finish(d):
+    if d is not None:
+        d["n_draws"] = int(d["n_draws"][0])
     return d
 
 
@@ -707,6 +743,42 @@ class SpamTreeMV:
     def functionals_diagnostics(self, max_lag=0, n_kept=None):
         """The same of the functionals' stored F_w and F_y draws; ``yhat`` None without X."""
         return self._diagnostics(self.lib.st_points_functionals_diagnostics, self.n_functionals, max_lag, self.points_have_X, n_kept)
+
+    # ---- exceedance, excursion functions and simultaneous bands of the stored draws (st_*_excursions; spamtree_amd.excursions)
+    def _excursions(self, call, n, m, G, n_kept, thresholds, side, mask, band, yhat):
+        thr = sd = None
+        if thresholds is not None:
+            thr, sd = _exc.expand_thresholds(thresholds, m, side)
+        elif not band:
+            raise ValueError("excursions: neither thresholds nor band")
+        mk = _exc.check_mask(mask, n)
+        _exc.check_keep(n_kept, band)
+        spec, keep = excursion_spec(thr, sd, mk, band)
+        T = 0 if thr is None else thr.shape[0]
+        dw, ow = excursion_buffers(n, T, G, int(n_kept), band)
+        dy, oy = excursion_buffers(n, T, G, int(n_kept), band, yhat)
+        self._check(call(self.h, C.byref(spec), C.byref(ow), C.byref(oy) if oy is not None else None))
+        del keep
+        return dict(w=excursion_finish(dw), yhat=excursion_finish(dy))
+
+    def summary_excursions(self, n_kept, thresholds=None, side=1, mask=None, band=False):
+        """Exceedance counts and probabilities, the excursion function and, with ``band``, the mean, sd and per-draw largest
+        standardised deviation of every row's stored w and yhat draws (st_summary_reserve before the saved iterations; ``n_kept``
+        of them are stored).  ``thresholds``: ``excursions.expand_thresholds`` over the q outcomes; ``mask``: n_all entries in
+        model row order, 0 = in no domain.  dict(w=dict(count, prob, excur (T, n_all), joint_all (T, q), mean, sd (n_all),
+        maxdev (q, K), n_flat (q), n_draws), yhat=the same), model row order."""
+        return self._excursions(self.lib.st_summary_excursions, self.n_all, self.q, self.q, n_kept, thresholds, side, mask, band, True)
+
+    def points_excursions(self, n_kept, thresholds=None, side=1, mask=None, band=False):
+        """The same of the point set's stored w* and yhat* draws (st_points_summary_reserve), caller order; ``yhat`` None without X."""
+        return self._excursions(self.lib.st_points_summary_excursions, self.n_points, self.q, self.q, n_kept, thresholds, side, mask,
+                                band, self.points_have_X)
+
+    def functionals_excursions(self, n_kept, thresholds=None, side=1, mask=None, band=False):
+        """The same of the functionals' stored F_w and F_y draws: one domain, a threshold value per functional (a scalar entry
+        serves all); ``yhat`` None without X."""
+        return self._excursions(self.lib.st_points_functionals_excursions, self.n_functionals, self.n_functionals, 1, n_kept, thresholds,
+                                side, mask, band, self.points_have_X)
 
     # ---- criteria over the fit's own rows (st_rows_score_*): conditional on w
     def rows_score_set(self, y_holdout=None, y=None):

@@ -17,6 +17,7 @@ from typing import Optional
 
 import numpy as np
 
+from . import excursions as _exc
 from . import fit
 from .model import SpamTreeMV, _dp, _f64, functionals_csr, joint_labels, score_values
 from .topology import Topology, _nearest_rows
@@ -106,7 +107,7 @@ def conditioning_set(topo: Topology, anchor: int) -> np.ndarray:
 
 def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, return_draws=True, device=0, z=None,
                 mode=0, force_generic=False, return_moments=False, joint=None, functionals=None, y_new=None, quantiles=(),
-                crps=True, diagnostics=False, diagnostics_max_lag=0):
+                crps=True, diagnostics=False, diagnostics_max_lag=0, excursions=None):
     """Predictive at new locations for every saved draw of a chain.
 
     ``model_inputs``: the problem as ``spamtree_mv_mcmc`` took it (the dict of ``synthetic.make_workload``; its ``topo``
@@ -139,6 +140,12 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
     ``diagnostics``: ESS, MCSE, sd and split-R-hat of every point's w* and yhat* draws (``spamtree_amd.diagnostics``), formed on
     the device after the last draw from the draws it keeps (``z`` None, ``mode`` 0; 4 .. 16384 saved draws).  The result then
     holds ``diagnostics``: dict(w, yhat) and, with ``functionals``, ``functionals["diagnostics"]``.
+
+    ``excursions=dict(thresholds=, side=, mask=, band=)``: exceedance probabilities, excursion function and band ingredients of
+    the points' w* and yhat* draws (``spamtree_amd.excursions``; ``mask`` has one entry per point), formed on the device after the
+    last draw from the draws it keeps (``z`` None, ``mode`` 0; 1 .. 16384 saved draws).  The result then holds ``excursions``:
+    dict(w, yhat) and, with ``functionals``, ``functionals["excursions"]`` (``thresholds_fun``, ``mask_fun`` as in
+    ``fit.spamtree_mv_mcmc``).
     """
     mi = model_inputs
     topo = mi["topo"]
@@ -162,6 +169,19 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
             raise ValueError(f"diagnostics need 4 .. {fit.MAX_STORED_DRAWS} saved draws (the device keeps them)")
         if int(diagnostics_max_lag) < 0:
             raise ValueError("diagnostics_max_lag must not be negative (0: the default cap)")
+    exc = None
+    if excursions is not None:
+        exc = dict(excursions)
+        if set(exc) - {"thresholds", "side", "mask", "band", "thresholds_fun", "mask_fun"}:
+            raise ValueError("excursions: unknown keys")
+        if z is not None or mode != 0:
+            raise ValueError("excursions need the device draw: z=None and mode=0")
+        if exc.get("thresholds") is None and not exc.get("band"):
+            raise ValueError("excursions: neither thresholds nor band")
+        _exc.check_keep(len(draws["w_mcmc"]), bool(exc.get("band")))
+        _exc.check_mask(exc.get("mask"), n_new)
+        if exc.get("thresholds") is not None:
+            _exc.expand_thresholds(exc["thresholds"], int(np.unique(np.asarray(mi["mv_id"])).size), exc.get("side", 1))
     qs = tuple(float(x) for x in quantiles)
     if not all(0.0 <= x <= 1.0 for x in qs):
         raise ValueError("quantiles must lie in [0, 1]")
@@ -195,7 +215,7 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
             m.set_scores(ys)
             if crps:
                 m._check(m.lib.st_points_summary_reserve(m.h, keep))
-        if diagnostics:
+        if diagnostics or exc is not None:
             m._check(m.lib.st_points_summary_reserve(m.h, keep))
         cc = []
         w_out = np.zeros((n_new, keep)) if return_draws else None
@@ -210,7 +230,7 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
             m.theta_update(0, theta[:, s])
             if not m.get_loglik_comps_w(0):
                 raise FloatingPointError(f"st_factor failed on saved draw {s} (errtype {m.last_errtype})")
-            if fun is None and ys is None and not diagnostics:
+            if fun is None and ys is None and not diagnostics and exc is None:
                 out = m.predict_points(mode=mode, z=None if z is None else z[:, s], seed=seed, it=s)
             else:
                 out = m.accumulate_points(seed=seed, it=s)
@@ -249,6 +269,12 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
             res["diagnostics"] = m.points_diagnostics(int(diagnostics_max_lag), n_kept=keep)
             if fun is not None:
                 res["functionals"]["diagnostics"] = m.functionals_diagnostics(int(diagnostics_max_lag), n_kept=keep)
+        if exc is not None and n_new:
+            kw = dict(side=exc.get("side", 1), band=bool(exc.get("band")))
+            res["excursions"] = m.points_excursions(keep, exc.get("thresholds"), mask=exc.get("mask"), **kw)
+            if fun is not None:
+                res["functionals"]["excursions"] = m.functionals_excursions(keep, exc.get("thresholds_fun", exc.get("thresholds")),
+                                                                            mask=exc.get("mask_fun"), **kw)
         if joint is not None:
             packed = np.mean(cc, axis=0) if keep else np.zeros(0)
             for k, g in enumerate(m.joint_groups):
@@ -264,7 +290,7 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
 
 
 def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), return_draws=True, joint=None, functionals=None,
-                y_new=None, crps=True, diagnostics=False, diagnostics_max_lag=0, **mcmc):
+                y_new=None, crps=True, diagnostics=False, diagnostics_max_lag=0, excursions=None, **mcmc):
     """Fit the chain and predict at new locations on every saved iteration, without replaying it.
 
     ``model_inputs``: the problem as for :func:`predict_new`.  The points are located with :func:`locate` and handed to
@@ -284,6 +310,8 @@ def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), retu
     during the fit, whatever ``return_draws`` is.  For the CRPS the device keeps ``mcmc_keep`` draws of w and yhat per point (16 B
     each per point and draw, at most 16384 draws); ``crps=False`` scores without it and stores nothing.
     With ``diagnostics`` the fit's ``diagnostics`` (``fit.spamtree_mv_mcmc``) and ``new["diagnostics"]``, ``new["functionals"]["diagnostics"]``.
+    With ``excursions`` (the dict of ``fit.spamtree_mv_mcmc``) the fit's ``excursions``, ``new["excursions"]`` and
+    ``new["functionals"]["excursions"]``.
     """
     mi = model_inputs
     coords_new = np.asarray(coords_new, dtype=np.float64).reshape(-1, 2)
@@ -316,6 +344,6 @@ def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), retu
                                mi["res_is_ref"], mi["parents"], mi["children"], bool(mi.get("limited_tree", False)),
                                mi["block_names"], mi["block_groups"], mi["indexing"],
                                new_points=points, new_draws=return_draws,
-                               new_quantiles=qs, diagnostics=diagnostics, diagnostics_max_lag=diagnostics_max_lag, **kw)
+                               new_quantiles=qs, diagnostics=diagnostics, diagnostics_max_lag=diagnostics_max_lag, excursions=excursions, **kw)
     out["new"]["anchor"] = anchor
     return out
