@@ -193,6 +193,34 @@ int stm_mcmc_excursions(const st_problem *pb, const st_options *opt, const doubl
                         double *new_cond_cov, double *new_cov, const stm_functionals *fun, const stm_scores *scores,
                         const stm_diagnostics *diag, const stm_excursions *exc);
 
+/* Rank-normalised R-hat, bulk, tail, quantile and exceedance ESS of the stored draws (include/spamtree_hip.h,
+ * st_*_rank_diagnostics).  stm_mcmc_ranked is stm_mcmc_excursions plus one stm_rank_diagnostics, every array of which is
+ * optional: with want_rows it reserves mcmc_keep draws of the rows (one reservation, shared with diag and exc when several are
+ * given), with point or functional outputs mcmc_keep draws on the point set, and after the last iteration it calls
+ * st_summary_rank_diagnostics(rows_spec), st_points_summary_rank_diagnostics(new_spec) and
+ * st_points_functionals_rank_diagnostics(fun_spec).  rows_spec and new_spec carry n_thr x q thresholds, fun_spec n_thr x n_fun.
+ * It consumes no draw of streams 0-4, 6, 7 and changes no chain state: every output stm_mcmc_excursions also produces is the same
+ * bit for bit.  Refused before the first factorisation: any rank output with mcmc_keep > 16384 (ST_ERR_UNSUPPORTED); what the
+ * st_*_rank_diagnostics calls refuse of a spec, mcmc_keep < ST_DIAG_MIN_DRAWS, row outputs without want_rows, point or functional
+ * outputs without their set, yhat outputs without X_new (ST_ERR_USAGE). */
+typedef struct stm_rank_diagnostics {
+  int32_t want_rows;
+  st_rank_spec rows_spec, new_spec, fun_spec;
+  st_rank_out rows_w, rows_yhat;   /* n_all series, model row order */
+  st_rank_out new_w, new_yhat;     /* n_new series, caller order */
+  st_rank_out fun_w, fun_yhat;     /* n_fun series */
+} stm_rank_diagnostics;
+int stm_mcmc_ranked(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
+                    int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
+                    int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc, double *beta_mcmc,
+                    double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time, int64_t n_new,
+                    const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new, const double *X_new,
+                    const int64_t *joint_id_new, int64_t keep_draws, const double *quantiles, int32_t n_quantiles, double *new_w,
+                    double *new_cond_mean, double *new_cond_var, double *new_yhat, double *new_mean, double *new_var,
+                    double *new_w_mean, double *new_yhat_mean, double *new_w_q, double *new_yhat_q, int32_t *new_route,
+                    double *new_cond_cov, double *new_cov, const stm_functionals *fun, const stm_scores *scores,
+                    const stm_diagnostics *diag, const stm_excursions *exc, const stm_rank_diagnostics *rk);
+
 /* Criteria over the fit's own rows (include/spamtree_hip.h, st_rows_score_*): WAIC and DIC over the observed rows and the scores
  * of held-out values at NA rows, conditional on w.  stm_rows_score_set: st_rows_score_set on the chain's handle; call it before the
  * first iteration.  stm_mcmc_criteria is spamtree_mv_mcmc_c plus one stm_criteria: on every saved iteration, once tausq and beta are

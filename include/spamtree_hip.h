@@ -320,6 +320,66 @@ int st_summary_excursions(st_handle h, const st_excursion_spec *spec, const st_e
 int st_points_summary_excursions(st_handle h, const st_excursion_spec *spec, const st_excursion_out *w, const st_excursion_out *yhat);
 int st_points_functionals_excursions(st_handle h, const st_excursion_spec *spec, const st_excursion_out *w, const st_excursion_out *yhat);
 
+/* ---- rank-normalised R-hat, bulk, tail, quantile and exceedance ESS of the stored draws, on the device (Vehtari, Gelman, Simpson,
+ * Carpenter, Buerkner 2021, for the one chain the stores hold).  st_*_diagnostics above gives the ESS of the MEAN and a plain
+ * split-R-hat; these say how far a quantile, a tail or an exceedance probability of the same store can be trusted.  One series is
+ * x_0 .. x_{K-1}, ST_DIAG_MIN_DRAWS <= K <= 16384; xs is its ascending sort.  "the diagnostics on a series" are ess, rhat, lags and
+ * the truncated state of st_*_diagnostics, in that definition's order of operations and with its max_lag rule (one text:
+ * spamtree_amd/csrc/diag_kernels.hpp).  The definition (spamtree_amd/csrc/rank_kernels.hpp, spamtree_amd.diagnostics.
+ * rank_series_diagnostics and tests/rank_reference.py restate it):
+ *   ranks       lo_s = #{u : x_u < x_s}, hi_s = #{u : x_u <= x_s};  r2_s = lo_s + hi_s + 1, twice the average 1-based rank, an
+ *               integer; ties share it.
+ *   scores      p_s = (4 r2_s - 3) / (8 K + 2), one double division of two exact integers (= (r - 3/8) / (K + 1/4));
+ *               z_s = Phi^-1(p_s), Phi^-1 being st_norm_quantile_f of spamtree_amd/csrc/norm_quantile.hpp (Wichura's AS 241), the
+ *               same text on the host (st_norm_quantile), on the device and in the CPU check.
+ *   bulk        rhat_bulk = the diagnostics' rhat on z;  ess_bulk, lags_bulk = their ess and lags on z.  ess_bulk is NOT split
+ *               into half chains (posterior::ess_bulk is): the split check is R-hat's job here.
+ *   folded      med = xs[(K-1)/2] for odd K, 0.5 (xs[K/2-1] + xs[K/2]) for even K;  f_s = |x_s - med|;  zf = the scores of f;
+ *               rhat_fold = the diagnostics' rhat on zf;  rhat_rank = fmax(rhat_bulk, rhat_fold) (NaN only if both are).
+ *   indicator   for a 0/1 series I with c = sum I_s: c == 0 or c == K gives ess = NaN, lags = 0.  Otherwise, in 64-bit integers,
+ *               n11_t = sum_{s<K-t} I_s I_{s+t}, head_t = sum_{s<K-t} I_s, tail_t = sum_{s>=t} I_s,
+ *               A_t = K^2 n11_t - K c (head_t + tail_t) + (K - t) c^2  (= K^2 sum (I_s - c/K)(I_{s+t} - c/K); |A_t| <= 2^42;
+ *               A_0 = K c (K - c));  rho_t = A_t / A_0.  From rho_t on, the pairs, the stop rule, the monotone rule, tau, its
+ *               floor and ess = K / tau are the diagnostics', evaluated on the integer numerators: Gamma_k = N_k / A_0 with
+ *               N_k = A_2k + A_2k+1; stop at the first !(N_k > 0); N_k <- min(N_k, N_k-1); (|N_k| <= 2^43, at most 2^13 pairs)
+ *               tau = max((double)(2 sum N_k - A_0) / (double)A_0, 1 / log10 K): one quotient of integers (2 sum N_k - A_0 can
+ *               reach 2^57, so each conversion rounds once, as does the quotient), the same on any machine and in any
+ *               reduction order.  (With every rho_t rounded to double and the pairs summed in double, a
+ *               slowly mixing indicator of 8192 draws came out 1.3e-14 from the exact rational: more than the 1e-14 its test allows.)
+ *   quantile    n_prob <= ST_RANK_MAX_PROBS probabilities strictly inside (0, 1):  j = min(max(ceil(prob K), 1), K - 1) - 1
+ *               (one multiplication, then ceil);  I_s = [x_s <= xs[j]];  ess_q[k][i] = the indicator ESS.
+ *               ess_tail = fmin(indicator ESS at 0.05, at 0.95), whatever prob holds.
+ *   exceedance  thresholds and sides as in st_excursion_spec: thr[t q + outcome] for rows and points, thr[t n_fun + i] for
+ *               functionals, side +-1 (NULL: all +1), strict inequalities, at most ST_EXC_MAX_THRESHOLDS.  I_s = E_t(s, i);
+ *               ess_exc[t][i] = its indicator ESS;  prob = c / K (bit for bit the prob of st_*_excursions on the same store);
+ *               mcse_prob = sqrt(prob (1 - prob) / ess_exc), 0 where c is 0 or K.
+ *   degenerate  a series with a NaN draw: NaN in every double output, 0 in lags_bulk.  A constant series: all ranks tied, z = 0,
+ *               gamma_0 == 0 on z and the diagnostics' degenerate outputs follow (rhat NaN, ess NaN, lags 0).
+ * The outputs of a series are bitwise a function of its K values and the spec, wherever it is stored.  Any pointer of
+ * st_rank_out may be NULL: only what is asked for is computed and copied.  ess_q: n_prob x n; ess_exc, mcse_prob, prob: n_thr x n;
+ * the others n.  Each call accepts exactly the handles its *_diagnostics sibling accepts, works on the draws stored so far, changes
+ * no state and consumes no Philox draw.  ST_ERR_USAGE with a text: fewer than ST_DIAG_MIN_DRAWS stored draws; max_lag < 0; n_prob
+ * or n_thr outside 0 .. 8; a prob not strictly inside (0, 1); a NaN or infinite threshold; a side other than +-1; ess_q without
+ * prob; ess_exc, mcse_prob or prob without thr; yhat on a point set without X.  A set of size 0: ST_OK, nothing written.  A
+ * refusal leaves the handle usable. */
+#define ST_RANK_MAX_PROBS 8
+typedef struct st_rank_spec {
+  int32_t max_lag;                                       /* 0: ST_DIAG_DEFAULT_MAX_LAG */
+  int32_t n_prob; const double *prob;
+  int32_t n_thr; const double *thr; const int32_t *side;
+} st_rank_spec;
+typedef struct st_rank_out {          /* any pointer may be NULL; only what is asked for is computed and copied */
+  double *rhat_rank, *rhat_bulk, *rhat_fold, *ess_bulk, *ess_tail;   /* n */
+  int32_t *lags_bulk;                                                /* n */
+  double *ess_q;                                                     /* n_prob x n */
+  double *ess_exc, *mcse_prob, *prob;                                /* n_thr x n */
+} st_rank_out;
+int st_summary_rank_diagnostics(st_handle h, const st_rank_spec *spec, const st_rank_out *w, const st_rank_out *yhat);
+int st_points_summary_rank_diagnostics(st_handle h, const st_rank_spec *spec, const st_rank_out *w, const st_rank_out *yhat);
+int st_points_functionals_rank_diagnostics(st_handle h, const st_rank_spec *spec, const st_rank_out *w, const st_rank_out *yhat);
+/* z[i] = Phi^-1(p[i]) by the text the device runs (norm_quantile.hpp); needs no device.  Returns ST_OK. */
+int st_norm_quantile(const double *p, double *z, int64_t n);
+
 /* ---- new-point prediction from a fitted state: the predictive at locations that are not rows of the problem, the way the model
  * treats an NA row (make_tree's missing level, predict_std spamtree_model.cpp:1234-1358) without rebuilding the tree.
  * A point of margin j anchored at block b (the block of its nearest deepest-knot-level row, same margin if cherrypick_same_margin,

@@ -40,7 +40,20 @@ class StExcursionOut(C.Structure):    # st_excursion_out: any pointer may be NUL
                 ("maxdev", C.POINTER(C.c_double)), ("n_flat", C.POINTER(C.c_int64)), ("n_draws", C.POINTER(C.c_int64))]
 
 
+class StRankSpec(C.Structure):        # include/spamtree_hip.h, st_rank_spec
+    _fields_ = [("max_lag", C.c_int32), ("n_prob", C.c_int32), ("prob", C.POINTER(C.c_double)), ("n_thr", C.c_int32),
+                ("thr", C.POINTER(C.c_double)), ("side", C.POINTER(C.c_int32))]
+
+
+class StRankOut(C.Structure):         # st_rank_out: any pointer may be NULL
+    _fields_ = [("rhat_rank", C.POINTER(C.c_double)), ("rhat_bulk", C.POINTER(C.c_double)), ("rhat_fold", C.POINTER(C.c_double)),
+                ("ess_bulk", C.POINTER(C.c_double)), ("ess_tail", C.POINTER(C.c_double)), ("lags_bulk", C.POINTER(C.c_int32)),
+                ("ess_q", C.POINTER(C.c_double)), ("ess_exc", C.POINTER(C.c_double)), ("mcse_prob", C.POINTER(C.c_double)),
+                ("prob", C.POINTER(C.c_double))]
+
+
 ST_EXC_MAX_THRESHOLDS = 8
+ST_RANK_MAX_PROBS = 8
 ST_DIAG_MIN_DRAWS = 4
 ST_DIAG_DEFAULT_MAX_LAG = 1024
 
@@ -48,6 +61,7 @@ ST_DIAG_DEFAULT_MAX_LAG = 1024
 H = C.c_void_p
 c_sdp = C.POINTER(StSeriesDiag)
 c_xsp, c_xop = C.POINTER(StExcursionSpec), C.POINTER(StExcursionOut)
+c_rsp, c_rop = C.POINTER(StRankSpec), C.POINTER(StRankOut)
 SIGNATURES = {
     "st_create": (C.c_int, [C.POINTER(StProblem), C.POINTER(StOptions), C.POINTER(H)]),
     "st_destroy": (C.c_int, [H]),
@@ -120,6 +134,10 @@ SIGNATURES = {
     "st_summary_excursions": (C.c_int, [H, c_xsp, c_xop, c_xop]),
     "st_points_summary_excursions": (C.c_int, [H, c_xsp, c_xop, c_xop]),
     "st_points_functionals_excursions": (C.c_int, [H, c_xsp, c_xop, c_xop]),
+    "st_summary_rank_diagnostics": (C.c_int, [H, c_rsp, c_rop, c_rop]),
+    "st_points_summary_rank_diagnostics": (C.c_int, [H, c_rsp, c_rop, c_rop]),
+    "st_points_functionals_rank_diagnostics": (C.c_int, [H, c_rsp, c_rop, c_rop]),
+    "st_norm_quantile": (C.c_int, [c_dp, c_dp, C.c_int64]),
     "st_comm_unique_id": (C.c_int, [C.c_void_p, C.c_int32]),
     "st_comm_init": (C.c_int, [H, C.c_void_p]),
     "st_points_set": (C.c_int, [H, C.c_int64, c_dp, c_ip, c_ip, c_dp]),
@@ -232,6 +250,15 @@ class StmExcursions(C.Structure):    # include/spamtree_fit.h, stm_excursions
 
 
 SIGNATURES["stm_mcmc_excursions"] = (C.c_int, SIGNATURES["stm_mcmc_diagnosed"][1] + [C.POINTER(StmExcursions)])
+
+
+class StmRankDiagnostics(C.Structure):    # include/spamtree_fit.h, stm_rank_diagnostics
+    _fields_ = [("want_rows", C.c_int32), ("rows_spec", StRankSpec), ("new_spec", StRankSpec), ("fun_spec", StRankSpec),
+                ("rows_w", StRankOut), ("rows_yhat", StRankOut), ("new_w", StRankOut), ("new_yhat", StRankOut),
+                ("fun_w", StRankOut), ("fun_yhat", StRankOut)]
+
+
+SIGNATURES["stm_mcmc_ranked"] = (C.c_int, SIGNATURES["stm_mcmc_excursions"][1] + [C.POINTER(StmRankDiagnostics)])
 
 SIGNATURES["stm_rows_score_set"] = (C.c_int, [H, c_dp])
 SIGNATURES["stm_mcmc_criteria"] = (C.c_int, SIGNATURES["spamtree_mv_mcmc_c"][1] + [C.POINTER(StmCriteria)])

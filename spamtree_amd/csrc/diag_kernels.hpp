@@ -40,6 +40,114 @@ struct DiagArgs {
   int *lags;
 };
 
+#ifdef __HIPCC__
+// the sum of v over the wave, in every lane: the xor butterfly with partners 8, 4, 2, 1 inside each row of 16 lanes by DPP moves
+// (st_device.hpp: group_xor_sum), then partners 16 and 32 across the rows.  a + b == b + a bit for bit, so all lanes agree.
+__device__ __forceinline__ double diag_allsum(double v) {
+  v = group_xor_sum<16>(v);
+  v += __shfl_xor(v, 16, 64);
+  v += __shfl_xor(v, 32, 64);
+  return v;
+}
+
+// LDS written by one lane of the wave and read by another: order the wave's own LDS traffic (no workgroup barrier: a series belongs
+// to one wave)
+__device__ __forceinline__ void diag_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The diagnostics of one series by one wave: x[0 .. K) (LDS, or global memory that only this wave touches) is centred in place.
+// P1 .. P4 and, with LAGS, the lag pairs, in the order of the header; every lane returns the same values.  Without LAGS only sd
+// and rhat are formed (ess = NaN, mcse = 0, pairs = 0).  k_series_diag and the rank-normalised kernel (k_rank.hip) share this text.
+struct DiagOut { double ess, mcse, sd, rhat; int pairs; };
+template <bool LAGS>
+__device__ __forceinline__ DiagOut diag_series_wave(double *x, int K, int L, int lane) {
+  const int h = K / 2;
+  const double dK = (double)K, dh = (double)h;
+  // P1, P2: the mean
+  double a = 0.0;
+  for (int s = lane; s < K; s += 64) a += x[s];
+  const double m0 = diag_allsum(a) / dK;
+  double c = 0.0;
+  for (int s = lane; s < K; s += 64) c += x[s] - m0;
+  const double m = m0 + diag_allsum(c) / dK;
+  // P3: centre in place; g0 and the half sums
+  double g0 = 0.0, b1 = 0.0, b2 = 0.0;
+  for (int s = lane; s < K; s += 64) {
+    const double d = x[s] - m;
+    x[s] = d;
+    g0 = fma(d, d, g0);
+    if (s < h) b1 += d;
+    if (s >= K - h) b2 += d;
+  }
+  g0 = diag_allsum(g0);
+  const double mu1 = diag_allsum(b1) / dh, mu2 = diag_allsum(b2) / dh;
+  diag_wave_sync();
+  // P4: the half variances
+  double v1 = 0.0, v2 = 0.0;
+  for (int s = lane; s < K; s += 64) {
+    const double d = x[s];
+    if (s < h) { const double e = d - mu1; v1 = fma(e, e, v1); }
+    if (s >= K - h) { const double e = d - mu2; v2 = fma(e, e, v2); }
+  }
+  v1 = diag_allsum(v1);
+  v2 = diag_allsum(v2);
+  const double nan = __builtin_nan("");
+  double ess = nan, mcse = 0.0, sd = 0.0, rhat = nan;
+  int pairs = 0;
+  if (g0 != 0.0) {   // (a NaN series goes through the formulas)
+    sd = sqrt(g0 / (dK - 1.0));
+    const double W = (v1 / (dh - 1.0) + v2 / (dh - 1.0)) / 2.0;
+    const double mb = (mu1 + mu2) / 2.0;
+    const double e1 = mu1 - mb, e2 = mu2 - mb;
+    const double B = dh * fma(e1, e1, e2 * e2);
+    if (W != 0.0) rhat = sqrt(((dh - 1.0) / dh * W + B / dh) / W);
+    // the lag pairs
+    const int kmax = (L - 1) / 2;
+    double tsum = 0.0, prev = __builtin_inf();
+    bool stop = !LAGS;
+    for (int k0 = 0; k0 <= kmax && !stop; k0 += DIAG_NL / 2) {
+      const int t0 = 2 * k0, len = K - t0;   // len >= 2: t0 <= L - 1 <= K - 3
+      double acc[DIAG_NL];
+#pragma unroll
+      for (int j = 0; j < DIAG_NL; ++j) acc[j] = 0.0;
+      for (int s = lane; s < len; s += 64) {
+        const double ds = x[s];
+        const double *y = x + s + t0;
+#pragma unroll
+        for (int j = 0; j < DIAG_NL; ++j)
+          if (s + j < len) acc[j] = fma(ds, y[j], acc[j]);   // s + t0 + j < K
+      }
+#pragma unroll
+      for (int j = 0; j < DIAG_NL; ++j) acc[j] = diag_allsum(acc[j]);
+#pragma unroll
+      for (int j = 0; j < DIAG_NL / 2; ++j) {
+        if (!stop && k0 + j <= kmax) {
+          double G = acc[2 * j] / g0 + acc[2 * j + 1] / g0;
+          if (!(G > 0.0)) stop = true;
+          else {
+            G = fmin(G, prev);
+            prev = G;
+            tsum += G;
+            ++pairs;
+          }
+        }
+      }
+    }
+    if (LAGS) {
+      const double tau = fmax(2.0 * tsum - 1.0, 1.0 / log10(dK));
+      ess = dK / tau;
+      mcse = sd / sqrt(ess);
+    }
+  }
+  DiagOut o;
+  o.ess = ess; o.mcse = mcse; o.sd = sd; o.rhat = rhat; o.pairs = pairs;
+  return o;
+}
+#endif
+
 // R and Kp of a store of K draws under a per-workgroup LDS limit; false: one series does not fit
 bool series_diag_plan(long long K, size_t lds_limit, int *R, int *Kp);
 int series_diag_launch(const DiagArgs &A, size_t lds_limit, hipStream_t st);

@@ -4,23 +4,6 @@
 #include "st_handle.hpp"
 #include "diag_kernels.hpp"
 
-// the sum of v over the wave, in every lane: the xor butterfly with partners 8, 4, 2, 1 inside each row of 16 lanes by DPP moves
-// (st_device.hpp: group_xor_sum), then partners 16 and 32 across the rows.  a + b == b + a bit for bit, so all lanes agree.
-__device__ __forceinline__ double diag_allsum(double v) {
-  v = group_xor_sum<16>(v);
-  v += __shfl_xor(v, 16, 64);
-  v += __shfl_xor(v, 32, 64);
-  return v;
-}
-
-// LDS written by one lane of the wave and read by another: order the wave's own LDS traffic (no workgroup barrier: a series belongs
-// to one wave)
-__device__ __forceinline__ void diag_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __global__ __launch_bounds__(DIAG_NT) void k_series_diag(DiagArgs A) {
   extern __shared__ double lds[];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, nw = blockDim.x >> 6;
@@ -31,91 +14,16 @@ __global__ __launch_bounds__(DIAG_NT) void k_series_diag(DiagArgs A) {
     if (row0 + r < A.n) lds[(size_t)r * Kp + d] = A.draws[(size_t)d * A.n + row0 + r];
   }
   __syncthreads();
-  const int h = K / 2;
-  const double dK = (double)K, dh = (double)h;
   for (int r = wid; r < R && row0 + r < A.n; r += nw) {
     double *x = lds + (size_t)r * Kp;
-    // P1, P2: the mean
-    double a = 0.0;
-    for (int s = lane; s < K; s += 64) a += x[s];
-    const double m0 = diag_allsum(a) / dK;
-    double c = 0.0;
-    for (int s = lane; s < K; s += 64) c += x[s] - m0;
-    const double m = m0 + diag_allsum(c) / dK;
-    // P3: centre in place; g0 and the half sums
-    double g0 = 0.0, b1 = 0.0, b2 = 0.0;
-    for (int s = lane; s < K; s += 64) {
-      const double d = x[s] - m;
-      x[s] = d;
-      g0 = fma(d, d, g0);
-      if (s < h) b1 += d;
-      if (s >= K - h) b2 += d;
-    }
-    g0 = diag_allsum(g0);
-    const double mu1 = diag_allsum(b1) / dh, mu2 = diag_allsum(b2) / dh;
-    diag_wave_sync();
-    // P4: the half variances
-    double v1 = 0.0, v2 = 0.0;
-    for (int s = lane; s < K; s += 64) {
-      const double d = x[s];
-      if (s < h) { const double e = d - mu1; v1 = fma(e, e, v1); }
-      if (s >= K - h) { const double e = d - mu2; v2 = fma(e, e, v2); }
-    }
-    v1 = diag_allsum(v1);
-    v2 = diag_allsum(v2);
-    const double nan = __builtin_nan("");
-    double ess = nan, mcse = 0.0, sd = 0.0, rhat = nan;
-    int pairs = 0;
-    if (g0 != 0.0) {   // (a NaN series goes through the formulas)
-      sd = sqrt(g0 / (dK - 1.0));
-      const double W = (v1 / (dh - 1.0) + v2 / (dh - 1.0)) / 2.0;
-      const double mb = (mu1 + mu2) / 2.0;
-      const double e1 = mu1 - mb, e2 = mu2 - mb;
-      const double B = dh * fma(e1, e1, e2 * e2);
-      if (W != 0.0) rhat = sqrt(((dh - 1.0) / dh * W + B / dh) / W);
-      // the lag pairs
-      const int kmax = (A.L - 1) / 2;
-      double tsum = 0.0, prev = __builtin_inf();
-      bool stop = false;
-      for (int k0 = 0; k0 <= kmax && !stop; k0 += DIAG_NL / 2) {
-        const int t0 = 2 * k0, len = K - t0;   // len >= 2: t0 <= L - 1 <= K - 3
-        double acc[DIAG_NL];
-#pragma unroll
-        for (int j = 0; j < DIAG_NL; ++j) acc[j] = 0.0;
-        for (int s = lane; s < len; s += 64) {
-          const double ds = x[s];
-          const double *y = x + s + t0;
-#pragma unroll
-          for (int j = 0; j < DIAG_NL; ++j)
-            if (s + j < len) acc[j] = fma(ds, y[j], acc[j]);   // s + t0 + j < K
-        }
-#pragma unroll
-        for (int j = 0; j < DIAG_NL; ++j) acc[j] = diag_allsum(acc[j]);
-#pragma unroll
-        for (int j = 0; j < DIAG_NL / 2; ++j) {
-          if (!stop && k0 + j <= kmax) {
-            double G = acc[2 * j] / g0 + acc[2 * j + 1] / g0;
-            if (!(G > 0.0)) stop = true;
-            else {
-              G = fmin(G, prev);
-              prev = G;
-              tsum += G;
-              ++pairs;
-            }
-          }
-        }
-      }
-      const double tau = fmax(2.0 * tsum - 1.0, 1.0 / log10(dK));
-      ess = dK / tau;
-      mcse = sd / sqrt(ess);
-    }
+    const DiagOut o = diag_series_wave<true>(x, K, A.L, lane);
     if (lane == 0) {
       const long long i = row0 + r;
-      if (A.ess) A.ess[i] = ess;
-      if (A.mcse) A.mcse[i] = mcse;
-      if (A.sd) A.sd[i] = sd;
-      if (A.rhat) A.rhat[i] = rhat;
-      if (A.lags) A.lags[i] = 2 * pairs;
+      if (A.ess) A.ess[i] = o.ess;
+      if (A.mcse) A.mcse[i] = o.mcse;
+      if (A.sd) A.sd[i] = o.sd;
+      if (A.rhat) A.rhat[i] = o.rhat;
+      if (A.lags) A.lags[i] = 2 * o.pairs;
     }
   }
 }

@@ -1,0 +1,382 @@
+// Kernel translation unit of libspamtree_hip.so: rank-normalised R-hat, bulk, tail, quantile and exceedance ESS of the stored
+// draws (rank_kernels.hpp has the evaluation order, include/spamtree_hip.h the definition).  k_series_rank reads a store of saved
+// draws and writes only its own outputs and its own global slice; it draws nothing and touches no state of the chain.
+#include "st_handle.hpp"
+#include "diag_kernels.hpp"
+#include "norm_quantile.hpp"
+#include "rank_kernels.hpp"
+
+// R rows of Kpad = 2^k doubles each in LDS (row r at lds + r Kpad), every row sorted ascending by a bitonic network over the
+// workgroup (qt_sort_rows' network).  The rows are in LDS behind a barrier on entry and sorted behind one on return.
+__device__ __forceinline__ void rank_sort_rows(double *lds, int R, int Kpad, int tid) {
+  const int half = Kpad >> 1;
+  for (int k = 2; k <= Kpad; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int p = tid; p < R * half; p += RANK_NT) {
+        const int r = p / half, i = p - r * half;
+        const int i1 = 2 * j * (i / j) + (i % j), i2 = i1 + j;
+        double *a = lds + (size_t)r * Kpad;
+        const double x = a[i1], y = a[i2];
+        const bool up = (i1 & k) == 0;
+        if ((x > y) == up) { a[i1] = y; a[i2] = x; }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// r2 = lo + hi + 1 of v among the sorted a[0 .. K): lo = #{a < v}, hi = #{a <= v}, two binary searches (indices stay in [0, K])
+__device__ __forceinline__ int rank_twice(const double *a, int K, double v) {
+  int lo = 0, n = K;
+  while (n > 0) {
+    const int half = n >> 1;
+    if (a[lo + half] < v) { lo += half + 1; n -= half + 1; }
+    else n = half;
+  }
+  int hi = lo;
+  n = K - lo;
+  while (n > 0) {
+    const int half = n >> 1;
+    if (a[hi + half] <= v) { hi += half + 1; n -= half + 1; }
+    else n = half;
+  }
+  return lo + hi + 1;
+}
+
+// the bits of a word whose draw index base + b lies below `limit`
+__device__ __forceinline__ unsigned long long rank_mask_below(int limit, int base) {
+  const int nb = limit - base;
+  return nb <= 0 ? 0ull : nb >= 64 ? ~0ull : (1ull << nb) - 1ull;
+}
+
+// The indicator ESS of the bit mask B (W = ceil(K / 64) words, bits at and beyond K clear, c bits set), by one wave; every lane
+// returns the same values.  Integers up to tau's one quotient.
+__device__ __forceinline__ double rank_indicator_ess(const unsigned long long *B, int W, int K, int c, int L, int lane, int *lags) {
+  *lags = 0;
+  if (c == 0 || c == K) return __builtin_nan("");
+  const long long Kl = K, cl = c;
+  const long long A0 = Kl * cl * (Kl - cl);
+  const double dK = (double)K;
+  const int kmax = (L - 1) / 2, tmax = 2 * kmax + 1;   // tmax <= L <= K - 2
+  long long nsum = 0, prev = 0x7fffffffffffffffll;     // the pairs' numerators: |N_k| <= 2^43, at most 2^13 of them
+  int pairs = 0;
+  bool stop = false;
+  for (int t0 = 0; t0 <= tmax && !stop; t0 += 64) {
+    const int t = t0 + lane;
+    long long At = 0;
+    if (t <= tmax) {
+      const int q = t >> 6, sh = t & 63;
+      int n11 = 0, first = 0, last = 0;
+      for (int w = 0; w < W; ++w) {
+        const unsigned long long b = B[w];
+        const unsigned long long u0 = w + q < W ? B[w + q] : 0ull, u1 = w + q + 1 < W ? B[w + q + 1] : 0ull;
+        const unsigned long long shifted = sh ? (u0 >> sh) | (u1 << (64 - sh)) : u0;   // bit s: I_{s + t}
+        n11 += __popcll(b & shifted);
+        first += __popcll(b & rank_mask_below(t, 64 * w));
+        last += __popcll(b & ~rank_mask_below(K - t, 64 * w));
+      }
+      const long long head = c - last, tail = c - first;
+      At = Kl * Kl * n11 - Kl * cl * (head + tail) + (Kl - t) * cl * cl;
+    }
+    for (int j = 0; j < 32 && !stop && t0 / 2 + j <= kmax; ++j) {
+      const long long a0 = __shfl(At, 2 * j, 64), a1 = __shfl(At, 2 * j + 1, 64);
+      long long N = a0 + a1;   // Gamma_k = N / A_0
+      if (!(N > 0)) stop = true;
+      else {
+        N = N < prev ? N : prev;
+        prev = N;
+        nsum += N;
+        ++pairs;
+      }
+    }
+  }
+  const double tau = fmax((double)(2 * nsum - A0) / (double)A0, 1.0 / log10(dK));
+  *lags = 2 * pairs;
+  return dK / tau;
+}
+
+// steps 3 and 4 / 5 for the rows of one tile: the scores of v_s (x_s, or |x_s - med_r| with FOLD) among the sorted S_r into Z_r,
+// then one wave per series over Z_r (LDS rows or rows of the global slice: each call site is inlined with its own address space).
+// Returns through s_out[r] (LDS), written by lane 0.
+template <bool FOLD>
+__device__ __forceinline__ void rank_scores_and_moments(const RankArgs &A, const double *S, double *Z, const double *X, int nr,
+                                                        const double *s_med, const int *s_nan, DiagOut *s_out, int tid) {
+  const int K = A.K, lane = tid & 63, wid = tid >> 6;
+  for (int idx = tid; idx < nr * K; idx += RANK_NT) {
+    const int r = idx / K, s = idx - r * K;
+    if (s_nan[r]) continue;
+    double v = X[(size_t)r * K + s];
+    if (FOLD) v = fabs(v - s_med[r]);
+    Z[(size_t)r * A.Kz + s] = st_rank_score(rank_twice(S + (size_t)r * A.Kpad, K, v), K);
+  }
+  __syncthreads();
+  for (int r = wid; r < nr; r += RANK_NT / 64) {
+    if (s_nan[r]) continue;
+    const DiagOut o = diag_series_wave<!FOLD>(Z + (size_t)r * A.Kz, K, A.L, lane);
+    if (lane == 0) s_out[r] = o;
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(RANK_NT) void k_series_rank(RankArgs A) {
+  extern __shared__ double lds[];
+  __shared__ double s_med[RANK_MAX_R], s_cq[RANK_MAX_R][RANK_NQ];
+  __shared__ int s_nan[RANK_MAX_R];
+  __shared__ DiagOut s_bulk[RANK_MAX_R], s_fold[RANK_MAX_R];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int K = A.K, Kpad = A.Kpad, R = A.R, W = (K + 63) >> 6;
+  double *S = lds, *Zl = lds + (size_t)R * Kpad;
+  double *X = A.scratch + (size_t)blockIdx.x * A.slice, *Zg = X + (size_t)R * K;
+  const double inf = __builtin_inf(), nan = __builtin_nan("");
+  const int nquant = A.n_prob + (A.want_tail ? 2 : 0), nind = nquant + A.n_thr;
+  const bool need_sort = A.want_bulk || A.want_fold || nquant > 0;
+  const long long ntiles = (A.n + R - 1) / R;
+  for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const long long row0 = tile * R;
+    const int nr = (int)(A.n - row0 < R ? A.n - row0 : R);
+    if (tid < RANK_MAX_R) s_nan[tid] = 0;
+    __syncthreads();
+    // 1: stage
+    for (int idx = tid; idx < R * Kpad; idx += RANK_NT) {
+      const int d = idx / R, r = idx - d * R;   // R consecutive series of one draw: contiguous in memory
+      double v = inf;
+      if (d < K && r < nr) {
+        v = A.draws[(size_t)d * A.n + row0 + r];
+        X[(size_t)r * K + d] = v;
+        if (v != v) s_nan[r] = 1;   // (every writer stores the same value)
+      }
+      S[(size_t)r * Kpad + d] = v;
+    }
+    __syncthreads();
+    // 2: sort; the median and the quantile thresholds (exceedances alone need neither: they read X)
+    if (need_sort) rank_sort_rows(S, R, Kpad, tid);
+    if (need_sort && tid < 16 * nr) {
+      const int r = tid >> 4, k = tid & 15;
+      const double *a = S + (size_t)r * Kpad;
+      if (k == 15) s_med[r] = (K & 1) ? a[(K - 1) / 2] : 0.5 * (a[K / 2 - 1] + a[K / 2]);
+      else if (k < RANK_NQ) {
+        const int which = k < A.n_prob ? k : k - A.n_prob + ST_RANK_MAX_PROBS;   // the caller's, then the tails
+        if (k < nquant) s_cq[r][k] = a[A.jq[which]];
+      }
+    }
+    __syncthreads();
+    // 3, 4: bulk
+    if (A.want_bulk) {
+      if (A.z_global) rank_scores_and_moments<false>(A, S, Zg, X, nr, s_med, s_nan, s_bulk, tid);
+      else rank_scores_and_moments<false>(A, S, Zl, X, nr, s_med, s_nan, s_bulk, tid);
+    }
+    // 5: folded
+    if (A.want_fold) {
+      for (int idx = tid; idx < R * Kpad; idx += RANK_NT) {
+        const int r = idx / Kpad, s = idx - r * Kpad;
+        S[idx] = (s < K && r < nr) ? fabs(X[(size_t)r * K + s] - s_med[r]) : inf;
+      }
+      __syncthreads();
+      rank_sort_rows(S, R, Kpad, tid);
+      if (A.z_global) rank_scores_and_moments<true>(A, S, Zg, X, nr, s_med, s_nan, s_fold, tid);
+      else rank_scores_and_moments<true>(A, S, Zl, X, nr, s_med, s_nan, s_fold, tid);
+    }
+    if (tid < nr) {
+      const long long i = row0 + tid;
+      const bool bad = s_nan[tid] != 0;
+      const double rb = bad || !A.want_bulk ? nan : s_bulk[tid].rhat, rf = bad || !A.want_fold ? nan : s_fold[tid].rhat;
+      if (A.rhat_bulk) A.rhat_bulk[i] = rb;
+      if (A.ess_bulk) A.ess_bulk[i] = bad ? nan : s_bulk[tid].ess;
+      if (A.lags_bulk) A.lags_bulk[i] = bad ? 0 : 2 * s_bulk[tid].pairs;
+      if (A.rhat_fold) A.rhat_fold[i] = rf;
+      if (A.rhat_rank) A.rhat_rank[i] = fmax(rb, rf);
+    }
+    // 6: the indicators, one wave per series; the masks go where the sorted copy was
+    if (nind > 0) {
+      __syncthreads();
+      for (int r = wid; r < nr; r += RANK_NT / 64) {
+        const long long i = row0 + r;
+        const bool bad = s_nan[r] != 0;
+        unsigned long long *B = (unsigned long long *)(S + (size_t)r * Kpad);   // W <= Kpad words
+        const double *x = X + (size_t)r * K;
+        double e05 = nan;
+        for (int v = 0; v < nind; ++v) {
+          const int t = v - nquant;   // >= 0: an exceedance
+          int mode = 0;               // 0: x <= c;  1: x > c;  2: x < c
+          double c;
+          if (t < 0) c = s_cq[r][v];
+          else {
+            c = A.thr[(size_t)t * A.thr_stride + (A.per_series ? i : (A.outcome ? A.outcome[i] : 0))];
+            mode = (A.neg >> t) & 1u ? 2 : 1;
+          }
+          double ess = nan;
+          int cnt = 0, lags = 0;
+          if (!bad) {
+            for (int base = 0; base < K; base += 64) {
+              const int s = base + lane;
+              bool p = false;
+              if (s < K) {
+                const double xv = x[s];
+                p = mode == 0 ? xv <= c : mode == 1 ? xv > c : xv < c;
+              }
+              const unsigned long long word = __ballot(p);
+              if (lane == 0) B[base >> 6] = word;
+              cnt += __popcll(word);
+            }
+            diag_wave_sync();
+            ess = rank_indicator_ess(B, W, K, cnt, A.L, lane, &lags);
+            diag_wave_sync();   // the next indicator overwrites the mask
+          }
+          if (v == A.n_prob && t < 0) e05 = ess;
+          if (lane == 0) {
+            if (v < A.n_prob) { if (A.ess_q) A.ess_q[(size_t)v * A.n + i] = ess; }
+            else if (t < 0) { if (v == A.n_prob + 1 && A.ess_tail) A.ess_tail[i] = fmin(e05, ess); }
+            else {
+              const double pr = bad ? nan : (double)cnt / (double)K;
+              if (A.ess_exc) A.ess_exc[(size_t)t * A.n + i] = ess;
+              if (A.prob) A.prob[(size_t)t * A.n + i] = pr;
+              if (A.mcse_prob) A.mcse_prob[(size_t)t * A.n + i] = bad ? nan : (cnt == 0 || cnt == K) ? 0.0 : sqrt(pr * (1.0 - pr) / ess);
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();   // the next tile restages X and S
+  }
+}
+
+// ---- host side
+int series_rank_order(double prob, long long K) {
+  const long long c = (long long)std::ceil(prob * (double)K);
+  return (int)(std::min(std::max(c, 1ll), K - 1) - 1);
+}
+
+bool series_rank_plan(long long K, size_t lds_limit, int *R, int *Kpad, int *Kz, int *z_global) {
+  size_t kpad = 2;
+  while ((long long)kpad < K) kpad <<= 1;
+  const size_t kz = (size_t)(K | 1), lim = lds_limit > RANK_LDS_STATIC ? lds_limit - RANK_LDS_STATIC : 0;
+  *Kpad = (int)kpad; *Kz = (int)kz;
+  for (int zg = K > RANK_LDS_Z_MAX_K ? 1 : 0; zg < 2; ++zg) {   // z in LDS where it fits beside the sorted copy, else in the slice
+    const size_t per = (kpad + (zg ? 0 : kz)) * sizeof(double);
+    size_t r = std::min<size_t>(lim, RANK_TILE) / per;
+    if (r < 1) r = lim / per;   // a long series: what the device allows
+    if (r >= 1) { *R = (int)std::min<size_t>(r, RANK_MAX_R); *z_global = zg; return true; }
+  }
+  return false;
+}
+
+static bool rank_q_out(const st_rank_out *o) { return o && o->ess_q; }
+static bool rank_exc_out(const st_rank_out *o) { return o && (o->ess_exc || o->mcse_prob || o->prob); }
+
+int rank_check_spec(st_handle_s *h, const char *who, const st_rank_spec *spec, long long K, long long n_thr_values,
+                    const st_rank_out *w, const st_rank_out *yhat) {
+  const std::string W = std::string(who) + ": ";
+  if (!spec) { h->err = W + "no spec"; return ST_ERR_USAGE; }
+  if (spec->max_lag < 0) { h->err = W + "max_lag must not be negative (0: the default cap)"; return ST_ERR_USAGE; }
+  if (spec->n_prob < 0 || spec->n_prob > ST_RANK_MAX_PROBS) {
+    h->err = W + "n_prob = " + std::to_string(spec->n_prob) + " must lie in 0 .. " + std::to_string(ST_RANK_MAX_PROBS);
+    return ST_ERR_USAGE;
+  }
+  if (spec->n_thr < 0 || spec->n_thr > ST_EXC_MAX_THRESHOLDS) {
+    h->err = W + "n_thr = " + std::to_string(spec->n_thr) + " must lie in 0 .. " + std::to_string(ST_EXC_MAX_THRESHOLDS);
+    return ST_ERR_USAGE;
+  }
+  if (spec->n_prob > 0 && !spec->prob) { h->err = W + "n_prob = " + std::to_string(spec->n_prob) + " without prob"; return ST_ERR_USAGE; }
+  if (spec->n_thr > 0 && !spec->thr) { h->err = W + "n_thr = " + std::to_string(spec->n_thr) + " without thr"; return ST_ERR_USAGE; }
+  for (int k = 0; k < spec->n_prob; ++k)
+    if (!(spec->prob[k] > 0.0 && spec->prob[k] < 1.0)) { h->err = W + "prob " + std::to_string(k) + " must lie strictly inside (0, 1)"; return ST_ERR_USAGE; }
+  for (long long k = 0; k < (long long)spec->n_thr * n_thr_values; ++k)
+    if (!std::isfinite(spec->thr[k])) { h->err = W + "threshold " + std::to_string(k) + " is not finite"; return ST_ERR_USAGE; }
+  for (int t = 0; spec->side && t < spec->n_thr; ++t)
+    if (spec->side[t] != 1 && spec->side[t] != -1) { h->err = W + "side " + std::to_string(t) + " must be +1 or -1"; return ST_ERR_USAGE; }
+  if (spec->n_prob == 0 && (rank_q_out(w) || rank_q_out(yhat))) { h->err = W + "ess_q needs prob"; return ST_ERR_USAGE; }
+  if (spec->n_thr == 0 && (rank_exc_out(w) || rank_exc_out(yhat))) { h->err = W + "ess_exc, mcse_prob and prob need thresholds"; return ST_ERR_USAGE; }
+  if (K < ST_DIAG_MIN_DRAWS) {
+    h->err = W + std::to_string(K) + " draws stored, the diagnostics need at least " + std::to_string(ST_DIAG_MIN_DRAWS) +
+             " (reserve room before the saved iterations)";
+    return ST_ERR_USAGE;
+  }
+  return ST_OK;
+}
+
+int series_rank_store(st_handle_s *h, const char *who, const double *draws, long long n, long long K, const int *d_outcome, int G,
+                      bool thr_per_series, const long long *perm, const st_rank_spec *spec, const st_rank_out *out) {
+  if (!out || n <= 0) return ST_OK;
+  const bool bulk = out->rhat_rank || out->rhat_bulk || out->ess_bulk || out->lags_bulk, fold = out->rhat_rank || out->rhat_fold;
+  const int n_prob = out->ess_q ? spec->n_prob : 0, n_thr = rank_exc_out(out) ? spec->n_thr : 0;
+  if (!bulk && !fold && !out->ess_tail && !n_prob && !n_thr) return ST_OK;
+  RankArgs A = {};
+  A.draws = draws; A.n = n; A.K = (int)K;
+  A.L = (int)std::min<long long>(spec->max_lag == 0 ? ST_DIAG_DEFAULT_MAX_LAG : spec->max_lag, K - 2);
+  if (!series_rank_plan(K, h->lds_limit, &A.R, &A.Kpad, &A.Kz, &A.z_global)) {
+    h->err = std::string(who) + ": the sorted copy of " + std::to_string(K) + " stored draws of one series does not fit one workgroup's LDS";
+    return ST_ERR_UNSUPPORTED;
+  }
+  A.want_bulk = bulk; A.want_fold = fold; A.n_prob = n_prob; A.want_tail = out->ess_tail ? 1 : 0; A.n_thr = n_thr;
+  for (int k = 0; k < n_prob; ++k) A.jq[k] = series_rank_order(spec->prob[k], K);
+  A.jq[ST_RANK_MAX_PROBS] = series_rank_order(0.05, K);
+  A.jq[ST_RANK_MAX_PROBS + 1] = series_rank_order(0.95, K);
+  A.outcome = d_outcome; A.per_series = thr_per_series ? 1 : 0; A.thr_stride = thr_per_series ? n : G;
+  HCHK(h, hipSetDevice(h->device));
+  DevBuf<double> d_thr, d_scr, d_out;
+  DevBuf<int> d_lags;
+  if (n_thr) {   // the thresholds in store order
+    std::vector<double> tv((size_t)n_thr * A.thr_stride);
+    for (int t = 0; t < n_thr; ++t) {
+      for (long long j = 0; j < A.thr_stride; ++j)
+        tv[(size_t)t * A.thr_stride + j] = spec->thr[(size_t)t * A.thr_stride + ((thr_per_series && perm) ? perm[j] : j)];
+      if (spec->side && spec->side[t] < 0) A.neg |= 1u << t;
+    }
+    HCHK(h, d_thr.upload(tv));
+    A.thr = d_thr.p;
+  }
+  // the grid and its global slices
+  A.slice = (long long)A.R * K + (A.z_global ? (long long)A.R * A.Kz : 0);
+  const long long ntiles = (n + A.R - 1) / A.R;
+  const long long by_bytes = std::max<long long>(1, RANK_SCRATCH_BYTES / (A.slice * (long long)sizeof(double)));
+  const long long grid = std::min<long long>(ntiles, std::min<long long>(RANK_MAX_WGS, by_bytes));
+  HCHK(h, d_scr.alloc((size_t)grid * A.slice));
+  A.scratch = d_scr.p;
+  // the outputs, device side: the five per-series doubles, ess_q, the three exceedance arrays
+  const size_t n_dbl = (size_t)(5 + n_prob + 3 * n_thr) * n;
+  HCHK(h, d_out.alloc(n_dbl));
+  HCHK(h, d_lags.alloc((size_t)n));
+  double *p = d_out.p;
+  const auto take = [&](bool want, size_t rows) { double *q = want ? p : nullptr; p += rows * n; return q; };
+  A.rhat_rank = take(out->rhat_rank, 1); A.rhat_bulk = take(out->rhat_bulk, 1); A.rhat_fold = take(out->rhat_fold, 1);
+  A.ess_bulk = take(out->ess_bulk, 1); A.ess_tail = take(out->ess_tail, 1);
+  A.ess_q = take(n_prob > 0, n_prob);
+  A.ess_exc = take(n_thr && out->ess_exc, n_thr); A.mcse_prob = take(n_thr && out->mcse_prob, n_thr); A.prob = take(n_thr && out->prob, n_thr);
+  A.lags_bulk = out->lags_bulk ? d_lags.p : nullptr;
+  {
+    ProfScope pscope(h, 3);
+    const size_t lds = ((size_t)A.R * A.Kpad + (A.z_global ? 0 : (size_t)A.R * A.Kz)) * sizeof(double);
+    HCHK(h, hipFuncSetAttribute((const void *)k_series_rank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // (beside RANK_LDS_STATIC)
+    hipLaunchKernelGGL(k_series_rank, dim3((unsigned)grid), dim3(RANK_NT), lds, h->stream, A);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { h->err = std::string(who) + " launch: " + hipGetErrorString(e); return ST_ERR_HIP; }
+  }
+  // only what the caller asked for comes to the host
+  struct Part { double *dst; const double *src; int rows; };
+  const Part parts[] = {{out->rhat_rank, A.rhat_rank, 1}, {out->rhat_bulk, A.rhat_bulk, 1}, {out->rhat_fold, A.rhat_fold, 1},
+                        {out->ess_bulk, A.ess_bulk, 1}, {out->ess_tail, A.ess_tail, 1}, {out->ess_q, A.ess_q, n_prob},
+                        {out->ess_exc, A.ess_exc, n_thr}, {out->mcse_prob, A.mcse_prob, n_thr}, {out->prob, A.prob, n_thr}};
+  std::vector<std::vector<double>> tmp(sizeof(parts) / sizeof(parts[0]));
+  std::vector<int> tl(out->lags_bulk ? (size_t)n : 0);
+  for (size_t k = 0; k < tmp.size(); ++k) {
+    if (!parts[k].dst || !parts[k].src || parts[k].rows == 0) continue;
+    tmp[k].resize((size_t)parts[k].rows * n);
+    HCHK(h, hipMemcpyAsync(tmp[k].data(), parts[k].src, tmp[k].size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  if (out->lags_bulk) HCHK(h, hipMemcpyAsync(tl.data(), d_lags.p, tl.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  for (size_t k = 0; k < tmp.size(); ++k) {
+    if (tmp[k].empty()) continue;
+    for (int row = 0; row < parts[k].rows; ++row)
+      for (long long i = 0; i < n; ++i) parts[k].dst[(size_t)row * n + (perm ? perm[i] : i)] = tmp[k][(size_t)row * n + i];
+  }
+  if (out->lags_bulk)
+    for (long long i = 0; i < n; ++i) out->lags_bulk[perm ? perm[i] : i] = tl[i];
+  return ST_OK;
+}
+
+extern "C" int st_norm_quantile(const double *p, double *z, int64_t n) {
+  if (n > 0 && (!p || !z)) return ST_ERR_USAGE;
+  for (int64_t i = 0; i < n; ++i) z[i] = st_norm_quantile_f(p[i]);
+  return ST_OK;
+}

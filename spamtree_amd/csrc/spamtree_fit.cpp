@@ -597,9 +597,24 @@ static int exc_spec_refused(const st_excursion_spec &sp, int64_t nvals, const st
   return 0;
 }
 
+static bool rank_any(const st_rank_out &o) {
+  return o.rhat_rank || o.rhat_bulk || o.rhat_fold || o.ess_bulk || o.ess_tail || o.lags_bulk || o.ess_q || o.ess_exc || o.mcse_prob || o.prob;
+}
+// what st_*_rank_diagnostics would refuse of a spec after the chain, found before it: nvals thresholds per t
+static int rank_spec_refused(const st_rank_spec &sp, int64_t nvals, const st_rank_out &w, const st_rank_out &y) {
+  if (sp.max_lag < 0 || sp.n_prob < 0 || sp.n_prob > ST_RANK_MAX_PROBS || sp.n_thr < 0 || sp.n_thr > ST_EXC_MAX_THRESHOLDS) return ST_ERR_USAGE;
+  if ((sp.n_prob > 0 && !sp.prob) || (sp.n_thr > 0 && !sp.thr)) return ST_ERR_USAGE;
+  for (int k = 0; k < sp.n_prob; ++k) if (!(sp.prob[k] > 0.0 && sp.prob[k] < 1.0)) return ST_ERR_USAGE;
+  for (int64_t k = 0; k < (int64_t)sp.n_thr * nvals; ++k) if (!std::isfinite(sp.thr[k])) return ST_ERR_USAGE;
+  for (int t = 0; sp.side && t < sp.n_thr; ++t) if (sp.side[t] != 1 && sp.side[t] != -1) return ST_ERR_USAGE;
+  if (sp.n_prob == 0 && (w.ess_q || y.ess_q)) return ST_ERR_USAGE;
+  if (sp.n_thr == 0 && (w.ess_exc || w.mcse_prob || w.prob || y.ess_exc || y.mcse_prob || y.prob)) return ST_ERR_USAGE;
+  return 0;
+}
+
 // fun NULL: stm_mcmc_points_joint itself; scores NULL: stm_mcmc_functionals itself; diag NULL: stm_mcmc_scored itself; exc NULL:
-// stm_mcmc_diagnosed itself
-extern "C" int stm_mcmc_excursions(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
+// stm_mcmc_diagnosed itself; rk NULL: stm_mcmc_excursions itself
+extern "C" int stm_mcmc_ranked(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
                                     int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
                                     int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
                                     double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
@@ -609,9 +624,9 @@ extern "C" int stm_mcmc_excursions(const st_problem *pb, const st_options *opt, 
                                     double *new_mean, double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q,
                                     double *new_yhat_q, int32_t *new_route, double *new_cond_cov, double *new_cov,
                                     const stm_functionals *fun, const stm_scores *scores, const stm_diagnostics *diag,
-                                    const stm_excursions *exc) {
+                                    const stm_excursions *exc, const stm_rank_diagnostics *rk) {
   if (fun && fun->n_fun <= 0) fun = nullptr;
-  const bool plain = (diag || exc) && n_new == 0 && !coords_new && !mv_new && !anchor_new;   // the plain chain (with diag only: stm_mcmc_scored handles an empty set as before)
+  const bool plain = (diag || exc || rk) && n_new == 0 && !coords_new && !mv_new && !anchor_new;   // the plain chain (with diag only: stm_mcmc_scored handles an empty set as before)
   const bool d_rows = diag && diag->want_rows && (diag_any(diag->rows_w) || diag_any(diag->rows_yhat));
   const bool d_new = diag && !plain && (diag_any(diag->new_w) || diag_any(diag->new_yhat));
   const bool d_fun = diag && fun && (diag_any(diag->fun_w) || diag_any(diag->fun_yhat));
@@ -639,7 +654,22 @@ extern "C" int stm_mcmc_excursions(const st_problem *pb, const st_options *opt, 
     if (e_fun) if (const int r = exc_spec_refused(exc->fun_spec, fun->n_fun, exc->fun_w, exc->fun_yhat, mcmc_keep)) return r;
     if (e_new || e_fun) keep_draws = std::max<int64_t>(keep_draws, mcmc_keep);
   }
-  const bool store_rows = d_rows || e_rows;   // one reservation serves both
+  const bool r_rows = rk && rk->want_rows && (rank_any(rk->rows_w) || rank_any(rk->rows_yhat));
+  const bool r_new = rk && !plain && (rank_any(rk->new_w) || rank_any(rk->new_yhat));
+  const bool r_fun = rk && fun && (rank_any(rk->fun_w) || rank_any(rk->fun_yhat));
+  if (rk && !rk->want_rows && (rank_any(rk->rows_w) || rank_any(rk->rows_yhat))) return ST_ERR_USAGE;
+  if (rk && plain && (rank_any(rk->new_w) || rank_any(rk->new_yhat))) return ST_ERR_USAGE;
+  if (rk && !fun && (rank_any(rk->fun_w) || rank_any(rk->fun_yhat))) return ST_ERR_USAGE;
+  if ((r_new && rank_any(rk->new_yhat) && !X_new) || (r_fun && rank_any(rk->fun_yhat) && !X_new)) return ST_ERR_USAGE;
+  if (r_rows || r_new || r_fun) {
+    if (mcmc_keep > 16384) return ST_ERR_UNSUPPORTED;   // the stores' limit
+    if (mcmc_keep < ST_DIAG_MIN_DRAWS) return ST_ERR_USAGE;
+    if (r_rows) if (const int r = rank_spec_refused(rk->rows_spec, pb->q, rk->rows_w, rk->rows_yhat)) return r;
+    if (r_new) if (const int r = rank_spec_refused(rk->new_spec, pb->q, rk->new_w, rk->new_yhat)) return r;
+    if (r_fun) if (const int r = rank_spec_refused(rk->fun_spec, fun->n_fun, rk->fun_w, rk->fun_yhat)) return r;
+    if (r_new || r_fun) keep_draws = std::max<int64_t>(keep_draws, mcmc_keep);
+  }
+  const bool store_rows = d_rows || e_rows || r_rows;   // one reservation serves all three
   if (plain && (fun || (scores && scores->y_new) || joint_id_new || X_new || n_quantiles != 0)) return ST_ERR_USAGE;
   if (scores && !scores->y_new) scores = nullptr;
   if (scores && (!X_new || (scores->lpd_joint && !joint_id_new) || (scores->crps && keep_draws < 1))) return ST_ERR_USAGE;
@@ -675,6 +705,7 @@ extern "C" int stm_mcmc_excursions(const st_problem *pb, const st_options *opt, 
   if (plain) {   // the diagnostics and excursions of the rows are all a plain chain can ask for
     if (rc == 0 && d_rows) rc = st_summary_diagnostics(c->h, diag->max_lag, &diag->rows_w, &diag->rows_yhat);
     if (rc == 0 && e_rows) rc = st_summary_excursions(c->h, &exc->rows_spec, &exc->rows_w, &exc->rows_yhat);
+    if (rc == 0 && r_rows) rc = st_summary_rank_diagnostics(c->h, &rk->rows_spec, &rk->rows_w, &rk->rows_yhat);
     if (rc) c->err = st_last_error(c->h);
     stm_destroy(c);
     return rc;
@@ -710,8 +741,30 @@ extern "C" int stm_mcmc_excursions(const st_problem *pb, const st_options *opt, 
     rc = st_points_summary_excursions(c->h, &exc->new_spec, &exc->new_w, exc_any(exc->new_yhat) ? &exc->new_yhat : nullptr);
   if (rc == 0 && e_fun)
     rc = st_points_functionals_excursions(c->h, &exc->fun_spec, &exc->fun_w, exc_any(exc->fun_yhat) ? &exc->fun_yhat : nullptr);
+  if (rc == 0 && r_rows) rc = st_summary_rank_diagnostics(c->h, &rk->rows_spec, &rk->rows_w, &rk->rows_yhat);
+  if (rc == 0 && r_new)
+    rc = st_points_summary_rank_diagnostics(c->h, &rk->new_spec, &rk->new_w, rank_any(rk->new_yhat) ? &rk->new_yhat : nullptr);
+  if (rc == 0 && r_fun)
+    rc = st_points_functionals_rank_diagnostics(c->h, &rk->fun_spec, &rk->fun_w, rank_any(rk->fun_yhat) ? &rk->fun_yhat : nullptr);
   stm_destroy(c);
   return rc;
+}
+
+extern "C" int stm_mcmc_excursions(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
+                                    int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
+                                    int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
+                                    double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
+                                    int64_t n_new, const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new,
+                                    const double *X_new, const int64_t *joint_id_new, int64_t keep_draws, const double *quantiles,
+                                    int32_t n_quantiles, double *new_w, double *new_cond_mean, double *new_cond_var, double *new_yhat,
+                                    double *new_mean, double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q,
+                                    double *new_yhat_q, int32_t *new_route, double *new_cond_cov, double *new_cov,
+                                    const stm_functionals *fun, const stm_scores *scores, const stm_diagnostics *diag,
+                                    const stm_excursions *exc) {
+  return stm_mcmc_ranked(pb, opt, set_unif_bounds, theta, ntheta, beta, tausq, mcmcsd, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc,
+                         yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time, n_new, coords_new, mv_new, anchor_new, X_new,
+                         joint_id_new, keep_draws, quantiles, n_quantiles, new_w, new_cond_mean, new_cond_var, new_yhat, new_mean, new_var,
+                         new_w_mean, new_yhat_mean, new_w_q, new_yhat_q, new_route, new_cond_cov, new_cov, fun, scores, diag, exc, nullptr);
 }
 
 extern "C" int stm_mcmc_diagnosed(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,

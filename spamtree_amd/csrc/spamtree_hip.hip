@@ -28,6 +28,7 @@
 #include "misc_kernels.hpp"
 #include "diag_kernels.hpp"
 #include "excursion_kernels.hpp"
+#include "rank_kernels.hpp"
 #include "rows_score.hpp"
 #include <new>
 
@@ -1643,6 +1644,14 @@ extern "C" int st_summary_excursions(st_handle h, const st_excursion_spec *spec,
   if (const int rc = exc_check_spec(h, "st_summary_excursions", spec, h->n_draws, h->q, w, yhat)) return rc;
   if (const int rc = store_excursions(h, "st_summary_excursions", h->d_draws_w.p, h->n_all, h->n_draws, h->d_mv.p, h->q, false, h->dev2model.data(), spec, w)) return rc;
   return store_excursions(h, "st_summary_excursions", h->d_draws_yhat.p, h->n_all, h->n_draws, h->d_mv.p, h->q, false, h->dev2model.data(), spec, yhat);
+}
+// rank-normalised R-hat, bulk, tail, quantile and exceedance ESS of every row's stored draws (rank_kernels.hpp): k_series_rank over
+// each requested store; the thresholds go by outcome (d_mv, device order), the outputs come back in model row order
+extern "C" int st_summary_rank_diagnostics(st_handle h, const st_rank_spec *spec, const st_rank_out *w, const st_rank_out *yhat) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = rank_check_spec(h, "st_summary_rank_diagnostics", spec, h->n_draws, h->q, w, yhat)) return rc;
+  if (const int rc = series_rank_store(h, "st_summary_rank_diagnostics", h->d_draws_w.p, h->n_all, h->n_draws, h->d_mv.p, h->q, false, h->dev2model.data(), spec, w)) return rc;
+  return series_rank_store(h, "st_summary_rank_diagnostics", h->d_draws_yhat.p, h->n_all, h->n_draws, h->d_mv.p, h->q, false, h->dev2model.data(), spec, yhat);
 }
 extern "C" int st_summary_get(st_handle h, double *w_mean, double *yhat_mean, int64_t *n_accumulated) {
   if (!h) return ST_ERR_USAGE;

@@ -10,6 +10,7 @@
 #include "misc_kernels.hpp"
 #include "diag_kernels.hpp"
 #include "excursion_kernels.hpp"
+#include "rank_kernels.hpp"
 #include "points_layout.hpp"
 #include "points_score.hpp"
 
@@ -560,6 +561,17 @@ extern "C" int st_points_summary_excursions(st_handle h, const st_excursion_spec
   return store_excursions(h, "st_points_summary_excursions", ps->d_keep_yhat.p, ps->n, ps->n_kept, ps->d_pmv.p, h->q, false, nullptr, spec, yhat);
 }
 
+extern "C" int st_points_summary_rank_diagnostics(st_handle h, const st_rank_spec *spec, const st_rank_out *w, const st_rank_out *yhat) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_summary_rank_diagnostics")) return rc;
+  PointSet *ps = h->pts;
+  if (ps->n == 0) return ST_OK;
+  if (const int rc = rank_check_spec(h, "st_points_summary_rank_diagnostics", spec, ps->n_kept, h->q, w, yhat)) return rc;
+  if (yhat && !ps->has_X) { h->err = "st_points_summary_rank_diagnostics: yhat needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  if (const int rc = series_rank_store(h, "st_points_summary_rank_diagnostics", ps->d_keep_w.p, ps->n, ps->n_kept, ps->d_pmv.p, h->q, false, nullptr, spec, w)) return rc;
+  return series_rank_store(h, "st_points_summary_rank_diagnostics", ps->d_keep_yhat.p, ps->n, ps->n_kept, ps->d_pmv.p, h->q, false, nullptr, spec, yhat);
+}
+
 // ---- linear functionals of the predictions (points_fun.hpp): the term lists come from functionals_layout, without a device call
 extern "C" int st_points_functionals_set(st_handle h, int64_t n_fun, const int64_t *ptr, const int64_t *idx, const double *wt) {
   if (!h) return ST_ERR_USAGE;
@@ -685,6 +697,18 @@ extern "C" int st_points_functionals_excursions(st_handle h, const st_excursion_
   if (yhat && !ps->has_X) { h->err = "st_points_functionals_excursions: yhat needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
   if (const int rc = store_excursions(h, "st_points_functionals_excursions", fs->d_keep_w.p, fs->n_fun, fs->n_kept, nullptr, 1, true, nullptr, spec, w)) return rc;
   return store_excursions(h, "st_points_functionals_excursions", fs->d_keep_yhat.p, fs->n_fun, fs->n_kept, nullptr, 1, true, nullptr, spec, yhat);
+}
+
+extern "C" int st_points_functionals_rank_diagnostics(st_handle h, const st_rank_spec *spec, const st_rank_out *w, const st_rank_out *yhat) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = fun_refuse(h, "st_points_functionals_rank_diagnostics", false)) return rc;
+  const PointSet *ps = h->pts;
+  FunSet *fs = ps->fun.get();
+  if (fs->n_fun == 0 || ps->n == 0) return ST_OK;   // (the functionals of an empty point set store no draw)
+  if (const int rc = rank_check_spec(h, "st_points_functionals_rank_diagnostics", spec, fs->n_kept, fs->n_fun, w, yhat)) return rc;
+  if (yhat && !ps->has_X) { h->err = "st_points_functionals_rank_diagnostics: yhat needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  if (const int rc = series_rank_store(h, "st_points_functionals_rank_diagnostics", fs->d_keep_w.p, fs->n_fun, fs->n_kept, nullptr, 1, true, nullptr, spec, w)) return rc;
+  return series_rank_store(h, "st_points_functionals_rank_diagnostics", fs->d_keep_yhat.p, fs->n_fun, fs->n_kept, nullptr, 1, true, nullptr, spec, yhat);
 }
 
 // ---- scores of held-out observations at the point set (points_score.hpp)

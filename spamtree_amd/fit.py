@@ -11,7 +11,8 @@ from . import _lib
 from . import diagnostics as _diag
 from . import excursions as _exc
 from .model import (SpamTreeError, _dp, _f64, _i64, _ip, _lists_to_csr, functionals_csr, joint_labels, rows_criteria, rows_holdout, score_totals,
-                    score_values, series_diag_buffers, series_diag_finish, excursion_spec, excursion_buffers, excursion_finish)
+                    score_values, series_diag_buffers, series_diag_finish, excursion_spec, excursion_buffers, excursion_finish,
+                    rank_spec, rank_buffers, rank_finish)
 
 
 def _problem(y, X, coords, mv_id, res_is_ref, parents, children, block_names, block_groups, indexing):
@@ -242,7 +243,8 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                      main_verbose=True, verbose=False, debug=False, printall=False, sample_beta=True, sample_tausq=True,
                      sample_theta=True, sample_w=True, sample_predicts=True, seed=2021, device=0, reference_quirks=True,
                      new_points=None, new_draws=True, new_quantiles=(), save_w=True, save_yhat=True, force_generic=False,
-                     criteria=False, y_holdout=None, holdout_crps=True, diagnostics=False, diagnostics_max_lag=0, excursions=None):
+                     criteria=False, y_holdout=None, holdout_crps=True, diagnostics=False, diagnostics_max_lag=0, excursions=None,
+                     rank_diagnostics=None):
     """spamtree_fit.cpp:5-430 through the C++ driver.  `num_threads`, `use_alg`, the verbosity flags and `start_w` are
     accepted and ignored exactly where the reference ignores them (start_w, :95) or where they do not apply to a GPU.
 
@@ -299,8 +301,33 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     (``mask_new`` masks the points) and ``new["functionals"]["excursions"]`` (``thresholds_fun``: entries scalar or one value per
     functional, default ``thresholds`` when all its entries are scalars; ``mask_fun``).  May be combined with ``diagnostics``, not
     with ``criteria`` / ``y_holdout``.  ValueError before any device call: bad shapes, more than 8 thresholds, non-finite
-    thresholds, ``mcmc_keep`` outside 1 .. 16384 (2 with ``band``)."""
+    thresholds, ``mcmc_keep`` outside 1 .. 16384 (2 with ``band``).
+
+    ``rank_diagnostics=True`` or ``dict(probs=, thresholds=, sides=, max_lag=, thresholds_fun=)``: rank-normalised R-hat, bulk and
+    tail ESS, the ESS of the quantiles ``probs`` and of the exceedances of ``thresholds`` with their probability and its MCSE
+    (``spamtree_amd.diagnostics`` has the definition), formed on the device after the last iteration from ``mcmc_keep`` draws of w
+    and yhat it keeps per row (stm_mcmc_ranked: the chain is the same bit for bit).  The result holds ``rank_diagnostics``:
+    ``theta``, ``beta``, ``tausq`` from ``diagnostics.chains_rank_diagnostics`` on the saved scalar chains (host; ``probs`` only: the
+    thresholds are the field's), ``w`` and ``yhat`` per row from the device, and ``summary`` (``diagnostics.summarise_rank``, by
+    outcome for the rows); with ``new_points`` also ``new["rank_diagnostics"]`` and ``new["functionals"]["rank_diagnostics"]``
+    (``thresholds_fun``: entries scalar or one value per functional, default ``thresholds``).  May be combined with
+    ``diagnostics`` and ``excursions``, not with ``criteria`` / ``y_holdout``.  ValueError before any device call: what the calls
+    refuse of a spec, bad shapes, ``mcmc_keep`` outside 4 .. 16384."""
     crit = bool(criteria) or y_holdout is not None
+    rank = None
+    if rank_diagnostics is not None and rank_diagnostics is not False:
+        rank = {} if rank_diagnostics is True else dict(rank_diagnostics)
+        unknown = set(rank) - {"probs", "thresholds", "sides", "max_lag", "thresholds_fun"}
+        if unknown:
+            raise ValueError(f"rank_diagnostics: unknown keys {sorted(unknown)}")
+        if crit:
+            raise ValueError("rank_diagnostics and criteria / y_holdout are separate drivers (stm_mcmc_ranked, stm_mcmc_criteria): one per call")
+        if not _diag.MIN_DRAWS <= int(mcmc_keep) <= _diag.MAX_DRAWS:
+            raise ValueError(f"rank_diagnostics: mcmc_keep = {int(mcmc_keep)} must lie in {_diag.MIN_DRAWS} .. {_diag.MAX_DRAWS} "
+                             "(the series' length, and the draws the device keeps per row)")
+        rank["max_lag"] = int(rank.get("max_lag", 0))
+        rank["probs"], rank["thresholds"], rank["sides"] = _diag.check_rank_spec(rank.get("probs", ()), rank.get("thresholds", ()),
+                                                                                  rank.get("sides"), rank["max_lag"])
     exc = None
     if excursions is not None:
         exc = dict(excursions)
@@ -364,6 +391,17 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                 exc["spec_fun"] = excursion_spec(thr_f, sides_f, _exc.check_mask(exc.get("mask_fun"), nf_), exc["band"])
         elif any(exc.get(key) is not None for key in ("mask_new", "thresholds_fun", "mask_fun")):
             raise ValueError("excursions: mask_new, thresholds_fun and mask_fun need new_points")
+    if rank is not None:   # the shapes, still before any device call
+        q_out = int(np.unique(_i64(mv_id)).size)
+        rank["spec_rows"] = rank_spec(rank["probs"], rank["thresholds"], rank["sides"], rank["max_lag"], q_out)
+        if new_points is not None:
+            rank["spec_new"] = rank_spec(rank["probs"], rank["thresholds"], rank["sides"], rank["max_lag"], q_out)
+            if pts[6] is not None:
+                tf = rank.get("thresholds_fun")
+                tf, sf = (rank["thresholds"], rank["sides"]) if tf is None else _diag.check_rank_spec((), tf, rank["sides"], 0)[1:]
+                rank["spec_fun"] = rank_spec(rank["probs"], tf, sf, rank["max_lag"], pts[6][0].size - 1)
+        elif rank.get("thresholds_fun") is not None:
+            raise ValueError("rank_diagnostics: thresholds_fun needs new_points")
     lib = _lib.load()
     pb, keep, n, p, q = _problem(y, X, coords, mv_id, res_is_ref, parents, children, layer_names, layer_gibbs_group, indexing)
     theta = _f64(theta)
@@ -398,6 +436,15 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
         xy, xs.rows_yhat = excursion_buffers(n, exc["T"], q, int(mcmc_keep), exc["band"])
         exc_rows = dict(w=xw, yhat=xy)
     dsp = C.byref(ds) if ds is not None else None
+    xsp = C.byref(xs) if xs is not None else None
+    rank_rows = rank_new = rank_fun = rs = None
+    if rank is not None:  # stm_mcmc_ranked: stm_mcmc_excursions plus the rank diagnostics of the rows, points and functionals
+        rs = _lib.StmRankDiagnostics()
+        rs.want_rows = 1
+        rs.rows_spec, _, n_prob_r, n_thr_r = rank["spec_rows"]
+        rw, rs.rows_w = rank_buffers(n, n_prob_r, n_thr_r)
+        ry, rs.rows_yhat = rank_buffers(n, n_prob_r, n_thr_r)
+        rank_rows = dict(w=rw, yhat=ry)
     if crit:
         rows = {key: np.zeros(n) for key in ("lppd", "p_waic", "mean_ll", "mu_mean", "pit")}
         rows["crps"] = np.zeros(n) if (want_crps and mcmc_keep > 0) else None
@@ -412,6 +459,12 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                             totals=rows_criteria(tobs, theld, n_obs, n_held, have_crps=rows["crps"] is not None))
         elif rc not in (0, -10):
             err = SpamTreeError(f"stm_mcmc_criteria failed ({rc})")
+            err.code = rc
+            raise err
+    elif new_points is None and rank is not None:   # the plain chain through the ranked driver: no point argument
+        rc = lib.stm_mcmc_ranked(*common, 0, None, None, None, None, None, 0, None, 0, *([None] * 15), dsp, xsp, C.byref(rs))
+        if rc not in (0, -10):
+            err = SpamTreeError(f"stm_mcmc_ranked failed ({rc})")
             err.code = rc
             raise err
     elif new_points is None and exc is not None:   # the plain chain through the excursions driver: no point argument
@@ -495,6 +548,23 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                 if o_fy is not None:
                     xs.fun_yhat = o_fy
                 exc_fun = dict(w=xfw, yhat=xfy)
+        if rank is not None:
+            rs.new_spec, _, n_prob_r, n_thr_r = rank["spec_new"]
+            rnw, rs.new_w = rank_buffers(n_new, n_prob_r, n_thr_r)
+            rny, o_rny = rank_buffers(n_new, n_prob_r, n_thr_r, pX is not None)
+            if o_rny is not None:
+                rs.new_yhat = o_rny
+            rank_new = dict(w=rnw, yhat=rny)
+            if fun is not None:
+                rs.fun_spec, _, n_prob_f, n_thr_f = rank["spec_fun"]
+                rfw, rs.fun_w = rank_buffers(nf, n_prob_f, n_thr_f)
+                rfy, o_rfy = rank_buffers(nf, n_prob_f, n_thr_f, pX is not None)
+                if o_rfy is not None:
+                    rs.fun_yhat = o_rfy
+                rank_fun = dict(w=rfw, yhat=rfy)
+            rc = lib.stm_mcmc_ranked(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), _ip(labels) if labels is not None else None,
+                                     *tail, dp(ccov), dp(cov), fsp, C.byref(ss) if ss is not None else None, dsp, xsp, C.byref(rs))
+        elif exc is not None:
             rc = lib.stm_mcmc_excursions(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), _ip(labels) if labels is not None else None,
                                          *tail, dp(ccov), dp(cov), fsp, C.byref(ss) if ss is not None else None,
                                          C.byref(ds) if ds is not None else None, C.byref(xs))
@@ -544,6 +614,10 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                 new["excursions"] = {key: excursion_finish(v) for key, v in exc_new.items()}
             if exc_fun is not None and n_new > 0:
                 new["functionals"]["excursions"] = {key: excursion_finish(v) for key, v in exc_fun.items()}
+            if rank_new is not None and n_new > 0:
+                new["rank_diagnostics"] = {key: rank_finish(v, mcmc_keep, rank["max_lag"]) for key, v in rank_new.items()}
+            if rank_fun is not None and n_new > 0:
+                new["functionals"]["rank_diagnostics"] = {key: rank_finish(v, mcmc_keep, rank["max_lag"]) for key, v in rank_fun.items()}
     if rc == -10:
         raise FloatingPointError("At nan loglik: error.")
     if rc != 0 and new_points is not None:
@@ -574,4 +648,11 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
         out["diagnostics"] = d
     if exc_rows is not None:
         out["excursions"] = {key: excursion_finish(v) for key, v in exc_rows.items()}
+    if rank_rows is not None:
+        host = lambda a: _diag.chains_rank_diagnostics(a, probs=rank["probs"], max_lag=rank["max_lag"])   # noqa: E731
+        r = dict(theta=host(theta_mcmc), beta=host(np.transpose(beta_mcmc, (0, 2, 1))), tausq=host(tausq_mcmc),
+                 w=rank_finish(rank_rows["w"], mcmc_keep, rank["max_lag"]), yhat=rank_finish(rank_rows["yhat"], mcmc_keep, rank["max_lag"]))
+        mv_rows = _i64(mv_id).reshape(-1)
+        r["summary"] = {key: _diag.summarise_rank(r[key], mv_rows if key in ("w", "yhat") else None) for key in ("theta", "beta", "tausq", "w", "yhat")}
+        out["rank_diagnostics"] = r
     return out

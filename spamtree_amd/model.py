@@ -95,6 +95,42 @@ def excursion_finish(d):
     return d
 
 
+def rank_spec(probs, thresholds, sides, max_lag, m):
+    """The st_rank_spec of ``probs`` (at most 8, strictly inside (0, 1)), ``thresholds`` (at most 8 entries, each a scalar or m
+    values: ``excursions.expand_thresholds``) and ``sides``, checked (ValueError), and the arrays it points at, which must
+    outlive the call: (spec, keep, n_prob, n_thr)."""
+    pr, th, sd = _diag.check_rank_spec(probs, thresholds, 1 if sides is None else sides, max_lag)
+    prob = np.ascontiguousarray(pr, dtype=np.float64)
+    thr = side = None
+    if th:
+        thr, side = _exc.expand_thresholds(th, m, sd)
+    s = _lib.StRankSpec(int(max_lag), prob.size, _dp(prob) if prob.size else None, 0 if thr is None else int(thr.shape[0]),
+                        None if thr is None else _dp(thr), None if thr is None else side.ctypes.data_as(C.POINTER(C.c_int32)))
+    return s, (prob, thr, side), prob.size, 0 if thr is None else int(thr.shape[0])
+
+
+def rank_buffers(n, n_prob, n_thr, want=True):
+    """(dict of the outputs of one store; the st_rank_out pointing at them), or (None, None) without ``want``: rhat_rank,
+    rhat_bulk, rhat_fold, ess_bulk, ess_tail, lags_bulk (n); ess_q (n_prob, n); ess_exc, mcse_prob, prob (n_thr, n)."""
+    if not want:
+        return None, None
+    d = {k: np.zeros(n) for k in ("rhat_rank", "rhat_bulk", "rhat_fold", "ess_bulk", "ess_tail")}
+    d["lags_bulk"] = np.zeros(n, dtype=np.int32)
+    d["ess_q"] = np.zeros((n_prob, n))
+    d.update({k: np.zeros((n_thr, n)) for k in ("ess_exc", "mcse_prob", "prob")})
+    o = _lib.StRankOut(_dp(d["rhat_rank"]), _dp(d["rhat_bulk"]), _dp(d["rhat_fold"]), _dp(d["ess_bulk"]), _dp(d["ess_tail"]),
+                       d["lags_bulk"].ctypes.data_as(C.POINTER(C.c_int32)), _dp(d["ess_q"]) if n_prob else None,
+                       _dp(d["ess_exc"]) if n_thr else None, _dp(d["mcse_prob"]) if n_thr else None, _dp(d["prob"]) if n_thr else None)
+    return d, o
+
+
+def rank_finish(d, K, max_lag=0):
+    """Adds ``truncated`` (the series whose bulk pairs ran into the lag cap) to a dict of device rank diagnostics of K draws."""
+    if d is not None:
+        d["truncated"] = _diag.truncated(d["lags_bulk"], K, max_lag)
+    return d
+
+
 POINTS_MAX_JOINT = 16   # include/spamtree_hip.h: ST_POINTS_MAX_JOINT
 
 
@@ -743,6 +779,38 @@ class SpamTreeMV:
     def functionals_diagnostics(self, max_lag=0, n_kept=None):
         """The same of the functionals' stored F_w and F_y draws; ``yhat`` None without X."""
         return self._diagnostics(self.lib.st_points_functionals_diagnostics, self.n_functionals, max_lag, self.points_have_X, n_kept)
+
+    # ---- rank-normalised R-hat, bulk / tail / quantile / exceedance ESS of the stored draws (st_*_rank_diagnostics)
+    def _rank_diagnostics(self, call, n, m, probs, thresholds, sides, max_lag, yhat, n_kept):
+        spec, keep, n_prob, n_thr = rank_spec(probs, thresholds, sides, max_lag, m)
+        dw, ow = rank_buffers(n, n_prob, n_thr)
+        dy, oy = rank_buffers(n, n_prob, n_thr, yhat)
+        self._check(call(self.h, C.byref(spec), C.byref(ow), C.byref(oy) if oy is not None else None))
+        del keep
+        if n_kept is not None:
+            rank_finish(dw, n_kept, max_lag)
+            rank_finish(dy, n_kept, max_lag)
+        return dict(w=dw, yhat=dy)
+
+    def summary_rank_diagnostics(self, probs=(), thresholds=(), sides=None, max_lag=0, n_kept=None):
+        """Rank-normalised R-hat (bulk, folded, their maximum), bulk and tail ESS, the ESS of the quantiles ``probs`` and of the
+        exceedances of ``thresholds`` (a scalar or q values each, ``sides`` +1 / -1) with their probability and its MCSE, of every
+        row's stored w and yhat draws (st_summary_reserve before the saved iterations): dict(w=dict(rhat_rank, rhat_bulk,
+        rhat_fold, ess_bulk, ess_tail, lags_bulk (n_all), ess_q (n_prob, n_all), ess_exc, mcse_prob, prob (n_thr, n_all)),
+        yhat=the same), model row order.  With ``n_kept`` each also holds ``truncated``."""
+        return self._rank_diagnostics(self.lib.st_summary_rank_diagnostics, self.n_all, self.q, probs, thresholds, sides, max_lag,
+                                      True, n_kept)
+
+    def points_rank_diagnostics(self, probs=(), thresholds=(), sides=None, max_lag=0, n_kept=None):
+        """The same of the point set's stored w* and yhat* draws, in the caller's order; ``yhat`` None without X."""
+        return self._rank_diagnostics(self.lib.st_points_summary_rank_diagnostics, self.n_points, self.q, probs, thresholds, sides,
+                                      max_lag, self.points_have_X, n_kept)
+
+    def functionals_rank_diagnostics(self, probs=(), thresholds=(), sides=None, max_lag=0, n_kept=None):
+        """The same of the functionals' stored F_w and F_y draws: a threshold value per functional (a scalar entry serves all);
+        ``yhat`` None without X."""
+        return self._rank_diagnostics(self.lib.st_points_functionals_rank_diagnostics, self.n_functionals, self.n_functionals,
+                                      probs, thresholds, sides, max_lag, self.points_have_X, n_kept)
 
     # ---- exceedance, excursion functions and simultaneous bands of the stored draws (st_*_excursions; spamtree_amd.excursions)
     def _excursions(self, call, n, m, G, n_kept, thresholds, side, mask, band, yhat):

@@ -107,7 +107,7 @@ def conditioning_set(topo: Topology, anchor: int) -> np.ndarray:
 
 def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, return_draws=True, device=0, z=None,
                 mode=0, force_generic=False, return_moments=False, joint=None, functionals=None, y_new=None, quantiles=(),
-                crps=True, diagnostics=False, diagnostics_max_lag=0, excursions=None):
+                crps=True, diagnostics=False, diagnostics_max_lag=0, excursions=None, rank_diagnostics=None):
     """Predictive at new locations for every saved draw of a chain.
 
     ``model_inputs``: the problem as ``spamtree_mv_mcmc`` took it (the dict of ``synthetic.make_workload``; its ``topo``
@@ -146,6 +146,11 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
     last draw from the draws it keeps (``z`` None, ``mode`` 0; 1 .. 16384 saved draws).  The result then holds ``excursions``:
     dict(w, yhat) and, with ``functionals``, ``functionals["excursions"]`` (``thresholds_fun``, ``mask_fun`` as in
     ``fit.spamtree_mv_mcmc``).
+
+    ``rank_diagnostics=True | dict(probs=, thresholds=, sides=, max_lag=, thresholds_fun=)``: rank-normalised R-hat, bulk, tail,
+    quantile and exceedance ESS of the points' w* and yhat* draws (``spamtree_amd.diagnostics``), formed on the device after the
+    last draw from the draws it keeps (``z`` None, ``mode`` 0; 4 .. 16384 saved draws).  The result then holds
+    ``rank_diagnostics``: dict(w, yhat) and, with ``functionals``, ``functionals["rank_diagnostics"]``.
     """
     mi = model_inputs
     topo = mi["topo"]
@@ -182,6 +187,19 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
         _exc.check_mask(exc.get("mask"), n_new)
         if exc.get("thresholds") is not None:
             _exc.expand_thresholds(exc["thresholds"], int(np.unique(np.asarray(mi["mv_id"])).size), exc.get("side", 1))
+    rank = None
+    if rank_diagnostics is not None and rank_diagnostics is not False:   # fit.spamtree_mv_mcmc's argument, for the points
+        from . import diagnostics as _diag
+        rank = {} if rank_diagnostics is True else dict(rank_diagnostics)
+        if set(rank) - {"probs", "thresholds", "sides", "max_lag", "thresholds_fun"}:
+            raise ValueError("rank_diagnostics: unknown keys")
+        if z is not None or mode != 0:
+            raise ValueError("rank_diagnostics need the device draw: z=None and mode=0")
+        if not 4 <= len(draws["w_mcmc"]) <= fit.MAX_STORED_DRAWS:
+            raise ValueError(f"rank_diagnostics need 4 .. {fit.MAX_STORED_DRAWS} saved draws (the device keeps them)")
+        rank["max_lag"] = int(rank.get("max_lag", 0))
+        rank["probs"], rank["thresholds"], rank["sides"] = _diag.check_rank_spec(rank.get("probs", ()), rank.get("thresholds", ()),
+                                                                                  rank.get("sides"), rank["max_lag"])
     qs = tuple(float(x) for x in quantiles)
     if not all(0.0 <= x <= 1.0 for x in qs):
         raise ValueError("quantiles must lie in [0, 1]")
@@ -215,7 +233,7 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
             m.set_scores(ys)
             if crps:
                 m._check(m.lib.st_points_summary_reserve(m.h, keep))
-        if diagnostics or exc is not None:
+        if diagnostics or exc is not None or rank is not None:
             m._check(m.lib.st_points_summary_reserve(m.h, keep))
         cc = []
         w_out = np.zeros((n_new, keep)) if return_draws else None
@@ -230,7 +248,7 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
             m.theta_update(0, theta[:, s])
             if not m.get_loglik_comps_w(0):
                 raise FloatingPointError(f"st_factor failed on saved draw {s} (errtype {m.last_errtype})")
-            if fun is None and ys is None and not diagnostics and exc is None:
+            if fun is None and ys is None and not diagnostics and exc is None and rank is None:
                 out = m.predict_points(mode=mode, z=None if z is None else z[:, s], seed=seed, it=s)
             else:
                 out = m.accumulate_points(seed=seed, it=s)
@@ -275,6 +293,12 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
             if fun is not None:
                 res["functionals"]["excursions"] = m.functionals_excursions(keep, exc.get("thresholds_fun", exc.get("thresholds")),
                                                                             mask=exc.get("mask_fun"), **kw)
+        if rank is not None and n_new:
+            kw = dict(probs=rank["probs"], sides=rank["sides"], max_lag=rank["max_lag"], n_kept=keep)
+            res["rank_diagnostics"] = m.points_rank_diagnostics(thresholds=rank["thresholds"], **kw)
+            if fun is not None:
+                tf = rank.get("thresholds_fun")
+                res["functionals"]["rank_diagnostics"] = m.functionals_rank_diagnostics(thresholds=rank["thresholds"] if tf is None else tf, **kw)
         if joint is not None:
             packed = np.mean(cc, axis=0) if keep else np.zeros(0)
             for k, g in enumerate(m.joint_groups):
@@ -290,7 +314,7 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
 
 
 def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), return_draws=True, joint=None, functionals=None,
-                y_new=None, crps=True, diagnostics=False, diagnostics_max_lag=0, excursions=None, **mcmc):
+                y_new=None, crps=True, diagnostics=False, diagnostics_max_lag=0, excursions=None, rank_diagnostics=None, **mcmc):
     """Fit the chain and predict at new locations on every saved iteration, without replaying it.
 
     ``model_inputs``: the problem as for :func:`predict_new`.  The points are located with :func:`locate` and handed to
@@ -312,6 +336,8 @@ def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), retu
     With ``diagnostics`` the fit's ``diagnostics`` (``fit.spamtree_mv_mcmc``) and ``new["diagnostics"]``, ``new["functionals"]["diagnostics"]``.
     With ``excursions`` (the dict of ``fit.spamtree_mv_mcmc``) the fit's ``excursions``, ``new["excursions"]`` and
     ``new["functionals"]["excursions"]``.
+    With ``rank_diagnostics`` (True or the dict of ``fit.spamtree_mv_mcmc``) the fit's ``rank_diagnostics``,
+    ``new["rank_diagnostics"]`` and ``new["functionals"]["rank_diagnostics"]``.
     """
     mi = model_inputs
     coords_new = np.asarray(coords_new, dtype=np.float64).reshape(-1, 2)
@@ -344,6 +370,7 @@ def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), retu
                                mi["res_is_ref"], mi["parents"], mi["children"], bool(mi.get("limited_tree", False)),
                                mi["block_names"], mi["block_groups"], mi["indexing"],
                                new_points=points, new_draws=return_draws,
-                               new_quantiles=qs, diagnostics=diagnostics, diagnostics_max_lag=diagnostics_max_lag, excursions=excursions, **kw)
+                               new_quantiles=qs, diagnostics=diagnostics, diagnostics_max_lag=diagnostics_max_lag, excursions=excursions,
+                               rank_diagnostics=rank_diagnostics, **kw)
     out["new"]["anchor"] = anchor
     return out
