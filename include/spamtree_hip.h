@@ -90,6 +90,10 @@ int st_get_w(st_handle h, double *w);
 int st_set_beta(st_handle h, const double *Bcoeff);        /* p x q column-major; recomputes XB (spamtree_model.cpp:127, 1382) */
 int st_set_tausq_inv(st_handle h, const double *tausq_inv);/* q (spamtree_model.cpp:118, 1405-1407) */
 int st_get_xb(st_handle h, double *xb);                    /* n_all */
+/* inspection: the whitened residuals e = Ri (w_u - H_u w_pa) of the reference blocks, as the last st_factor / st_factor_local /
+ * st_factor_enqueue (either slot) stored them for the leaf levels below; n = n_all, model row order, 0 at other rows.
+ * limited_tree: chol(K_uu)^{-1} w_u of the blocks that have children. */
+int st_get_resid(st_handle h, double *out, int64_t n);
 
 /* ---- phase A: theta_update + get_loglik_comps_w(data) (spamtree_model.cpp:834-998, 1420-1422).
  * slot 0 = param_data, 1 = alter_data.  Returns 0 (the reference's `true`) or 1/2/3 (`false`, errtype);

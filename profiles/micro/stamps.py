@@ -20,7 +20,7 @@ from spamtree_amd.synthetic import make_workload  # noqa: E402
 
 NAMES = {0: "topology+coords", 1: "covariance", 2: "private ancestor step", 3: "panel barrier wait", 4: "panel compute (MFMA)",
          5: "DMA wait + pad", 6: "DMA issue", 7: "cholesky", 8: "N = -Ri T + store", 9: "final barrier", 10: "hv", 11: "R / leaf outputs",
-         12: "Ri out + e2", 13: "scalars", 14: "g = Linv w (shared step)", 15: "g = Linv w (private)"}
+         12: "Ri out + e2", 13: "scalars"}
 
 side = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
 q = int(sys.argv[2]) if len(sys.argv) > 2 else 1

@@ -71,6 +71,7 @@ SIGNATURES = {
     "st_set_beta": (C.c_int, [H, c_dp]),
     "st_set_tausq_inv": (C.c_int, [H, c_dp]),
     "st_get_xb": (C.c_int, [H, c_dp]),
+    "st_get_resid": (C.c_int, [H, c_dp, C.c_int64]),
     "st_factor": (C.c_int, [H, C.c_int, c_dp, C.c_int, c_dp]),
     "st_factor_begin": (C.c_int, [H, C.c_int, c_dp, C.c_int]),
     "st_factor_ahead_levels": (C.c_int, [H]),

@@ -331,6 +331,7 @@ __global__ __launch_bounds__(BM_NT, 2) void k_factor_bigmfma(FactorArgs A, CovPa
         for (int j = 0; j <= i; ++j) acc += Ril[i * m + j] * (wv[P + j] - hv[j]);
         wcore_part += acc * acc;
         logdet_part += log(Ril[i * m + i]);
+        if (A.resid) A.resid[B.row0 + i] = acc;
       }
     } else {
       // non-reference level: rows conditionally independent (spamtree_model.cpp:923-963).  sum_k V[k][i]^2 in four

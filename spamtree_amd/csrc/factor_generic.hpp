@@ -15,6 +15,7 @@ struct FactorArgs {
   const double *z;      // predict: normals (device order)
   double *panels;       // slot arena
   double *logdet_c, *loglik_c;
+  double *resid;        // reference blocks: the whitened residuals e = Ri (w_u - H_u w_pa) at the block's device rows (nullptr: not stored)
   int *errflag;         // atomicMin(level*16 + code)
   double *scratch;      // BIG
   long long scratch_stride;
@@ -36,6 +37,8 @@ struct MarginalArgs {
   double *panels;
   int *errflag;
   int maxM;
+  const double *w;   // with resid: g = chol(K_uu)^{-1} w_u, what the block's children take as the g of their chain, goes to ...
+  double *resid;     // ... the block's device rows (nullptr: not stored)
 };
 
 #ifdef ST_DEFS_FACTOR_GENERIC
@@ -71,6 +74,12 @@ __global__ __launch_bounds__(NT) void k_marginal_invchol(MarginalArgs A, CovPar 
       const int i = idx / m, j = idx - i * m;
       out[idx] = (j <= i) ? Li[idx] : 0.0;
     }
+    if (A.resid)
+      for (int i = tid; i < m; i += NT) {
+        double acc = 0.0;
+        for (int j = 0; j <= i; ++j) acc += Li[i * m + j] * A.w[B.row0 + j];
+        A.resid[B.row0 + i] = acc;
+      }
     if (tid == 0 && s_fail) atomicMin(A.errflag, B.level * 16 + 2);   // errtype 2 (:919), reported at the block's level
     __syncthreads();
   }
@@ -104,6 +113,11 @@ __global__ __launch_bounds__(NT) void k_marginal_invchol_wave(MarginalArgs A, Co
     for (int idx = lane; idx < m * m; idx += 64) {
       const int i = idx / m, j = idx - i * m;
       out[idx] = (j <= i) ? Li[i * CH_LD + j] : 0.0;
+    }
+    if (A.resid && lane < m) {
+      double acc = 0.0;
+      for (int j = 0; j <= lane; ++j) acc += Li[lane * CH_LD + j] * A.w[B.row0 + j];
+      A.resid[B.row0 + lane] = acc;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (lane == 0 && s_failw[wid]) atomicMin(A.errflag, B.level * 16 + 2);   // errtype 2 (:919), reported at the block's level
@@ -261,6 +275,7 @@ __global__ __launch_bounds__(NT) void k_factor(FactorArgs A, CovPar cp) {
         for (int j = 0; j <= i; ++j) acc += Ri[i * m + j] * (wv[P + j] - hv[j]);
         wcore_part += acc * acc;
         logdet_part += log(Ri[i * m + i]);
+        if (A.resid) A.resid[B.row0 + i] = acc;
       }
     } else {
       // non-reference level: rows conditionally independent (spamtree_model.cpp:923-963)

@@ -776,6 +776,7 @@ __global__ __launch_bounds__(BM_NT) void k_factor_ref_finish(FactorArgs A, CovPa
       for (int j = 0; j <= i; ++j) acc += Ril[i * m + j] * (wv[j] - hv[j]);
       wcore_part += acc * acc;
       logdet_part += log(Ril[i * m + i]);
+      if (A.resid) A.resid[B.row0 + i] = acc;
     }
     const double wcore = block_sum(wcore_part, s_red);
     const double logdet = block_sum(logdet_part, s_red);

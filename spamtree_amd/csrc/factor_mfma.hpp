@@ -13,6 +13,7 @@ struct FastArgs {
   const double *w;
   double *panels;
   double *logdet_c, *loglik_c;
+  double *resid;   // reference groups: the whitened residuals e = Ri (w_u - H_u w_pa) at the block's device rows (nullptr: not stored)
   int *errflag;
   const long long *gdesc;   // group descriptors of this launch's first group onwards
   int gd_stride;
@@ -335,6 +336,7 @@ __global__ __launch_bounds__(NT, 2) void k_factor_mfma(FastArgs A, CovPar cp) {
       for (int j = 0; j <= i; ++j) e += Ri[i * CH_LD + j] * (colw[j] - hv[j]);
       wcore_part = e * e;
       logdet_part = log(Ri[i * CH_LD + i]);
+      if (A.resid) A.resid[G.row0 + i] = e;
     }
     const double wcore = block_sum(wcore_part, s_red);
     const double logdet = block_sum(logdet_part, s_red);

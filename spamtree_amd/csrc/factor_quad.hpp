@@ -36,8 +36,11 @@ struct QuadArgs {
   const double *cx, *cy;
   const int *mv;
   const double *w;
+  const double *g_in;      // leaf levels (not phase P, not QM_TFROMV): g = Linv_pa w_pa per device row of the ancestors -- their stored
+                           // residuals e = Ri (w - H w_pa) (limited trees: chol(K_pa)^{-1} w_pa), gathered through the wpa / pw slots
   double *panels;
   double *logdet_c, *loglik_c;
+  double *resid;           // reference levels: e of every unit goes to its device rows (nullptr: not stored)
   int *errflag;
   int ldS;   // staged row stride: >= longest row + 24 zero-filled columns
   int wave_chol;   // the level's blocks have <= 27 rows: one-wave register elimination (a property of the LEVEL, so that a
@@ -72,8 +75,9 @@ __host__ __device__ constexpr int quad_vtiles(int nkx) { return 2 + 2 * ((4 * nk
 // (tree_layout.cpp, build_quad_records) exactly as the kernel keeps it in LDS.  The workgroup of launch position i copies
 // record i into this image with one round of LDS-DMA and takes one barrier.  Only w changes from call to call: the
 // slots wpa / colw / pw of a record hold the GLOBAL ROW of their entry (a long long in the double's bits, -1: no entry),
-// the kernel replaces them by w of that row.  Entries a quad does not have (units >= nu, columns >= M, private rows >=
-// pm, blocks >= nblk, chain rows >= Pc) are zero.  Every member's size is a multiple of 16 bytes (the DMA's piece).
+// the kernel replaces them by w of that row (the leaf bodies outside phase P: wpa / pw by g of that row, QuadArgs::g_in).
+// Entries a quad does not have (units >= nu, columns >= M, private rows >= pm, blocks >= nblk, chain rows >= Pc)
+// are zero.  Every member's size is a multiple of 16 bytes (the DMA's piece).
 template <int NU, int PMAX, bool ISREF>
 struct alignas(16) QuadRec {
   // leaf-only arrays: one 16-byte piece each in a reference quad's record (never read there)
@@ -136,7 +140,6 @@ __device__ __forceinline__ void dma_row(const double *src, double *dst, int Kb, 
 template <int NU, int NKX, int NKT, bool ISREF, bool WCH = true>
 __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar cp) {
   constexpr int NTQ = 128 * NU, NW = 2 * NU;
-  static_assert(NU >= 2, "s_g overlays two rows of s_e2");
   // covariance scratch ([KH][64] doubles per wave, lane-private slots): reference levels keep it in the SECOND staging buffer
   // (4 passes), leaf levels behind the arena (KH = 5: 20 KB), so that the first panel rows can travel by LDS-DMA UNDER the
   // covariance pass instead of after it
@@ -162,10 +165,6 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
   // lane out of the kernel arguments they are GLOBAL loads -- three or four dependent round trips per entry; the covariance
   // pass was 21-24 % of a quad's life at config #5 (stamps) -- so they live in LDS
   __shared__ double s_cvr[QMAX * QMAX], s_cva[QMAX * QMAX], s_cva2[QMAX * QMAX], s_cvp[QMAX];
-  // leaf units: g = Linv_pa w_pa, one entry per staged chain row, for the residual r_j (w_j - V_j' g).  Overlays: s_e2 is
-  // written after the main loop only, s_hv is a reference-level array (and phase P's, also after the main loop)
-  double (*s_g)[32] = s_e2;    // [step buffer][row of the step]
-  double (*s_gp)[32] = s_hv;   // [unit][row of the private ancestor]
 
   // Everything from here on is compiled once per mode (the dispatch follows the body, at the end of the kernel); the LDS
   // declarations above exist once.  The body keeps the kernel's indentation.
@@ -219,7 +218,9 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
   // ---- w of the shared chain (threads [0, Pc)), of the units' columns ([NTQ/2, NTQ/2 + 32 NU)) and of the private
   // ancestors' rows (the last 32 NU threads): requested here, ahead of the first panel rows, from the rows the record names;
   // the values stay in a register over the covariance pass and go to their slots behind it (nothing reads them before).
-  // QM_TFROMV reads no w.
+  // QM_TFROMV reads no w.  Leaf units outside phase P need w_pa only as g = Linv_pa w_pa (the residual of column j is
+  // r_j (w_j - V_j' g)), and the rows of g that belong to ancestor a are that block's own whitened residual, stored by whatever
+  // route factorised it (A.g_in): the chain and private-row slots take g of their row instead of w, same thread, same index.
   double wpark = 0.0;
   constexpr int o_wpa = (int)(offsetof(Rec, wpa) / 8), o_colw = (int)(offsetof(Rec, colw) / 8), o_pw = (int)(offsetof(Rec, pw) / 8);
   auto wslot = [&]() __attribute__((always_inline)) {   // this thread's slot (a double's index in s_q), -1: none
@@ -232,7 +233,11 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
     const int ws = wslot();
     if (ws >= 0) {
       const long long r = __double_as_longlong(((const double *)&s_q)[ws]);
-      if (r >= 0) wpark = A.w[r];
+      const double *src = A.w;
+      if constexpr (!ISREF) {
+        if (!(QM == QM_FULL && A.predict) && (tid < NTQ / 2 || tid >= NTQ / 2 + 32 * NU)) src = A.g_in;
+      }
+      if (r >= 0) wpark = src[r];
     }
   }
 
@@ -340,7 +345,7 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
   }
   // no barrier here: the scratch slots are lane-private, and the first DMA into their region (reference quads: step 1 into
   // the second buffer) is requested after the first barrier below
-  // the parked w to its slot (no entry: 0).  Leaf quads read the slots in the first staged step already (grow, by other
+  // the parked w / g to its slot (no entry: 0).  Leaf quads read the slots in the first staged tile already (hacc, by other
   // threads than wrote them): one barrier; reference quads read them behind the main loop's barriers
   if (QM != QM_TFROMV) {
     const int ws = wslot();
@@ -366,41 +371,6 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
     return (d4){__builtin_nontemporal_load(d), __builtin_nontemporal_load(d + 64), __builtin_nontemporal_load(d + 128),
                 __builtin_nontemporal_load(d + 192)};
   };
-  // g of one staged row per group of NS consecutive lanes (sub = lane % NS): s = fma(row[k], w[k], s) for k = sub, sub + NS, ...
-  // < len, in that order into ONE accumulator per lane, then the group's xor butterfly (the complete sum in each of its lanes).
-  // The operands of NB trips are requested TOGETHER before the batch's first fma: one LDS round trip per batch (as a loop of
-  // single products every trip was a fully exposed round trip, and every wave of the workgroup makes them at the same time,
-  // ahead of a barrier).  A trip with k >= len leaves s untouched -- it adds no product with zero; what it read (inside the
-  // staged rows / the record) is dropped.  w[k] = s_wpa[k] below wlim, beyond it the double at index k + pwo of the record
-  // (the unit's private rows).
-  //   * V-only body (no T accumulators): the loop is unrolled to its compile-time bound, ceil(PMAX / NS) trips, in ONE batch
-  //     -- one round trip per row; wreg != nullptr: the lane's w operands, already in registers.
-  //   * full body (at its register limit): a rolled loop over batches of 3 (shared step: 5 round trips instead of 13) or 5
-  //     trips (private sub-panel: 5 instead of 25) up to lmax (wave-uniform, >= len) -- the deepest batches at which no
-  //     instantiation gains a register; unrolled, the same batches cost 14 registers at every NKX and spills at NKX 50.
-  constexpr bool gdeep = QM == QM_VONLY;
-  const bool needg = !(QM == QM_FULL && A.predict);   // phase P takes hv = T w_pa and never reads hacc: no g (workgroup-uniform)
-  auto grow = [&](const double *row, int len, int lmax, int wlim, int pwo, const double *wreg, int sub, auto ns) __attribute__((always_inline)) {
-    constexpr int NS = decltype(ns)::value, NTR = (PMAX + NS - 1) / NS, NB = gdeep ? NTR : (NS == 8 ? 5 : 3);
-    const double *rec = (const double *)&s_q;
-    double s = 0.0;
-#pragma unroll 1
-    for (int k0 = sub; k0 < (gdeep ? sub + 1 : lmax); k0 += NB * NS) {   // (V-only body: one pass)
-      double a[NB], wv[NB];
-#pragma unroll
-      for (int i = 0; i < NB; ++i) {
-        const int k = k0 + NS * i;
-        a[i] = row[k];
-        wv[i] = wreg ? wreg[i] : rec[k + (k < wlim ? o_wpa : pwo)];
-      }
-#pragma unroll
-      for (int i = 0; i < NB; ++i) {
-        const double t = fma(a[i], wv[i], s);
-        s = k0 + NS * i < len ? t : s;
-      }
-    }
-    return group_xor_sum<NS>(s);
-  };
 
 #define QMFMA(a_, b_, c_) c_ = __builtin_amdgcn_mfma_f64_16x16x4f64(a_, b_, c_, 0, 0, 0)
   // One 16-row tile of the step (rows at tg, nk = ceil(rows / 4) K-steps of the T update, row length KbT): V = Linv K for
@@ -411,8 +381,9 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
   // jt = 0 wave forms the Schur tile (1, 0) = V_1' V_0 from it and its own tile, still in registers.
   // rmask >= 0 (private sub-panels packed without padding rows): V rows >= rmask are forced to zero (what the tile holds there
   // belongs to the next unit: finite, but not ours).
-  // gt: g of the tile's 16 rows (leaf units); pv: the V tile itself (QM_TFROMV); tix: the tile's index in the V scratch.
-  auto tile = [&](const double *tg, int nk, int KbT, int slot, int rmask, const double *gt, d4 pv, int tix) __attribute__((always_inline)) {
+  // gt: g of the tile's rows, gn of them (leaf units: the wpa / pw slots; what lies beyond belongs to other rows or is no
+  // double at all, and meets V rows of zeros: dropped); pv: the V tile itself (QM_TFROMV); tix: the tile's index in the V scratch.
+  auto tile = [&](const double *tg, int nk, int KbT, int slot, int rmask, const double *gt, int gn, d4 pv, int tix) __attribute__((always_inline)) {
     d4 p = (d4){0.0, 0.0, 0.0, 0.0};
     if (QM == QM_TFROMV) p = pv;
     else if (wact) {
@@ -461,7 +432,11 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
       } else {
         // explicit fma chains: the same bits in every mode, whatever the compiler would contract
         dacc = fma(p[3], p[3], fma(p[2], p[2], fma(p[1], p[1], fma(p[0], p[0], dacc))));
-        if (QM != QM_TFROMV && needg) hacc = fma(p[3], gt[l4 + 12], fma(p[2], gt[l4 + 8], fma(p[1], gt[l4 + 4], fma(p[0], gt[l4], hacc))));
+        if (QM != QM_TFROMV) {   // (phase P never reads hacc)
+          const double g0 = l4 < gn ? gt[l4] : 0.0, g1 = l4 + 4 < gn ? gt[l4 + 4] : 0.0, g2 = l4 + 8 < gn ? gt[l4 + 8] : 0.0,
+                       g3 = l4 + 12 < gn ? gt[l4 + 12] : 0.0;
+          hacc = fma(p[3], g3, fma(p[2], g2, fma(p[1], g1, fma(p[0], g0, hacc))));
+        }
       }
     }
     // QM_VONLY: the tile goes out at once
@@ -470,10 +445,10 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
   // one step (sr <= 32 rows of Linv staged at stg with stride ldS; Kb / KbA: length of the longest row of the step / of its
   // first tile -- shorter when the step straddles ancestors; columns up to Kb + 24 are zero beyond a row's own length).
   // Called by every wave of the workgroup (barriers inside for reference units); sr is the same for all of them.
-  // gs: g of the step's 32 rows; pA / pB: the step's V tiles (QM_TFROMV); tix: the index of its first tile
+  // gs: g of the step's sr rows; pA / pB: the step's V tiles (QM_TFROMV); tix: the index of its first tile
   auto compute = [&](const double *stg, int sr, int Kb, int KbA, const double *gs, const d4 &pA, const d4 &pB, int tix) __attribute__((always_inline)) {
-    tile(stg, (min(sr, 16) + 3) >> 2, KbA, 0, -1, gs, pA, tix);
-    if (sr > 16) tile(stg + 16 * ldS, (sr - 16 + 3) >> 2, Kb, 1, -1, gs + 16, pB, tix + 1);
+    tile(stg, (min(sr, 16) + 3) >> 2, KbA, 0, -1, gs, min(sr, 16), pA, tix);
+    if (sr > 16) tile(stg + 16 * ldS, (sr - 16 + 3) >> 2, Kb, 1, -1, gs + 16, sr - 16, pB, tix + 1);
   };
 
   // ---- private (last) ancestors (leaf quads): every unit's sub-panel staged side by side (LDS-DMA), all waves busy.
@@ -508,18 +483,11 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
         }
         const int r0 = sp == 0 ? 0 : p_sr0;
         STAMP(2);
-        if (QM != QM_TFROMV && needg) {   // g of the rows this wave staged, 8 lanes per row (zero for absent rows: they meet V rows of zeros)
-          const int row = jt + 2 * (lane >> 3);
-          const double gv = grow(buf + (size_t)row * ldS, row < sr ? p_Kb : 0, p_Kb, Pc, o_pw + u * Rec::NLD - Pc, nullptr, lane & 7,
-                                 std::integral_constant<int, 8>());
-          if ((lane & 7) == 0) s_gp[u][r0 + row] = gv;
-        }
-        STAMP(15);
         lds_barrier();
         if (sp == 1 && pf) issue(0, arena + (size_t)48 * ldS);
         // (row i of the sub-panel is chain row Pc + r0 + i of a LOWER-TRIANGULAR factor: nothing beyond column Pc + r0 + sr)
         if (sr > 0) {
-          tile(buf, (sr + 3) >> 2, min(p_Kb, Pc + r0 + sr), 0, sr, &s_gp[u][r0], kget(16 + 4 * sp), sp);
+          tile(buf, (sr + 3) >> 2, min(p_Kb, Pc + r0 + sr), 0, sr, &s_pw[u][r0], sr, kget(16 + 4 * sp), sp);
         }
         lds_barrier();
       }
@@ -543,13 +511,6 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
   {
     if constexpr (!ISREF) { if (nit > 0 && !pf) issue(0, arena); }   // (reference quads: requested before the covariance pass)
     int cur = pf ? 1 : 0;
-    // V-only body: the lane's w operands of grow (s_wpa[lane % NS + NS i], the same on every step) stay in registers over the loop
-    constexpr int NSG = 64 / RP, NTG = (!ISREF && gdeep) ? (PMAX + NSG - 1) / NSG : 1;
-    double wsh[NTG];
-    if (!ISREF && gdeep) {
-#pragma unroll
-      for (int i = 0; i < NTG; ++i) wsh[i] = ((const double *)&s_q)[o_wpa + lane % NSG + NSG * i];
-    }
     // QM_TFROMV: the V tiles of step i + 1 are requested when step i starts -- this step's in kx[0..7], the next step's in
     // kx[8..15] (no covariance pass: free registers); QM_VONLY stores each tile as soon as it is formed (tile)
     if (QM == QM_TFROMV && wact && nit > 0) { kset(0, vload(2)); if (Pc - 32 * (nit - 1) > 16) kset(4, vload(3)); }
@@ -573,17 +534,6 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
         }
       }
       STAMP(5);
-      if (!ISREF && QM != QM_TFROMV && needg) {   // g of the rows this wave staged, 64 / RP lanes per row (zero for absent rows)
-        constexpr int NS = 64 / RP;
-        const int rq = lane / NS, row = wid + NW * rq;
-        int len = rlen_cur[0];
-#pragma unroll
-        for (int rr = 1; rr < RP; ++rr) len = rq == rr ? rlen_cur[rr] : len;
-        const double gv = grow(buf + (size_t)(row < sr ? row : 0) * ldS, row < sr ? len : 0, Kb, 1 << 30, 0, gdeep ? wsh : nullptr, lane % NS,
-                               std::integral_constant<int, NS>());
-        if (lane % NS == 0) s_g[cur][row] = gv;
-      }
-      STAMP(14);
       lds_barrier();
       STAMP(3);
       if (i + 1 < nit) issue(i + 1, arena + (size_t)(cur ^ 1) * 32 * ldS);
@@ -591,7 +541,7 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
       STAMP(6);
       // the chain's factor is lower triangular in chain order: a row's stored length runs to the end of its ancestor's block,
       // but beyond the tile's last row index there are only (explicit) zeros -- 11 % of the V and 16 % of the T MFMAs at 25-row blocks
-      compute(buf, sr, min(Kb, c0 + 32), min(KbA0, c0 + 16), ISREF ? nullptr : s_g[cur], kget(0), kget(4), 2 + 2 * i);
+      compute(buf, sr, min(Kb, c0 + 32), min(KbA0, c0 + 16), ISREF ? nullptr : &s_wpa[c0], kget(0), kget(4), 2 + 2 * i);
       if (QM == QM_TFROMV) { kset(0, kget(8)); kset(4, kget(12)); }
       STAMP(4);
       cur ^= 1;
@@ -604,7 +554,7 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
   }
 
   // ---- hv = T w_pa for this wave's columns (tile rows l4 + 4 r), summed over the 16 chain columns of a tile row: reference
-  // units and phase P (the leaf units' log-density takes V' g instead: hacc)
+  // units and phase P (the leaf units' log-density takes V' g instead: hacc, with g gathered from the ancestors' residuals)
   double h0 = 0.0, h1 = 0.0, h2 = 0.0, h3 = 0.0;
   if (QM == QM_FULL && (ISREF || A.predict)) {
 #pragma unroll
@@ -790,6 +740,7 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
           if (i < Mu && pq == 0) {
             s_e2[u][i] = e * e;
             s_lg[u][i] = log(Ri[i * CH_LD + i]);
+            if (A.resid) A.resid[s_urow0[u] + i] = e;   // the leaf quads below gather it as the g of this block's chain rows
           }
         }
       }
@@ -881,6 +832,7 @@ __global__ __launch_bounds__(128 * NU, 2) void k_factor_quad(QuadArgs A, CovPar 
         if (i < Mu && pq == 0) {
           s_e2[u][i] = e * e;
           s_lg[u][i] = log(Ri[i * CH_LD + i]);
+          if (A.resid) A.resid[s_urow0[u] + i] = e;
         }
       }
     }

@@ -38,6 +38,7 @@ struct WideArgs {
   const double *w_in;
   double *panels;
   double *logdet_c, *loglik_c;
+  double *resid;   // reference blocks: the whitened residuals e = Ri (w_u - H_u w_pa) at the block's device rows (nullptr: not stored)
   int *errflag;
   double *scratch;
   long long scratch_stride;
@@ -315,6 +316,7 @@ __global__ __launch_bounds__(WG_NT, 2) void k_factor_wide(WideArgs A, CovPar cp)
           for (int j = 0; j <= i; ++j) acc += Ril[i * m + j] * (wv[P + cb + j] - hv[cb + j]);
           wcore_part += acc * acc;
           logdet_part += log(Ril[i * m + i]);
+          if (A.resid) A.resid[B.row0 + i] = acc;
         }
       } else {
         // non-reference level: rows conditionally independent (spamtree_model.cpp:923-963)

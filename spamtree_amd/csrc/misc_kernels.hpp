@@ -11,6 +11,7 @@ struct LoglikArgs {
   const double *panels;
   const double *w;
   double *loglik_c;
+  double *resid;   // reference blocks: the residuals e_i whose squares are summed, at the block's device rows (nullptr: not stored)
   int maxP, maxM;
 };
 
@@ -112,6 +113,7 @@ __global__ __launch_bounds__(NT) void k_loglik(LoglikArgs A) {
       double acc = tv[i];
       if (B.isref) {
         for (int j = 0; j <= i; ++j) acc += N[(size_t)i * ld + P + j] * wv[P + j];
+        if (A.resid) A.resid[B.row0 + i] = acc;
       } else {
         acc += N[(size_t)i * ld + P] * wv[P + i];
       }

@@ -277,6 +277,8 @@ static int create_state(st_handle_s *h) {
   CCHK(hipMemset(h->d_w.p, 0, n * sizeof(double)));
   CCHK(hipMemset(h->d_xb.p, 0, n * sizeof(double)));
   CCHK(hipMemset(h->d_z.p, 0, n * sizeof(double)));
+  CCHK(h->d_resid.alloc(n));
+  CCHK(hipMemset(h->d_resid.p, 0, n * sizeof(double)));
   CCHK(h->d_B.alloc((size_t)h->p * h->q));
   CCHK(h->d_tsq.alloc(QMAX));
   for (int s = 0; s < 2; ++s) {
@@ -399,6 +401,14 @@ extern "C" int st_get_w(st_handle h, double *w) {
   HCHK(h, hipSetDevice(h->device));
   return download_rows(h, h->d_w.p, w);
 }
+// inspection: the reference blocks' whitened residuals as the last factorisation (either slot) left them -- what the leaf
+// quads gather as the g of their chains (limited trees: chol(K_uu)^{-1} w_u of the blocks with children); rows of other blocks: 0
+extern "C" int st_get_resid(st_handle h, double *out, int64_t n) {
+  if (!h || !out || n != h->n_all) return ST_ERR_USAGE;
+  HCHK(h, hipSetDevice(h->device));
+  if (h->top_pending) HCHK(h, hipStreamWaitEvent(h->stream, h->ev_top, 0));   // (settle_top: the second stream may be writing top rows)
+  return download_rows(h, h->d_resid.p, out);
+}
 extern "C" int st_get_xb(st_handle h, double *xb) {
   if (!h || !xb) return ST_ERR_USAGE;
   HCHK(h, hipSetDevice(h->device));
@@ -452,6 +462,7 @@ static QuadArgs quad_args(st_handle h, int grp_first, long long qr_off, int qr_w
   F.qrec = qr_off >= 0 ? h->d_qrec.p + qr_off : nullptr; F.qrec_stride = qr_words; F.nquad = nquad;
   F.cx = h->d_cx.p; F.cy = h->d_cy.p; F.mv = h->d_mv.p; F.w = h->d_w.p; F.panels = h->d_panels[phys].p;
   F.errflag = errflag; F.ldS = ldS;
+  F.g_in = h->d_resid.p;   // leaf bodies (not phase P, not QM_TFROMV): the g of the chain rows, gathered like w
   return F;
 }
 // A slot whose leaf levels ran QM_VONLY gets its leaf panels here (QM_TFROMV, on the launch stream), before anything reads
@@ -608,6 +619,7 @@ static int factor_launch(st_handle h, int phys, const CovPar &cp, int g_lo = 0, 
     MarginalArgs M;
     M.blks = h->d_blks.p; M.list = h->d_twin.p; M.nlist = (int)h->twin_list.size(); M.cx = h->d_cx.p; M.cy = h->d_cy.p; M.mv = h->d_mv.p;
     M.panels = h->d_panels[phys].p; M.errflag = errflag; M.maxM = h->twin_maxM;
+    M.w = h->d_w.p; M.resid = h->d_resid.p;   // the g of the marginal chains (the conditional residuals below are not stored)
     const size_t lds = (size_t)2 * h->twin_maxM * h->twin_maxM * sizeof(double);
     if (h->twin_maxM <= 27 && !h->force_generic) {   // one block per wave, blocked DPP / MFMA elimination
       route(0, R_MARGINAL_INVCHOL_WAVE);
@@ -618,6 +630,8 @@ static int factor_launch(st_handle h, int phys, const CovPar &cp, int g_lo = 0, 
       hipLaunchKernelGGL(k_marginal_invchol, dim3(std::min(M.nlist, 8 * h->sm_count)), dim3(NT), lds, st, M, cp);
     }
   }
+  // the reference blocks' residuals, for the leaf quads below them (limited trees: their chains are marginal factors, see above)
+  double *resid = h->limited ? nullptr : h->d_resid.p;
   for (int g = g_lo; g < g_hi; ++g) {
     const LevelInfo &L = h->levels[g];
     if ((L.fast ? L.gown_n : L.own_n) == 0) continue;
@@ -626,12 +640,13 @@ static int factor_launch(st_handle h, int phys, const CovPar &cp, int g_lo = 0, 
     A.blks = h->d_blks.p; A.anc_idx = h->d_anc.p; A.list = h->d_lvl.p + L.first + L.own_lo; A.nlist = L.own_n;
     A.cx = h->d_cx.p; A.cy = h->d_cy.p; A.mv = h->d_mv.p; A.w_in = h->d_w.p; A.w_out = nullptr; A.z = nullptr;
     A.panels = h->d_panels[phys].p; A.logdet_c = h->d_logdet[phys].p; A.loglik_c = h->d_loglik[phys].p;
+    A.resid = resid;
     A.errflag = errflag; A.maxP = L.maxP; A.maxM = L.maxM; A.maxMa = L.maxMa; A.SR = L.big_factor ? 4 : 8;
     {
       ProfScope ps(h, 0, g, 1, st);
       if (L.fast && h->sw.factor_gen == 3 && L.q_nkx > 0) {
         QuadArgs F = quad_args(h, L.grp_first, L.qr_off, L.qr_words, L.qown_n, L.q_ldS, phys, errflag);
-        F.logdet_c = h->d_logdet[phys].p; F.loglik_c = h->d_loglik[phys].p;
+        F.logdet_c = h->d_logdet[phys].p; F.loglik_c = h->d_loglik[phys].p; F.resid = resid;
         F.wave_chol = L.maxM <= 27 ? 1 : 0;
         if (!L.isref && vonly && L.vl_off >= 0) { F.mode = QM_VONLY; F.vscr = h->d_vleaf.p + L.vl_off; F.vtiles = quad_vtiles(L.q_nkx); *deferred = true; }
         route(g, launch_quad(L.q_nkx, L.isref != 0, F.wave_chol != 0, L.qown_n, L.lds_quad, st, F, cp));
@@ -640,7 +655,7 @@ static int factor_launch(st_handle h, int phys, const CovPar &cp, int g_lo = 0, 
         std::memset(&F, 0, sizeof(F));
         F.blks = h->d_blks.p; F.anc_idx = h->d_anc.p; F.grps = h->d_grps.p + L.grp_first + L.gown_lo; F.ngrp = L.gown_n;
         F.cx = h->d_cx.p; F.cy = h->d_cy.p; F.mv = h->d_mv.p; F.w = h->d_w.p; F.panels = h->d_panels[phys].p;
-        F.logdet_c = h->d_logdet[phys].p; F.loglik_c = h->d_loglik[phys].p; F.errflag = errflag;
+        F.logdet_c = h->d_logdet[phys].p; F.loglik_c = h->d_loglik[phys].p; F.resid = resid; F.errflag = errflag;
         F.Pm4 = L.Pm4; F.ldKV = L.ldKV; F.ldS = L.ldS; F.SRm = L.SRm; F.stage_dbl = L.stage_dbl;
         F.gdesc = h->d_gdesc.p + (size_t)(L.grp_first + L.gown_lo) * h->gd_stride; F.gd_stride = h->gd_stride;
         route(g, R_FACTOR_MFMA);
@@ -669,7 +684,7 @@ static int factor_launch(st_handle h, int phys, const CovPar &cp, int g_lo = 0, 
         std::memset(&W, 0, sizeof(W));
         W.blks = h->d_blks.p; W.anc_idx = h->d_anc.p; W.list = h->d_lvl.p + L.first + L.own_lo; W.groups = h->d_wgrps.p + L.wide_first;
         W.ngroups = L.wide_count; W.cx = h->d_cx.p; W.cy = h->d_cy.p; W.mv = h->d_mv.p; W.w_in = h->d_w.p; W.panels = h->d_panels[phys].p;
-        W.logdet_c = h->d_logdet[phys].p; W.loglik_c = h->d_loglik[phys].p; W.errflag = errflag; W.scratch = h->d_scratch.p;
+        W.logdet_c = h->d_logdet[phys].p; W.loglik_c = h->d_loglik[phys].p; W.resid = resid; W.errflag = errflag; W.scratch = h->d_scratch.p;
         W.scratch_stride = h->scratch_stride; W.maxP = L.maxP; W.maxN = L.wide_maxN; W.maxM = L.maxM; W.maxMa = L.maxMa; W.ldS = L.bm_ldS;
         route(g, R_FACTOR_WIDE);
         hipLaunchKernelGGL((k_factor_wide<WG_JT>), dim3(std::min(L.wide_count, h->sm_count)), dim3(WG_NT), L.lds_wide, st, W, cp);
@@ -760,12 +775,13 @@ static int factor_local(st_handle h, int slot, const double *theta, int ntheta, 
     reuse = h->top_phys == phys && (int)h->top_theta.size() == ntheta && std::equal(theta, theta + ntheta, h->top_theta.begin());
     h->top_pending = false;
   }
+  // the top levels ran ahead of time with the w of the sweep's start: their quadratic forms AND the residuals the leaf quads
+  // below gather are redone with the current w before those levels are launched (outside factor_launch's phase bracket)
+  if (reuse) { rc = fix_top_comps(h, phys); if (rc) return rc; }
   bool deferred = false;
   rc = factor_launch(h, phys, cp, reuse ? h->g_top : 0, INT_MAX, nullptr, nullptr, vonly, &deferred);
   if (deferred) { h->leaf_pending[phys] = true; h->leaf_cp[phys] = cp; }
   if (rc || !reuse) return rc;
-  rc = fix_top_comps(h, phys);
-  if (rc) return rc;
   hipLaunchKernelGGL(k_merge_err, dim3(1), dim3(64), 0, h->stream, h->d_err.p, h->d_err2.p);
   HCHK(h, hipGetLastError());
   return ST_OK;
@@ -1240,7 +1256,7 @@ extern "C" int st_loglik_local(st_handle h, int slot) {
   const size_t lds = lds_loglik_bytes(maxP, maxM);
   LoglikArgs A;
   A.blks = h->d_blks.p; A.anc_idx = h->d_anc.p; A.list = h->d_ownslow.p; A.nlist = (int)h->own_obs_slow.size();
-  A.panels = h->d_panels[phys].p; A.w = h->d_w.p; A.loglik_c = h->d_loglik[phys].p; A.maxP = maxP; A.maxM = maxM;
+  A.panels = h->d_panels[phys].p; A.w = h->d_w.p; A.loglik_c = h->d_loglik[phys].p; A.resid = nullptr; A.maxP = maxP; A.maxM = maxM;
   {
     ProfScope ps(h, 2);
     if (A.nlist > 0) hipLaunchKernelGGL(k_loglik, dim3(A.nlist), dim3(NT), lds, h->stream, A);
@@ -1256,14 +1272,14 @@ extern "C" int st_loglik_local(st_handle h, int slot) {
   HCHK(h, reset_err(h) == ST_OK ? hipSuccess : hipErrorUnknown);
   return ST_OK;
 }
-// the quadratic forms of the top blocks with the CURRENT w (st_factor_begin ran them with the w of the sweep's start)
+// the quadratic forms and the residuals of the top blocks with the CURRENT w (st_factor_begin ran them with the w of the sweep's start)
 static int fix_top_comps(st_handle h, int phys) {
   if (h->n_toplist == 0) return ST_OK;
   int maxP = 0, maxM = 0;
   for (int g = 0; g < h->g_top; ++g) { maxP = std::max(maxP, h->levels[g].maxP); maxM = std::max(maxM, h->levels[g].maxM); }
   LoglikArgs A;
   A.blks = h->d_blks.p; A.anc_idx = h->d_anc.p; A.list = h->d_toplist.p; A.nlist = h->n_toplist;
-  A.panels = h->d_panels[phys].p; A.w = h->d_w.p; A.loglik_c = h->d_loglik[phys].p; A.maxP = maxP; A.maxM = maxM;
+  A.panels = h->d_panels[phys].p; A.w = h->d_w.p; A.loglik_c = h->d_loglik[phys].p; A.resid = h->d_resid.p; A.maxP = maxP; A.maxM = maxM;
   {
     ProfScope ps(h, 0, h->g_top > 0 ? h->g_top - 1 : 0);
     hipLaunchKernelGGL(k_loglik, dim3(A.nlist), dim3(NT), lds_loglik_bytes(maxP, maxM), h->stream, A);

@@ -98,6 +98,14 @@ struct st_handle_s : TreeLayout {
   bool leaf_pending[2] = {false, false};   // per physical arena
   CovPar leaf_cp[2];
   DevBuf<double> d_vleaf;
+  // The whitened residuals e = Ri (w_u - H_u w_pa) of the reference blocks, per device row (n_all): every phase-A route stores
+  // what it squares for the block's loglik_w component, and the leaf bodies of k_factor_quad gather them as the g = Linv_pa w_pa
+  // of their chain (limited trees: k_marginal_invchol stores chol(K_uu)^{-1} w_u instead, the g of the marginal chain).  ONE
+  // buffer for both slots: it is read only by the leaf launch of the factorisation that wrote it, on the same stream; the top
+  // levels st_factor_begin runs ahead of time on the second stream are ordered behind everything issued before them, nothing on
+  // the main stream reads the buffer until factor_local has waited for them, and their (stale) rows are rewritten by
+  // fix_top_comps before the levels below are launched.
+  DevBuf<double> d_resid;
   DevBuf<int> d_twin;
   ncclComm_t comm = nullptr;                  // native RCCL communicator (st_comm_init); null = exchanges are the caller's
   std::vector<int> route_a, route_b;          // per level: ST_ROUTE_A_SLOTS phase-A / 2 phase-B route codes of the last launch
