@@ -151,9 +151,3 @@ __device__ __forceinline__ DiagOut diag_series_wave(double *x, int K, int L, int
 // R and Kp of a store of K draws under a per-workgroup LDS limit; false: one series does not fit
 bool series_diag_plan(long long K, size_t lds_limit, int *R, int *Kp);
 int series_diag_launch(const DiagArgs &A, size_t lds_limit, hipStream_t st);
-
-// The one launcher of the three C-ABI calls: diagnostics of the first K rows of the store draws[K][n] into out's host arrays (any
-// may be NULL), element i of the store at out[perm ? perm[i] : i].  The caller has checked K and max_lag.
-struct st_handle_s;
-int series_diag_store(st_handle_s *h, const char *who, const double *draws, long long n, long long K, int32_t max_lag,
-                      const long long *perm, const st_series_diag *out);

@@ -1,0 +1,50 @@
+// draw_store.hpp -- one view of a store of saved draws for the summaries of the stored draws (quantiles, diagnostics, excursions,
+// rank diagnostics).  Draws are kept in three places: the fit's rows (rows_store, spamtree_hip.hip), the new points and their
+// functionals (points_store, fun_store, st_points.hip).  A C-ABI entry point is one store_* call on its resolver's view.
+// No HIP header: store_spec.cpp, the pure host helpers declared at the end, is compiled and checked without a device.
+#pragma once
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "spamtree_hip.h"
+
+// Owns nothing, allocates nothing.  A store is draws[d * n + i], d < K, i < n.
+struct DrawStore {
+  int rc = ST_OK;                               // the resolver's refusal (its text is in the handle): nothing else is looked at
+  const double *w = nullptr, *yhat = nullptr;   // device; yhat NULL: the store has none
+  long long n = 0, K = 0;                       // series and stored draws (n = 0: an empty store, ST_OK with nothing written)
+  const int *d_outcome = nullptr;               // the series' domains on the device, store order; NULL: one domain
+  int G = 1;                                    // domains
+  bool thr_per_series = false;                  // a spec holds n_thr x n thresholds in output order, else n_thr x G
+  const long long *perm = nullptr;              // element i of the store is element perm[i] of every per-series array; NULL: i
+  double *d_scratch = nullptr;                  // n doubles on the device that the quantile writes through
+  const char *reserve = "";                     // the call that makes room for the draws, for the refusals' texts
+  bool yhat_needs_X = false;                    // the point set came without X: a yhat output is refused
+  long long n_thr_values() const { return thr_per_series ? n : G; }
+};
+
+// Each refuses what does not depend on the store, returns ST_OK on an empty store (not the quantile: it refuses "no draw stored"),
+// checks the spec and K, refuses yhat without X, and runs its worker on w and on yhat.
+struct st_handle_s;
+int store_quantile(st_handle_s *h, const char *who, const DrawStore &s, double q, double *w_q, double *yhat_q);
+int store_diagnostics(st_handle_s *h, const char *who, const DrawStore &s, int32_t max_lag, const st_series_diag *w, const st_series_diag *yhat);
+int store_excursions(st_handle_s *h, const char *who, const DrawStore &s, const st_excursion_spec *spec, const st_excursion_out *w,
+                     const st_excursion_out *yhat);
+int store_rank_diagnostics(st_handle_s *h, const char *who, const DrawStore &s, const st_rank_spec *spec, const st_rank_out *w,
+                           const st_rank_out *yhat);
+
+// ---- store_spec.cpp
+// n_thr in min_thr .. ST_EXC_MAX_THRESHOLDS, thr given with n_thr > 0, n_thr x n_values finite values, sides +1 / -1 (NULL: all +1):
+// ST_OK, or ST_ERR_USAGE with W and the first failing check in msg
+int check_thresholds(const std::string &W, int n_thr, int min_thr, const double *thr, const int32_t *side, long long n_values, std::string &msg);
+// T x stride thresholds in store order into out -- column j from perm[j] where they go per series and the store has a perm;
+// returns the mask of the sides: bit t set for side -1
+unsigned thresholds_in_store_order(const double *thr, const int32_t *side, int T, long long stride, bool per_series, const long long *perm,
+                                   std::vector<double> &out);
+// out[i] = mask[perm ? perm[i] : i] != 0
+void mask_in_store_order(const uint8_t *mask, long long n, const long long *perm, std::vector<unsigned char> &out);
+// dst[r * n + (perm ? perm[i] : i)] = src[r * n + i], r < rows: device results in store order into the caller's arrays
+void scatter_rows(double *dst, const double *src, long long rows, long long n, const long long *perm);
+void scatter_rows(int32_t *dst, const int32_t *src, long long rows, long long n, const long long *perm);
+void scatter_rows(int64_t *dst, const int64_t *src, long long rows, long long n, const long long *perm);

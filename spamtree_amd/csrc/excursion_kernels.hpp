@@ -52,13 +52,3 @@ struct ExcArgs {
   double *prob, *excur;         // [T][n]
   double *joint_all;            // [T G]
 };
-
-// The one launcher of the three C-ABI calls: the outputs out asks for, of the first K rows of the store draws[K][n], into out's
-// host arrays; element i of the store at position perm ? perm[i] : i of every per-series array, and spec->mask read there too.
-// d_outcome: the series' outcomes on the device in store order (NULL: one domain); thr_per_series: spec->thr is n_thr x n, else
-// n_thr x G.  The caller has checked spec and K (exc_check_spec).
-struct st_handle_s;
-int exc_check_spec(st_handle_s *h, const char *who, const st_excursion_spec *spec, long long K, long long n_thr_values,
-                   const st_excursion_out *w, const st_excursion_out *yhat);
-int store_excursions(st_handle_s *h, const char *who, const double *draws, long long n, long long K, const int *d_outcome, int G,
-                     bool thr_per_series, const long long *perm, const st_excursion_spec *spec, const st_excursion_out *out);

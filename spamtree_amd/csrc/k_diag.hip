@@ -3,6 +3,7 @@
 // outputs; it draws nothing and touches no state of the chain.
 #include "st_handle.hpp"
 #include "diag_kernels.hpp"
+#include "draw_store.hpp"
 
 __global__ __launch_bounds__(DIAG_NT) void k_series_diag(DiagArgs A) {
   extern __shared__ double lds[];
@@ -47,9 +48,11 @@ int series_diag_launch(const DiagArgs &A, size_t lds_limit, hipStream_t st) {
   return e == hipSuccess ? 0 : (int)e;
 }
 
-int series_diag_store(st_handle_s *h, const char *who, const double *draws, long long n, long long K, int32_t max_lag,
-                      const long long *perm, const st_series_diag *out) {
-  if (!out || n <= 0 || !(out->ess || out->mcse || out->sd || out->rhat || out->lags)) return ST_OK;
+// diagnostics of one of the store's two sets of draws into out's host arrays (any may be NULL), element i of the store at
+// out[perm ? perm[i] : i]; store_diagnostics has checked K and max_lag
+static int series_diag_store(st_handle_s *h, const char *who, const DrawStore &s, const double *draws, int32_t max_lag, const st_series_diag *out) {
+  const long long n = s.n, K = s.K;
+  if (!out || !(out->ess || out->mcse || out->sd || out->rhat || out->lags)) return ST_OK;
   DiagArgs A;
   A.draws = draws; A.n = n; A.K = (int)K;
   A.L = (int)std::min<long long>(max_lag == 0 ? ST_DIAG_DEFAULT_MAX_LAG : max_lag, K - 2);
@@ -77,9 +80,22 @@ int series_diag_store(st_handle_s *h, const char *who, const double *draws, long
   if (out->lags) HCHK(h, hipMemcpyAsync(tl.data(), d_lags.p, tl.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HCHK(h, hipStreamSynchronize(h->stream));
   for (int k = 0; k < 4; ++k)
-    if (dst[k])
-      for (long long i = 0; i < n; ++i) dst[k][perm ? perm[i] : i] = tmp[(size_t)k * n + i];
-  if (out->lags)
-    for (long long i = 0; i < n; ++i) out->lags[perm ? perm[i] : i] = tl[i];
+    if (dst[k]) scatter_rows(dst[k], tmp.data() + (size_t)k * n, 1, n, s.perm);
+  if (out->lags) scatter_rows(out->lags, tl.data(), 1, n, s.perm);
+  return ST_OK;
+}
+
+int store_diagnostics(st_handle_s *h, const char *who, const DrawStore &s, int32_t max_lag, const st_series_diag *w, const st_series_diag *yhat) {
+  if (s.rc) return s.rc;
+  if (max_lag < 0) { h->err = std::string(who) + ": max_lag must not be negative (0: the default cap)"; return ST_ERR_USAGE; }
+  if (s.n == 0) return ST_OK;
+  if (s.K < ST_DIAG_MIN_DRAWS) {
+    h->err = std::string(who) + ": " + std::to_string(s.K) + " draws stored, the diagnostics need at least " + std::to_string(ST_DIAG_MIN_DRAWS) +
+             " (call " + s.reserve + " before the saved iterations)";
+    return ST_ERR_USAGE;
+  }
+  if (yhat && s.yhat_needs_X) { h->err = std::string(who) + ": yhat needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  for (int which = 0; which < 2; ++which)
+    if (const int rc = series_diag_store(h, who, s, which ? s.yhat : s.w, max_lag, which ? yhat : w)) return rc;
   return ST_OK;
 }

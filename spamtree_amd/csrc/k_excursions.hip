@@ -13,6 +13,7 @@
 //                 domain are counted in n_flat[g]
 #include "st_handle.hpp"
 #include "excursion_kernels.hpp"
+#include "draw_store.hpp"
 #include <cmath>
 
 __device__ __forceinline__ bool exc_event(double x, double c, bool neg) { return neg ? x < c : x > c; }
@@ -259,21 +260,15 @@ __global__ __launch_bounds__(EXC_NT) void k_exc_apply(ExcArgs A) {
 static bool exc_thr_out(const st_excursion_out *o) { return o && (o->count || o->prob || o->excur || o->joint_all); }
 static bool exc_band_out(const st_excursion_out *o) { return o && (o->mean || o->sd || o->maxdev || o->n_flat); }
 
-int exc_check_spec(st_handle_s *h, const char *who, const st_excursion_spec *spec, long long K, long long n_thr_values,
-                   const st_excursion_out *w, const st_excursion_out *yhat) {
+// what the three calls refuse of a spec and its outputs (K stored draws, n_thr_values thresholds per t)
+static int exc_check_spec(st_handle_s *h, const char *who, const st_excursion_spec *spec, long long K, long long n_thr_values,
+                          const st_excursion_out *w, const st_excursion_out *yhat) {
   const std::string W = std::string(who) + ": ";
   if (!spec) { h->err = W + "no spec"; return ST_ERR_USAGE; }
   const bool band = spec->want_band || exc_band_out(w) || exc_band_out(yhat);
   if (!spec->thr && !band) { h->err = W + "the spec holds neither thresholds nor a band request"; return ST_ERR_USAGE; }
   if (spec->thr) {
-    if (spec->n_thr < 1 || spec->n_thr > ST_EXC_MAX_THRESHOLDS) {
-      h->err = W + "n_thr = " + std::to_string(spec->n_thr) + " must lie in 1 .. " + std::to_string(ST_EXC_MAX_THRESHOLDS);
-      return ST_ERR_USAGE;
-    }
-    for (long long k = 0; k < (long long)spec->n_thr * n_thr_values; ++k)
-      if (!std::isfinite(spec->thr[k])) { h->err = W + "threshold " + std::to_string(k) + " is not finite"; return ST_ERR_USAGE; }
-    for (int t = 0; spec->side && t < spec->n_thr; ++t)
-      if (spec->side[t] != 1 && spec->side[t] != -1) { h->err = W + "side " + std::to_string(t) + " must be +1 or -1"; return ST_ERR_USAGE; }
+    if (const int rc = check_thresholds(W, spec->n_thr, 1, spec->thr, spec->side, n_thr_values, h->err)) return rc;
   } else if (exc_thr_out(w) || exc_thr_out(yhat)) {
     h->err = W + "count, prob, excur and joint_all need thresholds";
     return ST_ERR_USAGE;
@@ -289,9 +284,13 @@ static void exc_launch_passes(const ExcArgs &A, bool pass2, dim3 g1, dim3 g2, hi
   if (pass2) hipLaunchKernelGGL((k_store_drawreduce<TT, BAND, (TT > 1 ? 2 : 4)>), g2, dim3(EXC_NT), exc_pass2_lds(TT, BAND, A.G), st, A);
 }
 
-int store_excursions(st_handle_s *h, const char *who, const double *draws, long long n, long long K, const int *d_outcome, int G,
-                     bool thr_per_series, const long long *perm, const st_excursion_spec *spec, const st_excursion_out *out) {
-  if (!out || n <= 0) return ST_OK;
+// The outputs out asks for, of one of the store's two sets of draws, into out's host arrays; element i of the store at position
+// perm ? perm[i] : i of every per-series array, and spec->mask read there too.  store_excursions has checked spec and K.
+static int series_exc_store(st_handle_s *h, const char *who, const DrawStore &s, const double *draws, const st_excursion_spec *spec,
+                            const st_excursion_out *out) {
+  const long long n = s.n, K = s.K;
+  const int G = s.G;
+  if (!out) return ST_OK;
   if (out->n_draws) *out->n_draws = K;
   const bool thr = exc_thr_out(out), band = exc_band_out(out);
   if (!thr && !band) return ST_OK;
@@ -299,24 +298,20 @@ int store_excursions(st_handle_s *h, const char *who, const double *draws, long 
   const bool joint = out->excur || out->joint_all, pass2 = joint || out->maxdev;
   HCHK(h, hipSetDevice(h->device));
   ExcArgs A = {};
-  A.draws = draws; A.n = n; A.K = (int)K; A.T = T; A.G = G; A.outcome = d_outcome; A.per_series = thr_per_series ? 1 : 0;
-  A.thr_stride = thr_per_series ? n : G;
+  A.draws = draws; A.n = n; A.K = (int)K; A.T = T; A.G = G; A.outcome = s.d_outcome; A.per_series = s.thr_per_series ? 1 : 0;
+  A.thr_stride = s.n_thr_values();
   // the small inputs, in store order
   DevBuf<unsigned char> d_mask;
   DevBuf<double> d_thr, d_rinv;
   if (spec->mask) {
-    std::vector<unsigned char> mk((size_t)n);
-    for (long long i = 0; i < n; ++i) mk[i] = spec->mask[perm ? perm[i] : i] ? 1 : 0;
+    std::vector<unsigned char> mk;
+    mask_in_store_order(spec->mask, n, s.perm, mk);
     HCHK(h, d_mask.upload(mk));
     A.mask = d_mask.p;
   }
   if (T) {
-    std::vector<double> tv((size_t)T * A.thr_stride);
-    for (int t = 0; t < T; ++t) {
-      for (long long j = 0; j < A.thr_stride; ++j)
-        tv[(size_t)t * A.thr_stride + j] = spec->thr[(size_t)t * A.thr_stride + ((thr_per_series && perm) ? perm[j] : j)];
-      if (spec->side && spec->side[t] < 0) A.neg |= 1u << t;
-    }
+    std::vector<double> tv;
+    A.neg = thresholds_in_store_order(spec->thr, spec->side, T, A.thr_stride, s.thr_per_series, s.perm, tv);
     HCHK(h, d_thr.upload(tv));
     A.thr = d_thr.p;
   }
@@ -388,16 +383,21 @@ int store_excursions(st_handle_s *h, const char *who, const double *draws, long 
   if (out->maxdev) HCHK(h, d2h(out->maxdev, A.dev, (size_t)G * K * sizeof(double)));   // the bit patterns are the doubles
   if (out->n_flat) HCHK(h, d2h(hf.data(), A.n_flat, hf.size() * sizeof(unsigned long long)));
   HCHK(h, hipStreamSynchronize(h->stream));
-  for (long long i = 0; i < n; ++i) {
-    const long long o = perm ? perm[i] : i;
-    for (int t = 0; t < T; ++t) {
-      if (out->count) out->count[(size_t)t * n + o] = hc[(size_t)t * n + i];
-      if (out->prob) out->prob[(size_t)t * n + o] = hp[(size_t)t * n + i];
-      if (out->excur) out->excur[(size_t)t * n + o] = he[(size_t)t * n + i];
-    }
-    if (out->mean) out->mean[o] = hm[i];
-    if (out->sd) out->sd[o] = hs[i];
-  }
+  if (out->count) scatter_rows(out->count, hc.data(), T, n, s.perm);
+  if (out->prob) scatter_rows(out->prob, hp.data(), T, n, s.perm);
+  if (out->excur) scatter_rows(out->excur, he.data(), T, n, s.perm);
+  if (out->mean) scatter_rows(out->mean, hm.data(), 1, n, s.perm);
+  if (out->sd) scatter_rows(out->sd, hs.data(), 1, n, s.perm);
   for (int k = 0; out->n_flat && k < G; ++k) out->n_flat[k] = (int64_t)hf[k];
+  return ST_OK;
+}
+
+int store_excursions(st_handle_s *h, const char *who, const DrawStore &s, const st_excursion_spec *spec, const st_excursion_out *w,
+                     const st_excursion_out *yhat) {
+  if (s.rc || s.n == 0) return s.rc;
+  if (const int rc = exc_check_spec(h, who, spec, s.K, s.n_thr_values(), w, yhat)) return rc;
+  if (yhat && s.yhat_needs_X) { h->err = std::string(who) + ": yhat needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  for (int which = 0; which < 2; ++which)
+    if (const int rc = series_exc_store(h, who, s, which ? s.yhat : s.w, spec, which ? yhat : w)) return rc;
   return ST_OK;
 }

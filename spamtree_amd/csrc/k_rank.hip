@@ -5,6 +5,7 @@
 #include "diag_kernels.hpp"
 #include "norm_quantile.hpp"
 #include "rank_kernels.hpp"
+#include "draw_store.hpp"
 
 // R rows of Kpad = 2^k doubles each in LDS (row r at lds + r Kpad), every row sorted ascending by a bitonic network over the
 // workgroup (qt_sort_rows' network).  The rows are in LDS behind a barrier on entry and sorted behind one on return.
@@ -263,8 +264,9 @@ bool series_rank_plan(long long K, size_t lds_limit, int *R, int *Kpad, int *Kz,
 static bool rank_q_out(const st_rank_out *o) { return o && o->ess_q; }
 static bool rank_exc_out(const st_rank_out *o) { return o && (o->ess_exc || o->mcse_prob || o->prob); }
 
-int rank_check_spec(st_handle_s *h, const char *who, const st_rank_spec *spec, long long K, long long n_thr_values,
-                    const st_rank_out *w, const st_rank_out *yhat) {
+// what the three calls refuse of a spec and its outputs (K stored draws, n_thr_values thresholds per t)
+static int rank_check_spec(st_handle_s *h, const char *who, const st_rank_spec *spec, long long K, long long n_thr_values,
+                           const st_rank_out *w, const st_rank_out *yhat) {
   const std::string W = std::string(who) + ": ";
   if (!spec) { h->err = W + "no spec"; return ST_ERR_USAGE; }
   if (spec->max_lag < 0) { h->err = W + "max_lag must not be negative (0: the default cap)"; return ST_ERR_USAGE; }
@@ -272,18 +274,10 @@ int rank_check_spec(st_handle_s *h, const char *who, const st_rank_spec *spec, l
     h->err = W + "n_prob = " + std::to_string(spec->n_prob) + " must lie in 0 .. " + std::to_string(ST_RANK_MAX_PROBS);
     return ST_ERR_USAGE;
   }
-  if (spec->n_thr < 0 || spec->n_thr > ST_EXC_MAX_THRESHOLDS) {
-    h->err = W + "n_thr = " + std::to_string(spec->n_thr) + " must lie in 0 .. " + std::to_string(ST_EXC_MAX_THRESHOLDS);
-    return ST_ERR_USAGE;
-  }
   if (spec->n_prob > 0 && !spec->prob) { h->err = W + "n_prob = " + std::to_string(spec->n_prob) + " without prob"; return ST_ERR_USAGE; }
-  if (spec->n_thr > 0 && !spec->thr) { h->err = W + "n_thr = " + std::to_string(spec->n_thr) + " without thr"; return ST_ERR_USAGE; }
   for (int k = 0; k < spec->n_prob; ++k)
     if (!(spec->prob[k] > 0.0 && spec->prob[k] < 1.0)) { h->err = W + "prob " + std::to_string(k) + " must lie strictly inside (0, 1)"; return ST_ERR_USAGE; }
-  for (long long k = 0; k < (long long)spec->n_thr * n_thr_values; ++k)
-    if (!std::isfinite(spec->thr[k])) { h->err = W + "threshold " + std::to_string(k) + " is not finite"; return ST_ERR_USAGE; }
-  for (int t = 0; spec->side && t < spec->n_thr; ++t)
-    if (spec->side[t] != 1 && spec->side[t] != -1) { h->err = W + "side " + std::to_string(t) + " must be +1 or -1"; return ST_ERR_USAGE; }
+  if (const int rc = check_thresholds(W, spec->n_thr, 0, spec->thr, spec->side, n_thr_values, h->err)) return rc;
   if (spec->n_prob == 0 && (rank_q_out(w) || rank_q_out(yhat))) { h->err = W + "ess_q needs prob"; return ST_ERR_USAGE; }
   if (spec->n_thr == 0 && (rank_exc_out(w) || rank_exc_out(yhat))) { h->err = W + "ess_exc, mcse_prob and prob need thresholds"; return ST_ERR_USAGE; }
   if (K < ST_DIAG_MIN_DRAWS) {
@@ -294,9 +288,12 @@ int rank_check_spec(st_handle_s *h, const char *who, const st_rank_spec *spec, l
   return ST_OK;
 }
 
-int series_rank_store(st_handle_s *h, const char *who, const double *draws, long long n, long long K, const int *d_outcome, int G,
-                      bool thr_per_series, const long long *perm, const st_rank_spec *spec, const st_rank_out *out) {
-  if (!out || n <= 0) return ST_OK;
+// The outputs out asks for, of one of the store's two sets of draws, into out's host arrays (any may be NULL), element i of the
+// store at out[perm ? perm[i] : i].  store_rank_diagnostics has checked the spec and K.
+static int series_rank_store(st_handle_s *h, const char *who, const DrawStore &s, const double *draws, const st_rank_spec *spec,
+                             const st_rank_out *out) {
+  const long long n = s.n, K = s.K;
+  if (!out) return ST_OK;
   const bool bulk = out->rhat_rank || out->rhat_bulk || out->ess_bulk || out->lags_bulk, fold = out->rhat_rank || out->rhat_fold;
   const int n_prob = out->ess_q ? spec->n_prob : 0, n_thr = rank_exc_out(out) ? spec->n_thr : 0;
   if (!bulk && !fold && !out->ess_tail && !n_prob && !n_thr) return ST_OK;
@@ -311,17 +308,13 @@ int series_rank_store(st_handle_s *h, const char *who, const double *draws, long
   for (int k = 0; k < n_prob; ++k) A.jq[k] = series_rank_order(spec->prob[k], K);
   A.jq[ST_RANK_MAX_PROBS] = series_rank_order(0.05, K);
   A.jq[ST_RANK_MAX_PROBS + 1] = series_rank_order(0.95, K);
-  A.outcome = d_outcome; A.per_series = thr_per_series ? 1 : 0; A.thr_stride = thr_per_series ? n : G;
+  A.outcome = s.d_outcome; A.per_series = s.thr_per_series ? 1 : 0; A.thr_stride = s.n_thr_values();
   HCHK(h, hipSetDevice(h->device));
   DevBuf<double> d_thr, d_scr, d_out;
   DevBuf<int> d_lags;
-  if (n_thr) {   // the thresholds in store order
-    std::vector<double> tv((size_t)n_thr * A.thr_stride);
-    for (int t = 0; t < n_thr; ++t) {
-      for (long long j = 0; j < A.thr_stride; ++j)
-        tv[(size_t)t * A.thr_stride + j] = spec->thr[(size_t)t * A.thr_stride + ((thr_per_series && perm) ? perm[j] : j)];
-      if (spec->side && spec->side[t] < 0) A.neg |= 1u << t;
-    }
+  if (n_thr) {
+    std::vector<double> tv;
+    A.neg = thresholds_in_store_order(spec->thr, spec->side, n_thr, A.thr_stride, s.thr_per_series, s.perm, tv);
     HCHK(h, d_thr.upload(tv));
     A.thr = d_thr.p;
   }
@@ -365,13 +358,19 @@ int series_rank_store(st_handle_s *h, const char *who, const double *draws, long
   }
   if (out->lags_bulk) HCHK(h, hipMemcpyAsync(tl.data(), d_lags.p, tl.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HCHK(h, hipStreamSynchronize(h->stream));
-  for (size_t k = 0; k < tmp.size(); ++k) {
-    if (tmp[k].empty()) continue;
-    for (int row = 0; row < parts[k].rows; ++row)
-      for (long long i = 0; i < n; ++i) parts[k].dst[(size_t)row * n + (perm ? perm[i] : i)] = tmp[k][(size_t)row * n + i];
-  }
-  if (out->lags_bulk)
-    for (long long i = 0; i < n; ++i) out->lags_bulk[perm ? perm[i] : i] = tl[i];
+  for (size_t k = 0; k < tmp.size(); ++k)
+    if (!tmp[k].empty()) scatter_rows(parts[k].dst, tmp[k].data(), parts[k].rows, n, s.perm);
+  if (out->lags_bulk) scatter_rows(out->lags_bulk, tl.data(), 1, n, s.perm);
+  return ST_OK;
+}
+
+int store_rank_diagnostics(st_handle_s *h, const char *who, const DrawStore &s, const st_rank_spec *spec, const st_rank_out *w,
+                           const st_rank_out *yhat) {
+  if (s.rc || s.n == 0) return s.rc;
+  if (const int rc = rank_check_spec(h, who, spec, s.K, s.n_thr_values(), w, yhat)) return rc;
+  if (yhat && s.yhat_needs_X) { h->err = std::string(who) + ": yhat needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  for (int which = 0; which < 2; ++which)
+    if (const int rc = series_rank_store(h, who, s, which ? s.yhat : s.w, spec, which ? yhat : w)) return rc;
   return ST_OK;
 }
 

@@ -40,6 +40,13 @@ struct QtArgs {
   double q;
   double *out;
 };
+// The launch rule of k_qtile and k_score_crps, which sort with qt_sort_rows: rows padded to Kpad = 2^k >= max(keep, 2), R rows per
+// workgroup within 128 KiB of LDS (R Kpad doubles), grid ceil(n / R)
+static inline void qtile_plan(long long keep, int *Kpad, int *R) {
+  *Kpad = 2;
+  while (*Kpad < keep) *Kpad <<= 1;
+  *R = std::max(1, std::min(8, (int)(128 * 1024 / ((size_t)*Kpad * 8))));
+}
 
 // The sort of k_qtile, shared with k_score_crps (k_points_score.hip): R rows of K = 2^k doubles each in LDS (row r at lds + r K),
 // every row sorted ascending by a bitonic network over the NT threads of the workgroup.  The rows are in LDS behind a barrier on

@@ -68,13 +68,3 @@ struct RankArgs {
 bool series_rank_plan(long long K, size_t lds_limit, int *R, int *Kpad, int *Kz, int *z_global);
 // the order statistic of a probability: min(max(ceil(prob K), 1), K - 1) - 1
 int series_rank_order(double prob, long long K);
-
-// What the three calls refuse of a spec and its outputs (K stored draws, n_thr_values thresholds per t): ST_ERR_USAGE with a text.
-struct st_handle_s;
-int rank_check_spec(st_handle_s *h, const char *who, const st_rank_spec *spec, long long K, long long n_thr_values,
-                    const st_rank_out *w, const st_rank_out *yhat);
-// The one launcher of the three C-ABI calls, over the first K rows of the store draws[K][n]: out's host arrays (any may be NULL),
-// element i of the store at out[perm ? perm[i] : i].  d_outcome: the series' outcomes on the device in store order (NULL: one);
-// thr_per_series: spec->thr is n_thr x n in the order of the outputs, else n_thr x G.  The caller has checked the spec and K.
-int series_rank_store(st_handle_s *h, const char *who, const double *draws, long long n, long long K, const int *d_outcome, int G,
-                      bool thr_per_series, const long long *perm, const st_rank_spec *spec, const st_rank_out *out);

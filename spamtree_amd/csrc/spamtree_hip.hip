@@ -26,9 +26,7 @@
 
 #include "st_handle.hpp"
 #include "misc_kernels.hpp"
-#include "diag_kernels.hpp"
-#include "excursion_kernels.hpp"
-#include "rank_kernels.hpp"
+#include "draw_store.hpp"
 #include "rows_score.hpp"
 #include <new>
 
@@ -1619,55 +1617,52 @@ extern "C" int st_summary_reserve(st_handle h, int64_t keep) {
   h->draws_cap = keep;
   return ST_OK;
 }
-extern "C" int st_summary_quantile(st_handle h, double q, double *w_q, double *yhat_q) {
-  if (!h || !(q >= 0.0 && q <= 1.0)) return ST_ERR_USAGE;
-  if (h->n_draws == 0) { h->err = "no draw stored: call st_summary_reserve before the saved iterations"; return ST_ERR_USAGE; }
+// ---- the summaries of stored draws (draw_store.hpp).  The fit's rows as a store: device row order, the domains and thresholds
+// go by outcome (d_mv), the outputs come back in model row order (dev2model)
+static DrawStore rows_store(st_handle h) {
+  DrawStore s;
+  if (!h) { s.rc = ST_ERR_USAGE; return s; }
+  s.w = h->d_draws_w.p; s.yhat = h->d_draws_yhat.p; s.n = h->n_all; s.K = h->n_draws;
+  s.d_outcome = h->d_mv.p; s.G = h->q; s.perm = h->dev2model.data(); s.d_scratch = h->d_tmp_n.p;
+  s.reserve = "st_summary_reserve";
+  return s;
+}
+// k_qtile (misc_kernels.hpp) over the stored draws of w and yhat into w_q and yhat_q (NULL: skipped), through the store's scratch
+int store_quantile(st_handle_s *h, const char *who, const DrawStore &s, double q, double *w_q, double *yhat_q) {
+  if (s.rc) return s.rc;
+  if (!(q >= 0.0 && q <= 1.0)) { h->err = std::string(who) + ": q must lie in [0, 1]"; return ST_ERR_USAGE; }
+  if (s.K == 0) { h->err = std::string(who) + ": no draw stored (call " + s.reserve + " before the saved iterations)"; return ST_ERR_USAGE; }
+  if (yhat_q && s.yhat_needs_X) { h->err = std::string(who) + ": yhat_q needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
   HCHK(h, hipSetDevice(h->device));
-  int Kpad = 2;
-  while (Kpad < h->n_draws) Kpad <<= 1;
-  const int R = std::max(1, std::min(8, (int)(128 * 1024 / ((size_t)Kpad * 8))));
-  const size_t lds = (size_t)R * Kpad * sizeof(double);
+  QtArgs A;
+  A.n = s.n; A.keep = (int)s.K; A.q = q; A.out = s.d_scratch;
+  qtile_plan(s.K, &A.Kpad, &A.R);
+  const size_t lds = (size_t)A.R * A.Kpad * sizeof(double);
   (void)hipFuncSetAttribute((const void *)k_qtile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_limit);
+  std::vector<double> tmp(s.perm ? (size_t)s.n : 0);
   for (int which = 0; which < 2; ++which) {
-    double *dst = which == 0 ? w_q : yhat_q;
+    double *dst = which ? yhat_q : w_q;
     if (!dst) continue;
-    QtArgs A;
-    A.draws = which == 0 ? h->d_draws_w.p : h->d_draws_yhat.p; A.n = h->n_all; A.keep = (int)h->n_draws; A.Kpad = Kpad; A.R = R; A.q = q;
-    A.out = h->d_tmp_n.p;
-    hipLaunchKernelGGL(k_qtile, dim3((unsigned)((h->n_all + R - 1) / R)), dim3(NT), lds, h->stream, A);
+    A.draws = which ? s.yhat : s.w;
+    hipLaunchKernelGGL(k_qtile, dim3((unsigned)((s.n + A.R - 1) / A.R)), dim3(NT), lds, h->stream, A);
     HCHK(h, hipGetLastError());
-    const int rc = download_rows(h, h->d_tmp_n.p, dst);
-    if (rc) return rc;
+    HCHK(h, hipMemcpyAsync(s.perm ? tmp.data() : dst, s.d_scratch, (size_t)s.n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HCHK(h, hipStreamSynchronize(h->stream));
+    if (s.perm) scatter_rows(dst, tmp.data(), 1, s.n, s.perm);
   }
   return ST_OK;
 }
-// ESS, MCSE, sd and split-R-hat of every row's stored draws (diag_kernels.hpp): k_series_diag over each requested store
+extern "C" int st_summary_quantile(st_handle h, double q, double *w_q, double *yhat_q) {
+  return store_quantile(h, __func__, rows_store(h), q, w_q, yhat_q);
+}
 extern "C" int st_summary_diagnostics(st_handle h, int32_t max_lag, const st_series_diag *w, const st_series_diag *yhat) {
-  if (!h) return ST_ERR_USAGE;
-  if (max_lag < 0) { h->err = "st_summary_diagnostics: max_lag must not be negative (0: the default cap)"; return ST_ERR_USAGE; }
-  if (h->n_draws < ST_DIAG_MIN_DRAWS) {
-    h->err = "st_summary_diagnostics: " + std::to_string(h->n_draws) + " draws stored, the diagnostics need at least " +
-             std::to_string(ST_DIAG_MIN_DRAWS) + " (call st_summary_reserve before the saved iterations)";
-    return ST_ERR_USAGE;
-  }
-  if (const int rc = series_diag_store(h, "st_summary_diagnostics", h->d_draws_w.p, h->n_all, h->n_draws, max_lag, h->dev2model.data(), w)) return rc;
-  return series_diag_store(h, "st_summary_diagnostics", h->d_draws_yhat.p, h->n_all, h->n_draws, max_lag, h->dev2model.data(), yhat);
+  return store_diagnostics(h, __func__, rows_store(h), max_lag, w, yhat);
 }
-// exceedance counts, excursion functions and the simultaneous band of every row's stored draws (excursion_kernels.hpp): the
-// domains are the outcomes (d_mv, device order), the outputs come back in model row order
 extern "C" int st_summary_excursions(st_handle h, const st_excursion_spec *spec, const st_excursion_out *w, const st_excursion_out *yhat) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = exc_check_spec(h, "st_summary_excursions", spec, h->n_draws, h->q, w, yhat)) return rc;
-  if (const int rc = store_excursions(h, "st_summary_excursions", h->d_draws_w.p, h->n_all, h->n_draws, h->d_mv.p, h->q, false, h->dev2model.data(), spec, w)) return rc;
-  return store_excursions(h, "st_summary_excursions", h->d_draws_yhat.p, h->n_all, h->n_draws, h->d_mv.p, h->q, false, h->dev2model.data(), spec, yhat);
+  return store_excursions(h, __func__, rows_store(h), spec, w, yhat);
 }
-// rank-normalised R-hat, bulk, tail, quantile and exceedance ESS of every row's stored draws (rank_kernels.hpp): k_series_rank over
-// each requested store; the thresholds go by outcome (d_mv, device order), the outputs come back in model row order
 extern "C" int st_summary_rank_diagnostics(st_handle h, const st_rank_spec *spec, const st_rank_out *w, const st_rank_out *yhat) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = rank_check_spec(h, "st_summary_rank_diagnostics", spec, h->n_draws, h->q, w, yhat)) return rc;
-  if (const int rc = series_rank_store(h, "st_summary_rank_diagnostics", h->d_draws_w.p, h->n_all, h->n_draws, h->d_mv.p, h->q, false, h->dev2model.data(), spec, w)) return rc;
-  return series_rank_store(h, "st_summary_rank_diagnostics", h->d_draws_yhat.p, h->n_all, h->n_draws, h->d_mv.p, h->q, false, h->dev2model.data(), spec, yhat);
+  return store_rank_diagnostics(h, __func__, rows_store(h), spec, w, yhat);
 }
 extern "C" int st_summary_get(st_handle h, double *w_mean, double *yhat_mean, int64_t *n_accumulated) {
   if (!h) return ST_ERR_USAGE;
@@ -1763,12 +1758,10 @@ extern "C" int st_rows_score_accumulate(st_handle h) {
 // (draws accumulated, CRPS summed), so st_rows_score_get followed by st_rows_score_totals sorts the draws once.
 static int rows_finish(st_handle h, bool need_crps, bool *have_crps) {
   const bool can = h->n_draws > 0 && h->rs_n_held > 0;
-  if (need_crps && can && h->rs_crps_epoch != h->draws_epoch) {   // the launch rule of st_summary_quantile
+  if (need_crps && can && h->rs_crps_epoch != h->draws_epoch) {
     ScoreCrpsArgs C;
-    int Kpad = 2;
-    while (Kpad < h->n_draws) Kpad <<= 1;
-    C.draws = h->d_draws_yhat.p; C.y = h->d_rs_hold.p; C.n = h->n_all; C.keep = (int)h->n_draws; C.Kpad = Kpad;
-    C.R = std::max(1, std::min(8, (int)(128 * 1024 / ((size_t)Kpad * 8))));
+    C.draws = h->d_draws_yhat.p; C.y = h->d_rs_hold.p; C.n = h->n_all; C.keep = (int)h->n_draws;
+    qtile_plan(h->n_draws, &C.Kpad, &C.R);
     C.out = h->d_rs_crps.p;
     const int e = points_score_crps_launch(C, h->lds_limit, h->stream);
     if (e) { h->err = std::string("st_rows_score crps launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }

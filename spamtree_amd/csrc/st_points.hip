@@ -1,16 +1,16 @@
 // st_points.hip -- the C-ABI of new-point prediction (st_points_*): the device step of st_points_set / st_points_set_joint, predict,
-// accumulate, the summaries and quantiles, the linear functionals of the predictions (st_points_functionals_*) and the scores of
-// held-out observations (st_points_score_*).
+// accumulate, the running summaries, the linear functionals of the predictions (st_points_functionals_*) and the scores of
+// held-out observations (st_points_score_*).  The summaries of the stored draws -- quantiles, diagnostics, excursions, rank
+// diagnostics of the points and of the functionals -- are a resolver each (points_store, fun_store) and the store_* calls of
+// draw_store.hpp, which the fit's rows go through too.
 // predict_points.hpp, predict_joint.hpp, points_fun.hpp and points_score.hpp have the model; the launch structures of a point set and the term lists
 // of its functionals are built without a device call in points_layout.cpp; the kernels and their launchers live in k_predict.hip,
-// k_predict_joint.hip, k_points_acc.hip, k_points_fun.hip and k_points_score.hip (k_qtile in k_misc.hip).
+// k_predict_joint.hip, k_points_acc.hip, k_points_fun.hip and k_points_score.hip.
 #include <memory>
 
 #include "st_handle.hpp"
 #include "misc_kernels.hpp"
-#include "diag_kernels.hpp"
-#include "excursion_kernels.hpp"
-#include "rank_kernels.hpp"
+#include "draw_store.hpp"
 #include "points_layout.hpp"
 #include "points_score.hpp"
 
@@ -476,20 +476,14 @@ extern "C" int st_points_summary_get_cov(st_handle h, double *cov) {
   return ST_OK;
 }
 
-extern "C" int st_points_summary_get(st_handle h, double *mean, double *var, double *w_mean, double *yhat_mean, int64_t *n_accumulated) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = points_refuse(h, "st_points_summary_get")) return rc;
-  PointSet *ps = h->pts;
-  if (n_accumulated) *n_accumulated = ps->n_acc;
-  if (ps->n_acc == 0) { h->err = "st_points_summary_get: no iteration accumulated"; return ST_ERR_USAGE; }
-  if (yhat_mean && !ps->has_X) { h->err = "st_points_summary_get: yhat_mean needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
-  const long long n = ps->n;
+// The Welford accumulators d_acc (PA_NACC x n) after `count` iterations, read out into the caller's arrays (any may be NULL)
+static int pa_read_out(st_handle h, const double *d_acc, long long n, long long count, double *mean, double *var, double *w_mean, double *yhat_mean) {
   if (n == 0) return ST_OK;
   HCHK(h, hipSetDevice(h->device));
   std::vector<double> acc((size_t)PA_NACC * n);
-  HCHK(h, hipMemcpyAsync(acc.data(), ps->d_acc.p, acc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipMemcpyAsync(acc.data(), d_acc, acc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HCHK(h, hipStreamSynchronize(h->stream));
-  const double cnt = (double)ps->n_acc;
+  const double cnt = (double)count;
   const double *a = acc.data();
   for (long long i = 0; i < n; ++i) {
     if (mean) mean[i] = a[PA_MEAN * n + i];
@@ -500,76 +494,39 @@ extern "C" int st_points_summary_get(st_handle h, double *mean, double *var, dou
   return ST_OK;
 }
 
-// k_qtile over the first n_kept rows of [keep][n] stores (draws[0]: w, draws[1]: yhat) into dst[which] (NULL: skipped), through
-// n doubles of device scratch
-static int points_qtile(st_handle h, const double *const draws[2], long long n, long long n_kept, double q, double *scratch, double *const dst[2]) {
-  HCHK(h, hipSetDevice(h->device));
-  int Kpad = 2;
-  while (Kpad < n_kept) Kpad <<= 1;
-  const int R = std::max(1, std::min(8, (int)(128 * 1024 / ((size_t)Kpad * 8))));
-  const size_t lds = (size_t)R * Kpad * sizeof(double);
-  (void)hipFuncSetAttribute((const void *)k_qtile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_limit);
-  for (int which = 0; which < 2; ++which) {
-    if (!dst[which]) continue;
-    QtArgs A;
-    A.draws = draws[which]; A.n = n; A.keep = (int)n_kept; A.Kpad = Kpad; A.R = R; A.q = q;
-    A.out = scratch;
-    hipLaunchKernelGGL(k_qtile, dim3((unsigned)((n + R - 1) / R)), dim3(NT), lds, h->stream, A);
-    HCHK(h, hipGetLastError());
-    HCHK(h, hipMemcpyAsync(dst[which], scratch, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HCHK(h, hipStreamSynchronize(h->stream));
-  }
-  return ST_OK;
+extern "C" int st_points_summary_get(st_handle h, double *mean, double *var, double *w_mean, double *yhat_mean, int64_t *n_accumulated) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_summary_get")) return rc;
+  PointSet *ps = h->pts;
+  if (n_accumulated) *n_accumulated = ps->n_acc;
+  if (ps->n_acc == 0) { h->err = "st_points_summary_get: no iteration accumulated"; return ST_ERR_USAGE; }
+  if (yhat_mean && !ps->has_X) { h->err = "st_points_summary_get: yhat_mean needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  return pa_read_out(h, ps->d_acc.p, ps->n, ps->n_acc, mean, var, w_mean, yhat_mean);
 }
 
+// ---- the summaries of stored draws (draw_store.hpp).  The point set as a store: caller order, the domains and thresholds go by
+// outcome (d_pmv); d_out serves as the quantile's scratch, the next st_points_accumulate rewrites it anyway
+static DrawStore points_store(st_handle h, const char *who) {
+  DrawStore s;
+  s.rc = h ? points_refuse(h, who) : ST_ERR_USAGE;
+  if (s.rc) return s;
+  const PointSet *ps = h->pts;
+  s.w = ps->d_keep_w.p; s.yhat = ps->d_keep_yhat.p; s.n = ps->n; s.K = ps->n_kept;
+  s.d_outcome = ps->d_pmv.p; s.G = h->q; s.d_scratch = ps->d_out.p;
+  s.reserve = "st_points_summary_reserve"; s.yhat_needs_X = !ps->has_X;
+  return s;
+}
 extern "C" int st_points_summary_quantile(st_handle h, double q, double *w_q, double *yhat_q) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = points_refuse(h, "st_points_summary_quantile")) return rc;
-  if (!(q >= 0.0 && q <= 1.0)) { h->err = "st_points_summary_quantile: q must lie in [0, 1]"; return ST_ERR_USAGE; }
-  PointSet *ps = h->pts;
-  if (ps->n_kept == 0) { h->err = "st_points_summary_quantile: no draw stored (call st_points_summary_reserve before the saved iterations)"; return ST_ERR_USAGE; }
-  if (yhat_q && !ps->has_X) { h->err = "st_points_summary_quantile: yhat_q needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
-  double *const dst[2] = {w_q, yhat_q};
-  const double *const draws[2] = {ps->d_keep_w.p, ps->d_keep_yhat.p};
-  return points_qtile(h, draws, ps->n, ps->n_kept, q, ps->d_out.p, dst);   // d_out as scratch: the next st_points_accumulate rewrites it anyway
+  return store_quantile(h, __func__, points_store(h, __func__), q, w_q, yhat_q);
 }
-
 extern "C" int st_points_summary_diagnostics(st_handle h, int32_t max_lag, const st_series_diag *w, const st_series_diag *yhat) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = points_refuse(h, "st_points_summary_diagnostics")) return rc;
-  if (max_lag < 0) { h->err = "st_points_summary_diagnostics: max_lag must not be negative (0: the default cap)"; return ST_ERR_USAGE; }
-  PointSet *ps = h->pts;
-  if (ps->n == 0) return ST_OK;
-  if (ps->n_kept < ST_DIAG_MIN_DRAWS) {
-    h->err = "st_points_summary_diagnostics: " + std::to_string(ps->n_kept) + " draws stored, the diagnostics need at least " +
-             std::to_string(ST_DIAG_MIN_DRAWS) + " (call st_points_summary_reserve before the saved iterations)";
-    return ST_ERR_USAGE;
-  }
-  if (yhat && !ps->has_X) { h->err = "st_points_summary_diagnostics: yhat needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
-  if (const int rc = series_diag_store(h, "st_points_summary_diagnostics", ps->d_keep_w.p, ps->n, ps->n_kept, max_lag, nullptr, w)) return rc;
-  return series_diag_store(h, "st_points_summary_diagnostics", ps->d_keep_yhat.p, ps->n, ps->n_kept, max_lag, nullptr, yhat);
+  return store_diagnostics(h, __func__, points_store(h, __func__), max_lag, w, yhat);
 }
-
 extern "C" int st_points_summary_excursions(st_handle h, const st_excursion_spec *spec, const st_excursion_out *w, const st_excursion_out *yhat) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = points_refuse(h, "st_points_summary_excursions")) return rc;
-  PointSet *ps = h->pts;
-  if (ps->n == 0) return ST_OK;
-  if (const int rc = exc_check_spec(h, "st_points_summary_excursions", spec, ps->n_kept, h->q, w, yhat)) return rc;
-  if (yhat && !ps->has_X) { h->err = "st_points_summary_excursions: yhat needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
-  if (const int rc = store_excursions(h, "st_points_summary_excursions", ps->d_keep_w.p, ps->n, ps->n_kept, ps->d_pmv.p, h->q, false, nullptr, spec, w)) return rc;
-  return store_excursions(h, "st_points_summary_excursions", ps->d_keep_yhat.p, ps->n, ps->n_kept, ps->d_pmv.p, h->q, false, nullptr, spec, yhat);
+  return store_excursions(h, __func__, points_store(h, __func__), spec, w, yhat);
 }
-
 extern "C" int st_points_summary_rank_diagnostics(st_handle h, const st_rank_spec *spec, const st_rank_out *w, const st_rank_out *yhat) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = points_refuse(h, "st_points_summary_rank_diagnostics")) return rc;
-  PointSet *ps = h->pts;
-  if (ps->n == 0) return ST_OK;
-  if (const int rc = rank_check_spec(h, "st_points_summary_rank_diagnostics", spec, ps->n_kept, h->q, w, yhat)) return rc;
-  if (yhat && !ps->has_X) { h->err = "st_points_summary_rank_diagnostics: yhat needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
-  if (const int rc = series_rank_store(h, "st_points_summary_rank_diagnostics", ps->d_keep_w.p, ps->n, ps->n_kept, ps->d_pmv.p, h->q, false, nullptr, spec, w)) return rc;
-  return series_rank_store(h, "st_points_summary_rank_diagnostics", ps->d_keep_yhat.p, ps->n, ps->n_kept, ps->d_pmv.p, h->q, false, nullptr, spec, yhat);
+  return store_rank_diagnostics(h, __func__, points_store(h, __func__), spec, w, yhat);
 }
 
 // ---- linear functionals of the predictions (points_fun.hpp): the term lists come from functionals_layout, without a device call
@@ -641,74 +598,33 @@ extern "C" int st_points_functionals_get(st_handle h, double *mean, double *var,
   if (n_accumulated) *n_accumulated = fs->n_acc;
   if (fs->n_acc == 0) { h->err = "st_points_functionals_get: no iteration accumulated"; return ST_ERR_USAGE; }
   if (yhat_mean && !ps->has_X) { h->err = "st_points_functionals_get: yhat_mean needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
-  HCHK(h, hipSetDevice(h->device));
-  const long long n = fs->n_fun;
-  std::vector<double> acc((size_t)PA_NACC * n);
-  HCHK(h, hipMemcpyAsync(acc.data(), fs->d_acc.p, acc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  const double cnt = (double)fs->n_acc;
-  const double *a = acc.data();
-  for (long long i = 0; i < n; ++i) {   // the expressions of st_points_summary_get
-    if (mean) mean[i] = a[PA_MEAN * n + i];
-    if (var) var[i] = a[PA_VAR * n + i] / cnt + a[PA_M2 * n + i] / cnt;
-    if (w_mean) w_mean[i] = a[PA_W * n + i] / cnt;
-    if (yhat_mean) yhat_mean[i] = a[PA_YHAT * n + i] / cnt;
-  }
-  return ST_OK;
+  return pa_read_out(h, fs->d_acc.p, fs->n_fun, fs->n_acc, mean, var, w_mean, yhat_mean);
 }
 
+// The functionals as a store: caller order, one domain, a threshold value per functional.  The functionals of an empty point set
+// store no draw: an empty store.
+static DrawStore fun_store(st_handle h, const char *who) {
+  DrawStore s;
+  s.rc = h ? fun_refuse(h, who, false) : ST_ERR_USAGE;
+  if (s.rc) return s;
+  const PointSet *ps = h->pts;
+  const FunSet *fs = ps->fun.get();
+  s.w = fs->d_keep_w.p; s.yhat = fs->d_keep_yhat.p; s.n = ps->n == 0 ? 0 : fs->n_fun; s.K = fs->n_kept;
+  s.thr_per_series = true; s.d_scratch = fs->d_q.p;
+  s.reserve = "st_points_summary_reserve"; s.yhat_needs_X = !ps->has_X;
+  return s;
+}
 extern "C" int st_points_functionals_quantile(st_handle h, double q, double *w_q, double *yhat_q) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = fun_refuse(h, "st_points_functionals_quantile", false)) return rc;
-  if (!(q >= 0.0 && q <= 1.0)) { h->err = "st_points_functionals_quantile: q must lie in [0, 1]"; return ST_ERR_USAGE; }
-  const PointSet *ps = h->pts;
-  FunSet *fs = ps->fun.get();
-  if (fs->n_kept == 0) { h->err = "st_points_functionals_quantile: no draw stored (call st_points_summary_reserve before the saved iterations)"; return ST_ERR_USAGE; }
-  if (yhat_q && !ps->has_X) { h->err = "st_points_functionals_quantile: yhat_q needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
-  double *const dst[2] = {w_q, yhat_q};
-  const double *const draws[2] = {fs->d_keep_w.p, fs->d_keep_yhat.p};
-  return points_qtile(h, draws, fs->n_fun, fs->n_kept, q, fs->d_q.p, dst);
+  return store_quantile(h, __func__, fun_store(h, __func__), q, w_q, yhat_q);
 }
-
 extern "C" int st_points_functionals_diagnostics(st_handle h, int32_t max_lag, const st_series_diag *w, const st_series_diag *yhat) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = fun_refuse(h, "st_points_functionals_diagnostics", false)) return rc;
-  if (max_lag < 0) { h->err = "st_points_functionals_diagnostics: max_lag must not be negative (0: the default cap)"; return ST_ERR_USAGE; }
-  const PointSet *ps = h->pts;
-  FunSet *fs = ps->fun.get();
-  if (fs->n_fun == 0 || ps->n == 0) return ST_OK;   // (the functionals of an empty point set store no draw)
-  if (fs->n_kept < ST_DIAG_MIN_DRAWS) {
-    h->err = "st_points_functionals_diagnostics: " + std::to_string(fs->n_kept) + " draws stored, the diagnostics need at least " +
-             std::to_string(ST_DIAG_MIN_DRAWS) + " (call st_points_summary_reserve before the saved iterations)";
-    return ST_ERR_USAGE;
-  }
-  if (yhat && !ps->has_X) { h->err = "st_points_functionals_diagnostics: yhat needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
-  if (const int rc = series_diag_store(h, "st_points_functionals_diagnostics", fs->d_keep_w.p, fs->n_fun, fs->n_kept, max_lag, nullptr, w)) return rc;
-  return series_diag_store(h, "st_points_functionals_diagnostics", fs->d_keep_yhat.p, fs->n_fun, fs->n_kept, max_lag, nullptr, yhat);
+  return store_diagnostics(h, __func__, fun_store(h, __func__), max_lag, w, yhat);
 }
-
 extern "C" int st_points_functionals_excursions(st_handle h, const st_excursion_spec *spec, const st_excursion_out *w, const st_excursion_out *yhat) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = fun_refuse(h, "st_points_functionals_excursions", false)) return rc;
-  const PointSet *ps = h->pts;
-  FunSet *fs = ps->fun.get();
-  if (fs->n_fun == 0 || ps->n == 0) return ST_OK;   // (the functionals of an empty point set store no draw)
-  if (const int rc = exc_check_spec(h, "st_points_functionals_excursions", spec, fs->n_kept, fs->n_fun, w, yhat)) return rc;
-  if (yhat && !ps->has_X) { h->err = "st_points_functionals_excursions: yhat needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
-  if (const int rc = store_excursions(h, "st_points_functionals_excursions", fs->d_keep_w.p, fs->n_fun, fs->n_kept, nullptr, 1, true, nullptr, spec, w)) return rc;
-  return store_excursions(h, "st_points_functionals_excursions", fs->d_keep_yhat.p, fs->n_fun, fs->n_kept, nullptr, 1, true, nullptr, spec, yhat);
+  return store_excursions(h, __func__, fun_store(h, __func__), spec, w, yhat);
 }
-
 extern "C" int st_points_functionals_rank_diagnostics(st_handle h, const st_rank_spec *spec, const st_rank_out *w, const st_rank_out *yhat) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = fun_refuse(h, "st_points_functionals_rank_diagnostics", false)) return rc;
-  const PointSet *ps = h->pts;
-  FunSet *fs = ps->fun.get();
-  if (fs->n_fun == 0 || ps->n == 0) return ST_OK;   // (the functionals of an empty point set store no draw)
-  if (const int rc = rank_check_spec(h, "st_points_functionals_rank_diagnostics", spec, fs->n_kept, fs->n_fun, w, yhat)) return rc;
-  if (yhat && !ps->has_X) { h->err = "st_points_functionals_rank_diagnostics: yhat needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
-  if (const int rc = series_rank_store(h, "st_points_functionals_rank_diagnostics", fs->d_keep_w.p, fs->n_fun, fs->n_kept, nullptr, 1, true, nullptr, spec, w)) return rc;
-  return series_rank_store(h, "st_points_functionals_rank_diagnostics", fs->d_keep_yhat.p, fs->n_fun, fs->n_kept, nullptr, 1, true, nullptr, spec, yhat);
+  return store_rank_diagnostics(h, __func__, fun_store(h, __func__), spec, w, yhat);
 }
 
 // ---- scores of held-out observations at the point set (points_score.hpp)
@@ -770,12 +686,10 @@ extern "C" int st_points_score_get(st_handle h, double *lpd, double *pit, double
     HCHK(h, hipMemcpyAsync(jacc.data(), sc->d_jacc.p, jacc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   }
   if (n_degenerate) HCHK(h, hipMemcpyAsync(&ndeg, sc->d_ndeg.p, sizeof(ndeg), hipMemcpyDeviceToHost, h->stream));
-  if (crps) {   // the launch rule of points_qtile
+  if (crps) {
     ScoreCrpsArgs A;
-    int Kpad = 2;
-    while (Kpad < ps->n_kept) Kpad <<= 1;
-    A.draws = ps->d_keep_yhat.p; A.y = sc->d_y.p; A.n = n; A.keep = (int)ps->n_kept; A.Kpad = Kpad;
-    A.R = std::max(1, std::min(8, (int)(128 * 1024 / ((size_t)Kpad * 8))));
+    A.draws = ps->d_keep_yhat.p; A.y = sc->d_y.p; A.n = n; A.keep = (int)ps->n_kept;
+    qtile_plan(ps->n_kept, &A.Kpad, &A.R);
     A.out = sc->d_crps.p;
     const int e = points_score_crps_launch(A, h->lds_limit, h->stream);
     if (e) { h->err = std::string("st_points_score_get launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
