@@ -221,6 +221,43 @@ int stm_mcmc_ranked(const st_problem *pb, const st_options *opt, const double *s
                     double *new_cond_cov, double *new_cov, const stm_functionals *fun, const stm_scores *scores,
                     const stm_diagnostics *diag, const stm_excursions *exc, const stm_rank_diagnostics *rk);
 
+/* Several chains in one fit.  stm_mcmc_chains is stm_mcmc_ranked plus one stm_chains (ch = NULL: stm_mcmc_ranked itself; n_chains = 1
+ * with seeds[0] = seed: the same, bit for bit).  It runs M = n_chains chains one after another on ONE handle.  Each chain is the
+ * fit from scratch: w = 0, the caller's beta and tausq, theta0[c] (or `theta`), the RAM adaptation restarted from mcmcsd, both slots
+ * factorised, then mcmc_burn + mcmc_thin mcmc_keep iterations with seeds[c]; the `seed` argument is not used when ch is given.
+ * Philox counters are the chain's own: the rows' streams take the iteration m, the point draws of streams 6 / 7 the chain's own
+ * saved index -- so chain c's columns of every per-draw output are, bit for bit, those of the single-chain call with seed = seeds[c]
+ * and theta = theta0[c].
+ * Every per-draw output has M mcmc_keep columns, chain-major: chain c at columns c mcmc_keep .. (c + 1) mcmc_keep - 1 (beta_mcmc:
+ * p x M mcmc_keep x q).  The stores hold the M mcmc_keep draws in the same order; a point store that is reserved at all (keep_draws
+ * > 0, or any stored-draw output) holds all of them.  The running sums are never reset between chains -- the Welford accumulators
+ * of the points and functionals, the score mixtures -- so means, variances, quantiles, excursions and scores are those of the pooled
+ * draws.  After the last chain the diagnostics are st_*_chain_diagnostics and st_*_chain_rank_diagnostics with n_chains = M.
+ * paramsd receives the last chain's factor, ch->paramsd every chain's; mcmc_time the sum, ch->chain_time each.
+ * Refused before the first factorisation: n_chains outside 1 .. ST_DIAG_MAX_CHAINS or seeds NULL (ST_ERR_USAGE); with n_chains > 1,
+ * mcmc_keep < 1 (ST_ERR_USAGE), world > 1, and stored draws with M mcmc_keep > 16384 (ST_ERR_UNSUPPORTED).  No chain exists yet to
+ * carry a text for these: stm_mcmc_chains_last_error() returns it, with the numbers, for the calling thread's last call ("" if that
+ * call refused nothing of its chains).  With n_chains > 1 and no point argument (n_new = 0, coords_new, mv_new, anchor_new NULL)
+ * the call is the plain chain, whether or not a summary of the rows is asked for. */
+typedef struct stm_chains {
+  int32_t n_chains;
+  const uint64_t *seeds;     /* M */
+  const double *theta0;      /* k x M, or NULL: every chain starts at `theta` */
+  double *paramsd;           /* k x k x M, or NULL */
+  double *chain_time;        /* M, or NULL */
+} stm_chains;
+int stm_mcmc_chains(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
+                    int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
+                    int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc, double *beta_mcmc,
+                    double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time, int64_t n_new,
+                    const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new, const double *X_new,
+                    const int64_t *joint_id_new, int64_t keep_draws, const double *quantiles, int32_t n_quantiles, double *new_w,
+                    double *new_cond_mean, double *new_cond_var, double *new_yhat, double *new_mean, double *new_var,
+                    double *new_w_mean, double *new_yhat_mean, double *new_w_q, double *new_yhat_q, int32_t *new_route,
+                    double *new_cond_cov, double *new_cov, const stm_functionals *fun, const stm_scores *scores,
+                    const stm_diagnostics *diag, const stm_excursions *exc, const stm_rank_diagnostics *rk, const stm_chains *ch);
+const char *stm_mcmc_chains_last_error(void);
+
 /* Criteria over the fit's own rows (include/spamtree_hip.h, st_rows_score_*): WAIC and DIC over the observed rows and the scores
  * of held-out values at NA rows, conditional on w.  stm_rows_score_set: st_rows_score_set on the chain's handle; call it before the
  * first iteration.  stm_mcmc_criteria is spamtree_mv_mcmc_c plus one stm_criteria: on every saved iteration, once tausq and beta are

@@ -384,6 +384,54 @@ int st_points_functionals_rank_diagnostics(st_handle h, const st_rank_spec *spec
 /* z[i] = Phi^-1(p[i]) by the text the device runs (norm_quantile.hpp); needs no device.  Returns ST_OK. */
 int st_norm_quantile(const double *p, double *z, int64_t n);
 
+/* ---- the same diagnostics of several chains in one store: between-chain R-hat and the ESS of the combined chains, on the device.
+ * A store of K = M N draws, M = n_chains, is read as M chains of N draws laid end to end: x_{c,s} = x_{cN+s}, c < M, s < N (what a
+ * driver leaves that runs M chains one after another into one set of stores).  The definition (spamtree_amd/csrc/diag_kernels.hpp,
+ * rank_kernels.hpp, spamtree_amd.diagnostics.multichain_* and tests/multichain_reference.py restate it):
+ *   limits      1 <= M <= ST_DIAG_MAX_CHAINS = 16 (a design constant: a wave keeps one value per half chain in a lane of its own; not
+ *               a measurement);  N >= ST_DIAG_MIN_DRAWS;  K <= 16384.
+ *   M = 1       the single-chain definitions above and their results, bit for bit.
+ *   lag cap     L = min(max_lag, N - 2), max_lag = 0 meaning ST_DIAG_DEFAULT_MAX_LAG;  k_max = (L - 1) / 2.
+ *   within and  mu_c = the mean of chain c;  d_{c,s} = x_{c,s} - mu_c;  gamma_{c,t} = (1/N) sum_{s<N-t} d_{c,s} d_{c,s+t} (no product
+ *   between     crosses a chain boundary);  gbar_t = (1/M) sum_c gamma_{c,t};  mubar = (1/M) sum_c mu_c;
+ *               B' = sum_c (mu_c - mubar)^2 / (M - 1).
+ *   rho, ess    rho_t = (B' + gbar_t) / (B' + gbar_0): Stan's combined estimator with the divisor-N variance throughout, so that it
+ *               is gamma_t / gamma_0 at M = 1; it differs from the `posterior` package's, which takes the divisor N - 1 in the
+ *               within-chain variance, by O(1/N).  From rho_t on the text above holds: Geyer's pairs, the stop rule, the monotone
+ *               rule, tau = -1 + 2 sum Gamma_k floored at 1 / log10 K, ess = K / tau, lags and the truncated state.
+ *   sd, mcse    sd = the pooled sd of all K draws about the pooled mean, divisor K - 1: the sd of st_*_diagnostics on the same
+ *               store;  mcse = sd / sqrt(ess).
+ *   rhat        every chain is split: h = N / 2, halves x_{c,0..h-1} and x_{c,N-h..N-1} (N odd: the middle draw is dropped),
+ *               S = 2M segments with means m_j and sample variances s_j^2 (divisor h - 1);  W = (1/S) sum s_j^2;
+ *               B = h / (S - 1) sum (m_j - mbar)^2, mbar = (1/S) sum m_j;  rhat = sqrt(((h-1)/h W + B/h) / W).
+ *   degenerate  B' + gbar_0 == 0: ess = NaN, mcse = 0, sd = 0, rhat = NaN, lags = 0.  W == 0 otherwise: rhat = NaN only.
+ *   rank family ranks, scores z, the median, the folded series and the order statistics xs[j] are those of the pooled K draws,
+ *               exactly as above.  rhat_bulk, ess_bulk, lags_bulk = the multi-chain diagnostics on z;  rhat_fold = the multi-chain
+ *               rhat on zf;  rhat_rank = fmax of the two.  The quantile, tail and exceedance indicators are built as above; their
+ *               ESS is the multi-chain indicator ESS;  prob = C / K and mcse_prob as above.
+ *   indicator   in 64-bit integers, M >= 2: per chain c_c = sum_s I_{c,s} and A_{c,t} = the A_t above with K -> N on that chain's
+ *               draws alone;  C = sum c_c;  D = sum_c (M c_c - C)^2;  S_t = sum_c A_{c,t};
+ *               Num_t = N D + M (M - 1) S_t  (= (M - 1) M^2 N^3 (B' + gbar_t));  rho_t = Num_t / Num_0;  the pairs, the stop and
+ *               the monotone rule on the integers N_k = Num_2k + Num_2k+1;
+ *               tau = max((double)(2 sum N_k - Num_0) / (double)Num_0, 1 / log10 K);  ess = K / tau.  C == 0 or C == K: ess = NaN,
+ *               lags = 0.  Bound: sum_c (c_c - C/M)^2 <= M N^2 / 4 gives N D <= M^3 N^3 / 4 = K^3 / 4;  |A_{c,t}| = N^2 |sum_{s<N-t}
+ *               (I_s - p)(I_{s+t} - p)| <= N^2 N p (1 - p) <= N^3 / 4 (Cauchy-Schwarz) gives |M (M - 1) S_t| < M^3 N^3 / 4 = K^3 / 4;
+ *               so |Num_t| < K^3 / 2 <= 2^41, |N_k| < 2^42, and with at most 2^13 pairs |2 sum N_k - Num_0| < 2^57.
+ * Every sum is taken in an order that depends on K, M, max_lag and the lane geometry only: the outputs of a series are bitwise a
+ * function of its K values, n_chains and the spec, wherever it is stored.  Each call accepts exactly the handles, structs and specs
+ * of its single-chain sibling, works on the draws stored so far, changes no state and consumes no Philox draw.  ST_ERR_USAGE with a
+ * text and the numbers, beside the count of stored draws in the sibling's order of refusals: n_chains outside 1 .. 16; K not a
+ * multiple of n_chains; K / n_chains < ST_DIAG_MIN_DRAWS.  A refusal leaves the handle usable. */
+#define ST_DIAG_MAX_CHAINS 16
+int st_summary_chain_diagnostics(st_handle h, int32_t n_chains, int32_t max_lag, const st_series_diag *w, const st_series_diag *yhat);
+int st_points_summary_chain_diagnostics(st_handle h, int32_t n_chains, int32_t max_lag, const st_series_diag *w, const st_series_diag *yhat);
+int st_points_functionals_chain_diagnostics(st_handle h, int32_t n_chains, int32_t max_lag, const st_series_diag *w, const st_series_diag *yhat);
+int st_summary_chain_rank_diagnostics(st_handle h, int32_t n_chains, const st_rank_spec *spec, const st_rank_out *w, const st_rank_out *yhat);
+int st_points_summary_chain_rank_diagnostics(st_handle h, int32_t n_chains, const st_rank_spec *spec, const st_rank_out *w,
+                                             const st_rank_out *yhat);
+int st_points_functionals_chain_rank_diagnostics(st_handle h, int32_t n_chains, const st_rank_spec *spec, const st_rank_out *w,
+                                                 const st_rank_out *yhat);
+
 /* ---- new-point prediction from a fitted state: the predictive at locations that are not rows of the problem, the way the model
  * treats an NA row (make_tree's missing level, predict_std spamtree_model.cpp:1234-1358) without rebuilding the tree.
  * A point of margin j anchored at block b (the block of its nearest deepest-knot-level row, same margin if cherrypick_same_margin,

@@ -138,6 +138,12 @@ SIGNATURES = {
     "st_summary_rank_diagnostics": (C.c_int, [H, c_rsp, c_rop, c_rop]),
     "st_points_summary_rank_diagnostics": (C.c_int, [H, c_rsp, c_rop, c_rop]),
     "st_points_functionals_rank_diagnostics": (C.c_int, [H, c_rsp, c_rop, c_rop]),
+    "st_summary_chain_diagnostics": (C.c_int, [H, C.c_int32, C.c_int32, c_sdp, c_sdp]),
+    "st_points_summary_chain_diagnostics": (C.c_int, [H, C.c_int32, C.c_int32, c_sdp, c_sdp]),
+    "st_points_functionals_chain_diagnostics": (C.c_int, [H, C.c_int32, C.c_int32, c_sdp, c_sdp]),
+    "st_summary_chain_rank_diagnostics": (C.c_int, [H, C.c_int32, c_rsp, c_rop, c_rop]),
+    "st_points_summary_chain_rank_diagnostics": (C.c_int, [H, C.c_int32, c_rsp, c_rop, c_rop]),
+    "st_points_functionals_chain_rank_diagnostics": (C.c_int, [H, C.c_int32, c_rsp, c_rop, c_rop]),
     "st_norm_quantile": (C.c_int, [c_dp, c_dp, C.c_int64]),
     "st_comm_unique_id": (C.c_int, [C.c_void_p, C.c_int32]),
     "st_comm_init": (C.c_int, [H, C.c_void_p]),
@@ -260,6 +266,14 @@ class StmRankDiagnostics(C.Structure):    # include/spamtree_fit.h, stm_rank_dia
 
 
 SIGNATURES["stm_mcmc_ranked"] = (C.c_int, SIGNATURES["stm_mcmc_excursions"][1] + [C.POINTER(StmRankDiagnostics)])
+
+
+class StmChains(C.Structure):             # include/spamtree_fit.h, stm_chains
+    _fields_ = [("n_chains", C.c_int32), ("seeds", C.POINTER(C.c_uint64)), ("theta0", c_dp), ("paramsd", c_dp), ("chain_time", c_dp)]
+
+
+SIGNATURES["stm_mcmc_chains"] = (C.c_int, SIGNATURES["stm_mcmc_ranked"][1] + [C.POINTER(StmChains)])
+SIGNATURES["stm_mcmc_chains_last_error"] = (C.c_char_p, [])
 
 SIGNATURES["stm_rows_score_set"] = (C.c_int, [H, c_dp])
 SIGNATURES["stm_mcmc_criteria"] = (C.c_int, SIGNATURES["spamtree_mv_mcmc_c"][1] + [C.POINTER(StmCriteria)])

@@ -34,7 +34,17 @@ int store_excursions(st_handle_s *h, const char *who, const DrawStore &s, const 
 int store_rank_diagnostics(st_handle_s *h, const char *who, const DrawStore &s, const st_rank_spec *spec, const st_rank_out *w,
                            const st_rank_out *yhat);
 
+// The multi-chain forms: the K stored draws are n_chains chains of K / n_chains draws laid end to end.  The same refusals in the
+// same order, with check_chains beside the count of stored draws; n_chains = 1 is the call above, bit for bit.
+int store_chain_diagnostics(st_handle_s *h, const char *who, const DrawStore &s, int32_t n_chains, int32_t max_lag, const st_series_diag *w,
+                            const st_series_diag *yhat);
+int store_chain_rank_diagnostics(st_handle_s *h, const char *who, const DrawStore &s, int32_t n_chains, const st_rank_spec *spec,
+                                 const st_rank_out *w, const st_rank_out *yhat);
+
 // ---- store_spec.cpp
+// n_chains in 1 .. ST_DIAG_MAX_CHAINS, K a multiple of it, K / n_chains >= ST_DIAG_MIN_DRAWS: ST_OK, or ST_ERR_USAGE with W, the
+// numbers and the first failing check in msg
+int check_chains(const std::string &W, int n_chains, long long K, std::string &msg);
 // n_thr in min_thr .. ST_EXC_MAX_THRESHOLDS, thr given with n_thr > 0, n_thr x n_values finite values, sides +1 / -1 (NULL: all +1):
 // ST_OK, or ST_ERR_USAGE with W and the first failing check in msg
 int check_thresholds(const std::string &W, int n_thr, int min_thr, const double *thr, const int32_t *side, long long n_values, std::string &msg);

@@ -5,6 +5,8 @@
 #include "diag_kernels.hpp"
 #include "draw_store.hpp"
 
+// CHAINS: the multi-chain definition (A.M >= 2 chains, diag_chain_wave); staging, tiles and outputs are the same
+template <bool CHAINS>
 __global__ __launch_bounds__(DIAG_NT) void k_series_diag(DiagArgs A) {
   extern __shared__ double lds[];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, nw = blockDim.x >> 6;
@@ -17,7 +19,7 @@ __global__ __launch_bounds__(DIAG_NT) void k_series_diag(DiagArgs A) {
   __syncthreads();
   for (int r = wid; r < R && row0 + r < A.n; r += nw) {
     double *x = lds + (size_t)r * Kp;
-    const DiagOut o = diag_series_wave<true>(x, K, A.L, lane);
+    const DiagOut o = CHAINS ? diag_chain_wave<true>(x, K, A.M, A.L, lane) : diag_series_wave<true>(x, K, A.L, lane);
     if (lane == 0) {
       const long long i = row0 + r;
       if (A.ess) A.ess[i] = o.ess;
@@ -42,20 +44,22 @@ bool series_diag_plan(long long K, size_t lds_limit, int *R, int *Kp) {
 int series_diag_launch(const DiagArgs &A, size_t lds_limit, hipStream_t st) {
   if (A.n <= 0) return 0;
   const size_t lds = (size_t)A.R * A.Kp * sizeof(double);
-  (void)hipFuncSetAttribute((const void *)k_series_diag, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit);
-  hipLaunchKernelGGL(k_series_diag, dim3((unsigned)((A.n + A.R - 1) / A.R)), dim3(64 * std::min(A.R, DIAG_NT / 64)), lds, st, A);
+  const auto kernel = A.M > 1 ? k_series_diag<true> : k_series_diag<false>;
+  (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((A.n + A.R - 1) / A.R)), dim3(64 * std::min(A.R, DIAG_NT / 64)), lds, st, A);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }
 
 // diagnostics of one of the store's two sets of draws into out's host arrays (any may be NULL), element i of the store at
-// out[perm ? perm[i] : i]; store_diagnostics has checked K and max_lag
-static int series_diag_store(st_handle_s *h, const char *who, const DrawStore &s, const double *draws, int32_t max_lag, const st_series_diag *out) {
+// out[perm ? perm[i] : i]; store_chain_diagnostics has checked K, n_chains and max_lag
+static int series_diag_store(st_handle_s *h, const char *who, const DrawStore &s, const double *draws, int32_t n_chains, int32_t max_lag,
+                             const st_series_diag *out) {
   const long long n = s.n, K = s.K;
   if (!out || !(out->ess || out->mcse || out->sd || out->rhat || out->lags)) return ST_OK;
   DiagArgs A;
-  A.draws = draws; A.n = n; A.K = (int)K;
-  A.L = (int)std::min<long long>(max_lag == 0 ? ST_DIAG_DEFAULT_MAX_LAG : max_lag, K - 2);
+  A.draws = draws; A.n = n; A.K = (int)K; A.M = n_chains;
+  A.L = (int)std::min<long long>(max_lag == 0 ? ST_DIAG_DEFAULT_MAX_LAG : max_lag, K / n_chains - 2);
   if (!series_diag_plan(K, h->lds_limit, &A.R, &A.Kp)) {
     h->err = std::string(who) + ": " + std::to_string(K) + " stored draws of one series do not fit one workgroup's LDS";
     return ST_ERR_UNSUPPORTED;
@@ -85,7 +89,13 @@ static int series_diag_store(st_handle_s *h, const char *who, const DrawStore &s
   return ST_OK;
 }
 
+// the single-chain call is the multi-chain one with one chain: the same refusals in the same order, the same kernel as before
 int store_diagnostics(st_handle_s *h, const char *who, const DrawStore &s, int32_t max_lag, const st_series_diag *w, const st_series_diag *yhat) {
+  return store_chain_diagnostics(h, who, s, 1, max_lag, w, yhat);
+}
+
+int store_chain_diagnostics(st_handle_s *h, const char *who, const DrawStore &s, int32_t n_chains, int32_t max_lag, const st_series_diag *w,
+                            const st_series_diag *yhat) {
   if (s.rc) return s.rc;
   if (max_lag < 0) { h->err = std::string(who) + ": max_lag must not be negative (0: the default cap)"; return ST_ERR_USAGE; }
   if (s.n == 0) return ST_OK;
@@ -94,8 +104,9 @@ int store_diagnostics(st_handle_s *h, const char *who, const DrawStore &s, int32
              " (call " + s.reserve + " before the saved iterations)";
     return ST_ERR_USAGE;
   }
+  if (const int rc = check_chains(std::string(who) + ": ", n_chains, s.K, h->err)) return rc;
   if (yhat && s.yhat_needs_X) { h->err = std::string(who) + ": yhat needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
   for (int which = 0; which < 2; ++which)
-    if (const int rc = series_diag_store(h, who, s, which ? s.yhat : s.w, max_lag, which ? yhat : w)) return rc;
+    if (const int rc = series_diag_store(h, who, s, which ? s.yhat : s.w, n_chains, max_lag, which ? yhat : w)) return rc;
   return ST_OK;
 }

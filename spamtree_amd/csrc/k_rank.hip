@@ -50,6 +50,23 @@ __device__ __forceinline__ unsigned long long rank_mask_below(int limit, int bas
   return nb <= 0 ? 0ull : nb >= 64 ? ~0ull : (1ull << nb) - 1ull;
 }
 
+// A_t of the bit mask B (W = ceil(K / 64) words, bits at and beyond K clear, c bits set), t <= K - 2, by one lane
+__device__ __forceinline__ long long rank_lag_numerator(const unsigned long long *B, int W, int K, int c, int t) {
+  const long long Kl = K, cl = c;
+  const int q = t >> 6, sh = t & 63;
+  int n11 = 0, first = 0, last = 0;
+  for (int w = 0; w < W; ++w) {
+    const unsigned long long b = B[w];
+    const unsigned long long u0 = w + q < W ? B[w + q] : 0ull, u1 = w + q + 1 < W ? B[w + q + 1] : 0ull;
+    const unsigned long long shifted = sh ? (u0 >> sh) | (u1 << (64 - sh)) : u0;   // bit s: I_{s + t}
+    n11 += __popcll(b & shifted);
+    first += __popcll(b & rank_mask_below(t, 64 * w));
+    last += __popcll(b & ~rank_mask_below(K - t, 64 * w));
+  }
+  const long long head = c - last, tail = c - first;
+  return Kl * Kl * n11 - Kl * cl * (head + tail) + (Kl - t) * cl * cl;
+}
+
 // The indicator ESS of the bit mask B (W = ceil(K / 64) words, bits at and beyond K clear, c bits set), by one wave; every lane
 // returns the same values.  Integers up to tau's one quotient.
 __device__ __forceinline__ double rank_indicator_ess(const unsigned long long *B, int W, int K, int c, int L, int lane, int *lags) {
@@ -64,21 +81,7 @@ __device__ __forceinline__ double rank_indicator_ess(const unsigned long long *B
   bool stop = false;
   for (int t0 = 0; t0 <= tmax && !stop; t0 += 64) {
     const int t = t0 + lane;
-    long long At = 0;
-    if (t <= tmax) {
-      const int q = t >> 6, sh = t & 63;
-      int n11 = 0, first = 0, last = 0;
-      for (int w = 0; w < W; ++w) {
-        const unsigned long long b = B[w];
-        const unsigned long long u0 = w + q < W ? B[w + q] : 0ull, u1 = w + q + 1 < W ? B[w + q + 1] : 0ull;
-        const unsigned long long shifted = sh ? (u0 >> sh) | (u1 << (64 - sh)) : u0;   // bit s: I_{s + t}
-        n11 += __popcll(b & shifted);
-        first += __popcll(b & rank_mask_below(t, 64 * w));
-        last += __popcll(b & ~rank_mask_below(K - t, 64 * w));
-      }
-      const long long head = c - last, tail = c - first;
-      At = Kl * Kl * n11 - Kl * cl * (head + tail) + (Kl - t) * cl * cl;
-    }
+    const long long At = t <= tmax ? rank_lag_numerator(B, W, K, c, t) : 0;
     for (int j = 0; j < 32 && !stop && t0 / 2 + j <= kmax; ++j) {
       const long long a0 = __shfl(At, 2 * j, 64), a1 = __shfl(At, 2 * j + 1, 64);
       long long N = a0 + a1;   // Gamma_k = N / A_0
@@ -96,10 +99,55 @@ __device__ __forceinline__ double rank_indicator_ess(const unsigned long long *B
   return dK / tau;
 }
 
+// The multi-chain indicator ESS (rank_kernels.hpp, step 6 with M >= 2): chain c's mask is B + c Wc (Wc = ceil(N / 64) words, bits at
+// and beyond N clear), its count is lane c's cL; every lane returns the same values.  Integers up to tau's one quotient.
+__device__ __forceinline__ double rank_chain_indicator_ess(const unsigned long long *B, int Wc, int N, int M, int cL, int L, int lane,
+                                                           int *lags) {
+  *lags = 0;
+  const long long Nl = N, Ml = M, K = Nl * Ml;
+  long long C = 0;
+  for (int ch = 0; ch < M; ++ch) C += __shfl(cL, ch, 64);
+  if (C == 0 || C == K) return __builtin_nan("");
+  long long D = 0, S0 = 0;
+  for (int ch = 0; ch < M; ++ch) {
+    const long long cc = __shfl(cL, ch, 64), e = Ml * cc - C;
+    D += e * e;
+    S0 += Nl * cc * (Nl - cc);
+  }
+  const long long ND = Nl * D, MM = Ml * (Ml - 1), Num0 = ND + MM * S0;   // > 0: 0 < C < K
+  const int kmax = (L - 1) / 2, tmax = 2 * kmax + 1;   // tmax <= L <= N - 2
+  long long nsum = 0, prev = 0x7fffffffffffffffll;     // the pairs' numerators: |N_k| < 2^42, at most 2^13 of them
+  int pairs = 0;
+  bool stop = false;
+  for (int t0 = 0; t0 <= tmax && !stop; t0 += 64) {
+    const int t = t0 + lane;
+    long long St = 0;
+    for (int ch = 0; ch < M; ++ch) {
+      const int cc = __shfl(cL, ch, 64);   // (every lane takes part: the shuffle stands outside the lane's own condition)
+      if (t <= tmax) St += rank_lag_numerator(B + (size_t)ch * Wc, Wc, N, cc, t);
+    }
+    const long long Nt = ND + MM * St;
+    for (int j = 0; j < 32 && !stop && t0 / 2 + j <= kmax; ++j) {
+      const long long a0 = __shfl(Nt, 2 * j, 64), a1 = __shfl(Nt, 2 * j + 1, 64);
+      long long Np = a0 + a1;   // Gamma_k = Np / Num_0
+      if (!(Np > 0)) stop = true;
+      else {
+        Np = Np < prev ? Np : prev;
+        prev = Np;
+        nsum += Np;
+        ++pairs;
+      }
+    }
+  }
+  const double tau = fmax((double)(2 * nsum - Num0) / (double)Num0, 1.0 / log10((double)K));
+  *lags = 2 * pairs;
+  return (double)K / tau;
+}
+
 // steps 3 and 4 / 5 for the rows of one tile: the scores of v_s (x_s, or |x_s - med_r| with FOLD) among the sorted S_r into Z_r,
 // then one wave per series over Z_r (LDS rows or rows of the global slice: each call site is inlined with its own address space).
-// Returns through s_out[r] (LDS), written by lane 0.
-template <bool FOLD>
+// Returns through s_out[r] (LDS), written by lane 0.  CHAINS: the moments are diag_chain_wave's, of A.M chains.
+template <bool FOLD, bool CHAINS>
 __device__ __forceinline__ void rank_scores_and_moments(const RankArgs &A, const double *S, double *Z, const double *X, int nr,
                                                         const double *s_med, const int *s_nan, DiagOut *s_out, int tid) {
   const int K = A.K, lane = tid & 63, wid = tid >> 6;
@@ -113,12 +161,15 @@ __device__ __forceinline__ void rank_scores_and_moments(const RankArgs &A, const
   __syncthreads();
   for (int r = wid; r < nr; r += RANK_NT / 64) {
     if (s_nan[r]) continue;
-    const DiagOut o = diag_series_wave<!FOLD>(Z + (size_t)r * A.Kz, K, A.L, lane);
+    double *z = Z + (size_t)r * A.Kz;
+    const DiagOut o = CHAINS ? diag_chain_wave<!FOLD>(z, K, A.M, A.L, lane) : diag_series_wave<!FOLD>(z, K, A.L, lane);
     if (lane == 0) s_out[r] = o;
   }
   __syncthreads();
 }
 
+// CHAINS: the multi-chain definition (A.M >= 2 chains) in steps 4 to 6; staging, sort and ranks are the same
+template <bool CHAINS>
 __global__ __launch_bounds__(RANK_NT) void k_series_rank(RankArgs A) {
   extern __shared__ double lds[];
   __shared__ double s_med[RANK_MAX_R], s_cq[RANK_MAX_R][RANK_NQ];
@@ -163,8 +214,8 @@ __global__ __launch_bounds__(RANK_NT) void k_series_rank(RankArgs A) {
     __syncthreads();
     // 3, 4: bulk
     if (A.want_bulk) {
-      if (A.z_global) rank_scores_and_moments<false>(A, S, Zg, X, nr, s_med, s_nan, s_bulk, tid);
-      else rank_scores_and_moments<false>(A, S, Zl, X, nr, s_med, s_nan, s_bulk, tid);
+      if (A.z_global) rank_scores_and_moments<false, CHAINS>(A, S, Zg, X, nr, s_med, s_nan, s_bulk, tid);
+      else rank_scores_and_moments<false, CHAINS>(A, S, Zl, X, nr, s_med, s_nan, s_bulk, tid);
     }
     // 5: folded
     if (A.want_fold) {
@@ -174,8 +225,8 @@ __global__ __launch_bounds__(RANK_NT) void k_series_rank(RankArgs A) {
       }
       __syncthreads();
       rank_sort_rows(S, R, Kpad, tid);
-      if (A.z_global) rank_scores_and_moments<true>(A, S, Zg, X, nr, s_med, s_nan, s_fold, tid);
-      else rank_scores_and_moments<true>(A, S, Zl, X, nr, s_med, s_nan, s_fold, tid);
+      if (A.z_global) rank_scores_and_moments<true, CHAINS>(A, S, Zg, X, nr, s_med, s_nan, s_fold, tid);
+      else rank_scores_and_moments<true, CHAINS>(A, S, Zl, X, nr, s_med, s_nan, s_fold, tid);
     }
     if (tid < nr) {
       const long long i = row0 + tid;
@@ -207,7 +258,29 @@ __global__ __launch_bounds__(RANK_NT) void k_series_rank(RankArgs A) {
           }
           double ess = nan;
           int cnt = 0, lags = 0;
-          if (!bad) {
+          if (!bad && CHAINS) {   // every chain into words of its own: M ceil(N / 64) <= K / 64 + M < Kpad words
+            const int N = K / A.M, Wc = (N + 63) >> 6;
+            int cL = 0;
+            for (int ch = 0; ch < A.M; ++ch) {
+              int cc = 0;
+              for (int base = 0; base < N; base += 64) {
+                const int s = base + lane;
+                bool p = false;
+                if (s < N) {
+                  const double xv = x[ch * N + s];
+                  p = mode == 0 ? xv <= c : mode == 1 ? xv > c : xv < c;
+                }
+                const unsigned long long word = __ballot(p);
+                if (lane == 0) B[ch * Wc + (base >> 6)] = word;
+                cc += __popcll(word);
+              }
+              if (lane == ch) cL = cc;
+              cnt += cc;
+            }
+            diag_wave_sync();
+            ess = rank_chain_indicator_ess(B, Wc, N, A.M, cL, A.L, lane, &lags);
+            diag_wave_sync();   // the next indicator overwrites the masks
+          } else if (!bad) {
             for (int base = 0; base < K; base += 64) {
               const int s = base + lane;
               bool p = false;
@@ -289,17 +362,17 @@ static int rank_check_spec(st_handle_s *h, const char *who, const st_rank_spec *
 }
 
 // The outputs out asks for, of one of the store's two sets of draws, into out's host arrays (any may be NULL), element i of the
-// store at out[perm ? perm[i] : i].  store_rank_diagnostics has checked the spec and K.
-static int series_rank_store(st_handle_s *h, const char *who, const DrawStore &s, const double *draws, const st_rank_spec *spec,
-                             const st_rank_out *out) {
+// store at out[perm ? perm[i] : i].  store_chain_rank_diagnostics has checked the spec, K and n_chains.
+static int series_rank_store(st_handle_s *h, const char *who, const DrawStore &s, const double *draws, int32_t n_chains,
+                             const st_rank_spec *spec, const st_rank_out *out) {
   const long long n = s.n, K = s.K;
   if (!out) return ST_OK;
   const bool bulk = out->rhat_rank || out->rhat_bulk || out->ess_bulk || out->lags_bulk, fold = out->rhat_rank || out->rhat_fold;
   const int n_prob = out->ess_q ? spec->n_prob : 0, n_thr = rank_exc_out(out) ? spec->n_thr : 0;
   if (!bulk && !fold && !out->ess_tail && !n_prob && !n_thr) return ST_OK;
   RankArgs A = {};
-  A.draws = draws; A.n = n; A.K = (int)K;
-  A.L = (int)std::min<long long>(spec->max_lag == 0 ? ST_DIAG_DEFAULT_MAX_LAG : spec->max_lag, K - 2);
+  A.draws = draws; A.n = n; A.K = (int)K; A.M = n_chains;
+  A.L = (int)std::min<long long>(spec->max_lag == 0 ? ST_DIAG_DEFAULT_MAX_LAG : spec->max_lag, K / n_chains - 2);
   if (!series_rank_plan(K, h->lds_limit, &A.R, &A.Kpad, &A.Kz, &A.z_global)) {
     h->err = std::string(who) + ": the sorted copy of " + std::to_string(K) + " stored draws of one series does not fit one workgroup's LDS";
     return ST_ERR_UNSUPPORTED;
@@ -339,8 +412,9 @@ static int series_rank_store(st_handle_s *h, const char *who, const DrawStore &s
   {
     ProfScope pscope(h, 3);
     const size_t lds = ((size_t)A.R * A.Kpad + (A.z_global ? 0 : (size_t)A.R * A.Kz)) * sizeof(double);
-    HCHK(h, hipFuncSetAttribute((const void *)k_series_rank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // (beside RANK_LDS_STATIC)
-    hipLaunchKernelGGL(k_series_rank, dim3((unsigned)grid), dim3(RANK_NT), lds, h->stream, A);
+    const auto kernel = A.M > 1 ? k_series_rank<true> : k_series_rank<false>;
+    HCHK(h, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // (beside RANK_LDS_STATIC)
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(RANK_NT), lds, h->stream, A);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { h->err = std::string(who) + " launch: " + hipGetErrorString(e); return ST_ERR_HIP; }
   }
@@ -364,13 +438,20 @@ static int series_rank_store(st_handle_s *h, const char *who, const DrawStore &s
   return ST_OK;
 }
 
+// the single-chain call is the multi-chain one with one chain: the same refusals in the same order, the same kernel as before
 int store_rank_diagnostics(st_handle_s *h, const char *who, const DrawStore &s, const st_rank_spec *spec, const st_rank_out *w,
                            const st_rank_out *yhat) {
+  return store_chain_rank_diagnostics(h, who, s, 1, spec, w, yhat);
+}
+
+int store_chain_rank_diagnostics(st_handle_s *h, const char *who, const DrawStore &s, int32_t n_chains, const st_rank_spec *spec,
+                                 const st_rank_out *w, const st_rank_out *yhat) {
   if (s.rc || s.n == 0) return s.rc;
   if (const int rc = rank_check_spec(h, who, spec, s.K, s.n_thr_values(), w, yhat)) return rc;
+  if (const int rc = check_chains(std::string(who) + ": ", n_chains, s.K, h->err)) return rc;
   if (yhat && s.yhat_needs_X) { h->err = std::string(who) + ": yhat needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
   for (int which = 0; which < 2; ++which)
-    if (const int rc = series_rank_store(h, who, s, which ? s.yhat : s.w, spec, which ? yhat : w)) return rc;
+    if (const int rc = series_rank_store(h, who, s, which ? s.yhat : s.w, n_chains, spec, which ? yhat : w)) return rc;
   return ST_OK;
 }
 

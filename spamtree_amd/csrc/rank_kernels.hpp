@@ -26,6 +26,17 @@
 //      then the pairs in order, every lane the same, on the integer numerators: N_k = A_2k + A_2k+1 (Gamma_k = N_k / A_0), stop at
 //      !(N_k > 0), N_k <- min(N_k, N_k-1), sum;  tau = max((double)(2 sum N_k - A_0) / (double)A_0, 1 / log10 K), ess = K / tau:
 //      diag_kernels.hpp's rules, with integers up to tau's one quotient: no reduction order, no rounding per lag.
+// With M >= 2 chains (st_*_chain_rank_diagnostics, k_series_rank<true>; chain c is the draws c N .. (c + 1) N - 1, N = K / M) steps
+// 1 to 3 and the folded scores are unchanged -- ranks, scores, the median and xs[j] are those of the pooled K draws -- and
+//   4, 5  run diag_chain_wave (diag_kernels.hpp) on Z_r in place of diag_series_wave;
+//   6     every chain is balloted into words of its own, ceil(N / 64) per chain, chain c from word c ceil(N / 64) on with the bits
+//         at and beyond N clear, so that the lag walk of a chain is the single-chain walk with K -> N on its own words and no mask
+//         ever straddles a boundary;  c_c = the chain's popcount, kept in lane c;  C = sum c_c, D = sum (M c_c - C)^2.
+//         Lane l takes t = t0 + l and walks chain after chain:  S_t = sum_c A_{c,t} (int64),  Num_t = N D + M (M - 1) S_t
+//         (= (M - 1) M^2 N^3 (B' + gbar_t) of the indicator; Num_0 from A_{c,0} = N c_c (N - c_c)), then the pairs on the integers
+//         as above: N_k = Num_2k + Num_2k+1, tau = max((double)(2 sum N_k - Num_0) / (double)Num_0, 1 / log10 K), ess = K / tau.
+//         N D <= K^3 / 4 and |M (M - 1) S_t| < K^3 / 4 (|A_{c,t}| <= N^3 / 4 by Cauchy-Schwarz), so |Num_t| < K^3 / 2 <= 2^41, a pair
+//         is below 2^42, and with at most 2^13 pairs |2 sum N_k - Num_0| < 2^57.  C == 0 or C == K: ess NaN, lags 0.
 // The outputs of a series are bitwise a function of its K values and the spec: the sort gives the same values in any network, the
 // ranks and the A_t are integers, and the moments of z follow diag_series_wave's fixed order.  No atomics; no inline assembly
 // (diag_allsum's DPP moves are st_device.hpp's group_xor_sum).
@@ -45,7 +56,8 @@ struct RankArgs {
   const double *draws;   // [K][n]
   long long n;
   int K, Kpad, Kz, R;
-  int L;                 // min(max_lag, K - 2), max_lag = 0 resolved
+  int M;                 // chains the K draws are cut into (1: the single-chain definition and kernel)
+  int L;                 // min(max_lag, K / M - 2), max_lag = 0 resolved
   int z_global;          // Z rows in the global slice instead of LDS
   double *scratch;       // gridDim.x slices of `slice` doubles: X (R K) and, with z_global, Z (R Kz)
   long long slice;

@@ -161,6 +161,8 @@ struct stm_chain_s {
   bool defer_sync = true, early_beta = true;   // SPAMTREE_DEFER_SYNC / SPAMTREE_EARLY_BETA, read by stm_create
   double last_logaccept = 0;
   bool initialised = false;
+  std::vector<double> beta0, mcmcsd0;   // the caller's beta, tausq and mcmcsd: what stm_restart starts the next chain from
+  double tausq0 = 1.0;
 };
 
 extern "C" const char *stm_last_error(stm_chain c) { return c ? c->err.c_str() : "null chain"; }
@@ -189,6 +191,7 @@ extern "C" int stm_create(const st_problem *pb, const st_options *opt, const dou
   if (flags) { c->adapting = flags->adapting; c->sample_beta = flags->sample_beta; c->sample_tausq = flags->sample_tausq;
                c->sample_theta = flags->sample_theta; c->sample_w = flags->sample_w; }
   c->bounds.assign(set_unif_bounds, set_unif_bounds + (size_t)ntheta * 2);
+  c->beta0.assign(beta, beta + c->p); c->tausq0 = tausq; c->mcmcsd0.assign(mcmcsd, mcmcsd + (size_t)ntheta * ntheta);
   c->param.assign(theta, theta + ntheta);
   c->Bcoeff.assign((size_t)c->p * c->q, 0.0);
   for (int j = 0; j < c->q; ++j) for (int i = 0; i < c->p; ++i) c->Bcoeff[(size_t)j * c->p + i] = beta[i];   // :124-129
@@ -225,6 +228,29 @@ extern "C" int stm_init(stm_chain c) {
   c->current_loglik = c->loglik[0];
   c->initialised = true;
   return ST_OK;
+}
+
+// The next chain of stm_mcmc_chains on the same handle, from scratch as stm_create + stm_init start one: w = 0, the caller's beta
+// and tausq, theta, the RAM adaptation restarted from mcmcsd, the host streams of `seed`, the iteration counter at 0, then both
+// slots factorised at theta (st_factor on slot 0 voids the handle's theta-only caches).  The tree, the point set, the stores and
+// every running sum of the summaries stay as they are.
+static int stm_restart(stm_chain c, const double *theta, uint64_t seed) {
+  int rc;
+  c->seed = seed; c->rng = HostRng(seed);
+  c->param.assign(theta, theta + c->k);
+  c->theta_alt = c->param;
+  for (int j = 0; j < c->q; ++j) for (int i = 0; i < c->p; ++i) c->Bcoeff[(size_t)j * c->p + i] = c->beta0[i];
+  c->tausq_inv.assign(c->q, 1.0 / c->tausq0);
+  c->am = RAMAdapt();
+  if (!c->am.init(c->k, c->mcmcsd0.data())) { c->err = "mcmcsd is not positive definite"; return ST_ERR_USAGE; }
+  c->m = 0; c->tb_drawn = false;
+  c->last_accepted = 0; c->last_acceptable = 1; c->last_logaccept = 0;
+  c->loglik[0] = c->loglik[1] = c->current_loglik = 0;
+  const std::vector<double> w0((size_t)c->n_all, 0.0);
+  if ((rc = st_set_w(c->h, w0.data())) != 0 || (rc = st_set_beta(c->h, c->Bcoeff.data())) != 0 ||
+      (rc = st_set_tausq_inv(c->h, c->tausq_inv.data())) != 0) { c->err = st_last_error(c->h); return rc; }
+  c->initialised = false;
+  return stm_init(c);
 }
 
 // spamtree_fit.cpp:183-289 : w sweep, its log-density, Metropolis step for theta
@@ -452,7 +478,10 @@ struct FitPoints {   // the point set of stm_mcmc_points and where its per-draw 
 // iteration makes that st_summary_accumulate call (the caller has reserved the room): the stores the diagnostics read.
 static int run_fit(stm_chain c, int mcmc_keep, int mcmc_burn, int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc,
                    double *yhat_mcmc, double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
-                   const FitPoints *pts, const stm_criteria *crit = nullptr, bool store_rows = false) {
+                   const FitPoints *pts, const stm_criteria *crit = nullptr, bool store_rows = false, int saved0 = 0, int keep_total = 0) {
+  // saved0, keep_total: this is one chain of stm_mcmc_chains -- its saved draw s goes to column saved0 + s of per-draw outputs that
+  // have keep_total columns.  Every Philox counter stays the chain's own: the iteration m, and s for the point draws.
+  if (keep_total == 0) keep_total = mcmc_keep;
   int rc = 0;
   const int sample_predicts = flags ? flags->sample_predicts : 1;
   const auto t0 = std::chrono::steady_clock::now();
@@ -476,23 +505,24 @@ static int run_fit(stm_chain c, int mcmc_keep, int mcmc_burn, int mcmc_thin, uin
     rc = step_tausq_beta(c);
     if (rc) break;
     if (saving && msaved < mcmc_keep) {                                 // :376-389
-      if (tausq_mcmc) for (int j = 0; j < q; ++j) tausq_mcmc[(size_t)msaved * q + j] = 1.0 / c->tausq_inv[j];
+      const size_t col_s = (size_t)saved0 + msaved;   // the draw's column in the per-draw outputs
+      if (tausq_mcmc) for (int j = 0; j < q; ++j) tausq_mcmc[col_s * q + j] = 1.0 / c->tausq_inv[j];
       if (beta_mcmc) for (int j = 0; j < q; ++j) for (int i = 0; i < p; ++i)
-        beta_mcmc[(size_t)j * p * mcmc_keep + (size_t)msaved * p + i] = c->Bcoeff[(size_t)j * p + i];
-      if (theta_mcmc) std::memcpy(theta_mcmc + (size_t)msaved * k, c->param.data(), k * sizeof(double));
-      if (w_mcmc) rc = st_get_w(c->h, w_mcmc + (size_t)msaved * n);
-      if (!rc && yhat_mcmc) rc = st_yhat(c->h, nullptr, seed, (uint32_t)m, yhat_mcmc + (size_t)msaved * n);
+        beta_mcmc[(size_t)j * p * keep_total + col_s * p + i] = c->Bcoeff[(size_t)j * p + i];
+      if (theta_mcmc) std::memcpy(theta_mcmc + col_s * k, c->param.data(), k * sizeof(double));
+      if (w_mcmc) rc = st_get_w(c->h, w_mcmc + col_s * n);
+      if (!rc && yhat_mcmc) rc = st_yhat(c->h, nullptr, seed, (uint32_t)m, yhat_mcmc + col_s * n);
       if (!rc && pts) {
-        const size_t o = (size_t)msaved * pts->n;
+        const size_t o = col_s * pts->n;
         auto col = [&](double *a) { return a ? a + o : nullptr; };
         if (pts->cond_cov) {   // cond_var = max(diag, 0), from the packed blocks below
           rc = st_points_accumulate_joint(c->h, seed, (uint32_t)msaved, col(pts->w), col(pts->cond_mean),
-                                          pts->cond_cov + (size_t)msaved * pts->cov_len, nullptr, col(pts->yhat));
+                                          pts->cond_cov + col_s * pts->cov_len, nullptr, col(pts->yhat));
         } else {
           rc = st_points_accumulate(c->h, seed, (uint32_t)msaved, col(pts->w), col(pts->cond_mean), col(pts->cond_var), col(pts->yhat));
         }
         if (!rc && pts->fun && (pts->fun->fun_w || pts->fun->fun_cond_mean || pts->fun->fun_cond_var || pts->fun->fun_yhat)) {
-          const size_t of = (size_t)msaved * pts->fun->n_fun;
+          const size_t of = col_s * pts->fun->n_fun;
           auto fcol = [&](double *a) { return a ? a + of : nullptr; };
           rc = st_points_functionals_last(c->h, fcol(pts->fun->fun_w), fcol(pts->fun->fun_cond_mean), fcol(pts->fun->fun_cond_var),
                                           fcol(pts->fun->fun_yhat));
@@ -612,9 +642,14 @@ static int rank_spec_refused(const st_rank_spec &sp, int64_t nvals, const st_ran
   return 0;
 }
 
+// What stm_mcmc_chains refuses of its chains before a chain exists to carry the text: the calling thread's last such refusal
+static thread_local std::string g_chains_error;
+static int chains_refuse(int code, const std::string &msg) { g_chains_error = msg; return code; }
+extern "C" const char *stm_mcmc_chains_last_error(void) { return g_chains_error.c_str(); }
+
 // fun NULL: stm_mcmc_points_joint itself; scores NULL: stm_mcmc_functionals itself; diag NULL: stm_mcmc_scored itself; exc NULL:
-// stm_mcmc_diagnosed itself; rk NULL: stm_mcmc_excursions itself
-extern "C" int stm_mcmc_ranked(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
+// stm_mcmc_diagnosed itself; rk NULL: stm_mcmc_excursions itself; ch NULL: stm_mcmc_ranked itself
+extern "C" int stm_mcmc_chains(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
                                     int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
                                     int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
                                     double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
@@ -624,9 +659,29 @@ extern "C" int stm_mcmc_ranked(const st_problem *pb, const st_options *opt, cons
                                     double *new_mean, double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q,
                                     double *new_yhat_q, int32_t *new_route, double *new_cond_cov, double *new_cov,
                                     const stm_functionals *fun, const stm_scores *scores, const stm_diagnostics *diag,
-                                    const stm_excursions *exc, const stm_rank_diagnostics *rk) {
+                                    const stm_excursions *exc, const stm_rank_diagnostics *rk, const stm_chains *ch) {
   if (fun && fun->n_fun <= 0) fun = nullptr;
-  const bool plain = (diag || exc || rk) && n_new == 0 && !coords_new && !mv_new && !anchor_new;   // the plain chain (with diag only: stm_mcmc_scored handles an empty set as before)
+  // M chains one after another on one handle; chain c's saved draws are columns c keep .. (c + 1) keep - 1 of every per-draw output
+  // and of the stores
+  const int M = ch ? ch->n_chains : 1;
+  const std::string W = "stm_mcmc_chains: ";
+  g_chains_error.clear();
+  if (ch && (M < 1 || M > ST_DIAG_MAX_CHAINS))
+    return chains_refuse(ST_ERR_USAGE, W + "n_chains = " + std::to_string(M) + " must lie in 1 .. " + std::to_string(ST_DIAG_MAX_CHAINS));
+  if (ch && !ch->seeds) return chains_refuse(ST_ERR_USAGE, W + "seeds is NULL: one seed per chain (" + std::to_string(M) + ")");
+  if (M > 1 && mcmc_keep < 1)
+    return chains_refuse(ST_ERR_USAGE, W + "mcmc_keep = " + std::to_string(mcmc_keep) + ": " + std::to_string(M) + " chains need at least one saved draw each");
+  if (M > 1 && !theta) return chains_refuse(ST_ERR_USAGE, W + "theta is NULL");
+  if (M > 1 && opt && opt->world > 1)
+    return chains_refuse(ST_ERR_UNSUPPORTED, W + "world = " + std::to_string(opt->world) + ": several chains run on one GPU");
+  const long long total = (long long)M * mcmc_keep;   // the stored draws
+  const auto too_many = [&]() {
+    return chains_refuse(ST_ERR_UNSUPPORTED, W + std::to_string(M) + " chains x mcmc_keep = " + std::to_string(mcmc_keep) + " are " + std::to_string(total) +
+                                                 " stored draws, at most 16384");
+  };
+  // the plain chain: no point argument, and either a summary of the rows (with diag only: stm_mcmc_scored handles an empty set as
+  // before) or several chains
+  const bool plain = (diag || exc || rk || M > 1) && n_new == 0 && !coords_new && !mv_new && !anchor_new;
   const bool d_rows = diag && diag->want_rows && (diag_any(diag->rows_w) || diag_any(diag->rows_yhat));
   const bool d_new = diag && !plain && (diag_any(diag->new_w) || diag_any(diag->new_yhat));
   const bool d_fun = diag && fun && (diag_any(diag->fun_w) || diag_any(diag->fun_yhat));
@@ -636,9 +691,9 @@ extern "C" int stm_mcmc_ranked(const st_problem *pb, const st_options *opt, cons
   if (diag && !fun && (diag_any(diag->fun_w) || diag_any(diag->fun_yhat))) return ST_ERR_USAGE;
   if ((d_new && diag_any(diag->new_yhat) && !X_new) || (d_fun && diag_any(diag->fun_yhat) && !X_new)) return ST_ERR_USAGE;
   if (d_rows || d_new || d_fun) {
-    if (mcmc_keep > 16384) return ST_ERR_UNSUPPORTED;   // the stores' limit
+    if (total > 16384) return too_many();   // the stores' limit
     if (mcmc_keep < ST_DIAG_MIN_DRAWS) return ST_ERR_USAGE;
-    if (d_new || d_fun) keep_draws = std::max<int64_t>(keep_draws, mcmc_keep);
+    if (d_new || d_fun) keep_draws = std::max<int64_t>(keep_draws, total);
   }
   const bool e_rows = exc && exc->want_rows && (exc_any(exc->rows_w) || exc_any(exc->rows_yhat));
   const bool e_new = exc && !plain && (exc_any(exc->new_w) || exc_any(exc->new_yhat));
@@ -648,11 +703,11 @@ extern "C" int stm_mcmc_ranked(const st_problem *pb, const st_options *opt, cons
   if (exc && !fun && (exc_any(exc->fun_w) || exc_any(exc->fun_yhat))) return ST_ERR_USAGE;
   if ((e_new && exc_any(exc->new_yhat) && !X_new) || (e_fun && exc_any(exc->fun_yhat) && !X_new)) return ST_ERR_USAGE;
   if (e_rows || e_new || e_fun) {
-    if (mcmc_keep > 16384) return ST_ERR_UNSUPPORTED;   // the stores' limit
-    if (e_rows) if (const int r = exc_spec_refused(exc->rows_spec, pb->q, exc->rows_w, exc->rows_yhat, mcmc_keep)) return r;
-    if (e_new) if (const int r = exc_spec_refused(exc->new_spec, pb->q, exc->new_w, exc->new_yhat, mcmc_keep)) return r;
-    if (e_fun) if (const int r = exc_spec_refused(exc->fun_spec, fun->n_fun, exc->fun_w, exc->fun_yhat, mcmc_keep)) return r;
-    if (e_new || e_fun) keep_draws = std::max<int64_t>(keep_draws, mcmc_keep);
+    if (total > 16384) return too_many();   // the stores' limit
+    if (e_rows) if (const int r = exc_spec_refused(exc->rows_spec, pb->q, exc->rows_w, exc->rows_yhat, (int)total)) return r;
+    if (e_new) if (const int r = exc_spec_refused(exc->new_spec, pb->q, exc->new_w, exc->new_yhat, (int)total)) return r;
+    if (e_fun) if (const int r = exc_spec_refused(exc->fun_spec, fun->n_fun, exc->fun_w, exc->fun_yhat, (int)total)) return r;
+    if (e_new || e_fun) keep_draws = std::max<int64_t>(keep_draws, total);
   }
   const bool r_rows = rk && rk->want_rows && (rank_any(rk->rows_w) || rank_any(rk->rows_yhat));
   const bool r_new = rk && !plain && (rank_any(rk->new_w) || rank_any(rk->new_yhat));
@@ -662,14 +717,18 @@ extern "C" int stm_mcmc_ranked(const st_problem *pb, const st_options *opt, cons
   if (rk && !fun && (rank_any(rk->fun_w) || rank_any(rk->fun_yhat))) return ST_ERR_USAGE;
   if ((r_new && rank_any(rk->new_yhat) && !X_new) || (r_fun && rank_any(rk->fun_yhat) && !X_new)) return ST_ERR_USAGE;
   if (r_rows || r_new || r_fun) {
-    if (mcmc_keep > 16384) return ST_ERR_UNSUPPORTED;   // the stores' limit
+    if (total > 16384) return too_many();   // the stores' limit
     if (mcmc_keep < ST_DIAG_MIN_DRAWS) return ST_ERR_USAGE;
     if (r_rows) if (const int r = rank_spec_refused(rk->rows_spec, pb->q, rk->rows_w, rk->rows_yhat)) return r;
     if (r_new) if (const int r = rank_spec_refused(rk->new_spec, pb->q, rk->new_w, rk->new_yhat)) return r;
     if (r_fun) if (const int r = rank_spec_refused(rk->fun_spec, fun->n_fun, rk->fun_w, rk->fun_yhat)) return r;
-    if (r_new || r_fun) keep_draws = std::max<int64_t>(keep_draws, mcmc_keep);
+    if (r_new || r_fun) keep_draws = std::max<int64_t>(keep_draws, total);
   }
   const bool store_rows = d_rows || e_rows || r_rows;   // one reservation serves all three
+  if (M > 1 && keep_draws > 0) {   // a point store that is reserved at all holds every chain's draws
+    if (total > 16384) return too_many();
+    keep_draws = total;
+  }
   if (plain && (fun || (scores && scores->y_new) || joint_id_new || X_new || n_quantiles != 0)) return ST_ERR_USAGE;
   if (scores && !scores->y_new) scores = nullptr;
   if (scores && (!X_new || (scores->lpd_joint && !joint_id_new) || (scores->crps && keep_draws < 1))) return ST_ERR_USAGE;
@@ -678,12 +737,14 @@ extern "C" int stm_mcmc_ranked(const st_problem *pb, const st_options *opt, cons
   if (n_quantiles < 0 || (n_quantiles > 0 && (!quantiles || keep_draws < 1))) return ST_ERR_USAGE;   // a quantile needs stored draws
   for (int32_t i = 0; i < n_quantiles; ++i) if (!(quantiles[i] >= 0.0 && quantiles[i] <= 1.0)) return ST_ERR_USAGE;
   if ((new_yhat || new_yhat_mean || new_yhat_q) && !X_new) return ST_ERR_USAGE;
+  const auto chain_seed = [&](int cn) { return ch ? ch->seeds[cn] : seed; };
+  const auto chain_theta = [&](int cn) { return ch && ch->theta0 ? ch->theta0 + (size_t)cn * ntheta : theta; };
   stm_chain c = nullptr;
-  int rc = stm_create(pb, opt, set_unif_bounds, mcmcsd, theta, ntheta, beta, tausq, seed, flags, &c);
+  int rc = stm_create(pb, opt, set_unif_bounds, mcmcsd, chain_theta(0), ntheta, beta, tausq, chain_seed(0), flags, &c);
   if (rc == 0 && !plain) rc = stm_points_set_joint(c, n_new, coords_new, mv_new, anchor_new, X_new, joint_id_new, keep_draws);   // refusals: before any factorisation
   if (rc == 0 && store_rows) {
     rc = st_summary_reset(c->h);
-    if (rc == 0) rc = st_summary_reserve(c->h, mcmc_keep);
+    if (rc == 0) rc = st_summary_reserve(c->h, total);
   }
   int64_t nj = 0;
   std::vector<int64_t> joff, jptr, jmem;
@@ -694,24 +755,34 @@ extern "C" int stm_mcmc_ranked(const st_problem *pb, const st_options *opt, cons
     rc = st_points_joint_layout(c->h, &nj, nullptr, nullptr, nullptr);
     joff.resize(nj + 1); jptr.resize(nj + 1); jmem.resize(n_new);
     if (rc == 0) rc = st_points_joint_layout(c->h, &nj, joff.data(), jptr.data(), jmem.data());
-    if (rc == 0 && !new_cond_cov && new_cond_var) cov_scratch.resize((size_t)joff[nj] * std::max(mcmc_keep, 0));
+    if (rc == 0 && !new_cond_cov && new_cond_var) cov_scratch.resize((size_t)joff[nj] * std::max<long long>(total, 0));
   }
   if (rc == 0) rc = stm_init(c);
   if (rc != 0) { stm_destroy(c); return rc; }
   double *const ccov = !joint_id_new ? nullptr : (new_cond_cov ? new_cond_cov : (cov_scratch.empty() ? nullptr : cov_scratch.data()));
   const FitPoints pts{n_new, new_w, new_cond_mean, new_cond_var, new_yhat, ccov, joint_id_new ? joff[nj] : 0, fun};
-  rc = run_fit(c, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc, yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time,
-               plain ? nullptr : &pts, nullptr, store_rows);
+  double time_all = 0;
+  for (int cn = 0; cn < M && rc == 0; ++cn) {
+    if (cn > 0) rc = stm_restart(c, chain_theta(cn), chain_seed(cn));
+    double time_c = 0;
+    if (rc == 0)
+      rc = run_fit(c, mcmc_keep, mcmc_burn, mcmc_thin, chain_seed(cn), flags, w_mcmc, yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd,
+                   &time_c, plain ? nullptr : &pts, nullptr, store_rows, cn * mcmc_keep, (int)total);
+    if (rc == 0 && ch && ch->paramsd) std::memcpy(ch->paramsd + (size_t)cn * ntheta * ntheta, c->am.paramsd.data(), (size_t)ntheta * ntheta * sizeof(double));
+    if (rc == 0 && ch && ch->chain_time) ch->chain_time[cn] = time_c;
+    time_all += time_c;
+  }
+  if (rc == 0 && mcmc_time) *mcmc_time = time_all;   // (paramsd: the last chain's; every chain's in ch->paramsd)
   if (plain) {   // the diagnostics and excursions of the rows are all a plain chain can ask for
-    if (rc == 0 && d_rows) rc = st_summary_diagnostics(c->h, diag->max_lag, &diag->rows_w, &diag->rows_yhat);
+    if (rc == 0 && d_rows) rc = st_summary_chain_diagnostics(c->h, M, diag->max_lag, &diag->rows_w, &diag->rows_yhat);
     if (rc == 0 && e_rows) rc = st_summary_excursions(c->h, &exc->rows_spec, &exc->rows_w, &exc->rows_yhat);
-    if (rc == 0 && r_rows) rc = st_summary_rank_diagnostics(c->h, &rk->rows_spec, &rk->rows_w, &rk->rows_yhat);
+    if (rc == 0 && r_rows) rc = st_summary_chain_rank_diagnostics(c->h, M, &rk->rows_spec, &rk->rows_w, &rk->rows_yhat);
     if (rc) c->err = st_last_error(c->h);
     stm_destroy(c);
     return rc;
   }
   if (rc == 0 && ccov && new_cond_var)
-    for (int s = 0; s < mcmc_keep; ++s)
+    for (long long s = 0; s < total; ++s)
       for (int64_t k = 0; k < nj; ++k) {
         const int64_t g = jptr[k + 1] - jptr[k];
         for (int64_t a = 0; a < g; ++a)
@@ -731,23 +802,40 @@ extern "C" int stm_mcmc_ranked(const st_problem *pb, const st_options *opt, cons
                                         fun->fun_yhat_q ? fun->fun_yhat_q + (size_t)i * fun->n_fun : nullptr);
   if (rc == 0 && scores && mcmc_keep > 0)
     rc = st_points_score_get(c->h, scores->lpd, scores->pit, scores->crps, scores->lpd_joint, scores->n_scored, scores->n_degenerate);
-  if (rc == 0 && d_rows) rc = st_summary_diagnostics(c->h, diag->max_lag, &diag->rows_w, &diag->rows_yhat);
+  if (rc == 0 && d_rows) rc = st_summary_chain_diagnostics(c->h, M, diag->max_lag, &diag->rows_w, &diag->rows_yhat);
   if (rc == 0 && d_new)
-    rc = st_points_summary_diagnostics(c->h, diag->max_lag, &diag->new_w, diag_any(diag->new_yhat) ? &diag->new_yhat : nullptr);
+    rc = st_points_summary_chain_diagnostics(c->h, M, diag->max_lag, &diag->new_w, diag_any(diag->new_yhat) ? &diag->new_yhat : nullptr);
   if (rc == 0 && d_fun)
-    rc = st_points_functionals_diagnostics(c->h, diag->max_lag, &diag->fun_w, diag_any(diag->fun_yhat) ? &diag->fun_yhat : nullptr);
+    rc = st_points_functionals_chain_diagnostics(c->h, M, diag->max_lag, &diag->fun_w, diag_any(diag->fun_yhat) ? &diag->fun_yhat : nullptr);
   if (rc == 0 && e_rows) rc = st_summary_excursions(c->h, &exc->rows_spec, &exc->rows_w, &exc->rows_yhat);
   if (rc == 0 && e_new)
     rc = st_points_summary_excursions(c->h, &exc->new_spec, &exc->new_w, exc_any(exc->new_yhat) ? &exc->new_yhat : nullptr);
   if (rc == 0 && e_fun)
     rc = st_points_functionals_excursions(c->h, &exc->fun_spec, &exc->fun_w, exc_any(exc->fun_yhat) ? &exc->fun_yhat : nullptr);
-  if (rc == 0 && r_rows) rc = st_summary_rank_diagnostics(c->h, &rk->rows_spec, &rk->rows_w, &rk->rows_yhat);
+  if (rc == 0 && r_rows) rc = st_summary_chain_rank_diagnostics(c->h, M, &rk->rows_spec, &rk->rows_w, &rk->rows_yhat);
   if (rc == 0 && r_new)
-    rc = st_points_summary_rank_diagnostics(c->h, &rk->new_spec, &rk->new_w, rank_any(rk->new_yhat) ? &rk->new_yhat : nullptr);
+    rc = st_points_summary_chain_rank_diagnostics(c->h, M, &rk->new_spec, &rk->new_w, rank_any(rk->new_yhat) ? &rk->new_yhat : nullptr);
   if (rc == 0 && r_fun)
-    rc = st_points_functionals_rank_diagnostics(c->h, &rk->fun_spec, &rk->fun_w, rank_any(rk->fun_yhat) ? &rk->fun_yhat : nullptr);
+    rc = st_points_functionals_chain_rank_diagnostics(c->h, M, &rk->fun_spec, &rk->fun_w, rank_any(rk->fun_yhat) ? &rk->fun_yhat : nullptr);
   stm_destroy(c);
   return rc;
+}
+
+extern "C" int stm_mcmc_ranked(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
+                                    int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
+                                    int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
+                                    double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
+                                    int64_t n_new, const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new,
+                                    const double *X_new, const int64_t *joint_id_new, int64_t keep_draws, const double *quantiles,
+                                    int32_t n_quantiles, double *new_w, double *new_cond_mean, double *new_cond_var, double *new_yhat,
+                                    double *new_mean, double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q,
+                                    double *new_yhat_q, int32_t *new_route, double *new_cond_cov, double *new_cov,
+                                    const stm_functionals *fun, const stm_scores *scores, const stm_diagnostics *diag,
+                                    const stm_excursions *exc, const stm_rank_diagnostics *rk) {
+  return stm_mcmc_chains(pb, opt, set_unif_bounds, theta, ntheta, beta, tausq, mcmcsd, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc,
+                         yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time, n_new, coords_new, mv_new, anchor_new, X_new,
+                         joint_id_new, keep_draws, quantiles, n_quantiles, new_w, new_cond_mean, new_cond_var, new_yhat, new_mean, new_var,
+                         new_w_mean, new_yhat_mean, new_w_q, new_yhat_q, new_route, new_cond_cov, new_cov, fun, scores, diag, exc, rk, nullptr);
 }
 
 extern "C" int stm_mcmc_excursions(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,

@@ -1664,6 +1664,13 @@ extern "C" int st_summary_excursions(st_handle h, const st_excursion_spec *spec,
 extern "C" int st_summary_rank_diagnostics(st_handle h, const st_rank_spec *spec, const st_rank_out *w, const st_rank_out *yhat) {
   return store_rank_diagnostics(h, __func__, rows_store(h), spec, w, yhat);
 }
+extern "C" int st_summary_chain_diagnostics(st_handle h, int32_t n_chains, int32_t max_lag, const st_series_diag *w, const st_series_diag *yhat) {
+  return store_chain_diagnostics(h, __func__, rows_store(h), n_chains, max_lag, w, yhat);
+}
+extern "C" int st_summary_chain_rank_diagnostics(st_handle h, int32_t n_chains, const st_rank_spec *spec, const st_rank_out *w,
+                                                 const st_rank_out *yhat) {
+  return store_chain_rank_diagnostics(h, __func__, rows_store(h), n_chains, spec, w, yhat);
+}
 extern "C" int st_summary_get(st_handle h, double *w_mean, double *yhat_mean, int64_t *n_accumulated) {
   if (!h) return ST_ERR_USAGE;
   if (n_accumulated) *n_accumulated = h->n_summary;

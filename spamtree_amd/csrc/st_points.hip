@@ -528,6 +528,14 @@ extern "C" int st_points_summary_excursions(st_handle h, const st_excursion_spec
 extern "C" int st_points_summary_rank_diagnostics(st_handle h, const st_rank_spec *spec, const st_rank_out *w, const st_rank_out *yhat) {
   return store_rank_diagnostics(h, __func__, points_store(h, __func__), spec, w, yhat);
 }
+extern "C" int st_points_summary_chain_diagnostics(st_handle h, int32_t n_chains, int32_t max_lag, const st_series_diag *w,
+                                                   const st_series_diag *yhat) {
+  return store_chain_diagnostics(h, __func__, points_store(h, __func__), n_chains, max_lag, w, yhat);
+}
+extern "C" int st_points_summary_chain_rank_diagnostics(st_handle h, int32_t n_chains, const st_rank_spec *spec, const st_rank_out *w,
+                                                        const st_rank_out *yhat) {
+  return store_chain_rank_diagnostics(h, __func__, points_store(h, __func__), n_chains, spec, w, yhat);
+}
 
 // ---- linear functionals of the predictions (points_fun.hpp): the term lists come from functionals_layout, without a device call
 extern "C" int st_points_functionals_set(st_handle h, int64_t n_fun, const int64_t *ptr, const int64_t *idx, const double *wt) {
@@ -625,6 +633,14 @@ extern "C" int st_points_functionals_excursions(st_handle h, const st_excursion_
 }
 extern "C" int st_points_functionals_rank_diagnostics(st_handle h, const st_rank_spec *spec, const st_rank_out *w, const st_rank_out *yhat) {
   return store_rank_diagnostics(h, __func__, fun_store(h, __func__), spec, w, yhat);
+}
+extern "C" int st_points_functionals_chain_diagnostics(st_handle h, int32_t n_chains, int32_t max_lag, const st_series_diag *w,
+                                                       const st_series_diag *yhat) {
+  return store_chain_diagnostics(h, __func__, fun_store(h, __func__), n_chains, max_lag, w, yhat);
+}
+extern "C" int st_points_functionals_chain_rank_diagnostics(st_handle h, int32_t n_chains, const st_rank_spec *spec, const st_rank_out *w,
+                                                            const st_rank_out *yhat) {
+  return store_chain_rank_diagnostics(h, __func__, fun_store(h, __func__), n_chains, spec, w, yhat);
 }
 
 // ---- scores of held-out observations at the point set (points_score.hpp)

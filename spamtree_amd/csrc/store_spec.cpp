@@ -18,6 +18,23 @@ int check_thresholds(const std::string &W, int n_thr, int min_thr, const double 
   return ST_OK;
 }
 
+int check_chains(const std::string &W, int n_chains, long long K, std::string &msg) {
+  if (n_chains < 1 || n_chains > ST_DIAG_MAX_CHAINS) {
+    msg = W + "n_chains = " + std::to_string(n_chains) + " must lie in 1 .. " + std::to_string(ST_DIAG_MAX_CHAINS);
+    return ST_ERR_USAGE;
+  }
+  if (K % n_chains != 0) {
+    msg = W + std::to_string(K) + " draws stored are not a multiple of n_chains = " + std::to_string(n_chains);
+    return ST_ERR_USAGE;
+  }
+  if (K / n_chains < ST_DIAG_MIN_DRAWS) {
+    msg = W + std::to_string(K) + " draws stored in " + std::to_string(n_chains) + " chains are " + std::to_string(K / n_chains) +
+          " per chain, the diagnostics need at least " + std::to_string(ST_DIAG_MIN_DRAWS);
+    return ST_ERR_USAGE;
+  }
+  return ST_OK;
+}
+
 unsigned thresholds_in_store_order(const double *thr, const int32_t *side, int T, long long stride, bool per_series, const long long *perm,
                                    std::vector<double> &out) {
   unsigned neg = 0;

@@ -73,11 +73,12 @@ def series_diagnostics(x, max_lag=0):
     return dict(ess=ess, mcse=sd / math.sqrt(ess), sd=sd, rhat=rhat, lags=2 * pairs, truncated=pairs == k_max + 1)
 
 
-def chains_diagnostics(a, max_lag=0):
-    """series_diagnostics along the last axis of ``a`` (... x K): a dict of arrays of the leading shape."""
+def chains_diagnostics(a, max_lag=0, n_chains=1):
+    """series_diagnostics along the last axis of ``a`` (... x K): a dict of arrays of the leading shape.  With ``n_chains`` > 1
+    every series is that many chains laid end to end (multichain_diagnostics)."""
     a = np.asarray(a, dtype=np.float64)
     lead = a.shape[:-1]
-    rows = [series_diagnostics(r, max_lag) for r in a.reshape(-1, a.shape[-1])]
+    rows = [multichain_diagnostics(r, n_chains, max_lag) for r in a.reshape(-1, a.shape[-1])]
     out = {k: np.array([r[k] for r in rows], dtype=np.int32 if k == "lags" else np.float64).reshape(lead) for k in KEYS}
     out["truncated"] = np.array([r["truncated"] for r in rows], dtype=bool).reshape(lead)
     return out
@@ -261,18 +262,162 @@ def rank_series_diagnostics(x, probs=(), thresholds=(), sides=None, max_lag=0):
                 lags_exc=np.array([l for _, l in ex], dtype=np.int32))
 
 
-def chains_rank_diagnostics(a, probs=(), thresholds=(), sides=None, max_lag=0):
+def chains_rank_diagnostics(a, probs=(), thresholds=(), sides=None, max_lag=0, n_chains=1):
     """rank_series_diagnostics along the last axis of ``a`` (... x K): per-series outputs of the leading shape, ess_q
-    (n_prob, ...) and ess_exc, mcse_prob, prob (n_thr, ...)."""
+    (n_prob, ...) and ess_exc, mcse_prob, prob (n_thr, ...).  With ``n_chains`` > 1 every series is that many chains laid end to
+    end (multichain_rank_diagnostics)."""
     a = np.asarray(a, dtype=np.float64)
     lead = a.shape[:-1]
-    rows = [rank_series_diagnostics(r, probs, thresholds, sides, max_lag) for r in a.reshape(-1, a.shape[-1])]
+    rows = [multichain_rank_diagnostics(r, n_chains, probs, thresholds, sides, max_lag) for r in a.reshape(-1, a.shape[-1])]
     out = {k: np.array([r[k] for r in rows], dtype=np.int32 if k == "lags_bulk" else np.float64).reshape(lead) for k in RANK_KEYS}
     out["truncated"] = np.array([r["truncated"] for r in rows], dtype=bool).reshape(lead)
     for k in ("ess_q", "ess_exc", "mcse_prob", "prob"):
         m = np.array([r[k] for r in rows], dtype=np.float64).reshape(len(rows), -1)
         out[k] = m.T.reshape((m.shape[1],) + lead)
     return out
+
+
+# ---- several chains in one series (include/spamtree_hip.h, st_*_chain_diagnostics and st_*_chain_rank_diagnostics) ------------------
+# A series of K = M N draws is M = n_chains chains of N draws laid end to end: x_{c,s} = x[c N + s].  1 <= M <= MAX_CHAINS, N >= MIN_DRAWS.
+#   M = 1      series_diagnostics / rank_series_diagnostics, bit for bit
+#   lag cap    L = min(max_lag, N - 2) (max_lag = 0: DEFAULT_MAX_LAG);  k_max = (L - 1) // 2
+#   within     mu_c = mean of chain c;  d_{c,s} = x_{c,s} - mu_c;  gamma_{c,t} = (1/N) sum_{s<N-t} d_{c,s} d_{c,s+t};  gbar_t = mean_c gamma_{c,t}
+#   between    mubar = mean_c mu_c;  B' = sum_c (mu_c - mubar)^2 / (M - 1)
+#   rho, ess   rho_t = (B' + gbar_t) / (B' + gbar_0), then the pairs, the stop and monotone rules, tau floored at 1 / log10 K, ess = K / tau
+#   sd, mcse   sd = the pooled sd of the K draws (divisor K - 1);  mcse = sd / sqrt(ess)
+#   rhat       h = N // 2; the S = 2M half chains x_c[:h], x_c[N-h:]; W = mean of their sample variances (divisor h - 1);
+#              B = h / (S - 1) sum (m_j - mbar)^2;  rhat = sqrt(((h-1)/h W + B/h) / W)
+#   degenerate B' + gbar_0 == 0: ess NaN, mcse 0, sd 0, rhat NaN, lags 0;  W == 0: rhat NaN
+#   indicator  integers: c_c = sum_s I_{c,s}, A_{c,t} = indicator_ess's A_t of chain c alone (K -> N), C = sum c_c, D = sum (M c_c - C)^2,
+#              Num_t = N D + M (M - 1) sum_c A_{c,t};  rho_t = Num_t / Num_0;  the pairs on N_k = Num_2k + Num_2k+1;
+#              tau = max(float(2 sum N_k - Num_0) / float(Num_0), 1 / log10 K);  C in {0, K}: ess NaN, lags 0
+#   rank       ranks, scores, median, folded series and xs[j] of the pooled K draws; bulk / fold = the multi-chain diagnostics on z / zf;
+#              quantile, tail and exceedance ESS = the multi-chain indicator ESS;  prob = C / K, mcse_prob as before
+MAX_CHAINS = 16          # ST_DIAG_MAX_CHAINS
+
+
+def check_chains(K, n_chains):
+    """N = K // n_chains, checked as st_*_chain_diagnostics checks it (ValueError)."""
+    M = int(n_chains)
+    if not 1 <= M <= MAX_CHAINS:
+        raise ValueError(f"n_chains = {M} must lie in 1 .. {MAX_CHAINS}")
+    if K % M:
+        raise ValueError(f"{K} draws are not a multiple of n_chains = {M}")
+    if K // M < MIN_DRAWS:
+        raise ValueError(f"{K} draws in {M} chains are {K // M} per chain, the diagnostics need at least {MIN_DRAWS}")
+    return K // M
+
+
+def multichain_diagnostics(x, n_chains=1, max_lag=0):
+    """dict(ess, mcse, sd, rhat, lags, truncated) of one series of n_chains chains laid end to end, in float64."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    K, M = x.size, int(n_chains)
+    if M == 1:
+        return series_diagnostics(x, max_lag)
+    N = check_chains(K, M)
+    L, k_max = lag_cap(N, max_lag)
+    y = x - _mean(x)
+    g0 = float(y @ y)
+    yc = y.reshape(M, N)
+    nu = np.array([_mean(r) for r in yc])
+    d = yc - nu[:, None]
+    Q = K * float(((nu - nu.sum() / M) ** 2).sum()) / (M - 1)
+    den = Q + float((d * d).sum())
+    if den == 0.0:
+        return dict(ess=math.nan, mcse=0.0, sd=0.0, rhat=math.nan, lags=0, truncated=False)
+    sd = math.sqrt(g0 / (K - 1))
+    h = N // 2
+    seg = np.concatenate([np.stack([r[:h], r[N - h:]]) for r in d])   # 2M x h, about the chain's mean
+    mu = seg.sum(axis=1) / h
+    W = float((((seg - mu[:, None]) ** 2).sum(axis=1) / (h - 1)).sum()) / (2 * M)
+    mj = np.repeat(nu, 2) + mu
+    B = h / (2 * M - 1) * float(((mj - mj.sum() / (2 * M)) ** 2).sum())
+    rhat = math.sqrt(((h - 1) / h * W + B / h) / W) if W != 0.0 else math.nan
+    tsum, prev, pairs = 0.0, math.inf, 0
+    for k in range(k_max + 1):
+        t = 2 * k
+        a0, a1 = float((d[:, :N - t] * d[:, t:]).sum()), float((d[:, :N - t - 1] * d[:, t + 1:]).sum())
+        G = (Q + a0) / den + (Q + a1) / den
+        if not G > 0.0:
+            break
+        G = min(G, prev)
+        prev = G
+        tsum += G
+        pairs += 1
+    tau = max(2.0 * tsum - 1.0, 1.0 / math.log10(K))
+    ess = K / tau
+    return dict(ess=ess, mcse=sd / math.sqrt(ess), sd=sd, rhat=rhat, lags=2 * pairs, truncated=pairs == k_max + 1)
+
+
+def multichain_indicator_ess(I, n_chains=1, max_lag=0):
+    """(ess, lags) of a 0/1 series of n_chains chains laid end to end: integer Num_t, one float division, the diagnostics' pairs."""
+    I = np.asarray(I).astype(np.int64).reshape(-1)
+    K, M = I.size, int(n_chains)
+    if M == 1:
+        return indicator_ess(I, max_lag)
+    N = check_chains(K, M)
+    Ic = I.reshape(M, N)
+    cc = [int(v) for v in Ic.sum(axis=1)]
+    C = sum(cc)
+    if C == 0 or C == K:
+        return math.nan, 0
+    _, k_max = lag_cap(N, max_lag)
+    D = sum((M * c - C) ** 2 for c in cc)
+
+    def Num(t):
+        S = 0
+        for r, c in zip(Ic, cc):
+            n11 = int(r[:N - t] @ r[t:])
+            head, tail = int(r[:N - t].sum()), int(r[t:].sum())
+            S += N * N * n11 - N * c * (head + tail) + (N - t) * c * c
+        return N * D + M * (M - 1) * S
+    Num0 = Num(0)
+    nsum, prev, pairs = 0, None, 0
+    for k in range(k_max + 1):
+        Nk = Num(2 * k) + Num(2 * k + 1)
+        if not Nk > 0:
+            break
+        Nk = Nk if prev is None else min(Nk, prev)
+        prev = Nk
+        nsum += Nk
+        pairs += 1
+    tau = max(float(2 * nsum - Num0) / float(Num0), 1.0 / math.log10(K))
+    return K / tau, 2 * pairs
+
+
+def multichain_rank_diagnostics(x, n_chains=1, probs=(), thresholds=(), sides=None, max_lag=0):
+    """rank_series_diagnostics' dict of one series of n_chains chains laid end to end: ranks, scores, median and order statistics of
+    the pooled draws, the moments and the indicator ESS by the multi-chain definition."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    K, M = x.size, int(n_chains)
+    if M == 1:
+        return rank_series_diagnostics(x, probs, thresholds, sides, max_lag)
+    N = check_chains(K, M)
+    if K > MAX_DRAWS:
+        raise ValueError(f"the rank diagnostics take at most {MAX_DRAWS} draws, got {K}")
+    probs, thresholds, sides = check_rank_spec(probs, thresholds, sides, max_lag)
+    thresholds = [float(t) for t in thresholds]
+    nq, nt = len(probs), len(thresholds)
+    if np.isnan(x).any():
+        nan_q, nan_t = np.full(nq, math.nan), np.full(nt, math.nan)
+        return dict(rhat_rank=math.nan, rhat_bulk=math.nan, rhat_fold=math.nan, ess_bulk=math.nan, ess_tail=math.nan, lags_bulk=0,
+                    truncated=False, ess_q=nan_q, lags_q=np.zeros(nq, dtype=np.int32), ess_exc=nan_t, mcse_prob=nan_t.copy(),
+                    prob=nan_t.copy(), lags_exc=np.zeros(nt, dtype=np.int32))
+    xs = np.sort(x)
+    bulk = multichain_diagnostics(rank_scores(x)[1], M, max_lag)
+    med = xs[(K - 1) // 2] if K % 2 else 0.5 * (xs[K // 2 - 1] + xs[K // 2])
+    fold = multichain_diagnostics(rank_scores(np.abs(x - med))[1], M, max_lag)
+    qs = [multichain_indicator_ess(x <= xs[quantile_order(p, K)], M, max_lag) for p in probs]
+    tails = [multichain_indicator_ess(x <= xs[quantile_order(p, K)], M, max_lag)[0] for p in (0.05, 0.95)]
+    ex = [multichain_indicator_ess(x > t if s > 0 else x < t, M, max_lag) for t, s in zip(thresholds, sides)]
+    cnt = [int(np.count_nonzero(x > t if s > 0 else x < t)) for t, s in zip(thresholds, sides)]
+    prob = np.array([c / K for c in cnt], dtype=np.float64)
+    mcse = np.array([0.0 if c in (0, K) else math.sqrt(p * (1.0 - p) / e[0]) for c, p, e in zip(cnt, prob, ex)], dtype=np.float64)
+    return dict(rhat_rank=_fmax(bulk["rhat"], fold["rhat"]), rhat_bulk=bulk["rhat"], rhat_fold=fold["rhat"], ess_bulk=bulk["ess"],
+                ess_tail=_fmin(tails[0], tails[1]), lags_bulk=bulk["lags"], truncated=bulk["truncated"],
+                ess_q=np.array([e for e, _ in qs], dtype=np.float64), lags_q=np.array([l for _, l in qs], dtype=np.int32),
+                ess_exc=np.array([e for e, _ in ex], dtype=np.float64), mcse_prob=mcse, prob=prob,
+                lags_exc=np.array([l for _, l in ex], dtype=np.int32))
 
 
 def _rank_summary(rhat, bulk, tail):

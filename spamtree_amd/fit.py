@@ -244,7 +244,7 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                      sample_theta=True, sample_w=True, sample_predicts=True, seed=2021, device=0, reference_quirks=True,
                      new_points=None, new_draws=True, new_quantiles=(), save_w=True, save_yhat=True, force_generic=False,
                      criteria=False, y_holdout=None, holdout_crps=True, diagnostics=False, diagnostics_max_lag=0, excursions=None,
-                     rank_diagnostics=None):
+                     rank_diagnostics=None, chains=1, chain_seeds=None, chain_theta=None):
     """spamtree_fit.cpp:5-430 through the C++ driver.  `num_threads`, `use_alg`, the verbosity flags and `start_w` are
     accepted and ignored exactly where the reference ignores them (start_w, :95) or where they do not apply to a GPU.
 
@@ -312,8 +312,37 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     outcome for the rows); with ``new_points`` also ``new["rank_diagnostics"]`` and ``new["functionals"]["rank_diagnostics"]``
     (``thresholds_fun``: entries scalar or one value per functional, default ``thresholds``).  May be combined with
     ``diagnostics`` and ``excursions``, not with ``criteria`` / ``y_holdout``.  ValueError before any device call: what the calls
-    refuse of a spec, bad shapes, ``mcmc_keep`` outside 4 .. 16384."""
+    refuse of a spec, bad shapes, ``mcmc_keep`` outside 4 .. 16384.
+
+    ``chains=M`` > 1 (at most 16): M chains one after another on one handle (stm_mcmc_chains), each the fit from scratch with
+    ``chain_seeds[c]`` (default ``seed + c``) from ``chain_theta[c]`` (M x k; default ``theta``; ``mcmc.disperse_theta`` draws
+    dispersed starts) -- chain c's draws are, bit for bit, those of the single-chain call with that seed and start.  Every per-draw
+    array then has ``M * mcmc_keep`` columns, chain after chain, with ``chain_id`` naming each column's chain; ``paramsd`` is
+    k x k x M, ``chain_time`` the seconds per chain.  Means, variances, quantiles, excursions and scores are those of the pooled
+    draws.  ``diagnostics`` and ``rank_diagnostics`` are the multi-chain ones (``diagnostics.multichain_diagnostics``: the R-hat
+    over all 2M half chains, the ESS of the combined chains) under the same keys, on the device for rows, points and functionals
+    and on the host for theta, beta and tausq, with ``n_chains`` recorded in them; ``mcmc_keep`` is then the length of one chain.
+    ValueError: ``M * mcmc_keep`` > 16384, M outside 1 .. 16, together with ``criteria`` / ``y_holdout`` (a separate driver)."""
     crit = bool(criteria) or y_holdout is not None
+    M = int(chains)
+    if not 1 <= M <= _diag.MAX_CHAINS:
+        raise ValueError(f"chains = {M} must lie in 1 .. {_diag.MAX_CHAINS}")
+    keep_all = M * int(mcmc_keep)   # the columns of every per-draw array
+    if M > 1:
+        if crit:
+            raise ValueError("chains and criteria / y_holdout are separate drivers (stm_mcmc_chains, stm_mcmc_criteria): one per call")
+        if int(mcmc_keep) < 1 or keep_all > _diag.MAX_DRAWS:
+            raise ValueError(f"chains: {M} x mcmc_keep = {keep_all} draws must lie in {M} .. {_diag.MAX_DRAWS} (what the device stores)")
+        seeds = np.array([int(seed) + c for c in range(M)] if chain_seeds is None else [int(s) for s in chain_seeds], dtype=np.uint64)
+        if seeds.shape != (M,):
+            raise ValueError(f"chain_seeds must hold one seed per chain ({M})")
+        theta0 = None
+        if chain_theta is not None:
+            theta0 = np.ascontiguousarray(chain_theta, dtype=np.float64)   # M x k in C order: k x M column-major
+            if theta0.shape != (M, np.size(theta)):
+                raise ValueError(f"chain_theta must be {M} x {np.size(theta)}: one start per chain")
+    elif chain_seeds is not None or chain_theta is not None:
+        raise ValueError("chain_seeds and chain_theta need chains > 1")
     rank = None
     if rank_diagnostics is not None and rank_diagnostics is not False:
         rank = {} if rank_diagnostics is True else dict(rank_diagnostics)
@@ -410,11 +439,16 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     sd = np.asfortranarray(np.asarray(mcmcsd, dtype=np.float64))
     opt = _lib.StOptions(int(device), int(bool(reference_quirks)), 0, 1, int(bool(force_generic)), 2 if limited_tree else 0)
     fl = _lib.StmFlags(int(adapting), int(sample_beta), int(sample_tausq), int(sample_theta), int(sample_w), int(sample_predicts))
-    w_all = np.zeros((n, mcmc_keep), order="F") if save_w else None
-    yh_all = np.zeros((n, mcmc_keep), order="F") if save_yhat else None
-    beta_mcmc = np.zeros((p, mcmc_keep, q), order="F"); tausq_mcmc = np.zeros((q, mcmc_keep), order="F")
-    theta_mcmc = np.zeros((k, mcmc_keep), order="F"); paramsd = np.zeros((k, k), order="F")
+    w_all = np.zeros((n, keep_all), order="F") if save_w else None
+    yh_all = np.zeros((n, keep_all), order="F") if save_yhat else None
+    beta_mcmc = np.zeros((p, keep_all, q), order="F"); tausq_mcmc = np.zeros((q, keep_all), order="F")
+    theta_mcmc = np.zeros((k, keep_all), order="F"); paramsd = np.zeros((k, k), order="F")
     t = C.c_double()
+    chs = None
+    if M > 1:   # stm_mcmc_chains: stm_mcmc_ranked plus the chains
+        paramsd_all, chain_time = np.zeros((k, k, M), order="F"), np.zeros(M)
+        chs = _lib.StmChains(M, seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(theta0) if theta0 is not None else None,
+                             _dp(paramsd_all), _dp(chain_time))
     dp = lambda a: _dp(a) if a is not None else None   # noqa: E731
     common = (C.byref(pb), C.byref(opt), _dp(bounds), _dp(theta), k, _dp(_f64(beta)), float(tausq), _dp(sd), int(mcmc_keep),
               int(mcmc_burn), int(mcmc_thin), int(seed), C.byref(fl), dp(w_all), dp(yh_all), _dp(beta_mcmc), _dp(tausq_mcmc),
@@ -432,8 +466,8 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
         xs = _lib.StmExcursions()
         xs.want_rows = 1
         xs.rows_spec = exc["spec_rows"][0]
-        xw, xs.rows_w = excursion_buffers(n, exc["T"], q, int(mcmc_keep), exc["band"])
-        xy, xs.rows_yhat = excursion_buffers(n, exc["T"], q, int(mcmc_keep), exc["band"])
+        xw, xs.rows_w = excursion_buffers(n, exc["T"], q, keep_all, exc["band"])
+        xy, xs.rows_yhat = excursion_buffers(n, exc["T"], q, keep_all, exc["band"])
         exc_rows = dict(w=xw, yhat=xy)
     dsp = C.byref(ds) if ds is not None else None
     xsp = C.byref(xs) if xs is not None else None
@@ -461,6 +495,13 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
             err = SpamTreeError(f"stm_mcmc_criteria failed ({rc})")
             err.code = rc
             raise err
+    elif new_points is None and M > 1:   # the plain chains: no point argument
+        rc = lib.stm_mcmc_chains(*common, 0, None, None, None, None, None, 0, None, 0, *([None] * 15), dsp, xsp,
+                                 C.byref(rs) if rs is not None else None, C.byref(chs))
+        if rc not in (0, -10):
+            err = SpamTreeError(f"stm_mcmc_chains failed ({rc}) {lib.stm_mcmc_chains_last_error().decode()}".rstrip())
+            err.code = rc
+            raise err
     elif new_points is None and rank is not None:   # the plain chain through the ranked driver: no point argument
         rc = lib.stm_mcmc_ranked(*common, 0, None, None, None, None, None, 0, None, 0, *([None] * 15), dsp, xsp, C.byref(rs))
         if rc not in (0, -10):
@@ -484,8 +525,8 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     else:
         pc, pmv, pan, pX, qs, labels, fun, ynew, want_crps = pts
         n_new = pc.shape[0]
-        draws = {key: np.zeros((n_new, mcmc_keep), order="F") if new_draws else None for key in ("w", "cond_mean", "cond_var")}
-        draws["yhat"] = np.zeros((n_new, mcmc_keep), order="F") if (new_draws and pX is not None) else None
+        draws = {key: np.zeros((n_new, keep_all), order="F") if new_draws else None for key in ("w", "cond_mean", "cond_var")}
+        draws["yhat"] = np.zeros((n_new, keep_all), order="F") if (new_draws and pX is not None) else None
         summ = {key: np.zeros(n_new) for key in ("mean", "var", "w_mean")}
         summ["yhat_mean"] = np.zeros(n_new) if pX is not None else None
         wq = np.zeros((n_new, qs.size), order="F")
@@ -497,13 +538,13 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
         groups = off = ccov = cov = None
         if labels is not None:
             groups, off = _joint_layout(labels)
-            ccov = np.zeros((int(off[-1]), mcmc_keep), order="F") if new_draws else None
+            ccov = np.zeros((int(off[-1]), keep_all), order="F") if new_draws else None
             cov = np.zeros(int(off[-1]))
         fsp = None
         if fun is not None:       # stm_mcmc_functionals: both kinds of set, plus the functional outputs in one struct
             nf = fun[0].size - 1
-            fdraws = {key: np.zeros((nf, mcmc_keep), order="F") if new_draws else None for key in ("w", "cond_mean", "cond_var")}
-            fdraws["yhat"] = np.zeros((nf, mcmc_keep), order="F") if (new_draws and pX is not None) else None
+            fdraws = {key: np.zeros((nf, keep_all), order="F") if new_draws else None for key in ("w", "cond_mean", "cond_var")}
+            fdraws["yhat"] = np.zeros((nf, keep_all), order="F") if (new_draws and pX is not None) else None
             fsumm = {key: np.zeros(nf) for key in ("mean", "var", "w_mean")}
             fsumm["yhat_mean"] = np.zeros(nf) if pX is not None else None
             fwq = np.zeros((nf, qs.size), order="F")
@@ -535,16 +576,16 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
         if exc is not None:
             xs.new_spec = exc["spec_new"][0]
             T_f = 0
-            xnw, xs.new_w = excursion_buffers(n_new, exc["T"], q, int(mcmc_keep), exc["band"])
-            xny, o_ny = excursion_buffers(n_new, exc["T"], q, int(mcmc_keep), exc["band"], pX is not None)
+            xnw, xs.new_w = excursion_buffers(n_new, exc["T"], q, keep_all, exc["band"])
+            xny, o_ny = excursion_buffers(n_new, exc["T"], q, keep_all, exc["band"], pX is not None)
             if o_ny is not None:
                 xs.new_yhat = o_ny
             exc_new = dict(w=xnw, yhat=xny)
             if fun is not None:
                 xs.fun_spec = exc["spec_fun"][0]
                 T_f = int(xs.fun_spec.n_thr)
-                xfw, xs.fun_w = excursion_buffers(nf, T_f, 1, int(mcmc_keep), exc["band"])
-                xfy, o_fy = excursion_buffers(nf, T_f, 1, int(mcmc_keep), exc["band"], pX is not None)
+                xfw, xs.fun_w = excursion_buffers(nf, T_f, 1, keep_all, exc["band"])
+                xfy, o_fy = excursion_buffers(nf, T_f, 1, keep_all, exc["band"], pX is not None)
                 if o_fy is not None:
                     xs.fun_yhat = o_fy
                 exc_fun = dict(w=xfw, yhat=xfy)
@@ -562,6 +603,11 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                 if o_rfy is not None:
                     rs.fun_yhat = o_rfy
                 rank_fun = dict(w=rfw, yhat=rfy)
+        if M > 1:
+            rc = lib.stm_mcmc_chains(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), _ip(labels) if labels is not None else None,
+                                     *tail, dp(ccov), dp(cov), fsp, C.byref(ss) if ss is not None else None, dsp, xsp,
+                                     C.byref(rs) if rs is not None else None, C.byref(chs))
+        elif rank is not None:
             rc = lib.stm_mcmc_ranked(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), _ip(labels) if labels is not None else None,
                                      *tail, dp(ccov), dp(cov), fsp, C.byref(ss) if ss is not None else None, dsp, xsp, C.byref(rs))
         elif exc is not None:
@@ -595,7 +641,7 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
             if labels is not None:
                 new.update(groups=groups, cov=_unpack_joint(cov, groups, off))
                 if new_draws:
-                    new["cond_cov"] = [_unpack_joint(ccov[:, s], groups, off) for s in range(mcmc_keep)]
+                    new["cond_cov"] = [_unpack_joint(ccov[:, s], groups, off) for s in range(keep_all)]
             if fun is not None:
                 new["functionals"] = dict(fsumm, quantiles={float(x): (fwq[:, i].copy(), None if fyq is None else fyq[:, i].copy())
                                                             for i, x in enumerate(qs)})
@@ -630,29 +676,40 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
         return {"None": np.zeros(0)}
     out = {}
     if save_w:
-        out["w_mcmc"] = [w_all[:, i].reshape(-1, 1).copy() for i in range(mcmc_keep)]
+        out["w_mcmc"] = [w_all[:, i].reshape(-1, 1).copy() for i in range(keep_all)]
     if save_yhat:
-        out["yhat_mcmc"] = [yh_all[:, i].reshape(-1, 1).copy() for i in range(mcmc_keep)]
+        out["yhat_mcmc"] = [yh_all[:, i].reshape(-1, 1).copy() for i in range(keep_all)]
     out.update(beta_mcmc=beta_mcmc, tausq_mcmc=tausq_mcmc, theta_mcmc=theta_mcmc, paramsd=paramsd, mcmc_time=t.value)
+    if M > 1:   # per-draw arrays hold chain after chain; the multi-chain diagnostics name their n_chains
+        out.update(paramsd=paramsd_all, chain_time=chain_time, chain_id=np.repeat(np.arange(M), int(mcmc_keep)), n_chains=M)
     if new is not None:
         out["new"] = new
+        if M > 1:
+            for part in (new, new.get("functionals", {})):
+                for key in ("diagnostics", "rank_diagnostics"):
+                    if key in part:
+                        part[key]["n_chains"] = M
     if crit_out is not None:
         out["criteria"] = crit_out
     if diagnostics:
-        d = dict(theta=_diag.chains_diagnostics(theta_mcmc, max_lag),
-                 beta=_diag.chains_diagnostics(np.transpose(beta_mcmc, (0, 2, 1)), max_lag),
-                 tausq=_diag.chains_diagnostics(tausq_mcmc, max_lag),
+        d = dict(theta=_diag.chains_diagnostics(theta_mcmc, max_lag, M),
+                 beta=_diag.chains_diagnostics(np.transpose(beta_mcmc, (0, 2, 1)), max_lag, M),
+                 tausq=_diag.chains_diagnostics(tausq_mcmc, max_lag, M),
                  w=series_diag_finish(diag_rows["w"], mcmc_keep, max_lag), yhat=series_diag_finish(diag_rows["yhat"], mcmc_keep, max_lag))
         mv_rows = _i64(mv_id).reshape(-1)
         d["summary"] = {key: _diag.summarise(d[key], mv_rows if key in ("w", "yhat") else None) for key in ("theta", "beta", "tausq", "w", "yhat")}
+        if M > 1:
+            d["n_chains"] = M
         out["diagnostics"] = d
     if exc_rows is not None:
         out["excursions"] = {key: excursion_finish(v) for key, v in exc_rows.items()}
     if rank_rows is not None:
-        host = lambda a: _diag.chains_rank_diagnostics(a, probs=rank["probs"], max_lag=rank["max_lag"])   # noqa: E731
+        host = lambda a: _diag.chains_rank_diagnostics(a, probs=rank["probs"], max_lag=rank["max_lag"], n_chains=M)   # noqa: E731
         r = dict(theta=host(theta_mcmc), beta=host(np.transpose(beta_mcmc, (0, 2, 1))), tausq=host(tausq_mcmc),
                  w=rank_finish(rank_rows["w"], mcmc_keep, rank["max_lag"]), yhat=rank_finish(rank_rows["yhat"], mcmc_keep, rank["max_lag"]))
         mv_rows = _i64(mv_id).reshape(-1)
         r["summary"] = {key: _diag.summarise_rank(r[key], mv_rows if key in ("w", "yhat") else None) for key in ("theta", "beta", "tausq", "w", "yhat")}
+        if M > 1:
+            r["n_chains"] = M
         out["rank_diagnostics"] = r
     return out

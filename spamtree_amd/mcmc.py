@@ -53,6 +53,17 @@ def do_I_accept(logaccept, u):                            # mh_adapt.h:20-36
     return u < acceptj
 
 
+def disperse_theta(bounds, M, seed=2021):
+    """M starting values of theta (M x k) drawn uniformly inside ``bounds`` (k x 2: set_unif_bounds), one per chain of
+    ``fit.spamtree_mv_mcmc(chains=M, chain_theta=...)``: starts spread over the support are what lets a between-chain R-hat see a
+    chain that stays in another mode.  The outer thousandth of every interval is left out (the logit of a bound is infinite)."""
+    bounds = np.asarray(bounds, dtype=np.float64).reshape(-1, 2)
+    if int(M) < 1 or not np.all(bounds[:, 1] > bounds[:, 0]):
+        raise ValueError("disperse_theta: M >= 1 and bounds[:, 0] < bounds[:, 1]")
+    u = np.random.default_rng(seed).uniform(1e-3, 1.0 - 1e-3, size=(int(M), bounds.shape[0]))
+    return bounds[:, 0] + (bounds[:, 1] - bounds[:, 0]) * u
+
+
 class RAMAdapt:
     """Robust adaptive Metropolis (Vihola 2012) as configured in mh_adapt.h:78-135 (member g0 = 50)."""
 

@@ -756,61 +756,76 @@ class SpamTreeMV:
         return out
 
     # ---- convergence diagnostics of the stored draws (st_*_diagnostics; spamtree_amd.diagnostics has the definition)
-    def _diagnostics(self, call, n, max_lag, yhat, n_kept):
+    def _diagnostics(self, call, n, max_lag, yhat, n_kept, n_chains=1, chain_call=None):
         dw, sw = series_diag_buffers(n)
         dy, sy = series_diag_buffers(n, yhat)
-        self._check(call(self.h, int(max_lag), C.byref(sw), C.byref(sy) if sy is not None else None))
-        if n_kept is not None:   # the number of stored draws tells which series ran into the lag cap
-            series_diag_finish(dw, n_kept, max_lag)
-            series_diag_finish(dy, n_kept, max_lag)
+        outs = (C.byref(sw), C.byref(sy) if sy is not None else None)
+        if n_chains == 1:
+            self._check(call(self.h, int(max_lag), *outs))
+        else:   # the stored draws are n_chains chains laid end to end (st_*_chain_diagnostics)
+            self._check(chain_call(self.h, int(n_chains), int(max_lag), *outs))
+        if n_kept is not None:   # the number of stored draws per chain tells which series ran into the lag cap
+            series_diag_finish(dw, n_kept // n_chains, max_lag)
+            series_diag_finish(dy, n_kept // n_chains, max_lag)
         return dict(w=dw, yhat=dy)
 
-    def summary_diagnostics(self, max_lag=0, n_kept=None):
+    def summary_diagnostics(self, max_lag=0, n_kept=None, n_chains=1):
         """ESS, MCSE, sd, split-R-hat and lags of every row's stored w and yhat draws (st_summary_reserve before the saved
         iterations): dict(w=dict(ess, mcse, sd, rhat, lags), yhat=the same), n_all values each in model row order.  With
-        ``n_kept``, the number of stored draws, each also holds ``truncated``: the series that ran into the lag cap."""
-        return self._diagnostics(self.lib.st_summary_diagnostics, self.n_all, max_lag, True, n_kept)
+        ``n_kept``, the number of stored draws, each also holds ``truncated``: the series that ran into the lag cap.  With
+        ``n_chains`` > 1 the stored draws are that many chains laid end to end: the ESS of the combined chains and the R-hat over
+        all half chains (st_summary_chain_diagnostics)."""
+        return self._diagnostics(self.lib.st_summary_diagnostics, self.n_all, max_lag, True, n_kept, n_chains,
+                                 self.lib.st_summary_chain_diagnostics)
 
-    def points_diagnostics(self, max_lag=0, n_kept=None):
+    def points_diagnostics(self, max_lag=0, n_kept=None, n_chains=1):
         """The same of the point set's stored w* and yhat* draws (st_points_summary_reserve), in the caller's order; ``yhat``
         None without X."""
-        return self._diagnostics(self.lib.st_points_summary_diagnostics, self.n_points, max_lag, self.points_have_X, n_kept)
+        return self._diagnostics(self.lib.st_points_summary_diagnostics, self.n_points, max_lag, self.points_have_X, n_kept, n_chains,
+                                 self.lib.st_points_summary_chain_diagnostics)
 
-    def functionals_diagnostics(self, max_lag=0, n_kept=None):
+    def functionals_diagnostics(self, max_lag=0, n_kept=None, n_chains=1):
         """The same of the functionals' stored F_w and F_y draws; ``yhat`` None without X."""
-        return self._diagnostics(self.lib.st_points_functionals_diagnostics, self.n_functionals, max_lag, self.points_have_X, n_kept)
+        return self._diagnostics(self.lib.st_points_functionals_diagnostics, self.n_functionals, max_lag, self.points_have_X, n_kept,
+                                 n_chains, self.lib.st_points_functionals_chain_diagnostics)
 
     # ---- rank-normalised R-hat, bulk / tail / quantile / exceedance ESS of the stored draws (st_*_rank_diagnostics)
-    def _rank_diagnostics(self, call, n, m, probs, thresholds, sides, max_lag, yhat, n_kept):
+    def _rank_diagnostics(self, call, n, m, probs, thresholds, sides, max_lag, yhat, n_kept, n_chains=1, chain_call=None):
         spec, keep, n_prob, n_thr = rank_spec(probs, thresholds, sides, max_lag, m)
         dw, ow = rank_buffers(n, n_prob, n_thr)
         dy, oy = rank_buffers(n, n_prob, n_thr, yhat)
-        self._check(call(self.h, C.byref(spec), C.byref(ow), C.byref(oy) if oy is not None else None))
+        outs = (C.byref(spec), C.byref(ow), C.byref(oy) if oy is not None else None)
+        if n_chains == 1:
+            self._check(call(self.h, *outs))
+        else:   # the stored draws are n_chains chains laid end to end (st_*_chain_rank_diagnostics)
+            self._check(chain_call(self.h, int(n_chains), *outs))
         del keep
         if n_kept is not None:
-            rank_finish(dw, n_kept, max_lag)
-            rank_finish(dy, n_kept, max_lag)
+            rank_finish(dw, n_kept // n_chains, max_lag)
+            rank_finish(dy, n_kept // n_chains, max_lag)
         return dict(w=dw, yhat=dy)
 
-    def summary_rank_diagnostics(self, probs=(), thresholds=(), sides=None, max_lag=0, n_kept=None):
+    def summary_rank_diagnostics(self, probs=(), thresholds=(), sides=None, max_lag=0, n_kept=None, n_chains=1):
         """Rank-normalised R-hat (bulk, folded, their maximum), bulk and tail ESS, the ESS of the quantiles ``probs`` and of the
         exceedances of ``thresholds`` (a scalar or q values each, ``sides`` +1 / -1) with their probability and its MCSE, of every
         row's stored w and yhat draws (st_summary_reserve before the saved iterations): dict(w=dict(rhat_rank, rhat_bulk,
         rhat_fold, ess_bulk, ess_tail, lags_bulk (n_all), ess_q (n_prob, n_all), ess_exc, mcse_prob, prob (n_thr, n_all)),
-        yhat=the same), model row order.  With ``n_kept`` each also holds ``truncated``."""
+        yhat=the same), model row order.  With ``n_kept`` each also holds ``truncated``.  With ``n_chains`` > 1 the stored draws
+        are that many chains laid end to end (st_summary_chain_rank_diagnostics)."""
         return self._rank_diagnostics(self.lib.st_summary_rank_diagnostics, self.n_all, self.q, probs, thresholds, sides, max_lag,
-                                      True, n_kept)
+                                      True, n_kept, n_chains, self.lib.st_summary_chain_rank_diagnostics)
 
-    def points_rank_diagnostics(self, probs=(), thresholds=(), sides=None, max_lag=0, n_kept=None):
+    def points_rank_diagnostics(self, probs=(), thresholds=(), sides=None, max_lag=0, n_kept=None, n_chains=1):
         """The same of the point set's stored w* and yhat* draws, in the caller's order; ``yhat`` None without X."""
         return self._rank_diagnostics(self.lib.st_points_summary_rank_diagnostics, self.n_points, self.q, probs, thresholds, sides,
-                                      max_lag, self.points_have_X, n_kept)
+                                      max_lag, self.points_have_X, n_kept, n_chains, self.lib.st_points_summary_chain_rank_diagnostics)
 
-    def functionals_rank_diagnostics(self, probs=(), thresholds=(), sides=None, max_lag=0, n_kept=None):
+    def functionals_rank_diagnostics(self, probs=(), thresholds=(), sides=None, max_lag=0, n_kept=None, n_chains=1):
         """The same of the functionals' stored F_w and F_y draws: a threshold value per functional (a scalar entry serves all);
         ``yhat`` None without X."""
         return self._rank_diagnostics(self.lib.st_points_functionals_rank_diagnostics, self.n_functionals, self.n_functionals,
-                                      probs, thresholds, sides, max_lag, self.points_have_X, n_kept)
+                                      probs, thresholds, sides, max_lag, self.points_have_X, n_kept, n_chains,
+                                      self.lib.st_points_functionals_chain_rank_diagnostics)
 
     # ---- exceedance, excursion functions and simultaneous bands of the stored draws (st_*_excursions; spamtree_amd.excursions)
     def _excursions(self, call, n, m, G, n_kept, thresholds, side, mask, band, yhat):

@@ -314,7 +314,8 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
 
 
 def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), return_draws=True, joint=None, functionals=None,
-                y_new=None, crps=True, diagnostics=False, diagnostics_max_lag=0, excursions=None, rank_diagnostics=None, **mcmc):
+                y_new=None, crps=True, diagnostics=False, diagnostics_max_lag=0, excursions=None, rank_diagnostics=None, chains=1,
+                chain_seeds=None, chain_theta=None, **mcmc):
     """Fit the chain and predict at new locations on every saved iteration, without replaying it.
 
     ``model_inputs``: the problem as for :func:`predict_new`.  The points are located with :func:`locate` and handed to
@@ -338,6 +339,9 @@ def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), retu
     ``new["functionals"]["excursions"]``.
     With ``rank_diagnostics`` (True or the dict of ``fit.spamtree_mv_mcmc``) the fit's ``rank_diagnostics``,
     ``new["rank_diagnostics"]`` and ``new["functionals"]["rank_diagnostics"]``.
+    With ``chains`` > 1 (``chain_seeds``, ``chain_theta``: as ``fit.spamtree_mv_mcmc``) that many chains run one after another: every
+    per-draw array holds ``chains * mcmc_keep`` columns, chain after chain (``chain_id``), the summaries are those of the pooled
+    draws and the diagnostics the multi-chain ones.  :func:`predict_new` takes the concatenated result as it takes one chain's.
     """
     mi = model_inputs
     coords_new = np.asarray(coords_new, dtype=np.float64).reshape(-1, 2)
@@ -351,7 +355,7 @@ def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), retu
         raise ValueError("quantiles must lie in [0, 1]")
     fun = None if functionals is None else functionals_csr(functionals, coords_new.shape[0])
     ys = None if y_new is None else score_values(y_new, coords_new.shape[0], X_new is not None)
-    if ys is not None and crps and int(mcmc.get("mcmc_keep", 100)) > fit.MAX_STORED_DRAWS:
+    if ys is not None and crps and int(chains) == 1 and int(mcmc.get("mcmc_keep", 100)) > fit.MAX_STORED_DRAWS:
         raise ValueError(f"the CRPS keeps mcmc_keep draws per point on the device, at most {fit.MAX_STORED_DRAWS} (crps=False scores without it)")
     anchor = locate(mi["topo"], coords_new, mv_new, device=mcmc.get("device", 0), joint=joint)
     points = dict(coords=coords_new, mv=mv_new, anchor=anchor, X=X_new)
@@ -371,6 +375,6 @@ def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), retu
                                mi["block_names"], mi["block_groups"], mi["indexing"],
                                new_points=points, new_draws=return_draws,
                                new_quantiles=qs, diagnostics=diagnostics, diagnostics_max_lag=diagnostics_max_lag, excursions=excursions,
-                               rank_diagnostics=rank_diagnostics, **kw)
+                               rank_diagnostics=rank_diagnostics, chains=chains, chain_seeds=chain_seeds, chain_theta=chain_theta, **kw)
     out["new"]["anchor"] = anchor
     return out
