@@ -103,7 +103,32 @@ int st_factor(st_handle h, int slot, const double *theta, int ntheta, double *lo
  * attached: nothing yet), _finish waits and returns what st_factor returns.  In between the caller may issue calls that do not
  * touch the slot -- the C++ driver draws tausq / beta from the sweep's statistics and uploads them (st_tausq_stats, st_beta_stats,
  * st_set_tausq_inv, st_set_beta: none of them waits for the main stream), so that the Metropolis step's host round trip
- * (src/spamtree_fit.cpp:232-262, then :308-330) is the only one of the iteration.  No st_swap / st_sample_w* in between. */
+ * (src/spamtree_fit.cpp:232-262, then :308-330) is the only one of the iteration.  No st_swap / st_sample_w* in between.
+ *
+ * The contract of the two split operations, as the library enforces it (tests/protocol_model.py restates it and replays random
+ * call sequences against it).  "open" = between st_factor_enqueue(s, .) and st_factor_finish; "pending" = between
+ * st_sample_w_loglik_begin and _end; both may hold at once (the driver: _begin, _enqueue, statistics, setters, _finish, _end).
+ * refused = ST_ERR_USAGE, a text in st_last_error() that names the call, the handle unchanged.
+ *
+ *   call                                         | while open (slot s)        | while pending
+ *   ---------------------------------------------+----------------------------+---------------------------
+ *   st_factor_finish                             | legal (closes it)          | legal
+ *   st_sample_w_loglik_end                       | legal                      | legal (closes it)
+ *   st_beta_stats, st_tausq_stats                | legal                      | legal (of the sweep's w)
+ *   st_set_beta, st_set_tausq_inv                | legal                      | legal (the pending sweep does not see them)
+ *   st_get_resid, st_get_xb, st_xtx              | legal                      | legal
+ *   st_factor_ahead_enable                       | legal                      | legal
+ *   st_get_block, st_get_comps (slot t)          | refused for t == s         | legal
+ *   st_loglik_w (slot t)                         | refused for t == s         | refused
+ *   st_set_w, st_get_w, st_yhat                  | legal (queued behind it)   | refused
+ *   st_factor, st_factor_local, st_factor_enqueue| refused                    | legal
+ *   st_factor_begin                              | refused                    | legal
+ *   st_sample_w, st_sample_w_loglik, _begin      | refused                    | refused
+ *   st_swap, st_predict                          | refused                    | refused
+ *
+ * A st_factor_enqueue that is itself refused or fails (a negative code) opens nothing; one that returns 0 is open even when the
+ * factorisation fails: its code (1 / 2 / 3) comes from st_factor_finish.  A st_sample_w_loglik_begin with a negative code leaves
+ * nothing pending.  The multi-GPU building blocks (st_*_local, st_mg_*) are the caller's protocol and are not checked. */
 /* On slot 1 (one GPU, st_options.reserved bit 2 clear) the quad leaf levels compute V = Linv_pa K_pa,j and the log-density
  * only; their panel rows [-r_j T_j | r_j] are finished from the stored V by the first call that reads the slot's panels --
  * st_swap (before it swaps), st_get_block, st_loglik_w / st_loglik_local, st_sample_w_loglik(_begin) -- on the launch
@@ -113,11 +138,16 @@ int st_factor_is_async(st_handle h);   /* 1: _enqueue really starts the work (on
 int st_factor_finish(st_handle h, double *loglik);
 /* optional: start phase A of the latency-bound top levels ahead of time -- they depend on theta only (their blocks'
  * quadratic forms are redone with the current w afterwards) -- on a second stream, e.g. before the sweep; the next
- * st_factor / st_factor_local for the same slot and theta picks the result up.  Identical results; a no-op when the tree
+ * st_factor / st_factor_local / st_factor_enqueue for the same slot and theta picks the result up.  Identical results; a no-op when the tree
  * does not qualify (column-group levels above a k_factor_quad level) or SPAMTREE_ASYNC_TOP=0.  (The proposal of spamtree_fit.cpp:211-229 does not depend on the sweep.) */
 /* Contract: between st_factor_begin(slot, theta) and the st_factor / st_factor_local that picks its result up, st_swap is
  * refused (ST_ERR_USAGE: the arena being written would become the accepted slot); readers of the slot (st_get_block,
- * st_get_comps, st_loglik_w(1), st_mg_pack_comps) are ordered behind the launches in flight. */
+ * st_get_comps, st_loglik_w(1), st_mg_pack_comps) are ordered behind the launches in flight.
+ * From st_factor_begin(slot, theta) on, the slot's caches are those of no theta (its top levels are theta's, the rest what was
+ * there) until a factorisation of that slot succeeds.  The next factorisation of EITHER slot ends the ahead-of-time state: for
+ * the same slot and a theta equal in every entry it continues from the result; for another theta or the other slot the result
+ * is dropped and every level runs in full, as if st_factor_begin had not been called (the dropped launches are waited for, so
+ * nothing overlaps them).  A st_factor_begin after another one replaces it. */
 int st_factor_begin(st_handle h, int slot, const double *theta, int ntheta);
 int st_factor_ahead_levels(st_handle h);   /* how many leading levels st_factor_begin runs ahead (0: none) */
 /* measurement only: 0 switches the ahead-of-time path off (st_factor_begin becomes a no-op, every level runs inside
@@ -141,7 +171,9 @@ int st_sample_w_loglik(st_handle h, const double *z, uint64_t seed, uint32_t ite
 /* The same pair without its host synchronisation (spamtree_fit.cpp:182-185 then :211-289: the sweep's log-density is not read
  * before the Metropolis step): _begin enqueues sweep + phase C and returns; any later synchronising call (st_factor) brings the
  * results along; _end returns what st_sample_w_loglik would have (0 and *loglik, or the sweep's failure code 10 / 11).  One
- * _end per _begin, before the next sweep.  Multi-GPU handles run the synchronous protocol inside _begin. */
+ * _end per _begin, before the next sweep.  Multi-GPU handles run the synchronous protocol inside _begin.
+ * While a sweep is pending the handle's w is the sweep's (stream order) but no call that reads or replaces it on the host, runs
+ * another sweep, predicts or swaps is accepted: the table next to st_factor_enqueue lists what is legal and what is refused. */
 int st_sample_w_loglik_begin(st_handle h, const double *z, uint64_t seed, uint32_t iter, int slot);
 int st_sample_w_loglik_end(st_handle h, double *loglik);
 

@@ -388,14 +388,32 @@ static int download_rows(st_handle h, const double *src, double *dst) {
   return ST_OK;
 }
 
+// The call contract of the two split operations (include/spamtree_hip.h, next to st_factor_enqueue and st_sample_w_loglik_begin):
+// what would read or replace state that the open half is still producing is refused BEFORE it changes anything on the handle.
+// Checked at the C-ABI entry points only: the library's own compositions (st_factor = _enqueue + _finish, ...) call the inner
+// steps while neither flag is set.  slot < 0: whatever the slot.
+static int refuse_factor_open(st_handle h, const char *who, int slot = -1) {
+  if (!h->factor_open || (slot >= 0 && slot != h->factor_open_slot)) return ST_OK;
+  h->err = std::string(who) + " between st_factor_enqueue and st_factor_finish";
+  if (slot >= 0) h->err += " on the slot being factorised";
+  return ST_ERR_USAGE;
+}
+static int refuse_sweep_pending(st_handle h, const char *who) {
+  if (!h->c_pending) return ST_OK;
+  h->err = std::string(who) + " between st_sample_w_loglik_begin and st_sample_w_loglik_end";
+  return ST_ERR_USAGE;
+}
+
 extern "C" int st_set_w(st_handle h, const double *w) {
   if (!h || !w) return ST_ERR_USAGE;
+  if (const int rc = refuse_sweep_pending(h, "st_set_w")) return rc;
   invalidate_stats(h);
   HCHK(h, hipSetDevice(h->device));
   return upload_rows(h, w, h->d_w.p);
 }
 extern "C" int st_get_w(st_handle h, double *w) {
   if (!h || !w) return ST_ERR_USAGE;
+  if (const int rc = refuse_sweep_pending(h, "st_get_w")) return rc;
   HCHK(h, hipSetDevice(h->device));
   return download_rows(h, h->d_w.p, w);
 }
@@ -486,6 +504,8 @@ static int complete_leaf(st_handle h, int slot) {
 }
 extern "C" int st_swap(st_handle h) {
   if (!h) return ST_ERR_USAGE;
+  if (const int rc = refuse_factor_open(h, "st_swap")) return rc;
+  if (const int rc = refuse_sweep_pending(h, "st_swap")) return rc;
   if (h->top_pending) {   // the proposal's top levels are being written into the arena that would become the accepted slot
     h->err = "st_swap between st_factor_begin and the st_factor / st_factor_local that picks its result up";
     return ST_ERR_USAGE;
@@ -712,6 +732,7 @@ extern "C" int st_factor_ahead_enable(st_handle h, int enable) {
 }
 extern "C" int st_factor_begin(st_handle h, int slot, const double *theta, int ntheta) {
   if (!h || !theta || slot < 0 || slot > 1) return ST_ERR_USAGE;
+  if (const int rc = refuse_factor_open(h, "st_factor_begin")) return rc;
   if (!h->async_top || h->async_top_off) return ST_OK;
   HCHK(h, hipSetDevice(h->device));
   CovPar cp;
@@ -753,7 +774,10 @@ static int stats_begin(st_handle h) {
 }
 
 static int factor_local(st_handle h, int slot, const double *theta, int ntheta, bool vonly);
-extern "C" int st_factor_local(st_handle h, int slot, const double *theta, int ntheta) { return factor_local(h, slot, theta, ntheta, false); }
+extern "C" int st_factor_local(st_handle h, int slot, const double *theta, int ntheta) {
+  if (h) { if (const int rc = refuse_factor_open(h, "st_factor_local")) return rc; }
+  return factor_local(h, slot, theta, ntheta, false);
+}
 static int factor_local(st_handle h, int slot, const double *theta, int ntheta, bool vonly) {
   if (!h || !theta || slot < 0 || slot > 1) return ST_ERR_USAGE;
   HCHK(h, hipSetDevice(h->device));
@@ -851,6 +875,7 @@ extern "C" int st_comm_init(st_handle h, const void *unique_id) {
 static int factor_enqueue(st_handle h, int slot, const double *theta, int ntheta, bool vonly);
 extern "C" int st_factor(st_handle h, int slot, const double *theta, int ntheta, double *loglik) {
   if (!h) return ST_ERR_USAGE;
+  if (const int rc = refuse_factor_open(h, "st_factor")) return rc;
   if (uses_exchange(h)) {
     if (!h->comm) return refuse_without_comm(h, "st_factor_local / st_mg_pack_comps / (all-reduce) / st_mg_finish");
     int rc = st_factor_local(h, slot, theta, ntheta);
@@ -933,6 +958,8 @@ static int sweep_exchange(st_handle h, const double *z, uint64_t seed, uint32_t 
 // st_sample_w followed by st_loglik_w(slot) with ONE synchronisation.
 extern "C" int st_sample_w_loglik(st_handle h, const double *z, uint64_t seed, uint32_t iter, int slot, double *loglik) {
   if (!h || slot < 0 || slot > 1) return ST_ERR_USAGE;
+  if (const int rc = refuse_factor_open(h, "st_sample_w_loglik")) return rc;
+  if (const int rc = refuse_sweep_pending(h, "st_sample_w_loglik")) return rc;
   { const int rc0 = complete_leaf(h, slot); if (rc0) return rc0; }
   if (!uses_exchange(h)) {
     const int rc = enqueue_sweep_loglik(h, z, seed, iter, slot, &h->pin->sweep);
@@ -984,7 +1011,8 @@ extern "C" int st_sample_w_loglik(st_handle h, const double *z, uint64_t seed, u
 // With a communicator attached (multi-GPU) _begin simply runs the synchronous protocol and _end hands its result over.
 extern "C" int st_sample_w_loglik_begin(st_handle h, const double *z, uint64_t seed, uint32_t iter, int slot) {
   if (!h || slot < 0 || slot > 1) return ST_ERR_USAGE;
-  if (h->c_pending) return ST_ERR_USAGE;
+  if (const int rc = refuse_factor_open(h, "st_sample_w_loglik_begin")) return rc;
+  if (const int rc = refuse_sweep_pending(h, "st_sample_w_loglik_begin")) return rc;
   { const int rc0 = complete_leaf(h, slot); if (rc0) return rc0; }
   if (uses_exchange(h)) {
     h->c_ll = 0.0;
@@ -1000,7 +1028,8 @@ extern "C" int st_sample_w_loglik_begin(st_handle h, const double *z, uint64_t s
   return ST_OK;
 }
 extern "C" int st_sample_w_loglik_end(st_handle h, double *loglik) {
-  if (!h || !h->c_pending) return ST_ERR_USAGE;
+  if (!h) return ST_ERR_USAGE;
+  if (!h->c_pending) { h->err = "st_sample_w_loglik_end without st_sample_w_loglik_begin"; return ST_ERR_USAGE; }
   h->c_pending = false;
   if (h->c_rc != INT_MIN) {   // the synchronous protocol ran in _begin
     if (h->c_rc == ST_OK && loglik) *loglik = h->c_ll;
@@ -1220,6 +1249,8 @@ extern "C" int st_mg_gather_w_unpack(st_handle h) {
 
 extern "C" int st_sample_w(st_handle h, const double *z, uint64_t seed, uint32_t iter) {
   if (!h) return ST_ERR_USAGE;
+  if (const int rc = refuse_factor_open(h, "st_sample_w")) return rc;
+  if (const int rc = refuse_sweep_pending(h, "st_sample_w")) return rc;
   if (uses_exchange(h)) {
     if (!h->comm) return refuse_without_comm(h, "st_sample_w_local / st_mg_top_region / st_sample_w_top / st_mg_pack_w / st_mg_unpack_w");
     void *snd = nullptr, *rcv = nullptr;
@@ -1287,6 +1318,8 @@ static int fix_top_comps(st_handle h, int phys) {
 }
 extern "C" int st_loglik_w(st_handle h, int slot, double *loglik) {
   if (!h) return ST_ERR_USAGE;
+  if (slot >= 0 && slot <= 1) { if (const int rc = refuse_factor_open(h, "st_loglik_w", slot)) return rc; }
+  if (const int rc = refuse_sweep_pending(h, "st_loglik_w")) return rc;
   if (slot >= 0 && slot <= 1) { const int rc0 = complete_leaf(h, slot); if (rc0) return rc0; }
   if (uses_exchange(h)) {
     if (!h->comm) return refuse_without_comm(h, "st_loglik_local / st_mg_pack_comps / (all-reduce) / st_mg_finish");
@@ -1306,6 +1339,8 @@ extern "C" int st_loglik_w(st_handle h, int slot, double *loglik) {
 extern "C" int st_predict(st_handle h, int theta_changed) {
   (void)theta_changed;  // H of a prediction block is rebuilt from the ancestor chain every call: same values as the cache
   if (!h) return ST_ERR_USAGE;
+  if (const int rc = refuse_factor_open(h, "st_predict")) return rc;
+  if (const int rc = refuse_sweep_pending(h, "st_predict")) return rc;
   if (h->pred_list.empty()) return ST_OK;
   invalidate_stats(h);
   if (!h->z_valid) { h->err = "st_predict needs the normals of a preceding st_sample_w (spamtree_model.cpp:1325)"; return ST_ERR_USAGE; }
@@ -1406,6 +1441,7 @@ extern "C" int st_xtx(st_handle h, double *xtx) {
 
 extern "C" int st_yhat(st_handle h, const double *noise, uint64_t seed, uint32_t iter, double *yhat) {
   if (!h || !yhat) return ST_ERR_USAGE;
+  if (const int rc = refuse_sweep_pending(h, "st_yhat")) return rc;
   HCHK(h, hipSetDevice(h->device));
   int rc = gen_or_upload_z(h, noise, seed, iter, 5u, h->d_tmp_n.p);
   if (rc) return rc;
@@ -1428,6 +1464,7 @@ extern "C" int st_block_dims(st_handle h, int64_t u, int64_t *m, int64_t *P, int
 }
 extern "C" int st_get_block(st_handle h, int slot, int64_t u, double *negRiH, double *Ri) {
   if (!h || u < 0 || u >= h->n_blocks || slot < 0 || slot > 1) return ST_ERR_USAGE;
+  if (const int rc = refuse_factor_open(h, "st_get_block", slot)) return rc;
   const Blk &B = h->blks[h->blk_model2dev[u]];
   if (B.panel_off < 0) { h->err = "block has no observations, hence no cache"; return ST_ERR_USAGE; }
   HCHK(h, hipSetDevice(h->device));
@@ -1452,6 +1489,7 @@ extern "C" int st_get_block(st_handle h, int slot, int64_t u, double *negRiH, do
 }
 extern "C" int st_get_comps(st_handle h, int slot, double *logdet_c, double *loglik_c) {
   if (!h || slot < 0 || slot > 1) return ST_ERR_USAGE;
+  if (const int rc = refuse_factor_open(h, "st_get_comps", slot)) return rc;
   HCHK(h, hipSetDevice(h->device));
   { const int rc0 = settle_top(h); if (rc0) return rc0; }
   const int phys = h->slot_map[slot];

@@ -144,6 +144,22 @@ def test_deferred_sweep_protocol_failure_and_misuse():
     hm.set_w(np.zeros(pb["n"]))
     assert lib.st_sample_w_loglik_begin(h, z.ctypes.data_as(dp), 0, 0, 0) == 0
     assert lib.st_sample_w_loglik_begin(h, z.ctypes.data_as(dp), 0, 0, 0) < 0                  # a second _begin without _end: usage error
+    # ... like every other sweep, and whatever reads or replaces w on the host, predicts, swaps or takes a log-density (the
+    # header's table next to st_factor_enqueue): refused with a text that names the call, nothing changed -- _end below still
+    # hands over the synchronous pair's results
+    buf = np.zeros(pb["n"])
+    llx = C.c_double()
+    zp = z.ctypes.data_as(dp)
+    for name, call in [("st_sample_w_loglik_begin", lambda: lib.st_sample_w_loglik_begin(h, zp, 0, 0, 0)),
+                       ("st_sample_w", lambda: lib.st_sample_w(h, zp, 0, 0)),
+                       ("st_sample_w_loglik", lambda: lib.st_sample_w_loglik(h, zp, 0, 0, 0, C.byref(llx))),
+                       ("st_set_w", lambda: lib.st_set_w(h, buf.ctypes.data_as(dp))), ("st_get_w", lambda: lib.st_get_w(h, buf.ctypes.data_as(dp))),
+                       ("st_predict", lambda: lib.st_predict(h, 1)), ("st_yhat", lambda: lib.st_yhat(h, zp, 0, 0, buf.ctypes.data_as(dp))),
+                       ("st_swap", lambda: lib.st_swap(h)), ("st_loglik_w", lambda: lib.st_loglik_w(h, 0, C.byref(llx)))]:
+        assert call() == -1, name
+        text = lib.st_last_error(h).decode()
+        assert text.startswith(name + " ") and "st_sample_w_loglik_end" in text, (name, text)
+    assert np.all(buf == 0.0)
     ll_f = C.c_double()
     assert lib.st_factor(h, 1, th.ctypes.data_as(dp), th.size, C.byref(ll_f)) == 0
     ll_def = C.c_double()
@@ -204,6 +220,29 @@ def test_factor_in_two_halves_equals_st_factor():
     assert lib.st_factor_finish(h, C.byref(ll1)) < 0                      # nothing enqueued
     assert lib.st_factor_enqueue(h, 1, th.ctypes.data_as(dp), th.size) == 0
     assert lib.st_factor_enqueue(h, 1, th.ctypes.data_as(dp), th.size) < 0   # a second one before the first is finished
+    # what would read or replace the slot being factorised, sweep, predict or swap is refused with a text that names the call, and
+    # changes nothing (the header's table next to st_factor_enqueue): the log-density below still equals st_factor's
+    zb = rng.standard_normal(pb["n"]); zp = zb.ctypes.data_as(dp)
+    buf, big = np.zeros(pb["n"]), np.zeros(pb["n"] * 8)
+    llx = C.c_double()
+    thp = th.ctypes.data_as(dp)
+    w_before = hm.get_w().copy()
+    for name, call in [("st_swap", lambda: lib.st_swap(h)), ("st_sample_w", lambda: lib.st_sample_w(h, zp, 0, 0)),
+                       ("st_sample_w_loglik", lambda: lib.st_sample_w_loglik(h, zp, 0, 0, 0, C.byref(llx))),
+                       ("st_sample_w_loglik_begin", lambda: lib.st_sample_w_loglik_begin(h, zp, 0, 0, 0)),
+                       ("st_predict", lambda: lib.st_predict(h, 1)), ("st_factor", lambda: lib.st_factor(h, 0, thp, th.size, C.byref(llx))),
+                       ("st_factor", lambda: lib.st_factor(h, 1, thp, th.size, C.byref(llx))),
+                       ("st_factor_begin", lambda: lib.st_factor_begin(h, 1, thp, th.size)),
+                       ("st_factor_local", lambda: lib.st_factor_local(h, 1, thp, th.size)),
+                       ("st_get_block", lambda: lib.st_get_block(h, 1, 0, big.ctypes.data_as(dp), big.ctypes.data_as(dp))),
+                       ("st_get_comps", lambda: lib.st_get_comps(h, 1, buf.ctypes.data_as(dp), buf.ctypes.data_as(dp))),
+                       ("st_loglik_w", lambda: lib.st_loglik_w(h, 1, C.byref(llx)))]:
+        assert call() == -1, name
+        text = lib.st_last_error(h).decode()
+        assert text.startswith(name + " ") and "st_factor_finish" in text, (name, text)
+    assert lib.st_loglik_w(h, 0, C.byref(llx)) == 0 and abs(llx.value - hm.loglik_w[0]) <= 1e-9 * abs(hm.loglik_w[0])   # the accepted slot stays readable ...
+    assert lib.st_get_comps(h, 0, buf.ctypes.data_as(dp), buf.ctypes.data_as(dp)) == 0
+    assert np.array_equal(hm.get_w(), w_before)                                           # ... and so does w
     t2 = np.array([1.0 / 0.3]); b2 = np.full(pb["p"], 0.25)
     assert lib.st_set_tausq_inv(h, t2.ctypes.data_as(dp)) == 0 and lib.st_set_beta(h, b2.ctypes.data_as(dp)) == 0
     t2[:] = -1.0; b2[:] = 99.0                                               # the caller's buffers are free on return
