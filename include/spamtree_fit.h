@@ -283,6 +283,22 @@ int stm_mcmc_criteria(const st_problem *pb, const st_options *opt, const double 
                       const stm_flags *flags, double *w_mcmc, double *yhat_mcmc, double *beta_mcmc, double *tausq_mcmc,
                       double *theta_mcmc, double *paramsd, double *mcmc_time, const stm_criteria *criteria);
 
+/* Leave-one-out criteria with the latent field integrated out (include/spamtree_hip.h, st_rows_loo_*).  stm_mcmc_loo is
+ * stm_mcmc_criteria plus one stm_loo: st_rows_loo_set before the first factorisation, and on every saved iteration
+ * st_rows_loo_accumulate at the point where st_rows_score_accumulate runs.  It draws nothing: every output of spamtree_mv_mcmc_c and
+ * of stm_mcmc_criteria is the same bit for bit.  criteria may be NULL (no conditional criteria); loo NULL: stm_mcmc_criteria itself.
+ * stm_loo carries the outputs of st_rows_loo_get (n_all each; n_accumulated, n_skipped: one count each) and of st_rows_loo_totals
+ * (tot: ST_ROWS_LOO_N x q column-major; n_obs: q); any may be NULL.  limited_tree problems are refused (ST_ERR_UNSUPPORTED). */
+typedef struct stm_loo {
+  double *elpd_loo, *pit_loo, *mu_loo, *weight_ess;
+  double *tot;
+  int64_t *n_obs, *n_accumulated, *n_skipped;
+} stm_loo;
+int stm_mcmc_loo(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta, int ntheta,
+                 const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn, int mcmc_thin, uint64_t seed,
+                 const stm_flags *flags, double *w_mcmc, double *yhat_mcmc, double *beta_mcmc, double *tausq_mcmc,
+                 double *theta_mcmc, double *paramsd, double *mcmc_time, const stm_criteria *criteria, const stm_loo *loo);
+
 #ifdef __cplusplus
 }
 #endif

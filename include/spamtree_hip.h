@@ -645,6 +645,45 @@ int st_rows_score_get(st_handle h, double *lppd, double *p_waic, double *mean_ll
 int st_rows_score_totals(st_handle h, double *obs, double *held, int64_t *n_obs, int64_t *n_held);
 int st_rows_score_info(st_handle h, double *alg_bytes);
 
+/* ---- leave-one-out criteria with the latent field integrated out, on the device.  Unlike st_rows_score_*, which is conditional
+ * on w, saved draw s gives an observed row i of margin j the density of y_i with its own w_i integrated out against the prior
+ * full conditional w_i | w_-i, theta ~ N(m_i, v_i) of the tree's DAG:  v_i = 1 / Q_ii,  m_i = w_i - (Qw)_i / Q_ii,  Q = sum_u L_u' L_u
+ * over slot 0's panels of the blocks with observed rows (prediction blocks take no part; spamtree_amd/csrc/loo_kernels.hpp has the
+ * definition, the order of every sum and the rounding bound).  mu_s = XB_i + m_i, sigma2_s = v_i + 1 / tausq_inv_j,
+ * l_s = log N(y_i; mu_s, sigma2_s), Phi_s = Phi((y_i - mu_s) / sigma_s), and over the S accumulated draws, r_s = exp(-l_s):
+ *   elpd_loo_i = -log((1 / S) sum r_s)   (estimates log p(y_i | y_-i): E_post[1 / p(y_i | w_-i, theta, beta, tau2)] = 1 / p(y_i | y_-i)),
+ *   pit_loo_i = sum r_s Phi_s / sum r_s,   mu_loo_i = sum r_s mu_s / sum r_s,   weight_ess_i = (sum r_s)^2 / sum r_s^2.
+ * No Pareto smoothing and no k-hat: weight_ess is the diagnostic.  No leave-one-out for NA rows (pass them as new points).
+ * st_rows_loo_set: allocates and zeroes the state; st_rows_loo_clear frees it.
+ * st_rows_loo_accumulate: one draw from the current w, XB, tausq_inv and slot 0 (a deferred leaf half is finished first, as
+ *   st_simulate does): one launch per level from the deepest to the root.  It consumes no Philox draw, copies nothing to the host,
+ *   synchronises nothing and changes no state but its own.  A draw whose l_s is not finite at a row is skipped there and counted.
+ * st_rows_loo_last: Q_ii, (Qw)_i, m_i and v_i of the last accumulate, n_all values each in model row order, for every row of a
+ *   block of the density (NA rows of such a block included); NaN at the rows of prediction blocks.
+ * st_rows_loo_get: n_all values each, model row order, NaN where a row has no observed y (or every draw was skipped); n_skipped is
+ *   the number of (row, draw) pairs skipped.  A row's sums run over the draws not skipped at that row.
+ * st_rows_loo_totals: tot is ST_ROWS_LOO_N x q column-major (column j = outcome j) over the outcome's observed rows; n_obs: q counts.
+ * st_rows_loo_info: the bit set of routes of one accumulate (bit code - 1), its algorithmic bytes and flops, from shapes.
+ * st_rows_loo_route_name: the kernel behind a route code (NULL outside the table).
+ * Any output may be NULL.  Refused with a text, the handle stays usable: limited_tree and world > 1 handles (ST_ERR_UNSUPPORTED);
+ * any call before _set, _accumulate before slot 0 was factorised, _get / _totals / _last before the first accumulate (ST_ERR_USAGE). */
+#define ST_ROWS_LOO_ELPD 0
+#define ST_ROWS_LOO_LOOIC 1
+#define ST_ROWS_LOO_SQERR 2
+#define ST_ROWS_LOO_PIT 3
+#define ST_ROWS_LOO_MIN_ESS 4
+#define ST_ROWS_LOO_COUNT 5
+#define ST_ROWS_LOO_N 6
+int st_rows_loo_set(st_handle h);
+int st_rows_loo_clear(st_handle h);
+int st_rows_loo_accumulate(st_handle h);
+int st_rows_loo_last(st_handle h, double *q_diag, double *qw, double *cond_mean, double *cond_var);
+int st_rows_loo_get(st_handle h, double *elpd_loo, double *pit_loo, double *mu_loo, double *weight_ess, int64_t *n_accumulated,
+                    int64_t *n_skipped);
+int st_rows_loo_totals(st_handle h, double *tot, int64_t *n_obs);
+int st_rows_loo_info(st_handle h, int32_t *route_mask, double *alg_bytes, double *flops);
+const char *st_rows_loo_route_name(int32_t code);
+
 /* ---- prior simulation from slot 0: exact draws w ~ N(0, C_DAG) of the tree's own model and y = XB + w + sqrt(tau^2_j) eps.
  * st_simulate: a root-to-leaf sweep over slot 0 as the last st_factor(h, 0, theta) left it (a deferred leaf half is finished
  *   first), Ri_u w_u = z_u - N_u w_pa(u) per block, with the handle's current beta (XB) and tau^-2.  nd draws (1..16) in one

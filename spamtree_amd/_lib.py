@@ -174,6 +174,14 @@ SIGNATURES = {
     "st_rows_score_get": (C.c_int, [H, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_ip]),
     "st_rows_score_totals": (C.c_int, [H, c_dp, c_dp, c_ip, c_ip]),
     "st_rows_score_info": (C.c_int, [H, c_dp]),
+    "st_rows_loo_set": (C.c_int, [H]),
+    "st_rows_loo_clear": (C.c_int, [H]),
+    "st_rows_loo_accumulate": (C.c_int, [H]),
+    "st_rows_loo_last": (C.c_int, [H, c_dp, c_dp, c_dp, c_dp]),
+    "st_rows_loo_get": (C.c_int, [H, c_dp, c_dp, c_dp, c_dp, c_ip, c_ip]),
+    "st_rows_loo_totals": (C.c_int, [H, c_dp, c_ip]),
+    "st_rows_loo_info": (C.c_int, [H, C.POINTER(C.c_int32), c_dp, c_dp]),
+    "st_rows_loo_route_name": (C.c_char_p, [C.c_int32]),
     "st_simulate": (C.c_int, [H, C.c_int, c_dp, c_dp, C.c_uint64, C.c_uint32, c_dp, c_dp]),
     "st_simulate_info": (C.c_int, [H, C.c_int, C.POINTER(C.c_int32), c_dp, c_dp]),
     "st_simulate_route_name": (C.c_char_p, [C.c_int32]),
@@ -205,6 +213,12 @@ class StmCriteria(C.Structure):   # include/spamtree_fit.h, stm_criteria
 
 ST_ROWS_OBS = ("lppd", "p_waic", "waic", "Dbar", "Dhat", "p_D", "dic")   # include/spamtree_hip.h: ST_ROWS_OBS_*, ST_ROWS_HELD_*
 ST_ROWS_HELD = ("lppd", "pit", "crps", "sqerr")
+ST_ROWS_LOO = ("elpd_loo", "looic", "sqerr", "pit", "min_weight_ess", "count")   # ST_ROWS_LOO_*
+
+
+class StmLoo(C.Structure):   # include/spamtree_fit.h, stm_loo
+    _fields_ = [("elpd_loo", c_dp), ("pit_loo", c_dp), ("mu_loo", c_dp), ("weight_ess", c_dp), ("tot", c_dp), ("n_obs", c_ip),
+                ("n_accumulated", c_ip), ("n_skipped", c_ip)]
 
 # include/spamtree_fit.h (C++ host driver)
 SIGNATURES.update({
@@ -277,6 +291,7 @@ SIGNATURES["stm_mcmc_chains_last_error"] = (C.c_char_p, [])
 
 SIGNATURES["stm_rows_score_set"] = (C.c_int, [H, c_dp])
 SIGNATURES["stm_mcmc_criteria"] = (C.c_int, SIGNATURES["spamtree_mv_mcmc_c"][1] + [C.POINTER(StmCriteria)])
+SIGNATURES["stm_mcmc_loo"] = (C.c_int, SIGNATURES["stm_mcmc_criteria"][1] + [C.POINTER(StmLoo)])
 
 # include/spamtree_tree.h (device parts of the tree builder)
 c_i32p = C.POINTER(C.c_int32)

@@ -473,12 +473,13 @@ struct FitPoints {   // the point set of stm_mcmc_points and where its per-draw 
 // The whole of spamtree_mv_mcmc (spamtree_fit.cpp:5-430), on a created chain.  With pts, every saved iteration also predicts at the
 // point set once tausq and beta are drawn: the saved theta's factor in slot 0, the saved w, beta and tausq; draw counter = saved
 // index, Philox streams 6 / 7 only, so the chain itself is the same draw for draw.  With crit, every saved iteration also updates
-// the criteria over the fit's own rows (st_rows_score_accumulate) and, when their CRPS is wanted, stores the iteration's yhat on
+// the criteria over the fit's own rows (st_rows_score_accumulate; with loo also st_rows_loo_accumulate, right after it) and, when their CRPS is wanted, stores the iteration's yhat on
 // the device (st_summary_accumulate: stream 5 with the iteration's counter, what st_yhat draws).  With store_rows every saved
 // iteration makes that st_summary_accumulate call (the caller has reserved the room): the stores the diagnostics read.
 static int run_fit(stm_chain c, int mcmc_keep, int mcmc_burn, int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc,
                    double *yhat_mcmc, double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
-                   const FitPoints *pts, const stm_criteria *crit = nullptr, bool store_rows = false, int saved0 = 0, int keep_total = 0) {
+                   const FitPoints *pts, const stm_criteria *crit = nullptr, bool store_rows = false, int saved0 = 0, int keep_total = 0,
+                   bool loo = false) {
   // saved0, keep_total: this is one chain of stm_mcmc_chains -- its saved draw s goes to column saved0 + s of per-draw outputs that
   // have keep_total columns.  Every Philox counter stays the chain's own: the iteration m, and s for the point draws.
   if (keep_total == 0) keep_total = mcmc_keep;
@@ -532,6 +533,10 @@ static int run_fit(stm_chain c, int mcmc_keep, int mcmc_burn, int mcmc_thin, uin
       if (!rc && crit) {
         rc = st_rows_score_accumulate(c->h);
         if (!rc && crit->want_crps && crit->y_holdout) rc = st_summary_accumulate(c->h, seed, (uint32_t)m);
+        if (rc) c->err = st_last_error(c->h);
+      }
+      if (!rc && loo) {          // leave-one-out with w_i integrated out: reads w, XB, tausq_inv and slot 0, draws nothing
+        rc = st_rows_loo_accumulate(c->h);
         if (rc) c->err = st_last_error(c->h);
       }
       if (!rc && store_rows) {   // the diagnostics' draws of w and yhat (stream 5, the iteration's counter: st_yhat's yhat)
@@ -912,6 +917,44 @@ extern "C" int stm_mcmc_criteria(const st_problem *pb, const st_options *opt, co
   if (rc == 0 && cr && mcmc_keep > 0) {
     rc = st_rows_score_get(c->h, cr->lppd, cr->p_waic, cr->mean_ll, cr->mu_mean, cr->pit, cr->crps, cr->n_accumulated);
     if (rc == 0) rc = st_rows_score_totals(c->h, cr->obs, cr->held, cr->n_obs, cr->n_held);
+  }
+  stm_destroy(c);
+  return rc;
+}
+
+// stm_mcmc_criteria plus the leave-one-out criteria with the latent field integrated out; loo NULL: stm_mcmc_criteria itself
+extern "C" int stm_mcmc_loo(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
+                            int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
+                            int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
+                            double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
+                            const stm_criteria *criteria, const stm_loo *loo) {
+  if (!loo)
+    return stm_mcmc_criteria(pb, opt, set_unif_bounds, theta, ntheta, beta, tausq, mcmcsd, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags,
+                             w_mcmc, yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time, criteria);
+  const stm_criteria *cr = criteria;
+  const bool crps = cr && cr->want_crps && cr->y_holdout;
+  if (cr && cr->crps && !crps) return ST_ERR_USAGE;
+  if (crps && mcmc_keep > 16384) return ST_ERR_UNSUPPORTED;
+  if (cr && cr->y_holdout && flags && (!flags->sample_predicts || !flags->sample_w)) return ST_ERR_USAGE;
+  stm_chain c = nullptr;
+  int rc = stm_create(pb, opt, set_unif_bounds, mcmcsd, theta, ntheta, beta, tausq, seed, flags, &c);
+  if (rc == 0 && cr) rc = stm_rows_score_set(c, cr->y_holdout);
+  if (rc == 0) rc = st_rows_loo_set(c->h);                        // refusals (limited_tree): before any factorisation
+  if (rc == 0 && crps && mcmc_keep > 0) {
+    rc = st_summary_reset(c->h);
+    if (rc == 0) rc = st_summary_reserve(c->h, mcmc_keep);
+  }
+  if (rc == 0) rc = stm_init(c);
+  if (rc != 0) { stm_destroy(c); return rc; }
+  rc = run_fit(c, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc, yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time,
+               nullptr, cr, false, 0, 0, true);
+  if (rc == 0 && cr && mcmc_keep > 0) {
+    rc = st_rows_score_get(c->h, cr->lppd, cr->p_waic, cr->mean_ll, cr->mu_mean, cr->pit, cr->crps, cr->n_accumulated);
+    if (rc == 0) rc = st_rows_score_totals(c->h, cr->obs, cr->held, cr->n_obs, cr->n_held);
+  }
+  if (rc == 0 && mcmc_keep > 0) {
+    rc = st_rows_loo_get(c->h, loo->elpd_loo, loo->pit_loo, loo->mu_loo, loo->weight_ess, loo->n_accumulated, loo->n_skipped);
+    if (rc == 0) rc = st_rows_loo_totals(c->h, loo->tot, loo->n_obs);
   }
   stm_destroy(c);
   return rc;

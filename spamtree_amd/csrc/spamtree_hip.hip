@@ -1886,6 +1886,166 @@ extern "C" int st_rows_score_info(st_handle h, double *alg_bytes) {
   return ST_OK;
 }
 
+// ---- leave-one-out criteria with w_i integrated out (loo_kernels.hpp; the kernels and their launchers live in k_rows_loo.hip) ----
+static int loo_refuse(st_handle h, const char *who, bool need_set = true, bool need_draw = false) {
+  if (h->limited) { h->err = std::string(who) + ": limited_tree handles are not supported"; return ST_ERR_UNSUPPORTED; }
+  if (h->world > 1) { h->err = std::string(who) + ": multi-GPU handles are not supported"; return ST_ERR_UNSUPPORTED; }
+  if (need_set && !h->loo_set) { h->err = std::string(who) + " before st_rows_loo_set"; return ST_ERR_USAGE; }
+  if (need_draw && h->loo_n_acc == 0) { h->err = std::string(who) + ": no iteration accumulated"; return ST_ERR_USAGE; }
+  return ST_OK;
+}
+static void loo_free(st_handle h) {
+  h->d_loo_list.free(); h->d_loo_chptr.free(); h->d_loo_chidx.free(); h->d_loo_voff.free(); h->d_loo_S.free(); h->d_loo_last.free();
+  h->d_loo_acc.free(); h->d_loo_rows.free(); h->d_loo_tot.free();
+  h->loo_levels.clear();
+  h->loo_set = false; h->loo_n_acc = 0; h->loo_fin_acc = -1; h->loo_mask = 0; h->loo_bytes = h->loo_flops = 0;
+}
+extern "C" int st_rows_loo_set(st_handle h) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = loo_refuse(h, "st_rows_loo_set", false)) return rc;
+  LooLayout lay;
+  std::string msg;
+  if (const int rc = loo_layout(*h, lay, msg)) { h->err = "st_rows_loo_set: " + msg; return rc; }
+  HCHK(h, hipSetDevice(h->device));
+  const long long n = h->n_all;
+  std::vector<unsigned char> obs(n);
+  std::vector<int> mv(n);
+  HCHK(h, hipMemcpyAsync(obs.data(), h->d_obs.p, n * sizeof(unsigned char), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipMemcpyAsync(mv.data(), h->d_mv.p, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  std::vector<long long> nobs(h->q, 0);
+  for (long long i = 0; i < n; ++i) if (obs[i]) nobs[mv[i]]++;
+  DevBuf<int> d_list, d_chptr, d_chidx;   // the handle takes them once every allocation has succeeded
+  DevBuf<long long> d_voff;
+  DevBuf<double> d_S, d_last, d_acc, d_rows, d_tot;
+  HCHK(h, upload_or_dummy(d_list, lay.list)); HCHK(h, d_chptr.upload(lay.ch_ptr)); HCHK(h, upload_or_dummy(d_chidx, lay.ch_idx));
+  HCHK(h, d_voff.upload(lay.voff));
+  HCHK(h, d_S.alloc((size_t)std::max(lay.arena, 1ll)));
+  HCHK(h, d_last.upload(std::vector<double>((size_t)LOO_NLAST * n, std::nan(""))));
+  HCHK(h, d_acc.alloc((size_t)LOO_NACC * n)); HCHK(h, d_rows.alloc((size_t)LOO_NOUT * n)); HCHK(h, d_tot.alloc((size_t)h->q * LOO_NSUM));
+  HCHK(h, hipMemsetAsync(d_acc.p, 0, (size_t)LOO_NACC * n * sizeof(double), h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  loo_free(h);
+  h->d_loo_list = std::move(d_list); h->d_loo_chptr = std::move(d_chptr); h->d_loo_chidx = std::move(d_chidx);
+  h->d_loo_voff = std::move(d_voff); h->d_loo_S = std::move(d_S); h->d_loo_last = std::move(d_last); h->d_loo_acc = std::move(d_acc);
+  h->d_loo_rows = std::move(d_rows); h->d_loo_tot = std::move(d_tot);
+  for (const LooLevel &V : lay.levels) {
+    h->loo_levels.push_back(LooLevelLaunch{V.first, V.count, V.isref, V.maxLen, V.maxM});
+    h->loo_mask |= 1 << ((V.isref ? LOO_ROUTE_REF : LOO_ROUTE_LEAF) - 1);
+  }
+  h->loo_bytes = lay.alg_bytes; h->loo_flops = lay.flops;
+  h->loo_nobs_q = nobs;
+  h->loo_set = true;
+  return ST_OK;
+}
+extern "C" int st_rows_loo_clear(st_handle h) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = loo_refuse(h, "st_rows_loo_clear")) return rc;
+  HCHK(h, hipSetDevice(h->device));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  loo_free(h);
+  return ST_OK;
+}
+extern "C" int st_rows_loo_accumulate(st_handle h) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = loo_refuse(h, "st_rows_loo_accumulate")) return rc;
+  if (const int rc = refuse_factor_open(h, "st_rows_loo_accumulate", 0)) return rc;
+  if (const int rc = refuse_sweep_pending(h, "st_rows_loo_accumulate")) return rc;
+  if (h->theta[0].empty()) { h->err = "st_rows_loo_accumulate before st_factor(slot 0)"; return ST_ERR_USAGE; }
+  for (const LooLevelLaunch &L : h->loo_levels)
+    if (LOO_LDS(L.maxLen, L.maxM) > h->lds_limit) { h->err = "st_rows_loo_accumulate: a chain too long for the kernel's LDS"; return ST_ERR_UNSUPPORTED; }
+  HCHK(h, hipSetDevice(h->device));
+  if (const int rc = settle_top(h)) return rc;
+  if (const int rc = complete_leaf(h, 0)) return rc;
+  LooArgs A;
+  std::memset(&A, 0, sizeof(A));
+  A.blks = h->d_blks.p; A.anc_idx = h->d_anc.p; A.list = h->d_loo_list.p;
+  A.panels = h->d_panels[h->slot_map[0]].p;
+  A.w = h->d_w.p; A.xb = h->d_xb.p; A.y = h->d_y.p; A.tsq_inv = h->d_tsq.p; A.obs = h->d_obs.p; A.mv = h->d_mv.p;
+  A.voff = h->d_loo_voff.p; A.ch_ptr = h->d_loo_chptr.p; A.ch_idx = h->d_loo_chidx.p;
+  A.S = h->d_loo_S.p; A.last = h->d_loo_last.p; A.acc = h->d_loo_acc.p; A.n = h->n_all;
+  int mask = 0;
+  const int e = loo_launch(h->loo_levels.data(), (int)h->loo_levels.size(), A, h->stream, &mask);
+  if (e) { h->err = std::string("st_rows_loo_accumulate launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+  h->loo_n_acc += 1;
+  return ST_OK;
+}
+extern "C" int st_rows_loo_last(st_handle h, double *q_diag, double *qw, double *cond_mean, double *cond_var) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = loo_refuse(h, "st_rows_loo_last", true, true)) return rc;
+  HCHK(h, hipSetDevice(h->device));
+  double *const dst[LOO_NLAST] = {q_diag, qw, cond_mean, cond_var};   // LOO_LAST_* order
+  for (int k = 0; k < LOO_NLAST; ++k)
+    if (dst[k])
+      if (const int rc = download_rows(h, h->d_loo_last.p + (size_t)k * h->n_all, dst[k])) return rc;
+  return ST_OK;
+}
+// the per-row outputs and the totals, once per number of accumulated draws
+static int loo_finish(st_handle h) {
+  if (h->loo_fin_acc == h->loo_n_acc) return ST_OK;
+  LooFinishArgs F;
+  F.y = h->d_y.p; F.obs = h->d_obs.p; F.mv = h->d_mv.p; F.acc = h->d_loo_acc.p; F.n = h->n_all; F.S = (double)h->loo_n_acc; F.q = h->q;
+  F.rows = h->d_loo_rows.p; F.tot = h->d_loo_tot.p;
+  const int e = loo_finish_launch(F, h->stream);
+  if (e) { h->err = std::string("st_rows_loo finish launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+  h->loo_fin_acc = h->loo_n_acc;
+  return ST_OK;
+}
+extern "C" int st_rows_loo_get(st_handle h, double *elpd_loo, double *pit_loo, double *mu_loo, double *weight_ess, int64_t *n_accumulated,
+                               int64_t *n_skipped) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = loo_refuse(h, "st_rows_loo_get")) return rc;
+  if (n_accumulated) *n_accumulated = h->loo_n_acc;
+  if (const int rc = loo_refuse(h, "st_rows_loo_get", true, true)) return rc;
+  HCHK(h, hipSetDevice(h->device));
+  if (const int rc = loo_finish(h)) return rc;
+  double *const dst[LOO_NOUT] = {elpd_loo, pit_loo, mu_loo, weight_ess};   // LOO_OUT_* order
+  for (int k = 0; k < LOO_NOUT; ++k)
+    if (dst[k])
+      if (const int rc = download_rows(h, h->d_loo_rows.p + (size_t)k * h->n_all, dst[k])) return rc;
+  if (n_skipped) {
+    std::vector<double> ns(h->n_all);
+    HCHK(h, hipMemcpyAsync(ns.data(), h->d_loo_acc.p + (size_t)LOO_NS * h->n_all, h->n_all * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HCHK(h, hipStreamSynchronize(h->stream));
+    long long tot = 0;
+    for (double v : ns) tot += (long long)v;
+    *n_skipped = tot;
+  }
+  return ST_OK;
+}
+extern "C" int st_rows_loo_totals(st_handle h, double *tot, int64_t *n_obs) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = loo_refuse(h, "st_rows_loo_totals", true, true)) return rc;
+  HCHK(h, hipSetDevice(h->device));
+  if (const int rc = loo_finish(h)) return rc;
+  std::vector<double> t((size_t)h->q * LOO_NSUM);
+  HCHK(h, hipMemcpyAsync(t.data(), h->d_loo_tot.p, t.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  for (int j = 0; j < h->q; ++j) {
+    const double *s = t.data() + (size_t)j * LOO_NSUM;
+    if (n_obs) n_obs[j] = h->loo_nobs_q[j];
+    if (!tot) continue;
+    double *o = tot + (size_t)j * ST_ROWS_LOO_N;
+    o[ST_ROWS_LOO_ELPD] = s[LOO_SUM_ELPD];
+    o[ST_ROWS_LOO_LOOIC] = -2.0 * s[LOO_SUM_ELPD];
+    o[ST_ROWS_LOO_SQERR] = s[LOO_SUM_SQERR];
+    o[ST_ROWS_LOO_PIT] = s[LOO_SUM_PIT];
+    o[ST_ROWS_LOO_MIN_ESS] = s[LOO_MIN_ESS];
+    o[ST_ROWS_LOO_COUNT] = (double)h->loo_nobs_q[j];
+    if (h->loo_nobs_q[j] == 0) { o[ST_ROWS_LOO_ELPD] = o[ST_ROWS_LOO_LOOIC] = 0.0; o[ST_ROWS_LOO_MIN_ESS] = std::nan(""); }
+  }
+  return ST_OK;
+}
+extern "C" int st_rows_loo_info(st_handle h, int32_t *route_mask, double *alg_bytes, double *flops) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = loo_refuse(h, "st_rows_loo_info")) return rc;
+  if (route_mask) *route_mask = h->loo_mask;
+  if (alg_bytes) *alg_bytes = h->loo_bytes;
+  if (flops) *flops = h->loo_flops;
+  return ST_OK;
+}
+extern "C" const char *st_rows_loo_route_name(int32_t code) { return loo_route_name(code); }
+
 // ---- prior simulation from slot 0 (st_simulate; the kernels and their launcher live in k_simulate.hip) ----
 static int sim_pad(int nd) { int p = 1; while (p < nd) p <<= 1; return p; }
 

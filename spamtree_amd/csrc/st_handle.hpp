@@ -5,6 +5,8 @@
 #include "tree_layout.hpp"
 #include "st_protocol.hpp"
 #include "simulate_kernels.hpp"
+#include "loo_layout.hpp"
+#include "loo_kernels.hpp"
 
 // A device allocation that frees itself; a null buffer makes no HIP call.  (The owner has the device current when it goes.)
 template <typename T>
@@ -80,6 +82,16 @@ struct st_handle_s : TreeLayout {
   long long rs_crps_epoch = -1;               // d_rs_crps holds the CRPS of the stored draws of that epoch (-1: none)
   long long rs_fin_acc = -1, rs_fin_crps = -2;   // d_rs_rows / d_rs_tot are those of rs_fin_acc draws, with the CRPS of that epoch summed (-1: without)
   double rs_tau2_sum[ST_MAX_Q] = {0};         // sum over the accumulated draws of 1 / tausq_inv_j, added in call order
+  // st_rows_loo_*: leave-one-out criteria with w_i integrated out (loo_kernels.hpp, loo_layout.hpp); device row order
+  DevBuf<int> d_loo_list, d_loo_chptr, d_loo_chidx;
+  DevBuf<long long> d_loo_voff;
+  DevBuf<double> d_loo_S, d_loo_last, d_loo_acc, d_loo_rows, d_loo_tot;
+  std::vector<LooLevelLaunch> loo_levels;
+  double loo_bytes = 0, loo_flops = 0;
+  bool loo_set = false;
+  int loo_mask = 0;
+  long long loo_n_acc = 0, loo_fin_acc = -1;  // d_loo_rows / d_loo_tot are those of loo_fin_acc draws
+  std::vector<long long> loo_nobs_q;
   bool stats_valid = false;                   // d_stats matches the current w and XB
   bool host_stats_valid = false;              // ... and host_stats holds a copy of it
   std::vector<double> host_stats;

@@ -10,7 +10,8 @@ import numpy as np
 from . import _lib
 from . import diagnostics as _diag
 from . import excursions as _exc
-from .model import (SpamTreeError, _dp, _f64, _i64, _ip, _lists_to_csr, functionals_csr, joint_labels, rows_criteria, rows_holdout, score_totals,
+from .model import (SpamTreeError, _dp, _f64, _i64, _ip, _lists_to_csr, functionals_csr, joint_labels, rows_criteria, rows_holdout,
+                    rows_loo_criteria, score_totals,
                     score_values, series_diag_buffers, series_diag_finish, excursion_spec, excursion_buffers, excursion_finish,
                     rank_spec, rank_buffers, rank_finish)
 
@@ -244,7 +245,7 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                      sample_theta=True, sample_w=True, sample_predicts=True, seed=2021, device=0, reference_quirks=True,
                      new_points=None, new_draws=True, new_quantiles=(), save_w=True, save_yhat=True, force_generic=False,
                      criteria=False, y_holdout=None, holdout_crps=True, diagnostics=False, diagnostics_max_lag=0, excursions=None,
-                     rank_diagnostics=None, chains=1, chain_seeds=None, chain_theta=None):
+                     rank_diagnostics=None, chains=1, chain_seeds=None, chain_theta=None, loo=False):
     """spamtree_fit.cpp:5-430 through the C++ driver.  `num_threads`, `use_alg`, the verbosity flags and `start_w` are
     accepted and ignored exactly where the reference ignores them (start_w, :95) or where they do not apply to a GPU.
 
@@ -281,6 +282,12 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     ``holdout_crps=False`` scores without it.  Not together with ``new_points``.  As with ``new_points``, a failure of the
     chain (a refusal of the library, a Cholesky failure code) raises SpamTreeError with ``code`` set, where the plain call prints
     "MCMC has been interrupted." and returns ``{"None": ...}``; a NaN log-density is a FloatingPointError in both.
+    ``loo=True``: leave-one-out criteria with each row's own w_i integrated out, on the device (stm_mcmc_loo: stm_mcmc_criteria plus
+    st_rows_loo_accumulate on every saved iteration; the chain and the conditional criteria are the same bit for bit).  It may be
+    combined with ``criteria`` / ``y_holdout`` and not with what ``criteria`` excludes.  The result's ``criteria["loo"]`` holds the
+    per-row arrays ``elpd_loo``, ``pit_loo``, ``mu_loo``, ``weight_ess`` (NaN where a row has no observed y), ``n_accumulated``,
+    ``n_skipped`` and ``totals`` = ``model.rows_loo_criteria``'s dict, overall and by outcome (``spamtree_amd.loo`` has the
+    definition).  No Pareto smoothing: ``weight_ess`` is the diagnostic.  ValueError before any device call for ``limited_tree``.
     ``diagnostics=True``: the effective sample size ``ess``, the Monte-Carlo standard error of the posterior mean ``mcse``, the
     posterior sd of the draws ``sd``, the split-R-hat of the one chain ``rhat``, the lags used ``lags`` and whether the lag cap was
     hit ``truncated`` (``spamtree_amd.diagnostics`` has the definition; ``diagnostics_max_lag`` = 0 is its default cap of 1024
@@ -323,7 +330,11 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     over all 2M half chains, the ESS of the combined chains) under the same keys, on the device for rows, points and functionals
     and on the host for theta, beta and tausq, with ``n_chains`` recorded in them; ``mcmc_keep`` is then the length of one chain.
     ValueError: ``M * mcmc_keep`` > 16384, M outside 1 .. 16, together with ``criteria`` / ``y_holdout`` (a separate driver)."""
-    crit = bool(criteria) or y_holdout is not None
+    crit_cond = bool(criteria) or y_holdout is not None
+    loo = bool(loo)
+    if loo and limited_tree:
+        raise ValueError("loo: limited_tree workloads are not supported (the leave-one-out criteria need the full chain factors)")
+    crit = crit_cond or loo   # one driver: what excludes criteria excludes loo
     M = int(chains)
     if not 1 <= M <= _diag.MAX_CHAINS:
         raise ValueError(f"chains = {M} must lie in 1 .. {_diag.MAX_CHAINS}")
@@ -387,7 +398,7 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     if crit:
         if new_points is not None:
             raise ValueError("criteria and new_points are separate drivers (stm_mcmc_criteria, stm_mcmc_scored): one per call")
-        y_hold = rows_holdout(y_holdout, y)
+        y_hold = rows_holdout(y_holdout, y) if crit_cond else None
         if y_hold is not None and not (sample_predicts and sample_w):
             raise ValueError("y_holdout needs sample_predicts and sample_w: the NA rows' w would be stale")
         want_crps = bool(holdout_crps) and y_hold is not None
@@ -487,12 +498,26 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
         nacc = C.c_int64()
         cs = _lib.StmCriteria(dp(y_hold), int(want_crps), *[dp(rows[key]) for key in ("lppd", "p_waic", "mean_ll", "mu_mean", "pit", "crps")],
                               _dp(tobs), _dp(theld), _ip(n_obs), _ip(n_held), C.pointer(nacc))
-        rc = lib.stm_mcmc_criteria(*common, C.byref(cs))
+        driver = "stm_mcmc_loo" if loo else "stm_mcmc_criteria"
+        if loo:
+            lrows = {key: np.zeros(n) for key in ("elpd_loo", "pit_loo", "mu_loo", "weight_ess")}
+            ltot, ln_obs = np.zeros((len(_lib.ST_ROWS_LOO), q), order="F"), np.zeros(q, dtype=np.int64)
+            lacc, lskip = C.c_int64(), C.c_int64()
+            ls = _lib.StmLoo(*[_dp(lrows[key]) for key in ("elpd_loo", "pit_loo", "mu_loo", "weight_ess")], _dp(ltot), _ip(ln_obs),
+                             C.pointer(lacc), C.pointer(lskip))
+            rc = lib.stm_mcmc_loo(*common, C.byref(cs) if crit_cond else None, C.byref(ls))
+        else:
+            rc = lib.stm_mcmc_criteria(*common, C.byref(cs))
         if rc == 0 and mcmc_keep > 0:
-            crit_out = dict(rows, n_accumulated=int(nacc.value),
-                            totals=rows_criteria(tobs, theld, n_obs, n_held, have_crps=rows["crps"] is not None))
+            crit_out = {}
+            if crit_cond:
+                crit_out = dict(rows, n_accumulated=int(nacc.value),
+                                totals=rows_criteria(tobs, theld, n_obs, n_held, have_crps=rows["crps"] is not None))
+            if loo:
+                crit_out["loo"] = dict(lrows, n_accumulated=int(lacc.value), n_skipped=int(lskip.value),
+                                       totals=rows_loo_criteria(ltot, ln_obs))
         elif rc not in (0, -10):
-            err = SpamTreeError(f"stm_mcmc_criteria failed ({rc})")
+            err = SpamTreeError(f"{driver} failed ({rc})")
             err.code = rc
             raise err
     elif new_points is None and M > 1:   # the plain chains: no point argument

@@ -241,6 +241,33 @@ def rows_criteria(obs, held, n_obs, n_held, have_crps=True):
     return dict(observed=observed, held_out=held_out)
 
 
+def rows_loo_criteria(tot, n_obs):
+    """st_rows_loo_totals' table (ST_ROWS_LOO_N x q, one column per outcome) as a dict, overall and ``by_outcome``: n, elpd_loo,
+    looic = -2 elpd_loo, the means mse, rmse and pit of the leave-one-out predictions, and min_weight_ess.  The overall elpd_loo and
+    the sums behind the means are the outcomes' in outcome order.  Marginal over each row's own w_i (``spamtree_amd.loo``)."""
+    tot = np.asarray(tot, dtype=np.float64).reshape(len(_lib.ST_ROWS_LOO), -1, order="F")
+    n_obs = np.asarray(n_obs, dtype=np.int64)
+    t = {k: tot[i].copy() for i, k in enumerate(_lib.ST_ROWS_LOO)}
+    nn = int(n_obs.sum())
+    sums = {}
+    for k in ("elpd_loo", "sqerr", "pit"):
+        a = 0.0
+        for v, c in zip(t[k], n_obs):          # in outcome order
+            if c > 0:
+                a = a + float(v)
+        sums[k] = a
+    with np.errstate(invalid="ignore", divide="ignore"):
+        by = dict(n=n_obs.copy(), elpd_loo=t["elpd_loo"], looic=t["looic"], mse=np.where(n_obs > 0, t["sqerr"] / n_obs, np.nan),
+                  pit=np.where(n_obs > 0, t["pit"] / n_obs, np.nan), min_weight_ess=t["min_weight_ess"])
+    by["rmse"] = np.sqrt(by["mse"])
+    ess = [float(v) for v, c in zip(t["min_weight_ess"], n_obs) if c > 0]
+    out = dict(n=nn, elpd_loo=sums["elpd_loo"], looic=-2.0 * sums["elpd_loo"], mse=sums["sqerr"] / nn if nn else float("nan"),
+               pit=sums["pit"] / nn if nn else float("nan"), min_weight_ess=min(ess) if ess else float("nan"))
+    out["rmse"] = float(np.sqrt(out["mse"]))
+    out["by_outcome"] = by
+    return out
+
+
 def functionals_csr(A, n_points):
     """Linear functionals of the predictions at ``n_points`` points as CSR ``(ptr, idx, wt)``, checked before any device call.
     ``A``: a ``(ptr, idx, wt)`` triple (a tuple of three whose entries are not themselves (indices, weights) pairs); a dense n_fun x n_points array, whose zeros are dropped; or a list of
@@ -909,6 +936,52 @@ class SpamTreeMV:
         by = C.c_double()
         self._check(self.lib.st_rows_score_info(self.h, C.byref(by)))
         return dict(alg_bytes=float(by.value))
+
+    # ---- leave-one-out criteria with each row's own w_i integrated out (st_rows_loo_*)
+    def rows_loo_set(self):
+        self._check(self.lib.st_rows_loo_set(self.h))
+
+    def rows_loo_clear(self):
+        self._check(self.lib.st_rows_loo_clear(self.h))
+
+    def rows_loo_accumulate(self):
+        """One draw from the current w, XB, tausq_inv and slot 0 into the state; nothing comes to the host."""
+        self._check(self.lib.st_rows_loo_accumulate(self.h))
+
+    def rows_loo_last(self):
+        """dict(q_diag, qw, cond_mean, cond_var) of the last accumulate: n_all values each, NaN at the rows of prediction blocks."""
+        out = {k: np.zeros(self.n_all) for k in ("q_diag", "qw", "cond_mean", "cond_var")}
+        self._check(self.lib.st_rows_loo_last(self.h, _dp(out["q_diag"]), _dp(out["qw"]), _dp(out["cond_mean"]), _dp(out["cond_var"])))
+        return out
+
+    def rows_loo_get(self):
+        """dict(elpd_loo, pit_loo, mu_loo, weight_ess, n_accumulated, n_skipped): n_all values each, NaN off the observed rows."""
+        out = {k: np.zeros(self.n_all) for k in ("elpd_loo", "pit_loo", "mu_loo", "weight_ess")}
+        cnt, skip = C.c_int64(), C.c_int64()
+        self._check(self.lib.st_rows_loo_get(self.h, _dp(out["elpd_loo"]), _dp(out["pit_loo"]), _dp(out["mu_loo"]), _dp(out["weight_ess"]),
+                                             C.byref(cnt), C.byref(skip)))
+        out["n_accumulated"], out["n_skipped"] = int(cnt.value), int(skip.value)
+        return out
+
+    def rows_loo_totals(self, raw=False):
+        """``rows_loo_criteria`` of st_rows_loo_totals' table; ``raw``: (tot, n_obs) as the library returned them."""
+        tot = np.zeros((len(_lib.ST_ROWS_LOO), self.q), order="F")
+        n_obs = np.zeros(self.q, dtype=np.int64)
+        self._check(self.lib.st_rows_loo_totals(self.h, _dp(tot), _ip(n_obs)))
+        return (tot, n_obs) if raw else rows_loo_criteria(tot, n_obs)
+
+    def rows_loo_info(self):
+        """dict(routes=[kernel names of one accumulate], alg_bytes, flops), from shapes."""
+        r = C.c_int32()
+        by, fl = C.c_double(), C.c_double()
+        self._check(self.lib.st_rows_loo_info(self.h, C.byref(r), C.byref(by), C.byref(fl)))
+        routes = []
+        code = 1
+        while self.lib.st_rows_loo_route_name(code) is not None:
+            if r.value & (1 << (code - 1)):
+                routes.append(self.lib.st_rows_loo_route_name(code).decode())
+            code += 1
+        return dict(routes=routes, alg_bytes=float(by.value), flops=float(fl.value))
 
     def points_info(self):
         """Of the last predict_points: dict(routes=[kernel names that ran], n_groups, alg_bytes, flops)."""
