@@ -220,7 +220,56 @@ class StmLoo(C.Structure):   # include/spamtree_fit.h, stm_loo
     _fields_ = [("elpd_loo", c_dp), ("pit_loo", c_dp), ("mu_loo", c_dp), ("weight_ess", c_dp), ("tot", c_dp), ("n_obs", c_ip),
                 ("n_accumulated", c_ip), ("n_skipped", c_ip)]
 
-# include/spamtree_fit.h (C++ host driver)
+
+class StmDiagnostics(C.Structure):   # include/spamtree_fit.h, stm_diagnostics
+    _fields_ = [("max_lag", C.c_int32), ("want_rows", C.c_int32), ("rows_w", StSeriesDiag), ("rows_yhat", StSeriesDiag),
+                ("new_w", StSeriesDiag), ("new_yhat", StSeriesDiag), ("fun_w", StSeriesDiag), ("fun_yhat", StSeriesDiag)]
+
+
+class StmExcursions(C.Structure):    # include/spamtree_fit.h, stm_excursions
+    _fields_ = [("want_rows", C.c_int32), ("rows_spec", StExcursionSpec), ("new_spec", StExcursionSpec), ("fun_spec", StExcursionSpec),
+                ("rows_w", StExcursionOut), ("rows_yhat", StExcursionOut), ("new_w", StExcursionOut), ("new_yhat", StExcursionOut),
+                ("fun_w", StExcursionOut), ("fun_yhat", StExcursionOut)]
+
+
+class StmRankDiagnostics(C.Structure):    # include/spamtree_fit.h, stm_rank_diagnostics
+    _fields_ = [("want_rows", C.c_int32), ("rows_spec", StRankSpec), ("new_spec", StRankSpec), ("fun_spec", StRankSpec),
+                ("rows_w", StRankOut), ("rows_yhat", StRankOut), ("new_w", StRankOut), ("new_yhat", StRankOut),
+                ("fun_w", StRankOut), ("fun_yhat", StRankOut)]
+
+
+class StmChains(C.Structure):             # include/spamtree_fit.h, stm_chains
+    _fields_ = [("n_chains", C.c_int32), ("seeds", C.POINTER(C.c_uint64)), ("theta0", c_dp), ("paramsd", c_dp), ("chain_time", c_dp)]
+
+
+class StmRun(C.Structure):                # include/spamtree_fit.h, stm_run: the twenty arguments of spamtree_mv_mcmc_c
+    _fields_ = [("pb", C.POINTER(StProblem)), ("opt", C.POINTER(StOptions)), ("set_unif_bounds", c_dp), ("theta", c_dp),
+                ("ntheta", C.c_int), ("beta", c_dp), ("tausq", C.c_double), ("mcmcsd", c_dp), ("mcmc_keep", C.c_int),
+                ("mcmc_burn", C.c_int), ("mcmc_thin", C.c_int), ("seed", C.c_uint64), ("flags", C.POINTER(StmFlags)),
+                ("w_mcmc", c_dp), ("yhat_mcmc", c_dp), ("beta_mcmc", c_dp), ("tausq_mcmc", c_dp), ("theta_mcmc", c_dp),
+                ("paramsd", c_dp), ("mcmc_time", c_dp)]
+
+
+class StmNewPoints(C.Structure):          # include/spamtree_fit.h, stm_new_points: the point arguments of stm_mcmc_points_joint
+    _fields_ = [("n_new", C.c_int64), ("coords_new", c_dp), ("mv_new", c_ip), ("anchor_new", c_ip), ("X_new", c_dp),
+                ("joint_id_new", c_ip), ("keep_draws", C.c_int64), ("quantiles", c_dp), ("n_quantiles", C.c_int32),
+                ("new_w", c_dp), ("new_cond_mean", c_dp), ("new_cond_var", c_dp), ("new_yhat", c_dp), ("new_mean", c_dp),
+                ("new_var", c_dp), ("new_w_mean", c_dp), ("new_yhat_mean", c_dp), ("new_w_q", c_dp), ("new_yhat_q", c_dp),
+                ("new_route", C.POINTER(C.c_int32)), ("new_cond_cov", c_dp), ("new_cov", c_dp)]
+
+
+class StmFit(C.Structure):                # include/spamtree_fit.h, stm_fit: the run and its optional parts (NULL: none)
+    _fields_ = [("run", StmRun), ("pts", C.POINTER(StmNewPoints)), ("fun", C.POINTER(StmFunctionals)), ("scores", C.POINTER(StmScores)),
+                ("diag", C.POINTER(StmDiagnostics)), ("exc", C.POINTER(StmExcursions)), ("rk", C.POINTER(StmRankDiagnostics)),
+                ("ch", C.POINTER(StmChains)), ("criteria", C.POINTER(StmCriteria)), ("loo", C.POINTER(StmLoo))]
+
+
+# include/spamtree_fit.h (C++ host driver).  The positional whole-fit entry points take the fields of the request in its order: the
+# run's, then (the points family) the point set's and one pointer per further part.  JOINT_ONLY: what stm_mcmc_points leaves out.
+JOINT_ONLY = ("joint_id_new", "new_cond_cov", "new_cov")
+_run = [t for _, t in StmRun._fields_]
+_points = [t for _, t in StmNewPoints._fields_]
+_parts = dict(StmFit._fields_[2:])
 SIGNATURES.update({
     "stm_create": (C.c_int, [C.POINTER(StProblem), C.POINTER(StOptions), c_dp, c_dp, c_dp, C.c_int, c_dp, C.c_double,
                              C.c_uint64, C.POINTER(StmFlags), C.POINTER(H)]),
@@ -230,68 +279,21 @@ SIGNATURES.update({
     "stm_handle": (C.c_void_p, [H]),
     "stm_step": (C.c_int, [H, C.c_int]),
     "stm_state": (C.c_int, [H, c_dp, c_dp, c_dp, c_dp, c_dp, c_ip, c_dp]),
-    "spamtree_mv_mcmc_c": (C.c_int, [C.POINTER(StProblem), C.POINTER(StOptions), c_dp, c_dp, C.c_int, c_dp, C.c_double,
-                                     c_dp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(StmFlags), c_dp, c_dp,
-                                     c_dp, c_dp, c_dp, c_dp, c_dp]),
     "stm_points_set": (C.c_int, [H, C.c_int64, c_dp, c_ip, c_ip, c_dp, C.c_int64]),
-    "stm_mcmc_points": (C.c_int, [C.POINTER(StProblem), C.POINTER(StOptions), c_dp, c_dp, C.c_int, c_dp, C.c_double, c_dp,
-                                  C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(StmFlags), c_dp, c_dp, c_dp, c_dp, c_dp,
-                                  c_dp, c_dp, C.c_int64, c_dp, c_ip, c_ip, c_dp, C.c_int64, c_dp, C.c_int32, c_dp, c_dp,
-                                  c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, C.POINTER(C.c_int32)]),
     "stm_points_set_joint": (C.c_int, [H, C.c_int64, c_dp, c_ip, c_ip, c_dp, c_ip, C.c_int64]),
-    "stm_mcmc_points_joint": (C.c_int, [C.POINTER(StProblem), C.POINTER(StOptions), c_dp, c_dp, C.c_int, c_dp, C.c_double, c_dp,
-                                        C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(StmFlags), c_dp, c_dp, c_dp, c_dp, c_dp,
-                                        c_dp, c_dp, C.c_int64, c_dp, c_ip, c_ip, c_dp, c_ip, C.c_int64, c_dp, C.c_int32, c_dp,
-                                        c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, C.POINTER(C.c_int32), c_dp, c_dp]),
     "stm_points_functionals_set": (C.c_int, [H, C.c_int64, c_ip, c_ip, c_dp]),
-    "stm_mcmc_functionals": (C.c_int, [C.POINTER(StProblem), C.POINTER(StOptions), c_dp, c_dp, C.c_int, c_dp, C.c_double, c_dp,
-                                       C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(StmFlags), c_dp, c_dp, c_dp, c_dp, c_dp,
-                                       c_dp, c_dp, C.c_int64, c_dp, c_ip, c_ip, c_dp, c_ip, C.c_int64, c_dp, C.c_int32, c_dp,
-                                       c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, C.POINTER(C.c_int32), c_dp, c_dp,
-                                       C.POINTER(StmFunctionals)]),
     "stm_points_score_set": (C.c_int, [H, c_dp]),
+    "stm_rows_score_set": (C.c_int, [H, c_dp]),
+    "stm_mcmc_fit": (C.c_int, [C.POINTER(StmFit)]),
+    "stm_mcmc_chains_last_error": (C.c_char_p, []),
+    "spamtree_mv_mcmc_c": (C.c_int, _run),
+    "stm_mcmc_points": (C.c_int, _run + [t for name, t in StmNewPoints._fields_ if name not in JOINT_ONLY]),
+    "stm_mcmc_criteria": (C.c_int, _run + [_parts["criteria"]]),
+    "stm_mcmc_loo": (C.c_int, _run + [_parts["criteria"], _parts["loo"]]),
 })
-SIGNATURES["stm_mcmc_scored"] = (C.c_int, SIGNATURES["stm_mcmc_functionals"][1] + [C.POINTER(StmScores)])
-
-
-
-class StmDiagnostics(C.Structure):   # include/spamtree_fit.h, stm_diagnostics
-    _fields_ = [("max_lag", C.c_int32), ("want_rows", C.c_int32), ("rows_w", StSeriesDiag), ("rows_yhat", StSeriesDiag),
-                ("new_w", StSeriesDiag), ("new_yhat", StSeriesDiag), ("fun_w", StSeriesDiag), ("fun_yhat", StSeriesDiag)]
-
-
-SIGNATURES["stm_mcmc_diagnosed"] = (C.c_int, SIGNATURES["stm_mcmc_scored"][1] + [C.POINTER(StmDiagnostics)])
-
-
-
-class StmExcursions(C.Structure):    # include/spamtree_fit.h, stm_excursions
-    _fields_ = [("want_rows", C.c_int32), ("rows_spec", StExcursionSpec), ("new_spec", StExcursionSpec), ("fun_spec", StExcursionSpec),
-                ("rows_w", StExcursionOut), ("rows_yhat", StExcursionOut), ("new_w", StExcursionOut), ("new_yhat", StExcursionOut),
-                ("fun_w", StExcursionOut), ("fun_yhat", StExcursionOut)]
-
-
-SIGNATURES["stm_mcmc_excursions"] = (C.c_int, SIGNATURES["stm_mcmc_diagnosed"][1] + [C.POINTER(StmExcursions)])
-
-
-class StmRankDiagnostics(C.Structure):    # include/spamtree_fit.h, stm_rank_diagnostics
-    _fields_ = [("want_rows", C.c_int32), ("rows_spec", StRankSpec), ("new_spec", StRankSpec), ("fun_spec", StRankSpec),
-                ("rows_w", StRankOut), ("rows_yhat", StRankOut), ("new_w", StRankOut), ("new_yhat", StRankOut),
-                ("fun_w", StRankOut), ("fun_yhat", StRankOut)]
-
-
-SIGNATURES["stm_mcmc_ranked"] = (C.c_int, SIGNATURES["stm_mcmc_excursions"][1] + [C.POINTER(StmRankDiagnostics)])
-
-
-class StmChains(C.Structure):             # include/spamtree_fit.h, stm_chains
-    _fields_ = [("n_chains", C.c_int32), ("seeds", C.POINTER(C.c_uint64)), ("theta0", c_dp), ("paramsd", c_dp), ("chain_time", c_dp)]
-
-
-SIGNATURES["stm_mcmc_chains"] = (C.c_int, SIGNATURES["stm_mcmc_ranked"][1] + [C.POINTER(StmChains)])
-SIGNATURES["stm_mcmc_chains_last_error"] = (C.c_char_p, [])
-
-SIGNATURES["stm_rows_score_set"] = (C.c_int, [H, c_dp])
-SIGNATURES["stm_mcmc_criteria"] = (C.c_int, SIGNATURES["spamtree_mv_mcmc_c"][1] + [C.POINTER(StmCriteria)])
-SIGNATURES["stm_mcmc_loo"] = (C.c_int, SIGNATURES["stm_mcmc_criteria"][1] + [C.POINTER(StmLoo)])
+# stm_mcmc_points_joint and then one more part each: fun, scores, diag, exc, rk, ch
+for _i, _name in enumerate(("points_joint", "functionals", "scored", "diagnosed", "excursions", "ranked", "chains")):
+    SIGNATURES["stm_mcmc_" + _name] = (C.c_int, _run + _points + [t for _, t in StmFit._fields_[2:2 + _i]])
 
 # include/spamtree_tree.h (device parts of the tree builder)
 c_i32p = C.POINTER(C.c_int32)

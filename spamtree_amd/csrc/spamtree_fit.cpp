@@ -460,167 +460,15 @@ extern "C" int stm_rows_score_set(stm_chain c, const double *y_holdout) {
   return ST_OK;
 }
 
+// ---- the whole fit: one request (include/spamtree_fit.h, stm_fit) ------------------------------------------------------------------
 namespace {
-struct FitPoints {   // the point set of stm_mcmc_points and where its per-draw outputs go (n_new x keep, any may be NULL)
-  int64_t n;
-  double *w, *cond_mean, *cond_var, *yhat;
-  double *cond_cov;     // joint sets: packed length x keep, or NULL
-  int64_t cov_len;      // the packed length of st_points_joint_layout
-  const stm_functionals *fun;   // functionals of the set and where their per-draw outputs go (n_fun x keep), or NULL
-};
-}  // namespace
+bool any_out(const st_series_diag &d) { return d.ess || d.mcse || d.sd || d.rhat || d.lags; }
 
-// The whole of spamtree_mv_mcmc (spamtree_fit.cpp:5-430), on a created chain.  With pts, every saved iteration also predicts at the
-// point set once tausq and beta are drawn: the saved theta's factor in slot 0, the saved w, beta and tausq; draw counter = saved
-// index, Philox streams 6 / 7 only, so the chain itself is the same draw for draw.  With crit, every saved iteration also updates
-// the criteria over the fit's own rows (st_rows_score_accumulate; with loo also st_rows_loo_accumulate, right after it) and, when their CRPS is wanted, stores the iteration's yhat on
-// the device (st_summary_accumulate: stream 5 with the iteration's counter, what st_yhat draws).  With store_rows every saved
-// iteration makes that st_summary_accumulate call (the caller has reserved the room): the stores the diagnostics read.
-static int run_fit(stm_chain c, int mcmc_keep, int mcmc_burn, int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc,
-                   double *yhat_mcmc, double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
-                   const FitPoints *pts, const stm_criteria *crit = nullptr, bool store_rows = false, int saved0 = 0, int keep_total = 0,
-                   bool loo = false) {
-  // saved0, keep_total: this is one chain of stm_mcmc_chains -- its saved draw s goes to column saved0 + s of per-draw outputs that
-  // have keep_total columns.  Every Philox counter stays the chain's own: the iteration m, and s for the point draws.
-  if (keep_total == 0) keep_total = mcmc_keep;
-  int rc = 0;
-  const int sample_predicts = flags ? flags->sample_predicts : 1;
-  const auto t0 = std::chrono::steady_clock::now();
-  const long long mcmc = (long long)mcmc_thin * mcmc_keep + mcmc_burn;
-  std::vector<double> predict_param = c->param;
-  int msaved = 0;
-  const int p = c->p, q = c->q, k = c->k;
-  const long long n = c->n_all;
-  for (long long m = 0; m < mcmc && rc == 0; ++m) {
-    const long long mx = m - mcmc_burn;
-    const bool saving = mx >= 0 && (mx % mcmc_thin == 0);
-    rc = step_w_theta(c, !(saving && sample_predicts && c->sample_w));
-    if (rc) break;
-    if (saving && sample_predicts && c->sample_w) {                    // :300-306
-      int need_update = 0;
-      for (int j = 0; j < k; ++j) need_update += std::fabs(c->param[j] - predict_param[j]) > 1e-05;
-      rc = st_predict(c->h, need_update);
-      if (rc) break;
-      predict_param = c->param;
-    }
-    rc = step_tausq_beta(c);
-    if (rc) break;
-    if (saving && msaved < mcmc_keep) {                                 // :376-389
-      const size_t col_s = (size_t)saved0 + msaved;   // the draw's column in the per-draw outputs
-      if (tausq_mcmc) for (int j = 0; j < q; ++j) tausq_mcmc[col_s * q + j] = 1.0 / c->tausq_inv[j];
-      if (beta_mcmc) for (int j = 0; j < q; ++j) for (int i = 0; i < p; ++i)
-        beta_mcmc[(size_t)j * p * keep_total + col_s * p + i] = c->Bcoeff[(size_t)j * p + i];
-      if (theta_mcmc) std::memcpy(theta_mcmc + col_s * k, c->param.data(), k * sizeof(double));
-      if (w_mcmc) rc = st_get_w(c->h, w_mcmc + col_s * n);
-      if (!rc && yhat_mcmc) rc = st_yhat(c->h, nullptr, seed, (uint32_t)m, yhat_mcmc + col_s * n);
-      if (!rc && pts) {
-        const size_t o = col_s * pts->n;
-        auto col = [&](double *a) { return a ? a + o : nullptr; };
-        if (pts->cond_cov) {   // cond_var = max(diag, 0), from the packed blocks below
-          rc = st_points_accumulate_joint(c->h, seed, (uint32_t)msaved, col(pts->w), col(pts->cond_mean),
-                                          pts->cond_cov + col_s * pts->cov_len, nullptr, col(pts->yhat));
-        } else {
-          rc = st_points_accumulate(c->h, seed, (uint32_t)msaved, col(pts->w), col(pts->cond_mean), col(pts->cond_var), col(pts->yhat));
-        }
-        if (!rc && pts->fun && (pts->fun->fun_w || pts->fun->fun_cond_mean || pts->fun->fun_cond_var || pts->fun->fun_yhat)) {
-          const size_t of = col_s * pts->fun->n_fun;
-          auto fcol = [&](double *a) { return a ? a + of : nullptr; };
-          rc = st_points_functionals_last(c->h, fcol(pts->fun->fun_w), fcol(pts->fun->fun_cond_mean), fcol(pts->fun->fun_cond_var),
-                                          fcol(pts->fun->fun_yhat));
-        }
-        if (rc) c->err = st_last_error(c->h);
-      }
-      if (!rc && crit) {
-        rc = st_rows_score_accumulate(c->h);
-        if (!rc && crit->want_crps && crit->y_holdout) rc = st_summary_accumulate(c->h, seed, (uint32_t)m);
-        if (rc) c->err = st_last_error(c->h);
-      }
-      if (!rc && loo) {          // leave-one-out with w_i integrated out: reads w, XB, tausq_inv and slot 0, draws nothing
-        rc = st_rows_loo_accumulate(c->h);
-        if (rc) c->err = st_last_error(c->h);
-      }
-      if (!rc && store_rows) {   // the diagnostics' draws of w and yhat (stream 5, the iteration's counter: st_yhat's yhat)
-        rc = st_summary_accumulate(c->h, seed, (uint32_t)m);
-        if (rc) c->err = st_last_error(c->h);
-      }
-      ++msaved;
-    }
-  }
-  if (rc == 0) {
-    if (paramsd) std::memcpy(paramsd, c->am.paramsd.data(), (size_t)k * k * sizeof(double));
-    if (mcmc_time) *mcmc_time = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  }
-  return rc;
-}
-
-// beta_mcmc p x keep x q, tausq_mcmc q x keep, theta_mcmc k x keep, w_mcmc / yhat_mcmc n_all x keep (may be NULL).
-extern "C" int spamtree_mv_mcmc_c(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
-                                  int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
-                                  int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
-                                  double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time) {
-  stm_chain c = nullptr;
-  int rc = stm_create(pb, opt, set_unif_bounds, mcmcsd, theta, ntheta, beta, tausq, seed, flags, &c);
-  if (rc == 0) rc = stm_init(c);
-  if (rc != 0) { stm_destroy(c); return rc; }
-  rc = run_fit(c, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc, yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time,
-               nullptr);
-  stm_destroy(c);
-  return rc;
-}
-
-extern "C" int stm_mcmc_points(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
-                                         int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
-                                         int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
-                                         double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
-                                         int64_t n_new, const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new,
-                                         const double *X_new, int64_t keep_draws, const double *quantiles, int32_t n_quantiles,
-                                         double *new_w, double *new_cond_mean, double *new_cond_var, double *new_yhat, double *new_mean,
-                                         double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q, double *new_yhat_q,
-                                         int32_t *new_route) {
-  return stm_mcmc_points_joint(pb, opt, set_unif_bounds, theta, ntheta, beta, tausq, mcmcsd, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc,
-                               yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time, n_new, coords_new, mv_new, anchor_new, X_new,
-                               nullptr, keep_draws, quantiles, n_quantiles, new_w, new_cond_mean, new_cond_var, new_yhat, new_mean, new_var,
-                               new_w_mean, new_yhat_mean, new_w_q, new_yhat_q, new_route, nullptr, nullptr);
-}
-
-extern "C" int stm_mcmc_points_joint(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
-                                     int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
-                                     int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
-                                     double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
-                                     int64_t n_new, const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new,
-                                     const double *X_new, const int64_t *joint_id_new, int64_t keep_draws, const double *quantiles,
-                                     int32_t n_quantiles, double *new_w, double *new_cond_mean, double *new_cond_var, double *new_yhat,
-                                     double *new_mean, double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q,
-                                     double *new_yhat_q, int32_t *new_route, double *new_cond_cov, double *new_cov) {
-  return stm_mcmc_functionals(pb, opt, set_unif_bounds, theta, ntheta, beta, tausq, mcmcsd, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc,
-                              yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time, n_new, coords_new, mv_new, anchor_new, X_new,
-                              joint_id_new, keep_draws, quantiles, n_quantiles, new_w, new_cond_mean, new_cond_var, new_yhat, new_mean, new_var,
-                              new_w_mean, new_yhat_mean, new_w_q, new_yhat_q, new_route, new_cond_cov, new_cov, nullptr);
-}
-
-extern "C" int stm_mcmc_functionals(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
-                                    int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
-                                    int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
-                                    double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
-                                    int64_t n_new, const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new,
-                                    const double *X_new, const int64_t *joint_id_new, int64_t keep_draws, const double *quantiles,
-                                    int32_t n_quantiles, double *new_w, double *new_cond_mean, double *new_cond_var, double *new_yhat,
-                                    double *new_mean, double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q,
-                                    double *new_yhat_q, int32_t *new_route, double *new_cond_cov, double *new_cov,
-                                    const stm_functionals *fun) {
-  return stm_mcmc_scored(pb, opt, set_unif_bounds, theta, ntheta, beta, tausq, mcmcsd, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc,
-                         yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time, n_new, coords_new, mv_new, anchor_new, X_new,
-                         joint_id_new, keep_draws, quantiles, n_quantiles, new_w, new_cond_mean, new_cond_var, new_yhat, new_mean, new_var,
-                         new_w_mean, new_yhat_mean, new_w_q, new_yhat_q, new_route, new_cond_cov, new_cov, fun, nullptr);
-}
-
-static bool diag_any(const st_series_diag &d) { return d.ess || d.mcse || d.sd || d.rhat || d.lags; }
-
-static bool exc_thr_any(const st_excursion_out &o) { return o.count || o.prob || o.excur || o.joint_all; }
-static bool exc_band_any(const st_excursion_out &o) { return o.mean || o.sd || o.maxdev || o.n_flat; }
-static bool exc_any(const st_excursion_out &o) { return exc_thr_any(o) || exc_band_any(o) || o.n_draws; }
+bool exc_thr_any(const st_excursion_out &o) { return o.count || o.prob || o.excur || o.joint_all; }
+bool exc_band_any(const st_excursion_out &o) { return o.mean || o.sd || o.maxdev || o.n_flat; }
+bool any_out(const st_excursion_out &o) { return exc_thr_any(o) || exc_band_any(o) || o.n_draws; }
 // what st_*_excursions would refuse of a spec after the chain, found before it: nvals thresholds per t, keep draws to be stored
-static int exc_spec_refused(const st_excursion_spec &sp, int64_t nvals, const st_excursion_out &w, const st_excursion_out &y, int keep) {
+int exc_spec_refused(const st_excursion_spec &sp, int64_t nvals, const st_excursion_out &w, const st_excursion_out &y, int keep) {
   const bool band = sp.want_band || exc_band_any(w) || exc_band_any(y);
   if (!sp.thr && !band) return ST_ERR_USAGE;
   if (sp.thr) {
@@ -632,11 +480,11 @@ static int exc_spec_refused(const st_excursion_spec &sp, int64_t nvals, const st
   return 0;
 }
 
-static bool rank_any(const st_rank_out &o) {
+bool any_out(const st_rank_out &o) {
   return o.rhat_rank || o.rhat_bulk || o.rhat_fold || o.ess_bulk || o.ess_tail || o.lags_bulk || o.ess_q || o.ess_exc || o.mcse_prob || o.prob;
 }
 // what st_*_rank_diagnostics would refuse of a spec after the chain, found before it: nvals thresholds per t
-static int rank_spec_refused(const st_rank_spec &sp, int64_t nvals, const st_rank_out &w, const st_rank_out &y) {
+int rank_spec_refused(const st_rank_spec &sp, int64_t nvals, const st_rank_out &w, const st_rank_out &y) {
   if (sp.max_lag < 0 || sp.n_prob < 0 || sp.n_prob > ST_RANK_MAX_PROBS || sp.n_thr < 0 || sp.n_thr > ST_EXC_MAX_THRESHOLDS) return ST_ERR_USAGE;
   if ((sp.n_prob > 0 && !sp.prob) || (sp.n_thr > 0 && !sp.thr)) return ST_ERR_USAGE;
   for (int k = 0; k < sp.n_prob; ++k) if (!(sp.prob[k] > 0.0 && sp.prob[k] < 1.0)) return ST_ERR_USAGE;
@@ -647,315 +495,382 @@ static int rank_spec_refused(const st_rank_spec &sp, int64_t nvals, const st_ran
   return 0;
 }
 
-// What stm_mcmc_chains refuses of its chains before a chain exists to carry the text: the calling thread's last such refusal
-static thread_local std::string g_chains_error;
-static int chains_refuse(int code, const std::string &msg) { g_chains_error = msg; return code; }
+// Which stores one summary of the stored draws (stm_diagnostics, stm_excursions, stm_rank_diagnostics: the same six members) reads,
+// after the four refusals the three share, in their order
+struct Wanted {
+  bool rows = false, pts = false, fun = false;
+  bool any() const { return rows || pts || fun; }
+};
+template <class Part>
+int wanted_of(const Part *t, bool have_pts, const stm_functionals *fun, const double *X_new, Wanted *out) {
+  if (!t) return 0;
+  Wanted w;
+  w.rows = any_out(t->rows_w) || any_out(t->rows_yhat);
+  w.pts = any_out(t->new_w) || any_out(t->new_yhat);
+  w.fun = any_out(t->fun_w) || any_out(t->fun_yhat);
+  if (w.rows && !t->want_rows) return ST_ERR_USAGE;
+  if (w.pts && !have_pts) return ST_ERR_USAGE;
+  if (w.fun && !fun) return ST_ERR_USAGE;
+  if ((any_out(t->new_yhat) || any_out(t->fun_yhat)) && !X_new) return ST_ERR_USAGE;
+  *out = w;
+  return 0;
+}
+
+// What stm_mcmc_fit refuses before a chain exists to carry the text: the calling thread's last such refusal
+thread_local std::string g_chains_error;
+int chains_refuse(int code, const std::string &msg) { g_chains_error = msg; return code; }
+
+struct FitPlan {           // a request as stm_mcmc_fit runs it
+  stm_fit f;               // the request; a part that does not apply is NULL: fun of no functional, scores without y_new, pts of a plain chain
+  stm_new_points p;        // what f.pts points to: keep_draws raised to the stored draws, new_cond_cov where the packed blocks go
+  bool store_rows = false; // diag, exc or rk read the rows' stores: st_summary_accumulate on every saved iteration
+  int64_t cov_len = 0;     // the packed length of st_points_joint_layout
+};
+struct FitChain {          // one chain of a request: its saved draw s goes to column col0 + s of per-draw outputs with ncols columns
+  uint64_t seed;
+  int col0, ncols;
+};
+}  // namespace
+
 extern "C" const char *stm_mcmc_chains_last_error(void) { return g_chains_error.c_str(); }
 
-// fun NULL: stm_mcmc_points_joint itself; scores NULL: stm_mcmc_functionals itself; diag NULL: stm_mcmc_scored itself; exc NULL:
-// stm_mcmc_diagnosed itself; rk NULL: stm_mcmc_excursions itself; ch NULL: stm_mcmc_ranked itself
-extern "C" int stm_mcmc_chains(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
-                                    int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
-                                    int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
-                                    double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
-                                    int64_t n_new, const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new,
-                                    const double *X_new, const int64_t *joint_id_new, int64_t keep_draws, const double *quantiles,
-                                    int32_t n_quantiles, double *new_w, double *new_cond_mean, double *new_cond_var, double *new_yhat,
-                                    double *new_mean, double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q,
-                                    double *new_yhat_q, int32_t *new_route, double *new_cond_cov, double *new_cov,
-                                    const stm_functionals *fun, const stm_scores *scores, const stm_diagnostics *diag,
-                                    const stm_excursions *exc, const stm_rank_diagnostics *rk, const stm_chains *ch) {
-  if (fun && fun->n_fun <= 0) fun = nullptr;
+// The whole of spamtree_mv_mcmc (spamtree_fit.cpp:5-430) for one chain of a request, on a created chain.  Every Philox counter is the
+// chain's own: the iteration m for the rows (st_yhat and st_summary_accumulate draw the same stream 5 values), the saved index for
+// the points (streams 6 / 7 only), so the chain itself is the same draw for draw whatever parts the request has.
+static int run_fit(stm_chain c, const FitPlan &pl, const FitChain &ch, double *seconds) {
+  const stm_run &r = pl.f.run;
+  const stm_new_points *pts = pl.f.pts;
+  const stm_functionals *fun = pl.f.fun;
+  const stm_criteria *crit = pl.f.criteria;
+  int rc = 0;
+  const int sample_predicts = r.flags ? r.flags->sample_predicts : 1;
+  const auto t0 = std::chrono::steady_clock::now();
+  const long long mcmc = (long long)r.mcmc_thin * r.mcmc_keep + r.mcmc_burn;
+  std::vector<double> predict_param = c->param;
+  int msaved = 0;
+  const int p = c->p, q = c->q, k = c->k;
+  const long long n = c->n_all;
+  for (long long m = 0; m < mcmc && rc == 0; ++m) {
+    const long long mx = m - r.mcmc_burn;
+    const bool saving = mx >= 0 && (mx % r.mcmc_thin == 0);
+    rc = step_w_theta(c, !(saving && sample_predicts && c->sample_w));
+    if (rc) break;
+    if (saving && sample_predicts && c->sample_w) {                    // :300-306
+      int need_update = 0;
+      for (int j = 0; j < k; ++j) need_update += std::fabs(c->param[j] - predict_param[j]) > 1e-05;
+      rc = st_predict(c->h, need_update);
+      if (rc) break;
+      predict_param = c->param;
+    }
+    rc = step_tausq_beta(c);
+    if (rc) break;
+    if (saving && msaved < r.mcmc_keep) {                               // :376-389
+      const size_t col_s = (size_t)ch.col0 + msaved;   // the draw's column in the per-draw outputs
+      if (r.tausq_mcmc) for (int j = 0; j < q; ++j) r.tausq_mcmc[col_s * q + j] = 1.0 / c->tausq_inv[j];
+      if (r.beta_mcmc) for (int j = 0; j < q; ++j) for (int i = 0; i < p; ++i)
+        r.beta_mcmc[(size_t)j * p * ch.ncols + col_s * p + i] = c->Bcoeff[(size_t)j * p + i];
+      if (r.theta_mcmc) std::memcpy(r.theta_mcmc + col_s * k, c->param.data(), k * sizeof(double));
+      if (r.w_mcmc) rc = st_get_w(c->h, r.w_mcmc + col_s * n);
+      if (!rc && r.yhat_mcmc) rc = st_yhat(c->h, nullptr, ch.seed, (uint32_t)m, r.yhat_mcmc + col_s * n);
+      if (!rc && pts) {   // the saved theta's factor in slot 0, the saved w, beta and tausq
+        const size_t o = col_s * pts->n_new;
+        auto col = [&](double *a) { return a ? a + o : nullptr; };
+        if (pts->new_cond_cov) {   // cond_var = max(diag, 0), from the packed blocks after the last chain
+          rc = st_points_accumulate_joint(c->h, ch.seed, (uint32_t)msaved, col(pts->new_w), col(pts->new_cond_mean),
+                                          pts->new_cond_cov + col_s * pl.cov_len, nullptr, col(pts->new_yhat));
+        } else {
+          rc = st_points_accumulate(c->h, ch.seed, (uint32_t)msaved, col(pts->new_w), col(pts->new_cond_mean), col(pts->new_cond_var),
+                                    col(pts->new_yhat));
+        }
+        if (!rc && fun && (fun->fun_w || fun->fun_cond_mean || fun->fun_cond_var || fun->fun_yhat)) {
+          const size_t of = col_s * fun->n_fun;
+          auto fcol = [&](double *a) { return a ? a + of : nullptr; };
+          rc = st_points_functionals_last(c->h, fcol(fun->fun_w), fcol(fun->fun_cond_mean), fcol(fun->fun_cond_var), fcol(fun->fun_yhat));
+        }
+      }
+      if (!rc && crit) {         // the criteria over the fit's own rows and, when their CRPS is wanted, the iteration's yhat
+        rc = st_rows_score_accumulate(c->h);
+        if (!rc && crit->want_crps && crit->y_holdout) rc = st_summary_accumulate(c->h, ch.seed, (uint32_t)m);
+      }
+      if (!rc && pl.f.loo) rc = st_rows_loo_accumulate(c->h);   // reads w, XB, tausq_inv and slot 0, draws nothing
+      if (!rc && pl.store_rows) rc = st_summary_accumulate(c->h, ch.seed, (uint32_t)m);   // the draws diag, exc and rk read
+      if (rc) c->err = st_last_error(c->h);
+      ++msaved;
+    }
+  }
+  if (rc == 0) {
+    if (r.paramsd) std::memcpy(r.paramsd, c->am.paramsd.data(), (size_t)k * k * sizeof(double));
+    *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return rc;
+}
+
+extern "C" int stm_mcmc_fit(const stm_fit *fit) {
+  g_chains_error.clear();
+  if (!fit) return ST_ERR_USAGE;
+  FitPlan pl;
+  pl.f = *fit;
+  stm_fit &f = pl.f;
+  stm_new_points &p = pl.p;
+  const stm_run &r = f.run;
+  if ((f.criteria || f.loo) && (f.pts || f.fun || f.scores || f.diag || f.exc || f.rk || f.ch))
+    return chains_refuse(ST_ERR_USAGE, "stm_mcmc_fit: criteria and loo do not go with pts, fun, scores, diag, exc, rk or ch in one request");
+  if (f.fun && f.fun->n_fun <= 0) f.fun = nullptr;
+  p = f.pts ? *f.pts : stm_new_points{};
+  const stm_functionals *const fun = f.fun;
+  const stm_diagnostics *const diag = f.diag;
+  const stm_excursions *const exc = f.exc;
+  const stm_rank_diagnostics *const rk = f.rk;
+  const stm_chains *const ch = f.ch;
+  const int mcmc_keep = r.mcmc_keep, ntheta = r.ntheta;
   // M chains one after another on one handle; chain c's saved draws are columns c keep .. (c + 1) keep - 1 of every per-draw output
   // and of the stores
   const int M = ch ? ch->n_chains : 1;
   const std::string W = "stm_mcmc_chains: ";
-  g_chains_error.clear();
   if (ch && (M < 1 || M > ST_DIAG_MAX_CHAINS))
     return chains_refuse(ST_ERR_USAGE, W + "n_chains = " + std::to_string(M) + " must lie in 1 .. " + std::to_string(ST_DIAG_MAX_CHAINS));
   if (ch && !ch->seeds) return chains_refuse(ST_ERR_USAGE, W + "seeds is NULL: one seed per chain (" + std::to_string(M) + ")");
   if (M > 1 && mcmc_keep < 1)
     return chains_refuse(ST_ERR_USAGE, W + "mcmc_keep = " + std::to_string(mcmc_keep) + ": " + std::to_string(M) + " chains need at least one saved draw each");
-  if (M > 1 && !theta) return chains_refuse(ST_ERR_USAGE, W + "theta is NULL");
-  if (M > 1 && opt && opt->world > 1)
-    return chains_refuse(ST_ERR_UNSUPPORTED, W + "world = " + std::to_string(opt->world) + ": several chains run on one GPU");
+  if (M > 1 && !r.theta) return chains_refuse(ST_ERR_USAGE, W + "theta is NULL");
+  if (M > 1 && r.opt && r.opt->world > 1)
+    return chains_refuse(ST_ERR_UNSUPPORTED, W + "world = " + std::to_string(r.opt->world) + ": several chains run on one GPU");
   const long long total = (long long)M * mcmc_keep;   // the stored draws
   const auto too_many = [&]() {
     return chains_refuse(ST_ERR_UNSUPPORTED, W + std::to_string(M) + " chains x mcmc_keep = " + std::to_string(mcmc_keep) + " are " + std::to_string(total) +
                                                  " stored draws, at most 16384");
   };
-  // the plain chain: no point argument, and either a summary of the rows (with diag only: stm_mcmc_scored handles an empty set as
-  // before) or several chains
-  const bool plain = (diag || exc || rk || M > 1) && n_new == 0 && !coords_new && !mv_new && !anchor_new;
-  const bool d_rows = diag && diag->want_rows && (diag_any(diag->rows_w) || diag_any(diag->rows_yhat));
-  const bool d_new = diag && !plain && (diag_any(diag->new_w) || diag_any(diag->new_yhat));
-  const bool d_fun = diag && fun && (diag_any(diag->fun_w) || diag_any(diag->fun_yhat));
-  if (diag && diag->max_lag < 0) return ST_ERR_USAGE;
-  if (diag && ((diag_any(diag->rows_w) || diag_any(diag->rows_yhat)) && !diag->want_rows)) return ST_ERR_USAGE;
-  if (diag && plain && (diag_any(diag->new_w) || diag_any(diag->new_yhat))) return ST_ERR_USAGE;
-  if (diag && !fun && (diag_any(diag->fun_w) || diag_any(diag->fun_yhat))) return ST_ERR_USAGE;
-  if ((d_new && diag_any(diag->new_yhat) && !X_new) || (d_fun && diag_any(diag->fun_yhat) && !X_new)) return ST_ERR_USAGE;
-  if (d_rows || d_new || d_fun) {
-    if (total > 16384) return too_many();   // the stores' limit
-    if (mcmc_keep < ST_DIAG_MIN_DRAWS) return ST_ERR_USAGE;
-    if (d_new || d_fun) keep_draws = std::max<int64_t>(keep_draws, total);
-  }
-  const bool e_rows = exc && exc->want_rows && (exc_any(exc->rows_w) || exc_any(exc->rows_yhat));
-  const bool e_new = exc && !plain && (exc_any(exc->new_w) || exc_any(exc->new_yhat));
-  const bool e_fun = exc && fun && (exc_any(exc->fun_w) || exc_any(exc->fun_yhat));
-  if (exc && !exc->want_rows && (exc_any(exc->rows_w) || exc_any(exc->rows_yhat))) return ST_ERR_USAGE;
-  if (exc && plain && (exc_any(exc->new_w) || exc_any(exc->new_yhat))) return ST_ERR_USAGE;
-  if (exc && !fun && (exc_any(exc->fun_w) || exc_any(exc->fun_yhat))) return ST_ERR_USAGE;
-  if ((e_new && exc_any(exc->new_yhat) && !X_new) || (e_fun && exc_any(exc->fun_yhat) && !X_new)) return ST_ERR_USAGE;
-  if (e_rows || e_new || e_fun) {
-    if (total > 16384) return too_many();   // the stores' limit
-    if (e_rows) if (const int r = exc_spec_refused(exc->rows_spec, pb->q, exc->rows_w, exc->rows_yhat, (int)total)) return r;
-    if (e_new) if (const int r = exc_spec_refused(exc->new_spec, pb->q, exc->new_w, exc->new_yhat, (int)total)) return r;
-    if (e_fun) if (const int r = exc_spec_refused(exc->fun_spec, fun->n_fun, exc->fun_w, exc->fun_yhat, (int)total)) return r;
-    if (e_new || e_fun) keep_draws = std::max<int64_t>(keep_draws, total);
-  }
-  const bool r_rows = rk && rk->want_rows && (rank_any(rk->rows_w) || rank_any(rk->rows_yhat));
-  const bool r_new = rk && !plain && (rank_any(rk->new_w) || rank_any(rk->new_yhat));
-  const bool r_fun = rk && fun && (rank_any(rk->fun_w) || rank_any(rk->fun_yhat));
-  if (rk && !rk->want_rows && (rank_any(rk->rows_w) || rank_any(rk->rows_yhat))) return ST_ERR_USAGE;
-  if (rk && plain && (rank_any(rk->new_w) || rank_any(rk->new_yhat))) return ST_ERR_USAGE;
-  if (rk && !fun && (rank_any(rk->fun_w) || rank_any(rk->fun_yhat))) return ST_ERR_USAGE;
-  if ((r_new && rank_any(rk->new_yhat) && !X_new) || (r_fun && rank_any(rk->fun_yhat) && !X_new)) return ST_ERR_USAGE;
-  if (r_rows || r_new || r_fun) {
-    if (total > 16384) return too_many();   // the stores' limit
-    if (mcmc_keep < ST_DIAG_MIN_DRAWS) return ST_ERR_USAGE;
-    if (r_rows) if (const int r = rank_spec_refused(rk->rows_spec, pb->q, rk->rows_w, rk->rows_yhat)) return r;
-    if (r_new) if (const int r = rank_spec_refused(rk->new_spec, pb->q, rk->new_w, rk->new_yhat)) return r;
-    if (r_fun) if (const int r = rank_spec_refused(rk->fun_spec, fun->n_fun, rk->fun_w, rk->fun_yhat)) return r;
-    if (r_new || r_fun) keep_draws = std::max<int64_t>(keep_draws, total);
-  }
-  const bool store_rows = d_rows || e_rows || r_rows;   // one reservation serves all three
-  if (M > 1 && keep_draws > 0) {   // a point store that is reserved at all holds every chain's draws
+  // the plain chain: no point argument, and either a summary of the rows (an empty set without one reaches stm_points_set_joint)
+  // or several chains
+  const bool plain = (diag || exc || rk || M > 1) && p.n_new == 0 && !p.coords_new && !p.mv_new && !p.anchor_new;
+  f.pts = (f.pts && !plain) ? &p : nullptr;
+  const bool have_pts = f.pts != nullptr;
+  // diag, exc, rk: the shared refusals, the stores' limit, the minimum of draws (exc: per spec, below), the spec; a part that reads
+  // the point set's stores raises keep_draws to the stored draws
+  int rc;
+  Wanted d, e, k;
+  const auto stored = [&](const Wanted &w, int min_draws) {
     if (total > 16384) return too_many();
-    keep_draws = total;
+    if (mcmc_keep < min_draws) return (int)ST_ERR_USAGE;
+    if (w.pts || w.fun) p.keep_draws = std::max<int64_t>(p.keep_draws, total);
+    return 0;
+  };
+  if (diag && diag->max_lag < 0) return ST_ERR_USAGE;
+  if ((rc = wanted_of(diag, have_pts, fun, p.X_new, &d)) != 0) return rc;
+  if (d.any() && (rc = stored(d, ST_DIAG_MIN_DRAWS)) != 0) return rc;
+  if ((rc = wanted_of(exc, have_pts, fun, p.X_new, &e)) != 0) return rc;
+  if (e.any()) {
+    if ((rc = stored(e, 0)) != 0) return rc;
+    if (e.rows && (rc = exc_spec_refused(exc->rows_spec, r.pb->q, exc->rows_w, exc->rows_yhat, (int)total)) != 0) return rc;
+    if (e.pts && (rc = exc_spec_refused(exc->new_spec, r.pb->q, exc->new_w, exc->new_yhat, (int)total)) != 0) return rc;
+    if (e.fun && (rc = exc_spec_refused(exc->fun_spec, fun->n_fun, exc->fun_w, exc->fun_yhat, (int)total)) != 0) return rc;
   }
-  if (plain && (fun || (scores && scores->y_new) || joint_id_new || X_new || n_quantiles != 0)) return ST_ERR_USAGE;
-  if (scores && !scores->y_new) scores = nullptr;
-  if (scores && (!X_new || (scores->lpd_joint && !joint_id_new) || (scores->crps && keep_draws < 1))) return ST_ERR_USAGE;
-  if (fun && (fun->fun_yhat || fun->fun_yhat_mean || fun->fun_yhat_q) && !X_new) return ST_ERR_USAGE;
-  if ((new_cond_cov || new_cov) && !joint_id_new) return ST_ERR_USAGE;
-  if (n_quantiles < 0 || (n_quantiles > 0 && (!quantiles || keep_draws < 1))) return ST_ERR_USAGE;   // a quantile needs stored draws
-  for (int32_t i = 0; i < n_quantiles; ++i) if (!(quantiles[i] >= 0.0 && quantiles[i] <= 1.0)) return ST_ERR_USAGE;
-  if ((new_yhat || new_yhat_mean || new_yhat_q) && !X_new) return ST_ERR_USAGE;
-  const auto chain_seed = [&](int cn) { return ch ? ch->seeds[cn] : seed; };
-  const auto chain_theta = [&](int cn) { return ch && ch->theta0 ? ch->theta0 + (size_t)cn * ntheta : theta; };
+  if ((rc = wanted_of(rk, have_pts, fun, p.X_new, &k)) != 0) return rc;
+  if (k.any()) {
+    if ((rc = stored(k, ST_DIAG_MIN_DRAWS)) != 0) return rc;
+    if (k.rows && (rc = rank_spec_refused(rk->rows_spec, r.pb->q, rk->rows_w, rk->rows_yhat)) != 0) return rc;
+    if (k.pts && (rc = rank_spec_refused(rk->new_spec, r.pb->q, rk->new_w, rk->new_yhat)) != 0) return rc;
+    if (k.fun && (rc = rank_spec_refused(rk->fun_spec, fun->n_fun, rk->fun_w, rk->fun_yhat)) != 0) return rc;
+  }
+  pl.store_rows = d.rows || e.rows || k.rows;   // one reservation serves all three
+  if (M > 1 && p.keep_draws > 0) {   // a point store that is reserved at all holds every chain's draws
+    if (total > 16384) return too_many();
+    p.keep_draws = total;
+  }
+  // the point set, its functionals, scores and quantiles
+  if (!have_pts && (fun || (f.scores && f.scores->y_new) || p.joint_id_new || p.X_new || p.n_quantiles != 0)) return ST_ERR_USAGE;
+  if (f.scores && !f.scores->y_new) f.scores = nullptr;
+  const stm_scores *const scores = f.scores;
+  if (scores && (!p.X_new || (scores->lpd_joint && !p.joint_id_new) || (scores->crps && p.keep_draws < 1))) return ST_ERR_USAGE;
+  if (fun && (fun->fun_yhat || fun->fun_yhat_mean || fun->fun_yhat_q) && !p.X_new) return ST_ERR_USAGE;
+  if ((p.new_cond_cov || p.new_cov) && !p.joint_id_new) return ST_ERR_USAGE;
+  if (p.n_quantiles < 0 || (p.n_quantiles > 0 && (!p.quantiles || p.keep_draws < 1))) return ST_ERR_USAGE;   // a quantile needs stored draws
+  for (int32_t i = 0; i < p.n_quantiles; ++i) if (!(p.quantiles[i] >= 0.0 && p.quantiles[i] <= 1.0)) return ST_ERR_USAGE;
+  if ((p.new_yhat || p.new_yhat_mean || p.new_yhat_q) && !p.X_new) return ST_ERR_USAGE;
+  // the criteria over the fit's own rows
+  const stm_criteria *const cr = f.criteria;
+  const stm_loo *const loo = f.loo;
+  const bool crps = cr && cr->want_crps && cr->y_holdout;
+  if (cr && cr->crps && !crps) return ST_ERR_USAGE;
+  if (crps && mcmc_keep > 16384) return ST_ERR_UNSUPPORTED;   // st_summary_reserve's limit
+  if (cr && cr->y_holdout && r.flags && (!r.flags->sample_predicts || !r.flags->sample_w)) return ST_ERR_USAGE;   // the NA rows' w would be stale
+
+  // the chain and what it is given before its first factorisation: every refusal of these comes before stm_init
+  const auto chain_seed = [&](int cn) { return ch ? ch->seeds[cn] : r.seed; };
+  const auto chain_theta = [&](int cn) { return ch && ch->theta0 ? ch->theta0 + (size_t)cn * ntheta : r.theta; };
   stm_chain c = nullptr;
-  int rc = stm_create(pb, opt, set_unif_bounds, mcmcsd, chain_theta(0), ntheta, beta, tausq, chain_seed(0), flags, &c);
-  if (rc == 0 && !plain) rc = stm_points_set_joint(c, n_new, coords_new, mv_new, anchor_new, X_new, joint_id_new, keep_draws);   // refusals: before any factorisation
-  if (rc == 0 && store_rows) {
+  rc = stm_create(r.pb, r.opt, r.set_unif_bounds, r.mcmcsd, chain_theta(0), ntheta, r.beta, r.tausq, chain_seed(0), r.flags, &c);
+  if (rc == 0 && have_pts)
+    rc = stm_points_set_joint(c, p.n_new, p.coords_new, p.mv_new, p.anchor_new, p.X_new, p.joint_id_new, p.keep_draws);
+  if (rc == 0 && (pl.store_rows || (crps && mcmc_keep > 0))) {
     rc = st_summary_reset(c->h);
     if (rc == 0) rc = st_summary_reserve(c->h, total);
   }
   int64_t nj = 0;
   std::vector<int64_t> joff, jptr, jmem;
-  std::vector<double> cov_scratch;
+  std::vector<double> cov_scratch;   // the packed blocks of every draw when only new_cond_var is wanted of them
   if (rc == 0 && fun) rc = stm_points_functionals_set(c, fun->n_fun, fun->ptr, fun->idx, fun->wt);
   if (rc == 0 && scores) rc = stm_points_score_set(c, scores->y_new);
-  if (rc == 0 && joint_id_new) {
+  if (rc == 0 && p.joint_id_new) {
     rc = st_points_joint_layout(c->h, &nj, nullptr, nullptr, nullptr);
-    joff.resize(nj + 1); jptr.resize(nj + 1); jmem.resize(n_new);
+    joff.resize(nj + 1); jptr.resize(nj + 1); jmem.resize(p.n_new);
     if (rc == 0) rc = st_points_joint_layout(c->h, &nj, joff.data(), jptr.data(), jmem.data());
-    if (rc == 0 && !new_cond_cov && new_cond_var) cov_scratch.resize((size_t)joff[nj] * std::max<long long>(total, 0));
+    if (rc == 0 && !p.new_cond_cov && p.new_cond_var) cov_scratch.resize((size_t)joff[nj] * std::max<long long>(total, 0));
   }
+  if (rc == 0 && cr) rc = stm_rows_score_set(c, cr->y_holdout);
+  if (rc == 0 && loo) rc = st_rows_loo_set(c->h);   // (limited_tree is refused)
   if (rc == 0) rc = stm_init(c);
   if (rc != 0) { stm_destroy(c); return rc; }
-  double *const ccov = !joint_id_new ? nullptr : (new_cond_cov ? new_cond_cov : (cov_scratch.empty() ? nullptr : cov_scratch.data()));
-  const FitPoints pts{n_new, new_w, new_cond_mean, new_cond_var, new_yhat, ccov, joint_id_new ? joff[nj] : 0, fun};
+  double *const new_cond_var = p.new_cond_var;
+  if (p.joint_id_new) {
+    pl.cov_len = joff[nj];
+    if (!p.new_cond_cov && !cov_scratch.empty()) p.new_cond_cov = cov_scratch.data();
+  } else p.new_cond_cov = nullptr;
+  double *const ccov = p.new_cond_cov;
+
   double time_all = 0;
   for (int cn = 0; cn < M && rc == 0; ++cn) {
     if (cn > 0) rc = stm_restart(c, chain_theta(cn), chain_seed(cn));
     double time_c = 0;
-    if (rc == 0)
-      rc = run_fit(c, mcmc_keep, mcmc_burn, mcmc_thin, chain_seed(cn), flags, w_mcmc, yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd,
-                   &time_c, plain ? nullptr : &pts, nullptr, store_rows, cn * mcmc_keep, (int)total);
+    if (rc == 0) rc = run_fit(c, pl, FitChain{chain_seed(cn), cn * mcmc_keep, (int)total}, &time_c);
     if (rc == 0 && ch && ch->paramsd) std::memcpy(ch->paramsd + (size_t)cn * ntheta * ntheta, c->am.paramsd.data(), (size_t)ntheta * ntheta * sizeof(double));
     if (rc == 0 && ch && ch->chain_time) ch->chain_time[cn] = time_c;
     time_all += time_c;
   }
-  if (rc == 0 && mcmc_time) *mcmc_time = time_all;   // (paramsd: the last chain's; every chain's in ch->paramsd)
-  if (plain) {   // the diagnostics and excursions of the rows are all a plain chain can ask for
-    if (rc == 0 && d_rows) rc = st_summary_chain_diagnostics(c->h, M, diag->max_lag, &diag->rows_w, &diag->rows_yhat);
-    if (rc == 0 && e_rows) rc = st_summary_excursions(c->h, &exc->rows_spec, &exc->rows_w, &exc->rows_yhat);
-    if (rc == 0 && r_rows) rc = st_summary_chain_rank_diagnostics(c->h, M, &rk->rows_spec, &rk->rows_w, &rk->rows_yhat);
-    if (rc) c->err = st_last_error(c->h);
-    stm_destroy(c);
-    return rc;
-  }
-  if (rc == 0 && ccov && new_cond_var)
+  if (rc == 0 && r.mcmc_time) *r.mcmc_time = time_all;   // (paramsd: the last chain's; every chain's in ch->paramsd)
+
+  // the read-outs, in the order the header states
+  const bool saved = mcmc_keep > 0;
+  if (rc == 0 && have_pts && ccov && new_cond_var)
     for (long long s = 0; s < total; ++s)
-      for (int64_t k = 0; k < nj; ++k) {
-        const int64_t g = jptr[k + 1] - jptr[k];
-        for (int64_t a = 0; a < g; ++a)
-          new_cond_var[(size_t)s * n_new + jmem[jptr[k] + a]] = std::max(ccov[(size_t)s * joff[nj] + joff[k] + a * (g + 1)], 0.0);
+      for (int64_t g = 0; g < nj; ++g) {
+        const int64_t sz = jptr[g + 1] - jptr[g];
+        for (int64_t a = 0; a < sz; ++a)
+          new_cond_var[(size_t)s * p.n_new + jmem[jptr[g] + a]] = std::max(ccov[(size_t)s * joff[nj] + joff[g] + a * (sz + 1)], 0.0);
       }
-  if (rc == 0 && mcmc_keep > 0 && (new_mean || new_var || new_w_mean || new_yhat_mean))
-    rc = st_points_summary_get(c->h, new_mean, new_var, new_w_mean, new_yhat_mean, nullptr);
-  if (rc == 0 && mcmc_keep > 0 && new_cov) rc = st_points_summary_get_cov(c->h, new_cov);
-  for (int32_t i = 0; rc == 0 && i < n_quantiles && (new_w_q || new_yhat_q); ++i)
-    rc = st_points_summary_quantile(c->h, quantiles[i], new_w_q ? new_w_q + (size_t)i * n_new : nullptr,
-                                    new_yhat_q ? new_yhat_q + (size_t)i * n_new : nullptr);
-  if (rc == 0 && new_route) rc = st_points_info(c->h, new_route, nullptr, nullptr, nullptr);
-  if (rc == 0 && fun && mcmc_keep > 0 && (fun->fun_mean || fun->fun_var || fun->fun_w_mean || fun->fun_yhat_mean))
+  if (rc == 0 && have_pts && saved && (p.new_mean || p.new_var || p.new_w_mean || p.new_yhat_mean))
+    rc = st_points_summary_get(c->h, p.new_mean, p.new_var, p.new_w_mean, p.new_yhat_mean, nullptr);
+  if (rc == 0 && have_pts && saved && p.new_cov) rc = st_points_summary_get_cov(c->h, p.new_cov);
+  for (int32_t i = 0; rc == 0 && have_pts && i < p.n_quantiles && (p.new_w_q || p.new_yhat_q); ++i)
+    rc = st_points_summary_quantile(c->h, p.quantiles[i], p.new_w_q ? p.new_w_q + (size_t)i * p.n_new : nullptr,
+                                    p.new_yhat_q ? p.new_yhat_q + (size_t)i * p.n_new : nullptr);
+  if (rc == 0 && have_pts && p.new_route) rc = st_points_info(c->h, p.new_route, nullptr, nullptr, nullptr);
+  if (rc == 0 && fun && saved && (fun->fun_mean || fun->fun_var || fun->fun_w_mean || fun->fun_yhat_mean))
     rc = st_points_functionals_get(c->h, fun->fun_mean, fun->fun_var, fun->fun_w_mean, fun->fun_yhat_mean, nullptr);
-  for (int32_t i = 0; rc == 0 && fun && i < n_quantiles && (fun->fun_w_q || fun->fun_yhat_q); ++i)
-    rc = st_points_functionals_quantile(c->h, quantiles[i], fun->fun_w_q ? fun->fun_w_q + (size_t)i * fun->n_fun : nullptr,
+  for (int32_t i = 0; rc == 0 && fun && i < p.n_quantiles && (fun->fun_w_q || fun->fun_yhat_q); ++i)
+    rc = st_points_functionals_quantile(c->h, p.quantiles[i], fun->fun_w_q ? fun->fun_w_q + (size_t)i * fun->n_fun : nullptr,
                                         fun->fun_yhat_q ? fun->fun_yhat_q + (size_t)i * fun->n_fun : nullptr);
-  if (rc == 0 && scores && mcmc_keep > 0)
+  if (rc == 0 && scores && saved)
     rc = st_points_score_get(c->h, scores->lpd, scores->pit, scores->crps, scores->lpd_joint, scores->n_scored, scores->n_degenerate);
-  if (rc == 0 && d_rows) rc = st_summary_chain_diagnostics(c->h, M, diag->max_lag, &diag->rows_w, &diag->rows_yhat);
-  if (rc == 0 && d_new)
-    rc = st_points_summary_chain_diagnostics(c->h, M, diag->max_lag, &diag->new_w, diag_any(diag->new_yhat) ? &diag->new_yhat : nullptr);
-  if (rc == 0 && d_fun)
-    rc = st_points_functionals_chain_diagnostics(c->h, M, diag->max_lag, &diag->fun_w, diag_any(diag->fun_yhat) ? &diag->fun_yhat : nullptr);
-  if (rc == 0 && e_rows) rc = st_summary_excursions(c->h, &exc->rows_spec, &exc->rows_w, &exc->rows_yhat);
-  if (rc == 0 && e_new)
-    rc = st_points_summary_excursions(c->h, &exc->new_spec, &exc->new_w, exc_any(exc->new_yhat) ? &exc->new_yhat : nullptr);
-  if (rc == 0 && e_fun)
-    rc = st_points_functionals_excursions(c->h, &exc->fun_spec, &exc->fun_w, exc_any(exc->fun_yhat) ? &exc->fun_yhat : nullptr);
-  if (rc == 0 && r_rows) rc = st_summary_chain_rank_diagnostics(c->h, M, &rk->rows_spec, &rk->rows_w, &rk->rows_yhat);
-  if (rc == 0 && r_new)
-    rc = st_points_summary_chain_rank_diagnostics(c->h, M, &rk->new_spec, &rk->new_w, rank_any(rk->new_yhat) ? &rk->new_yhat : nullptr);
-  if (rc == 0 && r_fun)
-    rc = st_points_functionals_chain_rank_diagnostics(c->h, M, &rk->fun_spec, &rk->fun_w, rank_any(rk->fun_yhat) ? &rk->fun_yhat : nullptr);
-  stm_destroy(c);
-  return rc;
-}
-
-extern "C" int stm_mcmc_ranked(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
-                                    int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
-                                    int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
-                                    double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
-                                    int64_t n_new, const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new,
-                                    const double *X_new, const int64_t *joint_id_new, int64_t keep_draws, const double *quantiles,
-                                    int32_t n_quantiles, double *new_w, double *new_cond_mean, double *new_cond_var, double *new_yhat,
-                                    double *new_mean, double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q,
-                                    double *new_yhat_q, int32_t *new_route, double *new_cond_cov, double *new_cov,
-                                    const stm_functionals *fun, const stm_scores *scores, const stm_diagnostics *diag,
-                                    const stm_excursions *exc, const stm_rank_diagnostics *rk) {
-  return stm_mcmc_chains(pb, opt, set_unif_bounds, theta, ntheta, beta, tausq, mcmcsd, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc,
-                         yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time, n_new, coords_new, mv_new, anchor_new, X_new,
-                         joint_id_new, keep_draws, quantiles, n_quantiles, new_w, new_cond_mean, new_cond_var, new_yhat, new_mean, new_var,
-                         new_w_mean, new_yhat_mean, new_w_q, new_yhat_q, new_route, new_cond_cov, new_cov, fun, scores, diag, exc, rk, nullptr);
-}
-
-extern "C" int stm_mcmc_excursions(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
-                                    int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
-                                    int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
-                                    double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
-                                    int64_t n_new, const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new,
-                                    const double *X_new, const int64_t *joint_id_new, int64_t keep_draws, const double *quantiles,
-                                    int32_t n_quantiles, double *new_w, double *new_cond_mean, double *new_cond_var, double *new_yhat,
-                                    double *new_mean, double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q,
-                                    double *new_yhat_q, int32_t *new_route, double *new_cond_cov, double *new_cov,
-                                    const stm_functionals *fun, const stm_scores *scores, const stm_diagnostics *diag,
-                                    const stm_excursions *exc) {
-  return stm_mcmc_ranked(pb, opt, set_unif_bounds, theta, ntheta, beta, tausq, mcmcsd, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc,
-                         yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time, n_new, coords_new, mv_new, anchor_new, X_new,
-                         joint_id_new, keep_draws, quantiles, n_quantiles, new_w, new_cond_mean, new_cond_var, new_yhat, new_mean, new_var,
-                         new_w_mean, new_yhat_mean, new_w_q, new_yhat_q, new_route, new_cond_cov, new_cov, fun, scores, diag, exc, nullptr);
-}
-
-extern "C" int stm_mcmc_diagnosed(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
-                                    int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
-                                    int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
-                                    double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
-                                    int64_t n_new, const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new,
-                                    const double *X_new, const int64_t *joint_id_new, int64_t keep_draws, const double *quantiles,
-                                    int32_t n_quantiles, double *new_w, double *new_cond_mean, double *new_cond_var, double *new_yhat,
-                                    double *new_mean, double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q,
-                                    double *new_yhat_q, int32_t *new_route, double *new_cond_cov, double *new_cov,
-                                    const stm_functionals *fun, const stm_scores *scores, const stm_diagnostics *diag) {
-  return stm_mcmc_excursions(pb, opt, set_unif_bounds, theta, ntheta, beta, tausq, mcmcsd, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc,
-                             yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time, n_new, coords_new, mv_new, anchor_new, X_new,
-                             joint_id_new, keep_draws, quantiles, n_quantiles, new_w, new_cond_mean, new_cond_var, new_yhat, new_mean, new_var,
-                             new_w_mean, new_yhat_mean, new_w_q, new_yhat_q, new_route, new_cond_cov, new_cov, fun, scores, diag, nullptr);
-}
-
-extern "C" int stm_mcmc_scored(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
-                                    int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
-                                    int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
-                                    double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
-                                    int64_t n_new, const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new,
-                                    const double *X_new, const int64_t *joint_id_new, int64_t keep_draws, const double *quantiles,
-                                    int32_t n_quantiles, double *new_w, double *new_cond_mean, double *new_cond_var, double *new_yhat,
-                                    double *new_mean, double *new_var, double *new_w_mean, double *new_yhat_mean, double *new_w_q,
-                                    double *new_yhat_q, int32_t *new_route, double *new_cond_cov, double *new_cov,
-                                    const stm_functionals *fun, const stm_scores *scores) {
-  return stm_mcmc_diagnosed(pb, opt, set_unif_bounds, theta, ntheta, beta, tausq, mcmcsd, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc,
-                            yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time, n_new, coords_new, mv_new, anchor_new, X_new,
-                            joint_id_new, keep_draws, quantiles, n_quantiles, new_w, new_cond_mean, new_cond_var, new_yhat, new_mean, new_var,
-                            new_w_mean, new_yhat_mean, new_w_q, new_yhat_q, new_route, new_cond_cov, new_cov, fun, scores, nullptr);
-}
-
-// spamtree_mv_mcmc_c plus the criteria over the fit's own rows; criteria NULL: spamtree_mv_mcmc_c itself
-extern "C" int stm_mcmc_criteria(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
-                                 int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
-                                 int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
-                                 double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
-                                 const stm_criteria *criteria) {
-  const stm_criteria *cr = criteria;
-  const bool crps = cr && cr->want_crps && cr->y_holdout;
-  if (cr && cr->crps && !crps) return ST_ERR_USAGE;
-  if (crps && mcmc_keep > 16384) return ST_ERR_UNSUPPORTED;   // st_summary_reserve's limit
-  if (cr && cr->y_holdout && flags && (!flags->sample_predicts || !flags->sample_w)) return ST_ERR_USAGE;   // the NA rows' w would be stale
-  stm_chain c = nullptr;
-  int rc = stm_create(pb, opt, set_unif_bounds, mcmcsd, theta, ntheta, beta, tausq, seed, flags, &c);
-  if (rc == 0 && cr) rc = stm_rows_score_set(c, cr->y_holdout);   // refusals: before any factorisation
-  if (rc == 0 && crps && mcmc_keep > 0) {
-    rc = st_summary_reset(c->h);
-    if (rc == 0) rc = st_summary_reserve(c->h, mcmc_keep);
-  }
-  if (rc == 0) rc = stm_init(c);
-  if (rc != 0) { stm_destroy(c); return rc; }
-  rc = run_fit(c, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc, yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time,
-               nullptr, cr);
-  if (rc == 0 && cr && mcmc_keep > 0) {
+  if (rc == 0 && d.rows) rc = st_summary_chain_diagnostics(c->h, M, diag->max_lag, &diag->rows_w, &diag->rows_yhat);
+  if (rc == 0 && d.pts)
+    rc = st_points_summary_chain_diagnostics(c->h, M, diag->max_lag, &diag->new_w, any_out(diag->new_yhat) ? &diag->new_yhat : nullptr);
+  if (rc == 0 && d.fun)
+    rc = st_points_functionals_chain_diagnostics(c->h, M, diag->max_lag, &diag->fun_w, any_out(diag->fun_yhat) ? &diag->fun_yhat : nullptr);
+  if (rc == 0 && e.rows) rc = st_summary_excursions(c->h, &exc->rows_spec, &exc->rows_w, &exc->rows_yhat);
+  if (rc == 0 && e.pts)
+    rc = st_points_summary_excursions(c->h, &exc->new_spec, &exc->new_w, any_out(exc->new_yhat) ? &exc->new_yhat : nullptr);
+  if (rc == 0 && e.fun)
+    rc = st_points_functionals_excursions(c->h, &exc->fun_spec, &exc->fun_w, any_out(exc->fun_yhat) ? &exc->fun_yhat : nullptr);
+  if (rc == 0 && k.rows) rc = st_summary_chain_rank_diagnostics(c->h, M, &rk->rows_spec, &rk->rows_w, &rk->rows_yhat);
+  if (rc == 0 && k.pts)
+    rc = st_points_summary_chain_rank_diagnostics(c->h, M, &rk->new_spec, &rk->new_w, any_out(rk->new_yhat) ? &rk->new_yhat : nullptr);
+  if (rc == 0 && k.fun)
+    rc = st_points_functionals_chain_rank_diagnostics(c->h, M, &rk->fun_spec, &rk->fun_w, any_out(rk->fun_yhat) ? &rk->fun_yhat : nullptr);
+  if (rc == 0 && cr && saved) {
     rc = st_rows_score_get(c->h, cr->lppd, cr->p_waic, cr->mean_ll, cr->mu_mean, cr->pit, cr->crps, cr->n_accumulated);
     if (rc == 0) rc = st_rows_score_totals(c->h, cr->obs, cr->held, cr->n_obs, cr->n_held);
   }
-  stm_destroy(c);
-  return rc;
-}
-
-// stm_mcmc_criteria plus the leave-one-out criteria with the latent field integrated out; loo NULL: stm_mcmc_criteria itself
-extern "C" int stm_mcmc_loo(const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta,
-                            int ntheta, const double *beta, double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn,
-                            int mcmc_thin, uint64_t seed, const stm_flags *flags, double *w_mcmc, double *yhat_mcmc,
-                            double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time,
-                            const stm_criteria *criteria, const stm_loo *loo) {
-  if (!loo)
-    return stm_mcmc_criteria(pb, opt, set_unif_bounds, theta, ntheta, beta, tausq, mcmcsd, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags,
-                             w_mcmc, yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time, criteria);
-  const stm_criteria *cr = criteria;
-  const bool crps = cr && cr->want_crps && cr->y_holdout;
-  if (cr && cr->crps && !crps) return ST_ERR_USAGE;
-  if (crps && mcmc_keep > 16384) return ST_ERR_UNSUPPORTED;
-  if (cr && cr->y_holdout && flags && (!flags->sample_predicts || !flags->sample_w)) return ST_ERR_USAGE;
-  stm_chain c = nullptr;
-  int rc = stm_create(pb, opt, set_unif_bounds, mcmcsd, theta, ntheta, beta, tausq, seed, flags, &c);
-  if (rc == 0 && cr) rc = stm_rows_score_set(c, cr->y_holdout);
-  if (rc == 0) rc = st_rows_loo_set(c->h);                        // refusals (limited_tree): before any factorisation
-  if (rc == 0 && crps && mcmc_keep > 0) {
-    rc = st_summary_reset(c->h);
-    if (rc == 0) rc = st_summary_reserve(c->h, mcmc_keep);
-  }
-  if (rc == 0) rc = stm_init(c);
-  if (rc != 0) { stm_destroy(c); return rc; }
-  rc = run_fit(c, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc, yhat_mcmc, beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time,
-               nullptr, cr, false, 0, 0, true);
-  if (rc == 0 && cr && mcmc_keep > 0) {
-    rc = st_rows_score_get(c->h, cr->lppd, cr->p_waic, cr->mean_ll, cr->mu_mean, cr->pit, cr->crps, cr->n_accumulated);
-    if (rc == 0) rc = st_rows_score_totals(c->h, cr->obs, cr->held, cr->n_obs, cr->n_held);
-  }
-  if (rc == 0 && mcmc_keep > 0) {
+  if (rc == 0 && loo && saved) {
     rc = st_rows_loo_get(c->h, loo->elpd_loo, loo->pit_loo, loo->mu_loo, loo->weight_ess, loo->n_accumulated, loo->n_skipped);
     if (rc == 0) rc = st_rows_loo_totals(c->h, loo->tot, loo->n_obs);
   }
   stm_destroy(c);
   return rc;
+}
+
+// ---- the positional entry points: each fills a request from its arguments and calls stm_mcmc_fit -------------------------------
+// The two argument lists every one of them repeats, once: the run's twenty and the point set's twenty-two, in the structs' order
+#define STM_RUN_ARGS                                                                                                                    \
+  const st_problem *pb, const st_options *opt, const double *set_unif_bounds, const double *theta, int ntheta, const double *beta,     \
+      double tausq, const double *mcmcsd, int mcmc_keep, int mcmc_burn, int mcmc_thin, uint64_t seed, const stm_flags *flags,          \
+      double *w_mcmc, double *yhat_mcmc, double *beta_mcmc, double *tausq_mcmc, double *theta_mcmc, double *paramsd, double *mcmc_time
+#define STM_RUN                                                                                                                         \
+  { pb, opt, set_unif_bounds, theta, ntheta, beta, tausq, mcmcsd, mcmc_keep, mcmc_burn, mcmc_thin, seed, flags, w_mcmc, yhat_mcmc,      \
+    beta_mcmc, tausq_mcmc, theta_mcmc, paramsd, mcmc_time }
+#define STM_POINTS_ARGS                                                                                                                 \
+  int64_t n_new, const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new, const double *X_new,                      \
+      const int64_t *joint_id_new, int64_t keep_draws, const double *quantiles, int32_t n_quantiles, double *new_w,                    \
+      double *new_cond_mean, double *new_cond_var, double *new_yhat, double *new_mean, double *new_var, double *new_w_mean,             \
+      double *new_yhat_mean, double *new_w_q, double *new_yhat_q, int32_t *new_route, double *new_cond_cov, double *new_cov
+#define STM_POINTS                                                                                                                      \
+  const stm_new_points pts {                                                                                                            \
+    n_new, coords_new, mv_new, anchor_new, X_new, joint_id_new, keep_draws, quantiles, n_quantiles, new_w, new_cond_mean, new_cond_var, \
+        new_yhat, new_mean, new_var, new_w_mean, new_yhat_mean, new_w_q, new_yhat_q, new_route, new_cond_cov, new_cov                   \
+  }
+
+extern "C" int spamtree_mv_mcmc_c(STM_RUN_ARGS) {
+  const stm_fit f{STM_RUN};
+  return stm_mcmc_fit(&f);
+}
+extern "C" int stm_mcmc_points(STM_RUN_ARGS, int64_t n_new, const double *coords_new, const int64_t *mv_new, const int64_t *anchor_new,
+                               const double *X_new, int64_t keep_draws, const double *quantiles, int32_t n_quantiles, double *new_w,
+                               double *new_cond_mean, double *new_cond_var, double *new_yhat, double *new_mean, double *new_var,
+                               double *new_w_mean, double *new_yhat_mean, double *new_w_q, double *new_yhat_q, int32_t *new_route) {
+  const int64_t *const joint_id_new = nullptr;
+  double *const new_cond_cov = nullptr, *const new_cov = nullptr;
+  STM_POINTS;
+  const stm_fit f{STM_RUN, &pts};
+  return stm_mcmc_fit(&f);
+}
+extern "C" int stm_mcmc_points_joint(STM_RUN_ARGS, STM_POINTS_ARGS) {
+  STM_POINTS;
+  const stm_fit f{STM_RUN, &pts};
+  return stm_mcmc_fit(&f);
+}
+extern "C" int stm_mcmc_functionals(STM_RUN_ARGS, STM_POINTS_ARGS, const stm_functionals *fun) {
+  STM_POINTS;
+  const stm_fit f{STM_RUN, &pts, fun};
+  return stm_mcmc_fit(&f);
+}
+extern "C" int stm_mcmc_scored(STM_RUN_ARGS, STM_POINTS_ARGS, const stm_functionals *fun, const stm_scores *scores) {
+  STM_POINTS;
+  const stm_fit f{STM_RUN, &pts, fun, scores};
+  return stm_mcmc_fit(&f);
+}
+extern "C" int stm_mcmc_diagnosed(STM_RUN_ARGS, STM_POINTS_ARGS, const stm_functionals *fun, const stm_scores *scores,
+                                  const stm_diagnostics *diag) {
+  STM_POINTS;
+  const stm_fit f{STM_RUN, &pts, fun, scores, diag};
+  return stm_mcmc_fit(&f);
+}
+extern "C" int stm_mcmc_excursions(STM_RUN_ARGS, STM_POINTS_ARGS, const stm_functionals *fun, const stm_scores *scores,
+                                   const stm_diagnostics *diag, const stm_excursions *exc) {
+  STM_POINTS;
+  const stm_fit f{STM_RUN, &pts, fun, scores, diag, exc};
+  return stm_mcmc_fit(&f);
+}
+extern "C" int stm_mcmc_ranked(STM_RUN_ARGS, STM_POINTS_ARGS, const stm_functionals *fun, const stm_scores *scores,
+                               const stm_diagnostics *diag, const stm_excursions *exc, const stm_rank_diagnostics *rk) {
+  STM_POINTS;
+  const stm_fit f{STM_RUN, &pts, fun, scores, diag, exc, rk};
+  return stm_mcmc_fit(&f);
+}
+extern "C" int stm_mcmc_chains(STM_RUN_ARGS, STM_POINTS_ARGS, const stm_functionals *fun, const stm_scores *scores,
+                               const stm_diagnostics *diag, const stm_excursions *exc, const stm_rank_diagnostics *rk,
+                               const stm_chains *ch) {
+  STM_POINTS;
+  const stm_fit f{STM_RUN, &pts, fun, scores, diag, exc, rk, ch};
+  return stm_mcmc_fit(&f);
+}
+extern "C" int stm_mcmc_criteria(STM_RUN_ARGS, const stm_criteria *criteria) {
+  stm_fit f{STM_RUN};
+  f.criteria = criteria;
+  return stm_mcmc_fit(&f);
+}
+extern "C" int stm_mcmc_loo(STM_RUN_ARGS, const stm_criteria *criteria, const stm_loo *loo) {
+  stm_fit f{STM_RUN};
+  f.criteria = criteria;
+  f.loo = loo;
+  return stm_mcmc_fit(&f);
 }

@@ -4,6 +4,8 @@
 from __future__ import annotations
 
 import ctypes as C
+from types import SimpleNamespace
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -168,6 +170,19 @@ class Chain:
 MAX_STORED_DRAWS = 16384   # st_points_summary_reserve: one point's draws are sorted in one workgroup's LDS
 
 
+class PointsInputs(NamedTuple):
+    """The checked point set of spamtree_mv_mcmc(new_points=...)."""
+    coords: np.ndarray
+    mv: np.ndarray
+    anchor: np.ndarray
+    X: Optional[np.ndarray]
+    quantiles: np.ndarray
+    labels: Optional[np.ndarray]
+    functionals: Optional[tuple]   # model.functionals_csr's (ptr, idx, wt); None: no functional
+    y: Optional[np.ndarray]
+    crps: bool
+
+
 def _points_inputs(new_points, p, q, new_quantiles):
     """Checks the point set of spamtree_mv_mcmc(new_points=...) against itself and the problem, before any device call."""
     pts = dict(new_points)
@@ -219,7 +234,7 @@ def _points_inputs(new_points, p, q, new_quantiles):
     crps = bool(pts.get("crps", True)) and y is not None
     if "crps" in pts and y is None:
         raise ValueError("new_points: crps needs y")
-    return np.asfortranarray(coords), _i64(mv), _i64(anchor), X, qs, labels, fun, y, crps
+    return PointsInputs(np.asfortranarray(coords), _i64(mv), _i64(anchor), X, qs, labels, fun, y, crps)
 
 
 def _joint_layout(labels):
@@ -330,6 +345,116 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     over all 2M half chains, the ESS of the combined chains) under the same keys, on the device for rows, points and functionals
     and on the host for theta, beta and tausq, with ``n_chains`` recorded in them; ``mcmc_keep`` is then the length of one chain.
     ValueError: ``M * mcmc_keep`` > 16384, M outside 1 .. 16, together with ``criteria`` / ``y_holdout`` (a separate driver)."""
+    rq = _check_request(y, X, mv_id, theta, limited_tree, mcmc_keep, sample_predicts, sample_w, seed, new_points, new_quantiles, criteria,
+                        y_holdout, holdout_crps, diagnostics, diagnostics_max_lag, excursions, rank_diagnostics, chains, chain_seeds,
+                        chain_theta, loo)
+    M, keep_all, max_lag = rq.M, rq.keep_all, rq.max_lag
+    lib = _lib.load()
+    pb, keep, n, p, q = _problem(y, X, coords, mv_id, res_is_ref, parents, children, layer_names, layer_gibbs_group, indexing)
+    theta, beta = _f64(theta), _f64(beta)
+    k = theta.size
+    bounds = np.asfortranarray(np.asarray(set_unif_bounds_in, dtype=np.float64))
+    sd = np.asfortranarray(np.asarray(mcmcsd, dtype=np.float64))
+    opt = _lib.StOptions(int(device), int(bool(reference_quirks)), 0, 1, int(bool(force_generic)), 2 if limited_tree else 0)
+    fl = _lib.StmFlags(int(adapting), int(sample_beta), int(sample_tausq), int(sample_theta), int(sample_w), int(sample_predicts))
+    w_all = np.zeros((n, keep_all), order="F") if save_w else None
+    yh_all = np.zeros((n, keep_all), order="F") if save_yhat else None
+    beta_mcmc = np.zeros((p, keep_all, q), order="F"); tausq_mcmc = np.zeros((q, keep_all), order="F")
+    theta_mcmc = np.zeros((k, keep_all), order="F"); paramsd = np.zeros((k, k), order="F")
+    t = C.c_double()
+    # the request (include/spamtree_fit.h, stm_fit): the run, then one pointer per part that is asked for
+    req = _lib.StmFit()
+    req.run = _lib.StmRun(C.pointer(pb), C.pointer(opt), _dp(bounds), _dp(theta), k, _dp(beta), float(tausq), _dp(sd), int(mcmc_keep),
+                          int(mcmc_burn), int(mcmc_thin), int(seed), C.pointer(fl), _opt(w_all), _opt(yh_all), _dp(beta_mcmc),
+                          _dp(tausq_mcmc), _dp(theta_mcmc), _dp(paramsd), C.pointer(t))
+    if M > 1:
+        paramsd_all, chain_time = np.zeros((k, k, M), order="F"), np.zeros(M)
+        chs = _lib.StmChains(M, rq.seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _opt(rq.theta0), _dp(paramsd_all), _dp(chain_time))
+        req.ch = C.pointer(chs)
+    rows = _row_parts(req, rq, n, q, mcmc_keep)
+    new_result = _point_parts(lib, req, rq, rows, q, mcmc_keep, new_draws) if rq.pts is not None else None
+
+    rc = lib.stm_mcmc_fit(C.byref(req))
+    if rc == -10:
+        raise FloatingPointError("At nan loglik: error.")
+    if rc != 0:
+        driver = _reported_driver(rq)
+        if driver is None:
+            if main_verbose:
+                print("MCMC has been interrupted.")
+            return {"None": np.zeros(0)}
+        text = f"{driver} failed ({rc})"
+        if driver == "stm_mcmc_chains":   # what the library refused of the chains before a chain existed to carry the text
+            text = f"{text} {lib.stm_mcmc_chains_last_error().decode()}".rstrip()
+        err = SpamTreeError(text)
+        err.code = rc
+        raise err
+
+    out = {}
+    if save_w:
+        out["w_mcmc"] = [w_all[:, i].reshape(-1, 1).copy() for i in range(keep_all)]
+    if save_yhat:
+        out["yhat_mcmc"] = [yh_all[:, i].reshape(-1, 1).copy() for i in range(keep_all)]
+    out.update(beta_mcmc=beta_mcmc, tausq_mcmc=tausq_mcmc, theta_mcmc=theta_mcmc, paramsd=paramsd, mcmc_time=t.value)
+    if M > 1:   # per-draw arrays hold chain after chain; the multi-chain diagnostics name their n_chains
+        out.update(paramsd=paramsd_all, chain_time=chain_time, chain_id=np.repeat(np.arange(M), int(mcmc_keep)), n_chains=M)
+    if new_result is not None:
+        out["new"] = new = new_result()
+        if M > 1:
+            for part in (new, new.get("functionals", {})):
+                for key in ("diagnostics", "rank_diagnostics"):
+                    if key in part:
+                        part[key]["n_chains"] = M
+    if rows.criteria is not None and mcmc_keep > 0:
+        out["criteria"] = rows.criteria()
+    mv_rows = _i64(mv_id).reshape(-1)
+    scalars = dict(theta=theta_mcmc, beta=np.transpose(beta_mcmc, (0, 2, 1)), tausq=tausq_mcmc)   # the saved scalar chains: on the host
+
+    def rows_summary(host, finish, bufs, summarise):
+        d = {key: host(a) for key, a in scalars.items()}
+        d.update({key: finish(v) for key, v in bufs.items()})
+        d["summary"] = {key: summarise(d[key], mv_rows if key in ("w", "yhat") else None) for key in ("theta", "beta", "tausq", "w", "yhat")}
+        if M > 1:
+            d["n_chains"] = M
+        return d
+    if rows.diag is not None:
+        out["diagnostics"] = rows_summary(lambda a: _diag.chains_diagnostics(a, max_lag, M),
+                                          lambda v: series_diag_finish(v, mcmc_keep, max_lag), rows.diag, _diag.summarise)
+    if rows.exc is not None:
+        out["excursions"] = {key: excursion_finish(v) for key, v in rows.exc.items()}
+    if rows.rank is not None:
+        rank = rq.rank
+        out["rank_diagnostics"] = rows_summary(
+            lambda a: _diag.chains_rank_diagnostics(a, probs=rank["probs"], max_lag=rank["max_lag"], n_chains=M),
+            lambda v: rank_finish(v, mcmc_keep, rank["max_lag"]), rows.rank, _diag.summarise_rank)
+    return out
+
+
+def _opt(a, ptr=_dp):
+    return ptr(a) if a is not None else None
+
+
+def _reported_driver(rq):
+    """The entry point a failure of the chain is reported under in "<driver> failed (rc)": the positional one (include/spamtree_fit.h)
+    of the request's family.  None: the plain fit, which prints "MCMC has been interrupted." where the others raise."""
+    if rq.crit:
+        return "stm_mcmc_loo" if rq.loo else "stm_mcmc_criteria"
+    if rq.pts is not None:
+        return "stm_mcmc_points"
+    if rq.M > 1:
+        return "stm_mcmc_chains"
+    if rq.rank is not None:
+        return "stm_mcmc_ranked"
+    if rq.exc is not None:
+        return "stm_mcmc_excursions"
+    return "stm_mcmc_diagnosed" if rq.diagnostics else None
+
+
+def _check_request(y, X, mv_id, theta, limited_tree, mcmc_keep, sample_predicts, sample_w, seed, new_points, new_quantiles, criteria,
+                   y_holdout, holdout_crps, diagnostics, diagnostics_max_lag, excursions, rank_diagnostics, chains, chain_seeds, chain_theta,
+                   loo):
+    """Every check of spamtree_mv_mcmc's optional parts that needs no device (ValueError), and what they normalise: the chains'
+    seeds and starts, the rank and excursion specs, the held-out values of the rows, the point set."""
     crit_cond = bool(criteria) or y_holdout is not None
     loo = bool(loo)
     if loo and limited_tree:
@@ -339,6 +464,7 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     if not 1 <= M <= _diag.MAX_CHAINS:
         raise ValueError(f"chains = {M} must lie in 1 .. {_diag.MAX_CHAINS}")
     keep_all = M * int(mcmc_keep)   # the columns of every per-draw array
+    seeds = theta0 = None
     if M > 1:
         if crit:
             raise ValueError("chains and criteria / y_holdout are separate drivers (stm_mcmc_chains, stm_mcmc_criteria): one per call")
@@ -347,7 +473,6 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
         seeds = np.array([int(seed) + c for c in range(M)] if chain_seeds is None else [int(s) for s in chain_seeds], dtype=np.uint64)
         if seeds.shape != (M,):
             raise ValueError(f"chain_seeds must hold one seed per chain ({M})")
-        theta0 = None
         if chain_theta is not None:
             theta0 = np.ascontiguousarray(chain_theta, dtype=np.float64)   # M x k in C order: k x M column-major
             if theta0.shape != (M, np.size(theta)):
@@ -394,7 +519,7 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                              "(the series' length, and the draws the device keeps per row)")
         if int(diagnostics_max_lag) < 0:
             raise ValueError("diagnostics_max_lag must not be negative (0: the default cap)")
-    max_lag = int(diagnostics_max_lag)
+    y_hold, want_crps = None, False
     if crit:
         if new_points is not None:
             raise ValueError("criteria and new_points are separate drivers (stm_mcmc_criteria, stm_mcmc_scored): one per call")
@@ -405,336 +530,201 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
         if want_crps and int(mcmc_keep) > MAX_STORED_DRAWS:
             raise ValueError(f"y_holdout: the CRPS keeps mcmc_keep = {int(mcmc_keep)} draws per row on the device, at most "
                              f"{MAX_STORED_DRAWS} (holdout_crps=False scores without it)")
+    pts = None
+    q_out = int(np.unique(_i64(mv_id)).size)
     if new_points is not None:
-        pts = _points_inputs(new_points, np.asarray(X).shape[1], int(np.unique(_i64(mv_id)).size), new_quantiles)
-        if pts[8] and int(mcmc_keep) > MAX_STORED_DRAWS:
+        pts = _points_inputs(new_points, np.asarray(X).shape[1], q_out, new_quantiles)
+        if pts.crps and int(mcmc_keep) > MAX_STORED_DRAWS:
             raise ValueError(f"new_points: the CRPS keeps mcmc_keep = {int(mcmc_keep)} draws per point on the device, at most "
                              f"{MAX_STORED_DRAWS} (crps=False scores without it)")
     elif len(tuple(new_quantiles)):
         raise ValueError("new_quantiles needs new_points")
-    xs = None
+    n_fun = None if pts is None or pts.functionals is None else pts.functionals[0].size - 1
     if exc is not None:   # the shapes, still before any device call
-        n_rows, q_out = int(np.asarray(y).size), int(np.unique(_i64(mv_id)).size)
         thr = sides = None
         if exc.get("thresholds") is not None:
             thr, sides = _exc.expand_thresholds(exc["thresholds"], q_out, exc.get("side", 1))
-        exc["spec_rows"] = excursion_spec(thr, sides, _exc.check_mask(exc.get("mask"), n_rows), exc["band"])
+        exc["spec_rows"] = excursion_spec(thr, sides, _exc.check_mask(exc.get("mask"), int(np.asarray(y).size)), exc["band"])
         exc["T"] = 0 if thr is None else thr.shape[0]
-        if new_points is not None:
-            exc["spec_new"] = excursion_spec(thr, sides, _exc.check_mask(exc.get("mask_new"), pts[0].shape[0]), exc["band"])
-            if pts[6] is not None:
-                nf_ = pts[6][0].size - 1
+        if pts is not None:
+            exc["spec_new"] = excursion_spec(thr, sides, _exc.check_mask(exc.get("mask_new"), pts.coords.shape[0]), exc["band"])
+            if n_fun is not None:
                 tf = exc.get("thresholds_fun", exc.get("thresholds"))
                 thr_f = sides_f = None
                 if tf is not None:
-                    thr_f, sides_f = _exc.expand_thresholds(tf, nf_, exc.get("side", 1))
-                exc["spec_fun"] = excursion_spec(thr_f, sides_f, _exc.check_mask(exc.get("mask_fun"), nf_), exc["band"])
+                    thr_f, sides_f = _exc.expand_thresholds(tf, n_fun, exc.get("side", 1))
+                exc["spec_fun"] = excursion_spec(thr_f, sides_f, _exc.check_mask(exc.get("mask_fun"), n_fun), exc["band"])
         elif any(exc.get(key) is not None for key in ("mask_new", "thresholds_fun", "mask_fun")):
             raise ValueError("excursions: mask_new, thresholds_fun and mask_fun need new_points")
     if rank is not None:   # the shapes, still before any device call
-        q_out = int(np.unique(_i64(mv_id)).size)
         rank["spec_rows"] = rank_spec(rank["probs"], rank["thresholds"], rank["sides"], rank["max_lag"], q_out)
-        if new_points is not None:
+        if pts is not None:
             rank["spec_new"] = rank_spec(rank["probs"], rank["thresholds"], rank["sides"], rank["max_lag"], q_out)
-            if pts[6] is not None:
+            if n_fun is not None:
                 tf = rank.get("thresholds_fun")
                 tf, sf = (rank["thresholds"], rank["sides"]) if tf is None else _diag.check_rank_spec((), tf, rank["sides"], 0)[1:]
-                rank["spec_fun"] = rank_spec(rank["probs"], tf, sf, rank["max_lag"], pts[6][0].size - 1)
+                rank["spec_fun"] = rank_spec(rank["probs"], tf, sf, rank["max_lag"], n_fun)
         elif rank.get("thresholds_fun") is not None:
             raise ValueError("rank_diagnostics: thresholds_fun needs new_points")
-    lib = _lib.load()
-    pb, keep, n, p, q = _problem(y, X, coords, mv_id, res_is_ref, parents, children, layer_names, layer_gibbs_group, indexing)
-    theta = _f64(theta)
-    k = theta.size
-    bounds = np.asfortranarray(np.asarray(set_unif_bounds_in, dtype=np.float64))
-    sd = np.asfortranarray(np.asarray(mcmcsd, dtype=np.float64))
-    opt = _lib.StOptions(int(device), int(bool(reference_quirks)), 0, 1, int(bool(force_generic)), 2 if limited_tree else 0)
-    fl = _lib.StmFlags(int(adapting), int(sample_beta), int(sample_tausq), int(sample_theta), int(sample_w), int(sample_predicts))
-    w_all = np.zeros((n, keep_all), order="F") if save_w else None
-    yh_all = np.zeros((n, keep_all), order="F") if save_yhat else None
-    beta_mcmc = np.zeros((p, keep_all, q), order="F"); tausq_mcmc = np.zeros((q, keep_all), order="F")
-    theta_mcmc = np.zeros((k, keep_all), order="F"); paramsd = np.zeros((k, k), order="F")
-    t = C.c_double()
-    chs = None
-    if M > 1:   # stm_mcmc_chains: stm_mcmc_ranked plus the chains
-        paramsd_all, chain_time = np.zeros((k, k, M), order="F"), np.zeros(M)
-        chs = _lib.StmChains(M, seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(theta0) if theta0 is not None else None,
-                             _dp(paramsd_all), _dp(chain_time))
-    dp = lambda a: _dp(a) if a is not None else None   # noqa: E731
-    common = (C.byref(pb), C.byref(opt), _dp(bounds), _dp(theta), k, _dp(_f64(beta)), float(tausq), _dp(sd), int(mcmc_keep),
-              int(mcmc_burn), int(mcmc_thin), int(seed), C.byref(fl), dp(w_all), dp(yh_all), _dp(beta_mcmc), _dp(tausq_mcmc),
-              _dp(theta_mcmc), _dp(paramsd), C.byref(t))
-    new = None
-    crit_out = None
-    diag_rows = ds = None
-    if diagnostics:       # stm_mcmc_diagnosed: the rows' outputs here, the points' and functionals' below
+    return SimpleNamespace(crit_cond=crit_cond, loo=loo, crit=crit, M=M, keep_all=keep_all, seeds=seeds, theta0=theta0, rank=rank, exc=exc,
+                           diagnostics=diagnostics, max_lag=int(diagnostics_max_lag), y_hold=y_hold, want_crps=want_crps, pts=pts)
+
+
+def _row_parts(req, rq, n, q, mcmc_keep):
+    """The parts of the request over the fit's own rows, set in ``req``, and their buffers: the row members of diagnostics, excursions
+    and rank diagnostics (``ds``, ``xs``, ``rs``: _point_parts sets the points' and functionals' members), the criteria and the
+    leave-one-out criteria (``criteria()``: their part of the result)."""
+    out = SimpleNamespace(diag=None, exc=None, rank=None, ds=None, xs=None, rs=None, criteria=None)
+    if rq.diagnostics:
         dw, sw = series_diag_buffers(n)
         dy, sy = series_diag_buffers(n)
-        diag_rows = dict(w=dw, yhat=dy)
-        ds = _lib.StmDiagnostics(max_lag, 1, sw, sy)
-    exc_rows = exc_new = exc_fun = None
-    if exc is not None:   # stm_mcmc_excursions: stm_mcmc_diagnosed plus the excursions of the rows, points and functionals
-        xs = _lib.StmExcursions()
+        out.diag, out.ds = dict(w=dw, yhat=dy), _lib.StmDiagnostics(rq.max_lag, 1, sw, sy)
+        req.diag = C.pointer(out.ds)
+    if rq.exc is not None:
+        exc = rq.exc
+        out.xs = xs = _lib.StmExcursions()
         xs.want_rows = 1
         xs.rows_spec = exc["spec_rows"][0]
-        xw, xs.rows_w = excursion_buffers(n, exc["T"], q, keep_all, exc["band"])
-        xy, xs.rows_yhat = excursion_buffers(n, exc["T"], q, keep_all, exc["band"])
-        exc_rows = dict(w=xw, yhat=xy)
-    dsp = C.byref(ds) if ds is not None else None
-    xsp = C.byref(xs) if xs is not None else None
-    rank_rows = rank_new = rank_fun = rs = None
-    if rank is not None:  # stm_mcmc_ranked: stm_mcmc_excursions plus the rank diagnostics of the rows, points and functionals
-        rs = _lib.StmRankDiagnostics()
+        xw, xs.rows_w = excursion_buffers(n, exc["T"], q, rq.keep_all, exc["band"])
+        xy, xs.rows_yhat = excursion_buffers(n, exc["T"], q, rq.keep_all, exc["band"])
+        out.exc = dict(w=xw, yhat=xy)
+        req.exc = C.pointer(xs)
+    if rq.rank is not None:
+        out.rs = rs = _lib.StmRankDiagnostics()
         rs.want_rows = 1
-        rs.rows_spec, _, n_prob_r, n_thr_r = rank["spec_rows"]
-        rw, rs.rows_w = rank_buffers(n, n_prob_r, n_thr_r)
-        ry, rs.rows_yhat = rank_buffers(n, n_prob_r, n_thr_r)
-        rank_rows = dict(w=rw, yhat=ry)
-    if crit:
+        rs.rows_spec, _, n_prob, n_thr = rq.rank["spec_rows"]
+        rw, rs.rows_w = rank_buffers(n, n_prob, n_thr)
+        ry, rs.rows_yhat = rank_buffers(n, n_prob, n_thr)
+        out.rank = dict(w=rw, yhat=ry)
+        req.rk = C.pointer(rs)
+    if rq.crit_cond:
         rows = {key: np.zeros(n) for key in ("lppd", "p_waic", "mean_ll", "mu_mean", "pit")}
-        rows["crps"] = np.zeros(n) if (want_crps and mcmc_keep > 0) else None
+        rows["crps"] = np.zeros(n) if (rq.want_crps and mcmc_keep > 0) else None
         tobs = np.zeros((len(_lib.ST_ROWS_OBS), q), order="F"); theld = np.zeros((len(_lib.ST_ROWS_HELD), q), order="F")
         n_obs, n_held = np.zeros(q, dtype=np.int64), np.zeros(q, dtype=np.int64)
         nacc = C.c_int64()
-        cs = _lib.StmCriteria(dp(y_hold), int(want_crps), *[dp(rows[key]) for key in ("lppd", "p_waic", "mean_ll", "mu_mean", "pit", "crps")],
+        cs = _lib.StmCriteria(_opt(rq.y_hold), int(rq.want_crps), *[_opt(rows[key]) for key in ("lppd", "p_waic", "mean_ll", "mu_mean", "pit", "crps")],
                               _dp(tobs), _dp(theld), _ip(n_obs), _ip(n_held), C.pointer(nacc))
-        driver = "stm_mcmc_loo" if loo else "stm_mcmc_criteria"
-        if loo:
-            lrows = {key: np.zeros(n) for key in ("elpd_loo", "pit_loo", "mu_loo", "weight_ess")}
-            ltot, ln_obs = np.zeros((len(_lib.ST_ROWS_LOO), q), order="F"), np.zeros(q, dtype=np.int64)
-            lacc, lskip = C.c_int64(), C.c_int64()
-            ls = _lib.StmLoo(*[_dp(lrows[key]) for key in ("elpd_loo", "pit_loo", "mu_loo", "weight_ess")], _dp(ltot), _ip(ln_obs),
-                             C.pointer(lacc), C.pointer(lskip))
-            rc = lib.stm_mcmc_loo(*common, C.byref(cs) if crit_cond else None, C.byref(ls))
-        else:
-            rc = lib.stm_mcmc_criteria(*common, C.byref(cs))
-        if rc == 0 and mcmc_keep > 0:
-            crit_out = {}
-            if crit_cond:
-                crit_out = dict(rows, n_accumulated=int(nacc.value),
-                                totals=rows_criteria(tobs, theld, n_obs, n_held, have_crps=rows["crps"] is not None))
-            if loo:
-                crit_out["loo"] = dict(lrows, n_accumulated=int(lacc.value), n_skipped=int(lskip.value),
-                                       totals=rows_loo_criteria(ltot, ln_obs))
-        elif rc not in (0, -10):
-            err = SpamTreeError(f"{driver} failed ({rc})")
-            err.code = rc
-            raise err
-    elif new_points is None and M > 1:   # the plain chains: no point argument
-        rc = lib.stm_mcmc_chains(*common, 0, None, None, None, None, None, 0, None, 0, *([None] * 15), dsp, xsp,
-                                 C.byref(rs) if rs is not None else None, C.byref(chs))
-        if rc not in (0, -10):
-            err = SpamTreeError(f"stm_mcmc_chains failed ({rc}) {lib.stm_mcmc_chains_last_error().decode()}".rstrip())
-            err.code = rc
-            raise err
-    elif new_points is None and rank is not None:   # the plain chain through the ranked driver: no point argument
-        rc = lib.stm_mcmc_ranked(*common, 0, None, None, None, None, None, 0, None, 0, *([None] * 15), dsp, xsp, C.byref(rs))
-        if rc not in (0, -10):
-            err = SpamTreeError(f"stm_mcmc_ranked failed ({rc})")
-            err.code = rc
-            raise err
-    elif new_points is None and exc is not None:   # the plain chain through the excursions driver: no point argument
-        rc = lib.stm_mcmc_excursions(*common, 0, None, None, None, None, None, 0, None, 0, *([None] * 15), dsp, C.byref(xs))
-        if rc not in (0, -10):
-            err = SpamTreeError(f"stm_mcmc_excursions failed ({rc})")
-            err.code = rc
-            raise err
-    elif new_points is None and diagnostics:   # the plain chain through the diagnosed driver: no point argument
-        rc = lib.stm_mcmc_diagnosed(*common, 0, None, None, None, None, None, 0, None, 0, *([None] * 15), C.byref(ds))
-        if rc not in (0, -10):
-            err = SpamTreeError(f"stm_mcmc_diagnosed failed ({rc})")
-            err.code = rc
-            raise err
-    elif new_points is None:
-        rc = lib.spamtree_mv_mcmc_c(*common)
-    else:
-        pc, pmv, pan, pX, qs, labels, fun, ynew, want_crps = pts
-        n_new = pc.shape[0]
-        draws = {key: np.zeros((n_new, keep_all), order="F") if new_draws else None for key in ("w", "cond_mean", "cond_var")}
-        draws["yhat"] = np.zeros((n_new, keep_all), order="F") if (new_draws and pX is not None) else None
-        summ = {key: np.zeros(n_new) for key in ("mean", "var", "w_mean")}
-        summ["yhat_mean"] = np.zeros(n_new) if pX is not None else None
-        wq = np.zeros((n_new, qs.size), order="F")
-        yq = np.zeros((n_new, qs.size), order="F") if pX is not None else None
-        route = C.c_int32()
-        tail = (int(mcmc_keep) if (qs.size or want_crps) else 0, _dp(qs), int(qs.size), dp(draws["w"]), dp(draws["cond_mean"]),
-                dp(draws["cond_var"]), dp(draws["yhat"]), dp(summ["mean"]), dp(summ["var"]), dp(summ["w_mean"]),
-                dp(summ["yhat_mean"]), dp(wq if qs.size else None), dp(yq if qs.size else None), C.byref(route))
-        groups = off = ccov = cov = None
-        if labels is not None:
-            groups, off = _joint_layout(labels)
-            ccov = np.zeros((int(off[-1]), keep_all), order="F") if new_draws else None
-            cov = np.zeros(int(off[-1]))
-        fsp = None
-        if fun is not None:       # stm_mcmc_functionals: both kinds of set, plus the functional outputs in one struct
-            nf = fun[0].size - 1
-            fdraws = {key: np.zeros((nf, keep_all), order="F") if new_draws else None for key in ("w", "cond_mean", "cond_var")}
-            fdraws["yhat"] = np.zeros((nf, keep_all), order="F") if (new_draws and pX is not None) else None
-            fsumm = {key: np.zeros(nf) for key in ("mean", "var", "w_mean")}
-            fsumm["yhat_mean"] = np.zeros(nf) if pX is not None else None
-            fwq = np.zeros((nf, qs.size), order="F")
-            fyq = np.zeros((nf, qs.size), order="F") if pX is not None else None
-            fs = _lib.StmFunctionals(nf, _ip(fun[0]), _ip(fun[1]), _dp(fun[2]), dp(fdraws["w"]), dp(fdraws["cond_mean"]),
-                                     dp(fdraws["cond_var"]), dp(fdraws["yhat"]), dp(fsumm["mean"]), dp(fsumm["var"]), dp(fsumm["w_mean"]),
-                                     dp(fsumm["yhat_mean"]), dp(fwq if qs.size else None), dp(fyq if qs.size else None))
-            fsp = C.byref(fs)
-        ss = None
-        if ynew is not None:      # stm_mcmc_scored: the same call plus the scores; crps from the draws the device keeps
-            sc = dict(lpd=np.zeros(n_new), pit=np.zeros(n_new), crps=np.zeros(n_new) if (want_crps and mcmc_keep > 0) else None,
-                      lpd_joint=np.zeros(len(groups)) if labels is not None else None)
-            nsc, ndg = C.c_int64(), C.c_int64()
-            ss = _lib.StmScores(_dp(ynew), dp(sc["lpd"]), dp(sc["pit"]), dp(sc["crps"]), dp(sc["lpd_joint"]),
-                                C.pointer(nsc), C.pointer(ndg))
-        diag_new = diag_fun = None
-        if diagnostics:           # stm_mcmc_diagnosed: the same call plus the diagnostics of the rows, points and functionals
-            dnw, ds.new_w = series_diag_buffers(n_new)
-            dny, s_ny = series_diag_buffers(n_new, pX is not None)
-            if s_ny is not None:
-                ds.new_yhat = s_ny
-            diag_new = dict(w=dnw, yhat=dny)
-            if fun is not None:
-                dfw, ds.fun_w = series_diag_buffers(nf)
-                dfy, s_fy = series_diag_buffers(nf, pX is not None)
-                if s_fy is not None:
-                    ds.fun_yhat = s_fy
-                diag_fun = dict(w=dfw, yhat=dfy)
-        if exc is not None:
-            xs.new_spec = exc["spec_new"][0]
-            T_f = 0
-            xnw, xs.new_w = excursion_buffers(n_new, exc["T"], q, keep_all, exc["band"])
-            xny, o_ny = excursion_buffers(n_new, exc["T"], q, keep_all, exc["band"], pX is not None)
-            if o_ny is not None:
-                xs.new_yhat = o_ny
-            exc_new = dict(w=xnw, yhat=xny)
-            if fun is not None:
-                xs.fun_spec = exc["spec_fun"][0]
-                T_f = int(xs.fun_spec.n_thr)
-                xfw, xs.fun_w = excursion_buffers(nf, T_f, 1, keep_all, exc["band"])
-                xfy, o_fy = excursion_buffers(nf, T_f, 1, keep_all, exc["band"], pX is not None)
-                if o_fy is not None:
-                    xs.fun_yhat = o_fy
-                exc_fun = dict(w=xfw, yhat=xfy)
-        if rank is not None:
-            rs.new_spec, _, n_prob_r, n_thr_r = rank["spec_new"]
-            rnw, rs.new_w = rank_buffers(n_new, n_prob_r, n_thr_r)
-            rny, o_rny = rank_buffers(n_new, n_prob_r, n_thr_r, pX is not None)
-            if o_rny is not None:
-                rs.new_yhat = o_rny
-            rank_new = dict(w=rnw, yhat=rny)
-            if fun is not None:
-                rs.fun_spec, _, n_prob_f, n_thr_f = rank["spec_fun"]
-                rfw, rs.fun_w = rank_buffers(nf, n_prob_f, n_thr_f)
-                rfy, o_rfy = rank_buffers(nf, n_prob_f, n_thr_f, pX is not None)
-                if o_rfy is not None:
-                    rs.fun_yhat = o_rfy
-                rank_fun = dict(w=rfw, yhat=rfy)
-        if M > 1:
-            rc = lib.stm_mcmc_chains(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), _ip(labels) if labels is not None else None,
-                                     *tail, dp(ccov), dp(cov), fsp, C.byref(ss) if ss is not None else None, dsp, xsp,
-                                     C.byref(rs) if rs is not None else None, C.byref(chs))
-        elif rank is not None:
-            rc = lib.stm_mcmc_ranked(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), _ip(labels) if labels is not None else None,
-                                     *tail, dp(ccov), dp(cov), fsp, C.byref(ss) if ss is not None else None, dsp, xsp, C.byref(rs))
-        elif exc is not None:
-            rc = lib.stm_mcmc_excursions(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), _ip(labels) if labels is not None else None,
-                                         *tail, dp(ccov), dp(cov), fsp, C.byref(ss) if ss is not None else None,
-                                         C.byref(ds) if ds is not None else None, C.byref(xs))
-        elif diagnostics:
-            rc = lib.stm_mcmc_diagnosed(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), _ip(labels) if labels is not None else None,
-                                        *tail, dp(ccov), dp(cov), fsp, C.byref(ss) if ss is not None else None, C.byref(ds))
-        elif ynew is not None:
-            rc = lib.stm_mcmc_scored(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), _ip(labels) if labels is not None else None,
-                                     *tail, dp(ccov), dp(cov), fsp, C.byref(ss))
-        elif fun is not None:
-            rc = lib.stm_mcmc_functionals(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), _ip(labels) if labels is not None else None,
-                                          *tail, dp(ccov), dp(cov), fsp)
-        elif labels is None:
-            rc = lib.stm_mcmc_points(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), *tail)
-        else:
-            rc = lib.stm_mcmc_points_joint(*common, n_new, _dp(pc), _ip(pmv), _ip(pan), dp(pX), _ip(labels), *tail, dp(ccov),
-                                           _dp(cov))
-        if rc == 0:
-            names, code = [], 1
-            while lib.st_points_route_name(code) is not None:
-                if route.value & (1 << (code - 1)):
-                    names.append(lib.st_points_route_name(code).decode())
-                code += 1
-            new = dict(summ, route=names,
-                       quantiles={float(x): (wq[:, i].copy(), None if yq is None else yq[:, i].copy()) for i, x in enumerate(qs)})
-            if new_draws:
-                new.update(draws)
-            if labels is not None:
-                new.update(groups=groups, cov=_unpack_joint(cov, groups, off))
-                if new_draws:
-                    new["cond_cov"] = [_unpack_joint(ccov[:, s], groups, off) for s in range(keep_all)]
-            if fun is not None:
-                new["functionals"] = dict(fsumm, quantiles={float(x): (fwq[:, i].copy(), None if fyq is None else fyq[:, i].copy())
-                                                            for i, x in enumerate(qs)})
-                if new_draws:
-                    new["functionals"].update(fdraws)
-            if ynew is not None and mcmc_keep > 0:
-                sc.update(n_scored=int(nsc.value), n_degenerate=int(ndg.value))
-                lo_hi = (yq[:, int(np.argmin(qs))], yq[:, int(np.argmax(qs))]) if qs.size >= 2 else (None, None)
-                sc["totals"] = score_totals(sc, ynew, pmv, q, *lo_hi)
-                new["scores"] = sc
-            if diag_new is not None and n_new > 0:
-                new["diagnostics"] = {key: series_diag_finish(v, mcmc_keep, max_lag) for key, v in diag_new.items()}
-            if diag_fun is not None and n_new > 0:
-                new["functionals"]["diagnostics"] = {key: series_diag_finish(v, mcmc_keep, max_lag) for key, v in diag_fun.items()}
-            if exc_new is not None and n_new > 0:
-                new["excursions"] = {key: excursion_finish(v) for key, v in exc_new.items()}
-            if exc_fun is not None and n_new > 0:
-                new["functionals"]["excursions"] = {key: excursion_finish(v) for key, v in exc_fun.items()}
-            if rank_new is not None and n_new > 0:
-                new["rank_diagnostics"] = {key: rank_finish(v, mcmc_keep, rank["max_lag"]) for key, v in rank_new.items()}
-            if rank_fun is not None and n_new > 0:
-                new["functionals"]["rank_diagnostics"] = {key: rank_finish(v, mcmc_keep, rank["max_lag"]) for key, v in rank_fun.items()}
-    if rc == -10:
-        raise FloatingPointError("At nan loglik: error.")
-    if rc != 0 and new_points is not None:
-        err = SpamTreeError(f"stm_mcmc_points failed ({rc})")
-        err.code = rc
-        raise err
-    if rc != 0:
-        if main_verbose:
-            print("MCMC has been interrupted.")
-        return {"None": np.zeros(0)}
-    out = {}
-    if save_w:
-        out["w_mcmc"] = [w_all[:, i].reshape(-1, 1).copy() for i in range(keep_all)]
-    if save_yhat:
-        out["yhat_mcmc"] = [yh_all[:, i].reshape(-1, 1).copy() for i in range(keep_all)]
-    out.update(beta_mcmc=beta_mcmc, tausq_mcmc=tausq_mcmc, theta_mcmc=theta_mcmc, paramsd=paramsd, mcmc_time=t.value)
-    if M > 1:   # per-draw arrays hold chain after chain; the multi-chain diagnostics name their n_chains
-        out.update(paramsd=paramsd_all, chain_time=chain_time, chain_id=np.repeat(np.arange(M), int(mcmc_keep)), n_chains=M)
-    if new is not None:
-        out["new"] = new
-        if M > 1:
-            for part in (new, new.get("functionals", {})):
-                for key in ("diagnostics", "rank_diagnostics"):
-                    if key in part:
-                        part[key]["n_chains"] = M
-    if crit_out is not None:
-        out["criteria"] = crit_out
-    if diagnostics:
-        d = dict(theta=_diag.chains_diagnostics(theta_mcmc, max_lag, M),
-                 beta=_diag.chains_diagnostics(np.transpose(beta_mcmc, (0, 2, 1)), max_lag, M),
-                 tausq=_diag.chains_diagnostics(tausq_mcmc, max_lag, M),
-                 w=series_diag_finish(diag_rows["w"], mcmc_keep, max_lag), yhat=series_diag_finish(diag_rows["yhat"], mcmc_keep, max_lag))
-        mv_rows = _i64(mv_id).reshape(-1)
-        d["summary"] = {key: _diag.summarise(d[key], mv_rows if key in ("w", "yhat") else None) for key in ("theta", "beta", "tausq", "w", "yhat")}
-        if M > 1:
-            d["n_chains"] = M
-        out["diagnostics"] = d
-    if exc_rows is not None:
-        out["excursions"] = {key: excursion_finish(v) for key, v in exc_rows.items()}
-    if rank_rows is not None:
-        host = lambda a: _diag.chains_rank_diagnostics(a, probs=rank["probs"], max_lag=rank["max_lag"], n_chains=M)   # noqa: E731
-        r = dict(theta=host(theta_mcmc), beta=host(np.transpose(beta_mcmc, (0, 2, 1))), tausq=host(tausq_mcmc),
-                 w=rank_finish(rank_rows["w"], mcmc_keep, rank["max_lag"]), yhat=rank_finish(rank_rows["yhat"], mcmc_keep, rank["max_lag"]))
-        mv_rows = _i64(mv_id).reshape(-1)
-        r["summary"] = {key: _diag.summarise_rank(r[key], mv_rows if key in ("w", "yhat") else None) for key in ("theta", "beta", "tausq", "w", "yhat")}
-        if M > 1:
-            r["n_chains"] = M
-        out["rank_diagnostics"] = r
+        req.criteria = C.pointer(cs)
+    if rq.loo:
+        lrows = {key: np.zeros(n) for key in ("elpd_loo", "pit_loo", "mu_loo", "weight_ess")}
+        ltot, ln_obs = np.zeros((len(_lib.ST_ROWS_LOO), q), order="F"), np.zeros(q, dtype=np.int64)
+        lacc, lskip = C.c_int64(), C.c_int64()
+        ls = _lib.StmLoo(*[_dp(lrows[key]) for key in ("elpd_loo", "pit_loo", "mu_loo", "weight_ess")], _dp(ltot), _ip(ln_obs),
+                         C.pointer(lacc), C.pointer(lskip))
+        req.loo = C.pointer(ls)
+
+    def criteria():
+        res = {}
+        if rq.crit_cond:
+            res = dict(rows, n_accumulated=int(nacc.value), totals=rows_criteria(tobs, theld, n_obs, n_held, have_crps=rows["crps"] is not None))
+        if rq.loo:
+            res["loo"] = dict(lrows, n_accumulated=int(lacc.value), n_skipped=int(lskip.value), totals=rows_loo_criteria(ltot, ln_obs))
+        return res
+    if rq.crit:
+        out.criteria = criteria
     return out
+
+
+def _point_parts(lib, req, rq, rows, q, mcmc_keep, new_draws):
+    """The parts of the request at the new points, set in ``req``, and their buffers: the point set, its functionals and scores, and
+    the points' and functionals' members of ``rows.ds``, ``rows.xs`` and ``rows.rs``.  Returns the function that forms ``new`` of the
+    result after the call."""
+    pc, pmv, pan, pX, qs, labels, fun, ynew, want_crps = rq.pts
+    keep_all, has_X = rq.keep_all, pX is not None
+    n_new = pc.shape[0]
+
+    def outputs(m):
+        """Of a set of m series: the per-draw arrays, the summaries, the quantiles of w and yhat, and the ten pointers to them in
+        the order of stm_new_points and stm_functionals (yhat only with X, per-draw only with new_draws, quantiles only when asked)."""
+        draws = {key: np.zeros((m, keep_all), order="F") if new_draws else None for key in ("w", "cond_mean", "cond_var")}
+        draws["yhat"] = np.zeros((m, keep_all), order="F") if (new_draws and has_X) else None
+        summ = {key: np.zeros(m) for key in ("mean", "var", "w_mean")}
+        summ["yhat_mean"] = np.zeros(m) if has_X else None
+        wq = np.zeros((m, qs.size), order="F")
+        yq = np.zeros((m, qs.size), order="F") if has_X else None
+        return draws, summ, wq, yq, [_opt(a) for a in (*draws.values(), *summ.values(), wq if qs.size else None, yq if qs.size else None)]
+    draws, summ, wq, yq, ptrs = outputs(n_new)
+    route = C.c_int32()
+    groups = off = ccov = cov = None
+    if labels is not None:
+        groups, off = _joint_layout(labels)
+        ccov = np.zeros((int(off[-1]), keep_all), order="F") if new_draws else None
+        cov = np.zeros(int(off[-1]))
+    ps = _lib.StmNewPoints(n_new, _dp(pc), _ip(pmv), _ip(pan), _opt(pX), _opt(labels, _ip), int(mcmc_keep) if (qs.size or want_crps) else 0,
+                           _dp(qs), int(qs.size), *ptrs, C.pointer(route), _opt(ccov), _opt(cov))
+    req.pts = C.pointer(ps)
+    sets = dict(new=n_new)   # the sets of series a stored-draw summary can be asked of, and their sizes
+    if fun is not None:
+        sets["fun"] = nf = fun[0].size - 1
+        fdraws, fsumm, fwq, fyq, fptrs = outputs(nf)
+        fs = _lib.StmFunctionals(nf, _ip(fun[0]), _ip(fun[1]), _dp(fun[2]), *fptrs)
+        req.fun = C.pointer(fs)
+    if ynew is not None:      # crps from the draws the device keeps
+        sc = dict(lpd=np.zeros(n_new), pit=np.zeros(n_new), crps=np.zeros(n_new) if (want_crps and mcmc_keep > 0) else None,
+                  lpd_joint=np.zeros(len(groups)) if labels is not None else None)
+        nsc, ndg = C.c_int64(), C.c_int64()
+        ss = _lib.StmScores(_dp(ynew), _opt(sc["lpd"]), _opt(sc["pit"]), _opt(sc["crps"]), _opt(sc["lpd_joint"]), C.pointer(nsc), C.pointer(ndg))
+        req.scores = C.pointer(ss)
+
+    def stored(part, buffers):
+        """The buffers of one stored-draw summary for every set, its <set>_w and <set>_yhat members of ``part`` pointing at them; yhat
+        only with X.  ``buffers(set, m, want)`` is the summary's (dict, struct) of m series."""
+        out = {}
+        for name, m in sets.items():
+            bw, sw = buffers(name, m, True)
+            by, sy = buffers(name, m, has_X)
+            setattr(part, name + "_w", sw)
+            if sy is not None:
+                setattr(part, name + "_yhat", sy)
+            out[name] = dict(w=bw, yhat=by)
+        return out
+    summaries = []   # (result key, how a buffer dict is finished, the buffers by set)
+    if rq.diagnostics:
+        summaries.append(("diagnostics", lambda v: series_diag_finish(v, mcmc_keep, rq.max_lag),
+                          stored(rows.ds, lambda name, m, want: series_diag_buffers(m, want))))
+    if rq.exc is not None:
+        exc, xs = rq.exc, rows.xs
+        xs.new_spec = exc["spec_new"][0]
+        shape = dict(new=(exc["T"], q))
+        if fun is not None:
+            xs.fun_spec = exc["spec_fun"][0]
+            shape["fun"] = (int(xs.fun_spec.n_thr), 1)
+        summaries.append(("excursions", excursion_finish,
+                          stored(xs, lambda name, m, want: excursion_buffers(m, *shape[name], keep_all, exc["band"], want))))
+    if rq.rank is not None:
+        rank, rs, counts = rq.rank, rows.rs, {}
+        rs.new_spec, _, *counts["new"] = rank["spec_new"]
+        if fun is not None:
+            rs.fun_spec, _, *counts["fun"] = rank["spec_fun"]
+        summaries.append(("rank_diagnostics", lambda v: rank_finish(v, mcmc_keep, rank["max_lag"]),
+                          stored(rs, lambda name, m, want: rank_buffers(m, *counts[name], want))))
+
+    def result():
+        names, code = [], 1
+        while lib.st_points_route_name(code) is not None:
+            if route.value & (1 << (code - 1)):
+                names.append(lib.st_points_route_name(code).decode())
+            code += 1
+        quantiles = lambda w_q, y_q: {float(x): (w_q[:, i].copy(), None if y_q is None else y_q[:, i].copy()) for i, x in enumerate(qs)}   # noqa: E731
+        new = dict(summ, route=names, quantiles=quantiles(wq, yq))
+        if new_draws:
+            new.update(draws)
+        if labels is not None:
+            new.update(groups=groups, cov=_unpack_joint(cov, groups, off))
+            if new_draws:
+                new["cond_cov"] = [_unpack_joint(ccov[:, s], groups, off) for s in range(keep_all)]
+        if fun is not None:
+            new["functionals"] = dict(fsumm, quantiles=quantiles(fwq, fyq))
+            if new_draws:
+                new["functionals"].update(fdraws)
+        if ynew is not None and mcmc_keep > 0:
+            sc.update(n_scored=int(nsc.value), n_degenerate=int(ndg.value))
+            lo_hi = (yq[:, int(np.argmin(qs))], yq[:, int(np.argmax(qs))]) if qs.size >= 2 else (None, None)
+            sc["totals"] = score_totals(sc, ynew, pmv, q, *lo_hi)
+            new["scores"] = sc
+        for key, finish, by_set in summaries:
+            for name, bufs in by_set.items() if n_new > 0 else ():
+                (new if name == "new" else new["functionals"])[key] = {k: finish(v) for k, v in bufs.items()}
+        return new
+    return result
