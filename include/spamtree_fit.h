@@ -204,22 +204,38 @@ typedef struct stm_criteria {
  * the first factorisation, st_rows_loo_accumulate on every saved iteration right after st_rows_score_accumulate.  With or without
  * criteria.  The outputs of st_rows_loo_get (n_all each; n_accumulated, n_skipped: one count each) and of st_rows_loo_totals (tot:
  * ST_ROWS_LOO_N x q; n_obs: q).  limited_tree problems are refused (ST_ERR_UNSUPPORTED). */
+typedef struct stm_loo_psis stm_loo_psis;
 typedef struct stm_loo {
   double *elpd_loo, *pit_loo, *mu_loo, *weight_ess;
   double *tot;
   int64_t *n_obs, *n_accumulated, *n_skipped;
+  const stm_loo_psis *psis;   /* NULL: the raw weights alone */
 } stm_loo;
+
+/* Pareto smoothing of the leave-one-out weights (include/spamtree_hip.h, st_rows_loo_reserve / _psis / _psis_totals / _draws): a
+ * part of loo, so it cannot be asked for without it, and no entry point of its own: a request (or stm_mcmc_loo's loo) that leaves
+ * the pointer NULL runs as before.  mcmc_keep outside 1 .. ST_PSIS_MAX_DRAWS is refused in step 1, after the criteria's refusals
+ * (ST_ERR_UNSUPPORTED).  st_rows_loo_reserve(mcmc_keep) comes right after st_rows_loo_set; the read-out after loo's in step 3:
+ * out (n_all each), tot (ST_ROWS_PSIS_N x q) and n_obs (q) of st_rows_loo_psis and st_rows_loo_psis_totals, and the stored columns
+ * t, phi, mu of st_rows_loo_draws ([mcmc_keep][n_all] each).  Any pointer may be NULL.  The chain and every other output are bit
+ * for bit those of the same request without the part. */
+struct stm_loo_psis {
+  st_psis_out out;
+  double *tot;
+  int64_t *n_obs;
+  double *t, *phi, *mu;
+};
 
 /* The request.  stm_mcmc_fit runs it in three steps whose order is part of the contract:
  *  1. Before a chain exists, the refusals; the first failing check decides the return code.  Parts of both families; then the
  *     chains' (with a text, below), diag's, exc's, rk's (each in the order given above), the point set's, the scores', the
  *     quantiles'; then the criteria's.  Then stm_create, the point set, the rows' reservation, functionals, scores, the joint
- *     layout, stm_rows_score_set, st_rows_loo_set and stm_init: every refusal of those comes before the first sweep.
+ *     layout, stm_rows_score_set, st_rows_loo_set (with loo's psis: st_rows_loo_reserve) and stm_init: every refusal of those comes before the first sweep.
  *  2. Chain after chain; on every saved iteration st_get_w, st_yhat, the points' accumulate, st_points_functionals_last,
  *     st_rows_score_accumulate and its st_summary_accumulate, st_rows_loo_accumulate, the stores' st_summary_accumulate.
  *  3. After the last chain the read-outs, each only for a part that is there and only once a draw was saved: new_cond_var from
  *     the packed blocks, the points' summaries, covariance, quantiles and routes, the functionals' summaries and quantiles, the
- *     scores, diag (rows, points, functionals), exc, rk, the criteria, loo. */
+ *     scores, diag (rows, points, functionals), exc, rk, the criteria, loo, loo's psis. */
 typedef struct stm_fit {
   stm_run run;
   const stm_new_points *pts;   /* NULL: no point set */

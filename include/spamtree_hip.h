@@ -653,7 +653,8 @@ int st_rows_score_info(st_handle h, double *alg_bytes);
  * l_s = log N(y_i; mu_s, sigma2_s), Phi_s = Phi((y_i - mu_s) / sigma_s), and over the S accumulated draws, r_s = exp(-l_s):
  *   elpd_loo_i = -log((1 / S) sum r_s)   (estimates log p(y_i | y_-i): E_post[1 / p(y_i | w_-i, theta, beta, tau2)] = 1 / p(y_i | y_-i)),
  *   pit_loo_i = sum r_s Phi_s / sum r_s,   mu_loo_i = sum r_s mu_s / sum r_s,   weight_ess_i = (sum r_s)^2 / sum r_s^2.
- * No Pareto smoothing and no k-hat: weight_ess is the diagnostic.  No leave-one-out for NA rows (pass them as new points).
+ * These are the raw weights, with weight_ess as their diagnostic; Pareto smoothing and k-hat are st_rows_loo_reserve / st_rows_loo_psis
+ * below.  No leave-one-out for NA rows (pass them as new points).
  * st_rows_loo_set: allocates and zeroes the state; st_rows_loo_clear frees it.
  * st_rows_loo_accumulate: one draw from the current w, XB, tausq_inv and slot 0 (a deferred leaf half is finished first, as
  *   st_simulate does): one launch per level from the deepest to the root.  It consumes no Philox draw, copies nothing to the host,
@@ -683,6 +684,54 @@ int st_rows_loo_get(st_handle h, double *elpd_loo, double *pit_loo, double *mu_l
 int st_rows_loo_totals(st_handle h, double *tot, int64_t *n_obs);
 int st_rows_loo_info(st_handle h, int32_t *route_mask, double *alg_bytes, double *flops);
 const char *st_rows_loo_route_name(int32_t code);
+
+/* ---- Pareto-smoothed importance sampling of the leave-one-out weights, on the device (Vehtari, Simpson, Gelman, Yao, Gabry,
+ * "Pareto smoothed importance sampling"; the generalised Pareto fit of Zhang and Stephens with the weakly informative prior of
+ * loo::gpdfit; r_eff = 1).  spamtree_amd/psis.py has the definition, spamtree_amd/csrc/psis_kernels.hpp the order the kernel
+ * evaluates it in.  A series is K log ratios t_s (the rows' own: t_s = -l_s) with optional companions Phi_s, mu_s; a draw whose t_s
+ * is not finite is skipped, S = the finite ones.  Per series: khat, the Pareto shape of the largest M = min(S / 5, ceil(3 sqrt S))
+ * ratios (+inf where nothing is smoothed: M < 5, a constant tail, a quarter of the tail tied with the cut, a fit that is not
+ * finite; the estimates are then the raw ones), and with the smoothed log weights lw'_s
+ *   elpd_psis = log(sum w_s p_s / sum w_s),  pit_psis = sum w_s Phi_s / sum w_s,  mu_psis = sum w_s mu_s / sum w_s,
+ *   weight_ess_psis = (sum w_s)^2 / sum w_s^2,  tail_len = M (0: not smoothed),  n_draws = S  (S = 0: NaN, 0, 0).
+ * st_rows_loo_reserve: after st_rows_loo_set and before the first accumulate; three [keep][n_all] device arrays (t, Phi, mu: 24 B
+ *   per row and draw), NaN until written.  Every st_rows_loo_accumulate then also writes its draw's column (NaN in all three where
+ *   the draw is skipped at a row; nothing at rows without an observed y); the streaming outputs are bit for bit the same with and
+ *   without a store.  keep = 0 releases the store.  keep outside 0 .. ST_PSIS_MAX_DRAWS: ST_ERR_UNSUPPORTED; a failed allocation
+ *   is refused with its size and leaves the handle as it was; an accumulate beyond keep is refused (ST_ERR_USAGE) before any launch.
+ * st_rows_loo_draws: the stored columns, [n_accumulated][n_all] each, model row order (the pointwise matrix).
+ * st_rows_loo_psis: the outputs of every row, n_all values each in model row order, NaN (0 for the integers) where a row has no
+ *   observed y.  st_rows_loo_psis_totals: tot is ST_ROWS_PSIS_N x q column-major over the outcome's observed rows with n_draws > 0;
+ *   N_ABOVE counts khat > min(1 - 1 / log10(n_accumulated), 0.7), N_BAD khat > 0.7 (se of elpd_psis = sqrt(n var), formed by the
+ *   caller from ELPD and ELPD_SQ).  Both need a store and one accumulate, repeat the refusals of st_rows_loo_get, are repeatable
+ *   and leave the streaming state, the store and the chain untouched.
+ * st_psis: the same kernel on the caller's host arrays t, phi, mu [K][n] (phi, mu may be NULL: pit_psis, mu_psis are then not
+ *   written), 1 <= K <= ST_PSIS_MAX_DRAWS (else ST_ERR_UNSUPPORTED); n = 0 is ST_OK with nothing written.  The handle lends its
+ *   device, stream and LDS limit only: any handle will do, limited_tree included.
+ * st_psis_info: R (series per tile), the padded length, the dynamic LDS and the algorithmic bytes (every log ratio twice, every
+ *   companion value and the outputs once) of a pass over an n x K store with n_comp companions under the handle's LDS limit.
+ * Any output pointer may be NULL. */
+#define ST_PSIS_MAX_DRAWS 16384
+#define ST_ROWS_PSIS_COUNT 0
+#define ST_ROWS_PSIS_ELPD 1
+#define ST_ROWS_PSIS_ELPD_SQ 2
+#define ST_ROWS_PSIS_SQERR 3
+#define ST_ROWS_PSIS_PIT 4
+#define ST_ROWS_PSIS_MIN_ESS 5
+#define ST_ROWS_PSIS_MAX_KHAT 6
+#define ST_ROWS_PSIS_N_BAD 7
+#define ST_ROWS_PSIS_N_ABOVE 8
+#define ST_ROWS_PSIS_N 9
+typedef struct st_psis_out {
+  double *khat, *elpd_psis, *pit_psis, *mu_psis, *weight_ess_psis;
+  int32_t *tail_len, *n_draws;
+} st_psis_out;
+int st_rows_loo_reserve(st_handle h, int64_t keep);
+int st_rows_loo_draws(st_handle h, double *t, double *phi, double *mu);
+int st_rows_loo_psis(st_handle h, const st_psis_out *out);
+int st_rows_loo_psis_totals(st_handle h, double *tot, int64_t *n_obs);
+int st_psis(st_handle h, int64_t n, int64_t K, const double *t, const double *phi, const double *mu, const st_psis_out *out);
+int st_psis_info(st_handle h, int64_t n, int64_t K, int32_t n_comp, int32_t *R, int32_t *Kpad, int64_t *lds_bytes, double *alg_bytes);
 
 /* ---- prior simulation from slot 0: exact draws w ~ N(0, C_DAG) of the tree's own model and y = XB + w + sqrt(tau^2_j) eps.
  * st_simulate: a root-to-leaf sweep over slot 0 as the last st_factor(h, 0, theta) left it (a deferred leaf half is finished

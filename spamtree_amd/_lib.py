@@ -52,6 +52,13 @@ class StRankOut(C.Structure):         # st_rank_out: any pointer may be NULL
                 ("prob", C.POINTER(C.c_double))]
 
 
+class StPsisOut(C.Structure):         # st_psis_out: n values each, any pointer may be NULL
+    _fields_ = [("khat", C.POINTER(C.c_double)), ("elpd_psis", C.POINTER(C.c_double)), ("pit_psis", C.POINTER(C.c_double)),
+                ("mu_psis", C.POINTER(C.c_double)), ("weight_ess_psis", C.POINTER(C.c_double)), ("tail_len", C.POINTER(C.c_int32)),
+                ("n_draws", C.POINTER(C.c_int32))]
+
+
+ST_PSIS_MAX_DRAWS = 16384
 ST_EXC_MAX_THRESHOLDS = 8
 ST_RANK_MAX_PROBS = 8
 ST_DIAG_MIN_DRAWS = 4
@@ -182,6 +189,12 @@ SIGNATURES = {
     "st_rows_loo_totals": (C.c_int, [H, c_dp, c_ip]),
     "st_rows_loo_info": (C.c_int, [H, C.POINTER(C.c_int32), c_dp, c_dp]),
     "st_rows_loo_route_name": (C.c_char_p, [C.c_int32]),
+    "st_rows_loo_reserve": (C.c_int, [H, C.c_int64]),
+    "st_rows_loo_draws": (C.c_int, [H, c_dp, c_dp, c_dp]),
+    "st_rows_loo_psis": (C.c_int, [H, C.POINTER(StPsisOut)]),
+    "st_rows_loo_psis_totals": (C.c_int, [H, c_dp, c_ip]),
+    "st_psis": (C.c_int, [H, C.c_int64, C.c_int64, c_dp, c_dp, c_dp, C.POINTER(StPsisOut)]),
+    "st_psis_info": (C.c_int, [H, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_ip, c_dp]),
     "st_simulate": (C.c_int, [H, C.c_int, c_dp, c_dp, C.c_uint64, C.c_uint32, c_dp, c_dp]),
     "st_simulate_info": (C.c_int, [H, C.c_int, C.POINTER(C.c_int32), c_dp, c_dp]),
     "st_simulate_route_name": (C.c_char_p, [C.c_int32]),
@@ -214,11 +227,16 @@ class StmCriteria(C.Structure):   # include/spamtree_fit.h, stm_criteria
 ST_ROWS_OBS = ("lppd", "p_waic", "waic", "Dbar", "Dhat", "p_D", "dic")   # include/spamtree_hip.h: ST_ROWS_OBS_*, ST_ROWS_HELD_*
 ST_ROWS_HELD = ("lppd", "pit", "crps", "sqerr")
 ST_ROWS_LOO = ("elpd_loo", "looic", "sqerr", "pit", "min_weight_ess", "count")   # ST_ROWS_LOO_*
+ST_ROWS_PSIS = ("count", "elpd_psis", "elpd_psis_sq", "sqerr", "pit", "min_weight_ess", "max_khat", "n_khat_bad", "n_khat_above")   # ST_ROWS_PSIS_*
+
+
+class StmLooPsis(C.Structure):   # include/spamtree_fit.h, stm_loo_psis
+    _fields_ = [("out", StPsisOut), ("tot", c_dp), ("n_obs", c_ip), ("t", c_dp), ("phi", c_dp), ("mu", c_dp)]
 
 
 class StmLoo(C.Structure):   # include/spamtree_fit.h, stm_loo
     _fields_ = [("elpd_loo", c_dp), ("pit_loo", c_dp), ("mu_loo", c_dp), ("weight_ess", c_dp), ("tot", c_dp), ("n_obs", c_ip),
-                ("n_accumulated", c_ip), ("n_skipped", c_ip)]
+                ("n_accumulated", c_ip), ("n_skipped", c_ip), ("psis", C.POINTER(StmLooPsis))]
 
 
 class StmDiagnostics(C.Structure):   # include/spamtree_fit.h, stm_diagnostics

@@ -21,9 +21,14 @@ __device__ __forceinline__ void loo_row(const LooArgs &A, long long i, double wi
   const double sig = sqrt(v + 1.0 / A.tsq_inv[A.mv[i]]);
   const double z = (A.y[i] - mu) / sig;
   const double l = fma(-0.5 * z, z, -log(sig)) + HL2PI;
-  if (!(l >= -__DBL_MAX__ && l <= __DBL_MAX__)) { A.acc[LOO_NS * n + i] += 1.0; return; }
+  if (!(l >= -__DBL_MAX__ && l <= __DBL_MAX__)) {
+    A.acc[LOO_NS * n + i] += 1.0;
+    if (A.st_t) { const double nan = __builtin_nan(""); A.st_t[i] = nan; A.st_phi[i] = nan; A.st_mu[i] = nan; }
+    return;
+  }
   const double phi = 0.5 * erfc(-z * 0.70710678118654752440);
   const double t = -l;
+  if (A.st_t) { A.st_t[i] = t; A.st_phi[i] = phi; A.st_mu[i] = mu; }
   double M = A.acc[LOO_M * n + i], A1 = A.acc[LOO_A1 * n + i], A2 = A.acc[LOO_A2 * n + i], AP = A.acc[LOO_AP * n + i],
          AM = A.acc[LOO_AM * n + i];
   if (A1 == 0.0) { M = t; A1 = 1.0; A2 = 1.0; AP = phi; AM = mu; }

@@ -15,8 +15,10 @@
 // OVER THE S DRAWS, with weights r_s = exp(-l_s):
 //   elpd_loo = -log((1/S) sum r_s),  pit_loo = sum r_s Phi_s / sum r_s,  mu_loo = sum r_s mu_s / sum r_s,
 //   weight_ess = (sum r_s)^2 / sum r_s^2.
-// E_post[1 / p(y_i | w_-i, theta, beta, tau2)] = 1 / p(y_i | y_-i), so elpd_loo estimates log p(y_i | y_-i).  No Pareto smoothing:
-// weight_ess is the diagnostic.
+// E_post[1 / p(y_i | w_-i, theta, beta, tau2)] = 1 / p(y_i | y_-i), so elpd_loo estimates log p(y_i | y_-i).  These are the raw
+// weights, with weight_ess as their diagnostic; with a store reserved (st_rows_loo_reserve) every draw's (t, Phi, mu) is kept as
+// well -- NaN in all three where the draw is skipped -- and psis_kernels.hpp smooths the tail and gives khat.  The store changes
+// nothing of what is described here.
 //
 // STREAMING STATE, LOO_NACC arrays of n doubles in device row order, all zero = no draw yet.  With t = -l_s:
 //   no draw yet (A1 == 0):  M = t;  A1 = 1;  A2 = 1;  AP = Phi;  AM = mu
@@ -97,6 +99,7 @@ struct LooArgs {
   double *last;                  // LOO_NLAST x n
   double *acc;                   // LOO_NACC x n
   long long n;
+  double *st_t, *st_phi, *st_mu; // this draw's column of st_rows_loo_reserve's store (n each), or all NULL: no store
 };
 
 struct LooFinishArgs {

@@ -694,6 +694,10 @@ extern "C" int stm_mcmc_fit(const stm_fit *fit) {
   if (cr && cr->crps && !crps) return ST_ERR_USAGE;
   if (crps && mcmc_keep > 16384) return ST_ERR_UNSUPPORTED;   // st_summary_reserve's limit
   if (cr && cr->y_holdout && r.flags && (!r.flags->sample_predicts || !r.flags->sample_w)) return ST_ERR_USAGE;   // the NA rows' w would be stale
+  const stm_loo_psis *const psis = loo ? loo->psis : nullptr;
+  if (psis && (mcmc_keep < 1 || mcmc_keep > ST_PSIS_MAX_DRAWS))   // st_rows_loo_reserve's limits
+    return chains_refuse(ST_ERR_UNSUPPORTED, "stm_mcmc_fit: psis keeps every saved draw, mcmc_keep = " + std::to_string(mcmc_keep) + " must lie in 1 .. " +
+                                                 std::to_string(ST_PSIS_MAX_DRAWS));
 
   // the chain and what it is given before its first factorisation: every refusal of these comes before stm_init
   const auto chain_seed = [&](int cn) { return ch ? ch->seeds[cn] : r.seed; };
@@ -719,6 +723,7 @@ extern "C" int stm_mcmc_fit(const stm_fit *fit) {
   }
   if (rc == 0 && cr) rc = stm_rows_score_set(c, cr->y_holdout);
   if (rc == 0 && loo) rc = st_rows_loo_set(c->h);   // (limited_tree is refused)
+  if (rc == 0 && psis) rc = st_rows_loo_reserve(c->h, mcmc_keep);
   if (rc == 0) rc = stm_init(c);
   if (rc != 0) { stm_destroy(c); return rc; }
   double *const new_cond_var = p.new_cond_var;
@@ -784,6 +789,11 @@ extern "C" int stm_mcmc_fit(const stm_fit *fit) {
   if (rc == 0 && loo && saved) {
     rc = st_rows_loo_get(c->h, loo->elpd_loo, loo->pit_loo, loo->mu_loo, loo->weight_ess, loo->n_accumulated, loo->n_skipped);
     if (rc == 0) rc = st_rows_loo_totals(c->h, loo->tot, loo->n_obs);
+  }
+  if (rc == 0 && psis && saved) {
+    rc = st_rows_loo_psis(c->h, &psis->out);
+    if (rc == 0) rc = st_rows_loo_psis_totals(c->h, psis->tot, psis->n_obs);
+    if (rc == 0 && (psis->t || psis->phi || psis->mu)) rc = st_rows_loo_draws(c->h, psis->t, psis->phi, psis->mu);
   }
   stm_destroy(c);
   return rc;

@@ -1897,6 +1897,8 @@ static int loo_refuse(st_handle h, const char *who, bool need_set = true, bool n
 static void loo_free(st_handle h) {
   h->d_loo_list.free(); h->d_loo_chptr.free(); h->d_loo_chidx.free(); h->d_loo_voff.free(); h->d_loo_S.free(); h->d_loo_last.free();
   h->d_loo_acc.free(); h->d_loo_rows.free(); h->d_loo_tot.free();
+  h->d_loo_store.free(); h->d_psis_rows.free(); h->d_psis_tot.free(); h->d_psis_int.free();
+  h->loo_keep = 0; h->psis_fin_acc = -1;
   h->loo_levels.clear();
   h->loo_set = false; h->loo_n_acc = 0; h->loo_fin_acc = -1; h->loo_mask = 0; h->loo_bytes = h->loo_flops = 0;
 }
@@ -1954,6 +1956,7 @@ extern "C" int st_rows_loo_accumulate(st_handle h) {
   if (h->theta[0].empty()) { h->err = "st_rows_loo_accumulate before st_factor(slot 0)"; return ST_ERR_USAGE; }
   for (const LooLevelLaunch &L : h->loo_levels)
     if (LOO_LDS(L.maxLen, L.maxM) > h->lds_limit) { h->err = "st_rows_loo_accumulate: a chain too long for the kernel's LDS"; return ST_ERR_UNSUPPORTED; }
+  if (const int rc = psis_check_column("st_rows_loo_accumulate", h->loo_n_acc, h->loo_keep, h->err)) return rc;
   HCHK(h, hipSetDevice(h->device));
   if (const int rc = settle_top(h)) return rc;
   if (const int rc = complete_leaf(h, 0)) return rc;
@@ -1964,6 +1967,10 @@ extern "C" int st_rows_loo_accumulate(st_handle h) {
   A.w = h->d_w.p; A.xb = h->d_xb.p; A.y = h->d_y.p; A.tsq_inv = h->d_tsq.p; A.obs = h->d_obs.p; A.mv = h->d_mv.p;
   A.voff = h->d_loo_voff.p; A.ch_ptr = h->d_loo_chptr.p; A.ch_idx = h->d_loo_chidx.p;
   A.S = h->d_loo_S.p; A.last = h->d_loo_last.p; A.acc = h->d_loo_acc.p; A.n = h->n_all;
+  if (h->loo_keep) {   // this draw's column of the store
+    const size_t plane = (size_t)h->loo_keep * h->n_all, col = (size_t)h->loo_n_acc * h->n_all;
+    A.st_t = h->d_loo_store.p + col; A.st_phi = h->d_loo_store.p + plane + col; A.st_mu = h->d_loo_store.p + 2 * plane + col;
+  }
   int mask = 0;
   const int e = loo_launch(h->loo_levels.data(), (int)h->loo_levels.size(), A, h->stream, &mask);
   if (e) { h->err = std::string("st_rows_loo_accumulate launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
@@ -2045,6 +2052,161 @@ extern "C" int st_rows_loo_info(st_handle h, int32_t *route_mask, double *alg_by
   return ST_OK;
 }
 extern "C" const char *st_rows_loo_route_name(int32_t code) { return loo_route_name(code); }
+
+// ---- Pareto smoothing of the stored leave-one-out ratios (psis_kernels.hpp; the kernels and their launchers live in k_psis.hip) ----
+extern "C" int st_rows_loo_reserve(st_handle h, int64_t keep) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = loo_refuse(h, "st_rows_loo_reserve")) return rc;
+  if (h->loo_n_acc > 0) { h->err = "st_rows_loo_reserve after " + std::to_string(h->loo_n_acc) + " accumulated iterations (reserve right after st_rows_loo_set)"; return ST_ERR_USAGE; }
+  if (keep != 0)
+    if (const int rc = psis_check_draws("st_rows_loo_reserve", "keep", keep, h->err)) return rc;
+  HCHK(h, hipSetDevice(h->device));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  if (keep == 0) {
+    h->d_loo_store.free(); h->d_psis_rows.free(); h->d_psis_tot.free(); h->d_psis_int.free();
+    h->loo_keep = 0; h->psis_fin_acc = -1;
+    return ST_OK;
+  }
+  const size_t n = (size_t)h->n_all, cnt = 3 * (size_t)keep * n;
+  DevBuf<double> d_store, d_rows, d_tot;   // the handle takes them once every allocation has succeeded
+  DevBuf<int> d_int;
+  if (d_store.alloc(cnt) != hipSuccess || d_rows.alloc((size_t)PSIS_NOUT * n) != hipSuccess || d_int.alloc(2 * n) != hipSuccess ||
+      d_tot.alloc((size_t)h->q * PSIS_NSUM) != hipSuccess) {
+    (void)hipGetLastError();
+    char buf[160];
+    std::snprintf(buf, sizeof(buf), "st_rows_loo_reserve: the store of %lld draws x %lld rows (%.0f bytes) could not be allocated",
+                  (long long)keep, (long long)h->n_all, psis_store_bytes(keep, h->n_all));
+    h->err = buf;
+    return ST_ERR_HIP;
+  }
+  HCHK(h, hipMemsetAsync(d_store.p, 0xff, cnt * sizeof(double), h->stream));   // all bits set: a NaN
+  HCHK(h, hipStreamSynchronize(h->stream));
+  h->d_loo_store = std::move(d_store); h->d_psis_rows = std::move(d_rows); h->d_psis_int = std::move(d_int); h->d_psis_tot = std::move(d_tot);
+  h->loo_keep = keep; h->psis_fin_acc = -1;
+  return ST_OK;
+}
+static int psis_refuse(st_handle h, const char *who) {
+  if (const int rc = loo_refuse(h, who)) return rc;
+  if (h->loo_keep == 0) { h->err = std::string(who) + ": no store reserved (st_rows_loo_reserve before the first accumulate)"; return ST_ERR_USAGE; }
+  return loo_refuse(h, who, true, true);
+}
+extern "C" int st_rows_loo_draws(st_handle h, double *t, double *phi, double *mu) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = psis_refuse(h, "st_rows_loo_draws")) return rc;
+  HCHK(h, hipSetDevice(h->device));
+  double *const dst[3] = {t, phi, mu};
+  const size_t n = (size_t)h->n_all, plane = (size_t)h->loo_keep * n;
+  for (int k = 0; k < 3; ++k)
+    if (dst[k])
+      for (long long d = 0; d < h->loo_n_acc; ++d)
+        if (const int rc = download_rows(h, h->d_loo_store.p + k * plane + (size_t)d * n, dst[k] + (size_t)d * n)) return rc;
+  return ST_OK;
+}
+// one pass of k_loo_psis over a [K][n] device store into device outputs (PSIS_NOUT x n doubles; tail_len, n_draws: n each)
+static int psis_run(st_handle h, const char *who, long long n, long long K, const double *t, const double *phi, const double *mu,
+                    double *rows, int *ints) {
+  PsisArgs A = {};
+  if (!psis_plan(K, h->lds_limit, &A.R, &A.Kpad)) {
+    h->err = std::string(who) + ": the sorted copy of " + std::to_string(K) + " stored draws of one series does not fit one workgroup's LDS";
+    return ST_ERR_UNSUPPORTED;
+  }
+  A.t = t; A.phi = phi; A.mu = mu; A.n = n; A.K = (int)K; A.out = rows; A.tail_len = ints; A.n_draws = ints + n;
+  const int e = psis_launch(A, h->stream);
+  if (e) { h->err = std::string(who) + " launch: " + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+  return ST_OK;
+}
+// the rows' own outputs and totals, once per number of accumulated draws
+static int psis_finish(st_handle h, const char *who) {
+  if (h->psis_fin_acc == h->loo_n_acc) return ST_OK;
+  const size_t plane = (size_t)h->loo_keep * h->n_all;
+  if (const int rc = psis_run(h, who, h->n_all, h->loo_n_acc, h->d_loo_store.p, h->d_loo_store.p + plane, h->d_loo_store.p + 2 * plane,
+                              h->d_psis_rows.p, h->d_psis_int.p)) return rc;
+  PsisFinishArgs F = {};
+  F.y = h->d_y.p; F.obs = h->d_obs.p; F.mv = h->d_mv.p; F.rows = h->d_psis_rows.p; F.n_draws = h->d_psis_int.p + h->n_all;
+  F.n = h->n_all; F.q = h->q; F.tot = h->d_psis_tot.p;
+  F.thr = h->loo_n_acc > 1 ? std::min(1.0 - 1.0 / std::log10((double)h->loo_n_acc), 0.7) : -HUGE_VAL;
+  const int e = psis_finish_launch(F, h->stream);
+  if (e) { h->err = std::string(who) + " finish launch: " + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+  h->psis_fin_acc = h->loo_n_acc;
+  return ST_OK;
+}
+// the device outputs of a pass to the caller's arrays; perm (device row -> model row) or NULL
+static int psis_download(st_handle h, long long n, const double *rows, const int *ints, const long long *perm, const st_psis_out *out,
+                         bool have_phi, bool have_mu) {
+  if (!out || n == 0) return ST_OK;
+  double *const dst[PSIS_NOUT] = {out->khat, out->elpd_psis, have_phi ? out->pit_psis : nullptr, have_mu ? out->mu_psis : nullptr,
+                                  out->weight_ess_psis};   // PSIS_OUT_* order
+  int32_t *const idst[2] = {out->tail_len, out->n_draws};
+  std::vector<double> tmp((size_t)PSIS_NOUT * n);
+  std::vector<int> itmp(2 * (size_t)n);
+  HCHK(h, hipMemcpyAsync(tmp.data(), rows, tmp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipMemcpyAsync(itmp.data(), ints, itmp.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  for (int k = 0; k < PSIS_NOUT; ++k)
+    if (dst[k])
+      for (long long i = 0; i < n; ++i) dst[k][perm ? perm[i] : i] = tmp[(size_t)k * n + i];
+  for (int k = 0; k < 2; ++k)
+    if (idst[k])
+      for (long long i = 0; i < n; ++i) idst[k][perm ? perm[i] : i] = itmp[(size_t)k * n + i];
+  return ST_OK;
+}
+extern "C" int st_rows_loo_psis(st_handle h, const st_psis_out *out) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = psis_refuse(h, "st_rows_loo_psis")) return rc;
+  HCHK(h, hipSetDevice(h->device));
+  if (const int rc = psis_finish(h, "st_rows_loo_psis")) return rc;
+  return psis_download(h, h->n_all, h->d_psis_rows.p, h->d_psis_int.p, h->dev2model.data(), out, true, true);
+}
+extern "C" int st_rows_loo_psis_totals(st_handle h, double *tot, int64_t *n_obs) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = psis_refuse(h, "st_rows_loo_psis_totals")) return rc;
+  HCHK(h, hipSetDevice(h->device));
+  if (const int rc = psis_finish(h, "st_rows_loo_psis_totals")) return rc;
+  std::vector<double> t((size_t)h->q * PSIS_NSUM);
+  HCHK(h, hipMemcpyAsync(t.data(), h->d_psis_tot.p, t.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  for (int j = 0; j < h->q; ++j) {
+    double *s = t.data() + (size_t)j * PSIS_NSUM;
+    if (n_obs) n_obs[j] = h->loo_nobs_q[j];
+    if (s[ST_ROWS_PSIS_COUNT] == 0.0) s[ST_ROWS_PSIS_MIN_ESS] = s[ST_ROWS_PSIS_MAX_KHAT] = std::nan("");
+    if (tot) std::copy(s, s + PSIS_NSUM, tot + (size_t)j * ST_ROWS_PSIS_N);
+  }
+  return ST_OK;
+}
+extern "C" int st_psis(st_handle h, int64_t n, int64_t K, const double *t, const double *phi, const double *mu, const st_psis_out *out) {
+  if (!h) return ST_ERR_USAGE;
+  if (n < 0) { h->err = "st_psis: n = " + std::to_string(n) + " must not be negative"; return ST_ERR_USAGE; }
+  if (const int rc = psis_check_draws("st_psis", "K", K, h->err)) return rc;
+  if (n == 0) return ST_OK;
+  if (!t) { h->err = "st_psis: no log ratios"; return ST_ERR_USAGE; }
+  HCHK(h, hipSetDevice(h->device));
+  const size_t cnt = (size_t)n * K;
+  DevBuf<double> d_t, d_phi, d_mu, d_rows;
+  DevBuf<int> d_int;
+  HCHK(h, d_t.alloc(cnt)); HCHK(h, d_rows.alloc((size_t)PSIS_NOUT * n)); HCHK(h, d_int.alloc(2 * (size_t)n));
+  HCHK(h, hipMemcpyAsync(d_t.p, t, cnt * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (phi) { HCHK(h, d_phi.alloc(cnt)); HCHK(h, hipMemcpyAsync(d_phi.p, phi, cnt * sizeof(double), hipMemcpyHostToDevice, h->stream)); }
+  if (mu) { HCHK(h, d_mu.alloc(cnt)); HCHK(h, hipMemcpyAsync(d_mu.p, mu, cnt * sizeof(double), hipMemcpyHostToDevice, h->stream)); }
+  int rc = psis_run(h, "st_psis", n, K, d_t.p, d_phi.p, d_mu.p, d_rows.p, d_int.p);
+  if (rc == ST_OK) rc = psis_download(h, n, d_rows.p, d_int.p, nullptr, out, phi != nullptr, mu != nullptr);
+  const hipError_t es = hipStreamSynchronize(h->stream);   // the buffers go with this scope
+  if (rc == ST_OK && es != hipSuccess) { h->err = std::string("st_psis: ") + hipGetErrorString(es); rc = ST_ERR_HIP; }
+  return rc;
+}
+extern "C" int st_psis_info(st_handle h, int64_t n, int64_t K, int32_t n_comp, int32_t *R, int32_t *Kpad, int64_t *lds_bytes, double *alg_bytes) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = psis_check_draws("st_psis_info", "K", K, h->err)) return rc;
+  int r = 0, kp = 0;
+  if (!psis_plan(K, h->lds_limit, &r, &kp)) {
+    h->err = "st_psis_info: the sorted copy of " + std::to_string(K) + " stored draws of one series does not fit one workgroup's LDS";
+    return ST_ERR_UNSUPPORTED;
+  }
+  if (R) *R = r;
+  if (Kpad) *Kpad = kp;
+  if (lds_bytes) *lds_bytes = (int64_t)psis_lds_bytes(r, kp);
+  if (alg_bytes) *alg_bytes = (double)n * ((double)K * 8.0 * (2.0 + (double)std::max(0, std::min(n_comp, 2))) + 8.0 * PSIS_NOUT + 8.0);
+  return ST_OK;
+}
 
 // ---- prior simulation from slot 0 (st_simulate; the kernels and their launcher live in k_simulate.hip) ----
 static int sim_pad(int nd) { int p = 1; while (p < nd) p <<= 1; return p; }

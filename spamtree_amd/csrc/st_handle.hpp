@@ -7,6 +7,7 @@
 #include "simulate_kernels.hpp"
 #include "loo_layout.hpp"
 #include "loo_kernels.hpp"
+#include "psis_kernels.hpp"
 
 // A device allocation that frees itself; a null buffer makes no HIP call.  (The owner has the device current when it goes.)
 template <typename T>
@@ -92,6 +93,11 @@ struct st_handle_s : TreeLayout {
   int loo_mask = 0;
   long long loo_n_acc = 0, loo_fin_acc = -1;  // d_loo_rows / d_loo_tot are those of loo_fin_acc draws
   std::vector<long long> loo_nobs_q;
+  // st_rows_loo_reserve: the accumulated draws' (t, Phi, mu), [3][loo_keep][n_all] in device row order (psis_kernels.hpp), and
+  // st_rows_loo_psis' outputs of psis_fin_acc draws (PSIS_NOUT x n doubles; tail_len, n_draws; q x PSIS_NSUM totals)
+  DevBuf<double> d_loo_store, d_psis_rows, d_psis_tot;
+  DevBuf<int> d_psis_int;
+  long long loo_keep = 0, psis_fin_acc = -1;
   bool stats_valid = false;                   // d_stats matches the current w and XB
   bool host_stats_valid = false;              // ... and host_stats holds a copy of it
   std::vector<double> host_stats;

@@ -13,7 +13,7 @@ from . import _lib
 from . import diagnostics as _diag
 from . import excursions as _exc
 from .model import (SpamTreeError, _dp, _f64, _i64, _ip, _lists_to_csr, functionals_csr, joint_labels, rows_criteria, rows_holdout,
-                    rows_loo_criteria, score_totals,
+                    rows_loo_criteria, rows_psis_criteria, score_totals,
                     score_values, series_diag_buffers, series_diag_finish, excursion_spec, excursion_buffers, excursion_finish,
                     rank_spec, rank_buffers, rank_finish)
 
@@ -260,7 +260,7 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                      sample_theta=True, sample_w=True, sample_predicts=True, seed=2021, device=0, reference_quirks=True,
                      new_points=None, new_draws=True, new_quantiles=(), save_w=True, save_yhat=True, force_generic=False,
                      criteria=False, y_holdout=None, holdout_crps=True, diagnostics=False, diagnostics_max_lag=0, excursions=None,
-                     rank_diagnostics=None, chains=1, chain_seeds=None, chain_theta=None, loo=False):
+                     rank_diagnostics=None, chains=1, chain_seeds=None, chain_theta=None, loo=False, psis=False, psis_draws=False):
     """spamtree_fit.cpp:5-430 through the C++ driver.  `num_threads`, `use_alg`, the verbosity flags and `start_w` are
     accepted and ignored exactly where the reference ignores them (start_w, :95) or where they do not apply to a GPU.
 
@@ -302,7 +302,14 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     combined with ``criteria`` / ``y_holdout`` and not with what ``criteria`` excludes.  The result's ``criteria["loo"]`` holds the
     per-row arrays ``elpd_loo``, ``pit_loo``, ``mu_loo``, ``weight_ess`` (NaN where a row has no observed y), ``n_accumulated``,
     ``n_skipped`` and ``totals`` = ``model.rows_loo_criteria``'s dict, overall and by outcome (``spamtree_amd.loo`` has the
-    definition).  No Pareto smoothing: ``weight_ess`` is the diagnostic.  ValueError before any device call for ``limited_tree``.
+    definition).  These are the raw weights, with ``weight_ess`` as their diagnostic.  ValueError before any device call for
+    ``limited_tree``.
+    ``loo=True, psis=True``: the weights are also Pareto smoothed on the device (``spamtree_amd.psis`` has the definition): every
+    saved draw's log ratio, Phi and mu are kept there (24 B per row and draw), and ``criteria["loo"]["psis"]`` holds the per-row
+    arrays ``khat``, ``elpd_psis``, ``pit_psis``, ``mu_psis``, ``weight_ess_psis``, ``tail_len``, ``n_draws`` and ``totals`` =
+    ``model.rows_psis_criteria``'s dict (``se``, ``max_khat``, the counts of rows with a large khat), and with ``psis_draws=True`` the
+    pointwise matrices ``t``, ``phi``, ``mu`` (mcmc_keep x n).  The chain and every other output are the same bit for bit.
+    ValueError before any device call: ``psis`` without ``loo``, ``mcmc_keep`` outside 1 .. 16384.
     ``diagnostics=True``: the effective sample size ``ess``, the Monte-Carlo standard error of the posterior mean ``mcse``, the
     posterior sd of the draws ``sd``, the split-R-hat of the one chain ``rhat``, the lags used ``lags`` and whether the lag cap was
     hit ``truncated`` (``spamtree_amd.diagnostics`` has the definition; ``diagnostics_max_lag`` = 0 is its default cap of 1024
@@ -347,7 +354,7 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     ValueError: ``M * mcmc_keep`` > 16384, M outside 1 .. 16, together with ``criteria`` / ``y_holdout`` (a separate driver)."""
     rq = _check_request(y, X, mv_id, theta, limited_tree, mcmc_keep, sample_predicts, sample_w, seed, new_points, new_quantiles, criteria,
                         y_holdout, holdout_crps, diagnostics, diagnostics_max_lag, excursions, rank_diagnostics, chains, chain_seeds,
-                        chain_theta, loo)
+                        chain_theta, loo, psis, psis_draws)
     M, keep_all, max_lag = rq.M, rq.keep_all, rq.max_lag
     lib = _lib.load()
     pb, keep, n, p, q = _problem(y, X, coords, mv_id, res_is_ref, parents, children, layer_names, layer_gibbs_group, indexing)
@@ -452,13 +459,18 @@ def _reported_driver(rq):
 
 def _check_request(y, X, mv_id, theta, limited_tree, mcmc_keep, sample_predicts, sample_w, seed, new_points, new_quantiles, criteria,
                    y_holdout, holdout_crps, diagnostics, diagnostics_max_lag, excursions, rank_diagnostics, chains, chain_seeds, chain_theta,
-                   loo):
+                   loo, psis=False, psis_draws=False):
     """Every check of spamtree_mv_mcmc's optional parts that needs no device (ValueError), and what they normalise: the chains'
     seeds and starts, the rank and excursion specs, the held-out values of the rows, the point set."""
     crit_cond = bool(criteria) or y_holdout is not None
     loo = bool(loo)
     if loo and limited_tree:
         raise ValueError("loo: limited_tree workloads are not supported (the leave-one-out criteria need the full chain factors)")
+    psis = bool(psis) or bool(psis_draws)
+    if psis and not loo:
+        raise ValueError("psis smooths the leave-one-out weights: it needs loo=True")
+    if psis and not 1 <= int(mcmc_keep) <= _lib.ST_PSIS_MAX_DRAWS:
+        raise ValueError(f"psis: mcmc_keep = {int(mcmc_keep)} must lie in 1 .. {_lib.ST_PSIS_MAX_DRAWS} (the device keeps every saved draw's ratios)")
     crit = crit_cond or loo   # one driver: what excludes criteria excludes loo
     M = int(chains)
     if not 1 <= M <= _diag.MAX_CHAINS:
@@ -566,7 +578,7 @@ def _check_request(y, X, mv_id, theta, limited_tree, mcmc_keep, sample_predicts,
                 rank["spec_fun"] = rank_spec(rank["probs"], tf, sf, rank["max_lag"], n_fun)
         elif rank.get("thresholds_fun") is not None:
             raise ValueError("rank_diagnostics: thresholds_fun needs new_points")
-    return SimpleNamespace(crit_cond=crit_cond, loo=loo, crit=crit, M=M, keep_all=keep_all, seeds=seeds, theta0=theta0, rank=rank, exc=exc,
+    return SimpleNamespace(crit_cond=crit_cond, loo=loo, psis=psis, psis_draws=bool(psis_draws), crit=crit, M=M, keep_all=keep_all, seeds=seeds, theta0=theta0, rank=rank, exc=exc,
                            diagnostics=diagnostics, max_lag=int(diagnostics_max_lag), y_hold=y_hold, want_crps=want_crps, pts=pts)
 
 
@@ -612,6 +624,16 @@ def _row_parts(req, rq, n, q, mcmc_keep):
         lacc, lskip = C.c_int64(), C.c_int64()
         ls = _lib.StmLoo(*[_dp(lrows[key]) for key in ("elpd_loo", "pit_loo", "mu_loo", "weight_ess")], _dp(ltot), _ip(ln_obs),
                          C.pointer(lacc), C.pointer(lskip))
+        if rq.psis:
+            prow = {key: np.zeros(n) for key in ("khat", "elpd_psis", "pit_psis", "mu_psis", "weight_ess_psis")}
+            prow.update(tail_len=np.zeros(n, dtype=np.int32), n_draws=np.zeros(n, dtype=np.int32))
+            ptot, pn_obs = np.zeros((len(_lib.ST_ROWS_PSIS), q), order="F"), np.zeros(q, dtype=np.int64)
+            pdraws = {key: np.zeros((mcmc_keep, n)) for key in ("t", "phi", "mu")} if rq.psis_draws else {}
+            i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+            ps = _lib.StmLooPsis(_lib.StPsisOut(*[_dp(prow[key]) for key in ("khat", "elpd_psis", "pit_psis", "mu_psis", "weight_ess_psis")],
+                                                i32(prow["tail_len"]), i32(prow["n_draws"])), _dp(ptot), _ip(pn_obs),
+                                 *[_opt(pdraws.get(key)) for key in ("t", "phi", "mu")])
+            ls.psis = C.pointer(ps)
         req.loo = C.pointer(ls)
 
     def criteria():
@@ -620,6 +642,8 @@ def _row_parts(req, rq, n, q, mcmc_keep):
             res = dict(rows, n_accumulated=int(nacc.value), totals=rows_criteria(tobs, theld, n_obs, n_held, have_crps=rows["crps"] is not None))
         if rq.loo:
             res["loo"] = dict(lrows, n_accumulated=int(lacc.value), n_skipped=int(lskip.value), totals=rows_loo_criteria(ltot, ln_obs))
+            if rq.psis:
+                res["loo"]["psis"] = dict(prow, totals=rows_psis_criteria(ptot, pn_obs), **pdraws)
         return res
     if rq.crit:
         out.criteria = criteria

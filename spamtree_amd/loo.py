@@ -12,8 +12,9 @@ Over the S saved draws, with the weights r_s = exp(-l_s):
     weight_ess_i = (sum r_s)^2 / sum r_s^2.
 
 E_post[1 / p(y_i | w_-i, theta, beta, tausq)] = 1 / p(y_i | y_-i), so elpd_loo_i estimates the leave-one-out log predictive density
-log p(y_i | y_-i).  There is no Pareto smoothing and no k-hat: ``weight_ess`` is the diagnostic (on the checks of
-tests/test_rows_loo_cpu.py it stayed above 0.17 S).  NA rows get no leave-one-out value: they are leaves, predict them as new points.
+log p(y_i | y_-i).  These are the raw weights, with ``weight_ess`` as their diagnostic (on the checks of tests/test_rows_loo_cpu.py it
+stayed above 0.17 S); ``spamtree_amd.psis`` smooths their tail and gives k-hat from the per-draw terms the device keeps when asked
+(``draw_terms`` below: t_s = -l_s, Phi_s, mu_s).  NA rows get no leave-one-out value: they are leaves, predict them as new points.
 
 The streaming state is what the device keeps (spamtree_amd/csrc/loo_kernels.hpp gives the order of every operation there): the
 running maximum M of t_s = -l_s, A1 = sum e^(t - M), A2 = sum e^(2 (t - M)), AP = sum e^(t - M) Phi, AM = sum e^(t - M) mu, rescaled

@@ -268,6 +268,48 @@ def rows_loo_criteria(tot, n_obs):
     return out
 
 
+def rows_psis_criteria(tot, n_obs):
+    """st_rows_loo_psis_totals' table (ST_ROWS_PSIS_N x q, one column per outcome) as a dict, overall and ``by_outcome``: n (rows with
+    a value), elpd_psis, looic = -2 elpd_psis, se = sqrt(n var) of the pointwise elpd_psis (var with divisor n - 1; NaN below two
+    rows), the means mse, rmse and pit, min_weight_ess, max_khat, n_khat_bad (khat > 0.7) and n_khat_above (khat above the
+    sample-size threshold min(1 - 1 / log10 S, 0.7)).  The overall sums are the outcomes' in outcome order."""
+    tot = np.asarray(tot, dtype=np.float64).reshape(len(_lib.ST_ROWS_PSIS), -1, order="F")
+    n_obs = np.asarray(n_obs, dtype=np.int64)
+    t = {k: tot[i].copy() for i, k in enumerate(_lib.ST_ROWS_PSIS)}
+    cnt = t["count"].astype(np.int64)
+
+    def se(n, s1, s2):
+        if n < 2:
+            return float("nan")
+        var = max(s2 - s1 * s1 / n, 0.0) / (n - 1)
+        return float(np.sqrt(n * var))
+
+    sums = {}
+    for k in ("elpd_psis", "elpd_psis_sq", "sqerr", "pit", "n_khat_bad", "n_khat_above"):
+        a = 0.0
+        for v, c in zip(t[k], cnt):          # in outcome order
+            if c > 0:
+                a = a + float(v)
+        sums[k] = a
+    with np.errstate(invalid="ignore", divide="ignore"):
+        by = dict(n=cnt, n_obs=n_obs.copy(), elpd_psis=t["elpd_psis"], looic=-2.0 * t["elpd_psis"],
+                  se=np.array([se(int(c), float(a), float(b)) for c, a, b in zip(cnt, t["elpd_psis"], t["elpd_psis_sq"])]),
+                  mse=np.where(cnt > 0, t["sqerr"] / cnt, np.nan), pit=np.where(cnt > 0, t["pit"] / cnt, np.nan),
+                  min_weight_ess=t["min_weight_ess"], max_khat=t["max_khat"], n_khat_bad=t["n_khat_bad"].astype(np.int64),
+                  n_khat_above=t["n_khat_above"].astype(np.int64))
+    by["rmse"] = np.sqrt(by["mse"])
+    nn = int(cnt.sum())
+    ess = [float(v) for v, c in zip(t["min_weight_ess"], cnt) if c > 0]
+    kh = [float(v) for v, c in zip(t["max_khat"], cnt) if c > 0]
+    out = dict(n=nn, elpd_psis=sums["elpd_psis"], looic=-2.0 * sums["elpd_psis"], se=se(nn, sums["elpd_psis"], sums["elpd_psis_sq"]),
+               mse=sums["sqerr"] / nn if nn else float("nan"), pit=sums["pit"] / nn if nn else float("nan"),
+               min_weight_ess=min(ess) if ess else float("nan"), max_khat=max(kh) if kh else float("nan"),
+               n_khat_bad=int(sums["n_khat_bad"]), n_khat_above=int(sums["n_khat_above"]))
+    out["rmse"] = float(np.sqrt(out["mse"]))
+    out["by_outcome"] = by
+    return out
+
+
 def functionals_csr(A, n_points):
     """Linear functionals of the predictions at ``n_points`` points as CSR ``(ptr, idx, wt)``, checked before any device call.
     ``A``: a ``(ptr, idx, wt)`` triple (a tuple of three whose entries are not themselves (indices, weights) pairs); a dense n_fun x n_points array, whose zeros are dropped; or a list of
@@ -982,6 +1024,59 @@ class SpamTreeMV:
                 routes.append(self.lib.st_rows_loo_route_name(code).decode())
             code += 1
         return dict(routes=routes, alg_bytes=float(by.value), flops=float(fl.value))
+
+    # ---- Pareto smoothing of the leave-one-out weights (st_rows_loo_reserve / _draws / _psis*, st_psis; ``spamtree_amd.psis``)
+    def rows_loo_reserve(self, keep):
+        """Room for ``keep`` accumulated draws' (t, Phi, mu) on the device; after rows_loo_set, before the first accumulate.  0 frees."""
+        self._check(self.lib.st_rows_loo_reserve(self.h, int(keep)))
+
+    def rows_loo_draws(self, n_accumulated):
+        """dict(t, phi, mu): the stored columns, [n_accumulated][n_all] each in model row order (NaN: skipped, or no observed y)."""
+        out = {k: np.zeros((int(n_accumulated), self.n_all)) for k in ("t", "phi", "mu")}
+        self._check(self.lib.st_rows_loo_draws(self.h, _dp(out["t"]), _dp(out["phi"]), _dp(out["mu"])))
+        return out
+
+    @staticmethod
+    def _psis_out(n, pit=True, mu=True):
+        out = {k: np.zeros(n) for k in ("khat", "elpd_psis", "weight_ess_psis")}
+        if pit:
+            out["pit_psis"] = np.zeros(n)
+        if mu:
+            out["mu_psis"] = np.zeros(n)
+        out["tail_len"], out["n_draws"] = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        st = _lib.StPsisOut(_dp(out["khat"]), _dp(out["elpd_psis"]), _dp(out["pit_psis"]) if pit else None,
+                            _dp(out["mu_psis"]) if mu else None, _dp(out["weight_ess_psis"]), i32(out["tail_len"]), i32(out["n_draws"]))
+        return out, st
+
+    def rows_loo_psis(self):
+        """dict(khat, elpd_psis, pit_psis, mu_psis, weight_ess_psis, tail_len, n_draws): n_all values each, NaN / 0 off the observed rows."""
+        out, st = self._psis_out(self.n_all)
+        self._check(self.lib.st_rows_loo_psis(self.h, C.byref(st)))
+        return out
+
+    def rows_loo_psis_totals(self, raw=False):
+        """``rows_psis_criteria`` of st_rows_loo_psis_totals' table; ``raw``: (tot, n_obs) as the library returned them."""
+        tot = np.zeros((len(_lib.ST_ROWS_PSIS), self.q), order="F")
+        n_obs = np.zeros(self.q, dtype=np.int64)
+        self._check(self.lib.st_rows_loo_psis_totals(self.h, _dp(tot), _ip(n_obs)))
+        return (tot, n_obs) if raw else rows_psis_criteria(tot, n_obs)
+
+    def psis(self, t, phi=None, mu=None):
+        """st_psis on host arrays [K][n] (float64): the kernel of rows_loo_psis on the caller's log ratios and companions."""
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        K, n = t.shape
+        phi = None if phi is None else np.ascontiguousarray(phi, dtype=np.float64)
+        mu = None if mu is None else np.ascontiguousarray(mu, dtype=np.float64)
+        out, st = self._psis_out(n, phi is not None, mu is not None)
+        self._check(self.lib.st_psis(self.h, n, K, _dp(t), None if phi is None else _dp(phi), None if mu is None else _dp(mu), C.byref(st)))
+        return out
+
+    def psis_info(self, n, K, n_comp=2):
+        """dict(R, Kpad, lds_bytes, alg_bytes) of a pass of k_loo_psis over an n x K store, from shapes."""
+        r, kp, lb, by = C.c_int32(), C.c_int32(), C.c_int64(), C.c_double()
+        self._check(self.lib.st_psis_info(self.h, int(n), int(K), int(n_comp), C.byref(r), C.byref(kp), C.byref(lb), C.byref(by)))
+        return dict(R=int(r.value), Kpad=int(kp.value), lds_bytes=int(lb.value), alg_bytes=float(by.value))
 
     def points_info(self):
         """Of the last predict_points: dict(routes=[kernel names that ran], n_groups, alg_bytes, flops)."""
