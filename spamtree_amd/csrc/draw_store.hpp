@@ -1,5 +1,5 @@
 // draw_store.hpp -- one view of a store of saved draws for the summaries of the stored draws (quantiles, diagnostics, excursions,
-// rank diagnostics).  Draws are kept in three places: the fit's rows (rows_store, spamtree_hip.hip), the new points and their
+// rank diagnostics).  Draws are kept in three places: the fit's rows (rows_store, st_summary.hip), the new points and their
 // functionals (points_store, fun_store, st_points.hip).  A C-ABI entry point is one store_* call on its resolver's view.
 // No HIP header: store_spec.cpp, the pure host helpers declared at the end, is compiled and checked without a device.
 #pragma once

@@ -18,23 +18,21 @@
 // Messages to ancestors are pushed as per-ancestor (m_a x m_a, m_a) pairs and summed hierarchically through
 // direct children in a fixed order (no FP64 atomics -> bit-reproducible for any launch geometry).
 //
-// This translation unit is the HOST side: handle (st_handle.hpp), C-ABI, the device step of st_create and every launch of the
-// fit; new-point prediction (st_points_*) has its C-ABI in st_points.hip.  The launch structures the launches index are built
-// without a device call in tree_layout.cpp (the handle derives from its TreeLayout).  The kernels
-// live in one translation unit per family (k_factor_generic.hip, k_factor_mfma.hip, k_factor_quad.hip, k_factor_wide.hip,
-// k_sample.hip, k_misc.hip); the headers included here give their argument structures, launch constants and prototypes.
+// This translation unit is the HOST side: handle (st_handle.hpp) and its lifecycle, the iteration's C-ABI with every launch of
+// the fit, inspection, measurement and st_cross_covariance_ag10.  The feature families have their C-ABI and their state in host
+// units of their own: new-point prediction in st_points.hip, the criteria over the fit's rows, leave-one-out and Pareto smoothing
+// in st_rows.hip, prior simulation in st_simulate.hip, the running summaries in st_summary.hip.  tree_layout.cpp builds the launch
+// structures without a device call (the handle derives from its TreeLayout).  The kernels live in one translation unit per family
+// (k_factor_*.hip, k_sample.hip, k_misc.hip); the headers included here give their argument structures, constants and prototypes.
 
 #include "st_handle.hpp"
 #include "misc_kernels.hpp"
-#include "draw_store.hpp"
-#include "rows_score.hpp"
 #include <new>
 
 // ===============================================================================================================
 // host side
 // ===============================================================================================================
 static thread_local std::string g_create_error;
-void points_free(st_handle_s *h);   // st_points.hip: drops the handle's point set (st_destroy)
 
 // route codes (st_route_info): written by the launch sites themselves; st_route_name spells them as the source does
 enum RouteCode : int {
@@ -135,7 +133,7 @@ extern "C" int st_destroy(st_handle h) {
   if (h->pin_up) (void)hipHostFree(h->pin_up);
   for (int i = 0; i < 2; ++i) if (h->ev_up[i]) (void)hipEventDestroy(h->ev_up[i]);
   if (h->ev_factor) (void)hipEventDestroy(h->ev_factor);
-  points_free(h);
+  points_free(h); rows_free(h); loo_free(h); sim_free(h);   // the feature families' state (st_handle.hpp)
   if (h->stream && !h->ext_stream) (void)hipStreamDestroy(h->stream);
   delete h;   // the device buffers free themselves (DevBuf)
   return ST_OK;
@@ -380,7 +378,7 @@ static int upload_rows(st_handle h, const double *src, double *dst) {
   HCHK(h, hipStreamSynchronize(h->stream));
   return ST_OK;
 }
-static int download_rows(st_handle h, const double *src, double *dst) {
+int download_rows(st_handle h, const double *src, double *dst) {
   std::vector<double> tmp(h->n_all);
   HCHK(h, hipMemcpyAsync(tmp.data(), src, h->n_all * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HCHK(h, hipStreamSynchronize(h->stream));
@@ -392,13 +390,13 @@ static int download_rows(st_handle h, const double *src, double *dst) {
 // what would read or replace state that the open half is still producing is refused BEFORE it changes anything on the handle.
 // Checked at the C-ABI entry points only: the library's own compositions (st_factor = _enqueue + _finish, ...) call the inner
 // steps while neither flag is set.  slot < 0: whatever the slot.
-static int refuse_factor_open(st_handle h, const char *who, int slot = -1) {
+int refuse_factor_open(st_handle h, const char *who, int slot) {
   if (!h->factor_open || (slot >= 0 && slot != h->factor_open_slot)) return ST_OK;
   h->err = std::string(who) + " between st_factor_enqueue and st_factor_finish";
   if (slot >= 0) h->err += " on the slot being factorised";
   return ST_ERR_USAGE;
 }
-static int refuse_sweep_pending(st_handle h, const char *who) {
+int refuse_sweep_pending(st_handle h, const char *who) {
   if (!h->c_pending) return ST_OK;
   h->err = std::string(who) + " between st_sample_w_loglik_begin and st_sample_w_loglik_end";
   return ST_ERR_USAGE;
@@ -465,7 +463,7 @@ extern "C" int st_set_tausq_inv(st_handle h, const double *t) {
 }
 // readers of a slot's arena while st_factor_begin's launches may still be writing it on the second stream: order the
 // main stream behind them (top_pending stays set: the next st_factor still picks the result up)
-static int settle_top(st_handle h) {
+int settle_top(st_handle h) {
   if (h->top_pending) { HCHK(h, hipSetDevice(h->device)); HCHK(h, hipStreamWaitEvent(h->stream, h->ev_top, 0)); }
   return ST_OK;
 }
@@ -483,7 +481,7 @@ static QuadArgs quad_args(st_handle h, int grp_first, long long qr_off, int qr_w
 }
 // A slot whose leaf levels ran QM_VONLY gets its leaf panels here (QM_TFROMV, on the launch stream), before anything reads
 // them.  The time counts as phase A: the levels' launch slots (mean per phase-A launch) and the phase bracket, no launch added.
-static int complete_leaf(st_handle h, int slot) {
+int complete_leaf(st_handle h, int slot) {
   const int phys = h->slot_map[slot];
   if (!h->leaf_pending[phys]) return ST_OK;
   HCHK(h, hipSetDevice(h->device));
@@ -1039,7 +1037,7 @@ extern "C" int st_sample_w_loglik_end(st_handle h, double *loglik) {
   return landing_code(h->pin->deferred, loglik);
 }
 
-static int gen_or_upload_z(st_handle h, const double *z, uint64_t seed, uint32_t iter, unsigned stream_id, double *dst) {
+int gen_or_upload_z(st_handle h, const double *z, uint64_t seed, uint32_t iter, unsigned stream_id, double *dst) {
   if (z) return upload_rows(h, z, dst);
   {
     ProfScope ps(h, 5);
@@ -1612,725 +1610,3 @@ extern "C" int st_cross_covariance_ag10(const double *coords1, const int64_t *mv
   }
   return rc;
 }
-
-// ---- running posterior means on device: call st_summary_accumulate on every saved iteration
-extern "C" int st_summary_reset(st_handle h) {
-  if (!h) return ST_ERR_USAGE;
-  HCHK(h, hipSetDevice(h->device));
-  if (!h->d_sum_w.p) { HCHK(h, h->d_sum_w.alloc(h->n_all)); HCHK(h, h->d_sum_yhat.alloc(h->n_all)); }
-  HCHK(h, hipMemsetAsync(h->d_sum_w.p, 0, h->n_all * sizeof(double), h->stream));
-  HCHK(h, hipMemsetAsync(h->d_sum_yhat.p, 0, h->n_all * sizeof(double), h->stream));
-  h->n_summary = 0; h->n_draws = 0; h->draws_epoch += 1;
-  return ST_OK;
-}
-extern "C" int st_summary_accumulate(st_handle h, uint64_t seed, uint32_t iter) {   // yhat noise: device stream 5 (spamtree_fit.cpp:384)
-  if (!h) return ST_ERR_USAGE;
-  if (!h->d_sum_w.p) { const int rc0 = st_summary_reset(h); if (rc0) return rc0; }
-  HCHK(h, hipSetDevice(h->device));
-  int rc = gen_or_upload_z(h, nullptr, seed, iter, 5u, h->d_tmp_n.p);
-  if (rc) return rc;
-  const int grid = (int)((h->n_all + NT - 1) / NT);
-  hipLaunchKernelGGL(k_yhat, dim3(grid), dim3(NT), 0, h->stream, h->d_xb.p, h->d_w.p, h->d_tmp_n.p, h->d_mv.p, h->n_all, h->d_tsq.p, h->d_tmp_n.p);
-  hipLaunchKernelGGL(k_axpy_sum, dim3(grid), dim3(NT), 0, h->stream, h->d_sum_yhat.p, h->d_tmp_n.p, h->n_all);
-  hipLaunchKernelGGL(k_axpy_sum, dim3(grid), dim3(NT), 0, h->stream, h->d_sum_w.p, h->d_w.p, h->n_all);
-  HCHK(h, hipGetLastError());
-  if (h->n_draws < h->draws_cap) {   // keep the draw itself for the quantiles (device order, one contiguous row per draw)
-    HCHK(h, hipMemcpyAsync(h->d_draws_w.p + (size_t)h->n_draws * h->n_all, h->d_w.p, h->n_all * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    HCHK(h, hipMemcpyAsync(h->d_draws_yhat.p + (size_t)h->n_draws * h->n_all, h->d_tmp_n.p, h->n_all * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    h->n_draws += 1; h->draws_epoch += 1;
-  }
-  h->n_summary += 1;
-  return ST_OK;
-}
-extern "C" int st_summary_reserve(st_handle h, int64_t keep) {
-  if (!h || keep < 0) return ST_ERR_USAGE;
-  HCHK(h, hipSetDevice(h->device));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  h->d_draws_w.free(); h->d_draws_yhat.free();
-  h->draws_cap = 0; h->n_draws = 0; h->draws_epoch += 1;
-  if (keep == 0) return ST_OK;
-  if (keep > 16384) { h->err = "st_summary_reserve: at most 16384 saved draws (one row's draws are sorted in one workgroup's LDS)"; return ST_ERR_UNSUPPORTED; }
-  HCHK(h, h->d_draws_w.alloc((size_t)keep * h->n_all));
-  HCHK(h, h->d_draws_yhat.alloc((size_t)keep * h->n_all));
-  h->draws_cap = keep;
-  return ST_OK;
-}
-// ---- the summaries of stored draws (draw_store.hpp).  The fit's rows as a store: device row order, the domains and thresholds
-// go by outcome (d_mv), the outputs come back in model row order (dev2model)
-static DrawStore rows_store(st_handle h) {
-  DrawStore s;
-  if (!h) { s.rc = ST_ERR_USAGE; return s; }
-  s.w = h->d_draws_w.p; s.yhat = h->d_draws_yhat.p; s.n = h->n_all; s.K = h->n_draws;
-  s.d_outcome = h->d_mv.p; s.G = h->q; s.perm = h->dev2model.data(); s.d_scratch = h->d_tmp_n.p;
-  s.reserve = "st_summary_reserve";
-  return s;
-}
-// k_qtile (misc_kernels.hpp) over the stored draws of w and yhat into w_q and yhat_q (NULL: skipped), through the store's scratch
-int store_quantile(st_handle_s *h, const char *who, const DrawStore &s, double q, double *w_q, double *yhat_q) {
-  if (s.rc) return s.rc;
-  if (!(q >= 0.0 && q <= 1.0)) { h->err = std::string(who) + ": q must lie in [0, 1]"; return ST_ERR_USAGE; }
-  if (s.K == 0) { h->err = std::string(who) + ": no draw stored (call " + s.reserve + " before the saved iterations)"; return ST_ERR_USAGE; }
-  if (yhat_q && s.yhat_needs_X) { h->err = std::string(who) + ": yhat_q needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
-  HCHK(h, hipSetDevice(h->device));
-  QtArgs A;
-  A.n = s.n; A.keep = (int)s.K; A.q = q; A.out = s.d_scratch;
-  qtile_plan(s.K, &A.Kpad, &A.R);
-  const size_t lds = (size_t)A.R * A.Kpad * sizeof(double);
-  (void)hipFuncSetAttribute((const void *)k_qtile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_limit);
-  std::vector<double> tmp(s.perm ? (size_t)s.n : 0);
-  for (int which = 0; which < 2; ++which) {
-    double *dst = which ? yhat_q : w_q;
-    if (!dst) continue;
-    A.draws = which ? s.yhat : s.w;
-    hipLaunchKernelGGL(k_qtile, dim3((unsigned)((s.n + A.R - 1) / A.R)), dim3(NT), lds, h->stream, A);
-    HCHK(h, hipGetLastError());
-    HCHK(h, hipMemcpyAsync(s.perm ? tmp.data() : dst, s.d_scratch, (size_t)s.n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HCHK(h, hipStreamSynchronize(h->stream));
-    if (s.perm) scatter_rows(dst, tmp.data(), 1, s.n, s.perm);
-  }
-  return ST_OK;
-}
-extern "C" int st_summary_quantile(st_handle h, double q, double *w_q, double *yhat_q) {
-  return store_quantile(h, __func__, rows_store(h), q, w_q, yhat_q);
-}
-extern "C" int st_summary_diagnostics(st_handle h, int32_t max_lag, const st_series_diag *w, const st_series_diag *yhat) {
-  return store_diagnostics(h, __func__, rows_store(h), max_lag, w, yhat);
-}
-extern "C" int st_summary_excursions(st_handle h, const st_excursion_spec *spec, const st_excursion_out *w, const st_excursion_out *yhat) {
-  return store_excursions(h, __func__, rows_store(h), spec, w, yhat);
-}
-extern "C" int st_summary_rank_diagnostics(st_handle h, const st_rank_spec *spec, const st_rank_out *w, const st_rank_out *yhat) {
-  return store_rank_diagnostics(h, __func__, rows_store(h), spec, w, yhat);
-}
-extern "C" int st_summary_chain_diagnostics(st_handle h, int32_t n_chains, int32_t max_lag, const st_series_diag *w, const st_series_diag *yhat) {
-  return store_chain_diagnostics(h, __func__, rows_store(h), n_chains, max_lag, w, yhat);
-}
-extern "C" int st_summary_chain_rank_diagnostics(st_handle h, int32_t n_chains, const st_rank_spec *spec, const st_rank_out *w,
-                                                 const st_rank_out *yhat) {
-  return store_chain_rank_diagnostics(h, __func__, rows_store(h), n_chains, spec, w, yhat);
-}
-extern "C" int st_summary_get(st_handle h, double *w_mean, double *yhat_mean, int64_t *n_accumulated) {
-  if (!h) return ST_ERR_USAGE;
-  if (n_accumulated) *n_accumulated = h->n_summary;
-  if (h->n_summary == 0 || !h->d_sum_w.p) { h->err = "no iteration accumulated"; return ST_ERR_USAGE; }
-  HCHK(h, hipSetDevice(h->device));
-  const double inv = 1.0 / (double)h->n_summary;
-  if (w_mean) { int rc = download_rows(h, h->d_sum_w.p, w_mean); if (rc) return rc; for (long long i = 0; i < h->n_all; ++i) w_mean[i] *= inv; }
-  if (yhat_mean) { int rc = download_rows(h, h->d_sum_yhat.p, yhat_mean); if (rc) return rc; for (long long i = 0; i < h->n_all; ++i) yhat_mean[i] *= inv; }
-  return ST_OK;
-}
-
-
-// ---- criteria over the fit's own rows (rows_score.hpp; the kernels and their launchers live in k_rows_score.hip) ----
-static int rows_refuse(st_handle h, const char *who, bool need_set = true, bool need_draw = false) {
-  if (h->world > 1) { h->err = std::string(who) + ": multi-GPU handles are not supported"; return ST_ERR_UNSUPPORTED; }
-  if (need_set && !h->rs_set) { h->err = std::string(who) + " before st_rows_score_set"; return ST_ERR_USAGE; }
-  if (need_draw && h->rs_n_acc == 0) { h->err = std::string(who) + ": no iteration accumulated"; return ST_ERR_USAGE; }
-  return ST_OK;
-}
-static void rows_free(st_handle h) {
-  h->d_rs_tgt.free(); h->d_rs_hold.free(); h->d_rs_acc.free(); h->d_rs_rows.free(); h->d_rs_crps.free(); h->d_rs_partial.free();
-  h->d_rs_tot.free();
-  h->rs_set = false; h->rs_n_acc = 0; h->rs_n_tgt = 0; h->rs_n_held = 0;
-  h->rs_crps_epoch = -1; h->rs_fin_acc = -1; h->rs_fin_crps = -2;
-}
-extern "C" int st_rows_score_set(st_handle h, const double *y_holdout) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = rows_refuse(h, "st_rows_score_set", false)) return rc;
-  HCHK(h, hipSetDevice(h->device));
-  const long long n = h->n_all;
-  std::vector<double> y(n), tgt(n), hold(n);
-  std::vector<unsigned char> obs(n);
-  std::vector<int> mv(n);
-  HCHK(h, hipMemcpyAsync(y.data(), h->d_y.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HCHK(h, hipMemcpyAsync(obs.data(), h->d_obs.p, n * sizeof(unsigned char), hipMemcpyDeviceToHost, h->stream));
-  HCHK(h, hipMemcpyAsync(mv.data(), h->d_mv.p, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  // a refusal leaves the previous state in place: every check comes before the first change
-  for (long long r = 0; y_holdout && r < n; ++r) {
-    const double v = y_holdout[r];
-    if (std::isinf(v)) { h->err = "st_rows_score_set: y_holdout[" + std::to_string(r) + "] is infinite (NaN marks a row without a held-out value)"; return ST_ERR_USAGE; }
-    if (!std::isnan(v) && obs[h->model2dev[r]]) { h->err = "st_rows_score_set: y_holdout[" + std::to_string(r) + "] is finite at an observed row (held-out values belong to NA rows)"; return ST_ERR_USAGE; }
-  }
-  std::vector<long long> nobs(h->q, 0), nheld(h->q, 0);
-  long long n_tgt = 0, n_held = 0;
-  const double nan = std::nan("");
-  for (long long i = 0; i < n; ++i) {
-    const double v = y_holdout ? y_holdout[h->dev2model[i]] : nan;
-    hold[i] = obs[i] ? nan : v;
-    tgt[i] = obs[i] ? y[i] : v;
-    if (obs[i]) nobs[mv[i]]++;
-    else if (!std::isnan(v)) { nheld[mv[i]]++; ++n_held; }
-    n_tgt += !std::isnan(tgt[i]);
-  }
-  DevBuf<double> d_tgt, d_hold, d_acc, d_rows, d_crps, d_partial, d_tot;   // the handle takes them once every allocation has succeeded
-  HCHK(h, d_tgt.upload(tgt)); HCHK(h, d_hold.upload(hold));
-  HCHK(h, d_acc.alloc((size_t)RS_NACC * n)); HCHK(h, d_rows.alloc((size_t)RS_NOUT * n)); HCHK(h, d_crps.alloc((size_t)n));
-  HCHK(h, d_partial.alloc((size_t)STATS_WG * h->q * RS_NSUM)); HCHK(h, d_tot.alloc((size_t)h->q * RS_NSUM));
-  HCHK(h, hipMemsetAsync(d_acc.p, 0, (size_t)RS_NACC * n * sizeof(double), h->stream));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  h->d_rs_tgt = std::move(d_tgt); h->d_rs_hold = std::move(d_hold); h->d_rs_acc = std::move(d_acc); h->d_rs_rows = std::move(d_rows);
-  h->d_rs_crps = std::move(d_crps); h->d_rs_partial = std::move(d_partial); h->d_rs_tot = std::move(d_tot);
-  h->rs_nobs_q = nobs; h->rs_nheld_q = nheld;
-  h->rs_n_tgt = n_tgt; h->rs_n_held = n_held; h->rs_n_acc = 0; h->rs_set = true;
-  h->rs_crps_epoch = -1; h->rs_fin_acc = -1; h->rs_fin_crps = -2;
-  for (int j = 0; j < QMAX; ++j) h->rs_tau2_sum[j] = 0.0;
-  return ST_OK;
-}
-extern "C" int st_rows_score_clear(st_handle h) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = rows_refuse(h, "st_rows_score_clear", false)) return rc;
-  HCHK(h, hipSetDevice(h->device));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  rows_free(h);
-  return ST_OK;
-}
-extern "C" int st_rows_score_accumulate(st_handle h) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = rows_refuse(h, "st_rows_score_accumulate")) return rc;
-  HCHK(h, hipSetDevice(h->device));
-  RowsScoreArgs A;
-  A.tgt = h->d_rs_tgt.p; A.obs = h->d_obs.p; A.xb = h->d_xb.p; A.w = h->d_w.p; A.tsq_inv = h->d_tsq.p; A.mv = h->d_mv.p;
-  A.n = h->n_all; A.S = (double)(h->rs_n_acc + 1); A.acc = h->d_rs_acc.p;
-  const int e = rows_score_launch(A, h->stream);
-  if (e) { h->err = std::string("st_rows_score_accumulate launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
-  for (int j = 0; j < h->q; ++j) h->rs_tau2_sum[j] += 1.0 / h->tausq_inv[j];
-  h->rs_n_acc += 1;
-  return ST_OK;
-}
-// The per-row outputs and the sums, enqueued on the handle's stream; with need_crps (and draws stored, and a held-out row) first
-// the CRPS of the held-out rows.  Each is computed once per state: the CRPS per epoch of the stored draws, the outputs and sums per
-// (draws accumulated, CRPS summed), so st_rows_score_get followed by st_rows_score_totals sorts the draws once.
-static int rows_finish(st_handle h, bool need_crps, bool *have_crps) {
-  const bool can = h->n_draws > 0 && h->rs_n_held > 0;
-  if (need_crps && can && h->rs_crps_epoch != h->draws_epoch) {
-    ScoreCrpsArgs C;
-    C.draws = h->d_draws_yhat.p; C.y = h->d_rs_hold.p; C.n = h->n_all; C.keep = (int)h->n_draws;
-    qtile_plan(h->n_draws, &C.Kpad, &C.R);
-    C.out = h->d_rs_crps.p;
-    const int e = points_score_crps_launch(C, h->lds_limit, h->stream);
-    if (e) { h->err = std::string("st_rows_score crps launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
-    h->rs_crps_epoch = h->draws_epoch;
-  }
-  *have_crps = can && h->rs_crps_epoch == h->draws_epoch;
-  const long long with = *have_crps ? h->draws_epoch : -1;
-  if (h->rs_fin_acc == h->rs_n_acc && h->rs_fin_crps == with) return ST_OK;
-  RowsTotalsArgs T;
-  T.tgt = h->d_rs_tgt.p; T.obs = h->d_obs.p; T.mv = h->d_mv.p; T.acc = h->d_rs_acc.p; T.crps = *have_crps ? h->d_rs_crps.p : nullptr;
-  T.n = h->n_all; T.S = (double)h->rs_n_acc; T.rows = h->d_rs_rows.p; T.partial = h->d_rs_partial.p;
-  for (int j = 0; j < QMAX; ++j) T.tau2bar[j] = j < h->q ? h->rs_tau2_sum[j] / (double)h->rs_n_acc : 1.0;
-  const int e = rows_score_totals_launch(T, h->q, h->d_rs_tot.p, h->stream);
-  if (e) { h->err = std::string("st_rows_score totals launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
-  h->rs_fin_acc = h->rs_n_acc; h->rs_fin_crps = with;
-  return ST_OK;
-}
-extern "C" int st_rows_score_get(st_handle h, double *lppd, double *p_waic, double *mean_ll, double *mu_mean, double *pit, double *crps,
-                                 int64_t *n_accumulated) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = rows_refuse(h, "st_rows_score_get")) return rc;
-  if (n_accumulated) *n_accumulated = h->rs_n_acc;
-  if (const int rc = rows_refuse(h, "st_rows_score_get", true, true)) return rc;
-  if (crps && h->n_draws == 0) { h->err = "st_rows_score_get: crps needs a stored draw (st_summary_reserve before the st_summary_accumulate calls)"; return ST_ERR_USAGE; }
-  HCHK(h, hipSetDevice(h->device));
-  bool have_crps = false;
-  if (const int rc = rows_finish(h, crps != nullptr, &have_crps)) return rc;
-  double *const dst[RS_NOUT] = {lppd, mean_ll, p_waic, mu_mean, pit};   // RS_OUT_* order
-  for (int k = 0; k < RS_NOUT; ++k)
-    if (dst[k])
-      if (const int rc = download_rows(h, h->d_rs_rows.p + (size_t)k * h->n_all, dst[k])) return rc;
-  if (crps) {
-    if (have_crps) { if (const int rc = download_rows(h, h->d_rs_crps.p, crps)) return rc; }
-    else for (long long i = 0; i < h->n_all; ++i) crps[i] = std::nan("");   // (no held-out row)
-  }
-  return ST_OK;
-}
-extern "C" int st_rows_score_totals(st_handle h, double *obs, double *held, int64_t *n_obs, int64_t *n_held) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = rows_refuse(h, "st_rows_score_totals", true, true)) return rc;
-  HCHK(h, hipSetDevice(h->device));
-  bool have_crps = false;
-  if (const int rc = rows_finish(h, held != nullptr, &have_crps)) return rc;
-  std::vector<double> t((size_t)h->q * RS_NSUM);
-  HCHK(h, hipMemcpyAsync(t.data(), h->d_rs_tot.p, t.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  for (int j = 0; j < h->q; ++j) {
-    const double *s = t.data() + (size_t)j * RS_NSUM;
-    if (n_obs) n_obs[j] = h->rs_nobs_q[j];
-    if (n_held) n_held[j] = h->rs_nheld_q[j];
-    if (obs) {
-      double *o = obs + (size_t)j * ST_ROWS_OBS_N;
-      o[ST_ROWS_OBS_LPPD] = s[RS_SUM_O_LPPD];
-      o[ST_ROWS_OBS_P_WAIC] = s[RS_SUM_O_PWAIC];
-      o[ST_ROWS_OBS_WAIC] = -2.0 * (o[ST_ROWS_OBS_LPPD] - o[ST_ROWS_OBS_P_WAIC]);
-      o[ST_ROWS_OBS_DBAR] = -2.0 * s[RS_SUM_O_MEANLL];
-      o[ST_ROWS_OBS_DHAT] = -2.0 * s[RS_SUM_O_LOGN];
-      o[ST_ROWS_OBS_P_D] = o[ST_ROWS_OBS_DBAR] - o[ST_ROWS_OBS_DHAT];
-      o[ST_ROWS_OBS_DIC] = o[ST_ROWS_OBS_DBAR] + o[ST_ROWS_OBS_P_D];
-      if (h->rs_nobs_q[j] == 0) for (int k = 0; k < ST_ROWS_OBS_N; ++k) o[k] = 0.0;   // (not -0)
-    }
-    if (held) {
-      double *o = held + (size_t)j * ST_ROWS_HELD_N;
-      o[ST_ROWS_HELD_LPPD] = s[RS_SUM_H_LPPD];
-      o[ST_ROWS_HELD_PIT] = s[RS_SUM_H_PIT];
-      o[ST_ROWS_HELD_CRPS] = s[RS_SUM_H_CRPS];
-      o[ST_ROWS_HELD_SQERR] = s[RS_SUM_H_SQERR];
-    }
-  }
-  return ST_OK;
-}
-// from shapes: every row reads its target; a targeted row also obs, mv, xb, w (21 B) and reads and writes five doubles of
-// state, a held-out row six
-extern "C" int st_rows_score_info(st_handle h, double *alg_bytes) {
-  if (!h || !alg_bytes) return ST_ERR_USAGE;
-  *alg_bytes = h->rs_set ? 8.0 * (double)h->n_all + (21.0 + 80.0) * (double)h->rs_n_tgt + 16.0 * (double)h->rs_n_held : 0.0;
-  return ST_OK;
-}
-
-// ---- leave-one-out criteria with w_i integrated out (loo_kernels.hpp; the kernels and their launchers live in k_rows_loo.hip) ----
-static int loo_refuse(st_handle h, const char *who, bool need_set = true, bool need_draw = false) {
-  if (h->limited) { h->err = std::string(who) + ": limited_tree handles are not supported"; return ST_ERR_UNSUPPORTED; }
-  if (h->world > 1) { h->err = std::string(who) + ": multi-GPU handles are not supported"; return ST_ERR_UNSUPPORTED; }
-  if (need_set && !h->loo_set) { h->err = std::string(who) + " before st_rows_loo_set"; return ST_ERR_USAGE; }
-  if (need_draw && h->loo_n_acc == 0) { h->err = std::string(who) + ": no iteration accumulated"; return ST_ERR_USAGE; }
-  return ST_OK;
-}
-static void loo_free(st_handle h) {
-  h->d_loo_list.free(); h->d_loo_chptr.free(); h->d_loo_chidx.free(); h->d_loo_voff.free(); h->d_loo_S.free(); h->d_loo_last.free();
-  h->d_loo_acc.free(); h->d_loo_rows.free(); h->d_loo_tot.free();
-  h->d_loo_store.free(); h->d_psis_rows.free(); h->d_psis_tot.free(); h->d_psis_int.free();
-  h->loo_keep = 0; h->psis_fin_acc = -1;
-  h->loo_levels.clear();
-  h->loo_set = false; h->loo_n_acc = 0; h->loo_fin_acc = -1; h->loo_mask = 0; h->loo_bytes = h->loo_flops = 0;
-}
-extern "C" int st_rows_loo_set(st_handle h) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = loo_refuse(h, "st_rows_loo_set", false)) return rc;
-  LooLayout lay;
-  std::string msg;
-  if (const int rc = loo_layout(*h, lay, msg)) { h->err = "st_rows_loo_set: " + msg; return rc; }
-  HCHK(h, hipSetDevice(h->device));
-  const long long n = h->n_all;
-  std::vector<unsigned char> obs(n);
-  std::vector<int> mv(n);
-  HCHK(h, hipMemcpyAsync(obs.data(), h->d_obs.p, n * sizeof(unsigned char), hipMemcpyDeviceToHost, h->stream));
-  HCHK(h, hipMemcpyAsync(mv.data(), h->d_mv.p, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  std::vector<long long> nobs(h->q, 0);
-  for (long long i = 0; i < n; ++i) if (obs[i]) nobs[mv[i]]++;
-  DevBuf<int> d_list, d_chptr, d_chidx;   // the handle takes them once every allocation has succeeded
-  DevBuf<long long> d_voff;
-  DevBuf<double> d_S, d_last, d_acc, d_rows, d_tot;
-  HCHK(h, upload_or_dummy(d_list, lay.list)); HCHK(h, d_chptr.upload(lay.ch_ptr)); HCHK(h, upload_or_dummy(d_chidx, lay.ch_idx));
-  HCHK(h, d_voff.upload(lay.voff));
-  HCHK(h, d_S.alloc((size_t)std::max(lay.arena, 1ll)));
-  HCHK(h, d_last.upload(std::vector<double>((size_t)LOO_NLAST * n, std::nan(""))));
-  HCHK(h, d_acc.alloc((size_t)LOO_NACC * n)); HCHK(h, d_rows.alloc((size_t)LOO_NOUT * n)); HCHK(h, d_tot.alloc((size_t)h->q * LOO_NSUM));
-  HCHK(h, hipMemsetAsync(d_acc.p, 0, (size_t)LOO_NACC * n * sizeof(double), h->stream));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  loo_free(h);
-  h->d_loo_list = std::move(d_list); h->d_loo_chptr = std::move(d_chptr); h->d_loo_chidx = std::move(d_chidx);
-  h->d_loo_voff = std::move(d_voff); h->d_loo_S = std::move(d_S); h->d_loo_last = std::move(d_last); h->d_loo_acc = std::move(d_acc);
-  h->d_loo_rows = std::move(d_rows); h->d_loo_tot = std::move(d_tot);
-  for (const LooLevel &V : lay.levels) {
-    h->loo_levels.push_back(LooLevelLaunch{V.first, V.count, V.isref, V.maxLen, V.maxM});
-    h->loo_mask |= 1 << ((V.isref ? LOO_ROUTE_REF : LOO_ROUTE_LEAF) - 1);
-  }
-  h->loo_bytes = lay.alg_bytes; h->loo_flops = lay.flops;
-  h->loo_nobs_q = nobs;
-  h->loo_set = true;
-  return ST_OK;
-}
-extern "C" int st_rows_loo_clear(st_handle h) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = loo_refuse(h, "st_rows_loo_clear")) return rc;
-  HCHK(h, hipSetDevice(h->device));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  loo_free(h);
-  return ST_OK;
-}
-extern "C" int st_rows_loo_accumulate(st_handle h) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = loo_refuse(h, "st_rows_loo_accumulate")) return rc;
-  if (const int rc = refuse_factor_open(h, "st_rows_loo_accumulate", 0)) return rc;
-  if (const int rc = refuse_sweep_pending(h, "st_rows_loo_accumulate")) return rc;
-  if (h->theta[0].empty()) { h->err = "st_rows_loo_accumulate before st_factor(slot 0)"; return ST_ERR_USAGE; }
-  for (const LooLevelLaunch &L : h->loo_levels)
-    if (LOO_LDS(L.maxLen, L.maxM) > h->lds_limit) { h->err = "st_rows_loo_accumulate: a chain too long for the kernel's LDS"; return ST_ERR_UNSUPPORTED; }
-  if (const int rc = psis_check_column("st_rows_loo_accumulate", h->loo_n_acc, h->loo_keep, h->err)) return rc;
-  HCHK(h, hipSetDevice(h->device));
-  if (const int rc = settle_top(h)) return rc;
-  if (const int rc = complete_leaf(h, 0)) return rc;
-  LooArgs A;
-  std::memset(&A, 0, sizeof(A));
-  A.blks = h->d_blks.p; A.anc_idx = h->d_anc.p; A.list = h->d_loo_list.p;
-  A.panels = h->d_panels[h->slot_map[0]].p;
-  A.w = h->d_w.p; A.xb = h->d_xb.p; A.y = h->d_y.p; A.tsq_inv = h->d_tsq.p; A.obs = h->d_obs.p; A.mv = h->d_mv.p;
-  A.voff = h->d_loo_voff.p; A.ch_ptr = h->d_loo_chptr.p; A.ch_idx = h->d_loo_chidx.p;
-  A.S = h->d_loo_S.p; A.last = h->d_loo_last.p; A.acc = h->d_loo_acc.p; A.n = h->n_all;
-  if (h->loo_keep) {   // this draw's column of the store
-    const size_t plane = (size_t)h->loo_keep * h->n_all, col = (size_t)h->loo_n_acc * h->n_all;
-    A.st_t = h->d_loo_store.p + col; A.st_phi = h->d_loo_store.p + plane + col; A.st_mu = h->d_loo_store.p + 2 * plane + col;
-  }
-  int mask = 0;
-  const int e = loo_launch(h->loo_levels.data(), (int)h->loo_levels.size(), A, h->stream, &mask);
-  if (e) { h->err = std::string("st_rows_loo_accumulate launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
-  h->loo_n_acc += 1;
-  return ST_OK;
-}
-extern "C" int st_rows_loo_last(st_handle h, double *q_diag, double *qw, double *cond_mean, double *cond_var) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = loo_refuse(h, "st_rows_loo_last", true, true)) return rc;
-  HCHK(h, hipSetDevice(h->device));
-  double *const dst[LOO_NLAST] = {q_diag, qw, cond_mean, cond_var};   // LOO_LAST_* order
-  for (int k = 0; k < LOO_NLAST; ++k)
-    if (dst[k])
-      if (const int rc = download_rows(h, h->d_loo_last.p + (size_t)k * h->n_all, dst[k])) return rc;
-  return ST_OK;
-}
-// the per-row outputs and the totals, once per number of accumulated draws
-static int loo_finish(st_handle h) {
-  if (h->loo_fin_acc == h->loo_n_acc) return ST_OK;
-  LooFinishArgs F;
-  F.y = h->d_y.p; F.obs = h->d_obs.p; F.mv = h->d_mv.p; F.acc = h->d_loo_acc.p; F.n = h->n_all; F.S = (double)h->loo_n_acc; F.q = h->q;
-  F.rows = h->d_loo_rows.p; F.tot = h->d_loo_tot.p;
-  const int e = loo_finish_launch(F, h->stream);
-  if (e) { h->err = std::string("st_rows_loo finish launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
-  h->loo_fin_acc = h->loo_n_acc;
-  return ST_OK;
-}
-extern "C" int st_rows_loo_get(st_handle h, double *elpd_loo, double *pit_loo, double *mu_loo, double *weight_ess, int64_t *n_accumulated,
-                               int64_t *n_skipped) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = loo_refuse(h, "st_rows_loo_get")) return rc;
-  if (n_accumulated) *n_accumulated = h->loo_n_acc;
-  if (const int rc = loo_refuse(h, "st_rows_loo_get", true, true)) return rc;
-  HCHK(h, hipSetDevice(h->device));
-  if (const int rc = loo_finish(h)) return rc;
-  double *const dst[LOO_NOUT] = {elpd_loo, pit_loo, mu_loo, weight_ess};   // LOO_OUT_* order
-  for (int k = 0; k < LOO_NOUT; ++k)
-    if (dst[k])
-      if (const int rc = download_rows(h, h->d_loo_rows.p + (size_t)k * h->n_all, dst[k])) return rc;
-  if (n_skipped) {
-    std::vector<double> ns(h->n_all);
-    HCHK(h, hipMemcpyAsync(ns.data(), h->d_loo_acc.p + (size_t)LOO_NS * h->n_all, h->n_all * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HCHK(h, hipStreamSynchronize(h->stream));
-    long long tot = 0;
-    for (double v : ns) tot += (long long)v;
-    *n_skipped = tot;
-  }
-  return ST_OK;
-}
-extern "C" int st_rows_loo_totals(st_handle h, double *tot, int64_t *n_obs) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = loo_refuse(h, "st_rows_loo_totals", true, true)) return rc;
-  HCHK(h, hipSetDevice(h->device));
-  if (const int rc = loo_finish(h)) return rc;
-  std::vector<double> t((size_t)h->q * LOO_NSUM);
-  HCHK(h, hipMemcpyAsync(t.data(), h->d_loo_tot.p, t.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  for (int j = 0; j < h->q; ++j) {
-    const double *s = t.data() + (size_t)j * LOO_NSUM;
-    if (n_obs) n_obs[j] = h->loo_nobs_q[j];
-    if (!tot) continue;
-    double *o = tot + (size_t)j * ST_ROWS_LOO_N;
-    o[ST_ROWS_LOO_ELPD] = s[LOO_SUM_ELPD];
-    o[ST_ROWS_LOO_LOOIC] = -2.0 * s[LOO_SUM_ELPD];
-    o[ST_ROWS_LOO_SQERR] = s[LOO_SUM_SQERR];
-    o[ST_ROWS_LOO_PIT] = s[LOO_SUM_PIT];
-    o[ST_ROWS_LOO_MIN_ESS] = s[LOO_MIN_ESS];
-    o[ST_ROWS_LOO_COUNT] = (double)h->loo_nobs_q[j];
-    if (h->loo_nobs_q[j] == 0) { o[ST_ROWS_LOO_ELPD] = o[ST_ROWS_LOO_LOOIC] = 0.0; o[ST_ROWS_LOO_MIN_ESS] = std::nan(""); }
-  }
-  return ST_OK;
-}
-extern "C" int st_rows_loo_info(st_handle h, int32_t *route_mask, double *alg_bytes, double *flops) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = loo_refuse(h, "st_rows_loo_info")) return rc;
-  if (route_mask) *route_mask = h->loo_mask;
-  if (alg_bytes) *alg_bytes = h->loo_bytes;
-  if (flops) *flops = h->loo_flops;
-  return ST_OK;
-}
-extern "C" const char *st_rows_loo_route_name(int32_t code) { return loo_route_name(code); }
-
-// ---- Pareto smoothing of the stored leave-one-out ratios (psis_kernels.hpp; the kernels and their launchers live in k_psis.hip) ----
-extern "C" int st_rows_loo_reserve(st_handle h, int64_t keep) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = loo_refuse(h, "st_rows_loo_reserve")) return rc;
-  if (h->loo_n_acc > 0) { h->err = "st_rows_loo_reserve after " + std::to_string(h->loo_n_acc) + " accumulated iterations (reserve right after st_rows_loo_set)"; return ST_ERR_USAGE; }
-  if (keep != 0)
-    if (const int rc = psis_check_draws("st_rows_loo_reserve", "keep", keep, h->err)) return rc;
-  HCHK(h, hipSetDevice(h->device));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  if (keep == 0) {
-    h->d_loo_store.free(); h->d_psis_rows.free(); h->d_psis_tot.free(); h->d_psis_int.free();
-    h->loo_keep = 0; h->psis_fin_acc = -1;
-    return ST_OK;
-  }
-  const size_t n = (size_t)h->n_all, cnt = 3 * (size_t)keep * n;
-  DevBuf<double> d_store, d_rows, d_tot;   // the handle takes them once every allocation has succeeded
-  DevBuf<int> d_int;
-  if (d_store.alloc(cnt) != hipSuccess || d_rows.alloc((size_t)PSIS_NOUT * n) != hipSuccess || d_int.alloc(2 * n) != hipSuccess ||
-      d_tot.alloc((size_t)h->q * PSIS_NSUM) != hipSuccess) {
-    (void)hipGetLastError();
-    char buf[160];
-    std::snprintf(buf, sizeof(buf), "st_rows_loo_reserve: the store of %lld draws x %lld rows (%.0f bytes) could not be allocated",
-                  (long long)keep, (long long)h->n_all, psis_store_bytes(keep, h->n_all));
-    h->err = buf;
-    return ST_ERR_HIP;
-  }
-  HCHK(h, hipMemsetAsync(d_store.p, 0xff, cnt * sizeof(double), h->stream));   // all bits set: a NaN
-  HCHK(h, hipStreamSynchronize(h->stream));
-  h->d_loo_store = std::move(d_store); h->d_psis_rows = std::move(d_rows); h->d_psis_int = std::move(d_int); h->d_psis_tot = std::move(d_tot);
-  h->loo_keep = keep; h->psis_fin_acc = -1;
-  return ST_OK;
-}
-static int psis_refuse(st_handle h, const char *who) {
-  if (const int rc = loo_refuse(h, who)) return rc;
-  if (h->loo_keep == 0) { h->err = std::string(who) + ": no store reserved (st_rows_loo_reserve before the first accumulate)"; return ST_ERR_USAGE; }
-  return loo_refuse(h, who, true, true);
-}
-extern "C" int st_rows_loo_draws(st_handle h, double *t, double *phi, double *mu) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = psis_refuse(h, "st_rows_loo_draws")) return rc;
-  HCHK(h, hipSetDevice(h->device));
-  double *const dst[3] = {t, phi, mu};
-  const size_t n = (size_t)h->n_all, plane = (size_t)h->loo_keep * n;
-  for (int k = 0; k < 3; ++k)
-    if (dst[k])
-      for (long long d = 0; d < h->loo_n_acc; ++d)
-        if (const int rc = download_rows(h, h->d_loo_store.p + k * plane + (size_t)d * n, dst[k] + (size_t)d * n)) return rc;
-  return ST_OK;
-}
-// one pass of k_loo_psis over a [K][n] device store into device outputs (PSIS_NOUT x n doubles; tail_len, n_draws: n each)
-static int psis_run(st_handle h, const char *who, long long n, long long K, const double *t, const double *phi, const double *mu,
-                    double *rows, int *ints) {
-  PsisArgs A = {};
-  if (!psis_plan(K, h->lds_limit, &A.R, &A.Kpad)) {
-    h->err = std::string(who) + ": the sorted copy of " + std::to_string(K) + " stored draws of one series does not fit one workgroup's LDS";
-    return ST_ERR_UNSUPPORTED;
-  }
-  A.t = t; A.phi = phi; A.mu = mu; A.n = n; A.K = (int)K; A.out = rows; A.tail_len = ints; A.n_draws = ints + n;
-  const int e = psis_launch(A, h->stream);
-  if (e) { h->err = std::string(who) + " launch: " + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
-  return ST_OK;
-}
-// the rows' own outputs and totals, once per number of accumulated draws
-static int psis_finish(st_handle h, const char *who) {
-  if (h->psis_fin_acc == h->loo_n_acc) return ST_OK;
-  const size_t plane = (size_t)h->loo_keep * h->n_all;
-  if (const int rc = psis_run(h, who, h->n_all, h->loo_n_acc, h->d_loo_store.p, h->d_loo_store.p + plane, h->d_loo_store.p + 2 * plane,
-                              h->d_psis_rows.p, h->d_psis_int.p)) return rc;
-  PsisFinishArgs F = {};
-  F.y = h->d_y.p; F.obs = h->d_obs.p; F.mv = h->d_mv.p; F.rows = h->d_psis_rows.p; F.n_draws = h->d_psis_int.p + h->n_all;
-  F.n = h->n_all; F.q = h->q; F.tot = h->d_psis_tot.p;
-  F.thr = h->loo_n_acc > 1 ? std::min(1.0 - 1.0 / std::log10((double)h->loo_n_acc), 0.7) : -HUGE_VAL;
-  const int e = psis_finish_launch(F, h->stream);
-  if (e) { h->err = std::string(who) + " finish launch: " + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
-  h->psis_fin_acc = h->loo_n_acc;
-  return ST_OK;
-}
-// the device outputs of a pass to the caller's arrays; perm (device row -> model row) or NULL
-static int psis_download(st_handle h, long long n, const double *rows, const int *ints, const long long *perm, const st_psis_out *out,
-                         bool have_phi, bool have_mu) {
-  if (!out || n == 0) return ST_OK;
-  double *const dst[PSIS_NOUT] = {out->khat, out->elpd_psis, have_phi ? out->pit_psis : nullptr, have_mu ? out->mu_psis : nullptr,
-                                  out->weight_ess_psis};   // PSIS_OUT_* order
-  int32_t *const idst[2] = {out->tail_len, out->n_draws};
-  std::vector<double> tmp((size_t)PSIS_NOUT * n);
-  std::vector<int> itmp(2 * (size_t)n);
-  HCHK(h, hipMemcpyAsync(tmp.data(), rows, tmp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HCHK(h, hipMemcpyAsync(itmp.data(), ints, itmp.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  for (int k = 0; k < PSIS_NOUT; ++k)
-    if (dst[k])
-      for (long long i = 0; i < n; ++i) dst[k][perm ? perm[i] : i] = tmp[(size_t)k * n + i];
-  for (int k = 0; k < 2; ++k)
-    if (idst[k])
-      for (long long i = 0; i < n; ++i) idst[k][perm ? perm[i] : i] = itmp[(size_t)k * n + i];
-  return ST_OK;
-}
-extern "C" int st_rows_loo_psis(st_handle h, const st_psis_out *out) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = psis_refuse(h, "st_rows_loo_psis")) return rc;
-  HCHK(h, hipSetDevice(h->device));
-  if (const int rc = psis_finish(h, "st_rows_loo_psis")) return rc;
-  return psis_download(h, h->n_all, h->d_psis_rows.p, h->d_psis_int.p, h->dev2model.data(), out, true, true);
-}
-extern "C" int st_rows_loo_psis_totals(st_handle h, double *tot, int64_t *n_obs) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = psis_refuse(h, "st_rows_loo_psis_totals")) return rc;
-  HCHK(h, hipSetDevice(h->device));
-  if (const int rc = psis_finish(h, "st_rows_loo_psis_totals")) return rc;
-  std::vector<double> t((size_t)h->q * PSIS_NSUM);
-  HCHK(h, hipMemcpyAsync(t.data(), h->d_psis_tot.p, t.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  for (int j = 0; j < h->q; ++j) {
-    double *s = t.data() + (size_t)j * PSIS_NSUM;
-    if (n_obs) n_obs[j] = h->loo_nobs_q[j];
-    if (s[ST_ROWS_PSIS_COUNT] == 0.0) s[ST_ROWS_PSIS_MIN_ESS] = s[ST_ROWS_PSIS_MAX_KHAT] = std::nan("");
-    if (tot) std::copy(s, s + PSIS_NSUM, tot + (size_t)j * ST_ROWS_PSIS_N);
-  }
-  return ST_OK;
-}
-extern "C" int st_psis(st_handle h, int64_t n, int64_t K, const double *t, const double *phi, const double *mu, const st_psis_out *out) {
-  if (!h) return ST_ERR_USAGE;
-  if (n < 0) { h->err = "st_psis: n = " + std::to_string(n) + " must not be negative"; return ST_ERR_USAGE; }
-  if (const int rc = psis_check_draws("st_psis", "K", K, h->err)) return rc;
-  if (n == 0) return ST_OK;
-  if (!t) { h->err = "st_psis: no log ratios"; return ST_ERR_USAGE; }
-  HCHK(h, hipSetDevice(h->device));
-  const size_t cnt = (size_t)n * K;
-  DevBuf<double> d_t, d_phi, d_mu, d_rows;
-  DevBuf<int> d_int;
-  HCHK(h, d_t.alloc(cnt)); HCHK(h, d_rows.alloc((size_t)PSIS_NOUT * n)); HCHK(h, d_int.alloc(2 * (size_t)n));
-  HCHK(h, hipMemcpyAsync(d_t.p, t, cnt * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (phi) { HCHK(h, d_phi.alloc(cnt)); HCHK(h, hipMemcpyAsync(d_phi.p, phi, cnt * sizeof(double), hipMemcpyHostToDevice, h->stream)); }
-  if (mu) { HCHK(h, d_mu.alloc(cnt)); HCHK(h, hipMemcpyAsync(d_mu.p, mu, cnt * sizeof(double), hipMemcpyHostToDevice, h->stream)); }
-  int rc = psis_run(h, "st_psis", n, K, d_t.p, d_phi.p, d_mu.p, d_rows.p, d_int.p);
-  if (rc == ST_OK) rc = psis_download(h, n, d_rows.p, d_int.p, nullptr, out, phi != nullptr, mu != nullptr);
-  const hipError_t es = hipStreamSynchronize(h->stream);   // the buffers go with this scope
-  if (rc == ST_OK && es != hipSuccess) { h->err = std::string("st_psis: ") + hipGetErrorString(es); rc = ST_ERR_HIP; }
-  return rc;
-}
-extern "C" int st_psis_info(st_handle h, int64_t n, int64_t K, int32_t n_comp, int32_t *R, int32_t *Kpad, int64_t *lds_bytes, double *alg_bytes) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = psis_check_draws("st_psis_info", "K", K, h->err)) return rc;
-  int r = 0, kp = 0;
-  if (!psis_plan(K, h->lds_limit, &r, &kp)) {
-    h->err = "st_psis_info: the sorted copy of " + std::to_string(K) + " stored draws of one series does not fit one workgroup's LDS";
-    return ST_ERR_UNSUPPORTED;
-  }
-  if (R) *R = r;
-  if (Kpad) *Kpad = kp;
-  if (lds_bytes) *lds_bytes = (int64_t)psis_lds_bytes(r, kp);
-  if (alg_bytes) *alg_bytes = (double)n * ((double)K * 8.0 * (2.0 + (double)std::max(0, std::min(n_comp, 2))) + 8.0 * PSIS_NOUT + 8.0);
-  return ST_OK;
-}
-
-// ---- prior simulation from slot 0 (st_simulate; the kernels and their launcher live in k_simulate.hip) ----
-static int sim_pad(int nd) { int p = 1; while (p < nd) p <<= 1; return p; }
-
-// the sweep's levels, their routes and row ranges: a function of the tree only
-static void sim_plan(st_handle h) {
-  if (!h->sim_levels.empty()) return;
-  for (int g = 0; g < h->n_actual_groups; ++g) {
-    const LevelInfo &L = h->levels[g];
-    SimLevel S;
-    S.first = L.first; S.count = L.count; S.maxM = 0;
-    S.row_lo = LLONG_MAX; S.row_hi = 0;
-    for (int k = 0; k < L.count; ++k) {
-      const Blk &B = h->blks[h->lvl_list[L.first + k]];
-      S.maxM = std::max(S.maxM, B.m);
-      S.row_lo = std::min(S.row_lo, B.row0); S.row_hi = std::max(S.row_hi, B.row0 + B.m);
-    }
-    if (L.count == 0) S.row_lo = 0;
-    S.route = simulate_route(L.isref != 0, S.maxM, h->force_generic != 0);
-    h->sim_levels.push_back(S);
-  }
-}
-
-static int sim_refuse(st_handle h, int nd) {
-  if (h->world > 1) { h->err = "st_simulate: multi-GPU handles are not supported"; return ST_ERR_UNSUPPORTED; }
-  if (h->n_obs != h->n_all) { h->err = "st_simulate: the tree has NA rows; build it with every row observed"; return ST_ERR_UNSUPPORTED; }
-  if (nd < 1 || nd > SIM_MAX_ND) { h->err = "st_simulate: nd must be in 1..16"; return ST_ERR_USAGE; }
-  if (h->theta[0].empty()) { h->err = "st_simulate before st_factor(slot 0)"; return ST_ERR_USAGE; }
-  return ST_OK;
-}
-
-// caller's n_all x nd column-major (model order) -> [device row][ndp], unused columns zero
-static int sim_upload(st_handle h, const double *src, int nd, int ndp, double *dst) {
-  const long long n = h->n_all;
-  std::vector<double> tmp((size_t)n * ndp, 0.0);
-  for (long long i = 0; i < n; ++i) {
-    const long long r = h->dev2model[i];
-    for (int d = 0; d < nd; ++d) tmp[(size_t)i * ndp + d] = src[(size_t)d * n + r];
-  }
-  HCHK(h, hipMemcpyAsync(dst, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  return ST_OK;
-}
-static int sim_download(st_handle h, const double *src, int nd, int ndp, double *dst) {
-  const long long n = h->n_all;
-  std::vector<double> tmp((size_t)n * ndp);
-  HCHK(h, hipMemcpyAsync(tmp.data(), src, tmp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  for (long long i = 0; i < n; ++i) {
-    const long long r = h->dev2model[i];
-    for (int d = 0; d < nd; ++d) dst[(size_t)d * n + r] = tmp[(size_t)i * ndp + d];
-  }
-  return ST_OK;
-}
-
-extern "C" int st_simulate(st_handle h, int nd, const double *z, const double *eps, uint64_t seed, uint32_t iter0, double *w_out,
-                           double *y_out) {
-  if (!h) return ST_ERR_USAGE;
-  if (const int rc = sim_refuse(h, nd)) return rc;
-  HCHK(h, hipSetDevice(h->device));
-  if (const int rc = settle_top(h)) return rc;
-  if (const int rc = complete_leaf(h, 0)) return rc;
-  sim_plan(h);
-  const long long n = h->n_all;
-  const int ndp = sim_pad(nd);
-  for (const SimLevel &S : h->sim_levels)
-    if (S.route == SIM_ROUTE_GENERIC && SIM_GEN_LDS(S.maxM, ndp) > h->lds_limit) {
-      h->err = "st_simulate: a block too wide for the generic kernel's LDS";
-      return ST_ERR_UNSUPPORTED;
-    }
-  if (ndp > h->sim_cap) {
-    h->d_simz.free(); h->d_sime.free(); h->d_simw.free(); h->d_simy.free();
-    HCHK(h, h->d_simz.alloc((size_t)n * ndp)); HCHK(h, h->d_sime.alloc((size_t)n * ndp));
-    HCHK(h, h->d_simw.alloc((size_t)n * ndp)); HCHK(h, h->d_simy.alloc((size_t)n * ndp));
-    h->sim_cap = ndp;
-  }
-  if (!h->d_rowblk.p) {
-    std::vector<int> rb(n);
-    for (size_t b = 0; b < h->blks.size(); ++b)
-      for (int i = 0; i < h->blks[b].m; ++i) rb[h->blks[b].row0 + i] = (int)b;
-    HCHK(h, h->d_rowblk.upload(rb));
-  }
-  if (z) { if (const int rc = sim_upload(h, z, nd, ndp, h->d_simz.p)) return rc; }
-  else HCHK(h, (hipError_t)simulate_normals(h->d_simz.p, h->d_dev2model.p, n, nd, ndp, iter0, SIM_NOISE_Z, seed, h->stream));
-  if (y_out) {
-    if (eps) { if (const int rc = sim_upload(h, eps, nd, ndp, h->d_sime.p)) return rc; }
-    else HCHK(h, (hipError_t)simulate_normals(h->d_sime.p, h->d_dev2model.p, n, nd, ndp, iter0, SIM_NOISE_EPS, seed, h->stream));
-  }
-  SimArgs A;
-  std::memset(&A, 0, sizeof(A));
-  A.blks = h->d_blks.p; A.anc_idx = h->d_anc.p; A.list = h->d_lvl.p;
-  A.panels = h->d_panels[h->slot_map[0]].p;
-  A.z = h->d_simz.p; A.eps = h->d_sime.p; A.xb = h->d_xb.p; A.mv = h->d_mv.p; A.tsq_inv = h->d_tsq.p;
-  A.w = h->d_simw.p; A.y = y_out ? h->d_simy.p : nullptr; A.rowblk = h->d_rowblk.p;
-  int mask = 0;
-  HCHK(h, (hipError_t)simulate_launch(h->sim_levels.data(), (int)h->sim_levels.size(), A, ndp, h->stream, &mask));
-  if (w_out) { if (const int rc = sim_download(h, h->d_simw.p, nd, ndp, w_out)) return rc; }
-  if (y_out) { if (const int rc = sim_download(h, h->d_simy.p, nd, ndp, y_out)) return rc; }
-  return ST_OK;
-}
-
-extern "C" int st_simulate_info(st_handle h, int nd, int32_t *route_mask, double *alg_bytes, double *flops) {
-  if (!h) return ST_ERR_USAGE;
-  if (nd < 1 || nd > SIM_MAX_ND) { h->err = "st_simulate_info: nd must be in 1..16"; return ST_ERR_USAGE; }
-  sim_plan(h);
-  int mask = 0;
-  double bytes = 0.0, fl = 0.0;
-  for (size_t g = 0; g < h->sim_levels.size(); ++g) {
-    const SimLevel &S = h->sim_levels[g];
-    if (S.count == 0) continue;
-    mask |= 1 << (S.route - 1);
-    for (int k = 0; k < S.count; ++k) {
-      const Blk &B = h->blks[h->lvl_list[S.first + k]];
-      const double m = B.m, P = B.P, ri = B.isref ? m * (m + 1) / 2 : m;
-      bytes += 8.0 * (m * P + ri);                   // the block's panel, once
-      fl += 2.0 * nd * (m * P + ri);
-    }
-  }
-  // per row: z, eps, w, y and the ancestor gathers (8 nd B each), XB (8 B)
-  bytes += (double)h->n_all * (5.0 * 8.0 * nd + 8.0);
-  if (route_mask) *route_mask = mask;
-  if (alg_bytes) *alg_bytes = bytes;
-  if (flops) *flops = fl;
-  return ST_OK;
-}
-
-extern "C" const char *st_simulate_route_name(int32_t code) { return simulate_route_name(code); }

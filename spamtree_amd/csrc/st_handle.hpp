@@ -1,13 +1,11 @@
 // st_handle.hpp -- what the host translation units of the library share: the handle behind st_handle, its self-freeing device
-// buffers, the HIP error check of the C-ABI functions and the launch timing.  spamtree_hip.hip owns the handle (st_create,
-// st_destroy) and everything the Gibbs sweep launches; st_points.hip has new-point prediction (st_points_*).
+// buffers, the HIP error checks of the C-ABI functions and the launch timing.  spamtree_hip.hip owns the handle (st_create,
+// st_destroy) and everything the Gibbs sweep launches.  A feature family has a host unit of its own, which defines the family's
+// state; the handle only points to it: st_points.hip new-point prediction, st_rows.hip the criteria over the fit's rows with
+// leave-one-out and Pareto smoothing, st_simulate.hip prior simulation, st_summary.hip the running summaries (state: the handle's).
 #pragma once
 #include "tree_layout.hpp"
 #include "st_protocol.hpp"
-#include "simulate_kernels.hpp"
-#include "loo_layout.hpp"
-#include "loo_kernels.hpp"
-#include "psis_kernels.hpp"
 
 // A device allocation that frees itself; a null buffer makes no HIP call.  (The owner has the device current when it goes.)
 template <typename T>
@@ -69,35 +67,12 @@ struct st_handle_s : TreeLayout {
   int top_phys = -1;
   std::vector<double> top_theta;
   bool ext_stream = false;
+  // The running summaries (st_summary.hip), always present: the criteria over the rows read the stored draws and their epoch
   DevBuf<double> d_sum_w, d_sum_yhat;         // running sums over saved iterations (st_summary_*)
   long long n_summary = 0;
   DevBuf<double> d_draws_w, d_draws_yhat;     // st_summary_reserve: the saved draws themselves, [keep][n_all] (quantiles)
   long long draws_cap = 0, n_draws = 0;
-  // st_rows_score_*: criteria over the fit's own rows (rows_score.hpp); device row order throughout
-  DevBuf<double> d_rs_tgt, d_rs_hold;         // the targets; the same with NaN off the held-out rows (k_score_crps's y)
-  DevBuf<double> d_rs_acc, d_rs_rows, d_rs_crps, d_rs_partial, d_rs_tot;
-  bool rs_set = false;
-  long long rs_n_acc = 0, rs_n_tgt = 0, rs_n_held = 0;
-  std::vector<long long> rs_nobs_q, rs_nheld_q;
   long long draws_epoch = 0;                  // advances whenever the stored draws of st_summary_reserve change
-  long long rs_crps_epoch = -1;               // d_rs_crps holds the CRPS of the stored draws of that epoch (-1: none)
-  long long rs_fin_acc = -1, rs_fin_crps = -2;   // d_rs_rows / d_rs_tot are those of rs_fin_acc draws, with the CRPS of that epoch summed (-1: without)
-  double rs_tau2_sum[ST_MAX_Q] = {0};         // sum over the accumulated draws of 1 / tausq_inv_j, added in call order
-  // st_rows_loo_*: leave-one-out criteria with w_i integrated out (loo_kernels.hpp, loo_layout.hpp); device row order
-  DevBuf<int> d_loo_list, d_loo_chptr, d_loo_chidx;
-  DevBuf<long long> d_loo_voff;
-  DevBuf<double> d_loo_S, d_loo_last, d_loo_acc, d_loo_rows, d_loo_tot;
-  std::vector<LooLevelLaunch> loo_levels;
-  double loo_bytes = 0, loo_flops = 0;
-  bool loo_set = false;
-  int loo_mask = 0;
-  long long loo_n_acc = 0, loo_fin_acc = -1;  // d_loo_rows / d_loo_tot are those of loo_fin_acc draws
-  std::vector<long long> loo_nobs_q;
-  // st_rows_loo_reserve: the accumulated draws' (t, Phi, mu), [3][loo_keep][n_all] in device row order (psis_kernels.hpp), and
-  // st_rows_loo_psis' outputs of psis_fin_acc draws (PSIS_NOUT x n doubles; tail_len, n_draws; q x PSIS_NSUM totals)
-  DevBuf<double> d_loo_store, d_psis_rows, d_psis_tot;
-  DevBuf<int> d_psis_int;
-  long long loo_keep = 0, psis_fin_acc = -1;
   bool stats_valid = false;                   // d_stats matches the current w and XB
   bool host_stats_valid = false;              // ... and host_stats holds a copy of it
   std::vector<double> host_stats;
@@ -130,12 +105,11 @@ struct st_handle_s : TreeLayout {
   int route_p = ST_ROUTE_NONE;                // ... and of the last st_predict
   std::vector<double> xtx;
   std::vector<long long> n_obs_q;
-  struct PointSet *pts = nullptr;             // st_points_set: new locations to predict at (owned)
-  // st_simulate: draws [row][sim_cap] on the device (allocated on first use, grown with nd), the device block of every row
-  DevBuf<double> d_simz, d_sime, d_simw, d_simy;
-  DevBuf<int> d_rowblk;
-  int sim_cap = 0;
-  std::vector<SimLevel> sim_levels;
+  // The state of a feature family is defined in the family's host unit and owned here; null: not set.  st_destroy drops each.
+  struct PointSet *pts = nullptr;             // st_points.hip: new locations to predict at
+  struct RowsScore *rows = nullptr;           // st_rows.hip: the criteria over the fit's own rows
+  struct RowsLoo *loo = nullptr;              // st_rows.hip: the leave-one-out criteria and their Pareto store
+  struct SimState *sim = nullptr;             // st_simulate.hip: the level plan and the draws' buffers
 
   DevBuf<double> d_cx, d_cy, d_y, d_X, d_w, d_xb, d_z, d_B, d_panels[2], d_acc, d_logdet[2], d_loglik[2], d_scalars, d_partial,
       d_stats, d_xtx, d_scratch, d_tmp_n, d_tsq;
@@ -208,6 +182,9 @@ struct ProfScope {
   }
 };
 
+// A launcher's failure (the HIP error it returns as an int) as the entry point's: "<what> launch: <HIP's text>"
+inline int launch_failed(st_handle_s *h, const std::string &what, int e) { h->err = what + " launch: " + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+
 template <typename T>
 inline hipError_t upload_or_dummy(DevBuf<T> &d, const std::vector<T> &v) {   // an empty list still gets one (zero) element to point at
   return v.empty() ? d.upload(std::vector<T>(1)) : d.upload(v);
@@ -215,3 +192,11 @@ inline hipError_t upload_or_dummy(DevBuf<T> &d, const std::vector<T> &v) {   // 
 
 // defined in spamtree_hip.hip
 int make_covpar(st_handle h, const double *theta, int ntheta, CovPar *cp);
+int download_rows(st_handle h, const double *src, double *dst);   // n_all doubles, device row order -> model row order
+int refuse_factor_open(st_handle h, const char *who, int slot = -1);
+int refuse_sweep_pending(st_handle h, const char *who);
+int settle_top(st_handle h);
+int complete_leaf(st_handle h, int slot);
+int gen_or_upload_z(st_handle h, const double *z, uint64_t seed, uint32_t iter, unsigned stream_id, double *dst);
+// each drops its unit's state of the handle (st_destroy, and the unit's own clear and set): st_points.hip, st_rows.hip, st_simulate.hip
+void points_free(st_handle_s *h); void rows_free(st_handle_s *h); void loo_free(st_handle_s *h); void sim_free(st_handle_s *h);

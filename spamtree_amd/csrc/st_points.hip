@@ -194,8 +194,7 @@ static int points_run(st_handle h, PointSet *ps, int mode, bool use_z, uint64_t 
   PointsLaunch L;
   L.ntile128 = ps->ntile128; L.ntile256 = ps->ntile256; L.grid_generic = ps->grid_generic;
   ProfScope pscope(h, 6);
-  const int e = points_launch(L, A, cp, h->stream, &ps->route_mask);
-  if (e) { h->err = std::string(who) + " launch: " + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+  if (const int e = points_launch(L, A, cp, h->stream, &ps->route_mask)) return launch_failed(h, who, e);
   return ST_OK;
 }
 
@@ -235,8 +234,7 @@ static int points_run_joint(st_handle h, PointSet *ps, int mode, bool use_z, uin
   JointLaunch L;
   L.ntile128 = ps->jtile128; L.ntile256 = ps->jtile256; L.grid_generic = ps->jgrid_generic;
   ProfScope pscope(h, 6);
-  const int e = points_joint_launch(L, J, cp, h->stream, &ps->route_mask);
-  if (e) { h->err = std::string(who) + " launch: " + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+  if (const int e = points_joint_launch(L, J, cp, h->stream, &ps->route_mask)) return launch_failed(h, who, e);
   return ST_OK;
 }
 
@@ -309,8 +307,7 @@ static int fun_step(st_handle h, PointSet *ps) {
   A.count = (double)(fs->n_acc + 1);
   {
     ProfScope pscope(h, 6);
-    const int e = points_fun_launch(A, h->stream);
-    if (e) { h->err = std::string("st_points_accumulate launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+    if (const int e = points_fun_launch(A, h->stream)) return launch_failed(h, "st_points_accumulate", e);
   }
   fs->n_acc += 1;
   if (keep) fs->n_kept += 1;
@@ -344,7 +341,7 @@ static int score_step(st_handle h, PointSet *ps) {
     J.n_joint = ps->n_joint; J.groups = ps->d_jgroups.p; J.members = ps->d_jmem.p; J.jacc = sc->d_jacc.p; J.n_degenerate = sc->d_ndeg.p;
     e = points_score_joint_launch(J, sc->gmax, h->stream);
   }
-  if (e) { h->err = std::string("st_points_accumulate launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+  if (e) return launch_failed(h, "st_points_accumulate", e);
   return ST_OK;
 }
 
@@ -413,8 +410,7 @@ static int points_accumulate(st_handle h, uint64_t seed, uint32_t iter, double *
     B.mean = o + n; B.cov = ps->d_jout.p; B.acc = ps->d_acc.p; B.pacc = ps->d_pacc.p; B.groups = ps->d_jgroups.p; B.members = ps->d_jmem.p;
     B.pt_grp = ps->d_pt_grp.p; B.pt_a = ps->d_pt_a.p; B.count = (double)(ps->n_acc + 1); B.n = n; B.cov_total = ps->cov_total;
     ProfScope pscope(h, 6);
-    const int e = points_pair_acc_launch(B, h->stream);
-    if (e) { h->err = std::string("st_points_accumulate launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+    if (const int e = points_pair_acc_launch(B, h->stream)) return launch_failed(h, "st_points_accumulate", e);
   }
   PointsAccArgs A;
   A.w = o; A.mean = o + n; A.var = o + 2 * n; A.yhat = ps->has_X ? o + 3 * n : nullptr;
@@ -426,8 +422,7 @@ static int points_accumulate(st_handle h, uint64_t seed, uint32_t iter, double *
   A.n = n;
   {
     ProfScope pscope(h, 6);
-    const int e = points_acc_launch(A, h->stream);
-    if (e) { h->err = std::string("st_points_accumulate launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+    if (const int e = points_acc_launch(A, h->stream)) return launch_failed(h, "st_points_accumulate", e);
   }
   ps->n_acc += 1;
   if (keep) ps->n_kept += 1;
@@ -707,8 +702,7 @@ extern "C" int st_points_score_get(st_handle h, double *lpd, double *pit, double
     A.draws = ps->d_keep_yhat.p; A.y = sc->d_y.p; A.n = n; A.keep = (int)ps->n_kept;
     qtile_plan(ps->n_kept, &A.Kpad, &A.R);
     A.out = sc->d_crps.p;
-    const int e = points_score_crps_launch(A, h->lds_limit, h->stream);
-    if (e) { h->err = std::string("st_points_score_get launch: ") + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+    if (const int e = points_score_crps_launch(A, h->lds_limit, h->stream)) return launch_failed(h, "st_points_score_get", e);
     HCHK(h, hipMemcpyAsync(crps, sc->d_crps.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   }
   HCHK(h, hipStreamSynchronize(h->stream));

@@ -1,15 +1,17 @@
 """CPU-only: every kernel instantiation the host code launches is covered -- by a row of the route table of
 tests/test_gpu_routes.py (which proves through st_route_info that it reached it and compares it with the oracle), by
 the table's explicit exclusions, or by an existing test named here.  A kernel added later without a test fails here."""
+import glob
 import os
 import re
 
 from tests import test_gpu_routes as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "spamtree_amd", "csrc", "spamtree_hip.hip")
-SRC_POINTS = os.path.join(ROOT, "spamtree_amd", "csrc", "st_points.hip")
-SRC_POINTS_ACC = os.path.join(ROOT, "spamtree_amd", "csrc", "k_points_acc.hip")
+CSRC = os.path.join(ROOT, "spamtree_amd", "csrc")
+SRC = os.path.join(CSRC, "spamtree_hip.hip")
+SRC_UNITS = sorted(glob.glob(os.path.join(CSRC, "st_*.hip")))   # the host units of the feature families (st_points.hip, ...)
+SRC_POINTS_ACC = os.path.join(CSRC, "k_points_acc.hip")
 
 # launched kernels without a route code that other tests compare with the oracle (or, for plumbing, check bit for bit);
 # every route-coded kernel is reached by a row of the route table instead (test_every_route_coded_kernel_is_in_the_table)
@@ -39,8 +41,9 @@ def _norm(name):
 
 def launched_kernels():
     """Every instantiation named by a hipLaunchKernelGGL of the host code, the kernel table and template wrappers expanded."""
-    # (st_points.hip: the C-ABI of new-point prediction; k_points_acc is launched from its own translation unit)
-    src = open(SRC).read() + open(SRC_POINTS).read() + open(SRC_POINTS_ACC).read()
+    # (st_*.hip: the C-ABI of new-point prediction, the running summaries, ...; k_points_acc is launched from its own translation unit)
+    assert SRC_UNITS, CSRC
+    src = "".join(open(f).read() for f in [SRC] + SRC_UNITS + [SRC_POINTS_ACC])
     names = set()
     for m in re.finditer(r"hipLaunchKernelGGL\(\s*(\(\s*[A-Za-z_]\w*\s*<[^>]*>\s*\)|[A-Za-z_]\w*)", src):
         names.add(_norm(m.group(1).strip("() ")))
