@@ -115,7 +115,7 @@ C_BOUND = 8.0
 # (75 rows, q = 3, no parent) at the cross regime: measured e_dev / e_64 = 8.32 on both slots of wide4_default_pred,
 # wide4_bigmfma and wide4_sibling_groups, and 11.5 on wide4_generic (e_dev ~1e-11).  The identical value on the first three
 # is one path: a root level (P = 0, 75 columns) is factorised by k_factor_bigmfma's blocked epilogue on every non-generic
-# row (spamtree_hip.hip, the level dispatch), which also forms the quadratic form |Ri w|^2; wide4_generic runs the root on
+# row (st_factor.hip, the level dispatch), which also forms the quadratic form |Ri w|^2; wide4_generic runs the root on
 # k_factor<true, MODE_FACTOR>.  Every other level, regime and quantity of these rows keeps C_BOUND.
 C_FAMILY = {("wide4", "cross", 0, "loglik"): 16.0}
 NMAX = 6

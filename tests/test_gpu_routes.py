@@ -337,7 +337,7 @@ def compare_with_oracle(pb, inp, out, key=None):
 
 # the sweep kernels of levels on the big (scratch-arena) path: a rebuild sweep forms their Gram parts with k_gram_big
 BIG_SWEEP = {"k_sample<true, false>", "k_sample<true, true>", "k_sample_leaf_wide"}
-# the chain lengths (P) and block widths (m) each phase-A kernel is dispatched at (spamtree_hip.hip, factor_launch and the
+# the chain lengths (P) and block widths (m) each phase-A kernel is dispatched at (st_factor.hip, factor_launch and the
 # level geometry: k_factor_quad P <= 200, the column-group path P <= 256, k_factor_lchain<96> / <136> P <= 384 / <= 544,
 # k_factor_bigmfma by width: <= 48, <= 64, <= 80 columns)
 A_BOUNDS = {
