@@ -205,12 +205,32 @@ typedef struct stm_criteria {
  * criteria.  The outputs of st_rows_loo_get (n_all each; n_accumulated, n_skipped: one count each) and of st_rows_loo_totals (tot:
  * ST_ROWS_LOO_N x q; n_obs: q).  limited_tree problems are refused (ST_ERR_UNSUPPORTED). */
 typedef struct stm_loo_psis stm_loo_psis;
+typedef struct stm_loo_groups stm_loo_groups;
 typedef struct stm_loo {
   double *elpd_loo, *pit_loo, *mu_loo, *weight_ess;
   double *tot;
   int64_t *n_obs, *n_accumulated, *n_skipped;
   const stm_loo_psis *psis;   /* NULL: the raw weights alone */
+  const stm_loo_groups *groups;   /* NULL: rows alone */
 } stm_loo;
+
+/* Leave-group-out criteria (include/spamtree_hip.h, st_rows_loo_groups_*): a part of loo, so it cannot be asked for without it, and
+ * no entry point of its own: a request that leaves the pointer NULL runs bit for bit as before.  st_rows_loo_groups_set(labels)
+ * comes right after st_rows_loo_set (and loo's st_rows_loo_reserve), so its refusals come in step 1 after loo's; the read-out after
+ * loo's and psis' in step 3.  labels: n_all values, model row order.  The caller sizes the per-group outputs for n_all groups (there
+ * cannot be more) and reads n_groups and n_members: label, elpd_lgo, weight_ess, n_skipped, khat, elpd_psis, weight_ess_psis
+ * (n_groups used), ptr (n_groups + 1), rows (n_members); mu_lgo, pit_lgo: n_all; tot: ST_ROWS_LGO_N; by_outcome: ST_ROWS_LGO_OUT_N x q.
+ * khat, elpd_psis and weight_ess_psis are written only when loo has its psis part (the store); any pointer but labels may be NULL. */
+struct stm_loo_groups {
+  const int64_t *labels;
+  int64_t *n_groups, *n_members, *n_pairs;
+  int64_t *label, *ptr, *rows;
+  double *elpd_lgo, *weight_ess;
+  int64_t *n_skipped;
+  double *mu_lgo, *pit_lgo;
+  double *tot, *by_outcome;
+  double *khat, *elpd_psis, *weight_ess_psis;
+};
 
 /* Pareto smoothing of the leave-one-out weights (include/spamtree_hip.h, st_rows_loo_reserve / _psis / _psis_totals / _draws): a
  * part of loo, so it cannot be asked for without it, and no entry point of its own: a request (or stm_mcmc_loo's loo) that leaves
@@ -230,12 +250,12 @@ struct stm_loo_psis {
  *  1. Before a chain exists, the refusals; the first failing check decides the return code.  Parts of both families; then the
  *     chains' (with a text, below), diag's, exc's, rk's (each in the order given above), the point set's, the scores', the
  *     quantiles'; then the criteria's.  Then stm_create, the point set, the rows' reservation, functionals, scores, the joint
- *     layout, stm_rows_score_set, st_rows_loo_set (with loo's psis: st_rows_loo_reserve) and stm_init: every refusal of those comes before the first sweep.
+ *     layout, stm_rows_score_set, st_rows_loo_set (with loo's psis: st_rows_loo_reserve; with loo's groups: st_rows_loo_groups_set) and stm_init: every refusal of those comes before the first sweep.
  *  2. Chain after chain; on every saved iteration st_get_w, st_yhat, the points' accumulate, st_points_functionals_last,
  *     st_rows_score_accumulate and its st_summary_accumulate, st_rows_loo_accumulate, the stores' st_summary_accumulate.
  *  3. After the last chain the read-outs, each only for a part that is there and only once a draw was saved: new_cond_var from
  *     the packed blocks, the points' summaries, covariance, quantiles and routes, the functionals' summaries and quantiles, the
- *     scores, diag (rows, points, functionals), exc, rk, the criteria, loo, loo's psis. */
+ *     scores, diag (rows, points, functionals), exc, rk, the criteria, loo, loo's psis, loo's groups. */
 typedef struct stm_fit {
   stm_run run;
   const stm_new_points *pts;   /* NULL: no point set */

@@ -685,6 +685,61 @@ int st_rows_loo_totals(st_handle h, double *tot, int64_t *n_obs);
 int st_rows_loo_info(st_handle h, int32_t *route_mask, double *alg_bytes, double *flops);
 const char *st_rows_loo_route_name(int32_t code);
 
+/* ---- leave-group-out criteria: a group of rows (a site's outcomes, a small spatial block) left out together, its rows of the
+ * latent field integrated out jointly.  Saved draw s gives group G, with o its members with an observed y,
+ *   A = Q_GG,  V = A^-1,  m_G = w_G - V (Qw)_G,  mu_o = XB_o + m_o,  Sigma = V_oo + diag(1 / tausq_inv_{j(a)}),
+ *   l_s = log N(y_o; mu_o, Sigma),  Phi_a = Phi((y_a - mu_a) / sqrt(Sigma_aa)),
+ * and over the S accumulated draws, r_s = exp(-l_s): elpd_lgo_G = -log((1 / S) sum r_s), which estimates log p(y_G | y_-G),
+ * weight_ess_G = (sum r_s)^2 / sum r_s^2, and per observed member mu_lgo and pit_lgo weighted by r_s
+ * (spamtree_amd/csrc/lgo_kernels.hpp has the definition, the order of every operation and the rounding bound).  The off-diagonal
+ * entries of Q_GG are column-pair sums over the panels the sweep of st_rows_loo_accumulate reads anyway: with groups set that one
+ * sweep serves rows and groups, and everything st_rows_loo_* reports stays bit for bit what it is without groups.
+ * st_rows_loo_groups_set: labels, n_all values in model row order, negative = in no group.  A group is the set of rows with one label
+ *   that lie in a block of the density (labelled rows of prediction blocks are ignored; a member without an observed y is
+ *   integrated out with the group and not scored).  Groups are numbered by ascending label, members stand in ascending model row.
+ *   After st_rows_loo_set and before the first accumulate.  Refused with a text, the previous state kept: a group of more than
+ *   ST_ROWS_LGO_MAX_MEMBERS members (ST_ERR_UNSUPPORTED, with both numbers), a group without an observed member, no
+ *   st_rows_loo_set, an accumulated iteration (ST_ERR_USAGE); limited_tree and world > 1 handles as st_rows_loo_set.
+ * st_rows_loo_groups_clear: the groups leave (before the first accumulate, or after st_rows_loo_set anew); st_rows_loo_set and
+ *   st_rows_loo_clear drop them too.
+ * st_rows_loo_groups_count: the groups, their members in all, the non-structural member pairs, and the doubles of one of _last's
+ *   matrix arguments (sum of g^2).
+ * st_rows_loo_groups_index: CSR from group to member rows: label (n_groups), ptr (n_groups + 1), rows (n_members, model rows).
+ * st_rows_loo_groups_last: of the last accumulate, group after group: Q_GG and cond_cov = V (g x g row-major each), (Qw)_G and
+ *   cond_mean = m_G (n_members each).
+ * st_rows_loo_groups_get: per group elpd_lgo, weight_ess (NaN when every draw was skipped) and the draws skipped; per row, n_all
+ *   values in model row order, mu_lgo and pit_lgo, NaN off the observed members.
+ * st_rows_loo_groups_totals: tot, ST_ROWS_LGO_N values over the groups with a value: sum elpd_lgo, the criterion -2 sum, its
+ *   standard error sqrt(G var) (var with divisor G - 1; NaN below two groups), min weight_ess, the count; by_outcome,
+ *   ST_ROWS_LGO_OUT_N x q column-major over the outcome's observed members: sum (y - mu_lgo)^2, sum pit_lgo, the count.
+ * With a store (st_rows_loo_reserve below, called before or after the groups are set) every draw's group log ratio t_s = -l_s is
+ * kept too, 8 B per group and draw, NaN where the draw is skipped for the group; the streaming outputs do not change.
+ * st_rows_loo_groups_draws: the stored ratios, [n_accumulated][n_groups].
+ * st_rows_loo_groups_psis: st_psis' kernel over them, one series per group without companions: khat, elpd_psis, weight_ess_psis,
+ *   tail_len and n_draws per group.  Both need a store and one accumulate (ST_ERR_USAGE).
+ * Any output may be NULL.  Before the first accumulate _last, _get and _totals are ST_ERR_USAGE. */
+#define ST_ROWS_LGO_MAX_MEMBERS 16
+#define ST_ROWS_LGO_ELPD 0
+#define ST_ROWS_LGO_IC 1
+#define ST_ROWS_LGO_SE 2
+#define ST_ROWS_LGO_MIN_ESS 3
+#define ST_ROWS_LGO_COUNT 4
+#define ST_ROWS_LGO_N 5
+#define ST_ROWS_LGO_OUT_SQERR 0
+#define ST_ROWS_LGO_OUT_PIT 1
+#define ST_ROWS_LGO_OUT_COUNT 2
+#define ST_ROWS_LGO_OUT_N 3
+int st_rows_loo_groups_set(st_handle h, const int64_t *labels);
+int st_rows_loo_groups_clear(st_handle h);
+int st_rows_loo_groups_count(st_handle h, int64_t *n_groups, int64_t *n_members, int64_t *n_pairs, int64_t *n_matrix);
+int st_rows_loo_groups_index(st_handle h, int64_t *label, int64_t *ptr, int64_t *rows);
+int st_rows_loo_groups_last(st_handle h, double *q_gg, double *qw, double *cond_mean, double *cond_cov);
+int st_rows_loo_groups_get(st_handle h, double *elpd_lgo, double *weight_ess, int64_t *n_skipped, double *mu_lgo, double *pit_lgo,
+                           int64_t *n_accumulated);
+int st_rows_loo_groups_totals(st_handle h, double *tot, double *by_outcome);
+int st_rows_loo_groups_draws(st_handle h, double *t);
+int st_rows_loo_groups_psis(st_handle h, double *khat, double *elpd_psis, double *weight_ess_psis, int32_t *tail_len, int32_t *n_draws);
+
 /* ---- Pareto-smoothed importance sampling of the leave-one-out weights, on the device (Vehtari, Simpson, Gelman, Yao, Gabry,
  * "Pareto smoothed importance sampling"; the generalised Pareto fit of Zhang and Stephens with the weakly informative prior of
  * loo::gpdfit; r_eff = 1).  spamtree_amd/psis.py has the definition, spamtree_amd/csrc/psis_kernels.hpp the order the kernel

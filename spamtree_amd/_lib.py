@@ -189,6 +189,15 @@ SIGNATURES = {
     "st_rows_loo_totals": (C.c_int, [H, c_dp, c_ip]),
     "st_rows_loo_info": (C.c_int, [H, C.POINTER(C.c_int32), c_dp, c_dp]),
     "st_rows_loo_route_name": (C.c_char_p, [C.c_int32]),
+    "st_rows_loo_groups_set": (C.c_int, [H, c_ip]),
+    "st_rows_loo_groups_clear": (C.c_int, [H]),
+    "st_rows_loo_groups_count": (C.c_int, [H, c_ip, c_ip, c_ip, c_ip]),
+    "st_rows_loo_groups_index": (C.c_int, [H, c_ip, c_ip, c_ip]),
+    "st_rows_loo_groups_last": (C.c_int, [H, c_dp, c_dp, c_dp, c_dp]),
+    "st_rows_loo_groups_get": (C.c_int, [H, c_dp, c_dp, c_ip, c_dp, c_dp, c_ip]),
+    "st_rows_loo_groups_totals": (C.c_int, [H, c_dp, c_dp]),
+    "st_rows_loo_groups_draws": (C.c_int, [H, c_dp]),
+    "st_rows_loo_groups_psis": (C.c_int, [H, c_dp, c_dp, c_dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "st_rows_loo_reserve": (C.c_int, [H, C.c_int64]),
     "st_rows_loo_draws": (C.c_int, [H, c_dp, c_dp, c_dp]),
     "st_rows_loo_psis": (C.c_int, [H, C.POINTER(StPsisOut)]),
@@ -227,6 +236,9 @@ class StmCriteria(C.Structure):   # include/spamtree_fit.h, stm_criteria
 ST_ROWS_OBS = ("lppd", "p_waic", "waic", "Dbar", "Dhat", "p_D", "dic")   # include/spamtree_hip.h: ST_ROWS_OBS_*, ST_ROWS_HELD_*
 ST_ROWS_HELD = ("lppd", "pit", "crps", "sqerr")
 ST_ROWS_LOO = ("elpd_loo", "looic", "sqerr", "pit", "min_weight_ess", "count")   # ST_ROWS_LOO_*
+ST_ROWS_LGO = ("elpd_lgo", "lgoic", "se", "min_weight_ess", "n_groups")          # ST_ROWS_LGO_*
+ST_ROWS_LGO_OUT = ("sqerr", "pit", "count")                                      # ST_ROWS_LGO_OUT_*
+ST_ROWS_LGO_MAX_MEMBERS = 16
 ST_ROWS_PSIS = ("count", "elpd_psis", "elpd_psis_sq", "sqerr", "pit", "min_weight_ess", "max_khat", "n_khat_bad", "n_khat_above")   # ST_ROWS_PSIS_*
 
 
@@ -234,9 +246,15 @@ class StmLooPsis(C.Structure):   # include/spamtree_fit.h, stm_loo_psis
     _fields_ = [("out", StPsisOut), ("tot", c_dp), ("n_obs", c_ip), ("t", c_dp), ("phi", c_dp), ("mu", c_dp)]
 
 
+class StmLooGroups(C.Structure):   # include/spamtree_fit.h, stm_loo_groups
+    _fields_ = [("labels", c_ip), ("n_groups", c_ip), ("n_members", c_ip), ("n_pairs", c_ip), ("label", c_ip), ("ptr", c_ip), ("rows", c_ip),
+                ("elpd_lgo", c_dp), ("weight_ess", c_dp), ("n_skipped", c_ip), ("mu_lgo", c_dp), ("pit_lgo", c_dp), ("tot", c_dp),
+                ("by_outcome", c_dp), ("khat", c_dp), ("elpd_psis", c_dp), ("weight_ess_psis", c_dp)]
+
+
 class StmLoo(C.Structure):   # include/spamtree_fit.h, stm_loo
     _fields_ = [("elpd_loo", c_dp), ("pit_loo", c_dp), ("mu_loo", c_dp), ("weight_ess", c_dp), ("tot", c_dp), ("n_obs", c_ip),
-                ("n_accumulated", c_ip), ("n_skipped", c_ip), ("psis", C.POINTER(StmLooPsis))]
+                ("n_accumulated", c_ip), ("n_skipped", c_ip), ("psis", C.POINTER(StmLooPsis)), ("groups", C.POINTER(StmLooGroups))]
 
 
 class StmDiagnostics(C.Structure):   # include/spamtree_fit.h, stm_diagnostics

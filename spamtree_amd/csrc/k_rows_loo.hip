@@ -43,7 +43,7 @@ __device__ __forceinline__ void loo_row(const LooArgs &A, long long i, double wi
   A.acc[LOO_AM * n + i] = AM;
 }
 
-template <bool REF>
+template <bool REF, bool PAIRS>
 __global__ __launch_bounds__(NT) void k_loo_block(LooArgs A) {
   extern __shared__ double lds[];                   // x[P + m], e[m]
   __shared__ int s_am[MAXJ], s_ao[MAXJ + 1];
@@ -110,6 +110,27 @@ __global__ __launch_bounds__(NT) void k_loo_block(LooArgs A) {
     A.S[vo + len + k] = c;
     if (k >= P) loo_row(A, B.row0 + (k - P), x[k], d, c);
   }
+  // the pair part (lgo_kernels.hpp): one thread per pair slot of S_u
+  if (PAIRS) {
+    const int p0 = A.pr_ptr[b], np = A.pr_ptr[b + 1] - p0;
+    for (int t = tid; t < np; t += NT) {
+      const int ca = A.pr_a[p0 + t], cb = A.pr_b[p0 + t];
+      double p = 0.0;
+      if (REF || cb < P) {
+        for (int r = cb < P ? 0 : cb - P; r < m; ++r) p = fma(pan[(size_t)r * ld + ca], pan[(size_t)r * ld + cb], p);
+      } else {
+        p = fma(pan[(size_t)(cb - P) * ld + ca], pan[(size_t)(cb - P) * ld + P], p);
+      }
+      for (int j = c0; j < c1; ++j) {
+        const int ch = A.ch_idx[j];
+        const Blk Bc = A.blks[ch];
+        p += A.S[A.voff[ch] + 2ll * (Bc.P + Bc.m) + t];
+      }
+      A.S[vo + 2ll * len + t] = p;
+      const int fin = A.pr_fin[p0 + t];
+      if (fin >= 0) A.pairval[fin] = p;
+    }
+  }
 }
 
 // Per-row outputs and the per-outcome totals: workgroup v takes outcome v; every workgroup writes the outputs of its own
@@ -151,6 +172,12 @@ __global__ __launch_bounds__(NT) void k_loo_finish(LooFinishArgs A) {
   if (tid < LOO_NSUM) A.tot[v * LOO_NSUM + tid] = sm[tid][0];
 }
 
+template <bool REF, bool PAIRS>
+static void loo_launch_level(int count, size_t lds, hipStream_t st, const LooArgs &A) {
+  (void)hipFuncSetAttribute((const void *)k_loo_block<REF, PAIRS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((k_loo_block<REF, PAIRS>), dim3(count), dim3(NT), lds, st, A);
+}
+
 int loo_launch(const LooLevelLaunch *lv, int nlev, const LooArgs &A0, hipStream_t st, int *route_mask) {
   int mask = 0;
   for (int g = 0; g < nlev; ++g) {
@@ -160,13 +187,11 @@ int loo_launch(const LooLevelLaunch *lv, int nlev, const LooArgs &A0, hipStream_
     A.list = A0.list + L.first;
     A.nlist = L.count;
     const size_t lds = LOO_LDS(L.maxLen, L.maxM);
-    if (L.isref) {
-      (void)hipFuncSetAttribute((const void *)k_loo_block<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((k_loo_block<true>), dim3(L.count), dim3(NT), lds, st, A);
-    } else {
-      (void)hipFuncSetAttribute((const void *)k_loo_block<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((k_loo_block<false>), dim3(L.count), dim3(NT), lds, st, A);
-    }
+    const bool pairs = A.pr_ptr != nullptr;
+    if (L.isref && pairs) loo_launch_level<true, true>(L.count, lds, st, A);
+    else if (L.isref) loo_launch_level<true, false>(L.count, lds, st, A);
+    else if (pairs) loo_launch_level<false, true>(L.count, lds, st, A);
+    else loo_launch_level<false, false>(L.count, lds, st, A);
     mask |= 1 << ((L.isref ? LOO_ROUTE_REF : LOO_ROUTE_LEAF) - 1);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { *route_mask = mask; return (int)e; }

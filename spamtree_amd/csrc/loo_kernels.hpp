@@ -30,7 +30,8 @@
 // TOTALS per outcome over its observed rows, LOO_NSUM values: sum elpd_loo, sum (y - mu_loo)^2 (fma), sum pit_loo, min weight_ess;
 // one workgroup per outcome, thread t walks rows t, t + NT, ... ascending, then a fixed binary tree over the NT threads in LDS.
 //
-// THE KERNEL.  One launch per level from the deepest to the root; k_loo_block<REF>: one workgroup of NT threads per block.
+// THE KERNEL.  One launch per level from the deepest to the root; k_loo_block<REF, PAIRS>: one workgroup of NT threads per block
+// (PAIRS: the pair part of the leave-group-out criteria behind step 5, lgo_kernels.hpp; it changes nothing of steps 0 - 5).
 //   0. x[k], k < P + m: the w of the chain's rows, then the block's own, into LDS.
 //   1. e[r], wave r mod 4 of the workgroup: lane l adds the terms L[r,k] x[k] of the columns k = l, l + 64, ... in ascending order
 //      by fma from 0 (a reference row r has the columns k <= P + r; a non-reference row its P chain columns and then, as column
@@ -100,6 +101,9 @@ struct LooArgs {
   double *acc;                   // LOO_NACC x n
   long long n;
   double *st_t, *st_phi, *st_mu; // this draw's column of st_rows_loo_reserve's store (n each), or all NULL: no store
+  // the pair part of the leave-group-out criteria (lgo_kernels.hpp), or all NULL: k_loo_block<REF, false>
+  const int *pr_ptr, *pr_a, *pr_b, *pr_fin;   // per device block (CSR) its pair list; the slot in pairval where a pair finishes, or -1
+  double *pairval;
 };
 
 struct LooFinishArgs {
@@ -117,7 +121,8 @@ struct LooFinishArgs {
 #define LOO_LDS(maxLen, maxM) (((size_t)(maxLen) + (size_t)(maxM)) * sizeof(double))
 
 struct LooLevelLaunch { int first, count, isref, maxLen, maxM; };
-// the whole upward sweep on `st` (no synchronisation); *route_mask gets bit code - 1 of each route taken
+// the whole upward sweep on `st` (no synchronisation); *route_mask gets bit code - 1 of each route taken.  With A.pr_ptr set the
+// instantiations with the pair part run (voff then counts the p part of every S_u)
 int loo_launch(const LooLevelLaunch *lv, int nlev, const LooArgs &A, hipStream_t st, int *route_mask);
 int loo_finish_launch(const LooFinishArgs &A, hipStream_t st);
 const char *loo_route_name(int code);

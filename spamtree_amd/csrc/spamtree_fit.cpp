@@ -724,6 +724,8 @@ extern "C" int stm_mcmc_fit(const stm_fit *fit) {
   if (rc == 0 && cr) rc = stm_rows_score_set(c, cr->y_holdout);
   if (rc == 0 && loo) rc = st_rows_loo_set(c->h);   // (limited_tree is refused)
   if (rc == 0 && psis) rc = st_rows_loo_reserve(c->h, mcmc_keep);
+  const stm_loo_groups *const lgo = loo ? loo->groups : nullptr;
+  if (rc == 0 && lgo) rc = st_rows_loo_groups_set(c->h, lgo->labels);   // (oversized groups, groups without an observed member)
   if (rc == 0) rc = stm_init(c);
   if (rc != 0) { stm_destroy(c); return rc; }
   double *const new_cond_var = p.new_cond_var;
@@ -794,6 +796,15 @@ extern "C" int stm_mcmc_fit(const stm_fit *fit) {
     rc = st_rows_loo_psis(c->h, &psis->out);
     if (rc == 0) rc = st_rows_loo_psis_totals(c->h, psis->tot, psis->n_obs);
     if (rc == 0 && (psis->t || psis->phi || psis->mu)) rc = st_rows_loo_draws(c->h, psis->t, psis->phi, psis->mu);
+  }
+  if (rc == 0 && lgo) {
+    rc = st_rows_loo_groups_count(c->h, lgo->n_groups, lgo->n_members, lgo->n_pairs, nullptr);
+    if (rc == 0) rc = st_rows_loo_groups_index(c->h, lgo->label, lgo->ptr, lgo->rows);
+  }
+  if (rc == 0 && lgo && saved) {
+    rc = st_rows_loo_groups_get(c->h, lgo->elpd_lgo, lgo->weight_ess, lgo->n_skipped, lgo->mu_lgo, lgo->pit_lgo, nullptr);
+    if (rc == 0) rc = st_rows_loo_groups_totals(c->h, lgo->tot, lgo->by_outcome);
+    if (rc == 0 && psis) rc = st_rows_loo_groups_psis(c->h, lgo->khat, lgo->elpd_psis, lgo->weight_ess_psis, nullptr, nullptr);
   }
   stm_destroy(c);
   return rc;

@@ -12,6 +12,8 @@
 #include "loo_layout.hpp"
 #include "loo_kernels.hpp"
 #include "psis_kernels.hpp"
+#include "lgo_layout.hpp"
+#include "lgo_kernels.hpp"
 
 struct RowsScore {   // st_rows_score_set; device row order throughout
   DevBuf<double> d_tgt, d_hold;               // the targets; the same with NaN off the held-out rows (k_score_crps's y)
@@ -31,11 +33,29 @@ struct PsisStore {
   long long keep = 0, fin_acc = -1;
 };
 
+// st_rows_loo_groups_set: the groups' index structures (lgo_layout.hpp), the sweep's vectors with their pair part, the groups'
+// state and the last draw's matrices
+struct LooGroups {
+  LgoLayout lay;
+  DevBuf<int> d_prptr, d_pra, d_prb, d_prfin, d_grpptr, d_gpptr, d_gpidx, d_sqptr, d_memgrp;
+  DevBuf<long long> d_voff, d_memrow;
+  DevBuf<double> d_S, d_pairval, d_lastq, d_lastv, d_lastc, d_lastm, d_gacc, d_macc, d_gout, d_rows, d_tot;
+  std::vector<int> sq_ptr;
+  long long fin_acc = -1;                     // d_gout / d_rows / d_tot are those of fin_acc draws
+  // with a store reserved (st_rows_loo_reserve, before or after the groups): the draws' group log ratios [keep][n_groups] and
+  // st_rows_loo_groups_psis' outputs of psis_acc draws (PSIS_NOUT x n_groups doubles; tail_len, n_draws)
+  DevBuf<double> d_store, d_prow;
+  DevBuf<int> d_pint;
+  long long keep = 0, psis_acc = -1;
+};
+
 struct RowsLoo {   // st_rows_loo_set; device row order throughout
+  std::unique_ptr<LooGroups> grp;             // leaves with the state, or with st_rows_loo_groups_clear
   DevBuf<int> d_list, d_chptr, d_chidx;
   DevBuf<long long> d_voff;
   DevBuf<double> d_S, d_last, d_acc, d_rows, d_tot;
   std::vector<LooLevelLaunch> levels;
+  long long arena = 0;                        // doubles of d_S; while groups are set their own arena (with the pair parts) stands in and d_S is released
   double bytes = 0, flops = 0;
   int mask = 0;
   long long n_acc = 0, fin_acc = -1;          // d_rows / d_tot are those of fin_acc draws
@@ -238,7 +258,7 @@ extern "C" int st_rows_loo_set(st_handle h) {
     lo->levels.push_back(LooLevelLaunch{V.first, V.count, V.isref, V.maxLen, V.maxM});
     lo->mask |= 1 << ((V.isref ? LOO_ROUTE_REF : LOO_ROUTE_LEAF) - 1);
   }
-  lo->bytes = lay.alg_bytes; lo->flops = lay.flops;
+  lo->bytes = lay.alg_bytes; lo->flops = lay.flops; lo->arena = std::max(lay.arena, 1ll);
   loo_free(h);
   h->loo = lo.release();
   return ST_OK;
@@ -271,12 +291,30 @@ extern "C" int st_rows_loo_accumulate(st_handle h) {
   A.w = h->d_w.p; A.xb = h->d_xb.p; A.y = h->d_y.p; A.tsq_inv = h->d_tsq.p; A.obs = h->d_obs.p; A.mv = h->d_mv.p;
   A.voff = L.d_voff.p; A.ch_ptr = L.d_chptr.p; A.ch_idx = L.d_chidx.p;
   A.S = L.d_S.p; A.last = L.d_last.p; A.acc = L.d_acc.p; A.n = h->n_all;
+  if (L.grp) {   // the vectors with their pair part
+    LooGroups &G = *L.grp;
+    A.voff = G.d_voff.p; A.S = G.d_S.p;
+    A.pr_ptr = G.d_prptr.p; A.pr_a = G.d_pra.p; A.pr_b = G.d_prb.p; A.pr_fin = G.d_prfin.p; A.pairval = G.d_pairval.p;
+  }
   if (L.keep()) {   // this draw's column of the store
     const size_t plane = (size_t)L.keep() * h->n_all, col = (size_t)L.n_acc * h->n_all;
     A.st_t = L.psis->d_store.p + col; A.st_phi = L.psis->d_store.p + plane + col; A.st_mu = L.psis->d_store.p + 2 * plane + col;
   }
   int mask = 0;
   if (const int e = loo_launch(L.levels.data(), (int)L.levels.size(), A, h->stream, &mask)) return launch_failed(h, "st_rows_loo_accumulate", e);
+  if (L.grp) {   // after the root level's launch: d, c and every pair are there
+    LooGroups &G = *L.grp;
+    LgoArgs B;
+    std::memset(&B, 0, sizeof(B));
+    B.G = (int)G.lay.n_groups; B.n = h->n_all;
+    B.grp_ptr = G.d_grpptr.p; B.mem_row = G.d_memrow.p; B.gp_ptr = G.d_gpptr.p; B.gp_idx = G.d_gpidx.p; B.sq_ptr = G.d_sqptr.p;
+    B.pairval = G.d_pairval.p; B.last = L.d_last.p;
+    B.w = h->d_w.p; B.xb = h->d_xb.p; B.y = h->d_y.p; B.tsq_inv = h->d_tsq.p; B.obs = h->d_obs.p; B.mv = h->d_mv.p;
+    B.last_q = G.d_lastq.p; B.last_v = G.d_lastv.p; B.last_c = G.d_lastc.p; B.last_m = G.d_lastm.p;
+    B.gacc = G.d_gacc.p; B.macc = G.d_macc.p;
+    if (G.keep) B.st_t = G.d_store.p + (size_t)L.n_acc * G.lay.n_groups;
+    if (const int e = lgo_groups_launch(B, h->stream)) return launch_failed(h, "st_rows_loo_accumulate groups", e);
+  }
   L.n_acc += 1;
   return ST_OK;
 }
@@ -343,11 +381,176 @@ extern "C" int st_rows_loo_info(st_handle h, int32_t *route_mask, double *alg_by
   if (!h) return ST_ERR_USAGE;
   if (const int rc = loo_refuse(h, "st_rows_loo_info")) return rc;
   if (route_mask) *route_mask = h->loo->mask;
-  if (alg_bytes) *alg_bytes = h->loo->bytes;
-  if (flops) *flops = h->loo->flops;
+  if (alg_bytes) *alg_bytes = h->loo->bytes + (h->loo->grp ? h->loo->grp->lay.alg_bytes : 0.0);
+  if (flops) *flops = h->loo->flops + (h->loo->grp ? h->loo->grp->lay.flops : 0.0);
   return ST_OK;
 }
 extern "C" const char *st_rows_loo_route_name(int32_t code) { return loo_route_name(code); }
+
+// ---- leave-group-out criteria (lgo_kernels.hpp; the kernels and their launchers live in k_rows_loo.hip and k_rows_lgo.hip) ----
+// the groups' store of `keep` draws (0: none), NaN until written; a failed allocation is refused with its size
+static int lgo_store(st_handle h, const char *who, LooGroups &G, long long keep) {
+  DevBuf<double> store, prow;   // the groups keep what they have until every allocation has succeeded
+  DevBuf<int> pint;
+  if (keep > 0) {
+    const size_t ng = (size_t)std::max(G.lay.n_groups, 1ll), cnt = (size_t)keep * ng;
+    if (store.alloc(cnt) != hipSuccess || prow.alloc((size_t)PSIS_NOUT * ng) != hipSuccess || pint.alloc(2 * ng) != hipSuccess) {
+      (void)hipGetLastError();
+      h->err = std::string(who) + ": the store of " + std::to_string(keep) + " draws x " + std::to_string(G.lay.n_groups) + " groups could not be allocated";
+      return ST_ERR_HIP;
+    }
+    HCHK(h, hipMemsetAsync(store.p, 0xff, cnt * sizeof(double), h->stream));   // all bits set: a NaN
+    HCHK(h, hipStreamSynchronize(h->stream));
+  }
+  G.d_store = std::move(store); G.d_prow = std::move(prow); G.d_pint = std::move(pint);
+  G.keep = keep; G.psis_acc = -1;
+  return ST_OK;
+}
+static int lgo_refuse(st_handle h, const char *who, bool need_draw = false) {
+  if (const int rc = loo_refuse(h, who)) return rc;
+  if (!h->loo->grp) { h->err = std::string(who) + " before st_rows_loo_groups_set"; return ST_ERR_USAGE; }
+  return loo_refuse(h, who, true, need_draw);
+}
+extern "C" int st_rows_loo_groups_set(st_handle h, const int64_t *labels) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = loo_refuse(h, "st_rows_loo_groups_set")) return rc;
+  if (h->loo->n_acc > 0) { h->err = "st_rows_loo_groups_set after " + std::to_string(h->loo->n_acc) + " accumulated iterations (set the groups right after st_rows_loo_set)"; return ST_ERR_USAGE; }
+  if (!labels) { h->err = "st_rows_loo_groups_set: no labels"; return ST_ERR_USAGE; }
+  HCHK(h, hipSetDevice(h->device));
+  const long long n = h->n_all;
+  std::vector<unsigned char> obs(n);
+  HCHK(h, hipMemcpyAsync(obs.data(), h->d_obs.p, n * sizeof(unsigned char), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  LooLayout lay;
+  std::string msg;
+  if (const int rc = loo_layout(*h, lay, msg)) { h->err = "st_rows_loo_groups_set: " + msg; return rc; }
+  std::vector<long long> lab(labels, labels + n);
+  std::unique_ptr<LooGroups> gp(new LooGroups());   // the state takes it once every allocation has succeeded
+  LgoLayout &G = gp->lay;
+  if (const int rc = lgo_layout(*h, lay, lab.data(), obs.data(), G, msg)) { h->err = "st_rows_loo_groups_set: " + msg; return rc; }
+  std::vector<int> mem_grp;
+  gp->sq_ptr.assign(1, 0);
+  for (long long g = 0; g < G.n_groups; ++g) {
+    const int gm = G.grp_ptr[g + 1] - G.grp_ptr[g];
+    gp->sq_ptr.push_back(gp->sq_ptr.back() + gm * gm);
+    mem_grp.insert(mem_grp.end(), gm, (int)g);
+  }
+  const size_t ng = (size_t)std::max(G.n_groups, 1ll), nm = (size_t)std::max(G.n_members, 1ll), nsq = (size_t)std::max(gp->sq_ptr.back(), 1);
+  HCHK(h, gp->d_prptr.upload(G.pr_ptr)); HCHK(h, upload_or_dummy(gp->d_pra, G.pr_a)); HCHK(h, upload_or_dummy(gp->d_prb, G.pr_b));
+  HCHK(h, upload_or_dummy(gp->d_prfin, G.pr_fin)); HCHK(h, gp->d_grpptr.upload(G.grp_ptr)); HCHK(h, gp->d_gpptr.upload(G.gp_ptr));
+  HCHK(h, upload_or_dummy(gp->d_gpidx, G.gp_idx)); HCHK(h, gp->d_sqptr.upload(gp->sq_ptr)); HCHK(h, upload_or_dummy(gp->d_memgrp, mem_grp));
+  HCHK(h, gp->d_voff.upload(G.voff)); HCHK(h, upload_or_dummy(gp->d_memrow, G.mem_row));
+  HCHK(h, gp->d_S.alloc((size_t)std::max(G.arena, 1ll))); HCHK(h, gp->d_pairval.alloc((size_t)std::max(G.n_pairs, 1ll)));
+  HCHK(h, gp->d_lastq.alloc(nsq)); HCHK(h, gp->d_lastv.alloc(nsq)); HCHK(h, gp->d_lastc.alloc(nm)); HCHK(h, gp->d_lastm.alloc(nm));
+  HCHK(h, gp->d_gacc.alloc((size_t)LGO_NGACC * ng)); HCHK(h, gp->d_macc.alloc((size_t)LGO_NMACC * nm));
+  HCHK(h, gp->d_gout.alloc(2 * ng)); HCHK(h, gp->d_rows.alloc(2 * (size_t)n)); HCHK(h, gp->d_tot.alloc((size_t)LGO_NTOT + (size_t)h->q * LGO_NOUTC));
+  HCHK(h, hipMemsetAsync(gp->d_gacc.p, 0, (size_t)LGO_NGACC * ng * sizeof(double), h->stream));
+  HCHK(h, hipMemsetAsync(gp->d_macc.p, 0, (size_t)LGO_NMACC * nm * sizeof(double), h->stream));
+  HCHK(h, hipMemsetAsync(gp->d_rows.p, 0xff, 2 * (size_t)n * sizeof(double), h->stream));   // all bits set: a NaN
+  HCHK(h, hipStreamSynchronize(h->stream));
+  if (const int rc = lgo_store(h, "st_rows_loo_groups_set", *gp, h->loo->keep())) return rc;
+  h->loo->grp = std::move(gp);
+  h->loo->d_S = DevBuf<double>();   // the sweep runs on the groups' arena: the vectors are held once
+  return ST_OK;
+}
+extern "C" int st_rows_loo_groups_clear(st_handle h) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = lgo_refuse(h, "st_rows_loo_groups_clear")) return rc;
+  if (h->loo->n_acc > 0) { h->err = "st_rows_loo_groups_clear after " + std::to_string(h->loo->n_acc) + " accumulated iterations (st_rows_loo_set starts anew)"; return ST_ERR_USAGE; }
+  HCHK(h, hipSetDevice(h->device));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  if (!h->loo->d_S.p) HCHK(h, h->loo->d_S.alloc((size_t)h->loo->arena));   // the rows' own arena again, before the groups' leaves
+  h->loo->grp.reset();
+  return ST_OK;
+}
+extern "C" int st_rows_loo_groups_count(st_handle h, int64_t *n_groups, int64_t *n_members, int64_t *n_pairs, int64_t *n_matrix) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = lgo_refuse(h, "st_rows_loo_groups_count")) return rc;
+  const LooGroups &G = *h->loo->grp;
+  if (n_groups) *n_groups = G.lay.n_groups;
+  if (n_members) *n_members = G.lay.n_members;
+  if (n_pairs) *n_pairs = G.lay.n_pairs;
+  if (n_matrix) *n_matrix = G.sq_ptr.back();
+  return ST_OK;
+}
+extern "C" int st_rows_loo_groups_index(st_handle h, int64_t *label, int64_t *ptr, int64_t *rows) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = lgo_refuse(h, "st_rows_loo_groups_index")) return rc;
+  const LgoLayout &G = h->loo->grp->lay;
+  if (label) std::copy(G.label.begin(), G.label.end(), label);
+  if (ptr) std::copy(G.grp_ptr.begin(), G.grp_ptr.end(), ptr);
+  if (rows) std::copy(G.mem_model.begin(), G.mem_model.end(), rows);
+  return ST_OK;
+}
+static int download_to(st_handle h, const double *src, size_t count, double *dst) {
+  if (!dst || count == 0) return ST_OK;
+  HCHK(h, hipMemcpyAsync(dst, src, count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  return ST_OK;
+}
+extern "C" int st_rows_loo_groups_last(st_handle h, double *q_gg, double *qw, double *cond_mean, double *cond_cov) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = lgo_refuse(h, "st_rows_loo_groups_last", true)) return rc;
+  HCHK(h, hipSetDevice(h->device));
+  const LooGroups &G = *h->loo->grp;
+  const size_t nsq = (size_t)G.sq_ptr.back(), nm = (size_t)G.lay.n_members;
+  if (const int rc = download_to(h, G.d_lastq.p, nsq, q_gg)) return rc;
+  if (const int rc = download_to(h, G.d_lastc.p, nm, qw)) return rc;
+  if (const int rc = download_to(h, G.d_lastm.p, nm, cond_mean)) return rc;
+  return download_to(h, G.d_lastv.p, nsq, cond_cov);
+}
+// the groups' and members' outputs and the totals, once per number of accumulated draws
+static int lgo_finish(st_handle h) {
+  RowsLoo &L = *h->loo;
+  LooGroups &G = *L.grp;
+  if (G.fin_acc == L.n_acc) return ST_OK;
+  LgoFinishArgs F;
+  std::memset(&F, 0, sizeof(F));
+  F.G = (int)G.lay.n_groups; F.q = h->q; F.n = h->n_all; F.n_members = G.lay.n_members; F.S = (double)L.n_acc;
+  F.mem_grp = G.d_memgrp.p; F.mem_row = G.d_memrow.p; F.y = h->d_y.p; F.obs = h->d_obs.p; F.mv = h->d_mv.p;
+  F.gacc = G.d_gacc.p; F.macc = G.d_macc.p; F.gout = G.d_gout.p; F.rows = G.d_rows.p; F.tot = G.d_tot.p;
+  if (const int e = lgo_finish_launch(F, h->stream)) return launch_failed(h, "st_rows_loo_groups finish", e);
+  G.fin_acc = L.n_acc;
+  return ST_OK;
+}
+extern "C" int st_rows_loo_groups_get(st_handle h, double *elpd_lgo, double *weight_ess, int64_t *n_skipped, double *mu_lgo, double *pit_lgo,
+                                      int64_t *n_accumulated) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = lgo_refuse(h, "st_rows_loo_groups_get")) return rc;
+  if (n_accumulated) *n_accumulated = h->loo->n_acc;
+  if (const int rc = lgo_refuse(h, "st_rows_loo_groups_get", true)) return rc;
+  HCHK(h, hipSetDevice(h->device));
+  if (const int rc = lgo_finish(h)) return rc;
+  const LooGroups &G = *h->loo->grp;
+  const size_t ng = (size_t)G.lay.n_groups;
+  if (const int rc = download_to(h, G.d_gout.p, ng, elpd_lgo)) return rc;
+  if (const int rc = download_to(h, G.d_gout.p + ng, ng, weight_ess)) return rc;
+  if (n_skipped && ng) {
+    std::vector<double> ns;
+    if (const int rc = download_host(h, G.d_gacc.p + (size_t)LGO_NS * ng, ng, ns)) return rc;
+    for (size_t g = 0; g < ng; ++g) n_skipped[g] = (int64_t)ns[g];
+  }
+  double *const dst[2] = {mu_lgo, pit_lgo};
+  return download_planes(h, G.d_rows.p, h->n_all, 2, dst);
+}
+extern "C" int st_rows_loo_groups_totals(st_handle h, double *tot, double *by_outcome) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = lgo_refuse(h, "st_rows_loo_groups_totals", true)) return rc;
+  HCHK(h, hipSetDevice(h->device));
+  if (const int rc = lgo_finish(h)) return rc;
+  std::vector<double> t;
+  if (const int rc = download_host(h, h->loo->grp->d_tot.p, (size_t)LGO_NTOT + (size_t)h->q * LGO_NOUTC, t)) return rc;
+  if (tot) {
+    const double cnt = t[LGO_TOT_COUNT], sum = t[LGO_TOT_ELPD];
+    tot[ST_ROWS_LGO_ELPD] = sum;
+    tot[ST_ROWS_LGO_IC] = -2.0 * sum;
+    tot[ST_ROWS_LGO_SE] = cnt > 1.0 ? std::sqrt(cnt * t[LGO_TOT_ELPD_SQ] / (cnt - 1.0)) : std::nan("");   // the centred sum of squares
+    tot[ST_ROWS_LGO_MIN_ESS] = cnt > 0.0 ? t[LGO_TOT_MIN_ESS] : std::nan("");
+    tot[ST_ROWS_LGO_COUNT] = cnt;
+  }
+  if (by_outcome) std::copy(t.begin() + LGO_NTOT, t.end(), by_outcome);   // LGO_OUT_* = ST_ROWS_LGO_OUT_*
+  return ST_OK;
+}
 
 // ---- Pareto smoothing of the stored leave-one-out ratios (psis_kernels.hpp; the kernels and their launchers live in k_psis.hip) ----
 extern "C" int st_rows_loo_reserve(st_handle h, int64_t keep) {
@@ -358,7 +561,11 @@ extern "C" int st_rows_loo_reserve(st_handle h, int64_t keep) {
     if (const int rc = psis_check_draws("st_rows_loo_reserve", "keep", keep, h->err)) return rc;
   HCHK(h, hipSetDevice(h->device));
   HCHK(h, hipStreamSynchronize(h->stream));
-  if (keep == 0) { h->loo->psis.reset(); return ST_OK; }
+  if (keep == 0) {
+    h->loo->psis.reset();
+    if (h->loo->grp) return lgo_store(h, "st_rows_loo_reserve", *h->loo->grp, 0);
+    return ST_OK;
+  }
   const size_t n = (size_t)h->n_all, cnt = 3 * (size_t)keep * n;
   std::unique_ptr<PsisStore> ps(new PsisStore());   // the state takes it once every allocation has succeeded
   if (ps->d_store.alloc(cnt) != hipSuccess || ps->d_rows.alloc((size_t)PSIS_NOUT * n) != hipSuccess || ps->d_int.alloc(2 * n) != hipSuccess ||
@@ -372,6 +579,8 @@ extern "C" int st_rows_loo_reserve(st_handle h, int64_t keep) {
   }
   HCHK(h, hipMemsetAsync(ps->d_store.p, 0xff, cnt * sizeof(double), h->stream));   // all bits set: a NaN
   HCHK(h, hipStreamSynchronize(h->stream));
+  if (h->loo->grp)
+    if (const int rc = lgo_store(h, "st_rows_loo_reserve", *h->loo->grp, keep)) return rc;
   ps->keep = keep;
   h->loo->psis = std::move(ps);
   return ST_OK;
@@ -455,6 +664,33 @@ extern "C" int st_rows_loo_psis_totals(st_handle h, double *tot, int64_t *n_obs)
     if (tot) std::copy(s, s + PSIS_NSUM, tot + (size_t)j * ST_ROWS_PSIS_N);
   }
   return ST_OK;
+}
+// the groups' stored log ratios through the same kernel: one series per group, no companions
+static int lgo_psis_refuse(st_handle h, const char *who) {
+  if (const int rc = lgo_refuse(h, who)) return rc;
+  if (h->loo->grp->keep == 0) { h->err = std::string(who) + ": no store reserved (st_rows_loo_reserve before the first accumulate)"; return ST_ERR_USAGE; }
+  return lgo_refuse(h, who, true);
+}
+extern "C" int st_rows_loo_groups_draws(st_handle h, double *t) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = lgo_psis_refuse(h, "st_rows_loo_groups_draws")) return rc;
+  HCHK(h, hipSetDevice(h->device));
+  const LooGroups &G = *h->loo->grp;
+  return download_to(h, G.d_store.p, (size_t)h->loo->n_acc * (size_t)G.lay.n_groups, t);
+}
+extern "C" int st_rows_loo_groups_psis(st_handle h, double *khat, double *elpd_psis, double *weight_ess_psis, int32_t *tail_len, int32_t *n_draws) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = lgo_psis_refuse(h, "st_rows_loo_groups_psis")) return rc;
+  HCHK(h, hipSetDevice(h->device));
+  const RowsLoo &L = *h->loo;
+  LooGroups &G = *L.grp;
+  const long long ng = G.lay.n_groups;
+  if (G.psis_acc != L.n_acc) {
+    if (const int rc = psis_run(h, "st_rows_loo_groups_psis", ng, L.n_acc, G.d_store.p, nullptr, nullptr, G.d_prow.p, G.d_pint.p)) return rc;
+    G.psis_acc = L.n_acc;
+  }
+  const st_psis_out out = {khat, elpd_psis, nullptr, nullptr, weight_ess_psis, tail_len, n_draws};
+  return psis_download(h, ng, G.d_prow.p, G.d_pint.p, nullptr, &out, false, false);
 }
 extern "C" int st_psis(st_handle h, int64_t n, int64_t K, const double *t, const double *phi, const double *mu, const st_psis_out *out) {
   if (!h) return ST_ERR_USAGE;

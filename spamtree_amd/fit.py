@@ -12,6 +12,7 @@ import numpy as np
 from . import _lib
 from . import diagnostics as _diag
 from . import excursions as _exc
+from . import loo as _loo
 from .model import (SpamTreeError, _dp, _f64, _i64, _ip, _lists_to_csr, functionals_csr, joint_labels, rows_criteria, rows_holdout,
                     rows_loo_criteria, rows_psis_criteria, score_totals,
                     score_values, series_diag_buffers, series_diag_finish, excursion_spec, excursion_buffers, excursion_finish,
@@ -260,7 +261,8 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
                      sample_theta=True, sample_w=True, sample_predicts=True, seed=2021, device=0, reference_quirks=True,
                      new_points=None, new_draws=True, new_quantiles=(), save_w=True, save_yhat=True, force_generic=False,
                      criteria=False, y_holdout=None, holdout_crps=True, diagnostics=False, diagnostics_max_lag=0, excursions=None,
-                     rank_diagnostics=None, chains=1, chain_seeds=None, chain_theta=None, loo=False, psis=False, psis_draws=False):
+                     rank_diagnostics=None, chains=1, chain_seeds=None, chain_theta=None, loo=False, psis=False, psis_draws=False,
+                     loo_groups=None):
     """spamtree_fit.cpp:5-430 through the C++ driver.  `num_threads`, `use_alg`, the verbosity flags and `start_w` are
     accepted and ignored exactly where the reference ignores them (start_w, :95) or where they do not apply to a GPU.
 
@@ -310,6 +312,14 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     ``model.rows_psis_criteria``'s dict (``se``, ``max_khat``, the counts of rows with a large khat), and with ``psis_draws=True`` the
     pointwise matrices ``t``, ``phi``, ``mu`` (mcmc_keep x n).  The chain and every other output are the same bit for bit.
     ValueError before any device call: ``psis`` without ``loo``, ``mcmc_keep`` outside 1 .. 16384.
+    ``loo=True, loo_groups=labels``: leave-group-out criteria on top (``spamtree_amd.loo`` has the definition): one int64 label per
+    row, negative = in no group; the rows of one label (1 .. 16 of them, in blocks with an observed row) are left out together and
+    their rows of w integrated out jointly -- ``loo.site_groups(coords)`` labels all outcomes at a location, ``loo.block_groups(coords,
+    cell)`` square cells.  The same sweep serves rows and groups; ``criteria["loo"]`` is bit for bit that of the call without groups
+    and also holds ``groups``: dict(label, members (a list of row arrays), elpd_lgo, weight_ess, n_skipped per group; mu_lgo, pit_lgo
+    per row, NaN off the observed members; totals = dict(elpd_lgo, lgoic, se, min_weight_ess, n_groups, by_outcome)) and, with
+    ``psis=True``, the groups' ``khat``, ``elpd_psis`` and ``weight_ess_psis``.  ValueError before any device call: labels that are
+    not one integer per row, a group of more than 16 members or without an observed member, ``loo_groups`` without ``loo``.
     ``diagnostics=True``: the effective sample size ``ess``, the Monte-Carlo standard error of the posterior mean ``mcse``, the
     posterior sd of the draws ``sd``, the split-R-hat of the one chain ``rhat``, the lags used ``lags`` and whether the lag cap was
     hit ``truncated`` (``spamtree_amd.diagnostics`` has the definition; ``diagnostics_max_lag`` = 0 is its default cap of 1024
@@ -355,6 +365,7 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     rq = _check_request(y, X, mv_id, theta, limited_tree, mcmc_keep, sample_predicts, sample_w, seed, new_points, new_quantiles, criteria,
                         y_holdout, holdout_crps, diagnostics, diagnostics_max_lag, excursions, rank_diagnostics, chains, chain_seeds,
                         chain_theta, loo, psis, psis_draws)
+    rq.groups = _check_groups(loo_groups, rq.loo, y, indexing)
     M, keep_all, max_lag = rq.M, rq.keep_all, rq.max_lag
     lib = _lib.load()
     pb, keep, n, p, q = _problem(y, X, coords, mv_id, res_is_ref, parents, children, layer_names, layer_gibbs_group, indexing)
@@ -455,6 +466,23 @@ def _reported_driver(rq):
     if rq.exc is not None:
         return "stm_mcmc_excursions"
     return "stm_mcmc_diagnosed" if rq.diagnostics else None
+
+
+def _check_groups(loo_groups, loo, y, indexing):
+    """The labels of ``loo_groups`` as an int64 array after every check that needs no device (ValueError), or None."""
+    if loo_groups is None:
+        return None
+    if not loo:
+        raise ValueError("loo_groups labels the groups of the leave-group-out criteria: it needs loo=True")
+    labels = np.asarray(loo_groups)
+    y = np.asarray(y, dtype=np.float64).ravel()
+    if labels.shape != y.shape:
+        raise ValueError(f"loo_groups must be one integer label per row ({y.size}), got shape {labels.shape}")
+    obs = np.isfinite(y)
+    blocks = [np.asarray(ix, dtype=np.int64).ravel() for ix in indexing]
+    rows = np.concatenate([ix for ix in blocks if obs[ix].any()] + [np.zeros(0, dtype=np.int64)])   # the blocks of the density
+    _loo.group_index(labels, rows, obs)
+    return np.ascontiguousarray(labels, dtype=np.int64)
 
 
 def _check_request(y, X, mv_id, theta, limited_tree, mcmc_keep, sample_predicts, sample_w, seed, new_points, new_quantiles, criteria,
@@ -634,7 +662,31 @@ def _row_parts(req, rq, n, q, mcmc_keep):
                                                 i32(prow["tail_len"]), i32(prow["n_draws"])), _dp(ptot), _ip(pn_obs),
                                  *[_opt(pdraws.get(key)) for key in ("t", "phi", "mu")])
             ls.psis = C.pointer(ps)
+        if rq.groups is not None:
+            gcnt = [C.c_int64() for _ in range(3)]
+            gidx = dict(label=np.zeros(n, dtype=np.int64), ptr=np.zeros(n + 1, dtype=np.int64), rows=np.zeros(n, dtype=np.int64))
+            gout = {key: np.zeros(n) for key in ("elpd_lgo", "weight_ess", "mu_lgo", "pit_lgo", "khat", "elpd_psis", "weight_ess_psis")}
+            gskip = np.zeros(n, dtype=np.int64)
+            gtot, gby = np.zeros(len(_lib.ST_ROWS_LGO)), np.zeros((len(_lib.ST_ROWS_LGO_OUT), q), order="F")
+            gs = _lib.StmLooGroups(_ip(rq.groups), *[C.pointer(v) for v in gcnt], _ip(gidx["label"]), _ip(gidx["ptr"]), _ip(gidx["rows"]),
+                                   _dp(gout["elpd_lgo"]), _dp(gout["weight_ess"]), _ip(gskip), _dp(gout["mu_lgo"]), _dp(gout["pit_lgo"]),
+                                   _dp(gtot), _dp(gby), _dp(gout["khat"]), _dp(gout["elpd_psis"]), _dp(gout["weight_ess_psis"]))
+            ls.groups = C.pointer(gs)
         req.loo = C.pointer(ls)
+
+    def groups():
+        ng, nm = int(gcnt[0].value), int(gcnt[1].value)
+        res = dict(label=gidx["label"][:ng].copy(), members=[gidx["rows"][gidx["ptr"][g]:gidx["ptr"][g + 1]].copy() for g in range(ng)],
+                   n_pairs=int(gcnt[2].value), elpd_lgo=gout["elpd_lgo"][:ng].copy(), weight_ess=gout["weight_ess"][:ng].copy(),
+                   n_skipped=gskip[:ng].copy(), mu_lgo=gout["mu_lgo"], pit_lgo=gout["pit_lgo"])
+        tot = {key: float(gtot[i]) for i, key in enumerate(_lib.ST_ROWS_LGO)}
+        tot["n_groups"] = int(tot["n_groups"])
+        tot["by_outcome"] = {key: gby[i].copy() for i, key in enumerate(_lib.ST_ROWS_LGO_OUT)}
+        res["totals"] = tot
+        if rq.psis:
+            res.update({key: gout[key][:ng].copy() for key in ("khat", "elpd_psis", "weight_ess_psis")})
+        assert nm == sum(m.size for m in res["members"])
+        return res
 
     def criteria():
         res = {}
@@ -644,6 +696,8 @@ def _row_parts(req, rq, n, q, mcmc_keep):
             res["loo"] = dict(lrows, n_accumulated=int(lacc.value), n_skipped=int(lskip.value), totals=rows_loo_criteria(ltot, ln_obs))
             if rq.psis:
                 res["loo"]["psis"] = dict(prow, totals=rows_psis_criteria(ptot, pn_obs), **pdraws)
+            if rq.groups is not None:
+                res["loo"]["groups"] = groups()
         return res
     if rq.crit:
         out.criteria = criteria

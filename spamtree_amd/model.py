@@ -1025,6 +1025,83 @@ class SpamTreeMV:
             code += 1
         return dict(routes=routes, alg_bytes=float(by.value), flops=float(fl.value))
 
+    # ---- leave-group-out criteria: a group's rows integrated out jointly (st_rows_loo_groups_*; ``spamtree_amd.loo``)
+    def rows_loo_groups_set(self, labels):
+        """One int64 label per model row, negative = in no group (``loo.site_groups``, ``loo.block_groups``); after rows_loo_set,
+        before the first accumulate."""
+        labels = np.ascontiguousarray(labels, dtype=np.int64)
+        if labels.shape != (self.n_all,):
+            raise ValueError(f"labels must hold one value per row ({self.n_all}), got shape {labels.shape}")
+        self._check(self.lib.st_rows_loo_groups_set(self.h, _ip(labels)))
+
+    def rows_loo_groups_clear(self):
+        self._check(self.lib.st_rows_loo_groups_clear(self.h))
+
+    def rows_loo_groups_index(self):
+        """dict(label, ptr, rows, n_groups, n_members, n_pairs, n_matrix): group g has the model rows rows[ptr[g]:ptr[g + 1]]."""
+        c = [C.c_int64() for _ in range(4)]
+        self._check(self.lib.st_rows_loo_groups_count(self.h, *[C.byref(v) for v in c]))
+        ng, nm, npair, nsq = (int(v.value) for v in c)
+        label, ptr, rows = np.zeros(ng, dtype=np.int64), np.zeros(ng + 1, dtype=np.int64), np.zeros(nm, dtype=np.int64)
+        self._check(self.lib.st_rows_loo_groups_index(self.h, _ip(label), _ip(ptr), _ip(rows)))
+        return dict(label=label, ptr=ptr, rows=rows, n_groups=ng, n_members=nm, n_pairs=npair, n_matrix=nsq)
+
+    def rows_loo_groups_last(self):
+        """Per group of the last accumulate, lists of arrays: q_gg and cond_cov (g x g), qw and cond_mean (g)."""
+        ix = self.rows_loo_groups_index()
+        qg, cv = np.zeros(ix["n_matrix"]), np.zeros(ix["n_matrix"])
+        c, m = np.zeros(ix["n_members"]), np.zeros(ix["n_members"])
+        self._check(self.lib.st_rows_loo_groups_last(self.h, _dp(qg), _dp(c), _dp(m), _dp(cv)))
+        out = dict(q_gg=[], qw=[], cond_mean=[], cond_cov=[])
+        at = 0
+        for g in range(ix["n_groups"]):
+            a, b = int(ix["ptr"][g]), int(ix["ptr"][g + 1])
+            k = b - a
+            out["q_gg"].append(qg[at:at + k * k].reshape(k, k)); out["cond_cov"].append(cv[at:at + k * k].reshape(k, k))
+            out["qw"].append(c[a:b]); out["cond_mean"].append(m[a:b])
+            at += k * k
+        return out
+
+    def rows_loo_groups_get(self):
+        """dict(elpd_lgo, weight_ess, n_skipped per group; mu_lgo, pit_lgo per row, NaN off the observed members; n_accumulated)."""
+        ng = self.rows_loo_groups_index()["n_groups"]
+        out = dict(elpd_lgo=np.zeros(ng), weight_ess=np.zeros(ng), n_skipped=np.zeros(ng, dtype=np.int64), mu_lgo=np.zeros(self.n_all),
+                   pit_lgo=np.zeros(self.n_all))
+        cnt = C.c_int64()
+        self._check(self.lib.st_rows_loo_groups_get(self.h, _dp(out["elpd_lgo"]), _dp(out["weight_ess"]), _ip(out["n_skipped"]),
+                                                    _dp(out["mu_lgo"]), _dp(out["pit_lgo"]), C.byref(cnt)))
+        out["n_accumulated"] = int(cnt.value)
+        return out
+
+    def rows_loo_groups_totals(self):
+        """dict(elpd_lgo, lgoic, se, min_weight_ess, n_groups, by_outcome=dict(sqerr, pit, count: q values each))."""
+        tot = np.zeros(len(_lib.ST_ROWS_LGO))
+        by = np.zeros((len(_lib.ST_ROWS_LGO_OUT), self.q), order="F")
+        self._check(self.lib.st_rows_loo_groups_totals(self.h, _dp(tot), _dp(by)))
+        out = {k: float(tot[i]) for i, k in enumerate(_lib.ST_ROWS_LGO)}
+        out["n_groups"] = int(out["n_groups"])
+        out["by_outcome"] = {k: by[i].copy() for i, k in enumerate(_lib.ST_ROWS_LGO_OUT)}
+        return out
+
+    def rows_loo_groups_draws(self):
+        """The stored group log ratios t = -l, [n_accumulated][n_groups] (needs rows_loo_reserve)."""
+        ng = self.rows_loo_groups_index()["n_groups"]
+        cnt = C.c_int64()
+        self._check(self.lib.st_rows_loo_groups_get(self.h, None, None, None, None, None, C.byref(cnt)))
+        out = np.zeros((int(cnt.value), ng))
+        self._check(self.lib.st_rows_loo_groups_draws(self.h, _dp(out)))
+        return out
+
+    def rows_loo_groups_psis(self):
+        """dict(khat, elpd_psis, weight_ess_psis, tail_len, n_draws) per group: the Pareto smoothing of the stored group ratios."""
+        ng = self.rows_loo_groups_index()["n_groups"]
+        out = dict(khat=np.zeros(ng), elpd_psis=np.zeros(ng), weight_ess_psis=np.zeros(ng), tail_len=np.zeros(ng, dtype=np.int32),
+                   n_draws=np.zeros(ng, dtype=np.int32))
+        i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))   # noqa: E731
+        self._check(self.lib.st_rows_loo_groups_psis(self.h, _dp(out["khat"]), _dp(out["elpd_psis"]), _dp(out["weight_ess_psis"]),
+                                                     i32(out["tail_len"]), i32(out["n_draws"])))
+        return out
+
     # ---- Pareto smoothing of the leave-one-out weights (st_rows_loo_reserve / _draws / _psis*, st_psis; ``spamtree_amd.psis``)
     def rows_loo_reserve(self, keep):
         """Room for ``keep`` accumulated draws' (t, Phi, mu) on the device; after rows_loo_set, before the first accumulate.  0 frees."""
