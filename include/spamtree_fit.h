@@ -142,13 +142,31 @@ typedef struct stm_diagnostics {
 
 /* exc: exceedance maps, excursion functions and simultaneous bands (st_summary_excursions(rows_spec), st_points_summary_excursions
  * (new_spec), st_points_functionals_excursions(fun_spec)).  rows_spec and new_spec carry n_thr x q thresholds, fun_spec n_thr x
- * n_fun; their masks have n_all, n_new and n_fun bytes.  At least 1 stored draw, 2 with a band. */
+ * n_fun; their masks have n_all, n_new and n_fun bytes.  At least 1 stored draw, 2 with a band.
+ *
+ * rb: the Rao-Blackwellised exceedance probabilities at the new points (include/spamtree_hip.h, st_points_exceed_*): thr n_thr x q,
+ * side (NULL: all +1), thr_fun n_thr x n_fun (NULL: no functional part); new_w, new_yhat n_thr x n_new, fun_w n_thr x n_fun,
+ * n_accumulated one value; thr NULL or n_thr = 0 is no part.  It reads no store: it reserves nothing and raises no keep_draws, the stores' limit and minimum of draws
+ * do not apply to it, and an exc whose only content is rb is valid.  Refused before a chain exists (ST_ERR_USAGE): rb without a
+ * point set, a new_yhat output without X_new, fun_w without fun or without thr_fun, and what st_points_exceed_set refuses of the
+ * spec.  The thresholds are set once, after the point set and the functionals, and read out after the last chain: with several
+ * chains the state runs across them, pooled like the point summaries.  The chain is draw for draw the same with and without rb. */
+typedef struct stm_rb_exceed {
+  int32_t n_thr;
+  const double *thr;
+  const int32_t *side;
+  const double *thr_fun;
+  st_rb_out new_w, new_yhat, fun_w;
+  int64_t *n_accumulated;
+} stm_rb_exceed;
+
 typedef struct stm_excursions {
   int32_t want_rows;
   st_excursion_spec rows_spec, new_spec, fun_spec;
   st_excursion_out rows_w, rows_yhat;   /* n_all series, model row order */
   st_excursion_out new_w, new_yhat;     /* n_new series, caller order */
   st_excursion_out fun_w, fun_yhat;     /* n_fun series */
+  const stm_rb_exceed *rb;              /* NULL: none */
 } stm_excursions;
 
 /* rk: rank-normalised R-hat, bulk, tail, quantile and exceedance ESS (st_*_chain_rank_diagnostics).  rows_spec and new_spec carry

@@ -595,6 +595,34 @@ int st_points_functionals_info(st_handle h, int64_t *n_fun, int64_t *nnz, int64_
 int st_points_score_set(st_handle h, const double *y_new);
 int st_points_score_get(st_handle h, double *lpd, double *pit, double *crps, double *lpd_joint, int64_t *n_scored, int64_t *n_degenerate);
 
+/* ---- Rao-Blackwellised exceedance probabilities at the new points: the mean over the saved draws of the exact conditional
+ * probability, not a count over stored draws -- no reservation, no steps of 1 / K, no Monte-Carlo noise of the indicator.
+ * n_thr <= ST_EXC_MAX_THRESHOLDS thresholds, each with a side s_t in {+1, -1}; the value is per outcome, c = thr[t q + j] for a point
+ * of margin j, and thr_fun[t n_fun + f] for functional f.  Saved draw s gives (spamtree_amd/csrc/points_exceed.hpp has every
+ * operation's order):
+ *   point, target w:    m = cond_mean_s(i), v = cond_var_s(i) (clamped at 0; on a joint set max(Sigma_aa, 0)).  v > 0:
+ *                       p_s = Phi(s_t (m - c) / sqrt(v)), Phi(z) = erfc(-z / sqrt 2) / 2.  v == 0: p_s = 1 if s_t (m - c) > 0, else 0
+ *                       (strict, as the event of st_*_excursions).
+ *   point, target yhat: (needs X) mu = x_i'beta_j + m, sigma2 = v + 1 / tausq_inv_j, p_s = Phi(s_t (mu - c) / sigma).
+ *   functional, target w only: m = F_m, v = F_v of st_points_functionals_last, the same two rules.
+ * Over the S draws accumulated since the thresholds were set: prob = mean_s p_s (Welford, in call order) and prob_var = the
+ * population variance of p_s over the draws (the caller's MCSE is sqrt(prob_var / ESS)).  Nothing is NaN for a finite threshold.
+ * st_points_exceed_set: side NULL: all +1.  thr_fun NULL: no functional part; thr_fun needs functionals set.  n_thr = 0 or thr NULL
+ *   removes the thresholds.  ST_ERR_USAGE naming the index: n_thr outside 1 .. ST_EXC_MAX_THRESHOLDS, a threshold that is not
+ *   finite, a side other than +-1; the previous thresholds then stay.  Replaces the previous thresholds and zeroes their state
+ *   (16 n_thr B per point and target, nothing per draw); every other summary is left alone.  st_points_set / st_points_set_joint
+ *   drop the thresholds, st_points_summary_reset clears their state, st_points_functionals_set drops the functional part only.
+ * With thresholds set, st_points_accumulate(_joint) also runs the exceedance step after its functionals, on the same stream: it
+ *   consumes no draw of any stream and writes nothing another step reads, so every other output is the same bit for bit; with
+ *   NULL outputs it still copies nothing and synchronises nothing.  Without thresholds nothing is launched or allocated.
+ * st_points_exceed_get: w, yhat (n_thr x n_new, threshold-major, caller order), fun_w (n_thr x n_fun); any struct and either member
+ *   may be NULL.  ST_ERR_USAGE: before st_points_exceed_set, no iteration accumulated (n_accumulated is still written), yhat on
+ *   a set without X, fun_w without functional thresholds.  An empty point set returns ST_OK with nothing written.
+ * Both refuse limited_tree and world > 1 handles (ST_ERR_UNSUPPORTED). */
+typedef struct st_rb_out { double *prob, *prob_var; } st_rb_out;   /* n_thr x n, threshold-major; either may be NULL */
+int st_points_exceed_set(st_handle h, int32_t n_thr, const double *thr, const int32_t *side, const double *thr_fun);
+int st_points_exceed_get(st_handle h, const st_rb_out *w, const st_rb_out *yhat, const st_rb_out *fun_w, int64_t *n_accumulated);
+
 /* ---- criteria over the fit's own rows, on the device: WAIC and DIC over the observed rows, and the scores of held-out values at
  * NA rows of the problem (the reference's hold-out workflow: set part of y to NA, fit, compare yhat there with the truth).  All of
  * it is CONDITIONAL ON w: saved draw s gives row i of margin j the Gaussian N(mu_s, tau2_j), mu_s = XB_i + w_i, tau2_j = 1 / tausq_inv_j,

@@ -52,6 +52,10 @@ class StRankOut(C.Structure):         # st_rank_out: any pointer may be NULL
                 ("prob", C.POINTER(C.c_double))]
 
 
+class StRbOut(C.Structure):           # st_rb_out: n_thr x n, threshold-major; either may be NULL
+    _fields_ = [("prob", C.POINTER(C.c_double)), ("prob_var", C.POINTER(C.c_double))]
+
+
 class StPsisOut(C.Structure):         # st_psis_out: n values each, any pointer may be NULL
     _fields_ = [("khat", C.POINTER(C.c_double)), ("elpd_psis", C.POINTER(C.c_double)), ("pit_psis", C.POINTER(C.c_double)),
                 ("mu_psis", C.POINTER(C.c_double)), ("weight_ess_psis", C.POINTER(C.c_double)), ("tail_len", C.POINTER(C.c_int32)),
@@ -69,6 +73,7 @@ H = C.c_void_p
 c_sdp = C.POINTER(StSeriesDiag)
 c_xsp, c_xop = C.POINTER(StExcursionSpec), C.POINTER(StExcursionOut)
 c_rsp, c_rop = C.POINTER(StRankSpec), C.POINTER(StRankOut)
+c_rbp = C.POINTER(StRbOut)
 SIGNATURES = {
     "st_create": (C.c_int, [C.POINTER(StProblem), C.POINTER(StOptions), C.POINTER(H)]),
     "st_destroy": (C.c_int, [H]),
@@ -175,6 +180,8 @@ SIGNATURES = {
     "st_points_functionals_info": (C.c_int, [H, c_ip, c_ip, c_ip, c_ip, c_dp]),
     "st_points_score_set": (C.c_int, [H, c_dp]),
     "st_points_score_get": (C.c_int, [H, c_dp, c_dp, c_dp, c_dp, c_ip, c_ip]),
+    "st_points_exceed_set": (C.c_int, [H, C.c_int32, c_dp, C.POINTER(C.c_int32), c_dp]),
+    "st_points_exceed_get": (C.c_int, [H, c_rbp, c_rbp, c_rbp, c_ip]),
     "st_rows_score_set": (C.c_int, [H, c_dp]),
     "st_rows_score_clear": (C.c_int, [H]),
     "st_rows_score_accumulate": (C.c_int, [H]),
@@ -262,10 +269,15 @@ class StmDiagnostics(C.Structure):   # include/spamtree_fit.h, stm_diagnostics
                 ("new_w", StSeriesDiag), ("new_yhat", StSeriesDiag), ("fun_w", StSeriesDiag), ("fun_yhat", StSeriesDiag)]
 
 
+class StmRbExceed(C.Structure):      # include/spamtree_fit.h, stm_rb_exceed
+    _fields_ = [("n_thr", C.c_int32), ("thr", c_dp), ("side", C.POINTER(C.c_int32)), ("thr_fun", c_dp),
+                ("new_w", StRbOut), ("new_yhat", StRbOut), ("fun_w", StRbOut), ("n_accumulated", c_ip)]
+
+
 class StmExcursions(C.Structure):    # include/spamtree_fit.h, stm_excursions
     _fields_ = [("want_rows", C.c_int32), ("rows_spec", StExcursionSpec), ("new_spec", StExcursionSpec), ("fun_spec", StExcursionSpec),
                 ("rows_w", StExcursionOut), ("rows_yhat", StExcursionOut), ("new_w", StExcursionOut), ("new_yhat", StExcursionOut),
-                ("fun_w", StExcursionOut), ("fun_yhat", StExcursionOut)]
+                ("fun_w", StExcursionOut), ("fun_yhat", StExcursionOut), ("rb", C.POINTER(StmRbExceed))]
 
 
 class StmRankDiagnostics(C.Structure):    # include/spamtree_fit.h, stm_rank_diagnostics

@@ -480,6 +480,21 @@ int exc_spec_refused(const st_excursion_spec &sp, int64_t nvals, const st_excurs
   return 0;
 }
 
+bool any_out(const st_rb_out &o) { return o.prob || o.prob_var; }
+// what stm_mcmc_fit refuses of rb before a chain exists: the missing parts it needs, then what st_points_exceed_set would refuse of
+// the spec (q outcomes, n_fun functionals; fun NULL: none)
+int rb_refused(const stm_rb_exceed &rb, bool have_pts, const stm_functionals *fun, const double *X_new, int q) {
+  if (!have_pts) return ST_ERR_USAGE;
+  if (any_out(rb.new_yhat) && !X_new) return ST_ERR_USAGE;
+  if (any_out(rb.fun_w) && (!fun || !rb.thr_fun)) return ST_ERR_USAGE;
+  if (rb.n_thr < 1 || rb.n_thr > ST_EXC_MAX_THRESHOLDS) return ST_ERR_USAGE;
+  for (int64_t k = 0; k < (int64_t)rb.n_thr * q; ++k) if (!std::isfinite(rb.thr[k])) return ST_ERR_USAGE;
+  for (int t = 0; rb.side && t < rb.n_thr; ++t) if (rb.side[t] != 1 && rb.side[t] != -1) return ST_ERR_USAGE;
+  if (rb.thr_fun && !fun) return ST_ERR_USAGE;
+  for (int64_t k = 0; rb.thr_fun && k < (int64_t)rb.n_thr * fun->n_fun; ++k) if (!std::isfinite(rb.thr_fun[k])) return ST_ERR_USAGE;
+  return 0;
+}
+
 bool any_out(const st_rank_out &o) {
   return o.rhat_rank || o.rhat_bulk || o.rhat_fold || o.ess_bulk || o.ess_tail || o.lags_bulk || o.ess_q || o.ess_exc || o.mcse_prob || o.prob;
 }
@@ -665,6 +680,10 @@ extern "C" int stm_mcmc_fit(const stm_fit *fit) {
     if (e.pts && (rc = exc_spec_refused(exc->new_spec, r.pb->q, exc->new_w, exc->new_yhat, (int)total)) != 0) return rc;
     if (e.fun && (rc = exc_spec_refused(exc->fun_spec, fun->n_fun, exc->fun_w, exc->fun_yhat, (int)total)) != 0) return rc;
   }
+  // rb reads no store: no reservation, no limit, no minimum of draws.  (thr NULL or n_thr = 0: no part, as scores without y_new)
+  const stm_rb_exceed *const rb = (exc && exc->rb && exc->rb->thr && exc->rb->n_thr != 0) ? exc->rb : nullptr;
+  if (rb && !r.pb) return ST_ERR_USAGE;
+  if (rb && (rc = rb_refused(*rb, have_pts, fun, p.X_new, r.pb->q)) != 0) return rc;
   if ((rc = wanted_of(rk, have_pts, fun, p.X_new, &k)) != 0) return rc;
   if (k.any()) {
     if ((rc = stored(k, ST_DIAG_MIN_DRAWS)) != 0) return rc;
@@ -715,6 +734,7 @@ extern "C" int stm_mcmc_fit(const stm_fit *fit) {
   std::vector<double> cov_scratch;   // the packed blocks of every draw when only new_cond_var is wanted of them
   if (rc == 0 && fun) rc = stm_points_functionals_set(c, fun->n_fun, fun->ptr, fun->idx, fun->wt);
   if (rc == 0 && scores) rc = stm_points_score_set(c, scores->y_new);
+  if (rc == 0 && rb && (rc = st_points_exceed_set(c->h, rb->n_thr, rb->thr, rb->side, rb->thr_fun)) != 0) c->err = st_last_error(c->h);
   if (rc == 0 && p.joint_id_new) {
     rc = st_points_joint_layout(c->h, &nj, nullptr, nullptr, nullptr);
     joff.resize(nj + 1); jptr.resize(nj + 1); jmem.resize(p.n_new);
@@ -769,6 +789,9 @@ extern "C" int stm_mcmc_fit(const stm_fit *fit) {
                                         fun->fun_yhat_q ? fun->fun_yhat_q + (size_t)i * fun->n_fun : nullptr);
   if (rc == 0 && scores && saved)
     rc = st_points_score_get(c->h, scores->lpd, scores->pit, scores->crps, scores->lpd_joint, scores->n_scored, scores->n_degenerate);
+  if (rc == 0 && rb && saved)
+    rc = st_points_exceed_get(c->h, &rb->new_w, any_out(rb->new_yhat) ? &rb->new_yhat : nullptr, any_out(rb->fun_w) ? &rb->fun_w : nullptr,
+                              rb->n_accumulated);
   if (rc == 0 && d.rows) rc = st_summary_chain_diagnostics(c->h, M, diag->max_lag, &diag->rows_w, &diag->rows_yhat);
   if (rc == 0 && d.pts)
     rc = st_points_summary_chain_diagnostics(c->h, M, diag->max_lag, &diag->new_w, any_out(diag->new_yhat) ? &diag->new_yhat : nullptr);

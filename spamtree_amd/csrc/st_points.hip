@@ -1,11 +1,11 @@
 // st_points.hip -- the C-ABI of new-point prediction (st_points_*): the device step of st_points_set / st_points_set_joint, predict,
 // accumulate, the running summaries, the linear functionals of the predictions (st_points_functionals_*) and the scores of
-// held-out observations (st_points_score_*).  The summaries of the stored draws -- quantiles, diagnostics, excursions, rank
+// held-out observations (st_points_score_*) and the Rao-Blackwellised exceedance probabilities (st_points_exceed_*).  The summaries of the stored draws -- quantiles, diagnostics, excursions, rank
 // diagnostics of the points and of the functionals -- are a resolver each (points_store, fun_store) and the store_* calls of
 // draw_store.hpp, which the fit's rows go through too.
-// predict_points.hpp, predict_joint.hpp, points_fun.hpp and points_score.hpp have the model; the launch structures of a point set and the term lists
+// predict_points.hpp, predict_joint.hpp, points_fun.hpp, points_score.hpp and points_exceed.hpp have the model; the launch structures of a point set and the term lists
 // of its functionals are built without a device call in points_layout.cpp; the kernels and their launchers live in k_predict.hip,
-// k_predict_joint.hip, k_points_acc.hip, k_points_fun.hip and k_points_score.hip.
+// k_predict_joint.hip, k_points_acc.hip, k_points_fun.hip, k_points_score.hip and k_points_exceed.hip.
 #include <memory>
 
 #include "st_handle.hpp"
@@ -13,6 +13,7 @@
 #include "draw_store.hpp"
 #include "points_layout.hpp"
 #include "points_score.hpp"
+#include "points_exceed.hpp"
 
 // The functionals of a point set (st_points_functionals_set): the term lists and chunks on the device, their accumulators, the
 // values of the last iteration and, with a reservation, the draws F_w and F_y, [keep][n_fun] each
@@ -34,6 +35,17 @@ struct ScoreSet {
   std::vector<char> pt_obs, grp_obs;   // per point / joint group: scored (a group: any member observed)
   DevBuf<double> d_y, d_acc, d_jacc, d_crps;
   DevBuf<unsigned long long> d_ndeg;
+};
+
+// The thresholds of the Rao-Blackwellised exceedance probabilities (st_points_exceed_set): the values on the device, n_thr x q for
+// the points and, with a functional part, n_thr x n_fun; the running state of every point ([targets][n_thr][2][n], targets = 2
+// with X) and functional ([n_thr][2][n_fun])
+struct ExceedSet {
+  int n_thr = 0;
+  unsigned side_neg = 0;           // bit t: s_t = -1
+  bool fun = false;                // thr_fun given
+  long long n_acc = 0;
+  DevBuf<double> d_thr, d_acc, d_thr_fun, d_facc;
 };
 
 struct PointSet : PointsCounts {
@@ -60,6 +72,7 @@ struct PointSet : PointsCounts {
   DevBuf<double> d_jout, d_jscratch, d_pacc;   // cov and chol of the last call (2 x cov_total); scratch; pair accumulators
   std::unique_ptr<FunSet> fun;                 // st_points_functionals_set; leaves with the point set
   std::unique_ptr<ScoreSet> score;             // st_points_score_set; leaves with the point set
+  std::unique_ptr<ExceedSet> exceed;           // st_points_exceed_set; leaves with the point set
 };
 
 void points_free(st_handle_s *h) {
@@ -345,6 +358,38 @@ static int score_step(st_handle h, PointSet *ps) {
   return ST_OK;
 }
 
+// ---- the exceedance probabilities' share of reset and accumulate (the entry points follow the scores) ----
+static int exceed_reset(st_handle h, ExceedSet *ex) {
+  if (ex->d_acc.p) HCHK(h, hipMemsetAsync(ex->d_acc.p, 0, ex->d_acc.n * sizeof(double), h->stream));
+  if (ex->d_facc.p) HCHK(h, hipMemsetAsync(ex->d_facc.p, 0, ex->d_facc.n * sizeof(double), h->stream));
+  ex->n_acc = 0;
+  return ST_OK;
+}
+
+// the exceedance step of one saved iteration: after fun_step, on the same stream, from d_out, d_X, d_B, d_tsq and the
+// functionals' d_last.  An empty set counts the iteration and launches nothing.
+static int exceed_step(st_handle h, PointSet *ps) {
+  ExceedSet *ex = ps->exceed.get();
+  const long long n = ps->n;
+  ex->n_acc += 1;
+  if (n == 0) return ST_OK;
+  const double *o = ps->d_out.p;
+  ProfScope pscope(h, 6);
+  ExceedArgs A;
+  A.mean = o + n; A.var = o + 2 * n; A.X = ps->has_X ? ps->d_X.p : nullptr; A.B = h->d_B.p; A.tsq_inv = h->d_tsq.p; A.pmv = ps->d_pmv.p;
+  A.thr = ex->d_thr.p; A.side_neg = ex->side_neg; A.n_thr = ex->n_thr; A.p = h->p; A.q = h->q; A.n = n;
+  A.count = (double)ex->n_acc; A.acc = ex->d_acc.p;
+  int e = points_exceed_launch(A, h->stream);
+  if (!e && ex->fun && ps->fun) {
+    ExceedFunArgs F;
+    F.last = ps->fun->d_last.p; F.thr = ex->d_thr_fun.p; F.side_neg = ex->side_neg; F.n_thr = ex->n_thr; F.n_fun = ps->fun->n_fun;
+    F.count = A.count; F.acc = ex->d_facc.p;
+    e = points_exceed_fun_launch(F, h->stream);
+  }
+  if (e) return launch_failed(h, "st_points_accumulate", e);
+  return ST_OK;
+}
+
 // ---- predictive summaries of the point set over saved iterations (st_points_accumulate; the kernel lives in k_points_acc.hip) ----
 extern "C" int st_points_summary_reset(st_handle h) {
   if (!h) return ST_ERR_USAGE;
@@ -360,6 +405,8 @@ extern "C" int st_points_summary_reset(st_handle h) {
   ps->n_acc = 0; ps->n_kept = 0;
   if (ps->score)
     if (const int rc = score_reset(h, ps->score.get())) return rc;
+  if (ps->exceed)
+    if (const int rc = exceed_reset(h, ps->exceed.get())) return rc;
   if (ps->fun) return fun_reset(h, ps->fun.get());
   return ST_OK;
 }
@@ -394,6 +441,7 @@ static int points_accumulate(st_handle h, uint64_t seed, uint32_t iter, double *
   if (ps->n == 0) {   // functionals of an empty set have no term: zeros
     ps->n_acc += 1;
     if (ps->score) (void)score_step(h, ps);   // counts the iteration; an empty set launches nothing
+    if (ps->exceed) (void)exceed_step(h, ps); // likewise
     if (!ps->fun) return ST_OK;
     HCHK(h, hipSetDevice(h->device));
     return fun_step(h, ps);
@@ -430,6 +478,8 @@ static int points_accumulate(st_handle h, uint64_t seed, uint32_t iter, double *
     if (const int rcs = score_step(h, ps)) return rcs;
   if (ps->fun)
     if (const int rcf = fun_step(h, ps)) return rcf;
+  if (ps->exceed)
+    if (const int rce = exceed_step(h, ps)) return rce;
   double *const dst[4] = {w_new, cond_mean, cond_var, yhat_new};
   return points_copy_out(h, ps, dst, cond_cov, cond_chol, false);
 }
@@ -544,6 +594,10 @@ extern "C" int st_points_functionals_set(st_handle h, int64_t n_fun, const int64
   if (const int rc = functionals_layout(F, n_fun, ptr, idx, wt, L, h->err)) return rc;   // the previous functionals stay
   HCHK(h, hipSetDevice(h->device));
   HCHK(h, hipStreamSynchronize(h->stream));
+  if (ps->exceed) {   // thresholds per functional belong to the functionals they were given for
+    ps->exceed->fun = false;
+    ps->exceed->d_thr_fun.free(); ps->exceed->d_facc.free();
+  }
   if (n_fun == 0) { ps->fun.reset(); return ST_OK; }
   std::unique_ptr<FunSet> fs(new FunSet());   // the point set takes it once every upload has succeeded
   fs->n_fun = L.n_fun; fs->nnz = L.nnz; fs->n_var_terms = L.n_var_terms;
@@ -714,5 +768,84 @@ extern "C" int st_points_score_get(st_handle h, double *lpd, double *pit, double
   }
   for (long long k = 0; lpd_joint && k < ps->n_joint; ++k) lpd_joint[k] = sc->grp_obs[k] ? lme(jacc[2 * k], jacc[2 * k + 1]) : nan;
   if (n_degenerate) *n_degenerate = (int64_t)ndeg;
+  return ST_OK;
+}
+
+// ---- Rao-Blackwellised exceedance probabilities at the point set (points_exceed.hpp)
+extern "C" int st_points_exceed_set(st_handle h, int32_t n_thr, const double *thr, const int32_t *side, const double *thr_fun) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_exceed_set")) return rc;
+  PointSet *ps = h->pts;
+  const bool remove = n_thr == 0 || !thr;
+  const long long nf = ps->fun ? ps->fun->n_fun : 0;
+  if (!remove) {   // a refusal leaves the previous thresholds in place
+    const std::string W = "st_points_exceed_set: ";
+    if (n_thr < 1 || n_thr > ST_EXC_MAX_THRESHOLDS) { h->err = W + "n_thr = " + std::to_string(n_thr) + " must lie in 1 .. " + std::to_string(ST_EXC_MAX_THRESHOLDS); return ST_ERR_USAGE; }
+    for (long long k = 0; k < (long long)n_thr * h->q; ++k)
+      if (!std::isfinite(thr[k])) { h->err = W + "thr[" + std::to_string(k) + "] is not finite"; return ST_ERR_USAGE; }
+    for (int t = 0; side && t < n_thr; ++t)
+      if (side[t] != 1 && side[t] != -1) { h->err = W + "side[" + std::to_string(t) + "] = " + std::to_string(side[t]) + " is neither +1 nor -1"; return ST_ERR_USAGE; }
+    if (thr_fun && !ps->fun) { h->err = W + "thr_fun before st_points_functionals_set"; return ST_ERR_USAGE; }
+    for (long long k = 0; thr_fun && k < (long long)n_thr * nf; ++k)
+      if (!std::isfinite(thr_fun[k])) { h->err = W + "thr_fun[" + std::to_string(k) + "] is not finite"; return ST_ERR_USAGE; }
+  }
+  HCHK(h, hipSetDevice(h->device));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  if (remove) { ps->exceed.reset(); return ST_OK; }
+  std::unique_ptr<ExceedSet> ex(new ExceedSet());   // the point set takes it once every upload has succeeded
+  ex->n_thr = n_thr;
+  for (int t = 0; side && t < n_thr; ++t) ex->side_neg |= (side[t] < 0 ? 1u : 0u) << t;
+  ex->fun = thr_fun != nullptr;
+  HCHK(h, ex->d_thr.upload(std::vector<double>(thr, thr + (size_t)n_thr * h->q)));
+  HCHK(h, ex->d_acc.alloc((size_t)(ps->has_X ? 2 : 1) * n_thr * 2 * ps->n));
+  if (thr_fun) {
+    HCHK(h, ex->d_thr_fun.upload(std::vector<double>(thr_fun, thr_fun + (size_t)n_thr * nf)));
+    HCHK(h, ex->d_facc.alloc((size_t)n_thr * 2 * nf));
+  }
+  if (const int rc = exceed_reset(h, ex.get())) return rc;
+  ps->exceed = std::move(ex);
+  return ST_OK;
+}
+
+// prob and prob_var of one target from its [n_thr][2][m] state after S draws (either output may be NULL)
+static void exceed_read_out(const double *acc, int n_thr, long long m, double S, const st_rb_out *out) {
+  for (int t = 0; t < n_thr; ++t)
+    for (long long i = 0; i < m; ++i) {
+      if (out->prob) out->prob[(size_t)t * m + i] = acc[((size_t)t * 2 + EX_MEAN) * m + i];
+      if (out->prob_var) out->prob_var[(size_t)t * m + i] = acc[((size_t)t * 2 + EX_M2) * m + i] / S;
+    }
+}
+
+extern "C" int st_points_exceed_get(st_handle h, const st_rb_out *w, const st_rb_out *yhat, const st_rb_out *fun_w, int64_t *n_accumulated) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_exceed_get")) return rc;
+  PointSet *ps = h->pts;
+  ExceedSet *ex = ps->exceed.get();
+  if (!ex) { h->err = "st_points_exceed_get before st_points_exceed_set"; return ST_ERR_USAGE; }
+  if (n_accumulated) *n_accumulated = ex->n_acc;
+  if (ex->n_acc == 0) { h->err = "st_points_exceed_get: no iteration accumulated"; return ST_ERR_USAGE; }
+  if (yhat && !ps->has_X) { h->err = "st_points_exceed_get: the yhat target needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  if (fun_w && !(ex->fun && ps->fun)) { h->err = "st_points_exceed_get: fun_w without functional thresholds (thr_fun of st_points_exceed_set)"; return ST_ERR_USAGE; }
+  const long long n = ps->n;
+  if (n == 0) return ST_OK;   // nothing to write: the functionals of an empty set have no term either
+  HCHK(h, hipSetDevice(h->device));
+  const int T = ex->n_thr;
+  const double S = (double)ex->n_acc;
+  const size_t per = (size_t)T * 2 * n;
+  std::vector<double> acc, facc;
+  const bool want_w = w && (w->prob || w->prob_var), want_y = yhat && (yhat->prob || yhat->prob_var);
+  const bool want_f = fun_w && (fun_w->prob || fun_w->prob_var);
+  if (want_w || want_y) {
+    acc.resize(ex->d_acc.n);
+    HCHK(h, hipMemcpyAsync(acc.data(), ex->d_acc.p, acc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  if (want_f) {
+    facc.resize(ex->d_facc.n);
+    HCHK(h, hipMemcpyAsync(facc.data(), ex->d_facc.p, facc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  HCHK(h, hipStreamSynchronize(h->stream));
+  if (want_w) exceed_read_out(acc.data(), T, n, S, w);
+  if (want_y) exceed_read_out(acc.data() + per, T, n, S, yhat);
+  if (want_f) exceed_read_out(facc.data(), T, ps->fun->n_fun, S, fun_w);
   return ST_OK;
 }

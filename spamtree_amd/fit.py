@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _lib
 from . import diagnostics as _diag
+from . import exceed as _rb
 from . import excursions as _exc
 from . import loo as _loo
 from .model import (SpamTreeError, _dp, _f64, _i64, _ip, _lists_to_csr, functionals_csr, joint_labels, rows_criteria, rows_holdout,
@@ -187,9 +188,9 @@ class PointsInputs(NamedTuple):
 def _points_inputs(new_points, p, q, new_quantiles):
     """Checks the point set of spamtree_mv_mcmc(new_points=...) against itself and the problem, before any device call."""
     pts = dict(new_points)
-    unknown = set(pts) - {"coords", "mv", "anchor", "X", "joint", "functionals", "y", "crps"}
+    unknown = set(pts) - {"coords", "mv", "anchor", "X", "joint", "functionals", "y", "crps", "exceed"}
     if unknown:
-        raise ValueError(f"new_points: unknown keys {sorted(unknown)} (coords, mv, anchor, X, joint, functionals, y, crps)")
+        raise ValueError(f"new_points: unknown keys {sorted(unknown)} (coords, mv, anchor, X, joint, functionals, y, crps, exceed)")
     coords = np.asarray(pts["coords"], dtype=np.float64)
     if coords.ndim != 2 or coords.shape[1] != 2:
         raise ValueError("new_points: coords must be n_new x 2")
@@ -236,6 +237,18 @@ def _points_inputs(new_points, p, q, new_quantiles):
     if "crps" in pts and y is None:
         raise ValueError("new_points: crps needs y")
     return PointsInputs(np.asfortranarray(coords), _i64(mv), _i64(anchor), X, qs, labels, fun, y, crps)
+
+
+def _exceed_inputs(new_points, pts, q):
+    """``new_points["exceed"]`` checked against the point set ``pts`` (_points_inputs') before any device call: exceed.check_spec's
+    (thr, side, thr_fun), or None without the key."""
+    spec = dict(new_points).get("exceed")
+    if spec is None:
+        return None
+    try:
+        return _rb.check_spec(spec, q, None if pts.functionals is None else pts.functionals[0].size - 1)
+    except (ValueError, TypeError) as e:
+        raise ValueError(f"new_points: {e}") from None
 
 
 def _joint_layout(labels):
@@ -288,6 +301,13 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     predictive density, and ``model.score_totals``' means, with the coverage of [yhat_lo, yhat_hi] for the lowest and highest of
     two or more ``new_quantiles``.  The CRPS makes the device keep ``mcmc_keep`` draws of w and yhat per point (16 B each per
     point and draw; at most 16384 draws, more is a ValueError); ``new_points["crps"] = False`` scores without it and stores nothing.
+    ``new_points["exceed"] = dict(thresholds=, side=, thresholds_fun=)``: Rao-Blackwellised exceedance probabilities
+    (``spamtree_amd.exceed``; thresholds as for ``excursions``: up to 8, each a scalar or one value per outcome, sides +-1) -- on
+    every saved iteration the exact conditional probability of w* (and, with ``X``, yhat*) lying beyond each threshold is folded
+    into a running mean and variance on the device, so nothing per draw is stored and ``new_draws=False`` stays lean.  ``new``
+    then also holds ``exceed``: dict(thr, side, w=dict(prob, prob_var), yhat=the same or None, n_accumulated), T x n_new arrays
+    (``prob_var``: the population variance of the per-draw probabilities, MCSE = sqrt(prob_var / ESS)), and with
+    ``thresholds_fun`` (one value per functional) ``new["functionals"]["exceed"]`` for the functionals' w.
     ``criteria=True``: WAIC and DIC over the observed rows, on the device (stm_mcmc_criteria; the chain is the same bit for bit, and
     nothing per draw comes to the host, so it works with ``save_w=False, save_yhat=False``).  ``y_holdout``: the truth at NA rows
     of ``y`` (one value per row, NaN = none; ``model.rows_holdout`` checks it), scored there on every saved iteration; it implies
@@ -570,10 +590,11 @@ def _check_request(y, X, mv_id, theta, limited_tree, mcmc_keep, sample_predicts,
         if want_crps and int(mcmc_keep) > MAX_STORED_DRAWS:
             raise ValueError(f"y_holdout: the CRPS keeps mcmc_keep = {int(mcmc_keep)} draws per row on the device, at most "
                              f"{MAX_STORED_DRAWS} (holdout_crps=False scores without it)")
-    pts = None
+    pts = rb_spec = None
     q_out = int(np.unique(_i64(mv_id)).size)
     if new_points is not None:
         pts = _points_inputs(new_points, np.asarray(X).shape[1], q_out, new_quantiles)
+        rb_spec = _exceed_inputs(new_points, pts, q_out)
         if pts.crps and int(mcmc_keep) > MAX_STORED_DRAWS:
             raise ValueError(f"new_points: the CRPS keeps mcmc_keep = {int(mcmc_keep)} draws per point on the device, at most "
                              f"{MAX_STORED_DRAWS} (crps=False scores without it)")
@@ -607,7 +628,7 @@ def _check_request(y, X, mv_id, theta, limited_tree, mcmc_keep, sample_predicts,
         elif rank.get("thresholds_fun") is not None:
             raise ValueError("rank_diagnostics: thresholds_fun needs new_points")
     return SimpleNamespace(crit_cond=crit_cond, loo=loo, psis=psis, psis_draws=bool(psis_draws), crit=crit, M=M, keep_all=keep_all, seeds=seeds, theta0=theta0, rank=rank, exc=exc,
-                           diagnostics=diagnostics, max_lag=int(diagnostics_max_lag), y_hold=y_hold, want_crps=want_crps, pts=pts)
+                           diagnostics=diagnostics, max_lag=int(diagnostics_max_lag), y_hold=y_hold, want_crps=want_crps, pts=pts, exceed=rb_spec)
 
 
 def _row_parts(req, rq, n, q, mcmc_keep):
@@ -709,6 +730,7 @@ def _point_parts(lib, req, rq, rows, q, mcmc_keep, new_draws):
     the points' and functionals' members of ``rows.ds``, ``rows.xs`` and ``rows.rs``.  Returns the function that forms ``new`` of the
     result after the call."""
     pc, pmv, pan, pX, qs, labels, fun, ynew, want_crps = rq.pts
+    rb = rq.exceed
     keep_all, has_X = rq.keep_all, pX is not None
     n_new = pc.shape[0]
 
@@ -778,6 +800,23 @@ def _point_parts(lib, req, rq, rows, q, mcmc_keep, new_draws):
         summaries.append(("rank_diagnostics", lambda v: rank_finish(v, mcmc_keep, rank["max_lag"]),
                           stored(rs, lambda name, m, want: rank_buffers(m, *counts[name], want))))
 
+    if rb is not None:        # the Rao-Blackwellised exceedance probabilities: a member of the excursions' part that reads no store
+        rthr, rside, rthr_fun = rb
+
+        def rb_bufs(m, want=True):
+            d = dict(prob=np.zeros((rthr.shape[0], m)), prob_var=np.zeros((rthr.shape[0], m))) if want else None
+            return d, (_lib.StRbOut(_dp(d["prob"]), _dp(d["prob_var"])) if want else _lib.StRbOut())
+        rb_w, rb_sw = rb_bufs(n_new)
+        rb_y, rb_sy = rb_bufs(n_new, has_X)
+        rb_f, rb_sf = rb_bufs(sets.get("fun", 0), rthr_fun is not None)
+        rb_acc = C.c_int64()
+        rbs = _lib.StmRbExceed(rthr.shape[0], _dp(rthr), rside.ctypes.data_as(C.POINTER(C.c_int32)), _opt(rthr_fun), rb_sw, rb_sy, rb_sf,
+                               C.pointer(rb_acc))
+        if rows.xs is None:   # an exc whose only content is rb
+            rows.xs = _lib.StmExcursions()
+            req.exc = C.pointer(rows.xs)
+        rows.xs.rb = C.pointer(rbs)
+
     def result():
         names, code = [], 1
         while lib.st_points_route_name(code) is not None:
@@ -801,6 +840,10 @@ def _point_parts(lib, req, rq, rows, q, mcmc_keep, new_draws):
             lo_hi = (yq[:, int(np.argmin(qs))], yq[:, int(np.argmax(qs))]) if qs.size >= 2 else (None, None)
             sc["totals"] = score_totals(sc, ynew, pmv, q, *lo_hi)
             new["scores"] = sc
+        if rb is not None and mcmc_keep > 0:
+            new["exceed"] = dict(thr=rthr, side=rside, w=rb_w, yhat=rb_y, n_accumulated=int(rb_acc.value))
+            if rb_f is not None:
+                new["functionals"]["exceed"] = dict(thr=rthr_fun, side=rside, w=rb_f, n_accumulated=int(rb_acc.value))
         for key, finish, by_set in summaries:
             for name, bufs in by_set.items() if n_new > 0 else ():
                 (new if name == "new" else new["functionals"])[key] = {k: finish(v) for k, v in bufs.items()}

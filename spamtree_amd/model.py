@@ -12,6 +12,7 @@ import numpy as np
 
 from . import _lib
 from . import diagnostics as _diag
+from . import exceed as _rb
 from . import excursions as _exc
 
 
@@ -684,6 +685,7 @@ class SpamTreeMV:
         self.points_have_X = Xf is not None
         self.n_functionals = 0       # a new point set has none
         self.score_y = None          # ... and no scores
+        self.exceed_spec = None      # ... and no exceedance thresholds
         self.points_mv = mv
 
     def unpack_joint(self, packed):
@@ -757,6 +759,8 @@ class SpamTreeMV:
         ptr, idx, wt = functionals_csr(A, self.n_points) if A is not None else (np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros(0))
         self._check(self.lib.st_points_functionals_set(self.h, ptr.size - 1, _ip(ptr), _ip(idx), _dp(wt)))
         self.n_functionals = ptr.size - 1
+        if getattr(self, "exceed_spec", None) is not None:   # the library drops the functional part of the thresholds
+            self.exceed_spec = self.exceed_spec[:2] + (None,)
 
     def functionals_last(self):
         """F_w, F_m, F_v, F_y of the last accumulated iteration: dict(w, cond_mean, cond_var, yhat), yhat None without X."""
@@ -822,6 +826,47 @@ class SpamTreeMV:
                                                  _dp(out["lpd_joint"]) if joint else None, C.byref(ns), C.byref(nd)))
         out.update(n_scored=int(ns.value), n_degenerate=int(nd.value))
         out["totals"] = score_totals(out, self.score_y, self.points_mv, self.q, yhat_lo, yhat_hi)
+        return out
+
+    # ---- Rao-Blackwellised exceedance probabilities at the point set (st_points_exceed_*; spamtree_amd.exceed has the definition)
+    def set_exceed(self, thresholds, side=1, thresholds_fun=None):
+        """Thresholds of the exceedance probabilities P(w* > c) (side +1) or P(w* < c) (side -1) and, with X, of yhat*:
+        ``thresholds`` a scalar or up to 8 entries, each a scalar or one value per outcome; ``side`` a scalar or one per threshold;
+        ``thresholds_fun`` likewise with one value per functional (needs set_functionals).  None removes them.  Every
+        accumulate_points then also folds each draw's exact conditional probability into a running mean and variance on the
+        device: nothing per draw is stored."""
+        if thresholds is None:
+            self._check(self.lib.st_points_exceed_set(self.h, 0, None, None, None))
+            self.exceed_spec = None
+            return
+        thr, sd, thr_fun = _rb.check_spec(dict(thresholds=thresholds, side=side, thresholds_fun=thresholds_fun), self.q,
+                                          getattr(self, "n_functionals", 0))
+        self._check(self.lib.st_points_exceed_set(self.h, thr.shape[0], _dp(thr), sd.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  _dp(thr_fun) if thr_fun is not None else None))
+        self.exceed_spec = (thr, sd, thr_fun)
+
+    def exceed(self):
+        """The exceedance probabilities over the iterations accumulated since set_exceed: dict(thr, side, w=dict(prob, prob_var),
+        yhat=the same or None without X, n_accumulated), the arrays T x n_points in the caller's order; with ``thresholds_fun``
+        also ``functionals=dict(thr, w=dict(prob, prob_var))``, T x n_functionals.  ``prob_var`` is the population variance of the
+        per-draw probabilities: the MCSE of ``prob`` is sqrt(prob_var / ESS)."""
+        if getattr(self, "exceed_spec", None) is None:
+            raise ValueError("exceed before set_exceed")
+        thr, sd, thr_fun = self.exceed_spec
+        T, n = thr.shape[0], self.n_points
+
+        def bufs(m):
+            d = dict(prob=np.zeros((T, m)), prob_var=np.zeros((T, m)))
+            return d, _lib.StRbOut(_dp(d["prob"]), _dp(d["prob_var"]))
+        w, sw = bufs(n)
+        y, sy = bufs(n) if self.points_have_X else (None, None)
+        f, sf = bufs(self.n_functionals) if thr_fun is not None else (None, None)
+        cnt = C.c_int64()
+        self._check(self.lib.st_points_exceed_get(self.h, C.byref(sw), C.byref(sy) if sy is not None else None,
+                                                  C.byref(sf) if sf is not None else None, C.byref(cnt)))
+        out = dict(thr=thr.copy(), side=sd.copy(), w=w, yhat=y, n_accumulated=int(cnt.value))
+        if f is not None:
+            out["functionals"] = dict(thr=thr_fun.copy(), w=f)
         return out
 
     # ---- convergence diagnostics of the stored draws (st_*_diagnostics; spamtree_amd.diagnostics has the definition)

@@ -17,6 +17,7 @@ from typing import Optional
 
 import numpy as np
 
+from . import exceed as _rb
 from . import excursions as _exc
 from . import fit
 from .model import SpamTreeMV, _dp, _f64, functionals_csr, joint_labels, score_values
@@ -107,7 +108,7 @@ def conditioning_set(topo: Topology, anchor: int) -> np.ndarray:
 
 def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, return_draws=True, device=0, z=None,
                 mode=0, force_generic=False, return_moments=False, joint=None, functionals=None, y_new=None, quantiles=(),
-                crps=True, diagnostics=False, diagnostics_max_lag=0, excursions=None, rank_diagnostics=None):
+                crps=True, diagnostics=False, diagnostics_max_lag=0, excursions=None, rank_diagnostics=None, exceed=None):
     """Predictive at new locations for every saved draw of a chain.
 
     ``model_inputs``: the problem as ``spamtree_mv_mcmc`` took it (the dict of ``synthetic.make_workload``; its ``topo``
@@ -151,6 +152,11 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
     quantile and exceedance ESS of the points' w* and yhat* draws (``spamtree_amd.diagnostics``), formed on the device after the
     last draw from the draws it keeps (``z`` None, ``mode`` 0; 4 .. 16384 saved draws).  The result then holds
     ``rank_diagnostics``: dict(w, yhat) and, with ``functionals``, ``functionals["rank_diagnostics"]``.
+
+    ``exceed=dict(thresholds=, side=, thresholds_fun=)``: Rao-Blackwellised exceedance probabilities (``spamtree_amd.exceed``), the
+    mean over the saved draws of each draw's exact conditional probability, formed on the device as the replay goes through
+    ``st_points_accumulate`` (``z`` None, ``mode`` 0); no draw is kept for it.  The result then holds ``exceed``: dict(thr, side,
+    w=dict(prob, prob_var), yhat=the same or None, n_accumulated) and, with ``thresholds_fun``, ``functionals["exceed"]``.
     """
     mi = model_inputs
     topo = mi["topo"]
@@ -187,6 +193,14 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
         _exc.check_mask(exc.get("mask"), n_new)
         if exc.get("thresholds") is not None:
             _exc.expand_thresholds(exc["thresholds"], int(np.unique(np.asarray(mi["mv_id"])).size), exc.get("side", 1))
+    rb = None
+    if exceed is not None:
+        if z is not None or mode != 0:
+            raise ValueError("exceed needs the device draw: z=None and mode=0")
+        try:
+            rb = _rb.check_spec(exceed, int(np.unique(np.asarray(mi["mv_id"])).size), None if fun is None else fun[0].size - 1)
+        except TypeError as e:
+            raise ValueError(f"exceed: {e}") from None
     rank = None
     if rank_diagnostics is not None and rank_diagnostics is not False:   # fit.spamtree_mv_mcmc's argument, for the points
         from . import diagnostics as _diag
@@ -235,6 +249,8 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
                 m._check(m.lib.st_points_summary_reserve(m.h, keep))
         if diagnostics or exc is not None or rank is not None:
             m._check(m.lib.st_points_summary_reserve(m.h, keep))
+        if rb is not None:
+            m.set_exceed(list(rb[0]), rb[1], None if rb[2] is None else list(rb[2]))
         cc = []
         w_out = np.zeros((n_new, keep)) if return_draws else None
         y_out = np.zeros((n_new, keep)) if (return_draws and X_new is not None) else None
@@ -248,7 +264,7 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
             m.theta_update(0, theta[:, s])
             if not m.get_loglik_comps_w(0):
                 raise FloatingPointError(f"st_factor failed on saved draw {s} (errtype {m.last_errtype})")
-            if fun is None and ys is None and not diagnostics and exc is None and rank is None:
+            if fun is None and ys is None and not diagnostics and exc is None and rank is None and rb is None:
                 out = m.predict_points(mode=mode, z=None if z is None else z[:, s], seed=seed, it=s)
             else:
                 out = m.accumulate_points(seed=seed, it=s)
@@ -283,6 +299,12 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
                     m._check(m.lib.st_points_summary_quantile(m.h, x, None, _dp(yq)))
                     lo_hi.append(yq.copy())
             res["scores"] = m.scores(crps=crps, yhat_lo=lo_hi[0], yhat_hi=lo_hi[1])
+        if rb is not None and keep:
+            ex = m.exceed()
+            fex = ex.pop("functionals", None)
+            res["exceed"] = ex
+            if fex is not None:
+                res["functionals"]["exceed"] = dict(fex, side=ex["side"], n_accumulated=ex["n_accumulated"])
         if diagnostics and n_new:
             res["diagnostics"] = m.points_diagnostics(int(diagnostics_max_lag), n_kept=keep)
             if fun is not None:
@@ -315,7 +337,7 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
 
 def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), return_draws=True, joint=None, functionals=None,
                 y_new=None, crps=True, diagnostics=False, diagnostics_max_lag=0, excursions=None, rank_diagnostics=None, chains=1,
-                chain_seeds=None, chain_theta=None, **mcmc):
+                chain_seeds=None, chain_theta=None, exceed=None, **mcmc):
     """Fit the chain and predict at new locations on every saved iteration, without replaying it.
 
     ``model_inputs``: the problem as for :func:`predict_new`.  The points are located with :func:`locate` and handed to
@@ -339,6 +361,9 @@ def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), retu
     ``new["functionals"]["excursions"]``.
     With ``rank_diagnostics`` (True or the dict of ``fit.spamtree_mv_mcmc``) the fit's ``rank_diagnostics``,
     ``new["rank_diagnostics"]`` and ``new["functionals"]["rank_diagnostics"]``.
+    With ``exceed=dict(thresholds=, side=, thresholds_fun=)`` also ``new["exceed"]`` and ``new["functionals"]["exceed"]``: the
+    Rao-Blackwellised exceedance probabilities of ``fit.spamtree_mv_mcmc(new_points=dict(exceed=))`` -- with ``return_draws=False``
+    an exceedance map of any number of points with nothing of size n_new x mcmc_keep anywhere.
     With ``chains`` > 1 (``chain_seeds``, ``chain_theta``: as ``fit.spamtree_mv_mcmc``) that many chains run one after another: every
     per-draw array holds ``chains * mcmc_keep`` columns, chain after chain (``chain_id``), the summaries are those of the pooled
     draws and the diagnostics the multi-chain ones.  :func:`predict_new` takes the concatenated result as it takes one chain's.
@@ -357,6 +382,11 @@ def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), retu
     ys = None if y_new is None else score_values(y_new, coords_new.shape[0], X_new is not None)
     if ys is not None and crps and int(chains) == 1 and int(mcmc.get("mcmc_keep", 100)) > fit.MAX_STORED_DRAWS:
         raise ValueError(f"the CRPS keeps mcmc_keep draws per point on the device, at most {fit.MAX_STORED_DRAWS} (crps=False scores without it)")
+    if exceed is not None:   # before the points are located: that may use the device
+        try:
+            _rb.check_spec(exceed, int(np.unique(np.asarray(mi["mv_id"])).size), None if fun is None else fun[0].size - 1)
+        except TypeError as e:
+            raise ValueError(f"exceed: {e}") from None
     anchor = locate(mi["topo"], coords_new, mv_new, device=mcmc.get("device", 0), joint=joint)
     points = dict(coords=coords_new, mv=mv_new, anchor=anchor, X=X_new)
     if joint is not None:
@@ -366,6 +396,8 @@ def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), retu
     if ys is not None:
         points["y"] = ys
         points["crps"] = bool(crps)
+    if exceed is not None:
+        points["exceed"] = exceed
     theta = np.asarray(mcmc.pop("theta", mi["theta"]), dtype=np.float64)
     kw = dict(set_unif_bounds_in=mi["bounds"], start_w=np.zeros((int(mi["n"]), 1)), theta=theta, beta=np.zeros(int(mi["p"])),
               tausq=0.1, mcmcsd=0.01 * np.eye(theta.size))
