@@ -41,7 +41,31 @@ int store_chain_diagnostics(st_handle_s *h, const char *who, const DrawStore &s,
 int store_chain_rank_diagnostics(st_handle_s *h, const char *who, const DrawStore &s, int32_t n_chains, const st_rank_spec *spec,
                                  const st_rank_out *w, const st_rank_out *yhat);
 
+// The most draws a store holds: one series' draws are sorted in one workgroup's LDS (st_summary_reserve, st_points_summary_reserve)
+constexpr int STORE_MAX_DRAWS = 16384;
+
+// What an output struct asks for; NULL asks for nothing
+inline bool any_out(const st_series_diag *o) { return o && (o->ess || o->mcse || o->sd || o->rhat || o->lags); }
+inline bool exc_thr_out(const st_excursion_out *o) { return o && (o->count || o->prob || o->excur || o->joint_all); }
+inline bool exc_band_out(const st_excursion_out *o) { return o && (o->mean || o->sd || o->maxdev || o->n_flat); }
+inline bool any_out(const st_excursion_out *o) { return exc_thr_out(o) || exc_band_out(o) || (o && o->n_draws); }
+inline bool rank_q_out(const st_rank_out *o) { return o && o->ess_q; }
+inline bool rank_exc_out(const st_rank_out *o) { return o && (o->ess_exc || o->mcse_prob || o->prob); }
+inline bool any_out(const st_rank_out *o) {
+  return o && (o->rhat_rank || o->rhat_bulk || o->rhat_fold || o->ess_bulk || o->ess_tail || o->lags_bulk || o->ess_q || rank_exc_out(o));
+}
+inline bool any_out(const st_rb_out *o) { return o && (o->prob || o->prob_var); }
+
 // ---- store_spec.cpp
+// The one copy of each spec's checks, for the st_* calls on a handle and for the whole fit's plan (fit_plan.cpp) before a chain
+// exists: an excursion and a rank spec with their outputs, K draws stored and n_thr_values thresholds per t, and the thresholds of
+// st_points_exceed_set (thr n_thr x q, not NULL; thr_fun n_thr x n_fun or NULL; n_fun < 0: no functionals are set)
+int check_excursion_spec(const std::string &W, const st_excursion_spec *spec, long long K, long long n_thr_values, const st_excursion_out *w,
+                         const st_excursion_out *yhat, std::string &msg);
+int check_rank_spec(const std::string &W, const st_rank_spec *spec, long long K, long long n_thr_values, const st_rank_out *w,
+                    const st_rank_out *yhat, std::string &msg);
+int check_exceed_spec(const std::string &W, int n_thr, const double *thr, const int32_t *side, const double *thr_fun, long long q,
+                      long long n_fun, std::string &msg);
 // n_chains in 1 .. ST_DIAG_MAX_CHAINS, K a multiple of it, K / n_chains >= ST_DIAG_MIN_DRAWS: ST_OK, or ST_ERR_USAGE with W, the
 // numbers and the first failing check in msg
 int check_chains(const std::string &W, int n_chains, long long K, std::string &msg);

@@ -56,7 +56,7 @@ int series_diag_launch(const DiagArgs &A, size_t lds_limit, hipStream_t st) {
 static int series_diag_store(st_handle_s *h, const char *who, const DrawStore &s, const double *draws, int32_t n_chains, int32_t max_lag,
                              const st_series_diag *out) {
   const long long n = s.n, K = s.K;
-  if (!out || !(out->ess || out->mcse || out->sd || out->rhat || out->lags)) return ST_OK;
+  if (!any_out(out)) return ST_OK;
   DiagArgs A;
   A.draws = draws; A.n = n; A.K = (int)K; A.M = n_chains;
   A.L = (int)std::min<long long>(max_lag == 0 ? ST_DIAG_DEFAULT_MAX_LAG : max_lag, K / n_chains - 2);

@@ -257,27 +257,6 @@ __global__ __launch_bounds__(EXC_NT) void k_exc_apply(ExcArgs A) {
 }
 
 // ---- host side
-static bool exc_thr_out(const st_excursion_out *o) { return o && (o->count || o->prob || o->excur || o->joint_all); }
-static bool exc_band_out(const st_excursion_out *o) { return o && (o->mean || o->sd || o->maxdev || o->n_flat); }
-
-// what the three calls refuse of a spec and its outputs (K stored draws, n_thr_values thresholds per t)
-static int exc_check_spec(st_handle_s *h, const char *who, const st_excursion_spec *spec, long long K, long long n_thr_values,
-                          const st_excursion_out *w, const st_excursion_out *yhat) {
-  const std::string W = std::string(who) + ": ";
-  if (!spec) { h->err = W + "no spec"; return ST_ERR_USAGE; }
-  const bool band = spec->want_band || exc_band_out(w) || exc_band_out(yhat);
-  if (!spec->thr && !band) { h->err = W + "the spec holds neither thresholds nor a band request"; return ST_ERR_USAGE; }
-  if (spec->thr) {
-    if (const int rc = check_thresholds(W, spec->n_thr, 1, spec->thr, spec->side, n_thr_values, h->err)) return rc;
-  } else if (exc_thr_out(w) || exc_thr_out(yhat)) {
-    h->err = W + "count, prob, excur and joint_all need thresholds";
-    return ST_ERR_USAGE;
-  }
-  if (K < 1) { h->err = W + "no draw stored (reserve room before the saved iterations)"; return ST_ERR_USAGE; }
-  if (band && K < 2) { h->err = W + "the band needs at least 2 stored draws, " + std::to_string(K) + " stored"; return ST_ERR_USAGE; }
-  return ST_OK;
-}
-
 template <int TT, bool BAND>
 static void exc_launch_passes(const ExcArgs &A, bool pass2, dim3 g1, dim3 g2, hipStream_t st) {
   hipLaunchKernelGGL((k_store_colstats<TT, BAND>), g1, dim3(EXC_NT), 0, st, A);
@@ -395,7 +374,7 @@ static int series_exc_store(st_handle_s *h, const char *who, const DrawStore &s,
 int store_excursions(st_handle_s *h, const char *who, const DrawStore &s, const st_excursion_spec *spec, const st_excursion_out *w,
                      const st_excursion_out *yhat) {
   if (s.rc || s.n == 0) return s.rc;
-  if (const int rc = exc_check_spec(h, who, spec, s.K, s.n_thr_values(), w, yhat)) return rc;
+  if (const int rc = check_excursion_spec(std::string(who) + ": ", spec, s.K, s.n_thr_values(), w, yhat, h->err)) return rc;
   if (yhat && s.yhat_needs_X) { h->err = std::string(who) + ": yhat needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
   for (int which = 0; which < 2; ++which)
     if (const int rc = series_exc_store(h, who, s, which ? s.yhat : s.w, spec, which ? yhat : w)) return rc;

@@ -334,42 +334,14 @@ bool series_rank_plan(long long K, size_t lds_limit, int *R, int *Kpad, int *Kz,
   return false;
 }
 
-static bool rank_q_out(const st_rank_out *o) { return o && o->ess_q; }
-static bool rank_exc_out(const st_rank_out *o) { return o && (o->ess_exc || o->mcse_prob || o->prob); }
-
-// what the three calls refuse of a spec and its outputs (K stored draws, n_thr_values thresholds per t)
-static int rank_check_spec(st_handle_s *h, const char *who, const st_rank_spec *spec, long long K, long long n_thr_values,
-                           const st_rank_out *w, const st_rank_out *yhat) {
-  const std::string W = std::string(who) + ": ";
-  if (!spec) { h->err = W + "no spec"; return ST_ERR_USAGE; }
-  if (spec->max_lag < 0) { h->err = W + "max_lag must not be negative (0: the default cap)"; return ST_ERR_USAGE; }
-  if (spec->n_prob < 0 || spec->n_prob > ST_RANK_MAX_PROBS) {
-    h->err = W + "n_prob = " + std::to_string(spec->n_prob) + " must lie in 0 .. " + std::to_string(ST_RANK_MAX_PROBS);
-    return ST_ERR_USAGE;
-  }
-  if (spec->n_prob > 0 && !spec->prob) { h->err = W + "n_prob = " + std::to_string(spec->n_prob) + " without prob"; return ST_ERR_USAGE; }
-  for (int k = 0; k < spec->n_prob; ++k)
-    if (!(spec->prob[k] > 0.0 && spec->prob[k] < 1.0)) { h->err = W + "prob " + std::to_string(k) + " must lie strictly inside (0, 1)"; return ST_ERR_USAGE; }
-  if (const int rc = check_thresholds(W, spec->n_thr, 0, spec->thr, spec->side, n_thr_values, h->err)) return rc;
-  if (spec->n_prob == 0 && (rank_q_out(w) || rank_q_out(yhat))) { h->err = W + "ess_q needs prob"; return ST_ERR_USAGE; }
-  if (spec->n_thr == 0 && (rank_exc_out(w) || rank_exc_out(yhat))) { h->err = W + "ess_exc, mcse_prob and prob need thresholds"; return ST_ERR_USAGE; }
-  if (K < ST_DIAG_MIN_DRAWS) {
-    h->err = W + std::to_string(K) + " draws stored, the diagnostics need at least " + std::to_string(ST_DIAG_MIN_DRAWS) +
-             " (reserve room before the saved iterations)";
-    return ST_ERR_USAGE;
-  }
-  return ST_OK;
-}
-
 // The outputs out asks for, of one of the store's two sets of draws, into out's host arrays (any may be NULL), element i of the
 // store at out[perm ? perm[i] : i].  store_chain_rank_diagnostics has checked the spec, K and n_chains.
 static int series_rank_store(st_handle_s *h, const char *who, const DrawStore &s, const double *draws, int32_t n_chains,
                              const st_rank_spec *spec, const st_rank_out *out) {
   const long long n = s.n, K = s.K;
-  if (!out) return ST_OK;
+  if (!any_out(out)) return ST_OK;
   const bool bulk = out->rhat_rank || out->rhat_bulk || out->ess_bulk || out->lags_bulk, fold = out->rhat_rank || out->rhat_fold;
-  const int n_prob = out->ess_q ? spec->n_prob : 0, n_thr = rank_exc_out(out) ? spec->n_thr : 0;
-  if (!bulk && !fold && !out->ess_tail && !n_prob && !n_thr) return ST_OK;
+  const int n_prob = out->ess_q ? spec->n_prob : 0, n_thr = rank_exc_out(out) ? spec->n_thr : 0;   // (checked: positive where wanted)
   RankArgs A = {};
   A.draws = draws; A.n = n; A.K = (int)K; A.M = n_chains;
   A.L = (int)std::min<long long>(spec->max_lag == 0 ? ST_DIAG_DEFAULT_MAX_LAG : spec->max_lag, K / n_chains - 2);
@@ -447,7 +419,7 @@ int store_rank_diagnostics(st_handle_s *h, const char *who, const DrawStore &s, 
 int store_chain_rank_diagnostics(st_handle_s *h, const char *who, const DrawStore &s, int32_t n_chains, const st_rank_spec *spec,
                                  const st_rank_out *w, const st_rank_out *yhat) {
   if (s.rc || s.n == 0) return s.rc;
-  if (const int rc = rank_check_spec(h, who, spec, s.K, s.n_thr_values(), w, yhat)) return rc;
+  if (const int rc = check_rank_spec(std::string(who) + ": ", spec, s.K, s.n_thr_values(), w, yhat, h->err)) return rc;
   if (const int rc = check_chains(std::string(who) + ": ", n_chains, s.K, h->err)) return rc;
   if (yhat && s.yhat_needs_X) { h->err = std::string(who) + ": yhat needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
   for (int which = 0; which < 2; ++which)

@@ -461,90 +461,24 @@ extern "C" int stm_rows_score_set(stm_chain c, const double *y_holdout) {
 }
 
 // ---- the whole fit: one request (include/spamtree_fit.h, stm_fit) ------------------------------------------------------------------
+#include "draw_store.hpp"   // any_out: what an output struct asks for
+#include "fit_plan.hpp"     // FitPlan: the request as it is run, worked out without a device
+
 namespace {
-bool any_out(const st_series_diag &d) { return d.ess || d.mcse || d.sd || d.rhat || d.lags; }
-
-bool exc_thr_any(const st_excursion_out &o) { return o.count || o.prob || o.excur || o.joint_all; }
-bool exc_band_any(const st_excursion_out &o) { return o.mean || o.sd || o.maxdev || o.n_flat; }
-bool any_out(const st_excursion_out &o) { return exc_thr_any(o) || exc_band_any(o) || o.n_draws; }
-// what st_*_excursions would refuse of a spec after the chain, found before it: nvals thresholds per t, keep draws to be stored
-int exc_spec_refused(const st_excursion_spec &sp, int64_t nvals, const st_excursion_out &w, const st_excursion_out &y, int keep) {
-  const bool band = sp.want_band || exc_band_any(w) || exc_band_any(y);
-  if (!sp.thr && !band) return ST_ERR_USAGE;
-  if (sp.thr) {
-    if (sp.n_thr < 1 || sp.n_thr > ST_EXC_MAX_THRESHOLDS) return ST_ERR_USAGE;
-    for (int64_t k = 0; k < (int64_t)sp.n_thr * nvals; ++k) if (!std::isfinite(sp.thr[k])) return ST_ERR_USAGE;
-    for (int t = 0; sp.side && t < sp.n_thr; ++t) if (sp.side[t] != 1 && sp.side[t] != -1) return ST_ERR_USAGE;
-  } else if (exc_thr_any(w) || exc_thr_any(y)) return ST_ERR_USAGE;
-  if (keep < 1 || (band && keep < 2)) return ST_ERR_USAGE;
-  return 0;
-}
-
-bool any_out(const st_rb_out &o) { return o.prob || o.prob_var; }
-// what stm_mcmc_fit refuses of rb before a chain exists: the missing parts it needs, then what st_points_exceed_set would refuse of
-// the spec (q outcomes, n_fun functionals; fun NULL: none)
-int rb_refused(const stm_rb_exceed &rb, bool have_pts, const stm_functionals *fun, const double *X_new, int q) {
-  if (!have_pts) return ST_ERR_USAGE;
-  if (any_out(rb.new_yhat) && !X_new) return ST_ERR_USAGE;
-  if (any_out(rb.fun_w) && (!fun || !rb.thr_fun)) return ST_ERR_USAGE;
-  if (rb.n_thr < 1 || rb.n_thr > ST_EXC_MAX_THRESHOLDS) return ST_ERR_USAGE;
-  for (int64_t k = 0; k < (int64_t)rb.n_thr * q; ++k) if (!std::isfinite(rb.thr[k])) return ST_ERR_USAGE;
-  for (int t = 0; rb.side && t < rb.n_thr; ++t) if (rb.side[t] != 1 && rb.side[t] != -1) return ST_ERR_USAGE;
-  if (rb.thr_fun && !fun) return ST_ERR_USAGE;
-  for (int64_t k = 0; rb.thr_fun && k < (int64_t)rb.n_thr * fun->n_fun; ++k) if (!std::isfinite(rb.thr_fun[k])) return ST_ERR_USAGE;
-  return 0;
-}
-
-bool any_out(const st_rank_out &o) {
-  return o.rhat_rank || o.rhat_bulk || o.rhat_fold || o.ess_bulk || o.ess_tail || o.lags_bulk || o.ess_q || o.ess_exc || o.mcse_prob || o.prob;
-}
-// what st_*_rank_diagnostics would refuse of a spec after the chain, found before it: nvals thresholds per t
-int rank_spec_refused(const st_rank_spec &sp, int64_t nvals, const st_rank_out &w, const st_rank_out &y) {
-  if (sp.max_lag < 0 || sp.n_prob < 0 || sp.n_prob > ST_RANK_MAX_PROBS || sp.n_thr < 0 || sp.n_thr > ST_EXC_MAX_THRESHOLDS) return ST_ERR_USAGE;
-  if ((sp.n_prob > 0 && !sp.prob) || (sp.n_thr > 0 && !sp.thr)) return ST_ERR_USAGE;
-  for (int k = 0; k < sp.n_prob; ++k) if (!(sp.prob[k] > 0.0 && sp.prob[k] < 1.0)) return ST_ERR_USAGE;
-  for (int64_t k = 0; k < (int64_t)sp.n_thr * nvals; ++k) if (!std::isfinite(sp.thr[k])) return ST_ERR_USAGE;
-  for (int t = 0; sp.side && t < sp.n_thr; ++t) if (sp.side[t] != 1 && sp.side[t] != -1) return ST_ERR_USAGE;
-  if (sp.n_prob == 0 && (w.ess_q || y.ess_q)) return ST_ERR_USAGE;
-  if (sp.n_thr == 0 && (w.ess_exc || w.mcse_prob || w.prob || y.ess_exc || y.mcse_prob || y.prob)) return ST_ERR_USAGE;
-  return 0;
-}
-
-// Which stores one summary of the stored draws (stm_diagnostics, stm_excursions, stm_rank_diagnostics: the same six members) reads,
-// after the four refusals the three share, in their order
-struct Wanted {
-  bool rows = false, pts = false, fun = false;
-  bool any() const { return rows || pts || fun; }
-};
-template <class Part>
-int wanted_of(const Part *t, bool have_pts, const stm_functionals *fun, const double *X_new, Wanted *out) {
-  if (!t) return 0;
-  Wanted w;
-  w.rows = any_out(t->rows_w) || any_out(t->rows_yhat);
-  w.pts = any_out(t->new_w) || any_out(t->new_yhat);
-  w.fun = any_out(t->fun_w) || any_out(t->fun_yhat);
-  if (w.rows && !t->want_rows) return ST_ERR_USAGE;
-  if (w.pts && !have_pts) return ST_ERR_USAGE;
-  if (w.fun && !fun) return ST_ERR_USAGE;
-  if ((any_out(t->new_yhat) || any_out(t->fun_yhat)) && !X_new) return ST_ERR_USAGE;
-  *out = w;
-  return 0;
-}
-
 // What stm_mcmc_fit refuses before a chain exists to carry the text: the calling thread's last such refusal
 thread_local std::string g_chains_error;
-int chains_refuse(int code, const std::string &msg) { g_chains_error = msg; return code; }
 
-struct FitPlan {           // a request as stm_mcmc_fit runs it
-  stm_fit f;               // the request; a part that does not apply is NULL: fun of no functional, scores without y_new, pts of a plain chain
-  stm_new_points p;        // what f.pts points to: keep_draws raised to the stored draws, new_cond_cov where the packed blocks go
-  bool store_rows = false; // diag, exc or rk read the rows' stores: st_summary_accumulate on every saved iteration
-  int64_t cov_len = 0;     // the packed length of st_points_joint_layout
-};
 struct FitChain {          // one chain of a request: its saved draw s goes to column col0 + s of per-draw outputs with ncols columns
   uint64_t seed;
   int col0, ncols;
 };
+struct JointBlocks {       // st_points_joint_layout's groups, and the packed blocks of every draw when only new_cond_var is wanted of them
+  int64_t nj = 0;
+  std::vector<int64_t> off, ptr, mem;
+  std::vector<double> scratch;
+};
+uint64_t chain_seed(const stm_fit &f, int cn) { return f.ch ? f.ch->seeds[cn] : f.run.seed; }
+const double *chain_theta(const stm_fit &f, int cn) { return f.ch && f.ch->theta0 ? f.ch->theta0 + (size_t)cn * f.run.ntheta : f.run.theta; }
 }  // namespace
 
 extern "C" const char *stm_mcmc_chains_last_error(void) { return g_chains_error.c_str(); }
@@ -620,160 +554,70 @@ static int run_fit(stm_chain c, const FitPlan &pl, const FitChain &ch, double *s
   return rc;
 }
 
-extern "C" int stm_mcmc_fit(const stm_fit *fit) {
-  g_chains_error.clear();
-  if (!fit) return ST_ERR_USAGE;
-  FitPlan pl;
-  pl.f = *fit;
-  stm_fit &f = pl.f;
-  stm_new_points &p = pl.p;
+// Step 1 after the plan: the chain and what it is given before its first factorisation, so every refusal of these comes before
+// stm_init.  Fills pl.cov_len and jb and points p.new_cond_cov at the scratch where only new_cond_var is wanted; no chain is left
+// behind a refusal.
+static int fit_setup(FitPlan &pl, JointBlocks &jb, stm_chain *out) {
+  const stm_fit &f = pl.f;
   const stm_run &r = f.run;
-  if ((f.criteria || f.loo) && (f.pts || f.fun || f.scores || f.diag || f.exc || f.rk || f.ch))
-    return chains_refuse(ST_ERR_USAGE, "stm_mcmc_fit: criteria and loo do not go with pts, fun, scores, diag, exc, rk or ch in one request");
-  if (f.fun && f.fun->n_fun <= 0) f.fun = nullptr;
-  p = f.pts ? *f.pts : stm_new_points{};
+  stm_new_points &p = pl.p;
   const stm_functionals *const fun = f.fun;
+  const stm_loo *const loo = f.loo;
+  stm_chain c = nullptr;
+  int rc = stm_create(r.pb, r.opt, r.set_unif_bounds, r.mcmcsd, chain_theta(f, 0), r.ntheta, r.beta, r.tausq, chain_seed(f, 0), r.flags, &c);
+  if (rc == 0 && f.pts)
+    rc = stm_points_set_joint(c, p.n_new, p.coords_new, p.mv_new, p.anchor_new, p.X_new, p.joint_id_new, p.keep_draws);
+  if (rc == 0 && (pl.store_rows || (pl.crps && r.mcmc_keep > 0))) {
+    rc = st_summary_reset(c->h);
+    if (rc == 0) rc = st_summary_reserve(c->h, pl.total);
+  }
+  if (rc == 0 && fun) rc = stm_points_functionals_set(c, fun->n_fun, fun->ptr, fun->idx, fun->wt);
+  if (rc == 0 && f.scores) rc = stm_points_score_set(c, f.scores->y_new);
+  if (rc == 0 && pl.rb && (rc = st_points_exceed_set(c->h, pl.rb->n_thr, pl.rb->thr, pl.rb->side, pl.rb->thr_fun)) != 0) c->err = st_last_error(c->h);
+  if (rc == 0 && p.joint_id_new) {
+    rc = st_points_joint_layout(c->h, &jb.nj, nullptr, nullptr, nullptr);
+    jb.off.resize(jb.nj + 1); jb.ptr.resize(jb.nj + 1); jb.mem.resize(p.n_new);
+    if (rc == 0) rc = st_points_joint_layout(c->h, &jb.nj, jb.off.data(), jb.ptr.data(), jb.mem.data());
+    if (rc == 0 && !p.new_cond_cov && p.new_cond_var) jb.scratch.resize((size_t)jb.off[jb.nj] * std::max<long long>(pl.total, 0));
+  }
+  if (rc == 0 && f.criteria) rc = stm_rows_score_set(c, f.criteria->y_holdout);
+  if (rc == 0 && loo) rc = st_rows_loo_set(c->h);   // (limited_tree is refused)
+  if (rc == 0 && loo && loo->psis) rc = st_rows_loo_reserve(c->h, r.mcmc_keep);
+  if (rc == 0 && loo && loo->groups) rc = st_rows_loo_groups_set(c->h, loo->groups->labels);   // (oversized groups, groups without an observed member)
+  if (rc == 0) rc = stm_init(c);
+  if (rc != 0) { stm_destroy(c); return rc; }
+  if (p.joint_id_new) {
+    pl.cov_len = jb.off[jb.nj];
+    if (!p.new_cond_cov && !jb.scratch.empty()) p.new_cond_cov = jb.scratch.data();
+  } else p.new_cond_cov = nullptr;
+  *out = c;
+  return ST_OK;
+}
+
+// Step 3: the read-outs after the last chain, in the order the header states
+static int fit_read_out(stm_chain c, const FitPlan &pl, const JointBlocks &jb) {
+  const stm_fit &f = pl.f;
+  const stm_new_points &p = pl.p;
+  const stm_functionals *const fun = f.fun;
+  const stm_scores *const scores = f.scores;
   const stm_diagnostics *const diag = f.diag;
   const stm_excursions *const exc = f.exc;
   const stm_rank_diagnostics *const rk = f.rk;
-  const stm_chains *const ch = f.ch;
-  const int mcmc_keep = r.mcmc_keep, ntheta = r.ntheta;
-  // M chains one after another on one handle; chain c's saved draws are columns c keep .. (c + 1) keep - 1 of every per-draw output
-  // and of the stores
-  const int M = ch ? ch->n_chains : 1;
-  const std::string W = "stm_mcmc_chains: ";
-  if (ch && (M < 1 || M > ST_DIAG_MAX_CHAINS))
-    return chains_refuse(ST_ERR_USAGE, W + "n_chains = " + std::to_string(M) + " must lie in 1 .. " + std::to_string(ST_DIAG_MAX_CHAINS));
-  if (ch && !ch->seeds) return chains_refuse(ST_ERR_USAGE, W + "seeds is NULL: one seed per chain (" + std::to_string(M) + ")");
-  if (M > 1 && mcmc_keep < 1)
-    return chains_refuse(ST_ERR_USAGE, W + "mcmc_keep = " + std::to_string(mcmc_keep) + ": " + std::to_string(M) + " chains need at least one saved draw each");
-  if (M > 1 && !r.theta) return chains_refuse(ST_ERR_USAGE, W + "theta is NULL");
-  if (M > 1 && r.opt && r.opt->world > 1)
-    return chains_refuse(ST_ERR_UNSUPPORTED, W + "world = " + std::to_string(r.opt->world) + ": several chains run on one GPU");
-  const long long total = (long long)M * mcmc_keep;   // the stored draws
-  const auto too_many = [&]() {
-    return chains_refuse(ST_ERR_UNSUPPORTED, W + std::to_string(M) + " chains x mcmc_keep = " + std::to_string(mcmc_keep) + " are " + std::to_string(total) +
-                                                 " stored draws, at most 16384");
-  };
-  // the plain chain: no point argument, and either a summary of the rows (an empty set without one reaches stm_points_set_joint)
-  // or several chains
-  const bool plain = (diag || exc || rk || M > 1) && p.n_new == 0 && !p.coords_new && !p.mv_new && !p.anchor_new;
-  f.pts = (f.pts && !plain) ? &p : nullptr;
-  const bool have_pts = f.pts != nullptr;
-  // diag, exc, rk: the shared refusals, the stores' limit, the minimum of draws (exc: per spec, below), the spec; a part that reads
-  // the point set's stores raises keep_draws to the stored draws
-  int rc;
-  Wanted d, e, k;
-  const auto stored = [&](const Wanted &w, int min_draws) {
-    if (total > 16384) return too_many();
-    if (mcmc_keep < min_draws) return (int)ST_ERR_USAGE;
-    if (w.pts || w.fun) p.keep_draws = std::max<int64_t>(p.keep_draws, total);
-    return 0;
-  };
-  if (diag && diag->max_lag < 0) return ST_ERR_USAGE;
-  if ((rc = wanted_of(diag, have_pts, fun, p.X_new, &d)) != 0) return rc;
-  if (d.any() && (rc = stored(d, ST_DIAG_MIN_DRAWS)) != 0) return rc;
-  if ((rc = wanted_of(exc, have_pts, fun, p.X_new, &e)) != 0) return rc;
-  if (e.any()) {
-    if ((rc = stored(e, 0)) != 0) return rc;
-    if (e.rows && (rc = exc_spec_refused(exc->rows_spec, r.pb->q, exc->rows_w, exc->rows_yhat, (int)total)) != 0) return rc;
-    if (e.pts && (rc = exc_spec_refused(exc->new_spec, r.pb->q, exc->new_w, exc->new_yhat, (int)total)) != 0) return rc;
-    if (e.fun && (rc = exc_spec_refused(exc->fun_spec, fun->n_fun, exc->fun_w, exc->fun_yhat, (int)total)) != 0) return rc;
-  }
-  // rb reads no store: no reservation, no limit, no minimum of draws.  (thr NULL or n_thr = 0: no part, as scores without y_new)
-  const stm_rb_exceed *const rb = (exc && exc->rb && exc->rb->thr && exc->rb->n_thr != 0) ? exc->rb : nullptr;
-  if (rb && !r.pb) return ST_ERR_USAGE;
-  if (rb && (rc = rb_refused(*rb, have_pts, fun, p.X_new, r.pb->q)) != 0) return rc;
-  if ((rc = wanted_of(rk, have_pts, fun, p.X_new, &k)) != 0) return rc;
-  if (k.any()) {
-    if ((rc = stored(k, ST_DIAG_MIN_DRAWS)) != 0) return rc;
-    if (k.rows && (rc = rank_spec_refused(rk->rows_spec, r.pb->q, rk->rows_w, rk->rows_yhat)) != 0) return rc;
-    if (k.pts && (rc = rank_spec_refused(rk->new_spec, r.pb->q, rk->new_w, rk->new_yhat)) != 0) return rc;
-    if (k.fun && (rc = rank_spec_refused(rk->fun_spec, fun->n_fun, rk->fun_w, rk->fun_yhat)) != 0) return rc;
-  }
-  pl.store_rows = d.rows || e.rows || k.rows;   // one reservation serves all three
-  if (M > 1 && p.keep_draws > 0) {   // a point store that is reserved at all holds every chain's draws
-    if (total > 16384) return too_many();
-    p.keep_draws = total;
-  }
-  // the point set, its functionals, scores and quantiles
-  if (!have_pts && (fun || (f.scores && f.scores->y_new) || p.joint_id_new || p.X_new || p.n_quantiles != 0)) return ST_ERR_USAGE;
-  if (f.scores && !f.scores->y_new) f.scores = nullptr;
-  const stm_scores *const scores = f.scores;
-  if (scores && (!p.X_new || (scores->lpd_joint && !p.joint_id_new) || (scores->crps && p.keep_draws < 1))) return ST_ERR_USAGE;
-  if (fun && (fun->fun_yhat || fun->fun_yhat_mean || fun->fun_yhat_q) && !p.X_new) return ST_ERR_USAGE;
-  if ((p.new_cond_cov || p.new_cov) && !p.joint_id_new) return ST_ERR_USAGE;
-  if (p.n_quantiles < 0 || (p.n_quantiles > 0 && (!p.quantiles || p.keep_draws < 1))) return ST_ERR_USAGE;   // a quantile needs stored draws
-  for (int32_t i = 0; i < p.n_quantiles; ++i) if (!(p.quantiles[i] >= 0.0 && p.quantiles[i] <= 1.0)) return ST_ERR_USAGE;
-  if ((p.new_yhat || p.new_yhat_mean || p.new_yhat_q) && !p.X_new) return ST_ERR_USAGE;
-  // the criteria over the fit's own rows
+  const stm_rb_exceed *const rb = pl.rb;
   const stm_criteria *const cr = f.criteria;
   const stm_loo *const loo = f.loo;
-  const bool crps = cr && cr->want_crps && cr->y_holdout;
-  if (cr && cr->crps && !crps) return ST_ERR_USAGE;
-  if (crps && mcmc_keep > 16384) return ST_ERR_UNSUPPORTED;   // st_summary_reserve's limit
-  if (cr && cr->y_holdout && r.flags && (!r.flags->sample_predicts || !r.flags->sample_w)) return ST_ERR_USAGE;   // the NA rows' w would be stale
   const stm_loo_psis *const psis = loo ? loo->psis : nullptr;
-  if (psis && (mcmc_keep < 1 || mcmc_keep > ST_PSIS_MAX_DRAWS))   // st_rows_loo_reserve's limits
-    return chains_refuse(ST_ERR_UNSUPPORTED, "stm_mcmc_fit: psis keeps every saved draw, mcmc_keep = " + std::to_string(mcmc_keep) + " must lie in 1 .. " +
-                                                 std::to_string(ST_PSIS_MAX_DRAWS));
-
-  // the chain and what it is given before its first factorisation: every refusal of these comes before stm_init
-  const auto chain_seed = [&](int cn) { return ch ? ch->seeds[cn] : r.seed; };
-  const auto chain_theta = [&](int cn) { return ch && ch->theta0 ? ch->theta0 + (size_t)cn * ntheta : r.theta; };
-  stm_chain c = nullptr;
-  rc = stm_create(r.pb, r.opt, r.set_unif_bounds, r.mcmcsd, chain_theta(0), ntheta, r.beta, r.tausq, chain_seed(0), r.flags, &c);
-  if (rc == 0 && have_pts)
-    rc = stm_points_set_joint(c, p.n_new, p.coords_new, p.mv_new, p.anchor_new, p.X_new, p.joint_id_new, p.keep_draws);
-  if (rc == 0 && (pl.store_rows || (crps && mcmc_keep > 0))) {
-    rc = st_summary_reset(c->h);
-    if (rc == 0) rc = st_summary_reserve(c->h, total);
-  }
-  int64_t nj = 0;
-  std::vector<int64_t> joff, jptr, jmem;
-  std::vector<double> cov_scratch;   // the packed blocks of every draw when only new_cond_var is wanted of them
-  if (rc == 0 && fun) rc = stm_points_functionals_set(c, fun->n_fun, fun->ptr, fun->idx, fun->wt);
-  if (rc == 0 && scores) rc = stm_points_score_set(c, scores->y_new);
-  if (rc == 0 && rb && (rc = st_points_exceed_set(c->h, rb->n_thr, rb->thr, rb->side, rb->thr_fun)) != 0) c->err = st_last_error(c->h);
-  if (rc == 0 && p.joint_id_new) {
-    rc = st_points_joint_layout(c->h, &nj, nullptr, nullptr, nullptr);
-    joff.resize(nj + 1); jptr.resize(nj + 1); jmem.resize(p.n_new);
-    if (rc == 0) rc = st_points_joint_layout(c->h, &nj, joff.data(), jptr.data(), jmem.data());
-    if (rc == 0 && !p.new_cond_cov && p.new_cond_var) cov_scratch.resize((size_t)joff[nj] * std::max<long long>(total, 0));
-  }
-  if (rc == 0 && cr) rc = stm_rows_score_set(c, cr->y_holdout);
-  if (rc == 0 && loo) rc = st_rows_loo_set(c->h);   // (limited_tree is refused)
-  if (rc == 0 && psis) rc = st_rows_loo_reserve(c->h, mcmc_keep);
   const stm_loo_groups *const lgo = loo ? loo->groups : nullptr;
-  if (rc == 0 && lgo) rc = st_rows_loo_groups_set(c->h, lgo->labels);   // (oversized groups, groups without an observed member)
-  if (rc == 0) rc = stm_init(c);
-  if (rc != 0) { stm_destroy(c); return rc; }
-  double *const new_cond_var = p.new_cond_var;
-  if (p.joint_id_new) {
-    pl.cov_len = joff[nj];
-    if (!p.new_cond_cov && !cov_scratch.empty()) p.new_cond_cov = cov_scratch.data();
-  } else p.new_cond_cov = nullptr;
-  double *const ccov = p.new_cond_cov;
-
-  double time_all = 0;
-  for (int cn = 0; cn < M && rc == 0; ++cn) {
-    if (cn > 0) rc = stm_restart(c, chain_theta(cn), chain_seed(cn));
-    double time_c = 0;
-    if (rc == 0) rc = run_fit(c, pl, FitChain{chain_seed(cn), cn * mcmc_keep, (int)total}, &time_c);
-    if (rc == 0 && ch && ch->paramsd) std::memcpy(ch->paramsd + (size_t)cn * ntheta * ntheta, c->am.paramsd.data(), (size_t)ntheta * ntheta * sizeof(double));
-    if (rc == 0 && ch && ch->chain_time) ch->chain_time[cn] = time_c;
-    time_all += time_c;
-  }
-  if (rc == 0 && r.mcmc_time) *r.mcmc_time = time_all;   // (paramsd: the last chain's; every chain's in ch->paramsd)
-
-  // the read-outs, in the order the header states
-  const bool saved = mcmc_keep > 0;
-  if (rc == 0 && have_pts && ccov && new_cond_var)
-    for (long long s = 0; s < total; ++s)
-      for (int64_t g = 0; g < nj; ++g) {
-        const int64_t sz = jptr[g + 1] - jptr[g];
+  const Wanted &d = pl.d, &e = pl.e, &k = pl.k;
+  const int M = pl.M;   // (diag and rk: the stored draws are M chains laid end to end)
+  const bool have_pts = f.pts != nullptr, saved = f.run.mcmc_keep > 0;
+  int rc = 0;
+  if (have_pts && p.new_cond_cov && p.new_cond_var)
+    for (long long s = 0; s < pl.total; ++s)
+      for (int64_t g = 0; g < jb.nj; ++g) {
+        const int64_t sz = jb.ptr[g + 1] - jb.ptr[g];
         for (int64_t a = 0; a < sz; ++a)
-          new_cond_var[(size_t)s * p.n_new + jmem[jptr[g] + a]] = std::max(ccov[(size_t)s * joff[nj] + joff[g] + a * (sz + 1)], 0.0);
+          p.new_cond_var[(size_t)s * p.n_new + jb.mem[jb.ptr[g] + a]] = std::max(p.new_cond_cov[(size_t)s * pl.cov_len + jb.off[g] + a * (sz + 1)], 0.0);
       }
   if (rc == 0 && have_pts && saved && (p.new_mean || p.new_var || p.new_w_mean || p.new_yhat_mean))
     rc = st_points_summary_get(c->h, p.new_mean, p.new_var, p.new_w_mean, p.new_yhat_mean, nullptr);
@@ -789,24 +633,18 @@ extern "C" int stm_mcmc_fit(const stm_fit *fit) {
                                         fun->fun_yhat_q ? fun->fun_yhat_q + (size_t)i * fun->n_fun : nullptr);
   if (rc == 0 && scores && saved)
     rc = st_points_score_get(c->h, scores->lpd, scores->pit, scores->crps, scores->lpd_joint, scores->n_scored, scores->n_degenerate);
-  if (rc == 0 && rb && saved)
-    rc = st_points_exceed_get(c->h, &rb->new_w, any_out(rb->new_yhat) ? &rb->new_yhat : nullptr, any_out(rb->fun_w) ? &rb->fun_w : nullptr,
-                              rb->n_accumulated);
+  // a yhat (rb: fun_w too) struct that asks for nothing goes as NULL: its store need not exist
+  const auto opt = [](const auto &o) { return any_out(&o) ? &o : nullptr; };
+  if (rc == 0 && rb && saved) rc = st_points_exceed_get(c->h, &rb->new_w, opt(rb->new_yhat), opt(rb->fun_w), rb->n_accumulated);
   if (rc == 0 && d.rows) rc = st_summary_chain_diagnostics(c->h, M, diag->max_lag, &diag->rows_w, &diag->rows_yhat);
-  if (rc == 0 && d.pts)
-    rc = st_points_summary_chain_diagnostics(c->h, M, diag->max_lag, &diag->new_w, any_out(diag->new_yhat) ? &diag->new_yhat : nullptr);
-  if (rc == 0 && d.fun)
-    rc = st_points_functionals_chain_diagnostics(c->h, M, diag->max_lag, &diag->fun_w, any_out(diag->fun_yhat) ? &diag->fun_yhat : nullptr);
+  if (rc == 0 && d.pts) rc = st_points_summary_chain_diagnostics(c->h, M, diag->max_lag, &diag->new_w, opt(diag->new_yhat));
+  if (rc == 0 && d.fun) rc = st_points_functionals_chain_diagnostics(c->h, M, diag->max_lag, &diag->fun_w, opt(diag->fun_yhat));
   if (rc == 0 && e.rows) rc = st_summary_excursions(c->h, &exc->rows_spec, &exc->rows_w, &exc->rows_yhat);
-  if (rc == 0 && e.pts)
-    rc = st_points_summary_excursions(c->h, &exc->new_spec, &exc->new_w, any_out(exc->new_yhat) ? &exc->new_yhat : nullptr);
-  if (rc == 0 && e.fun)
-    rc = st_points_functionals_excursions(c->h, &exc->fun_spec, &exc->fun_w, any_out(exc->fun_yhat) ? &exc->fun_yhat : nullptr);
+  if (rc == 0 && e.pts) rc = st_points_summary_excursions(c->h, &exc->new_spec, &exc->new_w, opt(exc->new_yhat));
+  if (rc == 0 && e.fun) rc = st_points_functionals_excursions(c->h, &exc->fun_spec, &exc->fun_w, opt(exc->fun_yhat));
   if (rc == 0 && k.rows) rc = st_summary_chain_rank_diagnostics(c->h, M, &rk->rows_spec, &rk->rows_w, &rk->rows_yhat);
-  if (rc == 0 && k.pts)
-    rc = st_points_summary_chain_rank_diagnostics(c->h, M, &rk->new_spec, &rk->new_w, any_out(rk->new_yhat) ? &rk->new_yhat : nullptr);
-  if (rc == 0 && k.fun)
-    rc = st_points_functionals_chain_rank_diagnostics(c->h, M, &rk->fun_spec, &rk->fun_w, any_out(rk->fun_yhat) ? &rk->fun_yhat : nullptr);
+  if (rc == 0 && k.pts) rc = st_points_summary_chain_rank_diagnostics(c->h, M, &rk->new_spec, &rk->new_w, opt(rk->new_yhat));
+  if (rc == 0 && k.fun) rc = st_points_functionals_chain_rank_diagnostics(c->h, M, &rk->fun_spec, &rk->fun_w, opt(rk->fun_yhat));
   if (rc == 0 && cr && saved) {
     rc = st_rows_score_get(c->h, cr->lppd, cr->p_waic, cr->mean_ll, cr->mu_mean, cr->pit, cr->crps, cr->n_accumulated);
     if (rc == 0) rc = st_rows_score_totals(c->h, cr->obs, cr->held, cr->n_obs, cr->n_held);
@@ -829,9 +667,40 @@ extern "C" int stm_mcmc_fit(const stm_fit *fit) {
     if (rc == 0) rc = st_rows_loo_groups_totals(c->h, lgo->tot, lgo->by_outcome);
     if (rc == 0 && psis) rc = st_rows_loo_groups_psis(c->h, lgo->khat, lgo->elpd_psis, lgo->weight_ess_psis, nullptr, nullptr);
   }
+  return rc;
+}
+
+// The request in four steps: the plan (fit_plan.cpp: every refusal that needs no device), the setup, chain after chain, the read-outs
+extern "C" int stm_mcmc_fit(const stm_fit *fit) {
+  g_chains_error.clear();
+  if (!fit) return ST_ERR_USAGE;
+  FitPlan pl;
+  JointBlocks jb;
+  stm_chain c = nullptr;
+  std::string which;   // the failing check of every refusal: the plan's own tests read it, no caller does
+  int rc = fit_plan(*fit, pl, g_chains_error, which);
+  if (rc == 0) rc = fit_setup(pl, jb, &c);
+  if (rc != 0) return rc;
+  const stm_run &r = pl.f.run;
+  const stm_chains *const ch = pl.f.ch;
+  const size_t kk = (size_t)r.ntheta * r.ntheta;
+  // M chains one after another on one handle; chain cn's saved draws are columns cn keep .. (cn + 1) keep - 1 of every per-draw
+  // output and of the stores
+  double time_all = 0;
+  for (int cn = 0; cn < pl.M && rc == 0; ++cn) {
+    if (cn > 0) rc = stm_restart(c, chain_theta(pl.f, cn), chain_seed(pl.f, cn));
+    double time_c = 0;
+    if (rc == 0) rc = run_fit(c, pl, FitChain{chain_seed(pl.f, cn), cn * r.mcmc_keep, (int)pl.total}, &time_c);
+    if (rc == 0 && ch && ch->paramsd) std::memcpy(ch->paramsd + cn * kk, c->am.paramsd.data(), kk * sizeof(double));
+    if (rc == 0 && ch && ch->chain_time) ch->chain_time[cn] = time_c;
+    time_all += time_c;
+  }
+  if (rc == 0 && r.mcmc_time) *r.mcmc_time = time_all;   // (paramsd: the last chain's; every chain's in ch->paramsd)
+  if (rc == 0) rc = fit_read_out(c, pl, jb);
   stm_destroy(c);
   return rc;
 }
+
 
 // ---- the positional entry points: each fills a request from its arguments and calls stm_mcmc_fit -------------------------------
 // The two argument lists every one of them repeats, once: the run's twenty and the point set's twenty-two, in the structs' order

@@ -5,7 +5,8 @@
 // st_sweep.hip phases B and C; st_shard.hip everything that needs a communicator or serves a caller-run exchange; st_stats.hip
 // the statistics and the outputs that read w and XB.  A feature family has a host unit of its own, which defines the family's
 // state; the handle only points to it: st_points.hip new-point prediction, st_rows.hip the criteria over the fit's rows with
-// leave-one-out and Pareto smoothing, st_simulate.hip prior simulation, st_summary.hip the running summaries (state: the handle's).
+// leave-one-out and Pareto smoothing, st_simulate.hip prior simulation, st_summary.hip the running summaries (state: the handle's).  Above the C-ABI, spamtree_fit.cpp
+// is the whole-fit driver; fit_plan.cpp works out its request without a device, as tree_layout.cpp and points_layout.cpp do theirs.
 // Members that one unit alone reads and writes are a member structure named after their job (the lifecycle sets them up and
 // tears them down); what several units read is flat in the handle, under a heading.
 #pragma once

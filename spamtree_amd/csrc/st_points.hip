@@ -414,7 +414,10 @@ extern "C" int st_points_summary_reset(st_handle h) {
 extern "C" int st_points_summary_reserve(st_handle h, int64_t keep) {
   if (!h || keep < 0) return ST_ERR_USAGE;
   if (const int rc = points_refuse(h, "st_points_summary_reserve")) return rc;
-  if (keep > 16384) { h->err = "st_points_summary_reserve: at most 16384 saved draws (one point's draws are sorted in one workgroup's LDS)"; return ST_ERR_UNSUPPORTED; }
+  if (keep > STORE_MAX_DRAWS) {
+    h->err = "st_points_summary_reserve: at most " + std::to_string(STORE_MAX_DRAWS) + " saved draws (one point's draws are sorted in one workgroup's LDS)";
+    return ST_ERR_UNSUPPORTED;
+  }
   PointSet *ps = h->pts;
   HCHK(h, hipSetDevice(h->device));
   HCHK(h, hipStreamSynchronize(h->stream));
@@ -778,17 +781,8 @@ extern "C" int st_points_exceed_set(st_handle h, int32_t n_thr, const double *th
   PointSet *ps = h->pts;
   const bool remove = n_thr == 0 || !thr;
   const long long nf = ps->fun ? ps->fun->n_fun : 0;
-  if (!remove) {   // a refusal leaves the previous thresholds in place
-    const std::string W = "st_points_exceed_set: ";
-    if (n_thr < 1 || n_thr > ST_EXC_MAX_THRESHOLDS) { h->err = W + "n_thr = " + std::to_string(n_thr) + " must lie in 1 .. " + std::to_string(ST_EXC_MAX_THRESHOLDS); return ST_ERR_USAGE; }
-    for (long long k = 0; k < (long long)n_thr * h->q; ++k)
-      if (!std::isfinite(thr[k])) { h->err = W + "thr[" + std::to_string(k) + "] is not finite"; return ST_ERR_USAGE; }
-    for (int t = 0; side && t < n_thr; ++t)
-      if (side[t] != 1 && side[t] != -1) { h->err = W + "side[" + std::to_string(t) + "] = " + std::to_string(side[t]) + " is neither +1 nor -1"; return ST_ERR_USAGE; }
-    if (thr_fun && !ps->fun) { h->err = W + "thr_fun before st_points_functionals_set"; return ST_ERR_USAGE; }
-    for (long long k = 0; thr_fun && k < (long long)n_thr * nf; ++k)
-      if (!std::isfinite(thr_fun[k])) { h->err = W + "thr_fun[" + std::to_string(k) + "] is not finite"; return ST_ERR_USAGE; }
-  }
+  if (!remove)   // a refusal leaves the previous thresholds in place
+    if (const int rc = check_exceed_spec("st_points_exceed_set: ", n_thr, thr, side, thr_fun, h->q, ps->fun ? nf : -1, h->err)) return rc;
   HCHK(h, hipSetDevice(h->device));
   HCHK(h, hipStreamSynchronize(h->stream));
   if (remove) { ps->exceed.reset(); return ST_OK; }
@@ -833,8 +827,7 @@ extern "C" int st_points_exceed_get(st_handle h, const st_rb_out *w, const st_rb
   const double S = (double)ex->n_acc;
   const size_t per = (size_t)T * 2 * n;
   std::vector<double> acc, facc;
-  const bool want_w = w && (w->prob || w->prob_var), want_y = yhat && (yhat->prob || yhat->prob_var);
-  const bool want_f = fun_w && (fun_w->prob || fun_w->prob_var);
+  const bool want_w = any_out(w), want_y = any_out(yhat), want_f = any_out(fun_w);
   if (want_w || want_y) {
     acc.resize(ex->d_acc.n);
     HCHK(h, hipMemcpyAsync(acc.data(), ex->d_acc.p, acc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));

@@ -41,7 +41,10 @@ extern "C" int st_summary_reserve(st_handle h, int64_t keep) {
   h->d_draws_w.free(); h->d_draws_yhat.free();
   h->draws_cap = 0; h->n_draws = 0; h->draws_epoch += 1;
   if (keep == 0) return ST_OK;
-  if (keep > 16384) { h->err = "st_summary_reserve: at most 16384 saved draws (one row's draws are sorted in one workgroup's LDS)"; return ST_ERR_UNSUPPORTED; }
+  if (keep > STORE_MAX_DRAWS) {
+    h->err = "st_summary_reserve: at most " + std::to_string(STORE_MAX_DRAWS) + " saved draws (one row's draws are sorted in one workgroup's LDS)";
+    return ST_ERR_UNSUPPORTED;
+  }
   HCHK(h, h->d_draws_w.alloc((size_t)keep * h->n_all));
   HCHK(h, h->d_draws_yhat.alloc((size_t)keep * h->n_all));
   h->draws_cap = keep;

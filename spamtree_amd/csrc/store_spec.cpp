@@ -1,5 +1,5 @@
-// store_spec.cpp -- the pure host helpers of the summaries of the stored draws (draw_store.hpp): what the excursion and the rank
-// spec share of their checks, the small inputs brought into store order and the device results scattered into the caller's
+// store_spec.cpp -- the pure host helpers of the summaries of the stored draws (draw_store.hpp): the checks of the excursion, the
+// rank and the exceedance spec, the small inputs brought into store order and the device results scattered into the caller's
 // arrays.  No device call and no HIP header: tests/store_spec_check.cpp checks them on the CPU.
 #include <cmath>
 
@@ -15,6 +15,62 @@ int check_thresholds(const std::string &W, int n_thr, int min_thr, const double 
     if (!std::isfinite(thr[k])) { msg = W + "threshold " + std::to_string(k) + " is not finite"; return ST_ERR_USAGE; }
   for (int t = 0; side && t < n_thr; ++t)
     if (side[t] != 1 && side[t] != -1) { msg = W + "side " + std::to_string(t) + " must be +1 or -1"; return ST_ERR_USAGE; }
+  return ST_OK;
+}
+
+int check_excursion_spec(const std::string &W, const st_excursion_spec *spec, long long K, long long n_thr_values, const st_excursion_out *w,
+                         const st_excursion_out *yhat, std::string &msg) {
+  if (!spec) { msg = W + "no spec"; return ST_ERR_USAGE; }
+  const bool band = spec->want_band || exc_band_out(w) || exc_band_out(yhat);
+  if (!spec->thr && !band) { msg = W + "the spec holds neither thresholds nor a band request"; return ST_ERR_USAGE; }
+  if (spec->thr) {
+    if (const int rc = check_thresholds(W, spec->n_thr, 1, spec->thr, spec->side, n_thr_values, msg)) return rc;
+  } else if (exc_thr_out(w) || exc_thr_out(yhat)) {
+    msg = W + "count, prob, excur and joint_all need thresholds";
+    return ST_ERR_USAGE;
+  }
+  if (K < 1) { msg = W + "no draw stored (reserve room before the saved iterations)"; return ST_ERR_USAGE; }
+  if (band && K < 2) { msg = W + "the band needs at least 2 stored draws, " + std::to_string(K) + " stored"; return ST_ERR_USAGE; }
+  return ST_OK;
+}
+
+int check_rank_spec(const std::string &W, const st_rank_spec *spec, long long K, long long n_thr_values, const st_rank_out *w,
+                    const st_rank_out *yhat, std::string &msg) {
+  if (!spec) { msg = W + "no spec"; return ST_ERR_USAGE; }
+  if (spec->max_lag < 0) { msg = W + "max_lag must not be negative (0: the default cap)"; return ST_ERR_USAGE; }
+  if (spec->n_prob < 0 || spec->n_prob > ST_RANK_MAX_PROBS) {
+    msg = W + "n_prob = " + std::to_string(spec->n_prob) + " must lie in 0 .. " + std::to_string(ST_RANK_MAX_PROBS);
+    return ST_ERR_USAGE;
+  }
+  if (spec->n_prob > 0 && !spec->prob) { msg = W + "n_prob = " + std::to_string(spec->n_prob) + " without prob"; return ST_ERR_USAGE; }
+  for (int k = 0; k < spec->n_prob; ++k)
+    if (!(spec->prob[k] > 0.0 && spec->prob[k] < 1.0)) { msg = W + "prob " + std::to_string(k) + " must lie strictly inside (0, 1)"; return ST_ERR_USAGE; }
+  if (const int rc = check_thresholds(W, spec->n_thr, 0, spec->thr, spec->side, n_thr_values, msg)) return rc;
+  if (spec->n_prob == 0 && (rank_q_out(w) || rank_q_out(yhat))) { msg = W + "ess_q needs prob"; return ST_ERR_USAGE; }
+  if (spec->n_thr == 0 && (rank_exc_out(w) || rank_exc_out(yhat))) { msg = W + "ess_exc, mcse_prob and prob need thresholds"; return ST_ERR_USAGE; }
+  if (K < ST_DIAG_MIN_DRAWS) {
+    msg = W + std::to_string(K) + " draws stored, the diagnostics need at least " + std::to_string(ST_DIAG_MIN_DRAWS) +
+          " (reserve room before the saved iterations)";
+    return ST_ERR_USAGE;
+  }
+  return ST_OK;
+}
+
+// Its own texts (thr[k], side[t] = v, thr_fun before st_points_functionals_set: the callers of st_points_exceed_set read them), so
+// not check_thresholds
+int check_exceed_spec(const std::string &W, int n_thr, const double *thr, const int32_t *side, const double *thr_fun, long long q,
+                      long long n_fun, std::string &msg) {
+  if (n_thr < 1 || n_thr > ST_EXC_MAX_THRESHOLDS) {
+    msg = W + "n_thr = " + std::to_string(n_thr) + " must lie in 1 .. " + std::to_string(ST_EXC_MAX_THRESHOLDS);
+    return ST_ERR_USAGE;
+  }
+  for (long long k = 0; k < (long long)n_thr * q; ++k)
+    if (!std::isfinite(thr[k])) { msg = W + "thr[" + std::to_string(k) + "] is not finite"; return ST_ERR_USAGE; }
+  for (int t = 0; side && t < n_thr; ++t)
+    if (side[t] != 1 && side[t] != -1) { msg = W + "side[" + std::to_string(t) + "] = " + std::to_string(side[t]) + " is neither +1 nor -1"; return ST_ERR_USAGE; }
+  if (thr_fun && n_fun < 0) { msg = W + "thr_fun before st_points_functionals_set"; return ST_ERR_USAGE; }
+  for (long long k = 0; thr_fun && k < (long long)n_thr * n_fun; ++k)
+    if (!std::isfinite(thr_fun[k])) { msg = W + "thr_fun[" + std::to_string(k) + "] is not finite"; return ST_ERR_USAGE; }
   return ST_OK;
 }
 

@@ -155,6 +155,129 @@ static void check_refusals() {
   refused(check_thresholds(W, 3, 1, v, s0, 2, msg), msg, "threshold 5 is not finite");
 }
 
+// the whole texts of the three spec checkers, each refusal in its order; every buffer holds exactly n_thr x n_values values
+static void exact(int rc, const std::string &msg, int code, const std::string &text) {
+  REQUIRE(rc == code && msg == "who: " + text, "refusal \"%s\": code %d, text \"%s\"", text.c_str(), rc, msg.c_str());
+  ++n_refusals;
+}
+
+static void check_spec_refusals() {
+  const double nan = std::nan("");
+  const std::string W = "who: ";
+  std::string msg = "untouched";
+  double sink[1];
+  int32_t isink[1];
+  const std::vector<double> thr6 = {0.0, 1.0, 2.0, 3.0, 4.0, 5.0};   // 3 thresholds x 2 values
+  const int32_t sides[3] = {1, -1, 1};
+  {   // the excursion spec
+    st_excursion_spec sp{};
+    st_excursion_out w{}, y{};
+    exact(check_excursion_spec(W, nullptr, 5, 2, &w, &y, msg), msg, ST_ERR_USAGE, "no spec");
+    exact(check_excursion_spec(W, &sp, 5, 2, &w, nullptr, msg), msg, ST_ERR_USAGE, "the spec holds neither thresholds nor a band request");
+    w.count = isink;
+    sp.want_band = 1;
+    exact(check_excursion_spec(W, &sp, 5, 2, nullptr, &w, msg), msg, ST_ERR_USAGE, "count, prob, excur and joint_all need thresholds");
+    sp.thr = thr6.data();
+    sp.side = sides;
+    sp.n_thr = 0;
+    exact(check_excursion_spec(W, &sp, 5, 2, &w, &y, msg), msg, ST_ERR_USAGE, "n_thr = 0 must lie in 1 .. 8");
+    sp.n_thr = ST_EXC_MAX_THRESHOLDS + 1;   // (refused before any of the 9 x 2 values is read)
+    exact(check_excursion_spec(W, &sp, 5, 2, &w, &y, msg), msg, ST_ERR_USAGE, "n_thr = 9 must lie in 1 .. 8");
+    sp.n_thr = 3;
+    std::vector<double> bad = thr6;
+    bad[4] = nan;
+    sp.thr = bad.data();
+    exact(check_excursion_spec(W, &sp, 0, 2, &w, &y, msg), msg, ST_ERR_USAGE, "threshold 4 is not finite");   // (before the count of draws)
+    sp.thr = thr6.data();
+    const int32_t s0[3] = {1, 1, 0};
+    sp.side = s0;
+    exact(check_excursion_spec(W, &sp, 0, 2, &w, &y, msg), msg, ST_ERR_USAGE, "side 2 must be +1 or -1");
+    sp.side = sides;
+    exact(check_excursion_spec(W, &sp, 0, 2, &w, &y, msg), msg, ST_ERR_USAGE, "no draw stored (reserve room before the saved iterations)");
+    exact(check_excursion_spec(W, &sp, 1, 2, &w, &y, msg), msg, ST_ERR_USAGE, "the band needs at least 2 stored draws, 1 stored");
+    sp.want_band = 0;
+    y.maxdev = sink;   // a band output asks for the band as want_band does
+    exact(check_excursion_spec(W, &sp, 1, 2, &w, &y, msg), msg, ST_ERR_USAGE, "the band needs at least 2 stored draws, 1 stored");
+    msg = "untouched";
+    REQUIRE(check_excursion_spec(W, &sp, 2, 2, &w, &y, msg) == ST_OK && msg == "untouched", "a good excursion spec is refused: %s", msg.c_str());
+    y.maxdev = nullptr;
+    REQUIRE(check_excursion_spec(W, &sp, 1, 2, &w, &y, msg) == ST_OK, "thresholds alone on one draw are refused: %s", msg.c_str());
+  }
+  {   // the rank spec
+    st_rank_spec sp{};
+    st_rank_out w{}, y{};
+    const long long K = ST_DIAG_MIN_DRAWS;
+    exact(check_rank_spec(W, nullptr, K, 2, &w, &y, msg), msg, ST_ERR_USAGE, "no spec");
+    sp.max_lag = -1;
+    exact(check_rank_spec(W, &sp, K, 2, &w, &y, msg), msg, ST_ERR_USAGE, "max_lag must not be negative (0: the default cap)");
+    sp.max_lag = 0;
+    for (const int n : {-1, ST_RANK_MAX_PROBS + 1}) {
+      sp.n_prob = n;
+      exact(check_rank_spec(W, &sp, K, 2, &w, &y, msg), msg, ST_ERR_USAGE, "n_prob = " + std::to_string(n) + " must lie in 0 .. " + std::to_string(ST_RANK_MAX_PROBS));
+    }
+    sp.n_prob = 2;
+    exact(check_rank_spec(W, &sp, K, 2, &w, &y, msg), msg, ST_ERR_USAGE, "n_prob = 2 without prob");
+    for (const double bad : {0.0, 1.0, nan}) {
+      const double prob[2] = {0.5, bad};
+      sp.prob = prob;
+      sp.n_thr = ST_EXC_MAX_THRESHOLDS + 1;   // all of prob before the thresholds
+      exact(check_rank_spec(W, &sp, K, 2, &w, &y, msg), msg, ST_ERR_USAGE, "prob 1 must lie strictly inside (0, 1)");
+    }
+    const double prob[2] = {0.05, 0.95};
+    sp.prob = prob;
+    sp.thr = thr6.data();
+    exact(check_rank_spec(W, &sp, K, 2, &w, &y, msg), msg, ST_ERR_USAGE, "n_thr = 9 must lie in 0 .. 8");
+    sp.n_thr = -1;
+    exact(check_rank_spec(W, &sp, K, 2, &w, &y, msg), msg, ST_ERR_USAGE, "n_thr = -1 must lie in 0 .. 8");
+    sp.n_thr = 3;
+    sp.thr = nullptr;
+    exact(check_rank_spec(W, &sp, K, 2, &w, &y, msg), msg, ST_ERR_USAGE, "n_thr = 3 without thr");
+    std::vector<double> bad = thr6;
+    bad[5] = nan;
+    sp.thr = bad.data();
+    exact(check_rank_spec(W, &sp, K, 2, &w, &y, msg), msg, ST_ERR_USAGE, "threshold 5 is not finite");
+    sp.thr = thr6.data();
+    const int32_t s0[3] = {-2, 1, 1};
+    sp.side = s0;
+    exact(check_rank_spec(W, &sp, K, 2, &w, &y, msg), msg, ST_ERR_USAGE, "side 0 must be +1 or -1");
+    sp.side = sides;
+    sp.n_prob = 0;
+    y.ess_q = sink;
+    exact(check_rank_spec(W, &sp, K, 2, &w, &y, msg), msg, ST_ERR_USAGE, "ess_q needs prob");
+    sp.n_prob = 2;
+    sp.n_thr = 0;
+    for (int which = 0; which < 3; ++which) {
+      st_rank_out o{};
+      (which == 0 ? o.ess_exc : which == 1 ? o.mcse_prob : o.prob) = sink;
+      exact(check_rank_spec(W, &sp, K, 2, &o, &y, msg), msg, ST_ERR_USAGE, "ess_exc, mcse_prob and prob need thresholds");
+    }
+    sp.n_thr = 3;
+    exact(check_rank_spec(W, &sp, K - 1, 2, &w, &y, msg), msg, ST_ERR_USAGE,
+          std::to_string(K - 1) + " draws stored, the diagnostics need at least " + std::to_string(K) + " (reserve room before the saved iterations)");
+    msg = "untouched";
+    REQUIRE(check_rank_spec(W, &sp, K, 2, &w, &y, msg) == ST_OK && msg == "untouched", "a good rank spec is refused: %s", msg.c_str());
+    const st_rank_spec none{};
+    REQUIRE(check_rank_spec(W, &none, K, 2, &w, nullptr, msg) == ST_OK, "an empty rank spec is refused: %s", msg.c_str());
+  }
+  {   // the exceedance spec: thr 3 x q = 2, thr_fun 3 x n_fun = 1
+    const std::vector<double> tf3 = {0.5, 1.5, 2.5};
+    for (const int n : {-1, 0, ST_EXC_MAX_THRESHOLDS + 1})   // (before any of the n x 2 values is read)
+      exact(check_exceed_spec(W, n, thr6.data(), sides, tf3.data(), 2, 1, msg), msg, ST_ERR_USAGE, "n_thr = " + std::to_string(n) + " must lie in 1 .. 8");
+    std::vector<double> bad = thr6;
+    bad[3] = nan;
+    const int32_t s0[3] = {1, 0, 1};
+    exact(check_exceed_spec(W, 3, bad.data(), s0, tf3.data(), 2, -1, msg), msg, ST_ERR_USAGE, "thr[3] is not finite");
+    exact(check_exceed_spec(W, 3, thr6.data(), s0, tf3.data(), 2, -1, msg), msg, ST_ERR_USAGE, "side[1] = 0 is neither +1 nor -1");
+    exact(check_exceed_spec(W, 3, thr6.data(), sides, tf3.data(), 2, -1, msg), msg, ST_ERR_USAGE, "thr_fun before st_points_functionals_set");
+    std::vector<double> badf = tf3;
+    badf[2] = std::numeric_limits<double>::infinity();
+    exact(check_exceed_spec(W, 3, thr6.data(), sides, badf.data(), 2, 1, msg), msg, ST_ERR_USAGE, "thr_fun[2] is not finite");
+    msg = "untouched";
+    REQUIRE(check_exceed_spec(W, 3, thr6.data(), sides, tf3.data(), 2, 1, msg) == ST_OK && msg == "untouched", "a good exceedance spec is refused: %s", msg.c_str());
+    REQUIRE(check_exceed_spec(W, 3, thr6.data(), nullptr, nullptr, 2, -1, msg) == ST_OK, "no sides and no thr_fun are refused: %s", msg.c_str());
+  }
+}
+
 int main(int argc, char **argv) {
   const bool swap = argc > 1 && !strcmp(argv[1], "swap");
   for (const long long n : {1ll, 5ll, 64ll, 65ll})
@@ -171,6 +294,7 @@ int main(int argc, char **argv) {
       check_mask(n, kind);
     }
   check_refusals();
+  check_spec_refusals();
   printf("OK thresholds=%lld sides=%lld masks=%lld scatters=%lld refusals=%lld\n", n_thr_cases, n_neg_cases, n_mask_cases, n_scatter_cases, n_refusals);
   return 0;
 }

@@ -4,7 +4,9 @@ thresholds_in_store_order, mask_in_store_order, scatter_rows and check_threshold
 T in {0, 1, 8} (T = 0: the band-only excursions, where only the mask and the scatter run), G in {1, 3}, no perm, the identity, a
 reversal and a random permutation, thresholds per domain and per series (only the latter follow perm), every single negative side
 and its bit, every destination of a scatter written exactly once and none with rows = 0, and the refusals of a NaN, an infinity, a
-side of 0 and the counts -1 and ST_EXC_MAX_THRESHOLDS + 1 with the texts the C-ABI calls report.
+side of 0 and the counts -1 and ST_EXC_MAX_THRESHOLDS + 1 with the texts the C-ABI calls report.  The three spec checkers the
+C-ABI calls and the whole fit's plan share (check_excursion_spec, check_rank_spec, check_exceed_spec): every refusal of each with
+its whole text, in its order, and a count out of range refused before any value is read.
 
 The counts the program prints prove that the loops ran; one negative case proves that the checks can fail; and the same program
 built with the address and undefined-behaviour sanitizers runs clean (every input array has exactly the size a helper may read)."""
