@@ -40,7 +40,14 @@ extern "C" {
 
 typedef struct st_handle_s *st_handle;
 
-/* Inputs of the SpamTreeMV constructor (spamtree_model.cpp:8-37) that the hot path needs. */
+/* Inputs of the SpamTreeMV constructor (spamtree_model.cpp:8-37) that the hot path needs.
+ * Topologies beyond the tree builder's regular ones are supported (tests/tree_mutations.py builds them): a block may hang from
+ * any shallower reference level, as long as parents(u) = parents(last parent) + [last parent], so the blocks of one level may
+ * have chains of different lengths; blocks of one level may have any widths; a block may be empty or hold NA rows only (a
+ * prediction block: it needs a parent, has no cache -- st_get_block refuses it with "block has no observations, hence no
+ * cache" -- and its entries of st_get_comps are 0); a reference block may have from none to 64 direct child groups.  Sharded
+ * handles (world > 1) need every block below the cut level to descend from a block on it, and a rank's blocks contiguous in
+ * every level: st_create refuses a level-skipping tree there by name. */
 typedef struct st_problem {
   int64_t n_all;               /* rows (observed + NA)                                   coords.n_rows            */
   int32_t d;                   /* coordinate columns, must be 2                           coords.n_cols            */
