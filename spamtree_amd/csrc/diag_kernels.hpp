@@ -52,14 +52,6 @@ __device__ __forceinline__ double diag_allsum(double v) {
   return v;
 }
 
-// LDS written by one lane of the wave and read by another: order the wave's own LDS traffic (no workgroup barrier: a series belongs
-// to one wave)
-__device__ __forceinline__ void diag_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // The diagnostics of one series by one wave: x[0 .. K) (LDS, or global memory that only this wave touches) is centred in place.
 // P1 .. P4 and, with LAGS, the lag pairs, in the order of the header; every lane returns the same values.  Without LAGS only sd
 // and rhat are formed (ess = NaN, mcse = 0, pairs = 0).  k_series_diag and the rank-normalised kernel (k_rank.hip) share this text.
@@ -86,7 +78,7 @@ __device__ __forceinline__ DiagOut diag_series_wave(double *x, int K, int L, int
   }
   g0 = diag_allsum(g0);
   const double mu1 = diag_allsum(b1) / dh, mu2 = diag_allsum(b2) / dh;
-  diag_wave_sync();
+  wave_lds_sync();
   // P4: the half variances
   double v1 = 0.0, v2 = 0.0;
   for (int s = lane; s < K; s += 64) {
@@ -192,7 +184,7 @@ __device__ __forceinline__ DiagOut diag_chain_wave(double *x, int K, int M, int 
     g0 = fma(y, y, g0);
   }
   g0 = diag_allsum(g0);
-  diag_wave_sync();
+  wave_lds_sync();
   // C1 .. C3 per chain; the lanes' keepsakes
   double nuL = 0.0, mL = 0.0, vL = 0.0;
   double a0 = 0.0;   // a_0's lane sums, over the chains: formed in C2, as the d_s are (the lag pass's own order at t = 0)
@@ -213,7 +205,7 @@ __device__ __forceinline__ DiagOut diag_chain_wave(double *x, int K, int M, int 
       if (s >= N - h) b2 += d;
     }
     const double mu1 = diag_allsum(b1) / dh, mu2 = diag_allsum(b2) / dh;
-    diag_wave_sync();
+    wave_lds_sync();
     double v1 = 0.0, v2 = 0.0;
     for (int s = lane; s < N; s += 64) {
       const double d = xc[s];

@@ -4,6 +4,7 @@
 #include "st_handle.hpp"
 #include "diag_kernels.hpp"
 #include "draw_store.hpp"
+#include "series_tile.hpp"
 
 // CHAINS: the multi-chain definition (A.M >= 2 chains, diag_chain_wave); staging, tiles and outputs are the same
 template <bool CHAINS>
@@ -12,10 +13,9 @@ __global__ __launch_bounds__(DIAG_NT) void k_series_diag(DiagArgs A) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, nw = blockDim.x >> 6;
   const int K = A.K, Kp = A.Kp, R = A.R;
   const long long row0 = (long long)blockIdx.x * R;
-  for (int idx = tid; idx < R * K; idx += blockDim.x) {
-    const int d = idx / R, r = idx - d * R;   // R consecutive series of one draw: contiguous in memory
-    if (row0 + r < A.n) lds[(size_t)r * Kp + d] = A.draws[(size_t)d * A.n + row0 + r];
-  }
+  const int nr = (int)(A.n - row0 < R ? A.n - row0 : R);
+  // (no padding column: fill = K; the rows >= nr of the R Kp doubles get +inf, and nothing reads them)
+  tile_stage(lds, R, Kp, K, K, nr, tid, blockDim.x, [&](int d, int r) { return A.draws[(size_t)d * A.n + row0 + r]; });
   __syncthreads();
   for (int r = wid; r < R && row0 + r < A.n; r += nw) {
     double *x = lds + (size_t)r * Kp;
@@ -47,8 +47,7 @@ int series_diag_launch(const DiagArgs &A, size_t lds_limit, hipStream_t st) {
   const auto kernel = A.M > 1 ? k_series_diag<true> : k_series_diag<false>;
   (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit);
   hipLaunchKernelGGL(kernel, dim3((unsigned)((A.n + A.R - 1) / A.R)), dim3(64 * std::min(A.R, DIAG_NT / 64)), lds, st, A);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_rc();
 }
 
 // diagnostics of one of the store's two sets of draws into out's host arrays (any may be NULL), element i of the store at
@@ -76,17 +75,7 @@ static int series_diag_store(st_handle_s *h, const char *who, const DrawStore &s
     if (e) { h->err = std::string(who) + " launch: " + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
   }
   // only what the caller asked for comes to the host
-  double *const dst[4] = {out->ess, out->mcse, out->sd, out->rhat};
-  std::vector<double> tmp((size_t)4 * n);
-  std::vector<int> tl(out->lags ? (size_t)n : 0);
-  for (int k = 0; k < 4; ++k)
-    if (dst[k]) HCHK(h, hipMemcpyAsync(tmp.data() + (size_t)k * n, d_out.p + (size_t)k * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (out->lags) HCHK(h, hipMemcpyAsync(tl.data(), d_lags.p, tl.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  for (int k = 0; k < 4; ++k)
-    if (dst[k]) scatter_rows(dst[k], tmp.data() + (size_t)k * n, 1, n, s.perm);
-  if (out->lags) scatter_rows(out->lags, tl.data(), 1, n, s.perm);
-  return ST_OK;
+  return store_read_back(h, s, {{out->ess, A.ess, 1}, {out->mcse, A.mcse, 1}, {out->sd, A.sd, 1}, {out->rhat, A.rhat, 1}}, {{out->lags, A.lags, 1}});
 }
 
 // the single-chain call is the multi-chain one with one chain: the same refusals in the same order, the same kernel as before

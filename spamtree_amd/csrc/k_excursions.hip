@@ -349,24 +349,14 @@ static int series_exc_store(st_handle_s *h, const char *who, const DrawStore &s,
     if (e != hipSuccess) { h->err = std::string(who) + " launch: " + hipGetErrorString(e); return ST_ERR_HIP; }
   }
   // only what the caller asked for comes to the host
-  std::vector<int> hc(out->count ? (size_t)T * n : 0);
-  std::vector<double> hp(out->prob ? (size_t)T * n : 0), he(out->excur ? (size_t)T * n : 0), hm(out->mean ? (size_t)n : 0), hs(out->sd ? (size_t)n : 0);
+  // the three that are not per series first: the read-back's one synchronise covers them
   std::vector<unsigned long long> hf(out->n_flat ? (size_t)G : 0);
   const auto d2h = [&](void *dst, const void *src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream); };
-  if (out->count) HCHK(h, d2h(hc.data(), A.count, hc.size() * sizeof(int)));
-  if (out->prob) HCHK(h, d2h(hp.data(), A.prob, hp.size() * sizeof(double)));
-  if (out->excur) HCHK(h, d2h(he.data(), A.excur, he.size() * sizeof(double)));
-  if (out->mean) HCHK(h, d2h(hm.data(), A.mean, hm.size() * sizeof(double)));
-  if (out->sd) HCHK(h, d2h(hs.data(), A.sd, hs.size() * sizeof(double)));
   if (out->joint_all) HCHK(h, d2h(out->joint_all, A.joint_all, (size_t)TG * sizeof(double)));
   if (out->maxdev) HCHK(h, d2h(out->maxdev, A.dev, (size_t)G * K * sizeof(double)));   // the bit patterns are the doubles
   if (out->n_flat) HCHK(h, d2h(hf.data(), A.n_flat, hf.size() * sizeof(unsigned long long)));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  if (out->count) scatter_rows(out->count, hc.data(), T, n, s.perm);
-  if (out->prob) scatter_rows(out->prob, hp.data(), T, n, s.perm);
-  if (out->excur) scatter_rows(out->excur, he.data(), T, n, s.perm);
-  if (out->mean) scatter_rows(out->mean, hm.data(), 1, n, s.perm);
-  if (out->sd) scatter_rows(out->sd, hs.data(), 1, n, s.perm);
+  if (const int rc = store_read_back(h, s, {{out->prob, A.prob, T}, {out->excur, A.excur, T}, {out->mean, A.mean, 1}, {out->sd, A.sd, 1}},
+                                     {{out->count, A.count, T}})) return rc;
   for (int k = 0; out->n_flat && k < G; ++k) out->n_flat[k] = (int64_t)hf[k];
   return ST_OK;
 }

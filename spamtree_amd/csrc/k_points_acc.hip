@@ -29,6 +29,5 @@ __global__ __launch_bounds__(NT) void k_points_acc(PointsAccArgs A) {
 int points_acc_launch(const PointsAccArgs &A, hipStream_t st) {
   if (A.n <= 0) return 0;
   hipLaunchKernelGGL(k_points_acc, dim3((unsigned)((A.n + NT - 1) / NT)), dim3(NT), 0, st, A);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_rc();
 }

@@ -68,19 +68,14 @@ __global__ __launch_bounds__(NT) void k_exceed_fun_acc(ExceedFunArgs A) {
   }
 }
 
-static int ex_last() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
-}
-
 int points_exceed_launch(const ExceedArgs &A, hipStream_t st) {
   if (A.n <= 0 || A.n_thr <= 0) return 0;
   hipLaunchKernelGGL(k_exceed_acc, dim3((unsigned)((A.n + NT - 1) / NT)), dim3(NT), 0, st, A);
-  return ex_last();
+  return launch_rc();
 }
 
 int points_exceed_fun_launch(const ExceedFunArgs &A, hipStream_t st) {
   if (A.n_fun <= 0 || A.n_thr <= 0) return 0;
   hipLaunchKernelGGL(k_exceed_fun_acc, dim3((unsigned)((A.n_fun + NT - 1) / NT)), dim3(NT), 0, st, A);
-  return ex_last();
+  return launch_rc();
 }

@@ -72,6 +72,5 @@ int points_fun_launch(const FunArgs &A, hipStream_t st) {
   const long long nc = A.n_lin_chunks + A.n_var_chunks;
   if (nc > 0) hipLaunchKernelGGL(k_fun_chunks, dim3((unsigned)((nc + NT / 64 - 1) / (NT / 64))), dim3(NT), 0, st, A);
   hipLaunchKernelGGL(k_fun_finish, dim3((unsigned)((A.n_fun + NT - 1) / NT)), dim3(NT), 0, st, A);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_rc();
 }

@@ -139,24 +139,20 @@ __global__ __launch_bounds__(NT) void k_score_joint_acc(ScoreJointArgs A) {
   A.jacc[2 * k + 1] = Sa;
 }
 
-// A workgroup takes R points: d = yhat* - y of their stored draws into R LDS rows (padded to Kpad with +inf), k_qtile's sort, then
+// A workgroup takes R points: d = yhat* - y of their stored draws into R LDS rows (padded to Kpad with +inf), series_tile.hpp's sort, then
 // one wave per row: lane l adds the terms k = l, l + 64, ... in ascending order -- s1 += |d_(k)|, s2 = fma(2 k - K - 1, d_(k), s2)
 // -- the 64 lane sums go through a six-level xor butterfly, and crps = s1 / K - s2 / K^2.
 __global__ __launch_bounds__(NT) void k_score_crps(ScoreCrpsArgs A) {
   extern __shared__ double lds[];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, R = A.R, K = A.Kpad;
   const long long row0 = (long long)blockIdx.x * R;
-  for (int idx = tid; idx < R * K; idx += NT) {
-    const int d = idx / R, r = idx - d * R;   // R consecutive points of one draw: contiguous in memory
-    double v = __builtin_inf();
-    if (d < A.keep && row0 + r < A.n) {
-      const double y = A.y[row0 + r];
-      if (y == y) v = A.draws[(size_t)d * A.n + row0 + r] - y;
-    }
-    lds[(size_t)r * K + d] = v;
-  }
+  const int nr = (int)(A.n - row0 < R ? A.n - row0 : R);
+  tile_stage(lds, R, K, K, A.keep, nr, tid, NT, [&](int d, int r) {
+    const double y = A.y[row0 + r];
+    return y == y ? A.draws[(size_t)d * A.n + row0 + r] - y : __builtin_inf();
+  });
   __syncthreads();
-  qt_sort_rows(lds, R, K, tid);
+  tile_sort_rows(lds, R, K, tid, NT);
   for (int r = wid; r < R; r += NT / 64) {
     if (row0 + r >= A.n) break;
     const double *a = lds + (size_t)r * K;
@@ -175,15 +171,10 @@ __global__ __launch_bounds__(NT) void k_score_crps(ScoreCrpsArgs A) {
   }
 }
 
-static int sc_last() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
-}
-
 int points_score_launch(const ScoreArgs &A, hipStream_t st) {
   if (A.n <= 0) return 0;
   hipLaunchKernelGGL(k_score_acc, dim3((unsigned)((A.n + NT - 1) / NT)), dim3(NT), 0, st, A);
-  return sc_last();
+  return launch_rc();
 }
 
 int points_score_joint_launch(const ScoreJointArgs &A, int gmax, hipStream_t st) {
@@ -192,12 +183,12 @@ int points_score_joint_launch(const ScoreJointArgs &A, int gmax, hipStream_t st)
   if (gmax <= 4) hipLaunchKernelGGL(k_score_joint_acc<4>, grid, dim3(NT), 0, st, A);
   else if (gmax <= 8) hipLaunchKernelGGL(k_score_joint_acc<8>, grid, dim3(NT), 0, st, A);
   else hipLaunchKernelGGL(k_score_joint_acc<16>, grid, dim3(NT), 0, st, A);
-  return sc_last();
+  return launch_rc();
 }
 
 int points_score_crps_launch(const ScoreCrpsArgs &A, size_t lds_limit, hipStream_t st) {
   if (A.n <= 0) return 0;
   (void)hipFuncSetAttribute((const void *)k_score_crps, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit);
   hipLaunchKernelGGL(k_score_crps, dim3((unsigned)((A.n + A.R - 1) / A.R)), dim3(NT), (size_t)A.R * A.Kpad * sizeof(double), st, A);
-  return sc_last();
+  return launch_rc();
 }

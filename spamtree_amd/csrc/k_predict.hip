@@ -35,6 +35,5 @@ int points_launch(const PointsLaunch &L, const PointsArgs &A, const CovPar &cp, 
     mask |= 1 << (PP_ROUTE_GENERIC - 1);
   }
   *route_mask = mask;
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_rc();
 }

@@ -336,8 +336,7 @@ int points_joint_launch(const JointLaunch &L, const JointArgs &J, const CovPar &
     mask |= 1 << (PP_ROUTE_JOINT_GENERIC - 1);
   }
   *route_mask |= mask;
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_rc();
 }
 
 // ---- the pair summaries of st_points_accumulate on a joint set (PointsPairArgs).  They live here, not beside k_points_acc: that
@@ -365,6 +364,5 @@ __global__ __launch_bounds__(NT) void k_points_pair_acc(PointsPairArgs A) {
 int points_pair_acc_launch(const PointsPairArgs &A, hipStream_t st) {
   if (A.n <= 0) return 0;
   hipLaunchKernelGGL(k_points_pair_acc, dim3((unsigned)((A.n + NT - 1) / NT)), dim3(NT), 0, st, A);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_rc();
 }

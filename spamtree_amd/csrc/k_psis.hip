@@ -2,52 +2,8 @@
 // evaluation order, spamtree_amd/psis.py the definition).  k_loo_psis reads a store and writes only its own outputs; k_psis_finish
 // reduces them per outcome.  Neither draws anything nor touches any state of the chain.
 #include "psis_kernels.hpp"
+#include "series_tile.hpp"       // stage, sort and the searches of a sorted row: no floating-point arithmetic in them
 #pragma clang fp contract(off)
-
-// R rows of Kpad = 2^k doubles each in LDS, every row sorted ascending by a bitonic network over the workgroup (k_series_rank's).
-// The rows are in LDS behind a barrier on entry and sorted behind one on return.
-__device__ __forceinline__ void psis_sort_rows(double *lds, int R, int Kpad, int tid) {
-  const int half = Kpad >> 1;
-  for (int k = 2; k <= Kpad; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int p = tid; p < R * half; p += PSIS_NT) {
-        const int r = p / half, i = p - r * half;
-        const int i1 = 2 * j * (i / j) + (i % j), i2 = i1 + j;
-        double *a = lds + (size_t)r * Kpad;
-        const double x = a[i1], y = a[i2];
-        const bool up = (i1 & k) == 0;
-        if ((x > y) == up) { a[i1] = y; a[i2] = x; }
-      }
-      __syncthreads();
-    }
-  }
-}
-
-__device__ __forceinline__ void psis_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// #{a[0 .. K) < v} and #{a[0 .. K) <= v} of the ascending a (indices stay in [0, K))
-__device__ __forceinline__ int psis_count_below(const double *a, int K, double v) {
-  int lo = 0, n = K;
-  while (n > 0) {
-    const int half = n >> 1;
-    if (a[lo + half] < v) { lo += half + 1; n -= half + 1; }
-    else n = half;
-  }
-  return lo;
-}
-__device__ __forceinline__ int psis_count_upto(const double *a, int K, double v, int lo) {
-  int hi = lo, n = K - lo;
-  while (n > 0) {
-    const int half = n >> 1;
-    if (a[hi + half] <= v) { hi += half + 1; n -= half + 1; }
-    else n = half;
-  }
-  return hi;
-}
 
 __device__ __forceinline__ bool psis_finite(double v) { return v >= -__DBL_MAX__ && v <= __DBL_MAX__; }
 
@@ -64,7 +20,7 @@ __device__ __forceinline__ void psis_series_wave(const PsisArgs &A, long long i,
   const long long n = A.n;
   const int K = A.K;
   const double inf = __builtin_inf(), nan = __builtin_nan("");
-  const int S = psis_count_below(a, K, inf);
+  const int S = sorted_count_below(a, K, inf);
   if (S == 0) {
     if (lane == 0) {
       for (int k = 0; k < PSIS_NOUT; ++k) A.out[(size_t)k * n + i] = nan;
@@ -83,7 +39,7 @@ __device__ __forceinline__ void psis_series_wave(const PsisArgs &A, long long i,
   }
   if (smooth) {
     for (int j = lane; j < M; j += 64) X[j] = exp(a[S - M + j] - c) - ecut;
-    psis_wave_sync();
+    wave_lds_sync();
     const double xs = X[(M + 2) / 4 - 1], xN = X[M - 1];
     smooth = xs != 0.0;
     if (smooth) {
@@ -106,14 +62,14 @@ __device__ __forceinline__ void psis_series_wave(const PsisArgs &A, long long i,
       const double sigma = -k / th;
       khat = (k * dM + 5.0) / (dM + 10.0);
       smooth = psis_finite(khat) && psis_finite(sigma);
-      psis_wave_sync();   // every lane has read x before the smoothed values replace it
+      wave_lds_sync();   // every lane has read x before the smoothed values replace it
       if (smooth) {
         for (int j = lane; j < M; j += 64) {
           const double l1p = log1p(-((double)j + 0.5) / dM);
           const double q = khat == 0.0 ? -sigma * l1p : sigma * expm1(-khat * l1p) / khat;
           X[j] = fmin(log(q + ecut), 0.0);
         }
-        psis_wave_sync();
+        wave_lds_sync();
       } else khat = inf;
     }
   }
@@ -128,8 +84,8 @@ __device__ __forceinline__ void psis_series_wave(const PsisArgs &A, long long i,
     int lo = 0;
     bool tied = false;
     if (cand) {
-      lo = psis_count_below(a, S, tv);
-      tied = psis_count_upto(a, S, tv, lo) - lo > 1;
+      lo = sorted_count_below(a, S, tv);
+      tied = sorted_count_upto(a, S, tv, lo) - lo > 1;
     }
     int e = 0;
     unsigned long long tm = __ballot(tied);
@@ -184,18 +140,13 @@ __global__ __launch_bounds__(PSIS_NT) void k_loo_psis(PsisArgs A) {
     const long long row0 = tile * R;
     const int nr = (int)(A.n - row0 < R ? A.n - row0 : R);
     // 1: stage
-    for (int idx = tid; idx < R * Kpad; idx += PSIS_NT) {
-      const int d = idx / R, r = idx - d * R;   // R consecutive series of one draw: contiguous in memory
-      double v = inf;
-      if (d < K && r < nr) {
-        v = A.t[(size_t)d * A.n + row0 + r];
-        if (!psis_finite(v)) v = inf;
-      }
-      Srt[(size_t)r * Kpad + d] = v;
-    }
+    tile_stage(Srt, R, Kpad, Kpad, K, nr, tid, PSIS_NT, [&](int d, int r) {
+      const double v = A.t[(size_t)d * A.n + row0 + r];
+      return psis_finite(v) ? v : inf;
+    });
     __syncthreads();
     // 2: sort
-    psis_sort_rows(Srt, R, Kpad, tid);
+    tile_sort_rows(Srt, R, Kpad, tid, PSIS_NT);
     // 3: one wave per series
     for (int r = wid; r < nr; r += PSIS_NT / 64) psis_series_wave(A, row0 + r, Srt + (size_t)r * Kpad, Xt + (size_t)r * PSIS_MAX_TAIL, lane);
     __syncthreads();   // the next tile restages the rows
@@ -246,13 +197,11 @@ int psis_launch(const PsisArgs &A, hipStream_t st) {
   const hipError_t ea = hipFuncSetAttribute((const void *)k_loo_psis, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (ea != hipSuccess) return (int)ea;
   hipLaunchKernelGGL(k_loo_psis, dim3((unsigned)psis_grid(A.n, A.R)), dim3(PSIS_NT), lds, st, A);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_rc();
 }
 
 int psis_finish_launch(const PsisFinishArgs &A, hipStream_t st) {
   if (A.n <= 0 || A.q < 1) return 0;
   hipLaunchKernelGGL(k_psis_finish, dim3(A.q), dim3(NT), 0, st, A);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_rc();
 }

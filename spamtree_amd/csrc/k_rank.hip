@@ -6,42 +6,12 @@
 #include "norm_quantile.hpp"
 #include "rank_kernels.hpp"
 #include "draw_store.hpp"
+#include "series_tile.hpp"
 
-// R rows of Kpad = 2^k doubles each in LDS (row r at lds + r Kpad), every row sorted ascending by a bitonic network over the
-// workgroup (qt_sort_rows' network).  The rows are in LDS behind a barrier on entry and sorted behind one on return.
-__device__ __forceinline__ void rank_sort_rows(double *lds, int R, int Kpad, int tid) {
-  const int half = Kpad >> 1;
-  for (int k = 2; k <= Kpad; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int p = tid; p < R * half; p += RANK_NT) {
-        const int r = p / half, i = p - r * half;
-        const int i1 = 2 * j * (i / j) + (i % j), i2 = i1 + j;
-        double *a = lds + (size_t)r * Kpad;
-        const double x = a[i1], y = a[i2];
-        const bool up = (i1 & k) == 0;
-        if ((x > y) == up) { a[i1] = y; a[i2] = x; }
-      }
-      __syncthreads();
-    }
-  }
-}
-
-// r2 = lo + hi + 1 of v among the sorted a[0 .. K): lo = #{a < v}, hi = #{a <= v}, two binary searches (indices stay in [0, K])
+// r2 = lo + hi + 1 of v among the sorted a[0 .. K): lo = #{a < v}, hi = #{a <= v}
 __device__ __forceinline__ int rank_twice(const double *a, int K, double v) {
-  int lo = 0, n = K;
-  while (n > 0) {
-    const int half = n >> 1;
-    if (a[lo + half] < v) { lo += half + 1; n -= half + 1; }
-    else n = half;
-  }
-  int hi = lo;
-  n = K - lo;
-  while (n > 0) {
-    const int half = n >> 1;
-    if (a[hi + half] <= v) { hi += half + 1; n -= half + 1; }
-    else n = half;
-  }
-  return lo + hi + 1;
+  const int lo = sorted_count_below(a, K, v);
+  return lo + sorted_count_upto(a, K, v, lo) + 1;
 }
 
 // the bits of a word whose draw index base + b lies below `limit`
@@ -189,19 +159,15 @@ __global__ __launch_bounds__(RANK_NT) void k_series_rank(RankArgs A) {
     if (tid < RANK_MAX_R) s_nan[tid] = 0;
     __syncthreads();
     // 1: stage
-    for (int idx = tid; idx < R * Kpad; idx += RANK_NT) {
-      const int d = idx / R, r = idx - d * R;   // R consecutive series of one draw: contiguous in memory
-      double v = inf;
-      if (d < K && r < nr) {
-        v = A.draws[(size_t)d * A.n + row0 + r];
-        X[(size_t)r * K + d] = v;
-        if (v != v) s_nan[r] = 1;   // (every writer stores the same value)
-      }
-      S[(size_t)r * Kpad + d] = v;
-    }
+    tile_stage(S, R, Kpad, Kpad, K, nr, tid, RANK_NT, [&](int d, int r) {
+      const double v = A.draws[(size_t)d * A.n + row0 + r];
+      X[(size_t)r * K + d] = v;
+      if (v != v) s_nan[r] = 1;   // (every writer stores the same value)
+      return v;
+    });
     __syncthreads();
     // 2: sort; the median and the quantile thresholds (exceedances alone need neither: they read X)
-    if (need_sort) rank_sort_rows(S, R, Kpad, tid);
+    if (need_sort) tile_sort_rows(S, R, Kpad, tid, RANK_NT);
     if (need_sort && tid < 16 * nr) {
       const int r = tid >> 4, k = tid & 15;
       const double *a = S + (size_t)r * Kpad;
@@ -224,7 +190,7 @@ __global__ __launch_bounds__(RANK_NT) void k_series_rank(RankArgs A) {
         S[idx] = (s < K && r < nr) ? fabs(X[(size_t)r * K + s] - s_med[r]) : inf;
       }
       __syncthreads();
-      rank_sort_rows(S, R, Kpad, tid);
+      tile_sort_rows(S, R, Kpad, tid, RANK_NT);
       if (A.z_global) rank_scores_and_moments<true, CHAINS>(A, S, Zg, X, nr, s_med, s_nan, s_fold, tid);
       else rank_scores_and_moments<true, CHAINS>(A, S, Zl, X, nr, s_med, s_nan, s_fold, tid);
     }
@@ -277,9 +243,9 @@ __global__ __launch_bounds__(RANK_NT) void k_series_rank(RankArgs A) {
               if (lane == ch) cL = cc;
               cnt += cc;
             }
-            diag_wave_sync();
+            wave_lds_sync();
             ess = rank_chain_indicator_ess(B, Wc, N, A.M, cL, A.L, lane, &lags);
-            diag_wave_sync();   // the next indicator overwrites the masks
+            wave_lds_sync();   // the next indicator overwrites the masks
           } else if (!bad) {
             for (int base = 0; base < K; base += 64) {
               const int s = base + lane;
@@ -292,9 +258,9 @@ __global__ __launch_bounds__(RANK_NT) void k_series_rank(RankArgs A) {
               if (lane == 0) B[base >> 6] = word;
               cnt += __popcll(word);
             }
-            diag_wave_sync();
+            wave_lds_sync();
             ess = rank_indicator_ess(B, W, K, cnt, A.L, lane, &lags);
-            diag_wave_sync();   // the next indicator overwrites the mask
+            wave_lds_sync();   // the next indicator overwrites the mask
           }
           if (v == A.n_prob && t < 0) e05 = ess;
           if (lane == 0) {
@@ -321,8 +287,7 @@ int series_rank_order(double prob, long long K) {
 }
 
 bool series_rank_plan(long long K, size_t lds_limit, int *R, int *Kpad, int *Kz, int *z_global) {
-  size_t kpad = 2;
-  while ((long long)kpad < K) kpad <<= 1;
+  const size_t kpad = (size_t)tile_pow2(K);
   const size_t kz = (size_t)(K | 1), lim = lds_limit > RANK_LDS_STATIC ? lds_limit - RANK_LDS_STATIC : 0;
   *Kpad = (int)kpad; *Kz = (int)kz;
   for (int zg = K > RANK_LDS_Z_MAX_K ? 1 : 0; zg < 2; ++zg) {   // z in LDS where it fits beside the sorted copy, else in the slice
@@ -391,23 +356,11 @@ static int series_rank_store(st_handle_s *h, const char *who, const DrawStore &s
     if (e != hipSuccess) { h->err = std::string(who) + " launch: " + hipGetErrorString(e); return ST_ERR_HIP; }
   }
   // only what the caller asked for comes to the host
-  struct Part { double *dst; const double *src; int rows; };
-  const Part parts[] = {{out->rhat_rank, A.rhat_rank, 1}, {out->rhat_bulk, A.rhat_bulk, 1}, {out->rhat_fold, A.rhat_fold, 1},
-                        {out->ess_bulk, A.ess_bulk, 1}, {out->ess_tail, A.ess_tail, 1}, {out->ess_q, A.ess_q, n_prob},
-                        {out->ess_exc, A.ess_exc, n_thr}, {out->mcse_prob, A.mcse_prob, n_thr}, {out->prob, A.prob, n_thr}};
-  std::vector<std::vector<double>> tmp(sizeof(parts) / sizeof(parts[0]));
-  std::vector<int> tl(out->lags_bulk ? (size_t)n : 0);
-  for (size_t k = 0; k < tmp.size(); ++k) {
-    if (!parts[k].dst || !parts[k].src || parts[k].rows == 0) continue;
-    tmp[k].resize((size_t)parts[k].rows * n);
-    HCHK(h, hipMemcpyAsync(tmp[k].data(), parts[k].src, tmp[k].size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  }
-  if (out->lags_bulk) HCHK(h, hipMemcpyAsync(tl.data(), d_lags.p, tl.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HCHK(h, hipStreamSynchronize(h->stream));
-  for (size_t k = 0; k < tmp.size(); ++k)
-    if (!tmp[k].empty()) scatter_rows(parts[k].dst, tmp[k].data(), parts[k].rows, n, s.perm);
-  if (out->lags_bulk) scatter_rows(out->lags_bulk, tl.data(), 1, n, s.perm);
-  return ST_OK;
+  return store_read_back(h, s,
+                         {{out->rhat_rank, A.rhat_rank, 1}, {out->rhat_bulk, A.rhat_bulk, 1}, {out->rhat_fold, A.rhat_fold, 1},
+                          {out->ess_bulk, A.ess_bulk, 1}, {out->ess_tail, A.ess_tail, 1}, {out->ess_q, A.ess_q, n_prob},
+                          {out->ess_exc, A.ess_exc, n_thr}, {out->mcse_prob, A.mcse_prob, n_thr}, {out->prob, A.prob, n_thr}},
+                         {{out->lags_bulk, A.lags_bulk, 1}});
 }
 
 // the single-chain call is the multi-chain one with one chain: the same refusals in the same order, the same kernel as before

@@ -223,13 +223,11 @@ int lgo_groups_launch(const LgoArgs &A, hipStream_t st) {
   if (A.G <= 0) return 0;
   constexpr int NG = LGO_WG / LGO_MAXG;
   hipLaunchKernelGGL(k_lgo_groups, dim3((A.G + NG - 1) / NG), dim3(LGO_WG), 0, st, A);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_rc();
 }
 
 int lgo_finish_launch(const LgoFinishArgs &A, hipStream_t st) {
   if (A.G <= 0 || A.q < 1) return 0;
   hipLaunchKernelGGL(k_lgo_finish, dim3(A.q + 1), dim3(NT), 0, st, A);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_rc();
 }

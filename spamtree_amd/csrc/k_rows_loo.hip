@@ -193,8 +193,7 @@ int loo_launch(const LooLevelLaunch *lv, int nlev, const LooArgs &A0, hipStream_
     else if (pairs) loo_launch_level<false, true>(L.count, lds, st, A);
     else loo_launch_level<false, false>(L.count, lds, st, A);
     mask |= 1 << ((L.isref ? LOO_ROUTE_REF : LOO_ROUTE_LEAF) - 1);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { *route_mask = mask; return (int)e; }
+    if (const int e = launch_rc()) { *route_mask = mask; return e; }
   }
   *route_mask = mask;
   return 0;
@@ -203,6 +202,5 @@ int loo_launch(const LooLevelLaunch *lv, int nlev, const LooArgs &A0, hipStream_
 int loo_finish_launch(const LooFinishArgs &A, hipStream_t st) {
   if (A.n <= 0 || A.q < 1) return 0;
   hipLaunchKernelGGL(k_loo_finish, dim3(A.q), dim3(NT), 0, st, A);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_rc();
 }

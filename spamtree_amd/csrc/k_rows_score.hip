@@ -117,15 +117,10 @@ __global__ __launch_bounds__(NT) void k_rows_score_totals(RowsTotalsArgs A) {
   }
 }
 
-static int rs_last() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
-}
-
 int rows_score_launch(const RowsScoreArgs &A, hipStream_t st) {
   if (A.n <= 0) return 0;
   hipLaunchKernelGGL(k_rows_score_acc, dim3((unsigned)((A.n + NT - 1) / NT)), dim3(NT), 0, st, A);
-  return rs_last();
+  return launch_rc();
 }
 
 int rows_score_totals_launch(const RowsTotalsArgs &A, int q, double *out, hipStream_t st) {
@@ -135,5 +130,5 @@ int rows_score_totals_launch(const RowsTotalsArgs &A, int q, double *out, hipStr
   if (A.n <= 0 || q < 1 || q > QMAX) return 0;
   hipLaunchKernelGGL(tab[q - 1], dim3(STATS_WG), dim3(NT), 0, st, A);
   hipLaunchKernelGGL(k_stats_final, dim3(q * RS_NSUM), dim3(NT), 0, st, A.partial, STATS_WG, q * RS_NSUM, out);
-  return rs_last();
+  return launch_rc();
 }

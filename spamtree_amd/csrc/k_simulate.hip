@@ -25,8 +25,7 @@ int simulate_normals(double *out, const long long *dev2model, long long n, int n
   if (cnt > 0)
     hipLaunchKernelGGL(k_sim_normals, dim3((unsigned)((cnt + SIM_NT - 1) / SIM_NT)), dim3(SIM_NT), 0, st, out, dev2model, n, nd,
                        nd_pad, iter0, stream, seed);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_rc();
 }
 
 template <int ND>
@@ -69,8 +68,7 @@ int simulate_launch(const SimLevel *lv, int nlev, const SimArgs &A, int nd_pad, 
       default: launch_level<16>(L, A, st);
     }
     mask |= 1 << (L.route - 1);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { *route_mask = mask; return (int)e; }
+    if (const int e = launch_rc()) { *route_mask = mask; return e; }
   }
   *route_mask = mask;
   return 0;

@@ -1,6 +1,7 @@
 // Phase C, the O(n) statistics, reductions, RNG, summaries and the small pack / gather kernels of the multi-GPU protocol.
 #pragma once
 #include "st_device.hpp"
+#include "series_tile.hpp"
 
 // k_loglik: phase C, one block per workgroup (any size)
 struct LoglikArgs {
@@ -40,32 +41,11 @@ struct QtArgs {
   double q;
   double *out;
 };
-// The launch rule of k_qtile and k_score_crps, which sort with qt_sort_rows: rows padded to Kpad = 2^k >= max(keep, 2), R rows per
+// The launch rule of k_qtile and k_score_crps (series_tile.hpp's stage and sort): rows padded to Kpad = tile_pow2(keep), R rows per
 // workgroup within 128 KiB of LDS (R Kpad doubles), grid ceil(n / R)
 static inline void qtile_plan(long long keep, int *Kpad, int *R) {
-  *Kpad = 2;
-  while (*Kpad < keep) *Kpad <<= 1;
+  *Kpad = (int)tile_pow2(keep);
   *R = std::max(1, std::min(8, (int)(128 * 1024 / ((size_t)*Kpad * 8))));
-}
-
-// The sort of k_qtile, shared with k_score_crps (k_points_score.hip): R rows of K = 2^k doubles each in LDS (row r at lds + r K),
-// every row sorted ascending by a bitonic network over the NT threads of the workgroup.  The rows are in LDS behind a barrier on
-// entry and sorted behind one on return.
-__device__ __forceinline__ void qt_sort_rows(double *lds, int R, int K, int tid) {
-  const int half = K >> 1;
-  for (int k = 2; k <= K; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int p = tid; p < R * half; p += NT) {
-        const int r = p / half, i = p - r * half;
-        const int i1 = 2 * j * (i / j) + (i % j), i2 = i1 + j;
-        double *a = lds + (size_t)r * K;
-        const double x = a[i1], y = a[i2];
-        const bool up = (i1 & k) == 0;
-        if ((x > y) == up) { a[i1] = y; a[i2] = x; }
-      }
-      __syncthreads();
-    }
-  }
 }
 
 #ifdef ST_DEFS_MISC
@@ -358,14 +338,10 @@ __global__ __launch_bounds__(NT) void k_qtile(QtArgs A) {
   extern __shared__ double lds[];
   const int tid = threadIdx.x, R = A.R, K = A.Kpad;
   const long long row0 = (long long)blockIdx.x * R;
-  for (int idx = tid; idx < R * K; idx += NT) {
-    const int d = idx / R, r = idx - d * R;   // R consecutive rows of one draw: contiguous in memory
-    double v = __builtin_inf();
-    if (d < A.keep && row0 + r < A.n) v = A.draws[(size_t)d * A.n + row0 + r];
-    lds[(size_t)r * K + d] = v;
-  }
+  const int nr = (int)(A.n - row0 < R ? A.n - row0 : R);
+  tile_stage(lds, R, K, K, A.keep, nr, tid, NT, [&](int d, int r) { return A.draws[(size_t)d * A.n + row0 + r]; });
   __syncthreads();
-  qt_sort_rows(lds, R, K, tid);
+  tile_sort_rows(lds, R, K, tid, NT);
   if (tid < R && row0 + tid < A.n) {
     const double *a = lds + (size_t)tid * K;
     const int len = A.keep;

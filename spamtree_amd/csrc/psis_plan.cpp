@@ -1,5 +1,6 @@
 // psis_plan.hpp's functions: host only, no HIP.
 #include "psis_plan.hpp"
+#include "series_tile.hpp"
 
 #include <algorithm>
 
@@ -14,8 +15,7 @@ size_t psis_lds_bytes(int R, int Kpad) { return (size_t)R * ((size_t)Kpad + PSIS
 
 bool psis_plan(long long K, size_t lds_limit, int *R, int *Kpad) {
   if (K < 1 || K > PSIS_MAX_DRAWS) return false;
-  size_t kpad = 2;
-  while ((long long)kpad < K) kpad <<= 1;
+  const size_t kpad = (size_t)tile_pow2(K);
   const size_t lim = lds_limit > PSIS_LDS_STATIC ? lds_limit - PSIS_LDS_STATIC : 0;
   const size_t per = psis_lds_bytes(1, (int)kpad);
   size_t r = std::min<size_t>(lim, PSIS_TILE) / per;

@@ -187,6 +187,20 @@ __device__ __forceinline__ int anc_of(const int *s_ao, int J, int k) {
 // (a prefetched sub-panel keeps travelling across it) nor for global stores
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// LDS written by one lane of a wave and read by another: order the wave's own LDS traffic (no workgroup barrier: the data belongs
+// to one wave)
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// what a launcher returns after its launches: 0, or the HIP error as an int
+static inline int launch_rc() {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : (int)e;
+}
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);

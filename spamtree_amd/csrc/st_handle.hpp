@@ -12,6 +12,7 @@
 #pragma once
 #include "tree_layout.hpp"
 #include "st_protocol.hpp"
+#include "draw_store.hpp"
 
 // A device allocation that frees itself; a null buffer makes no HIP call.  (The owner has the device current when it goes.)
 template <typename T>
@@ -215,6 +216,33 @@ struct ProfScope {
 
 // A launcher's failure (the HIP error it returns as an int) as the entry point's: "<what> launch: <HIP's text>"
 inline int launch_failed(st_handle_s *h, const std::string &what, int e) { h->err = what + " launch: " + hipGetErrorString((hipError_t)e); return ST_ERR_HIP; }
+
+// The one read-back of a store's per-series outputs (draw_store.hpp): rows x s.n values at the device address src, store order, into
+// the caller's dst through s.perm.  A part without dst, src or rows is skipped -- only what the caller asked for comes to the host.
+// The copies go on h->stream behind whatever the caller issued there, then one synchronise, then the scatters.
+template <typename T> struct StorePart { T *dst; const T *src; long long rows; };
+inline int store_read_back(st_handle_s *h, const DrawStore &s, const std::vector<StorePart<double>> &pd, const std::vector<StorePart<int32_t>> &pi) {
+  std::vector<std::vector<double>> td(pd.size());
+  std::vector<std::vector<int32_t>> ti(pi.size());
+  const auto issue = [&](const auto &parts, auto &tmp) {
+    for (size_t k = 0; k < parts.size(); ++k) {
+      if (!parts[k].dst || !parts[k].src || parts[k].rows == 0) continue;
+      tmp[k].resize((size_t)parts[k].rows * s.n);
+      HCHK(h, hipMemcpyAsync(tmp[k].data(), parts[k].src, tmp[k].size() * sizeof(tmp[k][0]), hipMemcpyDeviceToHost, h->stream));
+    }
+    return (int)ST_OK;
+  };
+  const auto land = [&](const auto &parts, const auto &tmp) {
+    for (size_t k = 0; k < parts.size(); ++k)
+      if (!tmp[k].empty()) scatter_rows(parts[k].dst, tmp[k].data(), parts[k].rows, s.n, s.perm);
+  };
+  if (const int rc = issue(pd, td)) return rc;
+  if (const int rc = issue(pi, ti)) return rc;
+  HCHK(h, hipStreamSynchronize(h->stream));
+  land(pd, td);
+  land(pi, ti);
+  return ST_OK;
+}
 
 template <typename T>
 inline hipError_t upload_or_dummy(DevBuf<T> &d, const std::vector<T> &v) {   // an empty list still gets one (zero) element to point at

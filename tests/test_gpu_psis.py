@@ -80,6 +80,23 @@ def test_case_list_against_the_restatement(hm):
     assert worst <= bound, (worst, where)
 
 
+def test_the_shortest_stores_against_the_restatement(hm):
+    """K = 1 (the fewest draws st_psis takes: one value beside one padding column), 2, 3 and 5, n = 5 series where a tile takes
+    eight: no tail is long enough to smooth, so these are the stage, the sort and the raw estimator alone.  The restatement and the
+    bound of the case list."""
+    bound = pr.DEVICE_FACTOR * pr.F64_DISTANCE
+    kinds = ("gauss", "sprinkled", "skipped", "ties", "gpd0.5")
+    for K in (1, 2, 3, 5):
+        cols = [pr.make_series(kind, K, 40 + i) for i, kind in enumerate(kinds)]
+        t, phi, mu = (np.ascontiguousarray(np.stack([c[k] for c in cols], axis=1)) for k in range(3))
+        got = hm.psis(t, phi, mu)
+        for i in range(len(kinds)):
+            ref = pr.series(t[:, i], phi[:, i], mu[:, i])
+            g = {k: got[k][i] for k in ALL}
+            assert g["tail_len"] == 0 and g["n_draws"] == ref["n_draws"], (K, i, g)
+            assert pr.distance(ref, g) <= bound, (K, i, g)
+
+
 def test_companions_are_optional(hm):
     name, t, phi, mu = next(c for c in pr.case_list() if c[0] == "K100_n9")
     full = hm.psis(t, phi, mu)

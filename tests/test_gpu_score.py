@@ -248,6 +248,30 @@ def test_crps():
     hm.close()
 
 
+def test_crps_of_fewer_points_than_a_workgroup_takes():
+    """n = 5 points where a workgroup takes R = 8: the tile's last three rows are padding only.  K = 1, 3 and 4 stored draws (a
+    padding column, one, none), y below, above and among the draws and one NaN; the reference and the bound of test_crps."""
+    pb = problem(1)
+    n = 5
+    pts, mv, anchor, X = plain_points(pb, n, 47)
+    hm = model(pb)
+    hm.set_points(pts, mv, anchor, X)
+    set_state(hm, pb, 0, np.random.default_rng(2), tausq=0.3)
+    y = np.array([-1e3, 1e3, 0.0, 0.5, np.nan])
+    hm.set_scores(y)
+    hm._check(hm.lib.st_points_summary_reserve(hm.h, 4))
+    draws = np.zeros((4, n))
+    for k in range(4):
+        draws[k] = hm.accumulate_points(seed=11, it=k)["yhat"]
+        if k + 1 in (1, 3, 4):
+            got = hm.scores()["crps"]
+            assert np.isnan(got[4])
+            for i in range(4):
+                want, mad = sr.crps_sorted(draws[:k + 1, i], y[i])
+                assert abs(Fraction(float(got[i])) - want) <= sr.crps_bound(k + 1, mad), (k + 1, i)
+    hm.close()
+
+
 def test_crps_of_a_point_does_not_depend_on_the_other_points():
     """The same stored draws in sets of different size and order: k_score_crps gives the same bits.  The draws of a point follow its
     index in the caller's order (the Philox counter), so the sets are built to keep each compared point at the same index."""
