@@ -57,6 +57,9 @@ int stm_points_set_joint(stm_chain c, int64_t n_new, const double *coords, const
 int stm_points_functionals_set(stm_chain c, int64_t n_fun, const int64_t *ptr, const int64_t *idx, const double *wt);
 int stm_points_score_set(stm_chain c, const double *y_new);
 int stm_rows_score_set(stm_chain c, const double *y_holdout);
+/* st_points_mixture_reserve on the chain's handle: room for the per-draw moments of the first `keep` saved draws (at most
+ * ST_MIX_MAX_DRAWS, else ST_ERR_UNSUPPORTED; 0 releases it).  After the point set, its functionals and scores. */
+int stm_points_mixture_reserve(stm_chain c, int64_t keep);
 
 /* ---- The whole fit: one request, stm_mcmc_fit ------------------------------------------------------------------------------------
  * A request is the run (the chain of spamtree_mv_mcmc) and up to nine optional parts, each a pointer that is NULL when the part is
@@ -287,6 +290,28 @@ typedef struct stm_fit {
   const stm_loo *loo;
 } stm_fit;
 int stm_mcmc_fit(const stm_fit *fit);
+
+/* Parts added after the request's layout was pinned travel beside it: stm_fit_run(fit, more) is stm_mcmc_fit(fit) with the parts of
+ * `more`, and stm_fit_run(fit, NULL) is stm_mcmc_fit(fit) bit for bit (stm_mcmc_fit is that call).
+ * mix: quantiles and the exact CRPS of the mixture predictive at the new points (st_points_mixture_*, include/spamtree_hip.h).
+ * probs: n_probs probabilities strictly inside (0, 1), at most ST_MIX_MAX_PROBS; new_w and new_yhat take n_probs x n_new quantiles
+ * (probability-major, caller order), fun_w n_probs x n_fun; crps and spread n_new each, NaN where the scores' y_new is; n_stored the
+ * components the store held.  Any output may be NULL; probs are read only when a quantile output (or n_probs != 0) is there.
+ * Refused before a chain exists, in this order, after every refusal of the request itself: ST_ERR_USAGE for mix without a point
+ * set, a new_yhat output or crps / spread without X_new, crps / spread without scores or with every y_new NaN, fun_w without fun, and what
+ * st_points_mixture_quantiles refuses of the probabilities; ST_ERR_UNSUPPORTED for chains x mcmc_keep beyond ST_MIX_MAX_DRAWS.  The
+ * store is reserved once for chains x mcmc_keep draws, after the point set, the functionals, the scores and rb's thresholds, and read
+ * out after the last chain, behind rb: with several chains it runs across them, pooled like the point summaries.  The chain and
+ * every other output are draw for draw the same with and without mix. */
+typedef struct stm_mixture {
+  const double *probs;
+  int32_t n_probs;
+  st_mix_out new_w, new_yhat, fun_w;
+  double *crps, *spread;
+  int64_t *n_stored;
+} stm_mixture;
+typedef struct stm_fit_more { const stm_mixture *mix; } stm_fit_more;
+int stm_fit_run(const stm_fit *fit, const stm_fit_more *more);
 /* The text, with the numbers, of what the calling thread's last stm_mcmc_fit refused of its chains or of parts of both families,
  * before a chain existed to carry it; "" otherwise.  Every stm_mcmc_fit clears it first, and so does every entry point below,
  * stm_mcmc_criteria and stm_mcmc_loo included. */

@@ -630,6 +630,48 @@ typedef struct st_rb_out { double *prob, *prob_var; } st_rb_out;   /* n_thr x n,
 int st_points_exceed_set(st_handle h, int32_t n_thr, const double *thr, const int32_t *side, const double *thr_fun);
 int st_points_exceed_get(st_handle h, const st_rb_out *w, const st_rb_out *yhat, const st_rb_out *fun_w, int64_t *n_accumulated);
 
+/* ---- quantiles and the exact CRPS of the mixture predictive at the new points.  Every saved draw s gives a point the exact
+ * conditional law of the targets above: w* ~ N(m_s, v_s) and, with X, yhat* ~ N(mu_s, sigma2_s), sigma2_s = v_s + 1 / tausq_inv_j; a
+ * functional's w ~ N(F_m, F_v).  The predictive is the equal-weight mixture of the K stored components (spamtree_amd/csrc/
+ * points_mixture.hpp has every operation's order and the rounding bounds, spamtree_amd.mixture the definition in float64):
+ *   CDF       F(x) = (1 / K) sum_s Phi((x - m_s) / sd_s); a component with v_s == 0 is the right-continuous step 1(x >= m_s).
+ *   quantile  inf{x : F(x) >= p}, p strictly inside (0, 1): a safeguarded Newton iteration inside the bracket
+ *             [min_s, max_s] of m_s + z_p sd_s, stopped at the width 2^-50 max(|bracket ends|).
+ *   CRPS at y A(d, s2) = d erf(d / (s sqrt 2)) + s sqrt(2 / pi) exp(-d^2 / (2 s2)), A(d, 0) = |d|;
+ *             crps = (1 / K) sum_s A(y - mu_s, sigma2_s) - spread,  spread = (1 / (2 K^2)) sum_s sum_t A(mu_s - mu_t, sigma2_s + sigma2_t)
+ *             (Grimit et al. 2006): O(K^2) per scored point.  spread does not depend on y.
+ * st_points_mixture_reserve: room for the first `keep` saved draws' moments: m, v and with X mu per point (24 B per point and draw,
+ *   16 B without X), tau2 per outcome, F_m and F_v per functional.  keep > ST_MIX_MAX_DRAWS: ST_ERR_UNSUPPORTED (one series' pairs of
+ *   doubles must fit one workgroup's LDS).  keep = 0 releases the store.  Replaces a previous store.  st_points_set(_joint) drops
+ *   the store, st_points_summary_reset clears its count, st_points_functionals_set drops (and, when functionals are given,
+ *   re-reserves empty) the functional part only.
+ * With a store, st_points_accumulate(_joint) also writes one column after its exceedance step, on the same stream, while fewer
+ *   than `keep` are stored: it consumes no draw of any stream and writes nothing another step reads, so every other output is the
+ *   same bit for bit; with NULL outputs it still copies nothing and synchronises nothing.  Without a store nothing is launched
+ *   or allocated.
+ * st_points_mixture_draws: the stored columns in caller order, n_stored x n_new each (m, v, mu) and n_stored x q (tau2); any may be
+ *   NULL; n_stored is written first.  ST_ERR_USAGE: no store reserved, mu on a set without X.
+ * st_points_mixture_quantiles: 1 <= n_probs <= ST_MIX_MAX_PROBS probabilities strictly inside (0, 1) in any order, otherwise
+ *   ST_ERR_USAGE naming the index.  q is n_probs x n (n_new, or n_fun for fun_w), probability-major, caller order; n_unconverged
+ *   counts the series that hit the cap on passes (0 in every case known).  Any struct and either member may be NULL.  The
+ *   quantiles of a series never decrease in p.  ST_ERR_USAGE: no stored draw, yhat on a set without X, fun_w without functionals.
+ * st_points_mixture_crps: crps and spread at every scored point (n_new each, NaN where y_new of st_points_score_set is; either may
+ *   be NULL), from the stored mu, v and tau2; needs nothing of st_points_summary_reserve.  Unscored points cost nothing.
+ *   ST_ERR_USAGE: before st_points_score_set, no scored point, no stored draw.
+ * An empty point set returns ST_OK with nothing written.  All four refuse limited_tree and world > 1 handles (ST_ERR_UNSUPPORTED). */
+#define ST_MIX_MAX_DRAWS 8192
+#define ST_MIX_MAX_PROBS 8
+typedef struct st_mix_out { double *q; int64_t *n_unconverged; } st_mix_out;       /* q: n_probs x n, probability-major */
+int st_points_mixture_reserve(st_handle h, int64_t keep);
+int st_points_mixture_draws(st_handle h, double *m, double *v, double *mu, double *tau2, int64_t *n_stored);
+int st_points_mixture_quantiles(st_handle h, int32_t n_probs, const double *probs,
+                                const st_mix_out *w, const st_mix_out *yhat, const st_mix_out *fun_w);
+int st_points_mixture_crps(st_handle h, double *crps, double *spread, int64_t *n_scored);   /* n_new each; NaN where y_new is */
+/* The store's room (keep), the components it holds, its bytes on the device, and of the last st_points_mixture_quantiles the
+ * quantiles solved (series x probabilities over the targets asked for) and the evaluations of F they took together: the passes per
+ * quantile are n_passes / n_solved.  Zeros without a store; any pointer may be NULL. */
+int st_points_mixture_info(st_handle h, int64_t *keep, int64_t *n_stored, double *store_bytes, int64_t *n_solved, int64_t *n_passes);
+
 /* ---- criteria over the fit's own rows, on the device: WAIC and DIC over the observed rows, and the scores of held-out values at
  * NA rows of the problem (the reference's hold-out workflow: set part of y to NA, fit, compare yhat there with the truth).  All of
  * it is CONDITIONAL ON w: saved draw s gives row i of margin j the Gaussian N(mu_s, tau2_j), mu_s = XB_i + w_i, tau2_j = 1 / tausq_inv_j,

@@ -56,6 +56,10 @@ class StRbOut(C.Structure):           # st_rb_out: n_thr x n, threshold-major; e
     _fields_ = [("prob", C.POINTER(C.c_double)), ("prob_var", C.POINTER(C.c_double))]
 
 
+class StMixOut(C.Structure):          # st_mix_out: q n_probs x n, probability-major; either may be NULL
+    _fields_ = [("q", C.POINTER(C.c_double)), ("n_unconverged", C.POINTER(C.c_int64))]
+
+
 class StPsisOut(C.Structure):         # st_psis_out: n values each, any pointer may be NULL
     _fields_ = [("khat", C.POINTER(C.c_double)), ("elpd_psis", C.POINTER(C.c_double)), ("pit_psis", C.POINTER(C.c_double)),
                 ("mu_psis", C.POINTER(C.c_double)), ("weight_ess_psis", C.POINTER(C.c_double)), ("tail_len", C.POINTER(C.c_int32)),
@@ -65,6 +69,8 @@ class StPsisOut(C.Structure):         # st_psis_out: n values each, any pointer 
 ST_PSIS_MAX_DRAWS = 16384
 ST_EXC_MAX_THRESHOLDS = 8
 ST_RANK_MAX_PROBS = 8
+ST_MIX_MAX_DRAWS = 8192
+ST_MIX_MAX_PROBS = 8
 ST_DIAG_MIN_DRAWS = 4
 ST_DIAG_DEFAULT_MAX_LAG = 1024
 
@@ -74,6 +80,7 @@ c_sdp = C.POINTER(StSeriesDiag)
 c_xsp, c_xop = C.POINTER(StExcursionSpec), C.POINTER(StExcursionOut)
 c_rsp, c_rop = C.POINTER(StRankSpec), C.POINTER(StRankOut)
 c_rbp = C.POINTER(StRbOut)
+c_mxp = C.POINTER(StMixOut)
 SIGNATURES = {
     "st_create": (C.c_int, [C.POINTER(StProblem), C.POINTER(StOptions), C.POINTER(H)]),
     "st_destroy": (C.c_int, [H]),
@@ -182,6 +189,11 @@ SIGNATURES = {
     "st_points_score_get": (C.c_int, [H, c_dp, c_dp, c_dp, c_dp, c_ip, c_ip]),
     "st_points_exceed_set": (C.c_int, [H, C.c_int32, c_dp, C.POINTER(C.c_int32), c_dp]),
     "st_points_exceed_get": (C.c_int, [H, c_rbp, c_rbp, c_rbp, c_ip]),
+    "st_points_mixture_reserve": (C.c_int, [H, C.c_int64]),
+    "st_points_mixture_draws": (C.c_int, [H, c_dp, c_dp, c_dp, c_dp, c_ip]),
+    "st_points_mixture_quantiles": (C.c_int, [H, C.c_int32, c_dp, c_mxp, c_mxp, c_mxp]),
+    "st_points_mixture_crps": (C.c_int, [H, c_dp, c_dp, c_ip]),
+    "st_points_mixture_info": (C.c_int, [H, c_ip, c_ip, c_dp, c_ip, c_ip]),
     "st_rows_score_set": (C.c_int, [H, c_dp]),
     "st_rows_score_clear": (C.c_int, [H]),
     "st_rows_score_accumulate": (C.c_int, [H]),
@@ -312,6 +324,15 @@ class StmFit(C.Structure):                # include/spamtree_fit.h, stm_fit: the
                 ("ch", C.POINTER(StmChains)), ("criteria", C.POINTER(StmCriteria)), ("loo", C.POINTER(StmLoo))]
 
 
+class StmMixture(C.Structure):            # include/spamtree_fit.h, stm_mixture
+    _fields_ = [("probs", c_dp), ("n_probs", C.c_int32), ("new_w", StMixOut), ("new_yhat", StMixOut), ("fun_w", StMixOut),
+                ("crps", c_dp), ("spread", c_dp), ("n_stored", c_ip)]
+
+
+class StmFitMore(C.Structure):            # include/spamtree_fit.h, stm_fit_more: the parts that travel beside the request
+    _fields_ = [("mix", C.POINTER(StmMixture))]
+
+
 # include/spamtree_fit.h (C++ host driver).  The positional whole-fit entry points take the fields of the request in its order: the
 # run's, then (the points family) the point set's and one pointer per further part.  JOINT_ONLY: what stm_mcmc_points leaves out.
 JOINT_ONLY = ("joint_id_new", "new_cond_cov", "new_cov")
@@ -332,7 +353,9 @@ SIGNATURES.update({
     "stm_points_functionals_set": (C.c_int, [H, C.c_int64, c_ip, c_ip, c_dp]),
     "stm_points_score_set": (C.c_int, [H, c_dp]),
     "stm_rows_score_set": (C.c_int, [H, c_dp]),
+    "stm_points_mixture_reserve": (C.c_int, [H, C.c_int64]),
     "stm_mcmc_fit": (C.c_int, [C.POINTER(StmFit)]),
+    "stm_fit_run": (C.c_int, [C.POINTER(StmFit), C.POINTER(StmFitMore)]),
     "stm_mcmc_chains_last_error": (C.c_char_p, []),
     "spamtree_mv_mcmc_c": (C.c_int, _run),
     "stm_mcmc_points": (C.c_int, _run + [t for name, t in StmNewPoints._fields_ if name not in JOINT_ONLY]),

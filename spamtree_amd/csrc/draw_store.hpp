@@ -55,11 +55,15 @@ inline bool any_out(const st_rank_out *o) {
   return o && (o->rhat_rank || o->rhat_bulk || o->rhat_fold || o->ess_bulk || o->ess_tail || o->lags_bulk || o->ess_q || rank_exc_out(o));
 }
 inline bool any_out(const st_rb_out *o) { return o && (o->prob || o->prob_var); }
+inline bool any_out(const st_mix_out *o) { return o && (o->q || o->n_unconverged); }
 
 // ---- store_spec.cpp
 // The one copy of each spec's checks, for the st_* calls on a handle and for the whole fit's plan (fit_plan.cpp) before a chain
 // exists: an excursion and a rank spec with their outputs, K draws stored and n_thr_values thresholds per t, and the thresholds of
 // st_points_exceed_set (thr n_thr x q, not NULL; thr_fun n_thr x n_fun or NULL; n_fun < 0: no functionals are set)
+// the probabilities of st_points_mixture_quantiles and of the whole fit's mix: n_probs in 1 .. ST_MIX_MAX_PROBS, each strictly inside
+// (0, 1) (a NaN is not); the text names the index
+int check_mixture_probs(const std::string &W, int n_probs, const double *probs, std::string &msg);
 int check_excursion_spec(const std::string &W, const st_excursion_spec *spec, long long K, long long n_thr_values, const st_excursion_out *w,
                          const st_excursion_out *yhat, std::string &msg);
 int check_rank_spec(const std::string &W, const st_rank_spec *spec, long long K, long long n_thr_values, const st_rank_out *w,

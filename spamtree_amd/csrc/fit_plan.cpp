@@ -22,7 +22,7 @@ static const char *wanted_of(const Part *t, bool have_pts, const stm_functionals
   return nullptr;
 }
 
-int fit_plan(const stm_fit &fit, FitPlan &pl, std::string &text, std::string &which) {
+int fit_plan(const stm_fit &fit, FitPlan &pl, std::string &text, std::string &which, const stm_fit_more *more) {
   text.clear(); which.clear();
   const auto refuse = [&](int code, const std::string &part, const std::string &what) { which = part + ": " + what; return code; };
   const auto no = [&](const char *part, const std::string &what) { return refuse(ST_ERR_USAGE, part, what); };
@@ -127,5 +127,23 @@ int fit_plan(const stm_fit &fit, FitPlan &pl, std::string &text, std::string &wh
   if (f.loo && f.loo->psis && (mcmc_keep < 1 || mcmc_keep > ST_PSIS_MAX_DRAWS))   // st_rows_loo_reserve's limits
     return aloud(ST_ERR_UNSUPPORTED, "loo.psis", "stm_mcmc_fit: psis keeps every saved draw, mcmc_keep = " + std::to_string(mcmc_keep) + " must lie in 1 .. " +
                                                      std::to_string(ST_PSIS_MAX_DRAWS));
+  // more's mix: the parts it needs, what st_points_mixture_quantiles would refuse of the probabilities, the store's limit
+  if (const stm_mixture *const mix = pl.mix = more ? more->mix : nullptr) {
+    pl.mix_q = any_out(&mix->new_w) || any_out(&mix->new_yhat) || any_out(&mix->fun_w);
+    pl.mix_crps = mix->crps || mix->spread;
+    if (!have_pts) return no("mix", "no point set");
+    if ((any_out(&mix->new_yhat) || pl.mix_crps) && !p.X_new) return no("mix", "new_yhat, crps or spread without X_new");
+    if (pl.mix_crps && !scores) return no("mix", "crps or spread without scores");
+    if (pl.mix_crps && p.n_new > 0) {   // what st_points_mixture_crps would refuse after the last chain: the host knows it now
+      bool any = false;
+      for (int64_t i = 0; i < p.n_new && !any; ++i) any = scores->y_new[i] == scores->y_new[i];
+      if (!any) return no("mix", "crps or spread with no scored point (every y_new is NaN)");
+    }
+    if (any_out(&mix->fun_w) && !fun) return no("mix", "fun_w without fun");
+    if ((pl.mix_q || mix->n_probs != 0) && (rc = check_mixture_probs("mix: ", mix->n_probs, mix->probs, which)) != 0) return rc;
+    if (total > ST_MIX_MAX_DRAWS)
+      return aloud(ST_ERR_UNSUPPORTED, "mix", "stm_fit_run: " + std::to_string(M) + " chains x mcmc_keep = " + std::to_string(mcmc_keep) + " are " +
+                                                  std::to_string(total) + " stored components, at most " + std::to_string(ST_MIX_MAX_DRAWS));
+  }
   return ST_OK;
 }

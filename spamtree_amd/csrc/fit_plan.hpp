@@ -17,6 +17,8 @@ struct FitPlan {
   long long total = 0;       // the stored draws, M mcmc_keep: the columns of every per-draw output
   Wanted d, e, k;            // what diag, exc and rk read
   const stm_rb_exceed *rb = nullptr;   // exc's rb; NULL without thresholds
+  const stm_mixture *mix = nullptr;    // stm_fit_more's mix
+  bool mix_q = false, mix_crps = false;   // ... asks for a quantile output; for crps or spread
   bool crps = false;         // the criteria's CRPS: want_crps with a y_holdout
   bool store_rows = false;   // diag, exc or rk read the rows' stores: st_summary_accumulate on every saved iteration
   int64_t cov_len = 0;       // the packed length of st_points_joint_layout (the setup step's: it needs the device)
@@ -26,4 +28,5 @@ struct FitPlan {
 // Fills a fresh pl.  The refusals come in the order of include/spamtree_fit.h's step 1 and the first failing check decides the
 // code.  text: what stm_mcmc_chains_last_error() reports, "" for most refusals; which: the failing check of every refusal, a
 // checker's own message after the part it came from ("exc.rows_spec: threshold 3 is not finite").
-int fit_plan(const stm_fit &fit, FitPlan &pl, std::string &text, std::string &which);
+// more: the parts of stm_fit_run beside the request (NULL: none); their refusals come after all of the request's.
+int fit_plan(const stm_fit &fit, FitPlan &pl, std::string &text, std::string &which, const stm_fit_more *more = nullptr);

@@ -453,6 +453,13 @@ extern "C" int stm_points_score_set(stm_chain c, const double *y_new) {
   return ST_OK;
 }
 
+extern "C" int stm_points_mixture_reserve(stm_chain c, int64_t keep) {
+  if (!c || !c->h) return ST_ERR_USAGE;
+  const int rc = st_points_mixture_reserve(c->h, keep);
+  if (rc != 0) { c->err = st_last_error(c->h); return rc; }
+  return ST_OK;
+}
+
 extern "C" int stm_rows_score_set(stm_chain c, const double *y_holdout) {
   if (!c || !c->h) return ST_ERR_USAGE;
   const int rc = st_rows_score_set(c->h, y_holdout);
@@ -574,6 +581,7 @@ static int fit_setup(FitPlan &pl, JointBlocks &jb, stm_chain *out) {
   if (rc == 0 && fun) rc = stm_points_functionals_set(c, fun->n_fun, fun->ptr, fun->idx, fun->wt);
   if (rc == 0 && f.scores) rc = stm_points_score_set(c, f.scores->y_new);
   if (rc == 0 && pl.rb && (rc = st_points_exceed_set(c->h, pl.rb->n_thr, pl.rb->thr, pl.rb->side, pl.rb->thr_fun)) != 0) c->err = st_last_error(c->h);
+  if (rc == 0 && pl.mix) rc = stm_points_mixture_reserve(c, pl.total);
   if (rc == 0 && p.joint_id_new) {
     rc = st_points_joint_layout(c->h, &jb.nj, nullptr, nullptr, nullptr);
     jb.off.resize(jb.nj + 1); jb.ptr.resize(jb.nj + 1); jb.mem.resize(p.n_new);
@@ -636,6 +644,11 @@ static int fit_read_out(stm_chain c, const FitPlan &pl, const JointBlocks &jb) {
   // a yhat (rb: fun_w too) struct that asks for nothing goes as NULL: its store need not exist
   const auto opt = [](const auto &o) { return any_out(&o) ? &o : nullptr; };
   if (rc == 0 && rb && saved) rc = st_points_exceed_get(c->h, &rb->new_w, opt(rb->new_yhat), opt(rb->fun_w), rb->n_accumulated);
+  if (const stm_mixture *const mix = pl.mix; mix && saved) {
+    if (rc == 0 && pl.mix_q) rc = st_points_mixture_quantiles(c->h, mix->n_probs, mix->probs, opt(mix->new_w), opt(mix->new_yhat), opt(mix->fun_w));
+    if (rc == 0 && pl.mix_crps) rc = st_points_mixture_crps(c->h, mix->crps, mix->spread, nullptr);
+    if (rc == 0 && mix->n_stored) rc = st_points_mixture_draws(c->h, nullptr, nullptr, nullptr, nullptr, mix->n_stored);
+  }
   if (rc == 0 && d.rows) rc = st_summary_chain_diagnostics(c->h, M, diag->max_lag, &diag->rows_w, &diag->rows_yhat);
   if (rc == 0 && d.pts) rc = st_points_summary_chain_diagnostics(c->h, M, diag->max_lag, &diag->new_w, opt(diag->new_yhat));
   if (rc == 0 && d.fun) rc = st_points_functionals_chain_diagnostics(c->h, M, diag->max_lag, &diag->fun_w, opt(diag->fun_yhat));
@@ -671,14 +684,16 @@ static int fit_read_out(stm_chain c, const FitPlan &pl, const JointBlocks &jb) {
 }
 
 // The request in four steps: the plan (fit_plan.cpp: every refusal that needs no device), the setup, chain after chain, the read-outs
-extern "C" int stm_mcmc_fit(const stm_fit *fit) {
+extern "C" int stm_mcmc_fit(const stm_fit *fit) { return stm_fit_run(fit, nullptr); }
+
+extern "C" int stm_fit_run(const stm_fit *fit, const stm_fit_more *more) {
   g_chains_error.clear();
   if (!fit) return ST_ERR_USAGE;
   FitPlan pl;
   JointBlocks jb;
   stm_chain c = nullptr;
   std::string which;   // the failing check of every refusal: the plan's own tests read it, no caller does
-  int rc = fit_plan(*fit, pl, g_chains_error, which);
+  int rc = fit_plan(*fit, pl, g_chains_error, which, more);
   if (rc == 0) rc = fit_setup(pl, jb, &c);
   if (rc != 0) return rc;
   const stm_run &r = pl.f.run;

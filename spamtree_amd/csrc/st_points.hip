@@ -14,6 +14,8 @@
 #include "points_layout.hpp"
 #include "points_score.hpp"
 #include "points_exceed.hpp"
+#include "points_mixture.hpp"
+#include "norm_quantile.hpp"
 
 // The functionals of a point set (st_points_functionals_set): the term lists and chunks on the device, their accumulators, the
 // values of the last iteration and, with a reservation, the draws F_w and F_y, [keep][n_fun] each
@@ -48,6 +50,17 @@ struct ExceedSet {
   DevBuf<double> d_thr, d_acc, d_thr_fun, d_facc;
 };
 
+// The store of per-draw moments behind the mixture quantiles and the exact CRPS (st_points_mixture_reserve): [keep][n] columns of
+// m, v and, with X, mu; tau2 [keep][q]; the functionals' F_m and F_v [keep][n_fun] with a count of their own (functionals set
+// later start empty); the outputs' room on the device
+struct MixSet {
+  long long keep = 0, n_kept = 0, fn_kept = 0, n_fun = 0;
+  long long passes = 0, solved = 0;   // of the last st_points_mixture_quantiles: evaluations of F, and series x probabilities
+  DevBuf<double> d_m, d_v, d_mu, d_tau2, d_fm, d_fv, d_q, d_crps;
+  DevBuf<long long> d_idx;
+  DevBuf<unsigned long long> d_cnt;
+};
+
 struct PointSet : PointsCounts {
   long long n = 0;
   bool has_X = false;
@@ -73,6 +86,7 @@ struct PointSet : PointsCounts {
   std::unique_ptr<FunSet> fun;                 // st_points_functionals_set; leaves with the point set
   std::unique_ptr<ScoreSet> score;             // st_points_score_set; leaves with the point set
   std::unique_ptr<ExceedSet> exceed;           // st_points_exceed_set; leaves with the point set
+  std::unique_ptr<MixSet> mix;                 // st_points_mixture_reserve; leaves with the point set
 };
 
 void points_free(st_handle_s *h) {
@@ -390,6 +404,39 @@ static int exceed_step(st_handle h, PointSet *ps) {
   return ST_OK;
 }
 
+// ---- the mixture store's share of reserve and accumulate (the entry points follow the exceedance probabilities) ----
+// room for the functional columns of the store (none without functionals)
+static int mix_reserve_fun(st_handle h, const PointSet *ps, MixSet *mx) {
+  mx->d_fm.free(); mx->d_fv.free();
+  mx->fn_kept = 0;
+  mx->n_fun = (ps->fun && ps->n > 0) ? ps->fun->n_fun : 0;
+  if (mx->n_fun == 0) return ST_OK;
+  HCHK(h, mx->d_fm.alloc((size_t)mx->keep * mx->n_fun)); HCHK(h, mx->d_fv.alloc((size_t)mx->keep * mx->n_fun));
+  return ST_OK;
+}
+
+// the store's step of one saved iteration: after exceed_step, on the same stream, from d_out, d_X, d_B, d_tsq and the functionals'
+// d_last.  A full store and an empty set launch nothing.
+static int mix_step(st_handle h, PointSet *ps) {
+  MixSet *mx = ps->mix.get();
+  const long long n = ps->n, c = mx->n_kept;
+  if (c >= mx->keep) return ST_OK;
+  mx->n_kept += 1;
+  if (n == 0) return ST_OK;
+  const double *o = ps->d_out.p;
+  const bool fun = mx->n_fun > 0 && ps->fun && mx->fn_kept < mx->keep;
+  MixStoreArgs A;
+  A.mean = o + n; A.var = o + 2 * n; A.X = ps->has_X ? ps->d_X.p : nullptr; A.B = h->d_B.p; A.tsq_inv = h->d_tsq.p; A.pmv = ps->d_pmv.p;
+  A.last = fun ? ps->fun->d_last.p : nullptr; A.p = h->p; A.q = h->q; A.n = n; A.n_fun = fun ? mx->n_fun : 0;
+  A.m = mx->d_m.p + (size_t)c * n; A.v = mx->d_v.p + (size_t)c * n; A.mu = ps->has_X ? mx->d_mu.p + (size_t)c * n : nullptr;
+  A.tau2 = mx->d_tau2.p + (size_t)c * h->q;
+  A.fm = fun ? mx->d_fm.p + (size_t)mx->fn_kept * mx->n_fun : nullptr; A.fv = fun ? mx->d_fv.p + (size_t)mx->fn_kept * mx->n_fun : nullptr;
+  ProfScope pscope(h, 6);
+  if (const int e = points_mix_store_launch(A, h->stream)) return launch_failed(h, "st_points_accumulate", e);
+  if (fun) mx->fn_kept += 1;
+  return ST_OK;
+}
+
 // ---- predictive summaries of the point set over saved iterations (st_points_accumulate; the kernel lives in k_points_acc.hip) ----
 extern "C" int st_points_summary_reset(st_handle h) {
   if (!h) return ST_ERR_USAGE;
@@ -407,6 +454,7 @@ extern "C" int st_points_summary_reset(st_handle h) {
     if (const int rc = score_reset(h, ps->score.get())) return rc;
   if (ps->exceed)
     if (const int rc = exceed_reset(h, ps->exceed.get())) return rc;
+  if (ps->mix) { ps->mix->n_kept = 0; ps->mix->fn_kept = 0; }
   if (ps->fun) return fun_reset(h, ps->fun.get());
   return ST_OK;
 }
@@ -445,6 +493,7 @@ static int points_accumulate(st_handle h, uint64_t seed, uint32_t iter, double *
     ps->n_acc += 1;
     if (ps->score) (void)score_step(h, ps);   // counts the iteration; an empty set launches nothing
     if (ps->exceed) (void)exceed_step(h, ps); // likewise
+    if (ps->mix) (void)mix_step(h, ps);       // likewise
     if (!ps->fun) return ST_OK;
     HCHK(h, hipSetDevice(h->device));
     return fun_step(h, ps);
@@ -483,6 +532,8 @@ static int points_accumulate(st_handle h, uint64_t seed, uint32_t iter, double *
     if (const int rcf = fun_step(h, ps)) return rcf;
   if (ps->exceed)
     if (const int rce = exceed_step(h, ps)) return rce;
+  if (ps->mix)
+    if (const int rcm = mix_step(h, ps)) return rcm;
   double *const dst[4] = {w_new, cond_mean, cond_var, yhat_new};
   return points_copy_out(h, ps, dst, cond_cov, cond_chol, false);
 }
@@ -601,7 +652,11 @@ extern "C" int st_points_functionals_set(st_handle h, int64_t n_fun, const int64
     ps->exceed->fun = false;
     ps->exceed->d_thr_fun.free(); ps->exceed->d_facc.free();
   }
-  if (n_fun == 0) { ps->fun.reset(); return ST_OK; }
+  if (n_fun == 0) {
+    ps->fun.reset();
+    if (ps->mix) return mix_reserve_fun(h, ps, ps->mix.get());
+    return ST_OK;
+  }
   std::unique_ptr<FunSet> fs(new FunSet());   // the point set takes it once every upload has succeeded
   fs->n_fun = L.n_fun; fs->nnz = L.nnz; fs->n_var_terms = L.n_var_terms;
   fs->n_lin_chunks = (long long)L.lin_chunks.size(); fs->n_var_chunks = (long long)L.var_chunks.size();
@@ -614,6 +669,7 @@ extern "C" int st_points_functionals_set(st_handle h, int64_t n_fun, const int64
   if (const int rc = fun_reset(h, fs.get())) return rc;
   if (const int rc = fun_reserve(h, ps, fs.get())) return rc;
   ps->fun = std::move(fs);
+  if (ps->mix) return mix_reserve_fun(h, ps, ps->mix.get());   // the store's functional columns belong to the functionals they were written for
   return ST_OK;
 }
 
@@ -840,5 +896,171 @@ extern "C" int st_points_exceed_get(st_handle h, const st_rb_out *w, const st_rb
   if (want_w) exceed_read_out(acc.data(), T, n, S, w);
   if (want_y) exceed_read_out(acc.data() + per, T, n, S, yhat);
   if (want_f) exceed_read_out(facc.data(), T, ps->fun->n_fun, S, fun_w);
+  return ST_OK;
+}
+
+// ---- quantiles and the exact CRPS of the mixture predictive at the point set (points_mixture.hpp)
+extern "C" int st_points_mixture_reserve(st_handle h, int64_t keep) {
+  if (!h || keep < 0) return ST_ERR_USAGE;
+  if (const int rc = points_refuse(h, "st_points_mixture_reserve")) return rc;
+  if (keep > ST_MIX_MAX_DRAWS) {
+    h->err = "st_points_mixture_reserve: keep = " + std::to_string(keep) + " beyond ST_MIX_MAX_DRAWS = " + std::to_string(ST_MIX_MAX_DRAWS) +
+             " (one series' components are staged in one workgroup's LDS)";
+    return ST_ERR_UNSUPPORTED;
+  }
+  PointSet *ps = h->pts;
+  HCHK(h, hipSetDevice(h->device));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  ps->mix.reset();
+  if (keep == 0) return ST_OK;
+  std::unique_ptr<MixSet> mx(new MixSet());   // the point set takes it once every allocation has succeeded
+  mx->keep = keep;
+  const size_t n = (size_t)ps->n;
+  if (n > 0) {
+    HCHK(h, mx->d_m.alloc((size_t)keep * n)); HCHK(h, mx->d_v.alloc((size_t)keep * n));
+    if (ps->has_X) HCHK(h, mx->d_mu.alloc((size_t)keep * n));
+    HCHK(h, mx->d_tau2.alloc((size_t)keep * h->q));
+    HCHK(h, mx->d_cnt.alloc(3));
+    if (const int rc = mix_reserve_fun(h, ps, mx.get())) return rc;
+  }
+  ps->mix = std::move(mx);
+  return ST_OK;
+}
+
+// what the store's outputs refuse first
+static int mix_refuse(st_handle h, const char *who) {
+  if (const int rc = points_refuse(h, who)) return rc;
+  if (!h->pts->mix) { h->err = std::string(who) + " before st_points_mixture_reserve"; return ST_ERR_USAGE; }
+  return ST_OK;
+}
+
+extern "C" int st_points_mixture_draws(st_handle h, double *m, double *v, double *mu, double *tau2, int64_t *n_stored) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = mix_refuse(h, "st_points_mixture_draws")) return rc;
+  PointSet *ps = h->pts;
+  MixSet *mx = ps->mix.get();
+  if (n_stored) *n_stored = mx->n_kept;
+  if (mu && !ps->has_X) { h->err = "st_points_mixture_draws: mu needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  if (ps->n == 0 || mx->n_kept == 0) return ST_OK;
+  HCHK(h, hipSetDevice(h->device));
+  const size_t cb = (size_t)mx->n_kept * ps->n * sizeof(double);
+  if (m) HCHK(h, hipMemcpyAsync(m, mx->d_m.p, cb, hipMemcpyDeviceToHost, h->stream));
+  if (v) HCHK(h, hipMemcpyAsync(v, mx->d_v.p, cb, hipMemcpyDeviceToHost, h->stream));
+  if (mu) HCHK(h, hipMemcpyAsync(mu, mx->d_mu.p, cb, hipMemcpyDeviceToHost, h->stream));
+  if (tau2) HCHK(h, hipMemcpyAsync(tau2, mx->d_tau2.p, (size_t)mx->n_kept * h->q * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  return ST_OK;
+}
+
+// one target's quantiles: the launch over its n series of K components, the copies and the wait
+static int mix_quantile_target(st_handle h, MixSet *mx, MixQuantileArgs &A, const st_mix_out *out) {
+  MixPlan P;
+  if (!mix_quantile_plan(A.K, A.n, h->lds_limit, &P)) {
+    h->err = "st_points_mixture_quantiles: " + std::to_string(A.K) + " components do not fit the device's LDS";
+    return ST_ERR_UNSUPPORTED;
+  }
+  const size_t cnt = (size_t)A.T * A.n;
+  if (mx->d_q.n < cnt) { mx->d_q.free(); HCHK(h, mx->d_q.alloc(cnt)); }
+  A.R = P.R; A.out = mx->d_q.p; A.counters = mx->d_cnt.p;
+  HCHK(h, hipMemsetAsync(mx->d_cnt.p, 0, 2 * sizeof(unsigned long long), h->stream));
+  if (const int e = points_mix_quantile_launch(A, P, h->lds_limit, h->stream)) return launch_failed(h, "st_points_mixture_quantiles", e);
+  unsigned long long unc[2] = {0, 0};
+  if (out->q) HCHK(h, hipMemcpyAsync(out->q, mx->d_q.p, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipMemcpyAsync(unc, mx->d_cnt.p, sizeof(unc), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  if (out->n_unconverged) *out->n_unconverged = (int64_t)unc[MIX_CNT_UNCONVERGED];
+  mx->passes += (long long)unc[MIX_CNT_PASSES]; mx->solved += (long long)cnt;
+  return ST_OK;
+}
+
+extern "C" int st_points_mixture_quantiles(st_handle h, int32_t n_probs, const double *probs, const st_mix_out *w, const st_mix_out *yhat,
+                                           const st_mix_out *fun_w) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = mix_refuse(h, "st_points_mixture_quantiles")) return rc;
+  PointSet *ps = h->pts;
+  MixSet *mx = ps->mix.get();
+  if (const int rc = check_mixture_probs("st_points_mixture_quantiles: ", n_probs, probs, h->err)) return rc;
+  if (yhat && !ps->has_X) { h->err = "st_points_mixture_quantiles: the yhat target needs the regressors X of st_points_set"; return ST_ERR_USAGE; }
+  if (fun_w && !ps->fun) { h->err = "st_points_mixture_quantiles: fun_w before st_points_functionals_set"; return ST_ERR_USAGE; }
+  if (mx->n_kept == 0 || (fun_w && ps->n > 0 && mx->fn_kept == 0)) { h->err = "st_points_mixture_quantiles: no stored draw"; return ST_ERR_USAGE; }
+  mx->passes = 0; mx->solved = 0;
+  if (ps->n == 0) return ST_OK;   // nothing to write: the functionals of an empty set have no term either
+  HCHK(h, hipSetDevice(h->device));
+  MixQuantileArgs A;
+  std::memset(&A, 0, sizeof(A));
+  A.T = n_probs; A.q = h->q;
+  std::vector<int> ord(n_probs);
+  for (int t = 0; t < n_probs; ++t) ord[t] = t;
+  std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return probs[a] < probs[b]; });
+  for (int t = 0; t < n_probs; ++t) { A.p[t] = probs[ord[t]]; A.z[t] = st_norm_quantile_f(A.p[t]); A.slot[t] = ord[t]; }
+  if (any_out(w)) {
+    A.m = mx->d_m.p; A.v = mx->d_v.p; A.tau2 = nullptr; A.pmv = nullptr; A.K = (int)mx->n_kept; A.n = ps->n;
+    if (const int rc = mix_quantile_target(h, mx, A, w)) return rc;
+  }
+  if (any_out(yhat)) {
+    A.m = mx->d_mu.p; A.v = mx->d_v.p; A.tau2 = mx->d_tau2.p; A.pmv = ps->d_pmv.p; A.K = (int)mx->n_kept; A.n = ps->n;
+    if (const int rc = mix_quantile_target(h, mx, A, yhat)) return rc;
+  }
+  if (any_out(fun_w)) {
+    A.m = mx->d_fm.p; A.v = mx->d_fv.p; A.tau2 = nullptr; A.pmv = nullptr; A.K = (int)mx->fn_kept; A.n = mx->n_fun;
+    if (const int rc = mix_quantile_target(h, mx, A, fun_w)) return rc;
+  }
+  return ST_OK;
+}
+
+extern "C" int st_points_mixture_info(st_handle h, int64_t *keep, int64_t *n_stored, double *store_bytes, int64_t *n_solved, int64_t *n_passes) {
+  if (!h) return ST_ERR_USAGE;
+  const PointSet *ps = h->pts;
+  const MixSet *mx = ps ? ps->mix.get() : nullptr;
+  if (keep) *keep = mx ? mx->keep : 0;
+  if (n_stored) *n_stored = mx ? mx->n_kept : 0;
+  if (store_bytes) *store_bytes = mx ? (double)mx->keep * mix_store_bytes(ps->n, ps->has_X, h->q, mx->n_fun) : 0.0;
+  if (n_solved) *n_solved = mx ? mx->solved : 0;
+  if (n_passes) *n_passes = mx ? mx->passes : 0;
+  return ST_OK;
+}
+
+extern "C" int st_points_mixture_crps(st_handle h, double *crps, double *spread, int64_t *n_scored) {
+  if (!h) return ST_ERR_USAGE;
+  if (const int rc = mix_refuse(h, "st_points_mixture_crps")) return rc;
+  PointSet *ps = h->pts;
+  MixSet *mx = ps->mix.get();
+  ScoreSet *sc = ps->score.get();
+  if (!sc) { h->err = "st_points_mixture_crps before st_points_score_set"; return ST_ERR_USAGE; }
+  if (n_scored) *n_scored = sc->n_scored;
+  if (ps->n == 0) return ST_OK;
+  if (sc->n_scored == 0) { h->err = "st_points_mixture_crps: no point is scored (every y_new is NaN)"; return ST_ERR_USAGE; }
+  if (mx->n_kept == 0) { h->err = "st_points_mixture_crps: no stored draw"; return ST_ERR_USAGE; }
+  if (!crps && !spread) return ST_OK;
+  HCHK(h, hipSetDevice(h->device));
+  const long long n = ps->n;
+  MixPlan P;
+  if (!mix_crps_plan(mx->n_kept, sc->n_scored, h->lds_limit, &P)) {
+    h->err = "st_points_mixture_crps: " + std::to_string(mx->n_kept) + " components do not fit the device's LDS";
+    return ST_ERR_UNSUPPORTED;
+  }
+  std::vector<long long> idx;
+  idx.reserve((size_t)sc->n_scored);
+  for (long long i = 0; i < n; ++i)
+    if (sc->pt_obs[i]) idx.push_back(i);
+  HCHK(h, hipStreamSynchronize(h->stream));   // a previous call's kernel may still read d_idx
+  HCHK(h, mx->d_idx.upload(idx));
+  if (!mx->d_crps.p) HCHK(h, mx->d_crps.alloc((size_t)2 * n));
+  MixCrpsArgs A;
+  A.mu = mx->d_mu.p; A.v = mx->d_v.p; A.tau2 = mx->d_tau2.p; A.y = sc->d_y.p; A.pmv = ps->d_pmv.p; A.idx = mx->d_idx.p;
+  A.n = n; A.n_scored = sc->n_scored; A.q = h->q; A.K = (int)mx->n_kept; A.R = P.R; A.G = P.G;
+  A.crps = mx->d_crps.p; A.spread = mx->d_crps.p + n;
+  {
+    ProfScope pscope(h, 6);
+    if (const int e = points_mix_crps_launch(A, P, h->lds_limit, h->stream)) return launch_failed(h, "st_points_mixture_crps", e);
+  }
+  std::vector<double> out((size_t)2 * n);
+  HCHK(h, hipMemcpyAsync(out.data(), mx->d_crps.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HCHK(h, hipStreamSynchronize(h->stream));
+  const double nan = std::nan("");
+  for (long long i = 0; i < n; ++i) {
+    if (crps) crps[i] = sc->pt_obs[i] ? out[i] : nan;
+    if (spread) spread[i] = sc->pt_obs[i] ? out[n + i] : nan;
+  }
   return ST_OK;
 }

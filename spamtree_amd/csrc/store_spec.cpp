@@ -115,3 +115,16 @@ static void scatter(T *dst, const T *src, long long rows, long long n, const lon
 void scatter_rows(double *dst, const double *src, long long rows, long long n, const long long *perm) { scatter(dst, src, rows, n, perm); }
 void scatter_rows(int32_t *dst, const int32_t *src, long long rows, long long n, const long long *perm) { scatter(dst, src, rows, n, perm); }
 void scatter_rows(int64_t *dst, const int64_t *src, long long rows, long long n, const long long *perm) { scatter(dst, src, rows, n, perm); }
+
+int check_mixture_probs(const std::string &W, int n_probs, const double *probs, std::string &msg) {
+  if (n_probs < 1 || n_probs > ST_MIX_MAX_PROBS || !probs) {
+    msg = W + "n_probs = " + std::to_string(n_probs) + " must lie in 1 .. " + std::to_string(ST_MIX_MAX_PROBS);
+    return ST_ERR_USAGE;
+  }
+  for (int t = 0; t < n_probs; ++t)
+    if (!(probs[t] > 0.0 && probs[t] < 1.0)) {   // NaN fails both comparisons
+      msg = W + "probs[" + std::to_string(t) + "] = " + std::to_string(probs[t]) + " is not strictly inside (0, 1)";
+      return ST_ERR_USAGE;
+    }
+  return ST_OK;
+}

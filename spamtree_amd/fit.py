@@ -12,6 +12,7 @@ import numpy as np
 from . import _lib
 from . import diagnostics as _diag
 from . import exceed as _rb
+from . import mixture as _mix
 from . import excursions as _exc
 from . import loo as _loo
 from .model import (SpamTreeError, _dp, _f64, _i64, _ip, _lists_to_csr, functionals_csr, joint_labels, rows_criteria, rows_holdout,
@@ -188,9 +189,9 @@ class PointsInputs(NamedTuple):
 def _points_inputs(new_points, p, q, new_quantiles):
     """Checks the point set of spamtree_mv_mcmc(new_points=...) against itself and the problem, before any device call."""
     pts = dict(new_points)
-    unknown = set(pts) - {"coords", "mv", "anchor", "X", "joint", "functionals", "y", "crps", "exceed"}
+    unknown = set(pts) - {"coords", "mv", "anchor", "X", "joint", "functionals", "y", "crps", "exceed", "mixture"}
     if unknown:
-        raise ValueError(f"new_points: unknown keys {sorted(unknown)} (coords, mv, anchor, X, joint, functionals, y, crps, exceed)")
+        raise ValueError(f"new_points: unknown keys {sorted(unknown)} (coords, mv, anchor, X, joint, functionals, y, crps, exceed, mixture)")
     coords = np.asarray(pts["coords"], dtype=np.float64)
     if coords.ndim != 2 or coords.shape[1] != 2:
         raise ValueError("new_points: coords must be n_new x 2")
@@ -247,6 +248,18 @@ def _exceed_inputs(new_points, pts, q):
         return None
     try:
         return _rb.check_spec(spec, q, None if pts.functionals is None else pts.functionals[0].size - 1)
+    except (ValueError, TypeError) as e:
+        raise ValueError(f"new_points: {e}") from None
+
+
+def _mixture_inputs(new_points, pts, keep_all):
+    """``new_points["mixture"]`` checked against the point set ``pts`` (_points_inputs') and the saved draws of all chains before any
+    device call: mixture.check_spec's (probs or None, crps), or None without the key."""
+    spec = dict(new_points).get("mixture")
+    if spec is None:
+        return None
+    try:
+        return _mix.check_spec(spec, pts.X is not None, pts.y is not None, keep_all, pts.y)
     except (ValueError, TypeError) as e:
         raise ValueError(f"new_points: {e}") from None
 
@@ -308,6 +321,11 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     then also holds ``exceed``: dict(thr, side, w=dict(prob, prob_var), yhat=the same or None, n_accumulated), T x n_new arrays
     (``prob_var``: the population variance of the per-draw probabilities, MCSE = sqrt(prob_var / ESS)), and with
     ``thresholds_fun`` (one value per functional) ``new["functionals"]["exceed"]`` for the functionals' w.
+    ``new_points["mixture"] = dict(probs=, crps=True)``: quantiles and the exact CRPS of the mixture predictive
+    (``spamtree_amd.mixture``): every saved draw's exact conditional law is one component, stored on the device (24 B per point and
+    draw; at most 8192 draws over all chains).  ``new`` then holds ``mixture``: dict(probs, w, yhat (None without X), n_stored,
+    n_unconverged), T x n_new arrays, and with functionals ``new["functionals"]["mixture"]``; with ``y`` and ``crps=True``
+    ``new["scores"]`` also holds ``crps_mixture`` and ``spread`` (O(K^2) per scored point) with their means in ``totals``.
     ``criteria=True``: WAIC and DIC over the observed rows, on the device (stm_mcmc_criteria; the chain is the same bit for bit, and
     nothing per draw comes to the host, so it works with ``save_w=False, save_yhat=False``).  ``y_holdout``: the truth at NA rows
     of ``y`` (one value per row, NaN = none; ``model.rows_holdout`` checks it), scored there on every saved iteration; it implies
@@ -412,7 +430,7 @@ def spamtree_mv_mcmc(y, X, Z, coords, mv_id, blocking, gix_block, res_is_ref, pa
     rows = _row_parts(req, rq, n, q, mcmc_keep)
     new_result = _point_parts(lib, req, rq, rows, q, mcmc_keep, new_draws) if rq.pts is not None else None
 
-    rc = lib.stm_mcmc_fit(C.byref(req))
+    rc = lib.stm_mcmc_fit(C.byref(req)) if rq.more is None else lib.stm_fit_run(C.byref(req), C.byref(rq.more))
     if rc == -10:
         raise FloatingPointError("At nan loglik: error.")
     if rc != 0:
@@ -590,11 +608,12 @@ def _check_request(y, X, mv_id, theta, limited_tree, mcmc_keep, sample_predicts,
         if want_crps and int(mcmc_keep) > MAX_STORED_DRAWS:
             raise ValueError(f"y_holdout: the CRPS keeps mcmc_keep = {int(mcmc_keep)} draws per row on the device, at most "
                              f"{MAX_STORED_DRAWS} (holdout_crps=False scores without it)")
-    pts = rb_spec = None
+    pts = rb_spec = mix_spec = None
     q_out = int(np.unique(_i64(mv_id)).size)
     if new_points is not None:
         pts = _points_inputs(new_points, np.asarray(X).shape[1], q_out, new_quantiles)
         rb_spec = _exceed_inputs(new_points, pts, q_out)
+        mix_spec = _mixture_inputs(new_points, pts, keep_all)
         if pts.crps and int(mcmc_keep) > MAX_STORED_DRAWS:
             raise ValueError(f"new_points: the CRPS keeps mcmc_keep = {int(mcmc_keep)} draws per point on the device, at most "
                              f"{MAX_STORED_DRAWS} (crps=False scores without it)")
@@ -628,7 +647,7 @@ def _check_request(y, X, mv_id, theta, limited_tree, mcmc_keep, sample_predicts,
         elif rank.get("thresholds_fun") is not None:
             raise ValueError("rank_diagnostics: thresholds_fun needs new_points")
     return SimpleNamespace(crit_cond=crit_cond, loo=loo, psis=psis, psis_draws=bool(psis_draws), crit=crit, M=M, keep_all=keep_all, seeds=seeds, theta0=theta0, rank=rank, exc=exc,
-                           diagnostics=diagnostics, max_lag=int(diagnostics_max_lag), y_hold=y_hold, want_crps=want_crps, pts=pts, exceed=rb_spec)
+                           diagnostics=diagnostics, max_lag=int(diagnostics_max_lag), y_hold=y_hold, want_crps=want_crps, pts=pts, exceed=rb_spec, mixture=mix_spec, more=None)
 
 
 def _row_parts(req, rq, n, q, mcmc_keep):
@@ -817,6 +836,24 @@ def _point_parts(lib, req, rq, rows, q, mcmc_keep, new_draws):
             req.exc = C.pointer(rows.xs)
         rows.xs.rb = C.pointer(rbs)
 
+    mix = rq.mixture
+    if mix is not None:       # the mixture predictive: travels beside the request (stm_fit_more)
+        mprobs, mcrps = mix
+        T = 0 if mprobs is None else mprobs.size
+
+        def mix_bufs(m, want=True):
+            want = want and T > 0
+            qv, unc = (np.zeros((T, m)), C.c_int64()) if want else (None, None)
+            return qv, unc, (_lib.StMixOut(_dp(qv), C.pointer(unc)) if want else _lib.StMixOut())
+        mx_w, mx_uw, mx_sw = mix_bufs(n_new)
+        mx_y, mx_uy, mx_sy = mix_bufs(n_new, has_X)
+        mx_f, mx_uf, mx_sf = mix_bufs(sets.get("fun", 0), fun is not None)
+        mx_crps, mx_spread = (np.zeros(n_new), np.zeros(n_new)) if mcrps else (None, None)
+        mx_n = C.c_int64()
+        mxs = _lib.StmMixture(_opt(mprobs), T, mx_sw, mx_sy, mx_sf, _opt(mx_crps), _opt(mx_spread), C.pointer(mx_n))
+        rq.more = _lib.StmFitMore(C.pointer(mxs))
+        rq.more_held = mxs
+
     def result():
         names, code = [], 1
         while lib.st_points_route_name(code) is not None:
@@ -844,6 +881,17 @@ def _point_parts(lib, req, rq, rows, q, mcmc_keep, new_draws):
             new["exceed"] = dict(thr=rthr, side=rside, w=rb_w, yhat=rb_y, n_accumulated=int(rb_acc.value))
             if rb_f is not None:
                 new["functionals"]["exceed"] = dict(thr=rthr_fun, side=rside, w=rb_f, n_accumulated=int(rb_acc.value))
+        if mix is not None and mcmc_keep > 0:
+            unc = lambda *u: sum(int(x.value) for x in u if x is not None)   # noqa: E731
+            if T > 0:
+                new["mixture"] = dict(probs=mprobs, w=mx_w, yhat=mx_y, n_stored=int(mx_n.value), n_unconverged=unc(mx_uw, mx_uy))
+                if mx_f is not None:
+                    new["functionals"]["mixture"] = dict(probs=mprobs, w=mx_f, n_stored=int(mx_n.value), n_unconverged=unc(mx_uf))
+            if mcrps:
+                new["scores"].update(crps_mixture=mx_crps, spread=mx_spread)
+                tot = new["scores"]["totals"]
+                for key, v in (("crps_mixture", mx_crps), ("spread", mx_spread)):
+                    tot[key], tot["by_outcome"][key] = _mix.point_means(v, ynew, pmv, q)
         for key, finish, by_set in summaries:
             for name, bufs in by_set.items() if n_new > 0 else ():
                 (new if name == "new" else new["functionals"])[key] = {k: finish(v) for k, v in bufs.items()}

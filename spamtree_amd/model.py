@@ -14,6 +14,7 @@ from . import _lib
 from . import diagnostics as _diag
 from . import exceed as _rb
 from . import excursions as _exc
+from . import mixture as _mix
 
 
 def _f64(a):
@@ -686,6 +687,7 @@ class SpamTreeMV:
         self.n_functionals = 0       # a new point set has none
         self.score_y = None          # ... and no scores
         self.exceed_spec = None      # ... and no exceedance thresholds
+        self.mixture_keep = 0        # ... and no mixture store
         self.points_mv = mv
 
     def unpack_joint(self, packed):
@@ -867,6 +869,72 @@ class SpamTreeMV:
         out = dict(thr=thr.copy(), side=sd.copy(), w=w, yhat=y, n_accumulated=int(cnt.value))
         if f is not None:
             out["functionals"] = dict(thr=thr_fun.copy(), w=f)
+        return out
+
+    # ---- quantiles and the exact CRPS of the mixture predictive at the point set (st_points_mixture_*; spamtree_amd.mixture)
+    def reserve_mixture(self, keep):
+        """Room for the per-draw moments of the first ``keep`` saved draws (at most 8192; 0 releases it): every accumulate_points then
+        also stores cond_mean, cond_var and, with X, x'beta + cond_mean and 1 / tausq_inv -- the components of the mixture predictive."""
+        keep = int(keep)
+        if keep < 0 or keep > _lib.ST_MIX_MAX_DRAWS:
+            raise ValueError(f"reserve_mixture: keep = {keep} must lie in 0 .. {_lib.ST_MIX_MAX_DRAWS}")
+        self._check(self.lib.st_points_mixture_reserve(self.h, keep))
+        self.mixture_keep = keep
+
+    def mixture_draws(self):
+        """The stored components in the caller's order: dict(m, v, mu (None without X), tau2, n_stored), the arrays n_stored x n_points
+        and tau2 n_stored x q."""
+        cnt = C.c_int64()
+        self._check(self.lib.st_points_mixture_draws(self.h, None, None, None, None, C.byref(cnt)))
+        K, n = int(cnt.value), self.n_points
+        out = dict(m=np.zeros((K, n)), v=np.zeros((K, n)), mu=np.zeros((K, n)) if self.points_have_X else None, tau2=np.zeros((K, self.q)))
+        self._check(self.lib.st_points_mixture_draws(self.h, _dp(out["m"]), _dp(out["v"]), _dp(out["mu"]) if out["mu"] is not None else None,
+                                                     _dp(out["tau2"]), C.byref(cnt)))
+        out["n_stored"] = K
+        return out
+
+    def mixture_quantiles(self, probs, functionals=None):
+        """Quantiles of the mixture predictive at up to 8 probabilities strictly inside (0, 1): dict(probs, w (T x n_points), yhat (the
+        same, None without X), n_unconverged); with functionals set (``functionals`` None: when there are any) also
+        ``functionals=dict(w (T x n_functionals), n_unconverged)``."""
+        p = _mix.check_probs(probs)
+        T, n = p.size, self.n_points
+        nf = getattr(self, "n_functionals", 0)
+        want_f = bool(nf) if functionals is None else bool(functionals)
+        if want_f and not nf:
+            raise ValueError("mixture_quantiles: functionals before set_functionals")
+
+        def bufs(m):
+            q, unc = np.zeros((T, m)), C.c_int64()
+            return q, unc, _lib.StMixOut(_dp(q), C.pointer(unc))
+        w, uw, sw = bufs(n)
+        y, uy, sy = bufs(n) if self.points_have_X else (None, None, None)
+        f, uf, sf = bufs(nf) if want_f else (None, None, None)
+        self._check(self.lib.st_points_mixture_quantiles(self.h, T, _dp(p), C.byref(sw), C.byref(sy) if sy is not None else None,
+                                                         C.byref(sf) if sf is not None else None))
+        out = dict(probs=p.copy(), w=w, yhat=y, n_unconverged=int(uw.value) + (int(uy.value) if uy is not None else 0))
+        if f is not None:
+            out["functionals"] = dict(w=f, n_unconverged=int(uf.value))
+        return out
+
+    def mixture_info(self):
+        """dict(keep, n_stored, store_bytes, n_solved, n_passes): the store's room, components and bytes on the device, and the
+        quantiles solved by the last mixture_quantiles with the evaluations of the CDF they took together."""
+        v = [C.c_int64() for _ in range(4)]
+        by = C.c_double()
+        self._check(self.lib.st_points_mixture_info(self.h, C.byref(v[0]), C.byref(v[1]), C.byref(by), C.byref(v[2]), C.byref(v[3])))
+        return dict(keep=v[0].value, n_stored=v[1].value, store_bytes=by.value, n_solved=v[2].value, n_passes=v[3].value)
+
+    def mixture_crps(self):
+        """The exact CRPS of the mixture predictive of yhat at every scored point (set_scores) and its sharpness term:
+        dict(crps, spread, n_scored), NaN where a point is not scored.  O(K^2) per scored point."""
+        if getattr(self, "score_y", None) is None:
+            raise ValueError("mixture_crps before set_scores")
+        n = self.n_points
+        out = dict(crps=np.zeros(n), spread=np.zeros(n))
+        ns = C.c_int64()
+        self._check(self.lib.st_points_mixture_crps(self.h, _dp(out["crps"]), _dp(out["spread"]), C.byref(ns)))
+        out["n_scored"] = int(ns.value)
         return out
 
     # ---- convergence diagnostics of the stored draws (st_*_diagnostics; spamtree_amd.diagnostics has the definition)

@@ -18,6 +18,7 @@ from typing import Optional
 import numpy as np
 
 from . import exceed as _rb
+from . import mixture as _mix
 from . import excursions as _exc
 from . import fit
 from .model import SpamTreeMV, _dp, _f64, functionals_csr, joint_labels, score_values
@@ -108,7 +109,7 @@ def conditioning_set(topo: Topology, anchor: int) -> np.ndarray:
 
 def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, return_draws=True, device=0, z=None,
                 mode=0, force_generic=False, return_moments=False, joint=None, functionals=None, y_new=None, quantiles=(),
-                crps=True, diagnostics=False, diagnostics_max_lag=0, excursions=None, rank_diagnostics=None, exceed=None):
+                crps=True, diagnostics=False, diagnostics_max_lag=0, excursions=None, rank_diagnostics=None, exceed=None, mixture=None):
     """Predictive at new locations for every saved draw of a chain.
 
     ``model_inputs``: the problem as ``spamtree_mv_mcmc`` took it (the dict of ``synthetic.make_workload``; its ``topo``
@@ -157,6 +158,10 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
     mean over the saved draws of each draw's exact conditional probability, formed on the device as the replay goes through
     ``st_points_accumulate`` (``z`` None, ``mode`` 0); no draw is kept for it.  The result then holds ``exceed``: dict(thr, side,
     w=dict(prob, prob_var), yhat=the same or None, n_accumulated) and, with ``thresholds_fun``, ``functionals["exceed"]``.
+    ``mixture=dict(probs=, crps=True)``: quantiles and the exact CRPS of the mixture predictive (``spamtree_amd.mixture``) from the
+    per-draw moments the replay stores on the device as it goes through ``st_points_accumulate`` (``z`` None, ``mode`` 0; at most
+    8192 saved draws).  The result then holds ``mixture``: dict(probs, w, yhat or None, n_stored, n_unconverged), with functionals
+    ``functionals["mixture"]``, and with ``y_new`` and ``crps=True`` ``scores["crps_mixture"]`` and ``scores["spread"]``.
     """
     mi = model_inputs
     topo = mi["topo"]
@@ -201,6 +206,14 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
             rb = _rb.check_spec(exceed, int(np.unique(np.asarray(mi["mv_id"])).size), None if fun is None else fun[0].size - 1)
         except TypeError as e:
             raise ValueError(f"exceed: {e}") from None
+    mix = None
+    if mixture is not None:
+        if z is not None or mode != 0:
+            raise ValueError("mixture needs the device draw: z=None and mode=0")
+        try:
+            mix = _mix.check_spec(mixture, X_new is not None, ys is not None, len(draws["w_mcmc"]), ys)
+        except TypeError as e:
+            raise ValueError(f"mixture: {e}") from None
     rank = None
     if rank_diagnostics is not None and rank_diagnostics is not False:   # fit.spamtree_mv_mcmc's argument, for the points
         from . import diagnostics as _diag
@@ -251,6 +264,8 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
             m._check(m.lib.st_points_summary_reserve(m.h, keep))
         if rb is not None:
             m.set_exceed(list(rb[0]), rb[1], None if rb[2] is None else list(rb[2]))
+        if mix is not None:
+            m.reserve_mixture(keep)
         cc = []
         w_out = np.zeros((n_new, keep)) if return_draws else None
         y_out = np.zeros((n_new, keep)) if (return_draws and X_new is not None) else None
@@ -264,7 +279,7 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
             m.theta_update(0, theta[:, s])
             if not m.get_loglik_comps_w(0):
                 raise FloatingPointError(f"st_factor failed on saved draw {s} (errtype {m.last_errtype})")
-            if fun is None and ys is None and not diagnostics and exc is None and rank is None and rb is None:
+            if fun is None and ys is None and not diagnostics and exc is None and rank is None and rb is None and mix is None:
                 out = m.predict_points(mode=mode, z=None if z is None else z[:, s], seed=seed, it=s)
             else:
                 out = m.accumulate_points(seed=seed, it=s)
@@ -305,6 +320,19 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
             res["exceed"] = ex
             if fex is not None:
                 res["functionals"]["exceed"] = dict(fex, side=ex["side"], n_accumulated=ex["n_accumulated"])
+        if mix is not None and keep:
+            if mix[0] is not None:
+                mq = m.mixture_quantiles(mix[0])
+                fmq = mq.pop("functionals", None)
+                res["mixture"] = dict(mq, n_stored=keep)
+                if fmq is not None:
+                    res["functionals"]["mixture"] = dict(fmq, probs=mq["probs"], n_stored=keep)
+            if mix[1]:
+                mc = m.mixture_crps()
+                res["scores"].update(crps_mixture=mc["crps"], spread=mc["spread"])
+                tot = res["scores"]["totals"]
+                for key, v in (("crps_mixture", mc["crps"]), ("spread", mc["spread"])):
+                    tot[key], tot["by_outcome"][key] = _mix.point_means(v, ys, mv_new, q)
         if diagnostics and n_new:
             res["diagnostics"] = m.points_diagnostics(int(diagnostics_max_lag), n_kept=keep)
             if fun is not None:
@@ -337,7 +365,7 @@ def predict_new(model_inputs, draws, coords_new, mv_new, X_new=None, seed=2021, 
 
 def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), return_draws=True, joint=None, functionals=None,
                 y_new=None, crps=True, diagnostics=False, diagnostics_max_lag=0, excursions=None, rank_diagnostics=None, chains=1,
-                chain_seeds=None, chain_theta=None, exceed=None, **mcmc):
+                chain_seeds=None, chain_theta=None, exceed=None, mixture=None, **mcmc):
     """Fit the chain and predict at new locations on every saved iteration, without replaying it.
 
     ``model_inputs``: the problem as for :func:`predict_new`.  The points are located with :func:`locate` and handed to
@@ -364,6 +392,9 @@ def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), retu
     With ``exceed=dict(thresholds=, side=, thresholds_fun=)`` also ``new["exceed"]`` and ``new["functionals"]["exceed"]``: the
     Rao-Blackwellised exceedance probabilities of ``fit.spamtree_mv_mcmc(new_points=dict(exceed=))`` -- with ``return_draws=False``
     an exceedance map of any number of points with nothing of size n_new x mcmc_keep anywhere.
+    With ``mixture=dict(probs=, crps=True)`` also ``new["mixture"]``, ``new["functionals"]["mixture"]`` and, with ``y_new``,
+    ``new["scores"]["crps_mixture"]`` and ``["spread"]``: the quantiles and the exact CRPS of the mixture predictive of
+    ``fit.spamtree_mv_mcmc(new_points=dict(mixture=))`` (at most 8192 saved draws over all chains).
     With ``chains`` > 1 (``chain_seeds``, ``chain_theta``: as ``fit.spamtree_mv_mcmc``) that many chains run one after another: every
     per-draw array holds ``chains * mcmc_keep`` columns, chain after chain (``chain_id``), the summaries are those of the pooled
     draws and the diagnostics the multi-chain ones.  :func:`predict_new` takes the concatenated result as it takes one chain's.
@@ -387,6 +418,11 @@ def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), retu
             _rb.check_spec(exceed, int(np.unique(np.asarray(mi["mv_id"])).size), None if fun is None else fun[0].size - 1)
         except TypeError as e:
             raise ValueError(f"exceed: {e}") from None
+    if mixture is not None:   # likewise
+        try:
+            _mix.check_spec(mixture, X_new is not None, ys is not None, int(chains) * int(mcmc.get("mcmc_keep", 100)), ys)
+        except TypeError as e:
+            raise ValueError(f"mixture: {e}") from None
     anchor = locate(mi["topo"], coords_new, mv_new, device=mcmc.get("device", 0), joint=joint)
     points = dict(coords=coords_new, mv=mv_new, anchor=anchor, X=X_new)
     if joint is not None:
@@ -398,6 +434,8 @@ def fit_predict(model_inputs, coords_new, mv_new, X_new=None, quantiles=(), retu
         points["crps"] = bool(crps)
     if exceed is not None:
         points["exceed"] = exceed
+    if mixture is not None:
+        points["mixture"] = mixture
     theta = np.asarray(mcmc.pop("theta", mi["theta"]), dtype=np.float64)
     kw = dict(set_unif_bounds_in=mi["bounds"], start_w=np.zeros((int(mi["n"]), 1)), theta=theta, beta=np.zeros(int(mi["p"])),
               tausq=0.1, mcmcsd=0.01 * np.eye(theta.size))
