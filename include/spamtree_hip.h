@@ -478,7 +478,7 @@ int st_points_functionals_chain_rank_diagnostics(st_handle h, int32_t n_chains, 
  * with k = K(S, x*), v = Linv_S k, mean = v' Linv_S w_S, var = max(K(x*, x*) - v'v, 0), draw = mean + sqrt(var) z,
  * yhat = x' beta_j + draw + sqrt(tausq_j) e.  Not for limited_tree or world > 1 handles (ST_ERR_UNSUPPORTED).
  * st_points_set: coords n_new x 2 column-major, mv 1-based, anchor 0-based block ids with observed rows, X n_new x p column-major
- *   or NULL (then no yhat).  Replaces the previous point set.
+ *   or NULL (then no yhat).  Replaces the previous point set.  A point set of size 0 has no X, whatever is passed.
  * st_points_predict: on slot 0 (refused before st_factor(0, ...)) and the current w / beta / tausq_inv.  mode 0 = draw, 1 =
  *   conditional mean only (w_new = cond_mean, no noise in yhat).  z: n_new normals in the caller's order, or NULL = Philox stream 6,
  *   counter (i, i >> 32, iter, 6), i = index in the caller's order; yhat noise: stream 7, same counter.  Any output may be NULL.
@@ -495,7 +495,9 @@ const char *st_points_route_name(int32_t code);
 /* ---- predictive summaries of the point set over saved iterations, kept on the device (the st_summary_* of the new points).
  * st_points_accumulate: st_points_predict's draw (mode 0, Philox streams 6 / 7 with counter `iter`) into device buffers, then one
  *   element-wise update per point, in call order: Welford mean and M2 of the conditional mean, running sums of the conditional
- *   variance, of w* and of yhat* (with X).  With a reservation it also stores w* and yhat* as row n_accumulated of [keep][n_new].
+ *   variance, of w* and of yhat* (with X).  With a reservation it also stores w* and yhat* as the next row of [keep][n_new] while
+ *   fewer than `keep` are stored: the store holds the first `keep` draws since the latest of st_points_set, st_points_summary_reset
+ *   and st_points_summary_reserve (its row count starts again there; n_accumulated runs on over a reservation).
  *   Outputs (caller order, n_new each) may be NULL: then nothing is copied to the host and nothing is synchronised.  Changes no
  *   state of the handle but the point set's.
  * st_points_summary_reset: zero the summaries and the stored draws (st_points_set starts a new set with none of either).
@@ -503,6 +505,7 @@ const char *st_points_route_name(int32_t code);
  *   the stored draws.
  * st_points_summary_get: mean = mean of the conditional means; var = mean of the conditional variances + population variance of the
  *   conditional means (st_points_predict's Rao-Blackwellised moments); w_mean, yhat_mean = means of the draws.  Any may be NULL.
+ *   ST_ERR_USAGE before the first accumulated iteration (n_accumulated is still written), as st_points_summary_get_cov.
  * st_points_summary_quantile: k_qtile over the stored draws (the rule and limit of st_summary_quantile); ST_ERR_USAGE without a
  *   stored draw or q outside [0, 1].
  * All refuse limited_tree and world > 1 handles (ST_ERR_UNSUPPORTED) and need st_points_set (ST_ERR_USAGE). */
@@ -558,7 +561,8 @@ int st_points_summary_get_cov(st_handle h, double *cov);
  * With functionals set, st_points_accumulate(_joint) also forms per functional F_w = a'w*, F_m = a'cond_mean, F_y = a'yhat (with X)
  *   and F_v = Var(a'w* | w, theta) (a plain set: from the clamped cond_var; a joint set: from the packed Sigma, the sum clamped at
  *   0) and updates the Welford mean and M2 of F_m, the running sums of F_v, F_w, F_y and, within st_points_summary_reserve's room,
- *   the stored draws F_w, F_y.  st_points_summary_reserve / _reset size and clear these along with their own.  (A point set of
+ *   the stored draws F_w, F_y, with a row count of their own: the first `keep` draws since the latest of st_points_functionals_set,
+ *   st_points_summary_reserve and _reset.  st_points_summary_reserve / _reset size and clear these along with their own.  (A point set of
  *   size 0 reserves nothing, as for its points: its functionals, all 0, store no draw and have no quantile.)  The summation order
  *   is fixed (spamtree_amd/csrc/points_fun.hpp): a functional's values depend on its own terms only, bit for bit.
  * st_points_functionals_last: the four values of the last accumulated iteration.
@@ -644,7 +648,8 @@ int st_points_exceed_get(st_handle h, const st_rb_out *w, const st_rb_out *yhat,
  *   16 B without X), tau2 per outcome, F_m and F_v per functional.  keep > ST_MIX_MAX_DRAWS: ST_ERR_UNSUPPORTED (one series' pairs of
  *   doubles must fit one workgroup's LDS).  keep = 0 releases the store.  Replaces a previous store.  st_points_set(_joint) drops
  *   the store, st_points_summary_reset clears its count, st_points_functionals_set drops (and, when functionals are given,
- *   re-reserves empty) the functional part only.
+ *   re-reserves empty) the functional part only.  A functional column is written only on an iteration that writes a point column:
+ *   functionals set when the point columns are full get none, and st_points_mixture_quantiles' fun_w then has no stored draw.
  * With a store, st_points_accumulate(_joint) also writes one column after its exceedance step, on the same stream, while fewer
  *   than `keep` are stored: it consumes no draw of any stream and writes nothing another step reads, so every other output is the
  *   same bit for bit; with NULL outputs it still copies nothing and synchronises nothing.  Without a store nothing is launched
